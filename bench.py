@@ -2,7 +2,7 @@
 """
 bench.py — atom-steps/s of the hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (pair geometry -> G2/G4 descriptors ->
 per-atom MLP -> energy -> analytic forces + virial) over this rank's resident
@@ -25,7 +25,10 @@ batch energy per step. `config5` in the same line: BASELINE.json configs[4],
 region (about 100 ms of work: the GPU is at its working clocks when the short
 single-frame region starts; W warm-up and K timed steps as asked for, both).
 
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line. `ms_per_step` in it is the headline region's elapsed time over K.
+`--dump-outputs DIR`: rank 0 also writes what its last timed step computed (energy, forces, virial,
+atomic energies) as DIR/<name>.npy, float64, at most 64 MB; the inputs are seeded, so two builds run
+with the same arguments can be compared array for array.
 """
 import argparse
 import hashlib
@@ -49,6 +52,7 @@ FP64_PEAK_TFLOPS = 78.6
 FLOP_PER_TRIPLE = 150.0  # forward + backward of one contributing triple
 E_TOL, F_TOL = 1e-6, 1e-5  # north_star parity tolerances (eV, eV/A)
 CONFIG5_FRAMES_PER_GPU = 64
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
 
 
 def host_cores():
@@ -257,9 +261,13 @@ def main():
     ap.add_argument("--no-config5", action="store_true")
     ap.add_argument("--no-extra-configs", action="store_true")
     ap.add_argument("--cpu-evals", type=int, default=40)  # ~10 s of 16-thread CPU work
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's batch) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return spawn_ranks(args)
 
@@ -576,6 +584,7 @@ def main():
         extra = None
         if world == 1 and fpg == 1 and args.rep == 10 and not args.no_extra_configs:
             extra = extra_config_rows(max(10, min(args.steps, 50)), host_cores())
+        dumped = dump_outputs(args.dump_outputs, res) if args.dump_outputs else None
         out = {
             "metric": "atom-steps/sec (energy+forces), 4000-atom Ni rcut=6.5 A",
             "value": value, "unit": "atom-steps/s", "n_gpus": world, "steps": args.steps,
@@ -600,6 +609,7 @@ def main():
             "extra_configs": extra,
             "set_frames": nl_info,
             "source_stamp": stamp,
+            "dump_outputs": dumped,
         }
         if world > 1 and config5 is not None:
             out["note"] = (f"N = {world}: read `config5` first — {config5['value']:.4g} atom-steps/s at "
@@ -614,6 +624,32 @@ def main():
     if out is not None:
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     os.close(real_stdout)
+
+
+def dump_outputs(dirname, res):
+    """`--dump-outputs DIR`: the arrays the last timed step handed back (energy per frame, forces,
+    virial per frame, atomic energies) as DIR/<name>.npy in float64, so that two builds can be
+    compared output for output on identical inputs. Above DUMP_MAX_BYTES in all, the per-atom arrays
+    keep the same fixed, seeded sample of atoms (sorted indices, RandomState(0)); the per-frame
+    arrays are always complete."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in res.items()}
+    n_atoms = len(arrays["forces"]) if "forces" in arrays else len(arrays.get("atomic", ()))
+    per_atom = [k for k in ("forces", "atomic") if k in arrays]
+    total = sum(a.nbytes for a in arrays.values())
+    sampled = None
+    if total > DUMP_MAX_BYTES and n_atoms:
+        atom_bytes = sum(arrays[k].nbytes for k in per_atom) / n_atoms
+        fixed = total - atom_bytes * n_atoms
+        keep = int(max(1, (DUMP_MAX_BYTES - fixed) // atom_bytes))
+        idx = np.sort(np.random.RandomState(0).choice(n_atoms, keep, replace=False))
+        for k in per_atom:
+            arrays[k] = np.ascontiguousarray(arrays[k][idx])
+        sampled = {"atoms_kept": keep, "atoms_total": n_atoms, "seed": 0}
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    return {"dir": dirname, "files": {k + ".npy": list(a.shape) for k, a in arrays.items()},
+            "dtype": "float64", "bytes": sum(a.nbytes for a in arrays.values()), "atom_sample": sampled}
 
 
 def extra_config_rows(steps, cores):
