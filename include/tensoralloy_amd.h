@@ -51,7 +51,8 @@ enum {
                                     this batch (only the MLP weights changed: training steps) */
 };
 
-enum { TA_MODEL_SF_MLP = 1, TA_MODEL_EAM_ALLOY = 2, TA_MODEL_EAM_ADP = 3, TA_MODEL_GRAP_MLP = 4 };
+enum { TA_MODEL_SF_MLP = 1, TA_MODEL_EAM_ALLOY = 2, TA_MODEL_EAM_ADP = 3, TA_MODEL_GRAP_MLP = 4,
+       TA_MODEL_EAM_FS = 5 /* eam/fs (Finnis-Sinclair, nn/eam/fs.py): inference only, see n_eam_nets */ };
 enum { TA_CUTOFF_COSINE = 0, TA_CUTOFF_POLYNOMIAL = 1 }; /* nn/cutoff.py:20-85 */
 
 /* activation ids follow `actfn_map` of atomic.py:323 for 0..3 */
@@ -123,7 +124,13 @@ typedef struct {
    * the number of function slots, 2 n_elements + n_pairs (ADP: + 2 n_pairs), in the order
    * rho[element], embed[element], phi[pair a <= b], dipole[pair], quadrupole[pair]; `n_layers`
    * [slot] (0 = analytic function, read from `eam_params`), `layer_sizes` ([1, h1, ..., 1] per
-   * nn slot) and `weights` (as above, per nn slot) describe them, `activation` applies to all. */
+   * nn slot) and `weights` (as above, per nn slot) describe them, `activation` applies to all.
+   * TA_MODEL_EAM_FS (nn/eam/fs.py): n_elements^2 + n_elements + n_pairs slots in the order
+   * rho[centre][neighbour] (centre-major over the sorted elements: rho_AB = density at an A centre
+   * from a B neighbour), embed[element], phi[pair a <= b]. Every slot is an nn function or
+   * tabulated (n_eam_nets is never 0; `eam_params` is read for nothing but must have its usual
+   * size). eam/fs models are inference only: ta_energy_gradient, ta_loss_gradient,
+   * ta_constant_gradient and ta_hessian_vectors return TA_ERR_INVALID for them. */
   int32_t n_eam_nets;
 
   /* EAM / ADP tabulated functions: a LAMMPS setfl / adp file's rho(r), F(rho), phi(r), u(r), w(r)
@@ -187,7 +194,7 @@ int ta_device_count(void);
  * sizeof(ta_model_desc) as the library was compiled: a binding checks both before the first real
  * call, so that a stale or foreign build of the library is refused instead of misreading a struct.
  * (The reference has no counterpart: its "ABI" is the frozen graph's `Metadata/api`, basic.py:43.) */
-#define TA_ABI_VERSION 4
+#define TA_ABI_VERSION 5
 int ta_abi_version(void);
 int ta_model_desc_size(void);
 
@@ -392,8 +399,9 @@ int ta_set_nn_tables(ta_handle h, int on);
  * `EamAlloyNN.export_to_setfl` (nn/eam/alloy.py:198-381) evaluates through a TF session before it
  * writes a LAMMPS setfl file. Rows: elements (sorted) for rho(r) [n_elements][n_r] and F(rho)
  * [n_elements][n_rho]; element pairs a <= b (upper triangle, row-major) for phi(r), and for an
- * ADP model u(r), w(r) (may be NULL), each [n_pairs][n_r]. Evaluated by the same device functions
- * the energy kernels use. */
+ * ADP model u(r), w(r) (may be NULL), each [n_pairs][n_r]. For an eam/fs model `rho_of_r` is
+ * [n_elements^2][n_r], rows rho[centre][neighbour] in the slot order of `n_eam_nets`. Evaluated by
+ * the same device functions the energy kernels use. */
 int ta_eam_tabulate(ta_handle h, int32_t n_r, const double *r, int32_t n_rho, const double *rho,
                     double *rho_of_r, double *phi_of_r, double *embed_of_rho, double *u_of_r,
                     double *w_of_r);

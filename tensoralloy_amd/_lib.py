@@ -27,12 +27,12 @@ TA_OK = 0
 TA_ERR_INVALID, TA_ERR_UNSUPPORTED, TA_ERR_HIP, TA_ERR_NOMEM = -1, -2, -3, -4
 TA_WANT_ENERGY, TA_WANT_FORCES, TA_WANT_VIRIAL, TA_WANT_ATOMIC, TA_WANT_DESCRIPTORS = 1, 2, 4, 8, 16
 TA_WANT_REUSE_DESCRIPTORS = 32
-TA_MODEL_SF_MLP, TA_MODEL_EAM_ALLOY, TA_MODEL_EAM_ADP, TA_MODEL_GRAP_MLP = 1, 2, 3, 4
+TA_MODEL_SF_MLP, TA_MODEL_EAM_ALLOY, TA_MODEL_EAM_ADP, TA_MODEL_GRAP_MLP, TA_MODEL_EAM_FS = 1, 2, 3, 4, 5
 TA_CUTOFF = {"cosine": 0, "polynomial": 1}
 TA_ACT = {"relu": 0, "softplus": 1, "tanh": 2, "squareplus": 3, "leaky_relu": 4,
           "sigmoid": 5, "softsign": 6, "elu": 7}
 TA_N_KERNEL_SLOTS = 10
-TA_ABI_VERSION = 4  # include/tensoralloy_amd.h: TA_ABI_VERSION
+TA_ABI_VERSION = 5  # include/tensoralloy_amd.h: TA_ABI_VERSION
 KERNEL_SLOTS = ["pair_geometry", "g4_forward", "descriptor_reduce", "mlp", "backward",
                 "force_gather", "frame_reduce", "eam", "neighbor_update", "grap_forward"]
 

@@ -9,7 +9,9 @@ caller's atom order exactly as the reference does (calculator.py:217-249).
 
 Differences (documented in INTEGRATION.md):
   * `graph_model_path` names a `<name>.json` + `<name>.npz` pair written by
-    `AtomicNN.export` / `EamAlloyNN.export`, the reference's native `.npz`, or a frozen
+    `AtomicNN.export` / `EamAlloyNN.export` / `AdpNN.export` / `EamFsNN.export` (eam/fs: energy,
+    forces and stress from the kernels; `hessian` / `elastic` by differences of the forces), the
+    reference's native `.npz`, or a frozen
     TensorFlow GraphDef `.pb` of the reference itself: its constants are read without
     TensorFlow (`tensoralloy_amd/graphdef.py`; Zjw04-family EAM graphs and symmetry-function
     `AtomicNN` graphs; anything else raises `ValueError`).

@@ -305,6 +305,12 @@ int fail(ta_context *h, int code, const std::string &msg) {
   return code;
 }
 
+// eam/fs models evaluate energies, forces and virials only
+std::string fs_inference_only(const char *fn) {
+  return std::string(fn) + ": not available for eam/fs models (inference only: no weight, constant or loss "
+         "gradients and no analytic Hessian-vector products; differences of the forces give the latter)";
+}
+
 template <typename T>
 T *upload(ta_context *h, const std::vector<T> &v) {
   T *d = nullptr;
@@ -985,7 +991,7 @@ int ta_create(const ta_model_desc *model, int device, ta_handle *out) {
       h->sf.eps = model->eps > 0.0 ? model->eps : 1e-14;
       h->sf.ndim = ta::grap_ndim(h->grap);
       build_mlp(h, model, h->sf.ndim);
-    } else if (model->kind == TA_MODEL_EAM_ALLOY || model->kind == TA_MODEL_EAM_ADP) {
+    } else if (model->kind == TA_MODEL_EAM_ALLOY || model->kind == TA_MODEL_EAM_ADP || model->kind == TA_MODEL_EAM_FS) {
       std::string err;
       h->eam = ta::eam_create(model, err);
       if (!h->eam) throw std::invalid_argument(err);
@@ -1068,7 +1074,7 @@ void ensure_job_lists(ta_context *h, size_t n_blk) {
 bool filter_applies(const ta_context *h) {
   if (!(h->skin > 0.0) || h->hp.n_atoms == 0 || std::getenv("TA_NO_LIST_FILTER")) return false;
   if (h->kind == TA_MODEL_SF_MLP) return h->use_v2;
-  if (h->kind == TA_MODEL_EAM_ALLOY) return ta::eam_is_plain(h->eam);
+  if (h->kind == TA_MODEL_EAM_ALLOY || h->kind == TA_MODEL_EAM_FS) return ta::eam_is_plain(h->eam);
   return false;
 }
 
@@ -1779,6 +1785,7 @@ int ta_update_weights(ta_handle h, const double *weights, int64_t n_weights) {
 
 int ta_energy_gradient(ta_handle h, const double *frame_coeff, double *grad, int64_t n_grad) {
   if (!h || !frame_coeff || !grad) return TA_ERR_INVALID;
+  if (h->kind == TA_MODEL_EAM_FS) return fail(h, TA_ERR_INVALID, fs_inference_only("ta_energy_gradient"));
   if (!h->have_batch) return fail(h, TA_ERR_INVALID, "no resident batch");
   if (h->eam)
     return guarded(h, [&]() {
@@ -1896,6 +1903,7 @@ void ensure_pair_jacobians(ta_context *h) {
 int ta_loss_gradient(ta_handle h, const double *frame_coeff, const double *dR, const double *dh, double *grad,
                      int64_t n_grad, double *dG_out) {
   if (!h || !grad) return TA_ERR_INVALID;
+  if (h->kind == TA_MODEL_EAM_FS) return fail(h, TA_ERR_INVALID, fs_inference_only("ta_loss_gradient"));
   if (!h->have_batch) return fail(h, TA_ERR_INVALID, "no resident batch");
   if (!dR && !dh) {
     if (!frame_coeff) return fail(h, TA_ERR_INVALID, "nothing to differentiate");
@@ -2020,6 +2028,7 @@ int ta_update_constants(ta_handle h, const double *constants, int64_t n_constant
 int ta_constant_gradient(ta_handle h, const double *frame_coeff, const double *dR, const double *dh, double *grad,
                          int64_t n_grad) {
   if (!h || !grad) return TA_ERR_INVALID;
+  if (h->kind == TA_MODEL_EAM_FS) return fail(h, TA_ERR_INVALID, fs_inference_only("ta_constant_gradient"));
   if (!h->have_batch) return fail(h, TA_ERR_INVALID, "no resident batch");
   if (!h->eam) return fail(h, TA_ERR_INVALID, "the model has no empirical potential");
   if (!frame_coeff && !dR && !dh) return fail(h, TA_ERR_INVALID, "nothing to differentiate");
@@ -2103,6 +2112,7 @@ void ta_free(void *p) { std::free(p); }
 int ta_hessian_vectors(ta_handle h, int32_t n_dir, int32_t first, const double *dR, const double *dh, double *dF,
                        double *dW) {
   if (!h || !dF || n_dir < 0) return TA_ERR_INVALID;
+  if (h->kind == TA_MODEL_EAM_FS) return fail(h, TA_ERR_INVALID, fs_inference_only("ta_hessian_vectors"));
   if (!h->have_batch) return fail(h, TA_ERR_INVALID, "no resident batch");
   const bool grap_model = h->kind == TA_MODEL_GRAP_MLP;
   const bool sf_model = h->kind == TA_MODEL_SF_MLP || grap_model;  // the descriptor + MLP models
@@ -2268,20 +2278,21 @@ int ta_eam_tabulate(ta_handle h, int32_t n_r, const double *r, int32_t n_rho, co
                     double *rho_of_r, double *phi_of_r, double *embed_of_rho, double *u_of_r,
                     double *w_of_r) {
   if (!h) return TA_ERR_INVALID;
-  if (h->kind != TA_MODEL_EAM_ALLOY && h->kind != TA_MODEL_EAM_ADP)
+  if (h->kind != TA_MODEL_EAM_ALLOY && h->kind != TA_MODEL_EAM_ADP && h->kind != TA_MODEL_EAM_FS)
     return fail(h, TA_ERR_INVALID, "ta_eam_tabulate needs an EAM / ADP model");
   if (n_r < 0 || n_rho < 0 || (n_r > 0 && (!r || !rho_of_r || !phi_of_r)) ||
       (n_rho > 0 && (!rho || !embed_of_rho)))
     return fail(h, TA_ERR_INVALID, "bad table arguments");
   return guarded(h, [&]() {
     const size_t nel = (size_t)h->n_elements, npair = nel * (nel + 1) / 2;
+    const size_t nrho = h->kind == TA_MODEL_EAM_FS ? nel * nel : nel;  // eam/fs: rho[centre][neighbour]
     const bool adp = h->kind == TA_MODEL_EAM_ADP && u_of_r && w_of_r;
     DevBuf<double> buf;
     const size_t n_in = (size_t)n_r + (size_t)n_rho;
-    const size_t n_out = (nel + npair * (adp ? 3 : 1)) * (size_t)n_r + nel * (size_t)n_rho;
+    const size_t n_out = (nrho + npair * (adp ? 3 : 1)) * (size_t)n_r + nel * (size_t)n_rho;
     buf.ensure(n_in + n_out + 8);
     double *d_r = buf.ptr, *d_rho = d_r + n_r;
-    double *d_rho_r = d_rho + n_rho, *d_phi = d_rho_r + nel * n_r, *d_embed = d_phi + npair * n_r;
+    double *d_rho_r = d_rho + n_rho, *d_phi = d_rho_r + nrho * n_r, *d_embed = d_phi + npair * n_r;
     double *d_u = adp ? d_embed + nel * n_rho : nullptr, *d_w = adp ? d_u + npair * n_r : nullptr;
     hipStream_t s = h->stream;
     if (n_r) HIP_CHECK(hipMemcpyAsync(d_r, r, (size_t)n_r * sizeof(double), hipMemcpyHostToDevice, s));
@@ -2291,7 +2302,7 @@ int ta_eam_tabulate(ta_handle h, int32_t n_r, const double *r, int32_t n_rho, co
     auto back = [&](double *dst, const double *src, size_t n) {
       if (dst && n) HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, s));
     };
-    back(rho_of_r, d_rho_r, nel * n_r);
+    back(rho_of_r, d_rho_r, nrho * n_r);
     back(phi_of_r, d_phi, npair * n_r);
     back(embed_of_rho, d_embed, nel * n_rho);
     if (adp) {

@@ -126,11 +126,22 @@ __device__ __forceinline__ int pair_type(int s1, int s2, int nel) {
 }
 
 // slot order of the function networks / tables: rho[element], embed[element], phi[pair type],
-// dipole[pair type], quadrupole[pair type]
-__host__ __device__ __forceinline__ int slot_rho(int e) { return e; }
-__host__ __device__ __forceinline__ int slot_embed(int nel, int e) { return nel + e; }
+// dipole[pair type], quadrupole[pair type]. eam/fs (FS = true): rho[centre][neighbour] (nel^2 slots,
+// centre-major), embed[element], phi[pair type]. A density function is picked by its KEY: the
+// neighbour's species (alloy, alloy.py:176), or centre * nel + neighbour (fs.py `_build_rho_nn`);
+// the key is also its bit in the nn_rho / tab_rho masks.
+template <bool FS = false>
+__host__ __device__ __forceinline__ int n_rho_slots(int nel) { return FS ? nel * nel : nel; }
+template <bool FS = false>
+__host__ __device__ __forceinline__ int rho_key(int nel, int centre, int neighbour) {
+  return FS ? centre * nel + neighbour : neighbour;
+}
+__host__ __device__ __forceinline__ int slot_rho(int key) { return key; }
+template <bool FS = false>
+__host__ __device__ __forceinline__ int slot_embed(int nel, int e) { return n_rho_slots<FS>(nel) + e; }
+template <bool FS = false>
 __host__ __device__ __forceinline__ int slot_pair(int nel, int cls /* 1 phi, 2 u, 3 w */, int pt) {
-  return 2 * nel + (cls - 1) * (nel * (nel + 1) / 2) + pt;
+  return n_rho_slots<FS>(nel) + nel + (cls - 1) * (nel * (nel + 1) / 2) + pt;
 }
 
 // The analytic functions are templates over the scalar type of the CONSTANTS: double for inference,
@@ -410,7 +421,8 @@ __device__ __forceinline__ void mishin_polar_r(T r, double p1, double p2, double
 // W lanes per atom (16: one DPP row, four atoms per wavefront; 64: one wavefront per atom): an atom
 // with n neighbours occupies ceil(n / W) W lane slots, so narrow groups waste fewer lanes (n = 90: 96
 // slots against 128) while wide ones put more wavefronts in flight for a single small frame.
-template <bool OTHER, int W>
+// FS: eam/fs densities rho_{centre species, neighbour species}; every function is nn or tabulated.
+template <bool OTHER, int W, bool FS = false>
 __global__ __launch_bounds__(kBlock) void eam_atom_kernel(EamParams P, DeviceBatch b, double *dF,
                                                           double *mom, double eps,
                                                           const double *__restrict__ pf, size_t ps,
@@ -427,12 +439,13 @@ __global__ __launch_bounds__(kBlock) void eam_atom_kernel(EamParams P, DeviceBat
     double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     const int pt = pair_type(sA, sb, nel);
     const double *pp = P.pair[pt];
-    const bool rho_nn = (P.nn_rho >> sb) & 1u, phi_nn = (P.nn_phi >> pt) & 1u;
+    const int rk = rho_key<FS>(nel, sA, sb);  // fixed per segment
+    const bool rho_nn = (P.nn_rho >> rk) & 1u, phi_nn = (P.nn_phi >> pt) & 1u;
     const bool u_nn = (P.nn_u >> pt) & 1u, w_nn = (P.nn_w >> pt) & 1u;
-    const bool rho_tab = (P.tab_rho >> sb) & 1u, phi_tab = (P.tab_phi >> pt) & 1u;
+    const bool rho_tab = (P.tab_rho >> rk) & 1u, phi_tab = (P.tab_phi >> pt) & 1u;
     const bool u_tab = (P.tab_u >> pt) & 1u, w_tab = (P.tab_w >> pt) & 1u;
     // like pairs of a Zjw04 element: rho and phi share an exponential and a quotient
-    const bool fused_aa = !OTHER && sb == sA && !rho_nn && !rho_tab && !phi_nn && !phi_tab;
+    const bool fused_aa = !FS && !OTHER && sb == sA && !rho_nn && !rho_tab && !phi_nn && !phi_tab;
     // The pair loop is a chain of dependent loads (pair_j -> position of j) in front of ~300
     // instructions, and a group makes several passes: the neighbour index and shift of the pass after
     // next and the neighbour position of the next pass are fetched before this pass is evaluated.
@@ -502,12 +515,12 @@ __global__ __launch_bounds__(kBlock) void eam_atom_kernel(EamParams P, DeviceBat
       if (fused_aa) {
         zjw_rho_phi_aa<double>(P.el[sb], r, f, df, fp, dfp);
       } else {
-        // density function of the NEIGHBOUR's element (alloy.py:176)
+        // density function of the NEIGHBOUR's element (alloy.py:176); eam/fs: of the ordered pair
         if (rho_nn) f = pf[PF_RHO * ps + q];
-        else if (rho_tab) spline_eval(tabs[slot_rho(sb)], r, f, df);
+        else if (FS || rho_tab) spline_eval(tabs[slot_rho(rk)], r, f, df);
         else el_rho<OTHER, double>(P, P.el, sb, r, f, df);
         if (phi_nn) fp = pf[PF_PHI * ps + q];
-        else if (phi_tab) spline_eval(tabs[slot_pair(nel, 1, pt)], r, fp, dfp);
+        else if (FS || phi_tab) spline_eval(tabs[slot_pair<FS>(nel, 1, pt)], r, fp, dfp);
         else pair_phi<OTHER, double>(P, P.el, P.phi, sA, sb, r, fp, dfp);
       }
       rho += f;
@@ -563,7 +576,7 @@ __global__ __launch_bounds__(kBlock) void eam_atom_kernel(EamParams P, DeviceBat
       b.eatom[i] = 0.5 * phis + eadp;
     } else {
       double F, d;
-      if ((P.tab_embed >> sA) & 1u) spline_eval(tabs[slot_embed(nel, sA)], rho, F, d);
+      if (FS || ((P.tab_embed >> sA) & 1u)) spline_eval(tabs[slot_embed<FS>(nel, sA)], rho, F, d);
       else el_embed<OTHER, double>(P, P.el, sA, rho, F, d);
       b.eatom[i] = F + 0.5 * phis + eadp;  // eam.py:353-355, :568
       dF[i] = d;
@@ -606,6 +619,12 @@ struct NnFnList {
   int8_t cls[3 * kMaxPairTypes + kMaxEamElements];
   int8_t k[3 * kMaxPairTypes + kMaxEamElements];
 };
+// eam/fs: nel^2 density functions (one mask bit each) and the phi pair types
+static_assert(kMaxEamElements * kMaxEamElements <= 32, "the eam/fs rho masks are uint32_t");
+static_assert(kMaxEamElements * kMaxEamElements + kMaxPairTypes <= 3 * kMaxPairTypes + kMaxEamElements,
+              "NnFnList holds every eam/fs pair function");
+static_assert(sizeof(EamParams) + sizeof(DeviceBatch) + 256 <= 4096,
+              "EamParams + DeviceBatch (+ the other kernel arguments) fit the 4 KB kernarg segment");
 
 // Fast path for the usual shape 1 -> H1 -> H2 -> 1 (Defaults.hidden_sizes = [64, 32]): one
 // wavefront evaluates f and f' for 16 pairs without leaving its registers.
@@ -615,7 +634,7 @@ struct NnFnList {
 //     read from the workgroup's LDS copy of W2; row stride = 16 mod 32 doubles: conflict-free);
 //   layer 3 has N = 1: h2 . w3 is a 16-lane DPP row sum of the accumulator columns.
 // The four wavefronts of a workgroup share one function's weights in LDS and stride over tiles.
-template <int ACT, int NT>
+template <int ACT, int NT, bool FS = false>
 __global__ __launch_bounds__(kBlock) void eam_nn_pair_fast_kernel(EamParams P, const MlpDev *__restrict__ nets,
                                                                   int act_rt, NnFnList fl, DeviceBatch b,
                                                                   const double *__restrict__ rbuf,
@@ -624,7 +643,7 @@ __global__ __launch_bounds__(kBlock) void eam_nn_pair_fast_kernel(EamParams P, c
   const int act = ACT >= 0 ? ACT : act_rt;
   const int cls = fl.cls[blockIdx.y], k = fl.k[blockIdx.y];
   const int nel = P.nel;
-  const MlpDev &net = nets[cls == 0 ? slot_rho(k) : slot_pair(nel, cls, k)];
+  const MlpDev &net = nets[cls == 0 ? slot_rho(k) : slot_pair<FS>(nel, cls, k)];
   const int H1 = net.layer[0].np, H2 = 16 * NT;
   const int s2 = (H2 % 32 == 0) ? H2 + 16 : H2;
   double *w1 = lds, *b1 = w1 + H1, *W2 = b1 + H1, *b2 = W2 + (size_t)H1 * s2, *w3 = b2 + H2;
@@ -653,7 +672,8 @@ __global__ __launch_bounds__(kBlock) void eam_nn_pair_fast_kernel(EamParams P, c
     double r = 0.0;
     if (valid) {
       const int sb = b.species[b.pair_j[p]];
-      const int key = cls == 0 ? sb : pair_type(b.species[b.pair_i[p]], sb, nel);
+      const int key = cls == 0 ? (FS ? rho_key<FS>(nel, b.species[b.pair_i[p]], sb) : sb)
+                               : pair_type(b.species[b.pair_i[p]], sb, nel);
       match = key == k;
       r = rbuf[p];
     }
@@ -719,7 +739,7 @@ __global__ __launch_bounds__(kBlock) void eam_nn_pair_fast_kernel(EamParams P, c
 
 // One hidden layer, 1 -> H1 -> 1: no GEMM at all. One lane per pair, the weights are LDS broadcasts,
 // four independent activation chains per trip.
-template <int ACT>
+template <int ACT, bool FS = false>
 __global__ __launch_bounds__(kBlock) void eam_nn_pair_1h_kernel(EamParams P, const MlpDev *__restrict__ nets,
                                                                 int act_rt, NnFnList fl, DeviceBatch b,
                                                                 const double *__restrict__ rbuf, double *pf,
@@ -728,7 +748,7 @@ __global__ __launch_bounds__(kBlock) void eam_nn_pair_1h_kernel(EamParams P, con
   const int act = ACT >= 0 ? ACT : act_rt;
   const int cls = fl.cls[blockIdx.y], k = fl.k[blockIdx.y];
   const int nel = P.nel;
-  const MlpDev &net = nets[cls == 0 ? slot_rho(k) : slot_pair(nel, cls, k)];
+  const MlpDev &net = nets[cls == 0 ? slot_rho(k) : slot_pair<FS>(nel, cls, k)];
   const int H1 = net.layer[0].np;  // multiple of 16; padded units have zero output weight
   double *w1 = lds, *b1 = w1 + H1, *w2 = b1 + H1;
   for (int idx = threadIdx.x; idx < H1; idx += kBlock) {
@@ -741,7 +761,8 @@ __global__ __launch_bounds__(kBlock) void eam_nn_pair_1h_kernel(EamParams P, con
   double *val = pf + (size_t)(2 * cls) * ps, *der = pf + (size_t)(2 * cls + 1) * ps;
   for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < b.n_pairs; p += (int64_t)gridDim.x * kBlock) {
     const int sb = b.species[b.pair_j[p]];
-    const int key = cls == 0 ? sb : pair_type(b.species[b.pair_i[p]], sb, nel);
+    const int key = cls == 0 ? (FS ? rho_key<FS>(nel, b.species[b.pair_i[p]], sb) : sb)
+                             : pair_type(b.species[b.pair_i[p]], sb, nel);
     if (key != k) continue;
     const double r = rbuf[p];
     double fv = b2, fd = 0.0;
@@ -760,7 +781,7 @@ __global__ __launch_bounds__(kBlock) void eam_nn_pair_1h_kernel(EamParams P, con
   }
 }
 
-template <int THREADS>
+template <int THREADS, bool FS = false>
 __global__ __launch_bounds__(THREADS) void eam_nn_pair_kernel(EamParams P, const MlpDev *__restrict__ nets,
                                                               int act, DeviceBatch b,
                                                               const double *__restrict__ rbuf, double *pf,
@@ -781,6 +802,7 @@ __global__ __launch_bounds__(THREADS) void eam_nn_pair_kernel(EamParams P, const
       r = rbuf[q];
       sb = b.species[b.pair_j[q]];
       pt = pair_type(b.species[b.pair_i[q]], sb, nel);
+      if (FS) sb = rho_key<FS>(nel, b.species[b.pair_i[q]], sb);  // eam/fs: the ordered pair
     }
     xr[tid] = r;
     key_sb[tid] = sb;
@@ -792,7 +814,7 @@ __global__ __launch_bounds__(THREADS) void eam_nn_pair_kernel(EamParams P, const
     const uint32_t nn = cls == 0 ? P.nn_rho : cls == 1 ? P.nn_phi : cls == 2 ? P.nn_u : P.nn_w;
     if (!nn) continue;
     const int *key = cls == 0 ? key_sb : key_pt;
-    const int nk = cls == 0 ? nel : npt;
+    const int nk = cls == 0 ? n_rho_slots<FS>(nel) : npt;
     for (int k = 0; k < nk; ++k) {
       if (!((nn >> k) & 1u)) continue;
       bool need = false;  // the same for every thread: read from LDS
@@ -800,7 +822,7 @@ __global__ __launch_bounds__(THREADS) void eam_nn_pair_kernel(EamParams P, const
       if (!need) continue;
       if (tid < kMlpRows) buf0[tid * stride] = xr[tid];
       __syncthreads();
-      const MlpDev &net = nets[cls == 0 ? slot_rho(k) : slot_pair(nel, cls, k)];
+      const MlpDev &net = nets[cls == 0 ? slot_rho(k) : slot_pair<FS>(nel, cls, k)];
       double *val = pf + (size_t)(2 * cls) * ps + p0, *der = pf + (size_t)(2 * cls + 1) * ps + p0;
       mlp_tile<16>(
           net, act, 1, nrows, buf0, buf1, stride, da,
@@ -816,7 +838,7 @@ struct EmbedTiles {
   int nel;
 };
 
-template <int THREADS>
+template <int THREADS, bool FS = false>
 __global__ __launch_bounds__(THREADS) void eam_nn_embed_kernel(const MlpDev *__restrict__ nets, EmbedTiles t,
                                                                int act, DeviceBatch b,
                                                                const double *__restrict__ rho_buf,
@@ -833,12 +855,12 @@ __global__ __launch_bounds__(THREADS) void eam_nn_embed_kernel(const MlpDev *__r
     buf0[threadIdx.x * stride] = (int)threadIdx.x < nrows ? rho_buf[atoms[a0 + threadIdx.x]] : 0.0;
   __syncthreads();
   mlp_tile<16>(
-      nets[slot_embed(t.nel, e)], act, 1, nrows, buf0, buf1, stride, da,
+      nets[slot_embed<FS>(t.nel, e)], act, 1, nrows, buf0, buf1, stride, da,
       [&](int row, double y) { b.eatom[atoms[a0 + row]] += y; },  // eam.py:568: y = phi + embed
       [&](int row, int, double d) { dF[atoms[a0 + row]] = d; });
 }
 
-template <bool OTHER>
+template <bool OTHER, bool FS = false>
 __global__ __launch_bounds__(kBlock) void eam_pair_kernel(EamParams P, DeviceBatch b,
                                                           const double *dF, const double *mom,
                                                           const double *__restrict__ pf, size_t ps,
@@ -861,11 +883,13 @@ __global__ __launch_bounds__(kBlock) void eam_pair_kernel(EamParams P, DeviceBat
   const double inv_r = 1.0 / r;  // the writer's 1 / sqrt(r^2)
   double f, drho, dphi;
   const int pt = pair_type(sA, sa, nel);
-  if ((P.nn_rho >> sa) & 1u) drho = pf[PF_DRHO * ps + p];
-  else if ((P.tab_rho >> sa) & 1u) spline_eval(tabs[slot_rho(sa)], r, f, drho);
+  // eam/fs: rho'_{sA sa} of this directed pair; the reverse pair carries F'(rho_j) rho'_{sa sA}
+  const int rk = rho_key<FS>(nel, sA, sa);
+  if ((P.nn_rho >> rk) & 1u) drho = pf[PF_DRHO * ps + p];
+  else if (FS || ((P.tab_rho >> rk) & 1u)) spline_eval(tabs[slot_rho(rk)], r, f, drho);
   else el_rho<OTHER, double>(P, P.el, sa, r, f, drho);
   if ((P.nn_phi >> pt) & 1u) dphi = pf[PF_DPHI * ps + p];
-  else if ((P.tab_phi >> pt) & 1u) spline_eval(tabs[slot_pair(nel, 1, pt)], r, f, dphi);
+  else if (FS || ((P.tab_phi >> pt) & 1u)) spline_eval(tabs[slot_pair<FS>(nel, 1, pt)], r, f, dphi);
   else pair_phi<OTHER, double>(P, P.el, P.phi, sA, sa, r, f, dphi);
   // dE/dD of the directed pair: the centre's terms only; the reverse pair carries the other half
   double c = (dF[i] * drho + 0.5 * dphi) * inv_r;
@@ -950,7 +974,9 @@ __device__ __forceinline__ void pair_vector(const PairFetch &f, int from_pos, co
   }
 }
 
-template <bool OTHER, int W>
+// FS: eam/fs, g[p] - g[rev p] = (F'(rho_i) rho'_{sA sb}(r) + F'(rho_j) rho'_{sb sA}(r) + phi'(r)) D / r;
+// both density slots are fixed per neighbour-species segment.
+template <bool OTHER, int W, bool FS = false>
 __global__ __launch_bounds__(16 * W) void eam_force_kernel(EamParams P, DeviceBatch b, const double *dF,
                                                            const TabDev *__restrict__ tabs, int from_pos,
                                                            double eps) {
@@ -968,7 +994,8 @@ __global__ __launch_bounds__(16 * W) void eam_force_kernel(EamParams P, DeviceBa
     const double ri[3] = {b.pos[3 * (size_t)i], b.pos[3 * (size_t)i + 1], b.pos[3 * (size_t)i + 2]};
     for (int sb = 0; sb < nel; ++sb) {
       const int pt = pair_type(sA, sb, nel);
-      const bool rhoB_tab = (P.tab_rho >> sb) & 1u, phi_tab = (P.tab_phi >> pt) & 1u;
+      const int kB = rho_key<FS>(nel, sA, sb), kA = rho_key<FS>(nel, sb, sA);
+      const bool rhoB_tab = (P.tab_rho >> kB) & 1u, phi_tab = (P.tab_phi >> pt) & 1u;
       // as in eam_atom_kernel: the geometry and F'(rho_j) of the next pass and the neighbour index of the
       // pass after next are fetched before this pass is evaluated
       const int q1 = seg[sb + 1];
@@ -997,16 +1024,16 @@ __global__ __launch_bounds__(16 * W) void eam_force_kernel(EamParams P, DeviceBa
         if (P.list_rc2 > 0.0 && !(v1.y < P.list_rc2)) continue;  // beyond rc: not a neighbour
         const double r = sqrt(v1.y);
         double fn, drhoB, drhoA, dphi;
-        if (!OTHER && sb == sA && !rhoB_tab && !phi_tab) {
+        if (!FS && !OTHER && sb == sA && !rhoB_tab && !phi_tab) {
           zjw_rho_phi_aa<double>(P.el[sb], r, fn, drhoB, fn, dphi);
           drhoA = drhoB;
         } else {
-          if (rhoB_tab) spline_eval(tabs[slot_rho(sb)], r, fn, drhoB);
+          if (FS || rhoB_tab) spline_eval(tabs[slot_rho(kB)], r, fn, drhoB);
           else el_rho<OTHER, double>(P, P.el, sb, r, fn, drhoB);
           if (sb == sA) drhoA = drhoB;
-          else if (rhoA_tab) spline_eval(tabs[slot_rho(sA)], r, fn, drhoA);
+          else if (FS || rhoA_tab) spline_eval(tabs[slot_rho(kA)], r, fn, drhoA);
           else el_rho<OTHER, double>(P, P.el, sA, r, fn, drhoA);
-          if (phi_tab) spline_eval(tabs[slot_pair(nel, 1, pt)], r, fn, dphi);
+          if (FS || phi_tab) spline_eval(tabs[slot_pair<FS>(nel, 1, pt)], r, fn, dphi);
           else pair_phi<OTHER, double>(P, P.el, P.phi, sA, sb, r, fn, dphi);
         }
         const double inv_r = 1.0 / r;
@@ -1161,34 +1188,38 @@ __global__ __launch_bounds__(16 * W) void adp_force_kernel(EamParams P, DeviceBa
 
 // Tables of the analytic functions on caller-supplied abscissae (setfl / ADP export,
 // reference nn/eam/alloy.py:198-381): rows = elements (rho(r), F(rho)) or element pairs a <= b
-// (phi, u, w), evaluated by the same device functions the energy kernels use.
+// (phi, u, w), evaluated by the same device functions the energy kernels use. eam/fs (FS): the rho
+// rows are the nel^2 ordered pairs, centre-major; rows of nn functions are written by the caller.
+template <bool FS>
 __global__ __launch_bounds__(kBlock) void eam_tabulate_kernel(EamParams P, int n_r, const double *r,
                                                               int n_rho, const double *rho,
                                                               double *rho_of_r, double *phi_of_r,
                                                               double *embed_of_rho, double *u_of_r,
                                                               double *w_of_r,
                                                               const TabDev *__restrict__ tabs) {
-  const int nel = P.nel, npair = nel * (nel + 1) / 2;
-  const int64_t n_rows_r = nel + npair;  // rho rows, then pair rows
+  const int nel = P.nel, npair = nel * (nel + 1) / 2, nrho = n_rho_slots<FS>(nel);
+  const int64_t n_rows_r = nrho + npair;  // rho rows, then pair rows
   const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const int64_t total_r = n_rows_r * n_r;
   if (idx < total_r) {
     const int row = (int)(idx / n_r), k = (int)(idx % n_r);
     const double x = r[k];
     double f, df;
-    if (row < nel) {
+    if (row < nrho) {
       if ((P.tab_rho >> row) & 1u) spline_eval(tabs[slot_rho(row)], x, f, df);
+      else if (FS) f = 0.0;
       else el_rho<true, double>(P, P.el, row, x, f, df);
       rho_of_r[(size_t)row * n_r + k] = f;
     } else {
-      const int pt = row - nel;
+      const int pt = row - nrho;
       int a = 0, rem = pt;
       while (rem >= nel - a) {
         rem -= nel - a;
         ++a;
       }
       const int b2 = a + rem;
-      if ((P.tab_phi >> pt) & 1u) spline_eval(tabs[slot_pair(nel, 1, pt)], x, f, df);
+      if ((P.tab_phi >> pt) & 1u) spline_eval(tabs[slot_pair<FS>(nel, 1, pt)], x, f, df);
+      else if (FS) f = 0.0;
       else pair_phi<true, double>(P, P.el, P.phi, a, b2, x, f, df);
       phi_of_r[(size_t)pt * n_r + k] = f;
       if (P.adp && u_of_r && w_of_r) {
@@ -1208,7 +1239,8 @@ __global__ __launch_bounds__(kBlock) void eam_tabulate_kernel(EamParams P, int n
   if (j < (int64_t)nel * n_rho) {
     const int row = (int)(j / n_rho), k = (int)(j % n_rho);
     double F, dF;
-    if ((P.tab_embed >> row) & 1u) spline_eval(tabs[slot_embed(nel, row)], rho[k], F, dF);
+    if ((P.tab_embed >> row) & 1u) spline_eval(tabs[slot_embed<FS>(nel, row)], rho[k], F, dF);
+    else if (FS) F = 0.0;
     else el_embed<true, double>(P, P.el, row, rho[k], F, dF);
     embed_of_rho[(size_t)row * n_rho + k] = F;
   }
@@ -1711,6 +1743,7 @@ struct EamModel {
   std::vector<double *> owned;    // device allocations of the weights
   int stride = 0, max_layers = 0; // LDS row stride / deepest network
   bool pair_nets = false, embed_nets = false;
+  bool fs = false;                // eam/fs: nel^2 density slots (rho_key), no analytic functions
   double *pf = nullptr;           // [8 or 4][cap_pairs] value / derivative columns, then r [cap_pairs]
   size_t cap_pairs = 0;
   TabDev *tabs_dev = nullptr;     // [n_slots] tabulated functions (n == 0: none)
@@ -1745,6 +1778,13 @@ T *eam_upload(EamModel *e, const std::vector<T> &v) {
 }
 
 int round16(int x) { return (x + 15) / 16 * 16; }
+
+// slots of a model: eam/alloy and ADP, or eam/fs
+int m_n_rho(const EamModel *m) { return m->fs ? n_rho_slots<true>(m->p.nel) : n_rho_slots(m->p.nel); }
+int m_slot_embed(const EamModel *m, int e) { return m->fs ? slot_embed<true>(m->p.nel, e) : slot_embed(m->p.nel, e); }
+int m_slot_pair(const EamModel *m, int cls, int pt) {
+  return m->fs ? slot_pair<true>(m->p.nel, cls, pt) : slot_pair(m->p.nel, cls, pt);
+}
 
 // function networks of the model description -> padded device copies, both orientations
 // (same layout as the per-element MLPs, ta_api.hip build_mlp)
@@ -1811,6 +1851,7 @@ void eam_set_nn_tables(EamModel *m, bool on);
 EamModel *eam_create(const ta_model_desc *m, std::string &err) {
   const int nel = m->n_elements;
   const bool adp = m->kind == TA_MODEL_EAM_ADP;
+  const bool fs = m->kind == TA_MODEL_EAM_FS;
   const int npair = nel * (nel + 1) / 2;
   // per element 20 constants + embed kind + potential kind; per pair phi kind + 7 constants; ADP: + 8 per pair
   const int need = nel * 22 + npair * 8 + (adp ? npair * 8 : 0);
@@ -1826,9 +1867,15 @@ EamModel *eam_create(const ta_model_desc *m, std::string &err) {
     err = "EAM/ADP models support at most 5 elements";
     return nullptr;
   }
-  const int n_slots = 2 * nel + npair * (adp ? 3 : 1);
+  const int n_rho = fs ? nel * nel : nel;
+  const int n_slots = n_rho + nel + npair * (adp ? 3 : 1);
   if (m->n_eam_nets != 0 && m->n_eam_nets != n_slots) {
     err = "n_eam_nets must be 0 or " + std::to_string(n_slots) + " for this model";
+    return nullptr;
+  }
+  if (fs && m->n_eam_nets == 0) {
+    err = "eam/fs models have no analytic functions: n_eam_nets must be " + std::to_string(n_slots) +
+          " (rho[centre][neighbour], embed[element], phi[pair]), every slot an nn function or tabulated";
     return nullptr;
   }
   const bool have_tables = m->eam_table_n || m->eam_table_dx || m->eam_table_coef;
@@ -1841,6 +1888,7 @@ EamModel *eam_create(const ta_model_desc *m, std::string &err) {
   e->rcut = m->rcut;
   e->p.nel = nel;
   e->p.adp = adp ? 1 : 0;
+  e->fs = fs;
   e->eps = m->eps > 0.0 ? m->eps : 1e-14;
   if (have_tables) {
     try {
@@ -1864,12 +1912,12 @@ EamModel *eam_create(const ta_model_desc *m, std::string &err) {
       }
       e->tabs_dev = eam_upload(e, tabs);
       e->tabs_host = tabs;
-      for (int k = 0; k < nel; ++k) {
+      for (int k = 0; k < n_rho; ++k)
         if (tabs[slot_rho(k)].n) e->p.tab_rho |= 1u << k;
-        if (tabs[slot_embed(nel, k)].n) e->p.tab_embed |= 1u << k;
-      }
+      for (int k = 0; k < nel; ++k)
+        if (tabs[m_slot_embed(e, k)].n) e->p.tab_embed |= 1u << k;
       for (int k = 0; k < npair; ++k) {
-        if (tabs[slot_pair(nel, 1, k)].n) e->p.tab_phi |= 1u << k;
+        if (tabs[m_slot_pair(e, 1, k)].n) e->p.tab_phi |= 1u << k;
         if (adp && tabs[slot_pair(nel, 2, k)].n) e->p.tab_u |= 1u << k;
         if (adp && tabs[slot_pair(nel, 3, k)].n) e->p.tab_w |= 1u << k;
       }
@@ -1887,12 +1935,12 @@ EamModel *eam_create(const ta_model_desc *m, std::string &err) {
       eam_destroy(e);
       return nullptr;
     }
-    for (int k = 0; k < nel; ++k) {
+    for (int k = 0; k < n_rho; ++k)
       if (e->nets[slot_rho(k)].n_layers) e->p.nn_rho |= 1u << k;
-      if (e->nets[slot_embed(nel, k)].n_layers) e->p.nn_embed |= 1u << k;
-    }
+    for (int k = 0; k < nel; ++k)
+      if (e->nets[m_slot_embed(e, k)].n_layers) e->p.nn_embed |= 1u << k;
     for (int k = 0; k < npair; ++k) {
-      if (e->nets[slot_pair(nel, 1, k)].n_layers) e->p.nn_phi |= 1u << k;
+      if (e->nets[m_slot_pair(e, 1, k)].n_layers) e->p.nn_phi |= 1u << k;
       if (adp && e->nets[slot_pair(nel, 2, k)].n_layers) e->p.nn_u |= 1u << k;
       if (adp && e->nets[slot_pair(nel, 3, k)].n_layers) e->p.nn_w |= 1u << k;
     }
@@ -1905,7 +1953,7 @@ EamModel *eam_create(const ta_model_desc *m, std::string &err) {
     int h2 = 0;
     size_t lds = 0, lds_1h = 0;
     auto add = [&](int cls, int k) {
-      const MlpDev &n = e->nets[cls == 0 ? slot_rho(k) : slot_pair(nel, cls, k)];
+      const MlpDev &n = e->nets[cls == 0 ? slot_rho(k) : m_slot_pair(e, cls, k)];
       if (!n.n_layers) return;
       e->fns.cls[e->fns.n] = (int8_t)cls;
       e->fns.k[e->fns.n] = (int8_t)k;
@@ -1920,7 +1968,7 @@ EamModel *eam_create(const ta_model_desc *m, std::string &err) {
       const int H1 = n.layer[0].np, s2 = (h2 % 32 == 0) ? h2 + 16 : h2;
       lds = std::max(lds, (size_t)(2 * H1 + (size_t)H1 * s2 + 2 * h2 + 2) * sizeof(double));
     };
-    for (int k = 0; k < nel; ++k) add(0, k);
+    for (int k = 0; k < n_rho; ++k) add(0, k);
     for (int cls = 1; cls < (adp ? 4 : 2); ++cls)
       for (int k = 0; k < npair; ++k) add(cls, k);
     if (fast && e->fns.n && lds <= 64 * 1024 && !getenv("TA_EAM_NN_GENERIC")) {
@@ -1965,6 +2013,16 @@ EamModel *eam_create(const ta_model_desc *m, std::string &err) {
       err = "r_eq, rho_e and rho_s must be positive";
       return nullptr;
     }
+  if (fs) {
+    const uint32_t all_rho = (uint32_t)((1ull << n_rho) - 1), all_el = (1u << nel) - 1, all_pt = (1u << npair) - 1;
+    if (((e->p.nn_rho | e->p.tab_rho) & all_rho) != all_rho || ((e->p.nn_embed | e->p.tab_embed) & all_el) != all_el ||
+        ((e->p.nn_phi | e->p.tab_phi) & all_pt) != all_pt) {
+      eam_destroy(e);
+      err = "eam/fs models have no analytic functions: every rho, embed and phi slot must be an nn function or "
+            "tabulated";
+      return nullptr;
+    }
+  }
   e->p_exact = e->p;
   e->pair_nets_exact = e->pair_nets;
   if (e->pair_nets) {
@@ -2006,9 +2064,9 @@ static void eam_build_nn_tables(EamModel *m) {
                        dx, m->knot_fv, m->nn_coef[slot]);
     m->tabs_host[slot] = TabDev{n, dx, 1.0 / dx, m->nn_coef[slot]};
   };
-  for (int e = 0; e < nel; ++e) build(slot_rho(e));
+  for (int k = 0; k < m_n_rho(m); ++k) build(slot_rho(k));
   for (int cls = 1; cls < (m->p.adp ? 4 : 2); ++cls)
-    for (int pt = 0; pt < npair; ++pt) build(slot_pair(nel, cls, pt));
+    for (int pt = 0; pt < npair; ++pt) build(m_slot_pair(m, cls, pt));
   if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess)
     throw std::runtime_error("tabulating the nn functions failed");
   if (!m->tabs_dev) {
@@ -2103,12 +2161,12 @@ void eam_ensure(EamModel *m, const DeviceBatch &b) {
 void eam_tabulate(EamModel *m, int n_r, const double *r, int n_rho, const double *rho, double *rho_of_r,
                   double *phi_of_r, double *embed_of_rho, double *u_of_r, double *w_of_r,
                   hipStream_t s) {
-  const int nel = m->p.nel, npair = nel * (nel + 1) / 2;
-  const int64_t total = (int64_t)(nel + npair) * n_r + (int64_t)nel * n_rho;
+  const int nel = m->p.nel, npair = nel * (nel + 1) / 2, nrho = m_n_rho(m);
+  const int64_t total = (int64_t)(nrho + npair) * n_r + (int64_t)nel * n_rho;
   if (total == 0) return;
-  hipLaunchKernelGGL(eam_tabulate_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock),
-                     0, s, m->p, n_r, r, n_rho, rho, rho_of_r, phi_of_r, embed_of_rho, u_of_r, w_of_r,
-                     m->tabs_dev);
+  hipLaunchKernelGGL((m->fs ? eam_tabulate_kernel<true> : eam_tabulate_kernel<false>),
+                     dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, m->p, n_r, r, n_rho, rho,
+                     rho_of_r, phi_of_r, embed_of_rho, u_of_r, w_of_r, m->tabs_dev);
   if (!m->n_slots) return;
   // rows of nn functions: one launch per function over the same abscissae
   const size_t lds = net_lds_bytes(m);
@@ -2117,12 +2175,10 @@ void eam_tabulate(EamModel *m, int n_r, const double *r, int n_rho, const double
     hipLaunchKernelGGL(eam_nn_table_kernel<kNetThreads>, dim3((unsigned)((n + kMlpRows - 1) / kMlpRows)),
                        dim3(kNetThreads), lds, s, m->nets_dev, slot, m->activation, x, n, out, m->stride);
   };
-  for (int e = 0; e < nel; ++e) {
-    table(slot_rho(e), r, n_r, rho_of_r + (size_t)e * n_r);
-    table(slot_embed(nel, e), rho, n_rho, embed_of_rho + (size_t)e * n_rho);
-  }
+  for (int k = 0; k < nrho; ++k) table(slot_rho(k), r, n_r, rho_of_r + (size_t)k * n_r);
+  for (int e = 0; e < nel; ++e) table(m_slot_embed(m, e), rho, n_rho, embed_of_rho + (size_t)e * n_rho);
   for (int pt = 0; pt < npair; ++pt) {
-    table(slot_pair(nel, 1, pt), r, n_r, phi_of_r + (size_t)pt * n_r);
+    table(m_slot_pair(m, 1, pt), r, n_r, phi_of_r + (size_t)pt * n_r);
     if (m->p.adp && u_of_r && w_of_r) {
       table(slot_pair(nel, 2, pt), r, n_r, u_of_r + (size_t)pt * n_r);
       table(slot_pair(nel, 3, pt), r, n_r, w_of_r + (size_t)pt * n_r);
@@ -2827,6 +2883,7 @@ void eam_compute(EamModel *m, const DeviceBatch &b, uint32_t want, hipStream_t s
   sf.eps = m->eps;
   const size_t ps = m->cap_pairs;
   const bool pair_nets = m->pair_nets && b.n_pairs > 0;
+  const bool fs = m->fs;  // eam/fs instantiations (FS = true) of the same kernels
   if (pair_nets) {
     double *rbuf = m->pf + (size_t)(m->p.adp ? 8 : 4) * ps;
     hipLaunchKernelGGL(eam_geom_kernel, dim3((unsigned)((b.n_pairs + kBlock - 1) / kBlock)), dim3(kBlock), 0,
@@ -2837,8 +2894,8 @@ void eam_compute(EamModel *m, const DeviceBatch &b, uint32_t want, hipStream_t s
       // times over, few enough that the LDS image of the weights is amortised
       const dim3 grid(std::min((tiles + 3) / 4, 2048u), (unsigned)m->fns.n);
 #define TA_NN_FAST(ACT, NT)                                                                              \
-  hipLaunchKernelGGL((eam_nn_pair_fast_kernel<ACT, NT>), grid, dim3(kBlock), m->fast_lds, s, m->p,        \
-                     m->nets_dev, m->activation, m->fns, b, rbuf, m->pf, ps)
+  hipLaunchKernelGGL((fs ? eam_nn_pair_fast_kernel<ACT, NT, true> : eam_nn_pair_fast_kernel<ACT, NT>), grid, \
+                     dim3(kBlock), m->fast_lds, s, m->p, m->nets_dev, m->activation, m->fns, b, rbuf, m->pf, ps)
 #define TA_NN_FAST_NT(ACT)                                                                               \
   switch (m->fast_nt) {                                                                                  \
     case 1: TA_NN_FAST(ACT, 1); break;                                                                   \
@@ -2856,14 +2913,16 @@ void eam_compute(EamModel *m, const DeviceBatch &b, uint32_t want, hipStream_t s
     } else if (m->fast_1h) {
       const dim3 grid(std::min((unsigned)((b.n_pairs + kBlock - 1) / kBlock), 4096u), (unsigned)m->fns.n);
       if (m->activation == TA_ACT_SOFTPLUS)
-        hipLaunchKernelGGL(eam_nn_pair_1h_kernel<TA_ACT_SOFTPLUS>, grid, dim3(kBlock), m->fast_lds, s, m->p,
-                           m->nets_dev, m->activation, m->fns, b, rbuf, m->pf, ps);
+        hipLaunchKernelGGL((fs ? eam_nn_pair_1h_kernel<TA_ACT_SOFTPLUS, true> : eam_nn_pair_1h_kernel<TA_ACT_SOFTPLUS>),
+                           grid, dim3(kBlock), m->fast_lds, s, m->p, m->nets_dev, m->activation, m->fns, b, rbuf,
+                           m->pf, ps);
       else
-        hipLaunchKernelGGL(eam_nn_pair_1h_kernel<-1>, grid, dim3(kBlock), m->fast_lds, s, m->p, m->nets_dev,
-                           m->activation, m->fns, b, rbuf, m->pf, ps);
+        hipLaunchKernelGGL((fs ? eam_nn_pair_1h_kernel<-1, true> : eam_nn_pair_1h_kernel<-1>), grid, dim3(kBlock),
+                           m->fast_lds, s, m->p, m->nets_dev, m->activation, m->fns, b, rbuf, m->pf, ps);
     } else {
-      hipLaunchKernelGGL(eam_nn_pair_kernel<kNetThreads>, dim3(tiles), dim3(kNetThreads), net_lds_bytes(m), s,
-                         m->p, m->nets_dev, m->activation, b, rbuf, m->pf, ps, m->stride);
+      hipLaunchKernelGGL((fs ? eam_nn_pair_kernel<kNetThreads, true> : eam_nn_pair_kernel<kNetThreads>), dim3(tiles),
+                         dim3(kNetThreads), net_lds_bytes(m), s, m->p, m->nets_dev, m->activation, b, rbuf, m->pf,
+                         ps, m->stride);
     }
   }
   bool other = false;
@@ -2885,19 +2944,23 @@ void eam_compute(EamModel *m, const DeviceBatch &b, uint32_t want, hipStream_t s
   const int W = w_env == 16 || w_env == 32 || w_env == 64 ? w_env
                 : (!m->p.adp || b.n_atoms >= 32768) ? 16 : 32;
   const dim3 agrid((unsigned)((b.n_atoms * W + kBlock - 1) / kBlock));
-#define TA_EAM_ATOM(O, WW)                                                                                   \
-  hipLaunchKernelGGL((eam_atom_kernel<O, WW>), agrid, dim3(kBlock), 0, s, m->p, b, m->dF, m->mom, m->eps,    \
+#define TA_EAM_ATOM(O, WW, F)                                                                               \
+  hipLaunchKernelGGL((eam_atom_kernel<O, WW, F>), agrid, dim3(kBlock), 0, s, m->p, b, m->dF, m->mom, m->eps, \
                      m->pf, ps, m->rho_buf, pair_nets ? 1 : (no_rec ? 2 : 0), m->tabs_dev)
 #define TA_EAM_BY_W(MACRO)                            \
   do {                                                \
-    if (other) {                                      \
-      if (W == 16) MACRO(true, 16);                   \
-      else if (W == 32) MACRO(true, 32);              \
-      else MACRO(true, 64);                           \
+    if (fs) {                                         \
+      if (W == 16) MACRO(false, 16, true);            \
+      else if (W == 32) MACRO(false, 32, true);       \
+      else MACRO(false, 64, true);                    \
+    } else if (other) {                               \
+      if (W == 16) MACRO(true, 16, false);            \
+      else if (W == 32) MACRO(true, 32, false);       \
+      else MACRO(true, 64, false);                    \
     } else {                                          \
-      if (W == 16) MACRO(false, 16);                  \
-      else if (W == 32) MACRO(false, 32);             \
-      else MACRO(false, 64);                          \
+      if (W == 16) MACRO(false, 16, false);           \
+      else if (W == 32) MACRO(false, 32, false);      \
+      else MACRO(false, 64, false);                   \
     }                                                 \
   } while (0)
   TA_EAM_BY_W(TA_EAM_ATOM);
@@ -2915,17 +2978,18 @@ void eam_compute(EamModel *m, const DeviceBatch &b, uint32_t want, hipStream_t s
     t.tile_start[t.nel] = blocks;
     t.elem_start[t.nel] = b.elem_start[t.nel];
     if (blocks)
-      hipLaunchKernelGGL(eam_nn_embed_kernel<kNetThreads>, dim3((unsigned)blocks), dim3(kNetThreads),
-                         net_lds_bytes(m), s, m->nets_dev, t, m->activation, b, m->rho_buf, m->dF,
-                         m->stride);
+      hipLaunchKernelGGL((fs ? eam_nn_embed_kernel<kNetThreads, true> : eam_nn_embed_kernel<kNetThreads>),
+                         dim3((unsigned)blocks), dim3(kNetThreads), net_lds_bytes(m), s, m->nets_dev, t,
+                         m->activation, b, m->rho_buf, m->dF, m->stride);
   }
   if (want_f) {
     if (fold) {
       const dim3 fgrid((unsigned)((b.n_atoms + 15) / 16));
-#define TA_EAM_FORCE(O, WW) \
-  hipLaunchKernelGGL((eam_force_kernel<O, WW>), fgrid, dim3(16 * WW), 0, s, m->p, b, m->dF, m->tabs_dev, \
+#define TA_EAM_FORCE(O, WW, F) \
+  hipLaunchKernelGGL((eam_force_kernel<O, WW, F>), fgrid, dim3(16 * WW), 0, s, m->p, b, m->dF, m->tabs_dev, \
                      no_rec ? 1 : 0, m->eps)
-#define TA_ADP_FORCE(O, WW)                                                                              \
+// (no eam/fs ADP: F is ignored)
+#define TA_ADP_FORCE(O, WW, F)                                                                           \
   hipLaunchKernelGGL((adp_force_kernel<O, WW>), fgrid, dim3(16 * WW), 0, s, m->p, b, m->dF, m->mom, \
                      m->tabs_dev, no_rec ? 1 : 0, m->eps)
       if (m->p.adp) TA_EAM_BY_W(TA_ADP_FORCE);
@@ -2934,7 +2998,10 @@ void eam_compute(EamModel *m, const DeviceBatch &b, uint32_t want, hipStream_t s
 #undef TA_ADP_FORCE
     } else {
       const dim3 pgrid((unsigned)((b.n_pairs + kBlock - 1) / kBlock));
-      if (other)
+      if (fs)
+        hipLaunchKernelGGL((eam_pair_kernel<false, true>), pgrid, dim3(kBlock), 0, s, m->p, b, m->dF, m->mom, m->pf,
+                           ps, m->tabs_dev);
+      else if (other)
         hipLaunchKernelGGL(eam_pair_kernel<true>, pgrid, dim3(kBlock), 0, s, m->p, b, m->dF, m->mom, m->pf, ps,
                            m->tabs_dev);
       else

@@ -4,6 +4,8 @@ analytic-potential hot path:
 
   EamAlloyNN  <- reference tensoralloy/nn/eam/alloy.py:24-127 (+ EamNN, eam.py:78-130)
   AdpNN       <- reference tensoralloy/nn/eam/adp.py (dipole / quadrupole terms)
+  EamFsNN     <- reference tensoralloy/nn/eam/fs.py (Finnis-Sinclair: rho per ordered element pair;
+                 "nn" and tabulated functions, inference only)
 
 Supported potentials: `sutton90` (AgSutton90), `Be/1` (AgrawalBe) and `grimes` (RWGrimes) for
 single-element rho / embed / phi, and the Zhou-Johnson-Wadley family for rho / embed / phi --
@@ -37,7 +39,8 @@ point, as the reference's `CubicInterpolator(x, y, natural_boundary=True)` does
 
 Function networks travel in the MLP fields of `ta_model_desc` as `n_eam_nets` slots in the order
 rho[element], embed[element], phi[pair], then for ADP dipole[pair], quadrupole[pair]; a slot with
-0 layers is an analytic function.
+0 layers is an analytic function. `EamFsNN`: rho[centre][neighbour] (centre-major), embed[element],
+phi[pair].
 """
 from __future__ import annotations
 
@@ -153,13 +156,17 @@ class EamAlloyNN:
     def _pair_functions(self):
         return ("phi",) + tuple(self._extra_functions())
 
+    def _function_layout(self):
+        """{section: [functions]}: per element rho and embed, per unique pair term phi (+ ADP terms)."""
+        res = {el: ["rho", "embed"] for el in self._elements}
+        res.update({t: list(self._pair_functions()) for t in self._unique_kbody_terms})
+        return res
+
     def _get_hidden_sizes(self, hidden_sizes):
         """Nested dict {section: {function: [sizes]}} from an int, a list or a nested dict
         (alloy.py:39-90, adp.py:51-105)."""
         default = list(Defaults.hidden_sizes)
-        res = {el: {"rho": list(default), "embed": list(default)} for el in self._elements}
-        res.update({t: {fn: list(default) for fn in self._pair_functions()}
-                    for t in self._unique_kbody_terms})
+        res = {sec: {fn: list(default) for fn in fns} for sec, fns in self._function_layout().items()}
         if hidden_sizes is None:
             return res
         for sec in res:
@@ -281,13 +288,17 @@ class EamAlloyNN:
             slots += [(t, fn) for t in pairs]
         return slots
 
+    @classmethod
+    def _read_file(cls, path: str):
+        from . import io
+        return io.read_adp_setfl(path) if cls.tag == "adp" else io.read_eam_alloy_setfl(path)
+
     def spline_table(self, section: str, fn: str):
         """The `io.Spline` of a `spline@<path>` function (files are read once per model)."""
-        from . import io
         path = str(self._potentials[section][fn])[len("spline@"):]
         cache = self.__dict__.setdefault("_setfl_cache", {})
         if path not in cache:
-            cache[path] = io.read_adp_setfl(path) if self._extra_functions() else io.read_eam_alloy_setfl(path)
+            cache[path] = self._read_file(path)
         fl = cache[path]
         if fn in ("rho", "embed"):
             group = getattr(fl, fn)
@@ -302,16 +313,19 @@ class EamAlloyNN:
 
     @classmethod
     def from_setfl(cls, path: str, elements=None, **kwargs):
-        """A model whose every function is tabulated in one setfl / adp file."""
-        from . import io
+        """A model whose every function is tabulated in one setfl / adp / eam/fs file."""
         path = os.path.abspath(str(path))
-        fl = io.read_adp_setfl(path) if cls.tag == "adp" else io.read_eam_alloy_setfl(path)
+        fl = cls._read_file(path)
         elements = sorted(elements or fl.elements)
         name = "spline@" + path
-        pots = {el: {"rho": name, "embed": name} for el in elements}
+        if cls.tag == "fs":
+            pots = {el: {"embed": name} for el in elements}
+            pots.update({a + b: {"rho": name} for a in elements for b in elements})
+        else:
+            pots = {el: {"rho": name, "embed": name} for el in elements}
         for i, a in enumerate(elements):
             for b in elements[i:]:
-                pots[a + b] = {"phi": name}
+                pots.setdefault(a + b, {})["phi"] = name
                 if cls.tag == "adp":
                     pots[a + b].update(dipole=name, quadrupole=name)
         nn = cls(elements, custom_potentials=pots, **kwargs)
@@ -662,7 +676,8 @@ class EamAlloyNN:
                 fp.write(f"{z} {atomic_masses[z]!r} {float(lattice_constants.get(el, 0.0))!r} "
                          f"{lattice_types.get(el, 'fcc')}\n")
                 fp.write(block(t["embed"][k]))
-                fp.write(block(t["rho"][k]))
+                for row in self._setfl_density_rows(k):
+                    fp.write(block(t["rho"][row]))
             index = {name: k for k, name in enumerate(t["pairs"])}
             order = [(i, j) for i in range(n) for j in range(i + 1)]  # setfl: (1,1) (2,1) (2,2) ...
             for i, j in order:
@@ -672,6 +687,10 @@ class EamAlloyNN:
                     for i, j in order:
                         fp.write(block(t[key][index[els[j] + els[i]]]))
         return setfl
+
+    def _setfl_density_rows(self, k):
+        """Rows of `eam_tabulate()["rho"]` written in the file block of element k."""
+        return [k]
 
 
 class AdpNN(EamAlloyNN):
@@ -730,10 +749,102 @@ class AdpNN(EamAlloyNN):
         return np.array(out, dtype=np.float64)
 
 
+class EamFsNN(EamAlloyNN):
+    """`eam/fs`, the Finnis-Sinclair form (reference nn/eam/fs.py): the density at an A-centre from a
+    B-neighbour is rho_AB(r), one function per ORDERED element pair, so that
+    E_i = F_A(sum_j rho_{A s_j}(r_ij)) + 1/2 sum_j phi(r_ij) and, for the pair i-j,
+    dE/dr_ij = F'_A(rho_i) rho'_AB(r) + F'_B(rho_j) rho'_BA(r) + phi'_AB(r).
+
+    Functions are "nn" (the reference's default) or `spline@<eam/fs file>`, mixed freely per
+    function; there are no analytic eam/fs potentials here (MSAH11 is reached through its tabulated
+    file: `EamFsNN.from_setfl`). Sections (fs.py `_setup_potentials`, `_get_hidden_sizes`): element ->
+    {"embed"}, every ordered k-body term "AB" -> {"rho"}, and the unique (sorted) pair terms also
+    {"phi"}. Slots handed to the C ABI (`TA_MODEL_EAM_FS`): rho[A][B] over the sorted elements
+    (centre-major), embed[element], phi[pair a <= b]. Inference only: weight, constant and loss
+    gradients and analytic Hessian-vector products are refused by the library (the calculator then
+    differences the forces for `hessian` / `elastic`).
+    """
+
+    tag = "fs"
+    _kind = _lib.TA_MODEL_EAM_FS
+
+    @property
+    def all_kbody_terms(self):
+        """The ordered k-body terms, centre-major over the sorted elements."""
+        return [a + b for a in self._elements for b in self._elements]
+
+    def _function_layout(self):
+        res = {el: ["embed"] for el in self._elements}
+        for term in self.all_kbody_terms:
+            res[term] = ["rho"] + (["phi"] if term in self._unique_kbody_terms else [])
+        return res
+
+    def _setup_potentials(self, custom):
+        custom = {} if custom is None else custom
+        layout = self._function_layout()
+        if isinstance(custom, str):
+            pots = {sec: {fn: custom for fn in fns} for sec, fns in layout.items()}
+        else:
+            pots = {sec: {fn: custom.get(sec, {}).get(fn, "nn") for fn in fns} for sec, fns in layout.items()}
+        for sec, fns in pots.items():
+            for fn, name in fns.items():
+                if str(name).lower() == "nn" or str(name).startswith("spline@"):
+                    continue
+                if str(name).lower() == "msah11":
+                    raise ValueError("msah11 (Mendelev et al.'s Al-Fe eam/fs potential) is available as its "
+                                     "tabulated LAMMPS file: use EamFsNN.from_setfl(<Mendelev_Al_Fe.fs.eam>)")
+                raise ValueError(f"potential '{name}' for {sec}/{fn} is not implemented for eam/fs models "
+                                 f"(EamFsNN takes 'nn' and 'spline@<eam/fs file>' functions)")
+        self._family = "fs"
+        self._el_kind = {el: "zjw" for el in self._elements}
+        return pots
+
+    def _all_slots(self):
+        n = len(self._elements)
+        slots = [(t, "rho") for t in self.all_kbody_terms] + [(el, "embed") for el in self._elements]
+        return slots + [(self._elements[i] + self._elements[j], "phi") for i in range(n) for j in range(i, n)]
+
+    @classmethod
+    def _read_file(cls, path: str):
+        from . import io
+        return io.read_eam_fs_setfl(path)
+
+    def spline_table(self, section: str, fn: str):
+        if fn == "rho":  # keyed by the ordered pair
+            path = str(self._potentials[section][fn])[len("spline@"):]
+            cache = self.__dict__.setdefault("_setfl_cache", {})
+            if path not in cache:
+                cache[path] = self._read_file(path)
+            if section not in cache[path].rho:
+                raise ValueError(f"{path} has no rho table for {section}")
+            return cache[path].rho[section]
+        return super().spline_table(section, fn)
+
+    def flat_parameters(self) -> np.ndarray:
+        """The block `ta_model_desc.eam_params` must hold; no eam/fs kernel reads it."""
+        el = dict.fromkeys(ZJW04_KEYS, 0.0)
+        el.update(r_eq=1.0, rho_e=1.0, rho_s=1.0)
+        n = len(self._elements)
+        out = ([el[k] for k in ZJW04_KEYS] + [0.0, 0.0]) * n + [0.0] * 8 * (n * (n + 1) // 2)
+        return np.array(out, dtype=np.float64)
+
+    def constant_names(self):
+        raise ValueError("eam/fs models are inference only: they have no trainable constants")
+
+    def constants(self) -> np.ndarray:
+        return self.constant_names()
+
+    def _setfl_density_rows(self, k):
+        # LAMMPS eam/fs: table J under element I = density an I-neighbour puts at a J-centre = rho[J + I]
+        # (io.read_eam_fs_setfl); `eam_tabulate` rows are rho[centre][neighbour], centre-major
+        n = len(self._elements)
+        return [j * n + k for j in range(n)]
+
+
 def nn_from_dict(cls_name: str, cfg: dict, npz=None):
     """Rebuild a model from `as_dict()`; `npz` = the weight archive of its nn functions."""
     cfg = dict(cfg)
-    cls = {"EamAlloyNN": EamAlloyNN, "AdpNN": AdpNN}[cls_name]
+    cls = {"EamAlloyNN": EamAlloyNN, "AdpNN": AdpNN, "EamFsNN": EamFsNN}[cls_name]
     nn = cls(**cfg)
     for slot in nn.nn_functions():
         if slot is None:

@@ -458,13 +458,15 @@ class Engine:
     def eam_tabulate(self, r, rho) -> dict:
         """rho(r), phi(r), F(rho) (and u, w for ADP) of an EAM model on the given abscissae,
         evaluated by the device functions of the energy kernels. Rows: sorted elements; pairs
-        a <= b in upper-triangle order."""
+        a <= b in upper-triangle order; for eam/fs the rho rows are rho[centre][neighbour],
+        centre-major."""
         r = np.ascontiguousarray(r, dtype=np.float64).ravel()
         rho = np.ascontiguousarray(rho, dtype=np.float64).ravel()
         nel = len(self._nn.elements)
         npair = nel * (nel + 1) // 2
         adp = getattr(self._nn, "tag", "") == "adp"
-        out = {"rho": np.zeros((nel, len(r))), "phi": np.zeros((npair, len(r))),
+        nrho = nel * nel if getattr(self._nn, "tag", "") == "fs" else nel
+        out = {"rho": np.zeros((nrho, len(r))), "phi": np.zeros((npair, len(r))),
                "embed": np.zeros((nel, len(rho)))}
         null = C.POINTER(C.c_double)()
         if adp:

@@ -110,7 +110,7 @@ class SetFL:
         raise KeyError(f"no {group} table for {a}-{b}")
 
 
-def _read_setfl(filename: str, is_adp: bool) -> SetFL:
+def _read_setfl(filename: str, is_adp: bool, is_fs: bool = False) -> SetFL:
     opener = gzip.open if str(filename).endswith(".gz") else open
     with opener(filename, "rb") as fp:
         # some published tables have "\r\r\n" line ends (Be_Agrawal.eam.alloy): drop every \r
@@ -143,7 +143,12 @@ def _read_setfl(filename: str, is_adp: bool) -> SetFL:
         types.append(tok[pos + 3])
         pos += 4
         embed[el] = Spline(0.0, 0.0, rho_x, take(nrho))
-        rho[el] = Spline(0.0, 0.0, r, take(nr))
+        if is_fs:
+            # table J under element I: the density an I-neighbour puts at a J-centre, keyed centre first
+            for nb in elements:
+                rho[nb + el] = Spline(0.0, 0.0, r, take(nr))
+        else:
+            rho[el] = Spline(0.0, 0.0, r, take(nr))
     # setfl order of the pair tables: (1,1), (2,1), (2,2), (3,1), ... (LAMMPS pair_eam_alloy).
     # The reference's reader walks (1,1), (1,2), (2,2), ... (io/lammps.py:153-160), which is the
     # same for one and two elements -- all its fixtures -- and mislabels tables beyond that.
@@ -157,6 +162,8 @@ def _read_setfl(filename: str, is_adp: bool) -> SetFL:
         for group in (dipole, quadrupole):
             for i, j in order:
                 group[elements[j] + elements[i]] = Spline(0.0, 0.0, r, take(nr))
+    if is_fs and pos != len(tok):
+        raise ValueError(f"{filename}: {len(tok) - pos} values after the last table (not an eam/fs file?)")
     return SetFL(elements=elements, rho=rho, phi=phi, embed=embed, dipole=dipole,
                  quadrupole=quadrupole, nr=nr, dr=dr, nrho=nrho, drho=drho, rcut=rcut,
                  atomic_masses=masses, lattice_constants=consts, lattice_types=types)
@@ -170,6 +177,24 @@ def read_eam_alloy_setfl(filename: str) -> SetFL:
 def read_adp_setfl(filename: str) -> SetFL:
     """Read a LAMMPS adp setfl file (io/lammps.py:231-235)."""
     return _read_setfl(filename, is_adp=True)
+
+
+def read_eam_fs_setfl(filename: str) -> SetFL:
+    """Read a LAMMPS eam/fs (Finnis-Sinclair setfl) file, plain or gzip'ed. Its layout is that of
+    eam/alloy except that every element block holds F(rho) followed by N density tables, one per
+    element of the file. `rho` is keyed by the ordered pair, centre first, as the k-body terms of the
+    reference's `EamFsNN` are (nn/eam/fs.py `_build_rho_nn`): `rho["AB"]` is the density an
+    B-neighbour puts at an A-centre.
+
+    Convention: LAMMPS accumulates rho[i] += rhor[type2rhor[jtype][itype]] with, for eam/fs,
+    type2rhor[a][b] = map[a] * N + map[b] (pair_eam.cpp `compute`, pair_eam_fs.cpp `file2array`;
+    recalled from the LAMMPS sources, which are not part of this project). The J-th density table
+    listed under element I is therefore the density an I-neighbour contributes at a J-centre, and
+    lands at key `J + I`. `EamFsNN.export_to_setfl` writes the reverse. The reference's
+    `EamFsNN.export_to_setfl` (nn/eam/fs.py:345-348) writes `rho[A + B]` under element A at position
+    B, the transpose of this reading; the two agree when the cross densities are symmetric, as they
+    are in Mendelev's Al-Fe file. LAMMPS owns the format, so it is followed here."""
+    return _read_setfl(filename, is_adp=False, is_fs=True)
 
 
 def natural_spline_coefficients(x: np.ndarray, y: np.ndarray) -> np.ndarray:

@@ -761,7 +761,7 @@ def load_model(graph_model_path: str):
             if not layers:
                 raise ValueError(f"{stem}.npz holds no weights of the GRAP filter network")
             nn.descriptor.filter_weights = layers
-    elif nn_cls in ("EamAlloyNN", "AdpNN"):
+    elif nn_cls in ("EamAlloyNN", "AdpNN", "EamFsNN"):
         from .eam import nn_from_dict
         npz = None
         if meta.get("weights"):

@@ -1,0 +1,225 @@
+"""eam/fs (Finnis-Sinclair) on the GPU: the FS kernels against the NumPy restatement
+(tests/fs_reference.py), against the file's own physics, and against the eam/alloy path."""
+import numpy as np
+import pytest
+
+from tests.fs_reference import alloy_as_fs, fs_evaluate, write_synthetic_fs
+from tests.helpers import golden_setfl
+from tests.test_gpu_sf import _alloy, E_TOL, F_TOL, W_TOL
+
+pytestmark = pytest.mark.gpu
+
+FE_A = 2.855312  # the file header's bcc Fe lattice constant
+
+
+def _bcc(symbol="Fe", a=FE_A, rep=(4, 4, 4), jitter=0.0, seed=7, al_fraction=0.0):
+    from tensoralloy_amd import Atoms
+    base = np.array([[0, 0, 0], [.5, .5, .5]]) * a
+    pts = np.array([base + np.array([x, y, z]) * a
+                    for x in range(rep[0]) for y in range(rep[1]) for z in range(rep[2])]).reshape(-1, 3)
+    rng = np.random.RandomState(seed)
+    pts = pts + rng.normal(0.0, jitter, pts.shape) if jitter else pts
+    syms = [symbol] * len(pts)
+    for k in rng.choice(len(pts), int(round(al_fraction * len(pts))), replace=False):
+        syms[k] = "Al"
+    return Atoms(symbols=syms, positions=pts, cell=np.diag(np.array(rep) * a), pbc=True)
+
+
+def _mendelev(tmp_path, **kw):
+    from tensoralloy_amd import UniversalTransformer
+    from tensoralloy_amd.eam import EamFsNN
+    nn = EamFsNN.from_setfl(golden_setfl("Mendelev_Al_Fe_thinned.fs.eam", tmp_path), **kw)
+    nn.attach_transformer(UniversalTransformer(["Al", "Fe"], rcut=6.5, angular=False))
+    return nn
+
+
+def _check(got, ref, e_tol, f_tol, w_tol):
+    assert abs(got["energy"] - ref["energy"]) < e_tol, abs(got["energy"] - ref["energy"])
+    assert np.abs(got["atomic"] - ref["atomic"]).max() < e_tol
+    assert np.abs(got["forces"] - ref["forces"]).max() < f_tol, np.abs(got["forces"] - ref["forces"]).max()
+    assert np.abs(got["virial"] - ref["virial"]).max() < w_tol, np.abs(got["virial"] - ref["virial"]).max()
+
+
+def _random_nn(elements, rcut=6.0, potentials=None, hidden_sizes=None, seed=5, out_scale=0.05):
+    """An FS model with "nn" functions at the scale of physical ones (as tests/helpers.make_eam)."""
+    from tensoralloy_amd import UniversalTransformer
+    from tensoralloy_amd.eam import EamFsNN
+    nn = EamFsNN(elements, custom_potentials=potentials, hidden_sizes=hidden_sizes)
+    nn.attach_transformer(UniversalTransformer(elements, rcut=rcut, angular=False))
+    nn.initialize(seed=seed, bias_scale=0.1)
+    for sec in nn.weights.values():
+        for layers in sec.values():
+            w, b = layers[-1]
+            layers[-1] = (w * out_scale, b)
+    return nn
+
+
+def test_tabulated_fs_against_the_restatement(lib, tmp_path):
+    from tensoralloy_amd import Engine
+    nn = _mendelev(tmp_path)
+    atoms = _bcc(jitter=0.05, al_fraction=0.1)
+    with Engine(nn) as eng:
+        got = eng.evaluate([atoms])[0]
+    _check(got, fs_evaluate(nn, atoms), 1e-9, 1e-10, 1e-8)
+
+
+def test_pure_fe_against_the_files_physics(lib, tmp_path):
+    """Perfect bcc Fe at the header's lattice constant: the cohesive energy of Mendelev's Fe
+    (-4.013 eV) and zero pressure; both from an independent NumPy / SciPy evaluation of the
+    tables (the full and the thinned tables agree to 1e-11 eV)."""
+    from tensoralloy_amd import Engine
+    nn = _mendelev(tmp_path)
+    atoms = _bcc()
+    with Engine(nn) as eng:
+        got = eng.evaluate([atoms])[0]
+    assert abs(got["energy"] / len(atoms) - (-4.012982306)) < 1e-8
+    assert abs(got["total_pressure"]) < 0.01
+
+
+def test_fs_reduces_to_alloy(lib, tmp_path):
+    """An eam/alloy file rewritten as eam/fs (each density table repeated) is the same potential:
+    the FS kernels must reproduce the alloy path."""
+    from tensoralloy_amd import Engine, UniversalTransformer
+    from tensoralloy_amd.eam import EamAlloyNN, EamFsNN
+    src = golden_setfl("Zhou_AlCu.alloy.eam", tmp_path)
+    fs = EamFsNN.from_setfl(alloy_as_fs(src, str(tmp_path / "AlCu.fs.eam")))
+    alloy = EamAlloyNN.from_setfl(src)
+    for nn in (fs, alloy):
+        nn.attach_transformer(UniversalTransformer(["Al", "Cu"], rcut=5.99, angular=False))
+    frames = [_alloy(["Al", "Cu"], rep=(2, 2, 2), a=3.9), _alloy(["Al", "Al", "Cu"], rep=(2, 2, 3), a=4.05)]
+    with Engine(fs) as e1, Engine(alloy) as e2:
+        for a, b in zip(e1.evaluate(frames), e2.evaluate(frames)):
+            _check(a, b, 1e-10, 1e-11, 1e-9)
+
+
+def test_asymmetric_densities_from_a_file(lib, tmp_path):
+    from tensoralloy_amd import Engine, UniversalTransformer
+    from tensoralloy_amd.eam import EamFsNN
+    nn = EamFsNN.from_setfl(write_synthetic_fs(str(tmp_path / "syn.fs.eam")))
+    nn.attach_transformer(UniversalTransformer(["Al", "Fe"], rcut=5.5, angular=False))
+    a, b = nn.spline_table("AlFe", "rho").y, nn.spline_table("FeAl", "rho").y
+    assert np.abs(a - b).max() > 0.1 * np.abs(a).max()
+    frames = [_alloy(["Al", "Fe", "Fe"], rep=(2, 2, 2), a=3.7), _bcc(a=2.9, rep=(3, 3, 3), jitter=0.08,
+                                                                   al_fraction=0.3)]
+    with Engine(nn) as eng:
+        for atoms, got in zip(frames, eng.evaluate(frames)):
+            _check(got, fs_evaluate(nn, atoms), 1e-9, 1e-10, 1e-8)
+
+
+@pytest.mark.parametrize("generic", [False, True])
+def test_asymmetric_nn_densities(lib, monkeypatch, generic):
+    """All-"nn" FS model (four different density networks): exact networks per pair (the nn pair
+    kernels, eam_pair_kernel, force gather) and their tables (the one-pass kernels)."""
+    from tensoralloy_amd import Engine
+    if generic:
+        monkeypatch.setenv("TA_EAM_NN_GENERIC", "1")
+    frames = [_alloy(["Al", "Fe", "Fe"], rep=(2, 2, 2), a=3.6), _alloy(["Fe", "Al"], rep=(1, 2, 2), a=3.4)]
+    for nn in (_random_nn(["Al", "Fe"]), _random_nn(["Al", "Fe"], hidden_sizes=[40], seed=9)):
+        with Engine(nn) as eng:
+            tables = eng.evaluate(frames)
+            eng.set_nn_tables(False)
+            exact = eng.evaluate(frames)
+            eng.set_nn_tables(True)
+            again = eng.evaluate(frames)
+        for atoms, t, x, t2 in zip(frames, tables, exact, again):
+            ref = fs_evaluate(nn, atoms)
+            for got in (t, x, t2):
+                _check(got, ref, E_TOL, F_TOL, W_TOL)
+            assert abs(t["energy"] - x["energy"]) < 1e-9
+
+
+def test_nn_and_spline_functions_in_one_model(lib, tmp_path):
+    from tensoralloy_amd import Engine
+    sp = "spline@" + golden_setfl("Mendelev_Al_Fe_thinned.fs.eam", tmp_path)
+    # Fe centres keep the file's densities and embedding (physical densities for its F(rho)); Al centres
+    # get networks
+    pots = {"Al": {"embed": "nn"}, "Fe": {"embed": sp}, "AlAl": {"rho": "nn", "phi": "nn"},
+            "AlFe": {"rho": "nn", "phi": sp}, "FeAl": {"rho": sp}, "FeFe": {"rho": sp, "phi": sp}}
+    nn = _random_nn(["Al", "Fe"], rcut=6.5, potentials=pots)
+    atoms = _bcc(jitter=0.05, al_fraction=0.2, rep=(3, 3, 3))
+    with Engine(nn) as eng:
+        got = eng.evaluate([atoms])[0]
+        eng.set_nn_tables(False)
+        exact = eng.evaluate([atoms])[0]
+    ref = fs_evaluate(nn, atoms)
+    _check(got, ref, E_TOL, F_TOL, W_TOL)
+    _check(exact, ref, E_TOL, F_TOL, W_TOL)
+
+
+def test_batches_and_the_md_path(lib, tmp_path):
+    from tensoralloy_amd import Engine
+    nn = _mendelev(tmp_path)
+    frames = [_bcc(jitter=0.05, al_fraction=0.1, seed=1), _bcc(rep=(3, 3, 4), jitter=0.05, al_fraction=0.2, seed=2),
+              _bcc(rep=(3, 3, 3), jitter=0.03, al_fraction=0.05, seed=3)]
+    with Engine(nn) as eng:
+        batch = eng.evaluate(frames)
+        singles = [eng.evaluate([f])[0] for f in frames]
+    for a, b in zip(batch, singles):
+        _check(a, b, 1e-10, 1e-11, 1e-9)
+    atoms = frames[0]
+    moved = atoms.positions + np.random.RandomState(4).normal(0.0, 0.02, atoms.positions.shape)
+    from tensoralloy_amd import Atoms
+    later = Atoms(symbols=atoms.get_chemical_symbols(), positions=moved, cell=np.asarray(atoms.get_cell()),
+                  pbc=True)
+    with Engine(nn) as eng:   # Verlet skin: the second call is one step on the resident list
+        eng.set_skin(0.5)
+        eng.evaluate_md(atoms)
+        step = eng.evaluate_md(later)
+    with Engine(nn) as eng:
+        fresh = eng.evaluate([later])[0]
+    _check(step, fresh, 1e-10, 1e-11, 1e-9)
+
+
+def test_calculator_export_and_setfl_round_trip(lib, tmp_path):
+    from tensoralloy_amd import Engine, TensorAlloyCalculator, UniversalTransformer
+    from tensoralloy_amd.eam import EamFsNN
+    nn = _random_nn(["Al", "Fe"], rcut=6.0)
+    # a setfl F(rho) table starts at rho = 0: flip the density networks of this random model to
+    # positive densities (3.5 - 16 on this cell) so that the table covers them
+    for term in nn.all_kbody_terms:
+        w, b = nn.weights[term]["rho"][-1]
+        nn.weights[term]["rho"][-1] = (-w, b)
+    atoms = _alloy(["Al", "Fe", "Fe"], rep=(2, 2, 2), a=3.6)
+    assert 0.0 < fs_evaluate(nn, atoms)["rho"].min()
+    with Engine(nn) as eng:
+        direct = eng.evaluate([atoms])[0]
+    path = nn.export(str(tmp_path / "fs.pb"))
+    calc = TensorAlloyCalculator(path)
+    assert abs(calc.get_potential_energy(atoms) - direct["energy"]) < 1e-10
+    assert np.abs(calc.get_forces(atoms) - direct["forces"]).max() < 1e-10
+    assert np.abs(calc.get_stress(atoms) - direct["stress"]).max() < 1e-10
+    # LAMMPS tables from the device functions, read back as splines
+    out = nn.export_to_setfl(str(tmp_path / "fs.eam.fs"), nr=3000, dr=0.002, nrho=3000, drho=0.01)
+    tab = EamFsNN.from_setfl(out)
+    tab.attach_transformer(UniversalTransformer(["Al", "Fe"], rcut=6.0, angular=False))
+    with Engine(tab) as eng:
+        got = eng.evaluate([atoms])[0]
+    _check(got, direct, 1e-5 * len(atoms), 1e-4, 1e-3)
+
+
+def test_elastic_constants_through_the_difference_fallback(lib, tmp_path):
+    from tensoralloy_amd import TensorAlloyCalculator
+    nn = _mendelev(tmp_path, export_properties=("energy", "forces", "stress", "hessian", "elastic"))
+    path = nn.export(str(tmp_path / "mendelev.pb"))
+    calc = TensorAlloyCalculator(path)
+    atoms = _bcc()
+    C = calc.get_elastic_constant_tensor(atoms)
+    c11, c12, c44 = C[0, 0], C[0, 1], C[3, 3]
+    print(f"Mendelev Fe (thinned tables): C11 {c11:.2f}  C12 {c12:.2f}  C44 {c44:.2f} GPa")
+    assert 200 < c11 < 290 and 110 < c12 < 180 and 90 < c44 < 140
+    assert abs(C[1, 1] - c11) < 1.0 and abs(C[4, 4] - c44) < 1.0
+
+
+def test_gradients_and_hessian_vectors_are_refused(lib):
+    from tensoralloy_amd import Engine
+    nn = _random_nn(["Al", "Fe"])
+    atoms = _alloy(["Al", "Fe"], rep=(1, 1, 1), a=3.6)
+    with Engine(nn) as eng:
+        eng.set_frames([atoms])
+        for call in (lambda: eng.hessian_vectors(), lambda: eng.energy_gradient([1.0]),
+                     lambda: eng.loss_gradient(frame_coeff=[1.0], dR=np.zeros((len(atoms), 3))),
+                     lambda: eng.constant_gradient(frame_coeff=[1.0])):
+            with pytest.raises(ValueError, match="eam/fs"):
+                call()
+        r = eng.evaluate([atoms])[0]           # the handle still evaluates
+    _check(r, fs_evaluate(nn, atoms), E_TOL, F_TOL, W_TOL)
