@@ -234,3 +234,38 @@ def nimo_supercell(name="Ni4Mo_mp-11507", rep=(7, 7, 8), jitter=0.05, seed=611):
         pts = pts + np.random.RandomState(seed).normal(0.0, jitter, pts.shape)
     return Atoms(symbols=list(c["symbols"]) * len(shifts), positions=pts,
                  cell=cell * np.array(rep)[:, None], pbc=True)
+
+
+CHILD = r"""
+import json, sys
+sys.path.insert(0, {root!r})
+import numpy as np
+from tensoralloy_amd import Engine
+from {module} import {func} as cases
+out = []
+for name, nn, frames in cases():
+    with Engine(nn) as eng:
+        res = eng.evaluate(frames, descriptors=True)
+        nnl = int(eng.info.nnl_max)
+    out.append(dict(name=name, nnl=nnl, res=[{{k: np.asarray(v).tolist() for k, v in r.items()}} for r in res]))
+print(json.dumps(out))
+"""
+
+
+def run_child(cases, env, timeout=300):
+    """Evaluate the (name, model, frames) list that `cases` ("module:function") returns in a fresh Python
+    process with `env` added to the environment: the library reads its A/B switches once per process.
+    Returns [{"name", "nnl", "res": per-frame result dicts}]."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    module, func = cases.split(":")
+    p = subprocess.run([sys.executable, "-c", CHILD.format(root=root, module=module, func=func)],
+                       env=dict(os.environ, **env), cwd=root, capture_output=True, text=True, timeout=timeout)
+    assert p.returncode == 0, p.stderr[-3000:]
+    out = json.loads([line for line in p.stdout.splitlines() if line.startswith("[")][-1])
+    for case in out:
+        case["res"] = [{k: np.asarray(v) if isinstance(v, list) else v for k, v in r.items()} for r in case["res"]]
+    return out

@@ -96,3 +96,52 @@ def test_c4_eam_adp_4000_full_size(lib, rc, adp):
     with Engine(nn) as eng:
         res = eng.evaluate([atoms])[0]
     _check(res, oracle_eam_eval(nn, atoms), 4000)
+
+
+def test_c5_per_gpu_share_64_frames(lib):
+    """C5's per-GPU share at full size: 64 distinct 4000-atom Ni frames (seeds and jitter differ, so a frame
+    offset bug shows), default G2 + G4 model (rc 6.5, 2 x 64), every frame against the C oracle."""
+    from bench import ni_frame, ni_model
+    from tensoralloy_amd import Engine
+    from tests.test_gpu_sf_dispatch import check
+    nn = ni_model()
+    frames = [ni_frame(5000 + k, jitter=0.03 + 0.0005 * k) for k in range(64)]
+    with Engine(nn) as eng:
+        res = eng.evaluate(frames)
+        assert int(eng.info.n_atoms) == 64 * 4000 and int(eng.info.nnl_max) <= 192
+    energies = []
+    for k, (atoms, r) in enumerate(zip(frames, res)):
+        ref = _c_oracle(nn, atoms)
+        _check(r, ref, 4000)
+        check(r, ref, f"c5/frame{k}", descriptors=False)
+        energies.append(r["energy"])
+    assert len(set(energies)) == 64
+
+
+def test_uneven_binary_batch_above_16384_atoms(lib):
+    """~20 binary frames of uneven sizes (none a multiple of 16), more than 16384 atoms in all: the
+    16-lane force gather, the one-wavefront MLP kernel chosen by itself (1024+ tiles) and groups of 16
+    atoms that straddle frame boundaries, at scale."""
+    from tensoralloy_amd import Atoms, Engine
+    from tests.test_gpu_sf_dispatch import check
+    nn = make_nn(["Mo", "Ni"], 6.5, True, [64, 64])
+    frames = []
+    for k in range(20):
+        rep = [(6, 6, 6), (5, 6, 7), (7, 6, 5), (6, 5, 7)][k % 4]
+        a = 3.52 + 0.01 * (k % 5)
+        base = np.array([[0, 0, 0], [.5, .5, 0], [.5, 0, .5], [0, .5, .5]]) * a
+        g = np.stack(np.meshgrid(*[np.arange(n) for n in rep], indexing="ij"), axis=-1).reshape(-1, 1, 3) * a
+        pts = (g + base[None]).reshape(-1, 3)[: -(2 * k + 1)]      # an odd number of atoms
+        rng = np.random.RandomState(700 + k)
+        pts = pts + rng.normal(0.0, 0.04 + 0.002 * k, pts.shape)
+        syms = np.where(rng.rand(len(pts)) < 0.2 + 0.02 * k, "Mo", "Ni").tolist()
+        frames.append(Atoms(symbols=syms, positions=pts, cell=np.diag(np.array(rep) * a), pbc=True))
+    n = sum(len(f) for f in frames)
+    assert n > 16384 and all(len(f) % 16 for f in frames)
+    with Engine(nn) as eng:
+        res = eng.evaluate(frames)
+        assert int(eng.info.n_atoms) == n
+    for k, (atoms, r) in enumerate(zip(frames, res)):
+        ref = _c_oracle(nn, atoms)
+        _check(r, ref, len(atoms))
+        check(r, ref, f"uneven/frame{k}", descriptors=False)

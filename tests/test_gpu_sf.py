@@ -21,6 +21,11 @@ def _compare(nn, atoms_list):
     from tensoralloy_amd import Engine
     with Engine(nn) as eng:
         res = eng.evaluate(atoms_list, descriptors=True)
+    return _check_against_oracle(nn, atoms_list, res)
+
+
+def _check_against_oracle(nn, atoms_list, res):
+    assert len(res) == len(atoms_list)
     for atoms, r in zip(atoms_list, res):
         o = oracle_eval(nn, atoms)
         assert np.abs(r["descriptors"] - o["descriptors"]).max() < G_TOL
@@ -307,13 +312,23 @@ def test_one_wavefront_mlp_kernel(lib, monkeypatch, hidden, activation, minmax):
                 assert np.abs(a["atomic"] - other["atomic"]).max() < 1e-11
 
 
-def test_angular_kernels_without_job_lists(lib, monkeypatch):
+def no_job_list_cases():
+    return [("ni", make_nn(["Ni"], 6.5, True, [16, 16]),
+             [fcc(rep=(3, 3, 3), jitter=0.05), fcc(rep=(2, 2, 2), a=3.4, seed=4)]),
+            ("nimo", make_nn(["Mo", "Ni"], 6.0, True, [16]), [_alloy(["Ni", "Ni", "Mo"], rep=(2, 2, 2))])]
+
+
+def test_angular_kernels_without_job_lists(lib):
     """`TA_NO_JOBS=1`: the second-generation kernels without the forward -> backward job list (lanes
     re-dealt by popcount, descriptors assembled from the lanes' partial sums in LDS). The path batches
-    fall back to when the list buffers are switched off; same parity gate."""
-    monkeypatch.setenv("TA_NO_JOBS", "1")
-    _compare(make_nn(["Ni"], 6.5, True, [16, 16]), [fcc(rep=(3, 3, 3), jitter=0.05), fcc(rep=(2, 2, 2), a=3.4, seed=4)])
-    _compare(make_nn(["Mo", "Ni"], 6.0, True, [16]), [_alloy(["Ni", "Ni", "Mo"], rep=(2, 2, 2))])
+    fall back to when the list buffers are switched off; same parity gate. The library reads the switch
+    once per process, so it runs in a fresh one (more settings and caps: test_gpu_sf_dispatch.py)."""
+    from tests.helpers import run_child
+    out = run_child("tests.test_gpu_sf:no_job_list_cases", {"TA_NO_JOBS": "1"})
+    cases = no_job_list_cases()
+    assert [c["name"] for c in out] == [c[0] for c in cases]
+    for case, (_, nn, frames) in zip(out, cases):
+        _check_against_oracle(nn, frames, case["res"])
 
 
 @pytest.mark.gpu
