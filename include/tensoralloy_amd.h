@@ -150,7 +150,21 @@ typedef struct {
    * variable TENSORALLOY_USE_CUSTOM_POW): an infinite value and an infinite or NaN derivative factor
    * become 0. 0: plain pow, as `tf.pow`. Integer exponents are products and never singular. */
   int32_t safe_pow;
+
+  /* Temperature-dependent models (TemperatureDependentAtomicNN, nn/atomic/finite_temperature.py:211-304)
+   * on TA_MODEL_SF_MLP and TA_MODEL_GRAP_MLP. 0 = plain per-element MLP. Otherwise bit 0 = 1, bit 1 =
+   * algo "Sommerfeld" (S = s(z) T instead of s(z)), bits 8-15 = the TA_ACT_* of the H nets
+   * (FiniteTemperatureOptions.activation). `n_layers`, `layer_sizes` and `weights` then describe
+   * 3 n_elements nets in the order H[element], U[element], S[element]: H maps the (min-max scaled,
+   * `xlo` / `xhi`) descriptors to K features (linear output layer with bias); U and S map
+   * z = [H, T] (K + 1 inputs, T = the frame's electron temperature in eV) to one output with
+   * `activation`. Per atom F = U - T S is the energy whose forces and virial are computed; U and S
+   * come from ta_get_td_results. Inference only: ta_param_count, ta_update_weights,
+   * ta_energy_gradient, ta_loss_gradient and ta_hessian_vectors return TA_ERR_UNSUPPORTED. */
+  int32_t finite_temperature;
 } ta_model_desc;
+
+enum { TA_TD_ON = 1, TA_TD_SOMMERFELD = 2, TA_TD_ACT_SHIFT = 8 };
 
 /* One structure = what `UniversalTransformer.get_np_feed_dict(atoms)`
  * (universal.py:851-893) receives: an `ase.Atoms`. Atom order is the caller's
@@ -241,13 +255,24 @@ int ta_list_sizes(ta_handle h, int64_t *n_pairs, int64_t *n_triples, int32_t *nn
 int ta_compute(ta_handle h, uint32_t want);
 
 /* copies results device->host and synchronises. Any pointer may be NULL.
- *   energy      [n_frames]            eV
+ *   energy      [n_frames]            eV (temperature-dependent models: the free energy F = U - T S)
  *   forces      [n_atoms_total][3]    eV/A        (caller's atom order)
  *   virial      [n_frames][9]         eV, W_ab = sum_pairs dE/dD_a * D_b
  *   atomic      [n_atoms_total]       eV
  *   descriptors [n_atoms_total][D]    raw G (before min-max)             */
 int ta_get_results(ta_handle h, double *energy, double *forces, double *virial,
                    double *atomic, double *descriptors);
+
+/* Temperature-dependent models only (TA_ERR_INVALID otherwise).
+ *   ta_set_electron_temperatures  T [n_frames] in eV for the frames of the last ta_set_frames (the
+ *                        reference's `etemperature`, universal.py:295). ta_set_frames resets every T to
+ *                        0; ta_update_positions, ta_step and list reuses keep them.
+ *   ta_get_td_results    after ta_compute: the internal energy U and the electron entropy S per frame
+ *                        [n_frames] and per atom [n_atoms_total] (caller's atom order); the frame
+ *                        values are the sums of the atom values. Any pointer may be NULL. */
+int ta_set_electron_temperatures(ta_handle h, int32_t n_frames, const double *T);
+int ta_get_td_results(ta_handle h, double *energy, double *eentropy, double *energy_atomic,
+                      double *eentropy_atomic);
 
 /* ta_set_frames + ta_compute + ta_get_results */
 int ta_eval(ta_handle h, int32_t n_frames, const ta_frame *frames, uint32_t want,

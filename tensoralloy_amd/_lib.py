@@ -20,7 +20,7 @@ INCLUDE_DIR = REPO_DIR / "include"
 LIB_PATH = PKG_DIR / "libtensoralloy_amd.so"
 
 SOURCES = ["ta_api.hip", "ta_kernels.hip", "ta_kernels_v2.hip", "ta_mlp.hip", "ta_eam.hip",
-           "ta_nlist.hip", "ta_grap.hip", "ta_train.hip", "ta_hvp.hip", "ta_neighbor.cpp"]
+           "ta_nlist.hip", "ta_grap.hip", "ta_train.hip", "ta_hvp.hip", "ta_neighbor.cpp", "ta_td.hip"]
 OBJ_DIR = CSRC_DIR / "build"
 
 TA_OK = 0
@@ -32,6 +32,8 @@ TA_CUTOFF = {"cosine": 0, "polynomial": 1}
 TA_ACT = {"relu": 0, "softplus": 1, "tanh": 2, "squareplus": 3, "leaky_relu": 4,
           "sigmoid": 5, "softsign": 6, "elu": 7}
 TA_N_KERNEL_SLOTS = 10
+# ta_model_desc.finite_temperature: bit 0 = temperature-dependent, bit 1 = Sommerfeld, bits 8-15 = H activation
+TA_TD_ON, TA_TD_SOMMERFELD, TA_TD_ACT_SHIFT = 1, 2, 8
 TA_ABI_VERSION = 5  # include/tensoralloy_amd.h: TA_ABI_VERSION
 KERNEL_SLOTS = ["pair_geometry", "g4_forward", "descriptor_reduce", "mlp", "backward",
                 "force_gather", "frame_reduce", "eam", "neighbor_update", "grap_forward"]
@@ -45,6 +47,7 @@ EXPORTED_SYMBOLS = [
     "ta_energy_gradient", "ta_measure_hbm_copy", "ta_set_skin", "ta_update_positions", "ta_list_stats",
     "ta_count_contributing_triples", "ta_loss_gradient", "ta_constant_count", "ta_get_constants", "ta_update_constants",
     "ta_constant_gradient", "ta_list_sizes", "ta_abi_version", "ta_model_desc_size", "ta_set_nn_tables", "ta_step", "ta_hessian_vectors", "ta_view_results", "ta_step_view",
+    "ta_set_electron_temperatures", "ta_get_td_results",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -68,6 +71,7 @@ class ModelDesc(C.Structure):
         ("n_eam_nets", C.c_int32),
         ("eam_table_n", _ip), ("eam_table_dx", _dp), ("eam_table_coef", _dp),
         ("safe_pow", C.c_int32),
+        ("finite_temperature", C.c_int32),
     ]
 
 
@@ -225,6 +229,8 @@ def load():
     lib.ta_free.argtypes = [C.c_void_p]
     lib.ta_eam_tabulate.argtypes = [H, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]
     lib.ta_free.restype = None
+    lib.ta_set_electron_temperatures.argtypes = [H, C.c_int32, _dp]
+    lib.ta_get_td_results.argtypes = [H, _dp, _dp, _dp, _dp]
     _lib = lib
     return lib
 

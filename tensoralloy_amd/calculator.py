@@ -19,7 +19,11 @@ Differences (documented in INTEGRATION.md):
     they raise `AttributeError`.
   * `hessian` and `elastic` are central differences of the analytic forces / virial (the
     reference differentiates its graph twice, basic.py:411-421, constraint/elastic.py:24-92);
-    `eentropy` and `enthalpy` are not implemented; `free_energy` only where it is the energy op.
+    `enthalpy` is not implemented; `eentropy` and a `free_energy` of its own only for
+    temperature-dependent models (`TemperatureDependentAtomicNN`: `energy` is the internal energy
+    U, `free_energy` F = U - T S, `eentropy` S; forces, stress and pressure derive from F; the
+    electron temperature is `atoms.info["etemperature"]` in eV, 0 when absent), elsewhere
+    `free_energy` only where it is the energy op.
 """
 from __future__ import annotations
 
@@ -110,6 +114,8 @@ class TensorAlloyCalculator(BaseCalculator):
                       "total_pressure", "hessian", "elastic"}
         if ops.get("free_energy") and ops.get("free_energy") == ops.get("energy"):
             producible.add("free_energy")
+        if int(self._meta.get("Metadata/is_finite_temperature", 0)):
+            producible |= {"free_energy", "eentropy", "free_energy/atom", "eentropy/atom"}
         ops = {k: v for k, v in ops.items() if k in producible}
         if not ops:
             raise Exception("Validated Ops cannot be found")  # calculator.py:161
@@ -223,10 +229,13 @@ class TensorAlloyCalculator(BaseCalculator):
 
     def _displaced(self, atoms, positions=None, cell=None):
         from .atoms import Atoms
+        # (a temperature-dependent model reads the frame's electron temperature from `info`)
+        info = {"etemperature": atoms.info["etemperature"]} \
+            if self._is_finite_temperature and "etemperature" in atoms.info else None
         return Atoms(numbers=np.asarray(atoms.numbers).copy(),
                      positions=atoms.positions if positions is None else positions,
                      cell=np.asarray(atoms.get_cell(complete=True)) if cell is None else cell,
-                     pbc=np.asarray(atoms.pbc).copy())
+                     pbc=np.asarray(atoms.pbc).copy(), info=info)
 
     def _hessian(self, atoms, vap):
         """[n_vap, 3, n_vap, 3], GSL order, virtual atom = zero row/column: the layout of
@@ -347,6 +356,8 @@ class TensorAlloyCalculator(BaseCalculator):
         for target in properties:
             if target == "energy":
                 results[target] = res["energy"]
+            elif target in ("free_energy", "eentropy") and self._is_finite_temperature:
+                results[target] = res[target]
             elif target == "free_energy":
                 results[target] = res["energy"]
             elif target == "total_stress":
@@ -358,6 +369,9 @@ class TensorAlloyCalculator(BaseCalculator):
                 # GSL order, virtual row stripped (atomic.py:289-299)
                 results[target] = res["atomic"] if vap.is_identity else \
                     vap.map_array(res["atomic"].reshape(-1, 1))[1:, 0]
+            elif target in ("free_energy/atom", "eentropy/atom"):
+                values = res[target.replace("/atom", "_atomic")]
+                results[target] = values if vap.is_identity else vap.map_array(values.reshape(-1, 1))[1:, 0]
             elif target == "forces":
                 # (identity map: GSL order is the caller's order, no gather through a padded copy)
                 results[target] = res["forces"] if vap.is_identity else vap.map_forces(res["forces"])[1:]

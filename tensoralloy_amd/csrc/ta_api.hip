@@ -21,6 +21,10 @@ size_t mlp_scratch_doubles(const MlpDev &mlp);
 void launch_mlp_impl(const MlpDev &mlp, int activation, int ndim, const int32_t *atoms, int n_atoms,
                      const DeviceBatch &b, double *scratch, hipStream_t s);
 size_t mlp_all_scratch_doubles(const MlpDev *mlps_host, int nel, const int32_t *elem_start);
+size_t td_scratch_doubles(const MlpDev *nets, int nel, int K, const int32_t *elem_start);
+void launch_td_all(const MlpDev *nets_dev, const MlpDev *nets_host, int nel, int K, int act_h, int act,
+                   int sommerfeld, int ndim, const DeviceBatch &b, const double *T, double *u_atom,
+                   double *s_atom, double *scratch, hipStream_t s);
 void launch_mlp_all(const MlpDev *mlps_dev, const MlpDev *mlps_host, int nel, int activation, int ndim,
                     const DeviceBatch &b, double *scratch, hipStream_t s);
 // weight gradients (ta_train.hip)
@@ -225,6 +229,11 @@ struct ta_context {
   bool use_v2 = false;
   ta::MlpDev *mlp_dev = nullptr;     // device copy of mlp[0..n_elements)
   ta::MlpDev mlp[ta::kMaxElements];
+  // temperature-dependent head (ta_model_desc.finite_temperature): nets H[el], U[el], S[el]
+  bool td = false, td_sommerfeld = false;
+  int td_act = 0, td_K = 0;
+  ta::MlpDev td_nets[3 * ta::kMaxElements];
+  ta::MlpDev *td_dev = nullptr;
   std::vector<void *> model_allocs;
   ta::EamModel *eam = nullptr;
   ta::GrapModel *grap = nullptr;
@@ -242,6 +251,7 @@ struct ta_context {
   DevBuf<double> results;
   size_t o_blk = 0;  // byte offset of blk_center in the packed input
   DevBuf<double> rec, part4, G, dEdG, g, wat, bpart, fown, benergy, mlp_scratch;
+  DevBuf<double> td_T, td_u, td_s;  // electron temperature per frame; U and S per atom
   DevBuf<unsigned long long> masks;
   DevBuf<uint32_t> job_word;
   DevBuf<int32_t> job_count;
@@ -303,6 +313,12 @@ int fail(ta_context *h, int code, const std::string &msg) {
   else
     g_create_error = msg;
   return code;
+}
+
+// temperature-dependent models evaluate energies, forces and virials only
+std::string td_inference_only(const char *fn) {
+  return std::string(fn) + ": not available for finite-temperature (temperature-dependent) models "
+         "(inference only: no weight or loss gradients and no analytic Hessian-vector products)";
 }
 
 // eam/fs models evaluate energies, forces and virials only
@@ -480,59 +496,102 @@ void build_sf_model(ta_context *h, const ta_model_desc *m) {
   build_mlp(h, m, sf.ndim);
 }
 
-// per-element MLP weights -> padded device copies, both orientations
+// one network's weights (layer_sizes `sizes[0..L]`, weights from `wsrc`, advanced past them) -> padded
+// device copies, both orientations. The output layer is linear; ResNet skips as convolutional.py:272.
+void build_net(ta_context *h, ta::MlpDev &md, int L, const int32_t *sizes, const double *&wsrc, int resnet) {
+  using namespace ta;
+  if (L < 1 || L > kMaxLayers) throw std::domain_error("MLP depth out of range (1..8 layers)");
+  md.n_layers = L;
+  md.max_np = md.max_kp = 0;
+  for (int l = 0; l < L; ++l) {
+    MlpLayerDev &ly = md.layer[l];
+    ly.k = sizes[l];
+    ly.n = sizes[l + 1];
+    if (ly.k < 1 || ly.n < 1 || ly.k > 512 || ly.n > 512)
+      throw std::domain_error("MLP layer width out of range (1..512)");
+    ly.kp = round_up(ly.k, 16);
+    ly.np = round_up(ly.n, 16);
+    ly.act = (l < L - 1) ? 1 : 0;
+    // ResNet skip: hidden layer j > 0 with equal widths (convolutional.py:272)
+    ly.res = (resnet && l > 0 && l < L - 1 && ly.k == ly.n) ? 1 : 0;
+    std::vector<double> w((size_t)ly.kp * ly.np, 0.0), wt((size_t)ly.np * ly.kp, 0.0), bb(ly.np, 0.0);
+    for (int k = 0; k < ly.k; ++k)
+      for (int n = 0; n < ly.n; ++n) {
+        const double v = wsrc[(size_t)k * ly.n + n];
+        w[(size_t)k * ly.np + n] = v;
+        wt[(size_t)n * ly.kp + k] = v;
+      }
+    wsrc += (size_t)ly.k * ly.n;
+    for (int n = 0; n < ly.n; ++n) bb[n] = wsrc[n];
+    wsrc += ly.n;
+    ly.w = upload(h, w);
+    ly.wt = upload(h, wt);
+    ly.b = upload(h, bb);
+    md.max_np = std::max(md.max_np, ly.np);
+    md.max_kp = std::max(md.max_kp, ly.kp);
+  }
+}
+
+// per-element MLP weights -> padded device copies, both orientations. Temperature-dependent models:
+// 3 n_elements nets H[el], U[el], S[el] (ta_model_desc.finite_temperature)
 void build_mlp(ta_context *h, const ta_model_desc *m, int ndim) {
   using namespace ta;
   const int nel = m->n_elements;
-  struct { int ndim; } sf{ndim};
   if (!m->n_layers || !m->layer_sizes || !m->weights)
     throw std::invalid_argument("MLP description missing");
   h->activation = m->activation;
   if (m->activation < 0 || m->activation > TA_ACT_ELU)
     throw std::invalid_argument("unknown activation");
+  const int td = m->finite_temperature;
   const int32_t *sizes = m->layer_sizes;
   const double *wsrc = m->weights;
+  if (td) {
+    if ((td & ~(TA_TD_ON | TA_TD_SOMMERFELD | (0xff << TA_TD_ACT_SHIFT))) || !(td & TA_TD_ON))
+      throw std::invalid_argument("unknown finite_temperature bits");
+    h->td = true;
+    h->td_sommerfeld = (td & TA_TD_SOMMERFELD) != 0;
+    h->td_act = (td >> TA_TD_ACT_SHIFT) & 0xff;
+    if (h->td_act > TA_ACT_ELU) throw std::invalid_argument("unknown activation of the H nets");
+    h->td_K = 0;
+    for (int q = 0; q < 3; ++q)
+      for (int el = 0; el < nel; ++el) {
+        MlpDev &md = h->td_nets[q * nel + el];
+        const int L = m->n_layers[q * nel + el];
+        if (L < 1 || L > kMaxLayers) throw std::domain_error("MLP depth out of range (1..8 layers)");
+        if (q == 0) {
+          if (sizes[0] != ndim) throw std::invalid_argument("H input size does not match the descriptor length");
+          if (el == 0) h->td_K = sizes[L];
+          if (sizes[L] != h->td_K) throw std::invalid_argument("H output width differs between elements");
+        } else {
+          if (sizes[0] != h->td_K + 1) throw std::invalid_argument("U / S input size must be the H width + 1");
+          if (sizes[L] != 1) throw std::invalid_argument("U / S output size must be 1");
+        }
+        build_net(h, md, L, sizes, wsrc, m->use_resnet_dt);
+        if (q == 0 && m->minmax_scale) {
+          if (!m->xlo || !m->xhi) throw std::invalid_argument("minmax_scale set but xlo/xhi missing");
+          std::vector<double> lo(m->xlo + (size_t)el * ndim, m->xlo + (size_t)(el + 1) * ndim);
+          std::vector<double> hi(m->xhi + (size_t)el * ndim, m->xhi + (size_t)(el + 1) * ndim);
+          md.xlo = upload(h, lo);
+          md.xhi = upload(h, hi);
+        }
+        sizes += L + 1;
+      }
+    std::vector<MlpDev> all(h->td_nets, h->td_nets + 3 * nel);
+    h->td_dev = upload(h, all);
+    return;
+  }
   for (int el = 0; el < nel; ++el) {
     MlpDev &md = h->mlp[el];
     const int L = m->n_layers[el];
     if (L < 1 || L > kMaxLayers) throw std::domain_error("MLP depth out of range (1..8 layers)");
-    if (sizes[0] != sf.ndim)
+    if (sizes[0] != ndim)
       throw std::invalid_argument("MLP input size does not match the descriptor length");
     if (sizes[L] != 1) throw std::invalid_argument("MLP output size must be 1");
-    md.n_layers = L;
-    md.max_np = md.max_kp = 0;
-    for (int l = 0; l < L; ++l) {
-      MlpLayerDev &ly = md.layer[l];
-      ly.k = sizes[l];
-      ly.n = sizes[l + 1];
-      if (ly.k < 1 || ly.n < 1 || ly.k > 512 || ly.n > 512)
-        throw std::domain_error("MLP layer width out of range (1..512)");
-      ly.kp = round_up(ly.k, 16);
-      ly.np = round_up(ly.n, 16);
-      ly.act = (l < L - 1) ? 1 : 0;
-      // ResNet skip: hidden layer j > 0 with equal widths (convolutional.py:272)
-      ly.res = (m->use_resnet_dt && l > 0 && l < L - 1 && ly.k == ly.n) ? 1 : 0;
-      std::vector<double> w((size_t)ly.kp * ly.np, 0.0), wt((size_t)ly.np * ly.kp, 0.0),
-          bb(ly.np, 0.0);
-      for (int k = 0; k < ly.k; ++k)
-        for (int n = 0; n < ly.n; ++n) {
-          const double v = wsrc[(size_t)k * ly.n + n];
-          w[(size_t)k * ly.np + n] = v;
-          wt[(size_t)n * ly.kp + k] = v;
-        }
-      wsrc += (size_t)ly.k * ly.n;
-      for (int n = 0; n < ly.n; ++n) bb[n] = wsrc[n];
-      wsrc += ly.n;
-      ly.w = upload(h, w);
-      ly.wt = upload(h, wt);
-      ly.b = upload(h, bb);
-      md.max_np = std::max(md.max_np, ly.np);
-      md.max_kp = std::max(md.max_kp, ly.kp);
-    }
+    build_net(h, md, L, sizes, wsrc, m->use_resnet_dt);
     if (m->minmax_scale) {
       if (!m->xlo || !m->xhi) throw std::invalid_argument("minmax_scale set but xlo/xhi missing");
-      std::vector<double> lo(m->xlo + (size_t)el * sf.ndim, m->xlo + (size_t)(el + 1) * sf.ndim);
-      std::vector<double> hi(m->xhi + (size_t)el * sf.ndim, m->xhi + (size_t)(el + 1) * sf.ndim);
+      std::vector<double> lo(m->xlo + (size_t)el * ndim, m->xlo + (size_t)(el + 1) * ndim);
+      std::vector<double> hi(m->xhi + (size_t)el * ndim, m->xhi + (size_t)(el + 1) * ndim);
       md.xlo = upload(h, lo);
       md.xhi = upload(h, hi);
     }
@@ -761,6 +820,16 @@ static void dump_stamps(ta_context *h) {
 }
 #endif
 
+// per-atom head on the descriptors: the MLP, or the temperature-dependent H / U / S nets
+void launch_head(ta_context *h, const ta::DeviceBatch &db, hipStream_t s) {
+  if (h->td)
+    ta::launch_td_all(h->td_dev, h->td_nets, h->n_elements, h->td_K, h->td_act, h->activation,
+                      h->td_sommerfeld ? 1 : 0, h->sf.ndim, db, h->td_T.ptr, h->td_u.ptr, h->td_s.ptr,
+                      h->mlp_scratch.ptr, s);
+  else
+    ta::launch_mlp_all(h->mlp_dev, h->mlp, h->n_elements, h->activation, h->sf.ndim, db, h->mlp_scratch.ptr, s);
+}
+
 void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
   using namespace ta;
 #ifdef TA_PHASE_STAMPS
@@ -787,8 +856,7 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
   const bool has_mlp = h->kind == TA_MODEL_SF_MLP || h->kind == TA_MODEL_GRAP_MLP;
   if ((want & TA_WANT_REUSE_DESCRIPTORS) && has_mlp && h->descriptors_valid && !need_forces) {
     begin(TA_K_MLP);
-    launch_mlp_all(h->mlp_dev, h->mlp, h->n_elements, h->activation, h->sf.ndim, db,
-                   h->mlp_scratch.ptr, s);
+    launch_head(h, db, s);
     end(TA_K_MLP);
     used[TA_K_MLP] = true;
   } else if (h->kind == TA_MODEL_SF_MLP) {
@@ -828,8 +896,7 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
       used[TA_K_DESCRIPTOR_REDUCE] = true;
     }
     begin(TA_K_MLP);
-    launch_mlp_all(h->mlp_dev, h->mlp, h->n_elements, h->activation, h->sf.ndim, db,
-                   h->mlp_scratch.ptr, s);
+    launch_head(h, db, s);
     end(TA_K_MLP);
     used[TA_K_MLP] = true;
     if (need_forces) {
@@ -867,8 +934,7 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
     end(TA_K_GRAP);
     used[TA_K_GRAP] = true;
     begin(TA_K_MLP);
-    launch_mlp_all(h->mlp_dev, h->mlp, h->n_elements, h->activation, h->sf.ndim, db,
-                   h->mlp_scratch.ptr, s);
+    launch_head(h, db, s);
     end(TA_K_MLP);
     used[TA_K_MLP] = true;
     if (need_forces) {
@@ -1297,6 +1363,13 @@ void set_frames_impl(ta_context *h, int32_t n_frames, const ta_frame *frames, ta
   } else {
     ta::eam_ensure(h->eam, h->db);
   }
+  if (h->td) {
+    const size_t N = (size_t)h->db.n_atoms;
+    h->mlp_scratch.ensure(ta::td_scratch_doubles(h->td_nets, h->n_elements, h->td_K, h->db.elem_start));
+    h->td_u.ensure(N + 1);
+    h->td_s.ensure(N + 1);
+    h->td_T.ensure((size_t)h->db.n_frames + 1);
+  }
   // what ta_update_positions needs: the geometry this list was built for and the frames' shapes
   // (host-side copies, made while the device still works on the reverse index)
   h->o_pos = o_pos;
@@ -1349,7 +1422,56 @@ extern "C" {
 int ta_set_frames(ta_handle h, int32_t n_frames, const ta_frame *frames, ta_batch_info *info) {
   if (!h) return TA_ERR_INVALID;
   if (n_frames < 0 || (n_frames > 0 && !frames)) return fail(h, TA_ERR_INVALID, "bad frames argument");
-  return guarded(h, [&]() { set_frames_impl(h, n_frames, frames, info); });
+  return guarded(h, [&]() {
+    set_frames_impl(h, n_frames, frames, info);
+    if (h->td)  // every frame starts at T = 0, the reference's default (universal.py:295)
+      HIP_CHECK(hipMemsetAsync(h->td_T.ptr, 0, (size_t)n_frames * sizeof(double), h->stream));
+  });
+}
+
+int ta_set_electron_temperatures(ta_handle h, int32_t n_frames, const double *T) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->td) return fail(h, TA_ERR_INVALID, "ta_set_electron_temperatures: not a temperature-dependent model");
+  if (!h->have_batch && h->keep_natoms.empty()) return fail(h, TA_ERR_INVALID, "no resident batch");
+  if (n_frames != (int32_t)h->keep_natoms.size() || (n_frames > 0 && !T))
+    return fail(h, TA_ERR_INVALID, "ta_set_electron_temperatures: one temperature per frame of the batch");
+  for (int32_t f = 0; f < n_frames; ++f)
+    if (!std::isfinite(T[f])) return fail(h, TA_ERR_INVALID, "electron temperatures must be finite");
+  return guarded(h, [&]() {
+    // nothing enqueued before may still read the old values; the copy is done when the call returns
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (n_frames > 0) {
+      HIP_CHECK(hipMemcpyAsync(h->td_T.ptr, T, (size_t)n_frames * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      HIP_CHECK(hipStreamSynchronize(h->stream));
+    }
+  });
+}
+
+int ta_get_td_results(ta_handle h, double *energy, double *eentropy, double *energy_atomic, double *eentropy_atomic) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->td) return fail(h, TA_ERR_INVALID, "ta_get_td_results: not a temperature-dependent model");
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "no resident batch");
+  return guarded(h, [&]() {
+    const size_t N = (size_t)h->db.n_atoms, F = h->keep_natoms.size();
+    std::vector<double> u(N), s(N);
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (N) {
+      HIP_CHECK(hipMemcpy(u.data(), h->td_u.ptr, N * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(s.data(), h->td_s.ptr, N * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    if (energy_atomic && N) std::memcpy(energy_atomic, u.data(), N * sizeof(double));
+    if (eentropy_atomic && N) std::memcpy(eentropy_atomic, s.data(), N * sizeof(double));
+    size_t a = 0;
+    for (size_t f = 0; f < F; ++f) {
+      double su = 0.0, ss = 0.0;
+      for (int32_t k = 0; k < h->keep_natoms[f]; ++k, ++a) {
+        su += u[a];
+        ss += s[a];
+      }
+      if (energy) energy[f] = su;
+      if (eentropy) eentropy[f] = ss;
+    }
+  });
 }
 
 int ta_set_skin(ta_handle h, double skin) {
@@ -1733,6 +1855,7 @@ int ta_copy_batch_energy(ta_handle h, void *dst_device) {
 
 int ta_param_count(ta_handle h, int64_t *n_params) {
   if (!h || !n_params) return TA_ERR_INVALID;
+  if (h->td) return fail(h, TA_ERR_UNSUPPORTED, td_inference_only("ta_param_count"));
   if (h->eam) {  // the nn functions of an EAM / ADP model, slot after slot
     *n_params = ta::eam_param_count(h->eam);
     return TA_OK;
@@ -1747,6 +1870,7 @@ int ta_param_count(ta_handle h, int64_t *n_params) {
 
 int ta_update_weights(ta_handle h, const double *weights, int64_t n_weights) {
   if (!h || !weights) return TA_ERR_INVALID;
+  if (h->td) return fail(h, TA_ERR_UNSUPPORTED, td_inference_only("ta_update_weights"));
   if (h->eam)
     return guarded(h, [&]() {
       HIP_CHECK(hipStreamSynchronize(h->stream));  // nothing may still read the old weights
@@ -1785,6 +1909,7 @@ int ta_update_weights(ta_handle h, const double *weights, int64_t n_weights) {
 
 int ta_energy_gradient(ta_handle h, const double *frame_coeff, double *grad, int64_t n_grad) {
   if (!h || !frame_coeff || !grad) return TA_ERR_INVALID;
+  if (h->td) return fail(h, TA_ERR_UNSUPPORTED, td_inference_only("ta_energy_gradient"));
   if (h->kind == TA_MODEL_EAM_FS) return fail(h, TA_ERR_INVALID, fs_inference_only("ta_energy_gradient"));
   if (!h->have_batch) return fail(h, TA_ERR_INVALID, "no resident batch");
   if (h->eam)
@@ -1903,6 +2028,7 @@ void ensure_pair_jacobians(ta_context *h) {
 int ta_loss_gradient(ta_handle h, const double *frame_coeff, const double *dR, const double *dh, double *grad,
                      int64_t n_grad, double *dG_out) {
   if (!h || !grad) return TA_ERR_INVALID;
+  if (h->td) return fail(h, TA_ERR_UNSUPPORTED, td_inference_only("ta_loss_gradient"));
   if (h->kind == TA_MODEL_EAM_FS) return fail(h, TA_ERR_INVALID, fs_inference_only("ta_loss_gradient"));
   if (!h->have_batch) return fail(h, TA_ERR_INVALID, "no resident batch");
   if (!dR && !dh) {
@@ -2112,6 +2238,7 @@ void ta_free(void *p) { std::free(p); }
 int ta_hessian_vectors(ta_handle h, int32_t n_dir, int32_t first, const double *dR, const double *dh, double *dF,
                        double *dW) {
   if (!h || !dF || n_dir < 0) return TA_ERR_INVALID;
+  if (h->td) return fail(h, TA_ERR_UNSUPPORTED, td_inference_only("ta_hessian_vectors"));
   if (h->kind == TA_MODEL_EAM_FS) return fail(h, TA_ERR_INVALID, fs_inference_only("ta_hessian_vectors"));
   if (!h->have_batch) return fail(h, TA_ERR_INVALID, "no resident batch");
   const bool grap_model = h->kind == TA_MODEL_GRAP_MLP;

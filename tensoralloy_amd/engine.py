@@ -37,6 +37,9 @@ class Engine:
         self._md_sig = None   # (n, numbers, pbc) of the single resident frame of `evaluate_md`
         self._md_cell = None
         self.batch_generation = 0  # bumped whenever the resident batch or its coordinates change
+        # temperature-dependent models: electron temperature (eV) of every resident frame
+        self.finite_temperature = bool(getattr(nn, "is_finite_temperature", False))
+        self._etemperatures = None
 
     # -- lifetime ----------------------------------------------------------------
     def close(self):
@@ -77,7 +80,33 @@ class Engine:
         self._md_sig = None
         self._volumes = np.array([abs(np.linalg.det(f.cell)) for f in frames])
         self._natoms = np.array([len(f.species) for f in frames], dtype=np.int64)
+        if self.finite_temperature:
+            # the reference's `etemperature` feature, 0 when the structure has none (universal.py:295)
+            self.set_electron_temperatures([float(a.info.get("etemperature", 0.0)) for a in atoms_list])
         return info
+
+    def set_electron_temperatures(self, temperatures):
+        """Electron temperature (eV) of every resident frame (temperature-dependent models only).
+        `set_frames` takes them from `atoms.info["etemperature"]`; coordinate updates keep them."""
+        T = np.ascontiguousarray(temperatures, dtype=np.float64).ravel()
+        self._check(self._lib.ta_set_electron_temperatures(self._handle, len(T), _lib.as_dp(T)))
+        self._etemperatures = T
+
+    def _td_results(self, out: dict) -> dict:
+        """Temperature-dependent models: `out` holds F (the library's energy, and per atom when
+        fetched); add U as `energy` / `atomic`, F as `free_energy` / `free_energy_atomic` and S as
+        `eentropy` / `eentropy_atomic`."""
+        N, F = int(self.info.n_atoms), int(self.info.n_frames)
+        u, s, ua, sa = np.empty(F), np.empty(F), np.empty(N), np.empty(N)
+        self._check(self._lib.ta_get_td_results(self._handle, _lib.as_dp(u), _lib.as_dp(s), _lib.as_dp(ua),
+                                                _lib.as_dp(sa)))
+        out = dict(out)
+        out["free_energy"] = out["energy"]
+        if out.get("atomic") is not None:
+            out["free_energy_atomic"] = out["atomic"]
+        out["energy"], out["atomic"] = u, ua
+        out["eentropy"], out["eentropy_atomic"] = s, sa
+        return out
 
     def set_nn_tables(self, on: bool):
         """nn pair functions of an EAM / ADP model through the library's Hermite tables (default for
@@ -189,6 +218,8 @@ class Engine:
             out["forces"], out["virial"] = forces, virial
         if want & _lib.TA_WANT_ATOMIC and atomic is not None:
             out["atomic"] = atomic
+        if self.finite_temperature:
+            out = self._td_results(out)
         return out
 
     def list_stats(self):
@@ -243,6 +274,8 @@ class Engine:
         if desc is not None:
             scale = getattr(self._nn, "descriptor_scale", None)
             out["descriptors"] = desc * scale() if scale is not None else desc
+        if self.finite_temperature:
+            out = self._td_results(out)
         return out
 
     def evaluate(self, atoms_list: Sequence, want: int = None, descriptors=False) -> List[dict]:
@@ -261,6 +294,12 @@ class Engine:
             d = {"energy": float(res["energy"][f])}
             if "atomic" in res:
                 d["atomic"] = res["atomic"][a:a + n]
+            for key in ("free_energy", "eentropy"):
+                if key in res:
+                    d[key] = float(res[key][f])
+            for key in ("free_energy_atomic", "eentropy_atomic"):
+                if key in res:
+                    d[key] = res[key][a:a + n]
             if "forces" in res:
                 d["forces"] = res["forces"][a:a + n]
                 w = res["virial"][f]
@@ -290,6 +329,10 @@ class Engine:
         pbc = tuple(bool(x) for x in atoms.pbc) if periodic else (False, False, False)
         sig = (len(atoms), np.asarray(atoms.numbers).tobytes(), pbc)
         cell = np.ascontiguousarray(atoms.get_cell(complete=True), dtype=np.float64).reshape(3, 3)
+        if sig == self._md_sig and self.info is not None and self.finite_temperature:
+            T = float(atoms.info.get("etemperature", 0.0))
+            if self._etemperatures is None or self._etemperatures[0] != T:
+                self.set_electron_temperatures([T])
         if sig == self._md_sig and self.info is not None and not descriptors:
             same_cell = np.array_equal(cell, self._md_cell)
             res = self.step(atoms.positions, want, None if same_cell else cell[None], view=True)

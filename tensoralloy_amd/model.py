@@ -34,6 +34,9 @@ API_VERSION = "1.1"  # reference nn/basic.py:43
 #: properties the reference can export (nn/basic.py:74-92)
 EXPORTABLE_PROPERTIES = ["energy", "eentropy", "free_energy", "atomic", "forces", "stress",
                          "total_pressure", "hessian", "elastic"]
+#: activation codes of the native `.npz` format (atomic.py:323)
+NATIVE_ACTFN = {"relu": 0, "softplus": 1, "tanh": 2, "squareplus": 3}
+
 #: properties this build computes
 SUPPORTED_PROPERTIES = ["energy", "atomic", "forces", "stress", "total_pressure"]
 
@@ -258,7 +261,7 @@ class AtomicNN:
         if not self.weights:
             raise ValueError("The model has no weights: call initialize() or set .weights")
         stem = _model_stem(output_graph_path)
-        props = {"energy": "Output/Energy/energy:0", "energy/atom": "Output/Energy/atomic:0"}
+        props = self._energy_ops()
         want = set(self._export_properties)
         if want & {"forces", "stress", "total_pressure"}:
             props["forces"] = "Output/Forces/forces:0"
@@ -277,18 +280,14 @@ class AtomicNN:
             "Metadata/timestamp": str(datetime.today()),
             "Metadata/precision": self.precision,
             "Metadata/variational_energy": self.variational_energy,
-            "Metadata/is_finite_temperature": 0,
+            "Metadata/is_finite_temperature": int(self.is_finite_temperature),
             "Metadata/api": API_VERSION,
             "Metadata/ops": props,
             "nn": self.as_dict(),
             "weights": os.path.basename(stem) + ".npz",
         }
-        data = {}
+        data = self._weight_arrays()
         for i, el in enumerate(self._elements):
-            for j, (w, b) in enumerate(self.weights[el]):
-                data[f"weights_{i}_{j}"] = np.asarray(w, dtype=np.float64)
-                if b is not None:
-                    data[f"biases_{i}_{j}"] = np.asarray(b, dtype=np.float64)
             if self._minmax_scale:
                 xlo, xhi = self.minmax[el]
                 data[f"xlo_{i}"] = np.asarray(xlo, dtype=np.float64)
@@ -301,6 +300,20 @@ class AtomicNN:
         with open(stem + ".json", "w") as fp:
             json.dump(meta, fp, indent=1)
         return stem + ".json"
+
+    def _energy_ops(self) -> dict:
+        """`Metadata/ops` entries of the energy (basic.py:679-787)."""
+        return {"energy": "Output/Energy/energy:0", "energy/atom": "Output/Energy/atomic:0"}
+
+    def _weight_arrays(self) -> dict:
+        """The network weights as the `.npz` arrays of `export`."""
+        data = {}
+        for i, el in enumerate(self._elements):
+            for j, (w, b) in enumerate(self.weights[el]):
+                data[f"weights_{i}_{j}"] = np.asarray(w, dtype=np.float64)
+                if b is not None:
+                    data[f"biases_{i}_{j}"] = np.asarray(b, dtype=np.float64)
+        return data
 
     def export_to_lammps_native(self, model_path: str, dtype=np.float64):
         """
@@ -315,15 +328,38 @@ class AtomicNN:
             raise ValueError("A transformer must be attached before exporting to a pb file.")
         if self._minmax_scale:
             raise ValueError("the native format has no slot for min-max scaling (atomic.py:360-478)")
-        from .atoms import atomic_masses, atomic_numbers
         sizes = list(self._hidden_sizes[self._elements[0]])
         for el in self._elements[1:]:
             if list(self._hidden_sizes[el]) != sizes:
                 raise ValueError("Layer sizes of all elements must be the same")
         layer_sizes = np.array(sizes + [1], dtype=np.int32)
-        actfn_map = {"relu": 0, "softplus": 1, "tanh": 2, "squareplus": 3}
-        if self._activation.lower() not in actfn_map:
+        if self._activation.lower() not in NATIVE_ACTFN:
             raise ValueError(f"activation '{self._activation}' has no code in the native format")
+        data = self._native_descriptor_data(dtype)
+        data["nlayers"] = np.int32(len(layer_sizes))
+        data["actfn"] = np.int32(NATIVE_ACTFN[self._activation.lower()])
+        data["layer_sizes"] = layer_sizes
+        data["use_resnet_dt"] = np.int32(self._use_resnet_dt)
+        data["apply_output_bias"] = np.int32(self._use_atomic_static_energy)
+        for i, el in enumerate(self._elements):
+            layers = self.weights[el]
+            for j, (w, b) in enumerate(layers[:-1]):
+                data[f"weights_{i}_{j}"] = np.asarray(w, dtype=dtype)
+                data[f"biases_{i}_{j}"] = (np.zeros(np.shape(w)[1], dtype=dtype) if b is None
+                                           else np.asarray(b, dtype=dtype))
+            wo, bo = layers[-1]
+            data[f"weights_{i}_{len(layers) - 1}"] = np.asarray(wo, dtype=dtype).ravel()
+            if self._use_atomic_static_energy:
+                data[f"biases_{i}_{len(layers) - 1}"] = (np.zeros(1, dtype=dtype) if bo is None
+                                                         else np.asarray(bo, dtype=dtype).ravel())
+        np.savez(model_path, **data)
+        return model_path if str(model_path).endswith(".npz") else str(model_path) + ".npz"
+
+    def _native_descriptor_data(self, dtype) -> dict:
+        """Keys of the native `.npz` shared by every model: species, cutoff and the GRAP descriptor
+        (atomic.py:360-448, finite_temperature.py:455-540)."""
+        from .atoms import atomic_masses, atomic_numbers
+        actfn_map = NATIVE_ACTFN
         chars = []
         for el in self._elements:
             chars.extend([ord(el[0]), 0] if len(el) == 1 else [ord(c) for c in el])
@@ -356,27 +392,10 @@ class AtomicNN:
             data["descriptor::method"] = np.int32(method)
             for key, values in algo["parameters"].items():
                 data[f"descriptor::{key}"] = np.array(values, dtype=dtype)
-        data["nlayers"] = np.int32(len(layer_sizes))
         data["max_moment"] = np.int32(gd.max_moment)
-        data["actfn"] = np.int32(actfn_map[self._activation.lower()])
         data["fctype"] = np.int32({"cosine": 0, "polynomial": 1}[gd.cutoff_function])
-        data["layer_sizes"] = layer_sizes
-        data["use_resnet_dt"] = np.int32(self._use_resnet_dt)
-        data["apply_output_bias"] = np.int32(self._use_atomic_static_energy)
         data["is_T_symmetric"] = np.int32(gd.is_T_symmetric)
-        for i, el in enumerate(self._elements):
-            layers = self.weights[el]
-            for j, (w, b) in enumerate(layers[:-1]):
-                data[f"weights_{i}_{j}"] = np.asarray(w, dtype=dtype)
-                data[f"biases_{i}_{j}"] = (np.zeros(np.shape(w)[1], dtype=dtype) if b is None
-                                           else np.asarray(b, dtype=dtype))
-            wo, bo = layers[-1]
-            data[f"weights_{i}_{len(layers) - 1}"] = np.asarray(wo, dtype=dtype).ravel()
-            if self._use_atomic_static_energy:
-                data[f"biases_{i}_{len(layers) - 1}"] = (np.zeros(1, dtype=dtype) if bo is None
-                                                         else np.asarray(bo, dtype=dtype).ravel())
-        np.savez(model_path, **data)
-        return model_path if str(model_path).endswith(".npz") else str(model_path) + ".npz"
+        return data
 
     # -- C ABI -----------------------------------------------------------------
     def to_desc(self):
@@ -413,15 +432,14 @@ class AtomicNN:
         # first layer (or into xlo / xhi when min-max scaling comes first).
         n_rad = D - self.ndim_angular() if nonsym else D
         n_layers, sizes, flat = [], [], []
-        for el in self._elements:
-            layers = self.weights[el]
+        for layers, d_in, first in self._desc_nets(D):
             n_layers.append(len(layers))
-            s = [D]
+            s = [d_in]
             for k, (w, b) in enumerate(layers):
                 w = np.asarray(w, dtype=np.float64)
                 if w.ndim != 2 or w.shape[0] != s[-1]:
                     raise ValueError(f"weight shape {w.shape} does not chain from {s[-1]}")
-                if nonsym and k == 0 and not self._minmax_scale:
+                if first and nonsym and k == 0 and not self._minmax_scale:
                     w = w.copy()
                     w[n_rad:] *= 2.0
                 s.append(w.shape[1])
@@ -462,7 +480,12 @@ class AtomicNN:
         desc.n_eam_params = 0
         desc.eps = 1e-8 if self.precision == "medium" else 1e-14  # precision.py:113-114
         desc.safe_pow = int(self.use_custom_pow)
+        desc.finite_temperature = 0
         return desc, keep
+
+    def _desc_nets(self, D):
+        """(layers, input width, takes the descriptors) of every net of `ta_model_desc`, in order."""
+        return [(self.weights[el], D, True) for el in self._elements]
 
     @property
     def use_custom_pow(self) -> bool:
@@ -651,11 +674,10 @@ def load_lammps_native(path: str):
     from .grap import GenericRadialAtomicPotential
     from .transformer import UniversalTransformer
     npz = np.load(path)
-    if int(npz["tdnp"]) != 0:
-        raise ValueError(f"{path}: temperature-dependent models are not implemented by tensoralloy_amd")
+    td = int(npz["tdnp"]) != 0   # TemperatureDependentAtomicNN (finite_temperature.py:390-650)
     chars = np.asarray(npz["numbers"], dtype=int).reshape(-1, 2)
     elements = ["".join(chr(c) for c in row if c) for row in chars]
-    if int(npz["use_fnn"]) != 0:   # the `nn` filter network: hyper-parameters and weights from fnn::*
+    if "use_fnn" in npz.files and int(npz["use_fnn"]) != 0:   # the `nn` filter network: hyper-parameters and weights from fnn::*
         method = "nn"
         parameters = {"h_abck_modifier": int(npz["fnn::h_abck_modifier"]) if "fnn::h_abck_modifier" in npz.files else 0,
                       "ckpt": str(path)}
@@ -670,15 +692,18 @@ def load_lammps_native(path: str):
         moment_tensors=list(range(max_moment + 1)),
         cutoff_function={0: "cosine", 1: "polynomial"}[int(npz["fctype"])],
         symmetric=bool(int(npz["is_T_symmetric"])), legacy_mode=False)
+    actfn = {v: k for k, v in NATIVE_ACTFN.items()}
+    clf = UniversalTransformer(elements, rcut=float(npz["rmax"]), angular=False)
+    order = sorted(range(len(elements)), key=lambda i: elements[i])  # the file's own element order
+    if td:
+        return _load_native_td(path, npz, elements, gd, clf, order, actfn)
     layer_sizes = [int(x) for x in np.atleast_1d(npz["layer_sizes"])]
-    activation = {0: "relu", 1: "softplus", 2: "tanh", 3: "squareplus"}[int(npz["actfn"])]
+    activation = actfn[int(npz["actfn"])]
     bias_out = bool(int(npz["apply_output_bias"]))
     nn = AtomicNN(elements, gd, hidden_sizes=layer_sizes[:-1], activation=activation, minmax_scale=False,
                   use_resnet_dt=bool(int(npz["use_resnet_dt"])), use_atomic_static_energy=bias_out,
                   export_properties=("energy", "forces", "stress"))
-    clf = UniversalTransformer(elements, rcut=float(npz["rmax"]), angular=False)
     nn.attach_transformer(clf)
-    order = sorted(range(len(elements)), key=lambda i: elements[i])  # the file's own element order
     L = len(layer_sizes)
     for i in order:
         layers = []
@@ -701,6 +726,50 @@ def load_lammps_native(path: str):
     return nn, clf, meta
 
 
+def _native_ops(energy_ops=None):
+    """`Metadata/ops` of a model read from the native `.npz`."""
+    return {"energy": "Output/Energy/energy:0", "energy/atom": "Output/Energy/atomic:0",
+            "forces": "Output/Forces/forces:0", "stress": "Output/Stress/Voigt/stress:0",
+            "virial": "Output/Stress/Full/virial:0", "total_pressure": "Output/Stress/pressure/GPa:0",
+            **(energy_ops or {})}
+
+
+def _load_native_td(path, npz, elements, gd, clf, order, actfn):
+    """The TD branch of `load_lammps_native`: nets H, U, S from the `H::`, `U::`, `S::` keys."""
+    from .td import NETS, TemperatureDependentAtomicNN
+    u_sizes = [int(x) for x in np.atleast_1d(npz["U::layer_sizes"])]
+    ft = {"activation": actfn[int(npz["H::actfn"])],
+          "layers": [int(x) for x in np.atleast_1d(npz["H::layer_sizes"])],
+          "algo": "Sommerfeld" if int(npz["tdnp::Sommerfeld"]) else "default"}
+    nn = TemperatureDependentAtomicNN(
+        elements, gd, hidden_sizes=u_sizes[:-1], activation=actfn[int(npz["U::actfn"])], minmax_scale=False,
+        use_resnet_dt=bool(int(npz["H::use_resnet_dt"])),
+        use_atomic_static_energy=bool(int(npz["U::apply_output_bias"])),
+        export_properties=("energy", "forces", "stress"), finite_temperature=ft)
+    nn.attach_transformer(clf)
+    for i in order:
+        nets = {}
+        for net in NETS:
+            L = int(npz[f"{net}::nlayers"])
+            bias_out = bool(int(npz[f"{net}::apply_output_bias"]))
+            layers = []
+            for j in range(L):
+                w = np.array(npz[f"{net}::weights_{i}_{j}"], dtype=np.float64)
+                if w.ndim == 1:   # squeezed kernels: [in] of a scalar output, [out] of a scalar input
+                    w = w.reshape(-1, 1) if j == L - 1 and net != "H" else w.reshape(1, -1)
+                b = (np.array(npz[f"{net}::biases_{i}_{j}"], dtype=np.float64).ravel()
+                     if j < L - 1 or bias_out else None)
+                layers.append((w, b))
+            nets[net] = layers
+        nn.weights[elements[i]] = nets
+    nn.precision = "high" if int(npz["precision"]) == 64 else "medium"
+    meta = {"format": "tensoralloy/native-npz", "Transformer/params": clf.as_dict(),
+            "Metadata/precision": nn.precision, "Metadata/api": API_VERSION,
+            "Metadata/variational_energy": "free_energy", "Metadata/is_finite_temperature": 1,
+            "Metadata/ops": _native_ops(nn._energy_ops()), "nn": nn.as_dict()}
+    return nn, clf, meta
+
+
 def load_model(graph_model_path: str):
     """
     Read a model written by `AtomicNN.export` (or `EamAlloyNN.export`), or a native `.npz` written by
@@ -711,7 +780,7 @@ def load_model(graph_model_path: str):
     path = str(graph_model_path)
     if path.endswith(".npz") and os.path.exists(path):
         with np.load(path) as probe:
-            native = "descriptor::method" in probe.files or "use_fnn" in probe.files
+            native = "descriptor::method" in probe.files or "use_fnn" in probe.files or "tdnp" in probe.files
         if native:
             return load_lammps_native(path)
     if path.endswith(".pb") or path.endswith(".pb.gz"):
@@ -760,6 +829,23 @@ def load_model(graph_model_path: str):
                 j += 1
             if not layers:
                 raise ValueError(f"{stem}.npz holds no weights of the GRAP filter network")
+            nn.descriptor.filter_weights = layers
+    elif nn_cls == "TemperatureDependentAtomicNN":
+        from .td import TemperatureDependentAtomicNN
+        nn = TemperatureDependentAtomicNN(**cfg)
+        nn.attach_transformer(clf)
+        npz = np.load(os.path.join(os.path.dirname(stem) or ".", meta["weights"]))
+        nn.set_weight_arrays(npz)
+        for i, el in enumerate(nn.elements):
+            if nn._minmax_scale:
+                nn.minmax[el] = (np.array(npz[f"xlo_{i}"]), np.array(npz[f"xhi_{i}"]))
+        if getattr(getattr(nn.descriptor, "algorithm", None), "name", "") == "nn":
+            layers, j = [], 0
+            while f"fnn::weights_0_{j}" in npz:
+                b = np.array(npz[f"fnn::biases_0_{j}"], dtype=np.float64).ravel() \
+                    if f"fnn::biases_0_{j}" in npz else None
+                layers.append((np.array(npz[f"fnn::weights_0_{j}"], dtype=np.float64), b))
+                j += 1
             nn.descriptor.filter_weights = layers
     elif nn_cls in ("EamAlloyNN", "AdpNN", "EamFsNN"):
         from .eam import nn_from_dict
