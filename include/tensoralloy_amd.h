@@ -159,8 +159,10 @@ typedef struct {
    * `xlo` / `xhi`) descriptors to K features (linear output layer with bias); U and S map
    * z = [H, T] (K + 1 inputs, T = the frame's electron temperature in eV) to one output with
    * `activation`. Per atom F = U - T S is the energy whose forces and virial are computed; U and S
-   * come from ta_get_td_results. Inference only: ta_param_count, ta_update_weights,
-   * ta_energy_gradient, ta_loss_gradient and ta_hessian_vectors return TA_ERR_UNSUPPORTED. */
+   * come from ta_get_td_results. Trainable: the parameter vector of ta_param_count /
+   * ta_update_weights is H of every element, then U, then S, in that net order; ta_td_loss_gradient
+   * differentiates a loss of U, F and S and the forces and stress of F; ta_energy_gradient and
+   * ta_loss_gradient take their coefficients as dL/dF. ta_hessian_vectors returns TA_ERR_UNSUPPORTED. */
   int32_t finite_temperature;
 } ta_model_desc;
 
@@ -363,6 +365,20 @@ int ta_energy_gradient(ta_handle h, const double *frame_coeff, double *grad, int
  * ta_energy_gradient on displaced frames instead). */
 int ta_loss_gradient(ta_handle h, const double *frame_coeff, const double *dR, const double *dh,
                      double *grad, int64_t n_grad, double *dG_out);
+
+/* The loss gradient of a temperature-dependent model (ta_model_desc.finite_temperature), whose loss
+ * has three energy terms (finite_temperature.py:358-388): with per-frame coefficients
+ * b = coeff_free_energy (dL/dF_f), a = coeff_energy (dL/dU_f), g = coeff_eentropy (dL/dS_f) and the
+ * force / stress direction (dR, dh) of F, built as for ta_loss_gradient,
+ *     grad = d/dtheta ( sum_f (a U_f + b F_f + g S_f)  +  D_delta F ).
+ * One second-order pass per 16-atom tile through H, U and S (ta_td_train.hip). Any coefficient array
+ * and the direction may be NULL (= 0); dG_out as for ta_loss_gradient (needs a direction). Returns
+ * TA_ERR_INVALID for a model that is not temperature-dependent, and TA_ERR_UNSUPPORTED for a direction
+ * on a skin-filtered batch. On such a model ta_energy_gradient(h, c, ...) and
+ * ta_loss_gradient(h, c, dR, dh, ...) are this call with b = c and a = g = NULL. */
+int ta_td_loss_gradient(ta_handle h, const double *coeff_free_energy, const double *coeff_energy,
+                        const double *coeff_eentropy, const double *dR, const double *dh, double *grad,
+                        int64_t n_grad, double *dG_out);
 
 /* Constants of the analytic functions of an EAM model as trainable parameters. The reference makes
  * every constant of its empirical potentials a tf.Variable (potentials/potentials.py:129-163;

@@ -20,7 +20,8 @@ INCLUDE_DIR = REPO_DIR / "include"
 LIB_PATH = PKG_DIR / "libtensoralloy_amd.so"
 
 SOURCES = ["ta_api.hip", "ta_kernels.hip", "ta_kernels_v2.hip", "ta_mlp.hip", "ta_eam.hip",
-           "ta_nlist.hip", "ta_grap.hip", "ta_train.hip", "ta_hvp.hip", "ta_neighbor.cpp", "ta_td.hip"]
+           "ta_nlist.hip", "ta_grap.hip", "ta_train.hip", "ta_hvp.hip", "ta_neighbor.cpp", "ta_td.hip",
+           "ta_td_train.hip"]
 OBJ_DIR = CSRC_DIR / "build"
 
 TA_OK = 0
@@ -47,7 +48,7 @@ EXPORTED_SYMBOLS = [
     "ta_energy_gradient", "ta_measure_hbm_copy", "ta_set_skin", "ta_update_positions", "ta_list_stats",
     "ta_count_contributing_triples", "ta_loss_gradient", "ta_constant_count", "ta_get_constants", "ta_update_constants",
     "ta_constant_gradient", "ta_list_sizes", "ta_abi_version", "ta_model_desc_size", "ta_set_nn_tables", "ta_step", "ta_hessian_vectors", "ta_view_results", "ta_step_view",
-    "ta_set_electron_temperatures", "ta_get_td_results",
+    "ta_set_electron_temperatures", "ta_get_td_results", "ta_td_loss_gradient",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -207,6 +208,7 @@ def load():
     lib.ta_update_weights.argtypes = [H, _dp, C.c_int64]
     lib.ta_energy_gradient.argtypes = [H, _dp, _dp, C.c_int64]
     lib.ta_loss_gradient.argtypes = [H, _dp, _dp, _dp, _dp, C.c_int64, _dp]
+    lib.ta_td_loss_gradient.argtypes = [H, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int64, _dp]
     lib.ta_constant_count.argtypes = [H, C.POINTER(C.c_int64)]
     lib.ta_get_constants.argtypes = [H, _dp, C.c_int64]
     lib.ta_update_constants.argtypes = [H, _dp, C.c_int64]

@@ -38,6 +38,13 @@ size_t mlp_grad2_scratch_doubles(const MlpDev &mlp, int n_atoms);
 void launch_mlp_grad2(const MlpDev &mlp, int activation, int ndim, const int32_t *atoms, int n_atoms,
                       const DeviceBatch &b, const double *dG, const double *frame_coeff, double *scratch,
                       double *partial, double *grad, hipStream_t s, double *kappa_out = nullptr);
+// weight gradients of the temperature-dependent head (ta_td_train.hip)
+int td_param_count(const MlpDev *nets, int nel);
+void td_grad2_sizes(const MlpDev *nets, int nel, int K, const int32_t *elem_start, size_t *scratch,
+                    size_t *partial);
+void launch_td_grad2(const MlpDev *nets_dev, const MlpDev *nets_host, int nel, int K, int act_h, int act,
+                     int sommerfeld, int ndim, const DeviceBatch &b, const double *T, const double *dG,
+                     const double *coeff, double *scratch, double *partial, double *grad, hipStream_t s);
 // analytic Hessian-vector products of the descriptor models (ta_hvp.hip)
 void launch_pair_vec(const DeviceBatch &b, double *Dv, hipStream_t s);
 void launch_backward_hvp(const SFParams &sf, const AngChunk &ch, int nb, int ng, int nz, bool first, bool angular,
@@ -315,10 +322,10 @@ int fail(ta_context *h, int code, const std::string &msg) {
   return code;
 }
 
-// temperature-dependent models evaluate energies, forces and virials only
+// temperature-dependent models have no analytic Hessian-vector products
 std::string td_inference_only(const char *fn) {
   return std::string(fn) + ": not available for finite-temperature (temperature-dependent) models "
-         "(inference only: no weight or loss gradients and no analytic Hessian-vector products)";
+         "(no analytic Hessian-vector products)";
 }
 
 // eam/fs models evaluate energies, forces and virials only
@@ -1855,7 +1862,10 @@ int ta_copy_batch_energy(ta_handle h, void *dst_device) {
 
 int ta_param_count(ta_handle h, int64_t *n_params) {
   if (!h || !n_params) return TA_ERR_INVALID;
-  if (h->td) return fail(h, TA_ERR_UNSUPPORTED, td_inference_only("ta_param_count"));
+  if (h->td) {  // H of every element, then U, then S
+    *n_params = ta::td_param_count(h->td_nets, h->n_elements);
+    return TA_OK;
+  }
   if (h->eam) {  // the nn functions of an EAM / ADP model, slot after slot
     *n_params = ta::eam_param_count(h->eam);
     return TA_OK;
@@ -1868,9 +1878,40 @@ int ta_param_count(ta_handle h, int64_t *n_params) {
   return TA_OK;
 }
 
+namespace {
+// one network's weights from the flat layout (per layer W[k][n] then b[n]) into its padded device copies,
+// both orientations; `src` advances past them
+void upload_net_weights(ta::MlpDev &md, const double *&src) {
+  for (int l = 0; l < md.n_layers; ++l) {
+    ta::MlpLayerDev &ly = md.layer[l];
+    std::vector<double> w((size_t)ly.kp * ly.np, 0.0), wt((size_t)ly.np * ly.kp, 0.0), bb(ly.np, 0.0);
+    for (int k = 0; k < ly.k; ++k)
+      for (int n = 0; n < ly.n; ++n) {
+        const double v = src[(size_t)k * ly.n + n];
+        w[(size_t)k * ly.np + n] = v;
+        wt[(size_t)n * ly.kp + k] = v;
+      }
+    src += (size_t)ly.k * ly.n;
+    for (int n = 0; n < ly.n; ++n) bb[n] = src[n];
+    src += ly.n;
+    HIP_CHECK(hipMemcpy(ly.w, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(ly.wt, wt.data(), wt.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(ly.b, bb.data(), bb.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+}
+}  // namespace
+
 int ta_update_weights(ta_handle h, const double *weights, int64_t n_weights) {
   if (!h || !weights) return TA_ERR_INVALID;
-  if (h->td) return fail(h, TA_ERR_UNSUPPORTED, td_inference_only("ta_update_weights"));
+  if (h->td)  // in place: the device copy of the net descriptions (td_dev) keeps its pointers
+    return guarded(h, [&]() {
+      const int64_t want = ta::td_param_count(h->td_nets, h->n_elements);
+      if (n_weights != want)
+        throw std::invalid_argument("ta_update_weights: expected " + std::to_string(want) + " values");
+      HIP_CHECK(hipStreamSynchronize(h->stream));  // nothing may still read the old weights
+      const double *src = weights;
+      for (int j = 0; j < 3 * h->n_elements; ++j) upload_net_weights(h->td_nets[j], src);
+    });
   if (h->eam)
     return guarded(h, [&]() {
       HIP_CHECK(hipStreamSynchronize(h->stream));  // nothing may still read the old weights
@@ -1885,31 +1926,14 @@ int ta_update_weights(ta_handle h, const double *weights, int64_t n_weights) {
       throw std::invalid_argument("ta_update_weights: expected " + std::to_string(want) + " values");
     HIP_CHECK(hipStreamSynchronize(h->stream));  // nothing may still read the old weights
     const double *src = weights;
-    for (int e = 0; e < h->n_elements; ++e) {
-      ta::MlpDev &md = h->mlp[e];
-      for (int l = 0; l < md.n_layers; ++l) {
-        ta::MlpLayerDev &ly = md.layer[l];
-        std::vector<double> w((size_t)ly.kp * ly.np, 0.0), wt((size_t)ly.np * ly.kp, 0.0), bb(ly.np, 0.0);
-        for (int k = 0; k < ly.k; ++k)
-          for (int n = 0; n < ly.n; ++n) {
-            const double v = src[(size_t)k * ly.n + n];
-            w[(size_t)k * ly.np + n] = v;
-            wt[(size_t)n * ly.kp + k] = v;
-          }
-        src += (size_t)ly.k * ly.n;
-        for (int n = 0; n < ly.n; ++n) bb[n] = src[n];
-        src += ly.n;
-        HIP_CHECK(hipMemcpy(ly.w, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(ly.wt, wt.data(), wt.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(ly.b, bb.data(), bb.size() * sizeof(double), hipMemcpyHostToDevice));
-      }
-    }
+    for (int e = 0; e < h->n_elements; ++e) upload_net_weights(h->mlp[e], src);
   });
 }
 
 int ta_energy_gradient(ta_handle h, const double *frame_coeff, double *grad, int64_t n_grad) {
   if (!h || !frame_coeff || !grad) return TA_ERR_INVALID;
-  if (h->td) return fail(h, TA_ERR_UNSUPPORTED, td_inference_only("ta_energy_gradient"));
+  if (h->td)  // frame_coeff = dL/dF_f
+    return ta_td_loss_gradient(h, frame_coeff, nullptr, nullptr, nullptr, nullptr, grad, n_grad, nullptr);
   if (h->kind == TA_MODEL_EAM_FS) return fail(h, TA_ERR_INVALID, fs_inference_only("ta_energy_gradient"));
   if (!h->have_batch) return fail(h, TA_ERR_INVALID, "no resident batch");
   if (h->eam)
@@ -2028,7 +2052,10 @@ void ensure_pair_jacobians(ta_context *h) {
 int ta_loss_gradient(ta_handle h, const double *frame_coeff, const double *dR, const double *dh, double *grad,
                      int64_t n_grad, double *dG_out) {
   if (!h || !grad) return TA_ERR_INVALID;
-  if (h->td) return fail(h, TA_ERR_UNSUPPORTED, td_inference_only("ta_loss_gradient"));
+  if (h->td) {  // frame_coeff = dL/dF_f, the direction that of F
+    if (!frame_coeff && !dR && !dh) return fail(h, TA_ERR_INVALID, "nothing to differentiate");
+    return ta_td_loss_gradient(h, frame_coeff, nullptr, nullptr, dR, dh, grad, n_grad, dG_out);
+  }
   if (h->kind == TA_MODEL_EAM_FS) return fail(h, TA_ERR_INVALID, fs_inference_only("ta_loss_gradient"));
   if (!h->have_batch) return fail(h, TA_ERR_INVALID, "no resident batch");
   if (!dR && !dh) {
@@ -2119,6 +2146,65 @@ int ta_loss_gradient(ta_handle h, const double *frame_coeff, const double *dR, c
                            h->train_partial.ptr, h->train_grad.ptr + off, s);
       off += (size_t)ta::mlp_param_count(h->mlp[e]);
     }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(grad, h->train_grad.ptr, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (dG_out && N)
+      HIP_CHECK(hipMemcpyAsync(dG_out, h->tan_dG.ptr, N * (size_t)D * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  });
+}
+
+int ta_td_loss_gradient(ta_handle h, const double *coeff_free_energy, const double *coeff_energy,
+                        const double *coeff_eentropy, const double *dR, const double *dh, double *grad,
+                        int64_t n_grad, double *dG_out) {
+  if (!h || !grad) return TA_ERR_INVALID;
+  if (!h->td) return fail(h, TA_ERR_INVALID, "ta_td_loss_gradient: not a temperature-dependent model");
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "no resident batch");
+  const bool direction = dR || dh;
+  // the per-pair buffers of the direction follow the resident list (see ta_loss_gradient)
+  if (direction && h->filtered)
+    return fail(h, TA_ERR_UNSUPPORTED, "ta_td_loss_gradient: not available on a skin-filtered batch; "
+                                       "ta_set_skin(h, 0) and ta_set_frames first");
+  return guarded(h, [&]() {
+    const int nel = h->n_elements;
+    const int64_t total = ta::td_param_count(h->td_nets, nel);
+    if (n_grad != total)
+      throw std::invalid_argument("ta_td_loss_gradient: expected room for " + std::to_string(total) + " values");
+    if (dG_out && !direction) throw std::invalid_argument("ta_td_loss_gradient: dG_out needs a direction");
+    hipStream_t s = h->stream;
+    const size_t N = (size_t)h->db.n_atoms, P = (size_t)h->db.n_pairs, F = (size_t)h->db.n_frames;
+    const int D = h->sf.ndim;
+    if (direction) {
+      ensure_pair_jacobians(h);
+      h->tan_dir.ensure(3 * N + 9 * F + 8);
+      h->tan_dD.ensure(4 * P + 8);
+      h->tan_dG.ensure(N * (size_t)D + 8);
+      double *d_dR = h->tan_dir.ptr, *d_dh = h->tan_dir.ptr + 3 * N;
+      if (dR) HIP_CHECK(hipMemcpyAsync(d_dR, dR, 3 * N * sizeof(double), hipMemcpyHostToDevice, s));
+      else HIP_CHECK(hipMemsetAsync(d_dR, 0, 3 * N * sizeof(double), s));
+      if (dh) HIP_CHECK(hipMemcpyAsync(d_dh, dh, 9 * F * sizeof(double), hipMemcpyHostToDevice, s));
+      else HIP_CHECK(hipMemsetAsync(d_dh, 0, 9 * F * sizeof(double), s));
+      ta::launch_pair_tangent(h->db, d_dR, d_dh, h->tan_dD.ptr, s);
+      ta::launch_descriptor_jvp(h->db, D, h->jvp_J.ptr, h->tan_dD.ptr, h->tan_dG.ptr, s);
+    } else if (!h->descriptors_valid) {
+      compute_impl(h, TA_WANT_ENERGY, false, nullptr);  // descriptors do not depend on the weights: once per batch
+    }
+    size_t scratch = 0, partial = 0;
+    ta::td_grad2_sizes(h->td_nets, nel, h->td_K, h->db.elem_start, &scratch, &partial);
+    h->train_scratch.ensure(scratch + 8);
+    h->train_partial.ensure(partial + 8);
+    h->train_grad.ensure((size_t)total + 8);
+    h->train_coeff.ensure(3 * F + 8);
+    // [a | b | g]: dL/dU_f, dL/dF_f, dL/dS_f; NULL = 0
+    const double *host_coeff[3] = {coeff_energy, coeff_free_energy, coeff_eentropy};
+    for (int q = 0; q < 3 && F; ++q) {
+      double *dst = h->train_coeff.ptr + q * F;
+      if (host_coeff[q]) HIP_CHECK(hipMemcpyAsync(dst, host_coeff[q], F * sizeof(double), hipMemcpyHostToDevice, s));
+      else HIP_CHECK(hipMemsetAsync(dst, 0, F * sizeof(double), s));
+    }
+    ta::launch_td_grad2(h->td_dev, h->td_nets, nel, h->td_K, h->td_act, h->activation, h->td_sommerfeld ? 1 : 0, D,
+                        h->db, h->td_T.ptr, direction ? h->tan_dG.ptr : nullptr, h->train_coeff.ptr,
+                        h->train_scratch.ptr, h->train_partial.ptr, h->train_grad.ptr, s);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(grad, h->train_grad.ptr, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, s));
     if (dG_out && N)

@@ -467,6 +467,12 @@ void launch_mlp_grad2(const MlpDev &mlp, int activation, int ndim, const int32_t
                      dim3(kThreads), 0, s, partial, blocks, lay.n_params, grad);
 }
 
+// grad = the fixed-order sum of `n_blocks` partial slices (the TD weight gradient, ta_td_train.hip)
+void launch_grad_reduce(const double *partial, int n_blocks, int n_params, double *grad, hipStream_t s) {
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((n_params + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
+                     partial, n_blocks, n_params, grad);
+}
+
 void launch_pair_tangent(const DeviceBatch &b, const double *dR, const double *dh, double *dD, hipStream_t s) {
   if (b.n_pairs == 0) return;
   hipLaunchKernelGGL(pair_tangent_kernel, dim3((unsigned)((b.n_pairs + kThreads - 1) / kThreads)), dim3(kThreads),

@@ -423,6 +423,35 @@ class Engine:
             return grad, (tangent * scale() if scale is not None else tangent)
         return grad
 
+    def td_loss_gradient(self, coeff_free_energy=None, coeff_energy=None, coeff_eentropy=None, dR=None, dh=None,
+                         return_tangent=False):
+        """Temperature-dependent models: d/dtheta (sum_f (a_f U_f + b_f F_f + g_f S_f) + D_delta F) for the
+        resident batch, b = `coeff_free_energy`, a = `coeff_energy`, g = `coeff_eentropy` (one per frame,
+        None = 0) and delta = (dR, dh) the force / stress direction of F as in `loss_gradient`
+        (`ta_td_loss_gradient`); flat parameter layout (H, U, S nets). `return_tangent` (needs a
+        direction) also returns the directional derivative of the raw descriptors [N, D]."""
+        null = C.POINTER(C.c_double)()
+        N, F = int(self.info.n_atoms), int(self.info.n_frames)
+
+        def arr(a, shape):
+            if a is None:
+                return None, null
+            a = np.ascontiguousarray(a, dtype=np.float64).reshape(shape)
+            return a, _lib.as_dp(a)
+        b, bp = arr(coeff_free_energy, (F,))
+        a, ap = arr(coeff_energy, (F,))
+        g, gp = arr(coeff_eentropy, (F,))
+        r, rp = arr(dR, (N, 3))
+        hh, hp = arr(dh, (F, 9))
+        grad = np.zeros(self.param_count())
+        tangent = np.zeros((N, int(self.info.descriptor_dim))) if return_tangent else None
+        self._check(self._lib.ta_td_loss_gradient(self._handle, bp, ap, gp, rp, hp, _lib.as_dp(grad), len(grad),
+                                                  _lib.as_dp(tangent) if return_tangent else null))
+        if return_tangent:
+            scale = getattr(self._nn, "descriptor_scale", None)
+            return grad, (tangent * scale() if scale is not None else tangent)
+        return grad
+
     # -- constants of the analytic EAM functions as parameters (potentials.py:129-163) ---------
     def constant_count(self) -> int:
         n = C.c_int64(0)

@@ -9,7 +9,8 @@ For atom i of element e in a frame of electron temperature T (eV): H = H_e(minma
 U_i = U_e(z), s_i = S_e(z) (hidden sizes `hidden_sizes[e]`, model activation; S always has an output
 bias, U has one iff `use_atomic_static_energy`), S_i = s_i T for algo "Sommerfeld" else s_i, and
 F_i = U_i - T S_i. Forces, stress and pressure derive from F (`variational_energy == "free_energy"`,
-basic.py:186-201). All arithmetic happens in the HIP library (csrc/ta_td.hip); inference only.
+basic.py:186-201). All arithmetic happens in the HIP library: inference in csrc/ta_td.hip, the loss
+gradient of training (`train.Trainer`, `Engine.td_loss_gradient`) in csrc/ta_td_train.hip.
 """
 from __future__ import annotations
 

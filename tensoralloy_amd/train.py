@@ -21,12 +21,24 @@ import numpy as np
 from .parallel import shard_range, world_from_env
 
 
+def _is_td(nn) -> bool:
+    return bool(getattr(nn, "is_finite_temperature", False))
+
+
+def _td_nets():
+    from .td import NETS
+    return NETS
+
+
 def _networks(nn):
     """The model's networks in the order of the C ABI's parameter vector, as (container, key):
     per element for an `AtomicNN`; per nn-function slot (rho[element], embed[element], phi[pair],
-    dipole[pair], quadrupole[pair]) for an `EamAlloyNN` / `AdpNN`."""
+    dipole[pair], quadrupole[pair]) for an `EamAlloyNN` / `AdpNN`; H of every element, then U, then
+    S for a `TemperatureDependentAtomicNN` (`td._desc_nets`)."""
     if hasattr(nn, "nn_functions"):
         return [(nn.weights[sec], fn) for sec, fn in (s for s in nn.nn_functions() if s is not None)]
+    if _is_td(nn):
+        return [(nn.weights[el], net) for net in _td_nets() for el in nn.elements]
     return [(nn.weights, el) for el in nn.elements]
 
 
@@ -47,7 +59,12 @@ def unflatten_weights(nn, flat: np.ndarray) -> Dict[str, List]:
     flat = np.asarray(flat, dtype=np.float64)
     out, k = {}, 0
     eam = hasattr(nn, "nn_functions")
-    names = [s for s in nn.nn_functions() if s is not None] if eam else [(None, el) for el in nn.elements]
+    if eam:
+        names = [s for s in nn.nn_functions() if s is not None]
+    elif _is_td(nn):   # {element: {"H" | "U" | "S": layers}}
+        names = [(el, None) for net in _td_nets() for el in nn.elements]
+    else:
+        names = [(None, el) for el in nn.elements]
     for (box, key), (sec, _) in zip(_networks(nn), names):
         layers = []
         for w, b in box[key]:
@@ -58,7 +75,7 @@ def unflatten_weights(nn, flat: np.ndarray) -> Dict[str, List]:
             b2 = None if b is None else flat[k:k + shape[1]].copy()
             k += shape[1]
             layers.append((w2, b2))
-        if eam:
+        if eam or sec is not None:
             out.setdefault(sec, {})[key] = layers
         else:
             out[key] = layers
@@ -69,8 +86,10 @@ def trainable_mask(nn) -> np.ndarray:
     """1 for real parameters, 0 for the bias slots of layers that have no bias and, when the model
     was built with `fixed_atomic_static_energy=True`, for every element's output bias: the
     reference creates that bias with `trainable=False` (atomic.py:249 -> `convolution1x1(...,
-    fixed_output_bias=True)`, convolutional.py:277-290), so the atomic static energies stay put."""
-    frozen_output_bias = bool(getattr(nn, "_fixed_atomic_static_energy", False))
+    fixed_output_bias=True)`, convolutional.py:277-290), so the atomic static energies stay put.
+    A temperature-dependent model freezes no output bias: none of the reference's three
+    `convolution1x1` calls passes `fixed_output_bias` (finite_temperature.py:120-209)."""
+    frozen_output_bias = bool(getattr(nn, "_fixed_atomic_static_energy", False)) and not _is_td(nn)
     out = []
     for box, key in _networks(nn):
         layers = box[key]
@@ -165,6 +184,9 @@ class EnergyTrainer:
     def __init__(self, nn, frames: Sequence, energies: Sequence[float], device=None, method="rmse",
                  per_atom_loss=True, loss_weight=1.0, learning_rate=0.01, **adam_kwargs):
         from .engine import Engine
+        if _is_td(nn):
+            raise ValueError("EnergyTrainer fits one energy; a temperature-dependent model has three "
+                             "(U, F, S): use Trainer")
         rank, local_rank, world = world_from_env()
         lo, hi = shard_range(len(frames), rank, world)
         self.nn = nn
@@ -304,7 +326,9 @@ def l2_regularization_loss(nn, theta, l2_weight, weight=0.01, step=0, decayed=Tr
     (convolutional.py:207-290): `l2_regularizer(l2_weight)` = l2_weight sum(w^2) / 2 on the kernel AND
     the bias of every hidden layer and on the kernel (not the bias) of the output layer; the sum is
     scaled by `weight`, exponentially decayed as weight * decay_rate ** (step / decay_steps) when
-    `decayed` (tf.train.exponential_decay, no staircase). `theta` in the C ABI's flat layout."""
+    `decayed` (tf.train.exponential_decay, no staircase). `theta` in the C ABI's flat layout. A
+    temperature-dependent model's H, U and S nets all carry `l2_weight` (finite_temperature.py:120-209,
+    255-300), under the same rule."""
     theta = np.asarray(theta, dtype=np.float64)
     sel = np.zeros_like(theta)
     k = 0
@@ -356,6 +380,12 @@ class Trainer:
     second-order pass per network (`ta_loss_gradient` again), ADP's dipole and quadrupole networks
     included. `analytic=False` forces the central difference of g = dE/dtheta on two displaced copies of
     every frame everywhere (step `fd_step` Angstrom, error O(step^2)).
+
+    A temperature-dependent model (finite_temperature.py:358-388) has three energy terms: `energies`
+    are the labels of U (the reference's `energy`, may be None), `free_energies` those of F and
+    `eentropies` those of S, each an `energy_loss` with `method` / `per_atom_loss` and its own weight.
+    Forces, stress and pressure are those of F; each frame's electron temperature is
+    `atoms.info["etemperature"]`. The analytic gradient is one `ta_td_loss_gradient` call.
     """
 
     def __init__(self, nn, frames, energies, forces=None, stresses=None, device=None,
@@ -363,8 +393,19 @@ class Trainer:
                  per_atom_loss=True, learning_rate=0.01, fd_step=1e-3, analytic=None, fixed=None,
                  pressures=None, pressure_weight=1.0, forces_method=None, l2_weight=0.0, l2_loss_weight=0.01,
                  l2_decayed=True, l2_decay_rate=0.99, l2_decay_steps=1000, max_train_steps=None,
-                 logscaled_dynamic_weight=True, train_constants=None, **adam_kwargs):
+                 logscaled_dynamic_weight=True, train_constants=None, free_energies=None, eentropies=None,
+                 free_energy_weight=1.0, eentropy_weight=1.0, **adam_kwargs):
         from .engine import Engine
+        self.td = _is_td(nn)
+        if not self.td and (free_energies is not None or eentropies is not None):
+            raise ValueError("free_energies / eentropies are labels of temperature-dependent models")
+        if self.td:
+            labels = {"energies": energies, "free_energies": free_energies, "eentropies": eentropies}
+            if all(v is None for v in labels.values()):
+                raise ValueError("a temperature-dependent model needs energies, free_energies or eentropies")
+            for name, v in labels.items():
+                if v is not None and len(v) != len(frames):
+                    raise ValueError(f"{name}: one label per frame ({len(frames)}), got {len(v)}")
         rank, local_rank, world = world_from_env()
         lo, hi = shard_range(len(frames), rank, world)
         self.nn = nn
@@ -386,7 +427,10 @@ class Trainer:
         self._resident = False
         self._generation = -1
         self.frames = list(frames[lo:hi])
-        self.e_ref = np.asarray(energies, dtype=np.float64)[lo:hi]
+        self.e_ref = None if (self.td and energies is None) else np.asarray(energies, dtype=np.float64)[lo:hi]
+        self.fe_ref = None if free_energies is None else np.asarray(free_energies, dtype=np.float64)[lo:hi]
+        self.es_ref = None if eentropies is None else np.asarray(eentropies, dtype=np.float64)[lo:hi]
+        self.td_weights = (free_energy_weight, eentropy_weight)
         self.f_ref = None if forces is None else [np.asarray(f, dtype=np.float64) for f in forces[lo:hi]]
         self.s_ref = None if stresses is None else np.asarray(stresses, dtype=np.float64).reshape(-1, 6)[lo:hi]
         self.n_atoms = np.array([len(a) for a in self.frames], dtype=np.float64)
@@ -436,9 +480,23 @@ class Trainer:
         we, wf, ws = (loss_weight_at(w, step, self.max_train_steps, self.logscale) for w in self.weights)
         wp = loss_weight_at(self.pressure_weight, step, self.max_train_steps, self.logscale)
         terms = {}
-        loss_e, mae_e, c = energy_loss(pred_e, self.e_ref, self.n_atoms, self.method, self.per_atom_loss, we)
-        terms["energy"] = loss_e
-        if not self.analytic:
+        if self.td:
+            # U (`energy`), F (`free_energy`) and S (`eentropy`) terms; c = dL/dF drives the forces' terms
+            wfe, wse = (loss_weight_at(w, step, self.max_train_steps, self.logscale) for w in self.td_weights)
+            td_coeff = {}
+            for key, ref, w in (("energy", self.e_ref, we), ("free_energy", self.fe_ref, wfe),
+                                ("eentropy", self.es_ref, wse)):
+                if ref is not None:
+                    pred = pred_e if key == "energy" else np.array([r[key] for r in res])
+                    terms[key], _, td_coeff[key] = energy_loss(pred, ref, self.n_atoms, self.method,
+                                                               self.per_atom_loss, w)
+            c = td_coeff.get("free_energy")
+            if not self.analytic:   # the energy terms alone, on the undisplaced batch
+                grad = eng.td_loss_gradient(c, td_coeff.get("energy"), td_coeff.get("eentropy"))
+        else:
+            loss_e, mae_e, c = energy_loss(pred_e, self.e_ref, self.n_atoms, self.method, self.per_atom_loss, we)
+            terms["energy"] = loss_e
+        if not self.analytic and not self.td:
             grad = eng.energy_gradient(c)      # the resident batch is the undisplaced one
         u = [np.zeros((len(a), 3)) for a in self.frames]
         Y = [np.zeros((3, 3)) for _ in self.frames]
@@ -474,6 +532,9 @@ class Trainer:
             dh = np.array([np.asarray(a.get_cell(complete=True), dtype=np.float64) @ Y[k]
                            for k, a in enumerate(self.frames)])
             gradient = eng.constant_gradient if self.constants_mode else eng.loss_gradient
+            if self.td:
+                gradient = lambda cf, r, h: eng.td_loss_gradient(cf, td_coeff.get("energy"),  # noqa: E731
+                                                                 td_coeff.get("eentropy"), r, h)
             try:
                 grad = gradient(c, dR if second else None, dh if second else None)
                 if self.mixed:   # ... and the constants of the analytic functions beside the networks
@@ -493,8 +554,11 @@ class Trainer:
                 scale = max(np.abs(dR).max(initial=0.0), np.abs(dh).max(), 1e-300)
                 e = self.fd_step / scale
                 for sgn in (1.0, -1.0):
-                    disp.append(Atoms(numbers=np.asarray(a.numbers).copy(), positions=a.positions + sgn * e * dR,
-                                      cell=h + sgn * e * dh, pbc=np.asarray(a.pbc).copy()))
+                    d = Atoms(numbers=np.asarray(a.numbers).copy(), positions=a.positions + sgn * e * dR,
+                              cell=h + sgn * e * dh, pbc=np.asarray(a.pbc).copy())
+                    if "etemperature" in a.info:   # the displaced copies of a TD model's frame keep its T
+                        d.info["etemperature"] = a.info["etemperature"]
+                    disp.append(d)
                     coeff.append(sgn / (2.0 * e))
             eng.set_frames(disp)
             grad = grad + eng.energy_gradient(np.array(coeff))
