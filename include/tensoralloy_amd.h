@@ -471,6 +471,27 @@ int ta_measure_hbm_copy(ta_handle h, int64_t bytes, int32_t reps, double *gbs);
  * energy evaluation first (the count reads the pair records). */
 int ta_count_contributing_triples(ta_handle h, int64_t *n_contributing);
 
+/* Triangle-once angular backward pass. A triangle {i, j, k} of three distinct atoms with all sides below
+ * acut adds a G4 term at each of its three apexes; the backward pass of one-element models with the
+ * default zeta grid (1, 4) evaluates the three terms together, once, at the triangle's owner: with the
+ * atom indices sorted, a < b < c, the owner is the one at rank t(a + b + c) in {0, 1, 2}
+ * (ta_device.h: triangle_owner_rank). It is used when every periodic cell width of the batch exceeds
+ * max(rcut, acut) (two images of one atom are then never in one triangle); otherwise, and for every
+ * other model, the per-apex pass runs. Forces, energies and virials are the same up to the order of
+ * the sums.
+ *   ta_set_triangles         `on` = 0 keeps the per-apex pass for this handle (default 1); takes effect
+ *                            at the next ta_compute.
+ *   ta_backward_variant      the angular backward builds the last evaluation with forces ran:
+ *                            0 none, bit 0 per apex, bit 1 triangles.
+ *   ta_count_owned_triangles like ta_count_contributing_triples, restricted to the triples whose centre
+ *                            owns the triangle (3 x owned = contributing when the triangle pass applies).
+ *   ta_triangle_owner        the rule on the host: owner[t] = the owning atom of triangle
+ *                            {abc[3t], abc[3t+1], abc[3t+2]}, or -1 when the three are not distinct. */
+int ta_set_triangles(ta_handle h, int on);
+int ta_backward_variant(ta_handle h, int32_t *variant);
+int ta_count_owned_triangles(ta_handle h, int64_t *n_owned);
+int ta_triangle_owner(int64_t n, const int32_t *abc, int32_t *owner);
+
 /* debugging / parity: host copy of the pair list of the resident batch
  * (centre, neighbour, shift[3]) in the library's order. Arrays sized n_pairs. */
 int ta_get_pairs(ta_handle h, int32_t *i, int32_t *j, int32_t *shift /*[n][3]*/);

@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "ta_count_contributing_triples", "ta_loss_gradient", "ta_constant_count", "ta_get_constants", "ta_update_constants",
     "ta_constant_gradient", "ta_list_sizes", "ta_abi_version", "ta_model_desc_size", "ta_set_nn_tables", "ta_step", "ta_hessian_vectors", "ta_view_results", "ta_step_view",
     "ta_set_electron_temperatures", "ta_get_td_results", "ta_td_loss_gradient",
+    "ta_set_triangles", "ta_backward_variant", "ta_count_owned_triangles", "ta_triangle_owner",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -223,6 +224,10 @@ def load():
     lib.ta_list_stats.argtypes = [H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.ta_list_sizes.argtypes = [H, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     lib.ta_set_nn_tables.argtypes = [H, C.c_int]
+    lib.ta_set_triangles.argtypes = [H, C.c_int]
+    lib.ta_backward_variant.argtypes = [H, C.POINTER(C.c_int32)]
+    lib.ta_count_owned_triangles.argtypes = [H, C.POINTER(C.c_int64)]
+    lib.ta_triangle_owner.argtypes = [C.c_int64, _ip, _ip]
     lib.ta_hessian_vectors.argtypes = [H, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]
     lib.ta_step.argtypes = [H, _dp, _dp, C.c_uint32, _dp, _dp, _dp, _dp, _ip]
     _dpp = C.POINTER(_dp)

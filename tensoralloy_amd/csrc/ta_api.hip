@@ -262,6 +262,13 @@ struct ta_context {
   DevBuf<unsigned long long> masks;
   DevBuf<uint32_t> job_word;
   DevBuf<int32_t> job_count;
+  // triangle-once backward pass (ta_set_triangles): the owned job lists, the handle's option, whether the
+  // resident batch's cells admit the ownership rule, and the builds the last backward pass ran
+  DevBuf<uint32_t> job_word_own;
+  DevBuf<int32_t> job_count_own;
+  bool triangles = true;
+  bool tri_cells_ok = false;
+  int last_bwd_variant = 0;
   DevBuf<int32_t> pair_start, seg_start, pair_i, pair_j, pair_shift, pair_rev;
   ta::NlGrid *d_grids = nullptr;  // view into inbuf
   // device neighbour list (ta_nlist.hip)
@@ -879,6 +886,11 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
       used[TA_K_PAIR_GEOMETRY] = true;
     }
     h->sf.ang_scale = h->use_v2 ? 1.0 : 0.5;
+    // triangle-once backward pass: the forward launches also leave the owned job lists
+    const bool tri = h->use_v2 && h->triangles && h->tri_cells_ok && h->n_elements == 1 && need_forces;
+    h->db.job_word_own = (tri && h->db.job_count) ? h->job_word_own.ptr : nullptr;
+    h->db.job_count_own = (tri && h->db.job_count) ? h->job_count_own.ptr : nullptr;
+    h->last_bwd_variant = 0;
     // the second-generation forward kernel assembles the descriptors itself in its last launch
     const bool reduce_in_forward = h->sf.angular && h->use_v2;
     if (h->sf.angular) {
@@ -912,7 +924,7 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
         bool first = true;
         if (h->use_v2)
           for (const ChunkPlan &cp : h->chunks_v2) {
-            launch_backward_v2(h->sf, cp.ch, cp.ng, cp.nz, first, db, s);
+            h->last_bwd_variant |= launch_backward_v2(h->sf, cp.ch, cp.ng, cp.nz, first, tri, db, s);
             first = false;
           }
         else
@@ -1107,6 +1119,7 @@ int ta_destroy(ta_handle h) {
                   &h->ex_seg_start, &h->ex_counts, &h->ex_map, &h->ex_blk, &h->ex_slot_q})
     b->release();
   h->masks.release(); h->job_word.release(); h->job_count.release();
+  h->job_word_own.release(); h->job_count_own.release();
   for (auto *b : {&h->nl_wrap, &h->nl_binid, &h->nl_bin_count, &h->nl_bin_start, &h->nl_bin_cursor,
                   &h->nl_bin_atoms, &h->nl_counts})
     b->release();
@@ -1134,6 +1147,10 @@ void ensure_job_lists(ta_context *h, size_t n_blk) {
   const int stride = ta::v2_job_stride(h->db.cap);
   h->job_word.ensure(n_blk * (size_t)stride + 8);
   h->job_count.ensure(n_blk + 8);
+  if (h->n_elements == 1) {  // the triangle-once builds are one-element ones
+    h->job_word_own.ensure(n_blk * (size_t)stride + 8);
+    h->job_count_own.ensure(n_blk + 8);
+  }
   h->db.job_word = h->job_word.ptr;
   h->db.job_count = h->job_count.ptr;
   h->db.job_stride = stride;
@@ -1196,6 +1213,28 @@ void apply_filter(ta_context *h) {
   h->filtered = true;
 }
 
+// The triangle-once backward pass needs the three vertices of every triangle to be distinct atoms. Two
+// images of one atom are a lattice vector L apart, and |L| is at least the smallest perpendicular width of
+// the cell over the periodic axes (some component n_k of L is non-zero, and the projection of L on the
+// normal of the other two cell vectors is n_k times width k). A triangle's sides are below acut, so when
+// every periodic width exceeds acut no triangle holds two images of one atom, and each vertex sees the
+// triangle exactly once among its own triples. The test asks for widths above max(rcut, acut) = rmax.
+bool cells_admit_triangles(double rmax, int32_t n_frames, const ta_frame *frames) {
+  for (int f = 0; f < n_frames; ++f) {
+    const double *c = frames[f].cell;
+    const double vol = std::fabs(c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) +
+                                 c[2] * (c[3] * c[7] - c[4] * c[6]));
+    for (int k = 0; k < 3; ++k) {
+      if (!frames[f].pbc[k]) continue;
+      const double *u = c + 3 * ((k + 1) % 3), *v = c + 3 * ((k + 2) % 3);
+      const double nx = u[1] * v[2] - u[2] * v[1], ny = u[2] * v[0] - u[0] * v[2], nz = u[0] * v[1] - u[1] * v[0];
+      const double area = std::sqrt(nx * nx + ny * ny + nz * nz);
+      if (!(vol > rmax * area)) return false;  // width = vol / area (a degenerate cell fails too)
+    }
+  }
+  return true;
+}
+
 // the body of ta_set_frames (also the rebuild path of ta_update_positions); throws
 void set_frames_impl(ta_context *h, int32_t n_frames, const ta_frame *frames, ta_batch_info *info) {
   for (int f = 0; f < n_frames; ++f) {
@@ -1221,6 +1260,7 @@ void set_frames_impl(ta_context *h, int32_t n_frames, const ta_frame *frames, ta
   h->db.blk_groups = 0;
   h->db.n_blk_dev = nullptr;
   h->r_list = h->rmax + h->skin;
+  h->tri_cells_ok = cells_admit_triangles(h->rmax, n_frames, frames);
   size_t N = 0;
   for (int f = 0; f < n_frames; ++f) N += (size_t)frames[f].n_atoms;
   if (N >= (1u << 30)) throw std::runtime_error("batch too large for 32-bit atom indices");
@@ -1752,8 +1792,9 @@ __global__ __launch_bounds__(256) void hbm_copy_nt_kernel(const double2 *__restr
 namespace {
 // unordered {j, k} of one centre with r_ij, r_ik and r_jk all below acut: the triples whose G4 term
 // is not identically zero (one wavefront per centre, lane a walks b > a; reads the pair records)
+// `owned`: only the triples whose centre owns the triangle (ta::owns_triangle)
 __global__ __launch_bounds__(256) void count_triples_kernel(ta::DeviceBatch b, double ac2, double eps,
-                                                            unsigned long long *out) {
+                                                            unsigned long long *out, int owned) {
   const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
   if (i >= b.n_atoms) return;
@@ -1766,7 +1807,8 @@ __global__ __launch_bounds__(256) void count_triples_kernel(ta::DeviceBatch b, d
     for (int pb = pa + 1; pb < p1; ++pb) {
       const double2 *rb = ta::pair_geom(b, (size_t)pb);
       const double ex = rb[0].x - ax, ey = rb[0].y - ay, ez = rb[1].x - az;
-      n += (rb[1].y < ac2 && ex * ex + ey * ey + ez * ez + eps < ac2) ? 1ull : 0ull;
+      n += (rb[1].y < ac2 && ex * ex + ey * ey + ez * ez + eps < ac2 &&
+            (!owned || ta::owns_triangle((int32_t)i, b.pair_j[pa], b.pair_j[pb]))) ? 1ull : 0ull;
     }
   }
   for (int off = 32; off; off >>= 1) n += __shfl_xor(n, off);
@@ -1787,13 +1829,60 @@ int ta_count_contributing_triples(ta_handle h, int64_t *n_contributing) {
     const int64_t N = h->db.n_atoms;
     if (N)
       hipLaunchKernelGGL(count_triples_kernel, dim3((unsigned)((N * 64 + 255) / 256)), dim3(256), 0, s, h->db,
-                         h->sf.acut * h->sf.acut, h->sf.eps, h->nl_stats.ptr);
+                         h->sf.acut * h->sf.acut, h->sf.eps, h->nl_stats.ptr, 0);
     HIP_CHECK(hipGetLastError());
     unsigned long long v = 0;
     HIP_CHECK(hipMemcpyAsync(&v, h->nl_stats.ptr, sizeof(v), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     *n_contributing = (int64_t)v;
   });
+}
+
+int ta_count_owned_triangles(ta_handle h, int64_t *n_owned) {
+  if (!h || !n_owned) return fail(h, TA_ERR_INVALID, "null argument");
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "no resident batch");
+  if (h->kind != TA_MODEL_SF_MLP || !h->sf.angular)
+    return fail(h, TA_ERR_INVALID, "only symmetry-function models with angular terms have triples");
+  return guarded(h, [&]() {
+    compute_impl(h, TA_WANT_ENERGY, false, nullptr);  // fills the pair records
+    h->nl_stats.ensure(8);
+    hipStream_t s = h->stream;
+    HIP_CHECK(hipMemsetAsync(h->nl_stats.ptr, 0, sizeof(unsigned long long), s));
+    const int64_t N = h->db.n_atoms;
+    if (N)
+      hipLaunchKernelGGL(count_triples_kernel, dim3((unsigned)((N * 64 + 255) / 256)), dim3(256), 0, s, h->db,
+                         h->sf.acut * h->sf.acut, h->sf.eps, h->nl_stats.ptr, 1);
+    HIP_CHECK(hipGetLastError());
+    unsigned long long v = 0;
+    HIP_CHECK(hipMemcpyAsync(&v, h->nl_stats.ptr, sizeof(v), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    *n_owned = (int64_t)v;
+  });
+}
+
+int ta_set_triangles(ta_handle h, int on) {
+  if (!h) return TA_ERR_INVALID;
+  h->triangles = on != 0;
+  return TA_OK;
+}
+
+int ta_backward_variant(ta_handle h, int32_t *variant) {
+  if (!h || !variant) return fail(h, TA_ERR_INVALID, "null argument");
+  *variant = h->last_bwd_variant;
+  return TA_OK;
+}
+
+int ta_triangle_owner(int64_t n, const int32_t *abc, int32_t *owner) {
+  if (n < 0 || (n > 0 && (!abc || !owner))) return TA_ERR_INVALID;
+  for (int64_t t = 0; t < n; ++t) {
+    int32_t a = abc[3 * t], b = abc[3 * t + 1], c = abc[3 * t + 2];
+    if (a > b) std::swap(a, b);
+    if (b > c) std::swap(b, c);
+    if (a > b) std::swap(a, b);
+    const int32_t sorted[3] = {a, b, c};
+    owner[t] = (a == b || b == c) ? -1 : sorted[ta::triangle_owner_rank((uint32_t)a + (uint32_t)b + (uint32_t)c)];
+  }
+  return TA_OK;
 }
 
 int ta_measure_hbm_copy(ta_handle h, int64_t bytes, int32_t reps, double *gbs) {
@@ -2010,7 +2099,8 @@ void backward_only(ta_context *h) {
       bool first = true;
       if (h->use_v2)
         for (const ChunkPlan &cp : h->chunks_v2) {
-          launch_backward_v2(h->sf, cp.ch, cp.ng, cp.nz, first, db, s);
+          // per apex: the callers keep g[p] per pair (J[c][p]), which the triangle pass distributes differently
+          launch_backward_v2(h->sf, cp.ch, cp.ng, cp.nz, first, false, db, s);
           first = false;
         }
       else

@@ -105,6 +105,12 @@ struct DeviceBatch {
   uint32_t *job_word = nullptr;
   int32_t *job_count = nullptr;
   int job_stride = 0;
+  // Triangle-once backward (one-element default-grid builds, see owns_triangle): the forward kernel
+  // also leaves the list restricted to the triangles the centre owns, in the same word format and at
+  // the same place per workgroup; job_count_own[blk] = -1: no list (the backward kernel then tests
+  // ownership per triple). null: not made in this evaluation.
+  uint32_t *job_word_own = nullptr;
+  int32_t *job_count_own = nullptr;
   double *G = nullptr;      // [N][D]
   double *dEdG = nullptr;   // [N][D]
   double *eatom = nullptr;  // [N]
@@ -127,6 +133,27 @@ struct DeviceBatch {
   double *virial = nullptr; // [F][9]
   double *batch_energy = nullptr;  // [1]
 };
+
+// Ownership of an angular triangle. A triangle {i, j, k} of three DISTINCT atoms (all three sides
+// below acut) is evaluated once in the backward pass, by one of its vertices: with the indices sorted,
+// a < b < c, the owner is the one at rank t(a + b + c) in {0, 1, 2}, a multiplicative hash of the
+// (symmetric) index sum. Every vertex reaches the same owner from its own view, and a centre's
+// triangles spread over all three ranks, so every centre owns about a third of its triangles ("the
+// smallest index owns" would give some centres all of theirs and others none). The atoms are distinct
+// whenever every periodic cell width exceeds acut: two images of one atom are at least one width apart.
+// (Fibonacci hashing modulo 2^24: 24-bit multiplications, full rate on the device)
+__host__ __device__ inline int triangle_owner_rank(uint32_t index_sum) {
+#ifdef __HIP_DEVICE_COMPILE__
+  const uint32_t h = __umul24(index_sum, 0x9E3779u);
+#else
+  const uint32_t h = index_sum * 0x9E3779u;  // the same low 24 bits
+#endif
+  return (int)(((h & 0xFFFFFFu) * 3u) >> 24);
+}
+// centre i owns the triangle {i, j, k}
+__host__ __device__ inline bool owns_triangle(int32_t i, int32_t j, int32_t k) {
+  return triangle_owner_rank((uint32_t)i + (uint32_t)j + (uint32_t)k) == (j < i ? 1 : 0) + (k < i ? 1 : 0);
+}
 
 // end of centre i's pairs (see DeviceBatch::pair_stop)
 #ifdef __HIPCC__
@@ -176,13 +203,15 @@ void launch_frame_reduce(const DeviceBatch &b, bool want_virial, double *mirror,
 size_t g4_lds_bytes(int nnl_max);
 
 // second-generation angular kernels (ta_kernels_v2.hip); `ch` holds one beta
-size_t v2_lds_bytes(bool backward, int cap, int n_local = 0, int nspec = 0);
+size_t v2_lds_bytes(bool backward, int cap, int n_local = 0, int nspec = 0, bool triangles = false);
 int v2_job_stride(int cap);
 // `reduce`: last forward launch of an evaluation, also assembles the descriptor vectors
 void launch_g4_forward_v2(const SFParams &sf, const AngChunk &ch, int ng, int nz, bool geometry,
                           bool reduce, const DeviceBatch &b, hipStream_t s);
-void launch_backward_v2(const SFParams &sf, const AngChunk &ch, int ng, int nz, bool first,
-                        const DeviceBatch &b, hipStream_t s);
+// `triangles`: one-element default-grid chunks take the triangle-once build (b.job_word_own made by the
+// forward launch, or ownership tested per triple). Returns the build used: 1 per apex, 2 triangles.
+int launch_backward_v2(const SFParams &sf, const AngChunk &ch, int ng, int nz, bool first, bool triangles,
+                       const DeviceBatch &b, hipStream_t s);
 
 // device-side neighbour list (ta_nlist.hip)
 struct NlGrid {  // linked-cell grid of one frame, in fractional coordinates

@@ -48,9 +48,11 @@ constexpr int kNFf = 7;  // forward: the last record is the species alone (8 byt
                          // which with the trimmed job counters lets 7 workgroups share a CU instead of 6
 // control words of the forward kernel's job mode, as ints: hist[20] start[20] (make_jobs), cstart[20] (first
 // pair of every centre of the workgroup), then segl[16][kSegW] (first pair of every (centre, neighbour species)
-// segment, + the centre's end) and sslot[16][kSegW] (first partial-sum slot of the segment)
+// segment, + the centre's end) and sslot[16][kSegW] (first partial-sum slot of the segment), then ohist[20]
+// ostart[20] (make_owned_jobs)
 constexpr int kSegW = 6;  // up to 5 species + the end
-constexpr int kJobCtlBytes = (60 + 2 * kMaxCentersPerBlock * kSegW) * 4;
+constexpr int kOwnCtl = 60 + 2 * kMaxCentersPerBlock * kSegW;
+constexpr int kJobCtlBytes = (kOwnCtl + 40) * 4;
 // The per-pair partial G4 sums of the forward sweep are only ever summed over a (centre, neighbour species)
 // segment, so they are kept per GROUP OF FOUR pairs of a segment: n_local x (cap / 4 + 16 nspec) doubles
 // instead of n_local x cap (one element: 22.0 -> 18.0 KB of LDS per workgroup, 8 instead of 7 workgroups per
@@ -162,9 +164,12 @@ __device__ __forceinline__ double hd_value(const SFParams &sf, const AngChunk &c
 // series + an exponential (about 50). The backward kernel stages the logarithmic derivative
 // L = (dH/dr) / (r H) instead of G = (dH/dr) / r: its triple body then factors T = Ha Hb Hd out of all
 // three derivatives (see there). H = 0 (pair beyond acut) gives L = 0; such a pair has no triples.
+// `jidx` (forward kernel, one element, owned job lists): the neighbour's atom index per pair slot, in place
+// of the species.
 template <int HD>
 __device__ __forceinline__ void stage(const SFParams &sf, const AngChunk &ch, double beta, const DeviceBatch &b,
-                                      const Fields &f, int s0, int M, int geom = 0, bool forward = false) {
+                                      const Fields &f, int s0, int M, int geom = 0, bool forward = false,
+                                      int *jidx = nullptr) {
   for (int item = threadIdx.x; item < M; item += blockDim.x) {
     double2 v0, v1, v2;
     if (geom) {
@@ -225,7 +230,8 @@ __device__ __forceinline__ void stage(const SFParams &sf, const AngChunk &ch, do
       }
     }
     f.ih[item] = make_double2(v2.x, H);
-    if (forward) f.sp1[item] = (double)b.species[b.pair_j[s0 + item]];
+    if (jidx) jidx[item] = b.pair_j[s0 + item];
+    else if (forward) f.sp1[item] = (double)b.species[b.pair_j[s0 + item]];
     else f.gs[item] = make_double2(L, (double)b.species[b.pair_j[s0 + item]]);
   }
   __syncthreads();
@@ -391,6 +397,70 @@ __device__ __forceinline__ int make_jobs(JobLists &j, bool active, int item, int
 
 // job of lane `tid` in round `r` (T lanes): serpentine over the size-sorted list
 __device__ __forceinline__ int job_slot(int r, int tid, int T) { return r * T + ((r & 1) ? T - 1 - tid : tid); }
+
+// The list of the triangle-once backward build: the jobs a lane swept (`word[r]`, up to four rounds) with
+// their candidate bits replaced by those of the contributing triples the centre owns (`own[r]`, found by
+// the forward sweep itself, see run_item), sorted by size exactly as in make_jobs and written straight to
+// `out` (the words are not swept here, so they need no room in LDS). `hist` must be zero on entry.
+__device__ __forceinline__ void make_owned_jobs(int *hist, int *start, const uint32_t word[4], const unsigned own[4],
+                                                uint32_t *out, int32_t *count) {
+  const int tid = threadIdx.x;
+  int cnt[4], rank[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    cnt[r] = __popc(own[r]);
+    if (cnt[r]) rank[r] = atomicAdd(&hist[16 - cnt[r]], 1);
+  }
+  __syncthreads();
+  if (tid < 64) {
+    const int v = tid < 16 ? hist[tid] : 0;
+    int incl = v;
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) {
+      const int u = __shfl_up(incl, off);
+      if (tid >= off) incl += u;
+    }
+    if (tid < 16) start[tid] = incl - v;
+    if (tid == 15) *count = incl;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    if (cnt[r]) out[start[16 - cnt[r]] + rank[r]] = (word[r] & 0xffffu) | (own[r] << 16);
+}
+
+// DEFZ: the angular dE/dG of one atom (one element) as the coefficients of S0(w) = sum_k pc[k] w^k,
+// w = 2 cos(theta): S0 = sum_c dE/dG_c kz (1 + gamma c)^zeta over the chunk's (gamma, zeta = 1, 4) channels
+template <int NG, int NZ>
+__device__ __forceinline__ void defz_coeffs(const AngChunk &ch, const double *wsrc, double pc[5]) {
+  double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0, p4 = 0.0;
+#pragma unroll
+  for (int ig = 0; ig < NG; ++ig) {
+    const double g1 = ch.gamma[ig], g2 = g1 * g1;
+    const double w1 = wsrc[ch.chan[ig * NZ]] * ch.kz[0], w4 = wsrc[ch.chan[ig * NZ + 1]] * ch.kz[1];
+    p0 += w1 + w4;
+    p1 += g1 * (w1 + 4.0 * w4);
+    p2 += 6.0 * g2 * w4;
+    p3 += 4.0 * g2 * g1 * w4;
+    p4 += g2 * g2 * w4;
+  }
+  // in powers of w = 2 cos(theta) (what the triple body has: (r_a^2 + r_b^2 - r_ab^2) / (r_a r_b))
+  pc[0] = p0;
+  pc[1] = 0.5 * p1;
+  pc[2] = 0.25 * p2;
+  pc[3] = 0.125 * p3;
+  pc[4] = 0.0625 * p4;
+}
+
+// 1 / sqrt(x) in double precision: the hardware estimate and two Newton steps (a few ulp; the staging's
+// 1.0 / sqrt costs a correctly rounded square root and a division, some 25 instructions)
+__device__ __forceinline__ double rsqrt_f64(double x) {
+  double y = __builtin_amdgcn_rsq(x);
+  const double hx = 0.5 * x;
+  y = fma(y, fma(-hx * y, y, 0.5), y);
+  y = fma(y, fma(-hx * y, y, 0.5), y);
+  return y;
+}
 
 // Descriptor vectors of the workgroup's centres from data that is still in LDS, one wavefront per
 // centre, round robin. G2 from r^2 (sf.py:79-119):
@@ -599,11 +669,14 @@ __global__ __launch_bounds__(kBlock)
       const int k = ((int)threadIdx.x - 64) / (NSPEC + 1), sg = ((int)threadIdx.x - 64) % (NSPEC + 1);
       cnt[60 + k * kSegW + sg] = b.seg_start[(size_t)(c0 + k) * (NSPEC + 1) + sg] - s0;
     }
+    if (NSPEC == 1 && b.job_word_own && threadIdx.x < 20) cnt[kOwnCtl + threadIdx.x] = 0;  // ohist
     double *P0 = reinterpret_cast<double *>(raw + v2_counter_offset(kCap) + kJobCtlBytes);
     for (int k = threadIdx.x; k < NSPEC * NG * NZ * v2_pcols(kCap, NSPEC); k += blockDim.x) P0[k] = 0.0;
   }
+  // owned job lists (one element only): the neighbours' atom indices take the place of their species (sp1)
+  int *jidx = (NSPEC == 1 && b.job_word_own && b.job_count) ? reinterpret_cast<int *>(f.sp1) : nullptr;
   TA_STAMP(b, 0, 0);
-  stage<HD>(sf, ch, beta, b, f, s0, M, geom, true);
+  stage<HD>(sf, ch, beta, b, f, s0, M, geom, true, jidx);
   TA_STAMP(b, 0, 1);
   if (b.job_count && threadIdx.x == 0) {
     // sslot[k][sg]: first partial-sum slot of segment (centre c0 + k, neighbour species sg), one slot per
@@ -624,14 +697,26 @@ __global__ __launch_bounds__(kBlock)
   // `pacc`: job mode, the sums of this (pair, partner subset) are ADDED to P[channel][item] in LDS
   // `is_job` (std::true_type): `mask0` is a job word (see make_jobs): 16 candidate bits and their window,
   // walked with 32-bit operations and without the loop over blocks of 64 candidate steps
+  // job mode with `jidx` (owned job lists): returns the job's bits of the contributing triples whose
+  // triangle the centre owns (owns_triangle), tested where the body has found the triple contributes
   auto run_item = [&](int item, bool have_mask, unsigned long long mask0, double *out, double *pacc, auto is_job) {
     constexpr bool kJob = decltype(is_job)::value;
     const int64_t p = (int64_t)s0 + item;
     int base, n;
     int pslot = item;  // column index of this pair's partial sums in `pacc`
+    unsigned own = 0u;  // owned bits of the job (jidx)
+    int kbit = 0;       // bit of the job word the current candidate came from
+    uint32_t sij = 0u;  // centre + neighbour index (jidx)
+    int ic = 0, rij = 0;
     if constexpr (kJob) {
       const int *cstart = reinterpret_cast<const int *>(reinterpret_cast<const char *>(lds) + v2_counter_offset(kCap)) + 40;
       const int ci = job_centre((uint32_t)mask0);
+      if (NSPEC == 1 && jidx) {
+        ic = c0 + ci;
+        const int j = jidx[item];
+        sij = (uint32_t)ic + (uint32_t)j;
+        rij = j < ic ? 1 : 0;
+      }
       base = cstart[ci];
       n = cstart[ci + 1] - base;
       {
@@ -675,6 +760,12 @@ __global__ __launch_bounds__(kBlock)
         const double d2 = fma(ex, ex, fma(ey, ey, fma(ez, ez, sf.eps)));
         const double u = kProbe(flags, 30) ? 0.5 : d2 * sf.inv_ac2;
         if (!(u < 1.0)) return;  // exact test (the mask is a superset); H_b = 0 adds nothing
+        if constexpr (kJob && NSPEC == 1) {
+          if (jidx) {
+            const int kk = jidx[q];
+            own |= (triangle_owner_rank(sij + (uint32_t)kk) == rij + (kk < ic ? 1 : 0) ? 1u : 0u) << kbit;
+          }
+        }
         const double2 bih = f.ih[kProbe(flags, 29) ? (int)threadIdx.x : q];
         const double cth = (ra2 + bzr.y - d2) * 0.5 * inv_ra * bih.x;
         const double common = Ha * bih.y * hd_value<HD>(sf, ch, beta, u);
@@ -717,6 +808,7 @@ __global__ __launch_bounds__(kBlock)
       while (m) {
         const int k = __ffs((int)m) - 1;
         m &= m - 1;
+        kbit = k;
         triple(k0 + k);
       }
     } else {
@@ -763,6 +855,7 @@ __global__ __launch_bounds__(kBlock)
           else
             b.part4[(size_t)(sp * sf.n_ang + c) * b.n_pairs + p] = v;
         }
+    return own;
   };
 
   // balanced path: one pair per lane, one scan pass for every centre of the workgroup
@@ -798,14 +891,23 @@ __global__ __launch_bounds__(kBlock)
       if (threadIdx.x == 0) b.job_count[blockIdx.x] = n_jobs;
       for (int slot = threadIdx.x; slot < n_jobs; slot += blockDim.x) b.job_word[jbase + slot] = jl.word[slot];
       TA_STAMP(b, 0, 4);
+      uint32_t swept[4] = {0u, 0u, 0u, 0u};  // jobs of this lane (at most four rounds: n_jobs <= 4 M)
+      unsigned owned[4] = {0u, 0u, 0u, 0u};
       if (!(flags & (1 << 27)))
         for (int r = 0; r * (int)blockDim.x < n_jobs; ++r) {
           const int slot = job_slot(r, threadIdx.x, blockDim.x);
           if (slot < n_jobs) {
             const uint32_t jw = jl.word[slot];
-            run_item(job_item(jw), true, jw, nullptr, P, std::true_type{});
+            const unsigned o = run_item(job_item(jw), true, jw, nullptr, P, std::true_type{});
+            if (r < 4) {
+              swept[r] = jw;
+              owned[r] = o;
+            }
           }
         }
+      if (jidx)  // the list of the triangle-once backward build
+        make_owned_jobs(jl.hist + kOwnCtl, jl.hist + kOwnCtl + 20, swept, owned, b.job_word_own + jbase,
+                        b.job_count_own + blockIdx.x);
       __syncthreads();
       TA_STAMP(b, 0, 5);
       if (flags & 4) {
@@ -865,6 +967,7 @@ __global__ __launch_bounds__(kBlock)
     }
   } else {
     if (b.job_count && threadIdx.x == 0) b.job_count[blockIdx.x] = -1;  // no list: the backward kernel scans itself
+    if (jidx && threadIdx.x == 0) b.job_count_own[blockIdx.x] = -1;
     for (int it = threadIdx.x; it < M; it += blockDim.x) run_item(it, false, 0ull, nullptr, nullptr, std::false_type{});
   }
 
@@ -891,7 +994,9 @@ __global__ __launch_bounds__(kBlock)
   }
 }
 
-template <int NSPEC, int NG, int NZ, int HD, bool DEFZ, int CAP, int WPE = (DEFZ ? (NSPEC <= 2 ? 5 : 4) : 0)>
+// TRI: the triangle-once build (one element, default grid, Hd series; see `run_tri`).
+template <int NSPEC, int NG, int NZ, int HD, bool DEFZ, int CAP, int WPE = (DEFZ ? (NSPEC <= 2 ? 5 : 4) : 0),
+          bool TRI = false>
 // Occupancy: the backward body is latency-bound at the 3 wavefronts per SIMD the compiler settles for
 // (133 VGPRs); asking for 5 (96 VGPRs, 10 spilled) measured 72 -> 66 us on the benchmark frame and
 // 51 -> 45 us per frame in batches (4: 69 / 47, 6: 68 / 45). Only the default-grid instantiations
@@ -900,6 +1005,7 @@ __global__ __launch_bounds__(kBlock)
     __attribute__((amdgpu_waves_per_eu(WPE > 0 ? WPE : 1, 8))) void backward_v2_kernel(SFParams sf, AngChunk ch,
                                                              DeviceBatch b, int flags) {
   static_assert(!DEFZ || NZ == 2, "DEFZ needs the two-zeta grid");
+  static_assert(!TRI || (NSPEC == 1 && DEFZ && HD > 0), "the triangle build is one-element, default grid, Hd series");
   const int first = flags & 1;
   if (b.n_blk_dev && (int)blockIdx.x >= *b.n_blk_dev) return;  // grid sized by an upper bound (MD loop)
   stagger(flags);
@@ -962,10 +1068,146 @@ __global__ __launch_bounds__(kBlock)
       rtab[ci * kRTab + rem] = b.dEdG[(size_t)i * sf.ndim + radial_term2(b.species[i], sb) * sf.n_rad + c];
     }
   }
+  // TRI: the S0 coefficients of every NEIGHBOUR atom per pair slot, {p0 p1} {p2 p3} p4 (5 cap doubles
+  // behind the per-centre tables): a triangle body reads those of its partner pair with 16-byte reads
+  double2 *pn01 = reinterpret_cast<double2 *>(rtab + kMaxCentersPerBlock * kRTab), *pn23 = pn01 + kCap;
+  double *pn4 = reinterpret_cast<double *>(pn23 + kCap);
+  if constexpr (TRI) {
+    for (int item = threadIdx.x; item < M; item += blockDim.x) {
+      double pc[5];
+      defz_coeffs<NG, NZ>(ch, b.dEdG + (size_t)b.pair_j[s0 + item] * sf.ndim + sf.n_radial_dim, pc);
+      pn01[item] = make_double2(pc[0], pc[1]);
+      pn23[item] = make_double2(pc[2], pc[3]);
+      pn4[item] = pc[4];
+    }
+  }
   TA_STAMP(b, 1, 0);
   stage<HD>(sf, ch, beta, b, f, s0, M);
   TA_STAMP(b, 1, 1);
   const int nel = sf.n_elements;
+
+  // Triangle-once body (TRI). A triangle {i, j, k} with all three sides below acut adds
+  //   V = T [S0_i(w_i) + S0_j(w_j) + S0_k(w_k)],   T = H(A) H(B) H(D),
+  // to the energy, where A = ra^2, B = rb^2, D = d^2 are the squared sides seen from the owner i (pairs
+  // a = D_ij, b = D_ik, d = b - a), w_i = (A + B - D) / (ra rb), w_j = (A + D - B) / (ra d),
+  // w_k = (B + D - A) / (rb d) twice the cosines at the three apexes, and S0_x the degree-4 polynomial of
+  // atom x's dE/dG (defz_coeffs). The per-apex build evaluates the triangle three times, once from each
+  // vertex; here its owner puts the gradient of all three terms onto its own two pairs, since V depends
+  // on a and b alone. With F_1, F_2, F_3 the partial derivatives of V by A, B, D:
+  //   dV/da = ca a + Q b,  dV/db = cb b + Q a,  ca = 2 (F_1 + F_3), cb = 2 (F_2 + F_3), Q = -2 F_3,
+  // the shape the per-apex body accumulates. With Y_x = T dS0_x/dw (x = i, j, k), X = (sum S0) Ha Hb Hd2,
+  // Z_A = Y_i w_i + Y_j w_j, Z_B = Y_i w_i + Y_k w_k, Z_D = Y_j w_j + Y_k w_k:
+  //   ca = T (sum S0) La + X - Z_A / A - Z_D / D + 4 Y_j / (ra d)
+  //   cb = T (sum S0) Lb + X - Z_B / B - Z_D / D + 4 Y_k / (rb d)
+  //   Q  = -X + 2 (Y_i / (ra rb) - Y_j / (ra d) - Y_k / (rb d)) + Z_D / D
+  // (La, Lb, Hd2 as in the per-apex body). One Hd sweep, one reciprocal square root and three
+  // polynomial pairs per triangle instead of three sweeps and three bodies.
+  // Which triples are the centre's: the job words of `b.job_word_own` (make_owned_jobs) carry only owned
+  // bits; without that list (a workgroup the forward kernel could not give one) ownership is tested here.
+  auto run_tri = [&](int item, bool have_mask, unsigned long long mask0, auto is_job) {
+    constexpr bool kJob = decltype(is_job)::value;
+    const int64_t p = (int64_t)s0 + item;
+    int i, base, n;
+    if constexpr (kJob) {
+      const int ci = job_centre((uint32_t)mask0);
+      i = c0 + ci;
+      base = cstart[ci];
+      n = cstart[ci + 1] - base;
+    } else {
+      i = b.pair_i[p];
+      base = b.pair_start[i] - s0;
+      n = pair_stop_of(b, i) - b.pair_start[i];
+    }
+    const int a = item - base;
+    const double2 axy = f.xy[item], azr = f.zr[item], aih = f.ih[item], ags = f.gs[item];
+    const double ax = axy.x, ay = axy.y, az = azr.x;
+    const double A = azr.y, inv_ra = aih.x, Ha = aih.y, La = ags.x;
+    const double inv_A = inv_ra * inv_ra;
+    double pi_[5], pj_[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) pi_[k] = pctab[5 * (i - c0) + k];
+    {
+      const double2 p01 = pn01[item], p23 = pn23[item];
+      pj_[0] = p01.x;
+      pj_[1] = p01.y;
+      pj_[2] = p23.x;
+      pj_[3] = p23.y;
+      pj_[4] = pn4[item];
+    }
+    const int ja = kJob ? 0 : b.pair_j[p];  // ownership test of the list-less path only
+    double csum = 0.0, gx = 0.0, gy = 0.0, gz = 0.0;
+    auto tri = [&](int bl) {
+      bl = (int)min((unsigned)bl, (unsigned)bl - (unsigned)n);  // bl < 2 n: bl mod n without a compare / select
+      const int q = base + bl;
+      if constexpr (!kJob) {
+        if (!owns_triangle(i, ja, b.pair_j[s0 + q])) return;
+      }
+      const double2 bxy = f.xy[q], bzr = f.zr[q];
+      const double bx = bxy.x, by = bxy.y, bz = bzr.x;
+      const double ex = bx - ax, ey = by - ay, ez = bz - az;
+      const double D = fma(ex, ex, fma(ey, ey, fma(ez, ez, sf.eps)));
+      const double u = D * sf.inv_ac2;
+      if (!(u < 1.0)) return;  // exact test (the mask is a superset)
+      const double2 bih = f.ih[q], bgs = f.gs[q], p01 = pn01[q], p23 = pn23[q];
+      const double pk4 = pn4[q];
+      const double B = bzr.y, inv_rb = bih.x, Hb = bih.y, Lb = bgs.x;
+      double Hd, dHd;
+      hd_eval<HD>(sf, ch, beta, u, Hd, dHd);
+      const double inv_d = rsqrt_f64(D);
+      const double inv_ab = inv_ra * inv_rb, inv_ad = inv_ra * inv_d, inv_bd = inv_rb * inv_d;
+      const double wi = (A + B - D) * inv_ab, wj = (A + D - B) * inv_ad, wk = (B + D - A) * inv_bd;
+      // S0 and dS0/dw of the three apexes (Horner)
+      const double Si = fma(fma(fma(fma(pi_[4], wi, pi_[3]), wi, pi_[2]), wi, pi_[1]), wi, pi_[0]);
+      const double Pi = fma(fma(fma(4.0 * pi_[4], wi, 3.0 * pi_[3]), wi, 2.0 * pi_[2]), wi, pi_[1]);
+      const double Sj = fma(fma(fma(fma(pj_[4], wj, pj_[3]), wj, pj_[2]), wj, pj_[1]), wj, pj_[0]);
+      const double Pj = fma(fma(fma(4.0 * pj_[4], wj, 3.0 * pj_[3]), wj, 2.0 * pj_[2]), wj, pj_[1]);
+      const double Sk = fma(fma(fma(fma(pk4, wk, p23.y), wk, p23.x), wk, p01.y), wk, p01.x);
+      const double Pk = fma(fma(fma(4.0 * pk4, wk, 3.0 * p23.y), wk, 2.0 * p23.x), wk, p01.y);
+      const double HH = Ha * Hb, T = HH * Hd;
+      const double sum = Si + Sj + Sk;
+      const double TS = T * sum;
+      const double X = (sum * HH) * (sf.two_inv_ac2 * dHd);
+      const double Yi = Pi * T, Yj = Pj * T, Yk = Pk * T;
+      const double Ywi = Yi * wi, Ywj = Yj * wj, Ywk = Yk * wk;
+      const double inv_D = inv_d * inv_d;
+      const double ZD = (Ywj + Ywk) * inv_D;
+      const double Yjd = Yj * inv_ad, Ykd = Yk * inv_bd;
+      const double ca = fma(TS, La, fma(-(Ywi + Ywj), inv_A, fma(4.0, Yjd, X - ZD)));
+      const double cb = fma(TS, Lb, fma(-(Ywi + Ywk), inv_rb * inv_rb, fma(4.0, Ykd, X - ZD)));
+      const double Q = fma(2.0, fma(Yi, inv_ab, -(Yjd + Ykd)), ZD - X);
+      csum += ca;
+      gx = fma(Q, bx, gx);
+      gy = fma(Q, by, gy);
+      gz = fma(Q, bz, gz);
+      atomicAdd(&gacc[q], fma(cb, bx, Q * ax));
+      atomicAdd(&gacc[kCap + q], fma(cb, by, Q * ay));
+      atomicAdd(&gacc[2 * kCap + q], fma(cb, bz, Q * az));
+    };
+    if constexpr (kJob) {
+      const uint32_t jw = (uint32_t)mask0;
+      unsigned m = (flags & (1 << 24)) ? 0u : jw >> 16;  // bit 24: measurement switch, triple bodies off
+      const int k0 = a + 1 + 16 * (int)((jw >> 8) & 3u);
+      while (m) {
+        const int k = __ffs((int)m) - 1;
+        m &= m - 1;
+        tri(k0 + k);
+      }
+    } else {
+      const int smax = (Ha != 0.0) ? n / 2 : 0;
+      for (int sc = 1; sc <= smax; sc += 64) {
+        unsigned long long mask = have_mask ? mask0 : b.masks[(size_t)(sc >> 6) * b.n_pairs + p];
+        if (flags & (1 << 24)) mask = 0ull;
+        while (mask) {
+          const int k = __ffsll((long long)mask) - 1;
+          mask &= mask - 1;
+          tri(a + sc + k);
+        }
+      }
+    }
+    atomicAdd(&gacc[item], fma(csum, ax, gx));
+    atomicAdd(&gacc[kCap + item], fma(csum, ay, gy));
+    atomicAdd(&gacc[2 * kCap + item], fma(csum, az, gz));
+  };
 
   auto run_item = [&](int item, bool have_mask, unsigned long long mask0, auto is_job) {
     constexpr bool kJob = decltype(is_job)::value;  // see the forward kernel
@@ -1149,7 +1391,10 @@ __global__ __launch_bounds__(kBlock)
       n_own = pair_stop_of(b, i) - b.pair_start[i];
     }
     const bool one_pass = M <= (int)blockDim.x && !__syncthreads_or(active && (n_own >> 1) > 64);
-    const int n_jobs = (one_pass && b.job_count) ? b.job_count[blockIdx.x] : -1;
+    // TRI: the list of owned triangles (make_owned_jobs)
+    const int32_t *jcount = TRI ? b.job_count_own : b.job_count;
+    const uint32_t *jword = TRI ? b.job_word_own : b.job_word;
+    const int n_jobs = (one_pass && jcount) ? jcount[blockIdx.x] : -1;
     if (n_jobs >= 0) {  // the forward kernel's job list (see make_jobs): no scan, no sort here
       const size_t jbase = (size_t)blockIdx.x * b.job_stride;
       // at most four rounds (four jobs per pair, one pair per lane): the words of all of them are
@@ -1158,14 +1403,17 @@ __global__ __launch_bounds__(kBlock)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int slot = job_slot(r, threadIdx.x, blockDim.x);
-        jws[r] = slot < n_jobs ? b.job_word[jbase + slot] : 0u;
+        jws[r] = slot < n_jobs ? jword[jbase + slot] : 0u;
       }
       TA_STAMP(b, 1, 2);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         if (r * (int)blockDim.x >= n_jobs) break;
         const int slot = job_slot(r, threadIdx.x, blockDim.x);
-        if (slot < n_jobs) run_item(job_item(jws[r]), true, jws[r], std::true_type{});
+        if (slot < n_jobs) {
+          if constexpr (TRI) run_tri(job_item(jws[r]), true, jws[r], std::true_type{});
+          else run_item(job_item(jws[r]), true, jws[r], std::true_type{});
+        }
       }
       TA_STAMP(b, 1, 3);
     } else if (one_pass) {  // see deal_by_popcount
@@ -1177,9 +1425,15 @@ __global__ __launch_bounds__(kBlock)
       }
       // (no re-dealing by popcount here: its scratch lived in the rings, which this kernel no longer has;
       // this path runs only with TA_NO_JOBS=1)
-      if (active) run_item(item, true, mask, std::false_type{});
+      if (active) {
+        if constexpr (TRI) run_tri(item, true, mask, std::false_type{});
+        else run_item(item, true, mask, std::false_type{});
+      }
     } else {
-      for (int it = threadIdx.x; it < M; it += blockDim.x) run_item(it, false, 0ull, std::false_type{});
+      for (int it = threadIdx.x; it < M; it += blockDim.x) {
+        if constexpr (TRI) run_tri(it, false, 0ull, std::false_type{});
+        else run_item(it, false, 0ull, std::false_type{});
+      }
     }
   }
   __syncthreads();
@@ -1269,9 +1523,34 @@ void fwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int geo
     hipLaunchKernelGGL((g4_forward_v2_kernel<NSPEC, NG, NZ, 0, false, 0>), grid, block, lds, s, sf, ch, b, geom);
 }
 template <int NSPEC, int NG, int NZ>
-void bwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int first, hipStream_t s) {
+void bwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int first, bool tri, int &variant,
+           hipStream_t s) {
   const dim3 grid((unsigned)b.n_blk), block((unsigned)(b.cap < kBlock ? b.cap : kBlock));
   const size_t lds = v2_lds_bytes(true, b.cap);
+  variant = 1;
+  if constexpr (NZ == 2 && NSPEC == 1) {
+    // triangle-once builds: the default grid with an Hd series, one element
+    if (tri && (ch.n_hd == 12 || ch.n_hd == 16) && ch.zeta_int[0] == 1 && ch.zeta_int[1] == 4) {
+      const size_t lds_t = v2_lds_bytes(true, b.cap, 0, 0, true);
+      variant = 2;
+      // 5 wavefronts per SIMD (96 VGPRs, 17 spilled); TA_BWD_WPE=4 (A/B) takes the 4-wavefront build (125 VGPRs, none
+      // spilled), measured slower: 38.7 against 37.0 us on the benchmark frame
+      static const int force = getenv("TA_BWD_WPE") ? atoi(getenv("TA_BWD_WPE")) : 0;
+      if (ch.n_hd == 12 && b.cap == kCapMin && force == 4)
+        hipLaunchKernelGGL((backward_v2_kernel<1, NG, NZ, 12, true, kCapMin, 4, true>), grid, block, lds_t, s, sf, ch,
+                           b, first);
+      else if (ch.n_hd == 12 && b.cap == kCapMin)
+        hipLaunchKernelGGL((backward_v2_kernel<1, NG, NZ, 12, true, kCapMin, 5, true>), grid, block, lds_t, s, sf, ch,
+                           b, first);
+      else if (ch.n_hd == 12)
+        hipLaunchKernelGGL((backward_v2_kernel<1, NG, NZ, 12, true, 0, 5, true>), grid, block, lds_t, s, sf, ch, b,
+                           first);
+      else
+        hipLaunchKernelGGL((backward_v2_kernel<1, NG, NZ, 16, true, 0, 5, true>), grid, block, lds_t, s, sf, ch, b,
+                           first);
+      return;
+    }
+  }
   if constexpr (NZ == 2) {
     if (ch.n_hd == 12 && ch.zeta_int[0] == 1 && ch.zeta_int[1] == 4) {
       if (b.cap == kCapMin) {
@@ -1307,12 +1586,13 @@ void bwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int fir
 }  // namespace
 
 // n_local > 0: forward launch in job mode (counters + per-pair partial sums behind the fields)
-size_t v2_lds_bytes(bool backward, int cap, int n_local, int nspec) {
+// `triangles`: backward triangle build (+ the neighbours' S0 coefficients, 5 doubles per pair slot)
+size_t v2_lds_bytes(bool backward, int cap, int n_local, int nspec, bool triangles) {
   if (!backward && n_local > 0)
     return v2_counter_offset(cap) + kJobCtlBytes + (size_t)n_local * v2_pcols(cap, nspec) * sizeof(double);
   if (backward)  // fields, cstart gap, three accumulator planes, the per-centre tables
     return (size_t)cap * kNF * sizeof(double) + cap + 3 * (size_t)cap * sizeof(double) +
-           kMaxCentersPerBlock * (5 + kRTab) * sizeof(double);
+           kMaxCentersPerBlock * (5 + kRTab) * sizeof(double) + (triangles ? 5 * (size_t)cap * sizeof(double) : 0);
   return (size_t)cap * kNF * sizeof(double) + 3 * (size_t)(2 * cap + kRingPad) * sizeof(float) + cap;
 }
 int v2_job_stride(int cap) { return v2_max_jobs(cap); }
@@ -1375,12 +1655,14 @@ void launch_g4_forward_v2(const SFParams &sf, const AngChunk &ch, int ng, int nz
   TA_DISPATCH_V2(fwd_t, sf, ch, b, geom, s);
 }
 
-void launch_backward_v2(const SFParams &sf, const AngChunk &ch, int ng, int nz, bool first,
-                        const DeviceBatch &b, hipStream_t s) {
-  if (b.n_blk == 0) return;
+int launch_backward_v2(const SFParams &sf, const AngChunk &ch, int ng, int nz, bool first, bool triangles,
+                       const DeviceBatch &b, hipStream_t s) {
+  if (b.n_blk == 0) return 0;
   const int nspec = sf.n_elements;
   const int f = (first ? 1 : 0) | stagger_bits(b, "TA_STAGGER_BWD");
-  TA_DISPATCH_V2(bwd_t, sf, ch, b, f, s);
+  int variant = 0;
+  TA_DISPATCH_V2(bwd_t, sf, ch, b, f, triangles, variant, s);
+  return variant;
 }
 
 }  // namespace ta

@@ -364,6 +364,23 @@ class Engine:
         self._check(self._lib.ta_count_contributing_triples(self._handle, C.byref(n)))
         return int(n.value)
 
+    def count_owned_triangles(self) -> int:
+        """Contributing triples whose centre owns the triangle (`ta_count_owned_triangles`)."""
+        n = C.c_int64(0)
+        self._check(self._lib.ta_count_owned_triangles(self._handle, C.byref(n)))
+        return int(n.value)
+
+    def set_triangles(self, on: bool):
+        """Triangle-once angular backward pass where it applies (default) or the per-apex one
+        (`ta_set_triangles`); takes effect at the next evaluation."""
+        self._check(self._lib.ta_set_triangles(self._handle, 1 if on else 0))
+
+    def backward_variant(self) -> int:
+        """Angular backward builds of the last evaluation with forces: bit 0 per apex, bit 1 triangles."""
+        v = C.c_int32(0)
+        self._check(self._lib.ta_backward_variant(self._handle, C.byref(v)))
+        return int(v.value)
+
     def measure_hbm_copy(self, nbytes: int = 1 << 30, reps: int = 10) -> float:
         """Achievable device-to-device copy rate in GB/s (read + written bytes)."""
         g = C.c_double(0.0)
