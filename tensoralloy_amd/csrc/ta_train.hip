@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <stdexcept>
 
 #include "ta_device.h"
 #include "ta_mlp_tile.h"
@@ -27,6 +28,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 1024;  // persistent workgroups of the gradient kernel
+constexpr size_t kLdsLimit = 150 * 1024;  // dynamic LDS one workgroup may ask for (160 KB per CU)
 
 struct GradLayout {
   int w_off[kMaxLayers];  // offset of W_l (then b_l) inside one element's flat parameter block
@@ -397,6 +399,15 @@ __global__ __launch_bounds__(kThreads) void grad_reduce_kernel(const double *par
   grad[p] = s;
 }
 
+// dynamic LDS of the gradient kernels: `slabs` [16][stride] buffers (2: value; 4: value and tangent);
+// a network too wide for one workgroup is refused before anything is launched
+size_t grad_lds_bytes(const MlpDev &mlp, int slabs) {
+  const size_t bytes = (size_t)slabs * kMlpRows * mlp_stride(mlp) * sizeof(double);
+  if (bytes > kLdsLimit)
+    throw std::domain_error("MLP too wide for the LDS of the training tile (second-order pass: layers up to 288)");
+  return bytes;
+}
+
 GradLayout make_layout(const MlpDev &mlp) {
   GradLayout lay;
   int off = 0;
@@ -430,12 +441,12 @@ void launch_mlp_grad(const MlpDev &mlp, int activation, int ndim, const int32_t 
                      const DeviceBatch &b, const double *frame_coeff, double *scratch, double *partial,
                      double *grad, hipStream_t s) {
   const GradLayout lay = make_layout(mlp);
+  const size_t lds = grad_lds_bytes(mlp, 2);
   if (n_atoms == 0) {
     (void)hipMemsetAsync(grad, 0, (size_t)lay.n_params * sizeof(double), s);
     return;
   }
   const int stride = mlp_stride(mlp);
-  const size_t lds = 2 * (size_t)kMlpRows * stride * sizeof(double);
   const int blocks = std::min((n_atoms + kMlpRows - 1) / kMlpRows, kMaxBlocks);
   hipLaunchKernelGGL(mlp_grad_kernel, dim3((unsigned)blocks), dim3(kThreads), lds, s, mlp, lay, activation,
                      ndim, atoms, n_atoms, b.G, b.frame_of_atom, frame_coeff, nullptr, scratch, partial, stride);
@@ -454,12 +465,12 @@ void launch_mlp_grad2(const MlpDev &mlp, int activation, int ndim, const int32_t
                       const DeviceBatch &b, const double *dG, const double *frame_coeff, double *scratch,
                       double *partial, double *grad, hipStream_t s, double *kappa_out) {
   const GradLayout lay = make_layout(mlp);
+  const size_t lds = grad_lds_bytes(mlp, 4);
   if (n_atoms == 0) {
     (void)hipMemsetAsync(grad, 0, (size_t)lay.n_params * sizeof(double), s);
     return;
   }
   const int stride = mlp_stride(mlp);
-  const size_t lds = 4 * (size_t)kMlpRows * stride * sizeof(double);
   const int blocks = std::min((n_atoms + kMlpRows - 1) / kMlpRows, kMaxBlocks);
   hipLaunchKernelGGL(mlp_grad2_kernel, dim3((unsigned)blocks), dim3(kThreads), lds, s, mlp, lay, activation,
                      ndim, atoms, n_atoms, b.G, dG, b.frame_of_atom, frame_coeff, nullptr, scratch, partial, stride, kappa_out);
@@ -498,12 +509,12 @@ void launch_mlp_grad_rows(const MlpDev &mlp, int activation, const int32_t *atom
                           const double *frame_coeff, double *scratch, double *partial, double *grad,
                           hipStream_t s) {
   const GradLayout lay = make_layout(mlp);
+  const size_t lds = grad_lds_bytes(mlp, 2);
   if (n_rows == 0) {
     (void)hipMemsetAsync(grad, 0, (size_t)lay.n_params * sizeof(double), s);
     return;
   }
   const int stride = mlp_stride(mlp);
-  const size_t lds = 2 * (size_t)kMlpRows * stride * sizeof(double);
   const int blocks = std::min((n_rows + kMlpRows - 1) / kMlpRows, kMaxBlocks);
   hipLaunchKernelGGL(mlp_grad_kernel, dim3((unsigned)blocks), dim3(kThreads), lds, s, mlp, lay, activation, 1,
                      atoms, n_rows, x, frame_of_atom, frame_coeff, row_coeff, scratch, partial, stride);
@@ -520,12 +531,12 @@ void launch_mlp_grad2_rows(const MlpDev &mlp, int activation, const int32_t *ato
                            const double *frame_coeff, double *scratch, double *partial, double *grad,
                            hipStream_t s) {
   const GradLayout lay = make_layout(mlp);
+  const size_t lds = grad_lds_bytes(mlp, 4);
   if (n_rows == 0) {
     (void)hipMemsetAsync(grad, 0, (size_t)lay.n_params * sizeof(double), s);
     return;
   }
   const int stride = mlp_stride(mlp);
-  const size_t lds = 4 * (size_t)kMlpRows * stride * sizeof(double);
   const int blocks = std::min((n_rows + kMlpRows - 1) / kMlpRows, kMaxBlocks);
   hipLaunchKernelGGL(mlp_grad2_kernel, dim3((unsigned)blocks), dim3(kThreads), lds, s, mlp, lay, activation, 1,
                      atoms, n_rows, x, xdot, frame_of_atom, frame_coeff, row_coeff, scratch, partial, stride, (double *)nullptr);
