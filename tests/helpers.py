@@ -245,16 +245,17 @@ from {module} import {func} as cases
 out = []
 for name, nn, frames in cases():
     with Engine(nn) as eng:
-        res = eng.evaluate(frames, descriptors=True)
+        res = eng.evaluate(frames, descriptors={descriptors!r})
         nnl = int(eng.info.nnl_max)
     out.append(dict(name=name, nnl=nnl, res=[{{k: np.asarray(v).tolist() for k, v in r.items()}} for r in res]))
 print(json.dumps(out))
 """
 
 
-def run_child(cases, env, timeout=300):
+def run_child(cases, env, timeout=300, descriptors=True):
     """Evaluate the (name, model, frames) list that `cases` ("module:function") returns in a fresh Python
     process with `env` added to the environment: the library reads its A/B switches once per process.
+    `descriptors=False` for models without descriptors (EAM / ADP / eam/fs).
     Returns [{"name", "nnl", "res": per-frame result dicts}]."""
     import json
     import os
@@ -262,7 +263,8 @@ def run_child(cases, env, timeout=300):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     module, func = cases.split(":")
-    p = subprocess.run([sys.executable, "-c", CHILD.format(root=root, module=module, func=func)],
+    code = CHILD.format(root=root, module=module, func=func, descriptors=bool(descriptors))
+    p = subprocess.run([sys.executable, "-c", code],
                        env=dict(os.environ, **env), cwd=root, capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([line for line in p.stdout.splitlines() if line.startswith("[")][-1])

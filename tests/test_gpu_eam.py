@@ -8,13 +8,28 @@ from tests.test_gpu_sf import _alloy, E_TOL, F_TOL, W_TOL
 pytestmark = pytest.mark.gpu
 
 
+def _fp64(got, ref):
+    """What fp64 kernels owe an fp64 reference (tests/test_gpu_eam_dispatch.py): energies to
+    1e-9 x max(1, |E|), forces to 1e-9 x max(1, max|F|), virial to 1e-8 x max(1, max|W|)."""
+    e_scale = max(1.0, abs(ref["energy"]))
+    dev = dict(E=abs(got["energy"] - ref["energy"]), e=np.abs(got["atomic"] - ref["atomic"]).max(),
+               F=np.abs(got["forces"] - ref["forces"]).max(initial=0.0),
+               W=np.abs(got["virial"] - ref["virial"]).max())
+    assert dev["E"] < 1e-9 * e_scale and dev["e"] < 1e-9 * e_scale, dev
+    assert dev["F"] < 1e-9 * max(1.0, np.abs(ref["forces"]).max(initial=0.0)), dev
+    assert dev["W"] < 1e-8 * max(1.0, np.abs(ref["virial"]).max()), dev
+
+
 def _compare(nn, atoms_list):
     """GPU against the oracle at north_star's tolerances. Models with nn pair functions run twice:
     through the Hermite tables the library builds from the networks (the default for inference,
     `ta_set_nn_tables`) and with the networks evaluated exactly for every pair; the two must agree
     far inside the tolerances (the tables are an implementation of the same functions, not a model
-    change): 1e-9 eV per structure, 1e-8 eV/A."""
+    change): 1e-9 eV per structure, 1e-8 eV/A. Analytic functions, spline tables and exact networks
+    are also held to the fp64 bounds of `_fp64`."""
     from tensoralloy_amd import Engine
+    from tests.test_gpu_eam_dispatch import pair_nets
+    tabulated = bool(pair_nets(nn))   # `res` went through the Hermite tables of nn pair functions
     with Engine(nn) as eng:
         res = eng.evaluate(atoms_list)
         eng.set_nn_tables(False)
@@ -27,6 +42,9 @@ def _compare(nn, atoms_list):
             assert np.abs(got["forces"] - o["forces"]).max() < F_TOL
             assert np.abs(got["virial"] - o["virial"]).max() < W_TOL
             assert np.abs(got["stress"] - o["stress_voigt"]).max() < 1e-8
+        _fp64(x, o)
+        if not tabulated:
+            _fp64(r, o)
         assert abs(r["energy"] - x["energy"]) < 1e-9
         assert np.abs(r["forces"] - x["forces"]).max() < 1e-8
         assert np.abs(r["virial"] - x["virial"]).max() < 1e-7

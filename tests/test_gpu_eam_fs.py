@@ -40,6 +40,12 @@ def _check(got, ref, e_tol, f_tol, w_tol):
     assert np.abs(got["virial"] - ref["virial"]).max() < w_tol, np.abs(got["virial"] - ref["virial"]).max()
 
 
+def _fp64(got, ref):
+    """The fp64 bounds of tests/test_gpu_eam_dispatch.py, for spline tables and exact networks."""
+    from tests.test_gpu_eam import _fp64 as bounds
+    bounds(got, ref)
+
+
 def _random_nn(elements, rcut=6.0, potentials=None, hidden_sizes=None, seed=5, out_scale=0.05):
     """An FS model with "nn" functions at the scale of physical ones (as tests/helpers.make_eam)."""
     from tensoralloy_amd import UniversalTransformer
@@ -61,6 +67,7 @@ def test_tabulated_fs_against_the_restatement(lib, tmp_path):
     with Engine(nn) as eng:
         got = eng.evaluate([atoms])[0]
     _check(got, fs_evaluate(nn, atoms), 1e-9, 1e-10, 1e-8)
+    _fp64(got, fs_evaluate(nn, atoms))
 
 
 def test_pure_fe_against_the_files_physics(lib, tmp_path):
@@ -104,6 +111,7 @@ def test_asymmetric_densities_from_a_file(lib, tmp_path):
     with Engine(nn) as eng:
         for atoms, got in zip(frames, eng.evaluate(frames)):
             _check(got, fs_evaluate(nn, atoms), 1e-9, 1e-10, 1e-8)
+            _fp64(got, fs_evaluate(nn, atoms))
 
 
 @pytest.mark.parametrize("generic", [False, True])
@@ -125,6 +133,7 @@ def test_asymmetric_nn_densities(lib, monkeypatch, generic):
             ref = fs_evaluate(nn, atoms)
             for got in (t, x, t2):
                 _check(got, ref, E_TOL, F_TOL, W_TOL)
+            _fp64(x, ref)
             assert abs(t["energy"] - x["energy"]) < 1e-9
 
 
@@ -144,6 +153,7 @@ def test_nn_and_spline_functions_in_one_model(lib, tmp_path):
     ref = fs_evaluate(nn, atoms)
     _check(got, ref, E_TOL, F_TOL, W_TOL)
     _check(exact, ref, E_TOL, F_TOL, W_TOL)
+    _fp64(exact, ref)
 
 
 def test_batches_and_the_md_path(lib, tmp_path):
