@@ -13,8 +13,8 @@
 // and the tf.gradients that give forces and virial (nn/basic.py:277-331).
 //
 // Two passes over the packed pair list:
-//   eam_atom_kernel  16 / 32 / 64 lanes per atom: pair geometry (written to the pair records),
-//                    rho_i, sum phi, and (ADP) the
+//   eam_atom_kernel  16 / 32 lanes per atom: pair geometry (computed, or read from the records of
+//                    eam_geom_kernel for nn pair functions), rho_i, sum phi, and (ADP) the
 //                    dipole / quadrupole moments per neighbour species; lane 0
 //                    applies the embedding function and stores F'(rho_i).
 //   eam_force_kernel (plain EAM) forces and per-atom virial of a centre in one pass.
@@ -43,6 +43,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "ta_device.h"
@@ -113,6 +114,18 @@ __device__ __forceinline__ void spline_eval(const TabDev &t, double x, double &f
   const double2 a = c[0], b = c[1];
   f = fma(fma(fma(b.y, tt, b.x), tt, a.y), tt, a.x);
   df = fma(fma(3.0 * b.y, tt, 2.0 * b.x), tt, a.y);
+}
+// the same at a dual abscissa (Hessian-vector products): df carries f''(x) x-dot
+__device__ __forceinline__ void spline_eval(const TabDev &t, Dual x, Dual &f, Dual &df) {
+  int k = (int)(x.v * t.inv_dx);
+  k = k < 0 ? 0 : (k > t.n - 2 ? t.n - 2 : k);
+  const double tt = x.v - (double)k * t.dx;
+  const double2 *c = reinterpret_cast<const double2 *>(t.c + 4 * (size_t)k);
+  const double2 a = c[0], b = c[1];
+  const double d1 = fma(fma(3.0 * b.y, tt, 2.0 * b.x), tt, a.y);
+  const double d2 = fma(6.0 * b.y, tt, 2.0 * b.x);
+  f = make_dual(fma(fma(fma(b.y, tt, b.x), tt, a.y), tt, a.x), d1 * x.d);
+  df = make_dual(d1, d2 * x.d);
 }
 
 // columns of the per-pair function buffer `pf` (each `ps` doubles long)
@@ -295,11 +308,12 @@ __device__ __forceinline__ void morse_fn(R r, T d, T g, T r0, T &f, T &df) {
 
 // OTHER = false: every analytic function of the model is of the Zjw04 family (the kind tests and the
 // pow calls of the other potentials stay out of the kernels: -9 % on the plain Zjw04 path otherwise)
-template <bool OTHER, typename T>
-__device__ __forceinline__ void el_rho(const EamParams &P, const T (*el)[20], int e, double r, T &f, T &df) {
+// R: the distance's type as in zhou_exp (a Dual distance is only needed, and only compiles, without OTHER)
+template <bool OTHER, typename T, typename R = double>
+__device__ __forceinline__ void el_rho(const EamParams &P, const T (*el)[20], int e, R r, T &f, T &df) {
   const T *p = el[e];
-  if (!OTHER) {
-    zjw_rho<T>(p, r, f, df);
+  if constexpr (!OTHER) {
+    zjw_rho<T, R>(p, r, f, df);
   } else if (P.el_kind[e] == 1) {
     const T t = p[0] / r, t2 = t * t;
     f = t2 * t2 * t2;
@@ -322,12 +336,12 @@ __device__ __forceinline__ void el_rho(const EamParams &P, const T (*el)[20], in
   }
 }
 
-template <bool OTHER, typename T>
+template <bool OTHER, typename T, typename R = double>
 __device__ __forceinline__ void pair_phi(const EamParams &P, const T (*el)[20], const T (*phx)[7], int sa, int sb,
-                                         double r, T &f, T &df) {
+                                         R r, T &f, T &df) {
   const int kind = (OTHER && sa == sb) ? P.el_kind[sa] : 0;
-  if (!OTHER) {
-    zjw_phi<T>(P, el, phx, sa, sb, r, f, df);
+  if constexpr (!OTHER) {
+    zjw_phi<T, R>(P, el, phx, sa, sb, r, f, df);
   } else if (kind == 1) {
     const T t = el[sa][1] / r, t2 = t * t, t4 = t2 * t2;
     f = t4 * t4 * t4;
@@ -356,7 +370,7 @@ __device__ __forceinline__ void pair_phi(const EamParams &P, const T (*el)[20], 
 template <bool OTHER, typename T>
 __device__ __forceinline__ void el_embed(const EamParams &P, const T (*el)[20], int e, T rho, T &F, T &dF) {
   const T *p = el[e];
-  if (!OTHER) {
+  if constexpr (!OTHER) {
     zjw_embed<T>(p, P.embed_kind[e], rho, F, dF);
   } else if (P.el_kind[e] == 1) {
     const T s = t_sqrt(rho);
@@ -378,50 +392,223 @@ __device__ __forceinline__ void el_embed(const EamParams &P, const T (*el)[20], 
 
 
 // (p1 exp(-p2 r) + p3) psi((r - rc)/h), psi(x) = x^4/(1+x^4) for x < 0  (generic.py:52-84)
-template <typename T>
-__device__ __forceinline__ void mishin_polar(double r, T p1, T p2, T p3, T rc, T h, T &f, T &df) {
-  const T z = (r - rc) / h;
+// T: the constants' type, R: the distance's (as in zhou_exp); V: Dual if either is
+template <typename T, typename R, typename V>
+__device__ __forceinline__ void mishin_polar(R r, T p1, T p2, T p3, T rc, T h, V &f, V &df) {
+  const V z = (r - rc) / h;
   if (t_val(z) >= 0.0) {
-    f = T{};
-    df = T{};
+    f = V{};
+    df = V{};
     return;
   }
-  const T zz = -z, z2 = zz * zz, z4 = z2 * z2;
-  const T den = 1.0 / (1.0 + z4);
-  const T psi = z4 * den;
-  const T dpsi = -4.0 * z2 * zz * den * den / h;
-  const T e = t_exp(-p2 * r);
-  const T left = p1 * e + p3;
+  const V zz = -z, z2 = zz * zz, z4 = z2 * z2;
+  const V den = 1.0 / (1.0 + z4);
+  const V psi = z4 * den;
+  const V dpsi = -4.0 * z2 * zz * den * den / h;
+  const V e = t_exp(-p2 * r);
+  const V left = p1 * e + p3;
   f = left * psi;
   df = -p1 * p2 * e * psi + left * dpsi;
 }
 
-// the same with the distance of type T as well (Hessian-vector products: r is dual, the constants plain)
-template <typename T>
-__device__ __forceinline__ void mishin_polar_r(T r, double p1, double p2, double p3, double rc, double h, T &f,
-                                               T &df) {
-  const T z = (r - rc) / h;
-  if (t_val(z) >= 0.0) {
-    f = T{};
-    df = T{};
-    return;
+// ---- pieces the kernels share ---------------------------------------------------------------------
+// pair geometry D = Rj - Ri + S.h, r^2 = D.D + eps (universal.py:448-474) from the centre's position ri,
+// the neighbour's rj, the shift S and the cell h of the frame; returns r^2
+__device__ __forceinline__ double pair_vector(const double *ri, const double *rj, const int *S, const double *h,
+                                              double eps, double (&D)[3]) {
+  const double sx = (double)S[0], sy = (double)S[1], sz = (double)S[2];
+  D[0] = (rj[0] - ri[0]) + (sx * h[0] + sy * h[3] + sz * h[6]);
+  D[1] = (rj[1] - ri[1]) + (sx * h[1] + sy * h[4] + sz * h[7]);
+  D[2] = (rj[2] - ri[2]) + (sx * h[2] + sy * h[5] + sz * h[8]);
+  return D[0] * D[0] + D[1] * D[1] + D[2] * D[2] + eps;
+}
+// the same for pair q of centre i, read from the batch
+__device__ __forceinline__ double pair_vector(const DeviceBatch &b, int64_t i, int64_t q, double eps,
+                                              double (&D)[3]) {
+  const int S[3] = {b.pair_shift[3 * (size_t)q], b.pair_shift[3 * (size_t)q + 1], b.pair_shift[3 * (size_t)q + 2]};
+  return pair_vector(b.pos + 3 * (size_t)i, b.pos + 3 * (size_t)b.pair_j[q], S,
+                     b.cells + 9 * (size_t)b.frame_of_atom[i], eps, D);
+}
+
+template <typename V>
+__device__ __forceinline__ V lift(double x) {
+  if constexpr (std::is_same<V, Dual>::value) return make_dual(x);
+  else return x;
+}
+
+// The functions of the pairs of one (centre species sa, neighbour species sb) segment, each with its
+// derivative, chosen per function by the masks of EamParams (read once, at the segment's head): the exact
+// network's value / derivative columns of `pf` at pair q (NN: kernels that run after the nn pair kernels),
+// the spline of `tabs`, or the analytic function of the constants `el`, `phx`, `pp` (double, or Dual with
+// one constant seeded). r is double, or Dual along a displacement (Hessian-vector products, where only
+// Zjw04 and MishinH functions occur). eam/fs (FS) has no analytic functions. Callers that use only f or
+// only f' leave the other to dead-code elimination.
+template <bool OTHER, bool FS, bool NN, typename T = double, typename U = double>
+struct SegmentFns {
+  const EamParams &P;
+  const TabDev *tabs;
+  const double *pf;
+  size_t ps;
+  const T (*el)[20];
+  const T (*phx)[7];
+  const U *pp;  // d1 d2 d3 q1 q2 q3 h rc of the pair type
+  int sa, sb, pt, kb, ka;  // pair type; rho_key of the pair and of the reverse pair
+  bool rho_nn, rho_tab, rev_tab, phi_nn, phi_tab, u_nn, u_tab, w_nn, w_tab;
+
+  template <typename V>
+  __device__ __forceinline__ void column(int col, int64_t q, V &f, V &df) const {
+    f = lift<V>(pf[(size_t)col * ps + q]);
+    df = lift<V>(pf[(size_t)(col + 1) * ps + q]);
   }
-  const T zz = -z, z2 = zz * zz, z4 = z2 * z2;
-  const T den = 1.0 / (1.0 + z4);
-  const T psi = z4 * den;
-  const T dpsi = -4.0 * z2 * zz * den * den / h;
-  const T e = t_exp(-(p2 * r));
-  const T left = p1 * e + p3;
-  f = left * psi;
-  df = -(p1 * p2) * e * psi + left * dpsi;
+  template <typename R, typename V>
+  __device__ __forceinline__ void spline(int slot, R r, V &f, V &df) const {
+    if constexpr (std::is_same<R, double>::value && !std::is_same<V, double>::value) {
+      double a, d;
+      spline_eval(tabs[slot], r, a, d);
+      f = lift<V>(a);
+      df = lift<V>(d);
+    } else {
+      spline_eval(tabs[slot], r, f, df);
+    }
+  }
+  // density function of the pair (alloy: of the NEIGHBOUR's element, alloy.py:176; eam/fs: of the
+  // ordered pair)
+  template <typename R, typename V>
+  __device__ __forceinline__ void rho(int64_t q, R r, V &f, V &df) const {
+    if (rho_nn) column(PF_RHO, q, f, df);
+    else if (FS || rho_tab) spline(slot_rho(kb), r, f, df);
+    else el_rho<OTHER, T, R>(P, el, sb, r, f, df);
+  }
+  // the reverse pair's (centre sb, neighbour sa); not for nn functions
+  template <typename R, typename V>
+  __device__ __forceinline__ void rho_rev(R r, V &f, V &df) const {
+    if (FS || rev_tab) spline(slot_rho(ka), r, f, df);
+    else el_rho<OTHER, T, R>(P, el, sa, r, f, df);
+  }
+  template <typename R, typename V>
+  __device__ __forceinline__ void phi(int64_t q, R r, V &f, V &df) const {
+    if (phi_nn) column(PF_PHI, q, f, df);
+    else if (FS || phi_tab) spline(slot_pair<FS>(P.nel, 1, pt), r, f, df);
+    else pair_phi<OTHER, T, R>(P, el, phx, sa, sb, r, f, df);
+  }
+  // ADP dipole (u) and quadrupole (w) functions (MishinH, mishin.py:62-66)
+  template <typename R, typename V>
+  __device__ __forceinline__ void u(int64_t q, R r, V &f, V &df) const {
+    if (u_nn) column(PF_U, q, f, df);
+    else if (u_tab) spline(slot_pair(P.nel, 2, pt), r, f, df);
+    else mishin_polar(r, pp[0], pp[1], pp[2], pp[7], pp[6], f, df);
+  }
+  template <typename R, typename V>
+  __device__ __forceinline__ void w(int64_t q, R r, V &f, V &df) const {
+    if (w_nn) column(PF_W, q, f, df);
+    else if (w_tab) spline(slot_pair(P.nel, 3, pt), r, f, df);
+    else mishin_polar(r, pp[3], pp[4], pp[5], pp[7], pp[6], f, df);
+  }
+};
+template <bool OTHER, bool FS, bool NN, typename T, typename U>
+__device__ __forceinline__ SegmentFns<OTHER, FS, NN, T, U> segment_fns(const EamParams &P, const T (*el)[20],
+                                                                        const T (*phx)[7], const U (*prs)[8],
+                                                                        int sa, int sb, const TabDev *tabs,
+                                                                        const double *pf = nullptr,
+                                                                        size_t ps = 0) {
+  const int nel = P.nel, pt = pair_type(sa, sb, nel);
+  const int kb = rho_key<FS>(nel, sa, sb), ka = rho_key<FS>(nel, sb, sa);
+  return {P, tabs, pf, ps, el, phx, prs[pt], sa, sb, pt, kb, ka,
+          NN && ((P.nn_rho >> kb) & 1u), (bool)((P.tab_rho >> kb) & 1u), (bool)((P.tab_rho >> ka) & 1u),
+          NN && ((P.nn_phi >> pt) & 1u), (bool)((P.tab_phi >> pt) & 1u),
+          NN && ((P.nn_u >> pt) & 1u), (bool)((P.tab_u >> pt) & 1u),
+          NN && ((P.nn_w >> pt) & 1u), (bool)((P.tab_w >> pt) & 1u)};
+}
+// with the model's own (double) constants
+template <bool OTHER, bool FS, bool NN>
+__device__ __forceinline__ SegmentFns<OTHER, FS, NN> segment_fns(const EamParams &P, int sa, int sb,
+                                                                  const TabDev *tabs, const double *pf = nullptr,
+                                                                  size_t ps = 0) {
+  return segment_fns<OTHER, FS, NN>(P, P.el, P.phi, P.pair, sa, sb, tabs, pf, ps);
+}
+// the embedding function of element e: table or analytic (networks are the callers' business)
+template <bool OTHER, bool FS, typename T, typename V>
+__device__ __forceinline__ void embed_fn(const EamParams &P, const T (*el)[20], const TabDev *tabs, int e, V rho,
+                                         V &F, V &dF) {
+  if (FS || ((P.tab_embed >> e) & 1u)) spline_eval(tabs[slot_embed<FS>(P.nel, e)], rho, F, dF);
+  else el_embed<OTHER, T>(P, el, e, rho, F, dF);
+}
+
+// The constants as Dual in LDS (el, and phx / prs where given), with tangent 1 on the flat index `seeded`
+// (el, then phx, then prs: eam_constant_count's order) and 0 elsewhere.
+__device__ __forceinline__ void dual_constants(const EamParams &P, Dual (*el)[20], Dual (*phx)[7], Dual (*prs)[8],
+                                               int seeded = -1) {
+  const int nel = P.nel, npt = nel * (nel + 1) / 2;
+  for (int t = threadIdx.x; t < nel * 20; t += blockDim.x)
+    el[t / 20][t % 20] = make_dual(P.el[t / 20][t % 20], t == seeded ? 1.0 : 0.0);
+  if (phx)
+    for (int t = threadIdx.x; t < npt * 7; t += blockDim.x)
+      phx[t / 7][t % 7] = make_dual(P.phi[t / 7][t % 7], 20 * nel + t == seeded ? 1.0 : 0.0);
+  if (prs)
+    for (int t = threadIdx.x; t < npt * 8; t += blockDim.x)
+      prs[t / 8][t % 8] = make_dual(P.pair[t / 8][t % 8], 20 * nel + 7 * npt + t == seeded ? 1.0 : 0.0);
+  __syncthreads();
+}
+
+// ADP moments of an (atom, neighbour species): m[0..2] = mu = sum u D, m[3..8] = lambda = sum w D (x) D in
+// the order xx yy zz yz xz xy (adp.py:315-392, :394-498)
+constexpr int kMomA[6] = {0, 1, 2, 1, 0, 0}, kMomB[6] = {0, 1, 2, 2, 2, 1};
+template <typename V>
+__device__ __forceinline__ void add_moments(V (&m)[9], V u, V w, const double *D) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) m[c] = u * D[c] + m[c];
+#pragma unroll
+  for (int c = 0; c < 6; ++c) m[3 + c] = w * D[kMomA[c]] * D[kMomB[c]] + m[3 + c];
+}
+// their tangents along T, the tangent of D: mu-dot = sum (u' rdot D + u T),
+// lambda-dot = sum (w' rdot D (x) D + w (T (x) D + D (x) T)); ur = u' rdot, wr = w' rdot
+template <typename V>
+__device__ __forceinline__ void add_moment_tangents(V (&md)[9], V u, V ur, V w, V wr, const double *D,
+                                                    const double *T) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) md[c] += ur * D[c] + u * T[c];
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    const int a = kMomA[c], b = kMomB[c];
+    md[3 + c] += wr * D[a] * D[b] + w * (T[a] * D[b] + D[a] * T[b]);
+  }
+}
+// stored as `mom` keeps them: Lambda = lambda - (tr lambda / 3) I
+__device__ __forceinline__ void store_moments(double *dst, const double (&m)[9]) {
+  const double nu = m[3] + m[4] + m[5];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) dst[k] = (k >= 3 && k < 6) ? m[k] - nu / 3.0 : m[k];
+}
+// 1/2 |mu|^2 + 1/2 sum_ab lambda_ab^2 - 1/6 (tr lambda)^2, per k-body term (adp.py:371-392, :458-492)
+template <typename V>
+__device__ __forceinline__ V adp_energy(const V (&m)[9]) {
+  const V nu = m[3] + m[4] + m[5];
+  return 0.5 * (m[0] * m[0] + m[1] * m[1] + m[2] * m[2]) +
+         0.5 * (m[3] * m[3] + m[4] * m[4] + m[5] * m[5] + 2.0 * (m[6] * m[6] + m[7] * m[7] + m[8] * m[8])) -
+         nu * nu / 6.0;
+}
+template <typename A, typename B>
+__device__ __forceinline__ auto dot3(const A *a, const B *b) {
+  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
+}
+// l = Lambda D of the stored moments m (m[3..8] = Lambda, symmetric)
+template <typename V, typename X>
+__device__ __forceinline__ void lambda_dot(const V *m, const X *D, V (&l)[3]) {
+  l[0] = m[3] * D[0] + m[8] * D[1] + m[7] * D[2];
+  l[1] = m[8] * D[0] + m[4] * D[1] + m[6] * D[2];
+  l[2] = m[7] * D[0] + m[6] * D[1] + m[5] * D[2];
 }
 
 // moments per (atom, neighbour species): mu[3], Lambda[6] = lambda - (tr lambda / 3) I
 // in the order xx yy zz yz xz xy
-// W lanes per atom (16: one DPP row, four atoms per wavefront; 64: one wavefront per atom): an atom
-// with n neighbours occupies ceil(n / W) W lane slots, so narrow groups waste fewer lanes (n = 90: 96
-// slots against 128) while wide ones put more wavefronts in flight for a single small frame.
+// W lanes per atom (16: one DPP row, four atoms per wavefront; 32 for ADP below 32768 atoms): an atom with
+// n neighbours occupies ceil(n / W) W lane slots, so narrow groups waste fewer lanes (n = 90: 96 slots
+// against 128) while wide ones put more wavefronts in flight for a single small frame.
 // FS: eam/fs densities rho_{centre species, neighbour species}; every function is nn or tabulated.
+// geom_done = 1: eam_geom_kernel has written the pair records (exact nn pair functions); otherwise D is
+// computed here and not stored (the one-pass force kernels recompute it from the neighbour's position and
+// the shift: positions stay in L2; 16 bytes of indices per pair instead of a 32-byte store here and a
+// 32-byte load there).
 template <bool OTHER, int W, bool FS = false>
 __global__ __launch_bounds__(kBlock) void eam_atom_kernel(EamParams P, DeviceBatch b, double *dF,
                                                           double *mom, double eps,
@@ -437,15 +624,9 @@ __global__ __launch_bounds__(kBlock) void eam_atom_kernel(EamParams P, DeviceBat
   double rho = 0.0, phis = 0.0, eadp = 0.0;
   for (int sb = 0; sb < nel; ++sb) {
     double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const int pt = pair_type(sA, sb, nel);
-    const double *pp = P.pair[pt];
-    const int rk = rho_key<FS>(nel, sA, sb);  // fixed per segment
-    const bool rho_nn = (P.nn_rho >> rk) & 1u, phi_nn = (P.nn_phi >> pt) & 1u;
-    const bool u_nn = (P.nn_u >> pt) & 1u, w_nn = (P.nn_w >> pt) & 1u;
-    const bool rho_tab = (P.tab_rho >> rk) & 1u, phi_tab = (P.tab_phi >> pt) & 1u;
-    const bool u_tab = (P.tab_u >> pt) & 1u, w_tab = (P.tab_w >> pt) & 1u;
+    const auto fn = segment_fns<OTHER, FS, true>(P, sA, sb, tabs, pf, ps);
     // like pairs of a Zjw04 element: rho and phi share an exponential and a quotient
-    const bool fused_aa = !FS && !OTHER && sb == sA && !rho_nn && !rho_tab && !phi_nn && !phi_tab;
+    const bool fused_aa = !FS && !OTHER && sb == sA && !fn.rho_nn && !fn.rho_tab && !fn.phi_nn && !fn.phi_tab;
     // The pair loop is a chain of dependent loads (pair_j -> position of j) in front of ~300
     // instructions, and a group makes several passes: the neighbour index and shift of the pass after
     // next and the neighbour position of the next pass are fetched before this pass is evaluated.
@@ -466,19 +647,17 @@ __global__ __launch_bounds__(kBlock) void eam_atom_kernel(EamParams P, DeviceBat
         for (int c = 0; c < 3; ++c) pn[c] = b.pos[3 * (size_t)jn + c];
     }
     for (; q < q1; q += W) {
-      // pair geometry D = Rj - Ri + S.h, r^2 = D.D + eps (universal.py:448-474), computed here and
-      // left in the pair record for the pair kernel and the force gather
-      double rec[5];
-      if (geom_done == 1) {  // eam_geom_kernel has been here
+      double D[3], r2;
+      if (geom_done == 1) {
         const double2 *src = pair_geom(b, (size_t)q);
         const double2 a = src[0], c = src[1];
-        rec[0] = a.x;
-        rec[1] = a.y;
-        rec[2] = c.x;
-        rec[3] = c.y;
+        D[0] = a.x;
+        D[1] = a.y;
+        D[2] = c.x;
+        r2 = c.y;
       } else {
         const double rj[3] = {pn[0], pn[1], pn[2]};
-        const double sx = (double)sn[0], sy = (double)sn[1], sz = (double)sn[2];
+        const int S[3] = {sn[0], sn[1], sn[2]};
         if (q + W < q1) {
           for (int c = 0; c < 3; ++c) pn[c] = b.pos[3 * (size_t)j2 + c];
           for (int c = 0; c < 3; ++c) sn[c] = s2[c];
@@ -487,84 +666,32 @@ __global__ __launch_bounds__(kBlock) void eam_atom_kernel(EamParams P, DeviceBat
           j2 = b.pair_j[q + 2 * W];
           for (int c = 0; c < 3; ++c) s2[c] = b.pair_shift[3 * (size_t)(q + 2 * W) + c];
         }
-        const double *h = b.cells + 9 * (size_t)b.frame_of_atom[i];
-        const double *ri = b.pos + 3 * (size_t)i;
-        rec[0] = (rj[0] - ri[0]) + (sx * h[0] + sy * h[3] + sz * h[6]);
-        rec[1] = (rj[1] - ri[1]) + (sx * h[1] + sy * h[4] + sz * h[7]);
-        rec[2] = (rj[2] - ri[2]) + (sx * h[2] + sy * h[5] + sz * h[8]);
-        rec[3] = rec[0] * rec[0] + rec[1] * rec[1] + rec[2] * rec[2] + eps;
-        rec[4] = 1.0 / sqrt(rec[3]);
-        if (geom_done == 2) {
-          // no record: the one-pass force kernels recompute D from the neighbour's position and the
-          // shift (positions stay in L2; 16 bytes of indices per pair instead of a 32-byte store here
-          // and a 32-byte load there)
-        } else if (b.rec4) {  // compact 32-byte record {D, r^2}: the readers recompute 1 / r
-          double2 *dst = reinterpret_cast<double2 *>(b.rec4 + 4 * (size_t)q);
-          dst[0] = make_double2(rec[0], rec[1]);
-          dst[1] = make_double2(rec[2], rec[3]);
-        } else {
-          double2 *dst = reinterpret_cast<double2 *>(b.rec + kRecDoubles * (size_t)q);
-          dst[0] = make_double2(rec[0], rec[1]);
-          dst[1] = make_double2(rec[2], rec[3]);
-          dst[2] = make_double2(rec[4], 0.0);
-        }
+        r2 = pair_vector(b.pos + 3 * (size_t)i, rj, S, b.cells + 9 * (size_t)b.frame_of_atom[i], eps, D);
       }
-      if (P.list_rc2 > 0.0 && !(rec[3] < P.list_rc2)) continue;  // beyond rc: not a neighbour
-      const double r = sqrt(rec[3]);
-      double f, df = 0.0, fp, dfp = 0.0;
+      if (P.list_rc2 > 0.0 && !(r2 < P.list_rc2)) continue;  // beyond rc: not a neighbour
+      const double r = sqrt(r2);
+      double f, df, fp, dfp;
       if (fused_aa) {
         zjw_rho_phi_aa<double>(P.el[sb], r, f, df, fp, dfp);
       } else {
-        // density function of the NEIGHBOUR's element (alloy.py:176); eam/fs: of the ordered pair
-        if (rho_nn) f = pf[PF_RHO * ps + q];
-        else if (FS || rho_tab) spline_eval(tabs[slot_rho(rk)], r, f, df);
-        else el_rho<OTHER, double>(P, P.el, sb, r, f, df);
-        if (phi_nn) fp = pf[PF_PHI * ps + q];
-        else if (FS || phi_tab) spline_eval(tabs[slot_pair<FS>(nel, 1, pt)], r, fp, dfp);
-        else pair_phi<OTHER, double>(P, P.el, P.phi, sA, sb, r, fp, dfp);
+        fn.rho(q, r, f, df);
+        fn.phi(q, r, fp, dfp);
       }
       rho += f;
       phis += fp;
       if (P.adp) {
-        const double dx = rec[0], dy = rec[1], dz = rec[2];
         double u, du, w, dw;
-        if (u_nn) u = pf[PF_U * ps + q];
-        else if (u_tab) spline_eval(tabs[slot_pair(nel, 2, pt)], r, u, du);
-        else mishin_polar<double>(r, pp[0], pp[1], pp[2], pp[7], pp[6], u, du);
-        if (w_nn) w = pf[PF_W * ps + q];
-        else if (w_tab) spline_eval(tabs[slot_pair(nel, 3, pt)], r, w, dw);
-        else mishin_polar<double>(r, pp[3], pp[4], pp[5], pp[7], pp[6], w, dw);
-        m[0] = fma(u, dx, m[0]);
-        m[1] = fma(u, dy, m[1]);
-        m[2] = fma(u, dz, m[2]);
-        m[3] = fma(w * dx, dx, m[3]);
-        m[4] = fma(w * dy, dy, m[4]);
-        m[5] = fma(w * dz, dz, m[5]);
-        m[6] = fma(w * dy, dz, m[6]);
-        m[7] = fma(w * dx, dz, m[7]);
-        m[8] = fma(w * dx, dy, m[8]);
+        fn.u(q, r, u, du);
+        fn.w(q, r, w, dw);
+        add_moments(m, u, w, D);
       }
     }
     if (P.adp) {
 #pragma unroll
       for (int k = 0; k < 9; ++k) m[k] = group_sum<W>(m[k]);
       if (lane == 0) {
-        const double nu = m[3] + m[4] + m[5];
-        // 1/2 |mu|^2 + 1/2 sum_ab lambda_ab^2 - 1/6 (tr lambda)^2, per k-body term (adp.py:371-392, :458-492)
-        eadp += 0.5 * (m[0] * m[0] + m[1] * m[1] + m[2] * m[2]) +
-                0.5 * (m[3] * m[3] + m[4] * m[4] + m[5] * m[5] +
-                       2.0 * (m[6] * m[6] + m[7] * m[7] + m[8] * m[8])) -
-                nu * nu / 6.0;
-        double *dst = mom + ((size_t)i * nel + sb) * 9;
-        dst[0] = m[0];
-        dst[1] = m[1];
-        dst[2] = m[2];
-        dst[3] = m[3] - nu / 3.0;
-        dst[4] = m[4] - nu / 3.0;
-        dst[5] = m[5] - nu / 3.0;
-        dst[6] = m[6];
-        dst[7] = m[7];
-        dst[8] = m[8];
+        eadp += adp_energy(m);
+        store_moments(mom + ((size_t)i * nel + sb) * 9, m);
       }
     }
   }
@@ -576,8 +703,7 @@ __global__ __launch_bounds__(kBlock) void eam_atom_kernel(EamParams P, DeviceBat
       b.eatom[i] = 0.5 * phis + eadp;
     } else {
       double F, d;
-      if (FS || ((P.tab_embed >> sA) & 1u)) spline_eval(tabs[slot_embed<FS>(nel, sA)], rho, F, d);
-      else el_embed<OTHER, double>(P, P.el, sA, rho, F, d);
+      embed_fn<OTHER, FS>(P, P.el, tabs, sA, rho, F, d);
       b.eatom[i] = F + 0.5 * phis + eadp;  // eam.py:353-355, :568
       dF[i] = d;
     }
@@ -590,24 +716,17 @@ __global__ __launch_bounds__(kBlock) void eam_atom_kernel(EamParams P, DeviceBat
 __global__ __launch_bounds__(kBlock) void eam_geom_kernel(DeviceBatch b, double eps, double *rbuf) {
   const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (q >= b.n_pairs) return;
-  const int i = b.pair_i[q], j = b.pair_j[q];
-  const double *h = b.cells + 9 * (size_t)b.frame_of_atom[i];
-  const double sx = (double)b.pair_shift[3 * (size_t)q], sy = (double)b.pair_shift[3 * (size_t)q + 1],
-               sz = (double)b.pair_shift[3 * (size_t)q + 2];
-  const double *ri = b.pos + 3 * (size_t)i, *rj = b.pos + 3 * (size_t)j;
-  const double dx = (rj[0] - ri[0]) + (sx * h[0] + sy * h[3] + sz * h[6]);
-  const double dy = (rj[1] - ri[1]) + (sx * h[1] + sy * h[4] + sz * h[7]);
-  const double dz = (rj[2] - ri[2]) + (sx * h[2] + sy * h[5] + sz * h[8]);
-  const double r2 = dx * dx + dy * dy + dz * dz + eps;
+  double D[3];
+  const double r2 = pair_vector(b, b.pair_i[q], q, eps, D);
   const double r = sqrt(r2);
   if (b.rec4) {
     double2 *dst = reinterpret_cast<double2 *>(b.rec4 + 4 * (size_t)q);
-    dst[0] = make_double2(dx, dy);
-    dst[1] = make_double2(dz, r2);
+    dst[0] = make_double2(D[0], D[1]);
+    dst[1] = make_double2(D[2], r2);
   } else {
     double2 *dst = reinterpret_cast<double2 *>(b.rec + kRecDoubles * (size_t)q);
-    dst[0] = make_double2(dx, dy);
-    dst[1] = make_double2(dz, r2);
+    dst[0] = make_double2(D[0], D[1]);
+    dst[1] = make_double2(D[2], r2);
     dst[2] = make_double2(1.0 / r, 0.0);
   }
   rbuf[q] = r;
@@ -872,7 +991,7 @@ __global__ __launch_bounds__(kBlock) void eam_pair_kernel(EamParams P, DeviceBat
   const int sA = b.species[i], sa = b.species[b.pair_j[p]];
   const double2 *rec = pair_geom(b, (size_t)p);
   const double2 v0 = rec[0], v1 = rec[1];
-  const double dx = v0.x, dy = v0.y, dz = v1.x;
+  const double D[3] = {v0.x, v0.y, v1.x};
   if (P.list_rc2 > 0.0 && !(v1.y < P.list_rc2)) {  // beyond rc: not a neighbour
     b.g[4 * (size_t)p] = 0.0;
     b.g[4 * (size_t)p + 1] = 0.0;
@@ -881,52 +1000,26 @@ __global__ __launch_bounds__(kBlock) void eam_pair_kernel(EamParams P, DeviceBat
   }
   const double r = sqrt(v1.y);
   const double inv_r = 1.0 / r;  // the writer's 1 / sqrt(r^2)
-  double f, drho, dphi;
-  const int pt = pair_type(sA, sa, nel);
   // eam/fs: rho'_{sA sa} of this directed pair; the reverse pair carries F'(rho_j) rho'_{sa sA}
-  const int rk = rho_key<FS>(nel, sA, sa);
-  if ((P.nn_rho >> rk) & 1u) drho = pf[PF_DRHO * ps + p];
-  else if (FS || ((P.tab_rho >> rk) & 1u)) spline_eval(tabs[slot_rho(rk)], r, f, drho);
-  else el_rho<OTHER, double>(P, P.el, sa, r, f, drho);
-  if ((P.nn_phi >> pt) & 1u) dphi = pf[PF_DPHI * ps + p];
-  else if (FS || ((P.tab_phi >> pt) & 1u)) spline_eval(tabs[slot_pair<FS>(nel, 1, pt)], r, f, dphi);
-  else pair_phi<OTHER, double>(P, P.el, P.phi, sA, sa, r, f, dphi);
+  const auto fn = segment_fns<OTHER, FS, true>(P, sA, sa, tabs, pf, ps);
+  double f, drho, dphi;
+  fn.rho(p, r, f, drho);
+  fn.phi(p, r, f, dphi);
   // dE/dD of the directed pair: the centre's terms only; the reverse pair carries the other half
   double c = (dF[i] * drho + 0.5 * dphi) * inv_r;
-  double gx = c * dx, gy = c * dy, gz = c * dz;
+  double g[3] = {c * D[0], c * D[1], c * D[2]};
   if (P.adp) {
-    const double *pp = P.pair[pt];
     const double *m = mom + ((size_t)i * nel + sa) * 9;
-    double u, du, w, dw;
-    if ((P.nn_u >> pt) & 1u) {
-      u = pf[PF_U * ps + p];
-      du = pf[PF_DU * ps + p];
-    } else if ((P.tab_u >> pt) & 1u) {
-      spline_eval(tabs[slot_pair(nel, 2, pt)], r, u, du);
-    } else {
-      mishin_polar<double>(r, pp[0], pp[1], pp[2], pp[7], pp[6], u, du);
-    }
-    if ((P.nn_w >> pt) & 1u) {
-      w = pf[PF_W * ps + p];
-      dw = pf[PF_DW * ps + p];
-    } else if ((P.tab_w >> pt) & 1u) {
-      spline_eval(tabs[slot_pair(nel, 3, pt)], r, w, dw);
-    } else {
-      mishin_polar<double>(r, pp[3], pp[4], pp[5], pp[7], pp[6], w, dw);
-    }
-    const double muD = m[0] * dx + m[1] * dy + m[2] * dz;
-    const double lx = m[3] * dx + m[8] * dy + m[7] * dz;
-    const double ly = m[8] * dx + m[4] * dy + m[6] * dz;
-    const double lz = m[7] * dx + m[6] * dy + m[5] * dz;
-    const double DLD = dx * lx + dy * ly + dz * lz;
-    const double k = (muD * du + DLD * dw) * inv_r;
-    gx += k * dx + u * m[0] + 2.0 * w * lx;
-    gy += k * dy + u * m[1] + 2.0 * w * ly;
-    gz += k * dz + u * m[2] + 2.0 * w * lz;
+    double u, du, w, dw, l[3];
+    fn.u(p, r, u, du);
+    fn.w(p, r, w, dw);
+    lambda_dot(m, D, l);
+    const double k = (dot3(m, D) * du + dot3(D, l) * dw) * inv_r;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) g[c] += k * D[c] + u * m[c] + 2.0 * w * l[c];
   }
-  b.g[4 * (size_t)p] = gx;
-  b.g[4 * (size_t)p + 1] = gy;
-  b.g[4 * (size_t)p + 2] = gz;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) b.g[4 * (size_t)p + c] = g[c];
 }
 
 // Plain EAM (no dipole / quadrupole terms, no nn pair functions): forces and per-atom virial in ONE
@@ -935,51 +1028,32 @@ __global__ __launch_bounds__(kBlock) void eam_pair_kernel(EamParams P, DeviceBat
 // and the reverse pair has the same r and -D, so g[rev p] = -(F'(rho_j) rho'_a(r) + phi'_ab(r) / 2) D / r:
 // it is recomputed from an 8-byte gather of F'(rho_j) instead of a 32-byte random gather of a stored
 // g[rev p]; neither g nor the reverse-pair index is touched (eam.py:495-570 differentiated;
-// basic.py:277-331). One wavefront per atom, 16 atoms per workgroup (= one record of `bpart`).
-// W lanes per atom (see eam_atom_kernel), 16 atoms per workgroup (= one record of `bpart`).
-// The geometry of a pair in the one-pass force kernels: from the pair record (`from_pos` = 0) or
-// recomputed with the expressions of eam_atom_kernel from the neighbour's position and the shift,
-// which are prefetched one pass ahead as raw values (the arithmetic waits for them only when the pass
-// that needs them starts).
+// basic.py:277-331). W lanes per atom (see eam_atom_kernel), 16 atoms per workgroup (= one record of
+// `bpart`). The geometry of a pair is recomputed with pair_vector from the neighbour's position and the
+// shift, which are prefetched one pass ahead as raw values (the arithmetic waits for them only when the
+// pass that needs them starts).
 struct PairFetch {
-  double2 n0, n1;  // record, or {x_j, y_j}, {z_j, -}
+  double2 n0, n1;  // {x_j, y_j}, {z_j, -}
   int s[3];
 };
-__device__ __forceinline__ void fetch_pair(const DeviceBatch &b, int from_pos, int q, int j, PairFetch &f) {
-  if (from_pos) {
-    const double *rj = b.pos + 3 * (size_t)j;
-    f.n0 = make_double2(rj[0], rj[1]);
-    f.n1 = make_double2(rj[2], 0.0);
+__device__ __forceinline__ void fetch_pair(const DeviceBatch &b, int q, int j, PairFetch &f) {
+  const double *rj = b.pos + 3 * (size_t)j;
+  f.n0 = make_double2(rj[0], rj[1]);
+  f.n1 = make_double2(rj[2], 0.0);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) f.s[c] = b.pair_shift[3 * (size_t)q + c];
-  } else {
-    const double2 *rec = pair_geom(b, (size_t)q);
-    f.n0 = rec[0];
-    f.n1 = rec[1];
-  }
+  for (int c = 0; c < 3; ++c) f.s[c] = b.pair_shift[3 * (size_t)q + c];
 }
-__device__ __forceinline__ void pair_vector(const PairFetch &f, int from_pos, const double *ri, const double *h,
-                                            double eps, double &dx, double &dy, double &dz, double &r2) {
-  if (from_pos) {
-    const double sx = (double)f.s[0], sy = (double)f.s[1], sz = (double)f.s[2];
-    dx = (f.n0.x - ri[0]) + (sx * h[0] + sy * h[3] + sz * h[6]);
-    dy = (f.n0.y - ri[1]) + (sx * h[1] + sy * h[4] + sz * h[7]);
-    dz = (f.n1.x - ri[2]) + (sx * h[2] + sy * h[5] + sz * h[8]);
-    r2 = dx * dx + dy * dy + dz * dz + eps;
-  } else {
-    dx = f.n0.x;
-    dy = f.n0.y;
-    dz = f.n1.x;
-    r2 = f.n1.y;
-  }
+__device__ __forceinline__ double pair_vector(const PairFetch &f, const double *ri, const double *h, double eps,
+                                              double (&D)[3]) {
+  const double rj[3] = {f.n0.x, f.n0.y, f.n1.x};
+  return pair_vector(ri, rj, f.s, h, eps, D);
 }
 
 // FS: eam/fs, g[p] - g[rev p] = (F'(rho_i) rho'_{sA sb}(r) + F'(rho_j) rho'_{sb sA}(r) + phi'(r)) D / r;
 // both density slots are fixed per neighbour-species segment.
 template <bool OTHER, int W, bool FS = false>
 __global__ __launch_bounds__(16 * W) void eam_force_kernel(EamParams P, DeviceBatch b, const double *dF,
-                                                           const TabDev *__restrict__ tabs, int from_pos,
-                                                           double eps) {
+                                                           const TabDev *__restrict__ tabs, double eps) {
   const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x / W);
   const int lane = threadIdx.x & (W - 1);
   const bool active = i < b.n_atoms;
@@ -989,13 +1063,10 @@ __global__ __launch_bounds__(16 * W) void eam_force_kernel(EamParams P, DeviceBa
     const int sA = b.species[i];
     const double dFi = dF[i];
     const int32_t *seg = b.seg_start + (size_t)i * (nel + 1);
-    const bool rhoA_tab = (P.tab_rho >> sA) & 1u;
     const double *hcell = b.cells + 9 * (size_t)b.frame_of_atom[i];
     const double ri[3] = {b.pos[3 * (size_t)i], b.pos[3 * (size_t)i + 1], b.pos[3 * (size_t)i + 2]};
     for (int sb = 0; sb < nel; ++sb) {
-      const int pt = pair_type(sA, sb, nel);
-      const int kB = rho_key<FS>(nel, sA, sb), kA = rho_key<FS>(nel, sb, sA);
-      const bool rhoB_tab = (P.tab_rho >> kB) & 1u, phi_tab = (P.tab_phi >> pt) & 1u;
+      const auto fn = segment_fns<OTHER, FS, false>(P, sA, sb, tabs);
       // as in eam_atom_kernel: the geometry and F'(rho_j) of the next pass and the neighbour index of the
       // pass after next are fetched before this pass is evaluated
       const int q1 = seg[sb + 1];
@@ -1007,7 +1078,7 @@ __global__ __launch_bounds__(16 * W) void eam_force_kernel(EamParams P, DeviceBa
       int j2 = 0;
       if (q < q1) {
         const int j = b.pair_j[q];
-        fetch_pair(b, from_pos, q, j, nx);
+        fetch_pair(b, q, j, nx);
         dFn = dF[j];
       }
       if (q + W < q1) j2 = b.pair_j[q + W];
@@ -1015,31 +1086,27 @@ __global__ __launch_bounds__(16 * W) void eam_force_kernel(EamParams P, DeviceBa
         const PairFetch cur = nx;
         const double dFj = dFn;
         if (q + W < q1) {
-          fetch_pair(b, from_pos, q + W, j2, nx);
+          fetch_pair(b, q + W, j2, nx);
           dFn = dF[j2];
         }
         if (q + 2 * W < q1) j2 = b.pair_j[q + 2 * W];
-        double2 v0, v1;
-        pair_vector(cur, from_pos, ri, hcell, eps, v0.x, v0.y, v1.x, v1.y);
-        if (P.list_rc2 > 0.0 && !(v1.y < P.list_rc2)) continue;  // beyond rc: not a neighbour
-        const double r = sqrt(v1.y);
-        double fn, drhoB, drhoA, dphi;
-        if (!FS && !OTHER && sb == sA && !rhoB_tab && !phi_tab) {
-          zjw_rho_phi_aa<double>(P.el[sb], r, fn, drhoB, fn, dphi);
+        double d[3];
+        const double r2 = pair_vector(cur, ri, hcell, eps, d);
+        if (P.list_rc2 > 0.0 && !(r2 < P.list_rc2)) continue;  // beyond rc: not a neighbour
+        const double r = sqrt(r2);
+        double unused, drhoB, drhoA, dphi;
+        if (!FS && !OTHER && sb == sA && !fn.rho_tab && !fn.phi_tab) {
+          zjw_rho_phi_aa<double>(P.el[sb], r, unused, drhoB, unused, dphi);
           drhoA = drhoB;
         } else {
-          if (FS || rhoB_tab) spline_eval(tabs[slot_rho(kB)], r, fn, drhoB);
-          else el_rho<OTHER, double>(P, P.el, sb, r, fn, drhoB);
+          fn.rho(q, r, unused, drhoB);
           if (sb == sA) drhoA = drhoB;
-          else if (FS || rhoA_tab) spline_eval(tabs[slot_rho(kA)], r, fn, drhoA);
-          else el_rho<OTHER, double>(P, P.el, sA, r, fn, drhoA);
-          if (FS || phi_tab) spline_eval(tabs[slot_pair<FS>(nel, 1, pt)], r, fn, dphi);
-          else pair_phi<OTHER, double>(P, P.el, P.phi, sA, sb, r, fn, dphi);
+          else fn.rho_rev(r, unused, drhoA);
+          fn.phi(q, r, unused, dphi);
         }
         const double inv_r = 1.0 / r;
         const double own = (dFi * drhoB + 0.5 * dphi) * inv_r;   // g[p] = own D
         const double both = own + (dFj * drhoA + 0.5 * dphi) * inv_r;  // g[p] - g[rev p] = both D
-        const double d[3] = {v0.x, v0.y, v1.x};
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           f[c] = fma(both, d[c], f[c]);
@@ -1069,8 +1136,7 @@ __global__ __launch_bounds__(16 * W) void eam_force_kernel(EamParams P, DeviceBa
 template <bool OTHER, int W>
 __global__ __launch_bounds__(16 * W) void adp_force_kernel(EamParams P, DeviceBatch b, const double *dF,
                                                            const double *__restrict__ mom,
-                                                           const TabDev *__restrict__ tabs, int from_pos,
-                                                           double eps) {
+                                                           const TabDev *__restrict__ tabs, double eps) {
   const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x / W);
   const int lane = threadIdx.x & (W - 1);
   const bool active = i < b.n_atoms;
@@ -1080,21 +1146,17 @@ __global__ __launch_bounds__(16 * W) void adp_force_kernel(EamParams P, DeviceBa
     const int sA = b.species[i];
     const double dFi = dF[i];
     const int32_t *seg = b.seg_start + (size_t)i * (nel + 1);
-    const bool rhoA_tab = (P.tab_rho >> sA) & 1u;
     const double *hcell = b.cells + 9 * (size_t)b.frame_of_atom[i];
     const double ri[3] = {b.pos[3 * (size_t)i], b.pos[3 * (size_t)i + 1], b.pos[3 * (size_t)i + 2]};
     for (int sb = 0; sb < nel; ++sb) {
-      const int pt = pair_type(sA, sb, nel);
-      const double *pp = P.pair[pt];
-      const bool rhoB_tab = (P.tab_rho >> sb) & 1u, phi_tab = (P.tab_phi >> pt) & 1u;
-      const bool u_tab = (P.tab_u >> pt) & 1u, w_tab = (P.tab_w >> pt) & 1u;
+      const auto fn = segment_fns<OTHER, false, false>(P, sA, sb, tabs);
       double mi[9];
       {
         const double *src = mom + ((size_t)i * nel + sb) * 9;
 #pragma unroll
         for (int k = 0; k < 9; ++k) mi[k] = src[k];
       }
-      // pipelined as eam_force_kernel: record, F'(rho_j) and the moments of j for the next pass
+      // pipelined as eam_force_kernel: geometry, F'(rho_j) and the moments of j for the next pass
       const int q1 = seg[sb + 1];
       int q = seg[sb] + lane;
       PairFetch nx;
@@ -1104,7 +1166,7 @@ __global__ __launch_bounds__(16 * W) void adp_force_kernel(EamParams P, DeviceBa
       int j2 = 0;
       if (q < q1) {
         const int j = b.pair_j[q];
-        fetch_pair(b, from_pos, q, j, nx);
+        fetch_pair(b, q, j, nx);
         dFn = dF[j];
         const double *src = mom + ((size_t)j * nel + sA) * 9;
 #pragma unroll
@@ -1118,61 +1180,45 @@ __global__ __launch_bounds__(16 * W) void adp_force_kernel(EamParams P, DeviceBa
 #pragma unroll
         for (int k = 0; k < 9; ++k) mj[k] = mn[k];
         if (q + W < q1) {
-          fetch_pair(b, from_pos, q + W, j2, nx);
+          fetch_pair(b, q + W, j2, nx);
           dFn = dF[j2];
           const double *src = mom + ((size_t)j2 * nel + sA) * 9;
 #pragma unroll
           for (int k = 0; k < 9; ++k) mn[k] = src[k];
         }
         if (q + 2 * W < q1) j2 = b.pair_j[q + 2 * W];
-        double2 v0, v1;
-        pair_vector(cur, from_pos, ri, hcell, eps, v0.x, v0.y, v1.x, v1.y);
-        if (P.list_rc2 > 0.0 && !(v1.y < P.list_rc2)) continue;  // beyond rc: not a neighbour
-        const double r = sqrt(v1.y);
-        double fn, drhoB, drhoA, dphi;
-        if (!OTHER && sb == sA && !rhoB_tab && !phi_tab) {
-          zjw_rho_phi_aa<double>(P.el[sb], r, fn, drhoB, fn, dphi);
+        double d[3];
+        const double r2 = pair_vector(cur, ri, hcell, eps, d);
+        if (P.list_rc2 > 0.0 && !(r2 < P.list_rc2)) continue;  // beyond rc: not a neighbour
+        const double r = sqrt(r2);
+        double unused, drhoB, drhoA, dphi;
+        if (!OTHER && sb == sA && !fn.rho_tab && !fn.phi_tab) {
+          zjw_rho_phi_aa<double>(P.el[sb], r, unused, drhoB, unused, dphi);
           drhoA = drhoB;
         } else {
-          if (rhoB_tab) spline_eval(tabs[slot_rho(sb)], r, fn, drhoB);
-          else el_rho<OTHER, double>(P, P.el, sb, r, fn, drhoB);
+          fn.rho(q, r, unused, drhoB);
           if (sb == sA) drhoA = drhoB;
-          else if (rhoA_tab) spline_eval(tabs[slot_rho(sA)], r, fn, drhoA);
-          else el_rho<OTHER, double>(P, P.el, sA, r, fn, drhoA);
-          if (phi_tab) spline_eval(tabs[slot_pair(nel, 1, pt)], r, fn, dphi);
-          else pair_phi<OTHER, double>(P, P.el, P.phi, sA, sb, r, fn, dphi);
+          else fn.rho_rev(r, unused, drhoA);
+          fn.phi(q, r, unused, dphi);
         }
         double u, du, wq, dw;
-        if (u_tab) spline_eval(tabs[slot_pair(nel, 2, pt)], r, u, du);
-        else mishin_polar<double>(r, pp[0], pp[1], pp[2], pp[7], pp[6], u, du);
-        if (w_tab) spline_eval(tabs[slot_pair(nel, 3, pt)], r, wq, dw);
-        else mishin_polar<double>(r, pp[3], pp[4], pp[5], pp[7], pp[6], wq, dw);
+        fn.u(q, r, u, du);
+        fn.w(q, r, wq, dw);
         const double inv_r = 1.0 / r;
-        const double dx = v0.x, dy = v0.y, dz = v1.x;
+        double li[3], lj[3];
+        lambda_dot(mi, d, li);
+        lambda_dot(mj, d, lj);
         // own side
-        const double muD = mi[0] * dx + mi[1] * dy + mi[2] * dz;
-        const double lx = mi[3] * dx + mi[8] * dy + mi[7] * dz;
-        const double ly = mi[8] * dx + mi[4] * dy + mi[6] * dz;
-        const double lz = mi[7] * dx + mi[6] * dy + mi[5] * dz;
-        const double ci = (dFi * drhoB + 0.5 * dphi) * inv_r +
-                          (muD * du + (dx * lx + dy * ly + dz * lz) * dw) * inv_r;
-        const double g[3] = {ci * dx + u * mi[0] + 2.0 * wq * lx, ci * dy + u * mi[1] + 2.0 * wq * ly,
-                             ci * dz + u * mi[2] + 2.0 * wq * lz};
+        const double ci = (dFi * drhoB + 0.5 * dphi) * inv_r + (dot3(mi, d) * du + dot3(d, li) * dw) * inv_r;
         // reverse pair: centre j, -D
-        const double muDj = mj[0] * dx + mj[1] * dy + mj[2] * dz;
-        const double jx = mj[3] * dx + mj[8] * dy + mj[7] * dz;
-        const double jy = mj[8] * dx + mj[4] * dy + mj[6] * dz;
-        const double jz = mj[7] * dx + mj[6] * dy + mj[5] * dz;
-        const double cj = (dFj * drhoA + 0.5 * dphi) * inv_r +
-                          (-muDj * du + (dx * jx + dy * jy + dz * jz) * dw) * inv_r;
-        const double gr[3] = {-cj * dx + u * mj[0] - 2.0 * wq * jx, -cj * dy + u * mj[1] - 2.0 * wq * jy,
-                              -cj * dz + u * mj[2] - 2.0 * wq * jz};
-        const double d[3] = {dx, dy, dz};
+        const double cj = (dFj * drhoA + 0.5 * dphi) * inv_r + (-dot3(mj, d) * du + dot3(d, lj) * dw) * inv_r;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          f[c] += g[c] - gr[c];
+          const double g = ci * d[c] + u * mi[c] + 2.0 * wq * li[c];
+          const double gr = -cj * d[c] + u * mj[c] - 2.0 * wq * lj[c];
+          f[c] += g - gr;
 #pragma unroll
-          for (int e = 0; e < 3; ++e) w[3 * c + e] = fma(g[c], d[e], w[3 * c + e]);
+          for (int e = 0; e < 3; ++e) w[3 * c + e] = fma(g, d[e], w[3 * c + e]);
         }
       }
     }
@@ -1206,9 +1252,10 @@ __global__ __launch_bounds__(kBlock) void eam_tabulate_kernel(EamParams P, int n
     const double x = r[k];
     double f, df;
     if (row < nrho) {
-      if ((P.tab_rho >> row) & 1u) spline_eval(tabs[slot_rho(row)], x, f, df);
-      else if (FS) f = 0.0;
-      else el_rho<true, double>(P, P.el, row, x, f, df);
+      // the row's density function: rho_key = row (eam/fs: centre * nel + neighbour)
+      const auto fn = segment_fns<true, FS, false>(P, FS ? row / nel : 0, FS ? row % nel : row, tabs);
+      if (FS && !fn.rho_tab) f = 0.0;
+      else fn.rho(0, x, f, df);
       rho_of_r[(size_t)row * n_r + k] = f;
     } else {
       const int pt = row - nrho;
@@ -1217,18 +1264,14 @@ __global__ __launch_bounds__(kBlock) void eam_tabulate_kernel(EamParams P, int n
         rem -= nel - a;
         ++a;
       }
-      const int b2 = a + rem;
-      if ((P.tab_phi >> pt) & 1u) spline_eval(tabs[slot_pair<FS>(nel, 1, pt)], x, f, df);
-      else if (FS) f = 0.0;
-      else pair_phi<true, double>(P, P.el, P.phi, a, b2, x, f, df);
+      const auto fn = segment_fns<true, FS, false>(P, a, a + rem, tabs);
+      if (FS && !fn.phi_tab) f = 0.0;
+      else fn.phi(0, x, f, df);
       phi_of_r[(size_t)pt * n_r + k] = f;
       if (P.adp && u_of_r && w_of_r) {
-        const double *pp = P.pair[pt];
         double u, du, w, dw;
-        if ((P.tab_u >> pt) & 1u) spline_eval(tabs[slot_pair(nel, 2, pt)], x, u, du);
-        else mishin_polar<double>(x, pp[0], pp[1], pp[2], pp[7], pp[6], u, du);
-        if ((P.tab_w >> pt) & 1u) spline_eval(tabs[slot_pair(nel, 3, pt)], x, w, dw);
-        else mishin_polar<double>(x, pp[3], pp[4], pp[5], pp[7], pp[6], w, dw);
+        fn.u(0, x, u, du);
+        fn.w(0, x, w, dw);
         u_of_r[(size_t)pt * n_r + k] = u;
         w_of_r[(size_t)pt * n_r + k] = w;
       }
@@ -1239,9 +1282,8 @@ __global__ __launch_bounds__(kBlock) void eam_tabulate_kernel(EamParams P, int n
   if (j < (int64_t)nel * n_rho) {
     const int row = (int)(j / n_rho), k = (int)(j % n_rho);
     double F, dF;
-    if ((P.tab_embed >> row) & 1u) spline_eval(tabs[slot_embed<FS>(nel, row)], rho[k], F, dF);
-    else if (FS) F = 0.0;
-    else el_embed<true, double>(P, P.el, row, rho[k], F, dF);
+    if (FS && !((P.tab_embed >> row) & 1u)) F = 0.0;
+    else embed_fn<true, FS>(P, P.el, tabs, row, rho[k], F, dF);
     embed_of_rho[(size_t)row * n_rho + k] = F;
   }
 }
@@ -1275,15 +1317,14 @@ __global__ __launch_bounds__(kBlock) void eam_grad_coeff_kernel(EamParams P, Dev
       w = 0.5 * c;
     } else {
       const double2 *rec = pair_geom(b, (size_t)p);
-      const double dx = rec[0].x, dy = rec[0].y, dz = rec[1].x;
+      const double D[3] = {rec[0].x, rec[0].y, rec[1].x};
       const double *m = mom + ((size_t)i * nel + sb) * 9;
       if (cls == 2) {
-        w = c * (m[0] * dx + m[1] * dy + m[2] * dz);
+        w = c * dot3(m, D);
       } else {
-        const double lx = m[3] * dx + m[8] * dy + m[7] * dz;
-        const double ly = m[8] * dx + m[4] * dy + m[6] * dz;
-        const double lz = m[7] * dx + m[6] * dy + m[5] * dz;
-        w = c * (dx * lx + dy * ly + dz * lz);
+        double l[3];
+        lambda_dot(m, D, l);
+        w = c * dot3(D, l);
       }
     }
   }
@@ -1348,18 +1389,6 @@ __global__ __launch_bounds__(kBlock) void hermite_coef_kernel(int n, double dx, 
 // constants (nn/constraint/elastic.py:24-44), which round 2 took by central differences with a 1e-4 A
 // step. Plain EAM models whose functions are of the Zjw04 family or tabulated (setfl tables, nn pair
 // functions through their tables); everything else reports "unsupported" and keeps the differences.
-__device__ __forceinline__ void spline_eval_dual(const TabDev &t, Dual x, Dual &f, Dual &df) {
-  int k = (int)(x.v * t.inv_dx);
-  k = k < 0 ? 0 : (k > t.n - 2 ? t.n - 2 : k);
-  const double tt = x.v - (double)k * t.dx;
-  const double2 *c = reinterpret_cast<const double2 *>(t.c + 4 * (size_t)k);
-  const double2 a = c[0], b = c[1];
-  const double d1 = fma(fma(3.0 * b.y, tt, 2.0 * b.x), tt, a.y);
-  const double d2 = fma(6.0 * b.y, tt, 2.0 * b.x);
-  f = make_dual(fma(fma(fma(b.y, tt, b.x), tt, a.y), tt, a.x), d1 * x.d);
-  df = make_dual(d1, d2 * x.d);
-}
-
 struct HvpArgs {
   int n_dir, unit;     // unit: direction d displaces atom (first + d) / 3 along axis (first + d) % 3 (dR null)
   int first;
@@ -1389,20 +1418,28 @@ __device__ __forceinline__ void hvp_pair_tangent(const HvpArgs &a, const DeviceB
   }
 }
 
-// pass 1: F''(rho_i) rho_i-dot per (direction, atom); one wavefront per atom, grid.y = direction
-__global__ __launch_bounds__(kBlock) void eam_hvp_atom_kernel(EamParams P, DeviceBatch b, HvpArgs a,
-                                                              const TabDev *__restrict__ tabs, double *dFdot) {
+// pass 1: F''(rho_i) rho_i-dot per (direction, atom); one wavefront per atom, grid.y = direction.
+// ADP: adp_force_kernel's expression in dual arithmetic needs, besides D, r, rho', phi', F', the dipole /
+// quadrupole functions u, w (u', w' of a dual r carry u'' rdot, w'' rdot) and the moments of BOTH atoms of a
+// pair as duals, mu = (mu, mu-dot), Lambda = (Lambda, Lambda-dot): this pass also stores mu-dot, lambda-dot
+// (trace removed as in `mom`) per (direction, atom, neighbour species) in `momdot`.
+template <bool ADP>
+__global__ __launch_bounds__(kBlock) void hvp_atom_kernel(EamParams P, DeviceBatch b, HvpArgs a,
+                                                          const TabDev *__restrict__ tabs, double *dFdot,
+                                                          double *momdot) {
   __shared__ Dual el[kMaxEamElements][20];
+  dual_constants(P, el, nullptr, nullptr);
   const int nel = P.nel;
-  for (int t = threadIdx.x; t < nel * 20; t += kBlock) el[t / 20][t % 20] = make_dual(P.el[t / 20][t % 20]);
-  __syncthreads();
   const int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63, dir = blockIdx.y;
   if (i >= b.n_atoms) return;
   const int fr = b.frame_of_atom[i];
   double *out = dFdot + (size_t)dir * b.n_atoms + i;
+  double *mout = ADP ? momdot + (((size_t)dir * b.n_atoms + i) * nel) * 9 : nullptr;
   if (a.unit && b.frame_of_atom[(a.first + dir) / 3] != fr) {  // another structure of the batch: no coupling
     if (lane == 0) *out = 0.0;
+    if constexpr (ADP)
+      for (int k = lane; k < nel * 9; k += 64) mout[k] = 0.0;
     return;
   }
   const int sA = b.species[i];
@@ -1411,25 +1448,32 @@ __global__ __launch_bounds__(kBlock) void eam_hvp_atom_kernel(EamParams P, Devic
   const double *ri = b.pos + 3 * (size_t)i;
   double rho = 0.0, rhodot = 0.0;
   for (int sb = 0; sb < nel; ++sb) {
-    const bool rho_tab = (P.tab_rho >> sb) & 1u;
+    const auto fn = segment_fns<false, false, false>(P, sA, sb, tabs);
+    double md[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int q = seg[sb] + lane; q < seg[sb + 1]; q += 64) {
       const int j = b.pair_j[q];
       const int S[3] = {b.pair_shift[3 * (size_t)q], b.pair_shift[3 * (size_t)q + 1], b.pair_shift[3 * (size_t)q + 2]};
-      const double *rj = b.pos + 3 * (size_t)j;
-      double D[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) D[c] = (rj[c] - ri[c]) + (S[0] * h[c] + S[1] * h[3 + c] + S[2] * h[6 + c]);
-      const double r2 = D[0] * D[0] + D[1] * D[1] + D[2] * D[2] + a.eps;
+      double D[3], T[3];
+      const double r2 = pair_vector(ri, b.pos + 3 * (size_t)j, S, h, a.eps, D);
       if (P.list_rc2 > 0.0 && !(r2 < P.list_rc2)) continue;
       const double r = sqrt(r2);
-      double T[3];
       hvp_pair_tangent(a, b, dir, i, j, fr, S, T);
-      const double rdot = (D[0] * T[0] + D[1] * T[1] + D[2] * T[2]) / r;
+      const double rd = dot3(D, T) / r;
       double f, df;
-      if (rho_tab) spline_eval(tabs[slot_rho(sb)], r, f, df);
-      else zjw_rho<double>(P.el[sb], r, f, df);
+      fn.rho(q, r, f, df);
       rho += f;
-      rhodot = fma(df, rdot, rhodot);
+      rhodot = fma(df, rd, rhodot);
+      if constexpr (ADP) {
+        double u, du, w, dw;
+        fn.u(q, r, u, du);
+        fn.w(q, r, w, dw);
+        add_moment_tangents(md, u, du * rd, w, dw * rd, D, T);
+      }
+    }
+    if constexpr (ADP) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) md[k] = wave_sum(md[k]);
+      if (lane == 0) store_moments(mout + sb * 9, md);
     }
   }
   rho = wave_sum(rho);
@@ -1439,193 +1483,25 @@ __global__ __launch_bounds__(kBlock) void eam_hvp_atom_kernel(EamParams P, Devic
       *out = rhodot;  // an embedding NETWORK: F'' is applied by scalar_net_d2_kernel (eam_hvp)
     } else {
       Dual F, dF;
-      if ((P.tab_embed >> sA) & 1u) spline_eval_dual(tabs[slot_embed(nel, sA)], make_dual(rho, 1.0), F, dF);
-      else zjw_embed<Dual>(el[sA], P.embed_kind[sA], make_dual(rho, 1.0), F, dF);
+      embed_fn<false, false>(P, el, tabs, sA, make_dual(rho, 1.0), F, dF);
       *out = dF.d * rhodot;  // F''(rho_i) rho_i-dot
     }
   }
 }
 
 // pass 2: d forces / d eps per (direction, atom) and, when asked for, the per-atom virial rows' tangents
-__global__ __launch_bounds__(kBlock) void eam_hvp_force_kernel(EamParams P, DeviceBatch b, HvpArgs a,
-                                                               const TabDev *__restrict__ tabs,
-                                                               const double *__restrict__ dF,
-                                                               const double *__restrict__ dFdot, double *fdot,
-                                                               double *wdot) {
+template <bool ADP>
+__global__ __launch_bounds__(kBlock) void hvp_force_kernel(EamParams P, DeviceBatch b, HvpArgs a,
+                                                           const TabDev *__restrict__ tabs,
+                                                           const double *__restrict__ dF,
+                                                           const double *__restrict__ dFdot,
+                                                           const double *__restrict__ mom,
+                                                           const double *__restrict__ momdot, double *fdot,
+                                                           double *wdot) {
   __shared__ Dual el[kMaxEamElements][20];
   __shared__ Dual phx[kMaxPairTypes][7];
-  const int nel = P.nel, npt = nel * (nel + 1) / 2;
-  for (int t = threadIdx.x; t < nel * 20; t += kBlock) el[t / 20][t % 20] = make_dual(P.el[t / 20][t % 20]);
-  for (int t = threadIdx.x; t < npt * 7; t += kBlock) phx[t / 7][t % 7] = make_dual(P.phi[t / 7][t % 7]);
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63, dir = blockIdx.y;
-  if (i >= b.n_atoms) return;
-  const int fr = b.frame_of_atom[i];
-  double *fo = fdot + ((size_t)dir * b.n_atoms + i) * 3;
-  double *wo = wdot ? wdot + ((size_t)dir * b.n_atoms + i) * 9 : nullptr;
-  double fd[3] = {0, 0, 0}, wd[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  if (!(a.unit && b.frame_of_atom[(a.first + dir) / 3] != fr)) {
-    const int sA = b.species[i];
-    const int32_t *seg = b.seg_start + (size_t)i * (nel + 1);
-    const double *h = b.cells + 9 * (size_t)fr;
-    const double *ri = b.pos + 3 * (size_t)i;
-    const Dual dFi = make_dual(dF[i], dFdot[(size_t)dir * b.n_atoms + i]);
-    const bool rhoA_tab = (P.tab_rho >> sA) & 1u;
-    for (int sb = 0; sb < nel; ++sb) {
-      const int pt = pair_type(sA, sb, nel);
-      const bool rhoB_tab = (P.tab_rho >> sb) & 1u, phi_tab = (P.tab_phi >> pt) & 1u;
-      for (int q = seg[sb] + lane; q < seg[sb + 1]; q += 64) {
-        const int j = b.pair_j[q];
-        const int S[3] = {b.pair_shift[3 * (size_t)q], b.pair_shift[3 * (size_t)q + 1], b.pair_shift[3 * (size_t)q + 2]};
-        const double *rj = b.pos + 3 * (size_t)j;
-        double Dv[3], T[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) Dv[c] = (rj[c] - ri[c]) + (S[0] * h[c] + S[1] * h[3 + c] + S[2] * h[6 + c]);
-        const double r2v = Dv[0] * Dv[0] + Dv[1] * Dv[1] + Dv[2] * Dv[2] + a.eps;
-        if (P.list_rc2 > 0.0 && !(r2v < P.list_rc2)) continue;
-        hvp_pair_tangent(a, b, dir, i, j, fr, S, T);
-        const Dual D[3] = {make_dual(Dv[0], T[0]), make_dual(Dv[1], T[1]), make_dual(Dv[2], T[2])};
-        const Dual r = t_sqrt(make_dual(r2v, 2.0 * (Dv[0] * T[0] + Dv[1] * T[1] + Dv[2] * T[2])));
-        const Dual dFj = make_dual(dF[j], dFdot[(size_t)dir * b.n_atoms + j]);
-        Dual fn, drhoB, drhoA, dphi;
-        if (rhoB_tab) spline_eval_dual(tabs[slot_rho(sb)], r, fn, drhoB);
-        else zjw_rho<Dual, Dual>(el[sb], r, fn, drhoB);
-        if (sb == sA) drhoA = drhoB;
-        else if (rhoA_tab) spline_eval_dual(tabs[slot_rho(sA)], r, fn, drhoA);
-        else zjw_rho<Dual, Dual>(el[sA], r, fn, drhoA);
-        if (phi_tab) spline_eval_dual(tabs[slot_pair(nel, 1, pt)], r, fn, dphi);
-        else zjw_phi<Dual, Dual>(P, el, phx, sA, sb, r, fn, dphi);
-        const Dual inv_r = 1.0 / r;
-        const Dual own = (dFi * drhoB + 0.5 * dphi) * inv_r;              // g[p] = own D
-        const Dual both = own + (dFj * drhoA + 0.5 * dphi) * inv_r;       // g[p] - g[rev p] = both D
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          fd[c] += (both * D[c]).d;
-          if (wo) {
-            const Dual od = own * D[c];
-#pragma unroll
-            for (int e = 0; e < 3; ++e) wd[3 * c + e] += (od * D[e]).d;
-          }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) fd[k] = wave_sum(fd[k]);
-  if (wo) {
-#pragma unroll
-    for (int k = 0; k < 9; ++k) wd[k] = wave_sum(wd[k]);
-  }
-  if (lane == 0) {
-    for (int k = 0; k < 3; ++k) fo[k] = fd[k];
-    if (wo)
-      for (int k = 0; k < 9; ++k) wo[k] = wd[k];
-  }
-}
-
-// ---- the same for ADP models ----------------------------------------------------------------------
-// adp_force_kernel's expression in dual arithmetic: besides D, r, rho', phi', F' the dipole / quadrupole
-// functions u, w (u', w' of a dual r carry u'' rdot, w'' rdot: mishin_polar_r, or the spline's second
-// derivative) and the moments of BOTH atoms of a pair are dual, mu = (mu, mu-dot), Lambda = (Lambda,
-// Lambda-dot) with mu-dot = sum (u' rdot D + u T), lambda-dot = sum (w' rdot D (x) D + w (T (x) D + D (x) T))
-// from the first pass (trace removed as in `mom`).
-__global__ __launch_bounds__(kBlock) void adp_hvp_atom_kernel(EamParams P, DeviceBatch b, HvpArgs a,
-                                                              const TabDev *__restrict__ tabs, double *dFdot,
-                                                              double *momdot) {
-  __shared__ Dual el[kMaxEamElements][20];
+  dual_constants(P, el, phx, nullptr);
   const int nel = P.nel;
-  for (int t = threadIdx.x; t < nel * 20; t += kBlock) el[t / 20][t % 20] = make_dual(P.el[t / 20][t % 20]);
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63, dir = blockIdx.y;
-  if (i >= b.n_atoms) return;
-  const int fr = b.frame_of_atom[i];
-  double *out = dFdot + (size_t)dir * b.n_atoms + i;
-  double *mout = momdot + (((size_t)dir * b.n_atoms + i) * nel) * 9;
-  if (a.unit && b.frame_of_atom[(a.first + dir) / 3] != fr) {  // another structure of the batch: no coupling
-    if (lane == 0) *out = 0.0;
-    for (int k = lane; k < nel * 9; k += 64) mout[k] = 0.0;
-    return;
-  }
-  const int sA = b.species[i];
-  const int32_t *seg = b.seg_start + (size_t)i * (nel + 1);
-  const double *h = b.cells + 9 * (size_t)fr;
-  const double *ri = b.pos + 3 * (size_t)i;
-  double rho = 0.0, rhodot = 0.0;
-  for (int sb = 0; sb < nel; ++sb) {
-    const bool rho_tab = (P.tab_rho >> sb) & 1u;
-    const int pt = pair_type(sA, sb, nel);
-    const double *pp = P.pair[pt];
-    const bool u_tab = (P.tab_u >> pt) & 1u, w_tab = (P.tab_w >> pt) & 1u;
-    double md[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int q = seg[sb] + lane; q < seg[sb + 1]; q += 64) {
-      const int j = b.pair_j[q];
-      const int S[3] = {b.pair_shift[3 * (size_t)q], b.pair_shift[3 * (size_t)q + 1], b.pair_shift[3 * (size_t)q + 2]};
-      const double *rj = b.pos + 3 * (size_t)j;
-      double D[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) D[c] = (rj[c] - ri[c]) + (S[0] * h[c] + S[1] * h[3 + c] + S[2] * h[6 + c]);
-      const double r2 = D[0] * D[0] + D[1] * D[1] + D[2] * D[2] + a.eps;
-      if (P.list_rc2 > 0.0 && !(r2 < P.list_rc2)) continue;
-      const double r = sqrt(r2);
-      double T[3];
-      hvp_pair_tangent(a, b, dir, i, j, fr, S, T);
-      const double rd = (D[0] * T[0] + D[1] * T[1] + D[2] * T[2]) / r;
-      double f, df;
-      if (rho_tab) spline_eval(tabs[slot_rho(sb)], r, f, df);
-      else zjw_rho<double>(P.el[sb], r, f, df);
-      rho += f;
-      rhodot = fma(df, rd, rhodot);
-      double u, du, w, dw;
-      if (u_tab) spline_eval(tabs[slot_pair(nel, 2, pt)], r, u, du);
-      else mishin_polar<double>(r, pp[0], pp[1], pp[2], pp[7], pp[6], u, du);
-      if (w_tab) spline_eval(tabs[slot_pair(nel, 3, pt)], r, w, dw);
-      else mishin_polar<double>(r, pp[3], pp[4], pp[5], pp[7], pp[6], w, dw);
-      const double ur = du * rd, wr = dw * rd;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) md[c] += ur * D[c] + u * T[c];
-      md[3] += wr * D[0] * D[0] + 2.0 * w * T[0] * D[0];
-      md[4] += wr * D[1] * D[1] + 2.0 * w * T[1] * D[1];
-      md[5] += wr * D[2] * D[2] + 2.0 * w * T[2] * D[2];
-      md[6] += wr * D[1] * D[2] + w * (T[1] * D[2] + D[1] * T[2]);
-      md[7] += wr * D[0] * D[2] + w * (T[0] * D[2] + D[0] * T[2]);
-      md[8] += wr * D[0] * D[1] + w * (T[0] * D[1] + D[0] * T[1]);
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) md[k] = wave_sum(md[k]);
-    if (lane == 0) {
-      const double nu = md[3] + md[4] + md[5];
-      for (int k = 0; k < 9; ++k) mout[sb * 9 + k] = (k >= 3 && k < 6) ? md[k] - nu / 3.0 : md[k];
-    }
-  }
-  rho = wave_sum(rho);
-  rhodot = wave_sum(rhodot);
-  if (lane == 0) {
-    if ((P.nn_embed >> sA) & 1u) {
-      *out = rhodot;
-    } else {
-      Dual F, dF;
-      if ((P.tab_embed >> sA) & 1u) spline_eval_dual(tabs[slot_embed(nel, sA)], make_dual(rho, 1.0), F, dF);
-      else zjw_embed<Dual>(el[sA], P.embed_kind[sA], make_dual(rho, 1.0), F, dF);
-      *out = dF.d * rhodot;
-    }
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void adp_hvp_force_kernel(EamParams P, DeviceBatch b, HvpArgs a,
-                                                               const TabDev *__restrict__ tabs,
-                                                               const double *__restrict__ dF,
-                                                               const double *__restrict__ dFdot,
-                                                               const double *__restrict__ mom,
-                                                               const double *__restrict__ momdot, double *fdot,
-                                                               double *wdot) {
-  __shared__ Dual el[kMaxEamElements][20];
-  __shared__ Dual phx[kMaxPairTypes][7];
-  const int nel = P.nel, npt = nel * (nel + 1) / 2;
-  for (int t = threadIdx.x; t < nel * 20; t += kBlock) el[t / 20][t % 20] = make_dual(P.el[t / 20][t % 20]);
-  for (int t = threadIdx.x; t < npt * 7; t += kBlock) phx[t / 7][t % 7] = make_dual(P.phi[t / 7][t % 7]);
-  __syncthreads();
   const int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63, dir = blockIdx.y;
   if (i >= b.n_atoms) return;
@@ -1639,7 +1515,6 @@ __global__ __launch_bounds__(kBlock) void adp_hvp_force_kernel(EamParams P, Devi
     const double *h = b.cells + 9 * (size_t)fr;
     const double *ri = b.pos + 3 * (size_t)i;
     const Dual dFi = make_dual(dF[i], dFdot[(size_t)dir * b.n_atoms + i]);
-    const bool rhoA_tab = (P.tab_rho >> sA) & 1u;
     auto moments = [&](int64_t atom, int sp, Dual (&m)[9]) {
       const double *v = mom + ((size_t)atom * nel + sp) * 9;
       const double *d = momdot + (((size_t)dir * b.n_atoms + atom) * nel + sp) * 9;
@@ -1647,62 +1522,55 @@ __global__ __launch_bounds__(kBlock) void adp_hvp_force_kernel(EamParams P, Devi
       for (int k = 0; k < 9; ++k) m[k] = make_dual(v[k], d[k]);
     };
     for (int sb = 0; sb < nel; ++sb) {
-      const int pt = pair_type(sA, sb, nel);
-      const double *pp = P.pair[pt];
-      const bool rhoB_tab = (P.tab_rho >> sb) & 1u, phi_tab = (P.tab_phi >> pt) & 1u;
-      const bool u_tab = (P.tab_u >> pt) & 1u, w_tab = (P.tab_w >> pt) & 1u;
+      const auto fn = segment_fns<false, false, false>(P, el, phx, P.pair, sA, sb, tabs);
       Dual mi[9];
-      moments(i, sb, mi);
+      if constexpr (ADP) moments(i, sb, mi);
       for (int q = seg[sb] + lane; q < seg[sb + 1]; q += 64) {
         const int j = b.pair_j[q];
         const int S[3] = {b.pair_shift[3 * (size_t)q], b.pair_shift[3 * (size_t)q + 1], b.pair_shift[3 * (size_t)q + 2]};
-        const double *rj = b.pos + 3 * (size_t)j;
         double Dv[3], T[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) Dv[c] = (rj[c] - ri[c]) + (S[0] * h[c] + S[1] * h[3 + c] + S[2] * h[6 + c]);
-        const double r2v = Dv[0] * Dv[0] + Dv[1] * Dv[1] + Dv[2] * Dv[2] + a.eps;
+        const double r2v = pair_vector(ri, b.pos + 3 * (size_t)j, S, h, a.eps, Dv);
         if (P.list_rc2 > 0.0 && !(r2v < P.list_rc2)) continue;
         hvp_pair_tangent(a, b, dir, i, j, fr, S, T);
         const Dual D[3] = {make_dual(Dv[0], T[0]), make_dual(Dv[1], T[1]), make_dual(Dv[2], T[2])};
-        const Dual r = t_sqrt(make_dual(r2v, 2.0 * (Dv[0] * T[0] + Dv[1] * T[1] + Dv[2] * T[2])));
+        const Dual r = t_sqrt(make_dual(r2v, 2.0 * dot3(Dv, T)));
         const Dual dFj = make_dual(dF[j], dFdot[(size_t)dir * b.n_atoms + j]);
-        Dual mj[9];
-        moments(j, sA, mj);
-        Dual fn, drhoB, drhoA, dphi, u, du, w, dw;
-        if (rhoB_tab) spline_eval_dual(tabs[slot_rho(sb)], r, fn, drhoB);
-        else zjw_rho<Dual, Dual>(el[sb], r, fn, drhoB);
+        Dual unused, drhoB, drhoA, dphi;
+        fn.rho(q, r, unused, drhoB);
         if (sb == sA) drhoA = drhoB;
-        else if (rhoA_tab) spline_eval_dual(tabs[slot_rho(sA)], r, fn, drhoA);
-        else zjw_rho<Dual, Dual>(el[sA], r, fn, drhoA);
-        if (phi_tab) spline_eval_dual(tabs[slot_pair(nel, 1, pt)], r, fn, dphi);
-        else zjw_phi<Dual, Dual>(P, el, phx, sA, sb, r, fn, dphi);
-        if (u_tab) spline_eval_dual(tabs[slot_pair(nel, 2, pt)], r, u, du);
-        else mishin_polar_r<Dual>(r, pp[0], pp[1], pp[2], pp[7], pp[6], u, du);
-        if (w_tab) spline_eval_dual(tabs[slot_pair(nel, 3, pt)], r, w, dw);
-        else mishin_polar_r<Dual>(r, pp[3], pp[4], pp[5], pp[7], pp[6], w, dw);
+        else fn.rho_rev(r, unused, drhoA);
+        fn.phi(q, r, unused, dphi);
         const Dual inv_r = 1.0 / r;
-        auto lam = [&](const Dual (&m)[9], Dual (&l)[3]) {
-          l[0] = m[3] * D[0] + m[8] * D[1] + m[7] * D[2];
-          l[1] = m[8] * D[0] + m[4] * D[1] + m[6] * D[2];
-          l[2] = m[7] * D[0] + m[6] * D[1] + m[5] * D[2];
-        };
-        Dual li[3], lj[3];
-        lam(mi, li);
-        lam(mj, lj);
-        const Dual muD = mi[0] * D[0] + mi[1] * D[1] + mi[2] * D[2];
-        const Dual DLD = D[0] * li[0] + D[1] * li[1] + D[2] * li[2];
-        const Dual ci = (dFi * drhoB + 0.5 * dphi) * inv_r + (muD * du + DLD * dw) * inv_r;
-        const Dual muDj = mj[0] * D[0] + mj[1] * D[1] + mj[2] * D[2];
-        const Dual DLDj = D[0] * lj[0] + D[1] * lj[1] + D[2] * lj[2];
-        const Dual cj = (dFj * drhoA + 0.5 * dphi) * inv_r + (DLDj * dw - muDj * du) * inv_r;
+        if constexpr (!ADP) {
+          const Dual own = (dFi * drhoB + 0.5 * dphi) * inv_r;         // g[p] = own D
+          const Dual both = own + (dFj * drhoA + 0.5 * dphi) * inv_r;  // g[p] - g[rev p] = both D
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const Dual g = ci * D[c] + u * mi[c] + 2.0 * (w * li[c]);      // own side, dE/dD of (i -> j)
-          const Dual gr = u * mj[c] - cj * D[c] - 2.0 * (w * lj[c]);     // the reverse pair's, centre j, -D
-          fd[c] += (g - gr).d;
-          if (wo) {
+          for (int c = 0; c < 3; ++c) {
+            fd[c] += (both * D[c]).d;
+            if (wo) {
+              const Dual od = own * D[c];
 #pragma unroll
-            for (int e = 0; e < 3; ++e) wd[3 * c + e] += (g * D[e]).d;
+              for (int e = 0; e < 3; ++e) wd[3 * c + e] += (od * D[e]).d;
+            }
+          }
+        } else {
+          Dual mj[9], u, du, w, dw, li[3], lj[3];
+          moments(j, sA, mj);
+          fn.u(q, r, u, du);
+          fn.w(q, r, w, dw);
+          lambda_dot(mi, D, li);
+          lambda_dot(mj, D, lj);
+          const Dual ci = (dFi * drhoB + 0.5 * dphi) * inv_r + (dot3(mi, D) * du + dot3(D, li) * dw) * inv_r;
+          const Dual cj = (dFj * drhoA + 0.5 * dphi) * inv_r + (dot3(D, lj) * dw - dot3(mj, D) * du) * inv_r;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const Dual g = ci * D[c] + u * mi[c] + 2.0 * (w * li[c]);   // own side, dE/dD of (i -> j)
+            const Dual gr = u * mj[c] - cj * D[c] - 2.0 * (w * lj[c]);  // the reverse pair's, centre j, -D
+            fd[c] += (g - gr).d;
+            if (wo) {
+#pragma unroll
+              for (int e = 0; e < 3; ++e) wd[3 * c + e] += (g * D[e]).d;
+            }
           }
         }
       }
@@ -2354,9 +2222,8 @@ __global__ __launch_bounds__(kBlock) void eam_lg_atom_kernel(EamParams P, Device
                                                              double *rdot, double *rhodot, double *d2F,
                                                              double *momdot) {
   __shared__ Dual el[kMaxEamElements][20];
+  dual_constants(P, el, nullptr, nullptr);
   const int nel = P.nel;
-  for (int t = threadIdx.x; t < nel * 20; t += kBlock) el[t / 20][t % 20] = make_dual(P.el[t / 20][t % 20]);
-  __syncthreads();
   const int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (i >= b.n_atoms) return;
@@ -2367,77 +2234,36 @@ __global__ __launch_bounds__(kBlock) void eam_lg_atom_kernel(EamParams P, Device
   const double *ri = b.pos + 3 * (size_t)i;
   double acc = 0.0, rho_sum = 0.0;
   for (int sb = 0; sb < nel; ++sb) {
-    const bool rho_nn = (P.nn_rho >> sb) & 1u, rho_tab = (P.tab_rho >> sb) & 1u;
-    const int pt = pair_type(sA, sb, nel);
-    const double *pp = P.pair[pt];
-    const bool u_nn = (P.nn_u >> pt) & 1u, u_tab = (P.tab_u >> pt) & 1u;
-    const bool w_nn = (P.nn_w >> pt) & 1u, w_tab = (P.tab_w >> pt) & 1u;
+    const auto fn = segment_fns<false, false, true>(P, sA, sb, tabs, pf, ps);
     double md[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // ADP: mu-dot, lambda-dot (xx yy zz yz xz xy) of (i, sb)
     for (int q = seg[sb] + lane; q < seg[sb + 1]; q += 64) {
       const int j = b.pair_j[q];
       const int S[3] = {b.pair_shift[3 * (size_t)q], b.pair_shift[3 * (size_t)q + 1], b.pair_shift[3 * (size_t)q + 2]};
-      const double *rj = b.pos + 3 * (size_t)j;
-      double D[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) D[c] = (rj[c] - ri[c]) + (S[0] * h[c] + S[1] * h[3 + c] + S[2] * h[6 + c]);
-      const double r2 = D[0] * D[0] + D[1] * D[1] + D[2] * D[2] + a.eps;
+      double D[3], T[3];
+      const double r2 = pair_vector(ri, b.pos + 3 * (size_t)j, S, h, a.eps, D);
       if (P.list_rc2 > 0.0 && !(r2 < P.list_rc2)) {
         rdot[q] = 0.0;
         continue;
       }
       const double r = sqrt(r2);
-      double T[3];
       hvp_pair_tangent(a, b, 0, i, j, fr, S, T);
-      const double rd = (D[0] * T[0] + D[1] * T[1] + D[2] * T[2]) / r;
+      const double rd = dot3(D, T) / r;
       rdot[q] = rd;
       double f, df;
-      if (rho_nn) {
-        f = pf[PF_RHO * ps + q];
-        df = pf[PF_DRHO * ps + q];
-      } else if (rho_tab) {
-        spline_eval(tabs[slot_rho(sb)], r, f, df);
-      } else {
-        zjw_rho<double>(P.el[sb], r, f, df);
-      }
+      fn.rho(q, r, f, df);
       rho_sum += f;
       acc = fma(df, rd, acc);
-      if (P.adp) {  // mu-dot = sum (u' rdot D + u T), lambda-dot = sum (w' rdot D (x) D + w (T (x) D + D (x) T))
+      if (P.adp) {
         double u, du, w, dw;
-        if (u_nn) {
-          u = pf[PF_U * ps + q];
-          du = pf[PF_DU * ps + q];
-        } else if (u_tab) {
-          spline_eval(tabs[slot_pair(nel, 2, pt)], r, u, du);
-        } else {
-          mishin_polar<double>(r, pp[0], pp[1], pp[2], pp[7], pp[6], u, du);
-        }
-        if (w_nn) {
-          w = pf[PF_W * ps + q];
-          dw = pf[PF_DW * ps + q];
-        } else if (w_tab) {
-          spline_eval(tabs[slot_pair(nel, 3, pt)], r, w, dw);
-        } else {
-          mishin_polar<double>(r, pp[3], pp[4], pp[5], pp[7], pp[6], w, dw);
-        }
-        const double ur = du * rd, wr = dw * rd;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) md[c] += ur * D[c] + u * T[c];
-        md[3] += wr * D[0] * D[0] + 2.0 * w * T[0] * D[0];
-        md[4] += wr * D[1] * D[1] + 2.0 * w * T[1] * D[1];
-        md[5] += wr * D[2] * D[2] + 2.0 * w * T[2] * D[2];
-        md[6] += wr * D[1] * D[2] + w * (T[1] * D[2] + D[1] * T[2]);
-        md[7] += wr * D[0] * D[2] + w * (T[0] * D[2] + D[0] * T[2]);
-        md[8] += wr * D[0] * D[1] + w * (T[0] * D[1] + D[0] * T[1]);
+        fn.u(q, r, u, du);
+        fn.w(q, r, w, dw);
+        add_moment_tangents(md, u, du * rd, w, dw * rd, D, T);
       }
     }
     if (P.adp) {
 #pragma unroll
       for (int k = 0; k < 9; ++k) md[k] = wave_sum(md[k]);
-      if (lane == 0) {
-        const double nu = md[3] + md[4] + md[5];  // stored like the moments themselves: trace removed
-        double *dst = momdot + ((size_t)i * nel + sb) * 9;
-        for (int k = 0; k < 9; ++k) dst[k] = (k >= 3 && k < 6) ? md[k] - nu / 3.0 : md[k];
-      }
+      if (lane == 0) store_moments(momdot + ((size_t)i * nel + sb) * 9, md);  // trace removed, as `mom`
     }
   }
   acc = wave_sum(acc);
@@ -2446,9 +2272,8 @@ __global__ __launch_bounds__(kBlock) void eam_lg_atom_kernel(EamParams P, Device
     rhodot[i] = acc;
     if (!((P.nn_embed >> sA) & 1u)) {
       Dual F, dF;
-      const double rho = rho_sum;  // (rho_buf holds the densities of the atoms with an embedding NETWORK only)
-      if ((P.tab_embed >> sA) & 1u) spline_eval_dual(tabs[slot_embed(nel, sA)], make_dual(rho, 1.0), F, dF);
-      else zjw_embed<Dual>(el[sA], P.embed_kind[sA], make_dual(rho, 1.0), F, dF);
+      // (rho_buf holds the densities of the atoms with an embedding NETWORK only)
+      embed_fn<false, false>(P, el, tabs, sA, make_dual(rho_sum, 1.0), F, dF);
       d2F[i] = dF.d * acc;
     }
   }
@@ -2471,15 +2296,11 @@ __global__ __launch_bounds__(kBlock) void eam_lg_coeff_kernel(EamParams P, Devic
   const int sA = b.species[i], sb = b.species[j];
   const int key = cls == 0 ? sb : pair_type(sA, sb, nel);
   double va = 0.0, vb = 0.0;
-  // the pair vector again from the coordinates (the records need not exist in every mode of the forward pass)
+  // the pair vector again from the coordinates (the records exist only with exact nn pair functions)
   const int fr = b.frame_of_atom[i];
-  const double *h = b.cells + 9 * (size_t)fr;
   const int S[3] = {b.pair_shift[3 * (size_t)p], b.pair_shift[3 * (size_t)p + 1], b.pair_shift[3 * (size_t)p + 2]};
   double D[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-    D[c] = (b.pos[3 * (size_t)j + c] - b.pos[3 * (size_t)i + c]) + (S[0] * h[c] + S[1] * h[3 + c] + S[2] * h[6 + c]);
-  const double r2 = D[0] * D[0] + D[1] * D[1] + D[2] * D[2] + a.eps;
+  const double r2 = pair_vector(b.pos + 3 * (size_t)i, b.pos + 3 * (size_t)j, S, b.cells + 9 * (size_t)fr, a.eps, D);
   const bool listed = !(P.list_rc2 > 0.0) || r2 < P.list_rc2;
   if (key == k && listed) {
     const double c = frame_coeff ? frame_coeff[fr] : 0.0;
@@ -2494,18 +2315,15 @@ __global__ __launch_bounds__(kBlock) void eam_lg_coeff_kernel(EamParams P, Devic
       hvp_pair_tangent(a, b, 0, i, j, fr, S, T);
       const double *m = mom + ((size_t)i * nel + sb) * 9, *md = momdot + ((size_t)i * nel + sb) * 9;
       if (cls == 2) {  // dipole function u: E through mu = sum u D
-        const double muD = m[0] * D[0] + m[1] * D[1] + m[2] * D[2];
-        va = c * muD + (md[0] * D[0] + md[1] * D[1] + md[2] * D[2]) + (m[0] * T[0] + m[1] * T[1] + m[2] * T[2]);
+        const double muD = dot3(m, D);
+        va = c * muD + dot3(md, D) + dot3(m, T);
         vb = rdot[p] * muD;
       } else {         // quadrupole function w: E through lambda = sum w D (x) D; m[3..8] = Lambda (trace removed)
-        auto quad = [](const double *q, const double *x, const double *y) {
-          const double lx = q[3] * y[0] + q[8] * y[1] + q[7] * y[2];
-          const double ly = q[8] * y[0] + q[4] * y[1] + q[6] * y[2];
-          const double lz = q[7] * y[0] + q[6] * y[1] + q[5] * y[2];
-          return x[0] * lx + x[1] * ly + x[2] * lz;
-        };
-        const double DLD = quad(m, D, D);
-        va = c * DLD + quad(md, D, D) + 2.0 * quad(m, T, D);
+        double l[3], ld[3];
+        lambda_dot(m, D, l);
+        lambda_dot(md, D, ld);
+        const double DLD = dot3(D, l);
+        va = c * DLD + dot3(D, ld) + 2.0 * dot3(T, l);
         vb = rdot[p] * DLD;
       }
     }
@@ -2614,14 +2432,8 @@ __global__ __launch_bounds__(kBlock) void eam_const_grad_kernel(EamParams P, Dev
   __shared__ Dual prs[kMaxPairTypes][8];
   __shared__ double wpart[kBlock / 64];
   const int seeded = blockIdx.y;
-  const int nel = P.nel, npt = nel * (nel + 1) / 2;
-  for (int t = threadIdx.x; t < nel * 20; t += kBlock)
-    el[t / 20][t % 20] = make_dual(P.el[t / 20][t % 20], t == seeded ? 1.0 : 0.0);
-  for (int t = threadIdx.x; t < npt * 7; t += kBlock)
-    phx[t / 7][t % 7] = make_dual(P.phi[t / 7][t % 7], 20 * nel + t == seeded ? 1.0 : 0.0);
-  for (int t = threadIdx.x; t < npt * 8; t += kBlock)
-    prs[t / 8][t % 8] = make_dual(P.pair[t / 8][t % 8], 20 * nel + 7 * npt + t == seeded ? 1.0 : 0.0);
-  __syncthreads();
+  dual_constants(P, el, phx, prs, seeded);
+  const int nel = P.nel;
   const int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   double contrib = 0.0;
@@ -2635,76 +2447,36 @@ __global__ __launch_bounds__(kBlock) void eam_const_grad_kernel(EamParams P, Dev
     Dual eadp = make_dual(0.0);  // c E_adp + D_delta E_adp of this atom (lane 0)
     const double cf = frame_coeff ? frame_coeff[fr] : 0.0;
     for (int sb = 0; sb < nel; ++sb) {
-      // ADP moments of this neighbour species and their directional derivatives:
-      // m[0..2] = mu, m[3..8] = lambda (xx yy zz yz xz xy); md = the same for the tangent
+      const auto fn = segment_fns<OTHER, false, true>(P, el, phx, prs, sA, sb, tabs, pf, ps);
+      // ADP moments of this neighbour species (m) and their directional derivatives (md)
       Dual m[9], md[9];
 #pragma unroll
       for (int k = 0; k < 9; ++k) m[k] = md[k] = make_dual(0.0);
-      const Dual *pp = prs[pair_type(sA, sb, nel)];
       for (int q = seg[sb] + lane; q < seg[sb + 1]; q += 64) {
         const int j = b.pair_j[q];
-        const double sx = (double)b.pair_shift[3 * (size_t)q], sy = (double)b.pair_shift[3 * (size_t)q + 1],
-                     sz = (double)b.pair_shift[3 * (size_t)q + 2];
-        const double *rj = b.pos + 3 * (size_t)j;
-        const double dx = (rj[0] - ri[0]) + (sx * h[0] + sy * h[3] + sz * h[6]);
-        const double dy = (rj[1] - ri[1]) + (sx * h[1] + sy * h[4] + sz * h[7]);
-        const double dz = (rj[2] - ri[2]) + (sx * h[2] + sy * h[5] + sz * h[8]);
-        const double r2 = dx * dx + dy * dy + dz * dz + eps;
+        const int S[3] = {b.pair_shift[3 * (size_t)q], b.pair_shift[3 * (size_t)q + 1], b.pair_shift[3 * (size_t)q + 2]};
+        double D[3], T[3] = {0.0, 0.0, 0.0};
+        const double r2 = pair_vector(ri, b.pos + 3 * (size_t)j, S, h, eps, D);
         if (P.list_rc2 > 0.0 && !(r2 < P.list_rc2)) continue;
         const double r = sqrt(r2);
-        double rdot = 0.0, tx = 0.0, ty = 0.0, tz = 0.0;
-        if (dR) {
-          const double *g = dh + 9 * (size_t)fr;
-          const double *ui = dR + 3 * (size_t)i, *uj = dR + 3 * (size_t)j;
-          tx = (uj[0] - ui[0]) + (sx * g[0] + sy * g[3] + sz * g[6]);
-          ty = (uj[1] - ui[1]) + (sx * g[1] + sy * g[4] + sz * g[7]);
-          tz = (uj[2] - ui[2]) + (sx * g[2] + sy * g[5] + sz * g[8]);
-          rdot = (dx * tx + dy * ty + dz * tz) / r;
+        double rdot = 0.0;
+        if (dR) {  // T = dR_j - dR_i + S.dh, the tangent of D
+          pair_vector(dR + 3 * (size_t)i, dR + 3 * (size_t)j, S, dh + 9 * (size_t)fr, 0.0, T);
+          rdot = dot3(D, T) / r;
         }
         Dual f, df;
-        const int pt = pair_type(sA, sb, nel);
-        auto plain = [&](bool nn, bool tab, int col, int slot, Dual &fv, Dual &dfv) {  // a function without constants
-          double a0, a1;
-          if (nn) {
-            a0 = pf[(size_t)col * ps + q];
-            a1 = pf[(size_t)(col + 1) * ps + q];
-          } else {
-            spline_eval(tabs[slot], r, a0, a1);
-          }
-          (void)tab;
-          fv = make_dual(a0);
-          dfv = make_dual(a1);
-        };
-        // density function of the NEIGHBOUR's element
-        if (((P.nn_rho | P.tab_rho) >> sb) & 1u) plain((P.nn_rho >> sb) & 1u, true, PF_RHO, slot_rho(sb), f, df);
-        else el_rho<OTHER, Dual>(P, el, sb, r, f, df);
+        fn.rho(q, r, f, df);
         rho += f;
         rhodot += df * rdot;
-        if (((P.nn_phi | P.tab_phi) >> pt) & 1u) plain((P.nn_phi >> pt) & 1u, true, PF_PHI, slot_pair(nel, 1, pt), f, df);
-        else pair_phi<OTHER, Dual>(P, el, phx, sA, sb, r, f, df);
+        fn.phi(q, r, f, df);
         phis += f;
         phidot += df * rdot;
         if (P.adp) {
           Dual u, du, w, dw;
-          if (((P.nn_u | P.tab_u) >> pt) & 1u) plain((P.nn_u >> pt) & 1u, true, PF_U, slot_pair(nel, 2, pt), u, du);
-          else mishin_polar<Dual>(r, pp[0], pp[1], pp[2], pp[7], pp[6], u, du);
-          if (((P.nn_w | P.tab_w) >> pt) & 1u) plain((P.nn_w >> pt) & 1u, true, PF_W, slot_pair(nel, 3, pt), w, dw);
-          else mishin_polar<Dual>(r, pp[3], pp[4], pp[5], pp[7], pp[6], w, dw);
-          const double D[3] = {dx, dy, dz}, Td[3] = {tx, ty, tz};
-          const Dual ud = du * rdot, wd = dw * rdot;
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            m[c] += u * D[c];
-            md[c] += ud * D[c] + u * Td[c];
-          }
-          // xx yy zz yz xz xy
-          const int ia[6] = {0, 1, 2, 1, 0, 0}, ib[6] = {0, 1, 2, 2, 2, 1};
-#pragma unroll
-          for (int c = 0; c < 6; ++c) {
-            const double dd = D[ia[c]] * D[ib[c]];
-            m[3 + c] += w * dd;
-            md[3 + c] += wd * dd + w * (Td[ia[c]] * D[ib[c]] + D[ia[c]] * Td[ib[c]]);
-          }
+          fn.u(q, r, u, du);
+          fn.w(q, r, w, dw);
+          add_moments(m, u, w, D);
+          add_moment_tangents(md, u, du * rdot, w, dw * rdot, D, T);
         }
       }
       if (P.adp) {
@@ -2713,13 +2485,11 @@ __global__ __launch_bounds__(kBlock) void eam_const_grad_kernel(EamParams P, Dev
           m[k] = make_dual(wave_sum(m[k].v), wave_sum(m[k].d));
           md[k] = make_dual(wave_sum(md[k].v), wave_sum(md[k].d));
         }
+        // the directional derivative of adp_energy: mu . mudot + sum lambda_ab lambdadot_ab - tr lambda tr lambdadot / 3
         const Dual nu = m[3] + m[4] + m[5], nud = md[3] + md[4] + md[5];
-        const Dual e = 0.5 * (m[0] * m[0] + m[1] * m[1] + m[2] * m[2]) +
-                       0.5 * (m[3] * m[3] + m[4] * m[4] + m[5] * m[5] + 2.0 * (m[6] * m[6] + m[7] * m[7] + m[8] * m[8])) -
-                       nu * nu / 6.0;
         const Dual ed = m[0] * md[0] + m[1] * md[1] + m[2] * md[2] + m[3] * md[3] + m[4] * md[4] + m[5] * md[5] +
                         2.0 * (m[6] * md[6] + m[7] * md[7] + m[8] * md[8]) - nu * nud / 3.0;
-        eadp += cf * e + ed;
+        eadp += cf * adp_energy(m) + ed;
       }
     }
     rho = make_dual(wave_sum(rho.v), wave_sum(rho.d));
@@ -2731,10 +2501,8 @@ __global__ __launch_bounds__(kBlock) void eam_const_grad_kernel(EamParams P, Dev
       if ((P.nn_embed >> sA) & 1u) {         // (only the dual parts matter below)
         F = make_dual(0.0, dFv[i] * rho.d);
         dFd = make_dual(dFv[i], d2Fv[i] * rho.d);
-      } else if ((P.tab_embed >> sA) & 1u) {
-        spline_eval_dual(tabs[slot_embed(nel, sA)], rho, F, dFd);
       } else {
-        el_embed<OTHER, Dual>(P, el, sA, rho, F, dFd);
+        embed_fn<OTHER, false>(P, el, tabs, sA, rho, F, dFd);
       }
       const Dual L = cf * (F + 0.5 * phis) + dFd * rhodot + 0.5 * phidot + eadp;
       contrib = L.d;
@@ -2857,8 +2625,8 @@ void eam_hvp(EamModel *m, const DeviceBatch &b, int n_dir, bool unit, int first,
   if (b.n_atoms == 0 || n_dir == 0) return;
   const HvpArgs a{n_dir, unit ? 1 : 0, first, dR, dh, m->eps};
   const dim3 grid((unsigned)((b.n_atoms + kBlock / 64 - 1) / (kBlock / 64)), (unsigned)n_dir);
-  if (m->p.adp) hipLaunchKernelGGL(adp_hvp_atom_kernel, grid, dim3(kBlock), 0, s, m->p, b, a, m->tabs_dev, dFdot, extra);
-  else hipLaunchKernelGGL(eam_hvp_atom_kernel, grid, dim3(kBlock), 0, s, m->p, b, a, m->tabs_dev, dFdot);
+  hipLaunchKernelGGL((m->p.adp ? hvp_atom_kernel<true> : hvp_atom_kernel<false>), grid, dim3(kBlock), 0, s, m->p, b, a,
+                     m->tabs_dev, dFdot, extra);
   for (int e = 0; e < m->p.nel && m->embed_nets; ++e) {  // atoms with an embedding network: rho-dot -> F''(rho) rho-dot
     const MlpDev &net = m->nets[slot_embed(m->p.nel, e)];
     const int n_el = b.elem_start[e + 1] - b.elem_start[e];
@@ -2867,13 +2635,48 @@ void eam_hvp(EamModel *m, const DeviceBatch &b, int n_dir, bool unit, int first,
                        0, s, net, m->activation, b.elem_atoms + b.elem_start[e], n_el, m->rho_buf, dFdot, dFdot,
                        (size_t)b.n_atoms);
   }
-  if (m->p.adp)
-    hipLaunchKernelGGL(adp_hvp_force_kernel, grid, dim3(kBlock), 0, s, m->p, b, a, m->tabs_dev, m->dF, dFdot, m->mom,
-                       extra, fdot, wdot);
-  else
-    hipLaunchKernelGGL(eam_hvp_force_kernel, grid, dim3(kBlock), 0, s, m->p, b, a, m->tabs_dev, m->dF, dFdot, fdot,
-                       wdot);
+  hipLaunchKernelGGL((m->p.adp ? hvp_force_kernel<true> : hvp_force_kernel<false>), grid, dim3(kBlock), 0, s, m->p, b,
+                     a, m->tabs_dev, m->dF, dFdot, m->mom, extra, fdot, wdot);
 }
+
+namespace {
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <bool V>
+using Bool = std::integral_constant<bool, V>;
+// calls launch(o, fs) with the compile-time OTHER / FS of a model (eam/fs has no OTHER, EamFsNN has no
+// analytic functions), and launch(o, fs, w) with the lanes per atom W = 16 or 32 as well
+template <typename F>
+void by_model(bool fs, bool other, F &&launch) {
+  if (fs) launch(Bool<false>{}, Bool<true>{});
+  else if (other) launch(Bool<true>{}, Bool<false>{});
+  else launch(Bool<false>{}, Bool<false>{});
+}
+template <typename F>
+void by_model(bool fs, bool other, int W, F &&launch) {
+  by_model(fs, other, [&](auto o, auto f) {
+    if constexpr (f) launch(o, f, Int<16>{});  // eam/fs is never ADP: W = 16
+    else if (W == 32) launch(o, f, Int<32>{});
+    else launch(o, f, Int<16>{});
+  });
+}
+// calls launch(act) with the nn activation as the pair kernels take it: softplus, or -1 (read at run time)
+template <typename F>
+void by_activation(int activation, F &&launch) {
+  if (activation == TA_ACT_SOFTPLUS) launch(Int<TA_ACT_SOFTPLUS>{});
+  else launch(Int<-1>{});
+}
+// calls launch(nt) with the fast nn kernel's NT = 1..4 tiles of the second hidden layer
+template <typename F>
+void by_nt(int nt, F &&launch) {
+  switch (nt) {
+    case 1: launch(Int<1>{}); break;
+    case 2: launch(Int<2>{}); break;
+    case 3: launch(Int<3>{}); break;
+    default: launch(Int<4>{}); break;
+  }
+}
+}  // namespace
 
 void eam_compute(EamModel *m, const DeviceBatch &b, uint32_t want, hipStream_t s, hipEvent_t *) {
   if (b.n_atoms == 0) return;
@@ -2884,6 +2687,8 @@ void eam_compute(EamModel *m, const DeviceBatch &b, uint32_t want, hipStream_t s
   const size_t ps = m->cap_pairs;
   const bool pair_nets = m->pair_nets && b.n_pairs > 0;
   const bool fs = m->fs;  // eam/fs instantiations (FS = true) of the same kernels
+  bool other = false;
+  for (int e = 0; e < m->p.nel; ++e) other = other || m->p.el_kind[e] != 0;
   if (pair_nets) {
     double *rbuf = m->pf + (size_t)(m->p.adp ? 8 : 4) * ps;
     hipLaunchKernelGGL(eam_geom_kernel, dim3((unsigned)((b.n_pairs + kBlock - 1) / kBlock)), dim3(kBlock), 0,
@@ -2893,78 +2698,41 @@ void eam_compute(EamModel *m, const DeviceBatch &b, uint32_t want, hipStream_t s
       // workgroups of 4 wavefronts stride over the tiles; enough of them to fill the chip a few
       // times over, few enough that the LDS image of the weights is amortised
       const dim3 grid(std::min((tiles + 3) / 4, 2048u), (unsigned)m->fns.n);
-#define TA_NN_FAST(ACT, NT)                                                                              \
-  hipLaunchKernelGGL((fs ? eam_nn_pair_fast_kernel<ACT, NT, true> : eam_nn_pair_fast_kernel<ACT, NT>), grid, \
-                     dim3(kBlock), m->fast_lds, s, m->p, m->nets_dev, m->activation, m->fns, b, rbuf, m->pf, ps)
-#define TA_NN_FAST_NT(ACT)                                                                               \
-  switch (m->fast_nt) {                                                                                  \
-    case 1: TA_NN_FAST(ACT, 1); break;                                                                   \
-    case 2: TA_NN_FAST(ACT, 2); break;                                                                   \
-    case 3: TA_NN_FAST(ACT, 3); break;                                                                   \
-    default: TA_NN_FAST(ACT, 4); break;                                                                  \
-  }
-      if (m->activation == TA_ACT_SOFTPLUS) {
-        TA_NN_FAST_NT(TA_ACT_SOFTPLUS)
-      } else {
-        TA_NN_FAST_NT(-1)
-      }
-#undef TA_NN_FAST_NT
-#undef TA_NN_FAST
+      by_activation(m->activation, [&](auto act) {
+        by_nt(m->fast_nt, [&](auto nt) {
+          by_model(fs, false, [&](auto, auto f) {
+            hipLaunchKernelGGL((eam_nn_pair_fast_kernel<act, nt, f>), grid, dim3(kBlock), m->fast_lds, s, m->p,
+                               m->nets_dev, m->activation, m->fns, b, rbuf, m->pf, ps);
+          });
+        });
+      });
     } else if (m->fast_1h) {
       const dim3 grid(std::min((unsigned)((b.n_pairs + kBlock - 1) / kBlock), 4096u), (unsigned)m->fns.n);
-      if (m->activation == TA_ACT_SOFTPLUS)
-        hipLaunchKernelGGL((fs ? eam_nn_pair_1h_kernel<TA_ACT_SOFTPLUS, true> : eam_nn_pair_1h_kernel<TA_ACT_SOFTPLUS>),
-                           grid, dim3(kBlock), m->fast_lds, s, m->p, m->nets_dev, m->activation, m->fns, b, rbuf,
-                           m->pf, ps);
-      else
-        hipLaunchKernelGGL((fs ? eam_nn_pair_1h_kernel<-1, true> : eam_nn_pair_1h_kernel<-1>), grid, dim3(kBlock),
-                           m->fast_lds, s, m->p, m->nets_dev, m->activation, m->fns, b, rbuf, m->pf, ps);
+      by_activation(m->activation, [&](auto act) {
+        by_model(fs, false, [&](auto, auto f) {
+          hipLaunchKernelGGL((eam_nn_pair_1h_kernel<act, f>), grid, dim3(kBlock), m->fast_lds, s, m->p,
+                             m->nets_dev, m->activation, m->fns, b, rbuf, m->pf, ps);
+        });
+      });
     } else {
       hipLaunchKernelGGL((fs ? eam_nn_pair_kernel<kNetThreads, true> : eam_nn_pair_kernel<kNetThreads>), dim3(tiles),
                          dim3(kNetThreads), net_lds_bytes(m), s, m->p, m->nets_dev, m->activation, b, rbuf, m->pf,
                          ps, m->stride);
     }
   }
-  bool other = false;
-  for (int e = 0; e < m->p.nel; ++e) other = other || m->p.el_kind[e] != 0;
   // analytic / tabulated pair functions: forces in one pass per centre (eam_force_kernel,
   // adp_force_kernel); nn pair functions: dE/dD per pair, then the shared force gather
-  static const bool no_fold = getenv("TA_EAM_NO_FOLD") != nullptr;    // A/B switches
-  static const int w_env = getenv("TA_EAM_W") ? atoi(getenv("TA_EAM_W")) : 0;
   const bool want_f = (want & (TA_WANT_FORCES | TA_WANT_VIRIAL)) && b.n_pairs > 0;
-  static const bool no_fold_adp = getenv("TA_ADP_NO_FOLD") != nullptr;
-  const bool fold = want_f && !pair_nets && !no_fold && !(m->p.adp && no_fold_adp);
-  // One-pass force kernels (and energy-only evaluations) need no pair records: the force kernels
-  // recompute D from pos[j] + S.h. TA_EAM_RECORDS=1 keeps the record round trip (A/B switch).
-  static const bool keep_rec = getenv("TA_EAM_RECORDS") != nullptr;
-  const bool no_rec = !pair_nets && !keep_rec && (fold || !(want & (TA_WANT_FORCES | TA_WANT_VIRIAL)));
+  const bool fold = want_f && !pair_nets;
   // lanes per atom (measured, 4000-atom Ni frames, rc 6.5, us per frame for W = 16 / 32 / 64): EAM one
   // frame 25.5 / 26.2 / 28.0, 64 frames 11.3 / 14.1 / 16.7; ADP (one-pass force kernel, W = 16 / 32)
   // one frame 36.6 / 36.0, 64 frames 18.0 / 21.0
-  const int W = w_env == 16 || w_env == 32 || w_env == 64 ? w_env
-                : (!m->p.adp || b.n_atoms >= 32768) ? 16 : 32;
-  const dim3 agrid((unsigned)((b.n_atoms * W + kBlock - 1) / kBlock));
-#define TA_EAM_ATOM(O, WW, F)                                                                               \
-  hipLaunchKernelGGL((eam_atom_kernel<O, WW, F>), agrid, dim3(kBlock), 0, s, m->p, b, m->dF, m->mom, m->eps, \
-                     m->pf, ps, m->rho_buf, pair_nets ? 1 : (no_rec ? 2 : 0), m->tabs_dev)
-#define TA_EAM_BY_W(MACRO)                            \
-  do {                                                \
-    if (fs) {                                         \
-      if (W == 16) MACRO(false, 16, true);            \
-      else if (W == 32) MACRO(false, 32, true);       \
-      else MACRO(false, 64, true);                    \
-    } else if (other) {                               \
-      if (W == 16) MACRO(true, 16, false);            \
-      else if (W == 32) MACRO(true, 32, false);       \
-      else MACRO(true, 64, false);                    \
-    } else {                                          \
-      if (W == 16) MACRO(false, 16, false);           \
-      else if (W == 32) MACRO(false, 32, false);      \
-      else MACRO(false, 64, false);                   \
-    }                                                 \
-  } while (0)
-  TA_EAM_BY_W(TA_EAM_ATOM);
-#undef TA_EAM_ATOM
+  const int W = (m->p.adp && b.n_atoms < 32768) ? 32 : 16;
+  by_model(fs, other, W, [&](auto o, auto f, auto w) {
+    hipLaunchKernelGGL((eam_atom_kernel<o, w, f>), dim3((unsigned)((b.n_atoms * w + kBlock - 1) / kBlock)),
+                       dim3(kBlock), 0, s, m->p, b, m->dF, m->mom, m->eps, m->pf, ps, m->rho_buf,
+                       pair_nets ? 1 : 2, m->tabs_dev);
+  });
   if (m->embed_nets) {
     EmbedTiles t;
     std::memset(&t, 0, sizeof(t));
@@ -2982,37 +2750,28 @@ void eam_compute(EamModel *m, const DeviceBatch &b, uint32_t want, hipStream_t s
                          dim3((unsigned)blocks), dim3(kNetThreads), net_lds_bytes(m), s, m->nets_dev, t,
                          m->activation, b, m->rho_buf, m->dF, m->stride);
   }
-  if (want_f) {
-    if (fold) {
-      const dim3 fgrid((unsigned)((b.n_atoms + 15) / 16));
-#define TA_EAM_FORCE(O, WW, F) \
-  hipLaunchKernelGGL((eam_force_kernel<O, WW, F>), fgrid, dim3(16 * WW), 0, s, m->p, b, m->dF, m->tabs_dev, \
-                     no_rec ? 1 : 0, m->eps)
-// (no eam/fs ADP: F is ignored)
-#define TA_ADP_FORCE(O, WW, F)                                                                           \
-  hipLaunchKernelGGL((adp_force_kernel<O, WW>), fgrid, dim3(16 * WW), 0, s, m->p, b, m->dF, m->mom, \
-                     m->tabs_dev, no_rec ? 1 : 0, m->eps)
-      if (m->p.adp) TA_EAM_BY_W(TA_ADP_FORCE);
-      else TA_EAM_BY_W(TA_EAM_FORCE);
-#undef TA_EAM_FORCE
-#undef TA_ADP_FORCE
-    } else {
-      const dim3 pgrid((unsigned)((b.n_pairs + kBlock - 1) / kBlock));
-      if (fs)
-        hipLaunchKernelGGL((eam_pair_kernel<false, true>), pgrid, dim3(kBlock), 0, s, m->p, b, m->dF, m->mom, m->pf,
-                           ps, m->tabs_dev);
-      else if (other)
-        hipLaunchKernelGGL(eam_pair_kernel<true>, pgrid, dim3(kBlock), 0, s, m->p, b, m->dF, m->mom, m->pf, ps,
-                           m->tabs_dev);
-      else
-        hipLaunchKernelGGL(eam_pair_kernel<false>, pgrid, dim3(kBlock), 0, s, m->p, b, m->dF, m->mom, m->pf, ps,
-                           m->tabs_dev);
-      launch_force_gather(sf, b, s);
+  if (fold) {
+    const dim3 fgrid((unsigned)((b.n_atoms + 15) / 16));
+    if (m->p.adp) {  // (no eam/fs ADP)
+      by_model(false, other, W, [&](auto o, auto, auto w) {
+        hipLaunchKernelGGL((adp_force_kernel<o, w>), fgrid, dim3(16 * w), 0, s, m->p, b, m->dF, m->mom,
+                           m->tabs_dev, m->eps);
+      });
+    } else {  // EAM and eam/fs: W = 16
+      by_model(fs, other, [&](auto o, auto f) {
+        hipLaunchKernelGGL((eam_force_kernel<o, 16, f>), fgrid, dim3(16 * 16), 0, s, m->p, b, m->dF, m->tabs_dev,
+                           m->eps);
+      });
     }
-  } else if (want & (TA_WANT_FORCES | TA_WANT_VIRIAL)) {
+  } else if (want_f) {
+    by_model(fs, other, [&](auto o, auto f) {
+      hipLaunchKernelGGL((eam_pair_kernel<o, f>), dim3((unsigned)((b.n_pairs + kBlock - 1) / kBlock)),
+                         dim3(kBlock), 0, s, m->p, b, m->dF, m->mom, m->pf, ps, m->tabs_dev);
+    });
+    launch_force_gather(sf, b, s);
+  } else if (want & (TA_WANT_FORCES | TA_WANT_VIRIAL)) {  // no pairs
     launch_force_gather(sf, b, s);
   }
-#undef TA_EAM_BY_W
 }
 
 }  // namespace ta

@@ -5,12 +5,9 @@ The EAM / ADP / eam/fs kernels (ta_eam.hip) build by build, against the oracle a
   * `eam_atom_kernel<OTHER, W, FS>` and, with forces folded into one pass per centre,
     `eam_force_kernel<OTHER, W, FS>` or `adp_force_kernel<OTHER, W>`; otherwise `eam_pair_kernel<OTHER, FS>`
     and the shared force gather. OTHER: an element whose analytic functions are sutton90, Be/1 or grimes.
-    W (lanes per atom): 16 for EAM and eam/fs, for ADP 32 below 32768 atoms and 16 at or above; any of
-    16 / 32 / 64 under TA_EAM_W;
+    W (lanes per atom): 16 for EAM and eam/fs, for ADP 32 below 32768 atoms and 16 at or above;
   * the atom kernel's geometry mode: 1 = pair records written by `eam_geom_kernel` (exact nn pair
-    functions), 2 = no records (forces folded, or no forces asked for), 0 = records written by the atom
-    kernel (unfolded forces: TA_EAM_NO_FOLD / TA_ADP_NO_FOLD, or TA_EAM_RECORDS); the folded force kernels
-    read D from the records (from_pos = 0, TA_EAM_RECORDS) or recompute it (from_pos = 1);
+    functions), 2 = D computed and not stored (every other model); the folded force kernels recompute D;
   * for exact nn pair functions (tables off): `eam_nn_pair_fast_kernel<ACT, NT, FS>` when every pair network
     is 1 -> H1 -> H2 -> 1 with one padded H2 <= 64 (NT = H2 / 16) and an LDS image <= 64 KB,
     `eam_nn_pair_1h_kernel<ACT, FS>` when every one is 1 -> H -> 1, else (or under TA_EAM_NN_GENERIC) the
@@ -21,7 +18,7 @@ the row is named after, and `test_rows_cover_every_build` that the rows together
 restatement can produce (`reachable_builds`).
 
 Combinations that cannot be reached: eam/fs with OTHER (EamFsNN has no analytic functions, eam.py
-`EamFsNN._setup_potentials`, and `TA_EAM_BY_W` tests `fs` before `other`); eam/fs ADP (`adp_force_kernel` has
+`EamFsNN._setup_potentials`, and `by_model` tests `fs` before `other`); eam/fs ADP (`adp_force_kernel` has
 no FS parameter: ADP and eam/fs are different model kinds).
 
 Bounds: north_star (1e-6 eV, 1e-5 eV/A) and what fp64 kernels owe an fp64 reference: energies to
@@ -31,8 +28,7 @@ test_gpu_sf_dispatch), for analytic functions, spline tables and exact networks.
 Hermite tables the library builds from nn pair functions are another function: rows that use them are held
 to north_star against the reference and to 1e-9 eV / 1e-8 eV/A / 1e-7 eV against the exact networks.
 
-The library reads TA_EAM_W, TA_EAM_NO_FOLD, TA_ADP_NO_FOLD and TA_EAM_RECORDS once per process: each runs in a
-fresh process (`run_child`), one at a time.
+The rows under TA_EAM_NN_TABLES / TA_EAM_NN_GENERIC run in a fresh process (`run_child`), one at a time.
 """
 import functools
 import tempfile
@@ -100,13 +96,11 @@ def eam_builds(nn, n_atoms, want=FULL, tables=True, env=None):
     cls = nn_pair_class(nn, "TA_EAM_NN_GENERIC" in env)
     tables = tables and not env.get("TA_EAM_NN_TABLES", "1").startswith("0")
     nets_on = cls is not None and not tables
-    w_env = int(env.get("TA_EAM_W", "0"))
-    W = w_env if w_env in (16, 32, 64) else (16 if fam != "adp" or n_atoms >= ADP_NARROW else 32)
+    W = 16 if fam != "adp" or n_atoms >= ADP_NARROW else 32
     want_f = bool(want & (F | V))
-    fold = want_f and not nets_on and "TA_EAM_NO_FOLD" not in env and not (fam == "adp" and "TA_ADP_NO_FOLD" in env)
-    no_rec = not nets_on and "TA_EAM_RECORDS" not in env and (fold or not want_f)
+    fold = want_f and not nets_on
     b = lambda *a: ",".join(str(x).lower() for x in a)
-    out = {f"eam_atom_kernel<{b(other, W, fs)}>", f"geom_done={1 if nets_on else 2 if no_rec else 0}"}
+    out = {f"eam_atom_kernel<{b(other, W, fs)}>", f"geom_done={1 if nets_on else 2}"}
     if nets_on:
         if cls[0] == "fast":
             out.add(f"eam_nn_pair_fast_kernel<{cls[1]},{cls[2]},{b(fs)}>")
@@ -118,9 +112,9 @@ def eam_builds(nn, n_atoms, want=FULL, tables=True, env=None):
         out.add(f"eam_nn_embed_kernel<{b(fs)}>")
     if want_f:
         if fold and fam == "adp":
-            out |= {f"adp_force_kernel<{b(other, W)}>", f"adp_force:from_pos={int(no_rec)}"}
+            out.add(f"adp_force_kernel<{b(other, W)}>")
         elif fold:
-            out |= {f"eam_force_kernel<{b(other, W, fs)}>", f"eam_force:from_pos={int(no_rec)}"}
+            out.add(f"eam_force_kernel<{b(other, W, fs)}>")
         else:
             out |= {f"eam_pair_kernel<{b(other, fs)}>", "force_gather"}
     return out
@@ -130,16 +124,13 @@ def reachable_builds():
     """Every build `eam_compute` can launch (see the module docstring for the unreachable ones)."""
     b = lambda *a: ",".join(str(x).lower() for x in a)
     combos = [(False, False), (True, False), (False, True)]        # (OTHER, FS)
-    out = {"geom_done=0", "geom_done=1", "geom_done=2", "force_gather"}
+    out = {"geom_done=1", "geom_done=2", "force_gather"}
     for o, fs in combos:
-        out.add(f"eam_pair_kernel<{b(o, fs)}>")
-        for W in (16, 32, 64):
-            out |= {f"eam_atom_kernel<{b(o, W, fs)}>", f"eam_force_kernel<{b(o, W, fs)}>"}
-    for o in (False, True):
-        for W in (16, 32, 64):
+        out |= {f"eam_pair_kernel<{b(o, fs)}>", f"eam_atom_kernel<{b(o, 16, fs)}>", f"eam_force_kernel<{b(o, 16, fs)}>"}
+    for o in (False, True):                                        # ADP (never eam/fs)
+        out.add(f"eam_atom_kernel<{b(o, 32, False)}>")
+        for W in (16, 32):
             out.add(f"adp_force_kernel<{b(o, W)}>")
-    for kind in ("eam_force", "adp_force"):
-        out |= {f"{kind}:from_pos=0", f"{kind}:from_pos=1"}
     for fs in (False, True):
         out |= {f"eam_nn_pair_kernel<{b(fs)}>", f"eam_nn_embed_kernel<{b(fs)}>"}
         for act in ("softplus", "other"):
@@ -250,8 +241,7 @@ Row = namedtuple("Row", "id targets model frames tables")
 
 # In-process rows (the library's default switches). `targets`: builds the row is named after.
 ROWS = [
-    Row("alloy-zjw04", ("eam_atom_kernel<false,16,false>", "eam_force_kernel<false,16,false>", "geom_done=2",
-                        "eam_force:from_pos=1"),
+    Row("alloy-zjw04", ("eam_atom_kernel<false,16,false>", "eam_force_kernel<false,16,false>", "geom_done=2"),
         lambda: make_eam(["Mo", "Ni"], 6.0), lambda: nimo() + nimo(seed=9), True),
     Row("alloy-sutton90", ("eam_atom_kernel<true,16,false>", "eam_force_kernel<true,16,false>"),
         lambda: make_eam(["Ag"], 8.0, potential="sutton90"), ag, True),
@@ -262,7 +252,7 @@ ROWS = [
         True),
     Row("fs-spline", ("eam_atom_kernel<false,16,true>", "eam_force_kernel<false,16,true>"),
         mendelev, lambda: [bcc_fe()], True),
-    Row("adp-zjw04", ("eam_atom_kernel<false,32,false>", "adp_force_kernel<false,32>", "adp_force:from_pos=1"),
+    Row("adp-zjw04", ("eam_atom_kernel<false,32,false>", "adp_force_kernel<false,32>"),
         lambda: make_eam(["Mo", "Ni"], 6.0, adp=True), nimo, True),
     Row("adp-sutton90", ("eam_atom_kernel<true,32,false>", "adp_force_kernel<true,32>"), adp_other, ag, True),
     Row("alloy-nn-exact", ("eam_pair_kernel<false,false>", "force_gather", "geom_done=1",
@@ -285,15 +275,6 @@ for _id, _nn, _frames in nn_models():
     ROWS.append(Row(_id, (_t,), lambda m=_nn: m, lambda f=_frames: f, False))
 
 
-def switch_cases():
-    """(name, model, frames) run under each statically cached switch: every (family, OTHER) combination."""
-    return [("alloy-zjw04", make_eam(["Mo", "Ni"], 6.0), nimo(seed=11)),
-            ("alloy-sutton90", make_eam(["Ag"], 8.0, potential="sutton90"), ag(seed=12)),
-            ("fs-spline", mendelev(), [bcc_fe(seed=13)]),
-            ("adp-zjw04", make_eam(["Mo", "Ni"], 6.0, adp=True), nimo(seed=14)),
-            ("adp-sutton90", adp_other(), ag(seed=15))]
-
-
 def nn_switch_cases():
     """Exact-network models for TA_EAM_NN_TABLES=0 (with and without TA_EAM_NN_GENERIC): fast-, 1h- and
     generic-shaped networks, eam/alloy and eam/fs."""
@@ -305,10 +286,7 @@ def nn_switch_cases():
             ("adp-fast", make_eam(["Mo", "Ni"], 6.0, adp=True, potential=None, hidden_sizes=[32, 16]), nimo(seed=25))]
 
 
-SWITCHES = [("switch_cases", {"TA_EAM_W": "16"}), ("switch_cases", {"TA_EAM_W": "32"}),
-            ("switch_cases", {"TA_EAM_W": "64"}), ("switch_cases", {"TA_EAM_NO_FOLD": "1"}),
-            ("switch_cases", {"TA_ADP_NO_FOLD": "1"}), ("switch_cases", {"TA_EAM_RECORDS": "1"}),
-            ("nn_switch_cases", {"TA_EAM_NN_TABLES": "0"}),
+SWITCHES = [("nn_switch_cases", {"TA_EAM_NN_TABLES": "0"}),
             ("nn_switch_cases", {"TA_EAM_NN_TABLES": "0", "TA_EAM_NN_GENERIC": "1"})]
 
 
@@ -351,28 +329,24 @@ def test_rows_cover_every_build():
         for want in WANTS:
             seen |= eam_builds(model(), _n(frames()), want)
     seen |= eam_builds(make_eam(["Ni"], 6.0, adp=True), ADP_NARROW)
+    seen |= eam_builds(adp_other(), ADP_NARROW)
     assert seen == reachable_builds(), (sorted(reachable_builds() - seen), sorted(seen - reachable_builds()))
 
 
 def test_switch_rows_select_their_builds():
-    """CPU: what each switch changes, on the switch cases."""
-    cases = {name: (nn, frames) for name, nn, frames in switch_cases()}
-    nn, fr = cases["adp-zjw04"]
-    assert "adp_force_kernel<false,16>" in eam_builds(nn, _n(fr), env={"TA_EAM_W": "16"})
-    assert "adp_force_kernel<false,64>" in eam_builds(nn, _n(fr), env={"TA_EAM_W": "64"})
-    assert "eam_pair_kernel<false,false>" in eam_builds(nn, _n(fr), env={"TA_ADP_NO_FOLD": "1"})
-    nn, fr = cases["alloy-zjw04"]
-    assert "eam_force_kernel<false,16,false>" in eam_builds(nn, _n(fr), env={"TA_ADP_NO_FOLD": "1"})
-    assert {"eam_force:from_pos=0", "geom_done=0"} <= eam_builds(nn, _n(fr), env={"TA_EAM_RECORDS": "1"})
-    assert {"eam_pair_kernel<false,false>", "geom_done=0"} <= eam_builds(nn, _n(fr), env={"TA_EAM_NO_FOLD": "1"})
-    assert "geom_done=2" in eam_builds(nn, _n(fr), want=E | A, env={"TA_EAM_NO_FOLD": "1"})
-    nn, fr = cases["fs-spline"]
-    assert "eam_force_kernel<false,32,true>" in eam_builds(nn, _n(fr), env={"TA_EAM_W": "32"})
+    """CPU: what each switch changes, on the nn switch cases."""
+    cases = {name: (nn, frames) for name, nn, frames in nn_switch_cases()}
+    nn, fr = cases["alloy-1h"]
+    assert "eam_nn_pair_1h_kernel<other,false>" in eam_builds(nn, _n(fr), env={"TA_EAM_NN_TABLES": "0"})
+    assert "eam_nn_pair_kernel<false>" in eam_builds(nn, _n(fr), env={"TA_EAM_NN_TABLES": "0",
+                                                                      "TA_EAM_NN_GENERIC": "1"})
+    assert "eam_force_kernel<false,16,false>" in eam_builds(nn, _n(fr))
 
 
 def test_w_boundary_of_the_adp_rows():
     nn = make_eam(["Ni"], 6.0, adp=True)
     assert "adp_force_kernel<false,32>" in eam_builds(nn, ADP_NARROW - 1)
+    assert "adp_force_kernel<true,16>" in eam_builds(adp_other(), ADP_NARROW)
     assert "adp_force_kernel<false,16>" in eam_builds(nn, ADP_NARROW)
     assert "eam_force_kernel<false,16,false>" in eam_builds(make_eam(["Ni"], 6.0), 10)
 
@@ -568,3 +542,16 @@ def test_adp_at_the_lane_boundary(lib):
         res, _ = _run(nn, frames, True)
         for k, (atoms, r) in enumerate(zip(frames, res)):
             check(r, oracle_eam_eval(nn, atoms), f"adp-{_n(frames)}atoms-W{W}/frame{k}", descriptors=False)
+
+
+@gpu
+def test_adp_other_at_the_narrow_width(lib):
+    """ADP with a sutton90 element at 32768 atoms (W = 16): two 16384-atom Ag frames."""
+    nn = adp_other()
+    frames = [fcc("Ag", a=4.09, rep=(16, 16, 16), jitter=0.06, seed=81),
+              fcc("Ag", a=4.09, rep=(16, 16, 16), jitter=0.04, seed=82)]
+    assert _n(frames) == ADP_NARROW
+    assert {"eam_atom_kernel<true,16,false>", "adp_force_kernel<true,16>"} <= eam_builds(nn, _n(frames))
+    res, _ = _run(nn, frames, True)
+    for k, (atoms, r) in enumerate(zip(frames, res)):
+        check(r, oracle_eam_eval(nn, atoms), f"adp-other-{_n(frames)}atoms-W16/frame{k}", descriptors=False)
