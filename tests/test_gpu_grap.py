@@ -4,6 +4,7 @@ import pytest
 
 from tests.helpers import fcc, make_grap_nn, oracle_grap_eval
 from tests.test_gpu_sf import _alloy, E_TOL, F_TOL, G_TOL, W_TOL
+from tests.test_gpu_sf_dispatch import E_REL, F_REL, W_REL
 
 pytestmark = pytest.mark.gpu
 
@@ -21,6 +22,13 @@ def _compare(nn, atoms_list):
         assert np.abs(r["forces"] - o["forces"]).max() < F_TOL
         assert np.abs(r["virial"] - o["virial"]).max() < W_TOL
         assert np.abs(r["stress"] - o["stress_voigt"]).max() < 1e-8
+        # fp64 bounds (test_gpu_grap_dispatch): descriptors 1e-10, energies and forces 1e-9, virial 1e-8, relative
+        e_scale = max(1.0, abs(o["energy"]))
+        assert np.abs(r["descriptors"] - o["descriptors"]).max() < 1e-10 * scale
+        assert abs(r["energy"] - o["energy"]) < E_REL * e_scale
+        assert np.abs(r["atomic"] - o["atomic"]).max() < E_REL * e_scale
+        assert np.abs(r["forces"] - o["forces"]).max() < F_REL * max(1.0, np.abs(o["forces"]).max())
+        assert np.abs(r["virial"] - o["virial"]).max() < W_REL * max(1.0, np.abs(o["virial"]).max())
     return res
 
 
