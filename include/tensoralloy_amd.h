@@ -380,6 +380,26 @@ int ta_td_loss_gradient(ta_handle h, const double *coeff_free_energy, const doub
                         const double *coeff_eentropy, const double *dR, const double *dh, double *grad,
                         int64_t n_grad, double *dG_out);
 
+/* The `nn` filter network of a GRAP model (grap.py:620-643) as trainable parameters, as the reference
+ * trains it by default (NNAlgorithm.trainable, grap.py:235). Layout of its vector: per layer
+ * W[in][out] row-major, then b[out] (zeros where a layer has no bias: the output layer).
+ *   ta_filter_param_count    its length; 0 for a model without a filter network
+ *   ta_update_filter_weights replace the network of a live handle (synchronises the stream first); the
+ *                            resident descriptors and pair Jacobians are recomputed on their next use
+ *   ta_grap_loss_gradient    grad = [MLP weights (ta_param_count) | filter network (ta_filter_param_count)]
+ *                            of d/dtheta ( sum_f frame_coeff[f] E_f + D_delta E ), arguments as
+ *                            ta_loss_gradient (frame_coeff, dR, dh may each be NULL = 0; dR = dh = NULL:
+ *                            the energy term only). The descriptors' tangent comes from dual arithmetic
+ *                            through the forward expression (no pair Jacobian), the MLP part from its
+ *                            second-order pass, the filter part from per-pair adjoints of the network's
+ *                            value and r-derivative and a second-order sweep through the network.
+ *                            TA_ERR_UNSUPPORTED for models that are not GRAP with the `nn` algorithm, for
+ *                            temperature-dependent models and on a skin-filtered batch. */
+int ta_filter_param_count(ta_handle h, int64_t *n_params);
+int ta_update_filter_weights(ta_handle h, const double *weights, int64_t n_weights);
+int ta_grap_loss_gradient(ta_handle h, const double *frame_coeff, const double *dR, const double *dh,
+                          double *grad, int64_t n_grad);
+
 /* Constants of the analytic functions of an EAM model as trainable parameters. The reference makes
  * every constant of its empirical potentials a tf.Variable (potentials/potentials.py:129-163;
  * zjw04.py: shared variables per element) trained under the same loss. Layout of the vector:

@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = [
     "ta_constant_gradient", "ta_list_sizes", "ta_abi_version", "ta_model_desc_size", "ta_set_nn_tables", "ta_step", "ta_hessian_vectors", "ta_view_results", "ta_step_view",
     "ta_set_electron_temperatures", "ta_get_td_results", "ta_td_loss_gradient",
     "ta_set_triangles", "ta_backward_variant", "ta_count_owned_triangles", "ta_triangle_owner",
+    "ta_filter_param_count", "ta_update_filter_weights", "ta_grap_loss_gradient",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -210,6 +211,9 @@ def load():
     lib.ta_energy_gradient.argtypes = [H, _dp, _dp, C.c_int64]
     lib.ta_loss_gradient.argtypes = [H, _dp, _dp, _dp, _dp, C.c_int64, _dp]
     lib.ta_td_loss_gradient.argtypes = [H, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int64, _dp]
+    lib.ta_filter_param_count.argtypes = [H, C.POINTER(C.c_int64)]
+    lib.ta_update_filter_weights.argtypes = [H, _dp, C.c_int64]
+    lib.ta_grap_loss_gradient.argtypes = [H, _dp, _dp, _dp, _dp, C.c_int64]
     lib.ta_constant_count.argtypes = [H, C.POINTER(C.c_int64)]
     lib.ta_get_constants.argtypes = [H, _dp, C.c_int64]
     lib.ta_update_constants.argtypes = [H, _dp, C.c_int64]

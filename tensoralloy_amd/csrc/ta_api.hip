@@ -68,6 +68,15 @@ void grap_destroy(GrapModel *);
 void grap_ensure(GrapModel *, const DeviceBatch &b);
 void launch_grap_forward(GrapModel *, const DeviceBatch &b, double eps, hipStream_t s);
 void launch_grap_backward(GrapModel *, const DeviceBatch &b, hipStream_t s);
+// training the GRAP filter network (ta_grap.hip)
+int64_t grap_filter_param_count(const GrapModel *g);
+void grap_update_filter_weights(GrapModel *g, const double *flat, int64_t n);
+std::string grap_filter_train_refusal(const GrapModel *g);
+size_t grap_filter_grad_doubles(const GrapModel *g, const DeviceBatch &b);
+void launch_grap_filter_tangent(GrapModel *g, const DeviceBatch &b, double eps, const double *Dv, const double *Dd,
+                                double *Gdot, hipStream_t s);
+void grap_filter_gradient(GrapModel *g, const DeviceBatch &b, double eps, const double *Dv, const double *Dd,
+                          const double *kappa, double *scratch, double *grad, hipStream_t s);
 // EAM / ADP (ta_eam.hip)
 struct EamModel;
 EamModel *eam_create(const ta_model_desc *m, std::string &err);
@@ -291,6 +300,7 @@ struct ta_context {
   // force / stress terms of the loss: J[c][p] = dG_c / dD_p of the resident batch (made once per
   // batch by one backward launch per descriptor channel), the direction and its images
   DevBuf<double> jvp_J, tan_dD, tan_dG, tan_dir;
+  DevBuf<double> filt_scratch;  // ta_grap_loss_gradient: pair vectors, w-dot, per-pair adjoints, partial sums
   bool jvp_valid = false;
 
   // MD loop (ta_set_skin / ta_update_positions): the list covers rmax + skin and is kept while no
@@ -1126,6 +1136,7 @@ int ta_destroy(ta_handle h) {
   h->nl_stats.release();
   h->nl_zero.release();
   h->hvp_buf.release();
+  h->filt_scratch.release();
   h->nl_recs.release();
   for (auto &e : h->ev)
     if (e) (void)hipEventDestroy(e);
@@ -2299,6 +2310,105 @@ int ta_td_loss_gradient(ta_handle h, const double *coeff_free_energy, const doub
     HIP_CHECK(hipMemcpyAsync(grad, h->train_grad.ptr, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, s));
     if (dG_out && N)
       HIP_CHECK(hipMemcpyAsync(dG_out, h->tan_dG.ptr, N * (size_t)D * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  });
+}
+
+int ta_filter_param_count(ta_handle h, int64_t *n_params) {
+  if (!h || !n_params) return TA_ERR_INVALID;
+  *n_params = (h->kind == TA_MODEL_GRAP_MLP && h->grap) ? ta::grap_filter_param_count(h->grap) : 0;
+  return TA_OK;
+}
+
+int ta_update_filter_weights(ta_handle h, const double *weights, int64_t n_weights) {
+  if (!h || !weights) return TA_ERR_INVALID;
+  if (h->kind != TA_MODEL_GRAP_MLP || !h->grap || !ta::grap_uses_filter_net(h->grap))
+    return fail(h, TA_ERR_INVALID, "ta_update_filter_weights: the model has no filter network");
+  return guarded(h, [&]() {
+    HIP_CHECK(hipStreamSynchronize(h->stream));  // nothing may still read the old network
+    ta::grap_update_filter_weights(h->grap, weights, n_weights);
+    // the descriptors, the filter values behind them and the pair Jacobian all belong to the old network
+    h->descriptors_valid = false;
+    h->jvp_valid = false;
+  });
+}
+
+int ta_grap_loss_gradient(ta_handle h, const double *frame_coeff, const double *dR, const double *dh, double *grad,
+                          int64_t n_grad) {
+  if (!h || !grad) return TA_ERR_INVALID;
+  if (h->td)
+    return fail(h, TA_ERR_UNSUPPORTED, "ta_grap_loss_gradient: the filter network of a temperature-dependent model "
+                                       "is not trained");
+  if (h->kind != TA_MODEL_GRAP_MLP || !h->grap)
+    return fail(h, TA_ERR_UNSUPPORTED, "ta_grap_loss_gradient: not a GRAP model");
+  {
+    const std::string why = ta::grap_filter_train_refusal(h->grap);
+    if (!why.empty()) return fail(h, TA_ERR_UNSUPPORTED, "ta_grap_loss_gradient: " + why);
+  }
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "no resident batch");
+  if (!frame_coeff && !dR && !dh) return fail(h, TA_ERR_INVALID, "nothing to differentiate");
+  if (h->filtered)  // see ta_loss_gradient
+    return fail(h, TA_ERR_UNSUPPORTED, "ta_grap_loss_gradient: not available on a skin-filtered batch; "
+                                       "ta_set_skin(h, 0) and ta_set_frames first");
+  return guarded(h, [&]() {
+    int64_t n_mlp = 0;
+    for (int e = 0; e < h->n_elements; ++e) n_mlp += ta::mlp_param_count(h->mlp[e]);
+    const int64_t n_filter = ta::grap_filter_param_count(h->grap);
+    if (n_grad != n_mlp + n_filter)
+      throw std::invalid_argument("ta_grap_loss_gradient: expected room for " + std::to_string(n_mlp + n_filter) +
+                                  " values");
+    const bool direction = dR || dh;
+    // descriptors, filter values (Hbuf) and dE/dG of the current weights and network
+    compute_impl(h, TA_WANT_ENERGY, false, nullptr);
+    hipStream_t s = h->stream;
+    const size_t N = (size_t)h->db.n_atoms, P = (size_t)h->db.n_pairs, F = (size_t)h->db.n_frames;
+    const int D = h->sf.ndim;
+    h->tan_dir.ensure(3 * N + 9 * F + 8);
+    h->tan_dD.ensure(4 * P + 8);
+    h->tan_dG.ensure(N * (size_t)D + 8);
+    // [pair vectors 4 P | kappa N D | the filter gradient's scratch]
+    h->filt_scratch.ensure(4 * P + N * (size_t)D + ta::grap_filter_grad_doubles(h->grap, h->db) + 8);
+    double *Dv = h->filt_scratch.ptr, *kappa = Dv + 4 * P, *fscratch = kappa + N * (size_t)D;
+    ta::launch_pair_vec(h->db, Dv, s);
+    if (direction) {
+      double *d_dR = h->tan_dir.ptr, *d_dh = h->tan_dir.ptr + 3 * N;
+      if (dR) HIP_CHECK(hipMemcpyAsync(d_dR, dR, 3 * N * sizeof(double), hipMemcpyHostToDevice, s));
+      else HIP_CHECK(hipMemsetAsync(d_dR, 0, 3 * N * sizeof(double), s));
+      if (dh) HIP_CHECK(hipMemcpyAsync(d_dh, dh, 9 * F * sizeof(double), hipMemcpyHostToDevice, s));
+      else HIP_CHECK(hipMemsetAsync(d_dh, 0, 9 * F * sizeof(double), s));
+      ta::launch_pair_tangent(h->db, d_dR, d_dh, h->tan_dD.ptr, s);
+      // G-dot in one launch, by dual arithmetic through the forward expression
+      ta::launch_grap_filter_tangent(h->grap, h->db, h->sf.eps, Dv, h->tan_dD.ptr, h->tan_dG.ptr, s);
+    } else {
+      HIP_CHECK(hipMemsetAsync(h->tan_dD.ptr, 0, 4 * P * sizeof(double), s));
+      HIP_CHECK(hipMemsetAsync(h->tan_dG.ptr, 0, N * (size_t)D * sizeof(double), s));
+    }
+    // MLP part and kappa = c w + H_mlp G-dot: one second-order pass per element
+    size_t scratch = 0, partial = 0;
+    for (int e = 0; e < h->n_elements; ++e) {
+      const int n_el = h->db.elem_start[e + 1] - h->db.elem_start[e];
+      scratch = std::max(scratch, ta::mlp_grad2_scratch_doubles(h->mlp[e], n_el));
+      partial = std::max(partial, ta::mlp_grad_partial_doubles(h->mlp[e], n_el));
+    }
+    h->train_scratch.ensure(scratch + 8);
+    h->train_partial.ensure(partial + 8);
+    h->train_grad.ensure((size_t)n_mlp + 8);
+    h->train_coeff.ensure(F + 8);
+    if (frame_coeff && F)
+      HIP_CHECK(hipMemcpyAsync(h->train_coeff.ptr, frame_coeff, F * sizeof(double), hipMemcpyHostToDevice, s));
+    if (N) HIP_CHECK(hipMemsetAsync(kappa, 0, N * (size_t)D * sizeof(double), s));
+    size_t off = 0;
+    for (int e = 0; e < h->n_elements; ++e) {
+      const int n_el = h->db.elem_start[e + 1] - h->db.elem_start[e];
+      ta::launch_mlp_grad2(h->mlp[e], h->activation, D, h->db.elem_atoms + h->db.elem_start[e], n_el, h->db,
+                           h->tan_dG.ptr, frame_coeff ? h->train_coeff.ptr : nullptr, h->train_scratch.ptr,
+                           h->train_partial.ptr, h->train_grad.ptr + off, s, kappa);
+      off += (size_t)ta::mlp_param_count(h->mlp[e]);
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(grad, h->train_grad.ptr, (size_t)n_mlp * sizeof(double), hipMemcpyDeviceToHost, s));
+    // filter part: per-pair adjoints (a, b), then the second-order sweep through the network (synchronises)
+    ta::grap_filter_gradient(h->grap, h->db, h->sf.eps, Dv, h->tan_dD.ptr, kappa, fscratch, grad + n_mlp, s);
     HIP_CHECK(hipStreamSynchronize(s));
   });
 }

@@ -880,6 +880,359 @@ __global__ __launch_bounds__(kWave) void grap_hvp_kernel(GrapParams g, GrapNet n
   }
 }
 
+// ---- training the `nn` filter network (ta_grap_loss_gradient) -----------------------------------------
+// L = sum_f c_f E_f + D_delta E depends on the network only through v_k(x_p) and v'_k(x_p) of every pair:
+//     dL/dtheta = sum_{p,k} a_pk dv_k/dtheta + b_pk d(dv_k/dr)/dtheta,
+//     a_pk = fc (c_f Hbar_pk + Hbar-dot_pk) + fc' r-dot_p Hbar_pk,   b_pk = fc r-dot_p Hbar_pk,
+// Hbar_pk = dE/dH_pk = sum_d A[k][d] M_d(u_p), r-dot_p = u_p . delta D_p. Three kernels: G-dot by dual
+// arithmetic through the forward expression (grap_filter_tangent_kernel); (a, b) of every pair from A in dual
+// arithmetic, seeded with w-dot = c w + H_mlp G-dot of the MLP's second-order pass, which makes Hbar-dot
+// come out as c Hbar + Hbar-dot (grap_filter_coeff_kernel); then the second-order reverse sweep through the
+// network with the output adjoints (a, b) (grap_filter_grad_kernel). v and dv/dr of the current weights come
+// from Hbuf (grap_nn_filter_kernel of the forward pass that ran before).
+
+// one lane's pair along the pair tangent: r, the cutoff and the packed monomials as dual numbers
+__device__ __forceinline__ void pair_dual(const GrapParams &g, const unsigned long long *cwl, const double *Dv,
+                                          const double *Dd, size_t q, bool valid, double eps, Dual &r, Dual &f,
+                                          Dual (&M)[kMaxComp]) {
+  Dual D[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    D[c] = valid ? make_dual(Dv[4 * q + c], Dd[4 * q + c]) : make_dual(c == 0 ? 1.0 : 0.0);
+  const Dual r2 = D[0] * D[0] + D[1] * D[1] + D[2] * D[2] + eps;
+  r = t_sqrt(r2);
+  const Dual inv_r = 1.0 / r;
+  Dual u[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) u[c] = D[c] * inv_r;
+  const Dual uu = r2 * g.inv_rc2;
+  f = make_dual(0.0);
+  if (valid && uu.v < 1.0) {
+    double fv, d1, d2;
+    cutoff_u2(g.cutoff, uu.v, fv, d1, d2);
+    f = make_dual(fv, d1 * uu.d);
+  }
+  M[0] = make_dual(valid ? 1.0 : 0.0);
+  for (int d = 1; d < g.nd; ++d) {
+    const unsigned long long w = cwl[d];
+    const int ex = (int)((w >> 24) & 7), ey = (int)((w >> 27) & 7);
+    const int parent = ex ? (int)((w >> 6) & 63) : (ey ? (int)((w >> 12) & 63) : (int)((w >> 18) & 63));
+    M[d] = M[parent] * (ex ? u[0] : (ey ? u[1] : u[2]));
+  }
+}
+
+// P[k][d] of one (centre, species block) and its tangent into PA (LDS): H_k = v_k fc with v_k, dv_k/dr from Hbuf
+__device__ __forceinline__ void dual_moments(const GrapParams &g, const unsigned long long *cwl, const double *Dv,
+                                             const double *Dd, int lo, int hi, double eps, int lane, Dual *PA) {
+  const int K = g.K, nd = g.nd;
+  for (int idx = lane; idx < K * nd; idx += kWave) PA[idx] = make_dual(0.0);
+  __syncthreads();
+  for (int first = lo; first < hi; first += kWave) {
+    const int q = first + lane;
+    const bool valid = q < hi;
+    Dual r, f, M[kMaxComp];
+    pair_dual(g, cwl, Dv, Dd, (size_t)q, valid, eps, r, f, M);
+    const double *hp = g.Hbuf + (size_t)(valid ? q : lo) * (2 * g.Ks);
+    for (int k = 0; k < K; ++k) {
+      const Dual H = make_dual(hp[k], hp[g.Ks + k] * r.d) * f;
+      for (int d = 0; d < nd; ++d) {
+        const Dual t = H * M[d];
+        const double sv = wave_sum(valid ? t.v : 0.0), sd = wave_sum(valid ? t.d : 0.0);
+        if (lane == 0) PA[k * nd + d] += make_dual(sv, sd);
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// G-dot [N][ndim] (zeroed by the caller: empty species blocks have G = 0): the forward expression's tangent,
+// Q-dot[k][m] = sum_d T[d][m] 2 P P-dot; moment 0 of the new formulation sgn(P0) Q0-dot / (2 sqrt(Q0 + 1e-16))
+__global__ __launch_bounds__(kWave) void grap_filter_tangent_kernel(GrapParams g, DeviceBatch b, int ndim, double eps,
+                                                                    const double *__restrict__ Dv,
+                                                                    const double *__restrict__ Dd, double *Gdot) {
+  __shared__ Dual PA[kMaxFilters * kMaxComp];
+  __shared__ unsigned long long cwl[kMaxComp];
+  __shared__ double Tl[kMaxComp * kMaxMom];
+  const int64_t i = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int nel = g.nel, K = g.K, nd = g.nd, nm = g.max_moment + 1;
+  const int sA = b.species[i];
+  const int32_t *seg = b.seg_start + (size_t)i * (nel + 1);
+  for (int d = lane; d < nd; d += kWave) cwl[d] = g.cw[d];
+  for (int t = lane; t < nd * kMaxMom; t += kWave) Tl[t] = g.T[t];
+  for (int sb = 0; sb < nel; ++sb) {
+    const int lo = seg[sb], hi = seg[sb + 1];
+    if (lo == hi) continue;
+    const int tb = term_block(sA, sb);
+    __syncthreads();
+    dual_moments(g, cwl, Dv, Dd, lo, hi, eps, lane, PA);
+    for (int idx = lane; idx < K * nm; idx += kWave) {
+      const int k = idx / nm, m = idx - k * nm;
+      const int col = g.col_of_m[m];
+      if (col < 0) continue;
+      double q = 0.0, qd = 0.0;
+      for (int d = 0; d < nd; ++d) {
+        const double t = Tl[d * kMaxMom + m];
+        const Dual P = PA[k * nd + d];
+        q = fma(t, P.v * P.v, q);
+        qd = fma(t, 2.0 * P.v * P.d, qd);
+      }
+      if (m == 0) {
+        const Dual P0 = PA[k * nd];
+        const double sgn = P0.v > 0.0 ? 1.0 : (P0.v < 0.0 ? -1.0 : 0.0);
+        qd = g.legacy ? P0.d : sgn * qd / (2.0 * sqrt(q + 1e-16));
+      }
+      Gdot[(size_t)i * ndim + ((size_t)tb * K + k) * g.nf + col] = qd;
+    }
+  }
+}
+
+// coef [P][2 Ks]: a_pk at [p][k], b_pk at [p][Ks + k]. A[k][d] = dE/dP[k][d] as in grap_hvp_kernel, with
+// w = dE/dG dual: value b.dEdG, tangent `kappa` = c_f w + H_mlp G-dot
+__global__ __launch_bounds__(kWave) void grap_filter_coeff_kernel(GrapParams g, DeviceBatch b, int ndim, double eps,
+                                                                  const double *__restrict__ Dv,
+                                                                  const double *__restrict__ Dd,
+                                                                  const double *__restrict__ kappa, double *coef) {
+  __shared__ Dual PA[kMaxFilters * kMaxComp];  // P[k][d], then A[k][d] in place
+  __shared__ Dual C0[kMaxFilters];
+  __shared__ unsigned long long cwl[kMaxComp];
+  __shared__ double Tl[kMaxComp * kMaxMom];
+  const int64_t i = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int nel = g.nel, K = g.K, nd = g.nd, Ks = g.Ks;
+  const int sA = b.species[i];
+  const int32_t *seg = b.seg_start + (size_t)i * (nel + 1);
+  for (int d = lane; d < nd; d += kWave) cwl[d] = g.cw[d];
+  for (int t = lane; t < nd * kMaxMom; t += kWave) Tl[t] = g.T[t];
+  const double *wv = b.dEdG + (size_t)i * ndim, *wd = kappa + (size_t)i * ndim;
+  for (int sb = 0; sb < nel; ++sb) {
+    const int lo = seg[sb], hi = seg[sb + 1];
+    if (lo == hi) continue;
+    const int tb = term_block(sA, sb);
+    __syncthreads();
+    dual_moments(g, cwl, Dv, Dd, lo, hi, eps, lane, PA);
+    const int col0 = g.col_of_m[0];
+    for (int k = lane; k < K; k += kWave) {
+      Dual c = make_dual(0.0);
+      if (col0 >= 0 && !g.legacy) {
+        const int col = (tb * K + k) * g.nf + col0;
+        const Dual w0 = make_dual(wv[col], wd[col]);
+        const Dual P0 = PA[k * nd];
+        const double sgn = P0.v > 0.0 ? 1.0 : (P0.v < 0.0 ? -1.0 : 0.0);
+        c = w0 * sgn / (2.0 * t_sqrt(P0 * P0 + 1e-16));
+      }
+      C0[k] = c;
+    }
+    __syncthreads();
+    for (int idx = lane; idx < K * nd; idx += kWave) {
+      const int d = idx % nd, k = idx / nd;
+      Dual s = make_dual(0.0), lin = make_dual(0.0);
+      for (int m = 0; m < kMaxMom; ++m) {
+        if (m > g.max_moment) break;
+        const int cm = g.col_of_m[m];
+        if (cm < 0) continue;
+        const int col = (tb * K + k) * g.nf + cm;
+        Dual c = make_dual(wv[col], wd[col]);
+        if (m == 0) {
+          if (g.legacy) {
+            if (d == 0) lin = c;
+            continue;
+          }
+          c = C0[k];
+        }
+        s = s + c * Tl[d * kMaxMom + m];
+      }
+      PA[idx] = 2.0 * PA[idx] * s + lin;
+    }
+    __syncthreads();
+    for (int first = lo; first < hi; first += kWave) {
+      const int q = first + lane;
+      const bool valid = q < hi;
+      Dual r, f, M[kMaxComp];
+      pair_dual(g, cwl, Dv, Dd, (size_t)q, valid, eps, r, f, M);
+      if (!valid) continue;
+      double *dst = coef + (size_t)q * (2 * Ks);
+      for (int k = 0; k < K; ++k) {
+        Dual hb = make_dual(0.0);
+        for (int d = 0; d < nd; ++d) hb = hb + PA[k * nd + d] * M[d];
+        dst[k] = f.v * hb.d + f.d * hb.v;
+        dst[Ks + k] = f.v * r.d * hb.v;
+      }
+    }
+  }
+}
+
+// padded layout of the filter network's gradient: layer l = W [kp][np[l]] at off[l] (kp = 1 for layer 0, else
+// np[l - 1]), then b [np[l]]
+struct NetGradLayout {
+  int off[kNetMaxLayers];
+  int n;
+};
+
+// d/dtheta sum_{p,k} a_pk v_k(x_p) + b_pk dv_k/dr (x_p): one wavefront per workgroup, 16 pairs per tile (lane =
+// pair m, unit quad kq), grid-stride over the tiles. Forward: value and r-tangent of every hidden layer kept in
+// LDS; reverse with two adjoints per unit (of h and of h'):
+//     lambda = kappa a'(z) + nu a''(z) z',  mu = nu a'(z),  dW += h_in lambda + h'_in mu,  db += lambda,
+//     kappa_in = W lambda [+ kappa],  nu_in = W mu [+ nu]  (ResNet skip),
+// pre-activations recomputed from the stored inputs. The output layer is linear: its (lambda, mu) are (a, b).
+// Each workgroup adds its tiles into its own partial row (no atomics); launch_grad_reduce sums the rows in
+// a fixed order.
+template <int ACT>
+__global__ __launch_bounds__(kWave) void grap_filter_grad_kernel(GrapNet net, DeviceBatch b, NetGradLayout lay,
+                                                                 const double *__restrict__ coef, int K, int Ks,
+                                                                 double *partial) {
+  extern __shared__ double lds[];
+  constexpr int kPer = kNetMaxWidth / 4;  // units of one layer per lane
+  const int act = ACT >= 0 ? ACT : net.act;
+  const int lane = threadIdx.x, m = lane & 15, kq = lane >> 4;
+  const int L = net.L, xs = net.xs;
+  const size_t slab = (size_t)kMlpTileRows * xs;
+  // hidden layer l: h at X + 2 l slab, dh/dr at X + (2 l + 1) slab; then lambda, mu, kappa, nu of one layer
+  double *X = lds;
+  double *GA = X + 2 * (size_t)(L - 1) * slab, *GD = GA + slab, *AA = GD + slab, *AD = AA + slab;
+  __shared__ double xin[kMlpTileRows], xdin[kMlpTileRows];
+  double *part = partial + (size_t)blockIdx.x * lay.n;
+  const int64_t ntiles = (b.n_pairs + kMlpTileRows - 1) / kMlpTileRows;
+  bool first = true;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int64_t p = t * kMlpTileRows + m;
+    const bool valid = p < b.n_pairs;
+    double x = valid ? sqrt(b.rec[kRecDoubles * (size_t)p + 3]) : 0.0;
+    double xd = valid ? 1.0 : 0.0;  // d(input) / dr
+    if (net.modifier && valid) {
+      const double ir = net.inv_rcov[b.species[b.pair_i[p]]];
+      if (net.modifier == 1) {
+        x *= ir;
+        xd = ir;
+      } else {
+        x = exp(-x * ir);
+        xd = -x * ir;
+      }
+    }
+    __syncthreads();  // the previous tile's reads are done
+    if (kq == 0) {
+      xin[m] = x;
+      xdin[m] = xd;
+    }
+    for (int c = kq; c < net.np[0]; c += 4) {
+      const double wk = net.w[0][c];
+      double h, dh;
+      activation_fn(act, fma(wk, x, net.b[0][c]), h, dh);
+      X[m * xs + c] = h;
+      X[slab + m * xs + c] = dh * wk * xd;
+    }
+    __syncthreads();
+    for (int l = 1; l < L - 1; ++l) {
+      const int kp = net.np[l - 1], np = net.np[l];
+      const double *W = net.w[l];
+      const double *Xi = X + 2 * (size_t)(l - 1) * slab, *Xid = Xi + slab;
+      double *Xo = X + 2 * (size_t)l * slab, *Xod = Xo + slab;
+      for (int c = kq; c < np; c += 4) {
+        double z = net.b[l][c], zd = 0.0;
+        for (int k = 0; k < kp; ++k) {
+          const double w = W[(size_t)k * np + c];
+          z = fma(w, Xi[m * xs + k], z);
+          zd = fma(w, Xid[m * xs + k], zd);
+        }
+        double h, dh;
+        activation_fn(act, z, h, dh);
+        double hd = dh * zd;
+        if (net.res[l]) {
+          h += Xi[m * xs + c];
+          hd += Xid[m * xs + c];
+        }
+        Xo[m * xs + c] = h;
+        Xod[m * xs + c] = hd;
+      }
+      __syncthreads();
+    }
+    for (int c = kq; c < net.np[L - 1]; c += 4) {
+      const bool on = valid && c < K;
+      GA[m * xs + c] = on ? coef[(size_t)p * (2 * Ks) + c] : 0.0;
+      GD[m * xs + c] = on ? coef[(size_t)p * (2 * Ks) + Ks + c] : 0.0;
+    }
+    __syncthreads();
+    for (int l = L - 1; l >= 0; --l) {
+      const int np = net.np[l], kp = l ? net.np[l - 1] : 1;
+      double *pw = part + lay.off[l], *pb = pw + (size_t)kp * np;
+      const double *Hi = l ? X + 2 * (size_t)(l - 1) * slab : nullptr;
+      for (int idx = lane; idx < kp * np; idx += kWave) {
+        const int k = idx / np, n = idx - k * np;
+        double s = 0.0;
+        if (l) {
+#pragma unroll 4
+          for (int r = 0; r < kMlpTileRows; ++r)
+            s = fma(GA[r * xs + n], Hi[r * xs + k], fma(GD[r * xs + n], Hi[slab + r * xs + k], s));
+        } else {
+#pragma unroll 4
+          for (int r = 0; r < kMlpTileRows; ++r) s = fma(GA[r * xs + n], xin[r], fma(GD[r * xs + n], xdin[r], s));
+        }
+        pw[idx] = first ? s : pw[idx] + s;
+      }
+      for (int n = lane; n < np; n += kWave) {
+        double s = 0.0;
+        for (int r = 0; r < kMlpTileRows; ++r) s += GA[r * xs + n];
+        pb[n] = first ? s : pb[n] + s;
+      }
+      if (l == 0) break;
+      // adjoints of layer l - 1's output, then of its pre-activation (recomputed from its stored input)
+      const double *W = net.w[l];
+      double ga[kPer], gd[kPer], aa[kPer], ad[kPer];
+#pragma unroll
+      for (int j = 0; j < kPer; ++j) {
+        const int c = kq + 4 * j;
+        ga[j] = gd[j] = aa[j] = ad[j] = 0.0;
+        if (c >= kp) continue;
+        double sa = 0.0, sd = 0.0;
+        for (int n = 0; n < np; ++n) {
+          const double w = W[(size_t)c * np + n];
+          sa = fma(w, GA[m * xs + n], sa);
+          sd = fma(w, GD[m * xs + n], sd);
+        }
+        if (net.res[l]) {
+          sa += AA[m * xs + c];
+          sd += AD[m * xs + c];
+        }
+        double z, zd;
+        if (l == 1) {
+          const double wk = net.w[0][c];
+          z = fma(wk, xin[m], net.b[0][c]);
+          zd = wk * xdin[m];
+        } else {
+          const int kp2 = net.np[l - 2];
+          const double *W2 = net.w[l - 1];
+          const double *Xi = X + 2 * (size_t)(l - 2) * slab;
+          z = net.b[l - 1][c];
+          zd = 0.0;
+          for (int k = 0; k < kp2; ++k) {
+            const double w = W2[(size_t)k * kp + c];
+            z = fma(w, Xi[m * xs + k], z);
+            zd = fma(w, Xi[slab + m * xs + k], zd);
+          }
+        }
+        double h, d1, d2;
+        activation_fn2(act, z, h, d1, d2);
+        ga[j] = fma(sa, d1, sd * d2 * zd);
+        gd[j] = sd * d1;
+        aa[j] = sa;
+        ad[j] = sd;
+      }
+      __syncthreads();  // every read of this layer's adjoints is done
+#pragma unroll
+      for (int j = 0; j < kPer; ++j) {
+        const int c = kq + 4 * j;
+        if (c >= kp) continue;
+        GA[m * xs + c] = ga[j];
+        GD[m * xs + c] = gd[j];
+        AA[m * xs + c] = aa[j];
+        AD[m * xs + c] = ad[j];
+      }
+      __syncthreads();
+    }
+    first = false;
+  }
+}
+
 }  // namespace
 
 struct GrapModel {
@@ -896,6 +1249,7 @@ struct GrapModel {
   double *Hbuf = nullptr;
   size_t cap_pairs = 0;
   size_t net_lds = 0;
+  int sizes[kNetMaxLayers + 1] = {0};    // real layer widths 1, h1, ..., K
 };
 
 void grap_destroy(GrapModel *g);
@@ -919,6 +1273,7 @@ void build_filter_net(GrapModel *g, const double *q, int n, int K, std::string &
     if (l > 0) need += (size_t)sizes[l - 1] * sizes[l] + sizes[l];
   }
   if (sizes[0] != 1 || sizes[L] != K) fail("GRAP/nn: the network maps 1 input to K filters");
+  for (int l = 0; l <= L; ++l) g->sizes[l] = sizes[l];
   const int nel = g->p.nel;
   if (modifier) need += (size_t)nel;  // covalent radii of the elements close the block
   if ((size_t)n != need) fail("grap_params: wrong length for the filter network");
@@ -1219,6 +1574,128 @@ void launch_grap_backward(GrapModel *g, const DeviceBatch &b, hipStream_t s) {
   else
     hipLaunchKernelGGL(grap_backward_kernel<kMaxComp>, dim3((unsigned)b.n_atoms), dim3(kWave), lds, s, g->p, b,
                        g->Pbuf, g->ndim);
+}
+
+// ---- training the filter network ----------------------------------------------------------------------
+void launch_grad_reduce(const double *partial, int n_blocks, int n_params, double *grad, hipStream_t s);
+
+namespace {
+NetGradLayout net_grad_layout(const GrapModel *g) {
+  NetGradLayout lay;
+  std::memset(&lay, 0, sizeof(lay));
+  int off = 0;
+  for (int l = 0; l < g->net.L; ++l) {
+    const int kp = l ? g->net.np[l - 1] : 1, np = g->net.np[l];
+    lay.off[l] = off;
+    off += kp * np + np;
+  }
+  lay.n = off;
+  return lay;
+}
+
+size_t filter_grad_lds(const GrapModel *g) {
+  return (2 * (size_t)(g->net.L - 1) + 4) * kMlpTileRows * g->net.xs * sizeof(double);
+}
+
+constexpr size_t kFilterGradLds = 160 * 1024;            // gfx950: LDS of one workgroup
+constexpr size_t kFilterPartialDoubles = (size_t)8 << 20;  // 64 MB of per-workgroup partial rows at most
+
+unsigned filter_grad_blocks(const GrapModel *g, const DeviceBatch &b) {
+  const int64_t tiles = (b.n_pairs + kMlpTileRows - 1) / kMlpTileRows;
+  const int64_t cap = std::max<int64_t>(1, (int64_t)(kFilterPartialDoubles / (size_t)net_grad_layout(g).n));
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>({tiles, (int64_t)1024, cap}));
+}
+}  // namespace
+
+// flat layout of ta_filter_param_count: per layer W [in][out] row-major, then b [out] (zeros: no bias)
+int64_t grap_filter_param_count(const GrapModel *g) {
+  if (g->p.algo != GRAP_NN) return 0;
+  int64_t n = 0;
+  for (int l = 0; l < g->net.L; ++l) n += (int64_t)g->sizes[l] * g->sizes[l + 1] + g->sizes[l + 1];
+  return n;
+}
+
+// the network's weights from the flat layout into the padded device copies (the caller synchronised)
+void grap_update_filter_weights(GrapModel *g, const double *flat, int64_t n) {
+  if (g->p.algo != GRAP_NN) throw std::invalid_argument("ta_update_filter_weights: the model has no filter network");
+  const int64_t want = grap_filter_param_count(g);
+  if (n != want)
+    throw std::invalid_argument("ta_update_filter_weights: expected " + std::to_string(want) + " values");
+  const double *src = flat;
+  for (int l = 0; l < g->net.L; ++l) {
+    const int k = g->sizes[l], nn = g->sizes[l + 1];
+    const int kp = l == 0 ? 1 : g->net.np[l - 1], np = g->net.np[l];
+    std::vector<double> w((size_t)kp * np, 0.0), bb(np, 0.0);
+    for (int a = 0; a < k; ++a)
+      for (int c = 0; c < nn; ++c) w[(size_t)a * np + c] = src[(size_t)a * nn + c];
+    src += (size_t)k * nn;
+    for (int c = 0; c < nn; ++c) bb[c] = src[c];
+    src += nn;
+    if (hipMemcpy(const_cast<double *>(g->net.w[l]), w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice) !=
+            hipSuccess ||
+        hipMemcpy(const_cast<double *>(g->net.b[l]), bb.data(), bb.size() * sizeof(double), hipMemcpyHostToDevice) !=
+            hipSuccess)
+      throw std::runtime_error("hipMemcpy of the GRAP filter network failed");
+  }
+}
+
+// empty: the filter gradient can be formed for this model; else why not
+std::string grap_filter_train_refusal(const GrapModel *g) {
+  if (g->p.algo != GRAP_NN) return "the model's radial filters are analytic functions, not the `nn` filter network";
+  if (g->p.K > kMaxFilters) return "at most " + std::to_string(kMaxFilters) + " filters";
+  if (filter_grad_lds(g) > kFilterGradLds) return "the filter network is too wide / deep for the training tile's LDS";
+  return "";
+}
+
+// doubles of device scratch: coefficients [P][2 Ks], padded gradient, per-workgroup partial rows
+size_t grap_filter_grad_doubles(const GrapModel *g, const DeviceBatch &b) {
+  const size_t n = (size_t)net_grad_layout(g).n;
+  return (size_t)b.n_pairs * 2 * g->p.Ks + n + (size_t)filter_grad_blocks(g, b) * n;
+}
+
+// G-dot [N][ndim] along the pair tangents Dd (Dv: the pair vectors)
+void launch_grap_filter_tangent(GrapModel *g, const DeviceBatch &b, double eps, const double *Dv, const double *Dd,
+                                double *Gdot, hipStream_t s) {
+  if (b.n_atoms == 0) return;
+  (void)hipMemsetAsync(Gdot, 0, (size_t)b.n_atoms * g->ndim * sizeof(double), s);
+  hipLaunchKernelGGL(grap_filter_tangent_kernel, dim3((unsigned)b.n_atoms), dim3(kWave), 0, s, g->p, b, g->ndim, eps,
+                     Dv, Dd, Gdot);
+}
+
+// d/dtheta_filter (sum_f c_f E_f + D_delta E) into `grad` (ta_filter_param_count values, host), from the
+// dual-w tangent kappa = c w + H_mlp G-dot [N][ndim]; `scratch` holds grap_filter_grad_doubles
+void grap_filter_gradient(GrapModel *g, const DeviceBatch &b, double eps, const double *Dv, const double *Dd,
+                          const double *kappa, double *scratch, double *grad, hipStream_t s) {
+  const NetGradLayout lay = net_grad_layout(g);
+  std::vector<double> pad((size_t)lay.n, 0.0);
+  if (b.n_atoms > 0 && b.n_pairs > 0) {
+    const int Ks = g->p.Ks;
+    double *coef = scratch, *gpad = coef + (size_t)b.n_pairs * 2 * Ks, *partial = gpad + lay.n;
+    hipLaunchKernelGGL(grap_filter_coeff_kernel, dim3((unsigned)b.n_atoms), dim3(kWave), 0, s, g->p, b, g->ndim, eps,
+                       Dv, Dd, kappa, coef);
+    const unsigned blocks = filter_grad_blocks(g, b);
+    const size_t lds = filter_grad_lds(g);
+    if (g->net.act == TA_ACT_SOFTPLUS)
+      hipLaunchKernelGGL(grap_filter_grad_kernel<TA_ACT_SOFTPLUS>, dim3(blocks), dim3(kWave), lds, s, g->net, b, lay,
+                         coef, g->p.K, Ks, partial);
+    else
+      hipLaunchKernelGGL(grap_filter_grad_kernel<-1>, dim3(blocks), dim3(kWave), lds, s, g->net, b, lay, coef, g->p.K,
+                         Ks, partial);
+    launch_grad_reduce(partial, (int)blocks, lay.n, gpad, s);
+    if (hipGetLastError() != hipSuccess) throw std::runtime_error("GRAP filter gradient: launch failed");
+    if (hipMemcpyAsync(pad.data(), gpad, pad.size() * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+      throw std::runtime_error("GRAP filter gradient: download failed");
+  }
+  // padded -> flat layout (per layer W [in][out], b [out])
+  double *dst = grad;
+  for (int l = 0; l < g->net.L; ++l) {
+    const int k = g->sizes[l], nn = g->sizes[l + 1], np = g->net.np[l], kp = l ? g->net.np[l - 1] : 1;
+    const double *pw = pad.data() + lay.off[l], *pb = pw + (size_t)kp * np;
+    for (int a = 0; a < k; ++a)
+      for (int c = 0; c < nn; ++c) *dst++ = pw[(size_t)a * np + c];
+    for (int c = 0; c < nn; ++c) *dst++ = pb[c];
+  }
 }
 
 }  // namespace ta

@@ -440,6 +440,37 @@ class Engine:
             return grad, (tangent * scale() if scale is not None else tangent)
         return grad
 
+    # -- the GRAP `nn` filter network as trainable parameters -----------------------------
+    def filter_param_count(self) -> int:
+        """Length of the filter network's flat vector (0 without one): per layer W[in][out], b[out]."""
+        n = C.c_int64(0)
+        self._check(self._lib.ta_filter_param_count(self._handle, C.byref(n)))
+        return int(n.value)
+
+    def update_filter_weights(self, flat):
+        """Replace the filter network of the live handle (layout of `filter_param_count`); the resident
+        descriptors are recomputed on their next use."""
+        flat = np.ascontiguousarray(flat, dtype=np.float64).ravel()
+        self._check(self._lib.ta_update_filter_weights(self._handle, _lib.as_dp(flat), len(flat)))
+
+    def grap_loss_gradient(self, frame_coeff=None, dR=None, dh=None) -> np.ndarray:
+        """`loss_gradient` of a GRAP/nn model with respect to [MLP weights | filter network]
+        (`ta_grap_loss_gradient`); dR = dh = None: the energy term only."""
+        null = C.POINTER(C.c_double)()
+        N, F = int(self.info.n_atoms), int(self.info.n_frames)
+
+        def arr(a, shape):
+            if a is None:
+                return None, null
+            a = np.ascontiguousarray(a, dtype=np.float64).reshape(shape)
+            return a, _lib.as_dp(a)
+        c, cp = arr(frame_coeff, (F,))
+        r, rp = arr(dR, (N, 3))
+        hh, hp = arr(dh, (F, 9))
+        grad = np.zeros(self.param_count() + self.filter_param_count())
+        self._check(self._lib.ta_grap_loss_gradient(self._handle, cp, rp, hp, _lib.as_dp(grad), len(grad)))
+        return grad
+
     def td_loss_gradient(self, coeff_free_energy=None, coeff_energy=None, coeff_eentropy=None, dR=None, dh=None,
                          return_tangent=False):
         """Temperature-dependent models: d/dtheta (sum_f (a_f U_f + b_f F_f + g_f S_f) + D_delta F) for the

@@ -7,10 +7,19 @@ Mirrors, for the energy term, reference nn/losses.py:204-285 (`get_energy_loss`:
 RMSE with the dtype's eps under the root, or log-cosh), nn/opt.py:89-166 (Adam with optional
 exponential learning-rate decay) and train/distribute_utils.py:56-81 (mean of the replicas'
 gradients; here `torch.distributed` all-reduce: RCCL between GPUs, gloo in the CPU tests).
-Force and stress terms of the loss need second derivatives of the descriptors and are not built.
+`EnergyTrainer`: descriptors do not depend on the MLP weights, so each rank keeps its shard of frames
+resident, computes the descriptors once, and every step re-runs only the MLP (forward for the loss,
+backward for dL/dtheta). `Trainer` adds the force and stress terms through second derivatives (see its
+docstring).
 
-Descriptors do not depend on the weights: each rank keeps its shard of frames resident, computes the
-descriptors once, and every step re-runs only the MLP (forward for the loss, backward for dL/dtheta).
+A GRAP model with the `nn` algorithm can also train its filter network, which the reference does by
+default (`NNAlgorithm.trainable`, grap.py:235; no L2 term on it): `Trainer(..., train_filters=True)`.
+Then the descriptors DO depend on theta, and every step recomputes them; `ta_grap_loss_gradient` returns
+[MLP weights | filter network] of d/dtheta (sum_f c_f E_f + D_delta E): the descriptors' tangent by dual
+arithmetic through the GRAP forward expression, the MLP's second-order pass, per-pair adjoints
+    a_pk = fc (c_f Hbar_pk + Hbar-dot_pk) + fc' r-dot_p Hbar_pk,   b_pk = fc r-dot_p Hbar_pk
+of the filter values v_k(x_p) and their r-derivatives (Hbar = dE/dH, H_pk = v_k(x_p) fc(r_p)), and one
+second-order sweep through the filter network with those adjoints.
 """
 from __future__ import annotations
 
@@ -121,6 +130,51 @@ def energy_loss(predictions, labels, n_atoms, method="rmse", per_atom_loss=True,
     else:
         raise ValueError(f"loss method '{method}' is not implemented for training")
     return float(weight * loss), mae, weight * dl
+
+
+def _filter_layers(nn):
+    """The `nn` filter network's layers of a GRAP model, or None."""
+    desc = getattr(nn, "descriptor", None)
+    if desc is None or getattr(getattr(desc, "algorithm", None), "name", None) != "nn":
+        return None
+    return desc.filter_weights
+
+
+def flatten_filter_weights(nn) -> np.ndarray:
+    """The filter network in the C ABI's layout (`ta_filter_param_count`): per layer W[in][out]
+    row-major then b[out] (zeros where the layer has no bias)."""
+    out = []
+    for w, b in _filter_layers(nn):
+        w = np.asarray(w, dtype=np.float64)
+        out.append(w.ravel())
+        out.append(np.zeros(w.shape[1]) if b is None else np.asarray(b, dtype=np.float64).ravel())
+    return np.concatenate(out)
+
+
+def unflatten_filter_weights(nn, flat: np.ndarray) -> List:
+    """Inverse of `flatten_filter_weights`; layers without a bias keep `None`."""
+    flat = np.asarray(flat, dtype=np.float64)
+    layers, k = [], 0
+    for w, b in _filter_layers(nn):
+        shape = np.shape(w)
+        n = shape[0] * shape[1]
+        w2 = flat[k:k + n].reshape(shape).copy()
+        k += n
+        b2 = None if b is None else flat[k:k + shape[1]].copy()
+        k += shape[1]
+        layers.append((w2, b2))
+    return layers
+
+
+def filter_trainable_mask(nn) -> np.ndarray:
+    """1 for the filter network's real parameters, 0 for the bias slots of layers without a bias (the
+    output layer, grap.py:640)."""
+    out = []
+    for w, b in _filter_layers(nn):
+        shape = np.shape(w)
+        out.append(np.ones(shape[0] * shape[1]))
+        out.append(np.zeros(shape[1]) if b is None else np.ones(shape[1]))
+    return np.concatenate(out)
 
 
 def _lib_want_all():
@@ -386,6 +440,12 @@ class Trainer:
     `eentropies` those of S, each an `energy_loss` with `method` / `per_atom_loss` and its own weight.
     Forces, stress and pressure are those of F; each frame's electron temperature is
     `atoms.info["etemperature"]`. The analytic gradient is one `ta_td_loss_gradient` call.
+
+    `train_filters=True` (GRAP models with the `nn` algorithm and `trainable` filters, analytic gradients
+    only, not temperature-dependent) also fits the filter network, as the reference does: theta = [MLP
+    weights | filter network], one `ta_grap_loss_gradient` call per step, the filter entries outside the
+    L2 term (the reference builds that network with l2_weight = 0); `fit()` writes the trained network back
+    to `nn.descriptor.filter_weights`. The default keeps the filters frozen.
     """
 
     def __init__(self, nn, frames, energies, forces=None, stresses=None, device=None,
@@ -394,9 +454,19 @@ class Trainer:
                  pressures=None, pressure_weight=1.0, forces_method=None, l2_weight=0.0, l2_loss_weight=0.01,
                  l2_decayed=True, l2_decay_rate=0.99, l2_decay_steps=1000, max_train_steps=None,
                  logscaled_dynamic_weight=True, train_constants=None, free_energies=None, eentropies=None,
-                 free_energy_weight=1.0, eentropy_weight=1.0, **adam_kwargs):
+                 free_energy_weight=1.0, eentropy_weight=1.0, train_filters=False, **adam_kwargs):
         from .engine import Engine
         self.td = _is_td(nn)
+        self.train_filters = bool(train_filters)
+        if self.train_filters:
+            if _filter_layers(nn) is None:
+                raise ValueError("train_filters: only a GRAP model with the 'nn' algorithm has a filter network")
+            if not nn.descriptor.algorithm.trainable:
+                raise ValueError("train_filters: the filter network was built with trainable=False")
+            if analytic is not None and not analytic:
+                raise ValueError("train_filters: the filter network is trained with analytic gradients only")
+            if self.td:
+                raise ValueError("train_filters: not available for temperature-dependent models")
         if not self.td and (free_energies is not None or eentropies is not None):
             raise ValueError("free_energies / eentropies are labels of temperature-dependent models")
         if self.td:
@@ -458,6 +528,10 @@ class Trainer:
                 self._n_weights = len(self.theta)
                 self.theta = np.concatenate([self.theta, nn.constants()])
                 self.mask = np.concatenate([self.mask, nn.constant_mask(fixed)])
+            elif self.train_filters:   # theta = [weights | filter network]
+                self._n_weights = len(self.theta)
+                self.theta = np.concatenate([self.theta, flatten_filter_weights(nn)])
+                self.mask = np.concatenate([self.mask, filter_trainable_mask(nn)])
         self.opt = Adam(len(self.theta), learning_rate=learning_rate, **adam_kwargs)
         self.history: List[dict] = []
 
@@ -468,7 +542,8 @@ class Trainer:
         # set_frames / update_positions on the (public) engine in between bumps its generation
         if self.analytic and self._resident and eng.batch_generation == self._generation:
             # same frames as the last step: the batch, its neighbour list, descriptors and their
-            # Jacobian are resident; only the MLP changed
+            # Jacobian are resident; only the MLP changed (with train_filters the network changed too:
+            # a compute with forces never reuses descriptors, and update_filter_weights invalidated them)
             eng.compute(_lib_want_all())
             res = eng._per_frame(eng.fetch(_lib_want_all()))
         else:
@@ -532,6 +607,8 @@ class Trainer:
             dh = np.array([np.asarray(a.get_cell(complete=True), dtype=np.float64) @ Y[k]
                            for k, a in enumerate(self.frames)])
             gradient = eng.constant_gradient if self.constants_mode else eng.loss_gradient
+            if self.train_filters:
+                gradient = eng.grap_loss_gradient
             if self.td:
                 gradient = lambda cf, r, h: eng.td_loss_gradient(cf, td_coeff.get("energy"),  # noqa: E731
                                                                  td_coeff.get("eentropy"), r, h)
@@ -570,7 +647,7 @@ class Trainer:
             eng.set_frames(self.frames)
             grad = np.concatenate([grad, eng.constant_gradient(c, Rc if second else None, hc if second else None)])
         if self.l2["l2_weight"] > 0.0 and self.l2["weight"] != 0.0 and not self.constants_mode:
-            nw = self._n_weights if self.mixed else len(self.theta)
+            nw = self._n_weights if (self.mixed or self.train_filters) else len(self.theta)
             l2, g2 = l2_regularization_loss(self.nn, self.theta[:nw], step=step, **self.l2)
             terms["l2"] = l2
             # every replica adds the same regulariser: the mean over ranks (step) leaves it as it is
@@ -593,6 +670,9 @@ class Trainer:
         elif self.mixed:
             self.engine.update_weights(self.theta[:self._n_weights])
             self.engine.update_constants(self.theta[self._n_weights:])
+        elif self.train_filters:
+            self.engine.update_weights(self.theta[:self._n_weights])
+            self.engine.update_filter_weights(self.theta[self._n_weights:])
         else:
             self.engine.update_weights(self.theta)
         self.history.append(dict(terms, total=total))
@@ -606,6 +686,9 @@ class Trainer:
         elif self.mixed:
             self.nn.weights = unflatten_weights(self.nn, self.theta[:self._n_weights])
             self.nn.set_constants(self.theta[self._n_weights:])
+        elif self.train_filters:
+            self.nn.weights = unflatten_weights(self.nn, self.theta[:self._n_weights])
+            self.nn.descriptor.filter_weights = unflatten_filter_weights(self.nn, self.theta[self._n_weights:])
         else:
             self.nn.weights = unflatten_weights(self.nn, self.theta)
         return self.history
