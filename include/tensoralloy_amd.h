@@ -456,6 +456,25 @@ int ta_hessian_vectors(ta_handle h, int32_t n_dir, int32_t first, const double *
  * ta_compute uses the new mode (call ta_set_frames again if a Verlet skin is in use). */
 int ta_set_nn_tables(ta_handle h, int on);
 
+/* The `nn` filter network of a GRAP model (grap.py:620-643) through a table, for inference. `on` != 0
+ * tabulates the network once, as cubic Hermite pieces of all K outputs over the network's own input x
+ * (h_abck_modifier 0: r in [0, rcut]; 1: r / rcov in [0, rcut / min rcov]; 2: exp(-r / rcov) in [0, 1];
+ * rcov of the centre's element), value and x-derivative exact at every knot, `n_knots` knots (0 = the
+ * library default, 4097; otherwise 5 .. 2^20 + 1, else TA_ERR_INVALID). A step then costs one 32-byte
+ * read and 3 to 5 FMAs per (pair, filter) instead of the network, and the per-pair filter buffer and the
+ * geometry pre-pass are gone. Forces use the derivative of the same cubic, so energy and forces stay
+ * consistent. `on` = 0 drops the table. OFF by default: the exact evaluation is what a handle does unless
+ * asked. At the default knot count the two differ by less than 1e-11 eV and 1e-10 eV/A per structure.
+ * Synchronises the stream and invalidates the resident descriptors and pair Jacobians; nothing resident is
+ * lost, Verlet-skin lists included. ta_update_filter_weights rebuilds the table. Entries that form a weight
+ * gradient on a GRAP handle (ta_energy_gradient, ta_loss_gradient, ta_grap_loss_gradient,
+ * ta_td_loss_gradient) need the network itself: the first such call switches the handle to exact
+ * evaluation for good, after which `on` != 0 is ignored. ta_hessian_vectors evaluates exactly for the
+ * duration of the call and leaves the table on. No effect (TA_OK) on a model without a filter network.
+ *   ta_filter_table_knots    the knot count in use, 0 while the handle evaluates the network exactly */
+int ta_set_filter_tables(ta_handle h, int on, int32_t n_knots);
+int ta_filter_table_knots(ta_handle h, int32_t *n_knots);
+
 /* Tables of an EAM / ADP model's functions (analytic, nn or tabulated) on caller-supplied abscissae: what
  * `EamAlloyNN.export_to_setfl` (nn/eam/alloy.py:198-381) evaluates through a TF session before it
  * writes a LAMMPS setfl file. Rows: elements (sorted) for rho(r) [n_elements][n_r] and F(rho)

@@ -8,6 +8,9 @@ that is bench.py). Prints one JSON object; run through gpurun and keep the outpu
   C3  Ni-Mo binary alloy (3920 atoms, 8:2), cross-element G2/G4, 2x128 MLP, E+F+virial
   C4  EAM (zjw04) and ADP (zjw04 + mishinh) for 4000-atom Ni, E+F+virial
   C5  batch of independent 4000-atom frames on one GPU (the per-GPU share of the 512-frame job)
+  N1  GRAP: pexp (N1_grap_Ni, N1_grap_NiMo), the `nn` filter network exact (N1_grap_nn_Ni) and, new beside it in
+      the full run too, through its Hermite table (N1_grap_nn_tables_Ni); `--grap-tables`: those three Ni rows
+      alone, five timed runs each (profiles/grap_filter_tables.json)
 """
 import json
 import os
@@ -77,22 +80,79 @@ def bench_nn_eam(steps=50):
     return out
 
 
-def bench_grap_nn(steps=50):
+def _repeat(eng, repeats, steps):
+    """`repeats` timed runs of `steps` evaluations each: median, all of them, and the kernel slots of the median run"""
+    runs = sorted((timeit(eng, WANT, steps=steps) for _ in range(repeats)), key=lambda t: t[0])
+    ms, slots = runs[len(runs) // 2]
+    return ms, slots, [t[0] for t in runs]
+
+
+def bench_grap_nn(steps=50, repeats=1):
     """GRAP with the `nn` filter network of defaults.toml `[nn.atomic.grap.nn]` (softplus, hidden
-    32-32-32 with ResNet skips, 16 filters), moments 0..3, rc 6.0, MLP 2 x 64."""
+    32-32-32 with ResNet skips, 16 filters), moments 0..3, rc 6.0, MLP 2 x 64: the network evaluated
+    exactly for every pair (N1_grap_nn_Ni) and through its Hermite table (N1_grap_nn_tables_Ni,
+    `Engine.set_filter_tables`), same model, same frame, same engine."""
     from tests.helpers import make_grap_nn, oracle_grap_eval
     atoms = ni_frame(611)
     nn = make_grap_nn(["Ni"], 6.0, [64, 64], "nn", moment_tensors=[0, 1, 2, 3])
+    o = oracle_grap_eval(nn, atoms)
+    out = {}
+    with Engine(nn) as eng:
+        exact = None
+        for tag, tables in (("N1_grap_nn_Ni", False), ("N1_grap_nn_tables_Ni", True)):
+            eng.set_filter_tables(tables)
+            r = eng.evaluate([atoms])[0]
+            ms, slots, runs = _repeat(eng, repeats, steps)
+            row = {"atoms": len(atoms), "pairs": int(eng.info.n_pairs), "D": nn.ndim(), "ms_per_eval": ms,
+                   "atom_steps_per_s": len(atoms) / ms * 1e3, "kernel_ms": slots,
+                   "filter_table_knots": eng.filter_table_knots,
+                   "parity": {"dE_eV": abs(o["energy"] - r["energy"]),
+                              "dF_max": float(np.abs(o["forces"] - r["forces"]).max()),
+                              "dW_max": float(np.abs(o["virial"] - r["virial"]).max())}}
+            if repeats > 1:
+                row["ms_per_eval_runs"] = runs
+            if tables:
+                row["vs_exact"] = {"dE_eV": abs(exact["energy"] - r["energy"]),
+                                   "dF_max": float(np.abs(exact["forces"] - r["forces"]).max()),
+                                   "dW_max": float(np.abs(exact["virial"] - r["virial"]).max())}
+            else:
+                exact = r
+            out[tag] = row
+    return out
+
+
+def bench_grap_pexp(tag, els, atoms, steps=100, repeats=1):
+    """N1: the reference's default production descriptor (io/input/defaults.toml:131-155):
+    GRAP, pexp, 16 filters, moments 0..3, new mode, cosine cutoff, rc = 6.0; MLP 2 x 64"""
+    from oracle import grap as ograp
+    from tensoralloy_amd.grap import GenericRadialAtomicPotential
+    rl = [1.0 + 0.2 * k for k in range(16)]
+    pl = [5.0 - 0.25 * k for k in range(16)]
+    gd = GenericRadialAtomicPotential(els, "pexp", {"rl": rl, "pl": pl}, moment_tensors=[0, 1, 2, 3],
+                                      legacy_mode=False)
+    nn = AtomicNN(els, gd, hidden_sizes=[64, 64], activation="softplus", minmax_scale=False,
+                  export_properties=("energy", "forces", "stress"))
+    nn.attach_transformer(UniversalTransformer(els, rcut=6.0))
+    nn.initialize(seed=611)
     with Engine(nn) as eng:
         r = eng.evaluate([atoms])[0]
-        ms, slots = timeit(eng, WANT, steps=steps)
-        o = oracle_grap_eval(nn, atoms)
-        return {"N1_grap_nn_Ni": {
-            "atoms": len(atoms), "pairs": int(eng.info.n_pairs), "D": nn.ndim(), "ms_per_eval": ms,
-            "atom_steps_per_s": len(atoms) / ms * 1e3, "kernel_ms": slots,
-            "parity": {"dE_eV": abs(o["energy"] - r["energy"]),
-                       "dF_max": float(np.abs(o["forces"] - r["forces"]).max()),
-                       "dW_max": float(np.abs(o["virial"] - r["virial"]).max())}}}
+        ms, slots, runs = _repeat(eng, repeats, steps)
+        d = gd.as_dict()
+        om = ograp.GrapModel(els, 6.0, algorithm="pexp", parameters=d["parameters"],
+                             moment_tensors=d["moment_tensors"], legacy_mode=False,
+                             weights=nn.weights, activation="softplus")
+        t0 = time.perf_counter()
+        o = ograp.evaluate(om, atoms.get_chemical_symbols(), atoms.positions,
+                           np.asarray(atoms.get_cell()), atoms.pbc)
+        row = {"atoms": len(atoms), "pairs": int(eng.info.n_pairs), "D": nn.ndim(),
+               "ms_per_eval": ms, "atom_steps_per_s": len(atoms) / ms * 1e3, "kernel_ms": slots,
+               "parity": {"dE_eV": abs(o["energy"] - r["energy"]),
+                          "dF_max": float(np.abs(o["forces"] - r["forces"]).max()),
+                          "dW_max": float(np.abs(o["virial"] - r["virial"]).max()),
+                          "cpu_oracle_s": time.perf_counter() - t0}}
+        if repeats > 1:
+            row["ms_per_eval_runs"] = runs
+        return {tag: row}
 
 
 def main():
@@ -102,6 +162,11 @@ def main():
         return
     if "--grap-nn" in sys.argv:
         print(json.dumps(bench_grap_nn(), indent=1))
+        return
+    if "--grap-tables" in sys.argv:   # the three GRAP rows of one session, five timed runs each
+        out = bench_grap_nn(repeats=5)
+        out.update(bench_grap_pexp("N1_grap_Ni", ["Ni"], ni_frame(611), repeats=5))
+        print(json.dumps(out, indent=1))
         return
     out = {}
 
@@ -178,39 +243,13 @@ def main():
     # alloy.py:110-112, Defaults.hidden_sizes)
     out.update(bench_nn_eam())
     out.update(bench_grap_nn())
-    # ---- N1: the reference's default production descriptor (io/input/defaults.toml:131-155):
-    # GRAP, pexp, 16 filters, moments 0..3, new mode, cosine cutoff, rc = 6.0; MLP 2 x 64
-    from oracle import grap as ograp
-    from tensoralloy_amd.grap import GenericRadialAtomicPotential
-    rl = [1.0 + 0.2 * k for k in range(16)]
-    pl = [5.0 - 0.25 * k for k in range(16)]
+    # ---- N1
     for tag, els, atoms in (("N1_grap_Ni", ["Ni"], ni_frame(611)), ("N1_grap_NiMo", ["Mo", "Ni"], None)):
         if atoms is None:
             base = ni_frame(611)
             atoms = Atoms(symbols=["Mo" if k % 5 == 0 else "Ni" for k in range(len(base))],
                           positions=base.positions, cell=np.asarray(base.get_cell()), pbc=True)
-        gd = GenericRadialAtomicPotential(els, "pexp", {"rl": rl, "pl": pl}, moment_tensors=[0, 1, 2, 3],
-                                          legacy_mode=False)
-        nn = AtomicNN(els, gd, hidden_sizes=[64, 64], activation="softplus", minmax_scale=False,
-                      export_properties=("energy", "forces", "stress"))
-        nn.attach_transformer(UniversalTransformer(els, rcut=6.0))
-        nn.initialize(seed=611)
-        with Engine(nn) as eng:
-            r = eng.evaluate([atoms])[0]
-            ms, slots = timeit(eng, WANT, steps=100)
-            d = gd.as_dict()
-            om = ograp.GrapModel(els, 6.0, algorithm="pexp", parameters=d["parameters"],
-                                 moment_tensors=d["moment_tensors"], legacy_mode=False,
-                                 weights=nn.weights, activation="softplus")
-            t0 = time.perf_counter()
-            o = ograp.evaluate(om, atoms.get_chemical_symbols(), atoms.positions,
-                               np.asarray(atoms.get_cell()), atoms.pbc)
-            out[tag] = {"atoms": len(atoms), "pairs": int(eng.info.n_pairs), "D": nn.ndim(),
-                        "ms_per_eval": ms, "atom_steps_per_s": len(atoms) / ms * 1e3, "kernel_ms": slots,
-                        "parity": {"dE_eV": abs(o["energy"] - r["energy"]),
-                                   "dF_max": float(np.abs(o["forces"] - r["forces"]).max()),
-                                   "dW_max": float(np.abs(o["virial"] - r["virial"]).max()),
-                                   "cpu_oracle_s": time.perf_counter() - t0}}
+        out.update(bench_grap_pexp(tag, els, atoms))
     print(json.dumps(out, indent=1))
 
 

@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "ta_set_electron_temperatures", "ta_get_td_results", "ta_td_loss_gradient",
     "ta_set_triangles", "ta_backward_variant", "ta_count_owned_triangles", "ta_triangle_owner",
     "ta_filter_param_count", "ta_update_filter_weights", "ta_grap_loss_gradient",
+    "ta_set_filter_tables", "ta_filter_table_knots",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -228,6 +229,8 @@ def load():
     lib.ta_list_stats.argtypes = [H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.ta_list_sizes.argtypes = [H, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     lib.ta_set_nn_tables.argtypes = [H, C.c_int]
+    lib.ta_set_filter_tables.argtypes = [H, C.c_int, C.c_int32]
+    lib.ta_filter_table_knots.argtypes = [H, C.POINTER(C.c_int32)]
     lib.ta_set_triangles.argtypes = [H, C.c_int]
     lib.ta_backward_variant.argtypes = [H, C.POINTER(C.c_int32)]
     lib.ta_count_owned_triangles.argtypes = [H, C.POINTER(C.c_int64)]

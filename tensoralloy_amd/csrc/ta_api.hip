@@ -70,7 +70,12 @@ void launch_grap_forward(GrapModel *, const DeviceBatch &b, double eps, hipStrea
 void launch_grap_backward(GrapModel *, const DeviceBatch &b, hipStream_t s);
 // training the GRAP filter network (ta_grap.hip)
 int64_t grap_filter_param_count(const GrapModel *g);
-void grap_update_filter_weights(GrapModel *g, const double *flat, int64_t n);
+void grap_update_filter_weights(GrapModel *g, const double *flat, int64_t n, hipStream_t s);
+int grap_filter_table_knots(const GrapModel *g);
+void grap_set_filter_tables(GrapModel *g, bool on, int n_knots, hipStream_t s);
+int grap_filter_table_target(const GrapModel *g, bool on, int n_knots);
+void grap_mark_trained(GrapModel *g);
+void grap_suspend_filter_tables(GrapModel *g, bool suspend);
 std::string grap_filter_train_refusal(const GrapModel *g);
 size_t grap_filter_grad_doubles(const GrapModel *g, const DeviceBatch &b);
 void launch_grap_filter_tangent(GrapModel *g, const DeviceBatch &b, double eps, const double *Dv, const double *Dd,
@@ -955,9 +960,10 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
       used[TA_K_FORCE_GATHER] = true;
     }
   } else if (h->kind == TA_MODEL_GRAP_MLP) {
-    // 32-byte pair records, as on the second-generation angular path; the `nn` filter network
-    // takes r from the full records its geometry pre-pass writes
-    h->db.rec4 = (!ta::grap_uses_filter_net(h->grap) && !getenv("TA_FULL_RECORDS")) ? h->db.rec : nullptr;
+    // 32-byte pair records, as on the second-generation angular path; the `nn` filter network evaluated
+    // exactly takes r from the full records its geometry pre-pass writes (through its table it has no pre-pass)
+    const bool net_exact = ta::grap_uses_filter_net(h->grap) && !ta::grap_filter_table_knots(h->grap);
+    h->db.rec4 = (!net_exact && !getenv("TA_FULL_RECORDS")) ? h->db.rec : nullptr;
     begin(TA_K_GRAP);
     launch_grap_forward(h->grap, db, h->sf.eps, s);  // computes the pair geometry while staging
     end(TA_K_GRAP);
@@ -2030,6 +2036,25 @@ int ta_update_weights(ta_handle h, const double *weights, int64_t n_weights) {
   });
 }
 
+namespace {
+// the evaluation of a GRAP filter network changed (table <-> exact): what either left behind is stale, and
+// the exact evaluation needs its per-pair buffer
+void grap_filter_mode_changed(ta_context *h) {
+  h->descriptors_valid = false;
+  h->jvp_valid = false;
+  if (h->have_batch) ta::grap_ensure(h->grap, h->db);
+}
+// Weight gradients and training differentiate the filter network itself (Hbuf, Jacobians of the exact
+// filters): the handle evaluates it exactly from here on, as an EAM handle does its nn pair functions
+void mark_grap_trained(ta_context *h) {
+  if (h->kind != TA_MODEL_GRAP_MLP || !h->grap || !ta::grap_uses_filter_net(h->grap)) return;
+  const bool was_on = ta::grap_filter_table_knots(h->grap) != 0;
+  if (was_on) HIP_CHECK(hipStreamSynchronize(h->stream));
+  ta::grap_mark_trained(h->grap);
+  if (was_on) grap_filter_mode_changed(h);
+}
+}  // namespace
+
 int ta_energy_gradient(ta_handle h, const double *frame_coeff, double *grad, int64_t n_grad) {
   if (!h || !frame_coeff || !grad) return TA_ERR_INVALID;
   if (h->td)  // frame_coeff = dL/dF_f
@@ -2069,6 +2094,7 @@ int ta_energy_gradient(ta_handle h, const double *frame_coeff, double *grad, int
     for (int e = 0; e < h->n_elements; ++e) total += ta::mlp_param_count(h->mlp[e]);
     if (n_grad != total)
       throw std::invalid_argument("ta_energy_gradient: expected room for " + std::to_string(total) + " values");
+    mark_grap_trained(h);
     // descriptors do not depend on the weights: computed once per resident batch
     if (!h->descriptors_valid) compute_impl(h, TA_WANT_ENERGY, false, nullptr);
     hipStream_t s = h->stream;
@@ -2212,6 +2238,7 @@ int ta_loss_gradient(ta_handle h, const double *frame_coeff, const double *dR, c
     for (int e = 0; e < h->n_elements; ++e) total += ta::mlp_param_count(h->mlp[e]);
     if (n_grad != total)
       throw std::invalid_argument("ta_loss_gradient: expected room for " + std::to_string(total) + " values");
+    mark_grap_trained(h);
     hipStream_t s = h->stream;
     const size_t N = (size_t)h->db.n_atoms, P = (size_t)h->db.n_pairs, F = (size_t)h->db.n_frames;
     const int D = h->sf.ndim;
@@ -2272,6 +2299,7 @@ int ta_td_loss_gradient(ta_handle h, const double *coeff_free_energy, const doub
     if (n_grad != total)
       throw std::invalid_argument("ta_td_loss_gradient: expected room for " + std::to_string(total) + " values");
     if (dG_out && !direction) throw std::invalid_argument("ta_td_loss_gradient: dG_out needs a direction");
+    mark_grap_trained(h);
     hipStream_t s = h->stream;
     const size_t N = (size_t)h->db.n_atoms, P = (size_t)h->db.n_pairs, F = (size_t)h->db.n_frames;
     const int D = h->sf.ndim;
@@ -2326,11 +2354,41 @@ int ta_update_filter_weights(ta_handle h, const double *weights, int64_t n_weigh
     return fail(h, TA_ERR_INVALID, "ta_update_filter_weights: the model has no filter network");
   return guarded(h, [&]() {
     HIP_CHECK(hipStreamSynchronize(h->stream));  // nothing may still read the old network
-    ta::grap_update_filter_weights(h->grap, weights, n_weights);
     // the descriptors, the filter values behind them and the pair Jacobian all belong to the old network
     h->descriptors_valid = false;
     h->jvp_valid = false;
+    try {
+      ta::grap_update_filter_weights(h->grap, weights, n_weights, h->stream);  // rebuilds the table when it is on
+    } catch (...) {
+      grap_filter_mode_changed(h);  // (a table that could not be rebuilt was dropped)
+      throw;
+    }
   });
+}
+
+int ta_set_filter_tables(ta_handle h, int on, int32_t n_knots) {
+  if (!h) return TA_ERR_INVALID;
+  if (n_knots != 0 && (n_knots < 5 || n_knots > (1 << 20) + 1))
+    return fail(h, TA_ERR_INVALID, "ta_set_filter_tables: 5 .. 2^20 + 1 knots, or 0 for the default");
+  if (h->kind != TA_MODEL_GRAP_MLP || !h->grap || !ta::grap_uses_filter_net(h->grap)) return TA_OK;
+  // nothing changes (same knot count already in use, or a trained handle asked for tables): nothing is invalidated
+  if (ta::grap_filter_table_target(h->grap, on != 0, n_knots) == ta::grap_filter_table_knots(h->grap)) return TA_OK;
+  return guarded(h, [&]() {
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    try {
+      ta::grap_set_filter_tables(h->grap, on != 0, n_knots, h->stream);
+    } catch (...) {
+      grap_filter_mode_changed(h);
+      throw;
+    }
+    grap_filter_mode_changed(h);
+  });
+}
+
+int ta_filter_table_knots(ta_handle h, int32_t *n_knots) {
+  if (!h || !n_knots) return TA_ERR_INVALID;
+  *n_knots = (h->kind == TA_MODEL_GRAP_MLP && h->grap) ? ta::grap_filter_table_knots(h->grap) : 0;
+  return TA_OK;
 }
 
 int ta_grap_loss_gradient(ta_handle h, const double *frame_coeff, const double *dR, const double *dh, double *grad,
@@ -2358,6 +2416,7 @@ int ta_grap_loss_gradient(ta_handle h, const double *frame_coeff, const double *
       throw std::invalid_argument("ta_grap_loss_gradient: expected room for " + std::to_string(n_mlp + n_filter) +
                                   " values");
     const bool direction = dR || dh;
+    mark_grap_trained(h);
     // descriptors, filter values (Hbuf) and dE/dG of the current weights and network
     compute_impl(h, TA_WANT_ENERGY, false, nullptr);
     hipStream_t s = h->stream;
@@ -2558,6 +2617,25 @@ int ta_hessian_vectors(ta_handle h, int32_t n_dir, int32_t first, const double *
       hipStream_t s = h->stream;
       const size_t P = (size_t)h->db.n_pairs, nd = (size_t)n_dir;
       const int D = h->sf.ndim;
+      // The pair Jacobians and the second derivatives are those of the exact filter network: a handle with the
+      // filter table on evaluates exactly for the duration of this call (same result as one that never had a
+      // table) and takes the table up again afterwards, with nothing of either evaluation left valid.
+      struct ExactFilters {
+        ta_context *h;
+        bool resume;
+        ~ExactFilters() {
+          if (!resume) return;
+          (void)hipStreamSynchronize(h->stream);
+          ta::grap_suspend_filter_tables(h->grap, false);
+          h->descriptors_valid = false;
+          h->jvp_valid = false;
+        }
+      } exact{h, grap_model && ta::grap_filter_table_knots(h->grap) != 0};
+      if (exact.resume) {
+        HIP_CHECK(hipStreamSynchronize(s));
+        ta::grap_suspend_filter_tables(h->grap, true);
+        grap_filter_mode_changed(h);
+      }
       ensure_pair_jacobians(h);
       compute_impl(h, TA_WANT_ENERGY, false, nullptr);  // dE/dG of the resident positions (the one-hots overwrote it)
       size_t scratch = 0, partial = 0, total = 0;

@@ -63,6 +63,14 @@ struct GrapParams {
   // grap_nn_filter_kernel: Hbuf[p][0 .. Ks) = v_k(r_p), Hbuf[p][Ks .. 2 Ks) = dv_k/dr
   const double *Hbuf;
   int Ks;                      // K rounded up to 16
+  // algorithm `nn` through its table (ta_set_filter_tables), nullptr = the network evaluated exactly: cubic
+  // Hermite pieces {c0, c1, c2, c3} in t = x - x_k of all Ks outputs as a function of the NETWORK'S input
+  // x (GrapNet::modifier), [tab_n knots][Ks][4]: one table for every element, and the 16 lanes that hold
+  // the 16 filters of a pair read 512 contiguous bytes
+  const double *tab;
+  int tab_n, tab_mod;          // knots x_k = k tab_h, k = 0 .. tab_n - 1; the network's input modifier
+  double tab_h, tab_inv_h;
+  double tab_ircov[kMaxElements];  // 1 / rcov of the centre's element (modifiers 1, 2)
 };
 
 // The packed components M_d = ux^nx uy^ny uz^nz come in the reference's order (grap.py:501-511):
@@ -118,19 +126,61 @@ constexpr int kBwdChunk = 64;
 // all packed monomials M[t][d] (every lane of a 16-lane row needs a different component of the
 // same pair: one ds_read instead of a per-lane select chain). Entries n .. round_up(n, 16) are
 // zero-filled so that the MFMA loops need no tail predicates.
-template <int CH, int MC>
-struct PairLds {
+// TAB (the filter network's table): `logr` holds t = x - x_k instead, and two more fields the knot index and
+// dx/dr. They exist only in the table kernels: the others keep their LDS footprint (workgroups per CU).
+template <int CH, bool TAB>
+struct PairTab {};
+template <int CH>
+struct PairTab<CH, true> {
+  double dxdr[CH];
+  int knot[CH];
+};
+template <int CH, int MC, bool TAB = false>
+struct PairLds : PairTab<CH, TAB> {
   double r[CH], logr[CH], inv_r[CH], f[CH], df[CH], ux[CH], uy[CH], uz[CH];
   double M[CH][MC];
 };
 
+// The network's input x(r) of a pair, the knot interval that holds it and t = x - x_k. The index is clamped
+// to the table: pairs of a skin list beyond rcut (fc = 0) extrapolate the last piece, and the zero-filled
+// padding rows read knot 0.
+__device__ __forceinline__ void table_coords(const GrapParams &g, double r, double ircov, int &knot, double &t,
+                                             double &dxdr) {
+  double x = r;
+  dxdr = 1.0;
+  if (g.tab_mod == 1) {
+    x = r * ircov;
+    dxdr = ircov;
+  } else if (g.tab_mod == 2) {
+    x = exp(-r * ircov);
+    dxdr = -x * ircov;
+  }
+  const double s = fmin(fmax(x * g.tab_inv_h, 0.0), (double)(g.tab_n - 2));
+  knot = (int)s;
+  t = fma(-(double)knot, g.tab_h, x);
+}
+
+// v(x) = c0 + t (c1 + t (c2 + t c3)) of filter k in the knot interval `knot`: one 32-byte read, 3 FMAs
+__device__ __forceinline__ double table_value(const GrapParams &g, int knot, int k, double t) {
+  const double4 c = *reinterpret_cast<const double4 *>(g.tab + ((size_t)knot * g.Ks + k) * 4);
+  return fma(t, fma(t, fma(t, c.w, c.z), c.y), c.x);
+}
+
+// ... and dv/dx = c1 + t (2 c2 + 3 c3 t), the derivative of the same cubic: energy and forces stay consistent
+__device__ __forceinline__ void table_value_deriv(const GrapParams &g, int knot, int k, double t, double &v,
+                                                  double &dvdx) {
+  const double4 c = *reinterpret_cast<const double4 *>(g.tab + ((size_t)knot * g.Ks + k) * 4);
+  v = fma(t, fma(t, fma(t, c.w, c.z), c.y), c.x);
+  dvdx = fma(t, fma(3.0 * t, c.w, c.z + c.z), c.y);
+}
+
 // GEOM: the pair geometry D = Rj - Ri + S.h, r^2 = D.D + eps (universal.py:448-474) is computed here
 // (forward pass) and left in the pair record for the backward kernel and the force gather.
 // `cwl`: the component words in LDS.
-template <int CH, int MC, bool GEOM>
+template <int CH, int MC, bool GEOM, bool TAB>
 __device__ __forceinline__ void stage_pairs(const GrapParams &g, const DeviceBatch &b, int first, int n,
-                                            PairLds<CH, MC> &L, const unsigned long long *cwl, int lane,
-                                            int64_t centre = 0, double eps = 0.0) {
+                                            PairLds<CH, MC, TAB> &L, const unsigned long long *cwl, int lane,
+                                            int64_t centre = 0, double eps = 0.0, double ircov = 1.0) {
   const int npad = min(CH, (n + 15) & ~15);
   for (int t = lane; t < npad; t += kWave) {
     double ux = 0.0, uy = 0.0, uz = 0.0, r = 1.0, inv_r = 1.0, f = 0.0, df = 0.0, one = 0.0;
@@ -178,7 +228,16 @@ __device__ __forceinline__ void stage_pairs(const GrapParams &g, const DeviceBat
       one = 1.0;
     }
     L.r[t] = r;
-    L.logr[t] = g.algo == GRAP_PEXP ? log(r) : 0.0;
+    if constexpr (TAB) {
+      int knot = 0;
+      double tt = 0.0, dxdr = 0.0;
+      if (t < n) table_coords(g, r, ircov, knot, tt, dxdr);
+      L.knot[t] = knot;
+      L.logr[t] = tt;
+      L.dxdr[t] = dxdr;
+    } else {
+      L.logr[t] = g.algo == GRAP_PEXP ? log(r) : 0.0;
+    }
     L.inv_r[t] = inv_r;
     L.f[t] = f;
     L.df[t] = df;
@@ -229,11 +288,12 @@ __device__ __forceinline__ void stage_pairs(const GrapParams &g, const DeviceBat
 
 // One wavefront (= workgroup) per atom: P (kept for the backward pass) and the features.
 // MC = size of the monomial table: 20 (moments 0..3) or 56 (moments 4, 5): NT = 2 or 4 column tiles.
-template <int MC>
+// TAB: the `nn` filters from their table (GrapParams::tab) instead of Hbuf.
+template <int MC, bool TAB = false>
 __global__ __launch_bounds__(kWave) void grap_forward_kernel(GrapParams g, DeviceBatch b, double *Pbuf,
                                                             int ndim, double eps) {
   constexpr int NT = (MC + 15) / 16;
-  __shared__ PairLds<kFwdChunk, MC> L;
+  __shared__ PairLds<kFwdChunk, MC, TAB> L;
   __shared__ unsigned long long cwl[MC];
   const int64_t i = blockIdx.x;
   const int lane = threadIdx.x;
@@ -241,6 +301,7 @@ __global__ __launch_bounds__(kWave) void grap_forward_kernel(GrapParams g, Devic
   const int nel = g.nel, K = g.K, nd = g.nd;
   const int sA = b.species[i];
   const int32_t *seg = b.seg_start + (size_t)i * (nel + 1);
+  const double ircov = TAB ? g.tab_ircov[sA] : 1.0;
   for (int d = lane; d < MC; d += kWave) cwl[d] = d < nd ? g.cw[d] : 0ull;
   bool d_ok[NT];
 #pragma unroll
@@ -268,14 +329,16 @@ __global__ __launch_bounds__(kWave) void grap_forward_kernel(GrapParams g, Devic
         const int n = min(kFwdChunk, hi - first);
         __syncthreads();
         if (kt == 0)
-          stage_pairs<kFwdChunk, MC, true>(g, b, first, n, L, cwl, lane, i, eps);
+          stage_pairs<kFwdChunk, MC, true, TAB>(g, b, first, n, L, cwl, lane, i, eps, ircov);
         else
-          stage_pairs<kFwdChunk, MC, false>(g, b, first, n, L, cwl, lane);
+          stage_pairs<kFwdChunk, MC, false, TAB>(g, b, first, n, L, cwl, lane, 0, 0.0, ircov);
         __syncthreads();
         for (int base = 0; base < n; base += 4) {
           const int t = base + q4;  // < round_up(n, 16): staged (zero beyond n)
           double v, dv;
-          if (g.algo == GRAP_NN)  // rows beyond n belong to later pairs (or the padding): f = 0 there
+          if constexpr (TAB)  // k < Ks: the table holds the padded outputs too
+            v = table_value(g, L.knot[t], k, L.logr[t]);
+          else if (g.algo == GRAP_NN)  // rows beyond n belong to later pairs (or the padding): f = 0 there
             v = g.Hbuf[(size_t)(first + t) * (2 * g.Ks) + (k_ok ? k : 0)];
           else
             filter_fn(g.algo, fp0, fp1, fp2, L.r[t], L.logr[t], L.inv_r[t], v, dv);
@@ -329,11 +392,11 @@ __global__ __launch_bounds__(kWave) void grap_forward_kernel(GrapParams g, Devic
 //   A[k][d] = dE/dP[k][d] = 2 P[k][d] sum_m c[k][m] T[d][m]  (+ dE/dG0 for d = 0 in legacy mode)
 // is formed while staging it in LDS. dM_d/du_c = n_c M_{d - e_c}: a second read of the monomial
 // table at the index of the component with one power of u_c less.
-template <int MC>
+template <int MC, bool TAB = false>
 __global__ __launch_bounds__(kWave) void grap_backward_kernel(GrapParams g, DeviceBatch b,
                                                              const double *Pbuf, int ndim) {
   constexpr int NT = (MC + 15) / 16;
-  __shared__ PairLds<kBwdChunk, MC> L;
+  __shared__ PairLds<kBwdChunk, MC, TAB> L;
   __shared__ unsigned long long cwl[MC];
   extern __shared__ double dyn[];  // A[Kp][nd], then FP[4 K]
   const int64_t i = blockIdx.x;
@@ -344,6 +407,7 @@ __global__ __launch_bounds__(kWave) void grap_backward_kernel(GrapParams g, Devi
   double *A = dyn, *FP = dyn + Kp * nd, *wrow = FP + 4 * K;  // wrow: this atom's dE/dG row
   const int sA = b.species[i];
   const int32_t *seg = b.seg_start + (size_t)i * (nel + 1);
+  const double ircov = TAB ? g.tab_ircov[sA] : 1.0;
   // The pair tiles are computed transposed (rows = components, columns = pairs): accumulator
   // register r of tile ct holds component d = 16 ct + q4 + 4 r of this lane's OWN pair j = m16, so
   // the sum over components is 4 NT terms in registers plus one exchange between the four 16-lane
@@ -395,12 +459,18 @@ __global__ __launch_bounds__(kWave) void grap_backward_kernel(GrapParams g, Devi
     for (int first = lo; first < hi; first += kBwdChunk) {
       const int n = min(kBwdChunk, hi - first);
       __syncthreads();
-      stage_pairs<kBwdChunk, MC, false>(g, b, first, n, L, cwl, lane);
+      stage_pairs<kBwdChunk, MC, false, TAB>(g, b, first, n, L, cwl, lane, 0, 0.0, ircov);
       __syncthreads();
       for (int j0 = 0; j0 < n; j0 += 16) {
         // B-operand columns: this lane's pair (zero-filled beyond n: f = df = 0)
         const int ta = j0 + m16;
         const double r = L.r[ta], logr = L.logr[ta], inv_r = L.inv_r[ta], f = L.f[ta], df = L.df[ta];
+        int knot = 0;
+        double dxdr = 0.0;
+        if constexpr (TAB) {
+          knot = L.knot[ta];
+          dxdr = L.dxdr[ta];
+        }
         f64x4 av[NT], bv[NT];
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct) {
@@ -412,7 +482,10 @@ __global__ __launch_bounds__(kWave) void grap_backward_kernel(GrapParams g, Devi
           double H = 0.0, dH = 0.0;
           if (k < K) {
             double v, dv;
-            if (g.algo == GRAP_NN) {
+            if constexpr (TAB) {
+              table_value_deriv(g, knot, k, logr, v, dv);  // (`logr` holds t)
+              dv *= dxdr;
+            } else if (g.algo == GRAP_NN) {
               const double *hp = g.Hbuf + (size_t)(first + ta) * (2 * g.Ks);
               v = hp[k];
               dv = hp[g.Ks + k];
@@ -632,6 +705,77 @@ __global__ __launch_bounds__(kBlock) void grap_nn_filter_kernel(GrapNet net, Dev
       }
     }
   }
+}
+
+// ---- the filter network's table (ta_set_filter_tables) ---------------------------------------------
+// Built once per network (and again by ta_update_filter_weights), not per step: a lane per knot evaluates the
+// network and its derivative in the network's own input x at x_k = k h with plain FMA loops over the padded
+// weight copies, then a lane per (knot, output) forms the cubic Hermite piece of [x_k, x_k+1] in t = x - x_k:
+//     c0 = f_k, c1 = f'_k, c2 = (3 s - 2 f'_k - f'_k+1) / h, c3 = (f'_k + f'_k+1 - 2 s) / h^2, s = (f_k+1 - f_k) / h.
+// The last knot closes the last interval; its own row (never indexed: table_coords clamps to tab_n - 2)
+// continues the function linearly.
+__global__ __launch_bounds__(kWave) void grap_table_knots_kernel(GrapNet net, int n_knots, double h, int Ks,
+                                                                 double *val, double *der) {
+  const int kn = blockIdx.x * kWave + threadIdx.x;
+  if (kn >= n_knots) return;
+  const double x = (double)kn * h;
+  // (private arrays = scratch memory: deliberate in this build-time kernel, not a pattern for a hot one)
+  double a[2][kNetMaxWidth], a1[2][kNetMaxWidth];
+  int cur = 0;
+  for (int c = 0; c < net.np[0]; ++c) {  // layer 0: one input
+    const double wk = net.w[0][c];
+    double hv, dh;
+    activation_fn(net.act, fma(wk, x, net.b[0][c]), hv, dh);
+    a[0][c] = hv;
+    a1[0][c] = dh * wk;
+  }
+  for (int l = 1; l < net.L; ++l) {
+    const int kp = net.np[l - 1], np = net.np[l], nxt = cur ^ 1;
+    const bool last = l == net.L - 1;
+    for (int n = 0; n < np; ++n) {
+      double z = net.b[l][n], z1 = 0.0;
+      for (int k = 0; k < kp; ++k) {
+        const double w = net.w[l][(size_t)k * np + n];
+        z = fma(w, a[cur][k], z);
+        z1 = fma(w, a1[cur][k], z1);
+      }
+      double o = z, o1 = z1;
+      if (!last) {
+        double dh;
+        activation_fn(net.act, z, o, dh);
+        o1 = dh * z1;
+        if (net.res[l]) {  // x = act(w x + b) + x
+          o += a[cur][n];
+          o1 += a1[cur][n];
+        }
+      }
+      a[nxt][n] = o;
+      a1[nxt][n] = o1;
+    }
+    cur = nxt;
+  }
+  for (int k = 0; k < Ks; ++k) {  // Ks = np of the output layer: its padding columns are zero
+    val[(size_t)kn * Ks + k] = a[cur][k];
+    der[(size_t)kn * Ks + k] = a1[cur][k];
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void grap_table_coef_kernel(int n_knots, int Ks, double h, const double *val,
+                                                                const double *der, double *tab) {
+  const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (idx >= (int64_t)n_knots * Ks) return;
+  const int kn = (int)(idx / Ks);
+  const double f0 = val[idx], d0 = der[idx];
+  double c2 = 0.0, c3 = 0.0;
+  if (kn + 1 < n_knots) {
+    const double f1 = val[idx + Ks], d1 = der[idx + Ks];
+    const double inv_h = 1.0 / h, s = (f1 - f0) * inv_h;
+    c2 = (3.0 * s - 2.0 * d0 - d1) * inv_h;
+    c3 = (d0 + d1 - 2.0 * s) * inv_h * inv_h;
+  }
+  double2 *dst = reinterpret_cast<double2 *>(tab + 4 * idx);
+  dst[0] = make_double2(f0, d0);
+  dst[1] = make_double2(c2, c3);
 }
 
 // ---- analytic Hessian-vector products (round 3) ------------------------------------------------------
@@ -1250,6 +1394,10 @@ struct GrapModel {
   size_t cap_pairs = 0;
   size_t net_lds = 0;
   int sizes[kNetMaxLayers + 1] = {0};    // real layer widths 1, h1, ..., K
+  // the network through its table (ta_set_filter_tables): p.tab is what the kernels test
+  double *tab = nullptr;
+  int tab_knots = 0;                     // knots of `tab`; 0: the network is evaluated exactly
+  bool trained = false;                  // a weight gradient was formed: exact from here on
 };
 
 void grap_destroy(GrapModel *g);
@@ -1493,13 +1641,15 @@ void grap_destroy(GrapModel *g) {
   if (g->cw_dev) (void)hipFree(g->cw_dev);
   if (g->Pbuf) (void)hipFree(g->Pbuf);
   if (g->Hbuf) (void)hipFree(g->Hbuf);
+  if (g->tab) (void)hipFree(g->tab);
   for (double *d : g->owned) (void)hipFree(d);
   delete g;
 }
 
 void grap_ensure(GrapModel *g, const DeviceBatch &b) {
   const size_t n = (size_t)b.n_atoms;
-  if (g->p.algo == GRAP_NN && (size_t)b.n_pairs > g->cap_pairs) {
+  // (with the filter table on nothing writes or reads the per-pair filter values)
+  if (g->p.algo == GRAP_NN && !g->p.tab && (size_t)b.n_pairs > g->cap_pairs) {
     if (g->Hbuf) (void)hipFree(g->Hbuf);
     g->Hbuf = nullptr;
     g->cap_pairs = 0;
@@ -1522,7 +1672,7 @@ void grap_ensure(GrapModel *g, const DeviceBatch &b) {
 
 void launch_grap_forward(GrapModel *g, const DeviceBatch &b, double eps, hipStream_t s) {
   if (b.n_atoms == 0) return;
-  if (g->p.algo == GRAP_NN && b.n_pairs > 0) {
+  if (g->p.algo == GRAP_NN && !g->p.tab && b.n_pairs > 0) {
     // geometry first (the filter network needs r), then the K filters of every pair
     SFParams sf;
     std::memset(&sf, 0, sizeof(sf));
@@ -1545,12 +1695,17 @@ void launch_grap_forward(GrapModel *g, const DeviceBatch &b, double eps, hipStre
     }
 #undef TA_GRAP_NET
   }
-  if (g->p.nd <= kSmallComp)
-    hipLaunchKernelGGL(grap_forward_kernel<kSmallComp>, dim3((unsigned)b.n_atoms), dim3(kWave), 0, s, g->p, b,
-                       g->Pbuf, g->ndim, eps);
-  else
-    hipLaunchKernelGGL(grap_forward_kernel<kMaxComp>, dim3((unsigned)b.n_atoms), dim3(kWave), 0, s, g->p, b,
-                       g->Pbuf, g->ndim, eps);
+#define TA_GRAP_FWD(MC, TAB)                                                                                   \
+  hipLaunchKernelGGL((grap_forward_kernel<MC, TAB>), dim3((unsigned)b.n_atoms), dim3(kWave), 0, s, g->p, b, g->Pbuf, \
+                     g->ndim, eps)
+  if (g->p.tab) {
+    if (g->p.nd <= kSmallComp) TA_GRAP_FWD(kSmallComp, true);
+    else TA_GRAP_FWD(kMaxComp, true);
+  } else {
+    if (g->p.nd <= kSmallComp) TA_GRAP_FWD(kSmallComp, false);
+    else TA_GRAP_FWD(kMaxComp, false);
+  }
+#undef TA_GRAP_FWD
 }
 
 bool grap_hvp_supported(const GrapModel *g) { return g->p.algo != GRAP_NN || g->p.K <= kMaxFilters; }
@@ -1568,13 +1723,104 @@ void launch_grap_backward(GrapModel *g, const DeviceBatch &b, hipStream_t s) {
   if (b.n_atoms == 0) return;
   const int Kp = (g->p.K + 3) & ~3;
   const size_t lds = ((size_t)Kp * g->p.nd + 4 * (size_t)g->p.K + (size_t)g->ndim) * sizeof(double);
-  if (g->p.nd <= kSmallComp)
-    hipLaunchKernelGGL(grap_backward_kernel<kSmallComp>, dim3((unsigned)b.n_atoms), dim3(kWave), lds, s, g->p, b,
-                       g->Pbuf, g->ndim);
-  else
-    hipLaunchKernelGGL(grap_backward_kernel<kMaxComp>, dim3((unsigned)b.n_atoms), dim3(kWave), lds, s, g->p, b,
-                       g->Pbuf, g->ndim);
+#define TA_GRAP_BWD(MC, TAB)                                                                                      \
+  hipLaunchKernelGGL((grap_backward_kernel<MC, TAB>), dim3((unsigned)b.n_atoms), dim3(kWave), lds, s, g->p, b, g->Pbuf, \
+                     g->ndim)
+  if (g->p.tab) {
+    if (g->p.nd <= kSmallComp) TA_GRAP_BWD(kSmallComp, true);
+    else TA_GRAP_BWD(kMaxComp, true);
+  } else {
+    if (g->p.nd <= kSmallComp) TA_GRAP_BWD(kSmallComp, false);
+    else TA_GRAP_BWD(kMaxComp, false);
+  }
+#undef TA_GRAP_BWD
 }
+
+// ---- the filter network's table -----------------------------------------------------------------------
+// 4097 knots: the whole-model deviation from the exact network is at its floor there (below 1e-13 eV, 1e-10
+// eV/A); past it the rounding of (f_k+1 - f_k) / h in c2, c3 grows again, and at Ks = 16 the table is 2 MiB,
+// inside one XCD's 4 MiB L2.
+constexpr int kFilterTableKnots = 4097;
+
+namespace {
+// (re)build g->tab from the current weights at g->tab_knots knots; the caller synchronised the stream
+void build_filter_table(GrapModel *g, hipStream_t s) {
+  const int n = g->tab_knots, Ks = g->p.Ks;
+  const GrapNet &net = g->net;
+  double xmax = g->p.rcut;  // range of the network's input over r in [0, rcut]
+  if (net.modifier == 1) {
+    double big = 0.0;
+    for (int e = 0; e < g->p.nel; ++e) big = std::max(big, net.inv_rcov[e]);
+    xmax = g->p.rcut * big;
+  } else if (net.modifier == 2) {
+    xmax = 1.0;
+  }
+  const double h = xmax / (double)(n - 1);
+  double *knots = nullptr;
+  const size_t cells = (size_t)n * Ks;
+  if (hipMalloc((void **)&knots, 2 * cells * sizeof(double)) != hipSuccess) throw std::bad_alloc();
+  hipLaunchKernelGGL(grap_table_knots_kernel, dim3((unsigned)((n + kWave - 1) / kWave)), dim3(kWave), 0, s, net, n, h,
+                     Ks, knots, knots + cells);
+  hipLaunchKernelGGL(grap_table_coef_kernel, dim3((unsigned)((cells + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, n, Ks,
+                     h, knots, knots + cells, g->tab);
+  const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+  (void)hipFree(knots);
+  if (!ok) throw std::runtime_error("building the GRAP filter table failed");
+  g->p.tab_n = n;
+  g->p.tab_mod = net.modifier;
+  g->p.tab_h = h;
+  g->p.tab_inv_h = 1.0 / h;
+  for (int e = 0; e < kMaxElements; ++e) g->p.tab_ircov[e] = net.inv_rcov[e];
+}
+
+void drop_filter_table(GrapModel *g) {
+  if (g->tab) (void)hipFree(g->tab);
+  g->tab = nullptr;
+  g->p.tab = nullptr;
+  g->tab_knots = 0;
+}
+}  // namespace
+
+// knots in use; 0: the network is evaluated exactly (also while ta_hessian_vectors has the table suspended)
+int grap_filter_table_knots(const GrapModel *g) { return g->p.tab ? g->tab_knots : 0; }
+
+// knots the handle would use after grap_set_filter_tables(g, on, n_knots); 0 = exact
+int grap_filter_table_target(const GrapModel *g, bool on, int n_knots) {
+  if (g->p.algo != GRAP_NN || !on || g->trained) return 0;
+  return n_knots ? n_knots : kFilterTableKnots;
+}
+
+// Build (n_knots, 0 = the default) or drop the table. The caller synchronised the stream and invalidates what
+// was computed with the other evaluation. A no-op for analytic filters and after a weight gradient.
+void grap_set_filter_tables(GrapModel *g, bool on, int n_knots, hipStream_t s) {
+  if (g->p.algo != GRAP_NN) return;
+  if (!on || g->trained) {
+    drop_filter_table(g);
+    return;
+  }
+  const int n = n_knots ? n_knots : kFilterTableKnots;
+  if (!g->tab || g->tab_knots != n) {
+    drop_filter_table(g);
+    if (hipMalloc((void **)&g->tab, (size_t)n * g->p.Ks * 4 * sizeof(double)) != hipSuccess) throw std::bad_alloc();
+  }
+  g->tab_knots = n;
+  try {
+    build_filter_table(g, s);
+  } catch (...) {
+    drop_filter_table(g);
+    throw;
+  }
+  g->p.tab = g->tab;
+}
+
+// weight gradients differentiate the network itself: exact evaluation from here on (the EAM precedent)
+void grap_mark_trained(GrapModel *g) {
+  g->trained = true;
+  drop_filter_table(g);
+}
+
+// ta_hessian_vectors: the table out of the kernels' sight for the duration of the call
+void grap_suspend_filter_tables(GrapModel *g, bool suspend) { g->p.tab = suspend ? nullptr : g->tab; }
 
 // ---- training the filter network ----------------------------------------------------------------------
 void launch_grad_reduce(const double *partial, int n_blocks, int n_params, double *grad, hipStream_t s);
@@ -1616,7 +1862,7 @@ int64_t grap_filter_param_count(const GrapModel *g) {
 }
 
 // the network's weights from the flat layout into the padded device copies (the caller synchronised)
-void grap_update_filter_weights(GrapModel *g, const double *flat, int64_t n) {
+void grap_update_filter_weights(GrapModel *g, const double *flat, int64_t n, hipStream_t s) {
   if (g->p.algo != GRAP_NN) throw std::invalid_argument("ta_update_filter_weights: the model has no filter network");
   const int64_t want = grap_filter_param_count(g);
   if (n != want)
@@ -1636,6 +1882,14 @@ void grap_update_filter_weights(GrapModel *g, const double *flat, int64_t n) {
         hipMemcpy(const_cast<double *>(g->net.b[l]), bb.data(), bb.size() * sizeof(double), hipMemcpyHostToDevice) !=
             hipSuccess)
       throw std::runtime_error("hipMemcpy of the GRAP filter network failed");
+  }
+  if (g->tab) {  // the table follows the network
+    try {
+      build_filter_table(g, s);
+    } catch (...) {
+      drop_filter_table(g);
+      throw;
+    }
   }
 }
 

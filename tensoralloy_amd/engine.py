@@ -114,6 +114,23 @@ class Engine:
         `set_frames`."""
         self._check(self._lib.ta_set_nn_tables(self._handle, 1 if on else 0))
 
+    def set_filter_tables(self, on: bool = True, knots=None):
+        """The `nn` filter network of a GRAP model through a device-built cubic Hermite table of `knots`
+        knots (None: the library default, `grap.FILTER_TABLE_KNOTS`) instead of evaluated for every pair
+        (`ta_set_filter_tables`). For inference, off by default; the resident batch stays. A weight gradient
+        or a training step on this engine turns it off for good; models without a filter network ignore it."""
+        n = 0 if knots is None else int(knots)
+        if knots is not None and n == 0:
+            raise ValueError("set_filter_tables: knots=None selects the default; 0 is not a knot count")
+        self._check(self._lib.ta_set_filter_tables(self._handle, 1 if on else 0, n))
+
+    @property
+    def filter_table_knots(self) -> int:
+        """Knots of the filter table in use; 0 while the filter network is evaluated exactly."""
+        n = C.c_int32(0)
+        self._check(self._lib.ta_filter_table_knots(self._handle, C.byref(n)))
+        return int(n.value)
+
     def set_skin(self, skin: float):
         """Verlet skin in Angstrom for the lists built from now on (0 = exact list)."""
         self._check(self._lib.ta_set_skin(self._handle, float(skin)))

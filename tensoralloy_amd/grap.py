@@ -20,6 +20,9 @@ from typing import Dict, List, Sequence, Union
 
 import numpy as np
 
+# knots of the `nn` filter network's table (`Engine.set_filter_tables`): the library's default, kFilterTableKnots
+# of csrc/ta_grap.hip. The deviation from the exact network is at its floor here; more knots only add rounding.
+FILTER_TABLE_KNOTS = 4097
 GRAP_ALGORITHMS = {"sf": 0, "morse": 1, "density": 2, "pexp": 3, "nn": 4}
 _ACT_IDS = {"relu": 0, "softplus": 1, "tanh": 2, "squareplus": 3, "leaky_relu": 4, "sigmoid": 5,
             "softsign": 6, "elu": 7}

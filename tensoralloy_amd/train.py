@@ -445,7 +445,8 @@ class Trainer:
     only, not temperature-dependent) also fits the filter network, as the reference does: theta = [MLP
     weights | filter network], one `ta_grap_loss_gradient` call per step, the filter entries outside the
     L2 term (the reference builds that network with l2_weight = 0); `fit()` writes the trained network back
-    to `nn.descriptor.filter_weights`. The default keeps the filters frozen.
+    to `nn.descriptor.filter_weights`. The default keeps the filters frozen. Training turns the filter table
+    (`Engine.set_filter_tables`) off on its engine: losses and gradients are those of the exact network.
     """
 
     def __init__(self, nn, frames, energies, forces=None, stresses=None, device=None,
@@ -538,6 +539,8 @@ class Trainer:
     def loss_and_gradient(self):
         from .atoms import Atoms
         eng = self.engine
+        if eng.filter_table_knots:  # (the first weight gradient would: the loss itself is exact too)
+            eng.set_filter_tables(False)
         # the shortcut holds only while the engine still has THIS trainer's frames resident: any
         # set_frames / update_positions on the (public) engine in between bumps its generation
         if self.analytic and self._resident and eng.batch_generation == self._generation:
