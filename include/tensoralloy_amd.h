@@ -298,6 +298,44 @@ int ta_view_results(ta_handle h, uint32_t want, const double **energy, const dou
 int ta_step_view(ta_handle h, const double *positions, const double *cells, uint32_t want, const double **energy,
                  const double **forces, const double **virial, const double **atomic, int32_t *rebuilt);
 
+/* Device-resident MD loop: n steps of the resident batch in ONE call, with positions, velocities and
+ * forces staying on the device (ta_step crosses the host twice per step). Consistent units, a = F / m:
+ * with lengths in A, energies in eV and masses in amu the time unit is A sqrt(amu / eV) (ASE's units).
+ * One step is velocity Verlet as ASE's VelocityVerlet:
+ *     v' = v + dt/2 F(x)/m;   x <- x + dt v';   v <- v' + dt/2 F(x)/m
+ * Positions stay unwrapped, cells fixed. Before each step a Berendsen thermostat (ASE's
+ * NVTBerendsen.scale_velocities) may scale the velocities of every frame by
+ *     lambda = sqrt(1 + (kT0 / kT - 1) dt / tau) clamped to [0.9, 1.1],  kT = 2 KE / (3 n_atoms of the frame)
+ * (lambda = 1 when KE = 0). The centre-of-mass momentum is NOT removed, neither at ta_md_init nor by the
+ * thermostat: hand in velocities without drift.
+ *   ta_md_init           masses [n_atoms_total] (finite, > 0) and velocities [n_atoms_total][3] (NULL = 0)
+ *                        of the resident batch, caller's atom order. Needs a resident batch. ta_set_frames
+ *                        (and ta_eval) drop the MD state; ta_update_positions / ta_step keep it, so a
+ *                        host-driven step may be mixed in between two runs.
+ *   ta_md_set_thermostat kT0 (energy) and tau (time); kT0 <= 0 switches the thermostat off (the default).
+ *   ta_md_run            n_steps steps of length dt. epot / ekin [n_steps / record_every + 1][n_frames] or
+ *                        NULL: the frame energy the model reports (temperature-dependent models: F) and the
+ *                        kinetic energy, for the state at entry (record 0) and after every record_every-th
+ *                        step; with a thermostat, ekin is the value before that step's scaling.
+ *                        n_steps = 0 evaluates the state at entry and writes that one record. On return
+ *                        the results of the last evaluation are resident as after
+ *                        ta_compute(want | ENERGY | FORCES) (ta_get_results / ta_view_results work), and the
+ *                        list bookkeeping is as if ta_update_positions had driven every step: each step
+ *                        counts as a list reuse or a list build in ta_list_stats, *n_rebuilds (may be
+ *                        NULL) = lists built by this run. The skin / 2 rule of ta_update_positions is tested
+ *                        on the device after every drift, and forces from a list that fails it never enter
+ *                        a kick: the run stops there, rebuilds from the device's positions and goes on.
+ *                        With skin = 0 every step rebuilds (correct, slow: one host round trip per step).
+ *                        A run without rebuilds moves no per-atom array between host and device. A rebuild
+ *                        that fails (non-finite coordinates ...) ends the run with an error that names the
+ *                        step; nothing is launched after it and no batch is resident.
+ *   ta_md_get_state      positions / velocities [n_atoms_total][3] of the resident state; either may be NULL. */
+int ta_md_init(ta_handle h, const double *masses, const double *velocities);
+int ta_md_set_thermostat(ta_handle h, double kT0, double tau);
+int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t record_every, double *epot,
+              double *ekin, int32_t *n_rebuilds);
+int ta_md_get_state(ta_handle h, double *positions, double *velocities);
+
 /* Enqueue all further work of this handle on `stream` (a hipStream_t of the
  * handle's device owned by the caller, e.g. the stream a RCCL collective is
  * ordered against); NULL restores the handle's own stream (to name the legacy

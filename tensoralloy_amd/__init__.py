@@ -16,6 +16,7 @@ from .td import FiniteTemperatureOptions, TemperatureDependentAtomicNN
 from .transformer import UniversalTransformer, VirtualAtomMap
 from .calculator import TensorAlloyCalculator
 from .engine import Engine
+from .md import DeviceMD, maxwell_boltzmann
 
 __all__ = ["Atoms", "AtomicNN", "TemperatureDependentAtomicNN", "FiniteTemperatureOptions", "SymmetryFunction", "GenericRadialAtomicPotential", "UniversalTransformer", "VirtualAtomMap",
-           "TensorAlloyCalculator", "Engine", "load_model", "HAVE_ASE"]
+           "TensorAlloyCalculator", "Engine", "load_model", "HAVE_ASE", "DeviceMD", "maxwell_boltzmann"]

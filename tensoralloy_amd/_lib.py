@@ -21,7 +21,7 @@ LIB_PATH = PKG_DIR / "libtensoralloy_amd.so"
 
 SOURCES = ["ta_api.hip", "ta_kernels.hip", "ta_kernels_v2.hip", "ta_mlp.hip", "ta_eam.hip",
            "ta_nlist.hip", "ta_grap.hip", "ta_train.hip", "ta_hvp.hip", "ta_neighbor.cpp", "ta_td.hip",
-           "ta_td_train.hip"]
+           "ta_td_train.hip", "ta_md.hip"]
 OBJ_DIR = CSRC_DIR / "build"
 
 TA_OK = 0
@@ -52,6 +52,7 @@ EXPORTED_SYMBOLS = [
     "ta_set_triangles", "ta_backward_variant", "ta_count_owned_triangles", "ta_triangle_owner",
     "ta_filter_param_count", "ta_update_filter_weights", "ta_grap_loss_gradient",
     "ta_set_filter_tables", "ta_filter_table_knots",
+    "ta_md_init", "ta_md_set_thermostat", "ta_md_run", "ta_md_get_state",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -245,6 +246,10 @@ def load():
     lib.ta_free.restype = None
     lib.ta_set_electron_temperatures.argtypes = [H, C.c_int32, _dp]
     lib.ta_get_td_results.argtypes = [H, _dp, _dp, _dp, _dp]
+    lib.ta_md_init.argtypes = [H, _dp, _dp]
+    lib.ta_md_set_thermostat.argtypes = [H, C.c_double, C.c_double]
+    lib.ta_md_run.argtypes = [H, C.c_int32, C.c_double, C.c_uint32, C.c_int32, _dp, _dp, _ip]
+    lib.ta_md_get_state.argtypes = [H, _dp, _dp]
     _lib = lib
     return lib
 

@@ -15,6 +15,7 @@
 
 #include "ta_device.h"
 #include "ta_internal.h"
+#include "ta_md.h"
 
 namespace ta {
 size_t mlp_scratch_doubles(const MlpDev &mlp);
@@ -329,6 +330,20 @@ struct ta_context {
   bool mirror_next = false;
   uint32_t mirror_want = 0;
   int64_t n_list_builds = 0, n_list_reuses = 0;
+
+  // device-resident MD loop (ta_md_init / ta_md_run; the integrator launch is in ta_md.hip): masses,
+  // velocities and the positions the resident list was built for (the device twin of ref_pos, as of
+  // list build number `md_ref_builds`); records of the running ta_md_run; the status word and its
+  // page-locked twin; the workgroup layout (`md_chunk` atoms each) that md_blk_start holds
+  bool md_valid = false;
+  DevBuf<double> md_mass, md_vel, md_ref, md_epot, md_ke;
+  DevBuf<int32_t> md_blk_start;
+  DevBuf<unsigned> md_status;
+  PinnedBuf md_status_host;
+  std::vector<int32_t> md_blk_start_host;
+  int md_chunk = 0, md_n_blk = 0;
+  int64_t md_ref_builds = -1;
+  double md_kT0 = 0.0, md_tau = 0.0;
 
   hipEvent_t ev[2 * TA_N_KERNEL_SLOTS + 2] = {nullptr};
   std::string err;
@@ -1144,6 +1159,10 @@ int ta_destroy(ta_handle h) {
   h->hvp_buf.release();
   h->filt_scratch.release();
   h->nl_recs.release();
+  for (auto *b : {&h->md_mass, &h->md_vel, &h->md_ref, &h->md_epot, &h->md_ke}) b->release();
+  h->md_blk_start.release();
+  h->md_status.release();
+  h->md_status_host.release();
   for (auto &e : h->ev)
     if (e) (void)hipEventDestroy(e);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -1479,6 +1498,24 @@ void set_frames_impl(ta_context *h, int32_t n_frames, const ta_frame *frames, ta
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   }
 }
+// the resident frames again with new coordinates (cells: null = unchanged): the rebuild path of
+// ta_update_positions and ta_md_run; throws
+void rebuild_list(ta_context *h, const double *positions, const double *cells) {
+  const size_t F = h->keep_natoms.size();
+  std::vector<ta_frame> frames(F);
+  const std::vector<int32_t> species(h->keep_species), pbc(h->keep_pbc), natoms(h->keep_natoms);
+  const std::vector<double> old_cells(h->ref_cells);
+  size_t a = 0;
+  for (size_t f = 0; f < F; ++f) {
+    frames[f].n_atoms = natoms[f];
+    frames[f].species = species.data() + a;
+    frames[f].positions = positions + 3 * a;
+    frames[f].cell = (cells ? cells : old_cells.data()) + 9 * f;
+    frames[f].pbc = pbc.data() + 3 * f;
+    a += (size_t)natoms[f];
+  }
+  set_frames_impl(h, (int32_t)F, frames.data(), nullptr);
+}
 }  // namespace
 
 extern "C" {
@@ -1486,6 +1523,7 @@ extern "C" {
 int ta_set_frames(ta_handle h, int32_t n_frames, const ta_frame *frames, ta_batch_info *info) {
   if (!h) return TA_ERR_INVALID;
   if (n_frames < 0 || (n_frames > 0 && !frames)) return fail(h, TA_ERR_INVALID, "bad frames argument");
+  h->md_valid = false;  // masses and velocities belong to the batch that leaves
   return guarded(h, [&]() {
     set_frames_impl(h, n_frames, frames, info);
     if (h->td)  // every frame starts at T = 0, the reference's default (universal.py:295)
@@ -1594,19 +1632,7 @@ int ta_update_positions(ta_handle h, const double *positions, const double *cell
       ++h->n_list_reuses;
       return;
     }
-    std::vector<ta_frame> frames(F);
-    const std::vector<int32_t> species(h->keep_species), pbc(h->keep_pbc), natoms(h->keep_natoms);
-    const std::vector<double> old_cells(h->ref_cells);
-    size_t a = 0;
-    for (size_t f = 0; f < F; ++f) {
-      frames[f].n_atoms = natoms[f];
-      frames[f].species = species.data() + a;
-      frames[f].positions = positions + 3 * a;
-      frames[f].cell = (cells ? cells : old_cells.data()) + 9 * f;
-      frames[f].pbc = pbc.data() + 3 * f;
-      a += (size_t)natoms[f];
-    }
-    set_frames_impl(h, (int32_t)F, frames.data(), nullptr);
+    rebuild_list(h, positions, cells);
   });
 }
 
@@ -1727,6 +1753,204 @@ int ta_step_view(ta_handle h, const double *positions, const double *cells, uint
   h->mirror_next = false;
   if (rc != TA_OK) return rc;
   return ta_view_results(h, want, energy, forces, virial, atomic);
+}
+
+namespace {
+// workgroups of the integrator launch: `chunk` consecutive atoms of one frame each, at least one per frame
+void md_plan_blocks(ta_context *h, int chunk) {
+  if (chunk == h->md_chunk && !h->md_blk_start_host.empty()) return;
+  const size_t F = h->keep_natoms.size();
+  std::vector<int32_t> &start = h->md_blk_start_host;
+  start.assign(F + 1, 0);
+  for (size_t f = 0; f < F; ++f)
+    start[f + 1] = start[f] + std::max(1, (h->keep_natoms[f] + chunk - 1) / chunk);
+  h->md_blk_start.ensure(F + 1);
+  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches read the old layout)
+  HIP_CHECK(hipMemcpy(h->md_blk_start.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+  h->md_chunk = chunk;
+  h->md_n_blk = start[F];
+}
+}  // namespace
+
+int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
+  if (!h || !masses) return fail(h, TA_ERR_INVALID, "ta_md_init: null argument");
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_init: no resident batch");
+  const size_t N = h->keep_species.size();
+  for (size_t i = 0; i < N; ++i)
+    if (!(masses[i] > 0.0) || !std::isfinite(masses[i]))
+      return fail(h, TA_ERR_INVALID, "ta_md_init: mass of atom " + std::to_string(i) + " is not a finite number > 0");
+  if (velocities)
+    for (size_t i = 0; i < 3 * N; ++i)
+      if (!std::isfinite(velocities[i])) return fail(h, TA_ERR_INVALID, "ta_md_init: non-finite velocity");
+  return guarded(h, [&]() {
+    h->md_valid = false;
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    h->upload_pending = false;
+    h->md_mass.ensure(N + 1);
+    h->md_vel.ensure(3 * N + 1);
+    h->md_ref.ensure(3 * N + 1);
+    h->md_status.ensure(2);
+    h->md_status_host.ensure(64);
+    if (N) {
+      HIP_CHECK(hipMemcpy(h->md_mass.ptr, masses, N * sizeof(double), hipMemcpyHostToDevice));
+      if (velocities)
+        HIP_CHECK(hipMemcpy(h->md_vel.ptr, velocities, 3 * N * sizeof(double), hipMemcpyHostToDevice));
+      else
+        HIP_CHECK(hipMemset(h->md_vel.ptr, 0, 3 * N * sizeof(double)));
+    }
+    h->md_ref_builds = -1;  // ta_md_run uploads ref_pos
+    h->md_chunk = 0;
+    h->md_blk_start_host.clear();
+    h->md_valid = true;
+  });
+}
+
+int ta_md_set_thermostat(ta_handle h, double kT0, double tau) {
+  if (!h) return TA_ERR_INVALID;
+  if (std::isnan(kT0) || std::isinf(kT0)) return fail(h, TA_ERR_INVALID, "ta_md_set_thermostat: kT0 must be finite");
+  if (kT0 > 0.0 && (!(tau > 0.0) || !std::isfinite(tau)))
+    return fail(h, TA_ERR_INVALID, "ta_md_set_thermostat: tau must be a finite time > 0");
+  h->md_kT0 = kT0 > 0.0 ? kT0 : 0.0;
+  h->md_tau = kT0 > 0.0 ? tau : 0.0;
+  return TA_OK;
+}
+
+int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t record_every, double *epot,
+              double *ekin, int32_t *n_rebuilds) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_run: no resident batch");
+  if (!h->md_valid) return fail(h, TA_ERR_INVALID, "ta_md_run called before ta_md_init (ta_set_frames drops the MD state)");
+  if (n_steps < 0 || record_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_run: n_steps >= 0 and record_every >= 1 are needed");
+  if (!std::isfinite(dt)) return fail(h, TA_ERR_INVALID, "ta_md_run: dt must be finite");
+  if (n_rebuilds) *n_rebuilds = 0;
+  want |= TA_WANT_ENERGY | TA_WANT_FORCES;
+  want &= ~(uint32_t)TA_WANT_REUSE_DESCRIPTORS;
+  return guarded(h, [&]() {
+    const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
+    hipStream_t s = h->stream;
+    const bool thermostat = h->md_kT0 > 0.0;
+    // with a thermostat one workgroup owns a whole frame: the factor needs the frame's kinetic energy
+    int chunk = ta::kMdChunk;
+    if (thermostat)
+      for (size_t f = 0; f < F; ++f) chunk = std::max(chunk, h->keep_natoms[f]);
+    const int threads = thermostat ? 1024 : 256;
+    md_plan_blocks(h, chunk);
+    const size_t n_blk = (size_t)h->md_n_blk, n_rec = (size_t)(n_steps / record_every) + 1;
+    h->md_epot.ensure(n_rec * F + 1);
+    h->md_ke.ensure(n_rec * n_blk + 1);
+    if (h->md_ref_builds != h->n_list_builds) {  // the host built the list that is resident: its positions go up once
+      HIP_CHECK(hipStreamSynchronize(s));
+      if (N) HIP_CHECK(hipMemcpy(h->md_ref.ptr, h->ref_pos.data(), 3 * N * sizeof(double), hipMemcpyHostToDevice));
+      h->md_ref_builds = h->n_list_builds;
+    }
+    volatile unsigned *status_host = reinterpret_cast<volatile unsigned *>(h->md_status_host.ptr);
+    status_host[0] = 0u;  // (no launch that writes it is in flight: every run ends with a wait)
+    HIP_CHECK(hipMemsetAsync(h->md_status.ptr, 0, 2 * sizeof(unsigned), s));
+
+    ta::MdLaunch a;
+    a.vel = h->md_vel.ptr;
+    a.mass = h->md_mass.ptr;
+    a.ref = h->md_ref.ptr;
+    a.blk_start = h->md_blk_start.ptr;
+    a.epot = h->md_epot.ptr;
+    a.ke_part = h->md_ke.ptr;
+    a.status = h->md_status.ptr;
+    a.status_host = const_cast<unsigned *>(status_host);
+    a.dt = dt;
+    a.kT0 = h->md_kT0;
+    a.dt_over_tau = thermostat ? dt / h->md_tau : 0.0;
+    a.lim2 = h->skin > 0.0 ? 0.25 * h->skin * h->skin : -1.0;  // skin = 0: every step rebuilds
+    a.n_frames = (int)F;
+    a.n_blk = (int)n_blk;
+    a.chunk = chunk;
+    auto integrate = [&](int k, bool drift) {
+      // (a rebuild may have moved the batch's arrays: the pointers are taken at every launch)
+      a.pos = h->db.pos;
+      a.forces = h->db.forces;
+      a.energy = h->db.energy;
+      a.atom_start = h->db.atom_start;
+      a.seq = (unsigned)k;
+      a.kick2 = k > 0 ? 1 : 0;  // the state at entry is a whole step
+      a.drift = drift ? 1 : 0;
+      a.rec = (k % record_every == 0) ? (long long)(k / record_every) : -1;
+      ta::launch_md_integrate(a, threads, s);
+      HIP_CHECK(hipGetLastError());
+    };
+
+    h->jvp_valid = false;
+    compute_impl(h, want, false, nullptr);  // F_0 and the record of the state at entry
+    const int look = h->skin > 0.0 ? ta::kMdLookahead : 1;
+    std::vector<double> x;
+    int k = 0, rebuilds = 0;
+    while (k < n_steps) {
+      // steps k .. k_end - 1 without a look at the device: integrator, exact list of the step, evaluation
+      const int k_end = (int)std::min<int64_t>(n_steps, (int64_t)k + look);
+      for (int q = k; q < k_end; ++q) {
+        integrate(q, true);
+        if (h->filtered) apply_filter(h);
+        compute_impl(h, want, false, nullptr);
+      }
+      wait_stream(s);
+      h->upload_pending = false;
+      const unsigned mark = status_host[0];
+      if (mark == 0u) {
+        h->n_list_reuses += k_end - k;
+        k = k_end;
+        continue;
+      }
+      // the drift of step q left the list stale: the launches behind it did nothing, the evaluations
+      // behind it ran on the stale list and are overwritten now
+      const int q = (int)mark - 1;
+      if (q < k || q >= k_end) throw std::runtime_error("ta_md_run: inconsistent status word");
+      h->n_list_reuses += q - k;
+      x.resize(3 * N);
+      if (N) HIP_CHECK(hipMemcpy(x.data(), h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+      status_host[0] = 0u;
+      HIP_CHECK(hipMemsetAsync(h->md_status.ptr, 0, 2 * sizeof(unsigned), s));
+      try {
+        rebuild_list(h, x.data(), nullptr);
+      } catch (const HipError &e) {
+        throw HipError("ta_md_run: list rebuild after step " + std::to_string(q + 1) + " failed: " + e.what());
+      } catch (const std::exception &e) {
+        throw std::runtime_error("ta_md_run: list rebuild after step " + std::to_string(q + 1) + " failed: " + e.what());
+      }
+      if (N) HIP_CHECK(hipMemcpyAsync(h->md_ref.ptr, h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToDevice, s));
+      h->md_ref_builds = h->n_list_builds;
+      compute_impl(h, want, false, nullptr);
+      ++rebuilds;
+      if (n_rebuilds) *n_rebuilds = rebuilds;
+      k = q + 1;
+    }
+    integrate(n_steps, false);  // the pending half-kick and the last record
+    HIP_CHECK(hipStreamSynchronize(s));
+    h->upload_pending = false;
+    if (n_rebuilds) *n_rebuilds = rebuilds;
+    if (epot && F) HIP_CHECK(hipMemcpy(epot, h->md_epot.ptr, n_rec * F * sizeof(double), hipMemcpyDeviceToHost));
+    if (ekin && F) {
+      std::vector<double> part(n_rec * n_blk);
+      HIP_CHECK(hipMemcpy(part.data(), h->md_ke.ptr, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+      const std::vector<int32_t> &start = h->md_blk_start_host;
+      for (size_t r = 0; r < n_rec; ++r)
+        for (size_t f = 0; f < F; ++f) {
+          double t = 0.0;
+          for (int32_t b = start[f]; b < start[f + 1]; ++b) t += part[r * n_blk + (size_t)b];
+          ekin[r * F + f] = t;
+        }
+    }
+  });
+}
+
+int ta_md_get_state(ta_handle h, double *positions, double *velocities) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_state: no resident batch");
+  if (!h->md_valid) return fail(h, TA_ERR_INVALID, "ta_md_get_state called before ta_md_init");
+  return guarded(h, [&]() {
+    const size_t N = h->keep_species.size();
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    h->upload_pending = false;
+    if (positions && N) HIP_CHECK(hipMemcpy(positions, h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+    if (velocities && N) HIP_CHECK(hipMemcpy(velocities, h->md_vel.ptr, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+  });
 }
 
 int ta_eval(ta_handle h, int32_t n_frames, const ta_frame *frames, uint32_t want, double *energy,

@@ -1,0 +1,126 @@
+// Device-resident MD loop (ta_md_run): the integrator launch that sits between two force evaluations.
+//
+// Velocity Verlet as ASE's VelocityVerlet, Berendsen as NVTBerendsen.scale_velocities (no centre-of-mass
+// fix), in the library's consistent units (a = F / m). One launch does, in this order:
+//   1. the second half-kick of step k             v_k  = v' + dt/2 F_k / m
+//   2. the kinetic energy of v_k, per workgroup, and the frame's potential energy, into the record
+//   3. the Berendsen factor of the frame          v_k <- lambda v_k
+//   4. the first half-kick of step k + 1          v'   = v_k + dt/2 F_k / m
+//   5. the drift                                  x_{k+1} = x_k + dt v'
+//   6. the skin test of ta_update_positions       !(|x_{k+1} - x_ref|^2 <= skin^2 / 4)
+//
+// A frame is cut into workgroups of `chunk` consecutive atoms; every workgroup leaves ONE kinetic-energy
+// partial per record (threads in a fixed order, no floating-point atomics), which the host adds up frame by
+// frame in workgroup order when the run returns. With a thermostat the factor of a frame needs the frame's
+// whole kinetic energy before any velocity is scaled, so the host then makes `chunk` the largest frame
+// (one workgroup per frame, 1024 threads).
+//
+// The launch is predicated on a device word: a drift that finds an atom beyond skin / 2 writes its own
+// sequence number + 1 there (and into a page-locked word the host reads after a stream wait), still
+// writes valid positions, and every LATER launch returns at once. The host may therefore enqueue several
+// steps ahead; the evaluations it enqueued for the stale list are overwritten after the rebuild.
+#include <hip/hip_runtime.h>
+
+#include "ta_device.h"
+#include "ta_math.h"
+#include "ta_md.h"
+
+namespace ta {
+namespace {
+
+// the sum over the workgroup, the same value in every thread: lanes by wave_sum, waves one after another
+__device__ __forceinline__ double md_block_sum(double v, double *s_wave, double *s_total) {
+  v = wave_sum(v);
+  const int wave = threadIdx.x >> 6, n_waves = (blockDim.x + 63) >> 6;
+  if ((threadIdx.x & 63) == 0) s_wave[wave] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int w = 0; w < n_waves; ++w) t += s_wave[w];
+    *s_total = t;
+  }
+  __syncthreads();
+  return *s_total;
+}
+
+__global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
+  __shared__ double s_wave[16];
+  __shared__ double s_total;
+  // (0, or the value this very launch writes, or the mark of an earlier launch: the same branch in every thread)
+  const unsigned mark = *static_cast<volatile unsigned *>(a.status);
+  if (mark != 0u && mark <= a.seq) return;
+  // frame of this workgroup: the last f with blk_start[f] <= blockIdx.x (every frame has at least one)
+  int f = 0;
+  {
+    int lo = 0, hi = a.n_frames - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (a.blk_start[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    f = lo;
+  }
+  const int blk0 = a.blk_start[f];
+  const int64_t f_lo = a.atom_start[f], f_hi = a.atom_start[f + 1];
+  const int64_t lo = f_lo + (int64_t)((int)blockIdx.x - blk0) * a.chunk;
+  const int64_t hi = lo + a.chunk < f_hi ? lo + a.chunk : f_hi;
+  const double hdt = 0.5 * a.dt;
+
+  double ke = 0.0;
+  for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+    const double m = a.mass[i];
+    double vx = a.vel[3 * i], vy = a.vel[3 * i + 1], vz = a.vel[3 * i + 2];
+    if (a.kick2) {
+      vx += hdt * a.forces[3 * i] / m;
+      vy += hdt * a.forces[3 * i + 1] / m;
+      vz += hdt * a.forces[3 * i + 2] / m;
+      a.vel[3 * i] = vx;
+      a.vel[3 * i + 1] = vy;
+      a.vel[3 * i + 2] = vz;
+    }
+    ke += 0.5 * m * (vx * vx + vy * vy + vz * vz);
+  }
+  ke = md_block_sum(ke, s_wave, &s_total);
+  if (threadIdx.x == 0 && a.rec >= 0) {
+    a.ke_part[(size_t)a.rec * a.n_blk + blockIdx.x] = ke;
+    if ((int)blockIdx.x == blk0) a.epot[(size_t)a.rec * a.n_frames + f] = a.energy[f];
+  }
+  if (!a.drift) return;
+
+  double lambda = 1.0;
+  if (a.kT0 > 0.0 && ke > 0.0) {  // (the host made this workgroup the whole frame)
+    const double kT = 2.0 * ke / (3.0 * (double)(f_hi - f_lo));
+    lambda = sqrt(1.0 + (a.kT0 / kT - 1.0) * a.dt_over_tau);
+    lambda = lambda > 1.1 ? 1.1 : (lambda < 0.9 ? 0.9 : lambda);
+  }
+  int stale = 0;
+  for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {  // (each thread meets its own atoms again)
+    const double m = a.mass[i];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      double v = lambda * a.vel[3 * i + c];
+      v += hdt * a.forces[3 * i + c] / m;
+      a.vel[3 * i + c] = v;
+    }
+    const double x = a.pos[3 * i] + a.dt * a.vel[3 * i], y = a.pos[3 * i + 1] + a.dt * a.vel[3 * i + 1],
+                 z = a.pos[3 * i + 2] + a.dt * a.vel[3 * i + 2];
+    a.pos[3 * i] = x;
+    a.pos[3 * i + 1] = y;
+    a.pos[3 * i + 2] = z;
+    const double dx = x - a.ref[3 * i], dy = y - a.ref[3 * i + 1], dz = z - a.ref[3 * i + 2];
+    const double d2 = dx * dx + dy * dy + dz * dz;
+    stale |= !(d2 <= a.lim2) ? 1 : 0;  // (a NaN fails the comparison too and is reported by the rebuild)
+  }
+  if (__syncthreads_or(stale) && threadIdx.x == 0) {
+    *static_cast<volatile unsigned *>(a.status) = a.seq + 1u;
+    *static_cast<volatile unsigned *>(a.status_host) = a.seq + 1u;
+  }
+}
+
+}  // namespace
+
+void launch_md_integrate(const MdLaunch &a, int threads, hipStream_t s) {
+  if (a.n_blk <= 0) return;
+  hipLaunchKernelGGL(md_integrate_kernel, dim3((unsigned)a.n_blk), dim3((unsigned)threads), 0, s, a);
+}
+
+}  // namespace ta

@@ -80,6 +80,8 @@ class Engine:
         self._md_sig = None
         self._volumes = np.array([abs(np.linalg.det(f.cell)) for f in frames])
         self._natoms = np.array([len(f.species) for f in frames], dtype=np.int64)
+        self._numbers = np.concatenate([np.asarray(a.numbers, dtype=np.int64) for a in atoms_list]) \
+            if len(frames) else np.zeros(0, dtype=np.int64)
         if self.finite_temperature:
             # the reference's `etemperature` feature, 0 when the structure has none (universal.py:295)
             self.set_electron_temperatures([float(a.info.get("etemperature", 0.0)) for a in atoms_list])
@@ -238,6 +240,68 @@ class Engine:
         if self.finite_temperature:
             out = self._td_results(out)
         return out
+
+    # -- device-resident MD loop -------------------------------------------------------------
+    def md_init(self, masses=None, velocities=None):
+        """Masses (amu; default: `atoms.atomic_masses` by atomic number) and velocities
+        (A / (A sqrt(amu / eV)), ASE's unit; default 0) of every atom of the resident batch, for
+        `md_run` (`ta_md_init`). `set_frames` drops them; `update_positions` / `step` keep them."""
+        if self.info is None:
+            raise ValueError("md_init: no resident batch (call set_frames first)")
+        N = int(self.info.n_atoms)
+        if masses is None:
+            from .atoms import atomic_masses
+            masses = np.array([atomic_masses[z] for z in self._numbers], dtype=np.float64)
+        m = np.ascontiguousarray(masses, dtype=np.float64).ravel()
+        if len(m) != N:
+            raise ValueError("md_init: one mass for every atom of the resident batch is needed")
+        vptr = C.POINTER(C.c_double)()
+        if velocities is not None:
+            v = np.ascontiguousarray(velocities, dtype=np.float64)
+            if v.size != 3 * N:
+                raise ValueError("md_init: velocities [n_atoms, 3] for every atom of the resident batch are needed")
+            vptr = _lib.as_dp(v)
+        self._check(self._lib.ta_md_init(self._handle, _lib.as_dp(m), vptr))
+
+    def md_set_thermostat(self, kT=0.0, tau=0.0):
+        """Berendsen thermostat of `md_run`: target kT (eV) and time constant (ASE time units);
+        kT <= 0 switches it off (the default)."""
+        self._check(self._lib.ta_md_set_thermostat(self._handle, float(kT), float(tau)))
+
+    def md_run(self, n_steps: int, dt: float, record_every: int = 1, want: int = None) -> dict:
+        """`n_steps` velocity-Verlet steps of length `dt` (ASE time units) of the resident batch on the
+        device (`ta_md_run`): no per-atom traffic while the neighbour list holds. Returns
+        `epot` / `ekin` [n_steps // record_every + 1, n_frames] (entry state first) and `n_rebuilds`.
+        Afterwards `fetch(want | ENERGY | FORCES)` hands out the results of the last step."""
+        if self.info is None:
+            raise ValueError("md_run: no resident batch (call set_frames first)")
+        n_steps, record_every = int(n_steps), int(record_every)
+        if n_steps < 0 or record_every < 1:
+            raise ValueError("md_run: n_steps >= 0 and record_every >= 1 are needed")
+        if want is None:
+            want = _lib.TA_WANT_ENERGY | _lib.TA_WANT_FORCES
+        F = int(self.info.n_frames)
+        n_rec = n_steps // record_every + 1
+        epot, ekin = np.empty((n_rec, F)), np.empty((n_rec, F))
+        rebuilds = C.c_int32(0)
+        rc = self._lib.ta_md_run(self._handle, n_steps, float(dt), int(want), record_every, _lib.as_dp(epot),
+                                 _lib.as_dp(ekin), C.byref(rebuilds))
+        self.batch_generation += 1  # the coordinates changed (also when the run ended early)
+        self._check(rc)
+        if rebuilds.value:
+            n_pairs, n_triples, nnl = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+            self._check(self._lib.ta_list_sizes(self._handle, C.byref(n_pairs), C.byref(n_triples), C.byref(nnl)))
+            self.info.n_pairs, self.info.n_triples, self.info.nnl_max = n_pairs.value, n_triples.value, nnl.value
+        return {"epot": epot, "ekin": ekin, "n_rebuilds": int(rebuilds.value)}
+
+    def md_state(self):
+        """(positions, velocities) [n_atoms, 3] of the resident batch as the device holds them."""
+        if self.info is None:
+            raise ValueError("md_state: no resident batch (call set_frames first)")
+        N = int(self.info.n_atoms)
+        x, v = np.empty((N, 3)), np.empty((N, 3))
+        self._check(self._lib.ta_md_get_state(self._handle, _lib.as_dp(x), _lib.as_dp(v)))
+        return x, v
 
     def list_stats(self):
         """(lists built, lists reused) by this engine."""

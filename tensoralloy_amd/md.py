@@ -1,0 +1,142 @@
+"""
+Molecular dynamics on the device: `DeviceMD` drives `Engine.md_run` (`ta_md_run`), which integrates the
+resident batch for n steps without moving coordinates, velocities or forces through the host.
+
+Units are ASE's: Angstrom, eV, amu, and therefore the time unit Angstrom sqrt(amu / eV); `fs` and `kB`
+are the same numbers as `ase.units.fs` and `ase.units.kB`. The integrator is ASE's `VelocityVerlet`, the
+thermostat ASE's `NVTBerendsen.scale_velocities`; neither removes the centre-of-mass momentum
+(`maxwell_boltzmann(..., zero_momentum=True)` hands out velocities without any).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+fs = 0.09822694788464063      # one femtosecond in Angstrom sqrt(amu / eV)
+kB = 8.617330337217213e-05    # eV / K
+
+__all__ = ["fs", "kB", "maxwell_boltzmann", "DeviceMD"]
+
+
+def maxwell_boltzmann(masses, kT, rng, zero_momentum=True):
+    """Velocities [n, 3] drawn from the Maxwell-Boltzmann distribution at `kT` (eV) for `masses` (amu):
+    every component is normal with variance kT / m. `rng` is a `numpy.random.RandomState` (or anything
+    with `standard_normal`). `zero_momentum` subtracts the centre-of-mass velocity afterwards."""
+    m = np.asarray(masses, dtype=np.float64).ravel()
+    if not np.all(np.isfinite(m)) or np.any(m <= 0.0):
+        raise ValueError("maxwell_boltzmann: masses must be finite and > 0")
+    if not (kT >= 0.0):
+        raise ValueError("maxwell_boltzmann: kT must be >= 0")
+    v = rng.standard_normal((len(m), 3)) * np.sqrt(kT / m)[:, None]
+    if zero_momentum and len(m):
+        v -= (m[:, None] * v).sum(axis=0) / m.sum()
+    return v
+
+
+class DeviceMD:
+    """
+    NVE (velocity Verlet) or Berendsen NVT dynamics of one structure or of a batch of independent
+    structures, integrated on the GPU.
+
+    engine_or_calculator : an `Engine`, or a `TensorAlloyCalculator` whose engine and skin are used (its
+                           cached results are invalidated by every run)
+    atoms_or_list        : one `Atoms` or a list of them (they become the resident batch); velocities are
+                           taken from `atoms.get_velocities()` where the object has them, else 0
+    timestep             : in ASE time units (e.g. `1.0 * fs`)
+    temperature_K, taut  : both given: Berendsen thermostat with that target and time constant
+    """
+
+    def __init__(self, engine_or_calculator, atoms_or_list, timestep, temperature_K=None, taut=None,
+                 velocities=None, masses=None):
+        if not (np.isfinite(timestep) and timestep > 0.0):
+            raise ValueError("DeviceMD: timestep must be a finite time > 0")
+        if (temperature_K is None) != (taut is None):
+            raise ValueError("DeviceMD: the thermostat needs both temperature_K and taut")
+        if temperature_K is not None and not (temperature_K > 0.0 and taut > 0.0):
+            raise ValueError("DeviceMD: temperature_K and taut must be > 0")
+        self._single = not isinstance(atoms_or_list, (list, tuple))
+        self.atoms_list = [atoms_or_list] if self._single else list(atoms_or_list)
+        if not self.atoms_list:
+            raise ValueError("DeviceMD: at least one structure is needed")
+        self._calc = None
+        engine = engine_or_calculator
+        if hasattr(engine_or_calculator, "_engine"):  # a TensorAlloyCalculator
+            self._calc = engine_or_calculator
+            engine = self._calc._engine
+        if not hasattr(engine, "md_run"):
+            raise ValueError("DeviceMD: an Engine or a TensorAlloyCalculator is needed")
+        self.engine = engine
+        self.dt = float(timestep)
+        self.nsteps = 0
+        self._observers = []
+        n = sum(len(a) for a in self.atoms_list)
+        if velocities is None:
+            parts = []
+            for a in self.atoms_list:
+                get = getattr(a, "get_velocities", None)
+                v = get() if get is not None else None
+                parts.append(np.zeros((len(a), 3)) if v is None else np.asarray(v, dtype=np.float64))
+            velocities = np.concatenate(parts) if parts else np.zeros((0, 3))
+        velocities = np.ascontiguousarray(velocities, dtype=np.float64).reshape(-1, 3)
+        if len(velocities) != n:
+            raise ValueError("DeviceMD: velocities for every atom are needed")
+        if masses is not None and len(np.ravel(masses)) != n:
+            raise ValueError("DeviceMD: one mass for every atom is needed")
+        engine.set_frames(self.atoms_list)
+        engine.md_init(masses, velocities)
+        engine.md_set_thermostat(kB * temperature_K if temperature_K is not None else 0.0,
+                                 taut if taut is not None else 0.0)
+        self._natoms = np.array([len(a) for a in self.atoms_list], dtype=np.int64)
+        self.velocities = velocities.copy()
+        self.epot = self.ekin = None   # per-frame records of the last state
+        self.n_rebuilds = 0
+        self._refresh(engine.md_run(0, self.dt))
+
+    def attach(self, fn, interval=1):
+        """Call `fn()` after every `interval` steps of `run` (the run is cut into chunks there)."""
+        if int(interval) < 1:
+            raise ValueError("DeviceMD.attach: interval must be >= 1")
+        self._observers.append((fn, int(interval)))
+
+    def _refresh(self, out):
+        self.epot, self.ekin = out["epot"][-1].copy(), out["ekin"][-1].copy()
+        self.n_rebuilds += out["n_rebuilds"]
+        x, v = self.engine.md_state()
+        self.velocities = v
+        a = 0
+        for atoms, n in zip(self.atoms_list, self._natoms):
+            atoms.positions[:] = x[a:a + n]
+            if hasattr(atoms, "set_velocities"):
+                atoms.set_velocities(v[a:a + n])
+            a += n
+        if self._calc is not None:  # what the calculator cached belongs to other coordinates
+            self._calc.reset()
+            self._calc._forces_local = None
+
+    def run(self, steps):
+        """`steps` more steps; afterwards the `Atoms` objects hold the new positions."""
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError("DeviceMD.run: steps must be >= 0")
+        done = 0
+        while done < steps:
+            chunk = steps - done
+            for _, interval in self._observers:
+                chunk = min(chunk, interval - (self.nsteps % interval))
+            out = self.engine.md_run(chunk, self.dt, record_every=chunk)
+            done += chunk
+            self.nsteps += chunk
+            self._refresh(out)
+            for fn, interval in self._observers:
+                if self.nsteps % interval == 0:
+                    fn()
+
+    def get_potential_energy(self):
+        return float(self.epot[0]) if self._single else self.epot.copy()
+
+    def get_kinetic_energy(self):
+        return float(self.ekin[0]) if self._single else self.ekin.copy()
+
+    def get_temperature(self):
+        """2 KE / (3 N kB) per frame, in K."""
+        t = 2.0 * self.ekin / (3.0 * np.maximum(self._natoms, 1) * kB)
+        return float(t[0]) if self._single else t
