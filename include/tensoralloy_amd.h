@@ -206,7 +206,8 @@ enum {
 
 int ta_device_count(void);
 
-/* Version of this header's ABI (entry points AND struct layouts; bumped whenever either changes) and
+/* Version of this header's ABI (bumped whenever a struct layout or the signature of an existing entry
+ * point changes; entry points that are only added leave it alone, a binding finds them by name) and
  * sizeof(ta_model_desc) as the library was compiled: a binding checks both before the first real
  * call, so that a stale or foreign build of the library is refused instead of misreading a struct.
  * (The reference has no counterpart: its "ABI" is the frozen graph's `Metadata/api`, basic.py:43.) */
@@ -329,9 +330,38 @@ int ta_step_view(ta_handle h, const double *positions, const double *cells, uint
  *                        A run without rebuilds moves no per-atom array between host and device. A rebuild
  *                        that fails (non-finite coordinates ...) ends the run with an error that names the
  *                        step; nothing is launched after it and no batch is resident.
- *   ta_md_get_state      positions / velocities [n_atoms_total][3] of the resident state; either may be NULL. */
+ *   ta_md_get_state      positions / velocities [n_atoms_total][3] of the resident state; either may be NULL.
+ *
+ * Langevin dynamics (canonical sampling) replaces the step by the second-order scheme of ASE's Langevin,
+ * without its centre-of-mass correction. With the friction fr (1 / time), sigma_i = sqrt(2 kT0 fr / m_i) and
+ *     c1 = dt/2 - dt^2 fr/8                             c2 = dt fr/2 - dt^2 fr^2/8
+ *     c3_i = sqrt(dt) sigma_i/2 - dt^1.5 fr sigma_i/8   c5_i = dt^1.5 sigma_i/(2 sqrt 3)   c4_i = fr/2 c5_i
+ * step k draws two standard normals xi, eta per atom and component and does
+ *     rv = c3_i xi - c4_i eta;   rp = c5_i eta
+ *     v += c1 F(x)/m - c2 v + rv;   x += dt v + rp;   v += c1 F(x_new)/m - c2 v + rv
+ * kT0 = 0 with fr > 0 is damped dynamics. The normals are made on the device and are a pure function of
+ * (seed, step, atom, component), so a run split over several ta_md_run calls, another skin or a step
+ * redone after a list rebuild sees the same numbers: Philox4x32-10 with
+ *     key     (seed & 0xffffffff, seed >> 32)
+ *     counter (i, c, step & 0xffffffff, step >> 32)   i: index of the atom in the resident batch (caller's
+ *             order over all frames), c: 0, 1, 2 = x, y, z, step: steps integrated since ta_md_init
+ *             (ta_md_run advances it by n_steps when it succeeds, ta_md_init sets it to 0)
+ * and from the output words w0 .. w3, all in fp64,
+ *     u1 = ((w0 >> 5) 2^26 + (w1 >> 6) + 0.5) 2^-53,  u2 likewise from w2, w3
+ *     xi = sqrt(-2 ln u1) cos(2 pi u2),   eta = sqrt(-2 ln u1) sin(2 pi u2)
+ *   ta_md_set_langevin   kT0 (energy, finite, >= 0), friction (finite, >= 0; 0 switches Langevin off, the
+ *                        default) and the seed. A property of the handle like the Berendsen setting
+ *                        (ta_set_frames keeps it). Only one thermostat at a time: TA_ERR_INVALID while the
+ *                        Berendsen thermostat is on, and ta_md_set_thermostat with kT0 > 0 is refused
+ *                        while Langevin is on. With Langevin, ekin records the kinetic energy after the
+ *                        step, and ta_md_run needs dt >= 0.
+ *   ta_md_noise          xi, eta [n_atoms_total][3]: the normals of absolute step `step` (>= 0) under the
+ *                        handle's seed, from the device function the integrator calls, so that a caller
+ *                        can reproduce a trajectory on the host. Needs ta_md_init. */
 int ta_md_init(ta_handle h, const double *masses, const double *velocities);
 int ta_md_set_thermostat(ta_handle h, double kT0, double tau);
+int ta_md_set_langevin(ta_handle h, double kT0, double friction, uint64_t seed);
+int ta_md_noise(ta_handle h, int64_t step, double *xi, double *eta);
 int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t record_every, double *epot,
               double *ekin, int32_t *n_rebuilds);
 int ta_md_get_state(ta_handle h, double *positions, double *velocities);

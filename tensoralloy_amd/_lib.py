@@ -53,6 +53,7 @@ EXPORTED_SYMBOLS = [
     "ta_filter_param_count", "ta_update_filter_weights", "ta_grap_loss_gradient",
     "ta_set_filter_tables", "ta_filter_table_knots",
     "ta_md_init", "ta_md_set_thermostat", "ta_md_run", "ta_md_get_state",
+    "ta_md_set_langevin", "ta_md_noise",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -250,6 +251,8 @@ def load():
     lib.ta_md_set_thermostat.argtypes = [H, C.c_double, C.c_double]
     lib.ta_md_run.argtypes = [H, C.c_int32, C.c_double, C.c_uint32, C.c_int32, _dp, _dp, _ip]
     lib.ta_md_get_state.argtypes = [H, _dp, _dp]
+    lib.ta_md_set_langevin.argtypes = [H, C.c_double, C.c_double, C.c_uint64]
+    lib.ta_md_noise.argtypes = [H, C.c_int64, _dp, _dp]
     _lib = lib
     return lib
 

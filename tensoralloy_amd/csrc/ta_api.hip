@@ -344,6 +344,12 @@ struct ta_context {
   int md_chunk = 0, md_n_blk = 0;
   int64_t md_ref_builds = -1;
   double md_kT0 = 0.0, md_tau = 0.0;
+  // Langevin (ta_md_set_langevin; off while md_friction == 0): bath, friction, the key of the noise; the
+  // steps integrated since ta_md_init (the noise's step counter) and the scratch of ta_md_noise
+  double md_lv_kT0 = 0.0, md_friction = 0.0;
+  uint64_t md_seed = 0;
+  int64_t md_step = 0;
+  DevBuf<double> md_noise;
 
   hipEvent_t ev[2 * TA_N_KERNEL_SLOTS + 2] = {nullptr};
   std::string err;
@@ -1159,7 +1165,7 @@ int ta_destroy(ta_handle h) {
   h->hvp_buf.release();
   h->filt_scratch.release();
   h->nl_recs.release();
-  for (auto *b : {&h->md_mass, &h->md_vel, &h->md_ref, &h->md_epot, &h->md_ke}) b->release();
+  for (auto *b : {&h->md_mass, &h->md_vel, &h->md_ref, &h->md_epot, &h->md_ke, &h->md_noise}) b->release();
   h->md_blk_start.release();
   h->md_status.release();
   h->md_status_host.release();
@@ -1801,6 +1807,7 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
     h->md_ref_builds = -1;  // ta_md_run uploads ref_pos
     h->md_chunk = 0;
     h->md_blk_start_host.clear();
+    h->md_step = 0;
     h->md_valid = true;
   });
 }
@@ -1810,9 +1817,45 @@ int ta_md_set_thermostat(ta_handle h, double kT0, double tau) {
   if (std::isnan(kT0) || std::isinf(kT0)) return fail(h, TA_ERR_INVALID, "ta_md_set_thermostat: kT0 must be finite");
   if (kT0 > 0.0 && (!(tau > 0.0) || !std::isfinite(tau)))
     return fail(h, TA_ERR_INVALID, "ta_md_set_thermostat: tau must be a finite time > 0");
+  if (kT0 > 0.0 && h->md_friction > 0.0)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_thermostat: the Langevin thermostat is on; switch it off "
+                                   "(ta_md_set_langevin with friction 0) before the Berendsen thermostat goes on");
   h->md_kT0 = kT0 > 0.0 ? kT0 : 0.0;
   h->md_tau = kT0 > 0.0 ? tau : 0.0;
   return TA_OK;
+}
+
+int ta_md_set_langevin(ta_handle h, double kT0, double friction, uint64_t seed) {
+  if (!h) return TA_ERR_INVALID;
+  if (!(friction >= 0.0) || !std::isfinite(friction))
+    return fail(h, TA_ERR_INVALID, "ta_md_set_langevin: friction must be a finite rate >= 0");
+  if (!(kT0 >= 0.0) || !std::isfinite(kT0))
+    return fail(h, TA_ERR_INVALID, "ta_md_set_langevin: kT0 must be finite and >= 0");
+  if (friction > 0.0 && h->md_kT0 > 0.0)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_langevin: the Berendsen thermostat is on; switch it off "
+                                   "(ta_md_set_thermostat with kT0 0) before the Langevin thermostat goes on");
+  h->md_friction = friction;
+  h->md_lv_kT0 = friction > 0.0 ? kT0 : 0.0;
+  h->md_seed = seed;
+  return TA_OK;
+}
+
+int ta_md_noise(ta_handle h, int64_t step, double *xi, double *eta) {
+  if (!h) return TA_ERR_INVALID;
+  if (!xi || !eta) return fail(h, TA_ERR_INVALID, "ta_md_noise: null argument");
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_noise: no resident batch");
+  if (!h->md_valid) return fail(h, TA_ERR_INVALID, "ta_md_noise called before ta_md_init");
+  if (step < 0) return fail(h, TA_ERR_INVALID, "ta_md_noise: step must be >= 0");
+  return guarded(h, [&]() {
+    const size_t N = h->keep_species.size();
+    if (!N) return;
+    h->md_noise.ensure(6 * N);
+    ta::launch_md_noise(h->md_seed, step, (long long)N, h->md_noise.ptr, h->md_noise.ptr + 3 * N, h->stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    HIP_CHECK(hipMemcpy(xi, h->md_noise.ptr, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(eta, h->md_noise.ptr + 3 * N, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+  });
 }
 
 int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t record_every, double *epot,
@@ -1822,14 +1865,15 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
   if (!h->md_valid) return fail(h, TA_ERR_INVALID, "ta_md_run called before ta_md_init (ta_set_frames drops the MD state)");
   if (n_steps < 0 || record_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_run: n_steps >= 0 and record_every >= 1 are needed");
   if (!std::isfinite(dt)) return fail(h, TA_ERR_INVALID, "ta_md_run: dt must be finite");
+  if (h->md_friction > 0.0 && dt < 0.0) return fail(h, TA_ERR_INVALID, "ta_md_run: Langevin dynamics needs dt >= 0");
   if (n_rebuilds) *n_rebuilds = 0;
   want |= TA_WANT_ENERGY | TA_WANT_FORCES;
   want &= ~(uint32_t)TA_WANT_REUSE_DESCRIPTORS;
   return guarded(h, [&]() {
     const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
     hipStream_t s = h->stream;
-    const bool thermostat = h->md_kT0 > 0.0;
-    // with a thermostat one workgroup owns a whole frame: the factor needs the frame's kinetic energy
+    const bool thermostat = h->md_kT0 > 0.0, langevin = h->md_friction > 0.0;  // (never both)
+    // with Berendsen scaling one workgroup owns a whole frame: the factor needs the frame's kinetic energy
     int chunk = ta::kMdChunk;
     if (thermostat)
       for (size_t f = 0; f < F; ++f) chunk = std::max(chunk, h->keep_natoms[f]);
@@ -1857,8 +1901,20 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     a.status = h->md_status.ptr;
     a.status_host = const_cast<unsigned *>(status_host);
     a.dt = dt;
-    a.kT0 = h->md_kT0;
+    a.kT0 = langevin ? h->md_lv_kT0 : h->md_kT0;
     a.dt_over_tau = thermostat ? dt / h->md_tau : 0.0;
+    a.langevin = langevin ? 1 : 0;
+    a.seed = h->md_seed;
+    a.c1 = a.c2 = a.c3 = a.c4 = a.c5 = 0.0;
+    if (langevin) {  // ASE's Langevin.updatevars with sigma_i = sqrt(2 kT0 fr) / sqrt(m_i)
+      const double fr = h->md_friction, sigma = std::sqrt(2.0 * h->md_lv_kT0 * fr);
+      a.c1 = dt / 2.0 - dt * dt * fr / 8.0;
+      a.c2 = dt * fr / 2.0 - dt * dt * fr * fr / 8.0;
+      a.c3 = std::sqrt(dt) * sigma / 2.0 - std::pow(dt, 1.5) * fr * sigma / 8.0;
+      a.c5 = std::pow(dt, 1.5) * sigma / (2.0 * std::sqrt(3.0));
+      a.c4 = fr / 2.0 * a.c5;
+    }
+    const int64_t step0 = h->md_step;  // absolute index of this run's first step
     a.lim2 = h->skin > 0.0 ? 0.25 * h->skin * h->skin : -1.0;  // skin = 0: every step rebuilds
     a.n_frames = (int)F;
     a.n_blk = (int)n_blk;
@@ -1870,6 +1926,7 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
       a.energy = h->db.energy;
       a.atom_start = h->db.atom_start;
       a.seq = (unsigned)k;
+      a.step = (long long)(step0 + k);  // (a step redone after a rebuild keeps its index)
       a.kick2 = k > 0 ? 1 : 0;  // the state at entry is a whole step
       a.drift = drift ? 1 : 0;
       a.rec = (k % record_every == 0) ? (long long)(k / record_every) : -1;
@@ -1924,6 +1981,7 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     integrate(n_steps, false);  // the pending half-kick and the last record
     HIP_CHECK(hipStreamSynchronize(s));
     h->upload_pending = false;
+    h->md_step = step0 + n_steps;
     if (n_rebuilds) *n_rebuilds = rebuilds;
     if (epot && F) HIP_CHECK(hipMemcpy(epot, h->md_epot.ptr, n_rec * F * sizeof(double), hipMemcpyDeviceToHost));
     if (ekin && F) {

@@ -6,7 +6,7 @@
 
 namespace ta {
 
-constexpr int kMdChunk = 1024;      // atoms per workgroup without a thermostat (256 threads, 4 atoms each)
+constexpr int kMdChunk = 1024;      // atoms per workgroup without Berendsen scaling (256 threads, 4 atoms each)
 constexpr int kMdLookahead = 4;     // steps ta_md_run enqueues between two looks at the status word
 
 struct MdLaunch {
@@ -29,8 +29,19 @@ struct MdLaunch {
   int n_frames, n_blk, chunk;
   int kick2;                  // the second half-kick is pending
   int drift;                  // 0: only finish the step (last launch of a run)
+  // Langevin (langevin != 0; kT0 is then the bath's, and no Berendsen factor is applied): the absolute
+  // index of the step this launch begins (steps integrated since ta_md_init before it), the key of the
+  // noise, and the parts of ASE's c1 .. c5 that do not depend on the atom:
+  //   c1 = dt/2 - dt^2 fr/8, c2 = dt fr/2 - dt^2 fr^2/8, c3_i = c3 / sqrt(m_i), likewise c4_i and c5_i
+  int langevin;
+  long long step;
+  unsigned long long seed;
+  double c1, c2, c3, c4, c5;
 };
 
 void launch_md_integrate(const MdLaunch &a, int threads, hipStream_t s);
+
+// xi, eta [n][3] (device): the normals md_integrate draws for absolute step `step`, atoms 0 .. n - 1
+void launch_md_noise(unsigned long long seed, long long step, long long n, double *xi, double *eta, hipStream_t s);
 
 }  // namespace ta

@@ -15,6 +15,17 @@
 // whole kinetic energy before any velocity is scaled, so the host then makes `chunk` the largest frame
 // (one workgroup per frame, 1024 threads).
 //
+// Langevin dynamics (md_integrate_kernel<true>) is ASE's second-order Langevin step without its
+// centre-of-mass correction. Per atom and component, with the normals xi, eta of the step:
+//     rv = c3_i xi - c4_i eta;  rp = c5_i eta
+//     v += c1 F(x)/m - c2 v + rv;   x += dt v + rp;   v += c1 F(x_new)/m - c2 v + rv
+// so the launch finishes step k - 1 with the noise of step k - 1, writes the record, and begins step k with
+// the noise of step k. The normals are a pure function of (seed, absolute step, atom, component):
+// Philox4x32-10 with key (seed lo, seed hi) and counter (atom, component, step lo, step hi), then
+// Box-Muller on two 53-bit uniforms. Nothing per atom is kept between launches, and a step that is redone
+// after a rebuild, enqueued behind a stale list or split over two runs draws the same numbers. There is
+// no per-frame factor, so the chunked layout holds at any frame size.
+//
 // The launch is predicated on a device word: a drift that finds an atom beyond skin / 2 writes its own
 // sequence number + 1 there (and into a page-locked word the host reads after a stream wait), still
 // writes valid positions, and every LATER launch returns at once. The host may therefore enqueue several
@@ -43,6 +54,45 @@ __device__ __forceinline__ double md_block_sum(double v, double *s_wave, double 
   return *s_total;
 }
 
+// Philox4x32-10 (Salmon et al., SC'11): ten rounds of two 32 x 32 -> 64 bit products
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t h0 = __umulhi(M0, c[0]), l0 = M0 * c[0], h1 = __umulhi(M1, c[2]), l1 = M1 * c[2];
+    c[0] = h1 ^ c[1] ^ k0;
+    c[1] = l1;
+    c[2] = h0 ^ c[3] ^ k1;
+    c[3] = l0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+
+// the two standard normals of (seed, step, atom, component): u in (0, 1) from 27 + 26 bits, Box-Muller
+__device__ __forceinline__ void md_normals(unsigned long long seed, long long step, uint32_t atom, uint32_t comp,
+                                           double *xi, double *eta) {
+  uint32_t w[4] = {atom, comp, (uint32_t)((unsigned long long)step & 0xffffffffull),
+                   (uint32_t)((unsigned long long)step >> 32)};
+  philox4x32_10(w, (uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32));
+  const double u1 = ((double)(w[0] >> 5) * 67108864.0 + (double)(w[1] >> 6) + 0.5) * 0x1p-53;
+  const double u2 = ((double)(w[2] >> 5) * 67108864.0 + (double)(w[3] >> 6) + 0.5) * 0x1p-53;
+  const double r = sqrt(-2.0 * log(u1));
+  double sn, cs;
+  sincos(6.283185307179586 * u2, &sn, &cs);
+  *xi = r * cs;
+  *eta = r * sn;
+}
+
+__global__ __launch_bounds__(256) void md_noise_kernel(unsigned long long seed, long long step, long long n3,
+                                                       double *xi, double *eta) {
+  const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n3) return;
+  md_normals(seed, step, (uint32_t)(j / 3), (uint32_t)(j % 3), &xi[j], &eta[j]);
+}
+
+// kLangevin = false: velocity Verlet with the optional Berendsen factor; true: the Langevin step
+template <bool kLangevin>
 __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
   __shared__ double s_wave[16];
   __shared__ double s_total;
@@ -69,7 +119,21 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
   for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
     const double m = a.mass[i];
     double vx = a.vel[3 * i], vy = a.vel[3 * i + 1], vz = a.vel[3 * i + 2];
-    if (a.kick2) {
+    if constexpr (kLangevin) {
+      if (a.kick2) {  // the second update of the step before, with that step's noise
+        const double rsm = 1.0 / sqrt(m);
+        double v[3] = {vx, vy, vz};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          double xi, eta;
+          md_normals(a.seed, a.step - 1, (uint32_t)i, (uint32_t)c, &xi, &eta);
+          const double rv = a.c3 * rsm * xi - a.c4 * rsm * eta;
+          v[c] += a.c1 * a.forces[3 * i + c] / m - a.c2 * v[c] + rv;
+          a.vel[3 * i + c] = v[c];
+        }
+        vx = v[0], vy = v[1], vz = v[2];
+      }
+    } else if (a.kick2) {
       vx += hdt * a.forces[3 * i] / m;
       vy += hdt * a.forces[3 * i + 1] / m;
       vz += hdt * a.forces[3 * i + 2] / m;
@@ -87,7 +151,7 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
   if (!a.drift) return;
 
   double lambda = 1.0;
-  if (a.kT0 > 0.0 && ke > 0.0) {  // (the host made this workgroup the whole frame)
+  if (!kLangevin && a.kT0 > 0.0 && ke > 0.0) {  // (the host made this workgroup the whole frame)
     const double kT = 2.0 * ke / (3.0 * (double)(f_hi - f_lo));
     lambda = sqrt(1.0 + (a.kT0 / kT - 1.0) * a.dt_over_tau);
     lambda = lambda > 1.1 ? 1.1 : (lambda < 0.9 ? 0.9 : lambda);
@@ -95,14 +159,30 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
   int stale = 0;
   for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {  // (each thread meets its own atoms again)
     const double m = a.mass[i];
+    double rp[3] = {0.0, 0.0, 0.0};  // (Langevin: the random part of the drift)
+    if constexpr (kLangevin) {
+      const double rsm = 1.0 / sqrt(m);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      double v = lambda * a.vel[3 * i + c];
-      v += hdt * a.forces[3 * i + c] / m;
-      a.vel[3 * i + c] = v;
+      for (int c = 0; c < 3; ++c) {
+        double xi, eta;
+        md_normals(a.seed, a.step, (uint32_t)i, (uint32_t)c, &xi, &eta);
+        const double rv = a.c3 * rsm * xi - a.c4 * rsm * eta;
+        rp[c] = a.c5 * rsm * eta;
+        double v = a.vel[3 * i + c];
+        v += a.c1 * a.forces[3 * i + c] / m - a.c2 * v + rv;
+        a.vel[3 * i + c] = v;
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        double v = lambda * a.vel[3 * i + c];
+        v += hdt * a.forces[3 * i + c] / m;
+        a.vel[3 * i + c] = v;
+      }
     }
-    const double x = a.pos[3 * i] + a.dt * a.vel[3 * i], y = a.pos[3 * i + 1] + a.dt * a.vel[3 * i + 1],
-                 z = a.pos[3 * i + 2] + a.dt * a.vel[3 * i + 2];
+    double x = a.pos[3 * i] + a.dt * a.vel[3 * i], y = a.pos[3 * i + 1] + a.dt * a.vel[3 * i + 1],
+           z = a.pos[3 * i + 2] + a.dt * a.vel[3 * i + 2];
+    if constexpr (kLangevin) x += rp[0], y += rp[1], z += rp[2];
     a.pos[3 * i] = x;
     a.pos[3 * i + 1] = y;
     a.pos[3 * i + 2] = z;
@@ -120,7 +200,16 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
 
 void launch_md_integrate(const MdLaunch &a, int threads, hipStream_t s) {
   if (a.n_blk <= 0) return;
-  hipLaunchKernelGGL(md_integrate_kernel, dim3((unsigned)a.n_blk), dim3((unsigned)threads), 0, s, a);
+  if (a.langevin)
+    hipLaunchKernelGGL(md_integrate_kernel<true>, dim3((unsigned)a.n_blk), dim3((unsigned)threads), 0, s, a);
+  else
+    hipLaunchKernelGGL(md_integrate_kernel<false>, dim3((unsigned)a.n_blk), dim3((unsigned)threads), 0, s, a);
+}
+
+void launch_md_noise(unsigned long long seed, long long step, long long n, double *xi, double *eta, hipStream_t s) {
+  if (n <= 0) return;
+  const long long n3 = 3 * n;
+  hipLaunchKernelGGL(md_noise_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, s, seed, step, n3, xi, eta);
 }
 
 }  // namespace ta

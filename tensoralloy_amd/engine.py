@@ -268,8 +268,31 @@ class Engine:
         kT <= 0 switches it off (the default)."""
         self._check(self._lib.ta_md_set_thermostat(self._handle, float(kT), float(tau)))
 
+    def md_set_langevin(self, kT=0.0, friction=0.0, seed=0):
+        """Langevin thermostat of `md_run` (`ta_md_set_langevin`): bath kT (eV, >= 0), friction (1 / ASE time
+        unit; 0 switches it off, the default) and the seed (0 .. 2^64 - 1) of the counter-based noise. It and
+        the Berendsen thermostat exclude each other: switch the one that is on off first."""
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("md_set_langevin: the seed must fit an unsigned 64-bit integer")
+        self._check(self._lib.ta_md_set_langevin(self._handle, float(kT), float(friction), seed))
+
+    def md_noise(self, step: int):
+        """(xi, eta) [n_atoms, 3]: the standard normals the Langevin step with absolute index `step` (steps
+        integrated since `md_init`) draws under the seed of `md_set_langevin`, made by the device function
+        the integrator calls (`ta_md_noise`). Needs `md_init`."""
+        if self.info is None:
+            raise ValueError("md_noise: no resident batch (call set_frames first)")
+        step = int(step)
+        if not -2 ** 63 <= step < 2 ** 63:
+            raise ValueError("md_noise: the step must fit a signed 64-bit integer")
+        N = int(self.info.n_atoms)
+        xi, eta = np.empty((N, 3)), np.empty((N, 3))
+        self._check(self._lib.ta_md_noise(self._handle, step, _lib.as_dp(xi), _lib.as_dp(eta)))
+        return xi, eta
+
     def md_run(self, n_steps: int, dt: float, record_every: int = 1, want: int = None) -> dict:
-        """`n_steps` velocity-Verlet steps of length `dt` (ASE time units) of the resident batch on the
+        """`n_steps` velocity-Verlet (or, with `md_set_langevin`, Langevin) steps of length `dt` (ASE time units) of the resident batch on the
         device (`ta_md_run`): no per-atom traffic while the neighbour list holds. Returns
         `epot` / `ekin` [n_steps // record_every + 1, n_frames] (entry state first) and `n_rebuilds`.
         Afterwards `fetch(want | ENERGY | FORCES)` hands out the results of the last step."""

@@ -3,9 +3,16 @@ Molecular dynamics on the device: `DeviceMD` drives `Engine.md_run` (`ta_md_run`
 resident batch for n steps without moving coordinates, velocities or forces through the host.
 
 Units are ASE's: Angstrom, eV, amu, and therefore the time unit Angstrom sqrt(amu / eV); `fs` and `kB`
-are the same numbers as `ase.units.fs` and `ase.units.kB`. The integrator is ASE's `VelocityVerlet`, the
-thermostat ASE's `NVTBerendsen.scale_velocities`; neither removes the centre-of-mass momentum
-(`maxwell_boltzmann(..., zero_momentum=True)` hands out velocities without any).
+are the same numbers as `ase.units.fs` and `ase.units.kB`. The integrator is ASE's `VelocityVerlet`, with
+one of two thermostats: ASE's `NVTBerendsen.scale_velocities` (`taut`), which steers the temperature but
+does not sample the canonical ensemble, or the second-order scheme of ASE's `Langevin` (`friction`), which
+does. None of them removes the centre-of-mass momentum (`maxwell_boltzmann(..., zero_momentum=True)` hands
+out velocities without any; under Langevin the centre of mass then diffuses like one heavy particle).
+
+The Langevin noise is made on the device by a counter-based generator (Philox4x32-10, then Box-Muller): a
+pure function of (seed, step since the start, atom, component). A trajectory therefore depends on the seed
+alone, not on how `run` is cut into calls, on the skin or on list rebuilds, and `Engine.md_noise(step)` hands
+out the very numbers of a step.
 """
 from __future__ import annotations
 
@@ -34,8 +41,8 @@ def maxwell_boltzmann(masses, kT, rng, zero_momentum=True):
 
 class DeviceMD:
     """
-    NVE (velocity Verlet) or Berendsen NVT dynamics of one structure or of a batch of independent
-    structures, integrated on the GPU.
+    NVE (velocity Verlet), Berendsen NVT or Langevin NVT dynamics of one structure or of a batch of
+    independent structures, integrated on the GPU.
 
     engine_or_calculator : an `Engine`, or a `TensorAlloyCalculator` whose engine and skin are used (its
                            cached results are invalidated by every run)
@@ -43,16 +50,32 @@ class DeviceMD:
                            taken from `atoms.get_velocities()` where the object has them, else 0
     timestep             : in ASE time units (e.g. `1.0 * fs`)
     temperature_K, taut  : both given: Berendsen thermostat with that target and time constant
+    temperature_K, friction : both given: Langevin thermostat with that bath temperature (>= 0; 0 is damped
+                           dynamics) and friction (1 / ASE time unit, e.g. `0.01 / fs`)
+    seed                 : of the Langevin noise, 0 .. 2^64 - 1; the same seed gives the same trajectory
     """
 
     def __init__(self, engine_or_calculator, atoms_or_list, timestep, temperature_K=None, taut=None,
-                 velocities=None, masses=None):
+                 velocities=None, masses=None, friction=None, seed=0):
         if not (np.isfinite(timestep) and timestep > 0.0):
             raise ValueError("DeviceMD: timestep must be a finite time > 0")
-        if (temperature_K is None) != (taut is None):
-            raise ValueError("DeviceMD: the thermostat needs both temperature_K and taut")
-        if temperature_K is not None and not (temperature_K > 0.0 and taut > 0.0):
-            raise ValueError("DeviceMD: temperature_K and taut must be > 0")
+        if taut is not None and friction is not None:
+            raise ValueError("DeviceMD: taut (Berendsen) and friction (Langevin) exclude each other")
+        if friction is not None:
+            if temperature_K is None:
+                raise ValueError("DeviceMD: the Langevin thermostat needs temperature_K with friction")
+            if not (np.isfinite(friction) and friction > 0.0):
+                raise ValueError("DeviceMD: friction must be a finite rate > 0")
+            if not (np.isfinite(temperature_K) and temperature_K >= 0.0):
+                raise ValueError("DeviceMD: temperature_K must be finite and >= 0")
+            if not 0 <= int(seed) < 2 ** 64:
+                raise ValueError("DeviceMD: the seed must fit an unsigned 64-bit integer")
+        else:
+            if (temperature_K is None) != (taut is None):
+                raise ValueError("DeviceMD: the thermostat needs both temperature_K and taut (Berendsen) "
+                                 "or temperature_K and friction (Langevin)")
+            if temperature_K is not None and not (temperature_K > 0.0 and taut > 0.0):
+                raise ValueError("DeviceMD: temperature_K and taut must be > 0")
         self._single = not isinstance(atoms_or_list, (list, tuple))
         self.atoms_list = [atoms_or_list] if self._single else list(atoms_or_list)
         if not self.atoms_list:
@@ -83,8 +106,13 @@ class DeviceMD:
             raise ValueError("DeviceMD: one mass for every atom is needed")
         engine.set_frames(self.atoms_list)
         engine.md_init(masses, velocities)
-        engine.md_set_thermostat(kB * temperature_K if temperature_K is not None else 0.0,
-                                 taut if taut is not None else 0.0)
+        if friction is not None:   # (one thermostat at a time: the other goes off first)
+            engine.md_set_thermostat(0.0, 0.0)
+            engine.md_set_langevin(kB * temperature_K, friction, int(seed))
+        else:
+            engine.md_set_langevin(0.0, 0.0, 0)
+            engine.md_set_thermostat(kB * temperature_K if temperature_K is not None else 0.0,
+                                     taut if taut is not None else 0.0)
         self._natoms = np.array([len(a) for a in self.atoms_list], dtype=np.int64)
         self.velocities = velocities.copy()
         self.epot = self.ekin = None   # per-frame records of the last state
