@@ -599,6 +599,25 @@ int ta_backward_variant(ta_handle h, int32_t *variant);
 int ta_count_owned_triangles(ta_handle h, int64_t *n_owned);
 int ta_triangle_owner(int64_t n, const int32_t *abc, int32_t *owner);
 
+/* Which per-atom network kernel the last evaluation launched (read-only; the dispatch does not read it).
+ * The network runs as one of several builds chosen by shape and batch size: the generic 16-row tile, one
+ * wavefront per tile (1-3 hidden layers up to 64 wide, from 1024 tiles), four or eight wavefronts per
+ * tile (widths up to 64 / 128, fewer tiles), each as a one-element and an all-elements launch, or the
+ * temperature-dependent head.
+ *   info[0] family: TA_MLP_NONE (nothing launched yet), TA_MLP_TILE, TA_MLP_TILE_ALL, TA_MLP_WAVE,
+ *           TA_MLP_WAVE_ALL, TA_MLP_QUAD, TA_MLP_QUAD_ALL or TA_MLP_TD
+ *   info[1] threads per workgroup
+ *   info[2] hidden layers of the wave / quad build (template argument LH), else 0
+ *   info[3] wavefronts per tile of the quad build (NT: 4 or 8), else 0
+ *   info[4], info[5] grid size x, y
+ *   info[6] dynamic LDS bytes per workgroup
+ *   info[7] activation derivatives: TA_MLP_DA_REGISTERS (wave, quad), TA_MLP_DA_LDS or TA_MLP_DA_GLOBAL (the
+ *           global scratch slab) */
+enum { TA_MLP_NONE = 0, TA_MLP_TILE = 1, TA_MLP_TILE_ALL = 2, TA_MLP_WAVE = 3, TA_MLP_WAVE_ALL = 4, TA_MLP_QUAD = 5,
+       TA_MLP_QUAD_ALL = 6, TA_MLP_TD = 7 };
+enum { TA_MLP_DA_REGISTERS = 0, TA_MLP_DA_LDS = 1, TA_MLP_DA_GLOBAL = 2 };
+int ta_mlp_launch_info(ta_handle h, int64_t *info /*[8]*/);
+
 /* debugging / parity: host copy of the pair list of the resident batch
  * (centre, neighbour, shift[3]) in the library's order. Arrays sized n_pairs. */
 int ta_get_pairs(ta_handle h, int32_t *i, int32_t *j, int32_t *shift /*[n][3]*/);

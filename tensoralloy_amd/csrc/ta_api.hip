@@ -20,14 +20,14 @@
 namespace ta {
 size_t mlp_scratch_doubles(const MlpDev &mlp);
 void launch_mlp_impl(const MlpDev &mlp, int activation, int ndim, const int32_t *atoms, int n_atoms,
-                     const DeviceBatch &b, double *scratch, hipStream_t s);
+                     const DeviceBatch &b, double *scratch, hipStream_t s, MlpLaunchInfo *info = nullptr);
 size_t mlp_all_scratch_doubles(const MlpDev *mlps_host, int nel, const int32_t *elem_start);
 size_t td_scratch_doubles(const MlpDev *nets, int nel, int K, const int32_t *elem_start);
 void launch_td_all(const MlpDev *nets_dev, const MlpDev *nets_host, int nel, int K, int act_h, int act,
                    int sommerfeld, int ndim, const DeviceBatch &b, const double *T, double *u_atom,
-                   double *s_atom, double *scratch, hipStream_t s);
+                   double *s_atom, double *scratch, hipStream_t s, MlpLaunchInfo *info = nullptr);
 void launch_mlp_all(const MlpDev *mlps_dev, const MlpDev *mlps_host, int nel, int activation, int ndim,
-                    const DeviceBatch &b, double *scratch, hipStream_t s);
+                    const DeviceBatch &b, double *scratch, hipStream_t s, MlpLaunchInfo *info = nullptr);
 // weight gradients (ta_train.hip)
 int mlp_param_count(const MlpDev &mlp);
 size_t mlp_grad_scratch_doubles(const MlpDev &mlp, int n_atoms);
@@ -284,6 +284,7 @@ struct ta_context {
   bool triangles = true;
   bool tri_cells_ok = false;
   int last_bwd_variant = 0;
+  ta::MlpLaunchInfo last_mlp_launch;  // ta_mlp_launch_info
   DevBuf<int32_t> pair_start, seg_start, pair_i, pair_j, pair_shift, pair_rev;
   ta::NlGrid *d_grids = nullptr;  // view into inbuf
   // device neighbour list (ta_nlist.hip)
@@ -875,9 +876,10 @@ void launch_head(ta_context *h, const ta::DeviceBatch &db, hipStream_t s) {
   if (h->td)
     ta::launch_td_all(h->td_dev, h->td_nets, h->n_elements, h->td_K, h->td_act, h->activation,
                       h->td_sommerfeld ? 1 : 0, h->sf.ndim, db, h->td_T.ptr, h->td_u.ptr, h->td_s.ptr,
-                      h->mlp_scratch.ptr, s);
+                      h->mlp_scratch.ptr, s, &h->last_mlp_launch);
   else
-    ta::launch_mlp_all(h->mlp_dev, h->mlp, h->n_elements, h->activation, h->sf.ndim, db, h->mlp_scratch.ptr, s);
+    ta::launch_mlp_all(h->mlp_dev, h->mlp, h->n_elements, h->activation, h->sf.ndim, db, h->mlp_scratch.ptr, s,
+                       &h->last_mlp_launch);
 }
 
 void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
@@ -2168,6 +2170,20 @@ int ta_set_triangles(ta_handle h, int on) {
 int ta_backward_variant(ta_handle h, int32_t *variant) {
   if (!h || !variant) return fail(h, TA_ERR_INVALID, "null argument");
   *variant = h->last_bwd_variant;
+  return TA_OK;
+}
+
+int ta_mlp_launch_info(ta_handle h, int64_t *info) {
+  if (!h || !info) return fail(h, TA_ERR_INVALID, "null argument");
+  const ta::MlpLaunchInfo &m = h->last_mlp_launch;
+  info[0] = m.family;
+  info[1] = m.threads;
+  info[2] = m.lh;
+  info[3] = m.nt;
+  info[4] = m.grid_x;
+  info[5] = m.grid_y;
+  info[6] = m.lds_bytes;
+  info[7] = m.da;
   return TA_OK;
 }
 

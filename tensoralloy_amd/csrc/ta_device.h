@@ -189,6 +189,18 @@ struct MlpDev {
   int max_np = 0, max_kp = 0;
 };
 
+// What the per-atom network launch of an evaluation was (ta_mlp_launch_info): host bookkeeping written
+// where the launch is issued, never read by the dispatch. `family` is a TA_MLP_* and `da` a TA_MLP_DA_* constant of tensoralloy_amd.h.
+struct MlpLaunchInfo {
+  int family = 0;   // TA_MLP_NONE = nothing launched
+  int threads = 0;  // workgroup size
+  int lh = 0;       // hidden layers of the wave / quad build, else 0
+  int nt = 0;       // wavefronts per tile of the quad build, else 0
+  int grid_x = 0, grid_y = 0;
+  long long lds_bytes = 0;  // dynamic LDS of one workgroup
+  int da = 0;               // where act' lived
+};
+
 void launch_pair_geometry(const SFParams &sf, const DeviceBatch &b, hipStream_t s);
 void launch_g4_forward(const SFParams &sf, const AngChunk &ch, int nb, int ng, int nz,
                        const DeviceBatch &b, hipStream_t s);

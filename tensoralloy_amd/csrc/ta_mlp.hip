@@ -684,11 +684,16 @@ void allow_lds(K kernel, size_t bytes) {
 }
 
 void launch_mlp_impl(const MlpDev &mlp, int activation, int ndim, const int32_t *atoms, int n_atoms,
-                     const DeviceBatch &b, double *scratch, hipStream_t s) {
+                     const DeviceBatch &b, double *scratch, hipStream_t s, MlpLaunchInfo *info) {
   if (n_atoms == 0) return;
+  // bookkeeping of the launch issued below (ta_mlp_launch_info)
+  auto note = [&](int family, int threads, int lh, int nt, unsigned gx, unsigned gy, size_t lds, int da) {
+    if (info) *info = MlpLaunchInfo{family, threads, lh, nt, (int)gx, (int)gy, (long long)lds, da};
+  };
   if (const int lh = mlp_quad_shape(mlp, (n_atoms + kMlpRows - 1) / kMlpRows)) {
     const unsigned qblocks = (unsigned)((n_atoms + kMlpRows - 1) / kMlpRows);
     const int nt = mlp_quad_tiles(mlp);
+    note(TA_MLP_QUAD, 64 * nt, lh, nt, qblocks, 1, 0, TA_MLP_DA_REGISTERS);
 #define TA_QUAD(LH, NT)                                                                                       \
   hipLaunchKernelGGL((mlp_quad_kernel<LH, NT>), dim3(qblocks), dim3(64 * NT), 0, s, mlp, activation, ndim, atoms, \
                      n_atoms, b.G, b.dEdG, b.eatom)
@@ -708,6 +713,7 @@ void launch_mlp_impl(const MlpDev &mlp, int activation, int ndim, const int32_t 
     const int ntiles = (n_atoms + kMlpRows - 1) / kMlpRows, nw = kWaveThreads / 64;
     const unsigned wblocks = (unsigned)std::min((ntiles + nw - 1) / nw, 256);
     const size_t lds = wave_lds_doubles(mlp, lh) * sizeof(double);
+    note(TA_MLP_WAVE, kWaveThreads, lh, 0, wblocks, 1, lds, TA_MLP_DA_REGISTERS);
     auto go = [&](auto kernel) {
       allow_lds(kernel, lds);
       hipLaunchKernelGGL(kernel, dim3(wblocks), dim3(kWaveThreads), lds, s, mlp, activation, ndim, atoms, n_atoms,
@@ -722,10 +728,13 @@ void launch_mlp_impl(const MlpDev &mlp, int activation, int ndim, const int32_t 
   size_t lds = 2 * (size_t)kMlpRows * stride * sizeof(double);
   const unsigned blocks = (unsigned)((n_atoms + kMlpRows - 1) / kMlpRows);
   const size_t lds_da = (size_t)mlp.n_layers * kMlpRows * stride * sizeof(double);
+  int da = TA_MLP_DA_GLOBAL;
   if (lds + lds_da <= 64 * 1024 && !getenv("TA_MLP_DA_GLOBAL")) {
     lds += lds_da;
     scratch = nullptr;
+    da = TA_MLP_DA_LDS;
   }
+  note(TA_MLP_TILE, mlp.max_np >= 128 ? 512 : kMlpThreads, 0, 0, blocks, 1, lds, da);
   // one wavefront per 16-column tile of the widest layer, at most 8
   if (mlp.max_np >= 128)
     hipLaunchKernelGGL(mlp_kernel<512>, dim3(blocks), dim3(512), lds, s, mlp, activation, ndim, atoms,
@@ -748,10 +757,14 @@ size_t mlp_all_scratch_doubles(const MlpDev *mlps_host, int nel, const int32_t *
 }
 
 void launch_mlp_all(const MlpDev *mlps_dev, const MlpDev *mlps_host, int nel, int activation, int ndim,
-                    const DeviceBatch &b, double *scratch, hipStream_t s) {
+                    const DeviceBatch &b, double *scratch, hipStream_t s, MlpLaunchInfo *info) {
+  if (info) *info = MlpLaunchInfo{};
+  auto note = [&](int family, int threads, int lh, int nt, unsigned gx, unsigned gy, size_t lds, int da) {
+    if (info) *info = MlpLaunchInfo{family, threads, lh, nt, (int)gx, (int)gy, (long long)lds, da};
+  };
   if (nel == 1) {  // the model description travels as a kernel argument: scalar loads
     launch_mlp_impl(mlps_host[0], activation, ndim, b.elem_atoms, b.elem_start[1] - b.elem_start[0], b,
-                    scratch, s);
+                    scratch, s, info);
     return;
   }
   MlpTiles t;
@@ -775,6 +788,7 @@ void launch_mlp_all(const MlpDev *mlps_dev, const MlpDev *mlps_host, int nel, in
     for (int e = 1; e < nel; ++e)
       if (mlp_quad_shape(mlps_host[e], blocks) != qlh || mlp_quad_tiles(mlps_host[e]) != qnt) qlh = 0;
     if (qlh) {
+      note(TA_MLP_QUAD_ALL, 64 * qnt, qlh, qnt, (unsigned)blocks, 1, 0, TA_MLP_DA_REGISTERS);
 #define TA_QUAD_ALL(LH, NT)                                                                                \
   hipLaunchKernelGGL((mlp_quad_all_kernel<LH, NT>), dim3((unsigned)blocks), dim3(64 * NT), 0, s, mlps_dev, t, \
                      activation, ndim, b.elem_atoms, b.G, b.dEdG, b.eatom)
@@ -803,6 +817,7 @@ void launch_mlp_all(const MlpDev *mlps_dev, const MlpDev *mlps_host, int nel, in
   if (lh) {
     const int nw = kWaveThreads / 64;
     const unsigned wblocks = (unsigned)std::min((max_tiles + nw - 1) / nw, std::max(256 / nel, 1));
+    note(TA_MLP_WAVE_ALL, kWaveThreads, lh, 0, wblocks, (unsigned)nel, wlds, TA_MLP_DA_REGISTERS);
     auto go = [&](auto kernel) {
       allow_lds(kernel, wlds);
       hipLaunchKernelGGL(kernel, dim3(wblocks, (unsigned)nel), dim3(kWaveThreads), wlds, s, mlps_dev, t, activation,
@@ -815,10 +830,13 @@ void launch_mlp_all(const MlpDev *mlps_dev, const MlpDev *mlps_host, int nel, in
   }
   size_t lds = 2 * (size_t)kMlpRows * stride * sizeof(double);
   const size_t lds_da = (size_t)layers * kMlpRows * stride * sizeof(double);
+  int da = TA_MLP_DA_GLOBAL;
   if (lds + lds_da <= 64 * 1024 && !getenv("TA_MLP_DA_GLOBAL")) {  // act' slab in LDS, see mlp_kernel
     lds += lds_da;
     scratch = nullptr;
+    da = TA_MLP_DA_LDS;
   }
+  note(TA_MLP_TILE_ALL, width >= 128 ? 512 : kMlpThreads, 0, 0, (unsigned)blocks, 1, lds, da);
   if (width >= 128)
     hipLaunchKernelGGL(mlp_all_kernel<512>, dim3((unsigned)blocks), dim3(512), lds, s, mlps_dev, t,
                        activation, ndim, b.elem_atoms, b.G, b.dEdG, b.eatom, scratch, stride,

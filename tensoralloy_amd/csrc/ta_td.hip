@@ -23,6 +23,7 @@
 #include <map>
 #include <mutex>
 #include <stdexcept>
+#include <string>
 
 #include "ta_device.h"
 #include "ta_mlp_tile.h"
@@ -301,7 +302,9 @@ TdPlan td_plan(const MlpDev *nets, int nel, int K, int act_h, int act, int somme
   const size_t with_da = base + (size_t)p.sh.da_tile * sizeof(double);
   p.da_in_lds = with_da <= kTdLdsLimit && !getenv("TA_MLP_DA_GLOBAL");
   p.lds_bytes = p.da_in_lds ? with_da : base;
-  if (p.lds_bytes > kTdLdsLimit) throw std::domain_error("finite-temperature network too wide for the LDS tile");
+  if (p.lds_bytes > kTdLdsLimit)
+    throw std::domain_error("finite-temperature network too wide for the LDS tile: " + std::to_string(p.lds_bytes) +
+                            " B of LDS per workgroup, limit " + std::to_string(kTdLdsLimit));
   p.threads = widest >= 128 ? 512 : 256;
   return p;
 }
@@ -320,7 +323,8 @@ size_t td_scratch_doubles(const MlpDev *nets, int nel, int K, const int32_t *ele
 // `nets_dev` is the device copy of `nets_host[0 .. 3 nel)`; T [n_frames], u_atom / s_atom [N]
 void launch_td_all(const MlpDev *nets_dev, const MlpDev *nets_host, int nel, int K, int act_h, int act,
                    int sommerfeld, int ndim, const DeviceBatch &b, const double *T, double *u_atom,
-                   double *s_atom, double *scratch, hipStream_t s) {
+                   double *s_atom, double *scratch, hipStream_t s, MlpLaunchInfo *info) {
+  if (info) *info = MlpLaunchInfo{};
   TdTiles t;
   t.nel = nel;
   int blocks = 0;
@@ -336,6 +340,9 @@ void launch_td_all(const MlpDev *nets_dev, const MlpDev *nets_host, int nel, int
   const TdPlan p = td_plan(nets_host, nel, K, act_h, act, sommerfeld);
   if (p.da_in_lds) scratch = nullptr;
   else if (!scratch) throw std::runtime_error("finite-temperature head: scratch slab missing");
+  if (info)
+    *info = MlpLaunchInfo{TA_MLP_TD, p.threads, 0, 0, blocks, 1, (long long)p.lds_bytes,
+                          p.da_in_lds ? TA_MLP_DA_LDS : TA_MLP_DA_GLOBAL};
   auto go = [&](auto kernel, int threads) {
     td_allow_lds(kernel, p.lds_bytes);
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(threads), p.lds_bytes, s, nets_dev, t, p.sh, ndim,

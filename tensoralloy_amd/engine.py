@@ -485,6 +485,16 @@ class Engine:
         self._check(self._lib.ta_backward_variant(self._handle, C.byref(v)))
         return int(v.value)
 
+    def mlp_launch(self) -> dict:
+        """What the last per-atom network launch of this engine was (`ta_mlp_launch_info`): `family` (tile,
+        tile_all, wave, wave_all, quad, quad_all, td, or none), `threads` per workgroup, `lh` / `nt` (hidden
+        layers and wavefronts per tile of the wave / quad builds, else 0), `grid` (x, y), dynamic `lds_bytes`
+        and `da`, where the activation derivatives lived (registers, lds or global)."""
+        v = (C.c_int64 * 8)()
+        self._check(self._lib.ta_mlp_launch_info(self._handle, v))
+        return {"family": _lib.TA_MLP_FAMILY[int(v[0])], "threads": int(v[1]), "lh": int(v[2]), "nt": int(v[3]),
+                "grid": (int(v[4]), int(v[5])), "lds_bytes": int(v[6]), "da": _lib.TA_MLP_DA[int(v[7])]}
+
     def measure_hbm_copy(self, nbytes: int = 1 << 30, reps: int = 10) -> float:
         """Achievable device-to-device copy rate in GB/s (read + written bytes)."""
         g = C.c_double(0.0)

@@ -1,4 +1,6 @@
 """Shared builders for tests: structures and seeded models."""
+from collections import namedtuple
+
 import numpy as np
 
 from tensoralloy_amd import Atoms, AtomicNN, SymmetryFunction, UniversalTransformer
@@ -271,3 +273,125 @@ def run_child(cases, env, timeout=300, descriptors=True):
     for case in out:
         case["res"] = [{k: np.asarray(v) if isinstance(v, list) else v for k, v in r.items()} for r in case["res"]]
     return out
+
+
+TILE_ROWS = 16                      # kMlpRows
+LDS_64K, LDS_150K = 64 * 1024, 150 * 1024
+WAVE_MIN_TILES, QUAD_MIN_TILES = 1024, 257
+WAVE_STRIDE = 80                    # kWaveStride
+ENV_SWITCHES = ("TA_MLP_TILE_KERNEL", "TA_MLP_WAVE_KERNEL", "TA_MLP_QUAD_KERNEL", "TA_MLP_DA_GLOBAL")
+
+
+# -- the dispatch of the per-atom network (ta_mlp.hip: launch_mlp_all / launch_mlp_impl), restated ------------------
+
+def pad16(n):
+    return (n + 15) // 16 * 16
+
+
+Net = namedtuple("Net", "kp np_ res")   # per layer (output layer included): padded in / out widths, skip flags
+
+
+def net_of(nn, el):
+    """build_net (ta_api.hip): padded layer widths and the skip connections of hidden layers l > 0 of equal width."""
+    sizes = [nn.ndim()] + list(nn.hidden_sizes[el]) + [1]
+    L = len(sizes) - 1
+    res = [bool(nn._use_resnet_dt and 0 < l < L - 1 and sizes[l] == sizes[l + 1]) for l in range(L)]
+    return Net([pad16(s) for s in sizes[:-1]], [pad16(s) for s in sizes[1:]], res)
+
+
+def mlp_stride(net):
+    return max(net.kp + net.np_) + 2
+
+
+def wave_lds_bytes(net):
+    """wave_lds_doubles: both weight orientations and the bias of every hidden layer, and the output column."""
+    lh = len(net.kp) - 1
+    n = 0
+    for l in range(lh):
+        kp, np_ = net.kp[l], net.np_[l]
+        swt = (kp + 16 if kp % 32 == 0 else kp) if l == 0 else WAVE_STRIDE
+        n += kp * WAVE_STRIDE + np_ * swt + np_
+    return 8 * (n + net.kp[lh])
+
+
+def quad_nt(net):
+    """mlp_quad_tiles: wavefronts per tile (4 or 8), 0 = shape not covered."""
+    lh = len(net.kp) - 1
+    if not 1 <= lh <= 3 or max(net.np_[:lh]) > 128 or any(net.res):
+        return 0
+    return 4 if max(net.np_[:lh]) <= 64 else 8
+
+
+def quad_shape(net, n_tiles, env):
+    if env in ("TA_MLP_TILE_KERNEL", "TA_MLP_WAVE_KERNEL"):
+        return 0
+    nt = quad_nt(net)
+    if not nt:
+        return 0
+    if env == "TA_MLP_QUAD_KERNEL":
+        return len(net.kp) - 1
+    if nt == 4 and (n_tiles >= WAVE_MIN_TILES or n_tiles < QUAD_MIN_TILES):
+        return 0
+    if nt == 8 and n_tiles >= 4 * WAVE_MIN_TILES:
+        return 0
+    return len(net.kp) - 1
+
+
+def wave_shape(net, n_tiles, env):
+    lh = len(net.kp) - 1
+    if not 1 <= lh <= 3 or env == "TA_MLP_TILE_KERNEL":
+        return 0
+    if n_tiles < WAVE_MIN_TILES and env != "TA_MLP_WAVE_KERNEL":
+        return 0
+    if max(net.np_[:lh]) > 64 or any(net.res) or wave_lds_bytes(net) > LDS_150K:
+        return 0
+    return lh
+
+
+def element_tiles(nn, frames):
+    syms = [s for a in frames for s in a.get_chemical_symbols()]
+    counts = [syms.count(el) for el in nn.elements]
+    return counts, [-(-n // TILE_ROWS) for n in counts]
+
+
+def _tile_launch(family, stride, layers, width, blocks, env):
+    lds, lds_da = 2 * TILE_ROWS * stride * 8, layers * TILE_ROWS * stride * 8
+    in_lds = lds + lds_da <= LDS_64K and env != "TA_MLP_DA_GLOBAL"
+    return dict(family=family, threads=512 if width >= 128 else 256, lh=0, nt=0, grid=(blocks, 1),
+                lds_bytes=lds + lds_da if in_lds else lds, da="lds" if in_lds else "global")
+
+
+def mirror_launch(nn, frames, env=None):
+    """What `Engine.mlp_launch()` must report after evaluating `frames` with the switch `env` set."""
+    nets = [net_of(nn, el) for el in nn.elements]
+    _, tiles = element_tiles(nn, frames)
+    blocks = sum(tiles)
+    if len(nets) == 1:
+        net = nets[0]
+        lh = quad_shape(net, blocks, env)
+        if lh:
+            nt = quad_nt(net)
+            return dict(family="quad", threads=64 * nt, lh=lh, nt=nt, grid=(blocks, 1), lds_bytes=0, da="registers")
+        lh = wave_shape(net, blocks, env)
+        if lh:
+            return dict(family="wave", threads=512, lh=lh, nt=0, grid=(min(-(-blocks // 8), 256), 1),
+                        lds_bytes=wave_lds_bytes(net), da="registers")
+        return _tile_launch("tile", mlp_stride(net), len(net.kp), max(net.np_), blocks, env)
+    shapes = {(quad_shape(n, blocks, env), quad_nt(n)) for n in nets}
+    if len(shapes) == 1 and next(iter(shapes))[0]:
+        (lh, nt), = shapes
+        return dict(family="quad_all", threads=64 * nt, lh=lh, nt=nt, grid=(blocks, 1), lds_bytes=0, da="registers")
+    shapes = {wave_shape(n, blocks, env) for n in nets}
+    if len(shapes) == 1 and next(iter(shapes)):
+        (lh,) = shapes
+        return dict(family="wave_all", threads=512, lh=lh, nt=0,
+                    grid=(min(-(-max(tiles) // 8), max(256 // len(nets), 1)), len(nets)),
+                    lds_bytes=max(wave_lds_bytes(n) for n in nets), da="registers")
+    return _tile_launch("tile_all", max(mlp_stride(n) for n in nets), max(len(n.kp) for n in nets),
+                        max(max(n.np_) for n in nets), blocks, env)
+
+
+def tile_slab_bytes(nn):
+    """(2 + layers) x 16 x stride doubles: what the generic tile needs to keep act' in LDS."""
+    nets = [net_of(nn, el) for el in nn.elements]
+    return (2 + max(len(n.kp) for n in nets)) * TILE_ROWS * max(mlp_stride(n) for n in nets) * 8

@@ -289,22 +289,29 @@ def test_one_wavefront_mlp_kernel(lib, monkeypatch, hidden, activation, minmax):
     and, to round-off, as the 16-row tile kernel: single element, alloy (one grid row per
     element), ragged last tile, widths that pad to 16 / 32 / 48 / 64, one to three hidden layers."""
     from tensoralloy_amd import Engine
+    from tests.helpers import mirror_launch
     frames = [fcc(rep=(2, 2, 2), jitter=0.05), fcc(rep=(3, 2, 2), a=3.4, seed=2, jitter=0.08)]   # 32 + 48 atoms
     alloy = [_alloy(["Ni", "Ni", "Mo"], rep=(2, 2, 3))]
-    for nn, fr in ((make_nn(["Ni"], 6.0, True, hidden, activation=activation, minmax=minmax), frames),
-                   (make_nn(["Mo", "Ni"], 5.5, True, hidden, activation=activation, minmax=minmax), alloy)):
-        monkeypatch.setenv("TA_MLP_TILE_KERNEL", "1")
+
+    def run(nn, fr, switch, family, **build):
+        """Evaluate under `switch`; the launch the engine reports is the build the switch asks for."""
+        monkeypatch.setenv(switch, "1")
         with Engine(nn) as eng:
-            tile = eng.evaluate(fr)
-        monkeypatch.delenv("TA_MLP_TILE_KERNEL")
-        monkeypatch.setenv("TA_MLP_WAVE_KERNEL", "1")
-        wave = _compare(nn, fr)
-        monkeypatch.delenv("TA_MLP_WAVE_KERNEL")
-        # forced: single-element models of these shapes take the four-wavefront kernel
-        # (`mlp_quad_kernel`; by itself from 257 tiles on), alloys the generic tile kernel
-        monkeypatch.setenv("TA_MLP_QUAD_KERNEL", "1")
-        quad = _compare(nn, fr)
-        monkeypatch.delenv("TA_MLP_QUAD_KERNEL")
+            res = eng.evaluate(fr, descriptors=True)
+            launch = eng.mlp_launch()
+        monkeypatch.delenv(switch)
+        assert launch["family"] == family and {k: launch[k] for k in build} == build, (switch, launch)
+        assert launch == mirror_launch(nn, fr, switch), (switch, launch)
+        return res
+
+    for nn, fr, sfx in ((make_nn(["Ni"], 6.0, True, hidden, activation=activation, minmax=minmax), frames, ""),
+                        (make_nn(["Mo", "Ni"], 5.5, True, hidden, activation=activation, minmax=minmax), alloy,
+                         "_all")):
+        tile = run(nn, fr, "TA_MLP_TILE_KERNEL", "tile" + sfx, threads=256, da="lds")
+        wave = _check_against_oracle(nn, fr, run(nn, fr, "TA_MLP_WAVE_KERNEL", "wave" + sfx, lh=len(hidden)))
+        # forced: models of these shapes take the four-wavefront kernel (`mlp_quad_kernel`, alloys
+        # `mlp_quad_all_kernel`; by itself from 257 tiles on)
+        quad = _check_against_oracle(nn, fr, run(nn, fr, "TA_MLP_QUAD_KERNEL", "quad" + sfx, lh=len(hidden), nt=4))
         for a, b, c in zip(tile, wave, quad):
             for other in (b, c):
                 assert abs(a["energy"] - other["energy"]) < 1e-10

@@ -238,3 +238,116 @@ def test_td_4000_atoms_against_c_oracle_descriptors():
     for key, ref in (("free_energy_atomic", h["F"]), ("atomic", h["U"]), ("eentropy_atomic", h["S"])):
         assert np.abs(r[key] - ref).max() <= 1e-9 * max(1.0, np.abs(ref).max()), key
     assert abs(r["free_energy"] - h["F"].sum()) <= 1e-9 * max(1.0, abs(h["F"].sum()))
+
+
+# -- the act' slab of td_all_kernel in the global scratch slab; ragged and empty tiles; the LDS refusal ------------
+
+TD_LDS_LIMIT = 150 * 1024       # kTdLdsLimit
+
+
+def td_plan_mirror(nn, da_global=False):
+    """td_plan (ta_td.hip) restated: dynamic LDS bytes, where act' lives, threads, doubles of act' per tile."""
+    pad = lambda n: (n + 15) // 16 * 16
+    w = wz = dah = dan = widest = 0
+    for el in nn.elements:
+        sizes = nn.layer_sizes(el)
+        H = [pad(s) for s in sizes["H"]]
+        w, widest = max([w] + H), max([widest] + H[1:])
+        dah = max(dah, sum(16 * (n + 2) for n in H[1:-1]))          # one [16][np + 2] block per hidden layer
+        for net in ("U", "S"):
+            N = [pad(s) for s in sizes[net]]
+            wz, w, widest = max(wz, N[0]), max([w] + N[1:]), max([widest] + N[1:])
+            dan = max(dan, sum(16 * (n + 2) for n in N[1:-1]))      # U and S share one region
+    base = 2 * 16 * (w + 2 + wz + 2) * 8
+    with_da = base + (dah + dan) * 8
+    in_lds = with_da <= TD_LDS_LIMIT and not da_global
+    lds = with_da if in_lds else base
+    return dict(lds_bytes=lds, da="lds" if in_lds else "global", threads=512 if widest >= 128 else 256,
+                refused=lds > TD_LDS_LIMIT, da_tile=dah + dan, base=base, with_da=with_da)
+
+
+# name: (H layers, U / S hidden, algo, resnet, minmax, TA_MLP_DA_GLOBAL, where act' must live, threads)
+SLAB_ROWS = {
+    "lds": ((20, 37), (30,), "default", False, True, False, "lds", 256),
+    "global-forced": ((20, 37), (30,), "default", False, True, True, "global", 256),
+    "global-by-itself": ((256, 256), (64, 64), "Sommerfeld", True, True, False, "global", 512),
+}
+TOO_WIDE = ((320, 320), (64, 64))
+
+
+def slab_model(name):
+    layers, hidden, algo, resnet, minmax = SLAB_ROWS[name][:5]
+    return td_from(_sf(["Mo", "Ni"]), layers, hidden, algo=algo, resnet=resnet, minmax=minmax)
+
+
+def slab_frames():
+    """Mo 36 atoms (3 tiles, the last one of 4), Ni 92 (6 tiles, the last one of 12): Mo absent from the second
+    frame, a single Mo atom in the third; every frame at its own temperature."""
+    frames = [binary(fcc("Ni", rep=(2, 2, 2), seed=21), other="Mo", every=3),
+              fcc("Ni", rep=(2, 2, 2), seed=22, jitter=0.07),
+              binary(fcc("Ni", rep=(2, 2, 1), seed=23), other="Mo", every=16),
+              binary(fcc("Ni", rep=(3, 2, 2), seed=24), other="Mo", every=2)]
+    for a, T in zip(frames, (0.4, 1.1, 0.0, 0.25)):
+        a.info["etemperature"] = T
+    return frames
+
+
+def slab_counts(frames):
+    return [[a.get_chemical_symbols().count(el) for el in ("Mo", "Ni")] for a in frames]
+
+
+_slab_reference = {}
+SLAB_SEEN = {}      # row -> launch the engine reported (collected by test_gpu_mlp_dispatch.py)
+
+
+def slab_launch(name, monkeypatch, frames, want=ALL):
+    """Evaluate `frames` with a slab row's model under its switch: (results, reported launch), which must be the
+    td build and act' placement the row names."""
+    da_global, where, threads = SLAB_ROWS[name][5:]
+    nn = slab_model(name)
+    plan = td_plan_mirror(nn, da_global)
+    assert (plan["da"], plan["threads"], plan["refused"]) == (where, threads, False), plan
+    if da_global:
+        monkeypatch.setenv("TA_MLP_DA_GLOBAL", "1")
+    with Engine(nn, device=0) as eng:
+        res = eng.evaluate(frames, want=want)
+        launch = eng.mlp_launch()
+    monkeypatch.delenv("TA_MLP_DA_GLOBAL", raising=False)
+    tiles = sum(-(-sum(c[e] for c in slab_counts(frames)) // 16) for e in (0, 1))
+    assert launch == dict(family="td", threads=threads, lh=0, nt=0, grid=(tiles, 1), lds_bytes=plan["lds_bytes"],
+                          da=where), launch
+    SLAB_SEEN[name] = launch
+    return res, launch
+
+
+def slab_reference(name, k, monkeypatch):
+    """The oracle on frame k of slab_frames(), once per model (the two (20, 37) rows share theirs)."""
+    key = (SLAB_ROWS[name][:5], k)
+    if key not in _slab_reference:
+        _slab_reference[key] = oracle_td_eval(slab_model(name), slab_frames()[k], monkeypatch)
+    return _slab_reference[key]
+
+
+@pytest.mark.parametrize("name", list(SLAB_ROWS))
+def test_td_slab_rows_against_oracle(name, monkeypatch):
+    """act' of H, then of U and S behind it, in LDS or in the global slab (`scratch + blockIdx.x * da_tile`,
+    `da + da_h`), over nine tiles with ragged last tiles; the launch the engine reports is checked first."""
+    res, launch = slab_launch(name, monkeypatch, slab_frames())
+    assert launch["grid"] == (9, 1), launch
+    for k, r in enumerate(res):
+        assert_close(r, slab_reference(name, k, monkeypatch), f"{name}/frame{k}")
+
+
+def test_td_too_wide_is_refused_then_a_valid_model(monkeypatch):
+    """H (320, 320): 168,960 B without the act' slab, above the 150 KB a workgroup may ask for. Refused with a
+    ValueError that names the limit; the process then evaluates a valid model correctly."""
+    nn = td_from(_sf(["Mo", "Ni"]), TOO_WIDE[0], TOO_WIDE[1], algo="Sommerfeld", resnet=True, minmax=True)
+    frames = slab_frames()
+    assert td_plan_mirror(nn)["refused"]
+    with Engine(nn, device=0) as eng:
+        with pytest.raises(ValueError, match=r"too wide for the LDS tile: 168960 B .* limit 153600"):
+            eng.evaluate(frames[:1], want=ALL)
+    with Engine(slab_model("lds"), device=0) as eng:
+        r = eng.evaluate(frames[:1], want=ALL)[0]
+        assert eng.mlp_launch()["family"] == "td"
+    assert_close(r, slab_reference("lds", 0, monkeypatch), "after the refusal")
