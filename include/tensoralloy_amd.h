@@ -366,6 +366,62 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
               double *ekin, int32_t *n_rebuilds);
 int ta_md_get_state(ta_handle h, double *positions, double *velocities);
 
+/* Device-resident structure relaxation: the resident batch is brought to a force minimum in ONE call, every
+ * frame on its own, with positions, velocities and forces staying on the device. The optimiser is FIRE
+ * (Bitzek et al., PRL 97, 170201) as ASE's FIRE with downhill_check = False. Per frame, with F the forces at
+ * the current positions and |.|, . over all 3 n components of the frame:
+ *     before every step:  if max_i |F_i|^2 < fmax^2: the frame is converged; it does not move again in this run
+ *     if first:         v = 0
+ *     else if F.v > 0:  v = (1 - a) v + a F |v| / |F|;  if npos > nmin: dt = min(dt finc, dtmax), a = a fa;  npos += 1
+ *     else:             v = 0;  a = astart;  dt = dt fdec;  npos = 0
+ *     v += dt F;  dr = dt v;  if |dr| > maxstep: dr = dr maxstep / |dr|;  x += dr
+ * (ASE's units: its FIRE treats every mass as 1.) Cells stay fixed, positions unwrapped. Atoms of the `fixed`
+ * mask have their forces read as 0 everywhere above, the convergence test included (ASE's FixAtoms), and
+ * their positions are never written. Converged frames stay in the batch and are still evaluated: a run costs
+ * (steps of the slowest frame) x (one evaluation of the whole batch).
+ *   ta_fire_params      ASE's names; NULL at ta_relax_init means ASE's defaults
+ *                       dt 0.1, dtmax 1.0, maxstep 0.2, finc 1.1, fdec 0.5, astart 0.1, fa 0.99, nmin 5.
+ *   ta_relax_init       Needs a resident batch. Resets the state of every frame: v = 0, dt, a = astart,
+ *                       npos = 0. fixed [n_atoms_total] (non-zero = fixed) or NULL. ta_set_frames (and ta_eval)
+ *                       drop the state; ta_update_positions / ta_step keep it. The relaxation owns its
+ *                       velocities: those of ta_md_init are left alone.
+ *                       TA_ERR_INVALID, with the argument named by ta_last_error: dt, dtmax or maxstep not
+ *                       finite or <= 0, finc < 1, fdec or fa outside (0, 1), astart outside (0, 1], nmin < 0.
+ *   ta_relax_run        Continues from the kept state (v, dt, a, npos of every frame), so a run may be cut into
+ *                       several calls, and a second run with a smaller fmax carries on: frames frozen by an
+ *                       earlier run are tested against the new fmax and wake if they fail it. Ends when every
+ *                       frame is converged, or when the frames that are not have taken max_steps steps in this
+ *                       run; max_steps = 0 evaluates the state, tests it and moves nothing.
+ *                       steps [n_frames]: steps the frame took in this run; converged [n_frames]: 1 / 0;
+ *                       fmax_out [n_frames]: max_i |F_i| (free atoms) of the frame's final state; any may be NULL.
+ *                       On return the results of the last evaluation, which is one of the final positions, are
+ *                       resident as after ta_compute(want | ENERGY | FORCES), and the list bookkeeping is as
+ *                       ta_md_run leaves it: each step of the run (of its slowest frame) counts as a list reuse
+ *                       or a list build in ta_list_stats, *n_rebuilds (may be NULL) = lists built by this run,
+ *                       rebuilds happen as in ta_md_run (skin / 2 rule tested on the device after every
+ *                       drift; a failed rebuild ends the run with an error that names the step), so a
+ *                       following ta_md_run or ta_step works. The host looks at the device every few steps
+ *                       only, so up to 3 evaluations are enqueued past the step at which the last frame
+ *                       converged; they re-evaluate unchanged positions.
+ *                       A run that fails (a rebuild that finds non-finite coordinates, a device error) drops
+ *                       the relaxation state, as the positions and velocities then stand somewhere on the
+ *                       way: ta_relax_run and ta_relax_get_state are TA_ERR_INVALID until ta_relax_init.
+ *                       A refused argument leaves the state as it was.
+ *                       Every workgroup (1024 atoms) re-adds all partial sums of its frame with one
+ *                       wavefront: 32 bytes per 1024 atoms of the frame, so the work per frame grows with
+ *                       the square of its workgroups; negligible up to some 1e6 atoms per frame.
+ *                       TA_ERR_INVALID: before ta_relax_init, fmax not finite or <= 0, max_steps < 0.
+ *   ta_relax_get_state  positions / velocities [n_atoms_total][3], dt / a / npos [n_frames] of the kept state;
+ *                       any may be NULL. */
+typedef struct {
+  double dt, dtmax, maxstep, finc, fdec, astart, fa;
+  int32_t nmin;
+} ta_fire_params;
+int ta_relax_init(ta_handle h, const ta_fire_params *p, const uint8_t *fixed);
+int ta_relax_run(ta_handle h, int32_t max_steps, double fmax, uint32_t want, int32_t *steps, int32_t *converged,
+                 double *fmax_out, int32_t *n_rebuilds);
+int ta_relax_get_state(ta_handle h, double *positions, double *velocities, double *dt, double *a, int32_t *npos);
+
 /* Enqueue all further work of this handle on `stream` (a hipStream_t of the
  * handle's device owned by the caller, e.g. the stream a RCCL collective is
  * ordered against); NULL restores the handle's own stream (to name the legacy

@@ -17,6 +17,7 @@ from .transformer import UniversalTransformer, VirtualAtomMap
 from .calculator import TensorAlloyCalculator
 from .engine import Engine
 from .md import DeviceMD, maxwell_boltzmann
+from .optimize import DeviceFIRE
 
 __all__ = ["Atoms", "AtomicNN", "TemperatureDependentAtomicNN", "FiniteTemperatureOptions", "SymmetryFunction", "GenericRadialAtomicPotential", "UniversalTransformer", "VirtualAtomMap",
-           "TensorAlloyCalculator", "Engine", "load_model", "HAVE_ASE", "DeviceMD", "maxwell_boltzmann"]
+           "TensorAlloyCalculator", "Engine", "load_model", "HAVE_ASE", "DeviceMD", "maxwell_boltzmann", "DeviceFIRE"]

@@ -21,7 +21,7 @@ LIB_PATH = PKG_DIR / "libtensoralloy_amd.so"
 
 SOURCES = ["ta_api.hip", "ta_kernels.hip", "ta_kernels_v2.hip", "ta_mlp.hip", "ta_eam.hip",
            "ta_nlist.hip", "ta_grap.hip", "ta_train.hip", "ta_hvp.hip", "ta_neighbor.cpp", "ta_td.hip",
-           "ta_td_train.hip", "ta_md.hip"]
+           "ta_td_train.hip", "ta_md.hip", "ta_relax.hip"]
 OBJ_DIR = CSRC_DIR / "build"
 
 TA_OK = 0
@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = [
     "ta_set_filter_tables", "ta_filter_table_knots",
     "ta_md_init", "ta_md_set_thermostat", "ta_md_run", "ta_md_get_state",
     "ta_md_set_langevin", "ta_md_noise",
+    "ta_relax_init", "ta_relax_run", "ta_relax_get_state",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -94,6 +95,11 @@ class BatchInfo(C.Structure):
                 ("n_triples", C.c_int64), ("nnl_max", C.c_int32), ("descriptor_dim", C.c_int32),
                 ("nl_on_device", C.c_int32), ("reserved_", C.c_int32),
                 ("nl_ms", C.c_double), ("set_frames_ms", C.c_double)]
+
+
+class FireParams(C.Structure):
+    _fields_ = [("dt", C.c_double), ("dtmax", C.c_double), ("maxstep", C.c_double), ("finc", C.c_double),
+                ("fdec", C.c_double), ("astart", C.c_double), ("fa", C.c_double), ("nmin", C.c_int32)]
 
 
 def hipcc_path() -> str:
@@ -257,6 +263,9 @@ def load():
     lib.ta_md_get_state.argtypes = [H, _dp, _dp]
     lib.ta_md_set_langevin.argtypes = [H, C.c_double, C.c_double, C.c_uint64]
     lib.ta_md_noise.argtypes = [H, C.c_int64, _dp, _dp]
+    lib.ta_relax_init.argtypes = [H, C.POINTER(FireParams), C.POINTER(C.c_uint8)]
+    lib.ta_relax_run.argtypes = [H, C.c_int32, C.c_double, C.c_uint32, _ip, _ip, _dp, _ip]
+    lib.ta_relax_get_state.argtypes = [H, _dp, _dp, _dp, _dp, _ip]
     _lib = lib
     return lib
 

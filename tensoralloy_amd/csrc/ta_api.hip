@@ -16,6 +16,7 @@
 #include "ta_device.h"
 #include "ta_internal.h"
 #include "ta_md.h"
+#include "ta_relax.h"
 
 namespace ta {
 size_t mlp_scratch_doubles(const MlpDev &mlp);
@@ -351,6 +352,18 @@ struct ta_context {
   uint64_t md_seed = 0;
   int64_t md_step = 0;
   DevBuf<double> md_noise;
+
+  // device-resident relaxation (ta_relax_init / ta_relax_run; the launches are in ta_relax.hip): FIRE
+  // velocities of its own, the mask of fixed atoms, the two copies of the per-frame state with the host's
+  // image of the current one, the workgroups' partial sums and the count of converged frames. The status
+  // words, md_ref and the workgroup layout are the MD loop's.
+  bool relax_valid = false;
+  ta_fire_params relax_p = {0.1, 1.0, 0.2, 1.1, 0.5, 0.1, 0.99, 5};
+  DevBuf<double> relax_vel, relax_part;
+  DevBuf<uint8_t> relax_fixed;
+  DevBuf<ta::RelaxFrameState> relax_state;
+  DevBuf<int> relax_count;
+  std::vector<ta::RelaxFrameState> relax_state_host;
 
   hipEvent_t ev[2 * TA_N_KERNEL_SLOTS + 2] = {nullptr};
   std::string err;
@@ -1171,6 +1184,11 @@ int ta_destroy(ta_handle h) {
   h->md_blk_start.release();
   h->md_status.release();
   h->md_status_host.release();
+  h->relax_vel.release();
+  h->relax_part.release();
+  h->relax_fixed.release();
+  h->relax_state.release();
+  h->relax_count.release();
   for (auto &e : h->ev)
     if (e) (void)hipEventDestroy(e);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -1532,6 +1550,7 @@ int ta_set_frames(ta_handle h, int32_t n_frames, const ta_frame *frames, ta_batc
   if (!h) return TA_ERR_INVALID;
   if (n_frames < 0 || (n_frames > 0 && !frames)) return fail(h, TA_ERR_INVALID, "bad frames argument");
   h->md_valid = false;  // masses and velocities belong to the batch that leaves
+  h->relax_valid = false;
   return guarded(h, [&]() {
     set_frames_impl(h, n_frames, frames, info);
     if (h->td)  // every frame starts at T = 0, the reference's default (universal.py:295)
@@ -1778,6 +1797,71 @@ void md_plan_blocks(ta_context *h, int chunk) {
   h->md_chunk = chunk;
   h->md_n_blk = start[F];
 }
+
+// The loop that ta_md_run and ta_relax_run share. `enqueue(q)` puts the launches of step q on the stream
+// (they are predicated on the status word and test the skin / 2 rule after their drift); this loop follows
+// each with the exact list of the step and an evaluation, looks at the page-locked status word every
+// kMdLookahead steps, and where a drift left the list stale rebuilds it from the device's positions and
+// goes on behind that step. After a look that found the list valid, `finished(k, k_end)` may name the step
+// in [k, k_end) from which on the launches moved nothing (-1: none): the loop ends there. Returns the
+// steps done; F of the state at entry must be resident. `*rebuilds` counts the lists built, `*n_rebuilds`
+// (may be null) follows it so that a run that fails reports what it did. Throws.
+extern "C++" template <class Enqueue, class Finished>
+int resident_steps(ta_context *h, const char *who, int n_steps, uint32_t want, Enqueue &&enqueue,
+                   Finished &&finished, int *rebuilds, int32_t *n_rebuilds) {
+  const size_t N = h->keep_species.size();
+  hipStream_t s = h->stream;
+  volatile unsigned *status_host = reinterpret_cast<volatile unsigned *>(h->md_status_host.ptr);
+  const int look = h->skin > 0.0 ? ta::kMdLookahead : 1;
+  std::vector<double> x;
+  int k = 0;
+  while (k < n_steps) {
+    // steps k .. k_end - 1 without a look at the device: integrator, exact list of the step, evaluation
+    const int k_end = (int)std::min<int64_t>(n_steps, (int64_t)k + look);
+    for (int q = k; q < k_end; ++q) {
+      enqueue(q);
+      if (h->filtered) apply_filter(h);
+      compute_impl(h, want, false, nullptr);
+    }
+    wait_stream(s);
+    h->upload_pending = false;
+    const unsigned mark = status_host[0];
+    if (mark == 0u) {
+      const int fin = finished(k, k_end);
+      if (fin >= 0) {
+        h->n_list_reuses += fin - k;
+        return fin;
+      }
+      h->n_list_reuses += k_end - k;
+      k = k_end;
+      continue;
+    }
+    // the drift of step q left the list stale: the launches behind it did nothing, the evaluations
+    // behind it ran on the stale list and are overwritten now
+    const int q = (int)mark - 1;
+    if (q < k || q >= k_end) throw std::runtime_error(std::string(who) + ": inconsistent status word");
+    h->n_list_reuses += q - k;
+    x.resize(3 * N);
+    if (N) HIP_CHECK(hipMemcpy(x.data(), h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+    status_host[0] = 0u;
+    HIP_CHECK(hipMemsetAsync(h->md_status.ptr, 0, 2 * sizeof(unsigned), s));
+    try {
+      rebuild_list(h, x.data(), nullptr);
+    } catch (const HipError &e) {
+      throw HipError(std::string(who) + ": list rebuild after step " + std::to_string(q + 1) + " failed: " + e.what());
+    } catch (const std::exception &e) {
+      throw std::runtime_error(std::string(who) + ": list rebuild after step " + std::to_string(q + 1) +
+                               " failed: " + e.what());
+    }
+    if (N) HIP_CHECK(hipMemcpyAsync(h->md_ref.ptr, h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToDevice, s));
+    h->md_ref_builds = h->n_list_builds;
+    compute_impl(h, want, false, nullptr);
+    ++*rebuilds;
+    if (n_rebuilds) *n_rebuilds = *rebuilds;
+    k = q + 1;
+  }
+  return n_steps;
+}
 }  // namespace
 
 int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
@@ -1938,48 +2022,9 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
 
     h->jvp_valid = false;
     compute_impl(h, want, false, nullptr);  // F_0 and the record of the state at entry
-    const int look = h->skin > 0.0 ? ta::kMdLookahead : 1;
-    std::vector<double> x;
-    int k = 0, rebuilds = 0;
-    while (k < n_steps) {
-      // steps k .. k_end - 1 without a look at the device: integrator, exact list of the step, evaluation
-      const int k_end = (int)std::min<int64_t>(n_steps, (int64_t)k + look);
-      for (int q = k; q < k_end; ++q) {
-        integrate(q, true);
-        if (h->filtered) apply_filter(h);
-        compute_impl(h, want, false, nullptr);
-      }
-      wait_stream(s);
-      h->upload_pending = false;
-      const unsigned mark = status_host[0];
-      if (mark == 0u) {
-        h->n_list_reuses += k_end - k;
-        k = k_end;
-        continue;
-      }
-      // the drift of step q left the list stale: the launches behind it did nothing, the evaluations
-      // behind it ran on the stale list and are overwritten now
-      const int q = (int)mark - 1;
-      if (q < k || q >= k_end) throw std::runtime_error("ta_md_run: inconsistent status word");
-      h->n_list_reuses += q - k;
-      x.resize(3 * N);
-      if (N) HIP_CHECK(hipMemcpy(x.data(), h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
-      status_host[0] = 0u;
-      HIP_CHECK(hipMemsetAsync(h->md_status.ptr, 0, 2 * sizeof(unsigned), s));
-      try {
-        rebuild_list(h, x.data(), nullptr);
-      } catch (const HipError &e) {
-        throw HipError("ta_md_run: list rebuild after step " + std::to_string(q + 1) + " failed: " + e.what());
-      } catch (const std::exception &e) {
-        throw std::runtime_error("ta_md_run: list rebuild after step " + std::to_string(q + 1) + " failed: " + e.what());
-      }
-      if (N) HIP_CHECK(hipMemcpyAsync(h->md_ref.ptr, h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToDevice, s));
-      h->md_ref_builds = h->n_list_builds;
-      compute_impl(h, want, false, nullptr);
-      ++rebuilds;
-      if (n_rebuilds) *n_rebuilds = rebuilds;
-      k = q + 1;
-    }
+    int rebuilds = 0;
+    resident_steps(h, "ta_md_run", n_steps, want, [&](int q) { integrate(q, true); },
+                   [](int, int) { return -1; }, &rebuilds, n_rebuilds);
     integrate(n_steps, false);  // the pending half-kick and the last record
     HIP_CHECK(hipStreamSynchronize(s));
     h->upload_pending = false;
@@ -2010,6 +2055,174 @@ int ta_md_get_state(ta_handle h, double *positions, double *velocities) {
     h->upload_pending = false;
     if (positions && N) HIP_CHECK(hipMemcpy(positions, h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
     if (velocities && N) HIP_CHECK(hipMemcpy(velocities, h->md_vel.ptr, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+  });
+}
+
+int ta_relax_init(ta_handle h, const ta_fire_params *p, const uint8_t *fixed) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_relax_init: no resident batch");
+  ta_fire_params q = {0.1, 1.0, 0.2, 1.1, 0.5, 0.1, 0.99, 5};  // ASE's defaults
+  if (p) q = *p;
+  auto positive = [](double v) { return std::isfinite(v) && v > 0.0; };
+  if (!positive(q.dt)) return fail(h, TA_ERR_INVALID, "ta_relax_init: dt must be finite and > 0");
+  if (!positive(q.dtmax)) return fail(h, TA_ERR_INVALID, "ta_relax_init: dtmax must be finite and > 0");
+  if (!positive(q.maxstep)) return fail(h, TA_ERR_INVALID, "ta_relax_init: maxstep must be finite and > 0");
+  if (!std::isfinite(q.finc) || q.finc < 1.0) return fail(h, TA_ERR_INVALID, "ta_relax_init: finc must be finite and >= 1");
+  if (!(q.fdec > 0.0 && q.fdec < 1.0)) return fail(h, TA_ERR_INVALID, "ta_relax_init: fdec must lie in (0, 1)");
+  if (!(q.fa > 0.0 && q.fa < 1.0)) return fail(h, TA_ERR_INVALID, "ta_relax_init: fa must lie in (0, 1)");
+  if (!(q.astart > 0.0 && q.astart <= 1.0)) return fail(h, TA_ERR_INVALID, "ta_relax_init: astart must lie in (0, 1]");
+  if (q.nmin < 0) return fail(h, TA_ERR_INVALID, "ta_relax_init: nmin must be >= 0");
+  return guarded(h, [&]() {
+    const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
+    h->relax_valid = false;
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    h->upload_pending = false;
+    h->relax_vel.ensure(3 * N + 1);
+    h->relax_fixed.ensure(N + 1);
+    h->relax_state.ensure(2 * F + 1);
+    h->relax_count.ensure(1);
+    h->md_ref.ensure(3 * N + 1);
+    h->md_ref_builds = -1;  // ta_relax_run uploads ref_pos
+    h->md_status.ensure(2);
+    h->md_status_host.ensure(64);
+    if (N) {
+      HIP_CHECK(hipMemset(h->relax_vel.ptr, 0, 3 * N * sizeof(double)));
+      if (fixed) {
+        std::vector<uint8_t> mask(N);
+        for (size_t i = 0; i < N; ++i) mask[i] = fixed[i] ? 1 : 0;
+        HIP_CHECK(hipMemcpy(h->relax_fixed.ptr, mask.data(), N, hipMemcpyHostToDevice));
+      } else {
+        HIP_CHECK(hipMemset(h->relax_fixed.ptr, 0, N));
+      }
+    }
+    ta::RelaxFrameState st;
+    st.dt = q.dt;
+    st.a = q.astart;
+    st.fmax2 = 0.0;
+    st.npos = 0;
+    st.first = 1;
+    st.converged = 0;
+    st.steps = 0;
+    h->relax_state_host.assign(F, st);
+    h->relax_p = q;
+    h->md_chunk = 0;  // (the workgroup layout is planned for this batch by the next run)
+    h->md_blk_start_host.clear();
+    h->relax_valid = true;
+  });
+}
+
+int ta_relax_run(ta_handle h, int32_t max_steps, double fmax, uint32_t want, int32_t *steps, int32_t *converged,
+                 double *fmax_out, int32_t *n_rebuilds) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_relax_run: no resident batch");
+  if (!h->relax_valid)
+    return fail(h, TA_ERR_INVALID, "ta_relax_run called before ta_relax_init (ta_set_frames drops the relaxation state)");
+  if (max_steps < 0) return fail(h, TA_ERR_INVALID, "ta_relax_run: max_steps must be >= 0");
+  if (!std::isfinite(fmax) || !(fmax > 0.0)) return fail(h, TA_ERR_INVALID, "ta_relax_run: fmax must be finite and > 0");
+  if (n_rebuilds) *n_rebuilds = 0;
+  want |= TA_WANT_ENERGY | TA_WANT_FORCES;
+  want &= ~(uint32_t)TA_WANT_REUSE_DESCRIPTORS;
+  // a run that fails leaves positions and velocities somewhere on its way and the host's image of the
+  // per-frame records behind them: the state is dropped, and only ta_relax_init makes a new one
+  h->relax_valid = false;
+  const int rc = guarded(h, [&]() {
+    const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
+    hipStream_t s = h->stream;
+    md_plan_blocks(h, ta::kMdChunk);
+    const size_t n_blk = (size_t)h->md_n_blk;
+    h->relax_part.ensure(4 * n_blk + 1);
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (h->md_ref_builds != h->n_list_builds) {  // the host built the list that is resident: its positions go up once
+      if (N) HIP_CHECK(hipMemcpy(h->md_ref.ptr, h->ref_pos.data(), 3 * N * sizeof(double), hipMemcpyHostToDevice));
+      h->md_ref_builds = h->n_list_builds;
+    }
+    // every frame is tested against this run's fmax: a frame frozen by an earlier run may wake
+    std::vector<ta::RelaxFrameState> &st = h->relax_state_host;
+    for (auto &r : st) r.converged = 0, r.steps = 0;
+    if (F) HIP_CHECK(hipMemcpy(h->relax_state.ptr, st.data(), F * sizeof(ta::RelaxFrameState), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemset(h->relax_count.ptr, 0, sizeof(int)));
+    volatile unsigned *status_host = reinterpret_cast<volatile unsigned *>(h->md_status_host.ptr);
+    status_host[0] = status_host[1] = 0u;  // (no launch that writes them is in flight: every run ends with a wait)
+    HIP_CHECK(hipMemsetAsync(h->md_status.ptr, 0, 2 * sizeof(unsigned), s));
+
+    const ta_fire_params &p = h->relax_p;
+    ta::RelaxLaunch a;
+    a.vel = h->relax_vel.ptr;
+    a.fixed = h->relax_fixed.ptr;
+    a.ref = h->md_ref.ptr;
+    a.blk_start = h->md_blk_start.ptr;
+    a.part = h->relax_part.ptr;
+    a.state = h->relax_state.ptr;
+    a.n_converged = h->relax_count.ptr;
+    a.status = h->md_status.ptr;
+    a.status_host = const_cast<unsigned *>(status_host);
+    a.dtmax = p.dtmax, a.maxstep = p.maxstep, a.finc = p.finc, a.fdec = p.fdec, a.astart = p.astart, a.fa = p.fa;
+    a.nmin = p.nmin;
+    a.fmax2 = fmax * fmax;
+    a.lim2 = h->skin > 0.0 ? 0.25 * h->skin * h->skin : -1.0;  // skin = 0: every step rebuilds
+    a.n_frames = (int)F;
+    a.n_blk = (int)n_blk;
+    a.chunk = ta::kMdChunk;
+    int launched = 0;  // launches that ran: the current copy of the state is launched & 1
+    auto step = [&](int k, bool drift) {
+      // (a rebuild may have moved the batch's arrays: the pointers are taken at every launch)
+      a.pos = h->db.pos;
+      a.forces = h->db.forces;
+      a.atom_start = h->db.atom_start;
+      a.seq = (unsigned)k;
+      a.drift = drift ? 1 : 0;
+      ta::launch_relax_step(a, s);
+      HIP_CHECK(hipGetLastError());
+      launched = k + 1;
+    };
+
+    h->jvp_valid = false;
+    compute_impl(h, want, false, nullptr);  // F of the state at entry
+    int rebuilds = 0;
+    bool all_converged = false;
+    // the launch at which the last frame converged, and every launch behind it, moved nothing
+    auto finished = [&](int k, int k_end) {
+      const unsigned done = status_host[1];
+      if (done == 0u) return -1;
+      if ((int)done - 1 < k || (int)done - 1 >= k_end) throw std::runtime_error("ta_relax_run: inconsistent done word");
+      all_converged = true;
+      return (int)done - 1;
+    };
+    const int done_steps = resident_steps(h, "ta_relax_run", max_steps, want, [&](int q) { step(q, true); }, finished,
+                                          &rebuilds, n_rebuilds);
+    if (!all_converged) step(done_steps, false);  // the test of the last evaluation
+    HIP_CHECK(hipStreamSynchronize(s));
+    h->upload_pending = false;
+    if (n_rebuilds) *n_rebuilds = rebuilds;
+    if (F)
+      HIP_CHECK(hipMemcpy(st.data(), h->relax_state.ptr + (size_t)(launched & 1) * F, F * sizeof(ta::RelaxFrameState),
+                          hipMemcpyDeviceToHost));
+    for (size_t f = 0; f < F; ++f) {
+      if (steps) steps[f] = st[f].steps;
+      if (converged) converged[f] = st[f].converged;
+      if (fmax_out) fmax_out[f] = std::sqrt(st[f].fmax2);
+    }
+  });
+  if (rc == TA_OK) h->relax_valid = true;
+  return rc;
+}
+
+int ta_relax_get_state(ta_handle h, double *positions, double *velocities, double *dt, double *a, int32_t *npos) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_relax_get_state: no resident batch");
+  if (!h->relax_valid) return fail(h, TA_ERR_INVALID, "ta_relax_get_state called before ta_relax_init");
+  return guarded(h, [&]() {
+    const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    h->upload_pending = false;
+    if (positions && N) HIP_CHECK(hipMemcpy(positions, h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+    if (velocities && N)
+      HIP_CHECK(hipMemcpy(velocities, h->relax_vel.ptr, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t f = 0; f < F; ++f) {
+      if (dt) dt[f] = h->relax_state_host[f].dt;
+      if (a) a[f] = h->relax_state_host[f].a;
+      if (npos) npos[f] = h->relax_state_host[f].npos;
+    }
   });
 }
 

@@ -167,6 +167,16 @@ __device__ __forceinline__ double wave_sum(double v) {
   v += __shfl_xor(v, 32, 64);
   return v;
 }
+// The largest value of the wavefront in every lane, moved like wave_sum (fmax: a NaN lane is dropped).
+__device__ __forceinline__ double wave_max(double v) {
+  v = fmax(v, dpp_move<0x128>(v));  // row_ror:8
+  v = fmax(v, dpp_move<0x124>(v));  // row_ror:4
+  v = fmax(v, dpp_move<0x122>(v));  // row_ror:2
+  v = fmax(v, dpp_move<0x121>(v));  // row_ror:1
+  v = fmax(v, __shfl_xor(v, 16, 64));
+  v = fmax(v, __shfl_xor(v, 32, 64));
+  return v;
+}
 
 // 1 / d for d in [1, 3]: hardware seed + two Newton steps (no scaling / fix-up needed in that range)
 __device__ __forceinline__ double rcp_1_3(double d) {

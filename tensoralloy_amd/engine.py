@@ -326,6 +326,73 @@ class Engine:
         self._check(self._lib.ta_md_get_state(self._handle, _lib.as_dp(x), _lib.as_dp(v)))
         return x, v
 
+    # -- device-resident relaxation ----------------------------------------------------------
+    def relax_init(self, fixed=None, **params):
+        """FIRE state of every frame of the resident batch for `relax_run` (`ta_relax_init`): v = 0, dt,
+        a = astart. `fixed`: boolean mask [n_atoms] or indices of atoms that do not move and do not count
+        towards convergence. `params`: dt, dtmax, maxstep, finc, fdec, astart, fa, nmin (ASE's FIRE defaults).
+        `set_frames` drops the state; `update_positions` / `step` keep it."""
+        if self.info is None:
+            raise ValueError("relax_init: no resident batch (call set_frames first)")
+        p = dict(dt=0.1, dtmax=1.0, maxstep=0.2, finc=1.1, fdec=0.5, astart=0.1, fa=0.99, nmin=5)
+        unknown = sorted(set(params) - set(p))
+        if unknown:
+            raise ValueError(f"relax_init: unknown parameter {unknown[0]!r} (known: {', '.join(p)})")
+        p.update(params)
+        if int(p["nmin"]) != p["nmin"]:
+            raise ValueError("relax_init: nmin must be an integer")
+        fp = _lib.FireParams(*(float(p[k]) for k in ("dt", "dtmax", "maxstep", "finc", "fdec", "astart", "fa")),
+                             max(-1, min(int(p["nmin"]), 2 ** 31 - 1)))
+        N = int(self.info.n_atoms)
+        mptr = C.POINTER(C.c_uint8)()
+        if fixed is not None:
+            from .utils import fixed_atoms_mask
+            mask = np.ascontiguousarray(fixed_atoms_mask(fixed, N, "relax_init"), dtype=np.uint8)
+            mptr = mask.ctypes.data_as(C.POINTER(C.c_uint8))
+        self._check(self._lib.ta_relax_init(self._handle, C.byref(fp), mptr))
+
+    def relax_run(self, max_steps: int, fmax: float, want: int = None) -> dict:
+        """FIRE steps of the resident batch on the device (`ta_relax_run`) until every frame has
+        max_i |F_i| < `fmax` (eV / A) or the others have taken `max_steps` steps; continues from the state the
+        last run left. Returns per frame `steps` (taken in this run), `converged`, `fmax` (of the final state)
+        and `energy`, and `n_rebuilds`. Afterwards `fetch(want | ENERGY | FORCES)` hands out the results of
+        the final state."""
+        if self.info is None:
+            raise ValueError("relax_run: no resident batch (call set_frames first)")
+        max_steps = int(max_steps)
+        if max_steps < 0:
+            raise ValueError("relax_run: max_steps must be >= 0")
+        if want is None:
+            want = _lib.TA_WANT_ENERGY | _lib.TA_WANT_FORCES
+        F = int(self.info.n_frames)
+        steps, conv = np.zeros(F, dtype=np.int32), np.zeros(F, dtype=np.int32)
+        fm = np.empty(F)
+        rebuilds = C.c_int32(0)
+        rc = self._lib.ta_relax_run(self._handle, max_steps, float(fmax), int(want), _lib.as_ip(steps),
+                                    _lib.as_ip(conv), _lib.as_dp(fm), C.byref(rebuilds))
+        self.batch_generation += 1  # the coordinates changed (also when the run ended early)
+        self._check(rc)
+        if rebuilds.value:
+            n_pairs, n_triples, nnl = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+            self._check(self._lib.ta_list_sizes(self._handle, C.byref(n_pairs), C.byref(n_triples), C.byref(nnl)))
+            self.info.n_pairs, self.info.n_triples, self.info.nnl_max = n_pairs.value, n_triples.value, nnl.value
+        energy = np.empty(F)
+        null = C.POINTER(C.c_double)()
+        self._check(self._lib.ta_get_results(self._handle, _lib.as_dp(energy), null, null, null, null))
+        return {"steps": steps.astype(np.int64), "converged": conv.astype(bool), "fmax": fm, "energy": energy,
+                "n_rebuilds": int(rebuilds.value)}
+
+    def relax_state(self) -> dict:
+        """positions, velocities [n_atoms, 3] and dt, a, npos [n_frames] of the relaxation as the device holds them."""
+        if self.info is None:
+            raise ValueError("relax_state: no resident batch (call set_frames first)")
+        N, F = int(self.info.n_atoms), int(self.info.n_frames)
+        x, v = np.empty((N, 3)), np.empty((N, 3))
+        dt, a, npos = np.empty(F), np.empty(F), np.zeros(F, dtype=np.int32)
+        self._check(self._lib.ta_relax_get_state(self._handle, _lib.as_dp(x), _lib.as_dp(v), _lib.as_dp(dt),
+                                                 _lib.as_dp(a), _lib.as_ip(npos)))
+        return {"positions": x, "velocities": v, "dt": dt, "a": a, "npos": npos.astype(np.int64)}
+
     def list_stats(self):
         """(lists built, lists reused) by this engine."""
         a, b = C.c_int64(0), C.c_int64(0)

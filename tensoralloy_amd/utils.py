@@ -130,3 +130,20 @@ def parameter_grid(**axes: Iterable[float]) -> List[Dict[str, float]]:
     keys = sorted(axes)
     values = [list(np.asarray(axes[k], dtype=float).ravel()) for k in keys]
     return [dict(zip(keys, combo)) for combo in itertools.product(*values)]
+
+
+def fixed_atoms_mask(fixed, n_atoms, who):
+    """Boolean mask [n_atoms] from `fixed`: a boolean mask of that length, or a list of atom indices
+    (negative ones count from the end). ValueError, in the name of `who`, for anything else."""
+    import numpy as np
+    fixed = np.asarray(fixed)
+    if fixed.dtype == np.bool_:
+        if fixed.size != n_atoms:
+            raise ValueError(f"{who}: the fixed mask needs one entry for every atom")
+        return fixed.ravel().copy()
+    idx = fixed.astype(np.int64).ravel()
+    if fixed.size and (not np.array_equal(idx, fixed.ravel()) or idx.min() < -n_atoms or idx.max() >= n_atoms):
+        raise ValueError(f"{who}: fixed must be a boolean mask or indices of atoms")
+    mask = np.zeros(n_atoms, dtype=bool)
+    mask[idx] = True
+    return mask
