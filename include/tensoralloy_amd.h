@@ -375,7 +375,7 @@ int ta_md_get_state(ta_handle h, double *positions, double *velocities);
  *     else if F.v > 0:  v = (1 - a) v + a F |v| / |F|;  if npos > nmin: dt = min(dt finc, dtmax), a = a fa;  npos += 1
  *     else:             v = 0;  a = astart;  dt = dt fdec;  npos = 0
  *     v += dt F;  dr = dt v;  if |dr| > maxstep: dr = dr maxstep / |dr|;  x += dr
- * (ASE's units: its FIRE treats every mass as 1.) Cells stay fixed, positions unwrapped. Atoms of the `fixed`
+ * (ASE's units: its FIRE treats every mass as 1.) Cells stay fixed unless ta_relax_set_cell says otherwise, positions unwrapped. Atoms of the `fixed`
  * mask have their forces read as 0 everywhere above, the convergence test included (ASE's FixAtoms), and
  * their positions are never written. Converged frames stay in the batch and are still evaluated: a run costs
  * (steps of the slowest frame) x (one evaluation of the whole batch).
@@ -421,6 +421,59 @@ int ta_relax_init(ta_handle h, const ta_fire_params *p, const uint8_t *fixed);
 int ta_relax_run(ta_handle h, int32_t max_steps, double fmax, uint32_t want, int32_t *steps, int32_t *converged,
                  double *fmax_out, int32_t *n_rebuilds);
 int ta_relax_get_state(ta_handle h, double *positions, double *velocities, double *dt, double *a, int32_t *npos);
+
+/* Cells relaxed together with the atoms (ASE's UnitCellFilter under the FIRE above). Per frame of n atoms, with
+ * h0 the cell when the option was switched on (rows are lattice vectors), G a 3x3 deformation gradient that
+ * starts at the identity, cf the cell factor, p an external pressure and M a symmetric 0/1 mask:
+ *     h = h0 G^T,   x_i = q_i G^T,   generalised coordinates: the n + 3 rows [q_1 .. q_n ; cf G]
+ *     f_i    = F_i G                               (a fixed atom: 0)
+ *     f_cell = -((W + p V I) G^-T) o M / cf        (hydrostatic: f_cell = I trace(f_cell) / 3 before the mask)
+ * with W the library's virial (dE / d strain) and V = |det h| of the current state: minus the gradient of
+ * E + p V. FIRE is the recurrence above with every ., |.| and the maxstep clamp over all 3 (n + 3)
+ * components, n + 3 velocity rows, and the convergence test max_row |f_row|^2 < fmax^2 over all n + 3 rows.
+ * A step with the clamped dr: q_i = x_i G^-T (recomputed from the positions, not stored); q_i += dr_i;
+ * G += dr_cell / cf; h = h0 G^T; x_i = q_i G^T. Fixed atoms keep their q_i, so they move affinely with the
+ * cell: the one difference from "never written" above. G may pick up a rotation (W G^-T is not symmetric),
+ * as in ASE.
+ *   ta_relax_cell_params  cell_factor 0 = the atoms of the frame (ASE's default); pressure in eV / A^3; mask in
+ *                       Voigt order xx yy zz yz xz xy, non-zero = free; hydrostatic != 0 = ASE's
+ *                       hydrostatic_strain. NULL at ta_relax_set_cell: cell_factor 0, pressure 0, mask all 1.
+ *   ta_relax_set_cell   Needs ta_relax_init, which switches the option off again (as do ta_set_frames and a run
+ *                       that fails). on != 0: h0 = the resident cells, G = I and cell velocities 0 for every
+ *                       frame; the FIRE state of the atoms stays. on = 0: back to fixed cells; the current
+ *                       cells stay. TA_ERR_INVALID with the argument named by ta_last_error and the state left
+ *                       as it was: a frame that is not periodic along all three axes or has a singular cell,
+ *                       cell_factor negative or not finite, pressure not finite, a mask of all zeros.
+ *                       Cells handed to ta_update_positions / ta_step while the option is on replace the
+ *                       relaxed ones: they become h0, G = I and the cell velocities 0.
+ *   ta_relax_run        with the option on: TA_WANT_VIRIAL is added to `want`; fmax_out is the maximum over
+ *                       all n + 3 rows. The cells change on the device, so the list test knows strain: with
+ *                       h_ref, x_ref the cell and positions the list was built for, rc = max(rcut, acut),
+ *                       A = h_ref^-1 h and u_i = x_i - x_ref,i A, every pair vector obeys
+ *                       D_new = D_ref A + (u_j - u_i), and sigma_min(A) >= 1 - |A - I|_F; the list is stale when
+ *                       lim = (skin - (rc + skin) |A - I|_F) / 2 <= 0 or some |u_i|^2 >= lim^2 (A = I: the
+ *                       skin / 2 rule; skin = 0: every step rebuilds). A periodic width shrinks by less than
+ *                       rc / (rc + skin) while a list is valid, so while the option is on the triangle-once
+ *                       backward pass is selected only when every periodic width of the list's cells exceeds
+ *                       rc + skin (ta_backward_variant reports what ran). When a run ends with cells other
+ *                       than those of its list, it builds one list for the final state and evaluates it
+ *                       again (counted in *n_rebuilds and ta_list_stats; results agree up to summation
+ *                       order): ta_md_run, ta_step, ta_update_positions and a fixed-cell ta_relax_run then
+ *                       find the cells the list was built for, and "cells = NULL: unchanged" of
+ *                       ta_update_positions means the relaxed cells. A run may still be cut into several calls.
+ *   ta_relax_get_cell   cells [n_frames][9] (= h0 G^T), deform [n_frames][9] (G), cell_velocities
+ *                       [n_frames][9] (of the rows cf G), cell_fmax [n_frames] (max row |f_cell| of the last
+ *                       state a cell run tested; 0 before one); any may be NULL. Needs ta_relax_init; with the
+ *                       option never switched on G = I and the velocities are 0. */
+typedef struct {
+  double cell_factor;
+  double pressure;
+  int32_t mask[6];
+  int32_t hydrostatic;
+  int32_t reserved_;
+} ta_relax_cell_params;
+int ta_relax_set_cell(ta_handle h, int on, const ta_relax_cell_params *p);
+int ta_relax_get_cell(ta_handle h, double *cells, double *deform, double *cell_velocities, double *cell_fmax);
 
 /* Enqueue all further work of this handle on `stream` (a hipStream_t of the
  * handle's device owned by the caller, e.g. the stream a RCCL collective is

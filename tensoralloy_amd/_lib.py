@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = [
     "ta_md_init", "ta_md_set_thermostat", "ta_md_run", "ta_md_get_state",
     "ta_md_set_langevin", "ta_md_noise",
     "ta_relax_init", "ta_relax_run", "ta_relax_get_state",
+    "ta_relax_set_cell", "ta_relax_get_cell",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -100,6 +101,11 @@ class BatchInfo(C.Structure):
 class FireParams(C.Structure):
     _fields_ = [("dt", C.c_double), ("dtmax", C.c_double), ("maxstep", C.c_double), ("finc", C.c_double),
                 ("fdec", C.c_double), ("astart", C.c_double), ("fa", C.c_double), ("nmin", C.c_int32)]
+
+
+class RelaxCellParams(C.Structure):
+    _fields_ = [("cell_factor", C.c_double), ("pressure", C.c_double), ("mask", C.c_int32 * 6),
+                ("hydrostatic", C.c_int32), ("reserved_", C.c_int32)]
 
 
 def hipcc_path() -> str:
@@ -266,6 +272,8 @@ def load():
     lib.ta_relax_init.argtypes = [H, C.POINTER(FireParams), C.POINTER(C.c_uint8)]
     lib.ta_relax_run.argtypes = [H, C.c_int32, C.c_double, C.c_uint32, _ip, _ip, _dp, _ip]
     lib.ta_relax_get_state.argtypes = [H, _dp, _dp, _dp, _dp, _ip]
+    lib.ta_relax_set_cell.argtypes = [H, C.c_int, C.POINTER(RelaxCellParams)]
+    lib.ta_relax_get_cell.argtypes = [H, _dp, _dp, _dp, _dp]
     _lib = lib
     return lib
 

@@ -284,6 +284,7 @@ struct ta_context {
   DevBuf<int32_t> job_count_own;
   bool triangles = true;
   bool tri_cells_ok = false;
+  bool tri_cells_wide_ok = false;  // every periodic width exceeds rmax + skin: what the cell relaxation asks for
   int last_bwd_variant = 0;
   ta::MlpLaunchInfo last_mlp_launch;  // ta_mlp_launch_info
   DevBuf<int32_t> pair_start, seg_start, pair_i, pair_j, pair_shift, pair_rev;
@@ -364,6 +365,14 @@ struct ta_context {
   DevBuf<ta::RelaxFrameState> relax_state;
   DevBuf<int> relax_count;
   std::vector<ta::RelaxFrameState> relax_state_host;
+  // cell mode of the relaxation (ta_relax_set_cell): h0 and the cell factor of every frame, the deformation
+  // gradient and the cell velocity (two copies on the device like relax_state, the current one on the host
+  // between runs), the reference cells of the resident list next to md_ref
+  bool relax_cell_on = false;
+  bool relax_cell_running = false;  // a cell run is under way: rebuilds take the cells from the device
+  ta_relax_cell_params relax_cell_p = {0.0, 0.0, {1, 1, 1, 1, 1, 1}, 0, 0};
+  DevBuf<double> relax_cell_h0, relax_cell_cf, relax_cell_G, relax_cell_vel, relax_cell_fmax2, md_ref_cells;
+  std::vector<double> relax_cell_G_host, relax_cell_vel_host;
 
   hipEvent_t ev[2 * TA_N_KERNEL_SLOTS + 2] = {nullptr};
   std::string err;
@@ -938,7 +947,9 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
     }
     h->sf.ang_scale = h->use_v2 ? 1.0 : 0.5;
     // triangle-once backward pass: the forward launches also leave the owned job lists
-    const bool tri = h->use_v2 && h->triangles && h->tri_cells_ok && h->n_elements == 1 && need_forces;
+    // (while cells relax, a list stays valid until a width has shrunk by rmax / (rmax + skin): the wider test)
+    const bool tri_cells = h->relax_cell_on ? h->tri_cells_wide_ok : h->tri_cells_ok;
+    const bool tri = h->use_v2 && h->triangles && tri_cells && h->n_elements == 1 && need_forces;
     h->db.job_word_own = (tri && h->db.job_count) ? h->job_word_own.ptr : nullptr;
     h->db.job_count_own = (tri && h->db.job_count) ? h->job_count_own.ptr : nullptr;
     h->last_bwd_variant = 0;
@@ -1189,6 +1200,9 @@ int ta_destroy(ta_handle h) {
   h->relax_fixed.release();
   h->relax_state.release();
   h->relax_count.release();
+  for (auto *b : {&h->relax_cell_h0, &h->relax_cell_cf, &h->relax_cell_G, &h->relax_cell_vel, &h->relax_cell_fmax2,
+                  &h->md_ref_cells})
+    b->release();
   for (auto &e : h->ev)
     if (e) (void)hipEventDestroy(e);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -1323,6 +1337,7 @@ void set_frames_impl(ta_context *h, int32_t n_frames, const ta_frame *frames, ta
   h->db.n_blk_dev = nullptr;
   h->r_list = h->rmax + h->skin;
   h->tri_cells_ok = cells_admit_triangles(h->rmax, n_frames, frames);
+  h->tri_cells_wide_ok = cells_admit_triangles(h->r_list, n_frames, frames);
   size_t N = 0;
   for (int f = 0; f < n_frames; ++f) N += (size_t)frames[f].n_atoms;
   if (N >= (1u << 30)) throw std::runtime_error("batch too large for 32-bit atom indices");
@@ -1551,6 +1566,7 @@ int ta_set_frames(ta_handle h, int32_t n_frames, const ta_frame *frames, ta_batc
   if (n_frames < 0 || (n_frames > 0 && !frames)) return fail(h, TA_ERR_INVALID, "bad frames argument");
   h->md_valid = false;  // masses and velocities belong to the batch that leaves
   h->relax_valid = false;
+  h->relax_cell_on = false;
   return guarded(h, [&]() {
     set_frames_impl(h, n_frames, frames, info);
     if (h->td)  // every frame starts at T = 0, the reference's default (universal.py:295)
@@ -1660,6 +1676,13 @@ int ta_update_positions(ta_handle h, const double *positions, const double *cell
       return;
     }
     rebuild_list(h, positions, cells);
+    if (cells && h->relax_cell_on && h->relax_valid && F) {
+      // the caller's cells replace the relaxed ones: they are h0 from here on, G = I, the cell velocities 0
+      HIP_CHECK(hipMemcpy(h->relax_cell_h0.ptr, h->ref_cells.data(), 9 * F * sizeof(double), hipMemcpyHostToDevice));
+      h->relax_cell_G_host.assign(9 * F, 0.0);
+      for (size_t f = 0; f < F; ++f) h->relax_cell_G_host[9 * f] = h->relax_cell_G_host[9 * f + 4] = h->relax_cell_G_host[9 * f + 8] = 1.0;
+      h->relax_cell_vel_host.assign(9 * F, 0.0);
+    }
   });
 }
 
@@ -1813,7 +1836,8 @@ int resident_steps(ta_context *h, const char *who, int n_steps, uint32_t want, E
   hipStream_t s = h->stream;
   volatile unsigned *status_host = reinterpret_cast<volatile unsigned *>(h->md_status_host.ptr);
   const int look = h->skin > 0.0 ? ta::kMdLookahead : 1;
-  std::vector<double> x;
+  std::vector<double> x, cells;
+  const size_t F = h->keep_natoms.size();
   int k = 0;
   while (k < n_steps) {
     // steps k .. k_end - 1 without a look at the device: integrator, exact list of the step, evaluation
@@ -1843,10 +1867,14 @@ int resident_steps(ta_context *h, const char *who, int n_steps, uint32_t want, E
     h->n_list_reuses += q - k;
     x.resize(3 * N);
     if (N) HIP_CHECK(hipMemcpy(x.data(), h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+    if (h->relax_cell_running) {  // the cells moved on the device: ref_cells are those of the stale list
+      cells.resize(9 * F);
+      if (F) HIP_CHECK(hipMemcpy(cells.data(), h->db.cells, 9 * F * sizeof(double), hipMemcpyDeviceToHost));
+    }
     status_host[0] = 0u;
     HIP_CHECK(hipMemsetAsync(h->md_status.ptr, 0, 2 * sizeof(unsigned), s));
     try {
-      rebuild_list(h, x.data(), nullptr);
+      rebuild_list(h, x.data(), h->relax_cell_running ? cells.data() : nullptr);
     } catch (const HipError &e) {
       throw HipError(std::string(who) + ": list rebuild after step " + std::to_string(q + 1) + " failed: " + e.what());
     } catch (const std::exception &e) {
@@ -1854,6 +1882,8 @@ int resident_steps(ta_context *h, const char *who, int n_steps, uint32_t want, E
                                " failed: " + e.what());
     }
     if (N) HIP_CHECK(hipMemcpyAsync(h->md_ref.ptr, h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (h->relax_cell_running && F)
+      HIP_CHECK(hipMemcpyAsync(h->md_ref_cells.ptr, h->db.cells, 9 * F * sizeof(double), hipMemcpyDeviceToDevice, s));
     h->md_ref_builds = h->n_list_builds;
     compute_impl(h, want, false, nullptr);
     ++*rebuilds;
@@ -2104,6 +2134,10 @@ int ta_relax_init(ta_handle h, const ta_fire_params *p, const uint8_t *fixed) {
     st.converged = 0;
     st.steps = 0;
     h->relax_state_host.assign(F, st);
+    h->relax_cell_on = false;
+    h->relax_cell_G_host.assign(9 * F, 0.0);
+    for (size_t f = 0; f < F; ++f) h->relax_cell_G_host[9 * f] = h->relax_cell_G_host[9 * f + 4] = h->relax_cell_G_host[9 * f + 8] = 1.0;
+    h->relax_cell_vel_host.assign(9 * F, 0.0);
     h->relax_p = q;
     h->md_chunk = 0;  // (the workgroup layout is planned for this batch by the next run)
     h->md_blk_start_host.clear();
@@ -2122,9 +2156,12 @@ int ta_relax_run(ta_handle h, int32_t max_steps, double fmax, uint32_t want, int
   if (n_rebuilds) *n_rebuilds = 0;
   want |= TA_WANT_ENERGY | TA_WANT_FORCES;
   want &= ~(uint32_t)TA_WANT_REUSE_DESCRIPTORS;
+  const bool cell = h->relax_cell_on;
+  if (cell) want |= TA_WANT_VIRIAL;  // the force on the cell rows
   // a run that fails leaves positions and velocities somewhere on its way and the host's image of the
   // per-frame records behind them: the state is dropped, and only ta_relax_init makes a new one
   h->relax_valid = false;
+  h->relax_cell_running = cell;
   const int rc = guarded(h, [&]() {
     const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
     hipStream_t s = h->stream;
@@ -2141,6 +2178,11 @@ int ta_relax_run(ta_handle h, int32_t max_steps, double fmax, uint32_t want, int
     for (auto &r : st) r.converged = 0, r.steps = 0;
     if (F) HIP_CHECK(hipMemcpy(h->relax_state.ptr, st.data(), F * sizeof(ta::RelaxFrameState), hipMemcpyHostToDevice));
     HIP_CHECK(hipMemset(h->relax_count.ptr, 0, sizeof(int)));
+    if (cell && F) {  // the current G and cell velocity into copy 0, the cells of the resident list next to md_ref
+      HIP_CHECK(hipMemcpy(h->relax_cell_G.ptr, h->relax_cell_G_host.data(), 9 * F * sizeof(double), hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(h->relax_cell_vel.ptr, h->relax_cell_vel_host.data(), 9 * F * sizeof(double), hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(h->md_ref_cells.ptr, h->ref_cells.data(), 9 * F * sizeof(double), hipMemcpyHostToDevice));
+    }
     volatile unsigned *status_host = reinterpret_cast<volatile unsigned *>(h->md_status_host.ptr);
     status_host[0] = status_host[1] = 0u;  // (no launch that writes them is in flight: every run ends with a wait)
     HIP_CHECK(hipMemsetAsync(h->md_status.ptr, 0, 2 * sizeof(unsigned), s));
@@ -2163,12 +2205,27 @@ int ta_relax_run(ta_handle h, int32_t max_steps, double fmax, uint32_t want, int
     a.n_frames = (int)F;
     a.n_blk = (int)n_blk;
     a.chunk = ta::kMdChunk;
+    a.cell = cell ? 1 : 0;
+    a.virial = nullptr, a.cells = nullptr;
+    a.ref_cells = h->md_ref_cells.ptr, a.cell_h0 = h->relax_cell_h0.ptr, a.cell_cf = h->relax_cell_cf.ptr;
+    a.cell_G = h->relax_cell_G.ptr, a.cell_vel = h->relax_cell_vel.ptr, a.cell_fmax2 = h->relax_cell_fmax2.ptr;
+    {
+      const int32_t *m = h->relax_cell_p.mask;  // Voigt xx yy zz yz xz xy
+      const int32_t full[9] = {m[0], m[5], m[4], m[5], m[1], m[3], m[4], m[3], m[2]};
+      for (int c = 0; c < 9; ++c) a.cell_mask[c] = full[c] ? 1.0 : 0.0;
+    }
+    a.pressure = h->relax_cell_p.pressure;
+    a.skin = h->skin;
+    a.r_list = h->rmax + h->skin;
+    a.hydrostatic = h->relax_cell_p.hydrostatic ? 1 : 0;
     int launched = 0;  // launches that ran: the current copy of the state is launched & 1
     auto step = [&](int k, bool drift) {
       // (a rebuild may have moved the batch's arrays: the pointers are taken at every launch)
       a.pos = h->db.pos;
       a.forces = h->db.forces;
       a.atom_start = h->db.atom_start;
+      a.virial = h->db.virial;
+      a.cells = h->db.cells;
       a.seq = (unsigned)k;
       a.drift = drift ? 1 : 0;
       ta::launch_relax_step(a, s);
@@ -2202,8 +2259,39 @@ int ta_relax_run(ta_handle h, int32_t max_steps, double fmax, uint32_t want, int
       if (converged) converged[f] = st[f].converged;
       if (fmax_out) fmax_out[f] = std::sqrt(st[f].fmax2);
     }
+    if (cell && F) {
+      HIP_CHECK(hipMemcpy(h->relax_cell_G_host.data(), h->relax_cell_G.ptr + 9 * (size_t)(launched & 1) * F,
+                          9 * F * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(h->relax_cell_vel_host.data(), h->relax_cell_vel.ptr + 9 * (size_t)(launched & 1) * F,
+                          9 * F * sizeof(double), hipMemcpyDeviceToHost));
+      // The cells moved under a list built for others: one list for the final state, so that ref_pos and
+      // ref_cells (the host's image of the resident geometry) are what ta_update_positions, ta_md_run and a
+      // fixed-cell run take them for. The evaluation is repeated on it; results agree up to summation order.
+      std::vector<double> cells(9 * F);
+      HIP_CHECK(hipMemcpy(cells.data(), h->db.cells, 9 * F * sizeof(double), hipMemcpyDeviceToHost));
+      if (std::memcmp(cells.data(), h->ref_cells.data(), 9 * F * sizeof(double)) != 0) {
+        std::vector<double> x(3 * N);
+        if (N) HIP_CHECK(hipMemcpy(x.data(), h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+        try {
+          rebuild_list(h, x.data(), cells.data());
+        } catch (const HipError &e) {
+          throw HipError(std::string("ta_relax_run: list rebuild for the final cells failed: ") + e.what());
+        } catch (const std::exception &e) {
+          throw std::runtime_error(std::string("ta_relax_run: list rebuild for the final cells failed: ") + e.what());
+        }
+        if (N) HIP_CHECK(hipMemcpyAsync(h->md_ref.ptr, h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToDevice, s));
+        h->md_ref_builds = h->n_list_builds;
+        compute_impl(h, want, false, nullptr);
+        HIP_CHECK(hipStreamSynchronize(s));
+        h->upload_pending = false;
+        ++rebuilds;
+        if (n_rebuilds) *n_rebuilds = rebuilds;
+      }
+    }
   });
+  h->relax_cell_running = false;
   if (rc == TA_OK) h->relax_valid = true;
+  else h->relax_cell_on = false;
   return rc;
 }
 
@@ -2222,6 +2310,80 @@ int ta_relax_get_state(ta_handle h, double *positions, double *velocities, doubl
       if (dt) dt[f] = h->relax_state_host[f].dt;
       if (a) a[f] = h->relax_state_host[f].a;
       if (npos) npos[f] = h->relax_state_host[f].npos;
+    }
+  });
+}
+
+int ta_relax_set_cell(ta_handle h, int on, const ta_relax_cell_params *p) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_relax_set_cell: no resident batch");
+  if (!h->relax_valid) return fail(h, TA_ERR_INVALID, "ta_relax_set_cell called before ta_relax_init");
+  if (!on) {
+    h->relax_cell_on = false;  // (the cells stay as they are)
+    return TA_OK;
+  }
+  ta_relax_cell_params q = {0.0, 0.0, {1, 1, 1, 1, 1, 1}, 0, 0};
+  if (p) q = *p;
+  if (!std::isfinite(q.cell_factor) || q.cell_factor < 0.0)
+    return fail(h, TA_ERR_INVALID, "ta_relax_set_cell: cell_factor must be finite and >= 0");
+  if (!std::isfinite(q.pressure)) return fail(h, TA_ERR_INVALID, "ta_relax_set_cell: pressure must be finite");
+  bool any = false;
+  for (int c = 0; c < 6; ++c) any = any || q.mask[c] != 0;
+  if (!any) return fail(h, TA_ERR_INVALID, "ta_relax_set_cell: mask leaves no component of the cell free");
+  const size_t F = h->keep_natoms.size();
+  std::vector<double> cf(F);
+  for (size_t f = 0; f < F; ++f) {
+    for (int k = 0; k < 3; ++k)
+      if (!h->keep_pbc[3 * f + k])
+        return fail(h, TA_ERR_INVALID, "ta_relax_set_cell: frame " + std::to_string(f) + " is not periodic along all three axes");
+    const double *c = h->ref_cells.data() + 9 * f;
+    const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
+    if (!std::isfinite(det) || !(std::fabs(det) > 0.0))
+      return fail(h, TA_ERR_INVALID, "ta_relax_set_cell: the cell of frame " + std::to_string(f) + " is singular");
+    cf[f] = q.cell_factor > 0.0 ? q.cell_factor : (double)std::max(1, h->keep_natoms[f]);
+  }
+  return guarded(h, [&]() {
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    h->upload_pending = false;
+    h->relax_cell_h0.ensure(9 * F + 1);
+    h->relax_cell_cf.ensure(F + 1);
+    h->relax_cell_G.ensure(2 * 9 * F + 1);
+    h->relax_cell_vel.ensure(2 * 9 * F + 1);
+    h->relax_cell_fmax2.ensure(F + 1);
+    h->md_ref_cells.ensure(9 * F + 1);
+    if (F) {
+      HIP_CHECK(hipMemcpy(h->relax_cell_h0.ptr, h->ref_cells.data(), 9 * F * sizeof(double), hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(h->relax_cell_cf.ptr, cf.data(), F * sizeof(double), hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemset(h->relax_cell_fmax2.ptr, 0, F * sizeof(double)));
+    }
+    h->relax_cell_G_host.assign(9 * F, 0.0);
+    for (size_t f = 0; f < F; ++f) h->relax_cell_G_host[9 * f] = h->relax_cell_G_host[9 * f + 4] = h->relax_cell_G_host[9 * f + 8] = 1.0;
+    h->relax_cell_vel_host.assign(9 * F, 0.0);
+    h->relax_cell_p = q;
+    h->relax_cell_on = true;
+  });
+}
+
+int ta_relax_get_cell(ta_handle h, double *cells, double *deform, double *cell_velocities, double *cell_fmax) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_relax_get_cell: no resident batch");
+  if (!h->relax_valid) return fail(h, TA_ERR_INVALID, "ta_relax_get_cell called before ta_relax_init");
+  return guarded(h, [&]() {
+    const size_t F = h->keep_natoms.size();
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    h->upload_pending = false;
+    if (!F) return;
+    // (between runs ref_cells is the image of the device's cells)
+    if (cells) std::memcpy(cells, h->ref_cells.data(), 9 * F * sizeof(double));
+    if (deform) std::memcpy(deform, h->relax_cell_G_host.data(), 9 * F * sizeof(double));
+    if (cell_velocities) std::memcpy(cell_velocities, h->relax_cell_vel_host.data(), 9 * F * sizeof(double));
+    if (cell_fmax) {
+      if (h->relax_cell_fmax2.ptr) {
+        HIP_CHECK(hipMemcpy(cell_fmax, h->relax_cell_fmax2.ptr, F * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t f = 0; f < F; ++f) cell_fmax[f] = std::sqrt(cell_fmax[f]);
+      } else {
+        for (size_t f = 0; f < F; ++f) cell_fmax[f] = 0.0;
+      }
     }
   });
 }

@@ -35,6 +35,20 @@ struct RelaxLaunch {
   unsigned seq;               // steps of this run before this launch
   int nmin, n_frames, n_blk, chunk;
   int drift;                  // 0: only the convergence test (last launch of a run that used up its steps)
+  // cell mode only (ta_relax_set_cell; the launches' kCell builds): the rows [q_1 .. q_n ; cf G] are relaxed
+  const double *virial;       // [F][9] W of the evaluation before this step
+  double *cells;              // [F][9] db.cells: written by the frame's first workgroup, read by no workgroup
+  const double *ref_cells;    // [F][9] cells the resident list was built for
+  const double *cell_h0;      // [F][9] cells at ta_relax_set_cell
+  const double *cell_cf;      // [F] cell factor
+  double *cell_G;             // [2][F][9] deformation gradient, double-buffered as `state`
+  double *cell_vel;           // [2][F][9] FIRE velocity of the rows cf G, likewise
+  double *cell_fmax2;         // [F] max row |f_cell|^2 of the last evaluation the frame was tested with
+  double cell_mask[9];        // 0 / 1, symmetric
+  double pressure;            // eV / A^3
+  double skin, r_list;        // r_list = max(rcut, acut) + skin
+  int hydrostatic;
+  int cell;                   // 0: the fixed-cell builds run and nothing above is read
 };
 
 // the reduce launch and the step launch of one FIRE step, in this order on `s`

@@ -26,6 +26,20 @@
 // Both launches are predicated on the status word of the MD loop: a drift that finds an atom beyond skin / 2
 // writes its own sequence number + 1 there, still writes valid positions, and every LATER launch returns at
 // once. Atoms of the `fixed` mask have their force read as 0 everywhere and are never written.
+//
+// Cell mode (ta_relax_set_cell; the kCell builds of both launches): ASE's UnitCellFilter. With h0 the cell
+// at ta_relax_set_cell, G a deformation gradient (h = h0 G^T, x_i = q_i G^T), cf the cell factor, p the
+// external pressure and M the mask, the n + 3 rows [q_1 .. q_n ; cf G] are relaxed under the forces
+//     f_i = F_i G,    f_cell = -((W + p V I) G^-T) o M / cf    (hydrostatic: I trace / 3 before the mask)
+// with W the frame virial of the last evaluation and V = |det h|. The reduce launch sums f_i = F_i G over the
+// atoms. In the step launch thread 0 of EVERY workgroup of the frame adds the three cell rows to the frame's
+// sums (the same arithmetic on the same inputs: bitwise the same branch everywhere), and after the branch
+// computes G' = G + dr_cell / cf, h' = h0 G'^T and A = h_ref^-1 h'; the atoms then move as q = x G^-T,
+// q += dr, x = q G'^T (fixed atoms keep q: they move with the cell). G and the cell velocity are kept twice
+// like the FIRE state; the frame's first workgroup alone writes the other copy and the new row of db.cells,
+// which no workgroup of the step launch reads. The list test knows strain: with u_i = x_i - x_ref,i A the
+// list is stale when lim = (skin - (rc + skin) |A - I|_F) / 2 <= 0 or some |u_i|^2 >= lim^2 (every pair
+// vector obeys D_new = D_ref A + u_j - u_i and sigma_min(A) >= 1 - |A - I|_F).
 #include <hip/hip_runtime.h>
 
 #include "ta_device.h"
@@ -47,6 +61,29 @@ __device__ __forceinline__ int relax_frame_of_block(const int32_t *blk_start, in
   return lo;
 }
 
+// o = m^-1 (row-major 3x3); returns det m
+__device__ __forceinline__ double relax_inv3(const double *m, double *o) {
+  const double c0 = m[4] * m[8] - m[5] * m[7], c1 = m[5] * m[6] - m[3] * m[8], c2 = m[3] * m[7] - m[4] * m[6];
+  const double det = m[0] * c0 + m[1] * c1 + m[2] * c2;
+  const double id = 1.0 / det;
+  o[0] = c0 * id, o[1] = (m[2] * m[7] - m[1] * m[8]) * id, o[2] = (m[1] * m[5] - m[2] * m[4]) * id;
+  o[3] = c1 * id, o[4] = (m[0] * m[8] - m[2] * m[6]) * id, o[5] = (m[2] * m[3] - m[0] * m[5]) * id;
+  o[6] = c2 * id, o[7] = (m[1] * m[6] - m[0] * m[7]) * id, o[8] = (m[0] * m[4] - m[1] * m[3]) * id;
+  return det;
+}
+
+// h = h0 G^T (rows are lattice vectors)
+__device__ __forceinline__ void relax_cell_of(const double *h0, const double *G, double *h) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) h[3 * r + c] = h0[3 * r] * G[3 * c] + h0[3 * r + 1] * G[3 * c + 1] + h0[3 * r + 2] * G[3 * c + 2];
+}
+
+// slots of the step launch's LDS block in cell mode
+constexpr int kCellG = 0, kCellGinv = 9, kCellGnew = 18, kCellA = 27, kCellLim2 = 36, kCellWords = 37;
+
+template <bool kCell>
 __global__ __launch_bounds__(kRelaxThreads) void relax_reduce_kernel(RelaxLaunch a) {
   __shared__ double s_wave[4][kRelaxThreads / 64];
   const unsigned mark = *static_cast<volatile unsigned *>(a.status);
@@ -57,10 +94,22 @@ __global__ __launch_bounds__(kRelaxThreads) void relax_reduce_kernel(RelaxLaunch
   const int64_t lo = a.atom_start[f] + (int64_t)((int)blockIdx.x - a.blk_start[f]) * a.chunk;
   const int64_t hi = lo + a.chunk < f_hi ? lo + a.chunk : f_hi;
 
+  double G[9];
+  if constexpr (kCell) {
+    const double *g = a.cell_G + 9 * ((size_t)(a.seq & 1u) * a.n_frames + f);
+#pragma unroll
+    for (int c = 0; c < 9; ++c) G[c] = g[c];
+  }
   double vf = 0.0, ff = 0.0, vv = 0.0, m2 = 0.0;
   for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
     if (a.fixed[i]) continue;
-    const double fx = a.forces[3 * i], fy = a.forces[3 * i + 1], fz = a.forces[3 * i + 2];
+    double fx = a.forces[3 * i], fy = a.forces[3 * i + 1], fz = a.forces[3 * i + 2];
+    if constexpr (kCell) {  // f_i = F_i G
+      const double Fx = fx, Fy = fy, Fz = fz;
+      fx = Fx * G[0] + Fy * G[3] + Fz * G[6];
+      fy = Fx * G[1] + Fy * G[4] + Fz * G[7];
+      fz = Fx * G[2] + Fy * G[5] + Fz * G[8];
+    }
     const double vx = a.vel[3 * i], vy = a.vel[3 * i + 1], vz = a.vel[3 * i + 2];
     const double f2 = fx * fx + fy * fy + fz * fz;
     vf += fx * vx + fy * vy + fz * vz;
@@ -89,8 +138,10 @@ __global__ __launch_bounds__(kRelaxThreads) void relax_reduce_kernel(RelaxLaunch
   }
 }
 
+template <bool kCell>
 __global__ __launch_bounds__(kRelaxThreads) void relax_step_kernel(RelaxLaunch a) {
   __shared__ double s_sum[4];
+  __shared__ double s_cell[kCell ? kCellWords : 1];  // (unused, and dropped, in the fixed-cell build)
   // (0, or the value this very launch writes, or the mark of an earlier launch: the same branch in every thread)
   const unsigned mark = *static_cast<volatile unsigned *>(a.status);
   if (mark != 0u && mark <= a.seq) return;
@@ -99,8 +150,27 @@ __global__ __launch_bounds__(kRelaxThreads) void relax_step_kernel(RelaxLaunch a
   const bool writer = (int)blockIdx.x == blk0 && threadIdx.x == 0;  // of the frame's record
   RelaxFrameState st = a.state[(size_t)(a.seq & 1u) * a.n_frames + f];
   RelaxFrameState *next = &a.state[(size_t)((a.seq + 1u) & 1u) * a.n_frames + f];
+  // cell mode: thread 0 of every workgroup of the frame holds the same G, cell velocity and cell force
+  double G[9], vc[9], fc[9], h0[9], cf = 1.0;
+  double *G_next = nullptr, *vc_next = nullptr;
+  if constexpr (kCell) {
+    if (threadIdx.x == 0) {
+      const size_t cur = 9 * ((size_t)(a.seq & 1u) * a.n_frames + f);
+      const size_t nxt = 9 * ((size_t)((a.seq + 1u) & 1u) * a.n_frames + f);
+#pragma unroll
+      for (int c = 0; c < 9; ++c) G[c] = a.cell_G[cur + c], vc[c] = a.cell_vel[cur + c];
+      G_next = a.cell_G + nxt;
+      vc_next = a.cell_vel + nxt;
+    }
+  }
   if (st.converged) {
-    if (writer) *next = st;
+    if (writer) {
+      *next = st;
+      if constexpr (kCell) {
+#pragma unroll
+        for (int c = 0; c < 9; ++c) G_next[c] = G[c], vc_next[c] = vc[c];
+      }
+    }
     return;
   }
   if (threadIdx.x < 64) {
@@ -118,6 +188,49 @@ __global__ __launch_bounds__(kRelaxThreads) void relax_step_kernel(RelaxLaunch a
     ff = wave_sum(ff);
     vv = wave_sum(vv);
     m2 = wave_max(m2);
+    if constexpr (kCell) {
+      if (threadIdx.x == 0) {
+        // the three cell rows: f_cell = -((W + p V I) G^-T) o M / cf, from the virial of the last evaluation
+        double Gi[9], h[9], W[9];
+        relax_inv3(G, Gi);
+        cf = a.cell_cf[f];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) h0[c] = a.cell_h0[9 * (size_t)f + c], W[c] = a.virial[9 * (size_t)f + c];
+        relax_cell_of(h0, G, h);
+        const double pV = a.pressure * fabs(h[0] * (h[4] * h[8] - h[5] * h[7]) - h[1] * (h[3] * h[8] - h[5] * h[6]) +
+                                            h[2] * (h[3] * h[7] - h[4] * h[6]));
+        W[0] += pV, W[4] += pV, W[8] += pV;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+            fc[3 * r + c] = -(W[3 * r] * Gi[3 * c] + W[3 * r + 1] * Gi[3 * c + 1] + W[3 * r + 2] * Gi[3 * c + 2]);
+        if (a.hydrostatic) {
+          const double t = (fc[0] + fc[4] + fc[8]) / 3.0;
+#pragma unroll
+          for (int c = 0; c < 9; ++c) fc[c] = (c == 0 || c == 4 || c == 8) ? t : 0.0;
+        }
+        double c2 = 0.0;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          double row = 0.0;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const double v = fc[3 * r + c] * a.cell_mask[3 * r + c] / cf;
+            fc[3 * r + c] = v;
+            vf += v * vc[3 * r + c];
+            vv += vc[3 * r + c] * vc[3 * r + c];
+            row += v * v;
+          }
+          ff += row;
+          m2 = fmax(m2, row);
+          c2 = fmax(c2, row);
+        }
+        if (writer) a.cell_fmax2[f] = c2;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) s_cell[kCellG + c] = G[c], s_cell[kCellGinv + c] = Gi[c];
+      }
+    }
     if (threadIdx.x == 0) s_sum[0] = vf, s_sum[1] = ff, s_sum[2] = vv, s_sum[3] = m2;
   }
   __syncthreads();
@@ -130,6 +243,10 @@ __global__ __launch_bounds__(kRelaxThreads) void relax_step_kernel(RelaxLaunch a
       st.converged = converged ? 1 : 0;
       st.fmax2 = ff == ff ? m2 : ff;
       *next = st;
+      if constexpr (kCell) {
+#pragma unroll
+        for (int c = 0; c < 9; ++c) G_next[c] = G[c], vc_next[c] = vc[c];
+      }
       if (converged && atomicAdd(a.n_converged, 1) == a.n_frames - 1)
         *static_cast<volatile unsigned *>(a.status_host + 1) = a.seq + 1u;
     }
@@ -167,6 +284,79 @@ __global__ __launch_bounds__(kRelaxThreads) void relax_step_kernel(RelaxLaunch a
   const int64_t lo = a.atom_start[f] + (int64_t)((int)blockIdx.x - blk0) * a.chunk;
   const int64_t hi = lo + a.chunk < f_hi ? lo + a.chunk : f_hi;
   int stale = 0;
+  if constexpr (kCell) {
+    if (threadIdx.x == 0) {
+      // G' = G + dr_cell / cf, h' = h0 G'^T, A = h_ref^-1 h' and the list's limit under this strain
+      double Gn[9], hn[9], hr[9], hri[9];
+#pragma unroll
+      for (int c = 0; c < 9; ++c) {
+        const double v = alpha * vc[c] + beta * fc[c];
+        double d = dt * v;
+        if (clamp) d = d * a.maxstep / dr;
+        vc[c] = v;
+        Gn[c] = G[c] + d / cf;
+        hr[c] = a.ref_cells[9 * (size_t)f + c];
+      }
+      relax_cell_of(h0, Gn, hn);
+      relax_inv3(hr, hri);
+      double n2 = 0.0;
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const double v = hri[3 * r] * hn[c] + hri[3 * r + 1] * hn[3 + c] + hri[3 * r + 2] * hn[6 + c];
+          s_cell[kCellA + 3 * r + c] = v;
+          const double e = v - (r == c ? 1.0 : 0.0);
+          n2 += e * e;
+        }
+      const double lim = 0.5 * (a.skin - a.r_list * sqrt(n2));
+      s_cell[kCellLim2] = lim > 0.0 ? lim * lim : -1.0;  // (a NaN strain: -1, every drift is stale)
+#pragma unroll
+      for (int c = 0; c < 9; ++c) s_cell[kCellGnew + c] = Gn[c];
+      if (writer) {
+#pragma unroll
+        for (int c = 0; c < 9; ++c) G_next[c] = Gn[c], vc_next[c] = vc[c], a.cells[9 * (size_t)f + c] = hn[c];
+      }
+    }
+    __syncthreads();
+    double Gi[9], Gn[9], A[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c)
+      G[c] = s_cell[kCellG + c], Gi[c] = s_cell[kCellGinv + c], Gn[c] = s_cell[kCellGnew + c], A[c] = s_cell[kCellA + c];
+    const double lim2 = s_cell[kCellLim2];
+    for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+      const double x[3] = {a.pos[3 * i], a.pos[3 * i + 1], a.pos[3 * i + 2]};
+      double q[3];  // q = x G^-T
+#pragma unroll
+      for (int c = 0; c < 3; ++c) q[c] = Gi[3 * c] * x[0] + Gi[3 * c + 1] * x[1] + Gi[3 * c + 2] * x[2];
+      if (!a.fixed[i]) {
+        const double F[3] = {a.forces[3 * i], a.forces[3 * i + 1], a.forces[3 * i + 2]};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const double v = alpha * a.vel[3 * i + c] + beta * (F[0] * G[c] + F[1] * G[3 + c] + F[2] * G[6 + c]);
+          a.vel[3 * i + c] = v;
+          double d = dt * v;
+          if (clamp) d = d * a.maxstep / dr;
+          q[c] += d;
+        }
+      }
+      double d2 = 0.0;  // x' = q G'^T (a fixed atom too: it moves with the cell), u = x' - x_ref A
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const double xn = Gn[3 * c] * q[0] + Gn[3 * c + 1] * q[1] + Gn[3 * c + 2] * q[2];
+        a.pos[3 * i + c] = xn;
+        const double u = xn - (a.ref[3 * i] * A[c] + a.ref[3 * i + 1] * A[3 + c] + a.ref[3 * i + 2] * A[6 + c]);
+        d2 += u * u;
+      }
+      stale |= !(d2 < lim2) ? 1 : 0;  // (a NaN fails the comparison too and is reported by the rebuild)
+    }
+    if (threadIdx.x == 0 && !(lim2 > 0.0)) stale = 1;  // (a frame without atoms in this workgroup strains the list too)
+    if (__syncthreads_or(stale) && threadIdx.x == 0) {
+      *static_cast<volatile unsigned *>(a.status) = a.seq + 1u;
+      *static_cast<volatile unsigned *>(a.status_host) = a.seq + 1u;
+    }
+    return;
+  }
   for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
     double x[3] = {a.pos[3 * i], a.pos[3 * i + 1], a.pos[3 * i + 2]};
     if (!a.fixed[i]) {
@@ -194,8 +384,13 @@ __global__ __launch_bounds__(kRelaxThreads) void relax_step_kernel(RelaxLaunch a
 
 void launch_relax_step(const RelaxLaunch &a, hipStream_t s) {
   if (a.n_blk <= 0) return;
-  hipLaunchKernelGGL(relax_reduce_kernel, dim3((unsigned)a.n_blk), dim3(kRelaxThreads), 0, s, a);
-  hipLaunchKernelGGL(relax_step_kernel, dim3((unsigned)a.n_blk), dim3(kRelaxThreads), 0, s, a);
+  if (a.cell) {
+    hipLaunchKernelGGL(relax_reduce_kernel<true>, dim3((unsigned)a.n_blk), dim3(kRelaxThreads), 0, s, a);
+    hipLaunchKernelGGL(relax_step_kernel<true>, dim3((unsigned)a.n_blk), dim3(kRelaxThreads), 0, s, a);
+    return;
+  }
+  hipLaunchKernelGGL(relax_reduce_kernel<false>, dim3((unsigned)a.n_blk), dim3(kRelaxThreads), 0, s, a);
+  hipLaunchKernelGGL(relax_step_kernel<false>, dim3((unsigned)a.n_blk), dim3(kRelaxThreads), 0, s, a);
 }
 
 }  // namespace ta

@@ -34,6 +34,7 @@ class Engine:
         self.info = None
         self._frames = None
         self._volumes = None
+        self._relax_cell = False   # `relax_set_cell` is on: `relax_run` moves the cells
         self._md_sig = None   # (n, numbers, pbc) of the single resident frame of `evaluate_md`
         self._md_cell = None
         self.batch_generation = 0  # bumped whenever the resident batch or its coordinates change
@@ -78,6 +79,7 @@ class Engine:
         self._frames = frames
         self.batch_generation += 1  # what is resident changed (train.Trainer's shortcut checks this)
         self._md_sig = None
+        self._relax_cell = False
         self._volumes = np.array([abs(np.linalg.det(f.cell)) for f in frames])
         self._natoms = np.array([len(f.species) for f in frames], dtype=np.int64)
         self._numbers = np.concatenate([np.asarray(a.numbers, dtype=np.int64) for a in atoms_list]) \
@@ -350,6 +352,48 @@ class Engine:
             mask = np.ascontiguousarray(fixed_atoms_mask(fixed, N, "relax_init"), dtype=np.uint8)
             mptr = mask.ctypes.data_as(C.POINTER(C.c_uint8))
         self._check(self._lib.ta_relax_init(self._handle, C.byref(fp), mptr))
+        self._relax_cell = False
+
+    def relax_set_cell(self, on=True, cell_factor=None, pressure=0.0, mask=None, hydrostatic=False):
+        """Relax the cells together with the atoms in `relax_run` (`ta_relax_set_cell`; ASE's `UnitCellFilter`):
+        the cells now resident become h0, the deformation gradient G = I. `cell_factor`: None = the atoms of
+        each frame; `pressure`: external scalar pressure in eV / A^3; `mask`: 6 Voigt entries (xx, yy, zz, yz,
+        xz, xy) or a symmetric 3 x 3 array, non-zero = free (None: all free); `hydrostatic`: only the volume
+        changes. `on=False` returns to fixed cells and keeps the current ones. Needs `relax_init`, which
+        switches the option off again."""
+        if self.info is None:
+            raise ValueError("relax_set_cell: no resident batch (call set_frames first)")
+        if not on:
+            self._check(self._lib.ta_relax_set_cell(self._handle, 0, None))
+            self._relax_cell = False
+            return
+        if mask is None:
+            m = np.ones(6, dtype=np.int64)
+        else:
+            m = np.asarray(mask)
+            if m.shape == (3, 3):
+                if not np.array_equal(m != 0, (m != 0).T):
+                    raise ValueError("relax_set_cell: a 3 x 3 mask must be symmetric")
+                m = np.array([m[0, 0], m[1, 1], m[2, 2], m[1, 2], m[0, 2], m[0, 1]])
+            if m.shape != (6,):
+                raise ValueError("relax_set_cell: mask must have 6 Voigt entries or be a 3 x 3 array")
+            m = (m != 0).astype(np.int64)
+        cp = _lib.RelaxCellParams(0.0 if cell_factor is None else float(cell_factor), float(pressure),
+                                  (C.c_int32 * 6)(*[int(v) for v in m]), 1 if hydrostatic else 0, 0)
+        self._check(self._lib.ta_relax_set_cell(self._handle, 1, C.byref(cp)))
+        self._relax_cell = True
+
+    def relax_cell_state(self) -> dict:
+        """cells (= h0 G^T), deform (G), cell_velocities [n_frames, 3, 3] and cell_fmax [n_frames] (largest row
+        of the generalised cell force at the last state a cell run tested) of the relaxation
+        (`ta_relax_get_cell`)."""
+        if self.info is None:
+            raise ValueError("relax_cell_state: no resident batch (call set_frames first)")
+        F = int(self.info.n_frames)
+        cells, G, v, fm = np.empty((F, 3, 3)), np.empty((F, 3, 3)), np.empty((F, 3, 3)), np.empty(F)
+        self._check(self._lib.ta_relax_get_cell(self._handle, _lib.as_dp(cells), _lib.as_dp(G), _lib.as_dp(v),
+                                                _lib.as_dp(fm)))
+        return {"cells": cells, "deform": G, "cell_velocities": v, "cell_fmax": fm}
 
     def relax_run(self, max_steps: int, fmax: float, want: int = None) -> dict:
         """FIRE steps of the resident batch on the device (`ta_relax_run`) until every frame has
@@ -371,13 +415,20 @@ class Engine:
         rc = self._lib.ta_relax_run(self._handle, max_steps, float(fmax), int(want), _lib.as_ip(steps),
                                     _lib.as_ip(conv), _lib.as_dp(fm), C.byref(rebuilds))
         self.batch_generation += 1  # the coordinates changed (also when the run ended early)
+        if rc != _lib.TA_OK:
+            self._relax_cell = False   # (a failed run drops the relaxation state, the cell option with it)
         self._check(rc)
+        null = C.POINTER(C.c_double)()
         if rebuilds.value:
             n_pairs, n_triples, nnl = C.c_int64(0), C.c_int64(0), C.c_int32(0)
             self._check(self._lib.ta_list_sizes(self._handle, C.byref(n_pairs), C.byref(n_triples), C.byref(nnl)))
             self.info.n_pairs, self.info.n_triples, self.info.nnl_max = n_pairs.value, n_triples.value, nnl.value
+        if self._relax_cell:   # the cells moved on the device: stress and pressure follow them
+            cells = np.empty((F, 3, 3))
+            self._check(self._lib.ta_relax_get_cell(self._handle, _lib.as_dp(cells), null, null, null))
+            self._volumes = np.abs(np.linalg.det(cells))
+            self._md_sig = None
         energy = np.empty(F)
-        null = C.POINTER(C.c_double)()
         self._check(self._lib.ta_get_results(self._handle, _lib.as_dp(energy), null, null, null, null))
         return {"steps": steps.astype(np.int64), "converged": conv.astype(bool), "fmax": fm, "energy": energy,
                 "n_rebuilds": int(rebuilds.value)}

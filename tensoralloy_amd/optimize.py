@@ -6,7 +6,8 @@ The optimiser is ASE's `FIRE` with `downhill_check=False` and the same parameter
 structure of a batch is relaxed on its own: it has its own time step and mixing factor, and it stops moving
 when its largest force drops below `fmax` while the others go on. Converged structures stay in the batch
 and are still evaluated, so a run costs (steps of the slowest structure) x (one evaluation of the batch).
-Cells stay fixed.
+Cells stay fixed unless `cell=True`: then the cell of every structure is relaxed with its atoms as ASE's
+`UnitCellFilter` does it (`Engine.relax_set_cell`), to zero stress or to the pressure `scalar_pressure`.
 """
 from __future__ import annotations
 
@@ -42,11 +43,19 @@ class DeviceFIRE:
     fixed                : boolean mask or list of indices over the concatenated atoms: these atoms do not
                            move and their forces do not count towards convergence (ASE's `FixAtoms`)
     dt, maxstep, dtmax, Nmin, finc, fdec, astart, fa : as ASE's `FIRE`
+    cell                 : relax the cells too (ASE's `UnitCellFilter`); `fmax` then also bounds the rows of the
+                           generalised cell force, and fixed atoms move affinely with the cell
+    mask, scalar_pressure, hydrostatic_strain, cell_factor : as ASE's `UnitCellFilter` (mask: 6 Voigt entries
+                           xx, yy, zz, yz, xz, xy or 3 x 3; pressure in eV / A^3; cell_factor None = atoms of
+                           the structure); only with `cell=True`
     """
 
     def __init__(self, engine_or_calculator, atoms_or_list, fixed=None, dt=0.1, maxstep=0.2, dtmax=1.0, Nmin=5,
-                 finc=1.1, fdec=0.5, astart=0.1, fa=0.99):
+                 finc=1.1, fdec=0.5, astart=0.1, fa=0.99, cell=False, mask=None, scalar_pressure=0.0,
+                 hydrostatic_strain=False, cell_factor=None):
         _check_params(dt, maxstep, dtmax, Nmin, finc, fdec, astart, fa)
+        if not cell and (mask is not None or scalar_pressure != 0.0 or hydrostatic_strain or cell_factor is not None):
+            raise ValueError("DeviceFIRE: mask, scalar_pressure, hydrostatic_strain and cell_factor need cell=True")
         self._single = not isinstance(atoms_or_list, (list, tuple))
         self.atoms_list = [atoms_or_list] if self._single else list(atoms_or_list)
         if not self.atoms_list:
@@ -72,6 +81,10 @@ class DeviceFIRE:
         engine.set_frames(self.atoms_list)
         engine.relax_init(fixed=fixed, dt=dt, dtmax=dtmax, maxstep=maxstep, finc=finc, fdec=fdec, astart=astart,
                           fa=fa, nmin=int(Nmin))
+        self.cell = bool(cell)
+        if self.cell:
+            engine.relax_set_cell(True, cell_factor=cell_factor, pressure=scalar_pressure, mask=mask,
+                                  hydrostatic=hydrostatic_strain)
         self._refresh(engine.relax_run(0, np.finfo(np.float64).tiny))   # energy and forces of the start
 
     def attach(self, fn, interval=1):
@@ -88,6 +101,9 @@ class DeviceFIRE:
         for atoms, n in zip(self.atoms_list, self._natoms):
             atoms.positions[:] = x[a:a + n]
             a += n
+        if self.cell:
+            for atoms, h in zip(self.atoms_list, self.engine.relax_cell_state()["cells"]):
+                atoms.set_cell(h, scale_atoms=False)
         if self._calc is not None:  # what the calculator cached belongs to other coordinates
             self._calc.reset()
             self._calc._forces_local = None
@@ -121,6 +137,15 @@ class DeviceFIRE:
 
     def get_potential_energy(self):
         return float(self.energy[0]) if self._single else self.energy.copy()
+
+    def get_stress(self):
+        """Stress W / V of the last state in Voigt order (xx, yy, zz, yz, xz, xy), eV / A^3: [6] for one
+        structure, [n, 6] for a list."""
+        from . import _lib
+        w = self.engine.fetch(_lib.TA_WANT_ENERGY | _lib.TA_WANT_FORCES | _lib.TA_WANT_VIRIAL)["virial"]
+        s = w / self.engine._volumes[:, None, None]
+        voigt = np.stack([s[:, 0, 0], s[:, 1, 1], s[:, 2, 2], s[:, 1, 2], s[:, 0, 2], s[:, 0, 1]], axis=1)
+        return voigt[0] if self._single else voigt
 
     def get_forces(self):
         """Forces [n_atoms, 3] of the last state (all structures concatenated), fixed atoms' set to 0."""
