@@ -731,6 +731,34 @@ int ta_mlp_launch_info(ta_handle h, int64_t *info /*[8]*/);
  * (centre, neighbour, shift[3]) in the library's order. Arrays sized n_pairs. */
 int ta_get_pairs(ta_handle h, int32_t *i, int32_t *j, int32_t *shift /*[n][3]*/);
 
+/* debugging / parity: the whole neighbour list as the kernels read it (read-only; changes no state).
+ * Two views: TA_LIST_RESIDENT is the list that was built (under a Verlet skin, the skin list);
+ * TA_LIST_KERNEL is the list the next evaluation runs on: the exact list extracted from the skin list
+ * where the model's kernels take one (second-generation symmetry-function kernels, plain EAM), else the
+ * resident list again.
+ *   ta_list_info  info[0] atoms, [1] elements, [2] n_slots: length of the pair arrays (the exact list is
+ *                 compacted in place, group by group of 16 centres, so it has the skin list's slots and
+ *                 leaves some unused), [3] n_blk: runs of the angular kernels' workgroup packing (0:
+ *                 none), [4] cap: pair records one such workgroup stages, [5] builder of the resident
+ *                 list: 0 host, 1 one-pass, 2 two-pass, [6] 1 when this view is an exact list extracted
+ *                 from a skin list, [7] 1 when its reverse index is the lookup through the skin list
+ *                 (no array of its own on the device).
+ *   ta_get_list   waits for the stream and copies to the host; null pointers are skipped. Centre i owns
+ *                 the slots [pair_start[i], pair_stop[i]); pair_stop[i] = pair_start[i + 1] where the
+ *                 device keeps no stops. pair_start[atoms] is the end of the resident list in both views.
+ *                 seg_start[i (elements + 1) + s] is the first slot of centre i whose neighbour is of
+ *                 element s; its closing entry [atoms (elements + 1)] is read from the device where a
+ *                 device builder made the resident list, else it is the last centre's stop.
+ *                 pair_rev[p] is the slot of the reverse pair (j -> i, -S); where the device looks it up
+ *                 (info[7]) the same lookup is made here for the slots a centre owns, -1 elsewhere.
+ *                 blk_center[b] is the first centre of run b, blk_center[n_blk] closes the last run; not
+ *                 written when n_blk = 0. Slots no centre owns hold no defined values. */
+enum { TA_LIST_RESIDENT = 0, TA_LIST_KERNEL = 1 };
+int ta_list_info(ta_handle h, int32_t which, int64_t *info /*[8]*/);
+int ta_get_list(ta_handle h, int32_t which, int32_t *pair_start /*[N+1]*/, int32_t *pair_stop /*[N]*/,
+                int32_t *seg_start /*[N*(nel+1)+1]*/, int32_t *pair_i, int32_t *pair_j,
+                int32_t *pair_shift /*[n_slots][3]*/, int32_t *pair_rev, int32_t *blk_center /*[n_blk+1]*/);
+
 #ifdef __cplusplus
 }
 #endif

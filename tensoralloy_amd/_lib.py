@@ -38,6 +38,8 @@ TA_MLP_FAMILY = {0: "none", 1: "tile", 2: "tile_all", 3: "wave", 4: "wave_all", 
 TA_MLP_DA = {0: "registers", 1: "lds", 2: "global"}
 # ta_model_desc.finite_temperature: bit 0 = temperature-dependent, bit 1 = Sommerfeld, bits 8-15 = H activation
 TA_TD_ON, TA_TD_SOMMERFELD, TA_TD_ACT_SHIFT = 1, 2, 8
+TA_LIST_VIEW = {"resident": 0, "kernel": 1}  # ta_list_info / ta_get_list
+TA_LIST_BUILDER = {0: "host", 1: "one_pass", 2: "two_pass"}
 TA_ABI_VERSION = 5  # include/tensoralloy_amd.h: TA_ABI_VERSION
 KERNEL_SLOTS = ["pair_geometry", "g4_forward", "descriptor_reduce", "mlp", "backward",
                 "force_gather", "frame_reduce", "eam", "neighbor_update", "grap_forward"]
@@ -59,6 +61,7 @@ EXPORTED_SYMBOLS = [
     "ta_md_set_langevin", "ta_md_noise",
     "ta_relax_init", "ta_relax_run", "ta_relax_get_state",
     "ta_relax_set_cell", "ta_relax_get_cell",
+    "ta_list_info", "ta_get_list",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -237,6 +240,8 @@ def load():
     lib.ta_update_constants.argtypes = [H, _dp, C.c_int64]
     lib.ta_constant_gradient.argtypes = [H, _dp, _dp, _dp, _dp, C.c_int64]
     lib.ta_get_pairs.argtypes = [H, _ip, _ip, _ip]
+    lib.ta_list_info.argtypes = [H, C.c_int32, C.POINTER(C.c_int64)]
+    lib.ta_get_list.argtypes = [H, C.c_int32, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _ip]
     lib.ta_neighbor_list.argtypes = [C.POINTER(Frame), C.c_int32, C.c_double,
                                      C.POINTER(C.c_int64), C.POINTER(_ip), C.POINTER(_ip),
                                      C.POINTER(_ip), C.POINTER(_ip)]

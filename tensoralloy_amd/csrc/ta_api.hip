@@ -273,6 +273,7 @@ struct ta_context {
   DevBuf<char> inbuf;
   DevBuf<double> results;
   size_t o_blk = 0;  // byte offset of blk_center in the packed input
+  int res_n_blk = 0;  // runs of the resident list's packing (db.n_blk is the exact list's while `filtered`)
   DevBuf<double> rec, part4, G, dEdG, g, wat, bpart, fown, benergy, mlp_scratch;
   DevBuf<double> td_T, td_u, td_s;  // electron temperature per frame; U and S per atom
   DevBuf<unsigned long long> masks;
@@ -1467,6 +1468,8 @@ void set_frames_impl(ta_context *h, int32_t n_frames, const ta_frame *frames, ta
       blk[nb++] = (int32_t)N;
     }
     h->db.n_blk = nb ? nb - 1 : 0;
+    h->res_n_blk = h->db.n_blk;
+    h->o_blk = o_blk;
     ensure_job_lists(h, (size_t)h->db.n_blk);
     if (nb) {
       if (list_done)  // a kernel on the compute stream reads the page-locked buffer: no DMA hand-over
@@ -3500,6 +3503,86 @@ int ta_get_pairs(ta_handle h, int32_t *i, int32_t *j, int32_t *shift) {
   if (j) std::memcpy(j, h->hp.pair_j.data(), P * sizeof(int32_t));
   if (shift) std::memcpy(shift, h->hp.pair_shift.data(), 3 * P * sizeof(int32_t));
   return TA_OK;
+}
+
+// which == TA_LIST_KERNEL on a skin-filtered batch: the exact list (ex_* arrays); else the resident one
+static bool list_view_is_exact(const ta_context *h, int32_t which) { return which == TA_LIST_KERNEL && h->filtered; }
+
+int ta_list_info(ta_handle h, int32_t which, int64_t *info) {
+  if (!h || !info) return fail(h, TA_ERR_INVALID, "null argument");
+  if (which != TA_LIST_RESIDENT && which != TA_LIST_KERNEL) return fail(h, TA_ERR_INVALID, "ta_list_info: unknown view");
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "no resident batch");
+  const bool exact = list_view_is_exact(h, which);
+  info[0] = h->hp.n_atoms;
+  info[1] = h->n_elements;
+  info[2] = h->hp.n_pairs;  // the exact list is compacted in place: same slots, some unused
+  info[3] = exact ? (h->kind == TA_MODEL_SF_MLP ? h->db.n_blk : 0) : h->res_n_blk;
+  info[4] = h->db.cap;
+  info[5] = h->pairs_on_device ? (h->nl_sorted ? 1 : 2) : 0;
+  info[6] = exact ? 1 : 0;
+  info[7] = exact && h->db.slot_q ? 1 : 0;
+  return TA_OK;
+}
+
+int ta_get_list(ta_handle h, int32_t which, int32_t *pair_start, int32_t *pair_stop, int32_t *seg_start,
+                int32_t *pair_i, int32_t *pair_j, int32_t *pair_shift, int32_t *pair_rev, int32_t *blk_center) {
+  if (!h) return TA_ERR_INVALID;
+  if (which != TA_LIST_RESIDENT && which != TA_LIST_KERNEL) return fail(h, TA_ERR_INVALID, "ta_get_list: unknown view");
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "no resident batch");
+  return guarded(h, [&]() {
+    const bool exact = list_view_is_exact(h, which);
+    const size_t N = (size_t)h->hp.n_atoms, P = (size_t)h->hp.n_pairs, nseg = N * (size_t)(h->n_elements + 1);
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    auto get = [&](int32_t *dst, const int32_t *src, size_t n) {
+      if (dst && n) HIP_CHECK(hipMemcpy(dst, src, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    };
+    // starts and stops are needed here as well (closing entries, the indirect reverse index)
+    std::vector<int32_t> start(N + 1, 0), stop(N, 0);
+    get(start.data(), exact ? h->ex_pair_start.ptr : h->pair_start.ptr, exact ? N : N + 1);
+    if (exact) {
+      start[N] = (int32_t)P;  // where a further group would begin: the end of the skin list
+      get(stop.data(), h->ex_pair_stop.ptr, N);
+    } else {
+      for (size_t i = 0; i < N; ++i) stop[i] = start[i + 1];
+    }
+    if (pair_start) std::memcpy(pair_start, start.data(), (N + 1) * sizeof(int32_t));
+    if (pair_stop && N) std::memcpy(pair_stop, stop.data(), N * sizeof(int32_t));
+    if (seg_start) {
+      // the closing entry: the device builders write one, read as it stands; the host builder and the filter
+      // keep none, there it is the last centre's stop
+      const bool dev_close = !exact && h->pairs_on_device && N;
+      get(seg_start, exact ? h->ex_seg_start.ptr : h->seg_start.ptr, nseg + (dev_close ? 1 : 0));
+      if (!dev_close) seg_start[nseg] = N ? stop[N - 1] : 0;
+    }
+    get(pair_i, exact ? h->ex_pair_i.ptr : h->pair_i.ptr, P);
+    get(pair_j, exact ? h->ex_pair_j.ptr : h->pair_j.ptr, P);
+    get(pair_shift, exact ? h->ex_pair_shift.ptr : h->pair_shift.ptr, 3 * P);
+    if (pair_rev && P) {
+      if (exact && h->db.slot_q) {
+        // pair_rev_of (ta_device.h) on the host, for the slots some centre owns
+        std::vector<int32_t> slot_q(P), rev_super(P), rev_map(P);
+        get(slot_q.data(), h->db.slot_q, P);
+        get(rev_super.data(), h->db.rev_super, P);
+        get(rev_map.data(), h->db.rev_map, P);
+        for (size_t p = 0; p < P; ++p) pair_rev[p] = -1;
+        for (size_t i = 0; i < N; ++i)
+          for (int32_t p = start[i]; p < stop[i]; ++p) {
+            const int32_t q = (p >= 0 && (size_t)p < P) ? slot_q[p] : -1;
+            const int32_t r = (q >= 0 && (size_t)q < P) ? rev_super[q] : -1;
+            if (p >= 0 && (size_t)p < P) pair_rev[p] = (r >= 0 && (size_t)r < P) ? rev_map[r] : -1;
+          }
+      } else {
+        get(pair_rev, exact ? h->ex_pair_rev.ptr : h->pair_rev.ptr, P);
+      }
+    }
+    if (blk_center) {
+      if (exact) {
+        if (h->kind == TA_MODEL_SF_MLP) get(blk_center, h->ex_blk.ptr, (size_t)h->db.n_blk + 1);
+      } else if (h->res_n_blk > 0) {
+        get(blk_center, reinterpret_cast<const int32_t *>(h->inbuf.ptr + h->o_blk), (size_t)h->res_n_blk + 1);
+      }
+    }
+  });
 }
 
 }  // extern "C"

@@ -838,3 +838,27 @@ class Engine:
         s = np.zeros((max(P, 1), 3), dtype=np.int32)
         self._check(self._lib.ta_get_pairs(self._handle, _lib.as_ip(i), _lib.as_ip(j), _lib.as_ip(s)))
         return i[:P], j[:P], s[:P]
+
+    def list_layout(self, which="resident") -> dict:
+        """The neighbour list as the kernels read it (`ta_list_info`, `ta_get_list`; debugging / parity).
+        `which`: "resident", the list that was built (under a skin the skin list), or "kernel", the list the
+        next evaluation runs on (the exact list where one is extracted, else the resident one). Returns the
+        `info` dict (atoms, elements, n_slots, n_blk, cap, builder: host / one_pass / two_pass, filtered,
+        rev_indirect) and the arrays pair_start [N + 1], pair_stop [N], seg_start [N, elements + 1] (and its
+        closing entry `seg_close`), pair_i, pair_j, pair_shift [n_slots, 3], pair_rev and blk_center [n_blk + 1]
+        (None without run packing)."""
+        view = _lib.TA_LIST_VIEW[which]
+        v = (C.c_int64 * 8)()
+        self._check(self._lib.ta_list_info(self._handle, view, v))
+        info = {"atoms": int(v[0]), "elements": int(v[1]), "n_slots": int(v[2]), "n_blk": int(v[3]), "cap": int(v[4]),
+                "builder": _lib.TA_LIST_BUILDER[int(v[5])], "filtered": bool(v[6]), "rev_indirect": bool(v[7])}
+        N, nel, P, nb = info["atoms"], info["elements"], info["n_slots"], info["n_blk"]
+        z = lambda *shape: np.zeros(shape, dtype=np.int32)
+        start, stop, seg = z(N + 1), z(max(N, 1)), z(N * (nel + 1) + 1)
+        pi, pj, ps, rev, blk = z(max(P, 1)), z(max(P, 1)), z(max(P, 1), 3), z(max(P, 1)), z(nb + 1)
+        self._check(self._lib.ta_get_list(self._handle, view, _lib.as_ip(start), _lib.as_ip(stop), _lib.as_ip(seg),
+                                          _lib.as_ip(pi), _lib.as_ip(pj), _lib.as_ip(ps), _lib.as_ip(rev),
+                                          _lib.as_ip(blk)))
+        return {"info": info, "pair_start": start, "pair_stop": stop[:N], "seg_start": seg[:N * (nel + 1)].reshape(N, nel + 1),
+                "seg_close": int(seg[-1]), "pair_i": pi[:P], "pair_j": pj[:P], "pair_shift": ps[:P], "pair_rev": rev[:P],
+                "blk_center": blk if nb > 0 else None}

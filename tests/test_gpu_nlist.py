@@ -127,6 +127,13 @@ def test_small_cells_self_images_and_fallback(lib):
     mixed = [fcc(rep=(1, 1, 2), seed=4), fcc(rep=(3, 3, 3), seed=5), c1[0]]
     info, dev = _device_pairs(nn, mixed, expect_device=True)
     assert np.array_equal(dev, _oracle_pairs(mixed, 6.5))
+    # the fallback: a cell with zero lattice rows (a molecule without a box, pbc off) cannot be binned on
+    # the device, and a batch that holds one is built on the host
+    from tests.helpers import RawCellAtoms
+    molecule = RawCellAtoms(symbols=["Ni"] * 12, positions=rng.rand(12, 3) * 8.0, cell=np.zeros((3, 3)), pbc=False)
+    for batch in ([molecule], [fcc(rep=(3, 3, 3), seed=5), molecule]):
+        info, dev = _device_pairs(nn, batch, expect_device=False)
+        assert np.array_equal(dev, _oracle_pairs(batch, 6.5))
 
 
 def test_results_do_not_depend_on_the_builder(lib, monkeypatch):
