@@ -304,7 +304,7 @@ int ta_step_view(ta_handle h, const double *positions, const double *cells, uint
  * with lengths in A, energies in eV and masses in amu the time unit is A sqrt(amu / eV) (ASE's units).
  * One step is velocity Verlet as ASE's VelocityVerlet:
  *     v' = v + dt/2 F(x)/m;   x <- x + dt v';   v <- v' + dt/2 F(x)/m
- * Positions stay unwrapped, cells fixed. Before each step a Berendsen thermostat (ASE's
+ * Positions stay unwrapped, cells fixed (unless ta_md_set_barostat says otherwise). Before each step a Berendsen thermostat (ASE's
  * NVTBerendsen.scale_velocities) may scale the velocities of every frame by
  *     lambda = sqrt(1 + (kT0 / kT - 1) dt / tau) clamped to [0.9, 1.1],  kT = 2 KE / (3 n_atoms of the frame)
  * (lambda = 1 when KE = 0). The centre-of-mass momentum is NOT removed, neither at ta_md_init nor by the
@@ -357,7 +357,59 @@ int ta_step_view(ta_handle h, const double *positions, const double *cells, uint
  *                        step, and ta_md_run needs dt >= 0.
  *   ta_md_noise          xi, eta [n_atoms_total][3]: the normals of absolute step `step` (>= 0) under the
  *                        handle's seed, from the device function the integrator calls, so that a caller
- *                        can reproduce a trajectory on the host. Needs ta_md_init. */
+ *                        can reproduce a trajectory on the host. Needs ta_md_init.
+ *
+ * Constant pressure: a Berendsen barostat, ASE's NPTBerendsen (isotropic) and Inhomogeneous_NPTBerendsen (per
+ * axis), computed inside the integrator launch with ONE force evaluation per step. Per frame, with h the cell
+ * (rows are lattice vectors), V = |det h|, W the library's virial (dE / d strain) of the evaluation at x_k, P0
+ * the target pressure, beta the compressibility and taup a time, step k -> k + 1 does, in this order:
+ *     1. the thermostat's velocity part as above (Berendsen: v <- lambda v; Langevin: nothing here)
+ *     2. P_c = (sum_i m_i v_ic^2 - W_cc) / V for c = x, y, z, from the velocities as they stand after 1.
+ *        isotropic: P = (P_x + P_y + P_z) / 3 and mu_x = mu_y = mu_z = 1 - (dt / taup) (beta / 3) (P0 - P)
+ *        with a mask: mu_c = 1 - (dt / taup) (beta / 3) (P0 - P_c) on free axes, mu_c = 1 exactly on the others
+ *        x_ic <- mu_c x_ic and h[:, c] <- mu_c h[:, c]: a diagonal strain on Cartesian components, which is
+ *        ASE's row scaling for the axis-aligned orthorhombic cells its class assumes and is defined for
+ *        triclinic cells too. Velocities are not scaled by mu and mu is not clamped, both as in ASE.
+ *     3. the rest of the step unchanged (the half-kick and drift, or Langevin's first update and drift), with
+ *        F_k, the forces evaluated at the UNSCALED x_k. This is what ASE does when forces are handed to
+ *        step(); ASE evaluates again after the scaling when none are handed in. The difference is of
+ *        order 1 - mu per step.
+ * The barostat composes with every thermostat setting: none, Berendsen, Langevin. It needs the frame's three
+ * sums of m v_c^2 before any position is scaled, so one workgroup of 1024 threads owns a whole frame, as with
+ * the Berendsen thermostat; the recorded kinetic energy is half the total of the three sums.
+ *   ta_md_set_barostat   NULL or taup <= 0 switches the barostat off (the default). A property of the handle
+ *                        like the thermostats (ta_set_frames keeps it). TA_ERR_INVALID, with the argument
+ *                        named by ta_last_error and the setting left as it was: pressure or taup not finite,
+ *                        compressibility not finite or < 0, isotropic == 0 with a mask of all zeros.
+ *   ta_md_run            with the barostat on: TA_WANT_VIRIAL is added to `want`. TA_ERR_INVALID for a batch
+ *                        with a frame that is not periodic along all three axes or has a singular cell. The
+ *                        cells change on the device, so the list test knows strain as in ta_relax_run: the
+ *                        launch keeps s_c, the product of the mu_c since the list was built (h = h_ref diag(s)),
+ *                        and with u_i = x_i - x_ref,i o s and rc = max(rcut, acut) the list is stale when
+ *                        lim = (skin - (rc + skin) |s - 1|_2) / 2 <= 0 or some |u_i|^2 >= lim^2 (s = 1: the
+ *                        skin / 2 rule). Rebuilds take the cells from the device. While the barostat is on,
+ *                        the triangle-once backward pass is selected as under ta_relax_set_cell: only when
+ *                        every periodic width of the list's cells exceeds rc + skin. A mu_c that is not a
+ *                        finite number > 0 ends the run with TA_ERR_INVALID that names the frame and the
+ *                        step; the MD state is dropped and no batch is resident. A run that ends with cells
+ *                        other than its list's cells builds one list for the final state and evaluates it
+ *                        again (counted in *n_rebuilds and ta_list_stats; an n_steps = 0 run moves no cell
+ *                        and builds nothing), exactly the rule of ta_relax_run: ta_step,
+ *                        ta_update_positions(cells = NULL), a fixed-cell ta_md_run and ta_relax_run then
+ *                        find the final cells. If ta_relax_set_cell is on, the moved cells become its h0,
+ *                        with G = I and cell velocities 0, as for cells handed to ta_update_positions.
+ *   ta_md_get_cell       cells [n_frames][9]: the resident cells.
+ *   ta_md_get_records    volume [n_rec][n_frames], press [n_rec][n_frames][3] (either may be NULL) of the last
+ *                        successful barostat run, at the slots of its epot / ekin: V and P_c of the recorded
+ *                        state from the recorded kinetic sums (with Berendsen scaling: the sums before the
+ *                        scaling). TA_ERR_INVALID when the last run had no barostat. */
+typedef struct {
+  double pressure;         /* target, energy / volume (eV / A^3) */
+  double taup;             /* time constant; <= 0: barostat off */
+  double compressibility;  /* volume / energy (A^3 / eV) */
+  int32_t mask[3];         /* x, y, z: non-zero = the axis is free; read when isotropic == 0 */
+  int32_t isotropic;       /* non-zero: one factor from the mean of the three pressures */
+} ta_md_barostat_params;
 int ta_md_init(ta_handle h, const double *masses, const double *velocities);
 int ta_md_set_thermostat(ta_handle h, double kT0, double tau);
 int ta_md_set_langevin(ta_handle h, double kT0, double friction, uint64_t seed);
@@ -365,6 +417,9 @@ int ta_md_noise(ta_handle h, int64_t step, double *xi, double *eta);
 int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t record_every, double *epot,
               double *ekin, int32_t *n_rebuilds);
 int ta_md_get_state(ta_handle h, double *positions, double *velocities);
+int ta_md_set_barostat(ta_handle h, const ta_md_barostat_params *p);
+int ta_md_get_cell(ta_handle h, double *cells);
+int ta_md_get_records(ta_handle h, double *volume, double *press);
 
 /* Device-resident structure relaxation: the resident batch is brought to a force minimum in ONE call, every
  * frame on its own, with positions, velocities and forces staying on the device. The optimiser is FIRE

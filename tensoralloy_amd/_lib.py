@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = [
     "ta_set_filter_tables", "ta_filter_table_knots",
     "ta_md_init", "ta_md_set_thermostat", "ta_md_run", "ta_md_get_state",
     "ta_md_set_langevin", "ta_md_noise",
+    "ta_md_set_barostat", "ta_md_get_cell", "ta_md_get_records",
     "ta_relax_init", "ta_relax_run", "ta_relax_get_state",
     "ta_relax_set_cell", "ta_relax_get_cell",
     "ta_list_info", "ta_get_list",
@@ -104,6 +105,11 @@ class BatchInfo(C.Structure):
 class FireParams(C.Structure):
     _fields_ = [("dt", C.c_double), ("dtmax", C.c_double), ("maxstep", C.c_double), ("finc", C.c_double),
                 ("fdec", C.c_double), ("astart", C.c_double), ("fa", C.c_double), ("nmin", C.c_int32)]
+
+
+class MdBarostatParams(C.Structure):
+    _fields_ = [("pressure", C.c_double), ("taup", C.c_double), ("compressibility", C.c_double),
+                ("mask", C.c_int32 * 3), ("isotropic", C.c_int32)]
 
 
 class RelaxCellParams(C.Structure):
@@ -274,6 +280,9 @@ def load():
     lib.ta_md_get_state.argtypes = [H, _dp, _dp]
     lib.ta_md_set_langevin.argtypes = [H, C.c_double, C.c_double, C.c_uint64]
     lib.ta_md_noise.argtypes = [H, C.c_int64, _dp, _dp]
+    lib.ta_md_set_barostat.argtypes = [H, C.POINTER(MdBarostatParams)]
+    lib.ta_md_get_cell.argtypes = [H, _dp]
+    lib.ta_md_get_records.argtypes = [H, _dp, _dp]
     lib.ta_relax_init.argtypes = [H, C.POINTER(FireParams), C.POINTER(C.c_uint8)]
     lib.ta_relax_run.argtypes = [H, C.c_int32, C.c_double, C.c_uint32, _ip, _ip, _dp, _ip]
     lib.ta_relax_get_state.argtypes = [H, _dp, _dp, _dp, _dp, _ip]

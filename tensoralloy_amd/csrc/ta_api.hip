@@ -354,6 +354,16 @@ struct ta_context {
   uint64_t md_seed = 0;
   int64_t md_step = 0;
   DevBuf<double> md_noise;
+  // Berendsen barostat (ta_md_set_barostat; off while md_baro_on is false): the setting, the cumulative
+  // scale of every frame since its list was built with the ones that reset it, the device records
+  // {V, P_x, P_y, P_z} of the running ta_md_run and the host's copy of the last successful run's
+  bool md_baro_on = false;
+  bool md_baro_running = false;  // a barostat run is under way: a rebuild resets the cumulative scale
+  ta_md_barostat_params md_baro_p = {0.0, 0.0, 0.0, {1, 1, 1}, 1};
+  DevBuf<double> md_baro_scale, md_baro_rec;
+  std::vector<double> md_baro_ones;
+  bool md_rec_valid = false;
+  std::vector<double> md_rec_volume, md_rec_press;  // [n_rec][F], [n_rec][F][3]
 
   // device-resident relaxation (ta_relax_init / ta_relax_run; the launches are in ta_relax.hip): FIRE
   // velocities of its own, the mask of fixed atoms, the two copies of the per-frame state with the host's
@@ -370,7 +380,7 @@ struct ta_context {
   // gradient and the cell velocity (two copies on the device like relax_state, the current one on the host
   // between runs), the reference cells of the resident list next to md_ref
   bool relax_cell_on = false;
-  bool relax_cell_running = false;  // a cell run is under way: rebuilds take the cells from the device
+  bool cell_running = false;  // a run that moves the cells (cell relaxation, barostat) is under way: rebuilds take them from the device
   ta_relax_cell_params relax_cell_p = {0.0, 0.0, {1, 1, 1, 1, 1, 1}, 0, 0};
   DevBuf<double> relax_cell_h0, relax_cell_cf, relax_cell_G, relax_cell_vel, relax_cell_fmax2, md_ref_cells;
   std::vector<double> relax_cell_G_host, relax_cell_vel_host;
@@ -948,8 +958,9 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
     }
     h->sf.ang_scale = h->use_v2 ? 1.0 : 0.5;
     // triangle-once backward pass: the forward launches also leave the owned job lists
-    // (while cells relax, a list stays valid until a width has shrunk by rmax / (rmax + skin): the wider test)
-    const bool tri_cells = h->relax_cell_on ? h->tri_cells_wide_ok : h->tri_cells_ok;
+    // (while cells relax or follow a barostat, a list stays valid until a width has shrunk by
+    // rmax / (rmax + skin): the wider test)
+    const bool tri_cells = (h->relax_cell_on || h->md_baro_on) ? h->tri_cells_wide_ok : h->tri_cells_ok;
     const bool tri = h->use_v2 && h->triangles && tri_cells && h->n_elements == 1 && need_forces;
     h->db.job_word_own = (tri && h->db.job_count) ? h->job_word_own.ptr : nullptr;
     h->db.job_count_own = (tri && h->db.job_count) ? h->job_count_own.ptr : nullptr;
@@ -1870,14 +1881,26 @@ int resident_steps(ta_context *h, const char *who, int n_steps, uint32_t want, E
     h->n_list_reuses += q - k;
     x.resize(3 * N);
     if (N) HIP_CHECK(hipMemcpy(x.data(), h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
-    if (h->relax_cell_running) {  // the cells moved on the device: ref_cells are those of the stale list
+    if (h->cell_running) {  // the cells moved on the device: ref_cells are those of the stale list
       cells.resize(9 * F);
       if (F) HIP_CHECK(hipMemcpy(cells.data(), h->db.cells, 9 * F * sizeof(double), hipMemcpyDeviceToHost));
+      if (h->md_baro_running) {  // a scale factor that was no finite number > 0 left NaNs in its frame's cell
+        for (size_t f = 0; f < F; ++f) {
+          bool ok = true;
+          for (int c = 0; c < 9; ++c) ok = ok && std::isfinite(cells[9 * f + c]);
+          if (!ok) {
+            h->have_batch = false;  // (positions and cells of the frame are lost)
+            h->md_valid = false;
+            throw std::invalid_argument(std::string(who) + ": the barostat's scale factor of frame " + std::to_string(f) +
+                                        " at step " + std::to_string(q + 1) + " is not a finite number > 0");
+          }
+        }
+      }
     }
     status_host[0] = 0u;
     HIP_CHECK(hipMemsetAsync(h->md_status.ptr, 0, 2 * sizeof(unsigned), s));
     try {
-      rebuild_list(h, x.data(), h->relax_cell_running ? cells.data() : nullptr);
+      rebuild_list(h, x.data(), h->cell_running ? cells.data() : nullptr);
     } catch (const HipError &e) {
       throw HipError(std::string(who) + ": list rebuild after step " + std::to_string(q + 1) + " failed: " + e.what());
     } catch (const std::exception &e) {
@@ -1885,8 +1908,12 @@ int resident_steps(ta_context *h, const char *who, int n_steps, uint32_t want, E
                                " failed: " + e.what());
     }
     if (N) HIP_CHECK(hipMemcpyAsync(h->md_ref.ptr, h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToDevice, s));
-    if (h->relax_cell_running && F)
-      HIP_CHECK(hipMemcpyAsync(h->md_ref_cells.ptr, h->db.cells, 9 * F * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (h->cell_running && F) {
+      if (h->md_baro_running)  // the barostat keeps the scale since the build, not the list's cells
+        HIP_CHECK(hipMemcpyAsync(h->md_baro_scale.ptr, h->md_baro_ones.data(), 3 * F * sizeof(double), hipMemcpyHostToDevice, s));
+      else
+        HIP_CHECK(hipMemcpyAsync(h->md_ref_cells.ptr, h->db.cells, 9 * F * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
     h->md_ref_builds = h->n_list_builds;
     compute_impl(h, want, false, nullptr);
     ++*rebuilds;
@@ -1927,6 +1954,7 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
     h->md_chunk = 0;
     h->md_blk_start_host.clear();
     h->md_step = 0;
+    h->md_rec_valid = false;
     h->md_valid = true;
   });
 }
@@ -1977,6 +2005,46 @@ int ta_md_noise(ta_handle h, int64_t step, double *xi, double *eta) {
   });
 }
 
+int ta_md_set_barostat(ta_handle h, const ta_md_barostat_params *p) {
+  if (!h) return TA_ERR_INVALID;
+  if (p && !std::isfinite(p->taup)) return fail(h, TA_ERR_INVALID, "ta_md_set_barostat: taup must be finite");
+  if (!p || !(p->taup > 0.0)) {
+    h->md_baro_on = false;
+    return TA_OK;
+  }
+  if (!std::isfinite(p->pressure)) return fail(h, TA_ERR_INVALID, "ta_md_set_barostat: pressure must be finite");
+  if (!std::isfinite(p->compressibility) || p->compressibility < 0.0)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_barostat: compressibility must be finite and >= 0");
+  if (!p->isotropic && !p->mask[0] && !p->mask[1] && !p->mask[2])
+    return fail(h, TA_ERR_INVALID, "ta_md_set_barostat: mask leaves no axis of the cell free");
+  h->md_baro_p = *p;
+  h->md_baro_on = true;
+  return TA_OK;
+}
+
+int ta_md_get_cell(ta_handle h, double *cells) {
+  if (!h) return TA_ERR_INVALID;
+  if (!cells) return fail(h, TA_ERR_INVALID, "ta_md_get_cell: null argument");
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_cell: no resident batch");
+  // (between runs ref_cells is the image of the device's cells)
+  const size_t F = h->keep_natoms.size();
+  if (F) std::memcpy(cells, h->ref_cells.data(), 9 * F * sizeof(double));
+  return TA_OK;
+}
+
+int ta_md_get_records(ta_handle h, double *volume, double *press) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_records: no resident batch");
+  if (!h->md_valid) return fail(h, TA_ERR_INVALID, "ta_md_get_records called before ta_md_init");
+  if (!h->md_rec_valid)
+    return fail(h, TA_ERR_INVALID, "ta_md_get_records: the last ta_md_run of this batch had no barostat");
+  if (volume && !h->md_rec_volume.empty())
+    std::memcpy(volume, h->md_rec_volume.data(), h->md_rec_volume.size() * sizeof(double));
+  if (press && !h->md_rec_press.empty())
+    std::memcpy(press, h->md_rec_press.data(), h->md_rec_press.size() * sizeof(double));
+  return TA_OK;
+}
+
 int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t record_every, double *epot,
               double *ekin, int32_t *n_rebuilds) {
   if (!h) return TA_ERR_INVALID;
@@ -1985,22 +2053,48 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
   if (n_steps < 0 || record_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_run: n_steps >= 0 and record_every >= 1 are needed");
   if (!std::isfinite(dt)) return fail(h, TA_ERR_INVALID, "ta_md_run: dt must be finite");
   if (h->md_friction > 0.0 && dt < 0.0) return fail(h, TA_ERR_INVALID, "ta_md_run: Langevin dynamics needs dt >= 0");
+  const bool baro = h->md_baro_on;
+  if (baro) {
+    const size_t F = h->keep_natoms.size();
+    for (size_t f = 0; f < F; ++f) {
+      for (int k = 0; k < 3; ++k)
+        if (!h->keep_pbc[3 * f + k])
+          return fail(h, TA_ERR_INVALID, "ta_md_run: the barostat is on and frame " + std::to_string(f) +
+                                         " is not periodic along all three axes");
+      const double *c = h->ref_cells.data() + 9 * f;
+      const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
+      if (!std::isfinite(det) || !(std::fabs(det) > 0.0))
+        return fail(h, TA_ERR_INVALID, "ta_md_run: the barostat is on and the cell of frame " + std::to_string(f) + " is singular");
+    }
+  }
   if (n_rebuilds) *n_rebuilds = 0;
   want |= TA_WANT_ENERGY | TA_WANT_FORCES;
   want &= ~(uint32_t)TA_WANT_REUSE_DESCRIPTORS;
-  return guarded(h, [&]() {
+  if (baro) want |= TA_WANT_VIRIAL;  // the pressure
+  h->md_rec_valid = false;
+  h->cell_running = h->md_baro_running = baro;
+  const int rc = guarded(h, [&]() {
     const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
     hipStream_t s = h->stream;
     const bool thermostat = h->md_kT0 > 0.0, langevin = h->md_friction > 0.0;  // (never both)
     // with Berendsen scaling one workgroup owns a whole frame: the factor needs the frame's kinetic energy
+    // (the barostat: the frame's three sums of m v_c^2)
     int chunk = ta::kMdChunk;
-    if (thermostat)
+    if (thermostat || baro)
       for (size_t f = 0; f < F; ++f) chunk = std::max(chunk, h->keep_natoms[f]);
-    const int threads = thermostat ? 1024 : 256;
+    const int threads = (thermostat || baro) ? 1024 : 256;
     md_plan_blocks(h, chunk);
     const size_t n_blk = (size_t)h->md_n_blk, n_rec = (size_t)(n_steps / record_every) + 1;
     h->md_epot.ensure(n_rec * F + 1);
     h->md_ke.ensure(n_rec * n_blk + 1);
+    const std::vector<double> cells_at_entry(baro ? h->ref_cells : std::vector<double>());
+    if (baro) {  // every run starts on a list built for the resident cells: the cumulative scale is 1
+      h->md_baro_rec.ensure(4 * n_rec * F + 1);
+      h->md_baro_scale.ensure(3 * F + 1);
+      h->md_baro_ones.assign(3 * F, 1.0);
+      HIP_CHECK(hipStreamSynchronize(s));
+      if (F) HIP_CHECK(hipMemcpy(h->md_baro_scale.ptr, h->md_baro_ones.data(), 3 * F * sizeof(double), hipMemcpyHostToDevice));
+    }
     if (h->md_ref_builds != h->n_list_builds) {  // the host built the list that is resident: its positions go up once
       HIP_CHECK(hipStreamSynchronize(s));
       if (N) HIP_CHECK(hipMemcpy(h->md_ref.ptr, h->ref_pos.data(), 3 * N * sizeof(double), hipMemcpyHostToDevice));
@@ -2038,12 +2132,24 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     a.n_frames = (int)F;
     a.n_blk = (int)n_blk;
     a.chunk = chunk;
+    a.baro = baro ? 1 : 0;
+    a.baro_iso = h->md_baro_p.isotropic ? 1 : 0;
+    a.cells = nullptr, a.virial = nullptr;
+    a.baro_scale = h->md_baro_scale.ptr;
+    a.baro_rec = h->md_baro_rec.ptr;
+    a.baro_p0 = h->md_baro_p.pressure;
+    a.baro_k = baro ? dt / h->md_baro_p.taup * h->md_baro_p.compressibility / 3.0 : 0.0;
+    for (int c = 0; c < 3; ++c) a.baro_mask[c] = h->md_baro_p.mask[c] ? 1 : 0;
+    a.skin = h->skin;
+    a.r_list = h->rmax + h->skin;
     auto integrate = [&](int k, bool drift) {
       // (a rebuild may have moved the batch's arrays: the pointers are taken at every launch)
       a.pos = h->db.pos;
       a.forces = h->db.forces;
       a.energy = h->db.energy;
       a.atom_start = h->db.atom_start;
+      a.cells = h->db.cells;
+      a.virial = h->db.virial;
       a.seq = (unsigned)k;
       a.step = (long long)(step0 + k);  // (a step redone after a rebuild keeps its index)
       a.kick2 = k > 0 ? 1 : 0;  // the state at entry is a whole step
@@ -2063,6 +2169,48 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     h->upload_pending = false;
     h->md_step = step0 + n_steps;
     if (n_rebuilds) *n_rebuilds = rebuilds;
+    if (baro && F) {
+      std::vector<double> rec(4 * n_rec * F);
+      HIP_CHECK(hipMemcpy(rec.data(), h->md_baro_rec.ptr, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
+      h->md_rec_volume.resize(n_rec * F);
+      h->md_rec_press.resize(3 * n_rec * F);
+      for (size_t j = 0; j < n_rec * F; ++j) {
+        h->md_rec_volume[j] = rec[4 * j];
+        for (int c = 0; c < 3; ++c) h->md_rec_press[3 * j + c] = rec[4 * j + 1 + c];
+      }
+      // The cells moved under a list built for others: one list for the final state, as at the end of a cell
+      // relaxation, so that ref_pos and ref_cells are what ta_update_positions, ta_step, a fixed-cell run and
+      // ta_relax_run take them for. The evaluation is repeated on it; results agree up to summation order.
+      std::vector<double> cells(9 * F);
+      HIP_CHECK(hipMemcpy(cells.data(), h->db.cells, 9 * F * sizeof(double), hipMemcpyDeviceToHost));
+      if (std::memcmp(cells.data(), h->ref_cells.data(), 9 * F * sizeof(double)) != 0) {
+        std::vector<double> x(3 * N);
+        if (N) HIP_CHECK(hipMemcpy(x.data(), h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+        try {
+          rebuild_list(h, x.data(), cells.data());
+        } catch (const HipError &e) {
+          throw HipError(std::string("ta_md_run: list rebuild for the final cells failed: ") + e.what());
+        } catch (const std::exception &e) {
+          throw std::runtime_error(std::string("ta_md_run: list rebuild for the final cells failed: ") + e.what());
+        }
+        if (N) HIP_CHECK(hipMemcpyAsync(h->md_ref.ptr, h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToDevice, s));
+        h->md_ref_builds = h->n_list_builds;
+        compute_impl(h, want, false, nullptr);
+        HIP_CHECK(hipStreamSynchronize(s));
+        h->upload_pending = false;
+        ++rebuilds;
+        if (n_rebuilds) *n_rebuilds = rebuilds;
+      }
+      if (h->relax_cell_on && h->relax_valid &&
+          std::memcmp(cells_at_entry.data(), h->ref_cells.data(), 9 * F * sizeof(double)) != 0) {
+        // the barostat's cells replace the relaxed ones: they are h0 from here on, G = I, the cell velocities 0
+        HIP_CHECK(hipMemcpy(h->relax_cell_h0.ptr, h->ref_cells.data(), 9 * F * sizeof(double), hipMemcpyHostToDevice));
+        h->relax_cell_G_host.assign(9 * F, 0.0);
+        for (size_t f = 0; f < F; ++f) h->relax_cell_G_host[9 * f] = h->relax_cell_G_host[9 * f + 4] = h->relax_cell_G_host[9 * f + 8] = 1.0;
+        h->relax_cell_vel_host.assign(9 * F, 0.0);
+      }
+      h->md_rec_valid = true;
+    }
     if (epot && F) HIP_CHECK(hipMemcpy(epot, h->md_epot.ptr, n_rec * F * sizeof(double), hipMemcpyDeviceToHost));
     if (ekin && F) {
       std::vector<double> part(n_rec * n_blk);
@@ -2076,6 +2224,8 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
         }
     }
   });
+  h->cell_running = h->md_baro_running = false;
+  return rc;
 }
 
 int ta_md_get_state(ta_handle h, double *positions, double *velocities) {
@@ -2164,7 +2314,7 @@ int ta_relax_run(ta_handle h, int32_t max_steps, double fmax, uint32_t want, int
   // a run that fails leaves positions and velocities somewhere on its way and the host's image of the
   // per-frame records behind them: the state is dropped, and only ta_relax_init makes a new one
   h->relax_valid = false;
-  h->relax_cell_running = cell;
+  h->cell_running = cell;
   const int rc = guarded(h, [&]() {
     const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
     hipStream_t s = h->stream;
@@ -2292,7 +2442,7 @@ int ta_relax_run(ta_handle h, int32_t max_steps, double fmax, uint32_t want, int
       }
     }
   });
-  h->relax_cell_running = false;
+  h->cell_running = false;
   if (rc == TA_OK) h->relax_valid = true;
   else h->relax_cell_on = false;
   return rc;

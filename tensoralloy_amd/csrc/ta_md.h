@@ -37,6 +37,18 @@ struct MdLaunch {
   long long step;
   unsigned long long seed;
   double c1, c2, c3, c4, c5;
+  // Barostat (baro != 0; every workgroup is then a whole frame): db.cells and the frame virials of the
+  // evaluation before this launch, the cumulative scale s_c since the list was built, the record
+  // {V, P_x, P_y, P_z}, the target pressure, k = (dt / taup) (beta / 3), the free axes (read unless
+  // baro_iso), and skin and rc + skin of the strain-aware list test (which replaces lim2)
+  int baro, baro_iso;
+  double *cells;              // [F][9]
+  const double *virial;       // [F][9]
+  double *baro_scale;         // [F][3]
+  double *baro_rec;           // [n_rec][F][4]
+  double baro_p0, baro_k;
+  int baro_mask[3];
+  double skin, r_list;
 };
 
 void launch_md_integrate(const MdLaunch &a, int threads, hipStream_t s);

@@ -26,6 +26,24 @@
 // after a rebuild, enqueued behind a stale list or split over two runs draws the same numbers. There is
 // no per-frame factor, so the chunked layout holds at any frame size.
 //
+// The barostat builds (md_integrate_kernel<., true>; ta_md_set_barostat) are ASE's NPTBerendsen (isotropic)
+// and Inhomogeneous_NPTBerendsen (per axis) with ONE force evaluation per step. Per frame, with h the cell
+// (rows are lattice vectors), V = |det h|, W the virial (dE / d strain) of the evaluation at x_k and S_c the
+// sum of m v_c^2 over the frame's atoms, between steps 3 and 4 above (Langevin: before the first update):
+//     P_c = (S_c - W_cc) / V            from the velocities as they stand, i.e. after the Berendsen factor
+//     mu_c = 1 - (dt / taup) (beta / 3) (P0 - P_c)     isotropic: P_c -> (P_x + P_y + P_z) / 3; masked axis: 1
+//     x_ic <- mu_c x_ic,  h[:, c] <- mu_c h[:, c]      velocities are not scaled, mu is not clamped
+// The kicks and the drift of the step then use F_k, the forces at the UNSCALED x_k: what ASE does when forces
+// are handed to step(); ASE evaluates again after the scaling when none are handed in, a difference of order
+// 1 - mu per step. The three sums are needed before any position is scaled, so one workgroup owns a whole
+// frame as with the Berendsen thermostat, under every thermostat setting; the recorded kinetic energy is
+// (S_x + S_y + S_z) / 2, and the record also takes V and P_c of the recorded state (S_c before the Berendsen
+// factor). Thread 0 writes the new cell into db.cells, which no other thread of the launch reads, and keeps
+// s_c, the product of the mu_c since the list was built: h = h_ref diag(s), so with u_i = x_i - x_ref,i o s
+// the list is stale when lim = (skin - (rc + skin) |s - 1|_2) / 2 <= 0 or some |u_i|^2 >= lim^2, the rule of
+// ta_relax.hip with A = diag(s). A mu_c that is not a finite number > 0 is made a NaN, which the host finds
+// in the cells it downloads before the rebuild.
+//
 // The launch is predicated on a device word: a drift that finds an atom beyond skin / 2 writes its own
 // sequence number + 1 there (and into a page-locked word the host reads after a stream wait), still
 // writes valid positions, and every LATER launch returns at once. The host may therefore enqueue several
@@ -91,11 +109,20 @@ __global__ __launch_bounds__(256) void md_noise_kernel(unsigned long long seed, 
   md_normals(seed, step, (uint32_t)(j / 3), (uint32_t)(j % 3), &xi[j], &eta[j]);
 }
 
-// kLangevin = false: velocity Verlet with the optional Berendsen factor; true: the Langevin step
-template <bool kLangevin>
+// slots of the barostat's LDS block
+constexpr int kBaroMu = 0, kBaroScale = 3, kBaroLim2 = 6, kBaroWords = 7;
+
+__device__ __forceinline__ double md_cell_volume(const double *h) {
+  return fabs(h[0] * (h[4] * h[8] - h[5] * h[7]) - h[1] * (h[3] * h[8] - h[5] * h[6]) + h[2] * (h[3] * h[7] - h[4] * h[6]));
+}
+
+// kLangevin = false: velocity Verlet with the optional Berendsen factor; true: the Langevin step.
+// kBaro: the Berendsen barostat before the step (one workgroup per frame)
+template <bool kLangevin, bool kBaro>
 __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
   __shared__ double s_wave[16];
   __shared__ double s_total;
+  __shared__ double s_baro[kBaro ? kBaroWords : 1];  // (unused, and dropped, in the fixed-cell builds)
   // (0, or the value this very launch writes, or the mark of an earlier launch: the same branch in every thread)
   const unsigned mark = *static_cast<volatile unsigned *>(a.status);
   if (mark != 0u && mark <= a.seq) return;
@@ -116,6 +143,7 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
   const double hdt = 0.5 * a.dt;
 
   double ke = 0.0;
+  double sx = 0.0, sy = 0.0, sz = 0.0;  // (kBaro: the frame's sums of m v_c^2)
   for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
     const double m = a.mass[i];
     double vx = a.vel[3 * i], vy = a.vel[3 * i + 1], vz = a.vel[3 * i + 2];
@@ -141,12 +169,31 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
       a.vel[3 * i + 1] = vy;
       a.vel[3 * i + 2] = vz;
     }
-    ke += 0.5 * m * (vx * vx + vy * vy + vz * vz);
+    if constexpr (kBaro) {
+      sx += m * vx * vx;
+      sy += m * vy * vy;
+      sz += m * vz * vz;
+    } else {
+      ke += 0.5 * m * (vx * vx + vy * vy + vz * vz);
+    }
   }
-  ke = md_block_sum(ke, s_wave, &s_total);
+  if constexpr (kBaro) {
+    sx = md_block_sum(sx, s_wave, &s_total);
+    sy = md_block_sum(sy, s_wave, &s_total);
+    sz = md_block_sum(sz, s_wave, &s_total);
+    ke = 0.5 * (sx + sy + sz);
+  } else {
+    ke = md_block_sum(ke, s_wave, &s_total);
+  }
   if (threadIdx.x == 0 && a.rec >= 0) {
     a.ke_part[(size_t)a.rec * a.n_blk + blockIdx.x] = ke;
     if ((int)blockIdx.x == blk0) a.epot[(size_t)a.rec * a.n_frames + f] = a.energy[f];
+    if constexpr (kBaro) {  // V and P_c of the recorded state
+      const double *h = a.cells + 9 * (size_t)f, *W = a.virial + 9 * (size_t)f;
+      const double V = md_cell_volume(h);
+      double *r = a.baro_rec + 4 * ((size_t)a.rec * a.n_frames + f);
+      r[0] = V, r[1] = (sx - W[0]) / V, r[2] = (sy - W[4]) / V, r[3] = (sz - W[8]) / V;
+    }
   }
   if (!a.drift) return;
 
@@ -157,6 +204,40 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
     lambda = lambda > 1.1 ? 1.1 : (lambda < 0.9 ? 0.9 : lambda);
   }
   int stale = 0;
+  double mu[3] = {1.0, 1.0, 1.0}, sc[3] = {1.0, 1.0, 1.0}, lim2 = a.lim2;
+  if constexpr (kBaro) {
+    if (threadIdx.x == 0) {
+      double h[9];
+#pragma unroll
+      for (int c = 0; c < 9; ++c) h[c] = a.cells[9 * (size_t)f + c];
+      const double *W = a.virial + 9 * (size_t)f;
+      const double V = md_cell_volume(h), l2 = lambda * lambda;
+      double P[3] = {(l2 * sx - W[0]) / V, (l2 * sy - W[4]) / V, (l2 * sz - W[8]) / V};
+      if (a.baro_iso) P[0] = P[1] = P[2] = (P[0] + P[1] + P[2]) / 3.0;
+      double n2 = 0.0;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        double m_c = 1.0;
+        if (a.baro_iso || a.baro_mask[c]) {
+          m_c = 1.0 - a.baro_k * (a.baro_p0 - P[c]);
+          if (!(m_c > 0.0) || isinf(m_c)) m_c = nan("");  // (the host finds it in the cells)
+        }
+        const double s_c = a.baro_scale[3 * (size_t)f + c] * m_c;
+        a.baro_scale[3 * (size_t)f + c] = s_c;
+        s_baro[kBaroMu + c] = m_c;
+        s_baro[kBaroScale + c] = s_c;
+        n2 += (s_c - 1.0) * (s_c - 1.0);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) a.cells[9 * (size_t)f + 3 * r + c] = h[3 * r + c] * m_c;
+      }
+      const double lim = 0.5 * (a.skin - a.r_list * sqrt(n2));
+      s_baro[kBaroLim2] = lim > 0.0 ? lim * lim : -1.0;  // (a NaN strain: -1, every drift is stale)
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 3; ++c) mu[c] = s_baro[kBaroMu + c], sc[c] = s_baro[kBaroScale + c];
+    lim2 = s_baro[kBaroLim2];
+  }
   for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {  // (each thread meets its own atoms again)
     const double m = a.mass[i];
     double rp[3] = {0.0, 0.0, 0.0};  // (Langevin: the random part of the drift)
@@ -180,15 +261,30 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
         a.vel[3 * i + c] = v;
       }
     }
-    double x = a.pos[3 * i] + a.dt * a.vel[3 * i], y = a.pos[3 * i + 1] + a.dt * a.vel[3 * i + 1],
-           z = a.pos[3 * i + 2] + a.dt * a.vel[3 * i + 2];
-    if constexpr (kLangevin) x += rp[0], y += rp[1], z += rp[2];
-    a.pos[3 * i] = x;
-    a.pos[3 * i + 1] = y;
-    a.pos[3 * i + 2] = z;
-    const double dx = x - a.ref[3 * i], dy = y - a.ref[3 * i + 1], dz = z - a.ref[3 * i + 2];
-    const double d2 = dx * dx + dy * dy + dz * dz;
-    stale |= !(d2 <= a.lim2) ? 1 : 0;  // (a NaN fails the comparison too and is reported by the rebuild)
+    if constexpr (kBaro) {  // the scaled x_k drifts; u = x_{k+1} - x_ref o s
+      double x = mu[0] * a.pos[3 * i] + a.dt * a.vel[3 * i], y = mu[1] * a.pos[3 * i + 1] + a.dt * a.vel[3 * i + 1],
+             z = mu[2] * a.pos[3 * i + 2] + a.dt * a.vel[3 * i + 2];
+      if constexpr (kLangevin) x += rp[0], y += rp[1], z += rp[2];
+      a.pos[3 * i] = x;
+      a.pos[3 * i + 1] = y;
+      a.pos[3 * i + 2] = z;
+      const double dx = x - a.ref[3 * i] * sc[0], dy = y - a.ref[3 * i + 1] * sc[1], dz = z - a.ref[3 * i + 2] * sc[2];
+      const double d2 = dx * dx + dy * dy + dz * dz;
+      stale |= !(d2 < lim2) ? 1 : 0;  // (a NaN fails the comparison too and is reported by the rebuild)
+    } else {
+      double x = a.pos[3 * i] + a.dt * a.vel[3 * i], y = a.pos[3 * i + 1] + a.dt * a.vel[3 * i + 1],
+             z = a.pos[3 * i + 2] + a.dt * a.vel[3 * i + 2];
+      if constexpr (kLangevin) x += rp[0], y += rp[1], z += rp[2];
+      a.pos[3 * i] = x;
+      a.pos[3 * i + 1] = y;
+      a.pos[3 * i + 2] = z;
+      const double dx = x - a.ref[3 * i], dy = y - a.ref[3 * i + 1], dz = z - a.ref[3 * i + 2];
+      const double d2 = dx * dx + dy * dy + dz * dz;
+      stale |= !(d2 <= a.lim2) ? 1 : 0;  // (a NaN fails the comparison too and is reported by the rebuild)
+    }
+  }
+  if constexpr (kBaro) {
+    if (threadIdx.x == 0 && !(lim2 > 0.0)) stale = 1;  // (a frame without atoms strains the list too)
   }
   if (__syncthreads_or(stale) && threadIdx.x == 0) {
     *static_cast<volatile unsigned *>(a.status) = a.seq + 1u;
@@ -200,10 +296,18 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
 
 void launch_md_integrate(const MdLaunch &a, int threads, hipStream_t s) {
   if (a.n_blk <= 0) return;
+  const dim3 grid((unsigned)a.n_blk), block((unsigned)threads);
+  if (a.baro) {  // (ta_md_run made every workgroup a whole frame)
+    if (a.langevin)
+      hipLaunchKernelGGL((md_integrate_kernel<true, true>), grid, block, 0, s, a);
+    else
+      hipLaunchKernelGGL((md_integrate_kernel<false, true>), grid, block, 0, s, a);
+    return;
+  }
   if (a.langevin)
-    hipLaunchKernelGGL(md_integrate_kernel<true>, dim3((unsigned)a.n_blk), dim3((unsigned)threads), 0, s, a);
+    hipLaunchKernelGGL((md_integrate_kernel<true, false>), grid, block, 0, s, a);
   else
-    hipLaunchKernelGGL(md_integrate_kernel<false>, dim3((unsigned)a.n_blk), dim3((unsigned)threads), 0, s, a);
+    hipLaunchKernelGGL((md_integrate_kernel<false, false>), grid, block, 0, s, a);
 }
 
 void launch_md_noise(unsigned long long seed, long long step, long long n, double *xi, double *eta, hipStream_t s) {

@@ -35,6 +35,7 @@ class Engine:
         self._frames = None
         self._volumes = None
         self._relax_cell = False   # `relax_set_cell` is on: `relax_run` moves the cells
+        self._md_barostat = False  # `md_set_barostat` is on: `md_run` moves the cells
         self._md_sig = None   # (n, numbers, pbc) of the single resident frame of `evaluate_md`
         self._md_cell = None
         self.batch_generation = 0  # bumped whenever the resident batch or its coordinates change
@@ -293,11 +294,47 @@ class Engine:
         self._check(self._lib.ta_md_noise(self._handle, step, _lib.as_dp(xi), _lib.as_dp(eta)))
         return xi, eta
 
+    def md_set_barostat(self, pressure=0.0, taup=0.0, compressibility=0.0, mask=None):
+        """Berendsen barostat of `md_run` (`ta_md_set_barostat`; ASE's `NPTBerendsen`, with a `mask` its
+        `Inhomogeneous_NPTBerendsen`): target `pressure` (eV / A^3), time constant `taup` (ASE time units; <= 0
+        switches it off, the default), `compressibility` (A^3 / eV) and `mask`: None = isotropic, one factor
+        from the mean pressure; three flags (x, y, z) = every free axis follows its own pressure, the others
+        keep their length exactly. It composes with either thermostat and stays on across `set_frames`."""
+        iso = mask is None
+        m = np.ones(3, dtype=np.int64) if iso else np.asarray(mask)
+        if m.shape != (3,):
+            raise ValueError("md_set_barostat: mask must have three entries (x, y, z)")
+        bp = _lib.MdBarostatParams(float(pressure), float(taup), float(compressibility),
+                                   (C.c_int32 * 3)(*[int(bool(v)) for v in m]), 1 if iso else 0)
+        self._check(self._lib.ta_md_set_barostat(self._handle, C.byref(bp)))
+        self._md_barostat = bool(taup > 0.0)
+
+    def md_cells(self):
+        """Cells [n_frames, 3, 3] of the resident batch as the library holds them (`ta_md_get_cell`)."""
+        if self.info is None:
+            raise ValueError("md_cells: no resident batch (call set_frames first)")
+        cells = np.empty((int(self.info.n_frames), 3, 3))
+        self._check(self._lib.ta_md_get_cell(self._handle, _lib.as_dp(cells)))
+        return cells
+
+    def md_records(self, n_rec: int):
+        """(volume [n_rec, n_frames], press [n_rec, n_frames, 3]) of the last `md_run` under the barostat
+        (`ta_md_get_records`); `n_rec` = that run's n_steps // record_every + 1."""
+        if self.info is None:
+            raise ValueError("md_records: no resident batch (call set_frames first)")
+        F = int(self.info.n_frames)
+        volume, press = np.empty((int(n_rec), F)), np.empty((int(n_rec), F, 3))
+        self._check(self._lib.ta_md_get_records(self._handle, _lib.as_dp(volume), _lib.as_dp(press)))
+        return volume, press
+
     def md_run(self, n_steps: int, dt: float, record_every: int = 1, want: int = None) -> dict:
         """`n_steps` velocity-Verlet (or, with `md_set_langevin`, Langevin) steps of length `dt` (ASE time units) of the resident batch on the
         device (`ta_md_run`): no per-atom traffic while the neighbour list holds. Returns
         `epot` / `ekin` [n_steps // record_every + 1, n_frames] (entry state first) and `n_rebuilds`.
-        Afterwards `fetch(want | ENERGY | FORCES)` hands out the results of the last step."""
+        Afterwards `fetch(want | ENERGY | FORCES)` hands out the results of the last step.
+        With `md_set_barostat` on, the cells follow the pressure, the dict also holds `volume` [n_rec, n_frames]
+        and `press` [n_rec, n_frames, 3] (eV / A^3, per axis) of the recorded states, and a run that moved the
+        cells ends with one list build for the final cells (counted in `n_rebuilds`)."""
         if self.info is None:
             raise ValueError("md_run: no resident batch (call set_frames first)")
         n_steps, record_every = int(n_steps), int(record_every)
@@ -317,7 +354,12 @@ class Engine:
             n_pairs, n_triples, nnl = C.c_int64(0), C.c_int64(0), C.c_int32(0)
             self._check(self._lib.ta_list_sizes(self._handle, C.byref(n_pairs), C.byref(n_triples), C.byref(nnl)))
             self.info.n_pairs, self.info.n_triples, self.info.nnl_max = n_pairs.value, n_triples.value, nnl.value
-        return {"epot": epot, "ekin": ekin, "n_rebuilds": int(rebuilds.value)}
+        out = {"epot": epot, "ekin": ekin, "n_rebuilds": int(rebuilds.value)}
+        if self._md_barostat:   # the cells moved on the device: stress and pressure follow them
+            out["volume"], out["press"] = self.md_records(n_rec)
+            self._volumes = np.abs(np.linalg.det(self.md_cells()))
+            self._md_sig = None
+        return out
 
     def md_state(self):
         """(positions, velocities) [n_atoms, 3] of the resident batch as the device holds them."""

@@ -13,6 +13,12 @@ The Langevin noise is made on the device by a counter-based generator (Philox4x3
 pure function of (seed, step since the start, atom, component). A trajectory therefore depends on the seed
 alone, not on how `run` is cut into calls, on the skin or on list rebuilds, and `Engine.md_noise(step)` hands
 out the very numbers of a step.
+
+Constant pressure: with `pressure`, `taup` and `compressibility` the cells follow a Berendsen barostat (ASE's
+`NPTBerendsen`; with a `mask` of three flags its `Inhomogeneous_NPTBerendsen`), under any of the thermostat
+settings. The scaling factor is computed inside the integrator launch from the forces of the unscaled
+positions, one force evaluation per step (what ASE does when forces are handed to its `step`). `GPa` and `bar`
+are the same numbers as `ase.units.GPa` and `ase.units.bar`.
 """
 from __future__ import annotations
 
@@ -20,8 +26,10 @@ import numpy as np
 
 fs = 0.09822694788464063      # one femtosecond in Angstrom sqrt(amu / eV)
 kB = 8.617330337217213e-05    # eV / K
+GPa = 1.0 / 160.21766208      # eV / Angstrom^3
+bar = 1.0e-4 * GPa
 
-__all__ = ["fs", "kB", "maxwell_boltzmann", "DeviceMD"]
+__all__ = ["fs", "kB", "GPa", "bar", "maxwell_boltzmann", "DeviceMD"]
 
 
 def maxwell_boltzmann(masses, kT, rng, zero_momentum=True):
@@ -53,12 +61,37 @@ class DeviceMD:
     temperature_K, friction : both given: Langevin thermostat with that bath temperature (>= 0; 0 is damped
                            dynamics) and friction (1 / ASE time unit, e.g. `0.01 / fs`)
     seed                 : of the Langevin noise, 0 .. 2^64 - 1; the same seed gives the same trajectory
+    pressure, taup, compressibility : all three given: Berendsen barostat with that target (eV / A^3, e.g.
+                           `1.0 * GPa`), time constant (> 0) and compressibility (A^3 / eV, >= 0), with any
+                           thermostat setting; every frame must be periodic along all three axes
+    mask                 : None = isotropic; three flags (x, y, z) = each free axis follows its own pressure
+
+    Under the barostat the cell of every `Atoms` follows (the atoms are not scaled again), and every `run` call
+    that moved the cells ends with one neighbour-list build for the final cells: an observer at interval 1
+    therefore costs a build per step. `Engine.md_run(..., record_every=...)` gives per-step traces of energy,
+    volume and pressure without cutting the run.
     """
 
     def __init__(self, engine_or_calculator, atoms_or_list, timestep, temperature_K=None, taut=None,
-                 velocities=None, masses=None, friction=None, seed=0):
+                 velocities=None, masses=None, friction=None, seed=0, pressure=None, taup=None,
+                 compressibility=None, mask=None):
         if not (np.isfinite(timestep) and timestep > 0.0):
             raise ValueError("DeviceMD: timestep must be a finite time > 0")
+        barostat = (pressure, taup, compressibility)
+        self._barostat = any(p is not None for p in barostat)
+        if self._barostat:
+            if any(p is None for p in barostat):
+                raise ValueError("DeviceMD: the barostat needs pressure, taup and compressibility")
+            if not np.isfinite(pressure):
+                raise ValueError("DeviceMD: pressure must be finite")
+            if not (np.isfinite(taup) and taup > 0.0):
+                raise ValueError("DeviceMD: taup must be a finite time > 0")
+            if not (np.isfinite(compressibility) and compressibility >= 0.0):
+                raise ValueError("DeviceMD: compressibility must be finite and >= 0")
+            if mask is not None and (np.shape(mask) != (3,) or not np.any(mask)):
+                raise ValueError("DeviceMD: mask must have three flags (x, y, z), at least one of them set")
+        elif mask is not None:
+            raise ValueError("DeviceMD: mask belongs to the barostat (pressure, taup, compressibility)")
         if taut is not None and friction is not None:
             raise ValueError("DeviceMD: taut (Berendsen) and friction (Langevin) exclude each other")
         if friction is not None:
@@ -113,9 +146,14 @@ class DeviceMD:
             engine.md_set_langevin(0.0, 0.0, 0)
             engine.md_set_thermostat(kB * temperature_K if temperature_K is not None else 0.0,
                                      taut if taut is not None else 0.0)
+        if self._barostat:
+            engine.md_set_barostat(pressure, taup, compressibility, mask)
+        else:
+            engine.md_set_barostat(0.0, 0.0, 0.0)
         self._natoms = np.array([len(a) for a in self.atoms_list], dtype=np.int64)
         self.velocities = velocities.copy()
         self.epot = self.ekin = None   # per-frame records of the last state
+        self.volume = self.press = None   # ... under the barostat: V [n_frames] and P_c [n_frames, 3]
         self.n_rebuilds = 0
         self._refresh(engine.md_run(0, self.dt))
 
@@ -136,6 +174,10 @@ class DeviceMD:
             if hasattr(atoms, "set_velocities"):
                 atoms.set_velocities(v[a:a + n])
             a += n
+        if self._barostat:
+            self.volume, self.press = out["volume"][-1].copy(), out["press"][-1].copy()
+            for atoms, h in zip(self.atoms_list, self.engine.md_cells()):
+                atoms.set_cell(h, scale_atoms=False)   # (the device scaled the positions)
         if self._calc is not None:  # what the calculator cached belongs to other coordinates
             self._calc.reset()
             self._calc._forces_local = None
@@ -163,6 +205,24 @@ class DeviceMD:
 
     def get_kinetic_energy(self):
         return float(self.ekin[0]) if self._single else self.ekin.copy()
+
+    def get_volume(self):
+        """Cell volume per frame, in A^3."""
+        v = np.array([abs(np.linalg.det(np.asarray(a.get_cell(complete=True)))) for a in self.atoms_list])
+        return float(v[0]) if self._single else v
+
+    def get_cell(self):
+        """The cell [3, 3] (a batch: [n_frames, 3, 3]) as the library holds it."""
+        h = self.engine.md_cells()
+        return h[0] if self._single else h
+
+    def get_pressure(self):
+        """(P_x + P_y + P_z) / 3 of the last state per frame, in eV / A^3: kinetic part included, as the barostat
+        sees it. Needs the barostat."""
+        if self.press is None:
+            raise ValueError("DeviceMD.get_pressure: the barostat is off (pressure, taup, compressibility)")
+        p = self.press.mean(axis=1)
+        return float(p[0]) if self._single else p
 
     def get_temperature(self):
         """2 KE / (3 N kB) per frame, in K."""
