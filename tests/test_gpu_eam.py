@@ -356,7 +356,9 @@ def test_analytic_hessian_vectors(lib, tmp_path, kind):
     from the unit directions. Models: Zjw04 Ni; Mo-Ni with the cross pair term, a sheared cell and a
     Verlet skin; the Al-Cu setfl tables as splines; nn pair functions through their Hermite tables; the
     reference's default all-nn Mo-Ni model (embedding networks included); ADP with the MishinH functions and
-    with networks for everything."""
+    with networks for everything. This guards the consistency of the force kernels with their dual-arithmetic
+    copies; against the oracle (a stencil of its forces, or the analytic second derivatives of
+    tests/eam_hvp_reference.py for tabulated functions) and on batches of different frames: test_gpu_hvp_oracle.py."""
     from tensoralloy_amd import Atoms, Engine
     from tensoralloy_amd.eam import EamAlloyNN
     if kind == "zjw04":

@@ -649,22 +649,24 @@ def hvp_directions(atoms, seed=2):
     return dR, dh
 
 
-def stencil(nn, atoms, dR, dh, eps):
-    """dF, dW along (dR, dh): (f(-2e) - 8 f(-e) + 8 f(e) - f(2e)) / (12 e) of the oracle's forces / virial."""
+def stencil(nn, atoms, dR, dh, eps, evaluator=oracle_grap_eval):
+    """dF, dW along (dR, dh): (f(-2e) - 8 f(-e) + 8 f(e) - f(2e)) / (12 e) of the oracle's forces / virial
+    (`evaluator`: the oracle of the model's family; test_gpu_hvp_oracle.py passes the SF and EAM ones)."""
     h = np.asarray(atoms.get_cell(complete=True), dtype=float)
     F, W = 0.0, 0.0
     for s, c in ((2, -1.0), (1, 8.0), (-1, -8.0), (-2, 1.0)):
         a = Atoms(symbols=atoms.get_chemical_symbols(), positions=atoms.positions + s * eps * dR,
-                  cell=h + s * eps * dh, pbc=True)
-        o = oracle_grap_eval(nn, a)
+                  cell=h + s * eps * dh, pbc=atoms.pbc)
+        o = evaluator(nn, a)
         F = F + c * o["forces"] / (12 * eps)
         W = W + c * o["virial"] / (12 * eps)
     return F, W
 
 
-def rc_margin(nn, atoms, dR, dh):
-    """min over pairs near rc of |r - rc| / |dD|: how far (in units of the step) the stencil stays from rc."""
-    rc = nn.transformer.rcut
+def rc_margin(nn, atoms, dR, dh, rc=None):
+    """min over pairs near rc of |r - rc| / |dD|: how far (in units of the step) the stencil stays from rc
+    (`rc`: another radius than the model's rcut, e.g. its angular cutoff)."""
+    rc = rc or nn.transformer.rcut
     R, h, i, j, S = frame_pairs(nn, atoms, rc + 0.5)
     D = R[j] - R[i] + S @ h
     dD = dR[j] - dR[i] + S @ dh

@@ -345,7 +345,9 @@ def test_analytic_hessian_vectors_of_the_descriptor_models(lib, kind):
     backward expression in dual arithmetic with w = (dE/dG, H_mlp G-dot); replaces tf.hessians,
     nn/basic.py:411-421, and the cell derivative of the virial, nn/constraint/elastic.py:24-44) against
     central differences of the GPU's own analytic forces and virials along random directions of positions
-    and cell, plus symmetry and the acoustic sum rule of the Hessian from the unit directions."""
+    and cell, plus symmetry and the acoustic sum rule of the Hessian from the unit directions. This guards the
+    consistency of the kernels with their dual-arithmetic copies; against the oracle, at 1e-8, batches of
+    different frames and every other path: test_gpu_hvp_oracle.py."""
     from tensoralloy_amd import Atoms, Engine
     from tests.helpers import fcc, make_nn
     if kind == "ni_default":

@@ -490,7 +490,8 @@ def test_descriptor_tangent_across_the_dispatch(lib, row):
 
 def test_hessian_vectors_of_the_wide_nimo_model(lib):
     """The [128, 128] Ni-Mo model of the C3 configuration (mlp_grad2 at 66,560 B of LDS) against central
-    differences of the GPU's forces and virial (test_gpu_sf.py::test_analytic_hessian_vectors_of_the_descriptor_models)."""
+    differences of the GPU's forces and virial (test_gpu_sf.py::test_analytic_hessian_vectors_of_the_descriptor_models;
+    the same kernels against the oracle at 1e-8: test_gpu_hvp_oracle.py)."""
     from tests.test_gpu_sf import _alloy
     nn = make_nn(["Ni", "Mo"], 6.5, True, [128, 128])
     assert lds_bytes(nn, 4) > LDS_64K
@@ -522,7 +523,7 @@ def test_hessian_vectors_of_the_wide_nimo_model(lib):
 
 def test_hessian_vectors_of_copies_above_1024_tiles(lib):
     """65 copies of a 256-atom frame (1040 tiles) with the same per-copy direction: every copy's dF and dW equal
-    the single frame's."""
+    the single frame's (batches of DIFFERENT frames, against the oracle: test_gpu_hvp_oracle.py)."""
     nn = make_nn(["Ni"], RC, True, [32, 32])
     atoms = fcc(rep=(4, 4, 4), jitter=0.08, seed=14)
     K, n = 65, len(atoms)
