@@ -2,6 +2,7 @@
 # LDS experiment switches of the angular kernels (wrong results by construction):
 #   TA_DEBUG_SKIP bit 4 (16): partner atomics to conflict-free addresses; bit 5 (32): the late partner
 #   reads ({1/r H}, {G species}) conflict-free; bit 6 (64): every partner read conflict-free, no exact test
+# Needs a library built with TA_EXTRA_HIPCC_FLAGS=-DTA_PROBE_SWITCHES: the shipped build ignores these switches.
 OUT=gpurun_out/lds_probe.txt; : > $OUT
 for nf in 1 16; do
   steps=$((nf > 4 ? 10 : 50))

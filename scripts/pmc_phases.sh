@@ -1,6 +1,7 @@
 #!/bin/bash
 # Forward-kernel instruction accounting by phase (TA_DEBUG_SKIP bits: 1 triple bodies, 2 candidate
 # scan, 4 G2 sums, 8 job sweep; wrong results by construction). Usage inside gpurun: bash scripts/pmc_phases.sh
+# Needs a library built with TA_EXTRA_HIPCC_FLAGS=-DTA_PROBE_SWITCHES: the shipped build ignores these switches.
 set -u
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/pmc_phases; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
 for SK in 0 1 8 10 14; do

@@ -2,6 +2,7 @@
 # VALU instruction accounting of the angular kernels: normal run against a run with the triple
 # bodies switched off (TA_DEBUG_NO_TRIPLES=1, wrong results) for 1 and 16 frames.
 # Usage (inside gpurun, repo root): bash scripts/pmc_variants.sh <tag>
+# Needs a library built with TA_EXTRA_HIPCC_FLAGS=-DTA_PROBE_SWITCHES: the shipped build ignores these switches.
 set -u
 TAG=${1:-r02}
 ROOT=$(pwd)

@@ -1,6 +1,7 @@
 #!/bin/bash
 # A/B sweep of the phase-stagger switch of the second-generation angular kernels (experiment).
 # Usage (inside gpurun): bash scripts/stagger_sweep.sh > gpurun_out/stagger.txt
+# Needs a library built with TA_EXTRA_HIPCC_FLAGS=-DTA_PROBE_SWITCHES: the shipped build ignores these switches.
 run() {
   python bench.py --no-cpu-baseline --steps 100 --warmup 10 2>/dev/null | python -c "
 import json,sys,os

@@ -21,14 +21,16 @@
 namespace ta {
 size_t mlp_scratch_doubles(const MlpDev &mlp);
 void launch_mlp_impl(const MlpDev &mlp, int activation, int ndim, const int32_t *atoms, int n_atoms,
-                     const DeviceBatch &b, double *scratch, hipStream_t s, MlpLaunchInfo *info = nullptr);
+                     const DeviceBatch &b, const Options &opt, double *scratch, hipStream_t s,
+                     MlpLaunchInfo *info = nullptr);
 size_t mlp_all_scratch_doubles(const MlpDev *mlps_host, int nel, const int32_t *elem_start);
-size_t td_scratch_doubles(const MlpDev *nets, int nel, int K, const int32_t *elem_start);
+size_t td_scratch_doubles(const MlpDev *nets, int nel, int K, const int32_t *elem_start, bool da_global);
 void launch_td_all(const MlpDev *nets_dev, const MlpDev *nets_host, int nel, int K, int act_h, int act,
-                   int sommerfeld, int ndim, const DeviceBatch &b, const double *T, double *u_atom,
+                   int sommerfeld, int ndim, const DeviceBatch &b, bool da_global, const double *T, double *u_atom,
                    double *s_atom, double *scratch, hipStream_t s, MlpLaunchInfo *info = nullptr);
 void launch_mlp_all(const MlpDev *mlps_dev, const MlpDev *mlps_host, int nel, int activation, int ndim,
-                    const DeviceBatch &b, double *scratch, hipStream_t s, MlpLaunchInfo *info = nullptr);
+                    const DeviceBatch &b, const Options &opt, double *scratch, hipStream_t s,
+                    MlpLaunchInfo *info = nullptr);
 // weight gradients (ta_train.hip)
 int mlp_param_count(const MlpDev &mlp);
 size_t mlp_grad_scratch_doubles(const MlpDev &mlp, int n_atoms);
@@ -86,7 +88,7 @@ void grap_filter_gradient(GrapModel *g, const DeviceBatch &b, double eps, const 
                           const double *kappa, double *scratch, double *grad, hipStream_t s);
 // EAM / ADP (ta_eam.hip)
 struct EamModel;
-EamModel *eam_create(const ta_model_desc *m, std::string &err);
+EamModel *eam_create(const ta_model_desc *m, const Options &opt, std::string &err);
 void eam_destroy(EamModel *);
 void eam_ensure(EamModel *, const DeviceBatch &b);
 void eam_tabulate(EamModel *m, int n_r, const double *r, int n_rho, const double *rho, double *rho_of_r,
@@ -178,11 +180,10 @@ __global__ __launch_bounds__(256) void staged_copy_kernel(double *__restrict__ d
 }
 constexpr size_t kStagedCopyMaxBytes = 4u << 20;  // beyond that the DMA engine's bandwidth wins
 
-// `host_side`: the page-locked end of the transfer (for the fallback's copy direction)
-void staged_copy(double *dst, const double *src, size_t n, bool to_host, hipStream_t s) {
+// `to_host`: the copy direction of the fallback, which Options::staged_copy_dma always takes (A/B switch)
+void staged_copy(double *dst, const double *src, size_t n, bool to_host, const ta::Options &opt, hipStream_t s) {
   if (n == 0) return;
-  static const bool use_dma = std::getenv("TA_STAGED_COPY_DMA") != nullptr;  // A/B switch
-  if (n * sizeof(double) > kStagedCopyMaxBytes || use_dma) {
+  if (n * sizeof(double) > kStagedCopyMaxBytes || opt.staged_copy_dma) {
     HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(double), to_host ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice, s));
     return;
   }
@@ -193,10 +194,9 @@ void staged_copy(double *dst, const double *src, size_t n, bool to_host, hipStre
 
 // Wait for the stream on the latency-critical paths (one MD step has three waits around ~50 us kernels):
 // poll the stream for a short while before blocking, since a blocked thread is woken by an interrupt
-// many microseconds after the work is done. TA_SYNC_BLOCKING=1 goes straight to the blocking wait.
-void wait_stream(hipStream_t s) {
-  static const bool blocking = std::getenv("TA_SYNC_BLOCKING") && std::getenv("TA_SYNC_BLOCKING")[0] == '1';
-  if (!blocking) {
+// many microseconds after the work is done. Options::sync_blocking goes straight to the blocking wait.
+void wait_stream(hipStream_t s, const ta::Options &opt) {
+  if (!opt.sync_blocking) {
     const auto t0 = std::chrono::steady_clock::now();
     for (;;) {
       const hipError_t e = hipStreamQuery(s);
@@ -239,6 +239,7 @@ struct ChunkPlan {
 }  // namespace
 
 struct ta_context {
+  ta::Options opt;  // the environment switches as they stood when ta_create ran
   int device = 0;
   hipStream_t stream = nullptr;      // stream all work is enqueued on
   hipStream_t own_stream = nullptr;  // created by ta_create
@@ -527,7 +528,7 @@ void build_sf_model(ta_context *h, const ta_model_desc *m) {
     if ((c & 3) == 0 || sf.omega[c] != sf.omega[c - 1] || !(sf.eta[c - 1] > 0.0)) continue;
     const double k = sf.eta[c] / sf.eta[c - 1];
     if (k >= 2.0 && k <= 16.0 && k == std::nearbyint(k) && k * sf.eta[c - 1] == sf.eta[c] &&
-        !std::getenv("TA_NO_ETA_CHAIN"))
+        !h->opt.no_eta_chain)
       sf.eta_pow[c] = (signed char)k;
   }
   sf.n_radial_dim = nel * sf.n_rad;
@@ -770,7 +771,7 @@ ta::NlWork nl_work(ta_context *h) {
 // One-pass builder (ta_nlist.hip::nl_build) first: it also WRITES the pairs (key order) while they fit
 // the pair arrays as they stand; when they do not (first batch, or a list that grew) the arrays grow and
 // it runs again. The two-pass builder (count, sizes to the host, fill) stays for what the one-pass one
-// declines: more than 384 neighbours per atom, shifts beyond +-511 cells, TA_NL_TWO_PASS=1.
+// declines: more than 384 neighbours per atom, shifts beyond +-511 cells, Options::nl_two_pass.
 void build_pairs_on_device(ta_context *h, size_t N, int n_bins) {
   using namespace ta;
   HostPairs &hp = h->hp;
@@ -788,9 +789,9 @@ void build_pairs_on_device(ta_context *h, size_t N, int n_bins) {
   unsigned long long *stats = reinterpret_cast<unsigned long long *>(h->stage_out.ptr);
   int32_t *starts = reinterpret_cast<int32_t *>(h->stage_out.ptr + 64);
   const int32_t *si = reinterpret_cast<const int32_t *>(stats);
-  const bool two_pass_only = std::getenv("TA_NL_TWO_PASS") && std::getenv("TA_NL_TWO_PASS")[0] == '1';
+  const bool two_pass_only = h->opt.nl_two_pass;
   h->nl_sorted = false;
-  const bool kernel_writes_host = !(std::getenv("TA_NL_COPY_STARTS") && std::getenv("TA_NL_COPY_STARTS")[0] == '1');
+  const bool kernel_writes_host = !h->opt.nl_copy_starts;
   if (!two_pass_only) {
     {  // the zero block stays clean from list to list while its layout (atoms, bins) does not change
       const unsigned long long *before = h->nl_zero.ptr;
@@ -819,9 +820,9 @@ void build_pairs_on_device(ta_context *h, size_t N, int n_bins) {
       h->nl_zero_clean = false;  // until this list is through (an exception below leaves it marked dirty)
       if (!kernel_writes_host)
         staged_copy(reinterpret_cast<double *>(starts), reinterpret_cast<const double *>(h->pair_start.ptr),
-                    (N + 2) / 2, true, s);
-      staged_copy(reinterpret_cast<double *>(stats), reinterpret_cast<const double *>(h->nl_zero.ptr), 8, true, s);
-      wait_stream(s);
+                    (N + 2) / 2, true, h->opt, s);
+      staged_copy(reinterpret_cast<double *>(stats), reinterpret_cast<const double *>(h->nl_zero.ptr), 8, true, h->opt, s);
+      wait_stream(s, h->opt);
       h->nl_zero_clean = N > 0;  // the kernels ran to the end: histogram cleared, the rest is cleared on entry
       if (si[3] != 0) break;  // beyond the one-pass builder's limits
       if (stats[4] > (unsigned long long)INT32_MAX) throw std::runtime_error("batch too large for 32-bit pair indices");
@@ -884,15 +885,15 @@ void fill_pairs_on_device(ta_context *h) {
 
 #ifdef TA_PHASE_STAMPS
 // diagnostic builds: phase stamps of the angular kernels of the LAST evaluation, written to the file
-// named by TA_PHASE_STAMPS_OUT at ta_destroy (scripts/phase_stamps.sh)
+// named by TA_PHASE_STAMPS_OUT (Options::phase_stamps_out) at ta_destroy (scripts/phase_stamps.sh)
 static void dump_stamps(ta_context *h) {
-  const char *path = std::getenv("TA_PHASE_STAMPS_OUT");
-  if (!path || !h->db.stamps || h->db.n_blk <= 0) return;
+  const std::string &path = h->opt.phase_stamps_out;
+  if (path.empty() || !h->db.stamps || h->db.n_blk <= 0) return;
   const size_t n = (size_t)2 * h->db.n_blk * 8;
   std::vector<unsigned long long> v(n);
   (void)hipStreamSynchronize(h->stream);
   (void)hipMemcpy(v.data(), h->db.stamps, n * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-  FILE *fp = std::fopen(path, "w");
+  FILE *fp = std::fopen(path.c_str(), "w");
   if (!fp) return;
   for (int k = 0; k < 2; ++k)
     for (int b = 0; b < h->db.n_blk; ++b) {
@@ -908,11 +909,11 @@ static void dump_stamps(ta_context *h) {
 void launch_head(ta_context *h, const ta::DeviceBatch &db, hipStream_t s) {
   if (h->td)
     ta::launch_td_all(h->td_dev, h->td_nets, h->n_elements, h->td_K, h->td_act, h->activation,
-                      h->td_sommerfeld ? 1 : 0, h->sf.ndim, db, h->td_T.ptr, h->td_u.ptr, h->td_s.ptr,
+                      h->td_sommerfeld ? 1 : 0, h->sf.ndim, db, h->opt.mlp_da_global, h->td_T.ptr, h->td_u.ptr, h->td_s.ptr,
                       h->mlp_scratch.ptr, s, &h->last_mlp_launch);
   else
-    ta::launch_mlp_all(h->mlp_dev, h->mlp, h->n_elements, h->activation, h->sf.ndim, db, h->mlp_scratch.ptr, s,
-                       &h->last_mlp_launch);
+    ta::launch_mlp_all(h->mlp_dev, h->mlp, h->n_elements, h->activation, h->sf.ndim, db, h->opt, h->mlp_scratch.ptr,
+                       s, &h->last_mlp_launch);
 }
 
 void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
@@ -946,9 +947,8 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
     used[TA_K_MLP] = true;
   } else if (h->kind == TA_MODEL_SF_MLP) {
     // second-generation angular path: 32-byte pair records {D, r^2} in the same buffer
-    // (TA_FULL_RECORDS=1 keeps the 64-byte ones for A/B runs)
-    static const bool full_records = getenv("TA_FULL_RECORDS") != nullptr;
-    h->db.rec4 = (h->sf.angular && h->use_v2 && !full_records) ? h->db.rec : nullptr;
+    // (Options::full_records keeps the 64-byte ones for A/B runs)
+    h->db.rec4 = (h->sf.angular && h->use_v2 && !h->opt.full_records) ? h->db.rec : nullptr;
     if (!h->use_v2) {
       // second-generation forward kernels compute the pair geometry while staging
       begin(TA_K_PAIR_GEOMETRY);
@@ -974,7 +974,7 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
         size_t left = h->chunks_v2.size();
         for (const ChunkPlan &cp : h->chunks_v2) {
           --left;
-          launch_g4_forward_v2(h->sf, cp.ch, cp.ng, cp.nz, geometry, left == 0, db, s);
+          launch_g4_forward_v2(h->sf, cp.ch, cp.ng, cp.nz, geometry, left == 0, db, h->opt, s);
           geometry = false;
         }
       } else
@@ -998,7 +998,7 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
         bool first = true;
         if (h->use_v2)
           for (const ChunkPlan &cp : h->chunks_v2) {
-            h->last_bwd_variant |= launch_backward_v2(h->sf, cp.ch, cp.ng, cp.nz, first, tri, db, s);
+            h->last_bwd_variant |= launch_backward_v2(h->sf, cp.ch, cp.ng, cp.nz, first, tri, db, h->opt, s);
             first = false;
           }
         else
@@ -1014,7 +1014,7 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
       end(TA_K_BACKWARD);
       used[TA_K_BACKWARD] = true;
       begin(TA_K_FORCE_GATHER);
-      launch_force_gather(h->sf, db, s);
+      launch_force_gather(h->sf, db, h->opt.gather_w, s);
       end(TA_K_FORCE_GATHER);
       used[TA_K_FORCE_GATHER] = true;
     }
@@ -1022,7 +1022,7 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
     // 32-byte pair records, as on the second-generation angular path; the `nn` filter network evaluated
     // exactly takes r from the full records its geometry pre-pass writes (through its table it has no pre-pass)
     const bool net_exact = ta::grap_uses_filter_net(h->grap) && !ta::grap_filter_table_knots(h->grap);
-    h->db.rec4 = (!net_exact && !getenv("TA_FULL_RECORDS")) ? h->db.rec : nullptr;
+    h->db.rec4 = (!net_exact && !h->opt.full_records) ? h->db.rec : nullptr;
     begin(TA_K_GRAP);
     launch_grap_forward(h->grap, db, h->sf.eps, s);  // computes the pair geometry while staging
     end(TA_K_GRAP);
@@ -1033,17 +1033,17 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
     used[TA_K_MLP] = true;
     if (need_forces) {
       begin(TA_K_BACKWARD);
-      h->db.own_sums = getenv("TA_NO_OWN_SUMS") ? 0 : 1;  // one wavefront per centre: the sums are nearly free there
+      h->db.own_sums = h->opt.no_own_sums ? 0 : 1;  // one wavefront per centre: the sums are nearly free there
       launch_grap_backward(h->grap, db, s);
       end(TA_K_BACKWARD);
       used[TA_K_BACKWARD] = true;
       begin(TA_K_FORCE_GATHER);
-      launch_force_gather(h->sf, db, s);
+      launch_force_gather(h->sf, db, h->opt.gather_w, s);
       end(TA_K_FORCE_GATHER);
       used[TA_K_FORCE_GATHER] = true;
     }
   } else {
-    h->db.rec4 = getenv("TA_FULL_RECORDS") ? nullptr : h->db.rec;  // 32-byte pair records {D, r^2}
+    h->db.rec4 = h->opt.full_records ? nullptr : h->db.rec;  // 32-byte pair records {D, r^2}
     begin(TA_K_EAM);
     eam_compute(h->eam, db, want, s, nullptr);
     end(TA_K_EAM);
@@ -1125,6 +1125,7 @@ int ta_create(const ta_model_desc *model, int device, ta_handle *out) {
   if (model->n_elements < 1 || model->n_elements > ta::kMaxElements)
     return fail(nullptr, TA_ERR_UNSUPPORTED, "n_elements must be in 1..8");
   ta_context *h = new ta_context();
+  h->opt = ta::options_from_env();
   h->device = device;
   h->kind = model->kind;
   h->n_elements = model->n_elements;
@@ -1153,7 +1154,7 @@ int ta_create(const ta_model_desc *model, int device, ta_handle *out) {
       build_mlp(h, model, h->sf.ndim);
     } else if (model->kind == TA_MODEL_EAM_ALLOY || model->kind == TA_MODEL_EAM_ADP || model->kind == TA_MODEL_EAM_FS) {
       std::string err;
-      h->eam = ta::eam_create(model, err);
+      h->eam = ta::eam_create(model, h->opt, err);
       if (!h->eam) throw std::invalid_argument(err);
       h->rmax = model->rcut;
       std::memset(&h->sf, 0, sizeof(h->sf));
@@ -1227,8 +1228,7 @@ int ta_destroy(ta_handle h) {
 namespace {
 // job lists of the angular kernels (ta_kernels_v2.hip::make_jobs): room for `n_blk` workgroups
 void ensure_job_lists(ta_context *h, size_t n_blk) {
-  static const bool off = std::getenv("TA_NO_JOBS") != nullptr;  // A/B switch: per-lane masks + re-dealing
-  if (off || !h->use_v2 || n_blk == 0) {
+  if (h->opt.no_jobs || !h->use_v2 || n_blk == 0) {  // (no_jobs, A/B switch: per-lane masks + re-dealing)
     h->db.job_count = nullptr;
     return;
   }
@@ -1250,7 +1250,7 @@ void ensure_job_lists(ta_context *h, size_t n_blk) {
 // generation symmetry-function kernels, plain EAM); the others run on the skin list itself, where
 // pairs beyond the cutoff contribute nothing.
 bool filter_applies(const ta_context *h) {
-  if (!(h->skin > 0.0) || h->hp.n_atoms == 0 || std::getenv("TA_NO_LIST_FILTER")) return false;
+  if (!(h->skin > 0.0) || h->hp.n_atoms == 0 || h->opt.no_list_filter) return false;
   if (h->kind == TA_MODEL_SF_MLP) return h->use_v2;
   if (h->kind == TA_MODEL_EAM_ALLOY || h->kind == TA_MODEL_EAM_FS) return ta::eam_is_plain(h->eam);
   return false;
@@ -1272,8 +1272,8 @@ void apply_filter(ta_context *h) {
   h->ex_blk.ensure((size_t)n_run_slots + 4);
   const bool blocks = h->kind == TA_MODEL_SF_MLP;
   // symmetry-function models: no reverse-index launch; force_gather looks the reverse pair up through the map
-  // (TA_FILTER_REV_KERNEL=1: the launch, for A/B)
-  const bool indirect = blocks && !std::getenv("TA_FILTER_REV_KERNEL");
+  // (Options::filter_rev_kernel: the launch, for A/B)
+  const bool indirect = blocks && !h->opt.filter_rev_kernel;
   if (indirect) h->ex_slot_q.ensure(P + 1);
   nl_filter((int)N, (int64_t)P, nel, h->rmax, h->db.pos, h->db.cells, h->db.frame_of_atom,
             h->pair_start.ptr, h->seg_start.ptr, h->pair_j.ptr, h->pair_shift.ptr, h->pair_rev.ptr, h->ex_map.ptr,
@@ -1406,10 +1406,10 @@ void set_frames_impl(ta_context *h, int32_t n_frames, const ta_frame *frames, ta
   }
   // Neighbour list: on the device (ta_nlist.hip; cells thinner than the cutoff along a periodic axis
   // included since round 3: one bin there, several images of it), the host builder (ta_neighbor.cpp)
-  // only for singular / incomplete cells, cells below ~1 A of height, or TA_HOST_NL=1.
+  // only for singular / incomplete cells, cells below ~1 A of height, or Options::host_nl.
   const auto t_nl = std::chrono::steady_clock::now();
   int n_bins = 0;
-  bool device_nl = N > 0 && !(std::getenv("TA_HOST_NL") && std::getenv("TA_HOST_NL")[0] == '1');
+  bool device_nl = N > 0 && !h->opt.host_nl;
   for (int f = 0; f < n_frames && device_nl; ++f) {
     device_nl = ta::nl_make_grid(frames[f], h->r_list, n_bins, grids[f]);
     if (device_nl) n_bins += ta::nl_bins(grids[f]);
@@ -1419,7 +1419,7 @@ void set_frames_impl(ta_context *h, int32_t n_frames, const ta_frame *frames, ta
   // one upload for everything but blk_center (which needs the pair counts)
   if (o_blk)  // (small batches: by a kernel reading the page-locked buffer, see staged_copy; sections are 16-byte aligned)
     staged_copy(reinterpret_cast<double *>(h->inbuf.ptr), reinterpret_cast<const double *>(hb), o_blk / sizeof(double),
-                false, h->stream);
+                false, h->opt, h->stream);
   char *db_ = h->inbuf.ptr;
   h->db.n_frames = n_frames;
   h->db.pos = reinterpret_cast<double *>(db_ + o_pos);
@@ -1446,7 +1446,7 @@ void set_frames_impl(ta_context *h, int32_t n_frames, const ta_frame *frames, ta
     fill_pairs_on_device(h);
     // "reverse pair missing" counter, read after the synchronisation below
     staged_copy(reinterpret_cast<double *>(h->stage_out.ptr), reinterpret_cast<const double *>(h->nl_stats_ptr),
-                8, true, h->stream);
+                8, true, h->opt, h->stream);
   }
   // second-generation angular kernels: workgroups own whole centres (<= kCap pairs)
   // second-generation kernels: 1-3 elements for every channel grid; 4 and 5 elements for
@@ -1457,7 +1457,7 @@ void set_frames_impl(ta_context *h, int32_t n_frames, const ta_frame *frames, ta
     for (const ChunkPlan &cp : h->chunks_v2) shapes_ok = shapes_ok && cp.ng == 2 && cp.nz == 2;
   }
   h->use_v2 = h->kind == TA_MODEL_SF_MLP && h->sf.angular && shapes_ok &&
-              h->hp.nnl_max <= ta::kCapMax && std::getenv("TA_FORCE_V1") == nullptr;
+              h->hp.nnl_max <= ta::kCapMax && !h->opt.force_v1;
   const int cap = std::max(ta::kCapMin, (h->hp.nnl_max + 63) / 64 * 64);
   h->db.cap = cap;
   {
@@ -1485,7 +1485,7 @@ void set_frames_impl(ta_context *h, int32_t n_frames, const ta_frame *frames, ta
     if (nb) {
       if (list_done)  // a kernel on the compute stream reads the page-locked buffer: no DMA hand-over
         staged_copy(reinterpret_cast<double *>(db_ + o_blk), reinterpret_cast<const double *>(blk), ((size_t)nb + 1) / 2,
-                    false, h->stream);
+                    false, h->opt, h->stream);
       else
         HIP_CHECK(hipMemcpyAsync(db_ + o_blk, blk, (size_t)nb * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     }
@@ -1503,7 +1503,7 @@ void set_frames_impl(ta_context *h, int32_t n_frames, const ta_frame *frames, ta
   }
   if (h->td) {
     const size_t N = (size_t)h->db.n_atoms;
-    h->mlp_scratch.ensure(ta::td_scratch_doubles(h->td_nets, h->n_elements, h->td_K, h->db.elem_start));
+    h->mlp_scratch.ensure(ta::td_scratch_doubles(h->td_nets, h->n_elements, h->td_K, h->db.elem_start, h->opt.mlp_da_global));
     h->td_u.ensure(N + 1);
     h->td_s.ensure(N + 1);
     h->td_T.ensure((size_t)h->db.n_frames + 1);
@@ -1527,7 +1527,7 @@ void set_frames_impl(ta_context *h, int32_t n_frames, const ta_frame *frames, ta
     // in flight out of stage_in, whose next writer waits for the stream (upload_pending)
     h->upload_pending = true;
   } else {
-    wait_stream(h->stream);  // staging buffers are reused by the next call
+    wait_stream(h->stream, h->opt);  // staging buffers are reused by the next call
     h->upload_pending = false;
   }
   if (h->pairs_on_device && !list_done) {
@@ -1667,7 +1667,7 @@ int ta_update_positions(ta_handle h, const double *positions, const double *cell
       }
       double *stage = reinterpret_cast<double *>(h->stage_in.ptr + h->o_pos);
       std::memcpy(stage, positions, 3 * N * sizeof(double));
-      staged_copy(h->db.pos, stage, 3 * N, false, h->stream);
+      staged_copy(h->db.pos, stage, 3 * N, false, h->opt, h->stream);
       h->upload_pending = true;
       if (h->filtered) apply_filter(h);  // the exact list of the new positions, on the device
       h->descriptors_valid = false;
@@ -1756,11 +1756,11 @@ const double *results_to_stage(ta_context *h, bool energy, bool forces, bool vir
     h->mirror_want = 0;
     h->stage_out.ensure((hi - lo) * sizeof(double));
     stage = reinterpret_cast<const double *>(h->stage_out.ptr) - lo;
-    staged_copy(reinterpret_cast<double *>(h->stage_out.ptr), h->results.ptr + lo, hi - lo, true, s);
+    staged_copy(reinterpret_cast<double *>(h->stage_out.ptr), h->results.ptr + lo, hi - lo, true, h->opt, s);
   }
   if (descriptors && N)
     HIP_CHECK(hipMemcpyAsync(descriptors, h->db.G, N * h->sf.ndim * sizeof(double), hipMemcpyDeviceToHost, s));
-  wait_stream(s);
+  wait_stream(s, h->opt);
   h->upload_pending = false;
   return stage;
 }
@@ -1861,7 +1861,7 @@ int resident_steps(ta_context *h, const char *who, int n_steps, uint32_t want, E
       if (h->filtered) apply_filter(h);
       compute_impl(h, want, false, nullptr);
     }
-    wait_stream(s);
+    wait_stream(s, h->opt);
     h->upload_pending = false;
     const unsigned mark = status_host[0];
     if (mark == 0u) {
@@ -2743,12 +2743,12 @@ int ta_measure_hbm_copy(ta_handle h, int64_t bytes, int32_t reps, double *gbs) {
     HIP_CHECK(hipEventCreate(&e0));
     HIP_CHECK(hipEventCreate(&e1));
     HIP_CHECK(hipMemsetAsync(src, 0, n * 16, s));
-    static const int per_cu = std::getenv("TA_COPY_WG_PER_CU") ? std::atoi(std::getenv("TA_COPY_WG_PER_CU")) : 8;
+    const int per_cu = h->opt.copy_wg_per_cu;
     const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)256 * std::max(1, per_cu));
     // three ways to copy, the fastest counts (measured on this pool: 4.8-5.2, 5.0-5.5 and 5.0-5.5 TB/s
     // read + written; the microarch guide quotes 6.29 for a float4 copy): the grid-stride kernel, the
     // runtime's device-to-device copy, the kernel with non-temporal loads and stores
-    static const int only = std::getenv("TA_COPY_MODE") ? std::atoi(std::getenv("TA_COPY_MODE")) : -1;
+    const int only = h->opt.copy_mode;
     double best = 0.0;
     for (int mode = 0; mode < 3; ++mode) {
       if (only >= 0 && mode != only) continue;
@@ -2963,7 +2963,7 @@ void backward_only(ta_context *h) {
       if (h->use_v2)
         for (const ChunkPlan &cp : h->chunks_v2) {
           // per apex: the callers keep g[p] per pair (J[c][p]), which the triangle pass distributes differently
-          launch_backward_v2(h->sf, cp.ch, cp.ng, cp.nz, first, false, db, s);
+          launch_backward_v2(h->sf, cp.ch, cp.ng, cp.nz, first, false, db, h->opt, s);
           first = false;
         }
       else

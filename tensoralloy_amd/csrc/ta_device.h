@@ -4,6 +4,7 @@
 
 #include <cstdint>
 
+#include "ta_options.h"
 #include "tensoralloy_amd.h"
 
 namespace ta {
@@ -209,7 +210,7 @@ void launch_mlp(const SFParams &sf, const MlpDev &mlp, int activation, int eleme
                 const DeviceBatch &b, hipStream_t s);
 void launch_backward(const SFParams &sf, const AngChunk &ch, int nb, int ng, int nz,
                      bool first, bool radial_only, const DeviceBatch &b, hipStream_t s);
-void launch_force_gather(const SFParams &sf, const DeviceBatch &b, hipStream_t s);
+void launch_force_gather(const SFParams &sf, const DeviceBatch &b, int gather_w, hipStream_t s);  // Options::gather_w
 void launch_frame_reduce(const DeviceBatch &b, bool want_virial, double *mirror, int64_t n_tail, hipStream_t s);
 
 size_t g4_lds_bytes(int nnl_max);
@@ -219,11 +220,11 @@ size_t v2_lds_bytes(bool backward, int cap, int n_local = 0, int nspec = 0, bool
 int v2_job_stride(int cap);
 // `reduce`: last forward launch of an evaluation, also assembles the descriptor vectors
 void launch_g4_forward_v2(const SFParams &sf, const AngChunk &ch, int ng, int nz, bool geometry,
-                          bool reduce, const DeviceBatch &b, hipStream_t s);
+                          bool reduce, const DeviceBatch &b, const Options &opt, hipStream_t s);
 // `triangles`: one-element default-grid chunks take the triangle-once build (b.job_word_own made by the
 // forward launch, or ownership tested per triple). Returns the build used: 1 per apex, 2 triangles.
 int launch_backward_v2(const SFParams &sf, const AngChunk &ch, int ng, int nz, bool first, bool triangles,
-                       const DeviceBatch &b, hipStream_t s);
+                       const DeviceBatch &b, const Options &opt, hipStream_t s);
 
 // device-side neighbour list (ta_nlist.hip)
 struct NlGrid {  // linked-cell grid of one frame, in fractional coordinates

@@ -1618,6 +1618,7 @@ struct EamModel {
   // training: per-pair weights, scratch and partial sums of the gradient kernels
   double *gcoeff = nullptr, *gscratch = nullptr, *gpartial = nullptr;
   size_t cap_gcoeff = 0, cap_gscratch = 0, cap_gpartial = 0;
+  int gather_w = 0;               // Options::gather_w of the handle, for launch_force_gather
   bool fast_1h = false;           // every pair function is 1 -> H1 -> 1 (no-GEMM kernel)
   int fast_nt = 0;                // > 0: every pair function is 1 -> H1 -> 16 fast_nt -> 1 (fast kernel)
   size_t fast_lds = 0;
@@ -1716,7 +1717,7 @@ size_t net_lds_bytes(const EamModel *e) {
 
 void eam_set_nn_tables(EamModel *m, bool on);
 
-EamModel *eam_create(const ta_model_desc *m, std::string &err) {
+EamModel *eam_create(const ta_model_desc *m, const Options &opt, std::string &err) {
   const int nel = m->n_elements;
   const bool adp = m->kind == TA_MODEL_EAM_ADP;
   const bool fs = m->kind == TA_MODEL_EAM_FS;
@@ -1754,6 +1755,7 @@ EamModel *eam_create(const ta_model_desc *m, std::string &err) {
   EamModel *e = new EamModel();
   std::memset(&e->p, 0, sizeof(e->p));
   e->rcut = m->rcut;
+  e->gather_w = opt.gather_w;
   e->p.nel = nel;
   e->p.adp = adp ? 1 : 0;
   e->fs = fs;
@@ -1839,10 +1841,10 @@ EamModel *eam_create(const ta_model_desc *m, std::string &err) {
     for (int k = 0; k < n_rho; ++k) add(0, k);
     for (int cls = 1; cls < (adp ? 4 : 2); ++cls)
       for (int k = 0; k < npair; ++k) add(cls, k);
-    if (fast && e->fns.n && lds <= 64 * 1024 && !getenv("TA_EAM_NN_GENERIC")) {
+    if (fast && e->fns.n && lds <= 64 * 1024 && !opt.eam_nn_generic) {
       e->fast_nt = h2 / 16;
       e->fast_lds = lds;
-    } else if (all_1h && e->fns.n && !getenv("TA_EAM_NN_GENERIC")) {
+    } else if (all_1h && e->fns.n && !opt.eam_nn_generic) {
       e->fast_1h = true;
       e->fast_lds = lds_1h;
     }
@@ -1893,16 +1895,13 @@ EamModel *eam_create(const ta_model_desc *m, std::string &err) {
   }
   e->p_exact = e->p;
   e->pair_nets_exact = e->pair_nets;
-  if (e->pair_nets) {
-    const char *env = getenv("TA_EAM_NN_TABLES");
-    if (!(env && env[0] == '0')) {
-      try {
-        eam_set_nn_tables(e, true);
-      } catch (const std::exception &ex) {
-        err = ex.what();
-        eam_destroy(e);
-        return nullptr;
-      }
+  if (e->pair_nets && opt.eam_nn_tables) {
+    try {
+      eam_set_nn_tables(e, true);
+    } catch (const std::exception &ex) {
+      err = ex.what();
+      eam_destroy(e);
+      return nullptr;
     }
   }
   return e;
@@ -2768,9 +2767,9 @@ void eam_compute(EamModel *m, const DeviceBatch &b, uint32_t want, hipStream_t s
       hipLaunchKernelGGL((eam_pair_kernel<o, f>), dim3((unsigned)((b.n_pairs + kBlock - 1) / kBlock)),
                          dim3(kBlock), 0, s, m->p, b, m->dF, m->mom, m->pf, ps, m->tabs_dev);
     });
-    launch_force_gather(sf, b, s);
+    launch_force_gather(sf, b, m->gather_w, s);
   } else if (want & (TA_WANT_FORCES | TA_WANT_VIRIAL)) {  // no pairs
-    launch_force_gather(sf, b, s);
+    launch_force_gather(sf, b, m->gather_w, s);
   }
 }
 

@@ -601,10 +601,9 @@ void launch_backward(const SFParams &sf, const AngChunk &ch, int nb, int ng, int
   TA_DISPATCH(launch_bwd_t, sf, ch, b, f, s);
 }
 
-void launch_force_gather(const SFParams &, const DeviceBatch &b, hipStream_t s) {
+void launch_force_gather(const SFParams &, const DeviceBatch &b, int gather_w, hipStream_t s) {
   if (b.n_atoms == 0) return;
-  static const int w_env = getenv("TA_GATHER_W") ? atoi(getenv("TA_GATHER_W")) : 0;  // A/B switch
-  const int W = (w_env == 16 || w_env == 32) ? w_env : (b.n_atoms < 16384 ? 32 : 16);
+  const int W = (gather_w == 16 || gather_w == 32) ? gather_w : (b.n_atoms < 16384 ? 32 : 16);  // (A/B switch)
   const dim3 grid((unsigned)((b.n_atoms + 15) / 16));
   if (W == 32) hipLaunchKernelGGL(force_gather_kernel<32>, grid, dim3(512), 0, s, b);
   else hipLaunchKernelGGL(force_gather_kernel<16>, grid, dim3(256), 0, s, b);

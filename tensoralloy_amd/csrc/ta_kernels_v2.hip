@@ -1485,7 +1485,7 @@ __global__ __launch_bounds__(kBlock)
 }
 
 template <int NSPEC, int NG, int NZ>
-void fwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int geom, hipStream_t s) {
+void fwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int geom, int wpe, hipStream_t s) {
   const dim3 grid((unsigned)b.n_blk), block((unsigned)(b.cap < kBlock ? b.cap : kBlock));
   const size_t lds = v2_lds_bytes(false, b.cap, b.job_count ? NSPEC * NG * NZ : 0, NSPEC);
   if constexpr (NZ == 2) {
@@ -1496,10 +1496,9 @@ void fwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int geo
         // 4000-atom frame are resident at once (they enter within 1.7 us instead of 22 us: before, 1536 ran
         // and the rest followed as a second lock-step round) -- forward 45.3 -> 41.6 us for one frame, and
         // 26.9 -> 24.8 us per frame in 64-frame batches, where the extra wavefront per SIMD hides more of
-        // the LDS latency of the sweep. TA_FWD_WPE=5 selects the 96-register build (A/B).
-        static const int force = getenv("TA_FWD_WPE") ? atoi(getenv("TA_FWD_WPE")) : 0;
+        // the LDS latency of the sweep. `wpe` (Options::fwd_wpe) == 5 selects the 96-register build (A/B).
         if constexpr (NSPEC <= 2) {
-          if (force != 5) {  // (two elements: 55.6 -> 54.2 us for one Ni-Mo frame, 34.9 -> 34.1 us per frame at 16)
+          if (wpe != 5) {  // (two elements: 55.6 -> 54.2 us for one Ni-Mo frame, 34.9 -> 34.1 us per frame at 16)
             hipLaunchKernelGGL((g4_forward_v2_kernel<NSPEC, NG, NZ, 12, true, kCapMin, 6>), grid, block, lds, s, sf, ch,
                                b, geom);
             return;
@@ -1523,7 +1522,7 @@ void fwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int geo
     hipLaunchKernelGGL((g4_forward_v2_kernel<NSPEC, NG, NZ, 0, false, 0>), grid, block, lds, s, sf, ch, b, geom);
 }
 template <int NSPEC, int NG, int NZ>
-void bwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int first, bool tri, int &variant,
+void bwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int first, bool tri, int wpe, int &variant,
            hipStream_t s) {
   const dim3 grid((unsigned)b.n_blk), block((unsigned)(b.cap < kBlock ? b.cap : kBlock));
   const size_t lds = v2_lds_bytes(true, b.cap);
@@ -1533,10 +1532,9 @@ void bwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int fir
     if (tri && (ch.n_hd == 12 || ch.n_hd == 16) && ch.zeta_int[0] == 1 && ch.zeta_int[1] == 4) {
       const size_t lds_t = v2_lds_bytes(true, b.cap, 0, 0, true);
       variant = 2;
-      // 5 wavefronts per SIMD (96 VGPRs, 17 spilled); TA_BWD_WPE=4 (A/B) takes the 4-wavefront build (125 VGPRs, none
-      // spilled), measured slower: 38.7 against 37.0 us on the benchmark frame
-      static const int force = getenv("TA_BWD_WPE") ? atoi(getenv("TA_BWD_WPE")) : 0;
-      if (ch.n_hd == 12 && b.cap == kCapMin && force == 4)
+      // 5 wavefronts per SIMD (96 VGPRs, 17 spilled); `wpe` (Options::bwd_wpe) == 4 (A/B) takes the 4-wavefront build
+      // (125 VGPRs, none spilled), measured slower: 38.7 against 37.0 us on the benchmark frame
+      if (ch.n_hd == 12 && b.cap == kCapMin && wpe == 4)
         hipLaunchKernelGGL((backward_v2_kernel<1, NG, NZ, 12, true, kCapMin, 4, true>), grid, block, lds_t, s, sf, ch,
                            b, first);
       else if (ch.n_hd == 12 && b.cap == kCapMin)
@@ -1556,10 +1554,9 @@ void bwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int fir
       if (b.cap == kCapMin) {
         // (the 80-register build of this kernel, which also lets every workgroup of one frame be resident at
         // once, measured the same as the 96-register one: 48.9-49.3 against 49.5 us for one frame, 33.1
-        // against 33.1 us per frame in batches; TA_BWD_WPE=6 selects it)
-        static const int force = getenv("TA_BWD_WPE") ? atoi(getenv("TA_BWD_WPE")) : 0;
+        // against 33.1 us per frame in batches; `wpe` == 6 selects it)
         if constexpr (NSPEC == 1) {
-          if (force == 6) {
+          if (wpe == 6) {
             hipLaunchKernelGGL((backward_v2_kernel<NSPEC, NG, NZ, 12, true, kCapMin, 6>), grid, block, lds, s, sf, ch,
                                b, first);
             return;
@@ -1630,38 +1627,40 @@ int v2_job_stride(int cap) { return v2_max_jobs(cap); }
   } while (0)
 #endif
 
-// stagger flags for a launch: "<count>[,<shift>]" from the environment (experiment switch)
-static int stagger_bits(const DeviceBatch &b, const char *var) {
-  const char *e = getenv(var);
-  if (getenv("TA_DEBUG_NO_TRIPLES")) return 1 << 24;  // instruction accounting (wrong results)
-  // more accounting switches (wrong results): bit 0 triple bodies, 1 candidate scan, 2 G2 sums, 3 job sweep
-  if (const char *d = getenv("TA_DEBUG_SKIP")) return (atoi(d) & 127) << 24;
-  if (!e) return 0;
-  int n = 0, shift = 3;
-  if (sscanf(e, "%d,%d", &n, &shift) < 1) return 0;
-  (void)b;
-  return ((n & 0xff) << 8) | ((shift & 31) << 16);
+// Probe flags of a launch (bits 8-20: stagger, 24-30: instruction accounting, WRONG results): 0 unless the
+// library is built with -DTA_PROBE_SWITCHES, then from the handle's options
+static int stagger_bits(const Options &opt, bool backward) {
+#ifdef TA_PROBE_SWITCHES
+  if (opt.debug_no_triples) return 1 << 24;
+  // more accounting switches: bit 0 triple bodies, 1 candidate scan, 2 G2 sums, 3 job sweep
+  if (opt.debug_skip >= 0) return opt.debug_skip << 24;
+  return backward ? opt.stagger_bwd : opt.stagger_fwd;
+#else
+  (void)opt;
+  (void)backward;
+  return 0;
+#endif
 }
 
 // `ch` must describe ONE beta (nb == 1).
 void launch_g4_forward_v2(const SFParams &sf, const AngChunk &ch, int ng, int nz, bool geometry,
-                          bool reduce, const DeviceBatch &b, hipStream_t s) {
+                          bool reduce, const DeviceBatch &b, const Options &opt, hipStream_t s) {
   if (b.n_blk == 0) return;
   const int nspec = sf.n_elements;
   // bit 0: compute the pair geometry; bit 1: assemble the descriptors at the end; bit 2: this is
   // the only forward launch (all angular channels are here)
   const int geom = (geometry ? 1 : 0) | (reduce ? 2 : 0) | ((geometry && reduce) ? 4 : 0) |
-                   stagger_bits(b, "TA_STAGGER_FWD");
-  TA_DISPATCH_V2(fwd_t, sf, ch, b, geom, s);
+                   stagger_bits(opt, false);
+  TA_DISPATCH_V2(fwd_t, sf, ch, b, geom, opt.fwd_wpe, s);
 }
 
 int launch_backward_v2(const SFParams &sf, const AngChunk &ch, int ng, int nz, bool first, bool triangles,
-                       const DeviceBatch &b, hipStream_t s) {
+                       const DeviceBatch &b, const Options &opt, hipStream_t s) {
   if (b.n_blk == 0) return 0;
   const int nspec = sf.n_elements;
-  const int f = (first ? 1 : 0) | stagger_bits(b, "TA_STAGGER_BWD");
+  const int f = (first ? 1 : 0) | stagger_bits(opt, true);
   int variant = 0;
-  TA_DISPATCH_V2(bwd_t, sf, ch, b, f, triangles, variant, s);
+  TA_DISPATCH_V2(bwd_t, sf, ch, b, f, triangles, opt.bwd_wpe, variant, s);
   return variant;
 }
 

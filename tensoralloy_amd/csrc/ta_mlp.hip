@@ -386,7 +386,7 @@ constexpr size_t kWaveLdsLimit = 150 * 1024;
 
 // hidden layers when the four-wavefront latency kernel applies (same shapes as the one-wavefront
 // kernel, launches BELOW its tile threshold), else 0
-int mlp_quad_shape(const MlpDev &mlp, int n_tiles);
+int mlp_quad_shape(const MlpDev &mlp, int n_tiles, const Options &opt);
 int mlp_quad_tiles(const MlpDev &mlp);
 
 // ---- four wavefronts per 16 atoms, transposed GEMMs, one barrier per layer ------------------------
@@ -615,10 +615,10 @@ __global__ __launch_bounds__(64 * NT) void mlp_quad_all_kernel(const MlpDev *__r
 constexpr int kWaveMinTiles = 1024;
 
 // number of hidden layers when the one-wavefront kernel applies to `n_tiles` tiles, else 0
-int mlp_wave_shape(const MlpDev &mlp, int n_tiles) {
+int mlp_wave_shape(const MlpDev &mlp, int n_tiles, const Options &opt) {
   const int lh = mlp.n_layers - 1;
-  if (lh < 1 || lh > kWaveMaxHidden || getenv("TA_MLP_TILE_KERNEL")) return 0;
-  if (n_tiles < kWaveMinTiles && !getenv("TA_MLP_WAVE_KERNEL")) return 0;
+  if (lh < 1 || lh > kWaveMaxHidden || opt.mlp_tile_kernel) return 0;
+  if (n_tiles < kWaveMinTiles && !opt.mlp_wave_kernel) return 0;
   for (int l = 0; l < lh; ++l) {
     const MlpLayerDev &ly = mlp.layer[l];
     if (ly.np > 16 * kWaveNT || ly.res || !ly.act) return 0;
@@ -655,11 +655,11 @@ int mlp_quad_tiles(const MlpDev &mlp) {
 }
 
 // number of hidden layers when the four / eight-wavefront kernel applies to `n_tiles` tiles, else 0
-int mlp_quad_shape(const MlpDev &mlp, int n_tiles) {
-  if (getenv("TA_MLP_TILE_KERNEL") || getenv("TA_MLP_WAVE_KERNEL")) return 0;
+int mlp_quad_shape(const MlpDev &mlp, int n_tiles, const Options &opt) {
+  if (opt.mlp_tile_kernel || opt.mlp_wave_kernel) return 0;
   const int nt = mlp_quad_tiles(mlp);
   if (!nt) return 0;
-  if (getenv("TA_MLP_QUAD_KERNEL")) return mlp.n_layers - 1;
+  if (opt.mlp_quad_kernel) return mlp.n_layers - 1;
   if (nt == kWaveNT && (n_tiles >= kWaveMinTiles || n_tiles < kQuadMinTiles)) return 0;
   if (nt == kQuadMaxNT && n_tiles >= 4 * kWaveMinTiles) return 0;  // (no one-wavefront kernel at this width)
   return mlp.n_layers - 1;
@@ -684,13 +684,13 @@ void allow_lds(K kernel, size_t bytes) {
 }
 
 void launch_mlp_impl(const MlpDev &mlp, int activation, int ndim, const int32_t *atoms, int n_atoms,
-                     const DeviceBatch &b, double *scratch, hipStream_t s, MlpLaunchInfo *info) {
+                     const DeviceBatch &b, const Options &opt, double *scratch, hipStream_t s, MlpLaunchInfo *info) {
   if (n_atoms == 0) return;
   // bookkeeping of the launch issued below (ta_mlp_launch_info)
   auto note = [&](int family, int threads, int lh, int nt, unsigned gx, unsigned gy, size_t lds, int da) {
     if (info) *info = MlpLaunchInfo{family, threads, lh, nt, (int)gx, (int)gy, (long long)lds, da};
   };
-  if (const int lh = mlp_quad_shape(mlp, (n_atoms + kMlpRows - 1) / kMlpRows)) {
+  if (const int lh = mlp_quad_shape(mlp, (n_atoms + kMlpRows - 1) / kMlpRows, opt)) {
     const unsigned qblocks = (unsigned)((n_atoms + kMlpRows - 1) / kMlpRows);
     const int nt = mlp_quad_tiles(mlp);
     note(TA_MLP_QUAD, 64 * nt, lh, nt, qblocks, 1, 0, TA_MLP_DA_REGISTERS);
@@ -709,7 +709,7 @@ void launch_mlp_impl(const MlpDev &mlp, int activation, int ndim, const int32_t 
 #undef TA_QUAD
     return;
   }
-  if (const int lh = mlp_wave_shape(mlp, (n_atoms + kMlpRows - 1) / kMlpRows)) {
+  if (const int lh = mlp_wave_shape(mlp, (n_atoms + kMlpRows - 1) / kMlpRows, opt)) {
     const int ntiles = (n_atoms + kMlpRows - 1) / kMlpRows, nw = kWaveThreads / 64;
     const unsigned wblocks = (unsigned)std::min((ntiles + nw - 1) / nw, 256);
     const size_t lds = wave_lds_doubles(mlp, lh) * sizeof(double);
@@ -729,7 +729,7 @@ void launch_mlp_impl(const MlpDev &mlp, int activation, int ndim, const int32_t 
   const unsigned blocks = (unsigned)((n_atoms + kMlpRows - 1) / kMlpRows);
   const size_t lds_da = (size_t)mlp.n_layers * kMlpRows * stride * sizeof(double);
   int da = TA_MLP_DA_GLOBAL;
-  if (lds + lds_da <= 64 * 1024 && !getenv("TA_MLP_DA_GLOBAL")) {
+  if (lds + lds_da <= 64 * 1024 && !opt.mlp_da_global) {
     lds += lds_da;
     scratch = nullptr;
     da = TA_MLP_DA_LDS;
@@ -757,14 +757,14 @@ size_t mlp_all_scratch_doubles(const MlpDev *mlps_host, int nel, const int32_t *
 }
 
 void launch_mlp_all(const MlpDev *mlps_dev, const MlpDev *mlps_host, int nel, int activation, int ndim,
-                    const DeviceBatch &b, double *scratch, hipStream_t s, MlpLaunchInfo *info) {
+                    const DeviceBatch &b, const Options &opt, double *scratch, hipStream_t s, MlpLaunchInfo *info) {
   if (info) *info = MlpLaunchInfo{};
   auto note = [&](int family, int threads, int lh, int nt, unsigned gx, unsigned gy, size_t lds, int da) {
     if (info) *info = MlpLaunchInfo{family, threads, lh, nt, (int)gx, (int)gy, (long long)lds, da};
   };
   if (nel == 1) {  // the model description travels as a kernel argument: scalar loads
     launch_mlp_impl(mlps_host[0], activation, ndim, b.elem_atoms, b.elem_start[1] - b.elem_start[0], b,
-                    scratch, s, info);
+                    opt, scratch, s, info);
     return;
   }
   MlpTiles t;
@@ -784,9 +784,9 @@ void launch_mlp_all(const MlpDev *mlps_dev, const MlpDev *mlps_host, int nel, in
   if (blocks == 0) return;
   // every element's network fits the four / eight-wavefront kernel (same depth and tile count)
   {
-    int qlh = mlp_quad_shape(mlps_host[0], blocks), qnt = mlp_quad_tiles(mlps_host[0]);
+    int qlh = mlp_quad_shape(mlps_host[0], blocks, opt), qnt = mlp_quad_tiles(mlps_host[0]);
     for (int e = 1; e < nel; ++e)
-      if (mlp_quad_shape(mlps_host[e], blocks) != qlh || mlp_quad_tiles(mlps_host[e]) != qnt) qlh = 0;
+      if (mlp_quad_shape(mlps_host[e], blocks, opt) != qlh || mlp_quad_tiles(mlps_host[e]) != qnt) qlh = 0;
     if (qlh) {
       note(TA_MLP_QUAD_ALL, 64 * qnt, qlh, qnt, (unsigned)blocks, 1, 0, TA_MLP_DA_REGISTERS);
 #define TA_QUAD_ALL(LH, NT)                                                                                \
@@ -806,11 +806,11 @@ void launch_mlp_all(const MlpDev *mlps_dev, const MlpDev *mlps_host, int nel, in
     }
   }
   // every element's network has the same one-wavefront shape: one grid row per element
-  int lh = mlp_wave_shape(mlps_host[0], blocks);
+  int lh = mlp_wave_shape(mlps_host[0], blocks, opt);
   size_t wlds = 0;
   int max_tiles = 0;
   for (int e = 0; e < nel; ++e) {
-    if (mlp_wave_shape(mlps_host[e], blocks) != lh) lh = 0;
+    if (mlp_wave_shape(mlps_host[e], blocks, opt) != lh) lh = 0;
     if (lh) wlds = std::max(wlds, wave_lds_doubles(mlps_host[e], lh) * sizeof(double));
     max_tiles = std::max(max_tiles, (b.elem_start[e + 1] - b.elem_start[e] + kMlpRows - 1) / kMlpRows);
   }
@@ -831,7 +831,7 @@ void launch_mlp_all(const MlpDev *mlps_dev, const MlpDev *mlps_host, int nel, in
   size_t lds = 2 * (size_t)kMlpRows * stride * sizeof(double);
   const size_t lds_da = (size_t)layers * kMlpRows * stride * sizeof(double);
   int da = TA_MLP_DA_GLOBAL;
-  if (lds + lds_da <= 64 * 1024 && !getenv("TA_MLP_DA_GLOBAL")) {  // act' slab in LDS, see mlp_kernel
+  if (lds + lds_da <= 64 * 1024 && !opt.mlp_da_global) {  // act' slab in LDS, see mlp_kernel
     lds += lds_da;
     scratch = nullptr;
     da = TA_MLP_DA_LDS;

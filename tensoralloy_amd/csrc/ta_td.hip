@@ -272,7 +272,7 @@ struct TdPlan {
   int threads;
 };
 
-TdPlan td_plan(const MlpDev *nets, int nel, int K, int act_h, int act, int sommerfeld) {
+TdPlan td_plan(const MlpDev *nets, int nel, int K, int act_h, int act, int sommerfeld, bool da_global) {
   TdPlan p;
   int w = 0, wz = 0, dah = 0, dan = 0, widest = 0;
   for (int e = 0; e < nel; ++e) {
@@ -300,7 +300,7 @@ TdPlan td_plan(const MlpDev *nets, int nel, int K, int act_h, int act, int somme
   p.sh.sommerfeld = sommerfeld;
   const size_t base = (size_t)2 * kMlpRows * (p.sh.sP + p.sh.sz) * sizeof(double);
   const size_t with_da = base + (size_t)p.sh.da_tile * sizeof(double);
-  p.da_in_lds = with_da <= kTdLdsLimit && !getenv("TA_MLP_DA_GLOBAL");
+  p.da_in_lds = with_da <= kTdLdsLimit && !da_global;
   p.lds_bytes = p.da_in_lds ? with_da : base;
   if (p.lds_bytes > kTdLdsLimit)
     throw std::domain_error("finite-temperature network too wide for the LDS tile: " + std::to_string(p.lds_bytes) +
@@ -312,17 +312,17 @@ TdPlan td_plan(const MlpDev *nets, int nel, int K, int act_h, int act, int somme
 }  // namespace
 
 // global scratch doubles a launch over this batch needs (0 when the act' region fits in LDS)
-size_t td_scratch_doubles(const MlpDev *nets, int nel, int K, const int32_t *elem_start) {
-  const TdPlan p = td_plan(nets, nel, K, 0, 0, 0);
+size_t td_scratch_doubles(const MlpDev *nets, int nel, int K, const int32_t *elem_start, bool da_global) {
+  const TdPlan p = td_plan(nets, nel, K, 0, 0, 0, da_global);
   if (p.da_in_lds) return 0;
   size_t tiles = 0;
   for (int e = 0; e < nel; ++e) tiles += (size_t)(elem_start[e + 1] - elem_start[e] + kMlpRows - 1) / kMlpRows;
   return tiles * (size_t)p.sh.da_tile;
 }
 
-// `nets_dev` is the device copy of `nets_host[0 .. 3 nel)`; T [n_frames], u_atom / s_atom [N]
+// `nets_dev`: device copy of `nets_host[0 .. 3 nel)`; T [n_frames], u_atom / s_atom [N]; da_global: Options::mlp_da_global
 void launch_td_all(const MlpDev *nets_dev, const MlpDev *nets_host, int nel, int K, int act_h, int act,
-                   int sommerfeld, int ndim, const DeviceBatch &b, const double *T, double *u_atom,
+                   int sommerfeld, int ndim, const DeviceBatch &b, bool da_global, const double *T, double *u_atom,
                    double *s_atom, double *scratch, hipStream_t s, MlpLaunchInfo *info) {
   if (info) *info = MlpLaunchInfo{};
   TdTiles t;
@@ -337,7 +337,7 @@ void launch_td_all(const MlpDev *nets_dev, const MlpDev *nets_host, int nel, int
   t.elem_start[nel] = b.elem_start[nel];
   for (int e = nel + 1; e <= kMaxElements; ++e) t.tile_start[e] = t.elem_start[e] = 0;
   if (blocks == 0) return;
-  const TdPlan p = td_plan(nets_host, nel, K, act_h, act, sommerfeld);
+  const TdPlan p = td_plan(nets_host, nel, K, act_h, act, sommerfeld, da_global);
   if (p.da_in_lds) scratch = nullptr;
   else if (!scratch) throw std::runtime_error("finite-temperature head: scratch slab missing");
   if (info)

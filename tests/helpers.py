@@ -264,7 +264,7 @@ print(json.dumps(out))
 
 def run_child(cases, env, timeout=300, descriptors=True):
     """Evaluate the (name, model, frames) list that `cases` ("module:function") returns in a fresh Python
-    process with `env` added to the environment: the library reads its A/B switches once per process.
+    process with `env` added to the environment (the library reads its A/B switches when a handle is created).
     `descriptors=False` for models without descriptors (EAM / ADP / eam/fs).
     Returns [{"name", "nnl", "res": per-frame result dicts}]."""
     import json

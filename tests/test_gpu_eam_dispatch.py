@@ -28,7 +28,8 @@ test_gpu_sf_dispatch), for analytic functions, spline tables and exact networks.
 Hermite tables the library builds from nn pair functions are another function: rows that use them are held
 to north_star against the reference and to 1e-9 eV / 1e-8 eV/A / 1e-7 eV against the exact networks.
 
-The rows under TA_EAM_NN_TABLES / TA_EAM_NN_GENERIC run in a fresh process (`run_child`), one at a time.
+The library reads TA_EAM_NN_TABLES / TA_EAM_NN_GENERIC when a handle is created: the rows under them set the
+switch before their engine exists and delete it after.
 """
 import functools
 import tempfile
@@ -38,7 +39,7 @@ import numpy as np
 import pytest
 
 from tests.fs_reference import fs_evaluate
-from tests.helpers import fcc, golden_setfl, hcp, make_eam, oracle_eam_eval, run_child
+from tests.helpers import fcc, golden_setfl, hcp, make_eam, oracle_eam_eval
 from tests.test_gpu_sf_dispatch import E_REL, E_TOL, F_REL, F_TOL, W_REL, W_TOL, check, drop
 from tests.test_gpu_sf import _alloy
 
@@ -390,14 +391,19 @@ def test_dispatch_row(lib, row):
 
 @gpu
 @pytest.mark.parametrize("func,env", SWITCHES, ids=["-".join(f"{k}={v}" for k, v in e.items()) for _, e in SWITCHES])
-def test_cached_switches_in_a_fresh_process(lib, func, env):
-    out = run_child(f"tests.test_gpu_eam_dispatch:{func}", env, descriptors=False)
-    cases = globals()[func]()
-    assert [c["name"] for c in out] == [c[0] for c in cases]
-    for case, (name, nn, frames) in zip(out, cases):
+def test_switches_set_before_the_engine(lib, monkeypatch, func, env):
+    from tensoralloy_amd import Engine
+    for name, nn, frames in globals()[func]():
+        for var, value in env.items():
+            monkeypatch.setenv(var, value)
+        eng = Engine(nn)
+        for var in env:
+            monkeypatch.delenv(var)
+        with eng:
+            res = eng.evaluate(frames, descriptors=False)
         builds = eam_builds(nn, _n(frames), FULL, True, env)
         tag = "-".join(f"{k}={v}" for k, v in env.items())
-        for k, (atoms, r) in enumerate(zip(frames, case["res"])):
+        for k, (atoms, r) in enumerate(zip(frames, res)):
             check(r, reference(nn, atoms), f"{tag}/{name}/frame{k}:" + "+".join(
                 sorted(x for x in builds if "<" in x)), descriptors=False)
 

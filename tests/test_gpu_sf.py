@@ -329,7 +329,7 @@ def test_angular_kernels_without_job_lists(lib):
     """`TA_NO_JOBS=1`: the second-generation kernels without the forward -> backward job list (lanes
     re-dealt by popcount, descriptors assembled from the lanes' partial sums in LDS). The path batches
     fall back to when the list buffers are switched off; same parity gate. The library reads the switch
-    once per process, so it runs in a fresh one (more settings and caps: test_gpu_sf_dispatch.py)."""
+    when a handle is created; the child has it set throughout (more settings and caps: test_gpu_sf_dispatch.py)."""
     from tests.helpers import run_child
     out = run_child("tests.test_gpu_sf:no_job_list_cases", {"TA_NO_JOBS": "1"})
     cases = no_job_list_cases()

@@ -14,16 +14,16 @@ Besides the north_star bounds (1e-6 eV, 1e-5 eV/A), results are held to what fp6
 oracle: descriptors to 1e-10, energies to 1e-9 x max(1, |E|), forces to 1e-9 x max(1, max|F|), virial to
 1e-8 x max(1, max|W|). A series coefficient off by one part in 1e-8 passes north_star and fails these.
 
-Also here: the statically cached environment switches (TA_NO_JOBS, TA_FWD_WPE, TA_BWD_WPE, TA_FULL_RECORDS),
-each in a fresh process, and the MD path (exact list filtered on the device from the skin list) for
-multi-species models.
+Also here: the environment switches TA_NO_JOBS, TA_FWD_WPE, TA_BWD_WPE and TA_FULL_RECORDS, which the library
+reads when a handle is created and keeps for that handle (each set before its engine exists and deleted
+after), and the MD path (exact list filtered on the device from the skin list) for multi-species models.
 """
 import os
 
 import numpy as np
 import pytest
 
-from tests.helpers import fcc, make_nn, run_child
+from tests.helpers import fcc, make_nn, mirror_launch
 from tensoralloy_amd import Atoms
 
 gpu = pytest.mark.gpu
@@ -352,7 +352,7 @@ def test_absent_species_and_sparse_centres(lib, nspec):
     run_rows(nn, frames, (1, 192), f"sparse-{nspec}el-h24")
 
 
-# -- statically cached switches, each in a fresh process ---------------------------------------------------
+# -- switches read at ta_create, held by the handle ---------------------------------------------------------
 
 def switch_cases():
     """(name, model, frames): one- and two-element default-grid models at cap 192 and at cap 256, and the
@@ -372,17 +372,51 @@ def switch_cases():
 @gpu
 @pytest.mark.parametrize("var,value", [("TA_NO_JOBS", "1"), ("TA_FWD_WPE", "5"), ("TA_BWD_WPE", "6"),
                                        ("TA_FULL_RECORDS", "1")])
-def test_cached_switches_in_a_fresh_process(lib, var, value):
+def test_switches_set_before_the_engine(lib, monkeypatch, var, value):
     """TA_NO_JOBS (per-lane masks, lanes re-dealt by popcount), TA_FWD_WPE=5 / TA_BWD_WPE=6 (the other kCapMin
-    builds), TA_FULL_RECORDS (64-byte pair records): the library caches each in a function-local static on
-    first use, so each setting runs in a process of its own."""
-    out = run_child("tests.test_gpu_sf_dispatch:switch_cases", {var: value})
-    cases = switch_cases()
-    assert [c["name"] for c in out] == [c[0] for c in cases]
-    for case, (name, nn, frames) in zip(out, cases):
-        assert (case["nnl"] <= 192) == name.endswith("cap192") and case["nnl"] <= 256, (name, case["nnl"])
-        for k, (atoms, r) in enumerate(zip(frames, case["res"])):
+    builds), TA_FULL_RECORDS (64-byte pair records): the library reads each in ta_create and keeps it with the
+    handle, so each is in the environment only while its engine is made."""
+    from tensoralloy_amd import Engine
+    for name, nn, frames in switch_cases():
+        monkeypatch.setenv(var, value)
+        eng = Engine(nn)
+        monkeypatch.delenv(var)
+        with eng:
+            res = eng.evaluate(frames, descriptors=True)
+            nnl = int(eng.info.nnl_max)
+        assert (nnl <= 192) == name.endswith("cap192") and nnl <= 256, (name, nnl)
+        for k, (atoms, r) in enumerate(zip(frames, res)):
             check(r, c_oracle(nn, atoms), f"{var}={value}/{name}/frame{k}")
+
+
+@gpu
+def test_switches_belong_to_the_handle(lib, monkeypatch):
+    """Two engines of one model side by side: A made under TA_MLP_QUAD_KERNEL, TA_HOST_NL and TA_NO_JOBS, B
+    after all three were deleted. Each keeps what it was made with, call after call, and a switch set once
+    both exist (TA_MLP_TILE_KERNEL) reaches neither."""
+    from tensoralloy_amd import Engine
+    nn = make_nn(ELEMENTS[1], 5.0, True, [16, 16])
+    atoms = alloy(ELEMENTS[1])
+    frames = [atoms]
+    o = c_oracle(nn, atoms)
+    made_with = {"TA_MLP_QUAD_KERNEL": "1", "TA_HOST_NL": "1", "TA_NO_JOBS": "1"}
+    for var, value in made_with.items():
+        monkeypatch.setenv(var, value)
+    a = Engine(nn)
+    for var in made_with:
+        monkeypatch.delenv(var)
+    b = Engine(nn)
+    monkeypatch.setenv("TA_MLP_TILE_KERNEL", "1")
+    expect = {"A": ("quad", mirror_launch(nn, frames, "TA_MLP_QUAD_KERNEL"), 0),
+              "B": ("tile", mirror_launch(nn, frames, None), 1)}
+    with a, b:
+        for k, (tag, eng) in enumerate([("A", a), ("B", b), ("A", a)]):
+            r = eng.evaluate(frames, descriptors=True)[0]
+            family, launch, on_device = expect[tag]
+            assert int(eng.info.nnl_max) <= 192
+            assert eng.mlp_launch()["family"] == family and eng.mlp_launch() == launch, (tag, eng.mlp_launch())
+            assert int(eng.info.nl_on_device) == on_device, tag
+            check(r, o, f"handle-{tag}/call{k}")
 
 
 # -- MD path: the exact list filtered on the device from the resident skin list ------------------------------
