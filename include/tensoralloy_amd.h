@@ -530,6 +530,60 @@ typedef struct {
 int ta_relax_set_cell(ta_handle h, int on, const ta_relax_cell_params *p);
 int ta_relax_get_cell(ta_handle h, double *cells, double *deform, double *cell_velocities, double *cell_fmax);
 
+/* Minimum-energy paths: a nudged elastic band under the FIRE above. The resident batch of F >= 3 frames is the
+ * band: image 0 and image F - 1 are fixed endpoints, images 1 .. F - 2 move. All images have the same n atoms
+ * in the same order with the same species, and the same cell and periodicity. Positions are unwrapped, and
+ * differences between images are plain differences, with no minimum-image convention. With X_i, E_i, F_i the
+ * positions, energy and forces of image i, forces of `fixed` atoms read as 0, and ., |.| taken over the 3n
+ * components of an image:
+ *     d+ = X_{i+1} - X_i,   d- = X_i - X_{i-1}
+ *     if   E_{i+1} > E_i > E_{i-1}:  t = d+
+ *     elif E_{i+1} < E_i < E_{i-1}:  t = d-
+ *     else: hi = max(|E_{i+1}-E_i|, |E_{i-1}-E_i|), lo = min(the same two)
+ *           t = d+ hi + d- lo   if E_{i+1} > E_{i-1}   else   t = d+ lo + d- hi
+ *     tau = t / |t|                      (t.t == 0: tau = 0)
+ *     B_i = F_i - (F_i.tau) tau + k (|d+| - |d-|) tau          ordinary image
+ *     B_c = F_c - 2 (F_c.tau) tau                               climbing image, if climb
+ *     B = 0 for images 0 and F-1 and for every fixed atom
+ * This is the improved tangent of Henkelman and Jonsson (J. Chem. Phys. 113, 9978); it matches ASE's
+ * NEB(method='improvedtangent', climb=...) with a single spring constant k. The climbing image c is the
+ * interior image of highest energy, re-chosen at every step; on a tie the lowest index wins.
+ * FIRE then runs on B exactly as documented for ta_relax_run, but as ONE system over the whole band, as ASE
+ * does when an optimiser is attached to a NEB: one dt, one a and one npos; F.v, |F|, |v| and the maxstep clamp
+ * are taken over all 3n(F - 2) moving components; convergence is max over all moving atoms of |B_i| < fmax. No
+ * image freezes on its own: an image under fmax now may be over it once its neighbours move. Both endpoint
+ * images are still evaluated at every step.
+ *   ta_band_params      k in eV / A^2; climb != 0: the climbing image. NULL at ta_relax_set_band: k = 0.1
+ *                       (ASE's default), climb = 0.
+ *   ta_relax_set_band   Needs ta_relax_init, which supplies the FIRE parameters and the `fixed` mask and
+ *                       switches the option off again (as do ta_set_frames and a run that fails). on != 0
+ *                       resets the FIRE state of the band: v = 0, dt, a = astart, npos = 0, first; calling it
+ *                       again, for example to turn climb on after a first run, restarts the optimiser, as one
+ *                       does with ASE. on = 0 returns to independent frames with their per-frame states reset
+ *                       the same way, also when the band was not on: unlike ta_relax_set_cell(on = 0), which only
+ *                       drops its flag, this call always zeroes the FIRE velocities and resets dt, a and npos of
+ *                       every frame, so do not call it in the middle of a relaxation whose state is to carry
+ *                       on. TA_ERR_INVALID, with the argument named by ta_last_error and the state
+ *                       left as it was: fewer than 3 frames; frames that differ in atom count, species order,
+ *                       cell or pbc; k not finite or <= 0; the cell option (ta_relax_set_cell) is on.
+ *                       ta_relax_set_cell(on != 0) while the band is on is TA_ERR_INVALID.
+ *   ta_relax_run        with the option on: steps [f] and converged [f] carry the band's one value for every f;
+ *                       fmax_out [f] is the band's max |B_i| over the moving atoms; max_steps = 0 evaluates,
+ *                       forms B and tests, and moves nothing. The skin / 2 test per atom, the rebuilds and the
+ *                       list bookkeeping are those of a run without the option. ta_relax_get_state reports
+ *                       the band's dt / a / npos for every frame.
+ *   ta_relax_get_band   band_forces / tangents [n_atoms_total][3] (B and tau; rows of the endpoint images are
+ *                       0), energies [n_frames], *climbing (image index, -1 without climb) of the state the
+ *                       last band run ended on; any may be NULL. Needs a band run to have been made since
+ *                       ta_relax_set_band(on != 0); max_steps = 0 counts. */
+typedef struct {
+  double k;
+  int32_t climb;
+  int32_t reserved_;
+} ta_band_params;
+int ta_relax_set_band(ta_handle h, int on, const ta_band_params *p);
+int ta_relax_get_band(ta_handle h, double *band_forces, double *tangents, double *energies, int32_t *climbing);
+
 /* Enqueue all further work of this handle on `stream` (a hipStream_t of the
  * handle's device owned by the caller, e.g. the stream a RCCL collective is
  * ordered against); NULL restores the handle's own stream (to name the legacy

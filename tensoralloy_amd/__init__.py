@@ -18,6 +18,8 @@ from .calculator import TensorAlloyCalculator
 from .engine import Engine
 from .md import DeviceMD, maxwell_boltzmann
 from .optimize import DeviceFIRE
+from .neb import DeviceNEB, interpolate
 
 __all__ = ["Atoms", "AtomicNN", "TemperatureDependentAtomicNN", "FiniteTemperatureOptions", "SymmetryFunction", "GenericRadialAtomicPotential", "UniversalTransformer", "VirtualAtomMap",
-           "TensorAlloyCalculator", "Engine", "load_model", "HAVE_ASE", "DeviceMD", "maxwell_boltzmann", "DeviceFIRE"]
+           "TensorAlloyCalculator", "Engine", "load_model", "HAVE_ASE", "DeviceMD", "maxwell_boltzmann", "DeviceFIRE",
+           "DeviceNEB", "interpolate"]

@@ -21,7 +21,7 @@ LIB_PATH = PKG_DIR / "libtensoralloy_amd.so"
 
 SOURCES = ["ta_api.hip", "ta_kernels.hip", "ta_kernels_v2.hip", "ta_mlp.hip", "ta_eam.hip",
            "ta_nlist.hip", "ta_grap.hip", "ta_train.hip", "ta_hvp.hip", "ta_neighbor.cpp", "ta_td.hip",
-           "ta_td_train.hip", "ta_md.hip", "ta_relax.hip", "ta_options.cpp"]
+           "ta_td_train.hip", "ta_md.hip", "ta_relax.hip", "ta_neb.hip", "ta_options.cpp"]
 OBJ_DIR = CSRC_DIR / "build"
 
 TA_OK = 0
@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = [
     "ta_md_set_barostat", "ta_md_get_cell", "ta_md_get_records",
     "ta_relax_init", "ta_relax_run", "ta_relax_get_state",
     "ta_relax_set_cell", "ta_relax_get_cell",
+    "ta_relax_set_band", "ta_relax_get_band",
     "ta_list_info", "ta_get_list",
 ]
 
@@ -115,6 +116,10 @@ class MdBarostatParams(C.Structure):
 class RelaxCellParams(C.Structure):
     _fields_ = [("cell_factor", C.c_double), ("pressure", C.c_double), ("mask", C.c_int32 * 6),
                 ("hydrostatic", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class BandParams(C.Structure):
+    _fields_ = [("k", C.c_double), ("climb", C.c_int32), ("reserved_", C.c_int32)]
 
 
 def hipcc_path() -> str:
@@ -288,6 +293,8 @@ def load():
     lib.ta_relax_get_state.argtypes = [H, _dp, _dp, _dp, _dp, _ip]
     lib.ta_relax_set_cell.argtypes = [H, C.c_int, C.POINTER(RelaxCellParams)]
     lib.ta_relax_get_cell.argtypes = [H, _dp, _dp, _dp, _dp]
+    lib.ta_relax_set_band.argtypes = [H, C.c_int, C.POINTER(BandParams)]
+    lib.ta_relax_get_band.argtypes = [H, _dp, _dp, _dp, _ip]
     _lib = lib
     return lib
 

@@ -16,6 +16,7 @@
 #include "ta_device.h"
 #include "ta_internal.h"
 #include "ta_md.h"
+#include "ta_neb.h"
 #include "ta_relax.h"
 
 namespace ta {
@@ -385,6 +386,21 @@ struct ta_context {
   ta_relax_cell_params relax_cell_p = {0.0, 0.0, {1, 1, 1, 1, 1, 1}, 0, 0};
   DevBuf<double> relax_cell_h0, relax_cell_cf, relax_cell_G, relax_cell_vel, relax_cell_fmax2, md_ref_cells;
   std::vector<double> relax_cell_G_host, relax_cell_vel_host;
+  // band mode of the relaxation (ta_relax_set_band; the band launches are in ta_neb.hip): the frames are the
+  // images of a nudged elastic band and FIRE runs on the band forces with the whole band as ONE pseudo-frame.
+  // The band owns its force and tangent arrays, the partials of its two launches, the mask (the user's OR-ed
+  // with the two endpoint images), the two copies of the one FIRE record and the pseudo-frame's layout
+  // {atom_start[2], blk_start[2], climbing image}.
+  bool relax_band_on = false;
+  bool relax_band_ran = false;  // a band run left B, tau and the climbing image of the resident state
+  ta_band_params relax_band_p = {0.1, 0, 0};
+  std::vector<uint8_t> relax_fixed_host;  // the mask of ta_relax_init
+  DevBuf<double> band_force, band_tau, band_part;
+  DevBuf<uint8_t> band_fixed;
+  DevBuf<ta::RelaxFrameState> band_state;
+  DevBuf<int32_t> band_layout;
+  ta::RelaxFrameState band_state_host = {};
+  std::vector<double> band_energy_host;  // [F] image energies of the state the last band run ended on
 
   hipEvent_t ev[2 * TA_N_KERNEL_SLOTS + 2] = {nullptr};
   std::string err;
@@ -1213,6 +1229,10 @@ int ta_destroy(ta_handle h) {
   h->relax_fixed.release();
   h->relax_state.release();
   h->relax_count.release();
+  for (auto *b : {&h->band_force, &h->band_tau, &h->band_part}) b->release();
+  h->band_fixed.release();
+  h->band_state.release();
+  h->band_layout.release();
   for (auto *b : {&h->relax_cell_h0, &h->relax_cell_cf, &h->relax_cell_G, &h->relax_cell_vel, &h->relax_cell_fmax2,
                   &h->md_ref_cells})
     b->release();
@@ -1581,6 +1601,7 @@ int ta_set_frames(ta_handle h, int32_t n_frames, const ta_frame *frames, ta_batc
   h->md_valid = false;  // masses and velocities belong to the batch that leaves
   h->relax_valid = false;
   h->relax_cell_on = false;
+  h->relax_band_on = h->relax_band_ran = false;
   return guarded(h, [&]() {
     set_frames_impl(h, n_frames, frames, info);
     if (h->td)  // every frame starts at T = 0, the reference's default (universal.py:295)
@@ -2274,9 +2295,13 @@ int ta_relax_init(ta_handle h, const ta_fire_params *p, const uint8_t *fixed) {
         std::vector<uint8_t> mask(N);
         for (size_t i = 0; i < N; ++i) mask[i] = fixed[i] ? 1 : 0;
         HIP_CHECK(hipMemcpy(h->relax_fixed.ptr, mask.data(), N, hipMemcpyHostToDevice));
+        h->relax_fixed_host = mask;
       } else {
         HIP_CHECK(hipMemset(h->relax_fixed.ptr, 0, N));
+        h->relax_fixed_host.assign(N, 0);
       }
+    } else {
+      h->relax_fixed_host.clear();
     }
     ta::RelaxFrameState st;
     st.dt = q.dt;
@@ -2288,6 +2313,7 @@ int ta_relax_init(ta_handle h, const ta_fire_params *p, const uint8_t *fixed) {
     st.steps = 0;
     h->relax_state_host.assign(F, st);
     h->relax_cell_on = false;
+    h->relax_band_on = h->relax_band_ran = false;
     h->relax_cell_G_host.assign(9 * F, 0.0);
     for (size_t f = 0; f < F; ++f) h->relax_cell_G_host[9 * f] = h->relax_cell_G_host[9 * f + 4] = h->relax_cell_G_host[9 * f + 8] = 1.0;
     h->relax_cell_vel_host.assign(9 * F, 0.0);
@@ -2310,17 +2336,24 @@ int ta_relax_run(ta_handle h, int32_t max_steps, double fmax, uint32_t want, int
   want |= TA_WANT_ENERGY | TA_WANT_FORCES;
   want &= ~(uint32_t)TA_WANT_REUSE_DESCRIPTORS;
   const bool cell = h->relax_cell_on;
+  const bool band = h->relax_band_on;  // (never with `cell`)
   if (cell) want |= TA_WANT_VIRIAL;  // the force on the cell rows
   // a run that fails leaves positions and velocities somewhere on its way and the host's image of the
   // per-frame records behind them: the state is dropped, and only ta_relax_init makes a new one
   h->relax_valid = false;
+  h->relax_band_ran = false;
   h->cell_running = cell;
   const int rc = guarded(h, [&]() {
     const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
     hipStream_t s = h->stream;
     md_plan_blocks(h, ta::kMdChunk);
-    const size_t n_blk = (size_t)h->md_n_blk;
+    // band mode: the FIRE launches see the whole band as one pseudo-frame of N atoms; the band launches cut
+    // every interior image into its own workgroups
+    const int band_n = band ? h->keep_natoms[0] : 0;
+    const int band_blk_per_image = std::max(1, (band_n + ta::kMdChunk - 1) / ta::kMdChunk);
+    const size_t n_blk = band ? std::max<size_t>(1, (N + ta::kMdChunk - 1) / ta::kMdChunk) : (size_t)h->md_n_blk;
     h->relax_part.ensure(4 * n_blk + 1);
+    if (band) h->band_part.ensure(4 * (F - 2) * (size_t)band_blk_per_image + 1);
     HIP_CHECK(hipStreamSynchronize(s));
     if (h->md_ref_builds != h->n_list_builds) {  // the host built the list that is resident: its positions go up once
       if (N) HIP_CHECK(hipMemcpy(h->md_ref.ptr, h->ref_pos.data(), 3 * N * sizeof(double), hipMemcpyHostToDevice));
@@ -2330,6 +2363,12 @@ int ta_relax_run(ta_handle h, int32_t max_steps, double fmax, uint32_t want, int
     std::vector<ta::RelaxFrameState> &st = h->relax_state_host;
     for (auto &r : st) r.converged = 0, r.steps = 0;
     if (F) HIP_CHECK(hipMemcpy(h->relax_state.ptr, st.data(), F * sizeof(ta::RelaxFrameState), hipMemcpyHostToDevice));
+    if (band) {  // the band's one record into copy 0, the pseudo-frame's layout next to the climbing word
+      h->band_state_host.converged = 0, h->band_state_host.steps = 0;
+      HIP_CHECK(hipMemcpy(h->band_state.ptr, &h->band_state_host, sizeof(ta::RelaxFrameState), hipMemcpyHostToDevice));
+      const int32_t layout[5] = {0, (int32_t)N, 0, (int32_t)n_blk, -1};
+      HIP_CHECK(hipMemcpy(h->band_layout.ptr, layout, sizeof(layout), hipMemcpyHostToDevice));
+    }
     HIP_CHECK(hipMemset(h->relax_count.ptr, 0, sizeof(int)));
     if (cell && F) {  // the current G and cell velocity into copy 0, the cells of the resident list next to md_ref
       HIP_CHECK(hipMemcpy(h->relax_cell_G.ptr, h->relax_cell_G_host.data(), 9 * F * sizeof(double), hipMemcpyHostToDevice));
@@ -2371,6 +2410,31 @@ int ta_relax_run(ta_handle h, int32_t max_steps, double fmax, uint32_t want, int
     a.skin = h->skin;
     a.r_list = h->rmax + h->skin;
     a.hydrostatic = h->relax_cell_p.hydrostatic ? 1 : 0;
+    ta::NebLaunch nb = {};
+    if (band) {
+      a.fixed = h->band_fixed.ptr;
+      a.blk_start = h->band_layout.ptr + 2;
+      a.state = h->band_state.ptr;
+      a.n_frames = 1;
+      nb.fixed = h->band_fixed.ptr;
+      nb.part = h->band_part.ptr;
+      nb.band = h->band_force.ptr;
+      nb.climbing = h->band_layout.ptr + 4;
+      nb.status = h->md_status.ptr;
+      nb.k = h->relax_band_p.k;
+      nb.n_images = (int)F, nb.n = band_n, nb.chunk = ta::kMdChunk, nb.blk_per_image = band_blk_per_image;
+      nb.climb = h->relax_band_p.climb ? 1 : 0;
+    }
+    // B (and, with `tangents`, tau) of the resident evaluation
+    auto band_force = [&](int k, bool tangents) {
+      nb.pos = h->db.pos;
+      nb.forces = h->db.forces;
+      nb.energy = h->db.energy;
+      nb.tau = tangents ? h->band_tau.ptr : nullptr;
+      nb.seq = (unsigned)k;
+      ta::launch_neb_force(nb, s);
+      HIP_CHECK(hipGetLastError());
+    };
     int launched = 0;  // launches that ran: the current copy of the state is launched & 1
     auto step = [&](int k, bool drift) {
       // (a rebuild may have moved the batch's arrays: the pointers are taken at every launch)
@@ -2381,6 +2445,11 @@ int ta_relax_run(ta_handle h, int32_t max_steps, double fmax, uint32_t want, int
       a.cells = h->db.cells;
       a.seq = (unsigned)k;
       a.drift = drift ? 1 : 0;
+      if (band) {  // FIRE runs on the band forces of the pseudo-frame; the last launch of a run leaves tau too
+        band_force(k, !drift);
+        a.forces = h->band_force.ptr;
+        a.atom_start = h->band_layout.ptr;
+      }
       ta::launch_relax_step(a, s);
       HIP_CHECK(hipGetLastError());
       launched = k + 1;
@@ -2401,9 +2470,22 @@ int ta_relax_run(ta_handle h, int32_t max_steps, double fmax, uint32_t want, int
     const int done_steps = resident_steps(h, "ta_relax_run", max_steps, want, [&](int q) { step(q, true); }, finished,
                                           &rebuilds, n_rebuilds);
     if (!all_converged) step(done_steps, false);  // the test of the last evaluation
+    else if (band) band_force(done_steps, true);  // (the converged state's B again, with tau)
     HIP_CHECK(hipStreamSynchronize(s));
     h->upload_pending = false;
     if (n_rebuilds) *n_rebuilds = rebuilds;
+    if (band) {
+      ta::RelaxFrameState &b = h->band_state_host;
+      HIP_CHECK(hipMemcpy(&b, h->band_state.ptr + (size_t)(launched & 1), sizeof(ta::RelaxFrameState), hipMemcpyDeviceToHost));
+      for (size_t f = 0; f < F; ++f) {
+        if (steps) steps[f] = b.steps;
+        if (converged) converged[f] = b.converged;
+        if (fmax_out) fmax_out[f] = std::sqrt(b.fmax2);
+      }
+      h->band_energy_host.resize(F);  // what ta_relax_get_band hands out next to B and tau of this state
+      HIP_CHECK(hipMemcpy(h->band_energy_host.data(), h->db.energy, F * sizeof(double), hipMemcpyDeviceToHost));
+      return;
+    }
     if (F)
       HIP_CHECK(hipMemcpy(st.data(), h->relax_state.ptr + (size_t)(launched & 1) * F, F * sizeof(ta::RelaxFrameState),
                           hipMemcpyDeviceToHost));
@@ -2443,8 +2525,8 @@ int ta_relax_run(ta_handle h, int32_t max_steps, double fmax, uint32_t want, int
     }
   });
   h->cell_running = false;
-  if (rc == TA_OK) h->relax_valid = true;
-  else h->relax_cell_on = false;
+  if (rc == TA_OK) h->relax_valid = true, h->relax_band_ran = band;
+  else h->relax_cell_on = h->relax_band_on = false;
   return rc;
 }
 
@@ -2459,10 +2541,11 @@ int ta_relax_get_state(ta_handle h, double *positions, double *velocities, doubl
     if (positions && N) HIP_CHECK(hipMemcpy(positions, h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
     if (velocities && N)
       HIP_CHECK(hipMemcpy(velocities, h->relax_vel.ptr, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
-    for (size_t f = 0; f < F; ++f) {
-      if (dt) dt[f] = h->relax_state_host[f].dt;
-      if (a) a[f] = h->relax_state_host[f].a;
-      if (npos) npos[f] = h->relax_state_host[f].npos;
+    for (size_t f = 0; f < F; ++f) {  // (band mode: the band's one record for every frame)
+      const ta::RelaxFrameState &r = h->relax_band_on ? h->band_state_host : h->relax_state_host[f];
+      if (dt) dt[f] = r.dt;
+      if (a) a[f] = r.a;
+      if (npos) npos[f] = r.npos;
     }
   });
 }
@@ -2475,6 +2558,8 @@ int ta_relax_set_cell(ta_handle h, int on, const ta_relax_cell_params *p) {
     h->relax_cell_on = false;  // (the cells stay as they are)
     return TA_OK;
   }
+  if (h->relax_band_on)
+    return fail(h, TA_ERR_INVALID, "ta_relax_set_cell: the band option is on (ta_relax_set_band); cells along a band stay fixed");
   ta_relax_cell_params q = {0.0, 0.0, {1, 1, 1, 1, 1, 1}, 0, 0};
   if (p) q = *p;
   if (!std::isfinite(q.cell_factor) || q.cell_factor < 0.0)
@@ -2538,6 +2623,88 @@ int ta_relax_get_cell(ta_handle h, double *cells, double *deform, double *cell_v
         for (size_t f = 0; f < F; ++f) cell_fmax[f] = 0.0;
       }
     }
+  });
+}
+
+int ta_relax_set_band(ta_handle h, int on, const ta_band_params *p) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_relax_set_band: no resident batch");
+  if (!h->relax_valid) return fail(h, TA_ERR_INVALID, "ta_relax_set_band called before ta_relax_init");
+  const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
+  ta_band_params q = {0.1, 0, 0};  // ASE's spring constant
+  if (on) {
+    if (p) q = *p;
+    if (F < 3) return fail(h, TA_ERR_INVALID, "ta_relax_set_band: a band needs at least 3 frames, the batch has " + std::to_string(F));
+    const size_t n = (size_t)h->keep_natoms[0];
+    for (size_t f = 1; f < F; ++f) {
+      const std::string who = "ta_relax_set_band: frame " + std::to_string(f) + " differs from frame 0 in its ";
+      if ((size_t)h->keep_natoms[f] != n) return fail(h, TA_ERR_INVALID, who + "atom count");
+      if (!std::equal(h->keep_species.begin(), h->keep_species.begin() + n, h->keep_species.begin() + f * n))
+        return fail(h, TA_ERR_INVALID, who + "species");
+      if (!std::equal(h->ref_cells.begin(), h->ref_cells.begin() + 9, h->ref_cells.begin() + 9 * f))
+        return fail(h, TA_ERR_INVALID, who + "cell");
+      if (!std::equal(h->keep_pbc.begin(), h->keep_pbc.begin() + 3, h->keep_pbc.begin() + 3 * f))
+        return fail(h, TA_ERR_INVALID, who + "pbc");
+    }
+    if (!std::isfinite(q.k) || !(q.k > 0.0)) return fail(h, TA_ERR_INVALID, "ta_relax_set_band: k must be finite and > 0");
+    if (h->relax_cell_on)
+      return fail(h, TA_ERR_INVALID, "ta_relax_set_band: the cell option is on (ta_relax_set_cell); cells along a band stay fixed");
+  }
+  return guarded(h, [&]() {
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    h->upload_pending = false;
+    // the optimiser starts again, in either direction: v = 0, dt, a = astart, npos = 0, first
+    ta::RelaxFrameState st;
+    st.dt = h->relax_p.dt;
+    st.a = h->relax_p.astart;
+    st.fmax2 = 0.0;
+    st.npos = 0;
+    st.first = 1;
+    st.converged = 0;
+    st.steps = 0;
+    h->relax_state_host.assign(F, st);
+    h->band_state_host = st;
+    if (N) HIP_CHECK(hipMemset(h->relax_vel.ptr, 0, 3 * N * sizeof(double)));
+    h->relax_band_ran = false;
+    if (!on) {
+      h->relax_band_on = false;
+      return;
+    }
+    const size_t n = (size_t)h->keep_natoms[0];
+    h->band_force.ensure(3 * N + 1);
+    h->band_tau.ensure(3 * N + 1);
+    h->band_fixed.ensure(N + 1);
+    h->band_state.ensure(2);
+    h->band_layout.ensure(5);
+    std::vector<uint8_t> mask(h->relax_fixed_host);  // the user's mask OR-ed with the two endpoint images
+    mask.resize(N, 0);
+    std::fill(mask.begin(), mask.begin() + n, 1);
+    std::fill(mask.end() - n, mask.end(), 1);
+    if (N) {
+      HIP_CHECK(hipMemcpy(h->band_fixed.ptr, mask.data(), N, hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemset(h->band_force.ptr, 0, 3 * N * sizeof(double)));  // (the endpoints' rows stay 0)
+      HIP_CHECK(hipMemset(h->band_tau.ptr, 0, 3 * N * sizeof(double)));
+    }
+    h->relax_band_p = q;
+    h->relax_band_on = true;
+  });
+}
+
+int ta_relax_get_band(ta_handle h, double *band_forces, double *tangents, double *energies, int32_t *climbing) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_relax_get_band: no resident batch");
+  if (!h->relax_valid) return fail(h, TA_ERR_INVALID, "ta_relax_get_band called before ta_relax_init");
+  if (!h->relax_band_on) return fail(h, TA_ERR_INVALID, "ta_relax_get_band: the band option is off (ta_relax_set_band)");
+  if (!h->relax_band_ran)
+    return fail(h, TA_ERR_INVALID, "ta_relax_get_band: no ta_relax_run of this band yet (max_steps = 0 counts)");
+  return guarded(h, [&]() {
+    const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    h->upload_pending = false;
+    if (band_forces && N) HIP_CHECK(hipMemcpy(band_forces, h->band_force.ptr, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+    if (tangents && N) HIP_CHECK(hipMemcpy(tangents, h->band_tau.ptr, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+    if (energies) std::memcpy(energies, h->band_energy_host.data(), F * sizeof(double));
+    if (climbing) HIP_CHECK(hipMemcpy(climbing, h->band_layout.ptr + 4, sizeof(int32_t), hipMemcpyDeviceToHost));
   });
 }
 

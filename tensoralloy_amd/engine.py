@@ -437,6 +437,33 @@ class Engine:
                                                 _lib.as_dp(fm)))
         return {"cells": cells, "deform": G, "cell_velocities": v, "cell_fmax": fm}
 
+    def relax_set_band(self, on=True, k=0.1, climb=False):
+        """Treat the resident batch as the images of a nudged elastic band in `relax_run`
+        (`ta_relax_set_band`): the first and the last frame are fixed endpoints, the others move under the
+        improved-tangent band force with one spring constant `k` (eV / A^2), and with `climb` the interior
+        image of highest energy climbs. FIRE then runs over the whole band as one system. Every call with
+        `on` restarts the optimiser (v = 0, dt, a); `on=False` returns to independent frames and resets their
+        FIRE states the same way, also when the band was not on. Needs
+        `relax_init`, which supplies the FIRE parameters and the fixed mask and switches the option off again."""
+        if self.info is None:
+            raise ValueError("relax_set_band: no resident batch (call set_frames first)")
+        if not on:
+            self._check(self._lib.ta_relax_set_band(self._handle, 0, None))
+            return
+        bp = _lib.BandParams(float(k), 1 if climb else 0, 0)
+        self._check(self._lib.ta_relax_set_band(self._handle, 1, C.byref(bp)))
+
+    def relax_band_state(self) -> dict:
+        """forces (the band forces B) and tangents [n_atoms, 3], energies [n_frames] and climbing (image index,
+        -1 without climb) of the state the last band run ended on (`ta_relax_get_band`)."""
+        if self.info is None:
+            raise ValueError("relax_band_state: no resident batch (call set_frames first)")
+        N, F = int(self.info.n_atoms), int(self.info.n_frames)
+        b, t, e = np.empty((N, 3)), np.empty((N, 3)), np.empty(F)
+        c = C.c_int32(-1)
+        self._check(self._lib.ta_relax_get_band(self._handle, _lib.as_dp(b), _lib.as_dp(t), _lib.as_dp(e), C.byref(c)))
+        return {"forces": b, "tangents": t, "energies": e, "climbing": int(c.value)}
+
     def relax_run(self, max_steps: int, fmax: float, want: int = None) -> dict:
         """FIRE steps of the resident batch on the device (`ta_relax_run`) until every frame has
         max_i |F_i| < `fmax` (eV / A) or the others have taken `max_steps` steps; continues from the state the
