@@ -6,12 +6,13 @@
 #     python scripts/run_config.py sf 1 20 && python scripts/phase_stamps.py gpurun_out/stamps.txt
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
+cd $ROOT
 CS=$ROOT/tensoralloy_amd/csrc
 OUT=$CS/build/stamps
 mkdir -p $OUT
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -pthread -I$ROOT/include -I$CS -DTA_PHASE_STAMPS -DTA_V2_FEW"
 pids=""
-for f in ta_api.hip ta_kernels.hip ta_kernels_v2.hip ta_mlp.hip ta_eam.hip ta_nlist.hip ta_grap.hip ta_train.hip ta_hvp.hip ta_neighbor.cpp; do
+for f in $(python -c "from tensoralloy_amd import _lib; print(' '.join(_lib.SOURCES))"); do  # every translation unit of the library
   /opt/rocm/bin/hipcc $FLAGS -c $CS/$f -o $OUT/${f%.*}.o &
   pids="$pids $!"
 done

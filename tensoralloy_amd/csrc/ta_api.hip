@@ -326,6 +326,7 @@ struct ta_context {
   // exact list of the current step, extracted on the device from the resident skin list (nl_filter)
   DevBuf<int32_t> ex_pair_i, ex_pair_j, ex_pair_shift, ex_pair_rev, ex_pair_start, ex_pair_stop, ex_seg_start, ex_counts,
       ex_map, ex_blk, ex_slot_q;
+  DevBuf<ta::BlockHeader> ex_hdr;              // the exact list's run headers (DeviceBatch::blk_hdr)
   bool filtered = false;                       // db points at the ex_* arrays
   // a copy out of stage_in may still be in flight (set by ta_update_positions, cleared by every wait
   // for the stream on the step path): whoever rewrites stage_in waits for the stream first. (An event
@@ -1210,6 +1211,7 @@ int ta_destroy(ta_handle h) {
   for (auto *b : {&h->ex_pair_i, &h->ex_pair_j, &h->ex_pair_shift, &h->ex_pair_rev, &h->ex_pair_start, &h->ex_pair_stop,
                   &h->ex_seg_start, &h->ex_counts, &h->ex_map, &h->ex_blk, &h->ex_slot_q})
     b->release();
+  h->ex_hdr.release();
   h->masks.release(); h->job_word.release(); h->job_count.release();
   h->job_word_own.release(); h->job_count_own.release();
   for (auto *b : {&h->nl_wrap, &h->nl_binid, &h->nl_bin_count, &h->nl_bin_start, &h->nl_bin_cursor,
@@ -1290,6 +1292,7 @@ void apply_filter(ta_context *h) {
   h->ex_map.ensure(P + 1);
   const int n_run_slots = nl_filter_blocks((int)N);
   h->ex_blk.ensure((size_t)n_run_slots + 4);
+  h->ex_hdr.ensure((size_t)n_run_slots + 1);
   const bool blocks = h->kind == TA_MODEL_SF_MLP;
   // symmetry-function models: no reverse-index launch; force_gather looks the reverse pair up through the map
   // (Options::filter_rev_kernel: the launch, for A/B)
@@ -1299,7 +1302,7 @@ void apply_filter(ta_context *h) {
             h->pair_start.ptr, h->seg_start.ptr, h->pair_j.ptr, h->pair_shift.ptr, h->pair_rev.ptr, h->ex_map.ptr,
             h->ex_seg_start.ptr, h->ex_pair_start.ptr, h->ex_pair_stop.ptr, h->ex_pair_i.ptr, h->ex_pair_j.ptr,
             h->ex_pair_shift.ptr, h->ex_pair_rev.ptr, indirect ? h->ex_slot_q.ptr : nullptr, h->db.cap,
-            blocks ? h->ex_blk.ptr : nullptr, h->stream);
+            blocks ? h->ex_blk.ptr : nullptr, blocks ? h->ex_hdr.ptr : nullptr, h->stream);
   h->db.slot_q = indirect ? h->ex_slot_q.ptr : nullptr;
   h->db.rev_super = indirect ? h->pair_rev.ptr : nullptr;
   h->db.rev_map = indirect ? h->ex_map.ptr : nullptr;
@@ -1313,6 +1316,7 @@ void apply_filter(ta_context *h) {
   h->db.pair_rev = h->ex_pair_rev.ptr;
   if (blocks) {
     h->db.blk_center = h->ex_blk.ptr;
+    h->db.blk_hdr = h->ex_hdr.ptr;
     h->db.n_blk = n_run_slots;  // 16 run slots per group of 16 centres; unused ones are empty runs
     h->db.blk_groups = n_run_slots / 16;
     h->db.n_blk_dev = nullptr;
@@ -1385,7 +1389,10 @@ void set_frames_impl(ta_context *h, int32_t n_frames, const ta_frame *frames, ta
   const size_t o_astart = align16(o_foa + N * sizeof(int32_t));
   const size_t o_elem = align16(o_astart + (F + 1) * sizeof(int32_t));
   const size_t o_blk = align16(o_elem + N * sizeof(int32_t));
-  const size_t total = align16(o_blk + (N + 2) * sizeof(int32_t));
+  // the run headers (ta::BlockHeader, 64-byte aligned) go behind the run starts actually written, so that one
+  // copy takes both; room for one run per atom
+  auto align64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
+  const size_t total = align64(o_blk + (N + 2) * sizeof(int32_t)) + (N + 1) * sizeof(ta::BlockHeader);
   h->stage_in.ensure(total);
   h->inbuf.ensure(total);
   char *hb = h->stage_in.ptr;
@@ -1501,13 +1508,23 @@ void set_frames_impl(ta_context *h, int32_t n_frames, const ta_frame *frames, ta
     h->db.n_blk = nb ? nb - 1 : 0;
     h->res_n_blk = h->db.n_blk;
     h->o_blk = o_blk;
+    // one header per run: what the angular workgroup of the run reads instead of the list
+    const size_t o_hdr = align64(o_blk + (size_t)nb * sizeof(int32_t));
+    ta::BlockHeader *hdr = reinterpret_cast<ta::BlockHeader *>(hb + o_hdr);
+    const int block = std::min(cap, 256);  // lanes of an angular workgroup
+    for (int r = 0; r < h->db.n_blk; ++r) {
+      const int32_t *ps = h->hp.pair_start.data() + blk[r];
+      ta::make_block_header(hdr[r], blk[r], blk[r + 1] - blk[r], ps[0], block, [&](int k) { return ps[k + 1] - ps[k]; });
+    }
+    h->db.blk_hdr = reinterpret_cast<const ta::BlockHeader *>(db_ + o_hdr);
     ensure_job_lists(h, (size_t)h->db.n_blk);
     if (nb) {
+      const size_t bytes = o_hdr + (size_t)h->db.n_blk * sizeof(ta::BlockHeader) - o_blk;  // a multiple of 16
       if (list_done)  // a kernel on the compute stream reads the page-locked buffer: no DMA hand-over
-        staged_copy(reinterpret_cast<double *>(db_ + o_blk), reinterpret_cast<const double *>(blk), ((size_t)nb + 1) / 2,
+        staged_copy(reinterpret_cast<double *>(db_ + o_blk), reinterpret_cast<const double *>(blk), bytes / sizeof(double),
                     false, h->opt, h->stream);
       else
-        HIP_CHECK(hipMemcpyAsync(db_ + o_blk, blk, (size_t)nb * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(db_ + o_blk, blk, bytes, hipMemcpyHostToDevice, h->stream));
     }
   }
   if (h->kind == TA_MODEL_SF_MLP) {

@@ -58,6 +58,8 @@ struct AngChunk {
   double hd[kMaxHd]; // power-series coefficients in u (v2 kernels, beta[0] only)
 };
 
+struct BlockHeader;
+
 struct DeviceBatch {
   int64_t n_atoms = 0, n_pairs = 0;
   int n_frames = 0, nnl_max = 0;
@@ -79,6 +81,9 @@ struct DeviceBatch {
   // looked up by the one kernel that needs it (force_gather) instead of a launch that writes it out
   const int32_t *slot_q = nullptr, *rev_super = nullptr, *rev_map = nullptr;
   int32_t *blk_center = nullptr; // [n_blk+1] first centre of every v2 workgroup
+  // [n_blk] what a second-generation angular workgroup needs to know about its run, written by whoever
+  // writes blk_center (see BlockHeader); the GRAP and first-generation kernels and ta_get_list read blk_center
+  const BlockHeader *blk_hdr = nullptr;
   int n_blk = 0;
   // MD step (ta_nlist.hip::filter_group_kernel): > 0 = number of groups of 16 centres, each owning 16
   // run slots of which the later ones are usually empty. Workgroup b then takes slot
@@ -134,6 +139,43 @@ struct DeviceBatch {
   double *virial = nullptr; // [F][9]
   double *batch_energy = nullptr;  // [1]
 };
+
+// One run of the angular workgroup packing (a run slot of `blk_center`) as ONE 64-byte record, so that a
+// workgroup learns its centres, its pairs and every centre's first pair with a single (scalar) load
+// instead of the chain blk_center -> pair_start -> pair_i -> pair_start / pair_stop, each link one L2
+// round trip that nothing in the workgroup can proceed past. Written with the packing, by
+// make_block_header; nothing in it changes between the packing and the evaluation.
+struct alignas(64) BlockHeader {
+  int32_t c0;        // first centre of the run
+  int32_t info;      // bits 0-7: centres of the run, 0 = unused run slot; kHdrOnePass
+  int32_t s0;        // first pair of the run in the list
+  int32_t M;         // pairs of the run (<= cap <= kCapMax)
+  uint16_t rel[24];  // rel[k], k <= centres: first pair of centre c0 + k relative to s0; M from `centres` on
+};
+static_assert(sizeof(BlockHeader) == 64, "one 64-byte record per run slot");
+static_assert(kMaxCentersPerBlock + 1 <= 24 && kCapMax < (1 << 16), "16-bit entries, one per centre and the end");
+// every pair of the run has a lane (M <= workgroup size) and every centre's rotation schedule fits one
+// 64-bit candidate mask (n / 2 <= 64): the angular kernels take their single-scan paths
+constexpr int32_t kHdrOnePass = 1 << 8;
+
+// `count(k)`: pairs of centre c0 + k; `block`: lanes of an angular workgroup, min(cap, 256)
+template <class CountFn>
+__host__ __device__ inline void make_block_header(BlockHeader &h, int c0, int ncent, int s0, int block, CountFn count) {
+  int m = 0;
+  bool wide = false;
+  for (int k = 0; k < 24; ++k) {
+    h.rel[k] = (uint16_t)m;
+    if (k < ncent) {
+      const int n = count(k);
+      wide = wide || (n >> 1) > 64;
+      m += n;
+    }
+  }
+  h.c0 = c0;
+  h.s0 = s0;
+  h.M = m;
+  h.info = ncent | ((ncent > 0 && m <= block && !wide) ? kHdrOnePass : 0);
+}
 
 // Ownership of an angular triangle. A triangle {i, j, k} of three DISTINCT atoms (all three sides
 // below acut) is evaluated once in the backward pass, by one of its vertices: with the indices sorted,
@@ -282,7 +324,8 @@ void nl_filter(int n_atoms, int64_t n_super, int nel, double rmax, const double 
                const int32_t *frame_of_atom, const int32_t *start_super, const int32_t *seg_super,
                const int32_t *pj_super, const int32_t *ps_super, const int32_t *rev_super, int32_t *map,
                int32_t *seg_exact, int32_t *pair_start, int32_t *pair_stop, int32_t *pi_out, int32_t *pj_out,
-               int32_t *ps_out, int32_t *rev_out, int32_t *slot_q, int cap, int32_t *blk_center, hipStream_t s);
+               int32_t *ps_out, int32_t *rev_out, int32_t *slot_q, int cap, int32_t *blk_center, BlockHeader *blk_hdr,
+               hipStream_t s);
 void nl_fill(int n_atoms, int64_t n_pairs, int nel, double rmax, const double *pos,
              const int32_t *species, const int32_t *frame_of_atom, const NlGrid *grids, NlWork &w,
              int32_t *pair_i, int32_t *pair_j, int32_t *pair_shift, int32_t *pair_rev, hipStream_t s);

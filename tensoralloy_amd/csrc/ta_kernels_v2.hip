@@ -83,6 +83,62 @@ __device__ __forceinline__ constexpr bool kProbe(int, int) { return false; }
 #define TA_STAMP(b, kernel, k) do {} while (0)
 #endif
 
+// A workgroup's BlockHeader (ta_device.h) in scalar registers: the address is the same for every lane, the
+// sixteen words are read once, and everything the staging and mask phases need to know about the list (the
+// run's extent, the centre of a pair, that centre's first pair and neighbour count) follows from them
+// without another global load. `rel2[k]`: entries 2 k and 2 k + 1 of BlockHeader::rel.
+struct HeaderRegs {
+  int c0, ncent, s0, M;
+  bool one_pass;
+  uint32_t rel2[12];
+};
+// `with_rel` false: the first sixteen bytes only (the backward kernel looks centres up in its LDS table)
+__device__ __forceinline__ HeaderRegs load_header(const BlockHeader *hp, bool with_rel = true) {
+  const uint4 *src = reinterpret_cast<const uint4 *>(hp);
+  const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+  const uint4 w0 = src[0], w1 = with_rel ? src[1] : zero, w2 = with_rel ? src[2] : zero, w3 = with_rel ? src[3] : zero;
+  auto sc = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+  HeaderRegs h;
+  h.c0 = (int)sc(w0.x);
+  const int info = (int)sc(w0.y);
+  h.ncent = info & 255;
+  h.one_pass = (info & kHdrOnePass) != 0;
+  h.s0 = (int)sc(w0.z);
+  h.M = (int)sc(w0.w);
+  h.rel2[0] = sc(w1.x); h.rel2[1] = sc(w1.y); h.rel2[2] = sc(w1.z); h.rel2[3] = sc(w1.w);
+  h.rel2[4] = sc(w2.x); h.rel2[5] = sc(w2.y); h.rel2[6] = sc(w2.z); h.rel2[7] = sc(w2.w);
+  h.rel2[8] = sc(w3.x); h.rel2[9] = sc(w3.y); h.rel2[10] = sc(w3.z); h.rel2[11] = sc(w3.w);
+  return h;
+}
+// BlockHeader::rel[k], k a compile-time constant (the words are never indexed by a variable)
+__device__ __forceinline__ int header_rel(const HeaderRegs &h, int k) {
+  return (int)((h.rel2[k >> 1] >> (16 * (k & 1))) & 0xffffu);
+}
+// the centre of pair `item` (< M) of the run: its index in the run, its first pair and its neighbour count.
+// Entries from the number of centres on hold M, so they never compare below `item`.
+__device__ __forceinline__ void centre_of(const HeaderRegs &h, int item, int &ci, int &base, int &n) {
+  ci = 0;
+  base = 0;
+  int end = header_rel(h, 1);
+#pragma unroll
+  for (int k = 1; k < kMaxCentersPerBlock; ++k) {
+    const bool ge = item >= header_rel(h, k);
+    ci += ge ? 1 : 0;
+    base = ge ? header_rel(h, k) : base;
+    end = ge ? header_rel(h, k + 1) : end;
+  }
+  n = end - base;
+}
+
+// The same from the table of the centres' first pairs in LDS (`cstart`, filled from the header before the
+// staging barrier): what the sweeps use, so that the header's words need not stay in registers
+__device__ __forceinline__ void centre_of_lds(const int *cstart, int ncent, int item, int &ci, int &base, int &n) {
+  ci = 0;
+  for (int k = 1; k < ncent; ++k) ci += (item >= cstart[k]) ? 1 : 0;
+  base = cstart[ci];
+  n = cstart[ci + 1] - base;
+}
+
 __device__ __forceinline__ int angular_term2(int s1, int s2, int nel) {
   int a = s1 < s2 ? s1 : s2, b = s1 < s2 ? s2 : s1;
   return a * nel - (a * (a - 1)) / 2 + (b - a);
@@ -166,15 +222,24 @@ __device__ __forceinline__ double hd_value(const SFParams &sf, const AngChunk &c
 // three derivatives (see there). H = 0 (pair beyond acut) gives L = 0; such a pair has no triples.
 // `jidx` (forward kernel, one element, owned job lists): the neighbour's atom index per pair slot, in place
 // of the species.
+// `hd`: the centre of a pair comes from the workgroup's header (centre_of), never from pair_i / pair_start:
+// the centre's position and frame are then loaded in the same round trip as the pair's neighbour and shift,
+// and the cell in the same one as the neighbour's position. `one_el`: every species is 0, nothing to look up.
 template <int HD>
 __device__ __forceinline__ void stage(const SFParams &sf, const AngChunk &ch, double beta, const DeviceBatch &b,
-                                      const Fields &f, int s0, int M, int geom = 0, bool forward = false,
-                                      int *jidx = nullptr) {
+                                      const Fields &f, const HeaderRegs &hd, bool one_el, int geom = 0,
+                                      bool forward = false, int *jidx = nullptr) {
+  const int s0 = hd.s0, M = hd.M;
   for (int item = threadIdx.x; item < M; item += blockDim.x) {
     double2 v0, v1, v2;
+    int ci = 0, cbase = 0, cn = 0;
+    if (geom || forward) centre_of(hd, item, ci, cbase, cn);
+    const bool want_j = geom || jidx || !one_el;
+    const int j = want_j ? b.pair_j[s0 + item] : 0;
+    const double spj = one_el ? 0.0 : (double)b.species[j];
     if (geom) {
       const int64_t p = (int64_t)s0 + item;
-      const int i = b.pair_i[p], j = b.pair_j[p];
+      const int i = hd.c0 + ci;
       const double *h = b.cells + 9 * (size_t)b.frame_of_atom[i];
       const double sx = (double)b.pair_shift[3 * p], sy = (double)b.pair_shift[3 * p + 1],
                    sz = (double)b.pair_shift[3 * p + 2];
@@ -211,8 +276,6 @@ __device__ __forceinline__ void stage(const SFParams &sf, const AngChunk &ch, do
     f.xy[item] = v0;
     f.zr[item] = v1;
     if (forward) {
-      const int ci = b.pair_i[s0 + item];
-      const int cbase = b.pair_start[ci] - s0, cn = pair_stop_of(b, ci) - b.pair_start[ci];
       const int k0 = 2 * cbase + (item - cbase);
       f.xf[k0] = f.xf[k0 + cn] = (float)v0.x;
       f.yf[k0] = f.yf[k0 + cn] = (float)v0.y;
@@ -230,9 +293,9 @@ __device__ __forceinline__ void stage(const SFParams &sf, const AngChunk &ch, do
       }
     }
     f.ih[item] = make_double2(v2.x, H);
-    if (jidx) jidx[item] = b.pair_j[s0 + item];
-    else if (forward) f.sp1[item] = (double)b.species[b.pair_j[s0 + item]];
-    else f.gs[item] = make_double2(L, (double)b.species[b.pair_j[s0 + item]]);
+    if (jidx) jidx[item] = j;
+    else if (forward) f.sp1[item] = spj;
+    else f.gs[item] = make_double2(L, spj);
   }
   __syncthreads();
 }
@@ -654,20 +717,26 @@ __global__ __launch_bounds__(kBlock)
   const Fields f = carve(lds, kCap, true);
   const int slot = b.blk_groups > 0 ? 16 * ((int)blockIdx.x % b.blk_groups) + (int)blockIdx.x / b.blk_groups
                                     : (int)blockIdx.x;
-  const int c0 = b.blk_center[slot], c1 = b.blk_center[slot + 1];
-  if (c0 >= c1) return;  // an unused run slot of the MD step's packing (ta_nlist.hip::filter_group_kernel)
-  const int s0 = b.pair_start[c0];
-  const int M = pair_stop_of(b, c1 - 1) - s0;  // a workgroup's centres are contiguous in the list
+  // everything about the run comes from its header: one load, a workgroup's centres are contiguous in the list
+  const BlockHeader *hp = b.blk_hdr + slot;
+  const HeaderRegs hd = load_header(hp);
+  if (hd.ncent == 0) return;  // an unused run slot of the MD step's packing (ta_nlist.hip::filter_group_kernel)
+  const int c0 = hd.c0, c1 = hd.c0 + hd.ncent;
+  const int s0 = hd.s0, M = hd.M;
   const double beta = ch.beta[0];
+  // cstart[k]: first pair of centre c0 + k (M from the end on), with or without job lists (the room is there
+  // either way, see v2_lds_bytes)
+  int *const cstart_w = reinterpret_cast<int *>(reinterpret_cast<char *>(lds) + v2_counter_offset(kCap)) + 40;
+  if (threadIdx.x >= 40 && threadIdx.x < 40 + 17) cstart_w[threadIdx.x - 40] = hp->rel[threadIdx.x - 40];
   if (b.job_count) {  // job counters and partial sums: cleared before the staging barrier
     char *raw = reinterpret_cast<char *>(lds);
     int *cnt = reinterpret_cast<int *>(raw + v2_counter_offset(kCap));
     if (threadIdx.x < 40) cnt[threadIdx.x] = 0;
-    else if (threadIdx.x < 40 + 17 && (int)threadIdx.x - 40 <= c1 - c0)  // cstart[k]: first pair of centre c0 + k
-      cnt[threadIdx.x] = ((int)threadIdx.x - 40 < c1 - c0 ? b.pair_start[c0 + threadIdx.x - 40] : s0 + M) - s0;
     else if (threadIdx.x >= 64 && (int)threadIdx.x - 64 < (c1 - c0) * (NSPEC + 1)) {  // segl[k][sg]
       const int k = ((int)threadIdx.x - 64) / (NSPEC + 1), sg = ((int)threadIdx.x - 64) % (NSPEC + 1);
-      cnt[60 + k * kSegW + sg] = b.seg_start[(size_t)(c0 + k) * (NSPEC + 1) + sg] - s0;
+      // one element: the only segment of a centre is its pairs
+      cnt[60 + k * kSegW + sg] = NSPEC == 1 ? (int)hp->rel[k + sg]
+                                            : b.seg_start[(size_t)(c0 + k) * (NSPEC + 1) + sg] - s0;
     }
     if (NSPEC == 1 && b.job_word_own && threadIdx.x < 20) cnt[kOwnCtl + threadIdx.x] = 0;  // ohist
     double *P0 = reinterpret_cast<double *>(raw + v2_counter_offset(kCap) + kJobCtlBytes);
@@ -676,7 +745,7 @@ __global__ __launch_bounds__(kBlock)
   // owned job lists (one element only): the neighbours' atom indices take the place of their species (sp1)
   int *jidx = (NSPEC == 1 && b.job_word_own && b.job_count) ? reinterpret_cast<int *>(f.sp1) : nullptr;
   TA_STAMP(b, 0, 0);
-  stage<HD>(sf, ch, beta, b, f, s0, M, geom, true, jidx);
+  stage<HD>(sf, ch, beta, b, f, hd, NSPEC == 1, geom, true, jidx);
   TA_STAMP(b, 0, 1);
   if (b.job_count && threadIdx.x == 0) {
     // sslot[k][sg]: first partial-sum slot of segment (centre c0 + k, neighbour species sg), one slot per
@@ -725,9 +794,8 @@ __global__ __launch_bounds__(kBlock)
         pslot = sslot[ci * kSegW + sg] + ((item - segl[ci * kSegW + sg]) >> 2);
       }
     } else {
-      const int i = b.pair_i[p];
-      base = b.pair_start[i] - s0;
-      n = pair_stop_of(b, i) - b.pair_start[i];
+      int ci;
+      centre_of_lds(cstart_w, c1 - c0, item, ci, base, n);
     }
     const int a = item - base;
     const double2 axy = f.xy[item], azr = f.zr[item], aih = f.ih[item];
@@ -861,18 +929,15 @@ __global__ __launch_bounds__(kBlock)
   // balanced path: one pair per lane, one scan pass for every centre of the workgroup
   int item = threadIdx.x;
   const bool active = item < M;
-  int n_own = 0;
-  if (active) {
-    const int i = b.pair_i[s0 + item];
-    n_own = pair_stop_of(b, i) - b.pair_start[i];
-  }
-  const bool one_pass = M <= (int)blockDim.x && !__syncthreads_or(active && (n_own >> 1) > 64);
+  // the centre of this lane's pair and whether one scan pass serves every centre: both from the header
+  int ci_own = 0, base_own = 0, n_own = 0;
+  if (active) centre_of(hd, item, ci_own, base_own, n_own);
+  const bool one_pass = hd.one_pass;
   if (one_pass) {
     unsigned long long mask = 0ull;
     if (active) {
       const int64_t p = (int64_t)s0 + item;
-      const int i = b.pair_i[p];
-      const int base = b.pair_start[i] - s0;
+      const int base = base_own;
       const int smax = (f.ih[item].y != 0.0) ? n_own / 2 : 0;
       if (smax > 0 && !(flags & (1 << 25))) mask = partner_mask(sf, f, base, n_own, item - base, 1, smax);
       if (b.masks && !b.job_count) b.masks[p] = mask;  // (with a job list the backward kernel reads that instead)
@@ -885,7 +950,7 @@ __global__ __launch_bounds__(kBlock)
       jl.hist = reinterpret_cast<int *>(raw + v2_counter_offset(kCap));
       jl.start = jl.hist + 20;
       double *P = reinterpret_cast<double *>(raw + v2_counter_offset(kCap) + kJobCtlBytes);
-      const int n_jobs = make_jobs(jl, active, item, active ? b.pair_i[s0 + item] - c0 : 0, mask);
+      const int n_jobs = make_jobs(jl, active, item, ci_own, mask);
       TA_STAMP(b, 0, 3);
       const size_t jbase = (size_t)blockIdx.x * b.job_stride;
       if (threadIdx.x == 0) b.job_count[blockIdx.x] = n_jobs;
@@ -920,7 +985,7 @@ __global__ __launch_bounds__(kBlock)
       if (active) {
         const int64_t p = (int64_t)s0 + threadIdx.x;
         // the first pair of every group of four carries the group's sum, the others zero
-        const int ci = b.pair_i[p] - c0, sg = NSPEC == 1 ? 0 : (int)f.sp1[threadIdx.x];
+        const int ci = ci_own, sg = NSPEC == 1 ? 0 : (int)f.sp1[threadIdx.x];
         const int *segl = jl.hist + 60, *sslot = segl + kMaxCentersPerBlock * kSegW;
         const int rel = (int)threadIdx.x - segl[ci * kSegW + sg];
         const int pidx = sslot[ci * kSegW + sg] + (rel >> 2);
@@ -1016,16 +1081,16 @@ __global__ __launch_bounds__(kBlock)
   double *gacc = lds + kNF * kCap + kCap / 8;
   const int slot = b.blk_groups > 0 ? 16 * ((int)blockIdx.x % b.blk_groups) + (int)blockIdx.x / b.blk_groups
                                     : (int)blockIdx.x;
-  const int c0 = b.blk_center[slot], c1 = b.blk_center[slot + 1];
-  if (c0 >= c1) return;  // unused run slot
-  const int s0 = b.pair_start[c0];
-  const int M = pair_stop_of(b, c1 - 1) - s0;
+  const BlockHeader *hp = b.blk_hdr + slot;
+  const HeaderRegs hd = load_header(hp, false);
+  if (hd.ncent == 0) return;  // unused run slot
+  const int c0 = hd.c0, c1 = hd.c0 + hd.ncent;
+  const int s0 = hd.s0, M = hd.M;
   const double beta = ch.beta[0];
   for (int k = threadIdx.x; k < 3 * kCap; k += blockDim.x) gacc[k] = 0.0;
   // cstart[k]: first pair of centre c0 + k (see job_centre), in the kCap bytes in front of gacc
   int *cstart = reinterpret_cast<int *>(gacc) - 20;
-  if ((int)threadIdx.x <= c1 - c0 && threadIdx.x < 17)
-    cstart[threadIdx.x] = ((int)threadIdx.x < c1 - c0 ? b.pair_start[c0 + threadIdx.x] : s0 + M) - s0;
+  if (threadIdx.x < 17) cstart[threadIdx.x] = hp->rel[threadIdx.x];
   // One-element default grid: the polynomial coefficients of dE/dG (see `pc` below) once per CENTRE,
   // by the last lanes of the workgroup while the others stage, instead of four dependent global loads
   // and twenty operations in the prologue of every job
@@ -1081,8 +1146,23 @@ __global__ __launch_bounds__(kBlock)
       pn4[item] = pc[4];
     }
   }
+  // The forward kernel's job list (TRI: the list of owned triangles, make_owned_jobs): up to four rounds of
+  // one job per lane. Its count and the words of the FIRST round are asked for here, in front of the staging
+  // and without waiting for the count, so that they are there when the records are staged; the words of the
+  // later rounds are asked for behind the staging (they arrive while the first round is swept; holding them
+  // in registers through the staging spilt four more). A lane's slots lie inside the workgroup's own slice
+  // of `job_stride` words whatever the count is; words beyond the count are discarded.
+  const int32_t *jcount = TRI ? b.job_count_own : b.job_count;
+  const uint32_t *jword = TRI ? b.job_word_own : b.job_word;
+  const size_t jbase = (size_t)blockIdx.x * b.job_stride;
+  uint32_t jw0 = 0u;
+  int n_listed = -1;
+  if (jcount) {
+    n_listed = jcount[blockIdx.x];
+    if ((int)threadIdx.x < b.job_stride) jw0 = jword[jbase + threadIdx.x];  // job_slot(0, lane) = lane
+  }
   TA_STAMP(b, 1, 0);
-  stage<HD>(sf, ch, beta, b, f, s0, M);
+  stage<HD>(sf, ch, beta, b, f, hd, NSPEC == 1);
   TA_STAMP(b, 1, 1);
   const int nel = sf.n_elements;
 
@@ -1114,9 +1194,9 @@ __global__ __launch_bounds__(kBlock)
       base = cstart[ci];
       n = cstart[ci + 1] - base;
     } else {
-      i = b.pair_i[p];
-      base = b.pair_start[i] - s0;
-      n = pair_stop_of(b, i) - b.pair_start[i];
+      int ci;
+      centre_of_lds(cstart, c1 - c0, item, ci, base, n);
+      i = c0 + ci;
     }
     const int a = item - base;
     const double2 axy = f.xy[item], azr = f.zr[item], aih = f.ih[item], ags = f.gs[item];
@@ -1219,9 +1299,9 @@ __global__ __launch_bounds__(kBlock)
       base = cstart[ci];
       n = cstart[ci + 1] - base;
     } else {
-      i = b.pair_i[p];
-      base = b.pair_start[i] - s0;
-      n = pair_stop_of(b, i) - b.pair_start[i];
+      int ci;
+      centre_of_lds(cstart, c1 - c0, item, ci, base, n);
+      i = c0 + ci;
     }
     const int a = item - base;
     const double2 axy = f.xy[item], azr = f.zr[item], aih = f.ih[item], ags = f.gs[item];
@@ -1385,25 +1465,15 @@ __global__ __launch_bounds__(kBlock)
   {
     int item = threadIdx.x;
     const bool active = item < M;
-    int n_own = 0;
-    if (active) {
-      const int i = b.pair_i[s0 + item];
-      n_own = pair_stop_of(b, i) - b.pair_start[i];
-    }
-    const bool one_pass = M <= (int)blockDim.x && !__syncthreads_or(active && (n_own >> 1) > 64);
-    // TRI: the list of owned triangles (make_owned_jobs)
-    const int32_t *jcount = TRI ? b.job_count_own : b.job_count;
-    const uint32_t *jword = TRI ? b.job_word_own : b.job_word;
-    const int n_jobs = (one_pass && jcount) ? jcount[blockIdx.x] : -1;
+    const bool one_pass = hd.one_pass;
+    const int n_jobs = one_pass ? n_listed : -1;  // (-1 also from the forward kernel: it left no list)
     if (n_jobs >= 0) {  // the forward kernel's job list (see make_jobs): no scan, no sort here
-      const size_t jbase = (size_t)blockIdx.x * b.job_stride;
-      // at most four rounds (four jobs per pair, one pair per lane): the words of all of them are
-      // fetched before the first job runs, not one dependent global load per round
       uint32_t jws[4];
+      jws[0] = jw0;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int slot = job_slot(r, threadIdx.x, blockDim.x);
-        jws[r] = slot < n_jobs ? jword[jbase + slot] : 0u;
+      for (int r = 1; r < 4; ++r) {
+        const int js = job_slot(r, threadIdx.x, blockDim.x);
+        jws[r] = js < n_jobs ? jword[jbase + js] : 0u;
       }
       TA_STAMP(b, 1, 2);
 #pragma unroll
@@ -1420,6 +1490,8 @@ __global__ __launch_bounds__(kBlock)
       unsigned long long mask = 0ull;
       if (active) {
         const int64_t p = (int64_t)s0 + item;
+        int ci, base, n_own;
+        centre_of_lds(cstart, c1 - c0, item, ci, base, n_own);
         const int smax = (f.ih[item].y != 0.0) ? n_own / 2 : 0;
         if (smax > 0) mask = b.masks[p];  // the forward kernel's candidate mask (always stored)
       }
@@ -1444,12 +1516,12 @@ __global__ __launch_bounds__(kBlock)
     if (first) {
       // radial (G2) share: s_p D / r  (sf.py:101-108 differentiated)
       const double *wr;
+      int ci = 0;
+      for (int k = 1; k < c1 - c0; ++k) ci += (item >= cstart[k]) ? 1 : 0;
       if (use_rtab) {
-        int ci = 0;
-        for (int k = 1; k < c1 - c0; ++k) ci += (item >= cstart[k]) ? 1 : 0;
         wr = rtab + ci * kRTab + (NSPEC == 1 ? 0 : (int)f.gs[item].y * sf.n_rad);
       } else {
-        const int i = b.pair_i[p];
+        const int i = c0 + ci;
         wr = b.dEdG + (size_t)i * sf.ndim + radial_term2(b.species[i], (int)f.gs[item].y) * sf.n_rad;
       }
       const double r2 = f.zr[item].y, inv_r = f.ih[item].x;

@@ -715,8 +715,10 @@ __global__ __launch_bounds__(64 * kFilterGroup) void filter_group_kernel(
     int n_atoms, int nel, double rmax, const double *pos, const double *cells,
     const int32_t *frame_of_atom, const int32_t *start_super, const int32_t *seg_super, const int32_t *pj_super,
     const int32_t *ps_super, int32_t *seg_exact, int32_t *pair_start, int32_t *pair_stop, int32_t *pi_out,
-    int32_t *pj_out, int32_t *ps_out, int32_t *map, int32_t *slot_q, int cap, int32_t *blk_center) {
+    int32_t *pj_out, int32_t *ps_out, int32_t *map, int32_t *slot_q, int cap, int32_t *blk_center,
+    BlockHeader *blk_hdr) {
   __shared__ int cnt[kFilterGroup][kFilterMaxEl + 1];
+  __shared__ BlockHeader hdr[kFilterGroup];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int i0 = blockIdx.x * kFilterGroup;
   const int i = i0 + w;
@@ -760,22 +762,57 @@ __global__ __launch_bounds__(64 * kFilterGroup) void filter_group_kernel(
   // run never crosses a group (kFilterGroup = kMaxCentersPerBlock), so every group owns the 16 run slots
   // [16 g, 16 g + 16); slots it does not need are empty runs (first centre = last), whose workgroups
   // leave at once. No prefix sum over the batch, no separate packing launch.
+  // The neighbour counts are in hand here, so every run slot's header (BlockHeader: the run's centres, its
+  // pairs and every centre's first pair, which the angular kernels read instead of the list) is made in the
+  // same breath: the group's pairs start at the group's offset in the skin list and are contiguous. Thread 0
+  // cuts the runs as before and notes each run's first centre, centres and first pair; sixteen lanes of its
+  // wavefront then build one header each, and the wavefront writes the group's 1 KB of headers, 16 bytes per lane.
+  __shared__ int run_k0[kFilterGroup], run_nc[kFilterGroup], run_first[kFilterGroup];
+  const int iend = min(i0 + kFilterGroup, n_atoms);
+  auto pairs_of = [&](int k) {
+    int n = 0;
+    for (int s = 0; s < nel; ++s) n += cnt[k][s];
+    return n;
+  };
   if (blk_center && threadIdx.x == 0) {
     int slot = i0, load = 0, nc = 0;
-    const int iend = min(i0 + kFilterGroup, n_atoms);
+    int total = start_super[i0];
     for (int k = 0; k < kFilterGroup && i0 + k < n_atoms; ++k) {
-      int n = 0;
-      for (int s = 0; s < nel; ++s) n += cnt[k][s];
+      const int n = pairs_of(k);
       if (k == 0 || load + n > cap || nc >= kMaxCentersPerBlock) {
+        if (k > 0) run_nc[slot - 1 - i0] = nc;
+        run_k0[slot - i0] = k;
+        run_first[slot - i0] = total;
         blk_center[slot++] = i0 + k;
         load = 0;
         nc = 0;
       }
       load += n;
+      total += n;
       ++nc;
     }
-    for (; slot < i0 + kFilterGroup; ++slot) blk_center[slot] = iend;
+    run_nc[slot - 1 - i0] = nc;
+    for (; slot < i0 + kFilterGroup; ++slot) {
+      blk_center[slot] = iend;
+      run_k0[slot - i0] = iend - i0;  // unused run slot: no centres
+      run_nc[slot - i0] = 0;
+      run_first[slot - i0] = 0;
+    }
     if (iend == n_atoms) blk_center[i0 + kFilterGroup] = n_atoms;  // closes the last group's last run
+  }
+  if (blk_center && threadIdx.x < 64) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (threadIdx.x < kFilterGroup) {
+      const int k0 = run_k0[threadIdx.x];
+      make_block_header(hdr[threadIdx.x], i0 + k0, run_nc[threadIdx.x], run_first[threadIdx.x], cap < 256 ? cap : 256,
+                        [&](int c) { return pairs_of(k0 + c); });
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    reinterpret_cast<uint4 *>(blk_hdr + i0)[threadIdx.x] = reinterpret_cast<const uint4 *>(hdr)[threadIdx.x];
   }
   if (!act) return;
   int off = start_super[i0];  // the group keeps its place in the skin list
@@ -1012,19 +1049,21 @@ void nl_reverse_sorted(int64_t n_pairs, int nel, const int32_t *species, const i
 // Exact list of the current positions out of the resident skin list (all device, no host round trip):
 // exact (i, j, S, rev), pair_start / pair_stop, seg_start, and the
 // workgroup packing for the angular kernels when `blk_center` is given ([nl_filter_blocks(n_atoms) + 1]
-// entries; the grid of those kernels is nl_filter_blocks(n_atoms)). `map` is a work buffer.
+// entries, and nl_filter_blocks(n_atoms) headers in `blk_hdr`; the grid of those kernels is
+// nl_filter_blocks(n_atoms)). `map` is a work buffer.
 int nl_filter_blocks(int n_atoms) { return (int)nblk(n_atoms, kFilterGroup) * kFilterGroup; }
 
 void nl_filter(int n_atoms, int64_t n_super, int nel, double rmax, const double *pos, const double *cells,
                const int32_t *frame_of_atom, const int32_t *start_super, const int32_t *seg_super,
                const int32_t *pj_super, const int32_t *ps_super, const int32_t *rev_super, int32_t *map,
                int32_t *seg_exact, int32_t *pair_start, int32_t *pair_stop, int32_t *pi_out, int32_t *pj_out,
-               int32_t *ps_out, int32_t *rev_out, int32_t *slot_q, int cap, int32_t *blk_center, hipStream_t s) {
+               int32_t *ps_out, int32_t *rev_out, int32_t *slot_q, int cap, int32_t *blk_center, BlockHeader *blk_hdr,
+               hipStream_t s) {
   if (n_atoms == 0) return;
   if (nel > kFilterMaxEl) throw std::domain_error("the MD-step list filter handles at most 8 elements");
   hipLaunchKernelGGL(filter_group_kernel, dim3(nblk(n_atoms, kFilterGroup)), dim3(64 * kFilterGroup), 0, s, n_atoms,
                      nel, rmax, pos, cells, frame_of_atom, start_super, seg_super, pj_super, ps_super, seg_exact,
-                     pair_start, pair_stop, pi_out, pj_out, ps_out, map, slot_q, cap, blk_center);
+                     pair_start, pair_stop, pi_out, pj_out, ps_out, map, slot_q, cap, blk_center, blk_hdr);
   // `slot_q` given: the one reader of the reverse index goes through the map itself (pair_rev_of)
   if (n_super > 0 && !slot_q)
     hipLaunchKernelGGL(filter_rev_kernel, dim3(nblk(n_super, kBlock)), dim3(kBlock), 0, s, n_super, rev_super, map,
