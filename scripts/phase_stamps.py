@@ -18,6 +18,16 @@ for k in (0, 1):
         continue
     a = np.array(rows[k])
     n = len(names[k])
+    if a.shape[1] >= 10 and (a[:, 8] > 0).all():
+        # slots 8 / 9: the wavefront's first instruction (in front of every argument load) and the arrival
+        # of the run header; "entry" is the stamp in front of the staging loop
+        h = a[(a[:, 9] > 0) & (a[:, 0] > 0)]
+        for label, d in (("wave start -> header arrived", (h[:, 9] - h[:, 8]) / 100.0),
+                         ("header arrived -> entry", (h[:, 0] - h[:, 9]) / 100.0)):
+            print(f"kernel {'forward' if k == 0 else 'backward'}: {label:<28s} mean {d.mean():6.2f}  "
+                  f"median {np.median(d):6.2f}  max {d.max():6.2f} us")
+        print(f"kernel {'forward' if k == 0 else 'backward'}: first wave start -> last end "
+              f"{(a[:, n - 1].max() - a[:, 8].min()) / 100:.1f} us")
     a = a[:, :n]
     ok = (a > 0).all(axis=1)
     a = a[ok]

@@ -906,7 +906,7 @@ void fill_pairs_on_device(ta_context *h) {
 static void dump_stamps(ta_context *h) {
   const std::string &path = h->opt.phase_stamps_out;
   if (path.empty() || !h->db.stamps || h->db.n_blk <= 0) return;
-  const size_t n = (size_t)2 * h->db.n_blk * 8;
+  const size_t n = (size_t)2 * h->db.n_blk * ta::kStampSlots;
   std::vector<unsigned long long> v(n);
   (void)hipStreamSynchronize(h->stream);
   (void)hipMemcpy(v.data(), h->db.stamps, n * sizeof(unsigned long long), hipMemcpyDeviceToHost);
@@ -915,7 +915,8 @@ static void dump_stamps(ta_context *h) {
   for (int k = 0; k < 2; ++k)
     for (int b = 0; b < h->db.n_blk; ++b) {
       std::fprintf(fp, "%d %d", k, b);
-      for (int q = 0; q < 8; ++q) std::fprintf(fp, " %llu", v[((size_t)k * h->db.n_blk + b) * 8 + q]);
+      for (int q = 0; q < ta::kStampSlots; ++q)
+        std::fprintf(fp, " %llu", v[((size_t)k * h->db.n_blk + b) * ta::kStampSlots + q]);
       std::fprintf(fp, "\n");
     }
   std::fclose(fp);
@@ -937,9 +938,10 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
   using namespace ta;
 #ifdef TA_PHASE_STAMPS
   if (h->db.n_blk > 0) {
-    h->stamp_buf.ensure((size_t)2 * h->db.n_blk * 8 + 8);
+    h->stamp_buf.ensure((size_t)2 * h->db.n_blk * ta::kStampSlots + 8);
     h->db.stamps = h->stamp_buf.ptr;
-    (void)hipMemsetAsync(h->db.stamps, 0, (size_t)2 * h->db.n_blk * 8 * sizeof(unsigned long long), h->stream);
+    (void)hipMemsetAsync(h->db.stamps, 0, (size_t)2 * h->db.n_blk * ta::kStampSlots * sizeof(unsigned long long),
+                         h->stream);
   }
 #endif
   h->db.rec4 = nullptr;  // only the second-generation angular path below sets it

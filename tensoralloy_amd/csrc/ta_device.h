@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "ta_options.h"
 #include "tensoralloy_amd.h"
@@ -18,6 +19,7 @@ constexpr int kCapMin = 192;      // pair records one v2 workgroup (one wavefron
 constexpr int kCapMax = 1024;
 constexpr int kMaxCentersPerBlock = 16;  // centres one angular workgroup may own
 constexpr int kMaxHd = 24;        // coefficients of the Hd(u) expansion
+constexpr int kStampSlots = 10;   // -DTA_PHASE_STAMPS builds: stamps per angular workgroup (DeviceBatch::stamps)
 
 // Symmetry-function constants, passed by value to every kernel.
 struct SFParams {
@@ -131,7 +133,7 @@ struct DeviceBatch {
   int own_sums = 0;
 #ifdef TA_PHASE_STAMPS
   // diagnostic builds only (scripts/phase_stamps.sh): s_memrealtime (100 MHz) at the phase boundaries
-  // of the angular kernels, [kernel 0 / 1][workgroup][8]
+  // of the angular kernels, [kernel 0 / 1][workgroup][kStampSlots]
   unsigned long long *stamps = nullptr;
 #endif
   double *bpart = nullptr;  // [ceil(N / 16)][10] {E, W[9]} of every group of 16 consecutive atoms
@@ -176,6 +178,29 @@ __host__ __device__ inline void make_block_header(BlockHeader &h, int c0, int nc
   h.M = m;
   h.info = ncent | ((ncent > 0 && m <= block && !wide) ? kHdrOnePass : 0);
 }
+
+// What a workgroup of the angular backward kernel needs before its staging barrier, as the FIRST kernel
+// parameter: one 64-byte line of the argument segment, read in one round of scalar loads (two 32-byte loads and
+// one wait) at the kernel's top, so that the header load, the dE/dG loads of the coefficient tables and the job
+// words are issued after ONE argument round trip. SFParams, AngChunk and DeviceBatch stay as parameters for
+// everything that is needed later. Filled by the launcher from DeviceBatch (make_launch_head), never kept anywhere.
+// (The forward kernel keeps its parameters: the same head measured nothing there, profiles/launch_head_notes.md.)
+struct alignas(64) LaunchHead {
+  const BlockHeader *blk_hdr;
+  const int32_t *n_blk_dev;   // DeviceBatch::n_blk_dev; no launch of this library sets it today (always null)
+  const int32_t *job_count;   // the list the launch reads: DeviceBatch::job_count or job_count_own
+  const uint32_t *job_word;   // likewise job_word or job_word_own
+  const double *dEdG;
+  const int32_t *pair_j;
+  int32_t blk_groups;
+  int32_t flags;              // the launch's flag word (was the last kernel parameter)
+  int32_t ndim;               // SFParams::ndim
+  uint32_t stride_nrad;       // bits 0-15 DeviceBatch::job_stride, bits 16-23 SFParams::n_rad
+};
+static_assert(sizeof(LaunchHead) == 64 && alignof(LaunchHead) == 64, "one line of the argument segment");
+static_assert(std::is_trivially_copyable<LaunchHead>::value && std::is_standard_layout<LaunchHead>::value,
+              "passed by value in the argument segment");
+static_assert(4 * kCapMax < (1 << 16) && kMaxRadial < (1 << 8), "job_stride and n_rad share a word");
 
 // Ownership of an angular triangle. A triangle {i, j, k} of three DISTINCT atoms (all three sides
 // below acut) is evaluated once in the backward pass, by one of its vertices: with the indices sorted,

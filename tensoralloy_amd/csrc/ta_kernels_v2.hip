@@ -77,11 +77,52 @@ __device__ __forceinline__ constexpr bool kProbe(int, int) { return false; }
 #define TA_STAMP(b, kernel, k)                                                                          \
   do {                                                                                                  \
     if ((b).stamps && threadIdx.x == 0)                                                                 \
-      (b).stamps[((size_t)(kernel) * gridDim.x + blockIdx.x) * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); \
+      (b).stamps[((size_t)(kernel) * gridDim.x + blockIdx.x) * kStampSlots + (k)] = __builtin_amdgcn_s_memrealtime(); \
+  } while (0)
+// the wavefront's start, taken in front of every argument load and kept in a register until the header
+// has arrived (slots 8 and 9): what the head of the kernel costs, which the "entry" stamp does not show
+#define TA_STAMP_ENTRY() const unsigned long long ta_t_start_ = __builtin_amdgcn_s_memrealtime()
+#define TA_STAMP_HEADER(b, kernel, hd)                                                                  \
+  do {                                                                                                  \
+    if ((b).stamps && threadIdx.x == 0 && (hd).M >= 0) {                                                \
+      unsigned long long *dst_ = (b).stamps + ((size_t)(kernel) * gridDim.x + blockIdx.x) * kStampSlots; \
+      dst_[9] = __builtin_amdgcn_s_memrealtime();                                                       \
+      dst_[8] = ta_t_start_;                                                                            \
+    }                                                                                                   \
   } while (0)
 #else
 #define TA_STAMP(b, kernel, k) do {} while (0)
+#define TA_STAMP_ENTRY() do {} while (0)
+#define TA_STAMP_HEADER(b, kernel, hd) do {} while (0)
 #endif
+
+// The words of the launch head in scalar registers at the kernel's entry: without this the compiler
+// leaves each argument load in the block that first uses it (load, wait, branch, load, wait, ...).
+__device__ __forceinline__ void pin_head(const LaunchHead &h) {
+  asm volatile("" ::"s"(h.blk_hdr), "s"(h.n_blk_dev), "s"(h.job_count), "s"(h.job_word), "s"(h.dEdG),
+               "s"(h.pair_j), "s"(h.blk_groups), "s"(h.flags), "s"(h.ndim), "s"(h.stride_nrad));
+}
+// The launch's flag word as the kernels see it. Bits 8-20 (stagger) and 24-30 (instruction accounting) are
+// probe switches: product builds know them to be zero, so no test of them is left in the code.
+__device__ __forceinline__ int head_flags(const LaunchHead &h) {
+#if defined(TA_PROBE_SWITCHES) || defined(TA_LDS_PROBE)
+  return h.flags;
+#else
+  return h.flags & 0xff;
+#endif
+}
+// Lanes of the workgroup: min(CAP, 256) where the build knows the capacity (the hidden-argument load and
+// the variable strides of the clear / stage loops go), else what the launch says
+template <int CAP>
+__device__ __forceinline__ int block_lanes() {
+  if constexpr (CAP > 0) return CAP < kBlock ? CAP : kBlock;
+  else return (int)blockDim.x;
+}
+// The run slot of workgroup `blk` (DeviceBatch::blk_groups); the host packing has no groups and no division
+__device__ __forceinline__ int run_slot(int blk, int groups) {
+  if (groups <= 0) return blk;
+  return 16 * (blk % groups) + blk / groups;
+}
 
 // A workgroup's BlockHeader (ta_device.h) in scalar registers: the address is the same for every lane, the
 // sixteen words are read once, and everything the staging and mask phases need to know about the list (the
@@ -222,20 +263,22 @@ __device__ __forceinline__ double hd_value(const SFParams &sf, const AngChunk &c
 // three derivatives (see there). H = 0 (pair beyond acut) gives L = 0; such a pair has no triples.
 // `jidx` (forward kernel, one element, owned job lists): the neighbour's atom index per pair slot, in place
 // of the species.
+// `pair_j`: the neighbour list where the caller has it in registers already (backward: LaunchHead), null =
+// DeviceBatch::pair_j. `nthr`: lanes of the workgroup.
 // `hd`: the centre of a pair comes from the workgroup's header (centre_of), never from pair_i / pair_start:
 // the centre's position and frame are then loaded in the same round trip as the pair's neighbour and shift,
 // and the cell in the same one as the neighbour's position. `one_el`: every species is 0, nothing to look up.
 template <int HD>
 __device__ __forceinline__ void stage(const SFParams &sf, const AngChunk &ch, double beta, const DeviceBatch &b,
-                                      const Fields &f, const HeaderRegs &hd, bool one_el, int geom = 0,
-                                      bool forward = false, int *jidx = nullptr) {
+                                      const Fields &f, const HeaderRegs &hd, const int32_t *pair_j, bool one_el,
+                                      unsigned nthr, int geom = 0, bool forward = false, int *jidx = nullptr) {
   const int s0 = hd.s0, M = hd.M;
-  for (int item = threadIdx.x; item < M; item += blockDim.x) {
+  for (int item = threadIdx.x; item < M; item += nthr) {
     double2 v0, v1, v2;
     int ci = 0, cbase = 0, cn = 0;
     if (geom || forward) centre_of(hd, item, ci, cbase, cn);
     const bool want_j = geom || jidx || !one_el;
-    const int j = want_j ? b.pair_j[s0 + item] : 0;
+    const int j = want_j ? (pair_j ? pair_j : b.pair_j)[s0 + item] : 0;
     const double spj = one_el ? 0.0 : (double)b.species[j];
     if (geom) {
       const int64_t p = (int64_t)s0 + item;
@@ -528,9 +571,9 @@ __device__ __forceinline__ double rsqrt_f64(double x) {
 // Descriptor vectors of the workgroup's centres from data that is still in LDS, one wavefront per
 // centre, round robin. G2 from r^2 (sf.py:79-119):
 __device__ __forceinline__ void reduce_radial_from_lds(const SFParams &sf, const DeviceBatch &b,
-                                                       const Fields &f, int c0, int c1, int s0) {
+                                                       const Fields &f, int c0, int c1, int s0, unsigned nthr) {
   const int nel = sf.n_elements;
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nwaves = blockDim.x >> 6;
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nwaves = nthr >> 6;
   // the usual grid has omega = 0 for every channel: exp(-eta r^2 / rc^2), no square root (uniform test)
   bool no_shift = true;
   for (int c = 0; c < sf.n_rad; ++c) no_shift = no_shift && sf.omega[c] == 0.0;
@@ -581,9 +624,9 @@ __device__ __forceinline__ void reduce_radial_from_lds(const SFParams &sf, const
 template <int NSPEC, int NG, int NZ>
 __device__ __forceinline__ void reduce_angular_from_lds(const SFParams &sf, const AngChunk &ch,
                                                         const DeviceBatch &b, const double *red, int cap,
-                                                        int c0, int c1, int s0, int sp_lo, int sp_hi) {
+                                                        int c0, int c1, int s0, int sp_lo, int sp_hi, unsigned nthr) {
   const int nel = sf.n_elements;
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nwaves = blockDim.x >> 6;
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nwaves = nthr >> 6;
   for (int64_t i = c0 + w; i < c1; i += nwaves) {
     const int32_t *seg = b.seg_start + (size_t)i * (nel + 1);
     double *Gi = b.G + (size_t)i * sf.ndim + sf.n_radial_dim;
@@ -616,11 +659,11 @@ __device__ __forceinline__ void reduce_angular_from_lds(const SFParams &sf, cons
 template <int NSPEC, int NG, int NZ>
 __device__ __forceinline__ void assemble_flat(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b,
                                               const Fields &f, const double *P, const int *sslot, int c0, int c1,
-                                              int s0, int item, bool active, bool skip_radial, int cap) {
+                                              int s0, int item, bool active, bool skip_radial, int cap, unsigned nthr) {
   constexpr int kGZ = NG * NZ;
   constexpr int kTerms = NSPEC * (NSPEC + 1) / 2;
   double *R = reinterpret_cast<double *>(f.xy);  // xy, ih, sp1 (5 cap doubles) are dead after the sweep
-  const int row = threadIdx.x >> 4, l = threadIdx.x & 15, nrows = blockDim.x >> 4;
+  const int row = threadIdx.x >> 4, l = threadIdx.x & 15, nrows = nthr >> 4;
   const int ncent = c1 - c0;
   bool no_shift = true;
   for (int c = 0; c < sf.n_rad; ++c) no_shift = no_shift && sf.omega[c] == 0.0;
@@ -709,6 +752,7 @@ __global__ __launch_bounds__(kBlock)
     __attribute__((amdgpu_waves_per_eu(WPE > 0 ? WPE : 1, 8))) void g4_forward_v2_kernel(SFParams sf, AngChunk ch,
                                                                DeviceBatch b, int flags) {
   static_assert(!DEFZ || NZ == 2, "DEFZ needs the two-zeta grid");
+  TA_STAMP_ENTRY();
   const int kCap = CAP > 0 ? CAP : b.cap;
   const int geom = flags & 1;
   if (b.n_blk_dev && (int)blockIdx.x >= *b.n_blk_dev) return;  // grid sized by an upper bound (MD loop)
@@ -720,6 +764,7 @@ __global__ __launch_bounds__(kBlock)
   // everything about the run comes from its header: one load, a workgroup's centres are contiguous in the list
   const BlockHeader *hp = b.blk_hdr + slot;
   const HeaderRegs hd = load_header(hp);
+  TA_STAMP_HEADER(b, 0, hd);
   if (hd.ncent == 0) return;  // an unused run slot of the MD step's packing (ta_nlist.hip::filter_group_kernel)
   const int c0 = hd.c0, c1 = hd.c0 + hd.ncent;
   const int s0 = hd.s0, M = hd.M;
@@ -745,7 +790,7 @@ __global__ __launch_bounds__(kBlock)
   // owned job lists (one element only): the neighbours' atom indices take the place of their species (sp1)
   int *jidx = (NSPEC == 1 && b.job_word_own && b.job_count) ? reinterpret_cast<int *>(f.sp1) : nullptr;
   TA_STAMP(b, 0, 0);
-  stage<HD>(sf, ch, beta, b, f, hd, NSPEC == 1, geom, true, jidx);
+  stage<HD>(sf, ch, beta, b, f, hd, nullptr, NSPEC == 1, blockDim.x, geom, true, jidx);
   TA_STAMP(b, 0, 1);
   if (b.job_count && threadIdx.x == 0) {
     // sslot[k][sg]: first partial-sum slot of segment (centre c0 + k, neighbour species sg), one slot per
@@ -977,7 +1022,7 @@ __global__ __launch_bounds__(kBlock)
       TA_STAMP(b, 0, 5);
       if (flags & 4) {
         assemble_flat<NSPEC, NG, NZ>(sf, ch, b, f, P, jl.hist + 60 + kMaxCentersPerBlock * kSegW, c0, c1, s0, item, active,
-                                     (flags & (1 << 26)) != 0, kCap);
+                                     (flags & (1 << 26)) != 0, kCap, blockDim.x);
         TA_STAMP(b, 0, 6);
         return;
       }
@@ -1022,8 +1067,8 @@ __global__ __launch_bounds__(kBlock)
             if (sp_lo * kGZ + k < kLocal) red[(size_t)k * kCap + item] = mine[sp_lo * kGZ + k];
         }
         __syncthreads();
-        if (sp_lo == 0) reduce_radial_from_lds(sf, b, f, c0, c1, s0);
-        reduce_angular_from_lds<NSPEC, NG, NZ>(sf, ch, b, red, kCap, c0, c1, s0, sp_lo, sp_hi);
+        if (sp_lo == 0) reduce_radial_from_lds(sf, b, f, c0, c1, s0, blockDim.x);
+        reduce_angular_from_lds<NSPEC, NG, NZ>(sf, ch, b, red, kCap, c0, c1, s0, sp_lo, sp_hi, blockDim.x);
         __syncthreads();
       }
       return;
@@ -1067,27 +1112,37 @@ template <int NSPEC, int NG, int NZ, int HD, bool DEFZ, int CAP, int WPE = (DEFZ
 // 51 -> 45 us per frame in batches (4: 69 / 47, 6: 68 / 45). Only the default-grid instantiations
 // are constrained; the generic ones keep the compiler's choice.
 __global__ __launch_bounds__(kBlock)
-    __attribute__((amdgpu_waves_per_eu(WPE > 0 ? WPE : 1, 8))) void backward_v2_kernel(SFParams sf, AngChunk ch,
-                                                             DeviceBatch b, int flags) {
+    __attribute__((amdgpu_waves_per_eu(WPE > 0 ? WPE : 1, 8))) void backward_v2_kernel(LaunchHead head, SFParams sf,
+                                                             AngChunk ch, DeviceBatch b) {
   static_assert(!DEFZ || NZ == 2, "DEFZ needs the two-zeta grid");
   static_assert(!TRI || (NSPEC == 1 && DEFZ && HD > 0), "the triangle build is one-element, default grid, Hd series");
+  TA_STAMP_ENTRY();
+  pin_head(head);
+  const int flags = head_flags(head);
+  const int nthr = block_lanes<CAP>();
   const int first = flags & 1;
-  if (b.n_blk_dev && (int)blockIdx.x >= *b.n_blk_dev) return;  // grid sized by an upper bound (MD loop)
   stagger(flags);
   extern __shared__ double lds[];
   const int kCap = CAP > 0 ? CAP : b.cap;  // multiple of 64
   const Fields f = carve(lds, kCap);
   // partner accumulators behind the fields (kCap bytes in between hold the centres' first pairs, `cstart`)
   double *gacc = lds + kNF * kCap + kCap / 8;
-  const int slot = b.blk_groups > 0 ? 16 * ((int)blockIdx.x % b.blk_groups) + (int)blockIdx.x / b.blk_groups
-                                    : (int)blockIdx.x;
-  const BlockHeader *hp = b.blk_hdr + slot;
+  // The header, and in the same round trip the grid's true size (MD loop, an upper bound was launched): every
+  // workgroup of the grid has a header slot, whoever made the packing
+  const BlockHeader *hp = head.blk_hdr + run_slot((int)blockIdx.x, head.blk_groups);
+  int n_blk_true = 0x7fffffff;
+  if (head.n_blk_dev) n_blk_true = *head.n_blk_dev;
   const HeaderRegs hd = load_header(hp, false);
+  TA_STAMP_HEADER(b, 1, hd);
+  if ((int)blockIdx.x >= n_blk_true) return;
   if (hd.ncent == 0) return;  // unused run slot
+  // SFParams::ndim, n_rad and n_radial_dim from the head (n_elements is this build's NSPEC)
+  const int ndim = head.ndim, n_rad = (int)(head.stride_nrad >> 16), n_radial_dim = NSPEC * n_rad;
+  const int job_stride = (int)(head.stride_nrad & 0xffffu);
   const int c0 = hd.c0, c1 = hd.c0 + hd.ncent;
   const int s0 = hd.s0, M = hd.M;
   const double beta = ch.beta[0];
-  for (int k = threadIdx.x; k < 3 * kCap; k += blockDim.x) gacc[k] = 0.0;
+  for (int k = threadIdx.x; k < 3 * kCap; k += nthr) gacc[k] = 0.0;
   // cstart[k]: first pair of centre c0 + k (see job_centre), in the kCap bytes in front of gacc
   int *cstart = reinterpret_cast<int *>(gacc) - 20;
   if (threadIdx.x < 17) cstart[threadIdx.x] = hp->rel[threadIdx.x];
@@ -1096,9 +1151,9 @@ __global__ __launch_bounds__(kBlock)
   // and twenty operations in the prologue of every job
   double *pctab = gacc + 3 * kCap;  // [kMaxCentersPerBlock][5]
   if constexpr (DEFZ && NSPEC == 1) {
-    const int k = (int)blockDim.x - 1 - (int)threadIdx.x;
+    const int k = nthr - 1 - (int)threadIdx.x;
     if (k < c1 - c0) {
-      const double *wsrc = b.dEdG + (size_t)(c0 + k) * sf.ndim + sf.n_radial_dim;
+      const double *wsrc = head.dEdG + (size_t)(c0 + k) * ndim + n_radial_dim;
       double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0, p4 = 0.0;
 #pragma unroll
       for (int ig = 0; ig < NG; ++ig) {
@@ -1122,15 +1177,17 @@ __global__ __launch_bounds__(kBlock)
   // here by the lanes next to those (the workgroup's last ones, mostly without a pair) so that the
   // epilogue walks no pair_i -> species / dE/dG chain of dependent global loads at the kernel's tail
   double *rtab = pctab + 5 * kMaxCentersPerBlock;  // [kMaxCentersPerBlock][kRTab]
-  const bool use_rtab = first && NSPEC * sf.n_rad <= kRTab;
+  const bool use_rtab = first && NSPEC * n_rad <= kRTab;
   if (use_rtab) {
-    const int per = NSPEC * sf.n_rad;
-    const int t = (int)blockDim.x - 1 - (int)threadIdx.x - kMaxCentersPerBlock;
+    const int per = NSPEC * n_rad;
+    const int t = nthr - 1 - (int)threadIdx.x - kMaxCentersPerBlock;
     if (t >= 0 && t < (c1 - c0) * per) {
       const int ci = t / per, rem = t - ci * per;
-      const int sb = rem / sf.n_rad, c = rem - sb * sf.n_rad;
+      const int sb = rem / n_rad, c = rem - sb * n_rad;
       const int64_t i = c0 + ci;
-      rtab[ci * kRTab + rem] = b.dEdG[(size_t)i * sf.ndim + radial_term2(b.species[i], sb) * sf.n_rad + c];
+      // (one element: the centre's species is 0 and its only radial term the first)
+      const int term = NSPEC == 1 ? 0 : radial_term2(b.species[i], sb);
+      rtab[ci * kRTab + rem] = head.dEdG[(size_t)i * ndim + term * n_rad + c];
     }
   }
   // TRI: the S0 coefficients of every NEIGHBOUR atom per pair slot, {p0 p1} {p2 p3} p4 (5 cap doubles
@@ -1138,9 +1195,9 @@ __global__ __launch_bounds__(kBlock)
   double2 *pn01 = reinterpret_cast<double2 *>(rtab + kMaxCentersPerBlock * kRTab), *pn23 = pn01 + kCap;
   double *pn4 = reinterpret_cast<double *>(pn23 + kCap);
   if constexpr (TRI) {
-    for (int item = threadIdx.x; item < M; item += blockDim.x) {
+    for (int item = threadIdx.x; item < M; item += nthr) {
       double pc[5];
-      defz_coeffs<NG, NZ>(ch, b.dEdG + (size_t)b.pair_j[s0 + item] * sf.ndim + sf.n_radial_dim, pc);
+      defz_coeffs<NG, NZ>(ch, head.dEdG + (size_t)head.pair_j[s0 + item] * ndim + n_radial_dim, pc);
       pn01[item] = make_double2(pc[0], pc[1]);
       pn23[item] = make_double2(pc[2], pc[3]);
       pn4[item] = pc[4];
@@ -1152,17 +1209,17 @@ __global__ __launch_bounds__(kBlock)
   // later rounds are asked for behind the staging (they arrive while the first round is swept; holding them
   // in registers through the staging spilt four more). A lane's slots lie inside the workgroup's own slice
   // of `job_stride` words whatever the count is; words beyond the count are discarded.
-  const int32_t *jcount = TRI ? b.job_count_own : b.job_count;
-  const uint32_t *jword = TRI ? b.job_word_own : b.job_word;
-  const size_t jbase = (size_t)blockIdx.x * b.job_stride;
+  const int32_t *jcount = head.job_count;  // TRI: the owned lists (the launcher chose)
+  const uint32_t *jword = head.job_word;
+  const size_t jbase = (size_t)blockIdx.x * job_stride;
   uint32_t jw0 = 0u;
   int n_listed = -1;
   if (jcount) {
     n_listed = jcount[blockIdx.x];
-    if ((int)threadIdx.x < b.job_stride) jw0 = jword[jbase + threadIdx.x];  // job_slot(0, lane) = lane
+    if ((int)threadIdx.x < job_stride) jw0 = jword[jbase + threadIdx.x];  // job_slot(0, lane) = lane
   }
   TA_STAMP(b, 1, 0);
-  stage<HD>(sf, ch, beta, b, f, hd, NSPEC == 1);
+  stage<HD>(sf, ch, beta, b, f, hd, head.pair_j, NSPEC == 1, nthr);
   TA_STAMP(b, 1, 1);
   const int nel = sf.n_elements;
 
@@ -1472,14 +1529,14 @@ __global__ __launch_bounds__(kBlock)
       jws[0] = jw0;
 #pragma unroll
       for (int r = 1; r < 4; ++r) {
-        const int js = job_slot(r, threadIdx.x, blockDim.x);
+        const int js = job_slot(r, threadIdx.x, nthr);
         jws[r] = js < n_jobs ? jword[jbase + js] : 0u;
       }
       TA_STAMP(b, 1, 2);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        if (r * (int)blockDim.x >= n_jobs) break;
-        const int slot = job_slot(r, threadIdx.x, blockDim.x);
+        if (r * nthr >= n_jobs) break;
+        const int slot = job_slot(r, threadIdx.x, nthr);
         if (slot < n_jobs) {
           if constexpr (TRI) run_tri(job_item(jws[r]), true, jws[r], std::true_type{});
           else run_item(job_item(jws[r]), true, jws[r], std::true_type{});
@@ -1502,7 +1559,7 @@ __global__ __launch_bounds__(kBlock)
         else run_item(item, true, mask, std::false_type{});
       }
     } else {
-      for (int it = threadIdx.x; it < M; it += blockDim.x) {
+      for (int it = threadIdx.x; it < M; it += nthr) {
         if constexpr (TRI) run_tri(it, false, 0ull, std::false_type{});
         else run_item(it, false, 0ull, std::false_type{});
       }
@@ -1510,7 +1567,7 @@ __global__ __launch_bounds__(kBlock)
   }
   __syncthreads();
   TA_STAMP(b, 1, 4);
-  for (int item = threadIdx.x; item < M; item += blockDim.x) {
+  for (int item = threadIdx.x; item < M; item += nthr) {
     const int64_t p = (int64_t)s0 + item;
     double gx = gacc[item], gy = gacc[kCap + item], gz = gacc[2 * kCap + item];
     if (first) {
@@ -1556,6 +1613,32 @@ __global__ __launch_bounds__(kBlock)
   TA_STAMP(b, 1, 5);
 }
 
+// the head is the FIRST parameter: it is the first line of the argument segment
+template <class F>
+struct first_param;
+template <class A, class... As>
+struct first_param<void (*)(A, As...)> {
+  using type = A;
+};
+using BwdDefault = decltype(&backward_v2_kernel<1, 2, 2, 12, true, kCapMin, 5, true>);
+static_assert(std::is_same<first_param<BwdDefault>::type, LaunchHead>::value, "LaunchHead leads the parameter list");
+
+// The launch head of the backward kernel (LaunchHead). `own`: the launch reads the owned lists.
+LaunchHead make_launch_head(const SFParams &sf, const DeviceBatch &b, int flags, bool own) {
+  LaunchHead h;
+  h.blk_hdr = b.blk_hdr;
+  h.n_blk_dev = b.n_blk_dev;
+  h.job_count = own ? b.job_count_own : b.job_count;
+  h.job_word = own ? b.job_word_own : b.job_word;
+  h.dEdG = b.dEdG;
+  h.pair_j = b.pair_j;
+  h.blk_groups = b.blk_groups;
+  h.flags = flags;
+  h.ndim = sf.ndim;
+  h.stride_nrad = (uint32_t)b.job_stride | ((uint32_t)sf.n_rad << 16);
+  return h;
+}
+
 template <int NSPEC, int NG, int NZ>
 void fwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int geom, int wpe, hipStream_t s) {
   const dim3 grid((unsigned)b.n_blk), block((unsigned)(b.cap < kBlock ? b.cap : kBlock));
@@ -1598,6 +1681,8 @@ void bwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int fir
            hipStream_t s) {
   const dim3 grid((unsigned)b.n_blk), block((unsigned)(b.cap < kBlock ? b.cap : kBlock));
   const size_t lds = v2_lds_bytes(true, b.cap);
+  const LaunchHead head = make_launch_head(sf, b, first, false);
+  const LaunchHead head_t = make_launch_head(sf, b, first, true);  // reads the owned lists
   variant = 1;
   if constexpr (NZ == 2 && NSPEC == 1) {
     // triangle-once builds: the default grid with an Hd series, one element
@@ -1607,17 +1692,17 @@ void bwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int fir
       // 5 wavefronts per SIMD (96 VGPRs, 17 spilled); `wpe` (Options::bwd_wpe) == 4 (A/B) takes the 4-wavefront build
       // (125 VGPRs, none spilled), measured slower: 38.7 against 37.0 us on the benchmark frame
       if (ch.n_hd == 12 && b.cap == kCapMin && wpe == 4)
-        hipLaunchKernelGGL((backward_v2_kernel<1, NG, NZ, 12, true, kCapMin, 4, true>), grid, block, lds_t, s, sf, ch,
-                           b, first);
+        hipLaunchKernelGGL((backward_v2_kernel<1, NG, NZ, 12, true, kCapMin, 4, true>), grid, block, lds_t, s, head_t,
+                           sf, ch, b);
       else if (ch.n_hd == 12 && b.cap == kCapMin)
-        hipLaunchKernelGGL((backward_v2_kernel<1, NG, NZ, 12, true, kCapMin, 5, true>), grid, block, lds_t, s, sf, ch,
-                           b, first);
+        hipLaunchKernelGGL((backward_v2_kernel<1, NG, NZ, 12, true, kCapMin, 5, true>), grid, block, lds_t, s, head_t,
+                           sf, ch, b);
       else if (ch.n_hd == 12)
-        hipLaunchKernelGGL((backward_v2_kernel<1, NG, NZ, 12, true, 0, 5, true>), grid, block, lds_t, s, sf, ch, b,
-                           first);
+        hipLaunchKernelGGL((backward_v2_kernel<1, NG, NZ, 12, true, 0, 5, true>), grid, block, lds_t, s, head_t,
+                           sf, ch, b);
       else
-        hipLaunchKernelGGL((backward_v2_kernel<1, NG, NZ, 16, true, 0, 5, true>), grid, block, lds_t, s, sf, ch, b,
-                           first);
+        hipLaunchKernelGGL((backward_v2_kernel<1, NG, NZ, 16, true, 0, 5, true>), grid, block, lds_t, s, head_t,
+                           sf, ch, b);
       return;
     }
   }
@@ -1629,27 +1714,28 @@ void bwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int fir
         // against 33.1 us per frame in batches; `wpe` == 6 selects it)
         if constexpr (NSPEC == 1) {
           if (wpe == 6) {
-            hipLaunchKernelGGL((backward_v2_kernel<NSPEC, NG, NZ, 12, true, kCapMin, 6>), grid, block, lds, s, sf, ch,
-                               b, first);
+            hipLaunchKernelGGL((backward_v2_kernel<NSPEC, NG, NZ, 12, true, kCapMin, 6>), grid, block, lds, s,
+                               head, sf, ch, b);
             return;
           }
         }
-        hipLaunchKernelGGL((backward_v2_kernel<NSPEC, NG, NZ, 12, true, kCapMin>), grid, block, lds, s, sf, ch, b, first);
+        hipLaunchKernelGGL((backward_v2_kernel<NSPEC, NG, NZ, 12, true, kCapMin>), grid, block, lds, s,
+                           head, sf, ch, b);
       } else
-        hipLaunchKernelGGL((backward_v2_kernel<NSPEC, NG, NZ, 12, true, 0>), grid, block, lds, s, sf, ch, b, first);
+        hipLaunchKernelGGL((backward_v2_kernel<NSPEC, NG, NZ, 12, true, 0>), grid, block, lds, s, head, sf, ch, b);
       return;
     }
     if (ch.n_hd == 16 && ch.zeta_int[0] == 1 && ch.zeta_int[1] == 4) {
-      hipLaunchKernelGGL((backward_v2_kernel<NSPEC, NG, NZ, 16, true, 0>), grid, block, lds, s, sf, ch, b, first);
+      hipLaunchKernelGGL((backward_v2_kernel<NSPEC, NG, NZ, 16, true, 0>), grid, block, lds, s, head, sf, ch, b);
       return;
     }
   }
   if (ch.n_hd > 0 && ch.n_hd <= 16)  // coefficients beyond n_hd are zero
-    hipLaunchKernelGGL((backward_v2_kernel<NSPEC, NG, NZ, 16, false, 0>), grid, block, lds, s, sf, ch, b, first);
+    hipLaunchKernelGGL((backward_v2_kernel<NSPEC, NG, NZ, 16, false, 0>), grid, block, lds, s, head, sf, ch, b);
   else if (ch.n_hd == 24)
-    hipLaunchKernelGGL((backward_v2_kernel<NSPEC, NG, NZ, 24, false, 0>), grid, block, lds, s, sf, ch, b, first);
+    hipLaunchKernelGGL((backward_v2_kernel<NSPEC, NG, NZ, 24, false, 0>), grid, block, lds, s, head, sf, ch, b);
   else
-    hipLaunchKernelGGL((backward_v2_kernel<NSPEC, NG, NZ, 0, false, 0>), grid, block, lds, s, sf, ch, b, first);
+    hipLaunchKernelGGL((backward_v2_kernel<NSPEC, NG, NZ, 0, false, 0>), grid, block, lds, s, head, sf, ch, b);
 }
 
 }  // namespace
