@@ -286,6 +286,9 @@ struct ta_context {
   DevBuf<uint32_t> job_word_own;
   DevBuf<int32_t> job_count_own;
   bool triangles = true;
+  // the last second-generation forward pass left the full job list (db.job_word / job_count) behind: it
+  // does not when every backward launch of its evaluation read the owned lists (forward_v2_launches)
+  bool full_jobs_valid = false;
   bool tri_cells_ok = false;
   bool tri_cells_wide_ok = false;  // every periodic width exceeds rmax + skin: what the cell relaxation asks for
   int last_bwd_variant = 0;
@@ -934,6 +937,23 @@ void launch_head(ta_context *h, const ta::DeviceBatch &db, hipStream_t s) {
                        s, &h->last_mlp_launch);
 }
 
+// The forward launches of the second-generation angular path, one per chunk. `tri`: the backward launches of
+// this evaluation are asked to take the triangle build. The full job list is left out only when EVERY one of
+// them does (a chunk that falls back to the per-apex kernel reads it), and the handle remembers which.
+void forward_v2_launches(ta_context *h, bool tri) {
+  using namespace ta;
+  bool unread = tri && h->db.job_word_own && h->db.job_count_own && h->db.job_count;
+  for (const ChunkPlan &cp : h->chunks_v2) unread = unread && v2_backward_takes_triangles(h->sf, cp.ch, cp.ng, cp.nz);
+  bool geometry = true;
+  size_t left = h->chunks_v2.size();
+  for (const ChunkPlan &cp : h->chunks_v2) {
+    --left;
+    launch_g4_forward_v2(h->sf, cp.ch, cp.ng, cp.nz, geometry, left == 0, unread, h->db, h->opt, h->stream);
+    geometry = false;
+  }
+  h->full_jobs_valid = !unread;
+}
+
 void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
   using namespace ta;
 #ifdef TA_PHASE_STAMPS
@@ -988,15 +1008,9 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
     const bool reduce_in_forward = h->sf.angular && h->use_v2;
     if (h->sf.angular) {
       begin(TA_K_G4_FORWARD);
-      if (h->use_v2) {
-        bool geometry = true;
-        size_t left = h->chunks_v2.size();
-        for (const ChunkPlan &cp : h->chunks_v2) {
-          --left;
-          launch_g4_forward_v2(h->sf, cp.ch, cp.ng, cp.nz, geometry, left == 0, db, h->opt, s);
-          geometry = false;
-        }
-      } else
+      if (h->use_v2)
+        forward_v2_launches(h, tri);
+      else
         for (const ChunkPlan &cp : h->chunks) launch_g4_forward(h->sf, cp.ch, cp.nb, cp.ng, cp.nz, db, s);
       end(TA_K_G4_FORWARD);
       used[TA_K_G4_FORWARD] = true;
@@ -1367,6 +1381,7 @@ void set_frames_impl(ta_context *h, int32_t n_frames, const ta_frame *frames, ta
   h->have_batch = false;
   h->descriptors_valid = false;
   h->jvp_valid = false;
+  h->full_jobs_valid = false;
   h->mirror_want = 0;  // (stage_out carries the builder's counts from here on)
   h->filtered = false;
   h->db.slot_q = h->db.rev_super = h->db.rev_map = nullptr;
@@ -1712,6 +1727,7 @@ int ta_update_positions(ta_handle h, const double *positions, const double *cell
       if (h->filtered) apply_filter(h);  // the exact list of the new positions, on the device
       h->descriptors_valid = false;
       h->jvp_valid = false;
+      h->full_jobs_valid = false;
       const double lim2 = 0.25 * h->skin * h->skin;
       const double *ref = h->ref_pos.data();
       for (size_t i = 0; i < N; ++i) {
@@ -3146,13 +3162,17 @@ void backward_only(ta_context *h) {
   if (h->kind == TA_MODEL_SF_MLP) {
     if (h->sf.angular) {
       bool first = true;
-      if (h->use_v2)
+      if (h->use_v2) {
+        // the per-apex kernel walks the FULL job list of the resident forward pass; an evaluation whose
+        // backward launches were all triangle builds left none, so the forward launches run again and write it
+        // (same geometry, same descriptors; dE/dG is the caller's and stays)
+        if (db.job_count && !h->full_jobs_valid) forward_v2_launches(h, false);
         for (const ChunkPlan &cp : h->chunks_v2) {
           // per apex: the callers keep g[p] per pair (J[c][p]), which the triangle pass distributes differently
           launch_backward_v2(h->sf, cp.ch, cp.ng, cp.nz, first, false, db, h->opt, s);
           first = false;
         }
-      else
+      } else
         for (const ChunkPlan &cp : h->chunks) {
           launch_backward(h->sf, cp.ch, cp.nb, cp.ng, cp.nz, first, false, db, s);
           first = false;

@@ -238,7 +238,31 @@ __device__ __forceinline__ int pair_rev_of(const DeviceBatch &b, int q) {
 __device__ __forceinline__ const double2 *pair_geom(const DeviceBatch &b, size_t q) {
   return reinterpret_cast<const double2 *>(b.rec4 ? b.rec4 + 4 * q : b.rec + kRecDoubles * q);
 }
+// 16-byte write-through stores (the `sc1` cache policy) for bulk data that only a LATER kernel reads: the
+// line goes to memory at once and does not stay dirty in the writing XCD's L2, so the release at the
+// kernel's end has nothing of it left to write back. Only the 16-byte form: narrower write-through stores
+// cost several times as much per byte. `base` and `bytes` must be wave-uniform (they become the buffer
+// descriptor, in scalar registers); stores at or beyond `bytes` are dropped by the range check.
+struct WtSlice {
+  __amdgpu_buffer_rsrc_t rsrc;
+};
+__device__ __forceinline__ WtSlice wt_slice(void *base, uint32_t bytes) {
+  WtSlice s;
+  s.rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, 0x00020000);
+  return s;
+}
+__device__ __forceinline__ void wt_store16(const WtSlice &s, uint32_t byte_offset, double2 v) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4 w = {(uint32_t)__double2loint(v.x), (uint32_t)__double2hiint(v.x), (uint32_t)__double2loint(v.y),
+                   (uint32_t)__double2hiint(v.y)};
+  __builtin_amdgcn_raw_buffer_store_b128(w, s.rsrc, (int)byte_offset, 0, 16);  // aux 16 = sc1
+}
 #endif
+// When a launch stores its hand-over data write-through: while all of it (32 bytes per pair) would fit in the
+// eight 4 MB L2s and so stay dirty until the kernel's end. A larger batch evicts most of its output while it
+// runs, nothing is left for the boundary, and plain stores are the cheaper ones there.
+constexpr size_t kWtMaxBytes = (size_t)32 << 20;
+inline bool wt_handover(const DeviceBatch &b) { return 32 * (size_t)b.n_pairs <= kWtMaxBytes; }
 
 // Per-element MLP on the device: padded weights, both orientations.
 struct MlpLayerDev {
@@ -286,8 +310,14 @@ size_t g4_lds_bytes(int nnl_max);
 size_t v2_lds_bytes(bool backward, int cap, int n_local = 0, int nspec = 0, bool triangles = false);
 int v2_job_stride(int cap);
 // `reduce`: last forward launch of an evaluation, also assembles the descriptor vectors
+// `full_list_unread`: no backward launch of this evaluation reads DeviceBatch::job_word (every one of them
+// takes the triangle build and reads job_word_own): the launch leaves job_count[blk] = -1 and no full list.
+// Honoured only where the launch makes the owned lists.
 void launch_g4_forward_v2(const SFParams &sf, const AngChunk &ch, int ng, int nz, bool geometry,
-                          bool reduce, const DeviceBatch &b, const Options &opt, hipStream_t s);
+                          bool reduce, bool full_list_unread, const DeviceBatch &b, const Options &opt, hipStream_t s);
+// Whether launch_backward_v2(.., triangles = true, ..) takes the triangle-once build for this chunk: one
+// element, the default zeta grid {1, 4}, an Hd series of 12 or 16 coefficients
+bool v2_backward_takes_triangles(const SFParams &sf, const AngChunk &ch, int ng, int nz);
 // `triangles`: one-element default-grid chunks take the triangle-once build (b.job_word_own made by the
 // forward launch, or ownership tested per triple). Returns the build used: 1 per apex, 2 triangles.
 int launch_backward_v2(const SFParams &sf, const AngChunk &ch, int ng, int nz, bool first, bool triangles,

@@ -61,6 +61,25 @@ constexpr int kJobCtlBytes = (kOwnCtl + 40) * 4;
 __host__ __device__ inline int v2_pcols(int cap, int nspec) {
   return nspec >= 1 ? cap / 4 + kMaxCentersPerBlock * nspec : cap;
 }
+// The stores with which the angular kernels hand data to the kernels behind them, each an A/B switch of its
+// own (-D...=0 / 1 builds for scripts/build_ab_lib.sh; profiles/handover_stores_notes.md has what each measured):
+//   TA_HANDOVER_REC_LATE   stage() stores the pair record behind the item's LDS writes, not in front of them
+//   TA_HANDOVER_SKIP_LIST  the forward kernel honours "full list unread" (flags bit 3)
+//   TA_HANDOVER_WT_REC     the compact pair record goes out write-through (wt_store16) where the launch
+//                          says so (flags bit 4, wt_handover)
+// (The backward epilogue's g[p] as write-through pieces was measured too and is not here: it gained nothing.)
+#ifndef TA_HANDOVER_REC_LATE
+#define TA_HANDOVER_REC_LATE 1
+#endif
+#ifndef TA_HANDOVER_SKIP_LIST
+#define TA_HANDOVER_SKIP_LIST 1
+#endif
+#ifndef TA_HANDOVER_WT_REC
+#define TA_HANDOVER_WT_REC 1
+#endif
+// Experiment build (-DTA_PROBE_NO_HANDOVER, never a product build): the forward kernel stores neither pair
+// records nor job lists, to time what those stores cost at the forward -> MLP boundary. Energies stay right;
+// launch_backward_v2 refuses to run in such a build.
 constexpr int kRingPad = 64;  // floats readable past the last ring (masked candidates)
 constexpr int kRTab = 8;      // backward: radial dE/dG values per centre kept in LDS (neighbour species x radial channels)
 
@@ -271,8 +290,42 @@ __device__ __forceinline__ double hd_value(const SFParams &sf, const AngChunk &c
 template <int HD>
 __device__ __forceinline__ void stage(const SFParams &sf, const AngChunk &ch, double beta, const DeviceBatch &b,
                                       const Fields &f, const HeaderRegs &hd, const int32_t *pair_j, bool one_el,
-                                      unsigned nthr, int geom = 0, bool forward = false, int *jidx = nullptr) {
+                                      unsigned nthr, int geom = 0, bool forward = false, int *jidx = nullptr,
+                                      bool wt = false) {
   const int s0 = hd.s0, M = hd.M;
+  // The record the geometry path leaves for the later kernels. Nothing in this kernel needs it early, and the
+  // other branches below join the geometry path with loads in flight, so a store issued in front of the LDS
+  // writes is waited for (vmcnt counts stores) before the first of them: it goes out behind them instead.
+#if TA_HANDOVER_WT_REC
+  const WtSlice wt_rec = wt_slice(b.rec4 ? b.rec4 + 4 * (size_t)s0 : nullptr, (geom && b.rec4) ? 32u * (uint32_t)M : 0u);
+#else
+  (void)wt;
+#endif
+  auto store_record = [&](int item, double2 v0, double2 v1, double2 v2) {
+#ifdef TA_PROBE_NO_HANDOVER
+    (void)item; (void)v0; (void)v1; (void)v2;
+#else
+    const int64_t p = (int64_t)s0 + item;
+    if (b.rec4) {  // compact record: 1 / r is recomputed by the readers
+#if TA_HANDOVER_WT_REC
+      if (wt) {
+        wt_store16(wt_rec, 32u * (uint32_t)item, v0);
+        wt_store16(wt_rec, 32u * (uint32_t)item + 16u, v1);
+        return;
+      }
+#endif
+      double2 *dst = reinterpret_cast<double2 *>(b.rec4 + 4 * (size_t)p);
+      dst[0] = v0;
+      dst[1] = v1;
+    } else {
+      double2 *dst = reinterpret_cast<double2 *>(b.rec + kRecDoubles * (size_t)p);
+      dst[0] = v0;
+      dst[1] = v1;
+      dst[2] = v2;
+      dst[3] = make_double2(0.0, 0.0);
+    }
+#endif
+  };
   for (int item = threadIdx.x; item < M; item += nthr) {
     double2 v0, v1, v2;
     int ci = 0, cbase = 0, cn = 0;
@@ -294,17 +347,9 @@ __device__ __forceinline__ void stage(const SFParams &sf, const AngChunk &ch, do
       v0 = make_double2(dx, dy);
       v1 = make_double2(dz, r2);
       v2 = make_double2(1.0 / sqrt(r2), 0.0);
-      if (b.rec4) {  // compact record: 1 / r is recomputed by the readers
-        double2 *dst = reinterpret_cast<double2 *>(b.rec4 + 4 * (size_t)p);
-        dst[0] = v0;
-        dst[1] = v1;
-      } else {
-        double2 *dst = reinterpret_cast<double2 *>(b.rec + kRecDoubles * (size_t)p);
-        dst[0] = v0;
-        dst[1] = v1;
-        dst[2] = v2;
-        dst[3] = make_double2(0.0, 0.0);
-      }
+#if !TA_HANDOVER_REC_LATE
+      store_record(item, v0, v1, v2);
+#endif
     } else if (b.rec4) {
       const double2 *src = reinterpret_cast<const double2 *>(b.rec4 + 4 * (size_t)(s0 + item));
       v0 = src[0];
@@ -339,6 +384,9 @@ __device__ __forceinline__ void stage(const SFParams &sf, const AngChunk &ch, do
     if (jidx) jidx[item] = j;
     else if (forward) f.sp1[item] = spj;
     else f.gs[item] = make_double2(L, spj);
+#if TA_HANDOVER_REC_LATE
+    if (geom) store_record(item, v0, v1, v2);
+#endif
   }
   __syncthreads();
 }
@@ -790,7 +838,7 @@ __global__ __launch_bounds__(kBlock)
   // owned job lists (one element only): the neighbours' atom indices take the place of their species (sp1)
   int *jidx = (NSPEC == 1 && b.job_word_own && b.job_count) ? reinterpret_cast<int *>(f.sp1) : nullptr;
   TA_STAMP(b, 0, 0);
-  stage<HD>(sf, ch, beta, b, f, hd, nullptr, NSPEC == 1, blockDim.x, geom, true, jidx);
+  stage<HD>(sf, ch, beta, b, f, hd, nullptr, NSPEC == 1, blockDim.x, geom, true, jidx, (flags & 16) != 0);
   TA_STAMP(b, 0, 1);
   if (b.job_count && threadIdx.x == 0) {
     // sslot[k][sg]: first partial-sum slot of segment (centre c0 + k, neighbour species sg), one slot per
@@ -998,8 +1046,18 @@ __global__ __launch_bounds__(kBlock)
       const int n_jobs = make_jobs(jl, active, item, ci_own, mask);
       TA_STAMP(b, 0, 3);
       const size_t jbase = (size_t)blockIdx.x * b.job_stride;
-      if (threadIdx.x == 0) b.job_count[blockIdx.x] = n_jobs;
-      for (int slot = threadIdx.x; slot < n_jobs; slot += blockDim.x) b.job_word[jbase + slot] = jl.word[slot];
+      // flags bit 3 (launch_g4_forward_v2: full list unread): every backward launch of this evaluation reads
+      // the owned list made below, so the copy of the full one is not written, and its count says so
+#if defined(TA_PROBE_NO_HANDOVER)
+      const bool skip_full = true;
+#elif TA_HANDOVER_SKIP_LIST
+      const bool skip_full = (flags & 8) && jidx;
+#else
+      const bool skip_full = false;
+#endif
+      if (threadIdx.x == 0) b.job_count[blockIdx.x] = skip_full ? -1 : n_jobs;
+      if (!skip_full)
+        for (int slot = threadIdx.x; slot < n_jobs; slot += blockDim.x) b.job_word[jbase + slot] = jl.word[slot];
       TA_STAMP(b, 0, 4);
       uint32_t swept[4] = {0u, 0u, 0u, 0u};  // jobs of this lane (at most four rounds: n_jobs <= 4 M)
       unsigned owned[4] = {0u, 0u, 0u, 0u};
@@ -1639,8 +1697,17 @@ LaunchHead make_launch_head(const SFParams &sf, const DeviceBatch &b, int flags,
   return h;
 }
 
+// Whether the backward launch of a chunk takes the triangle-once build when triangles are asked for: one
+// element, the default grid with an Hd series. What bwd_t dispatches on, and what allows a forward launch to
+// leave out the full job list (fwd_t).
+bool takes_triangles(int nspec, int nz, const AngChunk &ch) {
+  return nspec == 1 && nz == 2 && (ch.n_hd == 12 || ch.n_hd == 16) && ch.zeta_int[0] == 1 && ch.zeta_int[1] == 4;
+}
+
 template <int NSPEC, int NG, int NZ>
 void fwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int geom, int wpe, hipStream_t s) {
+  // "full list unread" (bit 3) only where this chunk's own backward launch reads the owned list
+  if (!(b.job_word_own && b.job_count && takes_triangles(NSPEC, NZ, ch))) geom &= ~8;
   const dim3 grid((unsigned)b.n_blk), block((unsigned)(b.cap < kBlock ? b.cap : kBlock));
   const size_t lds = v2_lds_bytes(false, b.cap, b.job_count ? NSPEC * NG * NZ : 0, NSPEC);
   if constexpr (NZ == 2) {
@@ -1686,7 +1753,7 @@ void bwd_t(const SFParams &sf, const AngChunk &ch, const DeviceBatch &b, int fir
   variant = 1;
   if constexpr (NZ == 2 && NSPEC == 1) {
     // triangle-once builds: the default grid with an Hd series, one element
-    if (tri && (ch.n_hd == 12 || ch.n_hd == 16) && ch.zeta_int[0] == 1 && ch.zeta_int[1] == 4) {
+    if (tri && takes_triangles(NSPEC, NZ, ch)) {
       const size_t lds_t = v2_lds_bytes(true, b.cap, 0, 0, true);
       variant = 2;
       // 5 wavefronts per SIMD (96 VGPRs, 17 spilled); `wpe` (Options::bwd_wpe) == 4 (A/B) takes the 4-wavefront build
@@ -1802,18 +1869,27 @@ static int stagger_bits(const Options &opt, bool backward) {
 
 // `ch` must describe ONE beta (nb == 1).
 void launch_g4_forward_v2(const SFParams &sf, const AngChunk &ch, int ng, int nz, bool geometry,
-                          bool reduce, const DeviceBatch &b, const Options &opt, hipStream_t s) {
+                          bool reduce, bool full_list_unread, const DeviceBatch &b, const Options &opt, hipStream_t s) {
   if (b.n_blk == 0) return;
   const int nspec = sf.n_elements;
   // bit 0: compute the pair geometry; bit 1: assemble the descriptors at the end; bit 2: this is
-  // the only forward launch (all angular channels are here)
+  // the only forward launch (all angular channels are here); bit 3: nobody will read the full job list;
+  // bit 4: the pair records go out write-through (wt_handover)
   const int geom = (geometry ? 1 : 0) | (reduce ? 2 : 0) | ((geometry && reduce) ? 4 : 0) |
-                   stagger_bits(opt, false);
+                   (full_list_unread ? 8 : 0) | (wt_handover(b) ? 16 : 0) | stagger_bits(opt, false);
   TA_DISPATCH_V2(fwd_t, sf, ch, b, geom, opt.fwd_wpe, s);
+}
+
+bool v2_backward_takes_triangles(const SFParams &sf, const AngChunk &ch, int ng, int nz) {
+  (void)ng;
+  return takes_triangles(sf.n_elements, nz, ch);
 }
 
 int launch_backward_v2(const SFParams &sf, const AngChunk &ch, int ng, int nz, bool first, bool triangles,
                        const DeviceBatch &b, const Options &opt, hipStream_t s) {
+#ifdef TA_PROBE_NO_HANDOVER
+  throw std::domain_error("TA_PROBE_NO_HANDOVER build: the forward kernel left no pair records, no forces");
+#endif
   if (b.n_blk == 0) return 0;
   const int nspec = sf.n_elements;
   const int f = (first ? 1 : 0) | stagger_bits(opt, true);
