@@ -363,7 +363,8 @@ int ta_step_view(ta_handle h, const double *positions, const double *cells, uint
  * axis), computed inside the integrator launch with ONE force evaluation per step. Per frame, with h the cell
  * (rows are lattice vectors), V = |det h|, W the library's virial (dE / d strain) of the evaluation at x_k, P0
  * the target pressure, beta the compressibility and taup a time, step k -> k + 1 does, in this order:
- *     1. the thermostat's velocity part as above (Berendsen: v <- lambda v; Langevin: nothing here)
+ *     1. the thermostat's velocity part (Berendsen: v <- lambda v; Langevin: nothing here; Nose-Hoover chain,
+ *        below: the opening half-update)
  *     2. P_c = (sum_i m_i v_ic^2 - W_cc) / V for c = x, y, z, from the velocities as they stand after 1.
  *        isotropic: P = (P_x + P_y + P_z) / 3 and mu_x = mu_y = mu_z = 1 - (dt / taup) (beta / 3) (P0 - P)
  *        with a mask: mu_c = 1 - (dt / taup) (beta / 3) (P0 - P_c) on free axes, mu_c = 1 exactly on the others
@@ -374,7 +375,7 @@ int ta_step_view(ta_handle h, const double *positions, const double *cells, uint
  *        F_k, the forces evaluated at the UNSCALED x_k. This is what ASE does when forces are handed to
  *        step(); ASE evaluates again after the scaling when none are handed in. The difference is of
  *        order 1 - mu per step.
- * The barostat composes with every thermostat setting: none, Berendsen, Langevin. It needs the frame's three
+ * The barostat composes with every thermostat setting: none, Berendsen, Langevin, Nose-Hoover chain. It needs the frame's three
  * sums of m v_c^2 before any position is scaled, so one workgroup of 1024 threads owns a whole frame, as with
  * the Berendsen thermostat; the recorded kinetic energy is half the total of the three sums.
  *   ta_md_set_barostat   NULL or taup <= 0 switches the barostat off (the default). A property of the handle
@@ -402,7 +403,54 @@ int ta_step_view(ta_handle h, const double *positions, const double *cells, uint
  *   ta_md_get_records    volume [n_rec][n_frames], press [n_rec][n_frames][3] (either may be NULL) of the last
  *                        successful barostat run, at the slots of its epot / ekin: V and P_c of the recorded
  *                        state from the recorded kinetic sums (with Berendsen scaling: the sums before the
- *                        scaling). TA_ERR_INVALID when the last run had no barostat. */
+ *                        scaling). TA_ERR_INVALID when the last run had no barostat.
+ *
+ * Nose-Hoover chain (deterministic, time-reversible canonical sampling): names as ASE's NoseHooverChainNVT
+ * (tdamp = tau, tchain = chain, tloop = loops), masses as LAMMPS fix nvt with Tdamp = tau. Every frame has
+ * g = 3 n_atoms - dof_removed degrees of freedom and its own chain of M thermostats with positions eta_k,
+ * velocities veta_k and masses Q_1 = g kT0 tau^2, Q_k = kT0 tau^2 (k >= 2). With K the frame's kinetic energy,
+ *     G_1 = (2 K - g kT0) / Q_1,   G_k = (Q_{k-1} veta_{k-1}^2 - kT0) / Q_k   (k >= 2)
+ * One half-update over Delta = dt / 2 is L loops of d = Delta / L, with s starting at 1 and G_1 evaluated with
+ * the current K s^2:
+ *     veta_M += (d/2) G_M
+ *     for k = M-1 .. 1:  a = exp(-(d/4) veta_{k+1});  veta_k = (veta_k a + (d/2) G_k) a
+ *     s *= exp(-d veta_1);   eta_k += d veta_k (all k)
+ *     for k = 1 .. M-1:  a = exp(-(d/4) veta_{k+1});  veta_k = (veta_k a + (d/2) G_k) a   (G_k as they now stand)
+ *     veta_M += (d/2) G_M
+ * then v <- s v for the frame's atoms and K <- K s^2 (M = 1: the two loops over k are empty and G_M is G_1).
+ * A step is: half-update, the velocity Verlet step above, half-update. The conserved quantity per frame is
+ *     H' = K + E_pot + E_chain,   E_chain = sum_k Q_k veta_k^2 / 2 + g kT0 eta_1 + kT0 sum_{k>=2} eta_k
+ * Under this thermostat record 0 is the state at entry and record r > 0 the state AFTER the closing half-update
+ * of its step: ekin is K s^2 and e_chain the chain terms as they stand then, so ekin + epot + e_chain is H' at
+ * every slot (under Berendsen ekin is the value before the scaling). The centre-of-mass momentum is not
+ * removed: hand in velocities without drift and choose dof_removed to match. One workgroup owns a whole frame,
+ * as with the Berendsen thermostat, and the chain arithmetic is one thread's, in fp64.
+ * The barostat composes with it: step 1 of its order is the opening half-update, so the pressure behind mu is
+ * that of the velocities after it, and the recorded press is that of the recorded state.
+ *   ta_md_set_nose_hoover  NULL or kT0 <= 0 switches it off (the default; always allowed). A property of the
+ *                        handle like the other thermostats: ta_set_frames keeps the setting and drops the MD
+ *                        state, chain included; ta_md_init sets every chain to eta = veta = 0, and so does a
+ *                        call that changes `chain` while the thermostat is on. Only one thermostat at a time:
+ *                        TA_ERR_INVALID while Berendsen or Langevin is on, and both refuse to go on while this
+ *                        one is. TA_ERR_INVALID, with the argument named by ta_last_error and the setting left
+ *                        as it was: kT0 not finite, tau not a finite time > 0, chain outside
+ *                        1 .. TA_MD_MAX_CHAIN, loops outside 1 .. 16, dof_removed < 0.
+ *   ta_md_run            TA_ERR_INVALID for a batch in which some frame has g < 1.
+ *   ta_md_get_chain      eta / veta [n_frames][chain] of the resident state; either may be NULL. Needs
+ *                        ta_md_init and the thermostat on, as does
+ *   ta_md_set_chain      the restart call: finite values [n_frames][chain], NULL = zeros. With the positions and
+ *                        velocities of ta_md_get_state handed to ta_set_frames / ta_md_init, a run goes on
+ *                        where another stopped.
+ *   ta_md_get_chain_records  e_chain [n_rec][n_frames] of the last successful run, at the slots of its epot /
+ *                        ekin. TA_ERR_INVALID when that run did not use this thermostat. */
+#define TA_MD_MAX_CHAIN 8
+typedef struct {
+  double kT0;           /* target, energy; <= 0 switches the thermostat off (the default) */
+  double tau;           /* time, finite, > 0 */
+  int32_t chain;        /* M, 1 .. TA_MD_MAX_CHAIN */
+  int32_t loops;        /* L, 1 .. 16 */
+  int32_t dof_removed;  /* >= 0; g = 3 n_atoms - dof_removed */
+} ta_md_nhc_params;
 typedef struct {
   double pressure;         /* target, energy / volume (eV / A^3) */
   double taup;             /* time constant; <= 0: barostat off */
@@ -420,6 +468,10 @@ int ta_md_get_state(ta_handle h, double *positions, double *velocities);
 int ta_md_set_barostat(ta_handle h, const ta_md_barostat_params *p);
 int ta_md_get_cell(ta_handle h, double *cells);
 int ta_md_get_records(ta_handle h, double *volume, double *press);
+int ta_md_set_nose_hoover(ta_handle h, const ta_md_nhc_params *p);
+int ta_md_get_chain(ta_handle h, double *eta, double *veta);
+int ta_md_set_chain(ta_handle h, const double *eta, const double *veta);
+int ta_md_get_chain_records(ta_handle h, double *e_chain);
 
 /* Device-resident structure relaxation: the resident batch is brought to a force minimum in ONE call, every
  * frame on its own, with positions, velocities and forces staying on the device. The optimiser is FIRE

@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = [
     "ta_md_init", "ta_md_set_thermostat", "ta_md_run", "ta_md_get_state",
     "ta_md_set_langevin", "ta_md_noise",
     "ta_md_set_barostat", "ta_md_get_cell", "ta_md_get_records",
+    "ta_md_set_nose_hoover", "ta_md_get_chain", "ta_md_set_chain", "ta_md_get_chain_records",
     "ta_relax_init", "ta_relax_run", "ta_relax_get_state",
     "ta_relax_set_cell", "ta_relax_get_cell",
     "ta_relax_set_band", "ta_relax_get_band",
@@ -111,6 +112,14 @@ class FireParams(C.Structure):
 class MdBarostatParams(C.Structure):
     _fields_ = [("pressure", C.c_double), ("taup", C.c_double), ("compressibility", C.c_double),
                 ("mask", C.c_int32 * 3), ("isotropic", C.c_int32)]
+
+
+TA_MD_MAX_CHAIN = 8  # include/tensoralloy_amd.h: TA_MD_MAX_CHAIN
+
+
+class MdNhcParams(C.Structure):
+    _fields_ = [("kT0", C.c_double), ("tau", C.c_double), ("chain", C.c_int32), ("loops", C.c_int32),
+                ("dof_removed", C.c_int32)]
 
 
 class RelaxCellParams(C.Structure):
@@ -288,6 +297,10 @@ def load():
     lib.ta_md_set_barostat.argtypes = [H, C.POINTER(MdBarostatParams)]
     lib.ta_md_get_cell.argtypes = [H, _dp]
     lib.ta_md_get_records.argtypes = [H, _dp, _dp]
+    lib.ta_md_set_nose_hoover.argtypes = [H, C.POINTER(MdNhcParams)]
+    lib.ta_md_get_chain.argtypes = [H, _dp, _dp]
+    lib.ta_md_set_chain.argtypes = [H, _dp, _dp]
+    lib.ta_md_get_chain_records.argtypes = [H, _dp]
     lib.ta_relax_init.argtypes = [H, C.POINTER(FireParams), C.POINTER(C.c_uint8)]
     lib.ta_relax_run.argtypes = [H, C.c_int32, C.c_double, C.c_uint32, _ip, _ip, _dp, _ip]
     lib.ta_relax_get_state.argtypes = [H, _dp, _dp, _dp, _dp, _ip]

@@ -354,6 +354,14 @@ struct ta_context {
   int md_chunk = 0, md_n_blk = 0;
   int64_t md_ref_builds = -1;
   double md_kT0 = 0.0, md_tau = 0.0;
+  // Nose-Hoover chain (ta_md_set_nose_hoover; off while md_nhc_on is false): the setting, the chain state
+  // [F][TA_MD_MAX_CHAIN] (zeroed by ta_md_init), the record of the running ta_md_run and the host's copy
+  // of the last successful run's chain terms
+  bool md_nhc_on = false;
+  ta_md_nhc_params md_nhc_p = {0.0, 0.0, 3, 1, 0};
+  DevBuf<double> md_nhc_eta, md_nhc_veta, md_nhc_rec;
+  bool md_nhc_rec_valid = false;
+  std::vector<double> md_rec_chain;  // [n_rec][F]
   // Langevin (ta_md_set_langevin; off while md_friction == 0): bath, friction, the key of the noise; the
   // steps integrated since ta_md_init (the noise's step counter) and the scratch of ta_md_noise
   double md_lv_kT0 = 0.0, md_friction = 0.0;
@@ -1238,7 +1246,9 @@ int ta_destroy(ta_handle h) {
   h->hvp_buf.release();
   h->filt_scratch.release();
   h->nl_recs.release();
-  for (auto *b : {&h->md_mass, &h->md_vel, &h->md_ref, &h->md_epot, &h->md_ke, &h->md_noise}) b->release();
+  for (auto *b : {&h->md_mass, &h->md_vel, &h->md_ref, &h->md_epot, &h->md_ke, &h->md_noise, &h->md_nhc_eta,
+                  &h->md_nhc_veta, &h->md_nhc_rec})
+    b->release();
   h->md_blk_start.release();
   h->md_status.release();
   h->md_status_host.release();
@@ -1999,6 +2009,12 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
     h->md_ref.ensure(3 * N + 1);
     h->md_status.ensure(2);
     h->md_status_host.ensure(64);
+    const size_t n_chain = h->keep_natoms.size() * ta::kMdMaxChain;  // every frame's chain starts at rest
+    h->md_nhc_eta.ensure(n_chain + 1);
+    h->md_nhc_veta.ensure(n_chain + 1);
+    HIP_CHECK(hipMemset(h->md_nhc_eta.ptr, 0, (n_chain + 1) * sizeof(double)));
+    HIP_CHECK(hipMemset(h->md_nhc_veta.ptr, 0, (n_chain + 1) * sizeof(double)));
+    h->md_nhc_rec_valid = false;
     if (N) {
       HIP_CHECK(hipMemcpy(h->md_mass.ptr, masses, N * sizeof(double), hipMemcpyHostToDevice));
       if (velocities)
@@ -2023,6 +2039,9 @@ int ta_md_set_thermostat(ta_handle h, double kT0, double tau) {
   if (kT0 > 0.0 && h->md_friction > 0.0)
     return fail(h, TA_ERR_INVALID, "ta_md_set_thermostat: the Langevin thermostat is on; switch it off "
                                    "(ta_md_set_langevin with friction 0) before the Berendsen thermostat goes on");
+  if (kT0 > 0.0 && h->md_nhc_on)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_thermostat: the Nose-Hoover chain thermostat is on; switch it off "
+                                   "(ta_md_set_nose_hoover with NULL) before the Berendsen thermostat goes on");
   h->md_kT0 = kT0 > 0.0 ? kT0 : 0.0;
   h->md_tau = kT0 > 0.0 ? tau : 0.0;
   return TA_OK;
@@ -2037,9 +2056,110 @@ int ta_md_set_langevin(ta_handle h, double kT0, double friction, uint64_t seed) 
   if (friction > 0.0 && h->md_kT0 > 0.0)
     return fail(h, TA_ERR_INVALID, "ta_md_set_langevin: the Berendsen thermostat is on; switch it off "
                                    "(ta_md_set_thermostat with kT0 0) before the Langevin thermostat goes on");
+  if (friction > 0.0 && h->md_nhc_on)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_langevin: the Nose-Hoover chain thermostat is on; switch it off "
+                                   "(ta_md_set_nose_hoover with NULL) before the Langevin thermostat goes on");
   h->md_friction = friction;
   h->md_lv_kT0 = friction > 0.0 ? kT0 : 0.0;
   h->md_seed = seed;
+  return TA_OK;
+}
+
+int ta_md_set_nose_hoover(ta_handle h, const ta_md_nhc_params *p) {
+  if (!h) return TA_ERR_INVALID;
+  if (p && std::isnan(p->kT0)) return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: kT0 must be finite");
+  if (!p || !(p->kT0 > 0.0)) {
+    h->md_nhc_on = false;
+    return TA_OK;
+  }
+  if (!std::isfinite(p->kT0)) return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: kT0 must be finite");
+  if (!(p->tau > 0.0) || !std::isfinite(p->tau))
+    return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: tau must be a finite time > 0");
+  if (p->chain < 1 || p->chain > TA_MD_MAX_CHAIN)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: chain must be 1 .. " + std::to_string(TA_MD_MAX_CHAIN));
+  if (p->loops < 1 || p->loops > 16) return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: loops must be 1 .. 16");
+  if (p->dof_removed < 0) return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: dof_removed must be >= 0");
+  if (h->md_kT0 > 0.0)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: the Berendsen thermostat is on; switch it off "
+                                   "(ta_md_set_thermostat with kT0 0) before the Nose-Hoover chain goes on");
+  if (h->md_friction > 0.0)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: the Langevin thermostat is on; switch it off "
+                                   "(ta_md_set_langevin with friction 0) before the Nose-Hoover chain goes on");
+  if (h->md_nhc_on && h->md_nhc_p.chain != p->chain && h->md_valid) {
+    // another chain length: the slots beyond the old one hold nothing, the chain starts again at rest
+    const size_t n_chain = h->keep_natoms.size() * ta::kMdMaxChain;
+    const int rc = guarded(h, [&]() {
+      HIP_CHECK(hipStreamSynchronize(h->stream));
+      HIP_CHECK(hipMemset(h->md_nhc_eta.ptr, 0, (n_chain + 1) * sizeof(double)));
+      HIP_CHECK(hipMemset(h->md_nhc_veta.ptr, 0, (n_chain + 1) * sizeof(double)));
+    });
+    if (rc != TA_OK) return rc;
+  }
+  h->md_nhc_p = *p;
+  h->md_nhc_on = true;
+  return TA_OK;
+}
+
+namespace {
+// what ta_md_get_chain and ta_md_set_chain need; returns 0 or the error code
+int md_chain_ready(ta_context *h, const char *who) {
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
+  if (!h->md_valid) return fail(h, TA_ERR_INVALID, std::string(who) + " called before ta_md_init");
+  if (!h->md_nhc_on)
+    return fail(h, TA_ERR_INVALID, std::string(who) + ": the Nose-Hoover chain thermostat is off (ta_md_set_nose_hoover)");
+  return TA_OK;
+}
+}  // namespace
+
+int ta_md_get_chain(ta_handle h, double *eta, double *veta) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int rc = md_chain_ready(h, "ta_md_get_chain")) return rc;
+  return guarded(h, [&]() {
+    const size_t F = h->keep_natoms.size(), M = (size_t)h->md_nhc_p.chain;
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    std::vector<double> buf(F * ta::kMdMaxChain);
+    for (int w = 0; w < 2; ++w) {
+      double *out = w ? veta : eta;
+      if (!out || !F) continue;
+      HIP_CHECK(hipMemcpy(buf.data(), w ? h->md_nhc_veta.ptr : h->md_nhc_eta.ptr, buf.size() * sizeof(double),
+                          hipMemcpyDeviceToHost));
+      for (size_t f = 0; f < F; ++f)
+        for (size_t k = 0; k < M; ++k) out[f * M + k] = buf[f * ta::kMdMaxChain + k];
+    }
+  });
+}
+
+int ta_md_set_chain(ta_handle h, const double *eta, const double *veta) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int rc = md_chain_ready(h, "ta_md_set_chain")) return rc;
+  const size_t F = h->keep_natoms.size(), M = (size_t)h->md_nhc_p.chain;
+  for (size_t j = 0; j < F * M; ++j) {
+    if (eta && !std::isfinite(eta[j])) return fail(h, TA_ERR_INVALID, "ta_md_set_chain: non-finite eta");
+    if (veta && !std::isfinite(veta[j])) return fail(h, TA_ERR_INVALID, "ta_md_set_chain: non-finite veta");
+  }
+  return guarded(h, [&]() {
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    std::vector<double> buf(F * ta::kMdMaxChain + 1);
+    for (int w = 0; w < 2; ++w) {
+      const double *in = w ? veta : eta;
+      std::fill(buf.begin(), buf.end(), 0.0);
+      if (in)
+        for (size_t f = 0; f < F; ++f)
+          for (size_t k = 0; k < M; ++k) buf[f * ta::kMdMaxChain + k] = in[f * M + k];
+      HIP_CHECK(hipMemcpy(w ? h->md_nhc_veta.ptr : h->md_nhc_eta.ptr, buf.data(), buf.size() * sizeof(double),
+                          hipMemcpyHostToDevice));
+    }
+  });
+}
+
+int ta_md_get_chain_records(ta_handle h, double *e_chain) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_chain_records: no resident batch");
+  if (!h->md_valid) return fail(h, TA_ERR_INVALID, "ta_md_get_chain_records called before ta_md_init");
+  if (!h->md_nhc_rec_valid)
+    return fail(h, TA_ERR_INVALID, "ta_md_get_chain_records: the last ta_md_run of this batch had no Nose-Hoover chain");
+  if (e_chain && !h->md_rec_chain.empty())
+    std::memcpy(e_chain, h->md_rec_chain.data(), h->md_rec_chain.size() * sizeof(double));
   return TA_OK;
 }
 
@@ -2123,26 +2243,36 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
         return fail(h, TA_ERR_INVALID, "ta_md_run: the barostat is on and the cell of frame " + std::to_string(f) + " is singular");
     }
   }
+  const bool nhc = h->md_nhc_on;
+  if (nhc) {
+    const size_t F = h->keep_natoms.size();
+    for (size_t f = 0; f < F; ++f)
+      if (3 * (int64_t)h->keep_natoms[f] - (int64_t)h->md_nhc_p.dof_removed < 1)
+        return fail(h, TA_ERR_INVALID, "ta_md_run: the Nose-Hoover chain is on and frame " + std::to_string(f) +
+                                       " has fewer than one degree of freedom (3 n_atoms - dof_removed)");
+  }
   if (n_rebuilds) *n_rebuilds = 0;
   want |= TA_WANT_ENERGY | TA_WANT_FORCES;
   want &= ~(uint32_t)TA_WANT_REUSE_DESCRIPTORS;
   if (baro) want |= TA_WANT_VIRIAL;  // the pressure
   h->md_rec_valid = false;
+  h->md_nhc_rec_valid = false;
   h->cell_running = h->md_baro_running = baro;
   const int rc = guarded(h, [&]() {
     const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
     hipStream_t s = h->stream;
     const bool thermostat = h->md_kT0 > 0.0, langevin = h->md_friction > 0.0;  // (never both)
     // with Berendsen scaling one workgroup owns a whole frame: the factor needs the frame's kinetic energy
-    // (the barostat: the frame's three sums of m v_c^2)
+    // (the barostat: the frame's three sums of m v_c^2; the Nose-Hoover chain: the kinetic energy again)
     int chunk = ta::kMdChunk;
-    if (thermostat || baro)
+    if (thermostat || baro || nhc)
       for (size_t f = 0; f < F; ++f) chunk = std::max(chunk, h->keep_natoms[f]);
-    const int threads = (thermostat || baro) ? 1024 : 256;
+    const int threads = (thermostat || baro || nhc) ? 1024 : 256;
     md_plan_blocks(h, chunk);
     const size_t n_blk = (size_t)h->md_n_blk, n_rec = (size_t)(n_steps / record_every) + 1;
     h->md_epot.ensure(n_rec * F + 1);
     h->md_ke.ensure(n_rec * n_blk + 1);
+    if (nhc) h->md_nhc_rec.ensure(n_rec * F + 1);
     const std::vector<double> cells_at_entry(baro ? h->ref_cells : std::vector<double>());
     if (baro) {  // every run starts on a list built for the resident cells: the cumulative scale is 1
       h->md_baro_rec.ensure(4 * n_rec * F + 1);
@@ -2198,6 +2328,11 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     for (int c = 0; c < 3; ++c) a.baro_mask[c] = h->md_baro_p.mask[c] ? 1 : 0;
     a.skin = h->skin;
     a.r_list = h->rmax + h->skin;
+    a.nhc = nhc ? 1 : 0;
+    a.nhc_chain = h->md_nhc_p.chain, a.nhc_loops = h->md_nhc_p.loops, a.nhc_dof = h->md_nhc_p.dof_removed;
+    a.nhc_kT0 = nhc ? h->md_nhc_p.kT0 : 0.0;
+    a.nhc_q = nhc ? h->md_nhc_p.kT0 * h->md_nhc_p.tau * h->md_nhc_p.tau : 0.0;
+    a.nhc_eta = h->md_nhc_eta.ptr, a.nhc_veta = h->md_nhc_veta.ptr, a.nhc_rec = h->md_nhc_rec.ptr;
     auto integrate = [&](int k, bool drift) {
       // (a rebuild may have moved the batch's arrays: the pointers are taken at every launch)
       a.pos = h->db.pos;
@@ -2266,6 +2401,11 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
         h->relax_cell_vel_host.assign(9 * F, 0.0);
       }
       h->md_rec_valid = true;
+    }
+    if (nhc) {
+      h->md_rec_chain.resize(n_rec * F);
+      if (F) HIP_CHECK(hipMemcpy(h->md_rec_chain.data(), h->md_nhc_rec.ptr, n_rec * F * sizeof(double), hipMemcpyDeviceToHost));
+      h->md_nhc_rec_valid = true;
     }
     if (epot && F) HIP_CHECK(hipMemcpy(epot, h->md_epot.ptr, n_rec * F * sizeof(double), hipMemcpyDeviceToHost));
     if (ekin && F) {

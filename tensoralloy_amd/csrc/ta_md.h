@@ -8,6 +8,7 @@ namespace ta {
 
 constexpr int kMdChunk = 1024;      // atoms per workgroup without Berendsen scaling (256 threads, 4 atoms each)
 constexpr int kMdLookahead = 4;     // steps ta_md_run enqueues between two looks at the status word
+constexpr int kMdMaxChain = 8;      // TA_MD_MAX_CHAIN: slots per frame of the Nose-Hoover chain arrays
 
 struct MdLaunch {
   double *pos;                // [N][3] db.pos, caller's atom order
@@ -49,6 +50,13 @@ struct MdLaunch {
   double baro_p0, baro_k;
   int baro_mask[3];
   double skin, r_list;
+  // Nose-Hoover chain (nhc != 0; every workgroup is then a whole frame, kT0 above is 0): the target, tau^2
+  // kT0 (Q_k for k >= 2; Q_1 = g Q_k with g = 3 n - nhc_dof), chain length M and loops L of a half-update,
+  // the chain state [F][kMdMaxChain] and the record of the chain terms of H'
+  int nhc, nhc_chain, nhc_loops, nhc_dof;
+  double nhc_kT0, nhc_q;
+  double *nhc_eta, *nhc_veta;  // [F][kMdMaxChain]
+  double *nhc_rec;             // [n_rec][F]
 };
 
 void launch_md_integrate(const MdLaunch &a, int threads, hipStream_t s);

@@ -44,6 +44,18 @@
 // ta_relax.hip with A = diag(s). A mu_c that is not a finite number > 0 is made a NaN, which the host finds
 // in the cells it downloads before the rebuild.
 //
+// The Nose-Hoover chain builds (md_integrate_kernel<false, ., true>; ta_md_set_nose_hoover) wrap the velocity
+// Verlet step into two half-updates of a chain of M thermostats per frame (Martyna, Tuckerman, Tobias, Klein,
+// Mol. Phys. 87, 1117; masses as LAMMPS fix nvt, names as ASE's NoseHooverChainNVT; the scheme is spelled out
+// in include/tensoralloy_amd.h). A half-update needs the frame's kinetic energy K and gives a factor s for the
+// frame's velocities, so one workgroup owns a whole frame and one reduction serves both half-updates of a
+// launch: after the pending half-kick and K, thread 0 closes step k (s1, K <- s1^2 K), the record takes
+// K, epot and the chain terms of the conserved quantity, thread 0 opens step k + 1 from the updated K (s2),
+// and the second loop scales by lambda = s1 s2 before its half-kick. The last launch of a run (no drift)
+// writes v <- s1 v instead. Thread 0 keeps eta and veta in LDS while it works, in fp64 with exp(), and
+// writes them back to [F][kMdMaxChain] arrays; the factors reach the other threads through LDS. All of it
+// sits behind the early return on the status word: a launch enqueued behind a stale list leaves the chain alone.
+//
 // The launch is predicated on a device word: a drift that finds an atom beyond skin / 2 writes its own
 // sequence number + 1 there (and into a page-locked word the host reads after a stream wait), still
 // writes valid positions, and every LATER launch returns at once. The host may therefore enqueue several
@@ -111,18 +123,51 @@ __global__ __launch_bounds__(256) void md_noise_kernel(unsigned long long seed, 
 
 // slots of the barostat's LDS block
 constexpr int kBaroMu = 0, kBaroScale = 3, kBaroLim2 = 6, kBaroWords = 7;
+// slots of the Nose-Hoover chain's LDS block
+constexpr int kNhcS1 = 0, kNhcS2 = 1, kNhcEta = 2, kNhcVeta = 2 + kMdMaxChain, kNhcWords = 2 + 2 * kMdMaxChain;
 
 __device__ __forceinline__ double md_cell_volume(const double *h) {
   return fabs(h[0] * (h[4] * h[8] - h[5] * h[7]) - h[1] * (h[3] * h[8] - h[5] * h[6]) + h[2] * (h[3] * h[7] - h[4] * h[6]));
 }
 
+// One half-update of a frame's chain over `delta` (thread 0 alone): L loops of d = delta / L, eta and veta
+// [M] in place. K is the frame's kinetic energy before it; returns s, the factor of the frame's velocities
+// (the kinetic energy is K s^2 afterwards). q1 = g kT0 tau^2, q = kT0 tau^2, gkT = g kT0.
+__device__ __forceinline__ double md_nhc_half(double *eta, double *veta, int M, int L, double delta, double K,
+                                              double gkT, double kT0, double q1, double q) {
+  const double d = delta / (double)L, hd = 0.5 * d, qd = 0.25 * d;
+  double s = 1.0;
+  // the force on thermostat k from the values as they stand
+  auto G = [&](int k) {
+    if (k == 0) return (2.0 * K * s * s - gkT) / q1;
+    return ((k == 1 ? q1 : q) * veta[k - 1] * veta[k - 1] - kT0) / q;
+  };
+  for (int l = 0; l < L; ++l) {
+    veta[M - 1] += hd * G(M - 1);
+    for (int k = M - 2; k >= 0; --k) {
+      const double e = exp(-qd * veta[k + 1]);
+      veta[k] = (veta[k] * e + hd * G(k)) * e;
+    }
+    s *= exp(-d * veta[0]);
+    for (int k = 0; k < M; ++k) eta[k] += d * veta[k];
+    for (int k = 0; k < M - 1; ++k) {
+      const double e = exp(-qd * veta[k + 1]);
+      veta[k] = (veta[k] * e + hd * G(k)) * e;
+    }
+    veta[M - 1] += hd * G(M - 1);
+  }
+  return s;
+}
+
 // kLangevin = false: velocity Verlet with the optional Berendsen factor; true: the Langevin step.
 // kBaro: the Berendsen barostat before the step (one workgroup per frame)
-template <bool kLangevin, bool kBaro>
+// kNhc: the Nose-Hoover chain around the velocity Verlet step (one workgroup per frame; never with kLangevin)
+template <bool kLangevin, bool kBaro, bool kNhc = false>
 __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
   __shared__ double s_wave[16];
   __shared__ double s_total;
   __shared__ double s_baro[kBaro ? kBaroWords : 1];  // (unused, and dropped, in the fixed-cell builds)
+  __shared__ double s_nhc[kNhc ? kNhcWords : 1];     // (likewise without the chain)
   // (0, or the value this very launch writes, or the mark of an earlier launch: the same branch in every thread)
   const unsigned mark = *static_cast<volatile unsigned *>(a.status);
   if (mark != 0u && mark <= a.seq) return;
@@ -185,6 +230,31 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
   } else {
     ke = md_block_sum(ke, s_wave, &s_total);
   }
+  double s1 = 1.0, s2 = 1.0;  // (kNhc: the factors of the closing and of the opening half-update)
+  if constexpr (kNhc) {
+    if (threadIdx.x == 0) {
+      const int M = a.nhc_chain;
+      double *eta = s_nhc + kNhcEta, *veta = s_nhc + kNhcVeta;
+      const size_t c0 = (size_t)f * kMdMaxChain;
+      for (int k = 0; k < M; ++k) eta[k] = a.nhc_eta[c0 + k], veta[k] = a.nhc_veta[c0 + k];
+      const double g = 3.0 * (double)(f_hi - f_lo) - (double)a.nhc_dof;  // (the host refused g < 1)
+      const double gkT = g * a.nhc_kT0, q1 = g * a.nhc_q;
+      if (a.kick2) s1 = md_nhc_half(eta, veta, M, a.nhc_loops, hdt, ke, gkT, a.nhc_kT0, q1, a.nhc_q);
+      if (a.rec >= 0) {  // the chain terms of H' beside K s1^2 and epot
+        double e = 0.5 * q1 * veta[0] * veta[0] + gkT * eta[0];
+        for (int k = 1; k < M; ++k) e += 0.5 * a.nhc_q * veta[k] * veta[k] + a.nhc_kT0 * eta[k];
+        a.nhc_rec[(size_t)a.rec * a.n_frames + f] = e;
+      }
+      if (a.drift) s2 = md_nhc_half(eta, veta, M, a.nhc_loops, hdt, ke * (s1 * s1), gkT, a.nhc_kT0, q1, a.nhc_q);
+      for (int k = 0; k < M; ++k) a.nhc_eta[c0 + k] = eta[k], a.nhc_veta[c0 + k] = veta[k];
+      s_nhc[kNhcS1] = s1, s_nhc[kNhcS2] = s2;
+    }
+    __syncthreads();
+    s1 = s_nhc[kNhcS1], s2 = s_nhc[kNhcS2];
+    const double s1sq = s1 * s1;  // the recorded state is the one after the closing half-update
+    ke *= s1sq;
+    if constexpr (kBaro) sx *= s1sq, sy *= s1sq, sz *= s1sq;
+  }
   if (threadIdx.x == 0 && a.rec >= 0) {
     a.ke_part[(size_t)a.rec * a.n_blk + blockIdx.x] = ke;
     if ((int)blockIdx.x == blk0) a.epot[(size_t)a.rec * a.n_frames + f] = a.energy[f];
@@ -195,6 +265,15 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
       r[0] = V, r[1] = (sx - W[0]) / V, r[2] = (sy - W[4]) / V, r[3] = (sz - W[8]) / V;
     }
   }
+  if constexpr (kNhc) {
+    if (!a.drift) {  // the run ends on a whole step: the closing factor goes into the velocities now
+      for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.vel[3 * i + c] = s1 * a.vel[3 * i + c];
+      }
+      return;
+    }
+  }
   if (!a.drift) return;
 
   double lambda = 1.0;
@@ -203,6 +282,7 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
     lambda = sqrt(1.0 + (a.kT0 / kT - 1.0) * a.dt_over_tau);
     lambda = lambda > 1.1 ? 1.1 : (lambda < 0.9 ? 0.9 : lambda);
   }
+  if constexpr (kNhc) lambda = s1 * s2;
   int stale = 0;
   double mu[3] = {1.0, 1.0, 1.0}, sc[3] = {1.0, 1.0, 1.0}, lim2 = a.lim2;
   if constexpr (kBaro) {
@@ -211,7 +291,9 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
 #pragma unroll
       for (int c = 0; c < 9; ++c) h[c] = a.cells[9 * (size_t)f + c];
       const double *W = a.virial + 9 * (size_t)f;
-      const double V = md_cell_volume(h), l2 = lambda * lambda;
+      const double V = md_cell_volume(h);
+      double l2 = lambda * lambda;
+      if constexpr (kNhc) l2 = s2 * s2;  // (sx, sy, sz already carry s1^2)
       double P[3] = {(l2 * sx - W[0]) / V, (l2 * sy - W[4]) / V, (l2 * sz - W[8]) / V};
       if (a.baro_iso) P[0] = P[1] = P[2] = (P[0] + P[1] + P[2]) / 3.0;
       double n2 = 0.0;
@@ -297,6 +379,13 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
 void launch_md_integrate(const MdLaunch &a, int threads, hipStream_t s) {
   if (a.n_blk <= 0) return;
   const dim3 grid((unsigned)a.n_blk), block((unsigned)threads);
+  if (a.nhc) {  // (ta_md_run made every workgroup a whole frame; ta_md_set_nose_hoover excludes Langevin)
+    if (a.baro)
+      hipLaunchKernelGGL((md_integrate_kernel<false, true, true>), grid, block, 0, s, a);
+    else
+      hipLaunchKernelGGL((md_integrate_kernel<false, false, true>), grid, block, 0, s, a);
+    return;
+  }
   if (a.baro) {  // (ta_md_run made every workgroup a whole frame)
     if (a.langevin)
       hipLaunchKernelGGL((md_integrate_kernel<true, true>), grid, block, 0, s, a);

@@ -36,6 +36,7 @@ class Engine:
         self._volumes = None
         self._relax_cell = False   # `relax_set_cell` is on: `relax_run` moves the cells
         self._md_barostat = False  # `md_set_barostat` is on: `md_run` moves the cells
+        self._md_chain = 0         # `md_set_nose_hoover` is on: thermostats per chain
         self._md_sig = None   # (n, numbers, pbc) of the single resident frame of `evaluate_md`
         self._md_cell = None
         self.batch_generation = 0  # bumped whenever the resident batch or its coordinates change
@@ -309,6 +310,43 @@ class Engine:
         self._check(self._lib.ta_md_set_barostat(self._handle, C.byref(bp)))
         self._md_barostat = bool(taup > 0.0)
 
+    def md_set_nose_hoover(self, kT=0.0, tau=0.0, chain=3, loops=1, dof_removed=0):
+        """Nose-Hoover chain thermostat of `md_run` (`ta_md_set_nose_hoover`; ASE's `NoseHooverChainNVT` with
+        tdamp = `tau`, tchain = `chain`, tloop = `loops`): target kT (eV; <= 0 switches it off, the default),
+        time constant (ASE time units), thermostats per chain (1 .. 8), loops per half-update (1 .. 16) and
+        the degrees of freedom to take off 3 n_atoms of every frame. Every frame has its own chain; `md_init`
+        puts it at rest. It excludes the Berendsen and the Langevin thermostat: switch the one that is on off
+        first. `md_run` then also returns `echain`, and `epot + ekin + echain` is conserved."""
+        p = _lib.MdNhcParams(float(kT), float(tau), int(chain), int(loops), int(dof_removed))
+        self._check(self._lib.ta_md_set_nose_hoover(self._handle, C.byref(p)))
+        self._md_chain = int(chain) if kT > 0.0 else 0
+
+    def md_chain(self):
+        """(eta, veta) [n_frames, chain]: positions and velocities of every frame's thermostat chain as the
+        device holds them (`ta_md_get_chain`). Needs `md_init` and `md_set_nose_hoover`."""
+        if self.info is None:
+            raise ValueError("md_chain: no resident batch (call set_frames first)")
+        shape = (int(self.info.n_frames), max(self._md_chain, 1))
+        eta, veta = np.empty(shape), np.empty(shape)
+        self._check(self._lib.ta_md_get_chain(self._handle, _lib.as_dp(eta), _lib.as_dp(veta)))
+        return eta, veta
+
+    def md_set_chain(self, eta=None, veta=None):
+        """Restart: hand the chains the (eta, veta) [n_frames, chain] of an earlier `md_chain` (None = zeros),
+        after `set_frames` + `md_init` with the positions and velocities of that moment (`ta_md_set_chain`)."""
+        if self.info is None:
+            raise ValueError("md_set_chain: no resident batch (call set_frames first)")
+        n = int(self.info.n_frames) * max(self._md_chain, 1)
+        arrays = []
+        for name, a in (("eta", eta), ("veta", veta)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.size != n:
+                    raise ValueError(f"md_set_chain: {name} [n_frames, chain] for every frame of the resident batch is needed")
+            arrays.append(a)
+        null = C.POINTER(C.c_double)()
+        self._check(self._lib.ta_md_set_chain(self._handle, *[null if a is None else _lib.as_dp(a) for a in arrays]))
+
     def md_cells(self):
         """Cells [n_frames, 3, 3] of the resident batch as the library holds them (`ta_md_get_cell`)."""
         if self.info is None:
@@ -334,7 +372,10 @@ class Engine:
         Afterwards `fetch(want | ENERGY | FORCES)` hands out the results of the last step.
         With `md_set_barostat` on, the cells follow the pressure, the dict also holds `volume` [n_rec, n_frames]
         and `press` [n_rec, n_frames, 3] (eV / A^3, per axis) of the recorded states, and a run that moved the
-        cells ends with one list build for the final cells (counted in `n_rebuilds`)."""
+        cells ends with one list build for the final cells (counted in `n_rebuilds`).
+        With `md_set_nose_hoover` on, the dict also holds `echain` [n_rec, n_frames], every record after the
+        first is the state after the closing half-update of its step, and `epot + ekin + echain` is the
+        conserved quantity."""
         if self.info is None:
             raise ValueError("md_run: no resident batch (call set_frames first)")
         n_steps, record_every = int(n_steps), int(record_every)
@@ -355,6 +396,9 @@ class Engine:
             self._check(self._lib.ta_list_sizes(self._handle, C.byref(n_pairs), C.byref(n_triples), C.byref(nnl)))
             self.info.n_pairs, self.info.n_triples, self.info.nnl_max = n_pairs.value, n_triples.value, nnl.value
         out = {"epot": epot, "ekin": ekin, "n_rebuilds": int(rebuilds.value)}
+        if self._md_chain:   # the chain terms of the conserved quantity, at the slots of epot / ekin
+            out["echain"] = np.empty((n_rec, F))
+            self._check(self._lib.ta_md_get_chain_records(self._handle, _lib.as_dp(out["echain"])))
         if self._md_barostat:   # the cells moved on the device: stress and pressure follow them
             out["volume"], out["press"] = self.md_records(n_rec)
             self._volumes = np.abs(np.linalg.det(self.md_cells()))

@@ -4,15 +4,29 @@ resident batch for n steps without moving coordinates, velocities or forces thro
 
 Units are ASE's: Angstrom, eV, amu, and therefore the time unit Angstrom sqrt(amu / eV); `fs` and `kB`
 are the same numbers as `ase.units.fs` and `ase.units.kB`. The integrator is ASE's `VelocityVerlet`, with
-one of two thermostats: ASE's `NVTBerendsen.scale_velocities` (`taut`), which steers the temperature but
-does not sample the canonical ensemble, or the second-order scheme of ASE's `Langevin` (`friction`), which
-does. None of them removes the centre-of-mass momentum (`maxwell_boltzmann(..., zero_momentum=True)` hands
+one of three thermostats: ASE's `NVTBerendsen.scale_velocities` (`taut`), which steers the temperature but
+does not sample the canonical ensemble; the second-order scheme of ASE's `Langevin` (`friction`), which
+does, with noise; or a Nose-Hoover chain (`tdamp`), which does without any. None of them removes the
+centre-of-mass momentum (`maxwell_boltzmann(..., zero_momentum=True)` hands
 out velocities without any; under Langevin the centre of mass then diffuses like one heavy particle).
 
 The Langevin noise is made on the device by a counter-based generator (Philox4x32-10, then Box-Muller): a
 pure function of (seed, step since the start, atom, component). A trajectory therefore depends on the seed
 alone, not on how `run` is cut into calls, on the skin or on list rebuilds, and `Engine.md_noise(step)` hands
 out the very numbers of a step.
+
+The Nose-Hoover chain (names as ASE's `NoseHooverChainNVT`: `tdamp`, `tchain`, `tloop`; masses as LAMMPS
+`fix nvt`) is deterministic and time-reversible, so velocity autocorrelations, diffusion constants and spectra
+can be taken from the thermostatted run. Every frame has g = 3 n - `dof_removed` degrees of freedom and a
+chain of `tchain` thermostats (eta_k, veta_k) with Q_1 = g kT tdamp^2 and Q_k = kT tdamp^2; a step is a
+half-update of the chain over dt / 2 (`tloop` loops), the velocity Verlet step, and another half-update, each
+of which multiplies the frame's velocities by one factor. The scheme is written out in
+include/tensoralloy_amd.h. The conserved quantity
+    H' = ekin + epot + sum_k Q_k veta_k^2 / 2 + g kT eta_1 + kT sum_{k>=2} eta_k
+is what `get_conserved_energy()` returns; the records of a run under this thermostat are taken after the
+closing half-update of a step, so that the three parts add up to H' at every slot (`Engine.md_run` hands out
+the chain part as `echain`). To restart, keep `Engine.md_state()` and `Engine.md_chain()` and hand them to
+`set_frames` / `md_init` and `Engine.md_set_chain`.
 
 Constant pressure: with `pressure`, `taup` and `compressibility` the cells follow a Berendsen barostat (ASE's
 `NPTBerendsen`; with a `mask` of three flags its `Inhomogeneous_NPTBerendsen`), under any of the thermostat
@@ -49,7 +63,7 @@ def maxwell_boltzmann(masses, kT, rng, zero_momentum=True):
 
 class DeviceMD:
     """
-    NVE (velocity Verlet), Berendsen NVT or Langevin NVT dynamics of one structure or of a batch of
+    NVE (velocity Verlet), Berendsen NVT, Langevin NVT or Nose-Hoover chain NVT dynamics of one structure or of a batch of
     independent structures, integrated on the GPU.
 
     engine_or_calculator : an `Engine`, or a `TensorAlloyCalculator` whose engine and skin are used (its
@@ -60,6 +74,11 @@ class DeviceMD:
     temperature_K, taut  : both given: Berendsen thermostat with that target and time constant
     temperature_K, friction : both given: Langevin thermostat with that bath temperature (>= 0; 0 is damped
                            dynamics) and friction (1 / ASE time unit, e.g. `0.01 / fs`)
+    temperature_K, tdamp : both given: Nose-Hoover chain thermostat with that target (> 0) and time constant
+                           (> 0, e.g. `20 * fs`); excludes `taut` and `friction`
+    tchain, tloop        : thermostats per chain (1 .. 8) and loops per half-update (1 .. 16)
+    dof_removed          : degrees of freedom taken off 3 n of every frame in the chain's g (3 for velocities
+                           without centre-of-mass motion)
     seed                 : of the Langevin noise, 0 .. 2^64 - 1; the same seed gives the same trajectory
     pressure, taup, compressibility : all three given: Berendsen barostat with that target (eV / A^3, e.g.
                            `1.0 * GPa`), time constant (> 0) and compressibility (A^3 / eV, >= 0), with any
@@ -74,7 +93,7 @@ class DeviceMD:
 
     def __init__(self, engine_or_calculator, atoms_or_list, timestep, temperature_K=None, taut=None,
                  velocities=None, masses=None, friction=None, seed=0, pressure=None, taup=None,
-                 compressibility=None, mask=None):
+                 compressibility=None, mask=None, tdamp=None, tchain=3, tloop=1, dof_removed=0):
         if not (np.isfinite(timestep) and timestep > 0.0):
             raise ValueError("DeviceMD: timestep must be a finite time > 0")
         barostat = (pressure, taup, compressibility)
@@ -94,7 +113,22 @@ class DeviceMD:
             raise ValueError("DeviceMD: mask belongs to the barostat (pressure, taup, compressibility)")
         if taut is not None and friction is not None:
             raise ValueError("DeviceMD: taut (Berendsen) and friction (Langevin) exclude each other")
-        if friction is not None:
+        if tdamp is not None:
+            if taut is not None or friction is not None:
+                raise ValueError("DeviceMD: tdamp (Nose-Hoover chain) excludes taut (Berendsen) and friction (Langevin)")
+            if temperature_K is None:
+                raise ValueError("DeviceMD: the Nose-Hoover chain thermostat needs temperature_K with tdamp")
+            if not (np.isfinite(tdamp) and tdamp > 0.0):
+                raise ValueError("DeviceMD: tdamp must be a finite time > 0")
+            if not (np.isfinite(temperature_K) and temperature_K > 0.0):
+                raise ValueError("DeviceMD: temperature_K must be finite and > 0")
+            if not 1 <= int(tchain) <= 8:
+                raise ValueError("DeviceMD: tchain must be 1 .. 8")
+            if not 1 <= int(tloop) <= 16:
+                raise ValueError("DeviceMD: tloop must be 1 .. 16")
+            if int(dof_removed) < 0:
+                raise ValueError("DeviceMD: dof_removed must be >= 0")
+        elif friction is not None:
             if temperature_K is None:
                 raise ValueError("DeviceMD: the Langevin thermostat needs temperature_K with friction")
             if not (np.isfinite(friction) and friction > 0.0):
@@ -139,10 +173,17 @@ class DeviceMD:
             raise ValueError("DeviceMD: one mass for every atom is needed")
         engine.set_frames(self.atoms_list)
         engine.md_init(masses, velocities)
-        if friction is not None:   # (one thermostat at a time: the other goes off first)
+        self._chain = tdamp is not None
+        if self._chain:   # (one thermostat at a time: the others go off first)
+            engine.md_set_thermostat(0.0, 0.0)
+            engine.md_set_langevin(0.0, 0.0, 0)
+            engine.md_set_nose_hoover(kB * temperature_K, tdamp, int(tchain), int(tloop), int(dof_removed))
+        elif friction is not None:
+            engine.md_set_nose_hoover(0.0)
             engine.md_set_thermostat(0.0, 0.0)
             engine.md_set_langevin(kB * temperature_K, friction, int(seed))
         else:
+            engine.md_set_nose_hoover(0.0)
             engine.md_set_langevin(0.0, 0.0, 0)
             engine.md_set_thermostat(kB * temperature_K if temperature_K is not None else 0.0,
                                      taut if taut is not None else 0.0)
@@ -153,6 +194,7 @@ class DeviceMD:
         self._natoms = np.array([len(a) for a in self.atoms_list], dtype=np.int64)
         self.velocities = velocities.copy()
         self.epot = self.ekin = None   # per-frame records of the last state
+        self.echain = None   # ... under the Nose-Hoover chain: the chain terms of the conserved quantity
         self.volume = self.press = None   # ... under the barostat: V [n_frames] and P_c [n_frames, 3]
         self.n_rebuilds = 0
         self._refresh(engine.md_run(0, self.dt))
@@ -166,6 +208,8 @@ class DeviceMD:
     def _refresh(self, out):
         self.epot, self.ekin = out["epot"][-1].copy(), out["ekin"][-1].copy()
         self.n_rebuilds += out["n_rebuilds"]
+        if self._chain:
+            self.echain = out["echain"][-1].copy()
         x, v = self.engine.md_state()
         self.velocities = v
         a = 0
@@ -205,6 +249,14 @@ class DeviceMD:
 
     def get_kinetic_energy(self):
         return float(self.ekin[0]) if self._single else self.ekin.copy()
+
+    def get_conserved_energy(self):
+        """ekin + epot + the chain terms per frame: the conserved quantity of the Nose-Hoover chain dynamics.
+        Needs the Nose-Hoover chain thermostat."""
+        if self.echain is None:
+            raise ValueError("DeviceMD.get_conserved_energy: the Nose-Hoover chain thermostat is off (temperature_K, tdamp)")
+        e = self.ekin + self.epot + self.echain
+        return float(e[0]) if self._single else e
 
     def get_volume(self):
         """Cell volume per frame, in A^3."""
