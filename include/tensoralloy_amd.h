@@ -442,8 +442,48 @@ int ta_step_view(ta_handle h, const double *positions, const double *cells, uint
  *                        velocities of ta_md_get_state handed to ta_set_frames / ta_md_init, a run goes on
  *                        where another stopped.
  *   ta_md_get_chain_records  e_chain [n_rec][n_frames] of the last successful run, at the slots of its epot /
- *                        ekin. TA_ERR_INVALID when that run did not use this thermostat. */
+ *                        ekin. TA_ERR_INVALID when that run did not use this thermostat.
+ *
+ * Time correlations inside the loop (opt-in; with sampling never switched on nothing changes). Let t be the
+ * absolute step (steps integrated since ta_md_init, the counter of the Langevin noise). With n_lags = L and
+ * sample_every = s the whole-step state (x(t), v(t)) of every t with t % s == 0 is sampled, once: the positions
+ * as the device holds them (unwrapped), and the velocities whose kinetic energy the record slot of that step
+ * holds (velocity Verlet / Berendsen: after the second half-kick, before the next Berendsen factor; Langevin:
+ * after the second update of step t - 1; Nose-Hoover chain: after the closing half-update). Samples are numbered
+ * n = 0, 1, ... from the first one taken after sampling was switched on; sample n lives in slot n % L of a ring
+ * [L][n_atoms_total][3] in device memory, written by the integrator launch. Behind every launch that sampled a
+ * correlation kernel adds, for every lag k = 0 .. min(n, L - 1), frame f and element e of the model,
+ *     A_v[f][e][k] += sum over atoms i of f with species e of  v_i(n) . v_i(n - k)
+ *     A_x[f][e][k] += sum over the same atoms of               |x_i(n) - x_i(n - k)|^2
+ * in a fixed order (no floating-point atomics), so the sums do not depend on how a run is cut into calls, on
+ * the skin or on list rebuilds beyond what the trajectories themselves differ by. The number of time origins at
+ * lag k is max(0, n_samples - k); normalising by it and by the atoms of (f, e) gives the velocity
+ * autocorrelation and the mean-square displacement. No centre-of-mass correction is made.
+ *   ta_md_set_sampling   NULL or n_lags == 0 switches sampling off (the default; always allowed) and frees the
+ *                        ring. Switching on needs a resident batch and ta_md_init; it allocates the rings and
+ *                        the accumulators [n_frames][n_elements][n_lags] x 2, zeroes the accumulators and
+ *                        forgets earlier samples (so does every further call). A property of the handle like
+ *                        the thermostats: ta_set_frames keeps the setting and drops the data with the MD state;
+ *                        ta_md_init starts an empty ring and zero accumulators. TA_ERR_INVALID, with the
+ *                        argument named by ta_last_error and the setting left as it was: n_lags outside
+ *                        0 .. 4096, sample_every < 1. TA_ERR_NOMEM when the device allocation fails; sampling
+ *                        is then off.
+ *   ta_md_run            TA_ERR_INVALID while sampling and the barostat are both on (displacements in a moving
+ *                        cell are not defined here). A run that fails leaves the correlation data invalid: both
+ *                        getters are TA_ERR_INVALID until ta_md_set_sampling or ta_md_init is called again.
+ *   ta_md_get_correlations  vacf_sum / msd_sum [n_frames][n_elements][n_lags]: the raw sums A_v / A_x;
+ *                        info [4] = {n_samples, n_lags, sample_every, absolute step of the newest sample or -1}.
+ *                        Any pointer may be NULL.
+ *   ta_md_get_samples    the snapshots first_lag .. first_lag + n - 1 back from the newest one (0 = the newest):
+ *                        positions / velocities [n][n_atoms_total][3] and their absolute steps [n]; any pointer
+ *                        may be NULL. TA_ERR_INVALID when first_lag < 0, n < 0 or first_lag + n exceeds the
+ *                        min(n_samples, n_lags) snapshots held. */
 #define TA_MD_MAX_CHAIN 8
+#define TA_MD_MAX_LAGS 4096
+typedef struct {
+  int32_t n_lags;        /* L, 1 .. TA_MD_MAX_LAGS; 0 switches sampling off (the default) */
+  int32_t sample_every;  /* s >= 1 */
+} ta_md_sampling_params;
 typedef struct {
   double kT0;           /* target, energy; <= 0 switches the thermostat off (the default) */
   double tau;           /* time, finite, > 0 */
@@ -472,6 +512,10 @@ int ta_md_set_nose_hoover(ta_handle h, const ta_md_nhc_params *p);
 int ta_md_get_chain(ta_handle h, double *eta, double *veta);
 int ta_md_set_chain(ta_handle h, const double *eta, const double *veta);
 int ta_md_get_chain_records(ta_handle h, double *e_chain);
+int ta_md_set_sampling(ta_handle h, const ta_md_sampling_params *p);
+int ta_md_get_correlations(ta_handle h, double *vacf_sum, double *msd_sum, int64_t *info);
+int ta_md_get_samples(ta_handle h, int32_t first_lag, int32_t n, double *positions, double *velocities,
+                      int64_t *steps);
 
 /* Device-resident structure relaxation: the resident batch is brought to a force minimum in ONE call, every
  * frame on its own, with positions, velocities and forces staying on the device. The optimiser is FIRE

@@ -362,6 +362,17 @@ struct ta_context {
   DevBuf<double> md_nhc_eta, md_nhc_veta, md_nhc_rec;
   bool md_nhc_rec_valid = false;
   std::vector<double> md_rec_chain;  // [n_rec][F]
+  // Sampling (ta_md_set_sampling; off while md_samp_on is false): the setting; the rings [L][N][3], the
+  // accumulators [2][F][E][L] (v . v, then |dx|^2), the correlation launch's partials and chunk layout; the
+  // absolute step of sample 0 (a multiple of sample_every) and of the newest sample (-1: none); whether the
+  // data are those of a run that succeeded
+  bool md_samp_on = false;
+  ta_md_sampling_params md_samp_p = {0, 1};
+  DevBuf<double> md_ring_x, md_ring_v, md_corr_acc, md_corr_part;
+  DevBuf<int32_t> md_corr_blk;
+  int md_corr_chunks = 0;
+  int64_t md_samp_origin = 0, md_samp_last = -1;
+  bool md_samp_valid = false;
   // Langevin (ta_md_set_langevin; off while md_friction == 0): bath, friction, the key of the noise; the
   // steps integrated since ta_md_init (the noise's step counter) and the scratch of ta_md_noise
   double md_lv_kT0 = 0.0, md_friction = 0.0;
@@ -1247,8 +1258,9 @@ int ta_destroy(ta_handle h) {
   h->filt_scratch.release();
   h->nl_recs.release();
   for (auto *b : {&h->md_mass, &h->md_vel, &h->md_ref, &h->md_epot, &h->md_ke, &h->md_noise, &h->md_nhc_eta,
-                  &h->md_nhc_veta, &h->md_nhc_rec})
+                  &h->md_nhc_veta, &h->md_nhc_rec, &h->md_ring_x, &h->md_ring_v, &h->md_corr_acc, &h->md_corr_part})
     b->release();
+  h->md_corr_blk.release();
   h->md_blk_start.release();
   h->md_status.release();
   h->md_status_host.release();
@@ -1901,6 +1913,57 @@ void md_plan_blocks(ta_context *h, int chunk) {
   h->md_n_blk = start[F];
 }
 
+// frees what sampling holds on the device; the setting stays
+void md_sampling_release(ta_context *h) {
+  for (auto *b : {&h->md_ring_x, &h->md_ring_v, &h->md_corr_acc, &h->md_corr_part}) b->release();
+  h->md_corr_blk.release();
+  h->md_corr_chunks = 0;
+  h->md_samp_valid = false;
+  h->md_samp_last = -1;
+}
+
+// exactly n elements (the ring may take gigabytes: no head room); false when the device has no room
+extern "C++" template <typename T>
+bool md_alloc_exact(DevBuf<T> &b, size_t n) {
+  b.release();
+  T *fresh = nullptr;
+  if (hipMalloc((void **)&fresh, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  b.ptr = fresh;
+  b.cap = std::max<size_t>(n, 1);
+  return true;
+}
+
+// Rings, zeroed accumulators and the correlation launch's chunk layout for the resident batch under setting
+// `p`, with no sample held: sample 0 will be the first multiple of sample_every at or behind the steps
+// integrated so far. False when the device has no room (everything is released then); throws otherwise.
+bool md_sampling_alloc(ta_context *h, const ta_md_sampling_params &p) {
+  const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
+  const size_t L = (size_t)p.n_lags, E = (size_t)h->n_elements;
+  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches read the old buffers)
+  md_sampling_release(h);
+  std::vector<int32_t> start(F + 1, 0);
+  for (size_t f = 0; f < F; ++f)
+    start[f + 1] = start[f] + std::max(1, (3 * h->keep_natoms[f] + ta::kMdCorrChunk - 1) / ta::kMdCorrChunk);
+  const size_t n_chunks = (size_t)start[F], n_acc = 2 * F * E * L;
+  if (!md_alloc_exact(h->md_ring_x, L * 3 * N) || !md_alloc_exact(h->md_ring_v, L * 3 * N) ||
+      !md_alloc_exact(h->md_corr_acc, n_acc) || !md_alloc_exact(h->md_corr_part, n_chunks * 2 * E * L) ||
+      !md_alloc_exact(h->md_corr_blk, F + 1)) {
+    md_sampling_release(h);
+    return false;
+  }
+  HIP_CHECK(hipMemset(h->md_corr_acc.ptr, 0, std::max<size_t>(n_acc, 1) * sizeof(double)));
+  HIP_CHECK(hipMemcpy(h->md_corr_blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+  h->md_corr_chunks = (int)n_chunks;
+  const int64_t s = p.sample_every;
+  h->md_samp_origin = (h->md_step + s - 1) / s * s;
+  h->md_samp_last = -1;
+  h->md_samp_valid = true;
+  return true;
+}
+
 // The loop that ta_md_run and ta_relax_run share. `enqueue(q)` puts the launches of step q on the stream
 // (they are predicated on the status word and test the skin / 2 rule after their drift); this loop follows
 // each with the exact list of the step and an evaluation, looks at the page-locked status word every
@@ -2000,7 +2063,8 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
   if (velocities)
     for (size_t i = 0; i < 3 * N; ++i)
       if (!std::isfinite(velocities[i])) return fail(h, TA_ERR_INVALID, "ta_md_init: non-finite velocity");
-  return guarded(h, [&]() {
+  bool ring_nomem = false;
+  const int rc = guarded(h, [&]() {
     h->md_valid = false;
     HIP_CHECK(hipStreamSynchronize(h->stream));
     h->upload_pending = false;
@@ -2027,8 +2091,15 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
     h->md_blk_start_host.clear();
     h->md_step = 0;
     h->md_rec_valid = false;
+    if (h->md_samp_on && !md_sampling_alloc(h, h->md_samp_p)) {  // an empty ring for this batch, or none
+      h->md_samp_on = false;
+      ring_nomem = true;
+    }
     h->md_valid = true;
   });
+  if (rc == TA_OK && ring_nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the rings of ta_md_set_sampling; sampling is off");
+  return rc;
 }
 
 int ta_md_set_thermostat(ta_handle h, double kT0, double tau) {
@@ -2163,6 +2234,94 @@ int ta_md_get_chain_records(ta_handle h, double *e_chain) {
   return TA_OK;
 }
 
+int ta_md_set_sampling(ta_handle h, const ta_md_sampling_params *p) {
+  if (!h) return TA_ERR_INVALID;
+  if (!p || p->n_lags == 0) {
+    h->md_samp_on = false;
+    return guarded(h, [&]() {
+      HIP_CHECK(hipStreamSynchronize(h->stream));
+      md_sampling_release(h);
+    });
+  }
+  if (p->n_lags < 0 || p->n_lags > TA_MD_MAX_LAGS)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_sampling: n_lags must be 0 .. " + std::to_string(TA_MD_MAX_LAGS));
+  if (p->sample_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_set_sampling: sample_every must be >= 1");
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_sampling: no resident batch");
+  if (!h->md_valid) return fail(h, TA_ERR_INVALID, "ta_md_set_sampling called before ta_md_init");
+  bool nomem = false;
+  const int rc = guarded(h, [&]() {
+    h->md_samp_on = false;  // (until the rings exist)
+    nomem = !md_sampling_alloc(h, *p);
+    if (!nomem) {
+      h->md_samp_p = *p;
+      h->md_samp_on = true;
+    }
+  });
+  if (rc == TA_OK && nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_set_sampling: no device memory for rings of n_lags = " + std::to_string(p->n_lags) +
+                                 " snapshots; sampling is off");
+  return rc;
+}
+
+namespace {
+// what the two getters of the sampled data need; returns 0 or the error code
+int md_samples_ready(ta_context *h, const char *who) {
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
+  if (!h->md_valid) return fail(h, TA_ERR_INVALID, std::string(who) + " called before ta_md_init");
+  if (!h->md_samp_on) return fail(h, TA_ERR_INVALID, std::string(who) + ": sampling is off (ta_md_set_sampling)");
+  if (!h->md_samp_valid)
+    return fail(h, TA_ERR_INVALID, std::string(who) + ": a ta_md_run failed and left the sampled data invalid; call "
+                                   "ta_md_set_sampling or ta_md_init again");
+  return TA_OK;
+}
+
+int64_t md_samples_taken(const ta_context *h) {
+  return h->md_samp_last < 0 ? 0 : (h->md_samp_last - h->md_samp_origin) / h->md_samp_p.sample_every + 1;
+}
+}  // namespace
+
+int ta_md_get_correlations(ta_handle h, double *vacf_sum, double *msd_sum, int64_t *info) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int rc = md_samples_ready(h, "ta_md_get_correlations")) return rc;
+  return guarded(h, [&]() {
+    const size_t n = h->keep_natoms.size() * (size_t)h->n_elements * (size_t)h->md_samp_p.n_lags;
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (vacf_sum && n) HIP_CHECK(hipMemcpy(vacf_sum, h->md_corr_acc.ptr, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (msd_sum && n) HIP_CHECK(hipMemcpy(msd_sum, h->md_corr_acc.ptr + n, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (info) {
+      info[0] = md_samples_taken(h);
+      info[1] = h->md_samp_p.n_lags;
+      info[2] = h->md_samp_p.sample_every;
+      info[3] = h->md_samp_last;
+    }
+  });
+}
+
+int ta_md_get_samples(ta_handle h, int32_t first_lag, int32_t n, double *positions, double *velocities,
+                      int64_t *steps) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int rc = md_samples_ready(h, "ta_md_get_samples")) return rc;
+  const int64_t taken = md_samples_taken(h), L = h->md_samp_p.n_lags, held = std::min(taken, L);
+  if (first_lag < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_samples: first_lag must be >= 0");
+  if (n < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_samples: n must be >= 0");
+  if ((int64_t)first_lag + n > held)
+    return fail(h, TA_ERR_INVALID, "ta_md_get_samples: first_lag + n = " + std::to_string((int64_t)first_lag + n) +
+                                   " exceeds the " + std::to_string(held) + " snapshots held (min(n_samples, n_lags))");
+  return guarded(h, [&]() {
+    const size_t row = 3 * h->keep_species.size();
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    for (int32_t j = 0; j < n; ++j) {
+      const int64_t idx = taken - 1 - first_lag - j;  // sample number
+      const size_t slot = (size_t)(idx % L);
+      if (positions && row)
+        HIP_CHECK(hipMemcpy(positions + (size_t)j * row, h->md_ring_x.ptr + slot * row, row * sizeof(double), hipMemcpyDeviceToHost));
+      if (velocities && row)
+        HIP_CHECK(hipMemcpy(velocities + (size_t)j * row, h->md_ring_v.ptr + slot * row, row * sizeof(double), hipMemcpyDeviceToHost));
+      if (steps) steps[j] = h->md_samp_origin + idx * h->md_samp_p.sample_every;
+    }
+  });
+}
+
 int ta_md_noise(ta_handle h, int64_t step, double *xi, double *eta) {
   if (!h) return TA_ERR_INVALID;
   if (!xi || !eta) return fail(h, TA_ERR_INVALID, "ta_md_noise: null argument");
@@ -2251,12 +2410,18 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
         return fail(h, TA_ERR_INVALID, "ta_md_run: the Nose-Hoover chain is on and frame " + std::to_string(f) +
                                        " has fewer than one degree of freedom (3 n_atoms - dof_removed)");
   }
+  const bool samp = h->md_samp_on;
+  if (samp && baro)
+    return fail(h, TA_ERR_INVALID, "ta_md_run: sampling (ta_md_set_sampling) and the barostat (ta_md_set_barostat) are both "
+                                   "on; displacements in a moving cell are not defined: switch one of them off");
   if (n_rebuilds) *n_rebuilds = 0;
   want |= TA_WANT_ENERGY | TA_WANT_FORCES;
   want &= ~(uint32_t)TA_WANT_REUSE_DESCRIPTORS;
   if (baro) want |= TA_WANT_VIRIAL;  // the pressure
   h->md_rec_valid = false;
   h->md_nhc_rec_valid = false;
+  const bool samp_was_valid = h->md_samp_valid;
+  h->md_samp_valid = false;  // (until this run has succeeded)
   h->cell_running = h->md_baro_running = baro;
   const int rc = guarded(h, [&]() {
     const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
@@ -2333,6 +2498,22 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     a.nhc_kT0 = nhc ? h->md_nhc_p.kT0 : 0.0;
     a.nhc_q = nhc ? h->md_nhc_p.kT0 * h->md_nhc_p.tau * h->md_nhc_p.tau : 0.0;
     a.nhc_eta = h->md_nhc_eta.ptr, a.nhc_veta = h->md_nhc_veta.ptr, a.nhc_rec = h->md_nhc_rec.ptr;
+    // Sampling: the launch of step k holds the whole-step state t = step0 + k. It samples when t is a multiple
+    // of sample_every at or behind sample 0, except launch 0 where the last launch of the run before sampled
+    // that very state. Sample number and ring slot are functions of t alone, so the launches that returned
+    // early behind a stale list and are enqueued again after the rebuild write what they would have written.
+    const bool sampling = samp && samp_was_valid && N > 0;
+    const int64_t samp_s = h->md_samp_p.sample_every, samp_L = h->md_samp_p.n_lags;
+    const int64_t samp_origin = h->md_samp_origin, samp_last = h->md_samp_last;
+    ta::MdCorrLaunch c;
+    c.ring_x = h->md_ring_x.ptr, c.ring_v = h->md_ring_v.ptr;
+    c.blk_start = h->md_corr_blk.ptr;
+    c.part = h->md_corr_part.ptr;
+    c.acc_v = h->md_corr_acc.ptr;
+    c.acc_x = sampling ? h->md_corr_acc.ptr + F * (size_t)h->n_elements * (size_t)samp_L : nullptr;
+    c.status = h->md_status.ptr;
+    c.n_atoms = (long long)N;
+    c.n_lags = (int)samp_L, c.n_elements = h->n_elements, c.n_frames = (int)F, c.n_chunks = h->md_corr_chunks;
     auto integrate = [&](int k, bool drift) {
       // (a rebuild may have moved the batch's arrays: the pointers are taken at every launch)
       a.pos = h->db.pos;
@@ -2346,8 +2527,24 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
       a.kick2 = k > 0 ? 1 : 0;  // the state at entry is a whole step
       a.drift = drift ? 1 : 0;
       a.rec = (k % record_every == 0) ? (long long)(k / record_every) : -1;
+      a.snap_x = a.snap_v = nullptr;
+      const int64_t t = step0 + k;
+      const bool due = sampling && t >= samp_origin && (t - samp_origin) % samp_s == 0 && !(k == 0 && t == samp_last);
+      if (due) {
+        c.n = (long long)((t - samp_origin) / samp_s);
+        const size_t slot = (size_t)(c.n % samp_L);
+        a.snap_x = h->md_ring_x.ptr + slot * 3 * N;
+        a.snap_v = h->md_ring_v.ptr + slot * 3 * N;
+      }
       ta::launch_md_integrate(a, threads, s);
       HIP_CHECK(hipGetLastError());
+      if (due) {  // directly behind the launch that sampled, under the same predicate
+        c.species = h->db.species;
+        c.atom_start = h->db.atom_start;
+        c.seq = (unsigned)k;
+        ta::launch_md_correlate(c, s);
+        HIP_CHECK(hipGetLastError());
+      }
     };
 
     h->jvp_valid = false;
@@ -2359,6 +2556,9 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     HIP_CHECK(hipStreamSynchronize(s));
     h->upload_pending = false;
     h->md_step = step0 + n_steps;
+    if (sampling && h->md_step >= samp_origin)  // the newest sample: the last multiple of sample_every reached
+      h->md_samp_last = std::max(samp_last, samp_origin + (h->md_step - samp_origin) / samp_s * samp_s);
+    h->md_samp_valid = samp_was_valid;
     if (n_rebuilds) *n_rebuilds = rebuilds;
     if (baro && F) {
       std::vector<double> rec(4 * n_rec * F);

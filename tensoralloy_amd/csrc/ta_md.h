@@ -57,9 +57,34 @@ struct MdLaunch {
   double nhc_kT0, nhc_q;
   double *nhc_eta, *nhc_veta;  // [F][kMdMaxChain]
   double *nhc_rec;             // [n_rec][F]
+  // Sampling (ta_md_set_sampling): this sample's rows [N][3] of the position and the velocity ring, both null
+  // in a launch that does not sample (the launcher picks the kSnap build from them). x(t) is stored before the
+  // drift, v(t) as the record's kinetic energy sees it.
+  double *snap_x, *snap_v;
+};
+
+constexpr int kMdCorrChunk = 768;   // ring doubles (256 atoms x 3) per workgroup of the correlation launch
+constexpr int kMdCorrLagTile = 8;   // lags per workgroup of the correlation launch
+
+// Arguments of the correlation launch (ta_md_corr.hip) that ta_md_run puts behind an integrator launch that
+// sampled: sample n (in ring slot n % n_lags) against the rows of the lags 0 .. min(n, n_lags - 1).
+struct MdCorrLaunch {
+  const double *ring_x, *ring_v;  // [n_lags][N][3]
+  const int32_t *species;         // [N]
+  const int32_t *atom_start;      // [F + 1]
+  const int32_t *blk_start;       // [F + 1] first chunk of kMdCorrChunk ring doubles of each frame (at least one each)
+  double *part;                   // [n_chunks][2][E][n_lags] per-workgroup sums: v . v, then |dx|^2
+  double *acc_v, *acc_x;          // [F][E][n_lags] the accumulators
+  const unsigned *status;         // the integrator's status word and
+  unsigned seq;                   // sequence number: the same predicate
+  long long n;                    // index of the newest sample
+  long long n_atoms;              // N
+  int n_lags, n_elements, n_frames, n_chunks;
 };
 
 void launch_md_integrate(const MdLaunch &a, int threads, hipStream_t s);
+
+void launch_md_correlate(const MdCorrLaunch &a, hipStream_t s);
 
 // xi, eta [n][3] (device): the normals md_integrate draws for absolute step `step`, atoms 0 .. n - 1
 void launch_md_noise(unsigned long long seed, long long step, long long n, double *xi, double *eta, hipStream_t s);

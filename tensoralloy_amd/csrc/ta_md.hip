@@ -56,6 +56,12 @@
 // writes them back to [F][kMdMaxChain] arrays; the factors reach the other threads through LDS. All of it
 // sits behind the early return on the status word: a launch enqueued behind a stale list leaves the chain alone.
 //
+// Sampling (ta_md_set_sampling): a launch whose step is due gets the rows of this sample in the position and the
+// velocity ring (snap_x, snap_v; null otherwise) and runs the kSnap build of its variant. It stores x_k as it finds it,
+// before its drift, and v_k as the record's kinetic energy sees it: after the pending half-kick (Langevin: the
+// second update) in the first loop, under the chain s1 v behind the reduction, on the drift and on the no-drift
+// path. The stores sit behind the early return; a launch that does not sample runs the build without them.
+//
 // The launch is predicated on a device word: a drift that finds an atom beyond skin / 2 writes its own
 // sequence number + 1 there (and into a page-locked word the host reads after a stream wait), still
 // writes valid positions, and every LATER launch returns at once. The host may therefore enqueue several
@@ -162,7 +168,8 @@ __device__ __forceinline__ double md_nhc_half(double *eta, double *veta, int M, 
 // kLangevin = false: velocity Verlet with the optional Berendsen factor; true: the Langevin step.
 // kBaro: the Berendsen barostat before the step (one workgroup per frame)
 // kNhc: the Nose-Hoover chain around the velocity Verlet step (one workgroup per frame; never with kLangevin)
-template <bool kLangevin, bool kBaro, bool kNhc = false>
+// kSnap: this launch samples (snap_x, snap_v are rows of the rings); without it the build is the one it was
+template <bool kLangevin, bool kBaro, bool kNhc = false, bool kSnap = false>
 __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
   __shared__ double s_wave[16];
   __shared__ double s_total;
@@ -213,6 +220,10 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
       a.vel[3 * i] = vx;
       a.vel[3 * i + 1] = vy;
       a.vel[3 * i + 2] = vz;
+    }
+    if constexpr (kSnap) {  // the whole-step state of this launch's step; the chain's v waits for s1
+      a.snap_x[3 * i] = a.pos[3 * i], a.snap_x[3 * i + 1] = a.pos[3 * i + 1], a.snap_x[3 * i + 2] = a.pos[3 * i + 2];
+      if constexpr (!kNhc) a.snap_v[3 * i] = vx, a.snap_v[3 * i + 1] = vy, a.snap_v[3 * i + 2] = vz;
     }
     if constexpr (kBaro) {
       sx += m * vx * vx;
@@ -269,7 +280,11 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
     if (!a.drift) {  // the run ends on a whole step: the closing factor goes into the velocities now
       for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) a.vel[3 * i + c] = s1 * a.vel[3 * i + c];
+        for (int c = 0; c < 3; ++c) {
+          const double v = s1 * a.vel[3 * i + c];
+          a.vel[3 * i + c] = v;
+          if constexpr (kSnap) a.snap_v[3 * i + c] = v;
+        }
       }
       return;
     }
@@ -338,6 +353,7 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
     } else {
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
+        if constexpr (kNhc && kSnap) a.snap_v[3 * i + c] = s1 * a.vel[3 * i + c];  // (after the closing half-update)
         double v = lambda * a.vel[3 * i + c];
         v += hdt * a.forces[3 * i + c] / m;
         a.vel[3 * i + c] = v;
@@ -374,6 +390,15 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
   }
 }
 
+// the build of a launch that samples, or the one without a snapshot store in it
+template <bool kLangevin, bool kBaro, bool kNhc>
+void md_launch_build(const MdLaunch &a, dim3 grid, dim3 block, hipStream_t s) {
+  if (a.snap_x)
+    hipLaunchKernelGGL((md_integrate_kernel<kLangevin, kBaro, kNhc, true>), grid, block, 0, s, a);
+  else
+    hipLaunchKernelGGL((md_integrate_kernel<kLangevin, kBaro, kNhc, false>), grid, block, 0, s, a);
+}
+
 }  // namespace
 
 void launch_md_integrate(const MdLaunch &a, int threads, hipStream_t s) {
@@ -381,22 +406,22 @@ void launch_md_integrate(const MdLaunch &a, int threads, hipStream_t s) {
   const dim3 grid((unsigned)a.n_blk), block((unsigned)threads);
   if (a.nhc) {  // (ta_md_run made every workgroup a whole frame; ta_md_set_nose_hoover excludes Langevin)
     if (a.baro)
-      hipLaunchKernelGGL((md_integrate_kernel<false, true, true>), grid, block, 0, s, a);
+      md_launch_build<false, true, true>(a, grid, block, s);
     else
-      hipLaunchKernelGGL((md_integrate_kernel<false, false, true>), grid, block, 0, s, a);
+      md_launch_build<false, false, true>(a, grid, block, s);
     return;
   }
   if (a.baro) {  // (ta_md_run made every workgroup a whole frame)
     if (a.langevin)
-      hipLaunchKernelGGL((md_integrate_kernel<true, true>), grid, block, 0, s, a);
+      md_launch_build<true, true, false>(a, grid, block, s);
     else
-      hipLaunchKernelGGL((md_integrate_kernel<false, true>), grid, block, 0, s, a);
+      md_launch_build<false, true, false>(a, grid, block, s);
     return;
   }
   if (a.langevin)
-    hipLaunchKernelGGL((md_integrate_kernel<true, false>), grid, block, 0, s, a);
+    md_launch_build<true, false, false>(a, grid, block, s);
   else
-    hipLaunchKernelGGL((md_integrate_kernel<false, false>), grid, block, 0, s, a);
+    md_launch_build<false, false, false>(a, grid, block, s);
 }
 
 void launch_md_noise(unsigned long long seed, long long step, long long n, double *xi, double *eta, hipStream_t s) {

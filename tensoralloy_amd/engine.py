@@ -37,6 +37,8 @@ class Engine:
         self._relax_cell = False   # `relax_set_cell` is on: `relax_run` moves the cells
         self._md_barostat = False  # `md_set_barostat` is on: `md_run` moves the cells
         self._md_chain = 0         # `md_set_nose_hoover` is on: thermostats per chain
+        self._md_lags = 0          # `md_set_sampling` is on: snapshots in the ring
+        self._n_elements = int(desc.n_elements)
         self._md_sig = None   # (n, numbers, pbc) of the single resident frame of `evaluate_md`
         self._md_cell = None
         self.batch_generation = 0  # bumped whenever the resident batch or its coordinates change
@@ -280,6 +282,72 @@ class Engine:
         if not 0 <= seed < 2 ** 64:
             raise ValueError("md_set_langevin: the seed must fit an unsigned 64-bit integer")
         self._check(self._lib.ta_md_set_langevin(self._handle, float(kT), float(friction), seed))
+
+    def md_set_sampling(self, n_lags=0, sample_every=1):
+        """Time correlations inside `md_run` (`ta_md_set_sampling`): with `n_lags` = L (1 .. 4096) the loop keeps
+        the last L sampled whole-step states (x, v) in a ring on the device, samples every step t (counted since
+        `md_init`) with t % `sample_every` == 0, and at every sample adds the velocity autocorrelation and the
+        mean-square displacement at all L lags, per frame and per element, onto accumulators that stay on the
+        device (`md_correlations`, `md_samples`). `n_lags` = 0 switches it off (the default) and frees the ring.
+        Needs `md_init`; every call starts an empty ring and zero accumulators, as `md_init` does. The setting
+        stays on across `set_frames`. No centre-of-mass correction is made. `md_run` refuses to sample under the
+        barostat. The ring takes 2 x L x n_atoms x 24 bytes of device memory."""
+        p = _lib.MdSamplingParams(int(n_lags), int(sample_every))
+        rc = self._lib.ta_md_set_sampling(self._handle, C.byref(p))
+        if rc == _lib.TA_ERR_NOMEM:   # (no room for the rings: the library switched sampling off)
+            self._md_lags = 0
+        self._check(rc)
+        self._md_lags = int(n_lags)
+
+    def _md_corr_shape(self, who):
+        if self.info is None:
+            raise ValueError(f"{who}: no resident batch (call set_frames first)")
+        return int(self.info.n_frames), self._n_elements, max(self._md_lags, 1)
+
+    def md_correlations(self):
+        """What the loop has accumulated since sampling was switched on (`ta_md_get_correlations`), a dict:
+        `vacf_sum`, `msd_sum` [n_frames, n_elements, n_lags]: sums over time origins and over the atoms of a frame
+        with that species of v(n) . v(n - k) and |x(n) - x(n - k)|^2 (positions unwrapped, no centre-of-mass
+        correction: under Langevin the diffusion of the centre of mass is included);
+        `n_origins` [n_lags] = max(0, n_samples - k); `counts` [n_frames, n_elements] atoms per frame and element;
+        `vacf`, `msd`: the sums over n_origins x counts, NaN where that is 0;
+        `n_samples`, `sample_every`, `last_step` (absolute step of the newest sample, -1: none)."""
+        F, E, L = self._md_corr_shape("md_correlations")
+        vs, xs = np.zeros((F, E, L)), np.zeros((F, E, L))
+        info = (C.c_int64 * 4)()
+        self._check(self._lib.ta_md_get_correlations(self._handle, _lib.as_dp(vs), _lib.as_dp(xs), info))
+        n_samples = int(info[0])
+        n_origins = np.maximum(0, n_samples - np.arange(L)).astype(np.int64)
+        counts = np.zeros((F, E), dtype=np.int64)
+        for f, fr in enumerate(self._frames):
+            counts[f] = np.bincount(fr.species, minlength=E)[:E]
+        den = (counts[:, :, None] * n_origins[None, None, :]).astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            vacf = np.where(den > 0, vs / den, np.nan)
+            msd = np.where(den > 0, xs / den, np.nan)
+        return {"vacf": vacf, "msd": msd, "vacf_sum": vs, "msd_sum": xs, "n_origins": n_origins, "counts": counts,
+                "n_samples": n_samples, "sample_every": int(info[2]), "last_step": int(info[3])}
+
+    def md_samples(self, n=None):
+        """The last `n` sampled states, oldest first (`ta_md_get_samples`; default: all the ring holds,
+        min(n_samples, n_lags)): a dict `x`, `v` [n, n_atoms, 3] and `steps` [n] (absolute steps). The first way
+        to trajectory frames that does not cut a run."""
+        F, E, L = self._md_corr_shape("md_samples")
+        null = C.POINTER(C.c_double)()
+        if n is None:
+            info = (C.c_int64 * 4)()
+            self._check(self._lib.ta_md_get_samples(self._handle, 0, 0, null, null, None))   # (its own refusals)
+            self._check(self._lib.ta_md_get_correlations(self._handle, null, null, info))
+            n = min(int(info[0]), int(info[1]))
+        n = int(n)
+        if n < 0:
+            raise ValueError("md_samples: n must be >= 0")
+        N = int(self.info.n_atoms)
+        x, v = np.empty((max(n, 1), N, 3)), np.empty((max(n, 1), N, 3))
+        steps = np.zeros(max(n, 1), dtype=np.int64)
+        self._check(self._lib.ta_md_get_samples(self._handle, 0, n, _lib.as_dp(x), _lib.as_dp(v),
+                                                steps.ctypes.data_as(C.POINTER(C.c_int64))))
+        return {"x": x[:n][::-1].copy(), "v": v[:n][::-1].copy(), "steps": steps[:n][::-1].copy()}
 
     def md_noise(self, step: int):
         """(xi, eta) [n_atoms, 3]: the standard normals the Langevin step with absolute index `step` (steps

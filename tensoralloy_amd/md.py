@@ -33,6 +33,16 @@ Constant pressure: with `pressure`, `taup` and `compressibility` the cells follo
 settings. The scaling factor is computed inside the integrator launch from the forces of the unscaled
 positions, one force evaluation per step (what ASE does when forces are handed to its `step`). `GPa` and `bar`
 are the same numbers as `ase.units.GPa` and `ase.units.bar`.
+
+Time correlations: with `n_lags` (and `sample_every`) the loop itself keeps the last `n_lags` sampled
+whole-step states in a ring on the device and, at every sample, adds the velocity autocorrelation
+<v(t0 + k) . v(t0)> and the mean-square displacement <|x(t0 + k) - x(t0)|^2> at all lags k, per frame and per
+element, over every time origin t0 it has seen (`Engine.md_set_sampling`; `DeviceMD.get_vacf`, `get_msd`,
+`get_samples`). The run is not cut and no per-atom data cross the bus. Positions are the unwrapped ones the
+integrator holds, and no centre-of-mass correction is made: velocities without net momentum keep the centre of
+mass at rest under NVE and the Nose-Hoover chain; under Langevin its diffusion is part of the result. Sampling
+under the barostat is refused. `vdos` turns a VACF into a vibrational density of states, `diffusion_coefficient`
+fits the slope of an MSD (Einstein) and `green_kubo_diffusion` integrates a VACF (Green-Kubo).
 """
 from __future__ import annotations
 
@@ -43,7 +53,8 @@ kB = 8.617330337217213e-05    # eV / K
 GPa = 1.0 / 160.21766208      # eV / Angstrom^3
 bar = 1.0e-4 * GPa
 
-__all__ = ["fs", "kB", "GPa", "bar", "maxwell_boltzmann", "DeviceMD"]
+__all__ = ["fs", "kB", "GPa", "bar", "maxwell_boltzmann", "DeviceMD", "vdos", "diffusion_coefficient",
+           "green_kubo_diffusion"]
 
 
 def maxwell_boltzmann(masses, kT, rng, zero_momentum=True):
@@ -59,6 +70,80 @@ def maxwell_boltzmann(masses, kT, rng, zero_momentum=True):
     if zero_momentum and len(m):
         v -= (m[:, None] * v).sum(axis=0) / m.sum()
     return v
+
+
+def _trapezoid(y, dx):
+    y = np.asarray(y, dtype=np.float64)
+    return dx * (y.sum(axis=-1) - 0.5 * (y[..., 0] + y[..., -1]))
+
+
+def vdos(vacf, dt_sample, window="hann"):
+    """Vibrational density of states from a velocity autocorrelation `vacf` [..., L] (L >= 2) sampled every
+    `dt_sample` (ASE time units): returns (nu, g) with nu [L] in THz, nu_j = j / (2 (L - 1) dt_sample), up to the
+    Nyquist frequency, and g [..., L] the one-sided cosine transform of c_k = vacf_k / vacf_0,
+        g(nu_j) ~ w_0 c_0 / 2 + sum_{k=1}^{L-2} w_k c_k cos(pi j k / (L - 1)) + w_{L-1} c_{L-1} cos(pi j) / 2
+    (the trapezoid rule in time). `window`: "hann", w_k = (1 + cos(pi k / (L - 1))) / 2, which takes the
+    truncated tail to zero, or None, w_k = 1. g is scaled so that its integral over nu by the trapezoid rule on
+    this grid is 1 (per THz)."""
+    c = np.asarray(vacf, dtype=np.float64)
+    L = c.shape[-1] if c.ndim else 0
+    if L < 2:
+        raise ValueError("vdos: a vacf with at least two lags along the last axis is needed")
+    if not (np.isfinite(dt_sample) and dt_sample > 0.0):
+        raise ValueError("vdos: dt_sample must be a finite time > 0")
+    k = np.arange(L)
+    if window == "hann":
+        w = 0.5 * (1.0 + np.cos(np.pi * k / (L - 1)))
+    elif window is None:
+        w = np.ones(L)
+    else:
+        raise ValueError("vdos: window must be 'hann' or None")
+    w[0] *= 0.5
+    w[-1] *= 0.5
+    with np.errstate(divide="ignore", invalid="ignore"):
+        c = c / c[..., :1]
+    g = (c * w) @ np.cos(np.pi * np.outer(k, k) / (L - 1))
+    nu = k / (2.0 * (L - 1) * (dt_sample / fs) * 1.0e-3)   # 1 / ps
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g = g / _trapezoid(g, nu[1] - nu[0])[..., None]
+    return nu, g
+
+
+def diffusion_coefficient(msd, dt_sample, fit=None):
+    """Einstein relation: the least-squares slope (with a free intercept) of `msd` [..., L] against the lag times
+    k dt_sample over the lags `fit` = (lo, hi), i.e. lo .. hi - 1, divided by 6: D in A^2 per ASE time unit
+    (multiply by `fs` for A^2 / fs). 0 <= lo < hi <= L is required, and two lags at least, since a slope needs
+    two points; default: the upper half of the lags, (L // 2, L)."""
+    y = np.asarray(msd, dtype=np.float64)
+    L = y.shape[-1] if y.ndim else 0
+    if not (np.isfinite(dt_sample) and dt_sample > 0.0):
+        raise ValueError("diffusion_coefficient: dt_sample must be a finite time > 0")
+    if fit is None:
+        fit = (L // 2, L)
+    if np.shape(fit) != (2,) or int(fit[0]) != fit[0] or int(fit[1]) != fit[1]:
+        raise ValueError("diffusion_coefficient: fit must be two integers (lo, hi)")
+    lo, hi = int(fit[0]), int(fit[1])
+    if not (0 <= lo < hi <= L):
+        raise ValueError(f"diffusion_coefficient: fit = (lo, hi) needs 0 <= lo < hi <= {L} lags")
+    if hi - lo < 2:
+        raise ValueError("diffusion_coefficient: fit must span at least two lags")
+    t = np.arange(lo, hi) * float(dt_sample)
+    tc = t - t.mean()
+    yy = y[..., lo:hi]
+    slope = ((yy - yy.mean(axis=-1, keepdims=True)) * tc).sum(axis=-1) / (tc * tc).sum()
+    return slope / 6.0
+
+
+def green_kubo_diffusion(vacf, dt_sample):
+    """Green-Kubo relation: the integral of `vacf` [..., L] over the lag times by the trapezoid rule, divided by
+    3: D in A^2 per ASE time unit. The integral is cut at the last lag; choose n_lags so that the vacf has
+    decayed there."""
+    c = np.asarray(vacf, dtype=np.float64)
+    if c.ndim == 0 or c.shape[-1] < 1:
+        raise ValueError("green_kubo_diffusion: a vacf with lags along the last axis is needed")
+    if not (np.isfinite(dt_sample) and dt_sample > 0.0):
+        raise ValueError("green_kubo_diffusion: dt_sample must be a finite time > 0")
+    return _trapezoid(c, float(dt_sample)) / 3.0
 
 
 class DeviceMD:
@@ -84,6 +169,10 @@ class DeviceMD:
                            `1.0 * GPa`), time constant (> 0) and compressibility (A^3 / eV, >= 0), with any
                            thermostat setting; every frame must be periodic along all three axes
     mask                 : None = isotropic; three flags (x, y, z) = each free axis follows its own pressure
+    n_lags, sample_every : `n_lags` given (1 .. 4096): the loop samples every `sample_every`-th step (the state at
+                           construction is the first sample) and accumulates the velocity autocorrelation and
+                           the mean-square displacement at `n_lags` lags on the device (`get_vacf`, `get_msd`,
+                           `get_samples`); excludes the barostat. The ring takes 2 x n_lags x n_atoms x 24 bytes
 
     Under the barostat the cell of every `Atoms` follows (the atoms are not scaled again), and every `run` call
     that moved the cells ends with one neighbour-list build for the final cells: an observer at interval 1
@@ -93,11 +182,23 @@ class DeviceMD:
 
     def __init__(self, engine_or_calculator, atoms_or_list, timestep, temperature_K=None, taut=None,
                  velocities=None, masses=None, friction=None, seed=0, pressure=None, taup=None,
-                 compressibility=None, mask=None, tdamp=None, tchain=3, tloop=1, dof_removed=0):
+                 compressibility=None, mask=None, tdamp=None, tchain=3, tloop=1, dof_removed=0, n_lags=None,
+                 sample_every=1):
         if not (np.isfinite(timestep) and timestep > 0.0):
             raise ValueError("DeviceMD: timestep must be a finite time > 0")
         barostat = (pressure, taup, compressibility)
         self._barostat = any(p is not None for p in barostat)
+        if n_lags is not None:
+            whole = lambda a: isinstance(a, (int, np.integer)) and not isinstance(a, bool)
+            if not (whole(n_lags) and 1 <= n_lags <= 4096):
+                raise ValueError("DeviceMD: n_lags must be an integer 1 .. 4096")
+            if not (whole(sample_every) and sample_every >= 1):
+                raise ValueError("DeviceMD: sample_every must be an integer >= 1")
+            if self._barostat:
+                raise ValueError("DeviceMD: n_lags (sampling) excludes the barostat (pressure, taup, compressibility): "
+                                 "displacements in a moving cell are not defined")
+        elif sample_every != 1:
+            raise ValueError("DeviceMD: sample_every belongs to sampling (n_lags)")
         if self._barostat:
             if any(p is None for p in barostat):
                 raise ValueError("DeviceMD: the barostat needs pressure, taup and compressibility")
@@ -191,6 +292,9 @@ class DeviceMD:
             engine.md_set_barostat(pressure, taup, compressibility, mask)
         else:
             engine.md_set_barostat(0.0, 0.0, 0.0)
+        self._lags = int(n_lags) if n_lags is not None else 0
+        self._sample_every = int(sample_every)
+        engine.md_set_sampling(self._lags, self._sample_every)   # (state 0 is the first sample)
         self._natoms = np.array([len(a) for a in self.atoms_list], dtype=np.int64)
         self.velocities = velocities.copy()
         self.epot = self.ekin = None   # per-frame records of the last state
@@ -257,6 +361,32 @@ class DeviceMD:
             raise ValueError("DeviceMD.get_conserved_energy: the Nose-Hoover chain thermostat is off (temperature_K, tdamp)")
         e = self.ekin + self.epot + self.echain
         return float(e[0]) if self._single else e
+
+    def _correlation(self, who, key):
+        if not self._lags:
+            raise ValueError(f"DeviceMD.{who}: sampling is off (n_lags)")
+        c = self.engine.md_correlations()[key]
+        t = np.arange(self._lags) * self._sample_every * self.dt
+        return t, (c[0] if self._single else c)
+
+    def get_vacf(self):
+        """(t, vacf): the lag times arange(n_lags) * sample_every * timestep and the velocity autocorrelation
+        <v(t0 + t) . v(t0)> per atom [n_elements, n_lags] (a batch: [n_frames, n_elements, n_lags]), averaged over
+        the atoms of an element and over every time origin sampled so far; NaN where there is none yet or the
+        frame has no atom of the element. No centre-of-mass correction. Needs `n_lags`."""
+        return self._correlation("get_vacf", "vacf")
+
+    def get_msd(self):
+        """(t, msd): as `get_vacf` for the mean-square displacement <|x(t0 + t) - x(t0)|^2> of the unwrapped
+        positions. Needs `n_lags`."""
+        return self._correlation("get_msd", "msd")
+
+    def get_samples(self, n=None):
+        """The last `n` sampled states the device holds (default: all, at most `n_lags`), oldest first: a dict
+        `x`, `v` [n, n_atoms, 3] and `steps` [n] (steps since construction). Needs `n_lags`."""
+        if not self._lags:
+            raise ValueError("DeviceMD.get_samples: sampling is off (n_lags)")
+        return self.engine.md_samples(n)
 
     def get_volume(self):
         """Cell volume per frame, in A^3."""
