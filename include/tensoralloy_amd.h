@@ -477,9 +477,49 @@ int ta_step_view(ta_handle h, const double *positions, const double *cells, uint
  *   ta_md_get_samples    the snapshots first_lag .. first_lag + n - 1 back from the newest one (0 = the newest):
  *                        positions / velocities [n][n_atoms_total][3] and their absolute steps [n]; any pointer
  *                        may be NULL. TA_ERR_INVALID when first_lag < 0, n < 0 or first_lag + n exceeds the
- *                        min(n_samples, n_lags) snapshots held. */
+ *                        min(n_samples, n_lags) snapshots held.
+ *
+ * Partial pair distributions inside the loop (opt-in; with it never switched on nothing changes). With n_bins = B,
+ * r_max and sample_every = s the whole-step state x(t) of every absolute step t with t % s == 0, from the first
+ * such step at or behind the call that switched the feature on, is sampled, once, however the run is cut into
+ * calls and whatever steps are redone after a list rebuild. A launch in front of the integrator launch of that
+ * step counts every directed pair (i, j, S) of the resident neighbour list, with the positions (unwrapped) and
+ * the cells as the device holds them:
+ *     C[f][a][b][k] += 1    a = species of the centre i, b = species of the neighbour j, f their frame,
+ *                           k = floor(r / dr),  dr = r_max / B,  r = |x_j - x_i + S . h| in fp64
+ * Pairs with k >= B are dropped; that compare alone decides (a pair exactly at r_max is dropped, there is no
+ * second test of r against r_max). A self-image (i == j, S != 0) counts like any other pair. The counts are
+ * unsigned 64-bit integers, summed with integer atomics: they are exact and do not depend on how a run is cut.
+ * Since every unordered pair is listed from both ends, C[f][a][b][k] == C[f][b][a][k].
+ *     g_ab(r_k) = C[a][b][k] V / (n_samples N_a N_b (4 pi / 3) ((k + 1)^3 - k^3) dr^3)
+ * for a frame periodic along all three axes, with N_a N_b (not N_a (N_b - delta_ab)) in the denominator.
+ * Sampling under the barostat is out of scope: normalising integer counts needs ONE volume.
+ *   ta_md_set_rdf        NULL or n_bins == 0 switches it off (the default; always allowed) and frees the
+ *                        accumulators. Switching on needs a resident batch and ta_md_init; it allocates the
+ *                        accumulators [n_frames][n_elements][n_elements][n_bins], zeroes them and the sample
+ *                        counter (so does every further call). A property of the handle with the life cycle of
+ *                        ta_md_set_sampling, and independent of it: ta_set_frames keeps the setting and drops the
+ *                        data with the MD state (the device memory of the old batch's counts is freed by the
+ *                        next ta_md_init, ta_md_set_rdf or ta_destroy); ta_md_init starts from zero counts.
+ *                        TA_ERR_INVALID, with the
+ *                        argument named by ta_last_error and the setting left as it was: n_bins outside
+ *                        0 .. TA_MD_MAX_BINS; sample_every < 1; r_max not finite, <= 0, or greater than
+ *                        max(rcut, acut) of the model (the neighbour list is not complete beyond that).
+ *                        TA_ERR_NOMEM when the device allocation fails; the feature is then off.
+ *   ta_md_run            TA_ERR_INVALID while this feature and the barostat are both on. A run that fails leaves
+ *                        the counts invalid: ta_md_get_rdf is TA_ERR_INVALID until ta_md_set_rdf or ta_md_init
+ *                        is called again.
+ *   ta_md_get_rdf        counts [n_frames][n_elements][n_elements][n_bins]; info [4] = {n_samples, n_bins,
+ *                        sample_every, absolute step of the newest sample or -1}; *r_max. Any pointer may be
+ *                        NULL. */
 #define TA_MD_MAX_CHAIN 8
 #define TA_MD_MAX_LAGS 4096
+#define TA_MD_MAX_BINS 4096
+typedef struct {
+  double r_max;          /* finite, > 0, <= max(rcut, acut) of the model */
+  int32_t n_bins;        /* B, 1 .. TA_MD_MAX_BINS; 0 switches the feature off (the default) */
+  int32_t sample_every;  /* s >= 1 */
+} ta_md_rdf_params;
 typedef struct {
   int32_t n_lags;        /* L, 1 .. TA_MD_MAX_LAGS; 0 switches sampling off (the default) */
   int32_t sample_every;  /* s >= 1 */
@@ -516,6 +556,8 @@ int ta_md_set_sampling(ta_handle h, const ta_md_sampling_params *p);
 int ta_md_get_correlations(ta_handle h, double *vacf_sum, double *msd_sum, int64_t *info);
 int ta_md_get_samples(ta_handle h, int32_t first_lag, int32_t n, double *positions, double *velocities,
                       int64_t *steps);
+int ta_md_set_rdf(ta_handle h, const ta_md_rdf_params *p);
+int ta_md_get_rdf(ta_handle h, int64_t *counts, int64_t *info, double *r_max);
 
 /* Device-resident structure relaxation: the resident batch is brought to a force minimum in ONE call, every
  * frame on its own, with positions, velocities and forces staying on the device. The optimiser is FIRE

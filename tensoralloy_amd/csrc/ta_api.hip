@@ -373,6 +373,16 @@ struct ta_context {
   int md_corr_chunks = 0;
   int64_t md_samp_origin = 0, md_samp_last = -1;
   bool md_samp_valid = false;
+  // Pair distributions (ta_md_set_rdf; off while md_rdf_on is false): the setting; the counts [F][E][E][n_bins],
+  // the launch's workgroup layout; the absolute step of sample 0 (a multiple of sample_every) and of the newest
+  // sample (-1: none); whether the counts are those of a run that succeeded
+  bool md_rdf_on = false;
+  ta_md_rdf_params md_rdf_p = {0.0, 0, 1};
+  DevBuf<unsigned long long> md_rdf_acc;
+  DevBuf<int32_t> md_rdf_blk;
+  int md_rdf_n_blk = 0, md_rdf_chunk = 0;
+  int64_t md_rdf_origin = 0, md_rdf_last = -1;
+  bool md_rdf_valid = false;
   // Langevin (ta_md_set_langevin; off while md_friction == 0): bath, friction, the key of the noise; the
   // steps integrated since ta_md_init (the noise's step counter) and the scratch of ta_md_noise
   double md_lv_kT0 = 0.0, md_friction = 0.0;
@@ -1261,6 +1271,8 @@ int ta_destroy(ta_handle h) {
                   &h->md_nhc_veta, &h->md_nhc_rec, &h->md_ring_x, &h->md_ring_v, &h->md_corr_acc, &h->md_corr_part})
     b->release();
   h->md_corr_blk.release();
+  h->md_rdf_acc.release();
+  h->md_rdf_blk.release();
   h->md_blk_start.release();
   h->md_status.release();
   h->md_status_host.release();
@@ -1964,6 +1976,41 @@ bool md_sampling_alloc(ta_context *h, const ta_md_sampling_params &p) {
   return true;
 }
 
+// frees what the pair distributions hold on the device; the setting stays
+void md_rdf_release(ta_context *h) {
+  h->md_rdf_acc.release();
+  h->md_rdf_blk.release();
+  h->md_rdf_n_blk = 0;
+  h->md_rdf_valid = false;
+  h->md_rdf_last = -1;
+}
+
+// Zeroed counts and the launch's workgroup layout for the resident batch under setting `p`, with no sample
+// taken: sample 0 will be the first multiple of sample_every at or behind the steps integrated so far. False
+// when the device has no room (everything is released then); throws otherwise.
+bool md_rdf_alloc(ta_context *h, const ta_md_rdf_params &p) {
+  const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
+  const size_t E = (size_t)h->n_elements, n_acc = F * E * E * (size_t)p.n_bins;
+  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches add to the old buffer)
+  md_rdf_release(h);
+  const int chunk = ta::md_rdf_chunk((long long)N);
+  std::vector<int32_t> start(F + 1, 0);
+  for (size_t f = 0; f < F; ++f) start[f + 1] = start[f] + std::max(1, (h->keep_natoms[f] + chunk - 1) / chunk);
+  if (!md_alloc_exact(h->md_rdf_acc, n_acc) || !md_alloc_exact(h->md_rdf_blk, F + 1)) {
+    md_rdf_release(h);
+    return false;
+  }
+  HIP_CHECK(hipMemset(h->md_rdf_acc.ptr, 0, std::max<size_t>(n_acc, 1) * sizeof(unsigned long long)));
+  HIP_CHECK(hipMemcpy(h->md_rdf_blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+  h->md_rdf_n_blk = (int)start[F];
+  h->md_rdf_chunk = chunk;
+  const int64_t s = p.sample_every;
+  h->md_rdf_origin = (h->md_step + s - 1) / s * s;
+  h->md_rdf_last = -1;
+  h->md_rdf_valid = true;
+  return true;
+}
+
 // The loop that ta_md_run and ta_relax_run share. `enqueue(q)` puts the launches of step q on the stream
 // (they are predicated on the status word and test the skin / 2 rule after their drift); this loop follows
 // each with the exact list of the step and an evaluation, looks at the page-locked status word every
@@ -2063,7 +2110,7 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
   if (velocities)
     for (size_t i = 0; i < 3 * N; ++i)
       if (!std::isfinite(velocities[i])) return fail(h, TA_ERR_INVALID, "ta_md_init: non-finite velocity");
-  bool ring_nomem = false;
+  bool ring_nomem = false, rdf_nomem = false;
   const int rc = guarded(h, [&]() {
     h->md_valid = false;
     HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -2095,10 +2142,16 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
       h->md_samp_on = false;
       ring_nomem = true;
     }
+    if (h->md_rdf_on && !md_rdf_alloc(h, h->md_rdf_p)) {  // zero counts for this batch, or none
+      h->md_rdf_on = false;
+      rdf_nomem = true;
+    }
     h->md_valid = true;
   });
   if (rc == TA_OK && ring_nomem)
     return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the rings of ta_md_set_sampling; sampling is off");
+  if (rc == TA_OK && rdf_nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the counts of ta_md_set_rdf; the feature is off");
   return rc;
 }
 
@@ -2322,6 +2375,63 @@ int ta_md_get_samples(ta_handle h, int32_t first_lag, int32_t n, double *positio
   });
 }
 
+int ta_md_set_rdf(ta_handle h, const ta_md_rdf_params *p) {
+  if (!h) return TA_ERR_INVALID;
+  if (!p || p->n_bins == 0) {
+    h->md_rdf_on = false;
+    return guarded(h, [&]() {
+      HIP_CHECK(hipStreamSynchronize(h->stream));
+      md_rdf_release(h);
+    });
+  }
+  if (p->n_bins < 0 || p->n_bins > TA_MD_MAX_BINS)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: n_bins must be 0 .. " + std::to_string(TA_MD_MAX_BINS));
+  if (p->sample_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: sample_every must be >= 1");
+  if (!std::isfinite(p->r_max) || !(p->r_max > 0.0))
+    return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: r_max must be a finite distance > 0");
+  if (p->r_max > h->rmax)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: r_max = " + std::to_string(p->r_max) + " exceeds the model's cutoff max(rcut, acut) = " +
+                                   std::to_string(h->rmax) + "; the neighbour list is not complete beyond that");
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: no resident batch");
+  if (!h->md_valid) return fail(h, TA_ERR_INVALID, "ta_md_set_rdf called before ta_md_init");
+  bool nomem = false;
+  const int rc = guarded(h, [&]() {
+    h->md_rdf_on = false;  // (until the counts exist)
+    nomem = !md_rdf_alloc(h, *p);
+    if (!nomem) {
+      h->md_rdf_p = *p;
+      h->md_rdf_on = true;
+    }
+  });
+  if (rc == TA_OK && nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_set_rdf: no device memory for counts of n_bins = " + std::to_string(p->n_bins) +
+                                 "; the feature is off");
+  return rc;
+}
+
+int ta_md_get_rdf(ta_handle h, int64_t *counts, int64_t *info, double *r_max) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_rdf: no resident batch");
+  if (!h->md_valid) return fail(h, TA_ERR_INVALID, "ta_md_get_rdf called before ta_md_init");
+  if (!h->md_rdf_on) return fail(h, TA_ERR_INVALID, "ta_md_get_rdf: the pair distributions are off (ta_md_set_rdf)");
+  if (!h->md_rdf_valid)
+    return fail(h, TA_ERR_INVALID, "ta_md_get_rdf: a ta_md_run failed and left the counts invalid; call ta_md_set_rdf or "
+                                   "ta_md_init again");
+  return guarded(h, [&]() {
+    const size_t E = (size_t)h->n_elements, n = h->keep_natoms.size() * E * E * (size_t)h->md_rdf_p.n_bins;
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the counts are copied as they are");
+    if (counts && n) HIP_CHECK(hipMemcpy(counts, h->md_rdf_acc.ptr, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (info) {
+      info[0] = h->md_rdf_last < 0 ? 0 : (h->md_rdf_last - h->md_rdf_origin) / h->md_rdf_p.sample_every + 1;
+      info[1] = h->md_rdf_p.n_bins;
+      info[2] = h->md_rdf_p.sample_every;
+      info[3] = h->md_rdf_last;
+    }
+    if (r_max) *r_max = h->md_rdf_p.r_max;
+  });
+}
+
 int ta_md_noise(ta_handle h, int64_t step, double *xi, double *eta) {
   if (!h) return TA_ERR_INVALID;
   if (!xi || !eta) return fail(h, TA_ERR_INVALID, "ta_md_noise: null argument");
@@ -2414,6 +2524,10 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
   if (samp && baro)
     return fail(h, TA_ERR_INVALID, "ta_md_run: sampling (ta_md_set_sampling) and the barostat (ta_md_set_barostat) are both "
                                    "on; displacements in a moving cell are not defined: switch one of them off");
+  const bool rdf = h->md_rdf_on;
+  if (rdf && baro)
+    return fail(h, TA_ERR_INVALID, "ta_md_run: the pair distributions (ta_md_set_rdf) and the barostat (ta_md_set_barostat) are "
+                                   "both on; normalising the counts needs one volume: switch one of them off");
   if (n_rebuilds) *n_rebuilds = 0;
   want |= TA_WANT_ENERGY | TA_WANT_FORCES;
   want &= ~(uint32_t)TA_WANT_REUSE_DESCRIPTORS;
@@ -2422,6 +2536,8 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
   h->md_nhc_rec_valid = false;
   const bool samp_was_valid = h->md_samp_valid;
   h->md_samp_valid = false;  // (until this run has succeeded)
+  const bool rdf_was_valid = h->md_rdf_valid;
+  h->md_rdf_valid = false;
   h->cell_running = h->md_baro_running = baro;
   const int rc = guarded(h, [&]() {
     const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
@@ -2514,7 +2630,36 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     c.status = h->md_status.ptr;
     c.n_atoms = (long long)N;
     c.n_lags = (int)samp_L, c.n_elements = h->n_elements, c.n_frames = (int)F, c.n_chunks = h->md_corr_chunks;
+    // Pair distributions: the state t = step0 + k is counted by a launch IN FRONT OF the integrator launch of
+    // step k, whose drift leaves x(t). With seq = k the integrator's predicate skips exactly the states that
+    // were reached on a stale list; after the rebuild the launch is enqueued again with the rest and counts
+    // then. Launch 0 does not count the state the last launch of the run before counted.
+    const bool rdf_run = rdf && rdf_was_valid && N > 0;
+    const int64_t rdf_s = h->md_rdf_p.sample_every, rdf_origin = h->md_rdf_origin, rdf_last = h->md_rdf_last;
+    ta::MdRdfLaunch g;
+    g.blk_start = h->md_rdf_blk.ptr;
+    g.counts = h->md_rdf_acc.ptr;
+    g.status = h->md_status.ptr;
+    g.n_bins = h->md_rdf_p.n_bins, g.n_elements = h->n_elements, g.n_frames = (int)F;
+    g.n_blk = h->md_rdf_n_blk, g.chunk = h->md_rdf_chunk;
+    g.dr = rdf_run ? h->md_rdf_p.r_max / (double)h->md_rdf_p.n_bins : 1.0;
     auto integrate = [&](int k, bool drift) {
+      if (rdf_run) {
+        const int64_t t = step0 + k;
+        if (t >= rdf_origin && (t - rdf_origin) % rdf_s == 0 && !(k == 0 && t == rdf_last)) {
+          g.pos = h->db.pos;
+          g.cells = h->db.cells;
+          g.species = h->db.species;
+          g.atom_start = h->db.atom_start;
+          g.pair_start = h->pair_start.ptr;  // the resident list, not the exact one filtered from it
+          g.pair_i = h->pair_i.ptr;
+          g.pair_j = h->pair_j.ptr;
+          g.pair_shift = h->pair_shift.ptr;
+          g.seq = (unsigned)k;
+          ta::launch_md_rdf(g, s);
+          HIP_CHECK(hipGetLastError());
+        }
+      }
       // (a rebuild may have moved the batch's arrays: the pointers are taken at every launch)
       a.pos = h->db.pos;
       a.forces = h->db.forces;
@@ -2559,6 +2704,9 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     if (sampling && h->md_step >= samp_origin)  // the newest sample: the last multiple of sample_every reached
       h->md_samp_last = std::max(samp_last, samp_origin + (h->md_step - samp_origin) / samp_s * samp_s);
     h->md_samp_valid = samp_was_valid;
+    if (rdf_run && h->md_step >= rdf_origin)
+      h->md_rdf_last = std::max(rdf_last, rdf_origin + (h->md_step - rdf_origin) / rdf_s * rdf_s);
+    h->md_rdf_valid = rdf_was_valid;
     if (n_rebuilds) *n_rebuilds = rebuilds;
     if (baro && F) {
       std::vector<double> rec(4 * n_rec * F);

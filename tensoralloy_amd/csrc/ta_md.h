@@ -82,9 +82,35 @@ struct MdCorrLaunch {
   int n_lags, n_elements, n_frames, n_chunks;
 };
 
+constexpr int kMdRdfLdsWords = 8192;  // most 32-bit bins of the pair-distribution launch's LDS histogram (32 KB)
+
+// Centres per workgroup of the pair-distribution launch for a batch of n_atoms: small batches spread over the
+// chip, large ones merge fewer histograms (the plan, blk_start, is made once by ta_md_set_rdf)
+inline int md_rdf_chunk(long long n_atoms) { return n_atoms <= 16384 ? 8 : 64; }
+
+// Arguments of the pair-distribution launch (ta_md_rdf.hip) that ta_md_run puts in front of the integrator
+// launch of a sampled step: the resident (skin) list, the positions and cells of that whole-step state.
+struct MdRdfLaunch {
+  const double *pos;              // [N][3] db.pos
+  const double *cells;            // [F][9]
+  const int32_t *species;         // [N]
+  const int32_t *atom_start;      // [F + 1]
+  const int32_t *blk_start;       // [F + 1] first workgroup of each frame (at least one each)
+  const int32_t *pair_start;      // [N + 1] the resident list: centre i owns pair_start[i] .. pair_start[i + 1] - 1
+  const int32_t *pair_i, *pair_j; // [P]
+  const int32_t *pair_shift;      // [P][3]
+  unsigned long long *counts;     // [F][E][E][n_bins] the accumulators
+  const unsigned *status;         // the integrator's status word and
+  unsigned seq;                   // sequence number: the same predicate
+  int n_bins, n_elements, n_frames, n_blk, chunk;
+  double dr;                      // r_max / n_bins
+};
+
 void launch_md_integrate(const MdLaunch &a, int threads, hipStream_t s);
 
 void launch_md_correlate(const MdCorrLaunch &a, hipStream_t s);
+
+void launch_md_rdf(const MdRdfLaunch &a, hipStream_t s);
 
 // xi, eta [n][3] (device): the normals md_integrate draws for absolute step `step`, atoms 0 .. n - 1
 void launch_md_noise(unsigned long long seed, long long step, long long n, double *xi, double *eta, hipStream_t s);

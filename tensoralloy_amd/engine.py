@@ -38,7 +38,10 @@ class Engine:
         self._md_barostat = False  # `md_set_barostat` is on: `md_run` moves the cells
         self._md_chain = 0         # `md_set_nose_hoover` is on: thermostats per chain
         self._md_lags = 0          # `md_set_sampling` is on: snapshots in the ring
+        self._md_bins = 0          # `md_set_rdf` is on: bins of the pair distributions
         self._n_elements = int(desc.n_elements)
+        # what the neighbour list is complete for: max(rcut, acut), acut counting for angular models only
+        self._md_cutoff = max(float(desc.rcut), float(desc.acut)) if int(desc.angular) else float(desc.rcut)
         self._md_sig = None   # (n, numbers, pbc) of the single resident frame of `evaluate_md`
         self._md_cell = None
         self.batch_generation = 0  # bumped whenever the resident batch or its coordinates change
@@ -267,7 +270,14 @@ class Engine:
             if v.size != 3 * N:
                 raise ValueError("md_init: velocities [n_atoms, 3] for every atom of the resident batch are needed")
             vptr = _lib.as_dp(v)
-        self._check(self._lib.ta_md_init(self._handle, _lib.as_dp(m), vptr))
+        rc = self._lib.ta_md_init(self._handle, _lib.as_dp(m), vptr)
+        if rc == _lib.TA_ERR_NOMEM:   # no room for what a setting needs: the library switched that setting off
+            msg = self._lib.ta_last_error(self._handle) or b""
+            if b"ta_md_set_rdf" in msg:
+                self._md_bins = 0
+            if b"ta_md_set_sampling" in msg:
+                self._md_lags = 0
+        self._check(rc)
 
     def md_set_thermostat(self, kT=0.0, tau=0.0):
         """Berendsen thermostat of `md_run`: target kT (eV) and time constant (ASE time units);
@@ -348,6 +358,50 @@ class Engine:
         self._check(self._lib.ta_md_get_samples(self._handle, 0, n, _lib.as_dp(x), _lib.as_dp(v),
                                                 steps.ctypes.data_as(C.POINTER(C.c_int64))))
         return {"x": x[:n][::-1].copy(), "v": v[:n][::-1].copy(), "steps": steps[:n][::-1].copy()}
+
+    def md_set_rdf(self, n_bins=0, r_max=None, sample_every=1):
+        """Partial pair distributions inside `md_run` (`ta_md_set_rdf`): with `n_bins` = B (1 .. 4096) the loop
+        counts, at every step t (counted since `md_init`) with t % `sample_every` == 0, every directed pair of the
+        resident neighbour list below `r_max` (default: the model's cutoff max(rcut, acut), which is also the
+        largest value allowed) into integer histograms of B bins per frame and pair of elements, which stay on
+        the device (`md_rdf`). `n_bins` = 0 switches it off (the default) and frees them. Needs `md_init`; every
+        call starts from zero counts, as `md_init` does. The setting stays on across `set_frames`. Independent of
+        `md_set_sampling`. `md_run` refuses it under the barostat."""
+        if r_max is None:
+            r_max = self._md_cutoff
+        p = _lib.MdRdfParams(float(r_max), int(n_bins), int(sample_every))
+        rc = self._lib.ta_md_set_rdf(self._handle, C.byref(p))
+        if rc == _lib.TA_ERR_NOMEM:   # (no room for the counts: the library switched the feature off)
+            self._md_bins = 0
+        self._check(rc)
+        self._md_bins = int(n_bins)
+
+    @property
+    def md_rdf_bins(self):
+        """Bins of the pair distributions `md_set_rdf` switched on, 0 while they are off."""
+        return self._md_bins
+
+    def md_rdf(self):
+        """What the loop has counted since `md_set_rdf` (`ta_md_get_rdf`), a dict: `counts` int64 [n_frames,
+        n_elements, n_elements, n_bins], counts[f, a, b, k] = directed pairs of a centre of species a and a
+        neighbour of species b in frame f with floor(r / (r_max / n_bins)) == k, summed over the samples;
+        `n_samples`, `r_max`, `sample_every`, `last_step` (absolute step of the newest sample, -1: none);
+        `n_by_element` [n_frames, n_elements] atoms per frame and element, `volumes` [n_frames] and `pbc`
+        [n_frames, 3] of the resident frames: what `md.rdf` normalises the counts with."""
+        if self.info is None:
+            raise ValueError("md_rdf: no resident batch (call set_frames first)")
+        F, E, B = int(self.info.n_frames), self._n_elements, max(self._md_bins, 1)
+        counts = np.zeros((F, E, E, B), dtype=np.int64)
+        info = (C.c_int64 * 4)()
+        r_max = C.c_double(0.0)
+        self._check(self._lib.ta_md_get_rdf(self._handle, counts.ctypes.data_as(C.POINTER(C.c_int64)), info,
+                                            C.byref(r_max)))
+        n_by_element = np.zeros((F, E), dtype=np.int64)
+        for f, fr in enumerate(self._frames):
+            n_by_element[f] = np.bincount(fr.species, minlength=E)[:E]
+        return {"counts": counts, "n_samples": int(info[0]), "r_max": float(r_max.value),
+                "sample_every": int(info[2]), "last_step": int(info[3]), "n_by_element": n_by_element,
+                "volumes": self._volumes.copy(), "pbc": np.array([fr.pbc != 0 for fr in self._frames]).reshape(F, 3)}
 
     def md_noise(self, step: int):
         """(xi, eta) [n_atoms, 3]: the standard normals the Langevin step with absolute index `step` (steps

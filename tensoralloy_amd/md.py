@@ -43,6 +43,12 @@ integrator holds, and no centre-of-mass correction is made: velocities without n
 mass at rest under NVE and the Nose-Hoover chain; under Langevin its diffusion is part of the result. Sampling
 under the barostat is refused. `vdos` turns a VACF into a vibrational density of states, `diffusion_coefficient`
 fits the slope of an MSD (Einstein) and `green_kubo_diffusion` integrates a VACF (Green-Kubo).
+
+Pair distributions: with `rdf_bins` (and `rdf_rmax`, `rdf_every`) the loop counts, at every sampled step, the
+pairs of its resident neighbour list below `rdf_rmax` into integer histograms per frame and pair of elements,
+on the device (`Engine.md_set_rdf`; `DeviceMD.get_rdf`). The counts are exact integers and do not depend on how
+a run is cut. `rdf` normalises counts to g_ab(r), `coordination_number` integrates g_ab to a neighbour count.
+Independent of `n_lags`; refused under the barostat, where there is no single volume to normalise with.
 """
 from __future__ import annotations
 
@@ -54,7 +60,7 @@ GPa = 1.0 / 160.21766208      # eV / Angstrom^3
 bar = 1.0e-4 * GPa
 
 __all__ = ["fs", "kB", "GPa", "bar", "maxwell_boltzmann", "DeviceMD", "vdos", "diffusion_coefficient",
-           "green_kubo_diffusion"]
+           "green_kubo_diffusion", "rdf", "coordination_number"]
 
 
 def maxwell_boltzmann(masses, kT, rng, zero_momentum=True):
@@ -146,6 +152,70 @@ def green_kubo_diffusion(vacf, dt_sample):
     return _trapezoid(c, float(dt_sample)) / 3.0
 
 
+def _shell_volumes(n_bins, dr):
+    k = np.arange(n_bins, dtype=np.float64)
+    return (4.0 * np.pi / 3.0) * ((k + 1.0) ** 3 - k ** 3) * dr ** 3
+
+
+def rdf(counts, n_samples, n_by_element, volume, r_max, pbc=None):
+    """Partial pair distribution functions from the integer pair counts of the device loop (`Engine.md_rdf`):
+    `counts` [..., E, E, B] directed pairs of a centre of element a and a neighbour of element b in bin k
+    (k = floor(r / dr), dr = `r_max` / B), summed over `n_samples` samples; `n_by_element` [..., E] atoms per
+    element; `volume` [...] of the cell. Returns (r, g): the bin centres r_k = (k + 1/2) dr [B] and
+        g_ab(r_k) = C[a][b][k] V / (n_samples N_a N_b (4 pi / 3) ((k + 1)^3 - k^3) dr^3)
+    [..., E, E, B]. The normalisation uses N_a N_b, not N_a (N_b - delta_ab): g_aa of an ideal gas is
+    (N_a - 1) / N_a, not 1, which matters for small cells only. Rows with N_a N_b == 0 (an element the frame
+    does not hold) and everything with `n_samples` == 0 are NaN. g is defined against the mean density of a
+    periodic cell: a `volume` that is not finite and > 0, or a `pbc` ([..., 3], optional) that is not periodic
+    in all three directions, raises ValueError; the counts of such frames are still meaningful."""
+    c = np.asarray(counts)
+    if c.ndim < 3 or c.shape[-2] != c.shape[-3] or c.shape[-1] < 1:
+        raise ValueError("rdf: counts must be [..., n_elements, n_elements, n_bins]")
+    B = c.shape[-1]
+    if not (np.isfinite(r_max) and r_max > 0.0):
+        raise ValueError("rdf: r_max must be a finite distance > 0")
+    if int(n_samples) != n_samples or n_samples < 0:
+        raise ValueError("rdf: n_samples must be an integer >= 0")
+    if pbc is not None and not np.all(pbc):
+        raise ValueError("rdf: g(r) needs a frame periodic in all three directions (the counts need not)")
+    V = np.asarray(volume, dtype=np.float64)
+    if not np.all(np.isfinite(V) & (V > 0.0)):
+        raise ValueError("rdf: volume must be finite and > 0")
+    n = np.asarray(n_by_element, dtype=np.float64)
+    if n.shape != c.shape[:-2]:
+        raise ValueError("rdf: n_by_element must be [..., n_elements], matching counts")
+    if V.shape not in ((), c.shape[:-3]):
+        raise ValueError("rdf: one volume, or one per frame of counts, is needed")
+    dr = float(r_max) / B
+    r = (np.arange(B) + 0.5) * dr
+    den = float(n_samples) * n[..., :, None] * n[..., None, :]
+    den = den[..., None] * _shell_volumes(B, dr)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g = np.where(den > 0.0, c * V[..., None, None, None] / den, np.nan)
+    return r, g
+
+
+def coordination_number(g, r, density_b, r_cut):
+    """Neighbours of element b around an atom of element a within `r_cut`: the running integral of
+    4 pi r^2 rho_b g_ab(r), from `g` [..., B] on the bin centres `r` [B] of `rdf` (uniform bins from 0) and
+    the number density `density_b` = N_b / V (a scalar, or an array that broadcasts against g without its
+    last axis). It is evaluated from the shell volumes (4 pi / 3) ((k + 1)^3 - k^3) dr^3 that `rdf` divided by,
+    over the bins whose centres lie below `r_cut`, so it returns the counts / (n_samples N_a) that went in,
+    not a quadrature of them."""
+    g = np.asarray(g, dtype=np.float64)
+    r = np.asarray(r, dtype=np.float64)
+    if r.ndim != 1 or len(r) < 1 or g.ndim < 1 or g.shape[-1] != len(r):
+        raise ValueError("coordination_number: g [..., n_bins] on the bin centres r [n_bins] is needed")
+    dr = 2.0 * float(r[0])
+    if not (np.isfinite(dr) and dr > 0.0 and np.allclose(r, (np.arange(len(r)) + 0.5) * dr, rtol=1e-9, atol=0.0)):
+        raise ValueError("coordination_number: r must be the centres (k + 1/2) dr of uniform bins from 0")
+    if not np.isfinite(r_cut):
+        raise ValueError("coordination_number: r_cut must be finite")
+    inside = r < r_cut
+    shells = np.where(inside, _shell_volumes(len(r), dr), 0.0)
+    return np.asarray(density_b, dtype=np.float64) * (np.where(inside, g, 0.0) * shells).sum(axis=-1)
+
+
 class DeviceMD:
     """
     NVE (velocity Verlet), Berendsen NVT, Langevin NVT or Nose-Hoover chain NVT dynamics of one structure or of a batch of
@@ -173,6 +243,12 @@ class DeviceMD:
                            construction is the first sample) and accumulates the velocity autocorrelation and
                            the mean-square displacement at `n_lags` lags on the device (`get_vacf`, `get_msd`,
                            `get_samples`); excludes the barostat. The ring takes 2 x n_lags x n_atoms x 24 bytes
+    rdf_bins, rdf_rmax, rdf_every : `rdf_bins` given (1 .. 4096): the loop counts the pairs below `rdf_rmax`
+                           (default and largest value: the model's cutoff) of every `rdf_every`-th step (the
+                           state at construction is the first sample) into `rdf_bins` bins per pair of elements
+                           on the device (`get_rdf`); excludes the barostat. Without `rdf_bins` no method of
+                           the pair distributions is called on the engine, unless its `md_rdf_bins` says that an
+                           earlier `DeviceMD` left them on: they are then switched off
 
     Under the barostat the cell of every `Atoms` follows (the atoms are not scaled again), and every `run` call
     that moved the cells ends with one neighbour-list build for the final cells: an observer at interval 1
@@ -183,7 +259,7 @@ class DeviceMD:
     def __init__(self, engine_or_calculator, atoms_or_list, timestep, temperature_K=None, taut=None,
                  velocities=None, masses=None, friction=None, seed=0, pressure=None, taup=None,
                  compressibility=None, mask=None, tdamp=None, tchain=3, tloop=1, dof_removed=0, n_lags=None,
-                 sample_every=1):
+                 sample_every=1, rdf_bins=None, rdf_rmax=None, rdf_every=1):
         if not (np.isfinite(timestep) and timestep > 0.0):
             raise ValueError("DeviceMD: timestep must be a finite time > 0")
         barostat = (pressure, taup, compressibility)
@@ -199,6 +275,19 @@ class DeviceMD:
                                  "displacements in a moving cell are not defined")
         elif sample_every != 1:
             raise ValueError("DeviceMD: sample_every belongs to sampling (n_lags)")
+        if rdf_bins is not None:
+            whole = lambda a: isinstance(a, (int, np.integer)) and not isinstance(a, bool)
+            if not (whole(rdf_bins) and 1 <= rdf_bins <= 4096):
+                raise ValueError("DeviceMD: rdf_bins must be an integer 1 .. 4096")
+            if not (whole(rdf_every) and rdf_every >= 1):
+                raise ValueError("DeviceMD: rdf_every must be an integer >= 1")
+            if rdf_rmax is not None and not (np.isfinite(rdf_rmax) and rdf_rmax > 0.0):
+                raise ValueError("DeviceMD: rdf_rmax must be a finite distance > 0")
+            if self._barostat:
+                raise ValueError("DeviceMD: rdf_bins (pair distributions) excludes the barostat (pressure, taup, "
+                                 "compressibility): normalising the counts needs one volume")
+        elif rdf_every != 1 or rdf_rmax is not None:
+            raise ValueError("DeviceMD: rdf_every and rdf_rmax belong to the pair distributions (rdf_bins)")
         if self._barostat:
             if any(p is None for p in barostat):
                 raise ValueError("DeviceMD: the barostat needs pressure, taup and compressibility")
@@ -295,6 +384,15 @@ class DeviceMD:
         self._lags = int(n_lags) if n_lags is not None else 0
         self._sample_every = int(sample_every)
         engine.md_set_sampling(self._lags, self._sample_every)   # (state 0 is the first sample)
+        self._rdf_bins = int(rdf_bins) if rdf_bins is not None else 0
+        # Opt-in: an engine that is never asked for pair distributions needs none of their methods, and none is
+        # called on it. Deliberately one exception: an engine that says (`md_rdf_bins`) that an earlier DeviceMD
+        # left them on is told to switch them off, so that this run neither pays for them nor is refused under
+        # the barostat because of them.
+        if self._rdf_bins:
+            engine.md_set_rdf(self._rdf_bins, rdf_rmax, int(rdf_every))
+        elif getattr(engine, "md_rdf_bins", 0):
+            engine.md_set_rdf(0)
         self._natoms = np.array([len(a) for a in self.atoms_list], dtype=np.int64)
         self.velocities = velocities.copy()
         self.epot = self.ekin = None   # per-frame records of the last state
@@ -387,6 +485,18 @@ class DeviceMD:
         if not self._lags:
             raise ValueError("DeviceMD.get_samples: sampling is off (n_lags)")
         return self.engine.md_samples(n)
+
+    def get_rdf(self):
+        """(r, g): the bin centres [rdf_bins] and the partial pair distribution functions g_ab(r)
+        [n_elements, n_elements, rdf_bins] (a batch: [n_frames, n_elements, n_elements, rdf_bins]) over every
+        state sampled so far, normalised as `rdf` does (NaN where the frame has no atom of an element or nothing
+        was sampled yet). Raises ValueError for a frame that is not periodic in all three directions; its counts
+        are in `engine.md_rdf()`. Needs `rdf_bins`."""
+        if not self._rdf_bins:
+            raise ValueError("DeviceMD.get_rdf: the pair distributions are off (rdf_bins)")
+        out = self.engine.md_rdf()
+        r, g = rdf(out["counts"], out["n_samples"], out["n_by_element"], out["volumes"], out["r_max"], pbc=out["pbc"])
+        return r, (g[0] if self._single else g)
 
     def get_volume(self):
         """Cell volume per frame, in A^3."""
