@@ -13,163 +13,13 @@
 #include <string>
 #include <vector>
 
-#include "ta_device.h"
-#include "ta_internal.h"
-#include "ta_md.h"
-#include "ta_neb.h"
-#include "ta_relax.h"
+#include "ta_context.h"
 
-namespace ta {
-size_t mlp_scratch_doubles(const MlpDev &mlp);
-void launch_mlp_impl(const MlpDev &mlp, int activation, int ndim, const int32_t *atoms, int n_atoms,
-                     const DeviceBatch &b, const Options &opt, double *scratch, hipStream_t s,
-                     MlpLaunchInfo *info = nullptr);
-size_t mlp_all_scratch_doubles(const MlpDev *mlps_host, int nel, const int32_t *elem_start);
-size_t td_scratch_doubles(const MlpDev *nets, int nel, int K, const int32_t *elem_start, bool da_global);
-void launch_td_all(const MlpDev *nets_dev, const MlpDev *nets_host, int nel, int K, int act_h, int act,
-                   int sommerfeld, int ndim, const DeviceBatch &b, bool da_global, const double *T, double *u_atom,
-                   double *s_atom, double *scratch, hipStream_t s, MlpLaunchInfo *info = nullptr);
-void launch_mlp_all(const MlpDev *mlps_dev, const MlpDev *mlps_host, int nel, int activation, int ndim,
-                    const DeviceBatch &b, const Options &opt, double *scratch, hipStream_t s,
-                    MlpLaunchInfo *info = nullptr);
-// weight gradients (ta_train.hip)
-int mlp_param_count(const MlpDev &mlp);
-size_t mlp_grad_scratch_doubles(const MlpDev &mlp, int n_atoms);
-size_t mlp_grad_partial_doubles(const MlpDev &mlp, int n_atoms);
-void launch_mlp_grad(const MlpDev &mlp, int activation, int ndim, const int32_t *atoms, int n_atoms,
-                     const DeviceBatch &b, const double *frame_coeff, double *scratch, double *partial,
-                     double *grad, hipStream_t s);
-size_t mlp_grad2_scratch_doubles(const MlpDev &mlp, int n_atoms);
-void launch_mlp_grad2(const MlpDev &mlp, int activation, int ndim, const int32_t *atoms, int n_atoms,
-                      const DeviceBatch &b, const double *dG, const double *frame_coeff, double *scratch,
-                      double *partial, double *grad, hipStream_t s, double *kappa_out = nullptr);
-// weight gradients of the temperature-dependent head (ta_td_train.hip)
-int td_param_count(const MlpDev *nets, int nel);
-void td_grad2_sizes(const MlpDev *nets, int nel, int K, const int32_t *elem_start, size_t *scratch,
-                    size_t *partial);
-void launch_td_grad2(const MlpDev *nets_dev, const MlpDev *nets_host, int nel, int K, int act_h, int act,
-                     int sommerfeld, int ndim, const DeviceBatch &b, const double *T, const double *dG,
-                     const double *coeff, double *scratch, double *partial, double *grad, hipStream_t s);
-// analytic Hessian-vector products of the descriptor models (ta_hvp.hip)
-void launch_pair_vec(const DeviceBatch &b, double *Dv, hipStream_t s);
-void launch_backward_hvp(const SFParams &sf, const AngChunk &ch, int nb, int ng, int nz, bool first, bool angular,
-                         const DeviceBatch &b, const double *Dv, const double *Dd, const double *wdot, double *gv,
-                         double *gd, hipStream_t s);
-void launch_hvp_gather(const DeviceBatch &b, const double *Dv, const double *Dd, const double *gv, const double *gd,
-                       double *fdot, double *wdot_at, hipStream_t s);
-void launch_pair_tangent(const DeviceBatch &b, const double *dR, const double *dh, double *dD, hipStream_t s);
-void launch_descriptor_jvp(const DeviceBatch &b, int ndim, const double *J, const double *dD, double *dG,
-                           hipStream_t s);
-void launch_one_hot(double *dEdG, int64_t n_atoms, int ndim, int c, hipStream_t s);
-// GRAP (ta_grap.hip)
-struct GrapModel;
-bool grap_hvp_supported(const GrapModel *);
-void launch_grap_hvp(GrapModel *, const DeviceBatch &b, double eps, const double *Dv, const double *Dd,
-                     const double *wdot, double *gv, double *gd, hipStream_t s);
-GrapModel *grap_create(const ta_model_desc *m, std::string &err);
-int grap_ndim(const GrapModel *g);
-bool grap_uses_filter_net(const GrapModel *g);
-void grap_destroy(GrapModel *);
-void grap_ensure(GrapModel *, const DeviceBatch &b);
-void launch_grap_forward(GrapModel *, const DeviceBatch &b, double eps, hipStream_t s);
-void launch_grap_backward(GrapModel *, const DeviceBatch &b, hipStream_t s);
-// training the GRAP filter network (ta_grap.hip)
-int64_t grap_filter_param_count(const GrapModel *g);
-void grap_update_filter_weights(GrapModel *g, const double *flat, int64_t n, hipStream_t s);
-int grap_filter_table_knots(const GrapModel *g);
-void grap_set_filter_tables(GrapModel *g, bool on, int n_knots, hipStream_t s);
-int grap_filter_table_target(const GrapModel *g, bool on, int n_knots);
-void grap_mark_trained(GrapModel *g);
-void grap_suspend_filter_tables(GrapModel *g, bool suspend);
-std::string grap_filter_train_refusal(const GrapModel *g);
-size_t grap_filter_grad_doubles(const GrapModel *g, const DeviceBatch &b);
-void launch_grap_filter_tangent(GrapModel *g, const DeviceBatch &b, double eps, const double *Dv, const double *Dd,
-                                double *Gdot, hipStream_t s);
-void grap_filter_gradient(GrapModel *g, const DeviceBatch &b, double eps, const double *Dv, const double *Dd,
-                          const double *kappa, double *scratch, double *grad, hipStream_t s);
-// EAM / ADP (ta_eam.hip)
-struct EamModel;
-EamModel *eam_create(const ta_model_desc *m, const Options &opt, std::string &err);
-void eam_destroy(EamModel *);
-void eam_ensure(EamModel *, const DeviceBatch &b);
-void eam_tabulate(EamModel *m, int n_r, const double *r, int n_rho, const double *rho, double *rho_of_r,
-                  double *phi_of_r, double *embed_of_rho, double *u_of_r, double *w_of_r,
-                  hipStream_t s);
-void eam_compute(EamModel *, const DeviceBatch &b, uint32_t want, hipStream_t s,
-                 hipEvent_t *ev /* 2 events or null */);
-void eam_set_list_cutoff(EamModel *, double rc /* 0: the list is exact, no test */);
-bool eam_is_plain(const EamModel *);
-void eam_set_nn_tables(EamModel *, bool on);
-bool eam_hvp_supported(const EamModel *);
-size_t eam_hvp_extra_doubles(const EamModel *, const DeviceBatch &b, int n_dir);
-void eam_hvp(EamModel *, const DeviceBatch &b, int n_dir, bool unit, int first, const double *dR, const double *dh,
-             double *dFdot, double *fdot, double *wdot, double *extra, hipStream_t s);
-bool eam_nn_tables_on(const EamModel *);
-void eam_mark_trained(EamModel *);
-int64_t eam_param_count(const EamModel *);
-void eam_update_weights(EamModel *, const double *flat, int64_t n);
-int64_t eam_constant_count(const EamModel *);
-void eam_get_constants(const EamModel *, double *flat);
-void eam_update_constants(EamModel *, const double *flat, int64_t n);
-void eam_constant_gradient(EamModel *, const DeviceBatch &b, const double *frame_coeff, const double *dR,
-                           const double *dh, double *grad, hipStream_t s);
-void eam_energy_gradient(EamModel *, const DeviceBatch &b, const double *frame_coeff, double *grad,
-                         hipStream_t s);
-bool eam_loss_gradient_supported(const EamModel *);
-void eam_loss_gradient(EamModel *, const DeviceBatch &b, const double *frame_coeff, const double *dR,
-                       const double *dh, double *grad, hipStream_t s);
-}  // namespace ta
+using namespace ta::host;
 
 namespace {
 
 thread_local std::string g_create_error;
-
-struct HipError : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-
-#define HIP_CHECK(expr)                                                                      \
-  do {                                                                                       \
-    hipError_t _e = (expr);                                                                  \
-    if (_e != hipSuccess)                                                                    \
-      throw HipError(std::string(#expr) + ": " + hipGetErrorString(_e) + " (" __FILE__ ":" + \
-                     std::to_string(__LINE__) + ")");                                        \
-  } while (0)
-
-// grow-only device buffer
-template <typename T>
-struct DevBuf {
-  T *ptr = nullptr;
-  size_t cap = 0;
-  void ensure(size_t n) {
-    if (n <= cap) return;
-    // the old allocation stays valid until the new one exists: a failed hipMalloc must not
-    // leave a dangling pointer behind (contents are not carried over: every user refills)
-    size_t want = n + n / 8 + 64;
-    T *fresh = nullptr;
-    hipError_t e = hipMalloc((void **)&fresh, want * sizeof(T));
-    if (e != hipSuccess && ptr) {  // retry once with the old block returned first
-      (void)hipGetLastError();
-      HIP_CHECK(hipFree(ptr));
-      ptr = nullptr;
-      cap = 0;
-      e = hipMalloc((void **)&fresh, want * sizeof(T));
-    }
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      throw HipError(std::string("hipMalloc of ") + std::to_string(want * sizeof(T)) + " bytes: " +
-                     hipGetErrorString(e));
-    }
-    if (ptr) HIP_CHECK(hipFree(ptr));
-    ptr = fresh;
-    cap = want;
-  }
-  void release() {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    cap = 0;
-  }
-};
 
 // Small transfers between the page-locked staging buffers and device memory as a kernel ON the
 // compute stream (the device reads / writes the mapped host memory over PCIe) instead of an
@@ -181,8 +31,10 @@ __global__ __launch_bounds__(256) void staged_copy_kernel(double *__restrict__ d
 }
 constexpr size_t kStagedCopyMaxBytes = 4u << 20;  // beyond that the DMA engine's bandwidth wins
 
-// `to_host`: the copy direction of the fallback, which Options::staged_copy_dma always takes (A/B switch)
-void staged_copy(double *dst, const double *src, size_t n, bool to_host, const ta::Options &opt, hipStream_t s) {
+}  // namespace
+
+void ta::host::staged_copy(double *dst, const double *src, size_t n, bool to_host, const ta::Options &opt,
+                           hipStream_t s) {
   if (n == 0) return;
   if (n * sizeof(double) > kStagedCopyMaxBytes || opt.staged_copy_dma) {
     HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(double), to_host ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice, s));
@@ -196,7 +48,7 @@ void staged_copy(double *dst, const double *src, size_t n, bool to_host, const t
 // Wait for the stream on the latency-critical paths (one MD step has three waits around ~50 us kernels):
 // poll the stream for a short while before blocking, since a blocked thread is woken by an interrupt
 // many microseconds after the work is done. Options::sync_blocking goes straight to the blocking wait.
-void wait_stream(hipStream_t s, const ta::Options &opt) {
+void ta::host::wait_stream(hipStream_t s, const ta::Options &opt) {
   if (!opt.sync_blocking) {
     const auto t0 = std::chrono::steady_clock::now();
     for (;;) {
@@ -212,242 +64,15 @@ void wait_stream(hipStream_t s, const ta::Options &opt) {
   HIP_CHECK(hipStreamSynchronize(s));
 }
 
-// grow-only page-locked host buffer (staging for the packed uploads / downloads)
-struct PinnedBuf {
-  char *ptr = nullptr;
-  size_t cap = 0;
-  void ensure(size_t n) {
-    if (n <= cap) return;
-    if (ptr) HIP_CHECK(hipHostFree(ptr));
-    ptr = nullptr;
-    cap = 0;
-    size_t want = n + n / 8 + 256;
-    HIP_CHECK(hipHostMalloc((void **)&ptr, want, hipHostMallocDefault));
-    cap = want;
-  }
-  void release() {
-    if (ptr) (void)hipHostFree(ptr);
-    ptr = nullptr;
-    cap = 0;
-  }
-};
-
-struct ChunkPlan {
-  ta::AngChunk ch;
-  int nb, ng, nz;
-};
-
-}  // namespace
-
-struct ta_context {
-  ta::Options opt;  // the environment switches as they stood when ta_create ran
-  int device = 0;
-  hipStream_t stream = nullptr;      // stream all work is enqueued on
-  hipStream_t own_stream = nullptr;  // created by ta_create
-  int kind = 0;
-  int n_elements = 0;
-  int activation = 0;
-  double rmax = 0.0;
-  ta::SFParams sf;
-  std::vector<ChunkPlan> chunks;     // first-generation kernels: up to 2 betas per launch
-  std::vector<ChunkPlan> chunks_v2;  // second-generation kernels: one beta per launch
-  bool use_v2 = false;
-  ta::MlpDev *mlp_dev = nullptr;     // device copy of mlp[0..n_elements)
-  ta::MlpDev mlp[ta::kMaxElements];
-  // temperature-dependent head (ta_model_desc.finite_temperature): nets H[el], U[el], S[el]
-  bool td = false, td_sommerfeld = false;
-  int td_act = 0, td_K = 0;
-  ta::MlpDev td_nets[3 * ta::kMaxElements];
-  ta::MlpDev *td_dev = nullptr;
-  std::vector<void *> model_allocs;
-  ta::EamModel *eam = nullptr;
-  ta::GrapModel *grap = nullptr;
-
-  ta::HostPairs hp;
-  ta::DeviceBatch db;
-  bool have_batch = false;
-  uint32_t last_want = 0;
-
-  // Inputs travel in one packed upload: [pos | cells | grids | species | frame_of_atom |
-  // atom_start | elem_atoms | blk_center]; results come back in one packed download:
-  // [energy F | virial 9F | atomic N | forces 3N].
-  PinnedBuf stage_in, stage_out;
-  DevBuf<char> inbuf;
-  DevBuf<double> results;
-  size_t o_blk = 0;  // byte offset of blk_center in the packed input
-  int res_n_blk = 0;  // runs of the resident list's packing (db.n_blk is the exact list's while `filtered`)
-  DevBuf<double> rec, part4, G, dEdG, g, wat, bpart, fown, benergy, mlp_scratch;
-  DevBuf<double> td_T, td_u, td_s;  // electron temperature per frame; U and S per atom
-  DevBuf<unsigned long long> masks;
-  DevBuf<uint32_t> job_word;
-  DevBuf<int32_t> job_count;
-  // triangle-once backward pass (ta_set_triangles): the owned job lists, the handle's option, whether the
-  // resident batch's cells admit the ownership rule, and the builds the last backward pass ran
-  DevBuf<uint32_t> job_word_own;
-  DevBuf<int32_t> job_count_own;
-  bool triangles = true;
-  // the last second-generation forward pass left the full job list (db.job_word / job_count) behind: it
-  // does not when every backward launch of its evaluation read the owned lists (forward_v2_launches)
-  bool full_jobs_valid = false;
-  bool tri_cells_ok = false;
-  bool tri_cells_wide_ok = false;  // every periodic width exceeds rmax + skin: what the cell relaxation asks for
-  int last_bwd_variant = 0;
-  ta::MlpLaunchInfo last_mlp_launch;  // ta_mlp_launch_info
-  DevBuf<int32_t> pair_start, seg_start, pair_i, pair_j, pair_shift, pair_rev;
-  ta::NlGrid *d_grids = nullptr;  // view into inbuf
-  // device neighbour list (ta_nlist.hip)
-  DevBuf<int32_t> nl_wrap, nl_binid, nl_bin_count, nl_bin_start, nl_bin_cursor, nl_bin_atoms, nl_counts;
-  DevBuf<unsigned long long> nl_stats, nl_zero;
-  unsigned long long *nl_stats_ptr = nullptr;  // statistics block of the builder that made the list
-  bool nl_sorted = false;  // list in key order (one-pass builder): reverse pairs by binary search
-  bool nl_rev_done = false;  // ... and the reverse index is already there (launched behind the pairs)
-  bool nl_zero_clean = false;  // nl_zero is all zero where the next list needs it (see nl_build)
-  int64_t nl_zero_atoms = -1;
-  int nl_zero_bins = -1;
-  DevBuf<double> hvp_buf;  // ta_hessian_vectors: tangents in, force / virial tangents out
-#ifdef TA_PHASE_STAMPS
-  DevBuf<unsigned long long> stamp_buf;
-#endif
-  DevBuf<ta::NlRec> nl_recs;
-  bool pairs_on_device = false;  // hp holds only the counts; ta_get_pairs downloads on demand
-  bool descriptors_valid = false;  // db.G holds the resident batch's descriptors
-  DevBuf<double> train_scratch, train_partial, train_grad, train_coeff;
-  // force / stress terms of the loss: J[c][p] = dG_c / dD_p of the resident batch (made once per
-  // batch by one backward launch per descriptor channel), the direction and its images
-  DevBuf<double> jvp_J, tan_dD, tan_dG, tan_dir;
-  DevBuf<double> filt_scratch;  // ta_grap_loss_gradient: pair vectors, w-dot, per-pair adjoints, partial sums
-  bool jvp_valid = false;
-
-  // MD loop (ta_set_skin / ta_update_positions): the list covers rmax + skin and is kept while no
-  // atom has moved more than skin / 2 from where it was when the list was built
-  double skin = 0.0;
-  double r_list = 0.0;                         // rmax + skin: cutoff of the resident list
-  std::vector<int32_t> keep_species;           // [N]
-  std::vector<int32_t> keep_natoms, keep_pbc;  // [F], [3 F]: what a rebuild needs besides stage_in
-  std::vector<double> ref_pos, ref_cells;      // positions / cells the resident list was built for
-  size_t o_pos = 0, o_cells = 0, o_species = 0;  // byte offsets in the packed input
-  // exact list of the current step, extracted on the device from the resident skin list (nl_filter)
-  DevBuf<int32_t> ex_pair_i, ex_pair_j, ex_pair_shift, ex_pair_rev, ex_pair_start, ex_pair_stop, ex_seg_start, ex_counts,
-      ex_map, ex_blk, ex_slot_q;
-  DevBuf<ta::BlockHeader> ex_hdr;              // the exact list's run headers (DeviceBatch::blk_hdr)
-  bool filtered = false;                       // db points at the ex_* arrays
-  // a copy out of stage_in may still be in flight (set by ta_update_positions, cleared by every wait
-  // for the stream on the step path): whoever rewrites stage_in waits for the stream first. (An event
-  // recorded behind the copy cost a 5 us bubble between the copy and the next kernel of every MD step.)
-  bool upload_pending = false;
-  // ta_step: the next compute mirrors its results into stage_out (frame_reduce_kernel); `mirror_want` = the
-  // want bits whose results the page-locked image holds right now (0: none), cleared by whoever reuses stage_out
-  bool mirror_next = false;
-  uint32_t mirror_want = 0;
-  int64_t n_list_builds = 0, n_list_reuses = 0;
-
-  // device-resident MD loop (ta_md_init / ta_md_run; the integrator launch is in ta_md.hip): masses,
-  // velocities and the positions the resident list was built for (the device twin of ref_pos, as of
-  // list build number `md_ref_builds`); records of the running ta_md_run; the status word and its
-  // page-locked twin; the workgroup layout (`md_chunk` atoms each) that md_blk_start holds
-  bool md_valid = false;
-  DevBuf<double> md_mass, md_vel, md_ref, md_epot, md_ke;
-  DevBuf<int32_t> md_blk_start;
-  DevBuf<unsigned> md_status;
-  PinnedBuf md_status_host;
-  std::vector<int32_t> md_blk_start_host;
-  int md_chunk = 0, md_n_blk = 0;
-  int64_t md_ref_builds = -1;
-  double md_kT0 = 0.0, md_tau = 0.0;
-  // Nose-Hoover chain (ta_md_set_nose_hoover; off while md_nhc_on is false): the setting, the chain state
-  // [F][TA_MD_MAX_CHAIN] (zeroed by ta_md_init), the record of the running ta_md_run and the host's copy
-  // of the last successful run's chain terms
-  bool md_nhc_on = false;
-  ta_md_nhc_params md_nhc_p = {0.0, 0.0, 3, 1, 0};
-  DevBuf<double> md_nhc_eta, md_nhc_veta, md_nhc_rec;
-  bool md_nhc_rec_valid = false;
-  std::vector<double> md_rec_chain;  // [n_rec][F]
-  // Sampling (ta_md_set_sampling; off while md_samp_on is false): the setting; the rings [L][N][3], the
-  // accumulators [2][F][E][L] (v . v, then |dx|^2), the correlation launch's partials and chunk layout; the
-  // absolute step of sample 0 (a multiple of sample_every) and of the newest sample (-1: none); whether the
-  // data are those of a run that succeeded
-  bool md_samp_on = false;
-  ta_md_sampling_params md_samp_p = {0, 1};
-  DevBuf<double> md_ring_x, md_ring_v, md_corr_acc, md_corr_part;
-  DevBuf<int32_t> md_corr_blk;
-  int md_corr_chunks = 0;
-  int64_t md_samp_origin = 0, md_samp_last = -1;
-  bool md_samp_valid = false;
-  // Pair distributions (ta_md_set_rdf; off while md_rdf_on is false): the setting; the counts [F][E][E][n_bins],
-  // the launch's workgroup layout; the absolute step of sample 0 (a multiple of sample_every) and of the newest
-  // sample (-1: none); whether the counts are those of a run that succeeded
-  bool md_rdf_on = false;
-  ta_md_rdf_params md_rdf_p = {0.0, 0, 1};
-  DevBuf<unsigned long long> md_rdf_acc;
-  DevBuf<int32_t> md_rdf_blk;
-  int md_rdf_n_blk = 0, md_rdf_chunk = 0;
-  int64_t md_rdf_origin = 0, md_rdf_last = -1;
-  bool md_rdf_valid = false;
-  // Langevin (ta_md_set_langevin; off while md_friction == 0): bath, friction, the key of the noise; the
-  // steps integrated since ta_md_init (the noise's step counter) and the scratch of ta_md_noise
-  double md_lv_kT0 = 0.0, md_friction = 0.0;
-  uint64_t md_seed = 0;
-  int64_t md_step = 0;
-  DevBuf<double> md_noise;
-  // Berendsen barostat (ta_md_set_barostat; off while md_baro_on is false): the setting, the cumulative
-  // scale of every frame since its list was built with the ones that reset it, the device records
-  // {V, P_x, P_y, P_z} of the running ta_md_run and the host's copy of the last successful run's
-  bool md_baro_on = false;
-  bool md_baro_running = false;  // a barostat run is under way: a rebuild resets the cumulative scale
-  ta_md_barostat_params md_baro_p = {0.0, 0.0, 0.0, {1, 1, 1}, 1};
-  DevBuf<double> md_baro_scale, md_baro_rec;
-  std::vector<double> md_baro_ones;
-  bool md_rec_valid = false;
-  std::vector<double> md_rec_volume, md_rec_press;  // [n_rec][F], [n_rec][F][3]
-
-  // device-resident relaxation (ta_relax_init / ta_relax_run; the launches are in ta_relax.hip): FIRE
-  // velocities of its own, the mask of fixed atoms, the two copies of the per-frame state with the host's
-  // image of the current one, the workgroups' partial sums and the count of converged frames. The status
-  // words, md_ref and the workgroup layout are the MD loop's.
-  bool relax_valid = false;
-  ta_fire_params relax_p = {0.1, 1.0, 0.2, 1.1, 0.5, 0.1, 0.99, 5};
-  DevBuf<double> relax_vel, relax_part;
-  DevBuf<uint8_t> relax_fixed;
-  DevBuf<ta::RelaxFrameState> relax_state;
-  DevBuf<int> relax_count;
-  std::vector<ta::RelaxFrameState> relax_state_host;
-  // cell mode of the relaxation (ta_relax_set_cell): h0 and the cell factor of every frame, the deformation
-  // gradient and the cell velocity (two copies on the device like relax_state, the current one on the host
-  // between runs), the reference cells of the resident list next to md_ref
-  bool relax_cell_on = false;
-  bool cell_running = false;  // a run that moves the cells (cell relaxation, barostat) is under way: rebuilds take them from the device
-  ta_relax_cell_params relax_cell_p = {0.0, 0.0, {1, 1, 1, 1, 1, 1}, 0, 0};
-  DevBuf<double> relax_cell_h0, relax_cell_cf, relax_cell_G, relax_cell_vel, relax_cell_fmax2, md_ref_cells;
-  std::vector<double> relax_cell_G_host, relax_cell_vel_host;
-  // band mode of the relaxation (ta_relax_set_band; the band launches are in ta_neb.hip): the frames are the
-  // images of a nudged elastic band and FIRE runs on the band forces with the whole band as ONE pseudo-frame.
-  // The band owns its force and tangent arrays, the partials of its two launches, the mask (the user's OR-ed
-  // with the two endpoint images), the two copies of the one FIRE record and the pseudo-frame's layout
-  // {atom_start[2], blk_start[2], climbing image}.
-  bool relax_band_on = false;
-  bool relax_band_ran = false;  // a band run left B, tau and the climbing image of the resident state
-  ta_band_params relax_band_p = {0.1, 0, 0};
-  std::vector<uint8_t> relax_fixed_host;  // the mask of ta_relax_init
-  DevBuf<double> band_force, band_tau, band_part;
-  DevBuf<uint8_t> band_fixed;
-  DevBuf<ta::RelaxFrameState> band_state;
-  DevBuf<int32_t> band_layout;
-  ta::RelaxFrameState band_state_host = {};
-  std::vector<double> band_energy_host;  // [F] image energies of the state the last band run ended on
-
-  hipEvent_t ev[2 * TA_N_KERNEL_SLOTS + 2] = {nullptr};
-  std::string err;
-};
-
-namespace {
-
-int fail(ta_context *h, int code, const std::string &msg) {
+int ta::host::fail(ta_context *h, int code, const std::string &msg) {
   if (h)
     h->err = msg;
   else
     g_create_error = msg;
   return code;
 }
+
+namespace {
 
 // temperature-dependent models have no analytic Hessian-vector products
 std::string td_inference_only(const char *fn) {
@@ -983,7 +608,9 @@ void forward_v2_launches(ta_context *h, bool tri) {
   h->full_jobs_valid = !unread;
 }
 
-void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
+}  // namespace
+
+void ta::host::compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
   using namespace ta;
 #ifdef TA_PHASE_STAMPS
   if (h->db.n_blk > 0) {
@@ -1028,7 +655,7 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
     // triangle-once backward pass: the forward launches also leave the owned job lists
     // (while cells relax or follow a barostat, a list stays valid until a width has shrunk by
     // rmax / (rmax + skin): the wider test)
-    const bool tri_cells = (h->relax_cell_on || h->md_baro_on) ? h->tri_cells_wide_ok : h->tri_cells_ok;
+    const bool tri_cells = (h->relax.cell.on || h->md.baro.on) ? h->tri_cells_wide_ok : h->tri_cells_ok;
     const bool tri = h->use_v2 && h->triangles && tri_cells && h->n_elements == 1 && need_forces;
     h->db.job_word_own = (tri && h->db.job_count) ? h->job_word_own.ptr : nullptr;
     h->db.job_count_own = (tri && h->db.job_count) ? h->job_count_own.ptr : nullptr;
@@ -1143,27 +770,6 @@ void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms) {
   }
 }
 
-template <typename F>
-int guarded(ta_context *h, F &&fn) {
-  try {
-    if (h) HIP_CHECK(hipSetDevice(h->device));
-    fn();
-    return TA_OK;
-  } catch (const HipError &e) {
-    return fail(h, TA_ERR_HIP, e.what());
-  } catch (const std::domain_error &e) {
-    return fail(h, TA_ERR_UNSUPPORTED, e.what());
-  } catch (const std::invalid_argument &e) {
-    return fail(h, TA_ERR_INVALID, e.what());
-  } catch (const std::bad_alloc &) {
-    return fail(h, TA_ERR_NOMEM, "host allocation failed");
-  } catch (const std::exception &e) {
-    return fail(h, TA_ERR_INVALID, e.what());
-  }
-}
-
-}  // namespace
-
 extern "C" {
 
 int ta_abi_version(void) { return TA_ABI_VERSION; }
@@ -1245,49 +851,6 @@ int ta_destroy(ta_handle h) {
   for (void *p : h->model_allocs) (void)hipFree(p);
   if (h->eam) ta::eam_destroy(h->eam);
   if (h->grap) ta::grap_destroy(h->grap);
-  h->stage_in.release(); h->stage_out.release(); h->inbuf.release(); h->results.release();
-  h->rec.release(); h->part4.release(); h->G.release();
-  h->dEdG.release(); h->g.release(); h->wat.release(); h->bpart.release(); h->fown.release();
-  h->benergy.release(); h->mlp_scratch.release();
-  h->train_scratch.release(); h->train_partial.release(); h->train_grad.release(); h->train_coeff.release();
-  h->jvp_J.release(); h->tan_dD.release(); h->tan_dG.release(); h->tan_dir.release();
-  h->pair_start.release(); h->seg_start.release(); h->pair_i.release(); h->pair_j.release();
-  h->pair_shift.release(); h->pair_rev.release();
-  for (auto *b : {&h->ex_pair_i, &h->ex_pair_j, &h->ex_pair_shift, &h->ex_pair_rev, &h->ex_pair_start, &h->ex_pair_stop,
-                  &h->ex_seg_start, &h->ex_counts, &h->ex_map, &h->ex_blk, &h->ex_slot_q})
-    b->release();
-  h->ex_hdr.release();
-  h->masks.release(); h->job_word.release(); h->job_count.release();
-  h->job_word_own.release(); h->job_count_own.release();
-  for (auto *b : {&h->nl_wrap, &h->nl_binid, &h->nl_bin_count, &h->nl_bin_start, &h->nl_bin_cursor,
-                  &h->nl_bin_atoms, &h->nl_counts})
-    b->release();
-  h->nl_stats.release();
-  h->nl_zero.release();
-  h->hvp_buf.release();
-  h->filt_scratch.release();
-  h->nl_recs.release();
-  for (auto *b : {&h->md_mass, &h->md_vel, &h->md_ref, &h->md_epot, &h->md_ke, &h->md_noise, &h->md_nhc_eta,
-                  &h->md_nhc_veta, &h->md_nhc_rec, &h->md_ring_x, &h->md_ring_v, &h->md_corr_acc, &h->md_corr_part})
-    b->release();
-  h->md_corr_blk.release();
-  h->md_rdf_acc.release();
-  h->md_rdf_blk.release();
-  h->md_blk_start.release();
-  h->md_status.release();
-  h->md_status_host.release();
-  h->relax_vel.release();
-  h->relax_part.release();
-  h->relax_fixed.release();
-  h->relax_state.release();
-  h->relax_count.release();
-  for (auto *b : {&h->band_force, &h->band_tau, &h->band_part}) b->release();
-  h->band_fixed.release();
-  h->band_state.release();
-  h->band_layout.release();
-  for (auto *b : {&h->relax_cell_h0, &h->relax_cell_cf, &h->relax_cell_G, &h->relax_cell_vel, &h->relax_cell_fmax2,
-                  &h->md_ref_cells})
-    b->release();
   for (auto &e : h->ev)
     if (e) (void)hipEventDestroy(e);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -1327,8 +890,9 @@ bool filter_applies(const ta_context *h) {
   if (h->kind == TA_MODEL_EAM_ALLOY || h->kind == TA_MODEL_EAM_FS) return ta::eam_is_plain(h->eam);
   return false;
 }
+}  // namespace
 
-void apply_filter(ta_context *h) {
+void ta::host::apply_filter(ta_context *h) {
   using namespace ta;
   const size_t N = (size_t)h->hp.n_atoms, P = (size_t)h->hp.n_pairs;
   const int nel = h->n_elements;
@@ -1375,6 +939,7 @@ void apply_filter(ta_context *h) {
   h->filtered = true;
 }
 
+namespace {
 // The triangle-once backward pass needs the three vertices of every triangle to be distinct atoms. Two
 // images of one atom are a lattice vector L apart, and |L| is at least the smallest perpendicular width of
 // the cell over the periodic axes (some component n_k of L is non-zero, and the projection of L on the
@@ -1641,9 +1206,9 @@ void set_frames_impl(ta_context *h, int32_t n_frames, const ta_frame *frames, ta
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   }
 }
-// the resident frames again with new coordinates (cells: null = unchanged): the rebuild path of
-// ta_update_positions and ta_md_run; throws
-void rebuild_list(ta_context *h, const double *positions, const double *cells) {
+}  // namespace
+
+void ta::host::rebuild_list(ta_context *h, const double *positions, const double *cells) {
   const size_t F = h->keep_natoms.size();
   std::vector<ta_frame> frames(F);
   const std::vector<int32_t> species(h->keep_species), pbc(h->keep_pbc), natoms(h->keep_natoms);
@@ -1659,17 +1224,16 @@ void rebuild_list(ta_context *h, const double *positions, const double *cells) {
   }
   set_frames_impl(h, (int32_t)F, frames.data(), nullptr);
 }
-}  // namespace
 
 extern "C" {
 
 int ta_set_frames(ta_handle h, int32_t n_frames, const ta_frame *frames, ta_batch_info *info) {
   if (!h) return TA_ERR_INVALID;
   if (n_frames < 0 || (n_frames > 0 && !frames)) return fail(h, TA_ERR_INVALID, "bad frames argument");
-  h->md_valid = false;  // masses and velocities belong to the batch that leaves
-  h->relax_valid = false;
-  h->relax_cell_on = false;
-  h->relax_band_on = h->relax_band_ran = false;
+  h->md.valid = false;  // masses and velocities belong to the batch that leaves
+  h->relax.valid = false;
+  h->relax.cell.on = false;
+  h->relax.band.on = h->relax.band.ran = false;
   return guarded(h, [&]() {
     set_frames_impl(h, n_frames, frames, info);
     if (h->td)  // every frame starts at T = 0, the reference's default (universal.py:295)
@@ -1780,12 +1344,10 @@ int ta_update_positions(ta_handle h, const double *positions, const double *cell
       return;
     }
     rebuild_list(h, positions, cells);
-    if (cells && h->relax_cell_on && h->relax_valid && F) {
+    if (cells && h->relax.cell.on && h->relax.valid && F) {
       // the caller's cells replace the relaxed ones: they are h0 from here on, G = I, the cell velocities 0
-      HIP_CHECK(hipMemcpy(h->relax_cell_h0.ptr, h->ref_cells.data(), 9 * F * sizeof(double), hipMemcpyHostToDevice));
-      h->relax_cell_G_host.assign(9 * F, 0.0);
-      for (size_t f = 0; f < F; ++f) h->relax_cell_G_host[9 * f] = h->relax_cell_G_host[9 * f + 4] = h->relax_cell_G_host[9 * f + 8] = 1.0;
-      h->relax_cell_vel_host.assign(9 * F, 0.0);
+      HIP_CHECK(hipMemcpy(h->relax.cell.h0.ptr, h->ref_cells.data(), 9 * F * sizeof(double), hipMemcpyHostToDevice));
+      h->relax.cell.reset_deformation(F);
     }
   });
 }
@@ -1907,1328 +1469,6 @@ int ta_step_view(ta_handle h, const double *positions, const double *cells, uint
   h->mirror_next = false;
   if (rc != TA_OK) return rc;
   return ta_view_results(h, want, energy, forces, virial, atomic);
-}
-
-namespace {
-// workgroups of the integrator launch: `chunk` consecutive atoms of one frame each, at least one per frame
-void md_plan_blocks(ta_context *h, int chunk) {
-  if (chunk == h->md_chunk && !h->md_blk_start_host.empty()) return;
-  const size_t F = h->keep_natoms.size();
-  std::vector<int32_t> &start = h->md_blk_start_host;
-  start.assign(F + 1, 0);
-  for (size_t f = 0; f < F; ++f)
-    start[f + 1] = start[f] + std::max(1, (h->keep_natoms[f] + chunk - 1) / chunk);
-  h->md_blk_start.ensure(F + 1);
-  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches read the old layout)
-  HIP_CHECK(hipMemcpy(h->md_blk_start.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-  h->md_chunk = chunk;
-  h->md_n_blk = start[F];
-}
-
-// frees what sampling holds on the device; the setting stays
-void md_sampling_release(ta_context *h) {
-  for (auto *b : {&h->md_ring_x, &h->md_ring_v, &h->md_corr_acc, &h->md_corr_part}) b->release();
-  h->md_corr_blk.release();
-  h->md_corr_chunks = 0;
-  h->md_samp_valid = false;
-  h->md_samp_last = -1;
-}
-
-// exactly n elements (the ring may take gigabytes: no head room); false when the device has no room
-extern "C++" template <typename T>
-bool md_alloc_exact(DevBuf<T> &b, size_t n) {
-  b.release();
-  T *fresh = nullptr;
-  if (hipMalloc((void **)&fresh, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  b.ptr = fresh;
-  b.cap = std::max<size_t>(n, 1);
-  return true;
-}
-
-// Rings, zeroed accumulators and the correlation launch's chunk layout for the resident batch under setting
-// `p`, with no sample held: sample 0 will be the first multiple of sample_every at or behind the steps
-// integrated so far. False when the device has no room (everything is released then); throws otherwise.
-bool md_sampling_alloc(ta_context *h, const ta_md_sampling_params &p) {
-  const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
-  const size_t L = (size_t)p.n_lags, E = (size_t)h->n_elements;
-  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches read the old buffers)
-  md_sampling_release(h);
-  std::vector<int32_t> start(F + 1, 0);
-  for (size_t f = 0; f < F; ++f)
-    start[f + 1] = start[f] + std::max(1, (3 * h->keep_natoms[f] + ta::kMdCorrChunk - 1) / ta::kMdCorrChunk);
-  const size_t n_chunks = (size_t)start[F], n_acc = 2 * F * E * L;
-  if (!md_alloc_exact(h->md_ring_x, L * 3 * N) || !md_alloc_exact(h->md_ring_v, L * 3 * N) ||
-      !md_alloc_exact(h->md_corr_acc, n_acc) || !md_alloc_exact(h->md_corr_part, n_chunks * 2 * E * L) ||
-      !md_alloc_exact(h->md_corr_blk, F + 1)) {
-    md_sampling_release(h);
-    return false;
-  }
-  HIP_CHECK(hipMemset(h->md_corr_acc.ptr, 0, std::max<size_t>(n_acc, 1) * sizeof(double)));
-  HIP_CHECK(hipMemcpy(h->md_corr_blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-  h->md_corr_chunks = (int)n_chunks;
-  const int64_t s = p.sample_every;
-  h->md_samp_origin = (h->md_step + s - 1) / s * s;
-  h->md_samp_last = -1;
-  h->md_samp_valid = true;
-  return true;
-}
-
-// frees what the pair distributions hold on the device; the setting stays
-void md_rdf_release(ta_context *h) {
-  h->md_rdf_acc.release();
-  h->md_rdf_blk.release();
-  h->md_rdf_n_blk = 0;
-  h->md_rdf_valid = false;
-  h->md_rdf_last = -1;
-}
-
-// Zeroed counts and the launch's workgroup layout for the resident batch under setting `p`, with no sample
-// taken: sample 0 will be the first multiple of sample_every at or behind the steps integrated so far. False
-// when the device has no room (everything is released then); throws otherwise.
-bool md_rdf_alloc(ta_context *h, const ta_md_rdf_params &p) {
-  const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
-  const size_t E = (size_t)h->n_elements, n_acc = F * E * E * (size_t)p.n_bins;
-  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches add to the old buffer)
-  md_rdf_release(h);
-  const int chunk = ta::md_rdf_chunk((long long)N);
-  std::vector<int32_t> start(F + 1, 0);
-  for (size_t f = 0; f < F; ++f) start[f + 1] = start[f] + std::max(1, (h->keep_natoms[f] + chunk - 1) / chunk);
-  if (!md_alloc_exact(h->md_rdf_acc, n_acc) || !md_alloc_exact(h->md_rdf_blk, F + 1)) {
-    md_rdf_release(h);
-    return false;
-  }
-  HIP_CHECK(hipMemset(h->md_rdf_acc.ptr, 0, std::max<size_t>(n_acc, 1) * sizeof(unsigned long long)));
-  HIP_CHECK(hipMemcpy(h->md_rdf_blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-  h->md_rdf_n_blk = (int)start[F];
-  h->md_rdf_chunk = chunk;
-  const int64_t s = p.sample_every;
-  h->md_rdf_origin = (h->md_step + s - 1) / s * s;
-  h->md_rdf_last = -1;
-  h->md_rdf_valid = true;
-  return true;
-}
-
-// The loop that ta_md_run and ta_relax_run share. `enqueue(q)` puts the launches of step q on the stream
-// (they are predicated on the status word and test the skin / 2 rule after their drift); this loop follows
-// each with the exact list of the step and an evaluation, looks at the page-locked status word every
-// kMdLookahead steps, and where a drift left the list stale rebuilds it from the device's positions and
-// goes on behind that step. After a look that found the list valid, `finished(k, k_end)` may name the step
-// in [k, k_end) from which on the launches moved nothing (-1: none): the loop ends there. Returns the
-// steps done; F of the state at entry must be resident. `*rebuilds` counts the lists built, `*n_rebuilds`
-// (may be null) follows it so that a run that fails reports what it did. Throws.
-extern "C++" template <class Enqueue, class Finished>
-int resident_steps(ta_context *h, const char *who, int n_steps, uint32_t want, Enqueue &&enqueue,
-                   Finished &&finished, int *rebuilds, int32_t *n_rebuilds) {
-  const size_t N = h->keep_species.size();
-  hipStream_t s = h->stream;
-  volatile unsigned *status_host = reinterpret_cast<volatile unsigned *>(h->md_status_host.ptr);
-  const int look = h->skin > 0.0 ? ta::kMdLookahead : 1;
-  std::vector<double> x, cells;
-  const size_t F = h->keep_natoms.size();
-  int k = 0;
-  while (k < n_steps) {
-    // steps k .. k_end - 1 without a look at the device: integrator, exact list of the step, evaluation
-    const int k_end = (int)std::min<int64_t>(n_steps, (int64_t)k + look);
-    for (int q = k; q < k_end; ++q) {
-      enqueue(q);
-      if (h->filtered) apply_filter(h);
-      compute_impl(h, want, false, nullptr);
-    }
-    wait_stream(s, h->opt);
-    h->upload_pending = false;
-    const unsigned mark = status_host[0];
-    if (mark == 0u) {
-      const int fin = finished(k, k_end);
-      if (fin >= 0) {
-        h->n_list_reuses += fin - k;
-        return fin;
-      }
-      h->n_list_reuses += k_end - k;
-      k = k_end;
-      continue;
-    }
-    // the drift of step q left the list stale: the launches behind it did nothing, the evaluations
-    // behind it ran on the stale list and are overwritten now
-    const int q = (int)mark - 1;
-    if (q < k || q >= k_end) throw std::runtime_error(std::string(who) + ": inconsistent status word");
-    h->n_list_reuses += q - k;
-    x.resize(3 * N);
-    if (N) HIP_CHECK(hipMemcpy(x.data(), h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
-    if (h->cell_running) {  // the cells moved on the device: ref_cells are those of the stale list
-      cells.resize(9 * F);
-      if (F) HIP_CHECK(hipMemcpy(cells.data(), h->db.cells, 9 * F * sizeof(double), hipMemcpyDeviceToHost));
-      if (h->md_baro_running) {  // a scale factor that was no finite number > 0 left NaNs in its frame's cell
-        for (size_t f = 0; f < F; ++f) {
-          bool ok = true;
-          for (int c = 0; c < 9; ++c) ok = ok && std::isfinite(cells[9 * f + c]);
-          if (!ok) {
-            h->have_batch = false;  // (positions and cells of the frame are lost)
-            h->md_valid = false;
-            throw std::invalid_argument(std::string(who) + ": the barostat's scale factor of frame " + std::to_string(f) +
-                                        " at step " + std::to_string(q + 1) + " is not a finite number > 0");
-          }
-        }
-      }
-    }
-    status_host[0] = 0u;
-    HIP_CHECK(hipMemsetAsync(h->md_status.ptr, 0, 2 * sizeof(unsigned), s));
-    try {
-      rebuild_list(h, x.data(), h->cell_running ? cells.data() : nullptr);
-    } catch (const HipError &e) {
-      throw HipError(std::string(who) + ": list rebuild after step " + std::to_string(q + 1) + " failed: " + e.what());
-    } catch (const std::exception &e) {
-      throw std::runtime_error(std::string(who) + ": list rebuild after step " + std::to_string(q + 1) +
-                               " failed: " + e.what());
-    }
-    if (N) HIP_CHECK(hipMemcpyAsync(h->md_ref.ptr, h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToDevice, s));
-    if (h->cell_running && F) {
-      if (h->md_baro_running)  // the barostat keeps the scale since the build, not the list's cells
-        HIP_CHECK(hipMemcpyAsync(h->md_baro_scale.ptr, h->md_baro_ones.data(), 3 * F * sizeof(double), hipMemcpyHostToDevice, s));
-      else
-        HIP_CHECK(hipMemcpyAsync(h->md_ref_cells.ptr, h->db.cells, 9 * F * sizeof(double), hipMemcpyDeviceToDevice, s));
-    }
-    h->md_ref_builds = h->n_list_builds;
-    compute_impl(h, want, false, nullptr);
-    ++*rebuilds;
-    if (n_rebuilds) *n_rebuilds = *rebuilds;
-    k = q + 1;
-  }
-  return n_steps;
-}
-}  // namespace
-
-int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
-  if (!h || !masses) return fail(h, TA_ERR_INVALID, "ta_md_init: null argument");
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_init: no resident batch");
-  const size_t N = h->keep_species.size();
-  for (size_t i = 0; i < N; ++i)
-    if (!(masses[i] > 0.0) || !std::isfinite(masses[i]))
-      return fail(h, TA_ERR_INVALID, "ta_md_init: mass of atom " + std::to_string(i) + " is not a finite number > 0");
-  if (velocities)
-    for (size_t i = 0; i < 3 * N; ++i)
-      if (!std::isfinite(velocities[i])) return fail(h, TA_ERR_INVALID, "ta_md_init: non-finite velocity");
-  bool ring_nomem = false, rdf_nomem = false;
-  const int rc = guarded(h, [&]() {
-    h->md_valid = false;
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    h->upload_pending = false;
-    h->md_mass.ensure(N + 1);
-    h->md_vel.ensure(3 * N + 1);
-    h->md_ref.ensure(3 * N + 1);
-    h->md_status.ensure(2);
-    h->md_status_host.ensure(64);
-    const size_t n_chain = h->keep_natoms.size() * ta::kMdMaxChain;  // every frame's chain starts at rest
-    h->md_nhc_eta.ensure(n_chain + 1);
-    h->md_nhc_veta.ensure(n_chain + 1);
-    HIP_CHECK(hipMemset(h->md_nhc_eta.ptr, 0, (n_chain + 1) * sizeof(double)));
-    HIP_CHECK(hipMemset(h->md_nhc_veta.ptr, 0, (n_chain + 1) * sizeof(double)));
-    h->md_nhc_rec_valid = false;
-    if (N) {
-      HIP_CHECK(hipMemcpy(h->md_mass.ptr, masses, N * sizeof(double), hipMemcpyHostToDevice));
-      if (velocities)
-        HIP_CHECK(hipMemcpy(h->md_vel.ptr, velocities, 3 * N * sizeof(double), hipMemcpyHostToDevice));
-      else
-        HIP_CHECK(hipMemset(h->md_vel.ptr, 0, 3 * N * sizeof(double)));
-    }
-    h->md_ref_builds = -1;  // ta_md_run uploads ref_pos
-    h->md_chunk = 0;
-    h->md_blk_start_host.clear();
-    h->md_step = 0;
-    h->md_rec_valid = false;
-    if (h->md_samp_on && !md_sampling_alloc(h, h->md_samp_p)) {  // an empty ring for this batch, or none
-      h->md_samp_on = false;
-      ring_nomem = true;
-    }
-    if (h->md_rdf_on && !md_rdf_alloc(h, h->md_rdf_p)) {  // zero counts for this batch, or none
-      h->md_rdf_on = false;
-      rdf_nomem = true;
-    }
-    h->md_valid = true;
-  });
-  if (rc == TA_OK && ring_nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the rings of ta_md_set_sampling; sampling is off");
-  if (rc == TA_OK && rdf_nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the counts of ta_md_set_rdf; the feature is off");
-  return rc;
-}
-
-int ta_md_set_thermostat(ta_handle h, double kT0, double tau) {
-  if (!h) return TA_ERR_INVALID;
-  if (std::isnan(kT0) || std::isinf(kT0)) return fail(h, TA_ERR_INVALID, "ta_md_set_thermostat: kT0 must be finite");
-  if (kT0 > 0.0 && (!(tau > 0.0) || !std::isfinite(tau)))
-    return fail(h, TA_ERR_INVALID, "ta_md_set_thermostat: tau must be a finite time > 0");
-  if (kT0 > 0.0 && h->md_friction > 0.0)
-    return fail(h, TA_ERR_INVALID, "ta_md_set_thermostat: the Langevin thermostat is on; switch it off "
-                                   "(ta_md_set_langevin with friction 0) before the Berendsen thermostat goes on");
-  if (kT0 > 0.0 && h->md_nhc_on)
-    return fail(h, TA_ERR_INVALID, "ta_md_set_thermostat: the Nose-Hoover chain thermostat is on; switch it off "
-                                   "(ta_md_set_nose_hoover with NULL) before the Berendsen thermostat goes on");
-  h->md_kT0 = kT0 > 0.0 ? kT0 : 0.0;
-  h->md_tau = kT0 > 0.0 ? tau : 0.0;
-  return TA_OK;
-}
-
-int ta_md_set_langevin(ta_handle h, double kT0, double friction, uint64_t seed) {
-  if (!h) return TA_ERR_INVALID;
-  if (!(friction >= 0.0) || !std::isfinite(friction))
-    return fail(h, TA_ERR_INVALID, "ta_md_set_langevin: friction must be a finite rate >= 0");
-  if (!(kT0 >= 0.0) || !std::isfinite(kT0))
-    return fail(h, TA_ERR_INVALID, "ta_md_set_langevin: kT0 must be finite and >= 0");
-  if (friction > 0.0 && h->md_kT0 > 0.0)
-    return fail(h, TA_ERR_INVALID, "ta_md_set_langevin: the Berendsen thermostat is on; switch it off "
-                                   "(ta_md_set_thermostat with kT0 0) before the Langevin thermostat goes on");
-  if (friction > 0.0 && h->md_nhc_on)
-    return fail(h, TA_ERR_INVALID, "ta_md_set_langevin: the Nose-Hoover chain thermostat is on; switch it off "
-                                   "(ta_md_set_nose_hoover with NULL) before the Langevin thermostat goes on");
-  h->md_friction = friction;
-  h->md_lv_kT0 = friction > 0.0 ? kT0 : 0.0;
-  h->md_seed = seed;
-  return TA_OK;
-}
-
-int ta_md_set_nose_hoover(ta_handle h, const ta_md_nhc_params *p) {
-  if (!h) return TA_ERR_INVALID;
-  if (p && std::isnan(p->kT0)) return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: kT0 must be finite");
-  if (!p || !(p->kT0 > 0.0)) {
-    h->md_nhc_on = false;
-    return TA_OK;
-  }
-  if (!std::isfinite(p->kT0)) return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: kT0 must be finite");
-  if (!(p->tau > 0.0) || !std::isfinite(p->tau))
-    return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: tau must be a finite time > 0");
-  if (p->chain < 1 || p->chain > TA_MD_MAX_CHAIN)
-    return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: chain must be 1 .. " + std::to_string(TA_MD_MAX_CHAIN));
-  if (p->loops < 1 || p->loops > 16) return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: loops must be 1 .. 16");
-  if (p->dof_removed < 0) return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: dof_removed must be >= 0");
-  if (h->md_kT0 > 0.0)
-    return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: the Berendsen thermostat is on; switch it off "
-                                   "(ta_md_set_thermostat with kT0 0) before the Nose-Hoover chain goes on");
-  if (h->md_friction > 0.0)
-    return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: the Langevin thermostat is on; switch it off "
-                                   "(ta_md_set_langevin with friction 0) before the Nose-Hoover chain goes on");
-  if (h->md_nhc_on && h->md_nhc_p.chain != p->chain && h->md_valid) {
-    // another chain length: the slots beyond the old one hold nothing, the chain starts again at rest
-    const size_t n_chain = h->keep_natoms.size() * ta::kMdMaxChain;
-    const int rc = guarded(h, [&]() {
-      HIP_CHECK(hipStreamSynchronize(h->stream));
-      HIP_CHECK(hipMemset(h->md_nhc_eta.ptr, 0, (n_chain + 1) * sizeof(double)));
-      HIP_CHECK(hipMemset(h->md_nhc_veta.ptr, 0, (n_chain + 1) * sizeof(double)));
-    });
-    if (rc != TA_OK) return rc;
-  }
-  h->md_nhc_p = *p;
-  h->md_nhc_on = true;
-  return TA_OK;
-}
-
-namespace {
-// what ta_md_get_chain and ta_md_set_chain need; returns 0 or the error code
-int md_chain_ready(ta_context *h, const char *who) {
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
-  if (!h->md_valid) return fail(h, TA_ERR_INVALID, std::string(who) + " called before ta_md_init");
-  if (!h->md_nhc_on)
-    return fail(h, TA_ERR_INVALID, std::string(who) + ": the Nose-Hoover chain thermostat is off (ta_md_set_nose_hoover)");
-  return TA_OK;
-}
-}  // namespace
-
-int ta_md_get_chain(ta_handle h, double *eta, double *veta) {
-  if (!h) return TA_ERR_INVALID;
-  if (const int rc = md_chain_ready(h, "ta_md_get_chain")) return rc;
-  return guarded(h, [&]() {
-    const size_t F = h->keep_natoms.size(), M = (size_t)h->md_nhc_p.chain;
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    std::vector<double> buf(F * ta::kMdMaxChain);
-    for (int w = 0; w < 2; ++w) {
-      double *out = w ? veta : eta;
-      if (!out || !F) continue;
-      HIP_CHECK(hipMemcpy(buf.data(), w ? h->md_nhc_veta.ptr : h->md_nhc_eta.ptr, buf.size() * sizeof(double),
-                          hipMemcpyDeviceToHost));
-      for (size_t f = 0; f < F; ++f)
-        for (size_t k = 0; k < M; ++k) out[f * M + k] = buf[f * ta::kMdMaxChain + k];
-    }
-  });
-}
-
-int ta_md_set_chain(ta_handle h, const double *eta, const double *veta) {
-  if (!h) return TA_ERR_INVALID;
-  if (const int rc = md_chain_ready(h, "ta_md_set_chain")) return rc;
-  const size_t F = h->keep_natoms.size(), M = (size_t)h->md_nhc_p.chain;
-  for (size_t j = 0; j < F * M; ++j) {
-    if (eta && !std::isfinite(eta[j])) return fail(h, TA_ERR_INVALID, "ta_md_set_chain: non-finite eta");
-    if (veta && !std::isfinite(veta[j])) return fail(h, TA_ERR_INVALID, "ta_md_set_chain: non-finite veta");
-  }
-  return guarded(h, [&]() {
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    std::vector<double> buf(F * ta::kMdMaxChain + 1);
-    for (int w = 0; w < 2; ++w) {
-      const double *in = w ? veta : eta;
-      std::fill(buf.begin(), buf.end(), 0.0);
-      if (in)
-        for (size_t f = 0; f < F; ++f)
-          for (size_t k = 0; k < M; ++k) buf[f * ta::kMdMaxChain + k] = in[f * M + k];
-      HIP_CHECK(hipMemcpy(w ? h->md_nhc_veta.ptr : h->md_nhc_eta.ptr, buf.data(), buf.size() * sizeof(double),
-                          hipMemcpyHostToDevice));
-    }
-  });
-}
-
-int ta_md_get_chain_records(ta_handle h, double *e_chain) {
-  if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_chain_records: no resident batch");
-  if (!h->md_valid) return fail(h, TA_ERR_INVALID, "ta_md_get_chain_records called before ta_md_init");
-  if (!h->md_nhc_rec_valid)
-    return fail(h, TA_ERR_INVALID, "ta_md_get_chain_records: the last ta_md_run of this batch had no Nose-Hoover chain");
-  if (e_chain && !h->md_rec_chain.empty())
-    std::memcpy(e_chain, h->md_rec_chain.data(), h->md_rec_chain.size() * sizeof(double));
-  return TA_OK;
-}
-
-int ta_md_set_sampling(ta_handle h, const ta_md_sampling_params *p) {
-  if (!h) return TA_ERR_INVALID;
-  if (!p || p->n_lags == 0) {
-    h->md_samp_on = false;
-    return guarded(h, [&]() {
-      HIP_CHECK(hipStreamSynchronize(h->stream));
-      md_sampling_release(h);
-    });
-  }
-  if (p->n_lags < 0 || p->n_lags > TA_MD_MAX_LAGS)
-    return fail(h, TA_ERR_INVALID, "ta_md_set_sampling: n_lags must be 0 .. " + std::to_string(TA_MD_MAX_LAGS));
-  if (p->sample_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_set_sampling: sample_every must be >= 1");
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_sampling: no resident batch");
-  if (!h->md_valid) return fail(h, TA_ERR_INVALID, "ta_md_set_sampling called before ta_md_init");
-  bool nomem = false;
-  const int rc = guarded(h, [&]() {
-    h->md_samp_on = false;  // (until the rings exist)
-    nomem = !md_sampling_alloc(h, *p);
-    if (!nomem) {
-      h->md_samp_p = *p;
-      h->md_samp_on = true;
-    }
-  });
-  if (rc == TA_OK && nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_set_sampling: no device memory for rings of n_lags = " + std::to_string(p->n_lags) +
-                                 " snapshots; sampling is off");
-  return rc;
-}
-
-namespace {
-// what the two getters of the sampled data need; returns 0 or the error code
-int md_samples_ready(ta_context *h, const char *who) {
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
-  if (!h->md_valid) return fail(h, TA_ERR_INVALID, std::string(who) + " called before ta_md_init");
-  if (!h->md_samp_on) return fail(h, TA_ERR_INVALID, std::string(who) + ": sampling is off (ta_md_set_sampling)");
-  if (!h->md_samp_valid)
-    return fail(h, TA_ERR_INVALID, std::string(who) + ": a ta_md_run failed and left the sampled data invalid; call "
-                                   "ta_md_set_sampling or ta_md_init again");
-  return TA_OK;
-}
-
-int64_t md_samples_taken(const ta_context *h) {
-  return h->md_samp_last < 0 ? 0 : (h->md_samp_last - h->md_samp_origin) / h->md_samp_p.sample_every + 1;
-}
-}  // namespace
-
-int ta_md_get_correlations(ta_handle h, double *vacf_sum, double *msd_sum, int64_t *info) {
-  if (!h) return TA_ERR_INVALID;
-  if (const int rc = md_samples_ready(h, "ta_md_get_correlations")) return rc;
-  return guarded(h, [&]() {
-    const size_t n = h->keep_natoms.size() * (size_t)h->n_elements * (size_t)h->md_samp_p.n_lags;
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    if (vacf_sum && n) HIP_CHECK(hipMemcpy(vacf_sum, h->md_corr_acc.ptr, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (msd_sum && n) HIP_CHECK(hipMemcpy(msd_sum, h->md_corr_acc.ptr + n, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (info) {
-      info[0] = md_samples_taken(h);
-      info[1] = h->md_samp_p.n_lags;
-      info[2] = h->md_samp_p.sample_every;
-      info[3] = h->md_samp_last;
-    }
-  });
-}
-
-int ta_md_get_samples(ta_handle h, int32_t first_lag, int32_t n, double *positions, double *velocities,
-                      int64_t *steps) {
-  if (!h) return TA_ERR_INVALID;
-  if (const int rc = md_samples_ready(h, "ta_md_get_samples")) return rc;
-  const int64_t taken = md_samples_taken(h), L = h->md_samp_p.n_lags, held = std::min(taken, L);
-  if (first_lag < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_samples: first_lag must be >= 0");
-  if (n < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_samples: n must be >= 0");
-  if ((int64_t)first_lag + n > held)
-    return fail(h, TA_ERR_INVALID, "ta_md_get_samples: first_lag + n = " + std::to_string((int64_t)first_lag + n) +
-                                   " exceeds the " + std::to_string(held) + " snapshots held (min(n_samples, n_lags))");
-  return guarded(h, [&]() {
-    const size_t row = 3 * h->keep_species.size();
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    for (int32_t j = 0; j < n; ++j) {
-      const int64_t idx = taken - 1 - first_lag - j;  // sample number
-      const size_t slot = (size_t)(idx % L);
-      if (positions && row)
-        HIP_CHECK(hipMemcpy(positions + (size_t)j * row, h->md_ring_x.ptr + slot * row, row * sizeof(double), hipMemcpyDeviceToHost));
-      if (velocities && row)
-        HIP_CHECK(hipMemcpy(velocities + (size_t)j * row, h->md_ring_v.ptr + slot * row, row * sizeof(double), hipMemcpyDeviceToHost));
-      if (steps) steps[j] = h->md_samp_origin + idx * h->md_samp_p.sample_every;
-    }
-  });
-}
-
-int ta_md_set_rdf(ta_handle h, const ta_md_rdf_params *p) {
-  if (!h) return TA_ERR_INVALID;
-  if (!p || p->n_bins == 0) {
-    h->md_rdf_on = false;
-    return guarded(h, [&]() {
-      HIP_CHECK(hipStreamSynchronize(h->stream));
-      md_rdf_release(h);
-    });
-  }
-  if (p->n_bins < 0 || p->n_bins > TA_MD_MAX_BINS)
-    return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: n_bins must be 0 .. " + std::to_string(TA_MD_MAX_BINS));
-  if (p->sample_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: sample_every must be >= 1");
-  if (!std::isfinite(p->r_max) || !(p->r_max > 0.0))
-    return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: r_max must be a finite distance > 0");
-  if (p->r_max > h->rmax)
-    return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: r_max = " + std::to_string(p->r_max) + " exceeds the model's cutoff max(rcut, acut) = " +
-                                   std::to_string(h->rmax) + "; the neighbour list is not complete beyond that");
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: no resident batch");
-  if (!h->md_valid) return fail(h, TA_ERR_INVALID, "ta_md_set_rdf called before ta_md_init");
-  bool nomem = false;
-  const int rc = guarded(h, [&]() {
-    h->md_rdf_on = false;  // (until the counts exist)
-    nomem = !md_rdf_alloc(h, *p);
-    if (!nomem) {
-      h->md_rdf_p = *p;
-      h->md_rdf_on = true;
-    }
-  });
-  if (rc == TA_OK && nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_set_rdf: no device memory for counts of n_bins = " + std::to_string(p->n_bins) +
-                                 "; the feature is off");
-  return rc;
-}
-
-int ta_md_get_rdf(ta_handle h, int64_t *counts, int64_t *info, double *r_max) {
-  if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_rdf: no resident batch");
-  if (!h->md_valid) return fail(h, TA_ERR_INVALID, "ta_md_get_rdf called before ta_md_init");
-  if (!h->md_rdf_on) return fail(h, TA_ERR_INVALID, "ta_md_get_rdf: the pair distributions are off (ta_md_set_rdf)");
-  if (!h->md_rdf_valid)
-    return fail(h, TA_ERR_INVALID, "ta_md_get_rdf: a ta_md_run failed and left the counts invalid; call ta_md_set_rdf or "
-                                   "ta_md_init again");
-  return guarded(h, [&]() {
-    const size_t E = (size_t)h->n_elements, n = h->keep_natoms.size() * E * E * (size_t)h->md_rdf_p.n_bins;
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the counts are copied as they are");
-    if (counts && n) HIP_CHECK(hipMemcpy(counts, h->md_rdf_acc.ptr, n * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (info) {
-      info[0] = h->md_rdf_last < 0 ? 0 : (h->md_rdf_last - h->md_rdf_origin) / h->md_rdf_p.sample_every + 1;
-      info[1] = h->md_rdf_p.n_bins;
-      info[2] = h->md_rdf_p.sample_every;
-      info[3] = h->md_rdf_last;
-    }
-    if (r_max) *r_max = h->md_rdf_p.r_max;
-  });
-}
-
-int ta_md_noise(ta_handle h, int64_t step, double *xi, double *eta) {
-  if (!h) return TA_ERR_INVALID;
-  if (!xi || !eta) return fail(h, TA_ERR_INVALID, "ta_md_noise: null argument");
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_noise: no resident batch");
-  if (!h->md_valid) return fail(h, TA_ERR_INVALID, "ta_md_noise called before ta_md_init");
-  if (step < 0) return fail(h, TA_ERR_INVALID, "ta_md_noise: step must be >= 0");
-  return guarded(h, [&]() {
-    const size_t N = h->keep_species.size();
-    if (!N) return;
-    h->md_noise.ensure(6 * N);
-    ta::launch_md_noise(h->md_seed, step, (long long)N, h->md_noise.ptr, h->md_noise.ptr + 3 * N, h->stream);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    HIP_CHECK(hipMemcpy(xi, h->md_noise.ptr, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(eta, h->md_noise.ptr + 3 * N, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
-  });
-}
-
-int ta_md_set_barostat(ta_handle h, const ta_md_barostat_params *p) {
-  if (!h) return TA_ERR_INVALID;
-  if (p && !std::isfinite(p->taup)) return fail(h, TA_ERR_INVALID, "ta_md_set_barostat: taup must be finite");
-  if (!p || !(p->taup > 0.0)) {
-    h->md_baro_on = false;
-    return TA_OK;
-  }
-  if (!std::isfinite(p->pressure)) return fail(h, TA_ERR_INVALID, "ta_md_set_barostat: pressure must be finite");
-  if (!std::isfinite(p->compressibility) || p->compressibility < 0.0)
-    return fail(h, TA_ERR_INVALID, "ta_md_set_barostat: compressibility must be finite and >= 0");
-  if (!p->isotropic && !p->mask[0] && !p->mask[1] && !p->mask[2])
-    return fail(h, TA_ERR_INVALID, "ta_md_set_barostat: mask leaves no axis of the cell free");
-  h->md_baro_p = *p;
-  h->md_baro_on = true;
-  return TA_OK;
-}
-
-int ta_md_get_cell(ta_handle h, double *cells) {
-  if (!h) return TA_ERR_INVALID;
-  if (!cells) return fail(h, TA_ERR_INVALID, "ta_md_get_cell: null argument");
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_cell: no resident batch");
-  // (between runs ref_cells is the image of the device's cells)
-  const size_t F = h->keep_natoms.size();
-  if (F) std::memcpy(cells, h->ref_cells.data(), 9 * F * sizeof(double));
-  return TA_OK;
-}
-
-int ta_md_get_records(ta_handle h, double *volume, double *press) {
-  if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_records: no resident batch");
-  if (!h->md_valid) return fail(h, TA_ERR_INVALID, "ta_md_get_records called before ta_md_init");
-  if (!h->md_rec_valid)
-    return fail(h, TA_ERR_INVALID, "ta_md_get_records: the last ta_md_run of this batch had no barostat");
-  if (volume && !h->md_rec_volume.empty())
-    std::memcpy(volume, h->md_rec_volume.data(), h->md_rec_volume.size() * sizeof(double));
-  if (press && !h->md_rec_press.empty())
-    std::memcpy(press, h->md_rec_press.data(), h->md_rec_press.size() * sizeof(double));
-  return TA_OK;
-}
-
-int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t record_every, double *epot,
-              double *ekin, int32_t *n_rebuilds) {
-  if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_run: no resident batch");
-  if (!h->md_valid) return fail(h, TA_ERR_INVALID, "ta_md_run called before ta_md_init (ta_set_frames drops the MD state)");
-  if (n_steps < 0 || record_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_run: n_steps >= 0 and record_every >= 1 are needed");
-  if (!std::isfinite(dt)) return fail(h, TA_ERR_INVALID, "ta_md_run: dt must be finite");
-  if (h->md_friction > 0.0 && dt < 0.0) return fail(h, TA_ERR_INVALID, "ta_md_run: Langevin dynamics needs dt >= 0");
-  const bool baro = h->md_baro_on;
-  if (baro) {
-    const size_t F = h->keep_natoms.size();
-    for (size_t f = 0; f < F; ++f) {
-      for (int k = 0; k < 3; ++k)
-        if (!h->keep_pbc[3 * f + k])
-          return fail(h, TA_ERR_INVALID, "ta_md_run: the barostat is on and frame " + std::to_string(f) +
-                                         " is not periodic along all three axes");
-      const double *c = h->ref_cells.data() + 9 * f;
-      const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
-      if (!std::isfinite(det) || !(std::fabs(det) > 0.0))
-        return fail(h, TA_ERR_INVALID, "ta_md_run: the barostat is on and the cell of frame " + std::to_string(f) + " is singular");
-    }
-  }
-  const bool nhc = h->md_nhc_on;
-  if (nhc) {
-    const size_t F = h->keep_natoms.size();
-    for (size_t f = 0; f < F; ++f)
-      if (3 * (int64_t)h->keep_natoms[f] - (int64_t)h->md_nhc_p.dof_removed < 1)
-        return fail(h, TA_ERR_INVALID, "ta_md_run: the Nose-Hoover chain is on and frame " + std::to_string(f) +
-                                       " has fewer than one degree of freedom (3 n_atoms - dof_removed)");
-  }
-  const bool samp = h->md_samp_on;
-  if (samp && baro)
-    return fail(h, TA_ERR_INVALID, "ta_md_run: sampling (ta_md_set_sampling) and the barostat (ta_md_set_barostat) are both "
-                                   "on; displacements in a moving cell are not defined: switch one of them off");
-  const bool rdf = h->md_rdf_on;
-  if (rdf && baro)
-    return fail(h, TA_ERR_INVALID, "ta_md_run: the pair distributions (ta_md_set_rdf) and the barostat (ta_md_set_barostat) are "
-                                   "both on; normalising the counts needs one volume: switch one of them off");
-  if (n_rebuilds) *n_rebuilds = 0;
-  want |= TA_WANT_ENERGY | TA_WANT_FORCES;
-  want &= ~(uint32_t)TA_WANT_REUSE_DESCRIPTORS;
-  if (baro) want |= TA_WANT_VIRIAL;  // the pressure
-  h->md_rec_valid = false;
-  h->md_nhc_rec_valid = false;
-  const bool samp_was_valid = h->md_samp_valid;
-  h->md_samp_valid = false;  // (until this run has succeeded)
-  const bool rdf_was_valid = h->md_rdf_valid;
-  h->md_rdf_valid = false;
-  h->cell_running = h->md_baro_running = baro;
-  const int rc = guarded(h, [&]() {
-    const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
-    hipStream_t s = h->stream;
-    const bool thermostat = h->md_kT0 > 0.0, langevin = h->md_friction > 0.0;  // (never both)
-    // with Berendsen scaling one workgroup owns a whole frame: the factor needs the frame's kinetic energy
-    // (the barostat: the frame's three sums of m v_c^2; the Nose-Hoover chain: the kinetic energy again)
-    int chunk = ta::kMdChunk;
-    if (thermostat || baro || nhc)
-      for (size_t f = 0; f < F; ++f) chunk = std::max(chunk, h->keep_natoms[f]);
-    const int threads = (thermostat || baro || nhc) ? 1024 : 256;
-    md_plan_blocks(h, chunk);
-    const size_t n_blk = (size_t)h->md_n_blk, n_rec = (size_t)(n_steps / record_every) + 1;
-    h->md_epot.ensure(n_rec * F + 1);
-    h->md_ke.ensure(n_rec * n_blk + 1);
-    if (nhc) h->md_nhc_rec.ensure(n_rec * F + 1);
-    const std::vector<double> cells_at_entry(baro ? h->ref_cells : std::vector<double>());
-    if (baro) {  // every run starts on a list built for the resident cells: the cumulative scale is 1
-      h->md_baro_rec.ensure(4 * n_rec * F + 1);
-      h->md_baro_scale.ensure(3 * F + 1);
-      h->md_baro_ones.assign(3 * F, 1.0);
-      HIP_CHECK(hipStreamSynchronize(s));
-      if (F) HIP_CHECK(hipMemcpy(h->md_baro_scale.ptr, h->md_baro_ones.data(), 3 * F * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (h->md_ref_builds != h->n_list_builds) {  // the host built the list that is resident: its positions go up once
-      HIP_CHECK(hipStreamSynchronize(s));
-      if (N) HIP_CHECK(hipMemcpy(h->md_ref.ptr, h->ref_pos.data(), 3 * N * sizeof(double), hipMemcpyHostToDevice));
-      h->md_ref_builds = h->n_list_builds;
-    }
-    volatile unsigned *status_host = reinterpret_cast<volatile unsigned *>(h->md_status_host.ptr);
-    status_host[0] = 0u;  // (no launch that writes it is in flight: every run ends with a wait)
-    HIP_CHECK(hipMemsetAsync(h->md_status.ptr, 0, 2 * sizeof(unsigned), s));
-
-    ta::MdLaunch a;
-    a.vel = h->md_vel.ptr;
-    a.mass = h->md_mass.ptr;
-    a.ref = h->md_ref.ptr;
-    a.blk_start = h->md_blk_start.ptr;
-    a.epot = h->md_epot.ptr;
-    a.ke_part = h->md_ke.ptr;
-    a.status = h->md_status.ptr;
-    a.status_host = const_cast<unsigned *>(status_host);
-    a.dt = dt;
-    a.kT0 = langevin ? h->md_lv_kT0 : h->md_kT0;
-    a.dt_over_tau = thermostat ? dt / h->md_tau : 0.0;
-    a.langevin = langevin ? 1 : 0;
-    a.seed = h->md_seed;
-    a.c1 = a.c2 = a.c3 = a.c4 = a.c5 = 0.0;
-    if (langevin) {  // ASE's Langevin.updatevars with sigma_i = sqrt(2 kT0 fr) / sqrt(m_i)
-      const double fr = h->md_friction, sigma = std::sqrt(2.0 * h->md_lv_kT0 * fr);
-      a.c1 = dt / 2.0 - dt * dt * fr / 8.0;
-      a.c2 = dt * fr / 2.0 - dt * dt * fr * fr / 8.0;
-      a.c3 = std::sqrt(dt) * sigma / 2.0 - std::pow(dt, 1.5) * fr * sigma / 8.0;
-      a.c5 = std::pow(dt, 1.5) * sigma / (2.0 * std::sqrt(3.0));
-      a.c4 = fr / 2.0 * a.c5;
-    }
-    const int64_t step0 = h->md_step;  // absolute index of this run's first step
-    a.lim2 = h->skin > 0.0 ? 0.25 * h->skin * h->skin : -1.0;  // skin = 0: every step rebuilds
-    a.n_frames = (int)F;
-    a.n_blk = (int)n_blk;
-    a.chunk = chunk;
-    a.baro = baro ? 1 : 0;
-    a.baro_iso = h->md_baro_p.isotropic ? 1 : 0;
-    a.cells = nullptr, a.virial = nullptr;
-    a.baro_scale = h->md_baro_scale.ptr;
-    a.baro_rec = h->md_baro_rec.ptr;
-    a.baro_p0 = h->md_baro_p.pressure;
-    a.baro_k = baro ? dt / h->md_baro_p.taup * h->md_baro_p.compressibility / 3.0 : 0.0;
-    for (int c = 0; c < 3; ++c) a.baro_mask[c] = h->md_baro_p.mask[c] ? 1 : 0;
-    a.skin = h->skin;
-    a.r_list = h->rmax + h->skin;
-    a.nhc = nhc ? 1 : 0;
-    a.nhc_chain = h->md_nhc_p.chain, a.nhc_loops = h->md_nhc_p.loops, a.nhc_dof = h->md_nhc_p.dof_removed;
-    a.nhc_kT0 = nhc ? h->md_nhc_p.kT0 : 0.0;
-    a.nhc_q = nhc ? h->md_nhc_p.kT0 * h->md_nhc_p.tau * h->md_nhc_p.tau : 0.0;
-    a.nhc_eta = h->md_nhc_eta.ptr, a.nhc_veta = h->md_nhc_veta.ptr, a.nhc_rec = h->md_nhc_rec.ptr;
-    // Sampling: the launch of step k holds the whole-step state t = step0 + k. It samples when t is a multiple
-    // of sample_every at or behind sample 0, except launch 0 where the last launch of the run before sampled
-    // that very state. Sample number and ring slot are functions of t alone, so the launches that returned
-    // early behind a stale list and are enqueued again after the rebuild write what they would have written.
-    const bool sampling = samp && samp_was_valid && N > 0;
-    const int64_t samp_s = h->md_samp_p.sample_every, samp_L = h->md_samp_p.n_lags;
-    const int64_t samp_origin = h->md_samp_origin, samp_last = h->md_samp_last;
-    ta::MdCorrLaunch c;
-    c.ring_x = h->md_ring_x.ptr, c.ring_v = h->md_ring_v.ptr;
-    c.blk_start = h->md_corr_blk.ptr;
-    c.part = h->md_corr_part.ptr;
-    c.acc_v = h->md_corr_acc.ptr;
-    c.acc_x = sampling ? h->md_corr_acc.ptr + F * (size_t)h->n_elements * (size_t)samp_L : nullptr;
-    c.status = h->md_status.ptr;
-    c.n_atoms = (long long)N;
-    c.n_lags = (int)samp_L, c.n_elements = h->n_elements, c.n_frames = (int)F, c.n_chunks = h->md_corr_chunks;
-    // Pair distributions: the state t = step0 + k is counted by a launch IN FRONT OF the integrator launch of
-    // step k, whose drift leaves x(t). With seq = k the integrator's predicate skips exactly the states that
-    // were reached on a stale list; after the rebuild the launch is enqueued again with the rest and counts
-    // then. Launch 0 does not count the state the last launch of the run before counted.
-    const bool rdf_run = rdf && rdf_was_valid && N > 0;
-    const int64_t rdf_s = h->md_rdf_p.sample_every, rdf_origin = h->md_rdf_origin, rdf_last = h->md_rdf_last;
-    ta::MdRdfLaunch g;
-    g.blk_start = h->md_rdf_blk.ptr;
-    g.counts = h->md_rdf_acc.ptr;
-    g.status = h->md_status.ptr;
-    g.n_bins = h->md_rdf_p.n_bins, g.n_elements = h->n_elements, g.n_frames = (int)F;
-    g.n_blk = h->md_rdf_n_blk, g.chunk = h->md_rdf_chunk;
-    g.dr = rdf_run ? h->md_rdf_p.r_max / (double)h->md_rdf_p.n_bins : 1.0;
-    auto integrate = [&](int k, bool drift) {
-      if (rdf_run) {
-        const int64_t t = step0 + k;
-        if (t >= rdf_origin && (t - rdf_origin) % rdf_s == 0 && !(k == 0 && t == rdf_last)) {
-          g.pos = h->db.pos;
-          g.cells = h->db.cells;
-          g.species = h->db.species;
-          g.atom_start = h->db.atom_start;
-          g.pair_start = h->pair_start.ptr;  // the resident list, not the exact one filtered from it
-          g.pair_i = h->pair_i.ptr;
-          g.pair_j = h->pair_j.ptr;
-          g.pair_shift = h->pair_shift.ptr;
-          g.seq = (unsigned)k;
-          ta::launch_md_rdf(g, s);
-          HIP_CHECK(hipGetLastError());
-        }
-      }
-      // (a rebuild may have moved the batch's arrays: the pointers are taken at every launch)
-      a.pos = h->db.pos;
-      a.forces = h->db.forces;
-      a.energy = h->db.energy;
-      a.atom_start = h->db.atom_start;
-      a.cells = h->db.cells;
-      a.virial = h->db.virial;
-      a.seq = (unsigned)k;
-      a.step = (long long)(step0 + k);  // (a step redone after a rebuild keeps its index)
-      a.kick2 = k > 0 ? 1 : 0;  // the state at entry is a whole step
-      a.drift = drift ? 1 : 0;
-      a.rec = (k % record_every == 0) ? (long long)(k / record_every) : -1;
-      a.snap_x = a.snap_v = nullptr;
-      const int64_t t = step0 + k;
-      const bool due = sampling && t >= samp_origin && (t - samp_origin) % samp_s == 0 && !(k == 0 && t == samp_last);
-      if (due) {
-        c.n = (long long)((t - samp_origin) / samp_s);
-        const size_t slot = (size_t)(c.n % samp_L);
-        a.snap_x = h->md_ring_x.ptr + slot * 3 * N;
-        a.snap_v = h->md_ring_v.ptr + slot * 3 * N;
-      }
-      ta::launch_md_integrate(a, threads, s);
-      HIP_CHECK(hipGetLastError());
-      if (due) {  // directly behind the launch that sampled, under the same predicate
-        c.species = h->db.species;
-        c.atom_start = h->db.atom_start;
-        c.seq = (unsigned)k;
-        ta::launch_md_correlate(c, s);
-        HIP_CHECK(hipGetLastError());
-      }
-    };
-
-    h->jvp_valid = false;
-    compute_impl(h, want, false, nullptr);  // F_0 and the record of the state at entry
-    int rebuilds = 0;
-    resident_steps(h, "ta_md_run", n_steps, want, [&](int q) { integrate(q, true); },
-                   [](int, int) { return -1; }, &rebuilds, n_rebuilds);
-    integrate(n_steps, false);  // the pending half-kick and the last record
-    HIP_CHECK(hipStreamSynchronize(s));
-    h->upload_pending = false;
-    h->md_step = step0 + n_steps;
-    if (sampling && h->md_step >= samp_origin)  // the newest sample: the last multiple of sample_every reached
-      h->md_samp_last = std::max(samp_last, samp_origin + (h->md_step - samp_origin) / samp_s * samp_s);
-    h->md_samp_valid = samp_was_valid;
-    if (rdf_run && h->md_step >= rdf_origin)
-      h->md_rdf_last = std::max(rdf_last, rdf_origin + (h->md_step - rdf_origin) / rdf_s * rdf_s);
-    h->md_rdf_valid = rdf_was_valid;
-    if (n_rebuilds) *n_rebuilds = rebuilds;
-    if (baro && F) {
-      std::vector<double> rec(4 * n_rec * F);
-      HIP_CHECK(hipMemcpy(rec.data(), h->md_baro_rec.ptr, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
-      h->md_rec_volume.resize(n_rec * F);
-      h->md_rec_press.resize(3 * n_rec * F);
-      for (size_t j = 0; j < n_rec * F; ++j) {
-        h->md_rec_volume[j] = rec[4 * j];
-        for (int c = 0; c < 3; ++c) h->md_rec_press[3 * j + c] = rec[4 * j + 1 + c];
-      }
-      // The cells moved under a list built for others: one list for the final state, as at the end of a cell
-      // relaxation, so that ref_pos and ref_cells are what ta_update_positions, ta_step, a fixed-cell run and
-      // ta_relax_run take them for. The evaluation is repeated on it; results agree up to summation order.
-      std::vector<double> cells(9 * F);
-      HIP_CHECK(hipMemcpy(cells.data(), h->db.cells, 9 * F * sizeof(double), hipMemcpyDeviceToHost));
-      if (std::memcmp(cells.data(), h->ref_cells.data(), 9 * F * sizeof(double)) != 0) {
-        std::vector<double> x(3 * N);
-        if (N) HIP_CHECK(hipMemcpy(x.data(), h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
-        try {
-          rebuild_list(h, x.data(), cells.data());
-        } catch (const HipError &e) {
-          throw HipError(std::string("ta_md_run: list rebuild for the final cells failed: ") + e.what());
-        } catch (const std::exception &e) {
-          throw std::runtime_error(std::string("ta_md_run: list rebuild for the final cells failed: ") + e.what());
-        }
-        if (N) HIP_CHECK(hipMemcpyAsync(h->md_ref.ptr, h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToDevice, s));
-        h->md_ref_builds = h->n_list_builds;
-        compute_impl(h, want, false, nullptr);
-        HIP_CHECK(hipStreamSynchronize(s));
-        h->upload_pending = false;
-        ++rebuilds;
-        if (n_rebuilds) *n_rebuilds = rebuilds;
-      }
-      if (h->relax_cell_on && h->relax_valid &&
-          std::memcmp(cells_at_entry.data(), h->ref_cells.data(), 9 * F * sizeof(double)) != 0) {
-        // the barostat's cells replace the relaxed ones: they are h0 from here on, G = I, the cell velocities 0
-        HIP_CHECK(hipMemcpy(h->relax_cell_h0.ptr, h->ref_cells.data(), 9 * F * sizeof(double), hipMemcpyHostToDevice));
-        h->relax_cell_G_host.assign(9 * F, 0.0);
-        for (size_t f = 0; f < F; ++f) h->relax_cell_G_host[9 * f] = h->relax_cell_G_host[9 * f + 4] = h->relax_cell_G_host[9 * f + 8] = 1.0;
-        h->relax_cell_vel_host.assign(9 * F, 0.0);
-      }
-      h->md_rec_valid = true;
-    }
-    if (nhc) {
-      h->md_rec_chain.resize(n_rec * F);
-      if (F) HIP_CHECK(hipMemcpy(h->md_rec_chain.data(), h->md_nhc_rec.ptr, n_rec * F * sizeof(double), hipMemcpyDeviceToHost));
-      h->md_nhc_rec_valid = true;
-    }
-    if (epot && F) HIP_CHECK(hipMemcpy(epot, h->md_epot.ptr, n_rec * F * sizeof(double), hipMemcpyDeviceToHost));
-    if (ekin && F) {
-      std::vector<double> part(n_rec * n_blk);
-      HIP_CHECK(hipMemcpy(part.data(), h->md_ke.ptr, part.size() * sizeof(double), hipMemcpyDeviceToHost));
-      const std::vector<int32_t> &start = h->md_blk_start_host;
-      for (size_t r = 0; r < n_rec; ++r)
-        for (size_t f = 0; f < F; ++f) {
-          double t = 0.0;
-          for (int32_t b = start[f]; b < start[f + 1]; ++b) t += part[r * n_blk + (size_t)b];
-          ekin[r * F + f] = t;
-        }
-    }
-  });
-  h->cell_running = h->md_baro_running = false;
-  return rc;
-}
-
-int ta_md_get_state(ta_handle h, double *positions, double *velocities) {
-  if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_state: no resident batch");
-  if (!h->md_valid) return fail(h, TA_ERR_INVALID, "ta_md_get_state called before ta_md_init");
-  return guarded(h, [&]() {
-    const size_t N = h->keep_species.size();
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    h->upload_pending = false;
-    if (positions && N) HIP_CHECK(hipMemcpy(positions, h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
-    if (velocities && N) HIP_CHECK(hipMemcpy(velocities, h->md_vel.ptr, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
-  });
-}
-
-int ta_relax_init(ta_handle h, const ta_fire_params *p, const uint8_t *fixed) {
-  if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_relax_init: no resident batch");
-  ta_fire_params q = {0.1, 1.0, 0.2, 1.1, 0.5, 0.1, 0.99, 5};  // ASE's defaults
-  if (p) q = *p;
-  auto positive = [](double v) { return std::isfinite(v) && v > 0.0; };
-  if (!positive(q.dt)) return fail(h, TA_ERR_INVALID, "ta_relax_init: dt must be finite and > 0");
-  if (!positive(q.dtmax)) return fail(h, TA_ERR_INVALID, "ta_relax_init: dtmax must be finite and > 0");
-  if (!positive(q.maxstep)) return fail(h, TA_ERR_INVALID, "ta_relax_init: maxstep must be finite and > 0");
-  if (!std::isfinite(q.finc) || q.finc < 1.0) return fail(h, TA_ERR_INVALID, "ta_relax_init: finc must be finite and >= 1");
-  if (!(q.fdec > 0.0 && q.fdec < 1.0)) return fail(h, TA_ERR_INVALID, "ta_relax_init: fdec must lie in (0, 1)");
-  if (!(q.fa > 0.0 && q.fa < 1.0)) return fail(h, TA_ERR_INVALID, "ta_relax_init: fa must lie in (0, 1)");
-  if (!(q.astart > 0.0 && q.astart <= 1.0)) return fail(h, TA_ERR_INVALID, "ta_relax_init: astart must lie in (0, 1]");
-  if (q.nmin < 0) return fail(h, TA_ERR_INVALID, "ta_relax_init: nmin must be >= 0");
-  return guarded(h, [&]() {
-    const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
-    h->relax_valid = false;
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    h->upload_pending = false;
-    h->relax_vel.ensure(3 * N + 1);
-    h->relax_fixed.ensure(N + 1);
-    h->relax_state.ensure(2 * F + 1);
-    h->relax_count.ensure(1);
-    h->md_ref.ensure(3 * N + 1);
-    h->md_ref_builds = -1;  // ta_relax_run uploads ref_pos
-    h->md_status.ensure(2);
-    h->md_status_host.ensure(64);
-    if (N) {
-      HIP_CHECK(hipMemset(h->relax_vel.ptr, 0, 3 * N * sizeof(double)));
-      if (fixed) {
-        std::vector<uint8_t> mask(N);
-        for (size_t i = 0; i < N; ++i) mask[i] = fixed[i] ? 1 : 0;
-        HIP_CHECK(hipMemcpy(h->relax_fixed.ptr, mask.data(), N, hipMemcpyHostToDevice));
-        h->relax_fixed_host = mask;
-      } else {
-        HIP_CHECK(hipMemset(h->relax_fixed.ptr, 0, N));
-        h->relax_fixed_host.assign(N, 0);
-      }
-    } else {
-      h->relax_fixed_host.clear();
-    }
-    ta::RelaxFrameState st;
-    st.dt = q.dt;
-    st.a = q.astart;
-    st.fmax2 = 0.0;
-    st.npos = 0;
-    st.first = 1;
-    st.converged = 0;
-    st.steps = 0;
-    h->relax_state_host.assign(F, st);
-    h->relax_cell_on = false;
-    h->relax_band_on = h->relax_band_ran = false;
-    h->relax_cell_G_host.assign(9 * F, 0.0);
-    for (size_t f = 0; f < F; ++f) h->relax_cell_G_host[9 * f] = h->relax_cell_G_host[9 * f + 4] = h->relax_cell_G_host[9 * f + 8] = 1.0;
-    h->relax_cell_vel_host.assign(9 * F, 0.0);
-    h->relax_p = q;
-    h->md_chunk = 0;  // (the workgroup layout is planned for this batch by the next run)
-    h->md_blk_start_host.clear();
-    h->relax_valid = true;
-  });
-}
-
-int ta_relax_run(ta_handle h, int32_t max_steps, double fmax, uint32_t want, int32_t *steps, int32_t *converged,
-                 double *fmax_out, int32_t *n_rebuilds) {
-  if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_relax_run: no resident batch");
-  if (!h->relax_valid)
-    return fail(h, TA_ERR_INVALID, "ta_relax_run called before ta_relax_init (ta_set_frames drops the relaxation state)");
-  if (max_steps < 0) return fail(h, TA_ERR_INVALID, "ta_relax_run: max_steps must be >= 0");
-  if (!std::isfinite(fmax) || !(fmax > 0.0)) return fail(h, TA_ERR_INVALID, "ta_relax_run: fmax must be finite and > 0");
-  if (n_rebuilds) *n_rebuilds = 0;
-  want |= TA_WANT_ENERGY | TA_WANT_FORCES;
-  want &= ~(uint32_t)TA_WANT_REUSE_DESCRIPTORS;
-  const bool cell = h->relax_cell_on;
-  const bool band = h->relax_band_on;  // (never with `cell`)
-  if (cell) want |= TA_WANT_VIRIAL;  // the force on the cell rows
-  // a run that fails leaves positions and velocities somewhere on its way and the host's image of the
-  // per-frame records behind them: the state is dropped, and only ta_relax_init makes a new one
-  h->relax_valid = false;
-  h->relax_band_ran = false;
-  h->cell_running = cell;
-  const int rc = guarded(h, [&]() {
-    const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
-    hipStream_t s = h->stream;
-    md_plan_blocks(h, ta::kMdChunk);
-    // band mode: the FIRE launches see the whole band as one pseudo-frame of N atoms; the band launches cut
-    // every interior image into its own workgroups
-    const int band_n = band ? h->keep_natoms[0] : 0;
-    const int band_blk_per_image = std::max(1, (band_n + ta::kMdChunk - 1) / ta::kMdChunk);
-    const size_t n_blk = band ? std::max<size_t>(1, (N + ta::kMdChunk - 1) / ta::kMdChunk) : (size_t)h->md_n_blk;
-    h->relax_part.ensure(4 * n_blk + 1);
-    if (band) h->band_part.ensure(4 * (F - 2) * (size_t)band_blk_per_image + 1);
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (h->md_ref_builds != h->n_list_builds) {  // the host built the list that is resident: its positions go up once
-      if (N) HIP_CHECK(hipMemcpy(h->md_ref.ptr, h->ref_pos.data(), 3 * N * sizeof(double), hipMemcpyHostToDevice));
-      h->md_ref_builds = h->n_list_builds;
-    }
-    // every frame is tested against this run's fmax: a frame frozen by an earlier run may wake
-    std::vector<ta::RelaxFrameState> &st = h->relax_state_host;
-    for (auto &r : st) r.converged = 0, r.steps = 0;
-    if (F) HIP_CHECK(hipMemcpy(h->relax_state.ptr, st.data(), F * sizeof(ta::RelaxFrameState), hipMemcpyHostToDevice));
-    if (band) {  // the band's one record into copy 0, the pseudo-frame's layout next to the climbing word
-      h->band_state_host.converged = 0, h->band_state_host.steps = 0;
-      HIP_CHECK(hipMemcpy(h->band_state.ptr, &h->band_state_host, sizeof(ta::RelaxFrameState), hipMemcpyHostToDevice));
-      const int32_t layout[5] = {0, (int32_t)N, 0, (int32_t)n_blk, -1};
-      HIP_CHECK(hipMemcpy(h->band_layout.ptr, layout, sizeof(layout), hipMemcpyHostToDevice));
-    }
-    HIP_CHECK(hipMemset(h->relax_count.ptr, 0, sizeof(int)));
-    if (cell && F) {  // the current G and cell velocity into copy 0, the cells of the resident list next to md_ref
-      HIP_CHECK(hipMemcpy(h->relax_cell_G.ptr, h->relax_cell_G_host.data(), 9 * F * sizeof(double), hipMemcpyHostToDevice));
-      HIP_CHECK(hipMemcpy(h->relax_cell_vel.ptr, h->relax_cell_vel_host.data(), 9 * F * sizeof(double), hipMemcpyHostToDevice));
-      HIP_CHECK(hipMemcpy(h->md_ref_cells.ptr, h->ref_cells.data(), 9 * F * sizeof(double), hipMemcpyHostToDevice));
-    }
-    volatile unsigned *status_host = reinterpret_cast<volatile unsigned *>(h->md_status_host.ptr);
-    status_host[0] = status_host[1] = 0u;  // (no launch that writes them is in flight: every run ends with a wait)
-    HIP_CHECK(hipMemsetAsync(h->md_status.ptr, 0, 2 * sizeof(unsigned), s));
-
-    const ta_fire_params &p = h->relax_p;
-    ta::RelaxLaunch a;
-    a.vel = h->relax_vel.ptr;
-    a.fixed = h->relax_fixed.ptr;
-    a.ref = h->md_ref.ptr;
-    a.blk_start = h->md_blk_start.ptr;
-    a.part = h->relax_part.ptr;
-    a.state = h->relax_state.ptr;
-    a.n_converged = h->relax_count.ptr;
-    a.status = h->md_status.ptr;
-    a.status_host = const_cast<unsigned *>(status_host);
-    a.dtmax = p.dtmax, a.maxstep = p.maxstep, a.finc = p.finc, a.fdec = p.fdec, a.astart = p.astart, a.fa = p.fa;
-    a.nmin = p.nmin;
-    a.fmax2 = fmax * fmax;
-    a.lim2 = h->skin > 0.0 ? 0.25 * h->skin * h->skin : -1.0;  // skin = 0: every step rebuilds
-    a.n_frames = (int)F;
-    a.n_blk = (int)n_blk;
-    a.chunk = ta::kMdChunk;
-    a.cell = cell ? 1 : 0;
-    a.virial = nullptr, a.cells = nullptr;
-    a.ref_cells = h->md_ref_cells.ptr, a.cell_h0 = h->relax_cell_h0.ptr, a.cell_cf = h->relax_cell_cf.ptr;
-    a.cell_G = h->relax_cell_G.ptr, a.cell_vel = h->relax_cell_vel.ptr, a.cell_fmax2 = h->relax_cell_fmax2.ptr;
-    {
-      const int32_t *m = h->relax_cell_p.mask;  // Voigt xx yy zz yz xz xy
-      const int32_t full[9] = {m[0], m[5], m[4], m[5], m[1], m[3], m[4], m[3], m[2]};
-      for (int c = 0; c < 9; ++c) a.cell_mask[c] = full[c] ? 1.0 : 0.0;
-    }
-    a.pressure = h->relax_cell_p.pressure;
-    a.skin = h->skin;
-    a.r_list = h->rmax + h->skin;
-    a.hydrostatic = h->relax_cell_p.hydrostatic ? 1 : 0;
-    ta::NebLaunch nb = {};
-    if (band) {
-      a.fixed = h->band_fixed.ptr;
-      a.blk_start = h->band_layout.ptr + 2;
-      a.state = h->band_state.ptr;
-      a.n_frames = 1;
-      nb.fixed = h->band_fixed.ptr;
-      nb.part = h->band_part.ptr;
-      nb.band = h->band_force.ptr;
-      nb.climbing = h->band_layout.ptr + 4;
-      nb.status = h->md_status.ptr;
-      nb.k = h->relax_band_p.k;
-      nb.n_images = (int)F, nb.n = band_n, nb.chunk = ta::kMdChunk, nb.blk_per_image = band_blk_per_image;
-      nb.climb = h->relax_band_p.climb ? 1 : 0;
-    }
-    // B (and, with `tangents`, tau) of the resident evaluation
-    auto band_force = [&](int k, bool tangents) {
-      nb.pos = h->db.pos;
-      nb.forces = h->db.forces;
-      nb.energy = h->db.energy;
-      nb.tau = tangents ? h->band_tau.ptr : nullptr;
-      nb.seq = (unsigned)k;
-      ta::launch_neb_force(nb, s);
-      HIP_CHECK(hipGetLastError());
-    };
-    int launched = 0;  // launches that ran: the current copy of the state is launched & 1
-    auto step = [&](int k, bool drift) {
-      // (a rebuild may have moved the batch's arrays: the pointers are taken at every launch)
-      a.pos = h->db.pos;
-      a.forces = h->db.forces;
-      a.atom_start = h->db.atom_start;
-      a.virial = h->db.virial;
-      a.cells = h->db.cells;
-      a.seq = (unsigned)k;
-      a.drift = drift ? 1 : 0;
-      if (band) {  // FIRE runs on the band forces of the pseudo-frame; the last launch of a run leaves tau too
-        band_force(k, !drift);
-        a.forces = h->band_force.ptr;
-        a.atom_start = h->band_layout.ptr;
-      }
-      ta::launch_relax_step(a, s);
-      HIP_CHECK(hipGetLastError());
-      launched = k + 1;
-    };
-
-    h->jvp_valid = false;
-    compute_impl(h, want, false, nullptr);  // F of the state at entry
-    int rebuilds = 0;
-    bool all_converged = false;
-    // the launch at which the last frame converged, and every launch behind it, moved nothing
-    auto finished = [&](int k, int k_end) {
-      const unsigned done = status_host[1];
-      if (done == 0u) return -1;
-      if ((int)done - 1 < k || (int)done - 1 >= k_end) throw std::runtime_error("ta_relax_run: inconsistent done word");
-      all_converged = true;
-      return (int)done - 1;
-    };
-    const int done_steps = resident_steps(h, "ta_relax_run", max_steps, want, [&](int q) { step(q, true); }, finished,
-                                          &rebuilds, n_rebuilds);
-    if (!all_converged) step(done_steps, false);  // the test of the last evaluation
-    else if (band) band_force(done_steps, true);  // (the converged state's B again, with tau)
-    HIP_CHECK(hipStreamSynchronize(s));
-    h->upload_pending = false;
-    if (n_rebuilds) *n_rebuilds = rebuilds;
-    if (band) {
-      ta::RelaxFrameState &b = h->band_state_host;
-      HIP_CHECK(hipMemcpy(&b, h->band_state.ptr + (size_t)(launched & 1), sizeof(ta::RelaxFrameState), hipMemcpyDeviceToHost));
-      for (size_t f = 0; f < F; ++f) {
-        if (steps) steps[f] = b.steps;
-        if (converged) converged[f] = b.converged;
-        if (fmax_out) fmax_out[f] = std::sqrt(b.fmax2);
-      }
-      h->band_energy_host.resize(F);  // what ta_relax_get_band hands out next to B and tau of this state
-      HIP_CHECK(hipMemcpy(h->band_energy_host.data(), h->db.energy, F * sizeof(double), hipMemcpyDeviceToHost));
-      return;
-    }
-    if (F)
-      HIP_CHECK(hipMemcpy(st.data(), h->relax_state.ptr + (size_t)(launched & 1) * F, F * sizeof(ta::RelaxFrameState),
-                          hipMemcpyDeviceToHost));
-    for (size_t f = 0; f < F; ++f) {
-      if (steps) steps[f] = st[f].steps;
-      if (converged) converged[f] = st[f].converged;
-      if (fmax_out) fmax_out[f] = std::sqrt(st[f].fmax2);
-    }
-    if (cell && F) {
-      HIP_CHECK(hipMemcpy(h->relax_cell_G_host.data(), h->relax_cell_G.ptr + 9 * (size_t)(launched & 1) * F,
-                          9 * F * sizeof(double), hipMemcpyDeviceToHost));
-      HIP_CHECK(hipMemcpy(h->relax_cell_vel_host.data(), h->relax_cell_vel.ptr + 9 * (size_t)(launched & 1) * F,
-                          9 * F * sizeof(double), hipMemcpyDeviceToHost));
-      // The cells moved under a list built for others: one list for the final state, so that ref_pos and
-      // ref_cells (the host's image of the resident geometry) are what ta_update_positions, ta_md_run and a
-      // fixed-cell run take them for. The evaluation is repeated on it; results agree up to summation order.
-      std::vector<double> cells(9 * F);
-      HIP_CHECK(hipMemcpy(cells.data(), h->db.cells, 9 * F * sizeof(double), hipMemcpyDeviceToHost));
-      if (std::memcmp(cells.data(), h->ref_cells.data(), 9 * F * sizeof(double)) != 0) {
-        std::vector<double> x(3 * N);
-        if (N) HIP_CHECK(hipMemcpy(x.data(), h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
-        try {
-          rebuild_list(h, x.data(), cells.data());
-        } catch (const HipError &e) {
-          throw HipError(std::string("ta_relax_run: list rebuild for the final cells failed: ") + e.what());
-        } catch (const std::exception &e) {
-          throw std::runtime_error(std::string("ta_relax_run: list rebuild for the final cells failed: ") + e.what());
-        }
-        if (N) HIP_CHECK(hipMemcpyAsync(h->md_ref.ptr, h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToDevice, s));
-        h->md_ref_builds = h->n_list_builds;
-        compute_impl(h, want, false, nullptr);
-        HIP_CHECK(hipStreamSynchronize(s));
-        h->upload_pending = false;
-        ++rebuilds;
-        if (n_rebuilds) *n_rebuilds = rebuilds;
-      }
-    }
-  });
-  h->cell_running = false;
-  if (rc == TA_OK) h->relax_valid = true, h->relax_band_ran = band;
-  else h->relax_cell_on = h->relax_band_on = false;
-  return rc;
-}
-
-int ta_relax_get_state(ta_handle h, double *positions, double *velocities, double *dt, double *a, int32_t *npos) {
-  if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_relax_get_state: no resident batch");
-  if (!h->relax_valid) return fail(h, TA_ERR_INVALID, "ta_relax_get_state called before ta_relax_init");
-  return guarded(h, [&]() {
-    const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    h->upload_pending = false;
-    if (positions && N) HIP_CHECK(hipMemcpy(positions, h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
-    if (velocities && N)
-      HIP_CHECK(hipMemcpy(velocities, h->relax_vel.ptr, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
-    for (size_t f = 0; f < F; ++f) {  // (band mode: the band's one record for every frame)
-      const ta::RelaxFrameState &r = h->relax_band_on ? h->band_state_host : h->relax_state_host[f];
-      if (dt) dt[f] = r.dt;
-      if (a) a[f] = r.a;
-      if (npos) npos[f] = r.npos;
-    }
-  });
-}
-
-int ta_relax_set_cell(ta_handle h, int on, const ta_relax_cell_params *p) {
-  if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_relax_set_cell: no resident batch");
-  if (!h->relax_valid) return fail(h, TA_ERR_INVALID, "ta_relax_set_cell called before ta_relax_init");
-  if (!on) {
-    h->relax_cell_on = false;  // (the cells stay as they are)
-    return TA_OK;
-  }
-  if (h->relax_band_on)
-    return fail(h, TA_ERR_INVALID, "ta_relax_set_cell: the band option is on (ta_relax_set_band); cells along a band stay fixed");
-  ta_relax_cell_params q = {0.0, 0.0, {1, 1, 1, 1, 1, 1}, 0, 0};
-  if (p) q = *p;
-  if (!std::isfinite(q.cell_factor) || q.cell_factor < 0.0)
-    return fail(h, TA_ERR_INVALID, "ta_relax_set_cell: cell_factor must be finite and >= 0");
-  if (!std::isfinite(q.pressure)) return fail(h, TA_ERR_INVALID, "ta_relax_set_cell: pressure must be finite");
-  bool any = false;
-  for (int c = 0; c < 6; ++c) any = any || q.mask[c] != 0;
-  if (!any) return fail(h, TA_ERR_INVALID, "ta_relax_set_cell: mask leaves no component of the cell free");
-  const size_t F = h->keep_natoms.size();
-  std::vector<double> cf(F);
-  for (size_t f = 0; f < F; ++f) {
-    for (int k = 0; k < 3; ++k)
-      if (!h->keep_pbc[3 * f + k])
-        return fail(h, TA_ERR_INVALID, "ta_relax_set_cell: frame " + std::to_string(f) + " is not periodic along all three axes");
-    const double *c = h->ref_cells.data() + 9 * f;
-    const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
-    if (!std::isfinite(det) || !(std::fabs(det) > 0.0))
-      return fail(h, TA_ERR_INVALID, "ta_relax_set_cell: the cell of frame " + std::to_string(f) + " is singular");
-    cf[f] = q.cell_factor > 0.0 ? q.cell_factor : (double)std::max(1, h->keep_natoms[f]);
-  }
-  return guarded(h, [&]() {
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    h->upload_pending = false;
-    h->relax_cell_h0.ensure(9 * F + 1);
-    h->relax_cell_cf.ensure(F + 1);
-    h->relax_cell_G.ensure(2 * 9 * F + 1);
-    h->relax_cell_vel.ensure(2 * 9 * F + 1);
-    h->relax_cell_fmax2.ensure(F + 1);
-    h->md_ref_cells.ensure(9 * F + 1);
-    if (F) {
-      HIP_CHECK(hipMemcpy(h->relax_cell_h0.ptr, h->ref_cells.data(), 9 * F * sizeof(double), hipMemcpyHostToDevice));
-      HIP_CHECK(hipMemcpy(h->relax_cell_cf.ptr, cf.data(), F * sizeof(double), hipMemcpyHostToDevice));
-      HIP_CHECK(hipMemset(h->relax_cell_fmax2.ptr, 0, F * sizeof(double)));
-    }
-    h->relax_cell_G_host.assign(9 * F, 0.0);
-    for (size_t f = 0; f < F; ++f) h->relax_cell_G_host[9 * f] = h->relax_cell_G_host[9 * f + 4] = h->relax_cell_G_host[9 * f + 8] = 1.0;
-    h->relax_cell_vel_host.assign(9 * F, 0.0);
-    h->relax_cell_p = q;
-    h->relax_cell_on = true;
-  });
-}
-
-int ta_relax_get_cell(ta_handle h, double *cells, double *deform, double *cell_velocities, double *cell_fmax) {
-  if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_relax_get_cell: no resident batch");
-  if (!h->relax_valid) return fail(h, TA_ERR_INVALID, "ta_relax_get_cell called before ta_relax_init");
-  return guarded(h, [&]() {
-    const size_t F = h->keep_natoms.size();
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    h->upload_pending = false;
-    if (!F) return;
-    // (between runs ref_cells is the image of the device's cells)
-    if (cells) std::memcpy(cells, h->ref_cells.data(), 9 * F * sizeof(double));
-    if (deform) std::memcpy(deform, h->relax_cell_G_host.data(), 9 * F * sizeof(double));
-    if (cell_velocities) std::memcpy(cell_velocities, h->relax_cell_vel_host.data(), 9 * F * sizeof(double));
-    if (cell_fmax) {
-      if (h->relax_cell_fmax2.ptr) {
-        HIP_CHECK(hipMemcpy(cell_fmax, h->relax_cell_fmax2.ptr, F * sizeof(double), hipMemcpyDeviceToHost));
-        for (size_t f = 0; f < F; ++f) cell_fmax[f] = std::sqrt(cell_fmax[f]);
-      } else {
-        for (size_t f = 0; f < F; ++f) cell_fmax[f] = 0.0;
-      }
-    }
-  });
-}
-
-int ta_relax_set_band(ta_handle h, int on, const ta_band_params *p) {
-  if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_relax_set_band: no resident batch");
-  if (!h->relax_valid) return fail(h, TA_ERR_INVALID, "ta_relax_set_band called before ta_relax_init");
-  const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
-  ta_band_params q = {0.1, 0, 0};  // ASE's spring constant
-  if (on) {
-    if (p) q = *p;
-    if (F < 3) return fail(h, TA_ERR_INVALID, "ta_relax_set_band: a band needs at least 3 frames, the batch has " + std::to_string(F));
-    const size_t n = (size_t)h->keep_natoms[0];
-    for (size_t f = 1; f < F; ++f) {
-      const std::string who = "ta_relax_set_band: frame " + std::to_string(f) + " differs from frame 0 in its ";
-      if ((size_t)h->keep_natoms[f] != n) return fail(h, TA_ERR_INVALID, who + "atom count");
-      if (!std::equal(h->keep_species.begin(), h->keep_species.begin() + n, h->keep_species.begin() + f * n))
-        return fail(h, TA_ERR_INVALID, who + "species");
-      if (!std::equal(h->ref_cells.begin(), h->ref_cells.begin() + 9, h->ref_cells.begin() + 9 * f))
-        return fail(h, TA_ERR_INVALID, who + "cell");
-      if (!std::equal(h->keep_pbc.begin(), h->keep_pbc.begin() + 3, h->keep_pbc.begin() + 3 * f))
-        return fail(h, TA_ERR_INVALID, who + "pbc");
-    }
-    if (!std::isfinite(q.k) || !(q.k > 0.0)) return fail(h, TA_ERR_INVALID, "ta_relax_set_band: k must be finite and > 0");
-    if (h->relax_cell_on)
-      return fail(h, TA_ERR_INVALID, "ta_relax_set_band: the cell option is on (ta_relax_set_cell); cells along a band stay fixed");
-  }
-  return guarded(h, [&]() {
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    h->upload_pending = false;
-    // the optimiser starts again, in either direction: v = 0, dt, a = astart, npos = 0, first
-    ta::RelaxFrameState st;
-    st.dt = h->relax_p.dt;
-    st.a = h->relax_p.astart;
-    st.fmax2 = 0.0;
-    st.npos = 0;
-    st.first = 1;
-    st.converged = 0;
-    st.steps = 0;
-    h->relax_state_host.assign(F, st);
-    h->band_state_host = st;
-    if (N) HIP_CHECK(hipMemset(h->relax_vel.ptr, 0, 3 * N * sizeof(double)));
-    h->relax_band_ran = false;
-    if (!on) {
-      h->relax_band_on = false;
-      return;
-    }
-    const size_t n = (size_t)h->keep_natoms[0];
-    h->band_force.ensure(3 * N + 1);
-    h->band_tau.ensure(3 * N + 1);
-    h->band_fixed.ensure(N + 1);
-    h->band_state.ensure(2);
-    h->band_layout.ensure(5);
-    std::vector<uint8_t> mask(h->relax_fixed_host);  // the user's mask OR-ed with the two endpoint images
-    mask.resize(N, 0);
-    std::fill(mask.begin(), mask.begin() + n, 1);
-    std::fill(mask.end() - n, mask.end(), 1);
-    if (N) {
-      HIP_CHECK(hipMemcpy(h->band_fixed.ptr, mask.data(), N, hipMemcpyHostToDevice));
-      HIP_CHECK(hipMemset(h->band_force.ptr, 0, 3 * N * sizeof(double)));  // (the endpoints' rows stay 0)
-      HIP_CHECK(hipMemset(h->band_tau.ptr, 0, 3 * N * sizeof(double)));
-    }
-    h->relax_band_p = q;
-    h->relax_band_on = true;
-  });
-}
-
-int ta_relax_get_band(ta_handle h, double *band_forces, double *tangents, double *energies, int32_t *climbing) {
-  if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_relax_get_band: no resident batch");
-  if (!h->relax_valid) return fail(h, TA_ERR_INVALID, "ta_relax_get_band called before ta_relax_init");
-  if (!h->relax_band_on) return fail(h, TA_ERR_INVALID, "ta_relax_get_band: the band option is off (ta_relax_set_band)");
-  if (!h->relax_band_ran)
-    return fail(h, TA_ERR_INVALID, "ta_relax_get_band: no ta_relax_run of this band yet (max_steps = 0 counts)");
-  return guarded(h, [&]() {
-    const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    h->upload_pending = false;
-    if (band_forces && N) HIP_CHECK(hipMemcpy(band_forces, h->band_force.ptr, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
-    if (tangents && N) HIP_CHECK(hipMemcpy(tangents, h->band_tau.ptr, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
-    if (energies) std::memcpy(energies, h->band_energy_host.data(), F * sizeof(double));
-    if (climbing) HIP_CHECK(hipMemcpy(climbing, h->band_layout.ptr + 4, sizeof(int32_t), hipMemcpyDeviceToHost));
-  });
 }
 
 int ta_eval(ta_handle h, int32_t n_frames, const ta_frame *frames, uint32_t want, double *energy,
@@ -4321,7 +2561,6 @@ int ta_eam_tabulate(ta_handle h, int32_t n_r, const double *r, int32_t n_rho, co
       back(w_of_r, d_w, npair * n_r);
     }
     HIP_CHECK(hipStreamSynchronize(s));
-    buf.release();
   });
 }
 

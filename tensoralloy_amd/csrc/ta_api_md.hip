@@ -1,0 +1,721 @@
+// C ABI of the device-resident MD loop: the ta_md_* entry points (include/tensoralloy_amd.h). The loop itself
+// is in ta_resident.hip; the integrator, correlation and pair-distribution launches are in ta_md.hip,
+// ta_md_corr.hip and ta_md_rdf.hip.
+#include <cmath>
+#include <cstring>
+
+#include "ta_context.h"
+#include "ta_md.h"
+
+using namespace ta::host;
+
+namespace {
+
+// `chunk` consecutive items of one frame per workgroup, at least one workgroup per frame: the first workgroup of
+// every frame, [F + 1], where frame f has per_atom * n_atoms items
+std::vector<int32_t> frame_blocks(const ta_context *h, int per_atom, int chunk) {
+  const size_t F = h->keep_natoms.size();
+  std::vector<int32_t> start(F + 1, 0);
+  for (size_t f = 0; f < F; ++f)
+    start[f + 1] = start[f] + std::max(1, (per_atom * h->keep_natoms[f] + chunk - 1) / chunk);
+  return start;
+}
+
+// Rings, zeroed accumulators and the correlation launch's chunk layout for the resident batch under setting
+// `p`, with no sample held. False when the device has no room (everything is released then); throws otherwise.
+bool md_sampling_alloc(ta_context *h, const ta_md_sampling_params &p) {
+  auto &c = h->md.corr;
+  const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
+  const size_t L = (size_t)p.n_lags, E = (size_t)h->n_elements;
+  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches read the old buffers)
+  c.release();
+  const std::vector<int32_t> start = frame_blocks(h, 3, ta::kMdCorrChunk);
+  const size_t n_chunks = (size_t)start[F], n_acc = 2 * F * E * L;
+  if (!c.ring_x.try_exact(L * 3 * N) || !c.ring_v.try_exact(L * 3 * N) || !c.acc.try_exact(n_acc) ||
+      !c.part.try_exact(n_chunks * 2 * E * L) || !c.blk.try_exact(F + 1)) {
+    c.release();
+    return false;
+  }
+  HIP_CHECK(hipMemset(c.acc.ptr, 0, std::max<size_t>(n_acc, 1) * sizeof(double)));
+  HIP_CHECK(hipMemcpy(c.blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+  c.n_chunks = (int)n_chunks;
+  c.sched.every = p.sample_every;
+  c.sched.start(h->md.step);
+  c.sched.valid = true;
+  return true;
+}
+
+// Zeroed counts and the launch's workgroup layout for the resident batch under setting `p`, with no sample
+// taken. False when the device has no room (everything is released then); throws otherwise.
+bool md_rdf_alloc(ta_context *h, const ta_md_rdf_params &p) {
+  auto &g = h->md.rdf;
+  const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
+  const size_t E = (size_t)h->n_elements, n_acc = F * E * E * (size_t)p.n_bins;
+  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches add to the old buffer)
+  g.release();
+  const int chunk = ta::md_rdf_chunk((long long)N);
+  const std::vector<int32_t> start = frame_blocks(h, 1, chunk);
+  if (!g.acc.try_exact(n_acc) || !g.blk.try_exact(F + 1)) {
+    g.release();
+    return false;
+  }
+  HIP_CHECK(hipMemset(g.acc.ptr, 0, std::max<size_t>(n_acc, 1) * sizeof(unsigned long long)));
+  HIP_CHECK(hipMemcpy(g.blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+  g.n_blk = (int)start[F];
+  g.chunk = chunk;
+  g.sched.every = p.sample_every;
+  g.sched.start(h->md.step);
+  g.sched.valid = true;
+  return true;
+}
+
+// what ta_md_get_chain and ta_md_set_chain need; returns 0 or the error code
+int md_chain_ready(ta_context *h, const char *who) {
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, std::string(who) + " called before ta_md_init");
+  if (!h->md.nhc.on)
+    return fail(h, TA_ERR_INVALID, std::string(who) + ": the Nose-Hoover chain thermostat is off (ta_md_set_nose_hoover)");
+  return TA_OK;
+}
+
+// what the two getters of the sampled data need; returns 0 or the error code
+int md_samples_ready(ta_context *h, const char *who) {
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, std::string(who) + " called before ta_md_init");
+  if (!h->md.corr.on) return fail(h, TA_ERR_INVALID, std::string(who) + ": sampling is off (ta_md_set_sampling)");
+  if (!h->md.corr.sched.valid)
+    return fail(h, TA_ERR_INVALID, std::string(who) + ": a ta_md_run failed and left the sampled data invalid; call "
+                                   "ta_md_set_sampling or ta_md_init again");
+  return TA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
+  if (!h || !masses) return fail(h, TA_ERR_INVALID, "ta_md_init: null argument");
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_init: no resident batch");
+  const size_t N = h->keep_species.size();
+  for (size_t i = 0; i < N; ++i)
+    if (!(masses[i] > 0.0) || !std::isfinite(masses[i]))
+      return fail(h, TA_ERR_INVALID, "ta_md_init: mass of atom " + std::to_string(i) + " is not a finite number > 0");
+  if (velocities)
+    for (size_t i = 0; i < 3 * N; ++i)
+      if (!std::isfinite(velocities[i])) return fail(h, TA_ERR_INVALID, "ta_md_init: non-finite velocity");
+  bool ring_nomem = false, rdf_nomem = false;
+  const int rc = guarded(h, [&]() {
+    auto &md = h->md;
+    md.valid = false;
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    h->upload_pending = false;
+    md.mass.ensure(N + 1);
+    md.vel.ensure(3 * N + 1);
+    h->res.ref.ensure(3 * N + 1);
+    h->res.status.ensure(2);
+    h->res.status_host.ensure(64);
+    const size_t n_chain = h->keep_natoms.size() * ta::kMdMaxChain;  // every frame's chain starts at rest
+    md.nhc.eta.ensure(n_chain + 1);
+    md.nhc.veta.ensure(n_chain + 1);
+    HIP_CHECK(hipMemset(md.nhc.eta.ptr, 0, (n_chain + 1) * sizeof(double)));
+    HIP_CHECK(hipMemset(md.nhc.veta.ptr, 0, (n_chain + 1) * sizeof(double)));
+    md.nhc.rec_valid = false;
+    if (N) {
+      HIP_CHECK(hipMemcpy(md.mass.ptr, masses, N * sizeof(double), hipMemcpyHostToDevice));
+      if (velocities)
+        HIP_CHECK(hipMemcpy(md.vel.ptr, velocities, 3 * N * sizeof(double), hipMemcpyHostToDevice));
+      else
+        HIP_CHECK(hipMemset(md.vel.ptr, 0, 3 * N * sizeof(double)));
+    }
+    h->res.ref_builds = -1;  // ta_md_run uploads ref_pos
+    h->res.chunk = 0;
+    h->res.blk_start_host.clear();
+    md.step = 0;
+    md.baro.rec_valid = false;
+    if (md.corr.on && !md_sampling_alloc(h, md.corr.p)) {  // an empty ring for this batch, or none
+      md.corr.on = false;
+      ring_nomem = true;
+    }
+    if (md.rdf.on && !md_rdf_alloc(h, md.rdf.p)) {  // zero counts for this batch, or none
+      md.rdf.on = false;
+      rdf_nomem = true;
+    }
+    md.valid = true;
+  });
+  if (rc == TA_OK && ring_nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the rings of ta_md_set_sampling; sampling is off");
+  if (rc == TA_OK && rdf_nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the counts of ta_md_set_rdf; the feature is off");
+  return rc;
+}
+
+int ta_md_set_thermostat(ta_handle h, double kT0, double tau) {
+  if (!h) return TA_ERR_INVALID;
+  if (std::isnan(kT0) || std::isinf(kT0)) return fail(h, TA_ERR_INVALID, "ta_md_set_thermostat: kT0 must be finite");
+  if (kT0 > 0.0 && (!(tau > 0.0) || !std::isfinite(tau)))
+    return fail(h, TA_ERR_INVALID, "ta_md_set_thermostat: tau must be a finite time > 0");
+  if (kT0 > 0.0 && h->md.langevin.friction > 0.0)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_thermostat: the Langevin thermostat is on; switch it off "
+                                   "(ta_md_set_langevin with friction 0) before the Berendsen thermostat goes on");
+  if (kT0 > 0.0 && h->md.nhc.on)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_thermostat: the Nose-Hoover chain thermostat is on; switch it off "
+                                   "(ta_md_set_nose_hoover with NULL) before the Berendsen thermostat goes on");
+  h->md.berendsen.kT0 = kT0 > 0.0 ? kT0 : 0.0;
+  h->md.berendsen.tau = kT0 > 0.0 ? tau : 0.0;
+  return TA_OK;
+}
+
+int ta_md_set_langevin(ta_handle h, double kT0, double friction, uint64_t seed) {
+  if (!h) return TA_ERR_INVALID;
+  if (!(friction >= 0.0) || !std::isfinite(friction))
+    return fail(h, TA_ERR_INVALID, "ta_md_set_langevin: friction must be a finite rate >= 0");
+  if (!(kT0 >= 0.0) || !std::isfinite(kT0))
+    return fail(h, TA_ERR_INVALID, "ta_md_set_langevin: kT0 must be finite and >= 0");
+  if (friction > 0.0 && h->md.berendsen.kT0 > 0.0)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_langevin: the Berendsen thermostat is on; switch it off "
+                                   "(ta_md_set_thermostat with kT0 0) before the Langevin thermostat goes on");
+  if (friction > 0.0 && h->md.nhc.on)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_langevin: the Nose-Hoover chain thermostat is on; switch it off "
+                                   "(ta_md_set_nose_hoover with NULL) before the Langevin thermostat goes on");
+  h->md.langevin.friction = friction;
+  h->md.langevin.kT0 = friction > 0.0 ? kT0 : 0.0;
+  h->md.langevin.seed = seed;
+  return TA_OK;
+}
+
+int ta_md_set_nose_hoover(ta_handle h, const ta_md_nhc_params *p) {
+  if (!h) return TA_ERR_INVALID;
+  if (p && std::isnan(p->kT0)) return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: kT0 must be finite");
+  auto &nhc = h->md.nhc;
+  if (!p || !(p->kT0 > 0.0)) {
+    nhc.on = false;
+    return TA_OK;
+  }
+  if (!std::isfinite(p->kT0)) return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: kT0 must be finite");
+  if (!(p->tau > 0.0) || !std::isfinite(p->tau))
+    return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: tau must be a finite time > 0");
+  if (p->chain < 1 || p->chain > TA_MD_MAX_CHAIN)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: chain must be 1 .. " + std::to_string(TA_MD_MAX_CHAIN));
+  if (p->loops < 1 || p->loops > 16) return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: loops must be 1 .. 16");
+  if (p->dof_removed < 0) return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: dof_removed must be >= 0");
+  if (h->md.berendsen.kT0 > 0.0)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: the Berendsen thermostat is on; switch it off "
+                                   "(ta_md_set_thermostat with kT0 0) before the Nose-Hoover chain goes on");
+  if (h->md.langevin.friction > 0.0)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_nose_hoover: the Langevin thermostat is on; switch it off "
+                                   "(ta_md_set_langevin with friction 0) before the Nose-Hoover chain goes on");
+  if (nhc.on && nhc.p.chain != p->chain && h->md.valid) {
+    // another chain length: the slots beyond the old one hold nothing, the chain starts again at rest
+    const size_t n_chain = h->keep_natoms.size() * ta::kMdMaxChain;
+    const int rc = guarded(h, [&]() {
+      HIP_CHECK(hipStreamSynchronize(h->stream));
+      HIP_CHECK(hipMemset(nhc.eta.ptr, 0, (n_chain + 1) * sizeof(double)));
+      HIP_CHECK(hipMemset(nhc.veta.ptr, 0, (n_chain + 1) * sizeof(double)));
+    });
+    if (rc != TA_OK) return rc;
+  }
+  nhc.p = *p;
+  nhc.on = true;
+  return TA_OK;
+}
+
+int ta_md_get_chain(ta_handle h, double *eta, double *veta) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int rc = md_chain_ready(h, "ta_md_get_chain")) return rc;
+  return guarded(h, [&]() {
+    const size_t F = h->keep_natoms.size(), M = (size_t)h->md.nhc.p.chain;
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    std::vector<double> buf(F * ta::kMdMaxChain);
+    for (int w = 0; w < 2; ++w) {
+      double *out = w ? veta : eta;
+      if (!out || !F) continue;
+      HIP_CHECK(hipMemcpy(buf.data(), w ? h->md.nhc.veta.ptr : h->md.nhc.eta.ptr, buf.size() * sizeof(double),
+                          hipMemcpyDeviceToHost));
+      for (size_t f = 0; f < F; ++f)
+        for (size_t k = 0; k < M; ++k) out[f * M + k] = buf[f * ta::kMdMaxChain + k];
+    }
+  });
+}
+
+int ta_md_set_chain(ta_handle h, const double *eta, const double *veta) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int rc = md_chain_ready(h, "ta_md_set_chain")) return rc;
+  const size_t F = h->keep_natoms.size(), M = (size_t)h->md.nhc.p.chain;
+  for (size_t j = 0; j < F * M; ++j) {
+    if (eta && !std::isfinite(eta[j])) return fail(h, TA_ERR_INVALID, "ta_md_set_chain: non-finite eta");
+    if (veta && !std::isfinite(veta[j])) return fail(h, TA_ERR_INVALID, "ta_md_set_chain: non-finite veta");
+  }
+  return guarded(h, [&]() {
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    std::vector<double> buf(F * ta::kMdMaxChain + 1);
+    for (int w = 0; w < 2; ++w) {
+      const double *in = w ? veta : eta;
+      std::fill(buf.begin(), buf.end(), 0.0);
+      if (in)
+        for (size_t f = 0; f < F; ++f)
+          for (size_t k = 0; k < M; ++k) buf[f * ta::kMdMaxChain + k] = in[f * M + k];
+      HIP_CHECK(hipMemcpy(w ? h->md.nhc.veta.ptr : h->md.nhc.eta.ptr, buf.data(), buf.size() * sizeof(double),
+                          hipMemcpyHostToDevice));
+    }
+  });
+}
+
+int ta_md_get_chain_records(ta_handle h, double *e_chain) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_chain_records: no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_get_chain_records called before ta_md_init");
+  if (!h->md.nhc.rec_valid)
+    return fail(h, TA_ERR_INVALID, "ta_md_get_chain_records: the last ta_md_run of this batch had no Nose-Hoover chain");
+  const std::vector<double> &rec = h->md.nhc.rec_host;
+  if (e_chain && !rec.empty()) std::memcpy(e_chain, rec.data(), rec.size() * sizeof(double));
+  return TA_OK;
+}
+
+int ta_md_set_sampling(ta_handle h, const ta_md_sampling_params *p) {
+  if (!h) return TA_ERR_INVALID;
+  auto &corr = h->md.corr;
+  if (!p || p->n_lags == 0) {
+    corr.on = false;
+    return guarded(h, [&]() {
+      HIP_CHECK(hipStreamSynchronize(h->stream));
+      corr.release();
+    });
+  }
+  if (p->n_lags < 0 || p->n_lags > TA_MD_MAX_LAGS)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_sampling: n_lags must be 0 .. " + std::to_string(TA_MD_MAX_LAGS));
+  if (p->sample_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_set_sampling: sample_every must be >= 1");
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_sampling: no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_set_sampling called before ta_md_init");
+  bool nomem = false;
+  const int rc = guarded(h, [&]() {
+    corr.on = false;  // (until the rings exist)
+    nomem = !md_sampling_alloc(h, *p);
+    if (!nomem) {
+      corr.p = *p;
+      corr.on = true;
+    }
+  });
+  if (rc == TA_OK && nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_set_sampling: no device memory for rings of n_lags = " + std::to_string(p->n_lags) +
+                                 " snapshots; sampling is off");
+  return rc;
+}
+
+int ta_md_get_correlations(ta_handle h, double *vacf_sum, double *msd_sum, int64_t *info) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int rc = md_samples_ready(h, "ta_md_get_correlations")) return rc;
+  return guarded(h, [&]() {
+    const auto &corr = h->md.corr;
+    const size_t n = h->keep_natoms.size() * (size_t)h->n_elements * (size_t)corr.p.n_lags;
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (vacf_sum && n) HIP_CHECK(hipMemcpy(vacf_sum, corr.acc.ptr, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (msd_sum && n) HIP_CHECK(hipMemcpy(msd_sum, corr.acc.ptr + n, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (info) {
+      info[0] = corr.sched.taken();
+      info[1] = corr.p.n_lags;
+      info[2] = corr.p.sample_every;
+      info[3] = corr.sched.last;
+    }
+  });
+}
+
+int ta_md_get_samples(ta_handle h, int32_t first_lag, int32_t n, double *positions, double *velocities,
+                      int64_t *steps) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int rc = md_samples_ready(h, "ta_md_get_samples")) return rc;
+  const auto &corr = h->md.corr;
+  const int64_t taken = corr.sched.taken(), L = corr.p.n_lags, held = std::min(taken, L);
+  if (first_lag < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_samples: first_lag must be >= 0");
+  if (n < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_samples: n must be >= 0");
+  if ((int64_t)first_lag + n > held)
+    return fail(h, TA_ERR_INVALID, "ta_md_get_samples: first_lag + n = " + std::to_string((int64_t)first_lag + n) +
+                                   " exceeds the " + std::to_string(held) + " snapshots held (min(n_samples, n_lags))");
+  return guarded(h, [&]() {
+    const size_t row = 3 * h->keep_species.size();
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    for (int32_t j = 0; j < n; ++j) {
+      const int64_t idx = taken - 1 - first_lag - j;  // sample number
+      const size_t slot = (size_t)(idx % L);
+      if (positions && row)
+        HIP_CHECK(hipMemcpy(positions + (size_t)j * row, corr.ring_x.ptr + slot * row, row * sizeof(double), hipMemcpyDeviceToHost));
+      if (velocities && row)
+        HIP_CHECK(hipMemcpy(velocities + (size_t)j * row, corr.ring_v.ptr + slot * row, row * sizeof(double), hipMemcpyDeviceToHost));
+      if (steps) steps[j] = corr.sched.step(idx);
+    }
+  });
+}
+
+int ta_md_set_rdf(ta_handle h, const ta_md_rdf_params *p) {
+  if (!h) return TA_ERR_INVALID;
+  auto &rdf = h->md.rdf;
+  if (!p || p->n_bins == 0) {
+    rdf.on = false;
+    return guarded(h, [&]() {
+      HIP_CHECK(hipStreamSynchronize(h->stream));
+      rdf.release();
+    });
+  }
+  if (p->n_bins < 0 || p->n_bins > TA_MD_MAX_BINS)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: n_bins must be 0 .. " + std::to_string(TA_MD_MAX_BINS));
+  if (p->sample_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: sample_every must be >= 1");
+  if (!std::isfinite(p->r_max) || !(p->r_max > 0.0))
+    return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: r_max must be a finite distance > 0");
+  if (p->r_max > h->rmax)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: r_max = " + std::to_string(p->r_max) + " exceeds the model's cutoff max(rcut, acut) = " +
+                                   std::to_string(h->rmax) + "; the neighbour list is not complete beyond that");
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_set_rdf called before ta_md_init");
+  bool nomem = false;
+  const int rc = guarded(h, [&]() {
+    rdf.on = false;  // (until the counts exist)
+    nomem = !md_rdf_alloc(h, *p);
+    if (!nomem) {
+      rdf.p = *p;
+      rdf.on = true;
+    }
+  });
+  if (rc == TA_OK && nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_set_rdf: no device memory for counts of n_bins = " + std::to_string(p->n_bins) +
+                                 "; the feature is off");
+  return rc;
+}
+
+int ta_md_get_rdf(ta_handle h, int64_t *counts, int64_t *info, double *r_max) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_rdf: no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_get_rdf called before ta_md_init");
+  const auto &rdf = h->md.rdf;
+  if (!rdf.on) return fail(h, TA_ERR_INVALID, "ta_md_get_rdf: the pair distributions are off (ta_md_set_rdf)");
+  if (!rdf.sched.valid)
+    return fail(h, TA_ERR_INVALID, "ta_md_get_rdf: a ta_md_run failed and left the counts invalid; call ta_md_set_rdf or "
+                                   "ta_md_init again");
+  return guarded(h, [&]() {
+    const size_t E = (size_t)h->n_elements, n = h->keep_natoms.size() * E * E * (size_t)rdf.p.n_bins;
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the counts are copied as they are");
+    if (counts && n) HIP_CHECK(hipMemcpy(counts, rdf.acc.ptr, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (info) {
+      info[0] = rdf.sched.taken();
+      info[1] = rdf.p.n_bins;
+      info[2] = rdf.p.sample_every;
+      info[3] = rdf.sched.last;
+    }
+    if (r_max) *r_max = rdf.p.r_max;
+  });
+}
+
+int ta_md_noise(ta_handle h, int64_t step, double *xi, double *eta) {
+  if (!h) return TA_ERR_INVALID;
+  if (!xi || !eta) return fail(h, TA_ERR_INVALID, "ta_md_noise: null argument");
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_noise: no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_noise called before ta_md_init");
+  if (step < 0) return fail(h, TA_ERR_INVALID, "ta_md_noise: step must be >= 0");
+  return guarded(h, [&]() {
+    const size_t N = h->keep_species.size();
+    if (!N) return;
+    auto &noise = h->md.langevin.noise;
+    noise.ensure(6 * N);
+    ta::launch_md_noise(h->md.langevin.seed, step, (long long)N, noise.ptr, noise.ptr + 3 * N, h->stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    HIP_CHECK(hipMemcpy(xi, noise.ptr, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(eta, noise.ptr + 3 * N, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+  });
+}
+
+int ta_md_set_barostat(ta_handle h, const ta_md_barostat_params *p) {
+  if (!h) return TA_ERR_INVALID;
+  if (p && !std::isfinite(p->taup)) return fail(h, TA_ERR_INVALID, "ta_md_set_barostat: taup must be finite");
+  if (!p || !(p->taup > 0.0)) {
+    h->md.baro.on = false;
+    return TA_OK;
+  }
+  if (!std::isfinite(p->pressure)) return fail(h, TA_ERR_INVALID, "ta_md_set_barostat: pressure must be finite");
+  if (!std::isfinite(p->compressibility) || p->compressibility < 0.0)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_barostat: compressibility must be finite and >= 0");
+  if (!p->isotropic && !p->mask[0] && !p->mask[1] && !p->mask[2])
+    return fail(h, TA_ERR_INVALID, "ta_md_set_barostat: mask leaves no axis of the cell free");
+  h->md.baro.p = *p;
+  h->md.baro.on = true;
+  return TA_OK;
+}
+
+int ta_md_get_cell(ta_handle h, double *cells) {
+  if (!h) return TA_ERR_INVALID;
+  if (!cells) return fail(h, TA_ERR_INVALID, "ta_md_get_cell: null argument");
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_cell: no resident batch");
+  // (between runs ref_cells is the image of the device's cells)
+  const size_t F = h->keep_natoms.size();
+  if (F) std::memcpy(cells, h->ref_cells.data(), 9 * F * sizeof(double));
+  return TA_OK;
+}
+
+int ta_md_get_records(ta_handle h, double *volume, double *press) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_records: no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_get_records called before ta_md_init");
+  const auto &baro = h->md.baro;
+  if (!baro.rec_valid)
+    return fail(h, TA_ERR_INVALID, "ta_md_get_records: the last ta_md_run of this batch had no barostat");
+  if (volume && !baro.rec_volume.empty())
+    std::memcpy(volume, baro.rec_volume.data(), baro.rec_volume.size() * sizeof(double));
+  if (press && !baro.rec_press.empty())
+    std::memcpy(press, baro.rec_press.data(), baro.rec_press.size() * sizeof(double));
+  return TA_OK;
+}
+
+int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t record_every, double *epot,
+              double *ekin, int32_t *n_rebuilds) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_run: no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_run called before ta_md_init (ta_set_frames drops the MD state)");
+  if (n_steps < 0 || record_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_run: n_steps >= 0 and record_every >= 1 are needed");
+  if (!std::isfinite(dt)) return fail(h, TA_ERR_INVALID, "ta_md_run: dt must be finite");
+  MdState &md = h->md;
+  ResidentLoop &res = h->res;
+  if (md.langevin.friction > 0.0 && dt < 0.0) return fail(h, TA_ERR_INVALID, "ta_md_run: Langevin dynamics needs dt >= 0");
+  const bool baro = md.baro.on;
+  if (baro) {
+    const size_t F = h->keep_natoms.size();
+    for (size_t f = 0; f < F; ++f) {
+      for (int k = 0; k < 3; ++k)
+        if (!h->keep_pbc[3 * f + k])
+          return fail(h, TA_ERR_INVALID, "ta_md_run: the barostat is on and frame " + std::to_string(f) +
+                                         " is not periodic along all three axes");
+      const double *c = h->ref_cells.data() + 9 * f;
+      const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
+      if (!std::isfinite(det) || !(std::fabs(det) > 0.0))
+        return fail(h, TA_ERR_INVALID, "ta_md_run: the barostat is on and the cell of frame " + std::to_string(f) + " is singular");
+    }
+  }
+  const bool nhc = md.nhc.on;
+  if (nhc) {
+    const size_t F = h->keep_natoms.size();
+    for (size_t f = 0; f < F; ++f)
+      if (3 * (int64_t)h->keep_natoms[f] - (int64_t)md.nhc.p.dof_removed < 1)
+        return fail(h, TA_ERR_INVALID, "ta_md_run: the Nose-Hoover chain is on and frame " + std::to_string(f) +
+                                       " has fewer than one degree of freedom (3 n_atoms - dof_removed)");
+  }
+  if (md.corr.on && baro)
+    return fail(h, TA_ERR_INVALID, "ta_md_run: sampling (ta_md_set_sampling) and the barostat (ta_md_set_barostat) are both "
+                                   "on; displacements in a moving cell are not defined: switch one of them off");
+  if (md.rdf.on && baro)
+    return fail(h, TA_ERR_INVALID, "ta_md_run: the pair distributions (ta_md_set_rdf) and the barostat (ta_md_set_barostat) are "
+                                   "both on; normalising the counts needs one volume: switch one of them off");
+  if (n_rebuilds) *n_rebuilds = 0;
+  want |= TA_WANT_ENERGY | TA_WANT_FORCES;
+  want &= ~(uint32_t)TA_WANT_REUSE_DESCRIPTORS;
+  if (baro) want |= TA_WANT_VIRIAL;  // the pressure
+  md.baro.rec_valid = false;
+  md.nhc.rec_valid = false;
+  const bool corr_was_valid = md.corr.sched.suspend(), rdf_was_valid = md.rdf.sched.suspend();
+  res.cell_running = md.baro.running = baro;
+  const int rc = guarded(h, [&]() {
+    const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
+    hipStream_t s = h->stream;
+    const bool thermostat = md.berendsen.kT0 > 0.0, langevin = md.langevin.friction > 0.0;  // (never both)
+    // with Berendsen scaling one workgroup owns a whole frame: the factor needs the frame's kinetic energy
+    // (the barostat: the frame's three sums of m v_c^2; the Nose-Hoover chain: the kinetic energy again)
+    int chunk = ta::kMdChunk;
+    if (thermostat || baro || nhc)
+      for (size_t f = 0; f < F; ++f) chunk = std::max(chunk, h->keep_natoms[f]);
+    const int threads = (thermostat || baro || nhc) ? 1024 : 256;
+    md_plan_blocks(h, chunk);
+    const size_t n_blk = (size_t)res.n_blk, n_rec = (size_t)(n_steps / record_every) + 1;
+    md.epot.ensure(n_rec * F + 1);
+    md.ke.ensure(n_rec * n_blk + 1);
+    if (nhc) md.nhc.rec.ensure(n_rec * F + 1);
+    const std::vector<double> cells_at_entry(baro ? h->ref_cells : std::vector<double>());
+    if (baro) {  // every run starts on a list built for the resident cells: the cumulative scale is 1
+      md.baro.rec.ensure(4 * n_rec * F + 1);
+      md.baro.scale.ensure(3 * F + 1);
+      md.baro.ones.assign(3 * F, 1.0);
+      HIP_CHECK(hipStreamSynchronize(s));
+      if (F) HIP_CHECK(hipMemcpy(md.baro.scale.ptr, md.baro.ones.data(), 3 * F * sizeof(double), hipMemcpyHostToDevice));
+    }
+    resident_begin(h);
+
+    ta::MdLaunch a;
+    a.vel = md.vel.ptr;
+    a.mass = md.mass.ptr;
+    a.ref = res.ref.ptr;
+    a.blk_start = res.blk_start.ptr;
+    a.epot = md.epot.ptr;
+    a.ke_part = md.ke.ptr;
+    a.status = res.status.ptr;
+    a.status_host = const_cast<unsigned *>(res.host_words());
+    a.dt = dt;
+    a.kT0 = langevin ? md.langevin.kT0 : md.berendsen.kT0;
+    a.dt_over_tau = thermostat ? dt / md.berendsen.tau : 0.0;
+    a.langevin = langevin ? 1 : 0;
+    a.seed = md.langevin.seed;
+    a.c1 = a.c2 = a.c3 = a.c4 = a.c5 = 0.0;
+    if (langevin) {  // ASE's Langevin.updatevars with sigma_i = sqrt(2 kT0 fr) / sqrt(m_i)
+      const double fr = md.langevin.friction, sigma = std::sqrt(2.0 * md.langevin.kT0 * fr);
+      a.c1 = dt / 2.0 - dt * dt * fr / 8.0;
+      a.c2 = dt * fr / 2.0 - dt * dt * fr * fr / 8.0;
+      a.c3 = std::sqrt(dt) * sigma / 2.0 - std::pow(dt, 1.5) * fr * sigma / 8.0;
+      a.c5 = std::pow(dt, 1.5) * sigma / (2.0 * std::sqrt(3.0));
+      a.c4 = fr / 2.0 * a.c5;
+    }
+    const int64_t step0 = md.step;  // absolute index of this run's first step
+    a.lim2 = h->skin > 0.0 ? 0.25 * h->skin * h->skin : -1.0;  // skin = 0: every step rebuilds
+    a.n_frames = (int)F;
+    a.n_blk = (int)n_blk;
+    a.chunk = chunk;
+    a.baro = baro ? 1 : 0;
+    a.baro_iso = md.baro.p.isotropic ? 1 : 0;
+    a.cells = nullptr, a.virial = nullptr;
+    a.baro_scale = md.baro.scale.ptr;
+    a.baro_rec = md.baro.rec.ptr;
+    a.baro_p0 = md.baro.p.pressure;
+    a.baro_k = baro ? dt / md.baro.p.taup * md.baro.p.compressibility / 3.0 : 0.0;
+    for (int c = 0; c < 3; ++c) a.baro_mask[c] = md.baro.p.mask[c] ? 1 : 0;
+    a.skin = h->skin;
+    a.r_list = h->rmax + h->skin;
+    a.nhc = nhc ? 1 : 0;
+    a.nhc_chain = md.nhc.p.chain, a.nhc_loops = md.nhc.p.loops, a.nhc_dof = md.nhc.p.dof_removed;
+    a.nhc_kT0 = nhc ? md.nhc.p.kT0 : 0.0;
+    a.nhc_q = nhc ? md.nhc.p.kT0 * md.nhc.p.tau * md.nhc.p.tau : 0.0;
+    a.nhc_eta = md.nhc.eta.ptr, a.nhc_veta = md.nhc.veta.ptr, a.nhc_rec = md.nhc.rec.ptr;
+    // Sampling: the launch of step k holds the whole-step state t = step0 + k and samples it when the schedule
+    // says so (ta_schedule.h). Sample number and ring slot are functions of t alone, so the launches that returned
+    // early behind a stale list and are enqueued again after the rebuild write what they would have written.
+    const bool sampling = md.corr.on && corr_was_valid && N > 0;
+    const ta::SampleSchedule &corr_sched = md.corr.sched;
+    const int64_t samp_L = md.corr.p.n_lags;
+    ta::MdCorrLaunch c;
+    c.ring_x = md.corr.ring_x.ptr, c.ring_v = md.corr.ring_v.ptr;
+    c.blk_start = md.corr.blk.ptr;
+    c.part = md.corr.part.ptr;
+    c.acc_v = md.corr.acc.ptr;
+    c.acc_x = sampling ? md.corr.acc.ptr + F * (size_t)h->n_elements * (size_t)samp_L : nullptr;
+    c.status = res.status.ptr;
+    c.n_atoms = (long long)N;
+    c.n_lags = (int)samp_L, c.n_elements = h->n_elements, c.n_frames = (int)F, c.n_chunks = md.corr.n_chunks;
+    // Pair distributions: the state t = step0 + k is counted by a launch IN FRONT OF the integrator launch of
+    // step k, whose drift leaves x(t). With seq = k the integrator's predicate skips exactly the states that
+    // were reached on a stale list; after the rebuild the launch is enqueued again with the rest and counts
+    // then.
+    const bool rdf_run = md.rdf.on && rdf_was_valid && N > 0;
+    const ta::SampleSchedule &rdf_sched = md.rdf.sched;
+    ta::MdRdfLaunch g;
+    g.blk_start = md.rdf.blk.ptr;
+    g.counts = md.rdf.acc.ptr;
+    g.status = res.status.ptr;
+    g.n_bins = md.rdf.p.n_bins, g.n_elements = h->n_elements, g.n_frames = (int)F;
+    g.n_blk = md.rdf.n_blk, g.chunk = md.rdf.chunk;
+    g.dr = rdf_run ? md.rdf.p.r_max / (double)md.rdf.p.n_bins : 1.0;
+    auto integrate = [&](int k, bool drift) {
+      if (rdf_run && rdf_sched.due(step0, k)) {
+        g.pos = h->db.pos;
+        g.cells = h->db.cells;
+        g.species = h->db.species;
+        g.atom_start = h->db.atom_start;
+        g.pair_start = h->pair_start.ptr;  // the resident list, not the exact one filtered from it
+        g.pair_i = h->pair_i.ptr;
+        g.pair_j = h->pair_j.ptr;
+        g.pair_shift = h->pair_shift.ptr;
+        g.seq = (unsigned)k;
+        ta::launch_md_rdf(g, s);
+        HIP_CHECK(hipGetLastError());
+      }
+      // (a rebuild may have moved the batch's arrays: the pointers are taken at every launch)
+      a.pos = h->db.pos;
+      a.forces = h->db.forces;
+      a.energy = h->db.energy;
+      a.atom_start = h->db.atom_start;
+      a.cells = h->db.cells;
+      a.virial = h->db.virial;
+      a.seq = (unsigned)k;
+      a.step = (long long)(step0 + k);  // (a step redone after a rebuild keeps its index)
+      a.kick2 = k > 0 ? 1 : 0;  // the state at entry is a whole step
+      a.drift = drift ? 1 : 0;
+      a.rec = (k % record_every == 0) ? (long long)(k / record_every) : -1;
+      a.snap_x = a.snap_v = nullptr;
+      const bool due = sampling && corr_sched.due(step0, k);
+      if (due) {
+        c.n = (long long)corr_sched.index(step0 + k);
+        const size_t slot = (size_t)(c.n % samp_L);
+        a.snap_x = md.corr.ring_x.ptr + slot * 3 * N;
+        a.snap_v = md.corr.ring_v.ptr + slot * 3 * N;
+      }
+      ta::launch_md_integrate(a, threads, s);
+      HIP_CHECK(hipGetLastError());
+      if (due) {  // directly behind the launch that sampled, under the same predicate
+        c.species = h->db.species;
+        c.atom_start = h->db.atom_start;
+        c.seq = (unsigned)k;
+        ta::launch_md_correlate(c, s);
+        HIP_CHECK(hipGetLastError());
+      }
+    };
+
+    h->jvp_valid = false;
+    compute_impl(h, want, false, nullptr);  // F_0 and the record of the state at entry
+    int rebuilds = 0;
+    resident_steps(h, "ta_md_run", n_steps, want, [&](int q) { integrate(q, true); },
+                   [](int, int) { return -1; }, &rebuilds, n_rebuilds);
+    integrate(n_steps, false);  // the pending half-kick and the last record
+    HIP_CHECK(hipStreamSynchronize(s));
+    h->upload_pending = false;
+    md.step = step0 + n_steps;
+    if (sampling) md.corr.sched.finish(md.step);
+    md.corr.sched.valid = corr_was_valid;
+    if (rdf_run) md.rdf.sched.finish(md.step);
+    md.rdf.sched.valid = rdf_was_valid;
+    if (n_rebuilds) *n_rebuilds = rebuilds;
+    if (baro && F) {
+      std::vector<double> rec(4 * n_rec * F);
+      HIP_CHECK(hipMemcpy(rec.data(), md.baro.rec.ptr, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
+      md.baro.rec_volume.resize(n_rec * F);
+      md.baro.rec_press.resize(3 * n_rec * F);
+      for (size_t j = 0; j < n_rec * F; ++j) {
+        md.baro.rec_volume[j] = rec[4 * j];
+        for (int c = 0; c < 3; ++c) md.baro.rec_press[3 * j + c] = rec[4 * j + 1 + c];
+      }
+      resident_final_cells(h, "ta_md_run", want, &rebuilds, n_rebuilds);
+      if (h->relax.cell.on && h->relax.valid &&
+          std::memcmp(cells_at_entry.data(), h->ref_cells.data(), 9 * F * sizeof(double)) != 0) {
+        // the barostat's cells replace the relaxed ones: they are h0 from here on, G = I, the cell velocities 0
+        HIP_CHECK(hipMemcpy(h->relax.cell.h0.ptr, h->ref_cells.data(), 9 * F * sizeof(double), hipMemcpyHostToDevice));
+        h->relax.cell.reset_deformation(F);
+      }
+      md.baro.rec_valid = true;
+    }
+    if (nhc) {
+      md.nhc.rec_host.resize(n_rec * F);
+      if (F) HIP_CHECK(hipMemcpy(md.nhc.rec_host.data(), md.nhc.rec.ptr, n_rec * F * sizeof(double), hipMemcpyDeviceToHost));
+      md.nhc.rec_valid = true;
+    }
+    if (epot && F) HIP_CHECK(hipMemcpy(epot, md.epot.ptr, n_rec * F * sizeof(double), hipMemcpyDeviceToHost));
+    if (ekin && F) {
+      std::vector<double> part(n_rec * n_blk);
+      HIP_CHECK(hipMemcpy(part.data(), md.ke.ptr, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+      const std::vector<int32_t> &start = res.blk_start_host;
+      for (size_t r = 0; r < n_rec; ++r)
+        for (size_t f = 0; f < F; ++f) {
+          double t = 0.0;
+          for (int32_t b = start[f]; b < start[f + 1]; ++b) t += part[r * n_blk + (size_t)b];
+          ekin[r * F + f] = t;
+        }
+    }
+  });
+  res.cell_running = md.baro.running = false;
+  return rc;
+}
+
+int ta_md_get_state(ta_handle h, double *positions, double *velocities) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_state: no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_get_state called before ta_md_init");
+  return guarded(h, [&]() {
+    const size_t N = h->keep_species.size();
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    h->upload_pending = false;
+    if (positions && N) HIP_CHECK(hipMemcpy(positions, h->db.pos, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+    if (velocities && N) HIP_CHECK(hipMemcpy(velocities, h->md.vel.ptr, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+  });
+}
+
+}  // extern "C"

@@ -1,0 +1,412 @@
+// The handle behind the C ABI and what the host translation units (ta_api, ta_api_md, ta_api_relax,
+// ta_resident .hip) share: error mapping, self-freeing buffers, and the helpers that ta_api.hip defines
+// for the others. Private to the library; the public interface is include/tensoralloy_amd.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <functional>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "ta_device.h"
+#include "ta_internal.h"
+#include "ta_launch.h"
+#include "ta_relax.h"
+#include "ta_schedule.h"
+
+namespace ta {
+namespace host {
+
+struct HipError : std::runtime_error {
+  using std::runtime_error::runtime_error;
+};
+
+#define HIP_CHECK(expr)                                                                                    \
+  do {                                                                                                     \
+    hipError_t _e = (expr);                                                                                \
+    if (_e != hipSuccess)                                                                                  \
+      throw ::ta::host::HipError(std::string(#expr) + ": " + hipGetErrorString(_e) + " (" __FILE__ ":" +   \
+                                 std::to_string(__LINE__) + ")");                                          \
+  } while (0)
+
+// grow-only device buffer; frees itself with its owner (the device of the handle must be current)
+template <typename T>
+struct DevBuf {
+  T *ptr = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { release(); }
+  void ensure(size_t n) {
+    if (n <= cap) return;
+    // the old allocation stays valid until the new one exists: a failed hipMalloc must not
+    // leave a dangling pointer behind (contents are not carried over: every user refills)
+    size_t want = n + n / 8 + 64;
+    T *fresh = nullptr;
+    hipError_t e = hipMalloc((void **)&fresh, want * sizeof(T));
+    if (e != hipSuccess && ptr) {  // retry once with the old block returned first
+      (void)hipGetLastError();
+      HIP_CHECK(hipFree(ptr));
+      ptr = nullptr;
+      cap = 0;
+      e = hipMalloc((void **)&fresh, want * sizeof(T));
+    }
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      throw HipError(std::string("hipMalloc of ") + std::to_string(want * sizeof(T)) + " bytes: " +
+                     hipGetErrorString(e));
+    }
+    if (ptr) HIP_CHECK(hipFree(ptr));
+    ptr = fresh;
+    cap = want;
+  }
+  // exactly n elements (a ring may take gigabytes: no head room); false when the device has no room
+  bool try_exact(size_t n) {
+    release();
+    T *fresh = nullptr;
+    if (hipMalloc((void **)&fresh, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+    ptr = fresh;
+    cap = std::max<size_t>(n, 1);
+    return true;
+  }
+  void release() {
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    cap = 0;
+  }
+};
+
+// grow-only page-locked host buffer (staging for the packed uploads / downloads); frees itself likewise
+struct PinnedBuf {
+  char *ptr = nullptr;
+  size_t cap = 0;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf &) = delete;
+  PinnedBuf &operator=(const PinnedBuf &) = delete;
+  ~PinnedBuf() { release(); }
+  void ensure(size_t n) {
+    if (n <= cap) return;
+    if (ptr) HIP_CHECK(hipHostFree(ptr));
+    ptr = nullptr;
+    cap = 0;
+    size_t want = n + n / 8 + 256;
+    HIP_CHECK(hipHostMalloc((void **)&ptr, want, hipHostMallocDefault));
+    cap = want;
+  }
+  void release() {
+    if (ptr) (void)hipHostFree(ptr);
+    ptr = nullptr;
+    cap = 0;
+  }
+};
+
+struct ChunkPlan {
+  ta::AngChunk ch;
+  int nb, ng, nz;
+};
+
+// What the loop of the device-resident runs (ta_resident.hip) keeps, for ta_md_run and ta_relax_run alike: the
+// status words and their page-locked twins; the positions (and, in a run that moves the cells, the cells) the
+// resident list was built for, the device twins of ref_pos / ref_cells as of list build number `ref_builds`;
+// the workgroup layout (`chunk` atoms each) that blk_start holds.
+struct ResidentLoop {
+  DevBuf<unsigned> status;
+  PinnedBuf status_host;
+  DevBuf<double> ref, ref_cells;
+  int64_t ref_builds = -1;
+  DevBuf<int32_t> blk_start;
+  std::vector<int32_t> blk_start_host;
+  int chunk = 0, n_blk = 0;
+  bool cell_running = false;  // a run that moves the cells (cell relaxation, barostat) is under way: rebuilds take them from the device
+  volatile unsigned *host_words() const { return reinterpret_cast<volatile unsigned *>(status_host.ptr); }
+};
+
+// device-resident MD loop (ta_api_md.hip; the integrator launch is in ta_md.hip): masses, velocities, the
+// records of the running ta_md_run, the steps integrated since ta_md_init (the noise's step counter and the
+// clock of the sample schedules), and one struct per feature with its setting, buffers and host records
+struct MdState {
+  bool valid = false;
+  DevBuf<double> mass, vel, epot, ke;
+  int64_t step = 0;
+  struct {  // ta_md_set_thermostat; off while kT0 == 0
+    double kT0 = 0.0, tau = 0.0;
+  } berendsen;
+  struct {  // ta_md_set_langevin; off while friction == 0: bath, friction, the key of the noise, ta_md_noise's scratch
+    double kT0 = 0.0, friction = 0.0;
+    uint64_t seed = 0;
+    DevBuf<double> noise;
+  } langevin;
+  // Nose-Hoover chain (ta_md_set_nose_hoover): the chain state [F][TA_MD_MAX_CHAIN] (zeroed by ta_md_init), the
+  // record of the running ta_md_run and the host's copy [n_rec][F] of the last successful run's chain terms
+  struct {
+    bool on = false;
+    ta_md_nhc_params p = {0.0, 0.0, 3, 1, 0};
+    DevBuf<double> eta, veta, rec;
+    bool rec_valid = false;
+    std::vector<double> rec_host;
+  } nhc;
+  // Berendsen barostat (ta_md_set_barostat): the cumulative scale of every frame since its list was built with
+  // the ones that reset it, the device records {V, P_x, P_y, P_z} of the running ta_md_run and the host's copy
+  // of the last successful run's, [n_rec][F] and [n_rec][F][3]
+  struct {
+    bool on = false;
+    bool running = false;  // a barostat run is under way: a rebuild resets the cumulative scale
+    ta_md_barostat_params p = {0.0, 0.0, 0.0, {1, 1, 1}, 1};
+    DevBuf<double> scale, rec;
+    std::vector<double> ones;
+    bool rec_valid = false;
+    std::vector<double> rec_volume, rec_press;
+  } baro;
+  // Sampling (ta_md_set_sampling): the rings [L][N][3], the accumulators [2][F][E][L] (v . v, then |dx|^2), the
+  // correlation launch's partials and chunk layout
+  struct Corr {
+    bool on = false;
+    ta_md_sampling_params p = {0, 1};
+    DevBuf<double> ring_x, ring_v, acc, part;
+    DevBuf<int32_t> blk;
+    int n_chunks = 0;
+    SampleSchedule sched;
+    void release() {  // frees what sampling holds on the device; the setting stays
+      for (auto *b : {&ring_x, &ring_v, &acc, &part}) b->release();
+      blk.release();
+      n_chunks = 0;
+      sched.valid = false;
+      sched.last = -1;
+    }
+  } corr;
+  // Pair distributions (ta_md_set_rdf): the counts [F][E][E][n_bins] and the launch's workgroup layout
+  struct Rdf {
+    bool on = false;
+    ta_md_rdf_params p = {0.0, 0, 1};
+    DevBuf<unsigned long long> acc;
+    DevBuf<int32_t> blk;
+    int n_blk = 0, chunk = 0;
+    SampleSchedule sched;
+    void release() {  // frees what the pair distributions hold on the device; the setting stays
+      acc.release();
+      blk.release();
+      n_blk = 0;
+      sched.valid = false;
+      sched.last = -1;
+    }
+  } rdf;
+};
+
+// device-resident relaxation (ta_api_relax.hip; the launches are in ta_relax.hip): FIRE velocities of its own,
+// the mask of fixed atoms (and the host's copy of ta_relax_init's), the two copies of the per-frame state with
+// the host's image of the current one, the workgroups' partial sums and the count of converged frames
+struct RelaxState {
+  bool valid = false;
+  ta_fire_params p = {0.1, 1.0, 0.2, 1.1, 0.5, 0.1, 0.99, 5};
+  DevBuf<double> vel, part;
+  DevBuf<uint8_t> fixed;
+  DevBuf<ta::RelaxFrameState> state;
+  DevBuf<int> count;
+  std::vector<ta::RelaxFrameState> state_host;
+  std::vector<uint8_t> fixed_host;
+  // cell mode (ta_relax_set_cell): h0 and the cell factor of every frame, the deformation gradient and the cell
+  // velocity (two copies on the device like `state`, the current one on the host between runs)
+  struct {
+    bool on = false;
+    ta_relax_cell_params p = {0.0, 0.0, {1, 1, 1, 1, 1, 1}, 0, 0};
+    DevBuf<double> h0, cf, G, vel, fmax2;
+    std::vector<double> G_host, vel_host;
+    void reset_deformation(size_t F) {  // G = I and the cell at rest, for F frames
+      G_host.assign(9 * F, 0.0);
+      for (size_t f = 0; f < F; ++f) G_host[9 * f] = G_host[9 * f + 4] = G_host[9 * f + 8] = 1.0;
+      vel_host.assign(9 * F, 0.0);
+    }
+  } cell;
+  // band mode (ta_relax_set_band; the band launches are in ta_neb.hip): the frames are the images of a nudged
+  // elastic band and FIRE runs on the band forces with the whole band as ONE pseudo-frame. The band owns its
+  // force and tangent arrays, the partials of its two launches, the mask (the user's OR-ed with the two endpoint
+  // images), the two copies of the one FIRE record and the pseudo-frame's layout {atom_start[2], blk_start[2],
+  // climbing image}.
+  struct {
+    bool on = false;
+    bool ran = false;  // a band run left B, tau and the climbing image of the resident state
+    ta_band_params p = {0.1, 0, 0};
+    DevBuf<double> force, tau, part;
+    DevBuf<uint8_t> fixed;
+    DevBuf<ta::RelaxFrameState> state;
+    DevBuf<int32_t> layout;
+    ta::RelaxFrameState state_host = {};
+    std::vector<double> energy_host;  // [F] image energies of the state the last band run ended on
+  } band;
+};
+
+}  // namespace host
+}  // namespace ta
+
+struct ta_context {
+  template <typename T>
+  using DevBuf = ta::host::DevBuf<T>;
+  using PinnedBuf = ta::host::PinnedBuf;
+  using ChunkPlan = ta::host::ChunkPlan;
+
+  ta::Options opt;  // the environment switches as they stood when ta_create ran
+  int device = 0;
+  hipStream_t stream = nullptr;      // stream all work is enqueued on
+  hipStream_t own_stream = nullptr;  // created by ta_create
+  int kind = 0;
+  int n_elements = 0;
+  int activation = 0;
+  double rmax = 0.0;
+  ta::SFParams sf;
+  std::vector<ChunkPlan> chunks;     // first-generation kernels: up to 2 betas per launch
+  std::vector<ChunkPlan> chunks_v2;  // second-generation kernels: one beta per launch
+  bool use_v2 = false;
+  ta::MlpDev *mlp_dev = nullptr;     // device copy of mlp[0..n_elements)
+  ta::MlpDev mlp[ta::kMaxElements];
+  // temperature-dependent head (ta_model_desc.finite_temperature): nets H[el], U[el], S[el]
+  bool td = false, td_sommerfeld = false;
+  int td_act = 0, td_K = 0;
+  ta::MlpDev td_nets[3 * ta::kMaxElements];
+  ta::MlpDev *td_dev = nullptr;
+  std::vector<void *> model_allocs;
+  ta::EamModel *eam = nullptr;
+  ta::GrapModel *grap = nullptr;
+
+  ta::HostPairs hp;
+  ta::DeviceBatch db;
+  bool have_batch = false;
+  uint32_t last_want = 0;
+
+  // Inputs travel in one packed upload: [pos | cells | grids | species | frame_of_atom |
+  // atom_start | elem_atoms | blk_center]; results come back in one packed download:
+  // [energy F | virial 9F | atomic N | forces 3N].
+  PinnedBuf stage_in, stage_out;
+  DevBuf<char> inbuf;
+  DevBuf<double> results;
+  size_t o_blk = 0;  // byte offset of blk_center in the packed input
+  int res_n_blk = 0;  // runs of the resident list's packing (db.n_blk is the exact list's while `filtered`)
+  DevBuf<double> rec, part4, G, dEdG, g, wat, bpart, fown, benergy, mlp_scratch;
+  DevBuf<double> td_T, td_u, td_s;  // electron temperature per frame; U and S per atom
+  DevBuf<unsigned long long> masks;
+  DevBuf<uint32_t> job_word;
+  DevBuf<int32_t> job_count;
+  // triangle-once backward pass (ta_set_triangles): the owned job lists, the handle's option, whether the
+  // resident batch's cells admit the ownership rule, and the builds the last backward pass ran
+  DevBuf<uint32_t> job_word_own;
+  DevBuf<int32_t> job_count_own;
+  bool triangles = true;
+  // the last second-generation forward pass left the full job list (db.job_word / job_count) behind: it
+  // does not when every backward launch of its evaluation read the owned lists (forward_v2_launches)
+  bool full_jobs_valid = false;
+  bool tri_cells_ok = false;
+  bool tri_cells_wide_ok = false;  // every periodic width exceeds rmax + skin: what the cell relaxation asks for
+  int last_bwd_variant = 0;
+  ta::MlpLaunchInfo last_mlp_launch;  // ta_mlp_launch_info
+  DevBuf<int32_t> pair_start, seg_start, pair_i, pair_j, pair_shift, pair_rev;
+  ta::NlGrid *d_grids = nullptr;  // view into inbuf
+  // device neighbour list (ta_nlist.hip)
+  DevBuf<int32_t> nl_wrap, nl_binid, nl_bin_count, nl_bin_start, nl_bin_cursor, nl_bin_atoms, nl_counts;
+  DevBuf<unsigned long long> nl_stats, nl_zero;
+  unsigned long long *nl_stats_ptr = nullptr;  // statistics block of the builder that made the list
+  bool nl_sorted = false;  // list in key order (one-pass builder): reverse pairs by binary search
+  bool nl_rev_done = false;  // ... and the reverse index is already there (launched behind the pairs)
+  bool nl_zero_clean = false;  // nl_zero is all zero where the next list needs it (see nl_build)
+  int64_t nl_zero_atoms = -1;
+  int nl_zero_bins = -1;
+  DevBuf<double> hvp_buf;  // ta_hessian_vectors: tangents in, force / virial tangents out
+#ifdef TA_PHASE_STAMPS
+  DevBuf<unsigned long long> stamp_buf;
+#endif
+  DevBuf<ta::NlRec> nl_recs;
+  bool pairs_on_device = false;  // hp holds only the counts; ta_get_pairs downloads on demand
+  bool descriptors_valid = false;  // db.G holds the resident batch's descriptors
+  DevBuf<double> train_scratch, train_partial, train_grad, train_coeff;
+  // force / stress terms of the loss: J[c][p] = dG_c / dD_p of the resident batch (made once per
+  // batch by one backward launch per descriptor channel), the direction and its images
+  DevBuf<double> jvp_J, tan_dD, tan_dG, tan_dir;
+  DevBuf<double> filt_scratch;  // ta_grap_loss_gradient: pair vectors, w-dot, per-pair adjoints, partial sums
+  bool jvp_valid = false;
+
+  // MD loop (ta_set_skin / ta_update_positions): the list covers rmax + skin and is kept while no
+  // atom has moved more than skin / 2 from where it was when the list was built
+  double skin = 0.0;
+  double r_list = 0.0;                         // rmax + skin: cutoff of the resident list
+  std::vector<int32_t> keep_species;           // [N]
+  std::vector<int32_t> keep_natoms, keep_pbc;  // [F], [3 F]: what a rebuild needs besides stage_in
+  std::vector<double> ref_pos, ref_cells;      // positions / cells the resident list was built for
+  size_t o_pos = 0, o_cells = 0, o_species = 0;  // byte offsets in the packed input
+  // exact list of the current step, extracted on the device from the resident skin list (nl_filter)
+  DevBuf<int32_t> ex_pair_i, ex_pair_j, ex_pair_shift, ex_pair_rev, ex_pair_start, ex_pair_stop, ex_seg_start, ex_counts,
+      ex_map, ex_blk, ex_slot_q;
+  DevBuf<ta::BlockHeader> ex_hdr;              // the exact list's run headers (DeviceBatch::blk_hdr)
+  bool filtered = false;                       // db points at the ex_* arrays
+  // a copy out of stage_in may still be in flight (set by ta_update_positions, cleared by every wait
+  // for the stream on the step path): whoever rewrites stage_in waits for the stream first. (An event
+  // recorded behind the copy cost a 5 us bubble between the copy and the next kernel of every MD step.)
+  bool upload_pending = false;
+  // ta_step: the next compute mirrors its results into stage_out (frame_reduce_kernel); `mirror_want` = the
+  // want bits whose results the page-locked image holds right now (0: none), cleared by whoever reuses stage_out
+  bool mirror_next = false;
+  uint32_t mirror_want = 0;
+  int64_t n_list_builds = 0, n_list_reuses = 0;
+
+  ta::host::ResidentLoop res;  // ta_md_run and ta_relax_run: the loop they share
+  ta::host::MdState md;
+  ta::host::RelaxState relax;
+
+  hipEvent_t ev[2 * TA_N_KERNEL_SLOTS + 2] = {nullptr};
+  std::string err;
+};
+
+namespace ta {
+namespace host {
+
+// ta_api.hip
+int fail(ta_context *h, int code, const std::string &msg);  // keeps the message for ta_last_error; returns code
+// `to_host`: the copy direction of the fallback, which Options::staged_copy_dma always takes (A/B switch)
+void staged_copy(double *dst, const double *src, size_t n, bool to_host, const ta::Options &opt, hipStream_t s);
+void wait_stream(hipStream_t s, const ta::Options &opt);
+void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms);
+void apply_filter(ta_context *h);
+// the resident frames again with new coordinates (cells: null = unchanged): the rebuild path of
+// ta_update_positions and the resident runs; throws
+void rebuild_list(ta_context *h, const double *positions, const double *cells);
+
+// ta_resident.hip
+// workgroups of the integrator launch: `chunk` consecutive atoms of one frame each, at least one per frame
+void md_plan_blocks(ta_context *h, int chunk);
+// what every resident run does before its first launch: where the host built the list that is resident, its
+// positions go up once as res.ref; the status words are reset
+void resident_begin(ta_context *h);
+// The loop that ta_md_run and ta_relax_run share (see ta_resident.hip). Returns the steps done; throws.
+int resident_steps(ta_context *h, const char *who, int n_steps, uint32_t want, const std::function<void(int)> &enqueue,
+                   const std::function<int(int, int)> &finished, int *rebuilds, int32_t *n_rebuilds);
+// after a run that moved the cells (F > 0): where they differ from ref_cells, one list for the final state and
+// the evaluation again on it, counted in *rebuilds and *n_rebuilds (may be null). `who` names the caller in the
+// messages.
+void resident_final_cells(ta_context *h, const char *who, uint32_t want, int *rebuilds, int32_t *n_rebuilds);
+
+// runs fn with the handle's device current and maps what it throws to the error codes of the C ABI
+template <typename F>
+int guarded(ta_context *h, F &&fn) {
+  try {
+    if (h) HIP_CHECK(hipSetDevice(h->device));
+    fn();
+    return TA_OK;
+  } catch (const HipError &e) {
+    return fail(h, TA_ERR_HIP, e.what());
+  } catch (const std::domain_error &e) {
+    return fail(h, TA_ERR_UNSUPPORTED, e.what());
+  } catch (const std::invalid_argument &e) {
+    return fail(h, TA_ERR_INVALID, e.what());
+  } catch (const std::bad_alloc &) {
+    return fail(h, TA_ERR_NOMEM, "host allocation failed");
+  } catch (const std::exception &e) {
+    return fail(h, TA_ERR_INVALID, e.what());
+  }
+}
+
+}  // namespace host
+}  // namespace ta

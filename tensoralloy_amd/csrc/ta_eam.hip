@@ -48,27 +48,12 @@
 
 #include "ta_device.h"
 #include "ta_dual.h"
+#include "ta_launch.h"
 #include "ta_math.h"
 #include "ta_mlp_tile.h"
 #include "ta_reduce.h"
 
 namespace ta {
-
-struct EamModel;
-void eam_destroy(EamModel *);
-// weight gradients (ta_train.hip)
-int mlp_param_count(const MlpDev &mlp);
-size_t mlp_grad_scratch_doubles(const MlpDev &mlp, int n_atoms);
-size_t mlp_grad_partial_doubles(const MlpDev &mlp, int n_atoms);
-void launch_mlp_grad_rows(const MlpDev &mlp, int activation, const int32_t *atoms, int n_rows,
-                          const double *x, const double *row_coeff, const int32_t *frame_of_atom,
-                          const double *frame_coeff, double *scratch, double *partial, double *grad,
-                          hipStream_t s);
-size_t mlp_grad2_scratch_doubles(const MlpDev &mlp, int n_atoms);
-void launch_mlp_grad2_rows(const MlpDev &mlp, int activation, const int32_t *atoms, int n_rows, const double *x,
-                           const double *xdot, const double *row_coeff, const int32_t *frame_of_atom,
-                           const double *frame_coeff, double *scratch, double *partial, double *grad,
-                           hipStream_t s);
 
 namespace {
 

@@ -31,6 +31,7 @@
 
 #include "ta_device.h"
 #include "ta_dual.h"
+#include "ta_launch.h"
 #include "ta_math.h"
 
 namespace ta {
@@ -1823,7 +1824,6 @@ void grap_mark_trained(GrapModel *g) {
 void grap_suspend_filter_tables(GrapModel *g, bool suspend) { g->p.tab = suspend ? nullptr : g->tab; }
 
 // ---- training the filter network ----------------------------------------------------------------------
-void launch_grad_reduce(const double *partial, int n_blocks, int n_params, double *grad, hipStream_t s);
 
 namespace {
 NetGradLayout net_grad_layout(const GrapModel *g) {

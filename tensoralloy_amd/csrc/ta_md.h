@@ -1,4 +1,4 @@
-// Arguments of the MD integrator launch (ta_md.hip), filled by ta_md_run (ta_api.hip).
+// Arguments of the MD integrator launch (ta_md.hip), filled by ta_md_run (ta_api_md.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

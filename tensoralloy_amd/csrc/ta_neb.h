@@ -1,5 +1,5 @@
 // Arguments of the two band launches of a nudged-elastic-band step (ta_neb.hip), filled by ta_relax_run
-// (ta_api.hip) in band mode (ta_relax_set_band). They run between the evaluation and the two FIRE launches.
+// (ta_api_relax.hip) in band mode (ta_relax_set_band). They run between the evaluation and the two FIRE launches.
 #pragma once
 #include <hip/hip_runtime.h>
 

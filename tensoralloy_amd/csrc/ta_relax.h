@@ -1,4 +1,4 @@
-// Arguments of the two launches of a FIRE step (ta_relax.hip), filled by ta_relax_run (ta_api.hip).
+// Arguments of the two launches of a FIRE step (ta_relax.hip), filled by ta_relax_run (ta_api_relax.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -24,11 +24,10 @@
 #include <stdexcept>
 
 #include "ta_device.h"
+#include "ta_launch.h"
 #include "ta_mlp_tile.h"
 
 namespace ta {
-
-void launch_grad_reduce(const double *partial, int n_blocks, int n_params, double *grad, hipStream_t s);
 
 namespace {
 
