@@ -511,7 +511,44 @@ int ta_step_view(ta_handle h, const double *positions, const double *cells, uint
  *                        is called again.
  *   ta_md_get_rdf        counts [n_frames][n_elements][n_elements][n_bins]; info [4] = {n_samples, n_bins,
  *                        sample_every, absolute step of the newest sample or -1}; *r_max. Any pointer may be
- *                        NULL. */
+ *                        NULL.
+ *
+ * Bond-angle distributions inside the loop (opt-in; with it never switched on nothing changes): the distribution of
+ * the angles j-i-k between the bonds of a centre i to its neighbours, the three-body companion of g_ab(r).
+ * Parameters: n_bins = B, sample_every = s and a symmetric bond cutoff rb[a][b] per pair of elements (r_bond: the
+ * same value for all pairs). The whole-step state of every absolute step t with t % s == 0, from the first such
+ * step at or behind the call that switched the feature on, is sampled, once, however the run is cut into calls and
+ * whatever steps are redone after a list rebuild (the schedule of ta_md_set_rdf, kept separately). A launch in
+ * front of the integrator launch of that step takes, for every centre i of species a, as neighbours the entries
+ * (j, S) of the resident neighbour list with
+ *     d = x_j - x_i + S . h  (fp64, positions unwrapped and cells as the device holds them),
+ *     d . d < rb[a][b]^2,    b = species of j
+ * A self-image, or two images of one atom, are neighbours like any other. Every unordered pair {(j, S), (k, S')}
+ * of distinct neighbours of i counts once:
+ *     u = d_ij, w = d_ik
+ *     theta = atan2(|u x w|, u . w)   in [0, pi]
+ *     kbin = min(B - 1, floor(theta / (pi / B)))
+ *     p = b E - b (b - 1) / 2 + (c - b)  for the species b <= c of the two neighbours,  P = E (E + 1) / 2
+ *     C[f][a][p][kbin] += 1           (unsigned 64-bit, integer atomics: exact, whatever the order)
+ * atan2 of cross and dot product needs no normalisation and is well conditioned at 0 and pi. A NaN counts
+ * nowhere; theta = pi belongs to the last bin. No volume enters: unlike the pair distributions this feature runs
+ * under the barostat, with the cells of the sampled state, and under every thermostat, independently of
+ * ta_md_set_sampling and ta_md_set_rdf.
+ *   ta_md_set_adf        NULL or n_bins == 0 switches it off (the default; always allowed) and frees the
+ *                        accumulators. r_bond_pairs [n_elements][n_elements], or NULL: r_bond for every pair
+ *                        (with r_bond_pairs given r_bond is not read). Switching on needs a resident batch and
+ *                        ta_md_init; it allocates the accumulators [n_frames][n_elements][P][n_bins], zeroes them
+ *                        and the sample counter (so does every further call). The life cycle is that of
+ *                        ta_md_set_rdf: ta_set_frames keeps the setting and drops the data with the MD state;
+ *                        ta_md_init starts from zero counts. TA_ERR_INVALID, with the argument named by
+ *                        ta_last_error and the setting left as it was: n_bins outside 0 .. TA_MD_MAX_BINS;
+ *                        sample_every < 1; a cutoff not finite, <= 0, or greater than max(rcut, acut) of the model
+ *                        (the neighbour list is not complete beyond that); r_bond_pairs not symmetric.
+ *                        TA_ERR_NOMEM when the device allocation fails; the feature is then off.
+ *   ta_md_run            A run that fails leaves the counts invalid: ta_md_get_adf is TA_ERR_INVALID until
+ *                        ta_md_set_adf or ta_md_init is called again.
+ *   ta_md_get_adf        counts [n_frames][n_elements][P][n_bins]; info [4] as ta_md_get_rdf; r_bond_pairs
+ *                        [n_elements][n_elements], the cutoffs in use. Any pointer may be NULL. */
 #define TA_MD_MAX_CHAIN 8
 #define TA_MD_MAX_LAGS 4096
 #define TA_MD_MAX_BINS 4096
@@ -520,6 +557,11 @@ typedef struct {
   int32_t n_bins;        /* B, 1 .. TA_MD_MAX_BINS; 0 switches the feature off (the default) */
   int32_t sample_every;  /* s >= 1 */
 } ta_md_rdf_params;
+typedef struct {
+  double r_bond;         /* bond cutoff of every pair of elements when r_bond_pairs is NULL */
+  int32_t n_bins;        /* B, 1 .. TA_MD_MAX_BINS; 0 switches the feature off (the default) */
+  int32_t sample_every;  /* s >= 1 */
+} ta_md_adf_params;
 typedef struct {
   int32_t n_lags;        /* L, 1 .. TA_MD_MAX_LAGS; 0 switches sampling off (the default) */
   int32_t sample_every;  /* s >= 1 */
@@ -558,6 +600,8 @@ int ta_md_get_samples(ta_handle h, int32_t first_lag, int32_t n, double *positio
                       int64_t *steps);
 int ta_md_set_rdf(ta_handle h, const ta_md_rdf_params *p);
 int ta_md_get_rdf(ta_handle h, int64_t *counts, int64_t *info, double *r_max);
+int ta_md_set_adf(ta_handle h, const ta_md_adf_params *p, const double *r_bond_pairs);
+int ta_md_get_adf(ta_handle h, int64_t *counts, int64_t *info, double *r_bond_pairs);
 
 /* Device-resident structure relaxation: the resident batch is brought to a force minimum in ONE call, every
  * frame on its own, with positions, velocities and forces staying on the device. The optimiser is FIRE

@@ -1,6 +1,6 @@
 // C ABI of the device-resident MD loop: the ta_md_* entry points (include/tensoralloy_amd.h). The loop itself
-// is in ta_resident.hip; the integrator, correlation and pair-distribution launches are in ta_md.hip,
-// ta_md_corr.hip and ta_md_rdf.hip.
+// is in ta_resident.hip; the integrator, correlation, pair-distribution and bond-angle launches are in ta_md.hip,
+// ta_md_corr.hip, ta_md_rdf.hip and ta_md_adf.hip.
 #include <cmath>
 #include <cstring>
 
@@ -69,6 +69,34 @@ bool md_rdf_alloc(ta_context *h, const ta_md_rdf_params &p) {
   return true;
 }
 
+// Zeroed counts, the squared cutoffs `rb`[E][E] and the launch's workgroup layout for the resident batch under
+// setting `p`, with no sample taken. False when the device has no room (everything is released then); throws
+// otherwise.
+bool md_adf_alloc(ta_context *h, const ta_md_adf_params &p, const std::vector<double> &rb) {
+  auto &g = h->md.adf;
+  const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
+  const size_t E = (size_t)h->n_elements, n_acc = F * E * (E * (E + 1) / 2) * (size_t)p.n_bins;
+  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches add to the old buffer)
+  g.release();
+  const int chunk = ta::md_adf_chunk((long long)N);
+  const std::vector<int32_t> start = frame_blocks(h, 1, chunk);
+  if (!g.acc.try_exact(n_acc) || !g.blk.try_exact(F + 1) || !g.rb2.try_exact(E * E)) {
+    g.release();
+    return false;
+  }
+  std::vector<double> rb2(E * E);
+  for (size_t k = 0; k < E * E; ++k) rb2[k] = rb[k] * rb[k];
+  HIP_CHECK(hipMemset(g.acc.ptr, 0, std::max<size_t>(n_acc, 1) * sizeof(unsigned long long)));
+  HIP_CHECK(hipMemcpy(g.blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(g.rb2.ptr, rb2.data(), E * E * sizeof(double), hipMemcpyHostToDevice));
+  g.n_blk = (int)start[F];
+  g.chunk = chunk;
+  g.sched.every = p.sample_every;
+  g.sched.start(h->md.step);
+  g.sched.valid = true;
+  return true;
+}
+
 // what ta_md_get_chain and ta_md_set_chain need; returns 0 or the error code
 int md_chain_ready(ta_context *h, const char *who) {
   if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
@@ -103,7 +131,7 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
   if (velocities)
     for (size_t i = 0; i < 3 * N; ++i)
       if (!std::isfinite(velocities[i])) return fail(h, TA_ERR_INVALID, "ta_md_init: non-finite velocity");
-  bool ring_nomem = false, rdf_nomem = false;
+  bool ring_nomem = false, rdf_nomem = false, adf_nomem = false;
   const int rc = guarded(h, [&]() {
     auto &md = h->md;
     md.valid = false;
@@ -140,12 +168,18 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
       md.rdf.on = false;
       rdf_nomem = true;
     }
+    if (md.adf.on && !md_adf_alloc(h, md.adf.p, md.adf.rb)) {  // likewise
+      md.adf.on = false;
+      adf_nomem = true;
+    }
     md.valid = true;
   });
   if (rc == TA_OK && ring_nomem)
     return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the rings of ta_md_set_sampling; sampling is off");
   if (rc == TA_OK && rdf_nomem)
     return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the counts of ta_md_set_rdf; the feature is off");
+  if (rc == TA_OK && adf_nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the counts of ta_md_set_adf; the feature is off");
   return rc;
 }
 
@@ -404,6 +438,79 @@ int ta_md_get_rdf(ta_handle h, int64_t *counts, int64_t *info, double *r_max) {
   });
 }
 
+int ta_md_set_adf(ta_handle h, const ta_md_adf_params *p, const double *r_bond_pairs) {
+  if (!h) return TA_ERR_INVALID;
+  auto &adf = h->md.adf;
+  if (!p || p->n_bins == 0) {
+    adf.on = false;
+    return guarded(h, [&]() {
+      HIP_CHECK(hipStreamSynchronize(h->stream));
+      adf.release();
+    });
+  }
+  if (p->n_bins < 0 || p->n_bins > TA_MD_MAX_BINS)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_adf: n_bins must be 0 .. " + std::to_string(TA_MD_MAX_BINS));
+  if (p->sample_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_set_adf: sample_every must be >= 1");
+  const size_t E = (size_t)h->n_elements;
+  std::vector<double> rb(E * E, p->r_bond);
+  if (r_bond_pairs) rb.assign(r_bond_pairs, r_bond_pairs + E * E);
+  const char *name = r_bond_pairs ? "r_bond_pairs" : "r_bond";
+  for (size_t k = 0; k < E * E; ++k) {
+    const std::string what = std::string("ta_md_set_adf: ") + name +
+                             (r_bond_pairs ? "[" + std::to_string(k / E) + "][" + std::to_string(k % E) + "]" : std::string());
+    if (!std::isfinite(rb[k]) || !(rb[k] > 0.0)) return fail(h, TA_ERR_INVALID, what + " must be a finite distance > 0");
+    if (rb[k] > h->rmax)
+      return fail(h, TA_ERR_INVALID, what + " = " + std::to_string(rb[k]) + " exceeds the model's cutoff max(rcut, acut) = " +
+                                     std::to_string(h->rmax) + "; the neighbour list is not complete beyond that");
+  }
+  for (size_t a = 0; a < E; ++a)
+    for (size_t b = a + 1; b < E; ++b)
+      if (rb[a * E + b] != rb[b * E + a])
+        return fail(h, TA_ERR_INVALID, "ta_md_set_adf: r_bond_pairs is not symmetric: [" + std::to_string(a) + "][" +
+                                       std::to_string(b) + "] differs from [" + std::to_string(b) + "][" + std::to_string(a) + "]");
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_adf: no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_set_adf called before ta_md_init");
+  bool nomem = false;
+  const int rc = guarded(h, [&]() {
+    adf.on = false;  // (until the counts exist)
+    nomem = !md_adf_alloc(h, *p, rb);
+    if (!nomem) {
+      adf.p = *p;
+      adf.rb = rb;
+      adf.on = true;
+    }
+  });
+  if (rc == TA_OK && nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_set_adf: no device memory for counts of n_bins = " + std::to_string(p->n_bins) +
+                                 "; the feature is off");
+  return rc;
+}
+
+int ta_md_get_adf(ta_handle h, int64_t *counts, int64_t *info, double *r_bond_pairs) {
+  if (!h) return TA_ERR_INVALID;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_adf: no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_get_adf called before ta_md_init");
+  const auto &adf = h->md.adf;
+  if (!adf.on) return fail(h, TA_ERR_INVALID, "ta_md_get_adf: the bond-angle distributions are off (ta_md_set_adf)");
+  if (!adf.sched.valid)
+    return fail(h, TA_ERR_INVALID, "ta_md_get_adf: a ta_md_run failed and left the counts invalid; call ta_md_set_adf or "
+                                   "ta_md_init again");
+  return guarded(h, [&]() {
+    const size_t E = (size_t)h->n_elements;
+    const size_t n = h->keep_natoms.size() * E * (E * (E + 1) / 2) * (size_t)adf.p.n_bins;
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the counts are copied as they are");
+    if (counts && n) HIP_CHECK(hipMemcpy(counts, adf.acc.ptr, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (info) {
+      info[0] = adf.sched.taken();
+      info[1] = adf.p.n_bins;
+      info[2] = adf.p.sample_every;
+      info[3] = adf.sched.last;
+    }
+    if (r_bond_pairs) std::memcpy(r_bond_pairs, adf.rb.data(), E * E * sizeof(double));
+  });
+}
+
 int ta_md_noise(ta_handle h, int64_t step, double *xi, double *eta) {
   if (!h) return TA_ERR_INVALID;
   if (!xi || !eta) return fail(h, TA_ERR_INVALID, "ta_md_noise: null argument");
@@ -509,6 +616,7 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
   md.baro.rec_valid = false;
   md.nhc.rec_valid = false;
   const bool corr_was_valid = md.corr.sched.suspend(), rdf_was_valid = md.rdf.sched.suspend();
+  const bool adf_was_valid = md.adf.sched.suspend();
   res.cell_running = md.baro.running = baro;
   const int rc = guarded(h, [&]() {
     const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
@@ -606,7 +714,31 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     g.n_bins = md.rdf.p.n_bins, g.n_elements = h->n_elements, g.n_frames = (int)F;
     g.n_blk = md.rdf.n_blk, g.chunk = md.rdf.chunk;
     g.dr = rdf_run ? md.rdf.p.r_max / (double)md.rdf.p.n_bins : 1.0;
+    // Bond-angle distributions: a launch of their own in the same place, under the same predicate (no volume
+    // enters, so they run under the barostat too: db.cells are those of the state t)
+    const bool adf_run = md.adf.on && adf_was_valid && N > 0;
+    const ta::SampleSchedule &adf_sched = md.adf.sched;
+    ta::MdAdfLaunch t;
+    t.blk_start = md.adf.blk.ptr;
+    t.rb2 = md.adf.rb2.ptr;
+    t.counts = md.adf.acc.ptr;
+    t.status = res.status.ptr;
+    t.n_bins = md.adf.p.n_bins, t.n_elements = h->n_elements, t.n_frames = (int)F;
+    t.n_blk = md.adf.n_blk, t.chunk = md.adf.chunk;
+    t.dtheta = adf_run ? M_PI / (double)md.adf.p.n_bins : 1.0;
     auto integrate = [&](int k, bool drift) {
+      if (adf_run && adf_sched.due(step0, k)) {
+        t.pos = h->db.pos;
+        t.cells = h->db.cells;
+        t.species = h->db.species;
+        t.atom_start = h->db.atom_start;
+        t.pair_start = h->pair_start.ptr;  // the resident list
+        t.pair_j = h->pair_j.ptr;
+        t.pair_shift = h->pair_shift.ptr;
+        t.seq = (unsigned)k;
+        ta::launch_md_adf(t, s);
+        HIP_CHECK(hipGetLastError());
+      }
       if (rdf_run && rdf_sched.due(step0, k)) {
         g.pos = h->db.pos;
         g.cells = h->db.cells;
@@ -664,6 +796,8 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     md.corr.sched.valid = corr_was_valid;
     if (rdf_run) md.rdf.sched.finish(md.step);
     md.rdf.sched.valid = rdf_was_valid;
+    if (adf_run) md.adf.sched.finish(md.step);
+    md.adf.sched.valid = adf_was_valid;
     if (n_rebuilds) *n_rebuilds = rebuilds;
     if (baro && F) {
       std::vector<double> rec(4 * n_rec * F);

@@ -197,6 +197,26 @@ struct MdState {
       sched.last = -1;
     }
   } rdf;
+  // Bond-angle distributions (ta_md_set_adf): the bond cutoffs [E][E] of the setting, their squares on the
+  // device, the counts [F][E][E (E + 1) / 2][n_bins] and the launch's workgroup layout
+  struct Adf {
+    bool on = false;
+    ta_md_adf_params p = {0.0, 0, 1};
+    std::vector<double> rb;
+    DevBuf<double> rb2;
+    DevBuf<unsigned long long> acc;
+    DevBuf<int32_t> blk;
+    int n_blk = 0, chunk = 0;
+    SampleSchedule sched;
+    void release() {  // frees what the bond-angle distributions hold on the device; the setting stays
+      rb2.release();
+      acc.release();
+      blk.release();
+      n_blk = 0;
+      sched.valid = false;
+      sched.last = -1;
+    }
+  } adf;
 };
 
 // device-resident relaxation (ta_api_relax.hip; the launches are in ta_relax.hip): FIRE velocities of its own,

@@ -106,11 +106,40 @@ struct MdRdfLaunch {
   double dr;                      // r_max / n_bins
 };
 
+constexpr int kMdAdfLdsWords = 8192;  // most 32-bit bins of the bond-angle launch's LDS histogram (32 KB)
+constexpr int kMdAdfSlab = 128;       // neighbours a wave of the bond-angle launch holds in LDS at a time
+
+// Centres per workgroup (four waves, one centre each at a time) of the bond-angle launch for a batch of n_atoms:
+// small batches spread over the chip, large ones merge fewer histograms (the plan, blk_start, is made once by
+// ta_md_set_adf)
+inline int md_adf_chunk(long long n_atoms) { return n_atoms <= 16384 ? 8 : 64; }
+
+// Arguments of the bond-angle launch (ta_md_adf.hip) that ta_md_run puts in front of the integrator launch of a
+// sampled step: the resident (skin) list, the positions and cells of that whole-step state.
+struct MdAdfLaunch {
+  const double *pos;              // [N][3] db.pos
+  const double *cells;            // [F][9]
+  const int32_t *species;         // [N]
+  const int32_t *atom_start;      // [F + 1]
+  const int32_t *blk_start;       // [F + 1] first workgroup of each frame (at least one each)
+  const int32_t *pair_start;      // [N + 1] the resident list: centre i owns pair_start[i] .. pair_start[i + 1] - 1
+  const int32_t *pair_j;          // [P]
+  const int32_t *pair_shift;      // [P][3]
+  const double *rb2;              // [E][E] squares of the bond cutoffs
+  unsigned long long *counts;     // [F][E][E (E + 1) / 2][n_bins] the accumulators
+  const unsigned *status;         // the integrator's status word and
+  unsigned seq;                   // sequence number: the same predicate
+  int n_bins, n_elements, n_frames, n_blk, chunk;
+  double dtheta;                  // pi / n_bins
+};
+
 void launch_md_integrate(const MdLaunch &a, int threads, hipStream_t s);
 
 void launch_md_correlate(const MdCorrLaunch &a, hipStream_t s);
 
 void launch_md_rdf(const MdRdfLaunch &a, hipStream_t s);
+
+void launch_md_adf(const MdAdfLaunch &a, hipStream_t s);
 
 // xi, eta [n][3] (device): the normals md_integrate draws for absolute step `step`, atoms 0 .. n - 1
 void launch_md_noise(unsigned long long seed, long long step, long long n, double *xi, double *eta, hipStream_t s);

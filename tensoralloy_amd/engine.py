@@ -39,6 +39,7 @@ class Engine:
         self._md_chain = 0         # `md_set_nose_hoover` is on: thermostats per chain
         self._md_lags = 0          # `md_set_sampling` is on: snapshots in the ring
         self._md_bins = 0          # `md_set_rdf` is on: bins of the pair distributions
+        self._md_adf_bins = 0      # `md_set_adf` is on: bins of the bond-angle distributions
         self._n_elements = int(desc.n_elements)
         # what the neighbour list is complete for: max(rcut, acut), acut counting for angular models only
         self._md_cutoff = max(float(desc.rcut), float(desc.acut)) if int(desc.angular) else float(desc.rcut)
@@ -275,6 +276,8 @@ class Engine:
             msg = self._lib.ta_last_error(self._handle) or b""
             if b"ta_md_set_rdf" in msg:
                 self._md_bins = 0
+            if b"ta_md_set_adf" in msg:
+                self._md_adf_bins = 0
             if b"ta_md_set_sampling" in msg:
                 self._md_lags = 0
         self._check(rc)
@@ -402,6 +405,58 @@ class Engine:
         return {"counts": counts, "n_samples": int(info[0]), "r_max": float(r_max.value),
                 "sample_every": int(info[2]), "last_step": int(info[3]), "n_by_element": n_by_element,
                 "volumes": self._volumes.copy(), "pbc": np.array([fr.pbc != 0 for fr in self._frames]).reshape(F, 3)}
+
+    def md_set_adf(self, n_bins=0, r_bond=None, sample_every=1):
+        """Bond-angle distributions inside `md_run` (`ta_md_set_adf`): with `n_bins` = B (1 .. 4096) the loop
+        counts, at every step t (counted since `md_init`) with t % `sample_every` == 0, for every centre the angle
+        between every unordered pair of its neighbours below the bond cutoff `r_bond` into integer histograms of B
+        bins over [0, pi] per frame, species of the centre and unordered pair of species of the two neighbours,
+        which stay on the device (`md_adf`). `r_bond`: one distance, or a symmetric [n_elements, n_elements]
+        matrix of cutoffs per pair of elements (centre, neighbour); None: the model's cutoff max(rcut, acut), which
+        is also the largest value allowed. `n_bins` = 0 switches it off (the default) and frees them. Needs
+        `md_init`; every call starts from zero counts, as `md_init` does. The setting stays on across
+        `set_frames`. Independent of `md_set_sampling` and `md_set_rdf`; runs under the barostat too."""
+        E = self._n_elements
+        pairs = C.POINTER(C.c_double)()
+        if r_bond is None:
+            r_bond = self._md_cutoff
+        if np.ndim(r_bond) == 0:
+            scalar = float(r_bond)
+        else:
+            rb = np.ascontiguousarray(r_bond, dtype=np.float64)
+            if rb.shape != (E, E):
+                raise ValueError(f"md_set_adf: r_bond must be one distance or [{E}, {E}] (n_elements of the model)")
+            pairs, scalar = _lib.as_dp(rb), float(rb.max())
+        p = _lib.MdAdfParams(scalar, int(n_bins), int(sample_every))
+        rc = self._lib.ta_md_set_adf(self._handle, C.byref(p), pairs)
+        if rc == _lib.TA_ERR_NOMEM:   # (no room for the counts: the library switched the feature off)
+            self._md_adf_bins = 0
+        self._check(rc)
+        self._md_adf_bins = int(n_bins)
+
+    @property
+    def md_adf_bins(self):
+        """Bins of the bond-angle distributions `md_set_adf` switched on, 0 while they are off."""
+        return self._md_adf_bins
+
+    def md_adf(self):
+        """What the loop has counted since `md_set_adf` (`ta_md_get_adf`), a dict: `counts` int64 [n_frames,
+        n_elements, P, n_bins], counts[f, a, p, k] = triples of a centre of species a in frame f and two of its
+        neighbours of species `pairs[p]` = (b, c), b <= c, with min(n_bins - 1, floor(theta / (pi / n_bins))) == k,
+        summed over the samples; `pairs`: the P = n_elements (n_elements + 1) / 2 tuples (b, c) in the order of p;
+        `r_bond` [n_elements, n_elements]: the cutoffs in use; `n_samples`, `n_bins`, `sample_every`, `last_step`
+        (absolute step of the newest sample, -1: none). `md.adf` normalises the counts."""
+        if self.info is None:
+            raise ValueError("md_adf: no resident batch (call set_frames first)")
+        F, E, B = int(self.info.n_frames), self._n_elements, max(self._md_adf_bins, 1)
+        pairs = [(b, c) for b in range(E) for c in range(b, E)]
+        counts = np.zeros((F, E, len(pairs), B), dtype=np.int64)
+        info = (C.c_int64 * 4)()
+        r_bond = np.zeros((E, E))
+        self._check(self._lib.ta_md_get_adf(self._handle, counts.ctypes.data_as(C.POINTER(C.c_int64)), info,
+                                            _lib.as_dp(r_bond)))
+        return {"counts": counts, "n_samples": int(info[0]), "n_bins": int(info[1]), "sample_every": int(info[2]),
+                "last_step": int(info[3]), "r_bond": r_bond, "pairs": pairs}
 
     def md_noise(self, step: int):
         """(xi, eta) [n_atoms, 3]: the standard normals the Langevin step with absolute index `step` (steps

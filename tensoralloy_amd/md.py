@@ -49,6 +49,14 @@ pairs of its resident neighbour list below `rdf_rmax` into integer histograms pe
 on the device (`Engine.md_set_rdf`; `DeviceMD.get_rdf`). The counts are exact integers and do not depend on how
 a run is cut. `rdf` normalises counts to g_ab(r), `coordination_number` integrates g_ab to a neighbour count.
 Independent of `n_lags`; refused under the barostat, where there is no single volume to normalise with.
+
+Bond-angle distributions: with `adf_bins` (and `adf_rbond`, `adf_every`) the loop counts, at every sampled step
+and for every centre, the angle j-i-k between every two of its neighbours below the bond cutoff into integer
+histograms over [0, pi] per frame, species of the centre and pair of species of the two neighbours, on the device
+(`Engine.md_set_adf`; `DeviceMD.get_adf`): the three-body companion of g(r), which tells a liquid from a glass
+from a defective crystal. The counts are exact integers and do not depend on how a run is cut. `adf` normalises
+them to a probability density per degree. No volume enters, so this runs under the barostat as well, and
+independently of `n_lags` and `rdf_bins`.
 """
 from __future__ import annotations
 
@@ -60,7 +68,7 @@ GPa = 1.0 / 160.21766208      # eV / Angstrom^3
 bar = 1.0e-4 * GPa
 
 __all__ = ["fs", "kB", "GPa", "bar", "maxwell_boltzmann", "DeviceMD", "vdos", "diffusion_coefficient",
-           "green_kubo_diffusion", "rdf", "coordination_number"]
+           "green_kubo_diffusion", "rdf", "coordination_number", "adf"]
 
 
 def maxwell_boltzmann(masses, kT, rng, zero_momentum=True):
@@ -216,6 +224,24 @@ def coordination_number(g, r, density_b, r_cut):
     return np.asarray(density_b, dtype=np.float64) * (np.where(inside, g, 0.0) * shells).sum(axis=-1)
 
 
+def adf(counts):
+    """Bond-angle distributions from the integer triple counts of the device loop (`Engine.md_adf`): `counts`
+    [..., E, P, B], triples of a centre of element a and two neighbours of the pair of elements p in bin k of B
+    uniform bins over [0, 180] degrees. Returns (theta, p): the bin centres theta_k = (k + 1/2) 180 / B in
+    degrees [B] and the probability density per degree [..., E, P, B]: every row [a][p] times the bin width
+    180 / B sums to 1. A row without any triple is NaN."""
+    c = np.asarray(counts)
+    if c.ndim < 3 or c.shape[-1] < 1:
+        raise ValueError("adf: counts must be [..., n_elements, n_pairs, n_bins]")
+    B = c.shape[-1]
+    width = 180.0 / B
+    theta = (np.arange(B) + 0.5) * width
+    total = c.sum(axis=-1, keepdims=True).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = np.where(total > 0.0, c / (total * width), np.nan)
+    return theta, p
+
+
 class DeviceMD:
     """
     NVE (velocity Verlet), Berendsen NVT, Langevin NVT or Nose-Hoover chain NVT dynamics of one structure or of a batch of
@@ -249,6 +275,13 @@ class DeviceMD:
                            on the device (`get_rdf`); excludes the barostat. Without `rdf_bins` no method of
                            the pair distributions is called on the engine, unless its `md_rdf_bins` says that an
                            earlier `DeviceMD` left them on: they are then switched off
+    adf_bins, adf_rbond, adf_every : `adf_bins` given (1 .. 4096): the loop counts the bond angles between the
+                           neighbours below `adf_rbond` (one distance or [n_elements, n_elements]; default and
+                           largest value: the model's cutoff) of every `adf_every`-th step (the state at
+                           construction is the first sample) into `adf_bins` bins over [0, pi] on the device
+                           (`get_adf`); runs under the barostat too. Without `adf_bins` no method of the
+                           bond-angle distributions is called on the engine, unless its `md_adf_bins` says that
+                           an earlier `DeviceMD` left them on: they are then switched off
 
     Under the barostat the cell of every `Atoms` follows (the atoms are not scaled again), and every `run` call
     that moved the cells ends with one neighbour-list build for the final cells: an observer at interval 1
@@ -259,7 +292,8 @@ class DeviceMD:
     def __init__(self, engine_or_calculator, atoms_or_list, timestep, temperature_K=None, taut=None,
                  velocities=None, masses=None, friction=None, seed=0, pressure=None, taup=None,
                  compressibility=None, mask=None, tdamp=None, tchain=3, tloop=1, dof_removed=0, n_lags=None,
-                 sample_every=1, rdf_bins=None, rdf_rmax=None, rdf_every=1):
+                 sample_every=1, rdf_bins=None, rdf_rmax=None, rdf_every=1, adf_bins=None, adf_rbond=None,
+                 adf_every=1):
         if not (np.isfinite(timestep) and timestep > 0.0):
             raise ValueError("DeviceMD: timestep must be a finite time > 0")
         barostat = (pressure, taup, compressibility)
@@ -288,6 +322,21 @@ class DeviceMD:
                                  "compressibility): normalising the counts needs one volume")
         elif rdf_every != 1 or rdf_rmax is not None:
             raise ValueError("DeviceMD: rdf_every and rdf_rmax belong to the pair distributions (rdf_bins)")
+        if adf_bins is not None:
+            whole = lambda a: isinstance(a, (int, np.integer)) and not isinstance(a, bool)
+            if not (whole(adf_bins) and 1 <= adf_bins <= 4096):
+                raise ValueError("DeviceMD: adf_bins must be an integer 1 .. 4096")
+            if not (whole(adf_every) and adf_every >= 1):
+                raise ValueError("DeviceMD: adf_every must be an integer >= 1")
+            if adf_rbond is not None:
+                rb = np.asarray(adf_rbond, dtype=np.float64)
+                if rb.ndim not in (0, 2) or rb.size == 0 or not (np.all(np.isfinite(rb)) and np.all(rb > 0.0)):
+                    raise ValueError("DeviceMD: adf_rbond must be a finite distance > 0, or a square matrix of them")
+                if rb.ndim == 2 and (rb.shape[0] != rb.shape[1] or not np.array_equal(rb, rb.T)):
+                    raise ValueError("DeviceMD: adf_rbond must be a finite distance > 0, or a square matrix of them, "
+                                     "symmetric")
+        elif adf_every != 1 or adf_rbond is not None:
+            raise ValueError("DeviceMD: adf_every and adf_rbond belong to the bond-angle distributions (adf_bins)")
         if self._barostat:
             if any(p is None for p in barostat):
                 raise ValueError("DeviceMD: the barostat needs pressure, taup and compressibility")
@@ -393,6 +442,11 @@ class DeviceMD:
             engine.md_set_rdf(self._rdf_bins, rdf_rmax, int(rdf_every))
         elif getattr(engine, "md_rdf_bins", 0):
             engine.md_set_rdf(0)
+        self._adf_bins = int(adf_bins) if adf_bins is not None else 0
+        if self._adf_bins:   # (opt-in in the same way)
+            engine.md_set_adf(self._adf_bins, adf_rbond, int(adf_every))
+        elif getattr(engine, "md_adf_bins", 0):
+            engine.md_set_adf(0)
         self._natoms = np.array([len(a) for a in self.atoms_list], dtype=np.int64)
         self.velocities = velocities.copy()
         self.epot = self.ekin = None   # per-frame records of the last state
@@ -497,6 +551,17 @@ class DeviceMD:
         out = self.engine.md_rdf()
         r, g = rdf(out["counts"], out["n_samples"], out["n_by_element"], out["volumes"], out["r_max"], pbc=out["pbc"])
         return r, (g[0] if self._single else g)
+
+    def get_adf(self):
+        """(theta, p): the bin centres in degrees [adf_bins] and the bond-angle distributions
+        [n_elements, P, adf_bins] (a batch: [n_frames, n_elements, P, adf_bins]) over every state sampled so far,
+        normalised as `adf` does: a probability density per degree for every species of the centre and pair of
+        species of the neighbours (`engine.md_adf()["pairs"]`), NaN where there was no triple. The counts are in
+        `engine.md_adf()`. Needs `adf_bins`."""
+        if not self._adf_bins:
+            raise ValueError("DeviceMD.get_adf: the bond-angle distributions are off (adf_bins)")
+        theta, p = adf(self.engine.md_adf()["counts"])
+        return theta, (p[0] if self._single else p)
 
     def get_volume(self):
         """Cell volume per frame, in A^3."""
