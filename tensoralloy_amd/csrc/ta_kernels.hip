@@ -142,7 +142,10 @@ __global__ __launch_bounds__(kBlock) void g4_forward_kernel(SFParams sf, AngChun
       const double u = d2 * sf.inv_ac2;
       const bool ok = (q != lp) && (u < 1.0);
       // cos(theta) = (rij^2 + rik^2 - rjk^2) / (2 rij rik)  (sf.py:145-148)
-      const double cth = (ra2 + rb2 - d2) * 0.5 * inv_ra * inv_rb;
+      // A masked term gets cos = 0, so that its power is finite and the factor 0 below really drops it: for the
+      // pair with itself (q == lp) the expression is 1 - eps / (2 r^2), which rounds above 1 for r^2 > ~25, and
+      // pow(1 - cos, non-integer zeta) is then NaN.
+      const double cth = ok ? (ra2 + rb2 - d2) * 0.5 * inv_ra * inv_rb : 0.0;
       const double fd = cutoff_u_value(sf.cutoff, u);
 #pragma unroll
       for (int ib = 0; ib < NB; ++ib) {

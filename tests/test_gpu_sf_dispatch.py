@@ -17,6 +17,9 @@ oracle: descriptors to 1e-10, energies to 1e-9 x max(1, |E|), forces to 1e-9 x m
 Also here: the environment switches TA_NO_JOBS, TA_FWD_WPE, TA_BWD_WPE and TA_FULL_RECORDS, which the library
 reads when a handle is created and keeps for that handle (each set before its engine exists and deleted
 after), and the MD path (exact list filtered on the device from the skin list) for multi-species models.
+
+The first-generation kernels (ta_kernels.hip) appear here only as the fallback beyond 1024 neighbours; their
+eight builds, their chunk chain and their callers are held to the same bounds in tests/test_gpu_sf_v1.py.
 """
 import os
 

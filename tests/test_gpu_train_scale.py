@@ -454,25 +454,47 @@ def _dispatch_rows():
             make_nn(els, 5.0, True, [16], sf_kwargs=dict(eta=[0.05, 4.0])),
             [alloy(els[:-1], seed=41), sparse_cluster(els), alloy(els, rep=(2, 2, 3), seed=42),
              sparse_cluster(els[1:], seed=6)], (1, 192))
+    # first-generation angular kernels (tests/test_gpu_sf_v1.py): `backward_only` runs their chunk chain once per
+    # descriptor with a one-hot dE/dG
+    from tests.test_gpu_sf_v1 import MODELS, edge_frames, uneven
+    # a = 3.35: rc = 5.0 lies between the 4th and the 5th shell (4.74, 5.30). In the a = 3.6 frames of
+    # test_gpu_sf_v1.py one pair sits 9e-5 A from the cutoff and crosses it inside the stencil; the difference
+    # quotient of the ORACLE's descriptors then changes by 1.6e-5 between e = 1e-3 and 5e-4 (6e-12 here).
+    rows["v1-multi-4el"] = lambda: (MODELS["b-multi-4el"][0](), uneven(ELEMENTS[4], 21, a=3.35), (1, 192))
+    rows["v1-6el-sparse"] = lambda: (MODELS["e-6el"][0](), edge_frames(MODELS["e-6el"][0]().elements), (1, 192))
+    rows["v1-forced-211"] = lambda: (MODELS["a-211"][0](), [alloy(ELEMENTS[2])], (1, 192))
     return rows
 
 
 DISPATCH = _dispatch_rows()
+V1_ROWS = {"v1-multi-4el": False, "v1-6el-sparse": False, "v1-forced-211": True}   # row: needs TA_FORCE_V1
+
+
+def _engine(nn, monkeypatch, row):
+    """Rows of V1_ROWS: the engine the dispatcher (or TA_FORCE_V1, read when it is made) gives these kernels."""
+    from tests.test_gpu_sf_v1 import engine
+    return engine(nn, monkeypatch, V1_ROWS.get(row, False))
+
+
+def _assert_first_generation(eng, row):
+    assert eng.list_layout("kernel")["info"]["n_blk"] == 0, row
 
 
 @pytest.mark.parametrize("row", list(DISPATCH))
-def test_descriptor_tangent_across_the_dispatch(lib, row):
+def test_descriptor_tangent_across_the_dispatch(lib, monkeypatch, row):
     """dG of `ta_loss_gradient` against a sixth-order central difference of the GPU's own descriptors (which
-    test_gpu_sf_dispatch.py pins to the oracle) along a random (dR, dh)."""
+    test_gpu_sf_dispatch.py and test_gpu_sf_v1.py pin to the oracle) along a random (dR, dh)."""
     nn, frames, window = DISPATCH[row]()
     rng = np.random.RandomState(5)
     dR = [rng.randn(len(a), 3) * 0.3 for a in frames]
     dh = [rng.randn(3, 3) * 0.05 if np.any(a.pbc) else np.zeros((3, 3)) for a in frames]
     e = 1e-3
-    with Engine(nn) as eng:
+    with _engine(nn, monkeypatch, row) as eng:
         eng.set_frames(frames)
         nnl = int(eng.info.nnl_max)
         assert window[0] <= nnl <= window[1], (row, nnl)
+        if row in V1_ROWS:
+            _assert_first_generation(eng, row)
         _, dG = eng.loss_gradient(np.ones(len(frames)), np.concatenate(dR), np.array(dh), return_tangent=True)
 
         def G_at(t):
@@ -484,6 +506,24 @@ def test_descriptor_tangent_across_the_dispatch(lib, row):
                  (G_at(3 * e) - G_at(-3 * e))) / (60.0 * e)
     assert np.abs(dG).max() > 1e-3
     assert np.abs(dG - dG_fd).max() < 1e-6 * max(1.0, np.abs(dG_fd).max()), (row, np.abs(dG - dG_fd).max())
+
+
+def test_loss_gradient_on_the_first_generation_kernels(lib, monkeypatch):
+    """`ta_energy_gradient` and `ta_loss_gradient` of the four-element 3 x 3 x 3 model (eight chunks per one-hot
+    backward chain) against oracle/train.py on the GPU's G and dG: the comparison and the 1e-9 bound of
+    `check_against_oracle`; G is pinned to the oracle by test_gpu_sf_v1.py, dG by the row `v1-multi-4el` above."""
+    row = "v1-multi-4el"
+    nn, frames, _ = DISPATCH[row]()
+    with _engine(nn, monkeypatch, row) as eng:
+        eng.set_frames(frames)
+        _assert_first_generation(eng, row)
+        G, ge, gl, dG, coeff = gradients(eng, frames)
+        _assert_first_generation(eng, row)
+    assert np.abs(dG).max() > 0.0
+    re, rl = reference(nn, frames, G, dG, coeff)
+    assert_close(ge, re, what=f"{row}: energy gradient")
+    assert_close(gl, rl, what=f"{row}: loss gradient")
+    assert np.abs(gl - ge).max() > 1e-6 * np.abs(ge).max()    # the direction term is really there
 
 
 # -- E. Hessian-vector products --------------------------------------------------------------------------------
