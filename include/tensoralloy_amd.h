@@ -548,7 +548,57 @@ int ta_step_view(ta_handle h, const double *positions, const double *cells, uint
  *   ta_md_run            A run that fails leaves the counts invalid: ta_md_get_adf is TA_ERR_INVALID until
  *                        ta_md_set_adf or ta_md_init is called again.
  *   ta_md_get_adf        counts [n_frames][n_elements][P][n_bins]; info [4] as ta_md_get_rdf; r_bond_pairs
- *                        [n_elements][n_elements], the cutoffs in use. Any pointer may be NULL. */
+ *                        [n_elements][n_elements], the cutoffs in use. Any pointer may be NULL.
+ *
+ * Bond-orientational order inside the loop (opt-in; with it never switched on nothing changes): the Steinhardt order
+ * parameters q_l of every atom, their neighbour average (Lechner and Dellago, J. Chem. Phys. 129, 114707) and the
+ * count of "solid bonds" (ten Wolde, Ruiz-Montero and Frenkel), which tell crystalline atoms from disordered ones
+ * and fcc from bcc from hcp. Parameters: up to TA_MD_ORDER_MAX_DEGREES degrees l, each 1 .. TA_MD_ORDER_MAX_L, in
+ * any order and without duplicates; n_bins = B, sample_every = s; a symmetric bond cutoff rb[a][b] per pair of
+ * elements (r_bond: the same value for all pairs); solid_degree, one of the degrees, and solid_threshold = c. The
+ * schedule is that of ta_md_set_adf, kept separately. Two launches in front of the integrator launch of a sampled
+ * step take, for every centre i of species a, the neighbours of ta_md_set_adf: the entries (j, S) of the resident
+ * list with d = x_j - x_i + S . h (fp64), d . d < rb[a][b]^2; a self-image, or several images of one atom, are
+ * separate neighbours. With N_b(i) their number, for every degree l and m = 0 .. l
+ *     q_lm(i)    = (1 / N_b) sum_neigh Y_lm(d / |d|)       Y_lm as scipy.special.sph_harm (Condon-Shortley phase);
+ *                                                          Y_{l,-m} = (-1)^m conj(Y_lm) is never stored
+ *     q_l(i)     = sqrt(4 pi / (2 l + 1) (|q_l0|^2 + 2 sum_{m > 0} |q_lm|^2))
+ *     qbar_lm(i) = (q_lm(i) + sum_neigh q_lm(j)) / (N_b(i) + 1),   qbar_l from qbar_lm as q_l from q_lm
+ *     s_ij       = Re sum_{m = -l .. l} q_lm(i) conj(q_lm(j)) / (|q_l(i)| |q_l(j)|)   for l = solid_degree, with
+ *                  |q_l| the 2-norm over all m; a centre or a neighbour with |q_l| = 0 forms no solid bond
+ *     n_conn(i)  = number of neighbours with s_ij > c
+ * An atom without neighbours has q_lm = 0 and q_l = qbar_l = 0, never NaN. Y_lm is evaluated without trigonometry
+ * from z / r and (x + i y) / r, so the poles are no special case. All sums are fp64 in an order that the resident
+ * list fixes: a run cut into calls reproduces the uncut run bit for bit. Another skin or another pattern of list
+ * rebuilds orders the list differently; per-atom values then agree to rounding (1e-13), not bitwise.
+ * Accumulated over the samples as unsigned 64-bit integer counts, per frame f and species a of the centre:
+ *     hist_q    [f][a][degree][k],  k = min(B - 1, floor(q_l B))      (q_l <= 1 by the addition theorem)
+ *     hist_qbar [f][a][degree][k]   likewise for qbar_l
+ *     hist_conn [f][a][min(n_conn, TA_MD_ORDER_MAX_CONN)]
+ * A NaN counts nowhere. Kept per atom for the NEWEST sample only and overwritten at every sample: q, qbar
+ * [n_atoms][n_degrees], N_b and n_conn [n_atoms], q_lm [n_atoms][sum (l + 1)][2] (degree by degree in the order
+ * given, m = 0 .. l, real then imaginary part): the classification of the state at info[3]. No volume enters: the
+ * feature runs under the barostat, with the cells of the sampled state, under every thermostat, and
+ * independently of ta_md_set_sampling, ta_md_set_rdf and ta_md_set_adf. ta_md_run with n_steps = 0 samples the
+ * resident state once: ta_md_init + ta_md_set_order + ta_md_run(0) analyses a static structure.
+ *   ta_md_set_order      NULL or n_bins == 0 switches it off (the default; always allowed) and frees the buffers.
+ *                        r_bond_pairs as for ta_md_set_adf. Switching on needs a resident batch and ta_md_init; it
+ *                        allocates and zeroes the counts and the sample counter (so does every further call). The
+ *                        life cycle is that of ta_md_set_adf: ta_set_frames keeps the setting and drops the data
+ *                        with the MD state; ta_md_init starts from zero counts. TA_ERR_INVALID, with the argument
+ *                        named by ta_last_error and the setting left as it was: n_bins outside
+ *                        0 .. TA_MD_MAX_BINS; sample_every < 1; n_degrees outside 1 .. TA_MD_ORDER_MAX_DEGREES; a
+ *                        degree outside 1 .. TA_MD_ORDER_MAX_L or given twice; solid_degree not among the
+ *                        degrees; solid_threshold not finite or not inside (-1, 1); a cutoff not finite, <= 0, or
+ *                        greater than max(rcut, acut) of the model; r_bond_pairs not symmetric. TA_ERR_NOMEM when
+ *                        the device allocation fails; the feature is then off.
+ *   ta_md_run            A run that fails leaves the counts invalid: both getters are TA_ERR_INVALID until
+ *                        ta_md_set_order or ta_md_init is called again.
+ *   ta_md_get_order      hist_q, hist_qbar [n_frames][n_elements][n_degrees][n_bins]; hist_conn
+ *                        [n_frames][n_elements][TA_MD_ORDER_MAX_CONN + 1]; info [4] as ta_md_get_adf; r_bond_pairs
+ *                        [n_elements][n_elements], the cutoffs in use. Any pointer may be NULL.
+ *   ta_md_get_order_atoms  the per-atom arrays of the newest sample (above); TA_ERR_INVALID while no sample has
+ *                        been taken. Any pointer may be NULL. */
 #define TA_MD_MAX_CHAIN 8
 #define TA_MD_MAX_LAGS 4096
 #define TA_MD_MAX_BINS 4096
@@ -562,8 +612,20 @@ typedef struct {
   int32_t n_bins;        /* B, 1 .. TA_MD_MAX_BINS; 0 switches the feature off (the default) */
   int32_t sample_every;  /* s >= 1 */
 } ta_md_adf_params;
+#define TA_MD_ORDER_MAX_DEGREES 4
+#define TA_MD_ORDER_MAX_L 12
+#define TA_MD_ORDER_MAX_CONN 31
 typedef struct {
-  int32_t n_lags;        /* L, 1 .. TA_MD_MAX_LAGS; 0 switches sampling off (the default) */
+  double r_bond;           /* bond cutoff of every pair of elements when r_bond_pairs is NULL */
+  double solid_threshold;  /* c, inside (-1, 1) */
+  int32_t n_bins;          /* B, 1 .. TA_MD_MAX_BINS; 0 switches the feature off (the default) */
+  int32_t sample_every;    /* s >= 1 */
+  int32_t n_degrees;       /* 1 .. TA_MD_ORDER_MAX_DEGREES */
+  int32_t degrees[4];      /* l, 1 .. TA_MD_ORDER_MAX_L each, no duplicates; read up to n_degrees */
+  int32_t solid_degree;    /* one of the degrees */
+} ta_md_order_params;
+typedef struct {
+  int32_t n_lags;       /* L, 1 .. TA_MD_MAX_LAGS; 0 switches sampling off (the default) */
   int32_t sample_every;  /* s >= 1 */
 } ta_md_sampling_params;
 typedef struct {
@@ -602,6 +664,10 @@ int ta_md_set_rdf(ta_handle h, const ta_md_rdf_params *p);
 int ta_md_get_rdf(ta_handle h, int64_t *counts, int64_t *info, double *r_max);
 int ta_md_set_adf(ta_handle h, const ta_md_adf_params *p, const double *r_bond_pairs);
 int ta_md_get_adf(ta_handle h, int64_t *counts, int64_t *info, double *r_bond_pairs);
+int ta_md_set_order(ta_handle h, const ta_md_order_params *p, const double *r_bond_pairs);
+int ta_md_get_order(ta_handle h, int64_t *hist_q, int64_t *hist_qbar, int64_t *hist_conn, int64_t *info,
+                    double *r_bond_pairs);
+int ta_md_get_order_atoms(ta_handle h, double *q, double *qbar, int32_t *n_bonds, int32_t *n_conn, double *qlm);
 
 /* Device-resident structure relaxation: the resident batch is brought to a force minimum in ONE call, every
  * frame on its own, with positions, velocities and forces staying on the device. The optimiser is FIRE

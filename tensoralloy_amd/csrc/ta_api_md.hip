@@ -1,6 +1,6 @@
 // C ABI of the device-resident MD loop: the ta_md_* entry points (include/tensoralloy_amd.h). The loop itself
-// is in ta_resident.hip; the integrator, correlation, pair-distribution and bond-angle launches are in ta_md.hip,
-// ta_md_corr.hip, ta_md_rdf.hip and ta_md_adf.hip.
+// is in ta_resident.hip; the integrator, correlation, pair-distribution, bond-angle and bond-order launches are in
+// ta_md.hip, ta_md_corr.hip, ta_md_rdf.hip, ta_md_adf.hip and ta_md_order.hip.
 #include <cmath>
 #include <cstring>
 
@@ -97,6 +97,75 @@ bool md_adf_alloc(ta_context *h, const ta_md_adf_params &p, const std::vector<do
   return true;
 }
 
+// Zeroed counts, the squared cutoffs `rb`[E][E], the N_lm, the per-atom arrays and the launches' workgroup layout
+// for the resident batch under setting `p`, with no sample taken. False when the device has no room (everything
+// is released then); throws otherwise.
+bool md_order_alloc(ta_context *h, const ta_md_order_params &p, const std::vector<double> &rb) {
+  auto &g = h->md.order;
+  const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
+  const size_t E = (size_t)h->n_elements, D = (size_t)p.n_degrees;
+  const size_t n_hist = F * E * D * (size_t)p.n_bins, n_acc = 2 * n_hist + F * E * (TA_MD_ORDER_MAX_CONN + 1);
+  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches add to the old buffers)
+  g.release();
+  // N_lm = sqrt((2 l + 1) / (4 pi) (l - m)! / (l + m)!), degree by degree, m = 0 .. l
+  std::vector<double> norm;
+  int solid = 0;
+  for (int d = 0; d < p.n_degrees; ++d) {
+    const int l = p.degrees[d];
+    if (l == p.solid_degree) solid = d;
+    for (int m = 0; m <= l; ++m) {
+      long double ratio = 1.0L;
+      for (int k = l - m + 1; k <= l + m; ++k) ratio /= (long double)k;
+      norm.push_back((double)std::sqrt((long double)(2 * l + 1) / (4.0L * 3.14159265358979323846264338327950288L) * ratio));
+    }
+  }
+  const size_t M = norm.size();
+  const int chunk = ta::md_order_chunk((long long)N);
+  const std::vector<int32_t> start = frame_blocks(h, 1, chunk);
+  if (!g.acc.try_exact(n_acc) || !g.blk.try_exact(F + 1) || !g.rb2.try_exact(E * E) || !g.norm.try_exact(M) ||
+      !g.qlm.try_exact(2 * M * N + 1) || !g.per_atom.try_exact(2 * D * N + 1) || !g.per_atom_int.try_exact(2 * N + 1)) {
+    g.release();
+    return false;
+  }
+  std::vector<double> rb2(E * E);
+  for (size_t k = 0; k < E * E; ++k) rb2[k] = rb[k] * rb[k];
+  HIP_CHECK(hipMemset(g.acc.ptr, 0, std::max<size_t>(n_acc, 1) * sizeof(unsigned long long)));
+  HIP_CHECK(hipMemcpy(g.blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(g.rb2.ptr, rb2.data(), E * E * sizeof(double), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(g.norm.ptr, norm.data(), M * sizeof(double), hipMemcpyHostToDevice));
+  g.n_blk = (int)start[F];
+  g.chunk = chunk;
+  g.n_lm = (int)M;
+  g.solid = solid;
+  g.sched.every = p.sample_every;
+  g.sched.start(h->md.step);
+  g.sched.valid = true;
+  return true;
+}
+
+// The bond cutoffs [E][E] of ta_md_set_adf and ta_md_set_order (`who`): r_bond for every pair, or r_bond_pairs.
+// Returns 0 with `rb` filled, or the error code: a cutoff not finite, <= 0 or above the model's, or no symmetry.
+int md_bond_cutoffs(ta_context *h, const std::string &who, double r_bond, const double *r_bond_pairs, std::vector<double> &rb) {
+  const size_t E = (size_t)h->n_elements;
+  rb.assign(E * E, r_bond);
+  if (r_bond_pairs) rb.assign(r_bond_pairs, r_bond_pairs + E * E);
+  const char *name = r_bond_pairs ? "r_bond_pairs" : "r_bond";
+  for (size_t k = 0; k < E * E; ++k) {
+    const std::string what = who + ": " + name +
+                             (r_bond_pairs ? "[" + std::to_string(k / E) + "][" + std::to_string(k % E) + "]" : std::string());
+    if (!std::isfinite(rb[k]) || !(rb[k] > 0.0)) return fail(h, TA_ERR_INVALID, what + " must be a finite distance > 0");
+    if (rb[k] > h->rmax)
+      return fail(h, TA_ERR_INVALID, what + " = " + std::to_string(rb[k]) + " exceeds the model's cutoff max(rcut, acut) = " +
+                                     std::to_string(h->rmax) + "; the neighbour list is not complete beyond that");
+  }
+  for (size_t a = 0; a < E; ++a)
+    for (size_t b = a + 1; b < E; ++b)
+      if (rb[a * E + b] != rb[b * E + a])
+        return fail(h, TA_ERR_INVALID, who + ": r_bond_pairs is not symmetric: [" + std::to_string(a) + "][" +
+                                       std::to_string(b) + "] differs from [" + std::to_string(b) + "][" + std::to_string(a) + "]");
+  return TA_OK;
+}
+
 // what ta_md_get_chain and ta_md_set_chain need; returns 0 or the error code
 int md_chain_ready(ta_context *h, const char *who) {
   if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
@@ -117,6 +186,18 @@ int md_samples_ready(ta_context *h, const char *who) {
   return TA_OK;
 }
 
+// what the two getters of the order parameters need; returns 0 or the error code
+int md_order_ready(ta_context *h, const char *who) {
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, std::string(who) + " called before ta_md_init");
+  if (!h->md.order.on)
+    return fail(h, TA_ERR_INVALID, std::string(who) + ": the bond-orientational order parameters are off (ta_md_set_order)");
+  if (!h->md.order.sched.valid)
+    return fail(h, TA_ERR_INVALID, std::string(who) + ": a ta_md_run failed and left the counts invalid; call "
+                                   "ta_md_set_order or ta_md_init again");
+  return TA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -131,7 +212,7 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
   if (velocities)
     for (size_t i = 0; i < 3 * N; ++i)
       if (!std::isfinite(velocities[i])) return fail(h, TA_ERR_INVALID, "ta_md_init: non-finite velocity");
-  bool ring_nomem = false, rdf_nomem = false, adf_nomem = false;
+  bool ring_nomem = false, rdf_nomem = false, adf_nomem = false, order_nomem = false;
   const int rc = guarded(h, [&]() {
     auto &md = h->md;
     md.valid = false;
@@ -172,6 +253,10 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
       md.adf.on = false;
       adf_nomem = true;
     }
+    if (md.order.on && !md_order_alloc(h, md.order.p, md.order.rb)) {  // likewise
+      md.order.on = false;
+      order_nomem = true;
+    }
     md.valid = true;
   });
   if (rc == TA_OK && ring_nomem)
@@ -180,6 +265,8 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
     return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the counts of ta_md_set_rdf; the feature is off");
   if (rc == TA_OK && adf_nomem)
     return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the counts of ta_md_set_adf; the feature is off");
+  if (rc == TA_OK && order_nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the buffers of ta_md_set_order; the feature is off");
   return rc;
 }
 
@@ -451,23 +538,8 @@ int ta_md_set_adf(ta_handle h, const ta_md_adf_params *p, const double *r_bond_p
   if (p->n_bins < 0 || p->n_bins > TA_MD_MAX_BINS)
     return fail(h, TA_ERR_INVALID, "ta_md_set_adf: n_bins must be 0 .. " + std::to_string(TA_MD_MAX_BINS));
   if (p->sample_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_set_adf: sample_every must be >= 1");
-  const size_t E = (size_t)h->n_elements;
-  std::vector<double> rb(E * E, p->r_bond);
-  if (r_bond_pairs) rb.assign(r_bond_pairs, r_bond_pairs + E * E);
-  const char *name = r_bond_pairs ? "r_bond_pairs" : "r_bond";
-  for (size_t k = 0; k < E * E; ++k) {
-    const std::string what = std::string("ta_md_set_adf: ") + name +
-                             (r_bond_pairs ? "[" + std::to_string(k / E) + "][" + std::to_string(k % E) + "]" : std::string());
-    if (!std::isfinite(rb[k]) || !(rb[k] > 0.0)) return fail(h, TA_ERR_INVALID, what + " must be a finite distance > 0");
-    if (rb[k] > h->rmax)
-      return fail(h, TA_ERR_INVALID, what + " = " + std::to_string(rb[k]) + " exceeds the model's cutoff max(rcut, acut) = " +
-                                     std::to_string(h->rmax) + "; the neighbour list is not complete beyond that");
-  }
-  for (size_t a = 0; a < E; ++a)
-    for (size_t b = a + 1; b < E; ++b)
-      if (rb[a * E + b] != rb[b * E + a])
-        return fail(h, TA_ERR_INVALID, "ta_md_set_adf: r_bond_pairs is not symmetric: [" + std::to_string(a) + "][" +
-                                       std::to_string(b) + "] differs from [" + std::to_string(b) + "][" + std::to_string(a) + "]");
+  std::vector<double> rb;
+  if (const int bad = md_bond_cutoffs(h, "ta_md_set_adf", p->r_bond, r_bond_pairs, rb)) return bad;
   if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_adf: no resident batch");
   if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_set_adf called before ta_md_init");
   bool nomem = false;
@@ -508,6 +580,101 @@ int ta_md_get_adf(ta_handle h, int64_t *counts, int64_t *info, double *r_bond_pa
       info[3] = adf.sched.last;
     }
     if (r_bond_pairs) std::memcpy(r_bond_pairs, adf.rb.data(), E * E * sizeof(double));
+  });
+}
+
+int ta_md_set_order(ta_handle h, const ta_md_order_params *p, const double *r_bond_pairs) {
+  if (!h) return TA_ERR_INVALID;
+  auto &order = h->md.order;
+  if (!p || p->n_bins == 0) {
+    order.on = false;
+    return guarded(h, [&]() {
+      HIP_CHECK(hipStreamSynchronize(h->stream));
+      order.release();
+    });
+  }
+  if (p->n_bins < 0 || p->n_bins > TA_MD_MAX_BINS)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_order: n_bins must be 0 .. " + std::to_string(TA_MD_MAX_BINS));
+  if (p->sample_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_set_order: sample_every must be >= 1");
+  if (p->n_degrees < 1 || p->n_degrees > TA_MD_ORDER_MAX_DEGREES)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_order: n_degrees must be 1 .. " + std::to_string(TA_MD_ORDER_MAX_DEGREES));
+  bool solid_found = false;
+  for (int d = 0; d < p->n_degrees; ++d) {
+    if (p->degrees[d] < 1 || p->degrees[d] > TA_MD_ORDER_MAX_L)
+      return fail(h, TA_ERR_INVALID, "ta_md_set_order: degrees[" + std::to_string(d) + "] = " + std::to_string(p->degrees[d]) +
+                                     " must be 1 .. " + std::to_string(TA_MD_ORDER_MAX_L));
+    for (int e = 0; e < d; ++e)
+      if (p->degrees[e] == p->degrees[d])
+        return fail(h, TA_ERR_INVALID, "ta_md_set_order: degrees[" + std::to_string(d) + "] = " + std::to_string(p->degrees[d]) +
+                                       " is given twice");
+    solid_found = solid_found || p->degrees[d] == p->solid_degree;
+  }
+  if (!solid_found)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_order: solid_degree = " + std::to_string(p->solid_degree) + " is not among the degrees");
+  if (!std::isfinite(p->solid_threshold) || !(p->solid_threshold > -1.0 && p->solid_threshold < 1.0))
+    return fail(h, TA_ERR_INVALID, "ta_md_set_order: solid_threshold must be a finite number inside (-1, 1)");
+  std::vector<double> rb;
+  if (const int bad = md_bond_cutoffs(h, "ta_md_set_order", p->r_bond, r_bond_pairs, rb)) return bad;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_order: no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_set_order called before ta_md_init");
+  bool nomem = false;
+  const int rc = guarded(h, [&]() {
+    order.on = false;  // (until the buffers exist)
+    ta_md_order_params clean = *p;
+    for (int d = p->n_degrees; d < TA_MD_ORDER_MAX_DEGREES; ++d) clean.degrees[d] = 0;
+    nomem = !md_order_alloc(h, clean, rb);
+    if (!nomem) {
+      order.p = clean;
+      order.rb = rb;
+      order.on = true;
+    }
+  });
+  if (rc == TA_OK && nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_set_order: no device memory for buffers of n_bins = " + std::to_string(p->n_bins) +
+                                 "; the feature is off");
+  return rc;
+}
+
+int ta_md_get_order(ta_handle h, int64_t *hist_q, int64_t *hist_qbar, int64_t *hist_conn, int64_t *info,
+                    double *r_bond_pairs) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int bad = md_order_ready(h, "ta_md_get_order")) return bad;
+  const auto &order = h->md.order;
+  return guarded(h, [&]() {
+    const size_t E = (size_t)h->n_elements, F = h->keep_natoms.size();
+    const size_t n_hist = F * E * (size_t)order.p.n_degrees * (size_t)order.p.n_bins;
+    const size_t n_conn = F * E * (TA_MD_ORDER_MAX_CONN + 1);
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the counts are copied as they are");
+    if (hist_q && n_hist) HIP_CHECK(hipMemcpy(hist_q, order.acc.ptr, n_hist * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (hist_qbar && n_hist)
+      HIP_CHECK(hipMemcpy(hist_qbar, order.acc.ptr + n_hist, n_hist * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (hist_conn && n_conn)
+      HIP_CHECK(hipMemcpy(hist_conn, order.acc.ptr + 2 * n_hist, n_conn * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (info) {
+      info[0] = order.sched.taken();
+      info[1] = order.p.n_bins;
+      info[2] = order.p.sample_every;
+      info[3] = order.sched.last;
+    }
+    if (r_bond_pairs) std::memcpy(r_bond_pairs, order.rb.data(), E * E * sizeof(double));
+  });
+}
+
+int ta_md_get_order_atoms(ta_handle h, double *q, double *qbar, int32_t *n_bonds, int32_t *n_conn, double *qlm) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int bad = md_order_ready(h, "ta_md_get_order_atoms")) return bad;
+  const auto &order = h->md.order;
+  if (order.sched.last < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_order_atoms: no sample has been taken yet");
+  return guarded(h, [&]() {
+    const size_t N = h->keep_species.size(), D = (size_t)order.p.n_degrees, M = (size_t)order.n_lm;
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (!N) return;
+    if (q) HIP_CHECK(hipMemcpy(q, order.per_atom.ptr, N * D * sizeof(double), hipMemcpyDeviceToHost));
+    if (qbar) HIP_CHECK(hipMemcpy(qbar, order.per_atom.ptr + N * D, N * D * sizeof(double), hipMemcpyDeviceToHost));
+    if (n_bonds) HIP_CHECK(hipMemcpy(n_bonds, order.per_atom_int.ptr, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (n_conn) HIP_CHECK(hipMemcpy(n_conn, order.per_atom_int.ptr + N, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (qlm) HIP_CHECK(hipMemcpy(qlm, order.qlm.ptr, N * 2 * M * sizeof(double), hipMemcpyDeviceToHost));
   });
 }
 
@@ -616,7 +783,7 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
   md.baro.rec_valid = false;
   md.nhc.rec_valid = false;
   const bool corr_was_valid = md.corr.sched.suspend(), rdf_was_valid = md.rdf.sched.suspend();
-  const bool adf_was_valid = md.adf.sched.suspend();
+  const bool adf_was_valid = md.adf.sched.suspend(), order_was_valid = md.order.sched.suspend();
   res.cell_running = md.baro.running = baro;
   const int rc = guarded(h, [&]() {
     const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
@@ -726,7 +893,43 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     t.n_bins = md.adf.p.n_bins, t.n_elements = h->n_elements, t.n_frames = (int)F;
     t.n_blk = md.adf.n_blk, t.chunk = md.adf.chunk;
     t.dtheta = adf_run ? M_PI / (double)md.adf.p.n_bins : 1.0;
+    // Bond-orientational order: its two launches in the same place, under the same predicate (no volume either)
+    const bool order_run = md.order.on && order_was_valid && N > 0;
+    const ta::SampleSchedule &order_sched = md.order.sched;
+    ta::MdOrderLaunch o;
+    o.blk_start = md.order.blk.ptr;
+    o.rb2 = md.order.rb2.ptr;
+    o.norm = md.order.norm.ptr;
+    o.qlm = md.order.qlm.ptr;
+    o.q = md.order.per_atom.ptr;
+    o.qbar = order_run ? md.order.per_atom.ptr + N * (size_t)md.order.p.n_degrees : nullptr;
+    o.n_bonds = md.order.per_atom_int.ptr;
+    o.n_conn = order_run ? md.order.per_atom_int.ptr + N : nullptr;
+    {
+      const size_t n_hist = F * (size_t)h->n_elements * (size_t)md.order.p.n_degrees * (size_t)md.order.p.n_bins;
+      o.hist_q = md.order.acc.ptr;
+      o.hist_qbar = order_run ? md.order.acc.ptr + n_hist : nullptr;
+      o.hist_conn = order_run ? md.order.acc.ptr + 2 * n_hist : nullptr;
+    }
+    o.status = res.status.ptr;
+    o.n_bins = md.order.p.n_bins, o.n_elements = h->n_elements, o.n_frames = (int)F;
+    o.n_blk = md.order.n_blk, o.chunk = md.order.chunk;
+    o.n_degrees = md.order.p.n_degrees, o.n_lm = md.order.n_lm, o.solid = md.order.solid;
+    o.deg0 = md.order.p.degrees[0], o.deg1 = md.order.p.degrees[1], o.deg2 = md.order.p.degrees[2], o.deg3 = md.order.p.degrees[3];
+    o.threshold = md.order.p.solid_threshold;
     auto integrate = [&](int k, bool drift) {
+      if (order_run && order_sched.due(step0, k)) {
+        o.pos = h->db.pos;
+        o.cells = h->db.cells;
+        o.species = h->db.species;
+        o.atom_start = h->db.atom_start;
+        o.pair_start = h->pair_start.ptr;  // the resident list
+        o.pair_j = h->pair_j.ptr;
+        o.pair_shift = h->pair_shift.ptr;
+        o.seq = (unsigned)k;
+        ta::launch_md_order(o, s);
+        HIP_CHECK(hipGetLastError());
+      }
       if (adf_run && adf_sched.due(step0, k)) {
         t.pos = h->db.pos;
         t.cells = h->db.cells;
@@ -798,6 +1001,8 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     md.rdf.sched.valid = rdf_was_valid;
     if (adf_run) md.adf.sched.finish(md.step);
     md.adf.sched.valid = adf_was_valid;
+    if (order_run) md.order.sched.finish(md.step);
+    md.order.sched.valid = order_was_valid;
     if (n_rebuilds) *n_rebuilds = rebuilds;
     if (baro && F) {
       std::vector<double> rec(4 * n_rec * F);

@@ -217,6 +217,30 @@ struct MdState {
       sched.last = -1;
     }
   } adf;
+  // Bond-orientational order (ta_md_set_order): the bond cutoffs [E][E] of the setting, their squares and the N_lm
+  // on the device, the counts (hist_q, hist_qbar [F][E][D][n_bins], then hist_conn [F][E][32], one buffer), the
+  // per-atom arrays of the newest sample (q_lm [N][n_lm][2]; q, qbar [N][D] in `per_atom`; N_b, n_conn [N] in
+  // `per_atom_int`) and the launches' workgroup layout
+  struct Order {
+    bool on = false;
+    ta_md_order_params p = {0.0, 0.0, 0, 1, 0, {0, 0, 0, 0}, 0};
+    std::vector<double> rb;
+    DevBuf<double> rb2, norm, qlm, per_atom;
+    DevBuf<int32_t> per_atom_int;
+    DevBuf<unsigned long long> acc;
+    DevBuf<int32_t> blk;
+    int n_blk = 0, chunk = 0, n_lm = 0, solid = 0;
+    SampleSchedule sched;
+    void release() {  // frees what the order parameters hold on the device; the setting stays
+      for (auto *b : {&rb2, &norm, &qlm, &per_atom}) b->release();
+      per_atom_int.release();
+      acc.release();
+      blk.release();
+      n_blk = 0;
+      sched.valid = false;
+      sched.last = -1;
+    }
+  } order;
 };
 
 // device-resident relaxation (ta_api_relax.hip; the launches are in ta_relax.hip): FIRE velocities of its own,

@@ -133,6 +133,46 @@ struct MdAdfLaunch {
   double dtheta;                  // pi / n_bins
 };
 
+constexpr int kMdOrderLdsWords = 8192;   // most 32-bit bins of the order launch's LDS histogram of q and q-bar (32 KB)
+constexpr int kMdOrderMaxDegrees = 4;    // TA_MD_ORDER_MAX_DEGREES
+constexpr int kMdOrderMaxL = 12;         // TA_MD_ORDER_MAX_L
+constexpr int kMdOrderMaxConn = 31;      // TA_MD_ORDER_MAX_CONN
+constexpr int kMdOrderMaxLm = 46;        // most (l, m >= 0) of a setting: degrees 12, 11, 10, 9
+constexpr int kMdOrderMaxChunk = 64;     // most centres of a workgroup (their values wait in LDS for the binning)
+
+// Centres per workgroup (four waves, one centre each at a time) of the two order launches for a batch of n_atoms:
+// small batches spread over the chip, large ones merge fewer histograms (the plan, blk_start, is made once by
+// ta_md_set_order). 64 centres keep a workgroup's LDS (32 KB of bins, 4.5 KB of per-atom values, 6 KB of wave
+// sums) at 43 KB: three workgroups of four waves fit the 160 KB of a compute unit.
+inline int md_order_chunk(long long n_atoms) { return n_atoms <= 16384 ? 8 : kMdOrderMaxChunk; }
+
+// Arguments of the two bond-orientational order launches (ta_md_order.hip) that ta_md_run puts in front of the
+// integrator launch of a sampled step, in stream order: the resident (skin) list, the positions and cells of that
+// whole-step state. Pass 1 writes qlm and n_bonds, pass 2 reads them and writes everything else.
+struct MdOrderLaunch {
+  const double *pos;              // [N][3] db.pos
+  const double *cells;            // [F][9]
+  const int32_t *species;         // [N]
+  const int32_t *atom_start;      // [F + 1]
+  const int32_t *blk_start;       // [F + 1] first workgroup of each frame (at least one each)
+  const int32_t *pair_start;      // [N + 1] the resident list: centre i owns pair_start[i] .. pair_start[i + 1] - 1
+  const int32_t *pair_j;          // [P]
+  const int32_t *pair_shift;      // [P][3]
+  const double *rb2;              // [E][E] squares of the bond cutoffs
+  const double *norm;             // [n_lm] N_lm of every (degree, m >= 0), degree by degree
+  double *qlm;                    // [N][n_lm][2] q_lm of the newest sample
+  double *q, *qbar;               // [N][n_degrees]
+  int32_t *n_bonds, *n_conn;      // [N]
+  unsigned long long *hist_q, *hist_qbar;  // [F][E][n_degrees][n_bins] the accumulators
+  unsigned long long *hist_conn;           // [F][E][kMdOrderMaxConn + 1]
+  const unsigned *status;         // the integrator's status word and
+  unsigned seq;                   // sequence number: the same predicate
+  int n_bins, n_elements, n_frames, n_blk, chunk;
+  int n_degrees, n_lm, solid;     // solid: index of solid_degree among the degrees
+  int deg0, deg1, deg2, deg3;     // the degrees (0 beyond n_degrees)
+  double threshold;               // c of the solid-bond test
+};
+
 void launch_md_integrate(const MdLaunch &a, int threads, hipStream_t s);
 
 void launch_md_correlate(const MdCorrLaunch &a, hipStream_t s);
@@ -140,6 +180,8 @@ void launch_md_correlate(const MdCorrLaunch &a, hipStream_t s);
 void launch_md_rdf(const MdRdfLaunch &a, hipStream_t s);
 
 void launch_md_adf(const MdAdfLaunch &a, hipStream_t s);
+
+void launch_md_order(const MdOrderLaunch &a, hipStream_t s);
 
 // xi, eta [n][3] (device): the normals md_integrate draws for absolute step `step`, atoms 0 .. n - 1
 void launch_md_noise(unsigned long long seed, long long step, long long n, double *xi, double *eta, hipStream_t s);

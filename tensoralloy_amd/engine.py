@@ -40,6 +40,9 @@ class Engine:
         self._md_lags = 0          # `md_set_sampling` is on: snapshots in the ring
         self._md_bins = 0          # `md_set_rdf` is on: bins of the pair distributions
         self._md_adf_bins = 0      # `md_set_adf` is on: bins of the bond-angle distributions
+        self._md_order_bins = 0    # `md_set_order` is on: bins of the order-parameter histograms,
+        self._md_order_degrees = ()        # its degrees
+        self._md_order_solid = (0, 0.0)    # and (solid_degree, threshold)
         self._n_elements = int(desc.n_elements)
         # what the neighbour list is complete for: max(rcut, acut), acut counting for angular models only
         self._md_cutoff = max(float(desc.rcut), float(desc.acut)) if int(desc.angular) else float(desc.rcut)
@@ -278,6 +281,8 @@ class Engine:
                 self._md_bins = 0
             if b"ta_md_set_adf" in msg:
                 self._md_adf_bins = 0
+            if b"ta_md_set_order" in msg:
+                self._md_order_bins = 0
             if b"ta_md_set_sampling" in msg:
                 self._md_lags = 0
         self._check(rc)
@@ -457,6 +462,96 @@ class Engine:
                                             _lib.as_dp(r_bond)))
         return {"counts": counts, "n_samples": int(info[0]), "n_bins": int(info[1]), "sample_every": int(info[2]),
                 "last_step": int(info[3]), "r_bond": r_bond, "pairs": pairs}
+
+    def md_set_order(self, degrees=(4, 6), r_bond=None, n_bins=0, sample_every=1, solid=(6, 0.5)):
+        """Bond-orientational order inside `md_run` (`ta_md_set_order`): with `n_bins` = B (1 .. 4096) the loop
+        evaluates, at every step t (counted since `md_init`) with t % `sample_every` == 0, for every atom the
+        Steinhardt parameters q_l of the `degrees` l (up to 4 of them, 1 .. 12, any order), their neighbour average
+        qbar_l (Lechner and Dellago) and the number n_conn of solid bonds: neighbours j with
+        Re sum_m q_lm(i) conj(q_lm(j)) / (|q_l(i)| |q_l(j)|) > c for `solid` = (l, c), l one of the degrees, c inside
+        (-1, 1). The neighbours are those below the bond cutoff `r_bond`, as for `md_set_adf`: one distance, or a
+        symmetric [n_elements, n_elements] matrix; None: the model's cutoff max(rcut, acut), the largest value
+        allowed. q_l and qbar_l are counted into integer histograms of B bins over [0, 1] and n_conn into one of
+        0 .. 31, per frame and species of the atom (`md_order`); the per-atom values of the newest sample stay on
+        the device as well (`md_order_atoms`). `n_bins` = 0 switches it off (the default) and frees the buffers.
+        Needs `md_init`; every call starts from zero counts, as `md_init` does. The setting stays on across
+        `set_frames`. Independent of `md_set_sampling`, `md_set_rdf` and `md_set_adf`; runs under the barostat too.
+        `md_run(0, dt)` samples the resident state once: `md_init`, `md_set_order`, `md_run(0, dt)` analyses a
+        static structure."""
+        E = self._n_elements
+        pairs = C.POINTER(C.c_double)()
+        if r_bond is None:
+            r_bond = self._md_cutoff
+        if np.ndim(r_bond) == 0:
+            scalar = float(r_bond)
+        else:
+            rb = np.ascontiguousarray(r_bond, dtype=np.float64)
+            if rb.shape != (E, E):
+                raise ValueError(f"md_set_order: r_bond must be one distance or [{E}, {E}] (n_elements of the model)")
+            pairs, scalar = _lib.as_dp(rb), float(rb.max())
+        degrees = [int(l) for l in np.atleast_1d(degrees)]
+        solid_degree, threshold = solid
+        p = _lib.MdOrderParams(scalar, float(threshold), int(n_bins), int(sample_every), len(degrees),   # (the library
+                               (C.c_int32 * 4)(*degrees[:4]), int(solid_degree))                         # counts them)
+        rc = self._lib.ta_md_set_order(self._handle, C.byref(p), pairs)
+        if rc == _lib.TA_ERR_NOMEM:   # (no room for the buffers: the library switched the feature off)
+            self._md_order_bins = 0
+        self._check(rc)
+        self._md_order_bins = int(n_bins)
+        if n_bins:
+            self._md_order_degrees, self._md_order_solid = tuple(degrees), (int(solid_degree), float(threshold))
+
+    @property
+    def md_order_bins(self):
+        """Bins of the order-parameter histograms `md_set_order` switched on, 0 while the feature is off."""
+        return self._md_order_bins
+
+    def md_order(self):
+        """What the loop has counted since `md_set_order` (`ta_md_get_order`), a dict: `hist_q`, `hist_qbar` int64
+        [n_frames, n_elements, n_degrees, n_bins], hist_q[f, a, d, k] = atoms of species a in frame f with
+        min(n_bins - 1, floor(q_l n_bins)) == k for l = `degrees`[d], summed over the samples, hist_qbar likewise
+        for the neighbour average; `hist_conn` int64 [n_frames, n_elements, 32]: atoms by min(n_conn, 31);
+        `degrees`, `solid` (degree, threshold), `r_bond` [n_elements, n_elements]: the setting in use;
+        `n_samples`, `n_bins`, `sample_every`, `last_step` (absolute step of the newest sample, -1: none);
+        `n_by_element` [n_frames, n_elements] atoms per frame and element. `md.order_distribution` and
+        `md.solid_fraction` normalise the counts."""
+        if self.info is None:
+            raise ValueError("md_order: no resident batch (call set_frames first)")
+        F, E, B = int(self.info.n_frames), self._n_elements, max(self._md_order_bins, 1)
+        D = max(len(self._md_order_degrees), 1)
+        hist_q, hist_qbar = np.zeros((F, E, D, B), dtype=np.int64), np.zeros((F, E, D, B), dtype=np.int64)
+        hist_conn = np.zeros((F, E, _lib.TA_MD_ORDER_MAX_CONN + 1), dtype=np.int64)
+        info = (C.c_int64 * 4)()
+        r_bond = np.zeros((E, E))
+        ip = C.POINTER(C.c_int64)
+        self._check(self._lib.ta_md_get_order(self._handle, hist_q.ctypes.data_as(ip), hist_qbar.ctypes.data_as(ip),
+                                              hist_conn.ctypes.data_as(ip), info, _lib.as_dp(r_bond)))
+        n_by_element = np.zeros((F, E), dtype=np.int64)
+        for f, fr in enumerate(self._frames):
+            n_by_element[f] = np.bincount(fr.species, minlength=E)[:E]
+        return {"hist_q": hist_q, "hist_qbar": hist_qbar, "hist_conn": hist_conn, "degrees": self._md_order_degrees,
+                "solid": self._md_order_solid, "r_bond": r_bond, "n_samples": int(info[0]), "n_bins": int(info[1]),
+                "sample_every": int(info[2]), "last_step": int(info[3]), "n_by_element": n_by_element}
+
+    def md_order_atoms(self):
+        """The order parameters of every atom in the newest sampled state (`ta_md_get_order_atoms`), a dict: `q`,
+        `qbar` [n_atoms, n_degrees]; `n_bonds`, `n_conn` int32 [n_atoms]: neighbours below the bond cutoff and solid
+        bonds among them; `qlm` complex [n_atoms, sum (l + 1)]: q_lm degree by degree in the order of `degrees`,
+        m = 0 .. l; `step`: the absolute step of that state. Costs a host sync and no list rebuild. Refused until
+        the first sample has been taken."""
+        if self.info is None:
+            raise ValueError("md_order_atoms: no resident batch (call set_frames first)")
+        N, D = int(self.info.n_atoms), max(len(self._md_order_degrees), 1)
+        M = max(sum(l + 1 for l in self._md_order_degrees), 1)
+        q, qbar, qlm = np.zeros((N, D)), np.zeros((N, D)), np.zeros((N, M, 2))
+        n_bonds, n_conn = np.zeros(N, dtype=np.int32), np.zeros(N, dtype=np.int32)
+        info = (C.c_int64 * 4)()
+        self._check(self._lib.ta_md_get_order_atoms(self._handle, _lib.as_dp(q), _lib.as_dp(qbar),
+                                                    n_bonds.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    n_conn.ctypes.data_as(C.POINTER(C.c_int32)), _lib.as_dp(qlm)))
+        self._check(self._lib.ta_md_get_order(self._handle, None, None, None, info, C.POINTER(C.c_double)()))
+        return {"q": q, "qbar": qbar, "n_bonds": n_bonds, "n_conn": n_conn, "qlm": qlm[..., 0] + 1j * qlm[..., 1],
+                "step": int(info[3])}
 
     def md_noise(self, step: int):
         """(xi, eta) [n_atoms, 3]: the standard normals the Langevin step with absolute index `step` (steps

@@ -57,6 +57,14 @@ histograms over [0, pi] per frame, species of the centre and pair of species of 
 from a defective crystal. The counts are exact integers and do not depend on how a run is cut. `adf` normalises
 them to a probability density per degree. No volume enters, so this runs under the barostat as well, and
 independently of `n_lags` and `rdf_bins`.
+
+Bond-orientational order: with `order_bins` (and `order_degrees`, `order_rbond`, `order_every`, `order_solid`) the
+loop evaluates, at every sampled step and for every atom, the Steinhardt parameters q_l of its bonds, their
+neighbour average qbar_l and the number of solid bonds n_conn, on the device (`Engine.md_set_order`;
+`DeviceMD.get_order`, `DeviceMD.get_order_atoms`): the per-atom answer to "which atoms are crystalline, and in
+which lattice". Histograms over the samples are exact integers; the per-atom values are those of the newest sample.
+`order_distribution` normalises a histogram of q, `solid_fraction` and `classify_solid` apply the usual test
+n_conn >= n_min. Runs under the barostat and independently of the other observables.
 """
 from __future__ import annotations
 
@@ -68,7 +76,8 @@ GPa = 1.0 / 160.21766208      # eV / Angstrom^3
 bar = 1.0e-4 * GPa
 
 __all__ = ["fs", "kB", "GPa", "bar", "maxwell_boltzmann", "DeviceMD", "vdos", "diffusion_coefficient",
-           "green_kubo_diffusion", "rdf", "coordination_number", "adf"]
+           "green_kubo_diffusion", "rdf", "coordination_number", "adf", "order_distribution", "solid_fraction",
+           "classify_solid"]
 
 
 def maxwell_boltzmann(masses, kT, rng, zero_momentum=True):
@@ -242,6 +251,43 @@ def adf(counts):
     return theta, p
 
 
+def order_distribution(hist):
+    """Distributions of an order parameter from the integer counts of the device loop (`Engine.md_order`): `hist`
+    [..., B] (`hist_q` or `hist_qbar`, [n_frames, n_elements, n_degrees, B]), atoms in bin k of B uniform bins over
+    [0, 1]. Returns (q, p): the bin centres q_k = (k + 1/2) / B [B] and the probability density per unit q
+    [..., B]: every row times the bin width 1 / B sums to 1. A row without atoms is NaN."""
+    c = np.asarray(hist)
+    if c.ndim < 1 or c.shape[-1] < 1:
+        raise ValueError("order_distribution: hist must be [..., n_bins]")
+    B = c.shape[-1]
+    q = (np.arange(B) + 0.5) / B
+    total = c.sum(axis=-1, keepdims=True).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = np.where(total > 0.0, c * B / total, np.nan)
+    return q, p
+
+
+def solid_fraction(hist_conn, n_min):
+    """Share of the sampled atoms with at least `n_min` solid bonds, from the counts `hist_conn` [..., C] of the
+    device loop (`Engine.md_order`; bin k = atoms with min(n_conn, C - 1) == k, so 0 <= `n_min` <= C - 1):
+    [...], per frame and element for the engine's [n_frames, n_elements, 32]. NaN where no atom was sampled."""
+    c = np.asarray(hist_conn)
+    n_min = int(n_min)
+    if c.ndim < 1 or c.shape[-1] < 1:
+        raise ValueError("solid_fraction: hist_conn must be [..., n_conn_bins]")
+    if not 0 <= n_min <= c.shape[-1] - 1:
+        raise ValueError(f"solid_fraction: n_min must be 0 .. {c.shape[-1] - 1} (the last bin holds everything above)")
+    total = c.sum(axis=-1).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(total > 0.0, c[..., n_min:].sum(axis=-1) / total, np.nan)
+
+
+def classify_solid(n_conn, n_min):
+    """The test of `solid_fraction` atom by atom: a bool array, True where `n_conn` (`Engine.md_order_atoms`)
+    is at least `n_min`."""
+    return np.asarray(n_conn) >= int(n_min)
+
+
 class DeviceMD:
     """
     NVE (velocity Verlet), Berendsen NVT, Langevin NVT or Nose-Hoover chain NVT dynamics of one structure or of a batch of
@@ -282,6 +328,14 @@ class DeviceMD:
                            (`get_adf`); runs under the barostat too. Without `adf_bins` no method of the
                            bond-angle distributions is called on the engine, unless its `md_adf_bins` says that
                            an earlier `DeviceMD` left them on: they are then switched off
+    order_bins, order_degrees, order_rbond, order_every, order_solid : `order_bins` given (1 .. 4096): the loop
+                           evaluates the Steinhardt parameters q_l of `order_degrees` (default (4, 6); up to 4 of
+                           1 .. 12), their neighbour averages and the solid bonds of `order_solid` = (degree,
+                           threshold) (default (6, 0.5)) among the neighbours below `order_rbond` (as `adf_rbond`)
+                           of every `order_every`-th step on the device (`get_order`, `get_order_atoms`); runs
+                           under the barostat too. Without `order_bins` no method of the order parameters is
+                           called on the engine, unless its `md_order_bins` says that an earlier `DeviceMD` left
+                           them on: they are then switched off
 
     Under the barostat the cell of every `Atoms` follows (the atoms are not scaled again), and every `run` call
     that moved the cells ends with one neighbour-list build for the final cells: an observer at interval 1
@@ -293,7 +347,7 @@ class DeviceMD:
                  velocities=None, masses=None, friction=None, seed=0, pressure=None, taup=None,
                  compressibility=None, mask=None, tdamp=None, tchain=3, tloop=1, dof_removed=0, n_lags=None,
                  sample_every=1, rdf_bins=None, rdf_rmax=None, rdf_every=1, adf_bins=None, adf_rbond=None,
-                 adf_every=1):
+                 adf_every=1, order_degrees=None, order_rbond=None, order_bins=None, order_every=1, order_solid=None):
         if not (np.isfinite(timestep) and timestep > 0.0):
             raise ValueError("DeviceMD: timestep must be a finite time > 0")
         barostat = (pressure, taup, compressibility)
@@ -337,6 +391,29 @@ class DeviceMD:
                                      "symmetric")
         elif adf_every != 1 or adf_rbond is not None:
             raise ValueError("DeviceMD: adf_every and adf_rbond belong to the bond-angle distributions (adf_bins)")
+        if order_bins is not None:
+            whole = lambda a: isinstance(a, (int, np.integer)) and not isinstance(a, bool)
+            if not (whole(order_bins) and 1 <= order_bins <= 4096):
+                raise ValueError("DeviceMD: order_bins must be an integer 1 .. 4096")
+            if not (whole(order_every) and order_every >= 1):
+                raise ValueError("DeviceMD: order_every must be an integer >= 1")
+            degrees = (4, 6) if order_degrees is None else tuple(np.atleast_1d(order_degrees).tolist())
+            if not (1 <= len(degrees) <= 4 and all(whole(l) and 1 <= l <= 12 for l in degrees)
+                    and len(set(degrees)) == len(degrees)):
+                raise ValueError("DeviceMD: order_degrees must be 1 .. 4 distinct integers 1 .. 12")
+            solid = (6, 0.5) if order_solid is None else tuple(order_solid)
+            if not (len(solid) == 2 and solid[0] in degrees and np.isfinite(solid[1]) and -1.0 < solid[1] < 1.0):
+                raise ValueError("DeviceMD: order_solid must be (one of order_degrees, a threshold inside (-1, 1))")
+            if order_rbond is not None:
+                rb = np.asarray(order_rbond, dtype=np.float64)
+                if rb.ndim not in (0, 2) or rb.size == 0 or not (np.all(np.isfinite(rb)) and np.all(rb > 0.0)):
+                    raise ValueError("DeviceMD: order_rbond must be a finite distance > 0, or a square matrix of them")
+                if rb.ndim == 2 and (rb.shape[0] != rb.shape[1] or not np.array_equal(rb, rb.T)):
+                    raise ValueError("DeviceMD: order_rbond must be a finite distance > 0, or a square matrix of them, "
+                                     "symmetric")
+        elif order_every != 1 or order_rbond is not None or order_degrees is not None or order_solid is not None:
+            raise ValueError("DeviceMD: order_degrees, order_rbond, order_every and order_solid belong to the "
+                             "bond-orientational order (order_bins)")
         if self._barostat:
             if any(p is None for p in barostat):
                 raise ValueError("DeviceMD: the barostat needs pressure, taup and compressibility")
@@ -447,6 +524,11 @@ class DeviceMD:
             engine.md_set_adf(self._adf_bins, adf_rbond, int(adf_every))
         elif getattr(engine, "md_adf_bins", 0):
             engine.md_set_adf(0)
+        self._order_bins = int(order_bins) if order_bins is not None else 0
+        if self._order_bins:   # (opt-in in the same way)
+            engine.md_set_order(degrees, order_rbond, self._order_bins, int(order_every), solid)
+        elif getattr(engine, "md_order_bins", 0):
+            engine.md_set_order(n_bins=0)
         self._natoms = np.array([len(a) for a in self.atoms_list], dtype=np.int64)
         self.velocities = velocities.copy()
         self.epot = self.ekin = None   # per-frame records of the last state
@@ -562,6 +644,26 @@ class DeviceMD:
             raise ValueError("DeviceMD.get_adf: the bond-angle distributions are off (adf_bins)")
         theta, p = adf(self.engine.md_adf()["counts"])
         return theta, (p[0] if self._single else p)
+
+    def get_order(self):
+        """(q, p, pbar): the bin centres [order_bins] and the distributions of q_l and of the neighbour average
+        qbar_l, [n_elements, n_degrees, order_bins] each (a batch: [n_frames, ...]), over every atom of every state
+        sampled so far, normalised as `order_distribution` does, NaN for an element without atoms. The counts,
+        `hist_conn` among them, are in `engine.md_order()`. Needs `order_bins`."""
+        if not self._order_bins:
+            raise ValueError("DeviceMD.get_order: the bond-orientational order is off (order_bins)")
+        out = self.engine.md_order()
+        q, p = order_distribution(out["hist_q"])
+        pbar = order_distribution(out["hist_qbar"])[1]
+        return q, (p[0] if self._single else p), (pbar[0] if self._single else pbar)
+
+    def get_order_atoms(self):
+        """The order parameters of every atom in the newest sampled state: the dict of `Engine.md_order_atoms`
+        (`q`, `qbar`, `n_bonds`, `n_conn`, `qlm`, `step`), the atoms of a batch in the order of the frames.
+        `classify_solid(n_conn, n_min)` marks the solid ones. Needs `order_bins`."""
+        if not self._order_bins:
+            raise ValueError("DeviceMD.get_order_atoms: the bond-orientational order is off (order_bins)")
+        return self.engine.md_order_atoms()
 
     def get_volume(self):
         """Cell volume per frame, in A^3."""
