@@ -598,7 +598,55 @@ int ta_step_view(ta_handle h, const double *positions, const double *cells, uint
  *                        [n_frames][n_elements][TA_MD_ORDER_MAX_CONN + 1]; info [4] as ta_md_get_adf; r_bond_pairs
  *                        [n_elements][n_elements], the cutoffs in use. Any pointer may be NULL.
  *   ta_md_get_order_atoms  the per-atom arrays of the newest sample (above); TA_ERR_INVALID while no sample has
- *                        been taken. Any pointer may be NULL. */
+ *                        been taken. Any pointer may be NULL.
+ *
+ * Structure factors inside the loop (opt-in; with it never switched on nothing changes): the static structure
+ * factor S(q), the intermediate scattering function F(q, t) and the longitudinal and transverse current
+ * correlations, by a direct sum over the atoms, so that nothing stops at the model's cutoff. The caller gives
+ * n_q = Q integer triples n[Q][3] (Miller indices, |n_c| <= TA_MD_SQ_MAX_INDEX), shared by all frames. With h the
+ * cell of frame f (rows are lattice vectors) and s_i = x_i h^-1 the wave vector is q = 2 pi h^-1 n, so that
+ * q . x_i = 2 pi n . s_i: commensurate with every frame's own cell, and unchanged when an atom moves by a lattice
+ * vector (the positions are unwrapped). Everything is fp64. At the whole-step state (x(t), v(t)) of every absolute
+ * step t with t % sample_every == 0, from the first such step at or behind the call that switched the feature on
+ * (the state and the velocities are those ta_md_set_sampling samples), per frame f, element a and vector q
+ *     rho_a(q) = sum_{i in a} exp(+i 2 pi n . s_i)
+ *     j_a(q)   = sum_{i in a} v_i exp(+i 2 pi n . s_i)        (three Cartesian components; with currents = 1)
+ * with the phase reduced exactly (n . s minus the nearest integer) before sine and cosine are taken. Sample number
+ * m lives in slot m % n_lags of a ring of amplitude rows on the device and is correlated with the rows of the lags
+ * k = 0 .. min(m, n_lags - 1), over every time origin, per ordered pair of elements (a, b):
+ *     A_rho[f][a][b][k][q] += Re(rho_a(q; m) conj rho_b(q; m - k))
+ *     A_L  [f][a][b][k][q] += Re((qhat . j_a(q; m)) conj (qhat . j_b(q; m - k)))     qhat = q / |q|, 0 for n = 0
+ *     A_J  [f][a][b][k][q] += Re(j_a(q; m) . conj j_b(q; m - k))                     (trace of the current tensor)
+ * The number of time origins at lag k is max(0, n_samples - k). F_ab(q, t_k) = A_rho[k] / (origins sqrt(N_a N_b))
+ * are the Ashcroft-Langreth partials, S_ab(q) = F_ab(q, 0); (A_J - A_L) / 2 is the transverse part. n_lags = 1 is
+ * the static case. All sums have a fixed order (the atoms of a chunk in index order, then the chunks of a frame
+ * in index order; no floating-point atomics): a run cut into calls reproduces the uncut run bit for bit. Device
+ * memory: the ring takes n_lags F E Q (1 or 4) 16 bytes, every accumulator F E^2 n_lags Q 8 bytes.
+ * Independent of every other observable and of the thermostat; ta_md_run with n_steps = 0 samples the resident
+ * state once: ta_md_init + ta_md_set_sq + ta_md_run(0) analyses a static structure.
+ *   ta_md_set_sq         NULL or n_q == 0 switches it off (the default; always allowed) and frees the buffers.
+ *                        Switching on needs a resident batch and ta_md_init; it allocates and zeroes the
+ *                        accumulators and forgets earlier samples (so does every further call). The life cycle is
+ *                        that of ta_md_set_sampling: ta_set_frames keeps the setting and drops the data with the MD
+ *                        state; ta_md_init starts an empty ring and zero accumulators. TA_ERR_INVALID, with the
+ *                        argument named by ta_last_error and the setting left as it was: n_q outside
+ *                        0 .. TA_MD_SQ_MAX_Q; n_lags outside 1 .. TA_MD_MAX_LAGS; sample_every < 1; currents not
+ *                        0 or 1; miller NULL or an index beyond TA_MD_SQ_MAX_INDEX; a frame that is not periodic
+ *                        along all three axes or whose cell is singular. TA_ERR_NOMEM when the device allocation
+ *                        fails; the feature is then off.
+ *   ta_md_run            TA_ERR_INVALID while this feature and the barostat are both on (cell and positions of the
+ *                        snapshot would belong to different states). A run that fails leaves the data invalid:
+ *                        both getters are TA_ERR_INVALID until ta_md_set_sq or ta_md_init is called again.
+ *   ta_md_get_sq         a_rho, a_l, a_j [n_frames][n_elements][n_elements][n_lags][n_q]: the raw sums; info [8] =
+ *                        {n_samples, n_q, n_lags, sample_every, absolute step of the newest sample or -1, currents,
+ *                        atoms per workgroup of the amplitude launch (the longest chain of additions of one
+ *                        partial sum; a frame's partials are then added one after another), 0}; miller [n_q][3].
+ *                        Any pointer may be NULL; a_l or a_j without currents is TA_ERR_INVALID.
+ *   ta_md_get_sq_amplitudes  the amplitude rows first_lag .. first_lag + n - 1 back from the newest one (0 = the
+ *                        newest): rho [n][n_frames][n_elements][n_q][2] (real, imaginary), cur
+ *                        [n][n_frames][n_elements][n_q][3][2] and their absolute steps [n]; any pointer may be
+ *                        NULL. TA_ERR_INVALID when first_lag < 0, n < 0, first_lag + n exceeds the
+ *                        min(n_samples, n_lags) rows held, or cur is asked for without currents. */
 #define TA_MD_MAX_CHAIN 8
 #define TA_MD_MAX_LAGS 4096
 #define TA_MD_MAX_BINS 4096
@@ -628,6 +676,14 @@ typedef struct {
   int32_t n_lags;       /* L, 1 .. TA_MD_MAX_LAGS; 0 switches sampling off (the default) */
   int32_t sample_every;  /* s >= 1 */
 } ta_md_sampling_params;
+#define TA_MD_SQ_MAX_Q 4096
+#define TA_MD_SQ_MAX_INDEX 64
+typedef struct {
+  int32_t n_q;           /* Q, 1 .. TA_MD_SQ_MAX_Q; 0 switches the feature off (the default) */
+  int32_t n_lags;        /* L, 1 .. TA_MD_MAX_LAGS; 1: the static structure factor only */
+  int32_t sample_every;  /* s >= 1 */
+  int32_t currents;      /* 0, or 1: j_a(q), A_L and A_J as well */
+} ta_md_sq_params;
 typedef struct {
   double kT0;           /* target, energy; <= 0 switches the thermostat off (the default) */
   double tau;           /* time, finite, > 0 */
@@ -668,6 +724,9 @@ int ta_md_set_order(ta_handle h, const ta_md_order_params *p, const double *r_bo
 int ta_md_get_order(ta_handle h, int64_t *hist_q, int64_t *hist_qbar, int64_t *hist_conn, int64_t *info,
                     double *r_bond_pairs);
 int ta_md_get_order_atoms(ta_handle h, double *q, double *qbar, int32_t *n_bonds, int32_t *n_conn, double *qlm);
+int ta_md_set_sq(ta_handle h, const ta_md_sq_params *p, const int32_t *miller);
+int ta_md_get_sq(ta_handle h, double *a_rho, double *a_l, double *a_j, int64_t *info, int32_t *miller);
+int ta_md_get_sq_amplitudes(ta_handle h, int32_t first_lag, int32_t n, double *rho, double *cur, int64_t *steps);
 
 /* Device-resident structure relaxation: the resident batch is brought to a force minimum in ONE call, every
  * frame on its own, with positions, velocities and forces staying on the device. The optimiser is FIRE

@@ -1,6 +1,7 @@
 // C ABI of the device-resident MD loop: the ta_md_* entry points (include/tensoralloy_amd.h). The loop itself
 // is in ta_resident.hip; the integrator, correlation, pair-distribution, bond-angle and bond-order launches are in
-// ta_md.hip, ta_md_corr.hip, ta_md_rdf.hip, ta_md_adf.hip and ta_md_order.hip.
+// ta_md.hip, ta_md_corr.hip, ta_md_rdf.hip, ta_md_adf.hip and ta_md_order.hip; the structure-factor launches in
+// ta_md_sq.hip.
 #include <cmath>
 #include <cstring>
 
@@ -143,6 +144,62 @@ bool md_order_alloc(ta_context *h, const ta_md_order_params &p, const std::vecto
   return true;
 }
 
+// The Miller triples on the device, an empty ring, zeroed accumulators, the partials, the snapshot rows and the
+// amplitude launch's workgroup layout for the resident batch under setting `p`, with no sample held. False when the
+// device has no room (everything is released then); throws otherwise.
+bool md_sq_alloc(ta_context *h, const ta_md_sq_params &p, const std::vector<int32_t> &miller) {
+  auto &g = h->md.sq;
+  const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
+  const size_t E = (size_t)h->n_elements, Q = (size_t)p.n_q, L = (size_t)p.n_lags, P = p.currents ? 8 : 2;
+  const size_t n_acc = (p.currents ? 3 : 1) * F * E * E * L * Q;
+  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches add to the old buffers)
+  g.release();
+  const int chunk = ta::md_sq_chunk((long long)N);
+  const std::vector<int32_t> start = frame_blocks(h, 1, chunk);
+  if (!g.acc.try_exact(n_acc) || !g.ring.try_exact(L * F * E * P * Q) || !g.part.try_exact((size_t)start[F] * E * P * Q) ||
+      !g.snap_x.try_exact(3 * N) || !g.snap_v.try_exact(3 * N) || !g.miller_dev.try_exact(3 * Q) || !g.blk.try_exact(F + 1)) {
+    g.release();
+    return false;
+  }
+  HIP_CHECK(hipMemset(g.acc.ptr, 0, std::max<size_t>(n_acc, 1) * sizeof(double)));
+  HIP_CHECK(hipMemcpy(g.blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(g.miller_dev.ptr, miller.data(), 3 * Q * sizeof(int32_t), hipMemcpyHostToDevice));
+  g.n_blk = (int)start[F];
+  g.chunk = chunk;
+  g.sched.every = p.sample_every;
+  g.sched.start(h->md.step);
+  g.sched.valid = true;
+  return true;
+}
+
+// what ta_md_set_sq asks of the resident frames: periodic along all three axes, a cell that can be inverted.
+// Returns 0 or the error code.
+int md_sq_frames(ta_context *h) {
+  const size_t F = h->keep_natoms.size();
+  for (size_t f = 0; f < F; ++f) {
+    for (int k = 0; k < 3; ++k)
+      if (!h->keep_pbc[3 * f + k])
+        return fail(h, TA_ERR_INVALID, "ta_md_set_sq: frame " + std::to_string(f) + " is not periodic along all three axes; "
+                                       "the wave vectors are those of the cell");
+    const double *c = h->ref_cells.data() + 9 * f;
+    const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
+    if (!std::isfinite(det) || !(std::fabs(det) > 0.0))
+      return fail(h, TA_ERR_INVALID, "ta_md_set_sq: the cell of frame " + std::to_string(f) + " is singular");
+  }
+  return TA_OK;
+}
+
+// what the two getters of the structure factors need; returns 0 or the error code
+int md_sq_ready(ta_context *h, const char *who) {
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, std::string(who) + " called before ta_md_init");
+  if (!h->md.sq.on) return fail(h, TA_ERR_INVALID, std::string(who) + ": the structure factors are off (ta_md_set_sq)");
+  if (!h->md.sq.sched.valid)
+    return fail(h, TA_ERR_INVALID, std::string(who) + ": a ta_md_run failed and left the data invalid; call "
+                                   "ta_md_set_sq or ta_md_init again");
+  return TA_OK;
+}
+
 // The bond cutoffs [E][E] of ta_md_set_adf and ta_md_set_order (`who`): r_bond for every pair, or r_bond_pairs.
 // Returns 0 with `rb` filled, or the error code: a cutoff not finite, <= 0 or above the model's, or no symmetry.
 int md_bond_cutoffs(ta_context *h, const std::string &who, double r_bond, const double *r_bond_pairs, std::vector<double> &rb) {
@@ -212,7 +269,10 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
   if (velocities)
     for (size_t i = 0; i < 3 * N; ++i)
       if (!std::isfinite(velocities[i])) return fail(h, TA_ERR_INVALID, "ta_md_init: non-finite velocity");
-  bool ring_nomem = false, rdf_nomem = false, adf_nomem = false, order_nomem = false;
+  bool ring_nomem = false, rdf_nomem = false, adf_nomem = false, order_nomem = false, sq_nomem = false;
+  // (a batch the wave vectors are not defined for: the feature goes off, as when there is no room for it)
+  const bool sq_unfit = h->md.sq.on && md_sq_frames(h) != TA_OK;
+  const std::string sq_why = sq_unfit ? h->err : std::string();
   const int rc = guarded(h, [&]() {
     auto &md = h->md;
     md.valid = false;
@@ -257,6 +317,15 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
       md.order.on = false;
       order_nomem = true;
     }
+    if (md.sq.on && sq_unfit) {
+      md.sq.on = false;
+      HIP_CHECK(hipStreamSynchronize(h->stream));
+      md.sq.release();
+    }
+    if (md.sq.on && !md_sq_alloc(h, md.sq.p, md.sq.miller)) {  // an empty ring for this batch, or none
+      md.sq.on = false;
+      sq_nomem = true;
+    }
     md.valid = true;
   });
   if (rc == TA_OK && ring_nomem)
@@ -267,6 +336,9 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
     return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the counts of ta_md_set_adf; the feature is off");
   if (rc == TA_OK && order_nomem)
     return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the buffers of ta_md_set_order; the feature is off");
+  if (rc == TA_OK && sq_nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the buffers of ta_md_set_sq; the feature is off");
+  if (rc == TA_OK && sq_unfit) return fail(h, TA_ERR_INVALID, "ta_md_init: " + sq_why + "; the feature is off");
   return rc;
 }
 
@@ -678,6 +750,109 @@ int ta_md_get_order_atoms(ta_handle h, double *q, double *qbar, int32_t *n_bonds
   });
 }
 
+int ta_md_set_sq(ta_handle h, const ta_md_sq_params *p, const int32_t *miller) {
+  if (!h) return TA_ERR_INVALID;
+  auto &sq = h->md.sq;
+  if (!p || p->n_q == 0) {
+    sq.on = false;
+    return guarded(h, [&]() {
+      HIP_CHECK(hipStreamSynchronize(h->stream));
+      sq.release();
+    });
+  }
+  if (p->n_q < 0 || p->n_q > TA_MD_SQ_MAX_Q)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_sq: n_q must be 0 .. " + std::to_string(TA_MD_SQ_MAX_Q));
+  if (p->n_lags < 1 || p->n_lags > TA_MD_MAX_LAGS)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_sq: n_lags must be 1 .. " + std::to_string(TA_MD_MAX_LAGS));
+  if (p->sample_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_set_sq: sample_every must be >= 1");
+  if (p->currents != 0 && p->currents != 1) return fail(h, TA_ERR_INVALID, "ta_md_set_sq: currents must be 0 or 1");
+  if (!miller) return fail(h, TA_ERR_INVALID, "ta_md_set_sq: miller is NULL");
+  for (int j = 0; j < 3 * p->n_q; ++j)
+    if (miller[j] < -TA_MD_SQ_MAX_INDEX || miller[j] > TA_MD_SQ_MAX_INDEX)
+      return fail(h, TA_ERR_INVALID, "ta_md_set_sq: miller[" + std::to_string(j / 3) + "][" + std::to_string(j % 3) + "] = " +
+                                     std::to_string(miller[j]) + " must be within +-" + std::to_string(TA_MD_SQ_MAX_INDEX));
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_sq: no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_set_sq called before ta_md_init");
+  if (const int bad = md_sq_frames(h)) return bad;
+  bool nomem = false;
+  const std::vector<int32_t> triples(miller, miller + 3 * (size_t)p->n_q);
+  const int rc = guarded(h, [&]() {
+    sq.on = false;  // (until the buffers exist)
+    nomem = !md_sq_alloc(h, *p, triples);
+    if (!nomem) {
+      sq.p = *p;
+      sq.miller = triples;
+      sq.on = true;
+    }
+  });
+  if (rc == TA_OK && nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_set_sq: no device memory for n_q = " + std::to_string(p->n_q) + " vectors at n_lags = " +
+                                 std::to_string(p->n_lags) + "; the feature is off");
+  return rc;
+}
+
+int ta_md_get_sq(ta_handle h, double *a_rho, double *a_l, double *a_j, int64_t *info, int32_t *miller) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int bad = md_sq_ready(h, "ta_md_get_sq")) return bad;
+  const auto &sq = h->md.sq;
+  if ((a_l || a_j) && !sq.p.currents)
+    return fail(h, TA_ERR_INVALID, "ta_md_get_sq: a_l and a_j need the currents (ta_md_sq_params.currents = 1)");
+  return guarded(h, [&]() {
+    const size_t E = (size_t)h->n_elements;
+    const size_t n = h->keep_natoms.size() * E * E * (size_t)sq.p.n_lags * (size_t)sq.p.n_q;
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (a_rho && n) HIP_CHECK(hipMemcpy(a_rho, sq.acc.ptr, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (a_l && n) HIP_CHECK(hipMemcpy(a_l, sq.acc.ptr + n, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (a_j && n) HIP_CHECK(hipMemcpy(a_j, sq.acc.ptr + 2 * n, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (info) {
+      info[0] = sq.sched.taken();
+      info[1] = sq.p.n_q;
+      info[2] = sq.p.n_lags;
+      info[3] = sq.p.sample_every;
+      info[4] = sq.sched.last;
+      info[5] = sq.p.currents;
+      info[6] = sq.chunk;
+      info[7] = 0;
+    }
+    if (miller) std::memcpy(miller, sq.miller.data(), sq.miller.size() * sizeof(int32_t));
+  });
+}
+
+int ta_md_get_sq_amplitudes(ta_handle h, int32_t first_lag, int32_t n, double *rho, double *cur, int64_t *steps) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int bad = md_sq_ready(h, "ta_md_get_sq_amplitudes")) return bad;
+  const auto &sq = h->md.sq;
+  const int64_t taken = sq.sched.taken(), L = sq.p.n_lags, held = std::min(taken, L);
+  if (first_lag < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_sq_amplitudes: first_lag must be >= 0");
+  if (n < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_sq_amplitudes: n must be >= 0");
+  if ((int64_t)first_lag + n > held)
+    return fail(h, TA_ERR_INVALID, "ta_md_get_sq_amplitudes: first_lag + n = " + std::to_string((int64_t)first_lag + n) +
+                                   " exceeds the " + std::to_string(held) + " rows held (min(n_samples, n_lags))");
+  if (cur && !sq.p.currents)
+    return fail(h, TA_ERR_INVALID, "ta_md_get_sq_amplitudes: cur needs the currents (ta_md_sq_params.currents = 1)");
+  return guarded(h, [&]() {
+    const size_t FE = h->keep_natoms.size() * (size_t)h->n_elements, Q = (size_t)sq.p.n_q, P = sq.p.currents ? 8 : 2;
+    const size_t row = FE * P * Q;
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    std::vector<double> buf(row);
+    for (int32_t j = 0; j < n; ++j) {
+      const int64_t idx = taken - 1 - first_lag - j;  // sample number
+      if (steps) steps[j] = sq.sched.step(idx);
+      if (!row || (!rho && !cur)) continue;
+      HIP_CHECK(hipMemcpy(buf.data(), sq.ring.ptr + (size_t)(idx % L) * row, row * sizeof(double), hipMemcpyDeviceToHost));
+      // the device row is [f][e][plane][q]; the caller's arrays have q before the components
+      for (size_t fe = 0; fe < FE; ++fe)
+        for (size_t q = 0; q < Q; ++q) {
+          const double *src = buf.data() + fe * P * Q + q;
+          if (rho)
+            for (size_t c = 0; c < 2; ++c) rho[(((size_t)j * FE + fe) * Q + q) * 2 + c] = src[c * Q];
+          if (cur)
+            for (size_t c = 0; c < 6; ++c) cur[(((size_t)j * FE + fe) * Q + q) * 6 + c] = src[(2 + c) * Q];
+        }
+    }
+  });
+}
+
 int ta_md_noise(ta_handle h, int64_t step, double *xi, double *eta) {
   if (!h) return TA_ERR_INVALID;
   if (!xi || !eta) return fail(h, TA_ERR_INVALID, "ta_md_noise: null argument");
@@ -776,6 +951,10 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
   if (md.rdf.on && baro)
     return fail(h, TA_ERR_INVALID, "ta_md_run: the pair distributions (ta_md_set_rdf) and the barostat (ta_md_set_barostat) are "
                                    "both on; normalising the counts needs one volume: switch one of them off");
+  if (md.sq.on && baro)
+    return fail(h, TA_ERR_INVALID, "ta_md_run: the structure factors (ta_md_set_sq) and the barostat (ta_md_set_barostat) are "
+                                   "both on; cell and positions of a snapshot would belong to different states: switch one of "
+                                   "them off");
   if (n_rebuilds) *n_rebuilds = 0;
   want |= TA_WANT_ENERGY | TA_WANT_FORCES;
   want &= ~(uint32_t)TA_WANT_REUSE_DESCRIPTORS;
@@ -784,6 +963,7 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
   md.nhc.rec_valid = false;
   const bool corr_was_valid = md.corr.sched.suspend(), rdf_was_valid = md.rdf.sched.suspend();
   const bool adf_was_valid = md.adf.sched.suspend(), order_was_valid = md.order.sched.suspend();
+  const bool sq_was_valid = md.sq.sched.suspend();
   res.cell_running = md.baro.running = baro;
   const int rc = guarded(h, [&]() {
     const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
@@ -917,6 +1097,25 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     o.n_degrees = md.order.p.n_degrees, o.n_lm = md.order.n_lm, o.solid = md.order.solid;
     o.deg0 = md.order.p.degrees[0], o.deg1 = md.order.p.degrees[1], o.deg2 = md.order.p.degrees[2], o.deg3 = md.order.p.degrees[3];
     o.threshold = md.order.p.solid_threshold;
+    // Structure factors: the integrator launch of a due step writes the whole-step state (x, v) to the slot of the
+    // correlation ring when md_set_sampling is due at the same launch, to two rows of this feature's otherwise;
+    // the three launches go BEHIND it, under the same predicate, and read that snapshot.
+    const bool sq_run = md.sq.on && sq_was_valid && N > 0;
+    const ta::SampleSchedule &sq_sched = md.sq.sched;
+    ta::MdSqLaunch u;
+    u.blk_start = md.sq.blk.ptr;
+    u.miller = md.sq.miller_dev.ptr;
+    u.part = md.sq.part.ptr;
+    u.ring = md.sq.ring.ptr;
+    {
+      const size_t E = (size_t)h->n_elements, n_acc = F * E * E * (size_t)md.sq.p.n_lags * (size_t)md.sq.p.n_q;
+      u.acc_rho = md.sq.acc.ptr;
+      u.acc_l = sq_run && md.sq.p.currents ? md.sq.acc.ptr + n_acc : nullptr;
+      u.acc_j = sq_run && md.sq.p.currents ? md.sq.acc.ptr + 2 * n_acc : nullptr;
+    }
+    u.status = res.status.ptr;
+    u.n_q = md.sq.p.n_q, u.n_lags = md.sq.p.n_lags, u.n_elements = h->n_elements, u.n_frames = (int)F;
+    u.n_blk = md.sq.n_blk, u.chunk = md.sq.chunk, u.currents = md.sq.p.currents;
     auto integrate = [&](int k, bool drift) {
       if (order_run && order_sched.due(step0, k)) {
         o.pos = h->db.pos;
@@ -975,6 +1174,8 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
         a.snap_x = md.corr.ring_x.ptr + slot * 3 * N;
         a.snap_v = md.corr.ring_v.ptr + slot * 3 * N;
       }
+      const bool sq_due = sq_run && sq_sched.due(step0, k);
+      if (sq_due && !due) a.snap_x = md.sq.snap_x.ptr, a.snap_v = md.sq.snap_v.ptr;
       ta::launch_md_integrate(a, threads, s);
       HIP_CHECK(hipGetLastError());
       if (due) {  // directly behind the launch that sampled, under the same predicate
@@ -982,6 +1183,16 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
         c.atom_start = h->db.atom_start;
         c.seq = (unsigned)k;
         ta::launch_md_correlate(c, s);
+        HIP_CHECK(hipGetLastError());
+      }
+      if (sq_due) {
+        u.x = a.snap_x, u.v = a.snap_v;
+        u.cells = h->db.cells;
+        u.species = h->db.species;
+        u.atom_start = h->db.atom_start;
+        u.seq = (unsigned)k;
+        u.n = (long long)sq_sched.index(step0 + k);
+        ta::launch_md_sq(u, s);
         HIP_CHECK(hipGetLastError());
       }
     };
@@ -1003,6 +1214,8 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     md.adf.sched.valid = adf_was_valid;
     if (order_run) md.order.sched.finish(md.step);
     md.order.sched.valid = order_was_valid;
+    if (sq_run) md.sq.sched.finish(md.step);
+    md.sq.sched.valid = sq_was_valid;
     if (n_rebuilds) *n_rebuilds = rebuilds;
     if (baro && F) {
       std::vector<double> rec(4 * n_rec * F);

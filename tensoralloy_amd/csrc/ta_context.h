@@ -241,6 +241,28 @@ struct MdState {
       sched.last = -1;
     }
   } order;
+  // Structure factors (ta_md_set_sq): the Miller triples [Q][3] of the setting and their device twin, the ring of
+  // amplitude rows [L][F][E][planes][Q] (planes = 2, or 8 with currents), the accumulators (A_rho, then A_L and
+  // A_J with currents, [F][E][E][L][Q] each, one buffer), the amplitude launch's partials and workgroup layout, and
+  // the two rows [N][3] the integrator writes a sampled state to when md_set_sampling's ring does not take it
+  struct Sq {
+    bool on = false;
+    ta_md_sq_params p = {0, 1, 1, 0};
+    std::vector<int32_t> miller;
+    DevBuf<int32_t> miller_dev;
+    DevBuf<double> ring, acc, part, snap_x, snap_v;
+    DevBuf<int32_t> blk;
+    int n_blk = 0, chunk = 0;
+    SampleSchedule sched;
+    void release() {  // frees what the structure factors hold on the device; the setting stays
+      for (auto *b : {&ring, &acc, &part, &snap_x, &snap_v}) b->release();
+      miller_dev.release();
+      blk.release();
+      n_blk = 0;
+      sched.valid = false;
+      sched.last = -1;
+    }
+  } sq;
 };
 
 // device-resident relaxation (ta_api_relax.hip; the launches are in ta_relax.hip): FIRE velocities of its own,

@@ -173,6 +173,36 @@ struct MdOrderLaunch {
   double threshold;               // c of the solid-bond test
 };
 
+constexpr int kMdSqTile = 64;    // q-vectors per workgroup of the amplitude launch: one wave, a lane is a q-vector
+constexpr int kMdSqSlab = 64;    // atoms a workgroup of the amplitude launch holds in LDS at a time
+constexpr int kMdSqMaxQ = 4096;  // TA_MD_SQ_MAX_Q
+
+// Atoms per workgroup of the amplitude launch for a batch of n_atoms: small batches spread over the chip, large
+// ones write fewer partials (the plan, blk_start, is made once by ta_md_set_sq). The chunk is also the longest
+// chain of additions of one partial.
+inline int md_sq_chunk(long long n_atoms) { return n_atoms <= 16384 ? 64 : 1024; }
+
+// Arguments of the three structure-factor launches (ta_md_sq.hip) that ta_md_run puts behind an integrator launch
+// that wrote the whole-step state (x, v) of a sampled step to `x` / `v`: the amplitudes rho_a(q) (and j_a(q) with
+// currents) of sample n per chunk, their sum in chunk order into ring slot n % n_lags, and the correlation of that
+// row with the rows of the lags 0 .. min(n, n_lags - 1). A row is [F][E][planes][Q] with planes = 2 (Re, Im of rho)
+// or 8 (then Re, Im of j_x, j_y, j_z): q fastest.
+struct MdSqLaunch {
+  const double *x, *v;            // [N][3] the snapshot the integrator launch in front wrote
+  const double *cells;            // [F][9]
+  const int32_t *species;         // [N]
+  const int32_t *atom_start;      // [F + 1]
+  const int32_t *blk_start;       // [F + 1] first chunk of each frame (at least one each)
+  const int32_t *miller;          // [Q][3]
+  double *part;                   // [n_blk][E][planes][Q] per-workgroup sums
+  double *ring;                   // [n_lags] rows
+  double *acc_rho, *acc_l, *acc_j;  // [F][E][E][n_lags][Q] the accumulators (acc_l, acc_j: with currents)
+  const unsigned *status;         // the integrator's status word and
+  unsigned seq;                   // sequence number: the same predicate
+  long long n;                    // index of the newest sample
+  int n_q, n_lags, n_elements, n_frames, n_blk, chunk, currents;
+};
+
 void launch_md_integrate(const MdLaunch &a, int threads, hipStream_t s);
 
 void launch_md_correlate(const MdCorrLaunch &a, hipStream_t s);
@@ -182,6 +212,8 @@ void launch_md_rdf(const MdRdfLaunch &a, hipStream_t s);
 void launch_md_adf(const MdAdfLaunch &a, hipStream_t s);
 
 void launch_md_order(const MdOrderLaunch &a, hipStream_t s);
+
+void launch_md_sq(const MdSqLaunch &a, hipStream_t s);
 
 // xi, eta [n][3] (device): the normals md_integrate draws for absolute step `step`, atoms 0 .. n - 1
 void launch_md_noise(unsigned long long seed, long long step, long long n, double *xi, double *eta, hipStream_t s);

@@ -43,6 +43,7 @@ class Engine:
         self._md_order_bins = 0    # `md_set_order` is on: bins of the order-parameter histograms,
         self._md_order_degrees = ()        # its degrees
         self._md_order_solid = (0, 0.0)    # and (solid_degree, threshold)
+        self._md_sq = (0, 1, False)        # `md_set_sq` is on: (n_q, n_lags, currents)
         self._n_elements = int(desc.n_elements)
         # what the neighbour list is complete for: max(rcut, acut), acut counting for angular models only
         self._md_cutoff = max(float(desc.rcut), float(desc.acut)) if int(desc.angular) else float(desc.rcut)
@@ -285,6 +286,10 @@ class Engine:
                 self._md_order_bins = 0
             if b"ta_md_set_sampling" in msg:
                 self._md_lags = 0
+            if b"ta_md_set_sq" in msg:
+                self._md_sq = (0, 1, False)
+        elif rc == _lib.TA_ERR_INVALID and b"ta_md_set_sq" in (self._lib.ta_last_error(self._handle) or b""):
+            self._md_sq = (0, 1, False)   # (a batch without wave vectors: the library switched the feature off)
         self._check(rc)
 
     def md_set_thermostat(self, kT=0.0, tau=0.0):
@@ -552,6 +557,103 @@ class Engine:
         self._check(self._lib.ta_md_get_order(self._handle, None, None, None, info, C.POINTER(C.c_double)()))
         return {"q": q, "qbar": qbar, "n_bonds": n_bonds, "n_conn": n_conn, "qlm": qlm[..., 0] + 1j * qlm[..., 1],
                 "step": int(info[3])}
+
+    def md_set_sq(self, miller=None, n_lags=1, sample_every=1, currents=False):
+        """Structure factors inside `md_run` (`ta_md_set_sq`): `miller` int [Q, 3] (1 .. 4096 triples, |n_c| <= 64;
+        `md.q_points` makes them) are the wave vectors q = 2 pi h^-1 n of every frame's own cell. At every step t
+        (counted since `md_init`) with t % `sample_every` == 0 the loop sums rho_a(q) = sum_i exp(i q . x_i) per
+        frame and element (with `currents` also j_a(q) = sum_i v_i exp(i q . x_i)) over ALL atoms, in fp64, keeps the
+        last `n_lags` rows in a ring on the device and adds Re(rho_a(q; n) conj rho_b(q; n - k)) (with `currents`
+        the longitudinal part and the trace of the current correlations too) at every lag k onto accumulators that
+        stay on the device (`md_sq`, `md_sq_amplitudes`). `n_lags` = 1 is the static structure factor alone.
+        `miller` None or empty switches it off (the default) and frees the buffers. Needs `md_init` and frames
+        periodic in all three directions; every call starts an empty ring and zero accumulators, as `md_init`
+        does. The setting stays on across `set_frames`. Independent of the other observables; `md_run` refuses it
+        under the barostat. Device memory: the ring takes n_lags x n_frames x n_elements x Q x 16 bytes (x 4 with
+        `currents`), each of the one (three) accumulators n_frames x n_elements^2 x n_lags x Q x 8 bytes: 64 frames
+        of two elements at Q = 1000 and 256 lags are 524 MB per accumulator."""
+        null = C.POINTER(C.c_int32)()
+        if miller is None or np.size(miller) == 0:
+            self._check(self._lib.ta_md_set_sq(self._handle, None, null))
+            self._md_sq = (0, 1, False)
+            return
+        m = np.asarray(miller)
+        if m.ndim != 2 or m.shape[1] != 3 or not np.issubdtype(m.dtype, np.integer):
+            raise ValueError("md_set_sq: miller must be integers [n_q, 3]")
+        if np.abs(m).max() > _lib.TA_MD_SQ_MAX_INDEX:
+            raise ValueError(f"md_set_sq: the Miller indices must be within +-{_lib.TA_MD_SQ_MAX_INDEX}")
+        if len(m) > _lib.TA_MD_SQ_MAX_Q:
+            raise ValueError(f"md_set_sq: at most {_lib.TA_MD_SQ_MAX_Q} wave vectors")
+        m = np.ascontiguousarray(m, dtype=np.int32)
+        p = _lib.MdSqParams(len(m), int(n_lags), int(sample_every), int(bool(currents)))
+        rc = self._lib.ta_md_set_sq(self._handle, C.byref(p), m.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc == _lib.TA_ERR_NOMEM:   # (no room: the library switched the feature off)
+            self._md_sq = (0, 1, False)
+        self._check(rc)
+        self._md_sq = (len(m), int(n_lags), bool(currents))
+
+    @property
+    def md_sq_vectors(self):
+        """Wave vectors per frame that `md_set_sq` switched on, 0 while the feature is off."""
+        return self._md_sq[0]
+
+    def md_sq(self):
+        """What the loop has accumulated since `md_set_sq` (`ta_md_get_sq`), a dict: `a_rho` [n_frames, n_elements,
+        n_elements, n_lags, n_q]: sums over the time origins of Re(rho_a(q; n) conj rho_b(q; n - k)); with currents
+        `a_l` and `a_j` likewise for the longitudinal current and for the trace of the current tensor (None
+        without); `miller` int32 [n_q, 3]; `q` [n_frames, n_q, 3] = 2 pi h^-1 n and `q_norm` [n_frames, n_q] for the
+        resident cells; `n_origins` [n_lags] = max(0, n_samples - k); `n_by_element` [n_frames, n_elements];
+        `n_samples`, `n_lags`, `sample_every`, `last_step` (absolute step of the newest sample, -1: none),
+        `currents`, `chunk` (atoms per workgroup of the amplitude launch). `md.intermediate_scattering` and
+        `md.structure_factor` normalise the sums."""
+        if self.info is None:
+            raise ValueError("md_sq: no resident batch (call set_frames first)")
+        F, E = int(self.info.n_frames), self._n_elements
+        Q, L, cur = max(self._md_sq[0], 1), self._md_sq[1], self._md_sq[2]
+        a_rho = np.zeros((F, E, E, L, Q))
+        a_l, a_j = (np.zeros((F, E, E, L, Q)), np.zeros((F, E, E, L, Q))) if cur else (None, None)
+        info = (C.c_int64 * 8)()
+        miller = np.zeros((Q, 3), dtype=np.int32)
+        null = C.POINTER(C.c_double)()
+        self._check(self._lib.ta_md_get_sq(self._handle, _lib.as_dp(a_rho), _lib.as_dp(a_l) if cur else null,
+                                           _lib.as_dp(a_j) if cur else null, info,
+                                           miller.ctypes.data_as(C.POINTER(C.c_int32))))
+        n_by_element = np.zeros((F, E), dtype=np.int64)
+        for f, fr in enumerate(self._frames):
+            n_by_element[f] = np.bincount(fr.species, minlength=E)[:E]
+        q = 2.0 * np.pi * np.einsum("fjc,qc->fqj", np.linalg.inv(self.md_cells()), miller.astype(np.float64))
+        n_samples = int(info[0])
+        return {"a_rho": a_rho, "a_l": a_l, "a_j": a_j, "miller": miller, "q": q, "q_norm": np.linalg.norm(q, axis=-1),
+                "n_origins": np.maximum(0, n_samples - np.arange(L)).astype(np.int64), "n_by_element": n_by_element,
+                "n_samples": n_samples, "n_lags": int(info[2]), "sample_every": int(info[3]), "last_step": int(info[4]),
+                "currents": bool(info[5]), "chunk": int(info[6])}
+
+    def md_sq_amplitudes(self, n=None):
+        """The last `n` amplitude rows the ring holds, oldest first (`ta_md_get_sq_amplitudes`; default: all,
+        min(n_samples, n_lags)): a dict `rho` complex [n, n_frames, n_elements, n_q], `cur` complex
+        [n, n_frames, n_elements, n_q, 3] (None without currents) and `steps` [n] (absolute steps)."""
+        if self.info is None:
+            raise ValueError("md_sq_amplitudes: no resident batch (call set_frames first)")
+        null = C.POINTER(C.c_double)()
+        if n is None:
+            info = (C.c_int64 * 8)()
+            self._check(self._lib.ta_md_get_sq_amplitudes(self._handle, 0, 0, null, null, None))   # (its own refusals)
+            self._check(self._lib.ta_md_get_sq(self._handle, null, null, null, info, C.POINTER(C.c_int32)()))
+            n = min(int(info[0]), int(info[2]))
+        n = int(n)
+        if n < 0:
+            raise ValueError("md_sq_amplitudes: n must be >= 0")
+        F, E = int(self.info.n_frames), self._n_elements
+        Q, cur = max(self._md_sq[0], 1), self._md_sq[2]
+        rho = np.zeros((max(n, 1), F, E, Q, 2))
+        j = np.zeros((max(n, 1), F, E, Q, 3, 2)) if cur else None
+        steps = np.zeros(max(n, 1), dtype=np.int64)
+        self._check(self._lib.ta_md_get_sq_amplitudes(self._handle, 0, n, _lib.as_dp(rho), _lib.as_dp(j) if cur else null,
+                                                      steps.ctypes.data_as(C.POINTER(C.c_int64))))
+        rho = (rho[..., 0] + 1j * rho[..., 1])[:n][::-1].copy()
+        if cur:
+            j = (j[..., 0] + 1j * j[..., 1])[:n][::-1].copy()
+        return {"rho": rho, "cur": j, "steps": steps[:n][::-1].copy()}
 
     def md_noise(self, step: int):
         """(xi, eta) [n_atoms, 3]: the standard normals the Langevin step with absolute index `step` (steps

@@ -65,6 +65,18 @@ neighbour average qbar_l and the number of solid bonds n_conn, on the device (`E
 which lattice". Histograms over the samples are exact integers; the per-atom values are those of the newest sample.
 `order_distribution` normalises a histogram of q, `solid_fraction` and `classify_solid` apply the usual test
 n_conn >= n_min. Runs under the barostat and independently of the other observables.
+
+Structure factors: with `sq_miller` (and `sq_lags`, `sq_every`, `sq_currents`) the loop sums, at every sampled step,
+the density amplitudes rho_a(q) = sum_i exp(i q . x_i) of every element over ALL atoms of a frame, at the wave
+vectors q = 2 pi h^-1 n of the integer triples given (`q_points` lists those below a |q|), keeps the last `sq_lags`
+rows on the device and correlates them at every lag (`Engine.md_set_sq`; `DeviceMD.get_structure_factor`,
+`get_intermediate_scattering`): the static structure factor S(q) that diffraction measures, which a Fourier
+transform of a g(r) that stops at the model's cutoff cannot give, the intermediate scattering function F(q, t) and,
+with `sq_currents`, the longitudinal and transverse current correlations C_L(q, t), C_T(q, t), from which phonon
+dispersions, sound velocities and damping are read. `intermediate_scattering` and `structure_factor` normalise the
+sums (Ashcroft-Langreth partials), `transverse_current` splits the current trace, `dynamic_structure_factor`
+transforms to S(q, nu), `shell_average` bins over |q|. Everything is fp64 with a fixed order of addition: a run cut
+into calls gives the same bits. Refused under the barostat.
 """
 from __future__ import annotations
 
@@ -77,7 +89,8 @@ bar = 1.0e-4 * GPa
 
 __all__ = ["fs", "kB", "GPa", "bar", "maxwell_boltzmann", "DeviceMD", "vdos", "diffusion_coefficient",
            "green_kubo_diffusion", "rdf", "coordination_number", "adf", "order_distribution", "solid_fraction",
-           "classify_solid"]
+           "classify_solid", "q_points", "intermediate_scattering", "structure_factor", "transverse_current",
+           "dynamic_structure_factor", "shell_average"]
 
 
 def maxwell_boltzmann(masses, kT, rng, zero_momentum=True):
@@ -109,20 +122,8 @@ def vdos(vacf, dt_sample, window="hann"):
     truncated tail to zero, or None, w_k = 1. g is scaled so that its integral over nu by the trapezoid rule on
     this grid is 1 (per THz)."""
     c = np.asarray(vacf, dtype=np.float64)
-    L = c.shape[-1] if c.ndim else 0
-    if L < 2:
-        raise ValueError("vdos: a vacf with at least two lags along the last axis is needed")
-    if not (np.isfinite(dt_sample) and dt_sample > 0.0):
-        raise ValueError("vdos: dt_sample must be a finite time > 0")
-    k = np.arange(L)
-    if window == "hann":
-        w = 0.5 * (1.0 + np.cos(np.pi * k / (L - 1)))
-    elif window is None:
-        w = np.ones(L)
-    else:
-        raise ValueError("vdos: window must be 'hann' or None")
-    w[0] *= 0.5
-    w[-1] *= 0.5
+    w, k = _cosine_weights("vdos", "vacf", c, dt_sample, window)
+    L = len(k)
     with np.errstate(divide="ignore", invalid="ignore"):
         c = c / c[..., :1]
     g = (c * w) @ np.cos(np.pi * np.outer(k, k) / (L - 1))
@@ -130,6 +131,26 @@ def vdos(vacf, dt_sample, window="hann"):
     with np.errstate(divide="ignore", invalid="ignore"):
         g = g / _trapezoid(g, nu[1] - nu[0])[..., None]
     return nu, g
+
+
+def _cosine_weights(who, what, c, dt_sample, window):
+    """The checks of a one-sided cosine transform of `c` [..., L] and its weights: the window times the trapezoid
+    rule's halves at both ends, and the lags arange(L)."""
+    L = c.shape[-1] if c.ndim else 0
+    if L < 2:
+        raise ValueError(f"{who}: a {what} with at least two lags along the last axis is needed")
+    if not (np.isfinite(dt_sample) and dt_sample > 0.0):
+        raise ValueError(f"{who}: dt_sample must be a finite time > 0")
+    k = np.arange(L)
+    if window == "hann":
+        w = 0.5 * (1.0 + np.cos(np.pi * k / (L - 1)))
+    elif window is None:
+        w = np.ones(L)
+    else:
+        raise ValueError(f"{who}: window must be 'hann' or None")
+    w[0] *= 0.5
+    w[-1] *= 0.5
+    return w, k
 
 
 def diffusion_coefficient(msd, dt_sample, fit=None):
@@ -288,6 +309,111 @@ def classify_solid(n_conn, n_min):
     return np.asarray(n_conn) >= int(n_min)
 
 
+def q_points(cell, q_max, max_index=64):
+    """The integer triples n [Q, 3] (int32) of all wave vectors q = 2 pi h^-1 n of `cell` (h [3, 3], rows are lattice
+    vectors) with 0 < |q| <= `q_max` (1 / A), one of each pair +-n (the first non-zero index is positive), ordered by
+    |q|. Since n_c = q . a_c / (2 pi), |n_c| <= q_max |a_c| / (2 pi); triples with an index beyond `max_index` (at
+    most 64, what the device takes) are left out."""
+    h = np.asarray(cell, dtype=np.float64)
+    if h.shape != (3, 3) or not np.all(np.isfinite(h)) or not abs(np.linalg.det(h)) > 0.0:
+        raise ValueError("q_points: cell must be a finite, non-singular [3, 3] matrix")
+    if not (np.isfinite(q_max) and q_max > 0.0):
+        raise ValueError("q_points: q_max must be finite and > 0")
+    if int(max_index) != max_index or not 1 <= max_index <= 64:
+        raise ValueError("q_points: max_index must be an integer 1 .. 64")
+    top = np.minimum(np.floor(q_max * np.linalg.norm(h, axis=1) / (2.0 * np.pi) * (1.0 + 1e-12)).astype(int), int(max_index))
+    n = np.stack(np.meshgrid(*[np.arange(-t, t + 1) for t in top], indexing="ij"), axis=-1).reshape(-1, 3)
+    first = np.where(n[:, 0] != 0, n[:, 0], np.where(n[:, 1] != 0, n[:, 1], n[:, 2]))
+    n = n[first > 0]
+    q = np.linalg.norm(2.0 * np.pi * n @ np.linalg.inv(h).T, axis=1)
+    keep = q <= q_max
+    n, q = n[keep], q[keep]
+    return np.ascontiguousarray(n[np.argsort(q, kind="stable")], dtype=np.int32)
+
+
+def intermediate_scattering(acc, n_samples, n_by_element):
+    """Ashcroft-Langreth partial intermediate scattering functions from the sums of the device loop
+    (`Engine.md_sq`): `acc` [..., E, E, L, Q] (`a_rho`; `a_l` or `transverse_current(a_j, a_l)` give the current
+    correlations C_L, C_T in the same way), `n_by_element` [..., E] atoms per element. Returns
+        F_ab(q, t_k) = A[a][b][k][q] / ((n_samples - k) sqrt(N_a N_b))
+    [..., E, E, L, Q]: NaN where an element is absent and at lags without a time origin (k >= n_samples)."""
+    a = np.asarray(acc, dtype=np.float64)
+    if a.ndim < 4 or a.shape[-3] != a.shape[-4]:
+        raise ValueError("intermediate_scattering: acc must be [..., n_elements, n_elements, n_lags, n_q]")
+    if int(n_samples) != n_samples or n_samples < 0:
+        raise ValueError("intermediate_scattering: n_samples must be an integer >= 0")
+    n = np.asarray(n_by_element, dtype=np.float64)
+    if n.shape != a.shape[:-3]:
+        raise ValueError("intermediate_scattering: n_by_element must be [..., n_elements], matching acc")
+    origins = np.maximum(0, int(n_samples) - np.arange(a.shape[-2])).astype(np.float64)
+    den = np.sqrt(n[..., :, None] * n[..., None, :])[..., None, None] * origins[:, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den > 0.0, a / den, np.nan)
+
+
+def structure_factor(a_rho, n_samples, n_by_element):
+    """(S_ab, S): the partial static structure factors S_ab(q) = F_ab(q, 0) [..., E, E, Q] of
+    `intermediate_scattering` and the total S(q) = sum_ab sqrt(c_a c_b) S_ab(q) [..., Q] with c_a = N_a / N (for one
+    element S = S_aa; for a mixture the structure factor of equal scattering lengths, |sum_i exp(i q . x_i)|^2 / N).
+    An absent element has NaN partials and no share in S."""
+    f = intermediate_scattering(a_rho, n_samples, n_by_element)[..., 0, :]
+    n = np.asarray(n_by_element, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        c = n / n.sum(axis=-1, keepdims=True)
+    w = np.sqrt(c[..., :, None] * c[..., None, :])[..., None]
+    total = np.where(w > 0.0, w * f, 0.0).sum(axis=(-3, -2))
+    sampled = (n.sum(axis=-1)[..., None] > 0.0) & (int(n_samples) > 0)
+    return f, np.where(sampled, total, np.nan)
+
+
+def transverse_current(a_j, a_l):
+    """(A_J - A_L) / 2: the current correlation per transverse direction, from the trace of the current tensor and its
+    longitudinal part (`Engine.md_sq`: `a_j`, `a_l`). Normalise it with `intermediate_scattering`."""
+    return 0.5 * (np.asarray(a_j, dtype=np.float64) - np.asarray(a_l, dtype=np.float64))
+
+
+def dynamic_structure_factor(F, dt_sample, window="hann"):
+    """Dynamic structure factor from an intermediate scattering function (or spectra of C_L, C_T from the current
+    correlations): `F` [..., L, Q] (L >= 2 lags along the last axis but one, as `intermediate_scattering` returns
+    it) sampled every `dt_sample` (ASE time units). Returns (nu, S): nu [L] in THz on the grid of `vdos`,
+    nu_j = j / (2 (L - 1) dt_sample), and
+        S(q, nu_j) = 2 dt (w_0 F_0 / 2 + sum_{k=1}^{L-2} w_k F_k cos(pi j k / (L - 1)) + w_{L-1} F_{L-1} cos(pi j) / 2)
+    [..., L, Q] with dt in ps: the cosine transform of `vdos` (the trapezoid rule in time, `window` "hann" or None)
+    without its normalisations, so that the integral of S over nu from -inf to inf is F(q, 0)."""
+    f = np.moveaxis(np.asarray(F, dtype=np.float64), -2, -1) if np.ndim(F) >= 2 else np.asarray(F, dtype=np.float64)
+    if f.ndim < 2:
+        raise ValueError("dynamic_structure_factor: F must be [..., n_lags, n_q]")
+    w, k = _cosine_weights("dynamic_structure_factor", "F", f, dt_sample, window)
+    L = len(k)
+    s = (f * w) @ np.cos(np.pi * np.outer(k, k) / (L - 1))
+    dt_ps = (dt_sample / fs) * 1.0e-3
+    nu = k / (2.0 * (L - 1) * dt_ps)
+    return nu, np.moveaxis(2.0 * dt_ps * s, -1, -2)
+
+
+def shell_average(values, q_norm, n_bins):
+    """Average over shells of |q|: `values` [..., Q] at the wave vectors of length `q_norm` [Q], in `n_bins` uniform
+    bins over (0, max |q|]. Returns (q, mean, counts): the mean |q| of every shell [n_bins] (NaN for an empty one),
+    the mean of the values [..., n_bins] (NaN likewise) and the number of vectors per shell."""
+    v = np.asarray(values, dtype=np.float64)
+    qn = np.asarray(q_norm, dtype=np.float64)
+    if qn.ndim != 1 or v.ndim < 1 or v.shape[-1] != len(qn) or len(qn) < 1:
+        raise ValueError("shell_average: values [..., n_q] and q_norm [n_q] are needed")
+    if int(n_bins) != n_bins or n_bins < 1:
+        raise ValueError("shell_average: n_bins must be an integer >= 1")
+    if not (np.all(np.isfinite(qn)) and np.all(qn >= 0.0) and qn.max() > 0.0):
+        raise ValueError("shell_average: q_norm must be finite, >= 0 and not all 0")
+    n_bins = int(n_bins)
+    k = np.minimum(np.ceil(qn / qn.max() * n_bins).astype(int) - 1, n_bins - 1)   # (edges belong to the shell below)
+    inside = k >= 0   # (q = 0 belongs to no shell)
+    onehot = (k[inside, None] == np.arange(n_bins)[None, :]).astype(np.float64)
+    counts = onehot.sum(axis=0).astype(np.int64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.where(counts > 0, qn[inside] @ onehot / counts, np.nan)
+        mean = np.where(counts > 0, v[..., inside] @ onehot / counts, np.nan)
+    return q, mean, counts
+
+
 class DeviceMD:
     """
     NVE (velocity Verlet), Berendsen NVT, Langevin NVT or Nose-Hoover chain NVT dynamics of one structure or of a batch of
@@ -336,6 +462,15 @@ class DeviceMD:
                            under the barostat too. Without `order_bins` no method of the order parameters is
                            called on the engine, unless its `md_order_bins` says that an earlier `DeviceMD` left
                            them on: they are then switched off
+    sq_miller, sq_lags, sq_every, sq_currents : `sq_miller` given (int [Q, 3], 1 .. 4096 triples with |n_c| <= 64,
+                           e.g. from `q_points`): the loop sums the density amplitudes at the wave vectors
+                           q = 2 pi h^-1 n of every `sq_every`-th step over all atoms (the state at construction is
+                           the first sample), keeps `sq_lags` rows (default 1: the static structure factor only) and
+                           correlates them on the device, with `sq_currents` the currents as well
+                           (`get_structure_factor`, `get_intermediate_scattering`); needs frames periodic in all three
+                           directions and excludes the barostat. Without `sq_miller` no method of the structure
+                           factors is called on the engine, unless its `md_sq_vectors` says that an earlier
+                           `DeviceMD` left them on: they are then switched off
 
     Under the barostat the cell of every `Atoms` follows (the atoms are not scaled again), and every `run` call
     that moved the cells ends with one neighbour-list build for the final cells: an observer at interval 1
@@ -347,7 +482,8 @@ class DeviceMD:
                  velocities=None, masses=None, friction=None, seed=0, pressure=None, taup=None,
                  compressibility=None, mask=None, tdamp=None, tchain=3, tloop=1, dof_removed=0, n_lags=None,
                  sample_every=1, rdf_bins=None, rdf_rmax=None, rdf_every=1, adf_bins=None, adf_rbond=None,
-                 adf_every=1, order_degrees=None, order_rbond=None, order_bins=None, order_every=1, order_solid=None):
+                 adf_every=1, order_degrees=None, order_rbond=None, order_bins=None, order_every=1, order_solid=None,
+                 sq_miller=None, sq_lags=None, sq_every=1, sq_currents=False):
         if not (np.isfinite(timestep) and timestep > 0.0):
             raise ValueError("DeviceMD: timestep must be a finite time > 0")
         barostat = (pressure, taup, compressibility)
@@ -414,6 +550,23 @@ class DeviceMD:
         elif order_every != 1 or order_rbond is not None or order_degrees is not None or order_solid is not None:
             raise ValueError("DeviceMD: order_degrees, order_rbond, order_every and order_solid belong to the "
                              "bond-orientational order (order_bins)")
+        if sq_miller is not None:
+            whole = lambda a: isinstance(a, (int, np.integer)) and not isinstance(a, bool)
+            miller = np.asarray(sq_miller)
+            if (miller.ndim != 2 or miller.shape[1] != 3 or not 1 <= len(miller) <= 4096
+                    or not np.issubdtype(miller.dtype, np.integer) or np.abs(miller).max() > 64):
+                raise ValueError("DeviceMD: sq_miller must be 1 .. 4096 integer triples [n_q, 3] with indices within +-64")
+            if sq_lags is not None and not (whole(sq_lags) and 1 <= sq_lags <= 4096):
+                raise ValueError("DeviceMD: sq_lags must be an integer 1 .. 4096")
+            if not (whole(sq_every) and sq_every >= 1):
+                raise ValueError("DeviceMD: sq_every must be an integer >= 1")
+            if not isinstance(sq_currents, (bool, np.bool_)):
+                raise ValueError("DeviceMD: sq_currents must be True or False")
+            if self._barostat:
+                raise ValueError("DeviceMD: sq_miller (structure factors) excludes the barostat (pressure, taup, "
+                                 "compressibility): cell and positions of a snapshot would belong to different states")
+        elif sq_lags is not None or sq_every != 1 or sq_currents is not False:
+            raise ValueError("DeviceMD: sq_lags, sq_every and sq_currents belong to the structure factors (sq_miller)")
         if self._barostat:
             if any(p is None for p in barostat):
                 raise ValueError("DeviceMD: the barostat needs pressure, taup and compressibility")
@@ -529,6 +682,13 @@ class DeviceMD:
             engine.md_set_order(degrees, order_rbond, self._order_bins, int(order_every), solid)
         elif getattr(engine, "md_order_bins", 0):
             engine.md_set_order(n_bins=0)
+        self._sq = sq_miller is not None
+        self._sq_every, self._sq_currents = int(sq_every), bool(sq_currents)
+        if self._sq:   # (opt-in in the same way)
+            engine.md_set_sq(np.ascontiguousarray(miller, dtype=np.int32), 1 if sq_lags is None else int(sq_lags),
+                             self._sq_every, self._sq_currents)
+        elif getattr(engine, "md_sq_vectors", 0):
+            engine.md_set_sq(None)
         self._natoms = np.array([len(a) for a in self.atoms_list], dtype=np.int64)
         self.velocities = velocities.copy()
         self.epot = self.ekin = None   # per-frame records of the last state
@@ -664,6 +824,35 @@ class DeviceMD:
         if not self._order_bins:
             raise ValueError("DeviceMD.get_order_atoms: the bond-orientational order is off (order_bins)")
         return self.engine.md_order_atoms()
+
+    def get_structure_factor(self):
+        """(q, q_norm, S_ab, S): the wave vectors [n_q, 3] and their lengths [n_q] (1 / A) for the frame's cell, the
+        Ashcroft-Langreth partial structure factors [n_elements, n_elements, n_q] and the total S(q) [n_q] over every
+        state sampled so far, as `structure_factor` normalises them (a batch: a leading axis n_frames on all four).
+        NaN where the frame has no atom of an element or nothing was sampled yet. Needs `sq_miller`."""
+        if not self._sq:
+            raise ValueError("DeviceMD.get_structure_factor: the structure factors are off (sq_miller)")
+        out = self.engine.md_sq()
+        s_ab, s = structure_factor(out["a_rho"], out["n_samples"], out["n_by_element"])
+        res = (out["q"], out["q_norm"], s_ab, s)
+        return tuple(r[0] for r in res) if self._single else res
+
+    def get_intermediate_scattering(self):
+        """(t, F): the lag times arange(sq_lags) * sq_every * timestep and the partial intermediate scattering
+        functions F_ab(q, t) [n_elements, n_elements, sq_lags, n_q] (a batch: [n_frames, ...]) over every time origin
+        sampled so far, as `intermediate_scattering` normalises them. With `sq_currents`: (t, F, C_L, C_T), the
+        longitudinal current correlation and the transverse one per direction, normalised in the same way.
+        `dynamic_structure_factor` transforms each of them to frequencies. Needs `sq_miller`."""
+        if not self._sq:
+            raise ValueError("DeviceMD.get_intermediate_scattering: the structure factors are off (sq_miller)")
+        out = self.engine.md_sq()
+        t = np.arange(out["n_lags"]) * self._sq_every * self.dt
+        res = [intermediate_scattering(out["a_rho"], out["n_samples"], out["n_by_element"])]
+        if self._sq_currents:
+            res.append(intermediate_scattering(out["a_l"], out["n_samples"], out["n_by_element"]))
+            res.append(intermediate_scattering(transverse_current(out["a_j"], out["a_l"]), out["n_samples"],
+                                               out["n_by_element"]))
+        return (t,) + tuple(r[0] if self._single else r for r in res)
 
     def get_volume(self):
         """Cell volume per frame, in A^3."""
