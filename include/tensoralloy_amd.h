@@ -600,6 +600,56 @@ int ta_step_view(ta_handle h, const double *positions, const double *cells, uint
  *   ta_md_get_order_atoms  the per-atom arrays of the newest sample (above); TA_ERR_INVALID while no sample has
  *                        been taken. Any pointer may be NULL.
  *
+ * Clusters of solid or selected atoms inside the loop (opt-in; with it never switched on nothing changes): the
+ * connected components of the selected atoms, for the size of the largest crystalline nucleus as a function of
+ * time (n_min > 0) and for the clusters of chosen elements in a solid solution (n_min = 0). Parameters: a
+ * species_mask, n_min, n_bins = B, n_series = T, sample_every = s and a symmetric link cutoff rl[a][b] per pair of
+ * elements (r_link: the same value for all pairs; NaN: max(rcut, acut) of the model), at most max(rcut, acut). The
+ * schedule is that of ta_md_set_adf, kept separately. At a sampled whole-step state
+ *     atom i of species a is SELECTED when bit a of species_mask is set and (n_min == 0 or n_conn(i) >= n_min),
+ *         n_conn being that of ta_md_set_order for the same state;
+ *     two selected atoms i != j are LINKED when the resident list holds an entry (j, S) of centre i with
+ *         d = x_j - x_i + S . h (fp64, unwrapped positions and cells as the device holds them), d . d < rl[a][b]^2;
+ *         an entry that is an image of i itself links nothing, several images of j link i and j once;
+ *     a CLUSTER is a connected component of the selected atoms under links. Its size is its number of atoms, not
+ *         images: a cluster that percolates through the periodic boundary is one cluster. Its LABEL is the smallest
+ *         index of its members, in the caller's atom order over the whole batch.
+ * Every output is an integer and a function of the state alone: exact, whatever the order in which threads arrive,
+ * the skin, the pattern of list rebuilds or the way a run is cut into calls. Four launches in front of the integrator
+ * launch of a sampled step, behind the order launches of that step (select; a lock-free union by index with integer
+ * atomic minima; flatten; summarise): no host wait, no grid barrier, no floating-point atomics. Kept per atom for
+ * the NEWEST sample only: label [n_atoms] (-1 when not selected) and size [n_atoms] (0 when not selected).
+ * Accumulated over the samples as unsigned 64-bit integer counts:
+ *     hist[f][k] += number of clusters of frame f with k = min(size, B) - 1      (the last bin collects sizes >= B)
+ * A time series on the device: sample n writes the row series[n % T][f][4] = {selected atoms, clusters, size of the
+ * largest cluster, label of the largest (among equals the smallest label); {0, 0, 0, -1} when nothing is selected}
+ * and its absolute step into steps[n % T]; the newest T rows are kept. No volume enters: the feature runs under the
+ * barostat, with the cells of the sampled state, under every thermostat, and independently of the other observables
+ * but for this: n_min > 0 reads the n_conn of ta_md_set_order for the same state. ta_md_run with n_steps = 0 samples
+ * the resident state once.
+ *   ta_md_set_clusters   NULL or n_bins == 0 switches it off (the default; always allowed) and frees the buffers.
+ *                        r_link_pairs: NULL, or [n_elements][n_elements] symmetric cutoffs that replace r_link.
+ *                        Switching on needs a resident batch and ta_md_init; it allocates and zeroes the histogram,
+ *                        the series and the sample counter (so does every further call). The life cycle is that of
+ *                        ta_md_set_adf: ta_set_frames keeps the setting and drops the data with the MD state;
+ *                        ta_md_init starts from zero. TA_ERR_INVALID, with the argument named by ta_last_error and
+ *                        the setting left as it was: n_bins outside 0 .. TA_MD_MAX_BINS; n_series outside
+ *                        1 .. TA_MD_CLUSTER_MAX_SERIES; sample_every < 1; n_min outside 0 .. TA_MD_ORDER_MAX_CONN;
+ *                        species_mask zero or with a bit at or above n_elements; a cutoff not finite (but for
+ *                        r_link = NaN), <= 0, or greater than max(rcut, acut) of the model; r_link_pairs not
+ *                        symmetric. TA_ERR_NOMEM when the device allocation fails; the feature is then off.
+ *   ta_md_run            With n_min > 0, TA_ERR_INVALID (ta_last_error names the reason) unless ta_md_set_order is
+ *                        on, this sample_every is a multiple of the order feature's and this schedule's first
+ *                        sample is not in front of the order schedule's. TA_ERR_HIP when a loop of the link launch
+ *                        overran its cap (never, by construction). A run that fails leaves the data invalid: both
+ *                        getters are TA_ERR_INVALID until ta_md_set_clusters or ta_md_init is called again.
+ *   ta_md_get_clusters   hist [n_frames][n_bins]; series [rows held][n_frames][4] and steps [rows held], oldest
+ *                        first; info [6] = {n_samples, n_bins, sample_every, absolute step of the newest sample or
+ *                        -1, rows held = min(n_samples, T), T}; r_link_pairs [n_elements][n_elements], the cutoffs
+ *                        in use. Any pointer may be NULL.
+ *   ta_md_get_cluster_atoms  label and size of the newest sample (above); TA_ERR_INVALID while no sample has been
+ *                        taken. Any pointer may be NULL.
+ *
  * Structure factors inside the loop (opt-in; with it never switched on nothing changes): the static structure
  * factor S(q), the intermediate scattering function F(q, t) and the longitudinal and transverse current
  * correlations, by a direct sum over the atoms, so that nothing stops at the model's cutoff. The caller gives
@@ -672,8 +722,17 @@ typedef struct {
   int32_t degrees[4];      /* l, 1 .. TA_MD_ORDER_MAX_L each, no duplicates; read up to n_degrees */
   int32_t solid_degree;    /* one of the degrees */
 } ta_md_order_params;
+#define TA_MD_CLUSTER_MAX_SERIES 1048576
 typedef struct {
-  int32_t n_lags;       /* L, 1 .. TA_MD_MAX_LAGS; 0 switches sampling off (the default) */
+  double r_link;          /* link cutoff of every pair when r_link_pairs is NULL; NaN: the model's cutoff */
+  int32_t n_min;          /* 0 .. TA_MD_ORDER_MAX_CONN; 0: n_conn is not read */
+  int32_t species_mask;   /* bit a: element a can be selected; non-zero, no bit at or above n_elements */
+  int32_t n_bins;         /* B, 1 .. TA_MD_MAX_BINS; 0 switches the feature off (the default) */
+  int32_t n_series;       /* T, 1 .. TA_MD_CLUSTER_MAX_SERIES */
+  int32_t sample_every;   /* s >= 1 */
+} ta_md_cluster_params;
+typedef struct {
+  int32_t n_lags;      /* L, 1 .. TA_MD_MAX_LAGS; 0 switches sampling off (the default) */
   int32_t sample_every;  /* s >= 1 */
 } ta_md_sampling_params;
 #define TA_MD_SQ_MAX_Q 4096
@@ -724,6 +783,9 @@ int ta_md_set_order(ta_handle h, const ta_md_order_params *p, const double *r_bo
 int ta_md_get_order(ta_handle h, int64_t *hist_q, int64_t *hist_qbar, int64_t *hist_conn, int64_t *info,
                     double *r_bond_pairs);
 int ta_md_get_order_atoms(ta_handle h, double *q, double *qbar, int32_t *n_bonds, int32_t *n_conn, double *qlm);
+int ta_md_set_clusters(ta_handle h, const ta_md_cluster_params *p, const double *r_link_pairs);
+int ta_md_get_clusters(ta_handle h, int64_t *hist, int64_t *series, int64_t *steps, int64_t *info, double *r_link_pairs);
+int ta_md_get_cluster_atoms(ta_handle h, int32_t *label, int32_t *size);
 int ta_md_set_sq(ta_handle h, const ta_md_sq_params *p, const int32_t *miller);
 int ta_md_get_sq(ta_handle h, double *a_rho, double *a_l, double *a_j, int64_t *info, int32_t *miller);
 int ta_md_get_sq_amplitudes(ta_handle h, int32_t first_lag, int32_t n, double *rho, double *cur, int64_t *steps);

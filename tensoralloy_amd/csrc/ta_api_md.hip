@@ -1,7 +1,7 @@
 // C ABI of the device-resident MD loop: the ta_md_* entry points (include/tensoralloy_amd.h). The loop itself
 // is in ta_resident.hip; the integrator, correlation, pair-distribution, bond-angle and bond-order launches are in
-// ta_md.hip, ta_md_corr.hip, ta_md_rdf.hip, ta_md_adf.hip and ta_md_order.hip; the structure-factor launches in
-// ta_md_sq.hip.
+// ta_md.hip, ta_md_corr.hip, ta_md_rdf.hip, ta_md_adf.hip and ta_md_order.hip; the cluster launches in
+// ta_md_cluster.hip, the structure-factor launches in ta_md_sq.hip.
 #include <cmath>
 #include <cstring>
 
@@ -144,6 +144,38 @@ bool md_order_alloc(ta_context *h, const ta_md_order_params &p, const std::vecto
   return true;
 }
 
+// Zeroed histogram, series and give-up word, the squared cutoffs `rl`[E][E], the per-atom arrays and the link launch's
+// workgroup layout for the resident batch under setting `p`, with no sample taken. False when the device has no room
+// (everything is released then); throws otherwise.
+bool md_cluster_alloc(ta_context *h, const ta_md_cluster_params &p, const std::vector<double> &rl) {
+  static_assert(TA_MD_MAX_BINS <= ta::kMdClusterLdsWords, "the summary launch keeps all bins of a frame in LDS");
+  auto &g = h->md.cluster;
+  const size_t N = h->keep_species.size(), F = h->keep_natoms.size(), E = (size_t)h->n_elements;
+  const size_t n_hist = F * (size_t)p.n_bins, n_series = (size_t)p.n_series * F * 4;
+  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches add to the old buffers)
+  g.release();
+  const int chunk = ta::md_order_chunk((long long)N);
+  const std::vector<int32_t> start = frame_blocks(h, 1, chunk);
+  if (!g.acc.try_exact(n_hist) || !g.series.try_exact(n_series) || !g.blk.try_exact(F + 1) || !g.rl2.try_exact(E * E) ||
+      !g.per_atom.try_exact(4 * N + 1) || !g.giveup.try_exact(4)) {
+    g.release();
+    return false;
+  }
+  std::vector<double> rl2(E * E);
+  for (size_t k = 0; k < E * E; ++k) rl2[k] = rl[k] * rl[k];
+  HIP_CHECK(hipMemset(g.acc.ptr, 0, std::max<size_t>(n_hist, 1) * sizeof(unsigned long long)));
+  HIP_CHECK(hipMemset(g.series.ptr, 0, std::max<size_t>(n_series, 1) * sizeof(long long)));
+  HIP_CHECK(hipMemset(g.giveup.ptr, 0, 4 * sizeof(unsigned)));
+  HIP_CHECK(hipMemcpy(g.blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(g.rl2.ptr, rl2.data(), E * E * sizeof(double), hipMemcpyHostToDevice));
+  g.n_blk = (int)start[F];
+  g.chunk = chunk;
+  g.sched.every = p.sample_every;
+  g.sched.start(h->md.step);
+  g.sched.valid = true;
+  return true;
+}
+
 // The Miller triples on the device, an empty ring, zeroed accumulators, the partials, the snapshot rows and the
 // amplitude launch's workgroup layout for the resident batch under setting `p`, with no sample held. False when the
 // device has no room (everything is released then); throws otherwise.
@@ -200,13 +232,15 @@ int md_sq_ready(ta_context *h, const char *who) {
   return TA_OK;
 }
 
-// The bond cutoffs [E][E] of ta_md_set_adf and ta_md_set_order (`who`): r_bond for every pair, or r_bond_pairs.
-// Returns 0 with `rb` filled, or the error code: a cutoff not finite, <= 0 or above the model's, or no symmetry.
-int md_bond_cutoffs(ta_context *h, const std::string &who, double r_bond, const double *r_bond_pairs, std::vector<double> &rb) {
+// The bond cutoffs [E][E] of ta_md_set_adf, ta_md_set_order and ta_md_set_clusters (`who`): r_bond for every pair, or
+// r_bond_pairs; the messages call them `one` and `pairs`. Returns 0 with `rb` filled, or the error code: a cutoff
+// not finite, <= 0 or above the model's, or no symmetry.
+int md_bond_cutoffs(ta_context *h, const std::string &who, double r_bond, const double *r_bond_pairs, std::vector<double> &rb,
+                    const char *one = "r_bond", const char *pairs = "r_bond_pairs") {
   const size_t E = (size_t)h->n_elements;
   rb.assign(E * E, r_bond);
   if (r_bond_pairs) rb.assign(r_bond_pairs, r_bond_pairs + E * E);
-  const char *name = r_bond_pairs ? "r_bond_pairs" : "r_bond";
+  const char *name = r_bond_pairs ? pairs : one;
   for (size_t k = 0; k < E * E; ++k) {
     const std::string what = who + ": " + name +
                              (r_bond_pairs ? "[" + std::to_string(k / E) + "][" + std::to_string(k % E) + "]" : std::string());
@@ -218,7 +252,7 @@ int md_bond_cutoffs(ta_context *h, const std::string &who, double r_bond, const 
   for (size_t a = 0; a < E; ++a)
     for (size_t b = a + 1; b < E; ++b)
       if (rb[a * E + b] != rb[b * E + a])
-        return fail(h, TA_ERR_INVALID, who + ": r_bond_pairs is not symmetric: [" + std::to_string(a) + "][" +
+        return fail(h, TA_ERR_INVALID, who + ": " + pairs + " is not symmetric: [" + std::to_string(a) + "][" +
                                        std::to_string(b) + "] differs from [" + std::to_string(b) + "][" + std::to_string(a) + "]");
   return TA_OK;
 }
@@ -255,6 +289,17 @@ int md_order_ready(ta_context *h, const char *who) {
   return TA_OK;
 }
 
+// what the two getters of the clusters need; returns 0 or the error code
+int md_cluster_ready(ta_context *h, const char *who) {
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, std::string(who) + " called before ta_md_init");
+  if (!h->md.cluster.on) return fail(h, TA_ERR_INVALID, std::string(who) + ": the cluster analysis is off (ta_md_set_clusters)");
+  if (!h->md.cluster.sched.valid)
+    return fail(h, TA_ERR_INVALID, std::string(who) + ": a ta_md_run failed and left the data invalid; call "
+                                   "ta_md_set_clusters or ta_md_init again");
+  return TA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -269,7 +314,7 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
   if (velocities)
     for (size_t i = 0; i < 3 * N; ++i)
       if (!std::isfinite(velocities[i])) return fail(h, TA_ERR_INVALID, "ta_md_init: non-finite velocity");
-  bool ring_nomem = false, rdf_nomem = false, adf_nomem = false, order_nomem = false, sq_nomem = false;
+  bool ring_nomem = false, rdf_nomem = false, adf_nomem = false, order_nomem = false, cluster_nomem = false, sq_nomem = false;
   // (a batch the wave vectors are not defined for: the feature goes off, as when there is no room for it)
   const bool sq_unfit = h->md.sq.on && md_sq_frames(h) != TA_OK;
   const std::string sq_why = sq_unfit ? h->err : std::string();
@@ -317,6 +362,10 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
       md.order.on = false;
       order_nomem = true;
     }
+    if (md.cluster.on && !md_cluster_alloc(h, md.cluster.p, md.cluster.rl)) {  // likewise
+      md.cluster.on = false;
+      cluster_nomem = true;
+    }
     if (md.sq.on && sq_unfit) {
       md.sq.on = false;
       HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -336,6 +385,8 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
     return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the counts of ta_md_set_adf; the feature is off");
   if (rc == TA_OK && order_nomem)
     return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the buffers of ta_md_set_order; the feature is off");
+  if (rc == TA_OK && cluster_nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the buffers of ta_md_set_clusters; the feature is off");
   if (rc == TA_OK && sq_nomem)
     return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the buffers of ta_md_set_sq; the feature is off");
   if (rc == TA_OK && sq_unfit) return fail(h, TA_ERR_INVALID, "ta_md_init: " + sq_why + "; the feature is off");
@@ -750,6 +801,93 @@ int ta_md_get_order_atoms(ta_handle h, double *q, double *qbar, int32_t *n_bonds
   });
 }
 
+int ta_md_set_clusters(ta_handle h, const ta_md_cluster_params *p, const double *r_link_pairs) {
+  if (!h) return TA_ERR_INVALID;
+  auto &cluster = h->md.cluster;
+  if (!p || p->n_bins == 0) {
+    cluster.on = false;
+    return guarded(h, [&]() {
+      HIP_CHECK(hipStreamSynchronize(h->stream));
+      cluster.release();
+    });
+  }
+  if (p->n_bins < 0 || p->n_bins > TA_MD_MAX_BINS)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_clusters: n_bins must be 0 .. " + std::to_string(TA_MD_MAX_BINS));
+  if (p->n_series < 1 || p->n_series > TA_MD_CLUSTER_MAX_SERIES)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_clusters: n_series must be 1 .. " + std::to_string(TA_MD_CLUSTER_MAX_SERIES));
+  if (p->sample_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_set_clusters: sample_every must be >= 1");
+  if (p->n_min < 0 || p->n_min > TA_MD_ORDER_MAX_CONN)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_clusters: n_min must be 0 .. " + std::to_string(TA_MD_ORDER_MAX_CONN));
+  if (p->species_mask == 0) return fail(h, TA_ERR_INVALID, "ta_md_set_clusters: species_mask selects no element");
+  if (p->species_mask < 0 || (h->n_elements < 31 && (p->species_mask >> h->n_elements) != 0))
+    return fail(h, TA_ERR_INVALID, "ta_md_set_clusters: species_mask = " + std::to_string(p->species_mask) +
+                                   " has a bit at or above n_elements = " + std::to_string(h->n_elements));
+  std::vector<double> rl;
+  const double r_link = !r_link_pairs && std::isnan(p->r_link) ? h->rmax : p->r_link;  // NaN: the model's cutoff
+  if (const int bad = md_bond_cutoffs(h, "ta_md_set_clusters", r_link, r_link_pairs, rl, "r_link", "r_link_pairs")) return bad;
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_clusters: no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_set_clusters called before ta_md_init");
+  bool nomem = false;
+  const int rc = guarded(h, [&]() {
+    cluster.on = false;  // (until the buffers exist)
+    nomem = !md_cluster_alloc(h, *p, rl);
+    if (!nomem) {
+      cluster.p = *p;
+      cluster.p.r_link = r_link;
+      cluster.rl = rl;
+      cluster.on = true;
+    }
+  });
+  if (rc == TA_OK && nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_set_clusters: no device memory for buffers of n_bins = " + std::to_string(p->n_bins) +
+                                 " and n_series = " + std::to_string(p->n_series) + "; the feature is off");
+  return rc;
+}
+
+int ta_md_get_clusters(ta_handle h, int64_t *hist, int64_t *series, int64_t *steps, int64_t *info, double *r_link_pairs) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int bad = md_cluster_ready(h, "ta_md_get_clusters")) return bad;
+  const auto &cluster = h->md.cluster;
+  return guarded(h, [&]() {
+    const size_t E = (size_t)h->n_elements, F = h->keep_natoms.size(), n_hist = F * (size_t)cluster.p.n_bins;
+    const int64_t taken = cluster.sched.taken(), T = cluster.p.n_series, held = std::min(taken, T);
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    static_assert(sizeof(int64_t) == sizeof(unsigned long long) && sizeof(int64_t) == sizeof(long long),
+                  "the counts and the rows are copied as they are");
+    if (hist && n_hist) HIP_CHECK(hipMemcpy(hist, cluster.acc.ptr, n_hist * sizeof(int64_t), hipMemcpyDeviceToHost));
+    for (int64_t j = 0; j < held; ++j) {  // oldest first
+      const int64_t idx = taken - held + j;  // sample number
+      if (series && F)
+        HIP_CHECK(hipMemcpy(series + (size_t)j * F * 4, cluster.series.ptr + (size_t)(idx % T) * F * 4,
+                            F * 4 * sizeof(int64_t), hipMemcpyDeviceToHost));
+      if (steps) steps[j] = cluster.sched.step(idx);
+    }
+    if (info) {
+      info[0] = taken;
+      info[1] = cluster.p.n_bins;
+      info[2] = cluster.p.sample_every;
+      info[3] = cluster.sched.last;
+      info[4] = held;
+      info[5] = T;
+    }
+    if (r_link_pairs) std::memcpy(r_link_pairs, cluster.rl.data(), E * E * sizeof(double));
+  });
+}
+
+int ta_md_get_cluster_atoms(ta_handle h, int32_t *label, int32_t *size) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int bad = md_cluster_ready(h, "ta_md_get_cluster_atoms")) return bad;
+  const auto &cluster = h->md.cluster;
+  if (cluster.sched.last < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_cluster_atoms: no sample has been taken yet");
+  return guarded(h, [&]() {
+    const size_t N = h->keep_species.size();
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (!N) return;
+    if (label) HIP_CHECK(hipMemcpy(label, cluster.per_atom.ptr + 2 * N, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (size) HIP_CHECK(hipMemcpy(size, cluster.per_atom.ptr + 3 * N, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+  });
+}
+
 int ta_md_set_sq(ta_handle h, const ta_md_sq_params *p, const int32_t *miller) {
   if (!h) return TA_ERR_INVALID;
   auto &sq = h->md.sq;
@@ -955,6 +1093,22 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     return fail(h, TA_ERR_INVALID, "ta_md_run: the structure factors (ta_md_set_sq) and the barostat (ta_md_set_barostat) are "
                                    "both on; cell and positions of a snapshot would belong to different states: switch one of "
                                    "them off");
+  if (md.cluster.on && md.cluster.p.n_min > 0) {  // n_conn of the order launches for the same state is read
+    if (!md.order.on)
+      return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and reads n_conn, but "
+                                     "the bond-orientational order parameters (ta_md_set_order) are off");
+    if (!md.order.sched.valid)
+      return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and reads n_conn, but a "
+                                     "ta_md_run failed and left the data of ta_md_set_order invalid; call ta_md_set_order again");
+    if (md.cluster.p.sample_every % md.order.p.sample_every != 0)
+      return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and its sample_every = " +
+                                     std::to_string(md.cluster.p.sample_every) + " is no multiple of that of ta_md_set_order, " +
+                                     std::to_string(md.order.p.sample_every) + ": n_conn of a sampled state would be missing");
+    if (md.cluster.sched.origin < md.order.sched.origin)
+      return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and its first sample, step " +
+                                     std::to_string(md.cluster.sched.origin) + ", is in front of the first one of ta_md_set_order, "
+                                     "step " + std::to_string(md.order.sched.origin) + ": switch the order parameters on first");
+  }
   if (n_rebuilds) *n_rebuilds = 0;
   want |= TA_WANT_ENERGY | TA_WANT_FORCES;
   want &= ~(uint32_t)TA_WANT_REUSE_DESCRIPTORS;
@@ -963,7 +1117,7 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
   md.nhc.rec_valid = false;
   const bool corr_was_valid = md.corr.sched.suspend(), rdf_was_valid = md.rdf.sched.suspend();
   const bool adf_was_valid = md.adf.sched.suspend(), order_was_valid = md.order.sched.suspend();
-  const bool sq_was_valid = md.sq.sched.suspend();
+  const bool sq_was_valid = md.sq.sched.suspend(), cluster_was_valid = md.cluster.sched.suspend();
   res.cell_running = md.baro.running = baro;
   const int rc = guarded(h, [&]() {
     const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
@@ -1097,6 +1251,25 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     o.n_degrees = md.order.p.n_degrees, o.n_lm = md.order.n_lm, o.solid = md.order.solid;
     o.deg0 = md.order.p.degrees[0], o.deg1 = md.order.p.degrees[1], o.deg2 = md.order.p.degrees[2], o.deg3 = md.order.p.degrees[3];
     o.threshold = md.order.p.solid_threshold;
+    // Clusters: four launches in the same place, behind the order launches of the step (n_min > 0 reads their
+    // n_conn), under the same predicate (no volume either)
+    const bool cluster_run = md.cluster.on && cluster_was_valid && N > 0;
+    const ta::SampleSchedule &cluster_sched = md.cluster.sched;
+    ta::MdClusterLaunch cl;
+    cl.blk_start = md.cluster.blk.ptr;
+    cl.rl2 = md.cluster.rl2.ptr;
+    cl.n_conn = cluster_run && md.cluster.p.n_min > 0 ? md.order.per_atom_int.ptr + N : nullptr;
+    cl.parent = md.cluster.per_atom.ptr;
+    cl.count = cluster_run ? md.cluster.per_atom.ptr + N : nullptr;
+    cl.label = cluster_run ? md.cluster.per_atom.ptr + 2 * N : nullptr;
+    cl.size = cluster_run ? md.cluster.per_atom.ptr + 3 * N : nullptr;
+    cl.hist = md.cluster.acc.ptr;
+    cl.giveup = md.cluster.giveup.ptr;
+    cl.status = res.status.ptr;
+    cl.n_atoms = (long long)N;
+    cl.n_bins = md.cluster.p.n_bins, cl.n_elements = h->n_elements, cl.n_frames = (int)F;
+    cl.n_blk = md.cluster.n_blk, cl.chunk = md.cluster.chunk;
+    cl.n_min = md.cluster.p.n_min, cl.species_mask = md.cluster.p.species_mask;
     // Structure factors: the integrator launch of a due step writes the whole-step state (x, v) to the slot of the
     // correlation ring when md_set_sampling is due at the same launch, to two rows of this feature's otherwise;
     // the three launches go BEHIND it, under the same predicate, and read that snapshot.
@@ -1127,6 +1300,19 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
         o.pair_shift = h->pair_shift.ptr;
         o.seq = (unsigned)k;
         ta::launch_md_order(o, s);
+        HIP_CHECK(hipGetLastError());
+      }
+      if (cluster_run && cluster_sched.due(step0, k)) {
+        cl.pos = h->db.pos;
+        cl.cells = h->db.cells;
+        cl.species = h->db.species;
+        cl.atom_start = h->db.atom_start;
+        cl.pair_start = h->pair_start.ptr;  // the resident list
+        cl.pair_j = h->pair_j.ptr;
+        cl.pair_shift = h->pair_shift.ptr;
+        cl.seq = (unsigned)k;
+        cl.row = md.cluster.series.ptr + (size_t)(cluster_sched.index(step0 + k) % md.cluster.p.n_series) * F * 4;
+        ta::launch_md_cluster(cl, s);
         HIP_CHECK(hipGetLastError());
       }
       if (adf_run && adf_sched.due(step0, k)) {
@@ -1216,6 +1402,16 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     md.order.sched.valid = order_was_valid;
     if (sq_run) md.sq.sched.finish(md.step);
     md.sq.sched.valid = sq_was_valid;
+    if (cluster_run) {
+      unsigned gave_up = 0u;
+      HIP_CHECK(hipMemcpy(&gave_up, md.cluster.giveup.ptr, sizeof(unsigned), hipMemcpyDeviceToHost));
+      if (gave_up) {  // the data stay invalid
+        HIP_CHECK(hipMemset(md.cluster.giveup.ptr, 0, 4 * sizeof(unsigned)));
+        throw HipError("ta_md_run: a loop of the cluster link launch overran its cap; the cluster data are invalid");
+      }
+      md.cluster.sched.finish(md.step);
+    }
+    md.cluster.sched.valid = cluster_was_valid;
     if (n_rebuilds) *n_rebuilds = rebuilds;
     if (baro && F) {
       std::vector<double> rec(4 * n_rec * F);

@@ -241,6 +241,33 @@ struct MdState {
       sched.last = -1;
     }
   } order;
+  // Clusters of selected atoms (ta_md_set_clusters): the link cutoffs [E][E] of the setting and their squares on the
+  // device, the per-atom arrays (parent, count, label, size, [N] each, one buffer), the histogram [F][n_bins], the
+  // ring of series rows [n_series][F][4], the give-up word of the link launch and that launch's workgroup layout
+  struct Cluster {
+    bool on = false;
+    ta_md_cluster_params p = {0.0, 0, 0, 0, 1, 1};
+    std::vector<double> rl;
+    DevBuf<double> rl2;
+    DevBuf<int32_t> per_atom;
+    DevBuf<unsigned long long> acc;
+    DevBuf<long long> series;
+    DevBuf<unsigned> giveup;
+    DevBuf<int32_t> blk;
+    int n_blk = 0, chunk = 0;
+    SampleSchedule sched;
+    void release() {  // frees what the clusters hold on the device; the setting stays
+      rl2.release();
+      per_atom.release();
+      acc.release();
+      series.release();
+      giveup.release();
+      blk.release();
+      n_blk = 0;
+      sched.valid = false;
+      sched.last = -1;
+    }
+  } cluster;
   // Structure factors (ta_md_set_sq): the Miller triples [Q][3] of the setting and their device twin, the ring of
   // amplitude rows [L][F][E][planes][Q] (planes = 2, or 8 with currents), the accumulators (A_rho, then A_L and
   // A_J with currents, [F][E][E][L][Q] each, one buffer), the amplitude launch's partials and workgroup layout, and

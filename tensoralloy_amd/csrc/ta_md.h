@@ -173,7 +173,36 @@ struct MdOrderLaunch {
   double threshold;               // c of the solid-bond test
 };
 
-constexpr int kMdSqTile = 64;    // q-vectors per workgroup of the amplitude launch: one wave, a lane is a q-vector
+constexpr int kMdClusterLdsWords = 4096;  // 32-bit bins of the cluster summary's LDS histogram (16 KB): TA_MD_MAX_BINS, no tiling
+
+// Arguments of the four cluster launches (ta_md_cluster.hip) that ta_md_run puts in front of the integrator launch
+// of a sampled step, behind the order launches of that step and in stream order: select, link, flatten, summarise.
+// The link launch has the workgroup layout of the order launches (md_order_chunk); select and flatten take a thread
+// per atom, the summary a workgroup per frame.
+struct MdClusterLaunch {
+  const double *pos;              // [N][3] db.pos
+  const double *cells;            // [F][9]
+  const int32_t *species;         // [N]
+  const int32_t *atom_start;      // [F + 1]
+  const int32_t *blk_start;       // [F + 1] first workgroup of each frame (at least one each)
+  const int32_t *pair_start;      // [N + 1] the resident list: centre i owns pair_start[i] .. pair_start[i + 1] - 1
+  const int32_t *pair_j;          // [P]
+  const int32_t *pair_shift;      // [P][3]
+  const double *rl2;              // [E][E] squares of the link cutoffs
+  const int32_t *n_conn;          // [N] of the order launches for the same state; read when n_min > 0
+  int32_t *parent, *count;        // [N] the union-find forest (-1: not selected) and the atoms under every root
+  int32_t *label, *size;          // [N] of the newest sample
+  unsigned long long *hist;       // [F][n_bins] the accumulator
+  long long *row;                 // [F][4] this sample's row of the series
+  unsigned *giveup;               // set when a loop overran its cap
+  const unsigned *status;         // the integrator's status word and
+  unsigned seq;                   // sequence number: the same predicate
+  long long n_atoms;              // N
+  int n_bins, n_elements, n_frames, n_blk, chunk;
+  int n_min, species_mask;
+};
+
+constexpr int kMdSqTile = 64;   // q-vectors per workgroup of the amplitude launch: one wave, a lane is a q-vector
 constexpr int kMdSqSlab = 64;    // atoms a workgroup of the amplitude launch holds in LDS at a time
 constexpr int kMdSqMaxQ = 4096;  // TA_MD_SQ_MAX_Q
 
@@ -212,6 +241,8 @@ void launch_md_rdf(const MdRdfLaunch &a, hipStream_t s);
 void launch_md_adf(const MdAdfLaunch &a, hipStream_t s);
 
 void launch_md_order(const MdOrderLaunch &a, hipStream_t s);
+
+void launch_md_cluster(const MdClusterLaunch &a, hipStream_t s);
 
 void launch_md_sq(const MdSqLaunch &a, hipStream_t s);
 

@@ -44,6 +44,7 @@ class Engine:
         self._md_order_degrees = ()        # its degrees
         self._md_order_solid = (0, 0.0)    # and (solid_degree, threshold)
         self._md_sq = (0, 1, False)        # `md_set_sq` is on: (n_q, n_lags, currents)
+        self._md_cluster = (0, 1)          # `md_set_clusters` is on: (n_bins, n_series)
         self._n_elements = int(desc.n_elements)
         # what the neighbour list is complete for: max(rcut, acut), acut counting for angular models only
         self._md_cutoff = max(float(desc.rcut), float(desc.acut)) if int(desc.angular) else float(desc.rcut)
@@ -284,6 +285,8 @@ class Engine:
                 self._md_adf_bins = 0
             if b"ta_md_set_order" in msg:
                 self._md_order_bins = 0
+            if b"ta_md_set_clusters" in msg:
+                self._md_cluster = (0, 1)
             if b"ta_md_set_sampling" in msg:
                 self._md_lags = 0
             if b"ta_md_set_sq" in msg:
@@ -557,6 +560,97 @@ class Engine:
         self._check(self._lib.ta_md_get_order(self._handle, None, None, None, info, C.POINTER(C.c_double)()))
         return {"q": q, "qbar": qbar, "n_bonds": n_bonds, "n_conn": n_conn, "qlm": qlm[..., 0] + 1j * qlm[..., 1],
                 "step": int(info[3])}
+
+    def md_set_clusters(self, r_link=None, n_min=0, species=None, n_bins=0, n_series=1, sample_every=1):
+        """Clusters of solid or selected atoms inside `md_run` (`ta_md_set_clusters`): with `n_bins` = B (1 .. 4096)
+        the loop finds, at every step t (counted since `md_init`) with t % `sample_every` == 0, the connected
+        components of the selected atoms on the device. An atom is selected when its element is among `species`
+        (element symbols or indices; None: all) and, with `n_min` > 0, it has at least `n_min` solid bonds (the
+        n_conn of `md_set_order` for the same state: that feature must then be on, with a `sample_every` that
+        divides this one, and switched on first). Two selected atoms are linked when they are closer than `r_link`:
+        one distance, or a symmetric [n_elements, n_elements] matrix; None: the model's cutoff max(rcut, acut), the
+        largest value allowed. A cluster's size counts atoms, not images; its label is the smallest index of its
+        members in the batch. Every result is an integer and a function of the state alone. The loop counts the
+        clusters by size into a histogram of B bins per frame (the last one collects sizes >= B) and keeps the last
+        `n_series` rows {selected atoms, clusters, size of the largest, its label} per frame (`md_clusters`); label
+        and size of every atom of the newest sample stay on the device as well (`md_cluster_atoms`). `n_bins` = 0
+        switches it off (the default) and frees the buffers. Needs `md_init`; every call starts from zero, as
+        `md_init` does. The setting stays on across `set_frames`. Runs under the barostat and every thermostat.
+        `md_run(0, dt)` samples the resident state once."""
+        E = self._n_elements
+        pairs = C.POINTER(C.c_double)()
+        if r_link is None:
+            scalar = float("nan")   # (the library takes the model's cutoff)
+        elif np.ndim(r_link) == 0:
+            scalar = float(r_link)
+        else:
+            rl = np.ascontiguousarray(r_link, dtype=np.float64)
+            if rl.shape != (E, E):
+                raise ValueError(f"md_set_clusters: r_link must be one distance or [{E}, {E}] (n_elements of the model)")
+            pairs, scalar = _lib.as_dp(rl), float(rl.max())
+        if species is None:
+            mask = (1 << E) - 1
+        else:
+            mask, names = 0, list(self._clf.elements)
+            for sp in ([species] if isinstance(species, (str, int, np.integer)) else list(species)):
+                if isinstance(sp, str):
+                    if sp not in names:
+                        raise ValueError(f"md_set_clusters: {sp!r} is not an element of the model ({names})")
+                    sp = names.index(sp)
+                if not 0 <= int(sp) < E:
+                    raise ValueError(f"md_set_clusters: species index {sp} is outside 0 .. {E - 1}")
+                mask |= 1 << int(sp)
+        p = _lib.MdClusterParams(scalar, int(n_min), int(mask), int(n_bins), int(n_series), int(sample_every))
+        rc = self._lib.ta_md_set_clusters(self._handle, C.byref(p), pairs)
+        if rc == _lib.TA_ERR_NOMEM:   # (no room for the buffers: the library switched the feature off)
+            self._md_cluster = (0, 1)
+        self._check(rc)
+        self._md_cluster = (int(n_bins), int(n_series) if n_bins else 1)
+
+    @property
+    def md_cluster_bins(self):
+        """Bins of the cluster-size histogram `md_set_clusters` switched on, 0 while the feature is off."""
+        return self._md_cluster[0]
+
+    def md_clusters(self):
+        """What the loop has found since `md_set_clusters` (`ta_md_get_clusters`), a dict: `hist` int64 [n_frames,
+        n_bins], hist[f, k] = clusters of frame f with min(size, n_bins) - 1 == k, summed over the samples; `series`
+        int64 [rows, n_frames, 4]: {selected atoms, clusters, size of the largest cluster, its label (-1: nothing
+        selected)} of the newest `rows` = min(n_samples, n_series) samples, oldest first, and `steps` int64 [rows],
+        their absolute steps; `n_samples`, `n_bins`, `sample_every`, `last_step` (absolute step of the newest sample,
+        -1: none), `rows`, `n_series`; `r_link` [n_elements, n_elements]: the cutoffs in use.
+        `md.largest_cluster` and `md.cluster_size_distribution` read them."""
+        if self.info is None:
+            raise ValueError("md_clusters: no resident batch (call set_frames first)")
+        F, E = int(self.info.n_frames), self._n_elements
+        B, T = max(self._md_cluster[0], 1), max(self._md_cluster[1], 1)
+        ip = C.POINTER(C.c_int64)
+        info = (C.c_int64 * 6)()
+        self._check(self._lib.ta_md_get_clusters(self._handle, None, None, None, info, C.POINTER(C.c_double)()))
+        rows = int(info[4])
+        hist = np.zeros((F, B), dtype=np.int64)
+        series, steps = np.zeros((max(rows, 1), F, 4), dtype=np.int64), np.zeros(max(rows, 1), dtype=np.int64)
+        r_link = np.zeros((E, E))
+        self._check(self._lib.ta_md_get_clusters(self._handle, hist.ctypes.data_as(ip), series.ctypes.data_as(ip),
+                                                 steps.ctypes.data_as(ip), info, _lib.as_dp(r_link)))
+        return {"hist": hist, "series": series[:rows], "steps": steps[:rows], "n_samples": int(info[0]),
+                "n_bins": int(info[1]), "sample_every": int(info[2]), "last_step": int(info[3]), "rows": rows,
+                "n_series": int(info[5]), "r_link": r_link}
+
+    def md_cluster_atoms(self):
+        """Cluster of every atom in the newest sampled state (`ta_md_get_cluster_atoms`), a dict: `label` int32
+        [n_atoms], the smallest index of the atom's cluster in the batch, -1 for an atom that is not selected;
+        `size` int32 [n_atoms], the atoms of that cluster, 0 likewise; `step`: the absolute step of that state. Costs
+        a host sync and no list rebuild. Refused until the first sample has been taken."""
+        if self.info is None:
+            raise ValueError("md_cluster_atoms: no resident batch (call set_frames first)")
+        N = int(self.info.n_atoms)
+        label, size = np.zeros(N, dtype=np.int32), np.zeros(N, dtype=np.int32)
+        info = (C.c_int64 * 6)()
+        self._check(self._lib.ta_md_get_cluster_atoms(self._handle, label.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      size.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._check(self._lib.ta_md_get_clusters(self._handle, None, None, None, info, C.POINTER(C.c_double)()))
+        return {"label": label, "size": size, "step": int(info[3])}
 
     def md_set_sq(self, miller=None, n_lags=1, sample_every=1, currents=False):
         """Structure factors inside `md_run` (`ta_md_set_sq`): `miller` int [Q, 3] (1 .. 4096 triples, |n_c| <= 64;

@@ -66,6 +66,14 @@ which lattice". Histograms over the samples are exact integers; the per-atom val
 `order_distribution` normalises a histogram of q, `solid_fraction` and `classify_solid` apply the usual test
 n_conn >= n_min. Runs under the barostat and independently of the other observables.
 
+Clusters: with `cluster_bins` (and `cluster_rlink`, `cluster_nmin`, `cluster_species`, `cluster_series`,
+`cluster_every`) the loop finds, at every sampled step, the connected components of the selected atoms on the device
+(`Engine.md_set_clusters`; `DeviceMD.get_clusters`): the size of the largest crystalline nucleus as a function of
+time (`cluster_nmin` > 0, on top of `order_bins`) or the clusters of chosen elements in a solid solution
+(`cluster_species`). Every result is an exact integer and a function of the state alone. `largest_cluster` reads the
+time series, `cluster_size_distribution` the histogram, `clusters_from_labels` the per-atom labels. Runs under the
+barostat and every thermostat.
+
 Structure factors: with `sq_miller` (and `sq_lags`, `sq_every`, `sq_currents`) the loop sums, at every sampled step,
 the density amplitudes rho_a(q) = sum_i exp(i q . x_i) of every element over ALL atoms of a frame, at the wave
 vectors q = 2 pi h^-1 n of the integer triples given (`q_points` lists those below a |q|), keeps the last `sq_lags`
@@ -89,7 +97,7 @@ bar = 1.0e-4 * GPa
 
 __all__ = ["fs", "kB", "GPa", "bar", "maxwell_boltzmann", "DeviceMD", "vdos", "diffusion_coefficient",
            "green_kubo_diffusion", "rdf", "coordination_number", "adf", "order_distribution", "solid_fraction",
-           "classify_solid", "q_points", "intermediate_scattering", "structure_factor", "transverse_current",
+           "classify_solid", "largest_cluster", "cluster_size_distribution", "clusters_from_labels", "q_points", "intermediate_scattering", "structure_factor", "transverse_current",
            "dynamic_structure_factor", "shell_average"]
 
 
@@ -309,6 +317,45 @@ def classify_solid(n_conn, n_min):
     return np.asarray(n_conn) >= int(n_min)
 
 
+def largest_cluster(series, steps, dt):
+    """(t, size): the times `steps` dt [rows] and the size of the largest cluster [rows, n_frames] from the time
+    series of the device loop (`Engine.md_clusters`: `series` int [rows, n_frames, 4], `steps` [rows])."""
+    ser, st = np.asarray(series), np.asarray(steps)
+    if ser.ndim != 3 or ser.shape[-1] != 4 or st.shape != ser.shape[:1]:
+        raise ValueError("largest_cluster: series must be [rows, n_frames, 4] and steps [rows]")
+    return st.astype(np.float64) * float(dt), ser[:, :, 2].copy()
+
+
+def cluster_size_distribution(hist, n_samples=None):
+    """(sizes, mean): the sizes 1 .. B [B] and the mean number of clusters of each size per sample and frame [B]
+    from the counts `hist` [..., B] of the device loop (`Engine.md_clusters`; the last bin holds every size >= B),
+    summed over the leading axes (frames). `n_samples`: the samples the counts were summed over (default 1)."""
+    c = np.asarray(hist)
+    if c.ndim < 1 or c.shape[-1] < 1:
+        raise ValueError("cluster_size_distribution: hist must be [..., n_bins]")
+    n = 1 if n_samples is None else int(n_samples)
+    if n < 1:
+        raise ValueError("cluster_size_distribution: n_samples must be >= 1")
+    frames = int(np.prod(c.shape[:-1])) if c.ndim > 1 else 1
+    total = c.reshape(-1, c.shape[-1]).sum(axis=0).astype(np.float64)
+    return np.arange(1, c.shape[-1] + 1), total / float(n * max(frames, 1))
+
+
+def clusters_from_labels(label):
+    """(sizes, members): the cluster sizes, largest first (among equals the smaller label first), and for each the
+    sorted indices of its atoms, from the per-atom labels of the device loop (`Engine.md_cluster_atoms`; -1 marks an
+    atom that is not selected)."""
+    lab = np.asarray(label)
+    if lab.ndim != 1:
+        raise ValueError("clusters_from_labels: label must be [n_atoms]")
+    groups = {}
+    for i, l in enumerate(lab.tolist()):
+        if l >= 0:
+            groups.setdefault(l, []).append(i)
+    keys = sorted(groups, key=lambda l: (-len(groups[l]), l))
+    return np.array([len(groups[l]) for l in keys], dtype=np.int64), [np.array(groups[l], dtype=np.int64) for l in keys]
+
+
 def q_points(cell, q_max, max_index=64):
     """The integer triples n [Q, 3] (int32) of all wave vectors q = 2 pi h^-1 n of `cell` (h [3, 3], rows are lattice
     vectors) with 0 < |q| <= `q_max` (1 / A), one of each pair +-n (the first non-zero index is positive), ordered by
@@ -462,6 +509,15 @@ class DeviceMD:
                            under the barostat too. Without `order_bins` no method of the order parameters is
                            called on the engine, unless its `md_order_bins` says that an earlier `DeviceMD` left
                            them on: they are then switched off
+    cluster_bins, cluster_rlink, cluster_nmin, cluster_species, cluster_series, cluster_every : `cluster_bins` given
+                           (1 .. 4096): the loop finds the clusters of the atoms of `cluster_species` (symbols or
+                           indices; default: all) with at least `cluster_nmin` solid bonds (default 0: no test;
+                           > 0 needs `order_bins` and a `cluster_every` that is a multiple of `order_every`), linked
+                           below `cluster_rlink` (as `adf_rbond`), of every `cluster_every`-th step on the device,
+                           and keeps the last `cluster_series` rows (default 1) of the time series
+                           (`get_clusters`); runs under the barostat too. Without `cluster_bins` no method of the
+                           clusters is called on the engine, unless its `md_cluster_bins` says that an earlier
+                           `DeviceMD` left them on: they are then switched off
     sq_miller, sq_lags, sq_every, sq_currents : `sq_miller` given (int [Q, 3], 1 .. 4096 triples with |n_c| <= 64,
                            e.g. from `q_points`): the loop sums the density amplitudes at the wave vectors
                            q = 2 pi h^-1 n of every `sq_every`-th step over all atoms (the state at construction is
@@ -483,7 +539,8 @@ class DeviceMD:
                  compressibility=None, mask=None, tdamp=None, tchain=3, tloop=1, dof_removed=0, n_lags=None,
                  sample_every=1, rdf_bins=None, rdf_rmax=None, rdf_every=1, adf_bins=None, adf_rbond=None,
                  adf_every=1, order_degrees=None, order_rbond=None, order_bins=None, order_every=1, order_solid=None,
-                 sq_miller=None, sq_lags=None, sq_every=1, sq_currents=False):
+                 sq_miller=None, sq_lags=None, sq_every=1, sq_currents=False, cluster_bins=None, cluster_rlink=None,
+                 cluster_nmin=0, cluster_species=None, cluster_series=1, cluster_every=1):
         if not (np.isfinite(timestep) and timestep > 0.0):
             raise ValueError("DeviceMD: timestep must be a finite time > 0")
         barostat = (pressure, taup, compressibility)
@@ -550,6 +607,36 @@ class DeviceMD:
         elif order_every != 1 or order_rbond is not None or order_degrees is not None or order_solid is not None:
             raise ValueError("DeviceMD: order_degrees, order_rbond, order_every and order_solid belong to the "
                              "bond-orientational order (order_bins)")
+        if cluster_bins is not None:
+            whole = lambda a: isinstance(a, (int, np.integer)) and not isinstance(a, bool)
+            if not (whole(cluster_bins) and 1 <= cluster_bins <= 4096):
+                raise ValueError("DeviceMD: cluster_bins must be an integer 1 .. 4096")
+            if not (whole(cluster_every) and cluster_every >= 1):
+                raise ValueError("DeviceMD: cluster_every must be an integer >= 1")
+            if not (whole(cluster_series) and 1 <= cluster_series <= 1048576):
+                raise ValueError("DeviceMD: cluster_series must be an integer 1 .. 1048576")
+            if not (whole(cluster_nmin) and 0 <= cluster_nmin <= 31):
+                raise ValueError("DeviceMD: cluster_nmin must be an integer 0 .. 31")
+            if cluster_nmin > 0 and order_bins is None:
+                raise ValueError("DeviceMD: cluster_nmin > 0 reads the solid bonds of the bond-orientational order "
+                                 "(order_bins)")
+            if cluster_nmin > 0 and cluster_every % order_every != 0:
+                raise ValueError("DeviceMD: with cluster_nmin > 0, cluster_every must be a multiple of order_every")
+            if cluster_species is not None:
+                sp = [cluster_species] if isinstance(cluster_species, (str, int, np.integer)) else list(cluster_species)
+                if not sp or not all(isinstance(e, str) or (whole(e) and e >= 0) for e in sp):
+                    raise ValueError("DeviceMD: cluster_species must be element symbols or indices >= 0, at least one")
+            if cluster_rlink is not None:
+                rb = np.asarray(cluster_rlink, dtype=np.float64)
+                if rb.ndim not in (0, 2) or rb.size == 0 or not (np.all(np.isfinite(rb)) and np.all(rb > 0.0)):
+                    raise ValueError("DeviceMD: cluster_rlink must be a finite distance > 0, or a square matrix of them")
+                if rb.ndim == 2 and (rb.shape[0] != rb.shape[1] or not np.array_equal(rb, rb.T)):
+                    raise ValueError("DeviceMD: cluster_rlink must be a finite distance > 0, or a square matrix of them, "
+                                     "symmetric")
+        elif (cluster_every != 1 or cluster_rlink is not None or cluster_nmin != 0 or cluster_species is not None
+              or cluster_series != 1):
+            raise ValueError("DeviceMD: cluster_rlink, cluster_nmin, cluster_species, cluster_series and cluster_every "
+                             "belong to the cluster analysis (cluster_bins)")
         if sq_miller is not None:
             whole = lambda a: isinstance(a, (int, np.integer)) and not isinstance(a, bool)
             miller = np.asarray(sq_miller)
@@ -682,6 +769,12 @@ class DeviceMD:
             engine.md_set_order(degrees, order_rbond, self._order_bins, int(order_every), solid)
         elif getattr(engine, "md_order_bins", 0):
             engine.md_set_order(n_bins=0)
+        self._cluster_bins = int(cluster_bins) if cluster_bins is not None else 0
+        if self._cluster_bins:   # (opt-in in the same way; behind the order parameters it may read)
+            engine.md_set_clusters(cluster_rlink, int(cluster_nmin), cluster_species, self._cluster_bins,
+                                   int(cluster_series), int(cluster_every))
+        elif getattr(engine, "md_cluster_bins", 0):
+            engine.md_set_clusters(n_bins=0)
         self._sq = sq_miller is not None
         self._sq_every, self._sq_currents = int(sq_every), bool(sq_currents)
         if self._sq:   # (opt-in in the same way)
@@ -816,6 +909,17 @@ class DeviceMD:
         q, p = order_distribution(out["hist_q"])
         pbar = order_distribution(out["hist_qbar"])[1]
         return q, (p[0] if self._single else p), (pbar[0] if self._single else pbar)
+
+    def get_clusters(self):
+        """The clusters the loop has found: the dict of `Engine.md_clusters` (`hist`, `series`, `steps`, ...) with
+        `label`, `size` and `step` of `Engine.md_cluster_atoms` for the newest sampled state, the atoms of a batch in
+        the order of the frames. `largest_cluster(series, steps, dt)` gives the nucleus size against time. Needs
+        `cluster_bins`."""
+        if not self._cluster_bins:
+            raise ValueError("DeviceMD.get_clusters: the cluster analysis is off (cluster_bins)")
+        out = self.engine.md_clusters()
+        out.update(self.engine.md_cluster_atoms())
+        return out
 
     def get_order_atoms(self):
         """The order parameters of every atom in the newest sampled state: the dict of `Engine.md_order_atoms`
