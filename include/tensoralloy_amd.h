@@ -650,6 +650,53 @@ int ta_step_view(ta_handle h, const double *positions, const double *cells, uint
  *   ta_md_get_cluster_atoms  label and size of the newest sample (above); TA_ERR_INVALID while no sample has been
  *                        taken. Any pointer may be NULL.
  *
+ * Common neighbour analysis inside the loop (opt-in; with it never switched on nothing changes): the lattice type
+ * of every atom, OVITO's numbering 0 OTHER, 1 FCC, 2 HCP, 3 BCC, 4 ICO, by the conventional analysis of
+ * Honeycutt-Andersen / Faken-Jonsson at a fixed cutoff (LAMMPS `compute cna/atom`) or adaptively (Stukowski 2012,
+ * OVITO's default). Parameters: mode, r_cut, r_max, n_series = T, sample_every = s. The schedule is that of
+ * ta_md_set_adf, kept separately. At a sampled whole-step state
+ *     the CANDIDATES of centre i are the entries (j, S) of the resident list with d = x_j - x_i + S . h (fp64,
+ *         unwrapped positions and cells as the device holds them), d . d < r^2, r = r_max (adaptive) or r_cut (fixed).
+ *         Species do not enter; self-images and several images of one atom are neighbours like any other. They are
+ *         ordered by the key (d . d, j, S0, S1, S2), so the selection does not depend on the order of the list;
+ *     for N neighbour vectors and a cutoff rc, neighbours j, k are BONDED when |d_j - d_k| < rc; the SIGNATURE of
+ *         neighbour j is (n_cn, n_b, l_cb): the neighbours bonded to j, the bonds among those, the most bonds in
+ *         one connected set of those bonds. FCC: N = 12, twelve (4,2,1). HCP: N = 12, six (4,2,1) and six (4,2,2).
+ *         ICO: N = 12, twelve (5,5,5). BCC: N = 14, eight (6,6,6) and six (4,4,4). Anything else is OTHER;
+ *     ADAPTIVE: fewer than 12 candidates: OTHER, r_local = 0. Else the 12 nearest with rc = (1 + sqrt 2) / 2 mean |d|
+ *         test FCC, HCP, ICO; if none matches and there are at least 14 candidates, the 14 nearest with
+ *         rc = (1 + sqrt 2) / 2 ((2 / sqrt 3) sum of the 8 nearest |d| + sum of the next 6) / 14 test BCC.
+ *         r_local is the rc of the last attempt made;
+ *     FIXED: all N candidates, rc = r_cut = r_local; N = 12 tests FCC, HCP, ICO, N = 14 tests BCC, any other N is OTHER.
+ * Every output but r_local is an integer and a function of the state alone: exact, whatever the skin, the pattern of
+ * list rebuilds or the way a run is cut into calls; r_local is a sum in the order of the sorted selection and
+ * reproduces itself bit for bit. A launch that zeroes the sample's row and the analysis go in front of the integrator
+ * launch of a sampled step, behind the order and cluster launches of that step: no host wait, no grid barrier, no
+ * floating-point atomics. Kept per atom for the NEWEST sample only: structure [n_atoms] and r_local [n_atoms].
+ * Accumulated over the samples as unsigned 64-bit integer counts:
+ *     counts[f][a][type] += atoms of species a of frame f with that type
+ * A time series on the device: sample n writes the row series[n % T][f][5], the atoms of every type summed over the
+ * species, and its absolute step into steps[n % T]; the newest T rows are kept. No volume enters: the feature runs
+ * under the barostat, with the cells of the sampled state, under every thermostat, and independently of the other
+ * observables. ta_md_run with n_steps = 0 analyses the resident state once.
+ *   ta_md_set_cna        NULL or n_series == 0 switches it off (the default; always allowed) and frees the buffers.
+ *                        Switching on needs a resident batch and ta_md_init; it allocates and zeroes the counts, the
+ *                        series and the sample counter (so does every further call). The life cycle is that of
+ *                        ta_md_set_adf: ta_set_frames keeps the setting and drops the data with the MD state;
+ *                        ta_md_init starts from zero. TA_ERR_INVALID, with the argument named by ta_last_error and
+ *                        the setting left as it was: mode neither TA_MD_CNA_ADAPTIVE nor TA_MD_CNA_FIXED; n_series
+ *                        outside 0 .. TA_MD_CLUSTER_MAX_SERIES; sample_every < 1; r_cut (fixed mode) or r_max
+ *                        (adaptive mode) not finite (but for r_max = NaN: the model's cutoff), <= 0, or greater than
+ *                        max(rcut, acut) of the model. TA_ERR_NOMEM when the device allocation fails; the feature is
+ *                        then off.
+ *   ta_md_run            A run that fails leaves the data invalid: both getters are TA_ERR_INVALID until
+ *                        ta_md_set_cna or ta_md_init is called again.
+ *   ta_md_get_cna        counts [n_frames][n_elements][5]; series [rows held][n_frames][5] and steps [rows held],
+ *                        oldest first; info [6] = {n_samples, mode, sample_every, absolute step of the newest sample
+ *                        or -1, rows held = min(n_samples, T), T}. Any pointer may be NULL.
+ *   ta_md_get_cna_atoms  structure and r_local of the newest sample (above); TA_ERR_INVALID while no sample has been
+ *                        taken. Any pointer may be NULL.
+ *
  * Structure factors inside the loop (opt-in; with it never switched on nothing changes): the static structure
  * factor S(q), the intermediate scattering function F(q, t) and the longitudinal and transverse current
  * correlations, by a direct sum over the atoms, so that nothing stops at the model's cutoff. The caller gives
@@ -731,6 +778,16 @@ typedef struct {
   int32_t n_series;       /* T, 1 .. TA_MD_CLUSTER_MAX_SERIES */
   int32_t sample_every;   /* s >= 1 */
 } ta_md_cluster_params;
+#define TA_MD_CNA_ADAPTIVE 0
+#define TA_MD_CNA_FIXED 1
+#define TA_MD_CNA_TYPES 5
+typedef struct {
+  double r_cut;          /* fixed mode: finite, > 0, <= max(rcut, acut); ignored in adaptive mode */
+  double r_max;          /* adaptive mode: candidate reach, finite, > 0, <= max(rcut, acut); NaN: the model's cutoff */
+  int32_t mode;          /* TA_MD_CNA_ADAPTIVE or TA_MD_CNA_FIXED */
+  int32_t n_series;      /* T, 1 .. TA_MD_CLUSTER_MAX_SERIES; 0 switches the feature off (the default) */
+  int32_t sample_every;  /* s >= 1 */
+} ta_md_cna_params;
 typedef struct {
   int32_t n_lags;      /* L, 1 .. TA_MD_MAX_LAGS; 0 switches sampling off (the default) */
   int32_t sample_every;  /* s >= 1 */
@@ -786,6 +843,9 @@ int ta_md_get_order_atoms(ta_handle h, double *q, double *qbar, int32_t *n_bonds
 int ta_md_set_clusters(ta_handle h, const ta_md_cluster_params *p, const double *r_link_pairs);
 int ta_md_get_clusters(ta_handle h, int64_t *hist, int64_t *series, int64_t *steps, int64_t *info, double *r_link_pairs);
 int ta_md_get_cluster_atoms(ta_handle h, int32_t *label, int32_t *size);
+int ta_md_set_cna(ta_handle h, const ta_md_cna_params *p);
+int ta_md_get_cna(ta_handle h, int64_t *counts, int64_t *series, int64_t *steps, int64_t *info);
+int ta_md_get_cna_atoms(ta_handle h, int32_t *structure, double *r_local);
 int ta_md_set_sq(ta_handle h, const ta_md_sq_params *p, const int32_t *miller);
 int ta_md_get_sq(ta_handle h, double *a_rho, double *a_l, double *a_j, int64_t *info, int32_t *miller);
 int ta_md_get_sq_amplitudes(ta_handle h, int32_t first_lag, int32_t n, double *rho, double *cur, int64_t *steps);

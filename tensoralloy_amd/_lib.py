@@ -21,7 +21,7 @@ LIB_PATH = PKG_DIR / "libtensoralloy_amd.so"
 
 SOURCES = ["ta_api.hip", "ta_api_md.hip", "ta_api_relax.hip", "ta_resident.hip", "ta_kernels.hip", "ta_kernels_v2.hip", "ta_mlp.hip", "ta_eam.hip",
            "ta_nlist.hip", "ta_grap.hip", "ta_train.hip", "ta_hvp.hip", "ta_neighbor.cpp", "ta_td.hip",
-           "ta_td_train.hip", "ta_md.hip", "ta_md_corr.hip", "ta_md_rdf.hip", "ta_md_adf.hip", "ta_md_order.hip", "ta_md_cluster.hip", "ta_md_sq.hip", "ta_relax.hip", "ta_neb.hip",
+           "ta_td_train.hip", "ta_md.hip", "ta_md_corr.hip", "ta_md_rdf.hip", "ta_md_adf.hip", "ta_md_order.hip", "ta_md_cluster.hip", "ta_md_cna.hip", "ta_md_sq.hip", "ta_relax.hip", "ta_neb.hip",
            "ta_options.cpp"]
 OBJ_DIR = CSRC_DIR / "build"
 
@@ -67,6 +67,7 @@ EXPORTED_SYMBOLS = [
     "ta_md_set_adf", "ta_md_get_adf",
     "ta_md_set_order", "ta_md_get_order", "ta_md_get_order_atoms",
     "ta_md_set_clusters", "ta_md_get_clusters", "ta_md_get_cluster_atoms",
+    "ta_md_set_cna", "ta_md_get_cna", "ta_md_get_cna_atoms",
     "ta_md_set_sq", "ta_md_get_sq", "ta_md_get_sq_amplitudes",
     "ta_relax_init", "ta_relax_run", "ta_relax_get_state",
     "ta_relax_set_cell", "ta_relax_get_cell",
@@ -160,6 +161,14 @@ TA_MD_CLUSTER_MAX_SERIES = 1048576  # include/tensoralloy_amd.h
 class MdClusterParams(C.Structure):
     _fields_ = [("r_link", C.c_double), ("n_min", C.c_int32), ("species_mask", C.c_int32), ("n_bins", C.c_int32),
                 ("n_series", C.c_int32), ("sample_every", C.c_int32)]
+
+
+TA_MD_CNA_ADAPTIVE, TA_MD_CNA_FIXED, TA_MD_CNA_TYPES = 0, 1, 5  # include/tensoralloy_amd.h
+
+
+class MdCnaParams(C.Structure):
+    _fields_ = [("r_cut", C.c_double), ("r_max", C.c_double), ("mode", C.c_int32), ("n_series", C.c_int32),
+                ("sample_every", C.c_int32)]
 
 
 TA_MD_SQ_MAX_Q, TA_MD_SQ_MAX_INDEX = 4096, 64  # include/tensoralloy_amd.h
@@ -363,6 +372,10 @@ def load():
     lib.ta_md_get_clusters.argtypes = [H, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                        C.POINTER(C.c_int64), _dp]
     lib.ta_md_get_cluster_atoms.argtypes = [H, _ip, _ip]
+    lib.ta_md_set_cna.argtypes = [H, C.POINTER(MdCnaParams)]
+    lib.ta_md_get_cna.argtypes = [H, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                  C.POINTER(C.c_int64)]
+    lib.ta_md_get_cna_atoms.argtypes = [H, _ip, _dp]
     lib.ta_md_set_sq.argtypes = [H, C.POINTER(MdSqParams), _ip]
     lib.ta_md_get_sq.argtypes = [H, _dp, _dp, _dp, C.POINTER(C.c_int64), _ip]
     lib.ta_md_get_sq_amplitudes.argtypes = [H, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int64)]

@@ -1,7 +1,7 @@
 // C ABI of the device-resident MD loop: the ta_md_* entry points (include/tensoralloy_amd.h). The loop itself
 // is in ta_resident.hip; the integrator, correlation, pair-distribution, bond-angle and bond-order launches are in
 // ta_md.hip, ta_md_corr.hip, ta_md_rdf.hip, ta_md_adf.hip and ta_md_order.hip; the cluster launches in
-// ta_md_cluster.hip, the structure-factor launches in ta_md_sq.hip.
+// ta_md_cluster.hip, the common neighbour analysis in ta_md_cna.hip, the structure-factor launches in ta_md_sq.hip.
 #include <cmath>
 #include <cstring>
 
@@ -176,6 +176,34 @@ bool md_cluster_alloc(ta_context *h, const ta_md_cluster_params &p, const std::v
   return true;
 }
 
+// Zeroed counts and series, the per-atom arrays and the launch's workgroup layout for the resident batch under setting
+// `p`, with no sample taken. False when the device has no room (everything is released then); throws otherwise.
+bool md_cna_alloc(ta_context *h, const ta_md_cna_params &p) {
+  static_assert(TA_MD_CNA_TYPES == ta::kMdCnaTypes && TA_MD_CNA_ADAPTIVE == ta::kMdCnaAdaptive &&
+                    TA_MD_CNA_FIXED == ta::kMdCnaFixed, "the header and the launch agree");
+  auto &g = h->md.cna;
+  const size_t N = h->keep_species.size(), F = h->keep_natoms.size(), E = (size_t)h->n_elements;
+  const size_t n_acc = F * E * TA_MD_CNA_TYPES, n_series = (size_t)p.n_series * F * TA_MD_CNA_TYPES;
+  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches add to the old buffers)
+  g.release();
+  const int chunk = ta::md_order_chunk((long long)N);
+  const std::vector<int32_t> start = frame_blocks(h, 1, chunk);
+  if (!g.acc.try_exact(n_acc) || !g.series.try_exact(n_series) || !g.blk.try_exact(F + 1) || !g.structure.try_exact(N + 1) ||
+      !g.r_local.try_exact(N + 1)) {
+    g.release();
+    return false;
+  }
+  HIP_CHECK(hipMemset(g.acc.ptr, 0, std::max<size_t>(n_acc, 1) * sizeof(unsigned long long)));
+  HIP_CHECK(hipMemset(g.series.ptr, 0, std::max<size_t>(n_series, 1) * sizeof(unsigned long long)));
+  HIP_CHECK(hipMemcpy(g.blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+  g.n_blk = (int)start[F];
+  g.chunk = chunk;
+  g.sched.every = p.sample_every;
+  g.sched.start(h->md.step);
+  g.sched.valid = true;
+  return true;
+}
+
 // The Miller triples on the device, an empty ring, zeroed accumulators, the partials, the snapshot rows and the
 // amplitude launch's workgroup layout for the resident batch under setting `p`, with no sample held. False when the
 // device has no room (everything is released then); throws otherwise.
@@ -300,6 +328,17 @@ int md_cluster_ready(ta_context *h, const char *who) {
   return TA_OK;
 }
 
+// what the two getters of the common neighbour analysis need; returns 0 or the error code
+int md_cna_ready(ta_context *h, const char *who) {
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, std::string(who) + " called before ta_md_init");
+  if (!h->md.cna.on) return fail(h, TA_ERR_INVALID, std::string(who) + ": the common neighbour analysis is off (ta_md_set_cna)");
+  if (!h->md.cna.sched.valid)
+    return fail(h, TA_ERR_INVALID, std::string(who) + ": a ta_md_run failed and left the data invalid; call "
+                                   "ta_md_set_cna or ta_md_init again");
+  return TA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -314,7 +353,7 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
   if (velocities)
     for (size_t i = 0; i < 3 * N; ++i)
       if (!std::isfinite(velocities[i])) return fail(h, TA_ERR_INVALID, "ta_md_init: non-finite velocity");
-  bool ring_nomem = false, rdf_nomem = false, adf_nomem = false, order_nomem = false, cluster_nomem = false, sq_nomem = false;
+  bool ring_nomem = false, rdf_nomem = false, adf_nomem = false, order_nomem = false, cluster_nomem = false, cna_nomem = false, sq_nomem = false;
   // (a batch the wave vectors are not defined for: the feature goes off, as when there is no room for it)
   const bool sq_unfit = h->md.sq.on && md_sq_frames(h) != TA_OK;
   const std::string sq_why = sq_unfit ? h->err : std::string();
@@ -366,6 +405,10 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
       md.cluster.on = false;
       cluster_nomem = true;
     }
+    if (md.cna.on && !md_cna_alloc(h, md.cna.p)) {  // likewise
+      md.cna.on = false;
+      cna_nomem = true;
+    }
     if (md.sq.on && sq_unfit) {
       md.sq.on = false;
       HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -387,6 +430,8 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
     return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the buffers of ta_md_set_order; the feature is off");
   if (rc == TA_OK && cluster_nomem)
     return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the buffers of ta_md_set_clusters; the feature is off");
+  if (rc == TA_OK && cna_nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the buffers of ta_md_set_cna; the feature is off");
   if (rc == TA_OK && sq_nomem)
     return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the buffers of ta_md_set_sq; the feature is off");
   if (rc == TA_OK && sq_unfit) return fail(h, TA_ERR_INVALID, "ta_md_init: " + sq_why + "; the feature is off");
@@ -888,6 +933,92 @@ int ta_md_get_cluster_atoms(ta_handle h, int32_t *label, int32_t *size) {
   });
 }
 
+int ta_md_set_cna(ta_handle h, const ta_md_cna_params *p) {
+  if (!h) return TA_ERR_INVALID;
+  auto &cna = h->md.cna;
+  if (!p || p->n_series == 0) {
+    cna.on = false;
+    return guarded(h, [&]() {
+      HIP_CHECK(hipStreamSynchronize(h->stream));
+      cna.release();
+    });
+  }
+  if (p->mode != TA_MD_CNA_ADAPTIVE && p->mode != TA_MD_CNA_FIXED)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_cna: mode = " + std::to_string(p->mode) + " must be TA_MD_CNA_ADAPTIVE (0) or "
+                                   "TA_MD_CNA_FIXED (1)");
+  if (p->n_series < 0 || p->n_series > TA_MD_CLUSTER_MAX_SERIES)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_cna: n_series must be 0 .. " + std::to_string(TA_MD_CLUSTER_MAX_SERIES));
+  if (p->sample_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_set_cna: sample_every must be >= 1");
+  const bool fixed = p->mode == TA_MD_CNA_FIXED;
+  const char *name = fixed ? "r_cut" : "r_max";
+  const double r = fixed ? p->r_cut : std::isnan(p->r_max) ? h->rmax : p->r_max;  // r_max = NaN: the model's cutoff
+  if (!std::isfinite(r) || !(r > 0.0))
+    return fail(h, TA_ERR_INVALID, std::string("ta_md_set_cna: ") + name + " must be a finite distance > 0");
+  if (r > h->rmax)
+    return fail(h, TA_ERR_INVALID, std::string("ta_md_set_cna: ") + name + " = " + std::to_string(r) +
+                                   " exceeds the model's cutoff max(rcut, acut) = " + std::to_string(h->rmax) +
+                                   "; the neighbour list is not complete beyond that");
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_cna: no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_set_cna called before ta_md_init");
+  bool nomem = false;
+  const int rc = guarded(h, [&]() {
+    cna.on = false;  // (until the buffers exist)
+    nomem = !md_cna_alloc(h, *p);
+    if (!nomem) {
+      cna.p = *p;
+      if (fixed) cna.p.r_max = 0.0; else cna.p.r_max = r, cna.p.r_cut = 0.0;
+      cna.on = true;
+    }
+  });
+  if (rc == TA_OK && nomem)
+    return fail(h, TA_ERR_NOMEM, "ta_md_set_cna: no device memory for buffers of n_series = " + std::to_string(p->n_series) +
+                                 "; the feature is off");
+  return rc;
+}
+
+int ta_md_get_cna(ta_handle h, int64_t *counts, int64_t *series, int64_t *steps, int64_t *info) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int bad = md_cna_ready(h, "ta_md_get_cna")) return bad;
+  const auto &cna = h->md.cna;
+  return guarded(h, [&]() {
+    const size_t E = (size_t)h->n_elements, F = h->keep_natoms.size(), n_acc = F * E * TA_MD_CNA_TYPES;
+    const size_t row = F * TA_MD_CNA_TYPES;
+    const int64_t taken = cna.sched.taken(), T = cna.p.n_series, held = std::min(taken, T);
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the counts and the rows are copied as they are");
+    if (counts && n_acc) HIP_CHECK(hipMemcpy(counts, cna.acc.ptr, n_acc * sizeof(int64_t), hipMemcpyDeviceToHost));
+    for (int64_t j = 0; j < held; ++j) {  // oldest first
+      const int64_t idx = taken - held + j;  // sample number
+      if (series && row)
+        HIP_CHECK(hipMemcpy(series + (size_t)j * row, cna.series.ptr + (size_t)(idx % T) * row, row * sizeof(int64_t),
+                            hipMemcpyDeviceToHost));
+      if (steps) steps[j] = cna.sched.step(idx);
+    }
+    if (info) {
+      info[0] = taken;
+      info[1] = cna.p.mode;
+      info[2] = cna.p.sample_every;
+      info[3] = cna.sched.last;
+      info[4] = held;
+      info[5] = T;
+    }
+  });
+}
+
+int ta_md_get_cna_atoms(ta_handle h, int32_t *structure, double *r_local) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int bad = md_cna_ready(h, "ta_md_get_cna_atoms")) return bad;
+  const auto &cna = h->md.cna;
+  if (cna.sched.last < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_cna_atoms: no sample has been taken yet");
+  return guarded(h, [&]() {
+    const size_t N = h->keep_species.size();
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (!N) return;
+    if (structure) HIP_CHECK(hipMemcpy(structure, cna.structure.ptr, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (r_local) HIP_CHECK(hipMemcpy(r_local, cna.r_local.ptr, N * sizeof(double), hipMemcpyDeviceToHost));
+  });
+}
+
 int ta_md_set_sq(ta_handle h, const ta_md_sq_params *p, const int32_t *miller) {
   if (!h) return TA_ERR_INVALID;
   auto &sq = h->md.sq;
@@ -1118,6 +1249,7 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
   const bool corr_was_valid = md.corr.sched.suspend(), rdf_was_valid = md.rdf.sched.suspend();
   const bool adf_was_valid = md.adf.sched.suspend(), order_was_valid = md.order.sched.suspend();
   const bool sq_was_valid = md.sq.sched.suspend(), cluster_was_valid = md.cluster.sched.suspend();
+  const bool cna_was_valid = md.cna.sched.suspend();
   res.cell_running = md.baro.running = baro;
   const int rc = guarded(h, [&]() {
     const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
@@ -1270,6 +1402,24 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     cl.n_bins = md.cluster.p.n_bins, cl.n_elements = h->n_elements, cl.n_frames = (int)F;
     cl.n_blk = md.cluster.n_blk, cl.chunk = md.cluster.chunk;
     cl.n_min = md.cluster.p.n_min, cl.species_mask = md.cluster.p.species_mask;
+    // Common neighbour analysis: its launch in the same place, behind the order and cluster launches, under the same
+    // predicate (no volume either); sample n counts into row n % n_series, which a launch in front zeroes
+    const bool cna_run = md.cna.on && cna_was_valid && N > 0;
+    const ta::SampleSchedule &cna_sched = md.cna.sched;
+    ta::MdCnaLaunch cn;
+    cn.blk_start = md.cna.blk.ptr;
+    cn.structure = md.cna.structure.ptr;
+    cn.r_local = md.cna.r_local.ptr;
+    cn.counts = md.cna.acc.ptr;
+    cn.status = res.status.ptr;
+    cn.n_elements = h->n_elements, cn.n_frames = (int)F;
+    cn.n_blk = md.cna.n_blk, cn.chunk = md.cna.chunk;
+    cn.mode = md.cna.p.mode;
+    cn.r_cut = md.cna.p.r_cut;
+    {
+      const double r = md.cna.p.mode == TA_MD_CNA_FIXED ? md.cna.p.r_cut : md.cna.p.r_max;
+      cn.r2 = r * r;
+    }
     // Structure factors: the integrator launch of a due step writes the whole-step state (x, v) to the slot of the
     // correlation ring when md_set_sampling is due at the same launch, to two rows of this feature's otherwise;
     // the three launches go BEHIND it, under the same predicate, and read that snapshot.
@@ -1313,6 +1463,19 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
         cl.seq = (unsigned)k;
         cl.row = md.cluster.series.ptr + (size_t)(cluster_sched.index(step0 + k) % md.cluster.p.n_series) * F * 4;
         ta::launch_md_cluster(cl, s);
+        HIP_CHECK(hipGetLastError());
+      }
+      if (cna_run && cna_sched.due(step0, k)) {
+        cn.pos = h->db.pos;
+        cn.cells = h->db.cells;
+        cn.species = h->db.species;
+        cn.atom_start = h->db.atom_start;
+        cn.pair_start = h->pair_start.ptr;  // the resident list
+        cn.pair_j = h->pair_j.ptr;
+        cn.pair_shift = h->pair_shift.ptr;
+        cn.seq = (unsigned)k;
+        cn.row = md.cna.series.ptr + (size_t)(cna_sched.index(step0 + k) % md.cna.p.n_series) * F * TA_MD_CNA_TYPES;
+        ta::launch_md_cna(cn, s);
         HIP_CHECK(hipGetLastError());
       }
       if (adf_run && adf_sched.due(step0, k)) {
@@ -1412,6 +1575,8 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
       md.cluster.sched.finish(md.step);
     }
     md.cluster.sched.valid = cluster_was_valid;
+    if (cna_run) md.cna.sched.finish(md.step);
+    md.cna.sched.valid = cna_was_valid;
     if (n_rebuilds) *n_rebuilds = rebuilds;
     if (baro && F) {
       std::vector<double> rec(4 * n_rec * F);

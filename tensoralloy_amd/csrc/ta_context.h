@@ -268,6 +268,29 @@ struct MdState {
       sched.last = -1;
     }
   } cluster;
+  // Common neighbour analysis (ta_md_set_cna): the setting (r_max resolved), the per-atom arrays of the newest sample,
+  // the counts [F][E][5], the ring of series rows [n_series][F][5] and the launch's workgroup layout
+  struct Cna {
+    bool on = false;
+    ta_md_cna_params p = {0.0, 0.0, 0, 0, 1};
+    DevBuf<int32_t> structure;
+    DevBuf<double> r_local;
+    DevBuf<unsigned long long> acc;
+    DevBuf<unsigned long long> series;
+    DevBuf<int32_t> blk;
+    int n_blk = 0, chunk = 0;
+    SampleSchedule sched;
+    void release() {  // frees what the analysis holds on the device; the setting stays
+      structure.release();
+      r_local.release();
+      acc.release();
+      series.release();
+      blk.release();
+      n_blk = 0;
+      sched.valid = false;
+      sched.last = -1;
+    }
+  } cna;
   // Structure factors (ta_md_set_sq): the Miller triples [Q][3] of the setting and their device twin, the ring of
   // amplitude rows [L][F][E][planes][Q] (planes = 2, or 8 with currents), the accumulators (A_rho, then A_L and
   // A_J with currents, [F][E][E][L][Q] each, one buffer), the amplitude launch's partials and workgroup layout, and

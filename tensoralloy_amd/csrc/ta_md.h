@@ -202,6 +202,34 @@ struct MdClusterLaunch {
   int n_min, species_mask;
 };
 
+constexpr int kMdCnaTypes = 5;  // TA_MD_CNA_TYPES, OVITO's numbering:
+constexpr int kMdCnaOther = 0, kMdCnaFcc = 1, kMdCnaHcp = 2, kMdCnaBcc = 3, kMdCnaIco = 4;
+constexpr int kMdCnaAdaptive = 0, kMdCnaFixed = 1;  // TA_MD_CNA_ADAPTIVE, TA_MD_CNA_FIXED
+
+// Arguments of the common neighbour analysis (ta_md_cna.hip) that ta_md_run puts in front of the integrator launch of
+// a sampled step, behind the order and cluster launches of that step: a launch that zeroes this sample's row of the
+// series and the analysis itself, which has the workgroup layout of the order launches (md_order_chunk).
+struct MdCnaLaunch {
+  const double *pos;              // [N][3] db.pos
+  const double *cells;            // [F][9]
+  const int32_t *species;         // [N]
+  const int32_t *atom_start;      // [F + 1]
+  const int32_t *blk_start;       // [F + 1] first workgroup of each frame (at least one each)
+  const int32_t *pair_start;      // [N + 1] the resident list: centre i owns pair_start[i] .. pair_start[i + 1] - 1
+  const int32_t *pair_j;          // [P]
+  const int32_t *pair_shift;      // [P][3]
+  int32_t *structure;             // [N] of the newest sample
+  double *r_local;                // [N] likewise
+  unsigned long long *counts;     // [F][E][kMdCnaTypes] the accumulator
+  unsigned long long *row;        // [F][kMdCnaTypes] this sample's row of the series
+  const unsigned *status;         // the integrator's status word and
+  unsigned seq;                   // sequence number: the same predicate
+  int n_elements, n_frames, n_blk, chunk;
+  int mode;                       // kMdCnaAdaptive or kMdCnaFixed
+  double r2;                      // square of the candidates' reach: r_max (adaptive) or r_cut (fixed)
+  double r_cut;                   // fixed mode: the bond cutoff and r_local of every atom
+};
+
 constexpr int kMdSqTile = 64;   // q-vectors per workgroup of the amplitude launch: one wave, a lane is a q-vector
 constexpr int kMdSqSlab = 64;    // atoms a workgroup of the amplitude launch holds in LDS at a time
 constexpr int kMdSqMaxQ = 4096;  // TA_MD_SQ_MAX_Q
@@ -243,6 +271,8 @@ void launch_md_adf(const MdAdfLaunch &a, hipStream_t s);
 void launch_md_order(const MdOrderLaunch &a, hipStream_t s);
 
 void launch_md_cluster(const MdClusterLaunch &a, hipStream_t s);
+
+void launch_md_cna(const MdCnaLaunch &a, hipStream_t s);
 
 void launch_md_sq(const MdSqLaunch &a, hipStream_t s);
 

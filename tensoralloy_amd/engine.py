@@ -45,6 +45,7 @@ class Engine:
         self._md_order_solid = (0, 0.0)    # and (solid_degree, threshold)
         self._md_sq = (0, 1, False)        # `md_set_sq` is on: (n_q, n_lags, currents)
         self._md_cluster = (0, 1)          # `md_set_clusters` is on: (n_bins, n_series)
+        self._md_cna = 0                   # `md_set_cna` is on: n_series
         self._n_elements = int(desc.n_elements)
         # what the neighbour list is complete for: max(rcut, acut), acut counting for angular models only
         self._md_cutoff = max(float(desc.rcut), float(desc.acut)) if int(desc.angular) else float(desc.rcut)
@@ -287,6 +288,8 @@ class Engine:
                 self._md_order_bins = 0
             if b"ta_md_set_clusters" in msg:
                 self._md_cluster = (0, 1)
+            if b"ta_md_set_cna" in msg:
+                self._md_cna = 0
             if b"ta_md_set_sampling" in msg:
                 self._md_lags = 0
             if b"ta_md_set_sq" in msg:
@@ -651,6 +654,76 @@ class Engine:
                                                       size.ctypes.data_as(C.POINTER(C.c_int32))))
         self._check(self._lib.ta_md_get_clusters(self._handle, None, None, None, info, C.POINTER(C.c_double)()))
         return {"label": label, "size": size, "step": int(info[3])}
+
+    def md_set_cna(self, mode="adaptive", r_cut=None, r_max=None, n_series=1, sample_every=1):
+        """Common neighbour analysis inside `md_run` (`ta_md_set_cna`): with `n_series` = T >= 1 the loop gives, at every
+        step t (counted since `md_init`) with t % `sample_every` == 0, every atom its lattice type on the device: 0
+        other, 1 fcc, 2 hcp, 3 bcc, 4 ico (`md.CNA_NAMES`, OVITO's numbering). `mode` "adaptive" (OVITO's default,
+        Stukowski 2012) takes the 12, then the 14 nearest of the list entries within `r_max` (None: the model's cutoff
+        max(rcut, acut), the largest value allowed) and a bond cutoff from their mean distance; "fixed" (LAMMPS
+        `compute cna/atom`) takes every neighbour within `r_cut`, which is the bond cutoff too. Every result but
+        `r_local` is an integer and a function of the state alone. The loop counts the atoms per frame, species and
+        type and keeps the last `n_series` rows of the counts per frame (`md_cna`); type and bond cutoff of every atom
+        of the newest sample stay on the device as well (`md_cna_atoms`). `n_series` = 0 switches it off (the default)
+        and frees the buffers. Needs `md_init`; every call starts from zero, as `md_init` does. The setting stays on
+        across `set_frames`. Runs under the barostat and every thermostat. `md_run(0, dt)` analyses the resident state
+        once."""
+        modes = {"adaptive": _lib.TA_MD_CNA_ADAPTIVE, "fixed": _lib.TA_MD_CNA_FIXED}
+        if isinstance(mode, str):
+            if mode not in modes:
+                raise ValueError(f"md_set_cna: mode must be 'adaptive' or 'fixed', not {mode!r}")
+            mode = modes[mode]
+        if int(mode) == _lib.TA_MD_CNA_FIXED and r_cut is None and n_series:
+            raise ValueError("md_set_cna: the fixed mode needs r_cut")
+        p = _lib.MdCnaParams(0.0 if r_cut is None else float(r_cut), float("nan") if r_max is None else float(r_max),
+                             int(mode), int(n_series), int(sample_every))
+        rc = self._lib.ta_md_set_cna(self._handle, C.byref(p))
+        if rc == _lib.TA_ERR_NOMEM:   # (no room for the buffers: the library switched the feature off)
+            self._md_cna = 0
+        self._check(rc)
+        self._md_cna = int(n_series)
+
+    @property
+    def md_cna_series(self):
+        """Rows of the series `md_set_cna` switched on, 0 while the feature is off."""
+        return self._md_cna
+
+    def md_cna(self):
+        """What the loop has found since `md_set_cna` (`ta_md_get_cna`), a dict: `counts` int64 [n_frames, n_elements,
+        5], the atoms of every frame and species with each type (`md.CNA_NAMES`), summed over the samples; `series`
+        int64 [rows, n_frames, 5]: the atoms of every type of the newest `rows` = min(n_samples, n_series) samples,
+        oldest first, and `steps` int64 [rows], their absolute steps; `n_samples`, `mode` ("adaptive" or "fixed"),
+        `sample_every`, `last_step` (absolute step of the newest sample, -1: none), `rows`, `n_series`.
+        `md.structure_fractions` normalises counts or series."""
+        if self.info is None:
+            raise ValueError("md_cna: no resident batch (call set_frames first)")
+        F, E, K = int(self.info.n_frames), self._n_elements, _lib.TA_MD_CNA_TYPES
+        ip = C.POINTER(C.c_int64)
+        info = (C.c_int64 * 6)()
+        self._check(self._lib.ta_md_get_cna(self._handle, None, None, None, info))
+        rows = int(info[4])
+        counts = np.zeros((F, E, K), dtype=np.int64)
+        series, steps = np.zeros((max(rows, 1), F, K), dtype=np.int64), np.zeros(max(rows, 1), dtype=np.int64)
+        self._check(self._lib.ta_md_get_cna(self._handle, counts.ctypes.data_as(ip), series.ctypes.data_as(ip),
+                                            steps.ctypes.data_as(ip), info))
+        return {"counts": counts, "series": series[:rows], "steps": steps[:rows], "n_samples": int(info[0]),
+                "mode": "fixed" if int(info[1]) == _lib.TA_MD_CNA_FIXED else "adaptive", "sample_every": int(info[2]),
+                "last_step": int(info[3]), "rows": rows, "n_series": int(info[5])}
+
+    def md_cna_atoms(self):
+        """Lattice type of every atom in the newest sampled state (`ta_md_get_cna_atoms`), a dict: `structure` int32
+        [n_atoms] (0 other, 1 fcc, 2 hcp, 3 bcc, 4 ico); `r_local` [n_atoms], the bond cutoff of the attempt that
+        decided (adaptive mode; 0 with fewer than 12 candidates) or `r_cut` (fixed mode); `step`: the absolute step of
+        that state. Costs a host sync and no list rebuild. Refused until the first sample has been taken."""
+        if self.info is None:
+            raise ValueError("md_cna_atoms: no resident batch (call set_frames first)")
+        N = int(self.info.n_atoms)
+        structure, r_local = np.zeros(N, dtype=np.int32), np.zeros(N, dtype=np.float64)
+        info = (C.c_int64 * 6)()
+        self._check(self._lib.ta_md_get_cna_atoms(self._handle, structure.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  _lib.as_dp(r_local)))
+        self._check(self._lib.ta_md_get_cna(self._handle, None, None, None, info))
+        return {"structure": structure, "r_local": r_local, "step": int(info[3])}
 
     def md_set_sq(self, miller=None, n_lags=1, sample_every=1, currents=False):
         """Structure factors inside `md_run` (`ta_md_set_sq`): `miller` int [Q, 3] (1 .. 4096 triples, |n_c| <= 64;

@@ -74,6 +74,12 @@ time (`cluster_nmin` > 0, on top of `order_bins`) or the clusters of chosen elem
 time series, `cluster_size_distribution` the histogram, `clusters_from_labels` the per-atom labels. Runs under the
 barostat and every thermostat.
 
+Common neighbour analysis: with `cna` ("adaptive" or "fixed"; and `cna_rcut`, `cna_rmax`, `cna_series`, `cna_every`) the
+loop gives, at every sampled step, every atom its lattice type on the device (`Engine.md_set_cna`;
+`DeviceMD.get_structure_types`, `DeviceMD.get_structure_counts`): 0 other, 1 fcc, 2 hcp, 3 bcc, 4 ico (`CNA_NAMES`), as
+OVITO's common neighbour analysis and LAMMPS `compute cna/atom` do. Every type is an exact integer and a function of
+the state alone. `structure_fractions` normalises the counts. Runs under the barostat and every thermostat.
+
 Structure factors: with `sq_miller` (and `sq_lags`, `sq_every`, `sq_currents`) the loop sums, at every sampled step,
 the density amplitudes rho_a(q) = sum_i exp(i q . x_i) of every element over ALL atoms of a frame, at the wave
 vectors q = 2 pi h^-1 n of the integer triples given (`q_points` lists those below a |q|), keeps the last `sq_lags`
@@ -97,7 +103,7 @@ bar = 1.0e-4 * GPa
 
 __all__ = ["fs", "kB", "GPa", "bar", "maxwell_boltzmann", "DeviceMD", "vdos", "diffusion_coefficient",
            "green_kubo_diffusion", "rdf", "coordination_number", "adf", "order_distribution", "solid_fraction",
-           "classify_solid", "largest_cluster", "cluster_size_distribution", "clusters_from_labels", "q_points", "intermediate_scattering", "structure_factor", "transverse_current",
+           "classify_solid", "largest_cluster", "cluster_size_distribution", "clusters_from_labels", "CNA_NAMES", "structure_fractions", "q_points", "intermediate_scattering", "structure_factor", "transverse_current",
            "dynamic_structure_factor", "shell_average"]
 
 
@@ -356,6 +362,21 @@ def clusters_from_labels(label):
     return np.array([len(groups[l]) for l in keys], dtype=np.int64), [np.array(groups[l], dtype=np.int64) for l in keys]
 
 
+CNA_NAMES = ("other", "fcc", "hcp", "bcc", "ico")   # the structure types of the device loop, OVITO's numbering
+
+
+def structure_fractions(counts):
+    """The fractions of the structure types from the counts `counts` [..., 5] or the series of the device loop
+    (`Engine.md_cna`): the last axis divided by its sum, NaN for a row without atoms."""
+    c = np.asarray(counts)
+    if c.ndim < 1 or c.shape[-1] != len(CNA_NAMES):
+        raise ValueError(f"structure_fractions: counts must be [..., {len(CNA_NAMES)}]")
+    c = c.astype(np.float64)
+    total = c.sum(axis=-1, keepdims=True)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(total > 0.0, c / total, np.nan)
+
+
 def q_points(cell, q_max, max_index=64):
     """The integer triples n [Q, 3] (int32) of all wave vectors q = 2 pi h^-1 n of `cell` (h [3, 3], rows are lattice
     vectors) with 0 < |q| <= `q_max` (1 / A), one of each pair +-n (the first non-zero index is positive), ordered by
@@ -518,6 +539,14 @@ class DeviceMD:
                            (`get_clusters`); runs under the barostat too. Without `cluster_bins` no method of the
                            clusters is called on the engine, unless its `md_cluster_bins` says that an earlier
                            `DeviceMD` left them on: they are then switched off
+    cna, cna_rcut, cna_rmax, cna_series, cna_every : `cna` given ("adaptive" or "fixed"): the loop gives every atom
+                           its lattice type (0 other, 1 fcc, 2 hcp, 3 bcc, 4 ico) at every `cna_every`-th step on the
+                           device, adaptively among the list entries within `cna_rmax` (default: the model's cutoff)
+                           or with every neighbour within `cna_rcut` (fixed mode, which needs it), and keeps the last
+                           `cna_series` rows (default 1) of the counts (`get_structure_types`,
+                           `get_structure_counts`); runs under the barostat too. Without `cna` no method of the
+                           analysis is called on the engine, unless its `md_cna_series` says that an earlier
+                           `DeviceMD` left it on: it is then switched off
     sq_miller, sq_lags, sq_every, sq_currents : `sq_miller` given (int [Q, 3], 1 .. 4096 triples with |n_c| <= 64,
                            e.g. from `q_points`): the loop sums the density amplitudes at the wave vectors
                            q = 2 pi h^-1 n of every `sq_every`-th step over all atoms (the state at construction is
@@ -540,7 +569,8 @@ class DeviceMD:
                  sample_every=1, rdf_bins=None, rdf_rmax=None, rdf_every=1, adf_bins=None, adf_rbond=None,
                  adf_every=1, order_degrees=None, order_rbond=None, order_bins=None, order_every=1, order_solid=None,
                  sq_miller=None, sq_lags=None, sq_every=1, sq_currents=False, cluster_bins=None, cluster_rlink=None,
-                 cluster_nmin=0, cluster_species=None, cluster_series=1, cluster_every=1):
+                 cluster_nmin=0, cluster_species=None, cluster_series=1, cluster_every=1, cna=None, cna_rcut=None,
+                 cna_rmax=None, cna_series=1, cna_every=1):
         if not (np.isfinite(timestep) and timestep > 0.0):
             raise ValueError("DeviceMD: timestep must be a finite time > 0")
         barostat = (pressure, taup, compressibility)
@@ -637,6 +667,26 @@ class DeviceMD:
               or cluster_series != 1):
             raise ValueError("DeviceMD: cluster_rlink, cluster_nmin, cluster_species, cluster_series and cluster_every "
                              "belong to the cluster analysis (cluster_bins)")
+        if cna is not None:
+            whole = lambda a: isinstance(a, (int, np.integer)) and not isinstance(a, bool)
+            if cna not in ("adaptive", "fixed"):
+                raise ValueError("DeviceMD: cna must be 'adaptive' or 'fixed'")
+            if not (whole(cna_every) and cna_every >= 1):
+                raise ValueError("DeviceMD: cna_every must be an integer >= 1")
+            if not (whole(cna_series) and 1 <= cna_series <= 1048576):
+                raise ValueError("DeviceMD: cna_series must be an integer 1 .. 1048576")
+            if cna == "fixed" and cna_rcut is None:
+                raise ValueError("DeviceMD: cna = 'fixed' needs cna_rcut")
+            if cna == "fixed" and cna_rmax is not None:
+                raise ValueError("DeviceMD: cna_rmax belongs to cna = 'adaptive'")
+            if cna == "adaptive" and cna_rcut is not None:
+                raise ValueError("DeviceMD: cna_rcut belongs to cna = 'fixed'")
+            for name, r in (("cna_rcut", cna_rcut), ("cna_rmax", cna_rmax)):
+                if r is not None and not (np.ndim(r) == 0 and np.isfinite(r) and r > 0.0):
+                    raise ValueError(f"DeviceMD: {name} must be a finite distance > 0")
+        elif cna_every != 1 or cna_rcut is not None or cna_rmax is not None or cna_series != 1:
+            raise ValueError("DeviceMD: cna_rcut, cna_rmax, cna_series and cna_every belong to the common neighbour "
+                             "analysis (cna)")
         if sq_miller is not None:
             whole = lambda a: isinstance(a, (int, np.integer)) and not isinstance(a, bool)
             miller = np.asarray(sq_miller)
@@ -775,6 +825,11 @@ class DeviceMD:
                                    int(cluster_series), int(cluster_every))
         elif getattr(engine, "md_cluster_bins", 0):
             engine.md_set_clusters(n_bins=0)
+        self._cna = cna
+        if cna is not None:   # (opt-in in the same way)
+            engine.md_set_cna(cna, cna_rcut, cna_rmax, int(cna_series), int(cna_every))
+        elif getattr(engine, "md_cna_series", 0):
+            engine.md_set_cna(n_series=0)
         self._sq = sq_miller is not None
         self._sq_every, self._sq_currents = int(sq_every), bool(sq_currents)
         if self._sq:   # (opt-in in the same way)
@@ -920,6 +975,22 @@ class DeviceMD:
         out = self.engine.md_clusters()
         out.update(self.engine.md_cluster_atoms())
         return out
+
+    def get_structure_types(self):
+        """The lattice type of every atom in the newest sampled state: the dict of `Engine.md_cna_atoms` (`structure`:
+        0 other, 1 fcc, 2 hcp, 3 bcc, 4 ico; `r_local`; `step`), the atoms of a batch in the order of the frames. Needs
+        `cna`."""
+        if self._cna is None:
+            raise ValueError("DeviceMD.get_structure_types: the common neighbour analysis is off (cna)")
+        return self.engine.md_cna_atoms()
+
+    def get_structure_counts(self):
+        """The atoms of every lattice type the loop has counted: the dict of `Engine.md_cna` (`counts` [n_frames,
+        n_elements, 5], `series` [rows, n_frames, 5], `steps`, ...); `structure_fractions` normalises them. Needs
+        `cna`."""
+        if self._cna is None:
+            raise ValueError("DeviceMD.get_structure_counts: the common neighbour analysis is off (cna)")
+        return self.engine.md_cna()
 
     def get_order_atoms(self):
         """The order parameters of every atom in the newest sampled state: the dict of `Engine.md_order_atoms`
