@@ -2,6 +2,17 @@
 // is in ta_resident.hip; the integrator, correlation, pair-distribution, bond-angle and bond-order launches are in
 // ta_md.hip, ta_md_corr.hip, ta_md_rdf.hip, ta_md_adf.hip and ta_md_order.hip; the cluster launches in
 // ta_md_cluster.hip, the common neighbour analysis in ta_md_cna.hip, the structure-factor launches in ta_md_sq.hip.
+//
+// The seven samplers (ta_md_set_sampling, _rdf, _adf, _order, _clusters, _cna, _sq) share one host-side lifecycle,
+// written once below: md_alloc_layout, md_sampler_ready, md_sampler_off / md_sampler_set, and the loops of ta_md_init
+// and ta_md_run. To add a sampler:
+//   1. ta_sampler_text.h: its texts, a constant in md_text;
+//   2. ta_context.h: a struct on MdSampler in MdState with its Setting, its buffers and its release(), and its place
+//      in for_each_sampler;
+//   3. here: its md_alloc (buffer sizes and uploads), its setter (parameter checks, then md_sampler_off or
+//      md_sampler_set) and its getters (md_sampler_ready, fill_info, copy_series);
+//   4. ta_md_run: its cross-checks, its launch struct, its place in the launch order of a step and in the order of
+//      the epilogue.
 #include <cmath>
 #include <cstring>
 
@@ -9,6 +20,8 @@
 #include "ta_md.h"
 
 using namespace ta::host;
+
+static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the getters copy the counts as they are");
 
 namespace {
 
@@ -22,98 +35,92 @@ std::vector<int32_t> frame_blocks(const ta_context *h, int per_atom, int chunk) 
   return start;
 }
 
-// Rings, zeroed accumulators and the correlation launch's chunk layout for the resident batch under setting
-// `p`, with no sample held. False when the device has no room (everything is released then); throws otherwise.
-bool md_sampling_alloc(ta_context *h, const ta_md_sampling_params &p) {
-  auto &c = h->md.corr;
-  const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
-  const size_t L = (size_t)p.n_lags, E = (size_t)h->n_elements;
-  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches read the old buffers)
-  c.release();
-  const std::vector<int32_t> start = frame_blocks(h, 3, ta::kMdCorrChunk);
-  const size_t n_chunks = (size_t)start[F], n_acc = 2 * F * E * L;
-  if (!c.ring_x.try_exact(L * 3 * N) || !c.ring_v.try_exact(L * 3 * N) || !c.acc.try_exact(n_acc) ||
-      !c.part.try_exact(n_chunks * 2 * E * L) || !c.blk.try_exact(F + 1)) {
-    c.release();
+template <typename T>
+void zero(DevBuf<T> &b, size_t n) {
+  HIP_CHECK(hipMemset(b.ptr, 0, std::max<size_t>(n, 1) * sizeof(T)));
+}
+template <typename T>
+void upload(DevBuf<T> &b, const std::vector<T> &v) {
+  HIP_CHECK(hipMemcpy(b.ptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+}
+// the squares of the cutoffs `r`[E][E] of a setting
+void upload_squares(DevBuf<double> &b, std::vector<double> r) {
+  for (double &x : r) x *= x;
+  upload(b, r);
+}
+
+// Allocating sampler `x` for the resident batch, around the feature's own part: the stream is waited for (an earlier
+// run's launches use the old buffers), everything is released, the launch's workgroup layout is planned (`chunk` of
+// the frame's per_atom * n_atoms items each), try_buffers(n_blk) allocates the feature's buffers, fill() zeroes its
+// accumulators and uploads its data, and the schedule starts with no sample taken. False when the device has no room
+// (everything is released then); throws otherwise.
+template <typename S, typename Try, typename Fill>
+bool md_alloc_layout(ta_context *h, S &x, int64_t every, int per_atom, int chunk, Try &&try_buffers, Fill &&fill) {
+  const size_t F = h->keep_natoms.size();
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+  x.release();
+  const std::vector<int32_t> start = frame_blocks(h, per_atom, chunk);
+  if (!try_buffers((size_t)start[F]) || !x.blk.try_exact(F + 1)) {
+    x.release();
     return false;
   }
-  HIP_CHECK(hipMemset(c.acc.ptr, 0, std::max<size_t>(n_acc, 1) * sizeof(double)));
-  HIP_CHECK(hipMemcpy(c.blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-  c.n_chunks = (int)n_chunks;
-  c.sched.every = p.sample_every;
-  c.sched.start(h->md.step);
-  c.sched.valid = true;
+  fill();
+  upload(x.blk, start);
+  x.n_blk = (int)start[F];
+  x.chunk = chunk;
+  x.sched.every = every;
+  x.sched.start(h->md.step);
+  x.sched.valid = true;
   return true;
 }
 
-// Zeroed counts and the launch's workgroup layout for the resident batch under setting `p`, with no sample
-// taken. False when the device has no room (everything is released then); throws otherwise.
-bool md_rdf_alloc(ta_context *h, const ta_md_rdf_params &p) {
-  auto &g = h->md.rdf;
+// md_alloc(h, x, s): sampler x allocated for setting `s` (its own, or a setter's candidate) as md_alloc_layout says.
+// Here: the rings, the accumulators and the partials of the correlation launch
+bool md_alloc(ta_context *h, MdState::Corr &c, const MdState::Corr::Setting &s) {
   const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
-  const size_t E = (size_t)h->n_elements, n_acc = F * E * E * (size_t)p.n_bins;
-  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches add to the old buffer)
-  g.release();
-  const int chunk = ta::md_rdf_chunk((long long)N);
-  const std::vector<int32_t> start = frame_blocks(h, 1, chunk);
-  if (!g.acc.try_exact(n_acc) || !g.blk.try_exact(F + 1)) {
-    g.release();
-    return false;
-  }
-  HIP_CHECK(hipMemset(g.acc.ptr, 0, std::max<size_t>(n_acc, 1) * sizeof(unsigned long long)));
-  HIP_CHECK(hipMemcpy(g.blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-  g.n_blk = (int)start[F];
-  g.chunk = chunk;
-  g.sched.every = p.sample_every;
-  g.sched.start(h->md.step);
-  g.sched.valid = true;
-  return true;
+  const size_t L = (size_t)s.p.n_lags, E = (size_t)h->n_elements, n_acc = 2 * F * E * L;
+  return md_alloc_layout(
+      h, c, s.p.sample_every, 3, ta::kMdCorrChunk,
+      [&](size_t n_blk) {
+        return c.ring_x.try_exact(L * 3 * N) && c.ring_v.try_exact(L * 3 * N) && c.acc.try_exact(n_acc) &&
+               c.part.try_exact(n_blk * 2 * E * L);
+      },
+      [&]() { zero(c.acc, n_acc); });
 }
 
-// Zeroed counts, the squared cutoffs `rb`[E][E] and the launch's workgroup layout for the resident batch under
-// setting `p`, with no sample taken. False when the device has no room (everything is released then); throws
-// otherwise.
-bool md_adf_alloc(ta_context *h, const ta_md_adf_params &p, const std::vector<double> &rb) {
-  auto &g = h->md.adf;
+// the counts
+bool md_alloc(ta_context *h, MdState::Rdf &g, const MdState::Rdf::Setting &s) {
   const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
-  const size_t E = (size_t)h->n_elements, n_acc = F * E * (E * (E + 1) / 2) * (size_t)p.n_bins;
-  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches add to the old buffer)
-  g.release();
-  const int chunk = ta::md_adf_chunk((long long)N);
-  const std::vector<int32_t> start = frame_blocks(h, 1, chunk);
-  if (!g.acc.try_exact(n_acc) || !g.blk.try_exact(F + 1) || !g.rb2.try_exact(E * E)) {
-    g.release();
-    return false;
-  }
-  std::vector<double> rb2(E * E);
-  for (size_t k = 0; k < E * E; ++k) rb2[k] = rb[k] * rb[k];
-  HIP_CHECK(hipMemset(g.acc.ptr, 0, std::max<size_t>(n_acc, 1) * sizeof(unsigned long long)));
-  HIP_CHECK(hipMemcpy(g.blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(g.rb2.ptr, rb2.data(), E * E * sizeof(double), hipMemcpyHostToDevice));
-  g.n_blk = (int)start[F];
-  g.chunk = chunk;
-  g.sched.every = p.sample_every;
-  g.sched.start(h->md.step);
-  g.sched.valid = true;
-  return true;
+  const size_t E = (size_t)h->n_elements, n_acc = F * E * E * (size_t)s.p.n_bins;
+  return md_alloc_layout(
+      h, g, s.p.sample_every, 1, ta::md_rdf_chunk((long long)N), [&](size_t) { return g.acc.try_exact(n_acc); },
+      [&]() { zero(g.acc, n_acc); });
 }
 
-// Zeroed counts, the squared cutoffs `rb`[E][E], the N_lm, the per-atom arrays and the launches' workgroup layout
-// for the resident batch under setting `p`, with no sample taken. False when the device has no room (everything
-// is released then); throws otherwise.
-bool md_order_alloc(ta_context *h, const ta_md_order_params &p, const std::vector<double> &rb) {
-  auto &g = h->md.order;
+// the counts and the squared cutoffs
+bool md_alloc(ta_context *h, MdState::Adf &g, const MdState::Adf::Setting &s) {
   const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
-  const size_t E = (size_t)h->n_elements, D = (size_t)p.n_degrees;
-  const size_t n_hist = F * E * D * (size_t)p.n_bins, n_acc = 2 * n_hist + F * E * (TA_MD_ORDER_MAX_CONN + 1);
-  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches add to the old buffers)
-  g.release();
+  const size_t E = (size_t)h->n_elements, n_acc = F * E * (E * (E + 1) / 2) * (size_t)s.p.n_bins;
+  return md_alloc_layout(
+      h, g, s.p.sample_every, 1, ta::md_adf_chunk((long long)N),
+      [&](size_t) { return g.acc.try_exact(n_acc) && g.rb2.try_exact(E * E); },
+      [&]() {
+        zero(g.acc, n_acc);
+        upload_squares(g.rb2, s.rb);
+      });
+}
+
+// the counts, the squared cutoffs, the N_lm and the per-atom arrays
+bool md_alloc(ta_context *h, MdState::Order &g, const MdState::Order::Setting &s) {
+  const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
+  const size_t E = (size_t)h->n_elements, D = (size_t)s.p.n_degrees;
+  const size_t n_hist = F * E * D * (size_t)s.p.n_bins, n_acc = 2 * n_hist + F * E * (TA_MD_ORDER_MAX_CONN + 1);
   // N_lm = sqrt((2 l + 1) / (4 pi) (l - m)! / (l + m)!), degree by degree, m = 0 .. l
   std::vector<double> norm;
   int solid = 0;
-  for (int d = 0; d < p.n_degrees; ++d) {
-    const int l = p.degrees[d];
-    if (l == p.solid_degree) solid = d;
+  for (int d = 0; d < s.p.n_degrees; ++d) {
+    const int l = s.p.degrees[d];
+    if (l == s.p.solid_degree) solid = d;
     for (int m = 0; m <= l; ++m) {
       long double ratio = 1.0L;
       for (int k = l - m + 1; k <= l + m; ++k) ratio /= (long double)k;
@@ -121,115 +128,74 @@ bool md_order_alloc(ta_context *h, const ta_md_order_params &p, const std::vecto
     }
   }
   const size_t M = norm.size();
-  const int chunk = ta::md_order_chunk((long long)N);
-  const std::vector<int32_t> start = frame_blocks(h, 1, chunk);
-  if (!g.acc.try_exact(n_acc) || !g.blk.try_exact(F + 1) || !g.rb2.try_exact(E * E) || !g.norm.try_exact(M) ||
-      !g.qlm.try_exact(2 * M * N + 1) || !g.per_atom.try_exact(2 * D * N + 1) || !g.per_atom_int.try_exact(2 * N + 1)) {
-    g.release();
-    return false;
-  }
-  std::vector<double> rb2(E * E);
-  for (size_t k = 0; k < E * E; ++k) rb2[k] = rb[k] * rb[k];
-  HIP_CHECK(hipMemset(g.acc.ptr, 0, std::max<size_t>(n_acc, 1) * sizeof(unsigned long long)));
-  HIP_CHECK(hipMemcpy(g.blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(g.rb2.ptr, rb2.data(), E * E * sizeof(double), hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(g.norm.ptr, norm.data(), M * sizeof(double), hipMemcpyHostToDevice));
-  g.n_blk = (int)start[F];
-  g.chunk = chunk;
-  g.n_lm = (int)M;
-  g.solid = solid;
-  g.sched.every = p.sample_every;
-  g.sched.start(h->md.step);
-  g.sched.valid = true;
-  return true;
+  return md_alloc_layout(
+      h, g, s.p.sample_every, 1, ta::md_order_chunk((long long)N),
+      [&](size_t) {
+        return g.acc.try_exact(n_acc) && g.rb2.try_exact(E * E) && g.norm.try_exact(M) && g.qlm.try_exact(2 * M * N + 1) &&
+               g.per_atom.try_exact(2 * D * N + 1) && g.per_atom_int.try_exact(2 * N + 1);
+      },
+      [&]() {
+        zero(g.acc, n_acc);
+        upload_squares(g.rb2, s.rb);
+        upload(g.norm, norm);
+        g.n_lm = (int)M;
+        g.solid = solid;
+      });
 }
 
-// Zeroed histogram, series and give-up word, the squared cutoffs `rl`[E][E], the per-atom arrays and the link launch's
-// workgroup layout for the resident batch under setting `p`, with no sample taken. False when the device has no room
-// (everything is released then); throws otherwise.
-bool md_cluster_alloc(ta_context *h, const ta_md_cluster_params &p, const std::vector<double> &rl) {
+// the histogram, the series, the give-up word, the squared cutoffs and the per-atom arrays; the layout is the link
+// launch's
+bool md_alloc(ta_context *h, MdState::Cluster &g, const MdState::Cluster::Setting &s) {
   static_assert(TA_MD_MAX_BINS <= ta::kMdClusterLdsWords, "the summary launch keeps all bins of a frame in LDS");
-  auto &g = h->md.cluster;
   const size_t N = h->keep_species.size(), F = h->keep_natoms.size(), E = (size_t)h->n_elements;
-  const size_t n_hist = F * (size_t)p.n_bins, n_series = (size_t)p.n_series * F * 4;
-  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches add to the old buffers)
-  g.release();
-  const int chunk = ta::md_order_chunk((long long)N);
-  const std::vector<int32_t> start = frame_blocks(h, 1, chunk);
-  if (!g.acc.try_exact(n_hist) || !g.series.try_exact(n_series) || !g.blk.try_exact(F + 1) || !g.rl2.try_exact(E * E) ||
-      !g.per_atom.try_exact(4 * N + 1) || !g.giveup.try_exact(4)) {
-    g.release();
-    return false;
-  }
-  std::vector<double> rl2(E * E);
-  for (size_t k = 0; k < E * E; ++k) rl2[k] = rl[k] * rl[k];
-  HIP_CHECK(hipMemset(g.acc.ptr, 0, std::max<size_t>(n_hist, 1) * sizeof(unsigned long long)));
-  HIP_CHECK(hipMemset(g.series.ptr, 0, std::max<size_t>(n_series, 1) * sizeof(long long)));
-  HIP_CHECK(hipMemset(g.giveup.ptr, 0, 4 * sizeof(unsigned)));
-  HIP_CHECK(hipMemcpy(g.blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(g.rl2.ptr, rl2.data(), E * E * sizeof(double), hipMemcpyHostToDevice));
-  g.n_blk = (int)start[F];
-  g.chunk = chunk;
-  g.sched.every = p.sample_every;
-  g.sched.start(h->md.step);
-  g.sched.valid = true;
-  return true;
+  const size_t n_hist = F * (size_t)s.p.n_bins, n_series = (size_t)s.p.n_series * F * 4;
+  return md_alloc_layout(
+      h, g, s.p.sample_every, 1, ta::md_order_chunk((long long)N),
+      [&](size_t) {
+        return g.acc.try_exact(n_hist) && g.series.try_exact(n_series) && g.rl2.try_exact(E * E) &&
+               g.per_atom.try_exact(4 * N + 1) && g.giveup.try_exact(4);
+      },
+      [&]() {
+        zero(g.acc, n_hist);
+        zero(g.series, n_series);
+        zero(g.giveup, 4);
+        upload_squares(g.rl2, s.rl);
+      });
 }
 
-// Zeroed counts and series, the per-atom arrays and the launch's workgroup layout for the resident batch under setting
-// `p`, with no sample taken. False when the device has no room (everything is released then); throws otherwise.
-bool md_cna_alloc(ta_context *h, const ta_md_cna_params &p) {
+// the counts, the series and the per-atom arrays
+bool md_alloc(ta_context *h, MdState::Cna &g, const MdState::Cna::Setting &s) {
   static_assert(TA_MD_CNA_TYPES == ta::kMdCnaTypes && TA_MD_CNA_ADAPTIVE == ta::kMdCnaAdaptive &&
                     TA_MD_CNA_FIXED == ta::kMdCnaFixed, "the header and the launch agree");
-  auto &g = h->md.cna;
   const size_t N = h->keep_species.size(), F = h->keep_natoms.size(), E = (size_t)h->n_elements;
-  const size_t n_acc = F * E * TA_MD_CNA_TYPES, n_series = (size_t)p.n_series * F * TA_MD_CNA_TYPES;
-  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches add to the old buffers)
-  g.release();
-  const int chunk = ta::md_order_chunk((long long)N);
-  const std::vector<int32_t> start = frame_blocks(h, 1, chunk);
-  if (!g.acc.try_exact(n_acc) || !g.series.try_exact(n_series) || !g.blk.try_exact(F + 1) || !g.structure.try_exact(N + 1) ||
-      !g.r_local.try_exact(N + 1)) {
-    g.release();
-    return false;
-  }
-  HIP_CHECK(hipMemset(g.acc.ptr, 0, std::max<size_t>(n_acc, 1) * sizeof(unsigned long long)));
-  HIP_CHECK(hipMemset(g.series.ptr, 0, std::max<size_t>(n_series, 1) * sizeof(unsigned long long)));
-  HIP_CHECK(hipMemcpy(g.blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-  g.n_blk = (int)start[F];
-  g.chunk = chunk;
-  g.sched.every = p.sample_every;
-  g.sched.start(h->md.step);
-  g.sched.valid = true;
-  return true;
+  const size_t n_acc = F * E * TA_MD_CNA_TYPES, n_series = (size_t)s.p.n_series * F * TA_MD_CNA_TYPES;
+  return md_alloc_layout(
+      h, g, s.p.sample_every, 1, ta::md_order_chunk((long long)N),
+      [&](size_t) {
+        return g.acc.try_exact(n_acc) && g.series.try_exact(n_series) && g.structure.try_exact(N + 1) &&
+               g.r_local.try_exact(N + 1);
+      },
+      [&]() {
+        zero(g.acc, n_acc);
+        zero(g.series, n_series);
+      });
 }
 
-// The Miller triples on the device, an empty ring, zeroed accumulators, the partials, the snapshot rows and the
-// amplitude launch's workgroup layout for the resident batch under setting `p`, with no sample held. False when the
-// device has no room (everything is released then); throws otherwise.
-bool md_sq_alloc(ta_context *h, const ta_md_sq_params &p, const std::vector<int32_t> &miller) {
-  auto &g = h->md.sq;
+// the Miller triples, an empty ring, the accumulators, the partials of the amplitude launch and the snapshot rows
+bool md_alloc(ta_context *h, MdState::Sq &g, const MdState::Sq::Setting &s) {
   const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
-  const size_t E = (size_t)h->n_elements, Q = (size_t)p.n_q, L = (size_t)p.n_lags, P = p.currents ? 8 : 2;
-  const size_t n_acc = (p.currents ? 3 : 1) * F * E * E * L * Q;
-  HIP_CHECK(hipStreamSynchronize(h->stream));  // (an earlier run's launches add to the old buffers)
-  g.release();
-  const int chunk = ta::md_sq_chunk((long long)N);
-  const std::vector<int32_t> start = frame_blocks(h, 1, chunk);
-  if (!g.acc.try_exact(n_acc) || !g.ring.try_exact(L * F * E * P * Q) || !g.part.try_exact((size_t)start[F] * E * P * Q) ||
-      !g.snap_x.try_exact(3 * N) || !g.snap_v.try_exact(3 * N) || !g.miller_dev.try_exact(3 * Q) || !g.blk.try_exact(F + 1)) {
-    g.release();
-    return false;
-  }
-  HIP_CHECK(hipMemset(g.acc.ptr, 0, std::max<size_t>(n_acc, 1) * sizeof(double)));
-  HIP_CHECK(hipMemcpy(g.blk.ptr, start.data(), (F + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(g.miller_dev.ptr, miller.data(), 3 * Q * sizeof(int32_t), hipMemcpyHostToDevice));
-  g.n_blk = (int)start[F];
-  g.chunk = chunk;
-  g.sched.every = p.sample_every;
-  g.sched.start(h->md.step);
-  g.sched.valid = true;
-  return true;
+  const size_t E = (size_t)h->n_elements, Q = (size_t)s.p.n_q, L = (size_t)s.p.n_lags, P = s.p.currents ? 8 : 2;
+  const size_t n_acc = (s.p.currents ? 3 : 1) * F * E * E * L * Q;
+  return md_alloc_layout(
+      h, g, s.p.sample_every, 1, ta::md_sq_chunk((long long)N),
+      [&](size_t n_blk) {
+        return g.acc.try_exact(n_acc) && g.ring.try_exact(L * F * E * P * Q) && g.part.try_exact(n_blk * E * P * Q) &&
+               g.snap_x.try_exact(3 * N) && g.snap_v.try_exact(3 * N) && g.miller_dev.try_exact(3 * Q);
+      },
+      [&]() {
+        zero(g.acc, n_acc);
+        upload(g.miller_dev, s.miller);
+      });
 }
 
 // what ta_md_set_sq asks of the resident frames: periodic along all three axes, a cell that can be inverted.
@@ -246,17 +212,6 @@ int md_sq_frames(ta_context *h) {
     if (!std::isfinite(det) || !(std::fabs(det) > 0.0))
       return fail(h, TA_ERR_INVALID, "ta_md_set_sq: the cell of frame " + std::to_string(f) + " is singular");
   }
-  return TA_OK;
-}
-
-// what the two getters of the structure factors need; returns 0 or the error code
-int md_sq_ready(ta_context *h, const char *who) {
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, std::string(who) + " called before ta_md_init");
-  if (!h->md.sq.on) return fail(h, TA_ERR_INVALID, std::string(who) + ": the structure factors are off (ta_md_set_sq)");
-  if (!h->md.sq.sched.valid)
-    return fail(h, TA_ERR_INVALID, std::string(who) + ": a ta_md_run failed and left the data invalid; call "
-                                   "ta_md_set_sq or ta_md_init again");
   return TA_OK;
 }
 
@@ -285,58 +240,98 @@ int md_bond_cutoffs(ta_context *h, const std::string &who, double r_bond, const 
   return TA_OK;
 }
 
+// what every call about the resident MD state needs; returns 0 or the error code
+int md_resident(ta_context *h, const std::string &who) {
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, who + ": no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, who + " called before ta_md_init");
+  return TA_OK;
+}
+
 // what ta_md_get_chain and ta_md_set_chain need; returns 0 or the error code
 int md_chain_ready(ta_context *h, const char *who) {
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, std::string(who) + " called before ta_md_init");
+  if (const int rc = md_resident(h, who)) return rc;
   if (!h->md.nhc.on)
     return fail(h, TA_ERR_INVALID, std::string(who) + ": the Nose-Hoover chain thermostat is off (ta_md_set_nose_hoover)");
   return TA_OK;
 }
 
-// what the two getters of the sampled data need; returns 0 or the error code
-int md_samples_ready(ta_context *h, const char *who) {
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, std::string(who) + " called before ta_md_init");
-  if (!h->md.corr.on) return fail(h, TA_ERR_INVALID, std::string(who) + ": sampling is off (ta_md_set_sampling)");
-  if (!h->md.corr.sched.valid)
-    return fail(h, TA_ERR_INVALID, std::string(who) + ": a ta_md_run failed and left the sampled data invalid; call "
-                                   "ta_md_set_sampling or ta_md_init again");
+// what the getters of sampler `x` need: it is on and holds the data of runs that succeeded; returns 0 or the error code
+int md_sampler_ready(ta_context *h, const MdSampler &x, const char *who) {
+  if (const int rc = md_resident(h, who)) return rc;
+  if (!x.on) return fail(h, TA_ERR_INVALID, ta::md_text_off(x.text, who));
+  if (!x.sched.valid) return fail(h, TA_ERR_INVALID, ta::md_text_invalid(x.text, who));
   return TA_OK;
 }
 
-// what the two getters of the order parameters need; returns 0 or the error code
-int md_order_ready(ta_context *h, const char *who) {
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, std::string(who) + " called before ta_md_init");
-  if (!h->md.order.on)
-    return fail(h, TA_ERR_INVALID, std::string(who) + ": the bond-orientational order parameters are off (ta_md_set_order)");
-  if (!h->md.order.sched.valid)
-    return fail(h, TA_ERR_INVALID, std::string(who) + ": a ta_md_run failed and left the counts invalid; call "
-                                   "ta_md_set_order or ta_md_init again");
-  return TA_OK;
+// A setter whose parameters say "off": the sampler goes off and gives back what it holds on the device
+template <typename S>
+int md_sampler_off(ta_context *h, S &x) {
+  x.on = false;
+  return guarded(h, [&]() {
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    x.release();
+  });
 }
 
-// what the two getters of the clusters need; returns 0 or the error code
-int md_cluster_ready(ta_context *h, const char *who) {
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, std::string(who) + " called before ta_md_init");
-  if (!h->md.cluster.on) return fail(h, TA_ERR_INVALID, std::string(who) + ": the cluster analysis is off (ta_md_set_clusters)");
-  if (!h->md.cluster.sched.valid)
-    return fail(h, TA_ERR_INVALID, std::string(who) + ": a ta_md_run failed and left the data invalid; call "
-                                   "ta_md_set_clusters or ta_md_init again");
-  return TA_OK;
+// A setter whose parameters passed its checks: with a resident batch behind ta_md_init (that batch_check, if any,
+// accepts), sampler x is allocated for the candidate `s` and keeps it as its setting. It is off while that has not
+// succeeded; TA_ERR_NOMEM names `what` there was no room for.
+template <typename S>
+int md_sampler_set(ta_context *h, S &x, const typename S::Setting &s, const std::string &what,
+                   int (*batch_check)(ta_context *) = nullptr) {
+  if (const int rc = md_resident(h, x.text.setter)) return rc;
+  if (batch_check)
+    if (const int rc = batch_check(h)) return rc;
+  bool nomem = false;
+  const int rc = guarded(h, [&]() {
+    x.on = false;  // (until the buffers exist)
+    nomem = !md_alloc(h, x, s);
+    if (!nomem) {
+      x.set = s;
+      x.on = true;
+    }
+  });
+  if (rc == TA_OK && nomem) return fail(h, TA_ERR_NOMEM, ta::md_text_nomem(x.text, x.text.setter, what));
+  return rc;
 }
 
-// what the two getters of the common neighbour analysis need; returns 0 or the error code
-int md_cna_ready(ta_context *h, const char *who) {
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, std::string(who) + ": no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, std::string(who) + " called before ta_md_init");
-  if (!h->md.cna.on) return fail(h, TA_ERR_INVALID, std::string(who) + ": the common neighbour analysis is off (ta_md_set_cna)");
-  if (!h->md.cna.sched.valid)
-    return fail(h, TA_ERR_INVALID, std::string(who) + ": a ta_md_run failed and left the data invalid; call "
-                                   "ta_md_set_cna or ta_md_init again");
-  return TA_OK;
+// the neighbour-list view of launch `k` of a run, for any launch struct that reads the resident list: the state and the
+// (skin) list of the batch, not the exact one filtered from it (a rebuild may have moved them: taken at every launch)
+template <typename L>
+void point_at_list(const ta_context *h, L &l, int k) {
+  l.pos = h->db.pos;
+  l.cells = h->db.cells;
+  l.species = h->db.species;
+  l.atom_start = h->db.atom_start;
+  l.pair_start = h->pair_start.ptr;
+  l.pair_j = h->pair_j.ptr;
+  l.pair_shift = h->pair_shift.ptr;
+  l.seq = (unsigned)k;
+}
+
+// the four words every sampler's getter begins its info with: samples taken, `size` (the feature's), sample_every, the
+// step of the newest sample
+void fill_info(int64_t *info, const MdSampler &x, int64_t size) {
+  info[0] = x.sched.taken();
+  info[1] = size;
+  info[2] = x.sched.every;
+  info[3] = x.sched.last;
+}
+
+// The held rows of a series ring (`n_rows` rows of `row` words; sample n is in row n % n_rows), oldest first, to
+// `series` and their steps to `steps` (either may be null). Returns the rows held.
+template <typename T>
+int64_t copy_series(const MdSampler &x, const DevBuf<T> &ring, int64_t n_rows, size_t row, int64_t *series, int64_t *steps) {
+  static_assert(sizeof(T) == sizeof(int64_t), "the rows are copied as they are");
+  const int64_t taken = x.sched.taken(), held = std::min(taken, n_rows);
+  for (int64_t j = 0; j < held; ++j) {
+    const int64_t idx = taken - held + j;  // sample number
+    if (series && row)
+      HIP_CHECK(hipMemcpy(series + (size_t)j * row, ring.ptr + (size_t)(idx % n_rows) * row, row * sizeof(int64_t),
+                          hipMemcpyDeviceToHost));
+    if (steps) steps[j] = x.sched.step(idx);
+  }
+  return held;
 }
 
 }  // namespace
@@ -353,7 +348,7 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
   if (velocities)
     for (size_t i = 0; i < 3 * N; ++i)
       if (!std::isfinite(velocities[i])) return fail(h, TA_ERR_INVALID, "ta_md_init: non-finite velocity");
-  bool ring_nomem = false, rdf_nomem = false, adf_nomem = false, order_nomem = false, cluster_nomem = false, cna_nomem = false, sq_nomem = false;
+  const ta::MdSamplerText *nomem = nullptr;  // of the first sampler, in their canonical order, that found no room
   // (a batch the wave vectors are not defined for: the feature goes off, as when there is no room for it)
   const bool sq_unfit = h->md.sq.on && md_sq_frames(h) != TA_OK;
   const std::string sq_why = sq_unfit ? h->err : std::string();
@@ -385,55 +380,20 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
     h->res.blk_start_host.clear();
     md.step = 0;
     md.baro.rec_valid = false;
-    if (md.corr.on && !md_sampling_alloc(h, md.corr.p)) {  // an empty ring for this batch, or none
-      md.corr.on = false;
-      ring_nomem = true;
-    }
-    if (md.rdf.on && !md_rdf_alloc(h, md.rdf.p)) {  // zero counts for this batch, or none
-      md.rdf.on = false;
-      rdf_nomem = true;
-    }
-    if (md.adf.on && !md_adf_alloc(h, md.adf.p, md.adf.rb)) {  // likewise
-      md.adf.on = false;
-      adf_nomem = true;
-    }
-    if (md.order.on && !md_order_alloc(h, md.order.p, md.order.rb)) {  // likewise
-      md.order.on = false;
-      order_nomem = true;
-    }
-    if (md.cluster.on && !md_cluster_alloc(h, md.cluster.p, md.cluster.rl)) {  // likewise
-      md.cluster.on = false;
-      cluster_nomem = true;
-    }
-    if (md.cna.on && !md_cna_alloc(h, md.cna.p)) {  // likewise
-      md.cna.on = false;
-      cna_nomem = true;
-    }
-    if (md.sq.on && sq_unfit) {
-      md.sq.on = false;
-      HIP_CHECK(hipStreamSynchronize(h->stream));
-      md.sq.release();
-    }
-    if (md.sq.on && !md_sq_alloc(h, md.sq.p, md.sq.miller)) {  // an empty ring for this batch, or none
-      md.sq.on = false;
-      sq_nomem = true;
-    }
+    for_each_sampler(md, [&](auto &x) {  // empty buffers for this batch from the stored setting, or none
+      if (sq_unfit && static_cast<MdSampler *>(&x) == &md.sq) {
+        x.on = false;
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        x.release();
+      }
+      if (x.on && !md_alloc(h, x, x.set)) {
+        x.on = false;
+        if (!nomem) nomem = &x.text;
+      }
+    });
     md.valid = true;
   });
-  if (rc == TA_OK && ring_nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the rings of ta_md_set_sampling; sampling is off");
-  if (rc == TA_OK && rdf_nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the counts of ta_md_set_rdf; the feature is off");
-  if (rc == TA_OK && adf_nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the counts of ta_md_set_adf; the feature is off");
-  if (rc == TA_OK && order_nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the buffers of ta_md_set_order; the feature is off");
-  if (rc == TA_OK && cluster_nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the buffers of ta_md_set_clusters; the feature is off");
-  if (rc == TA_OK && cna_nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the buffers of ta_md_set_cna; the feature is off");
-  if (rc == TA_OK && sq_nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_init: no device memory for the buffers of ta_md_set_sq; the feature is off");
+  if (rc == TA_OK && nomem) return fail(h, TA_ERR_NOMEM, ta::md_text_init_nomem(*nomem));
   if (rc == TA_OK && sq_unfit) return fail(h, TA_ERR_INVALID, "ta_md_init: " + sq_why + "; the feature is off");
   return rc;
 }
@@ -551,8 +511,7 @@ int ta_md_set_chain(ta_handle h, const double *eta, const double *veta) {
 
 int ta_md_get_chain_records(ta_handle h, double *e_chain) {
   if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_chain_records: no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_get_chain_records called before ta_md_init");
+  if (const int rc = md_resident(h, "ta_md_get_chain_records")) return rc;
   if (!h->md.nhc.rec_valid)
     return fail(h, TA_ERR_INVALID, "ta_md_get_chain_records: the last ta_md_run of this batch had no Nose-Hoover chain");
   const std::vector<double> &rec = h->md.nhc.rec_host;
@@ -562,58 +521,32 @@ int ta_md_get_chain_records(ta_handle h, double *e_chain) {
 
 int ta_md_set_sampling(ta_handle h, const ta_md_sampling_params *p) {
   if (!h) return TA_ERR_INVALID;
-  auto &corr = h->md.corr;
-  if (!p || p->n_lags == 0) {
-    corr.on = false;
-    return guarded(h, [&]() {
-      HIP_CHECK(hipStreamSynchronize(h->stream));
-      corr.release();
-    });
-  }
+  if (!p || p->n_lags == 0) return md_sampler_off(h, h->md.corr);
   if (p->n_lags < 0 || p->n_lags > TA_MD_MAX_LAGS)
     return fail(h, TA_ERR_INVALID, "ta_md_set_sampling: n_lags must be 0 .. " + std::to_string(TA_MD_MAX_LAGS));
   if (p->sample_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_set_sampling: sample_every must be >= 1");
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_sampling: no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_set_sampling called before ta_md_init");
-  bool nomem = false;
-  const int rc = guarded(h, [&]() {
-    corr.on = false;  // (until the rings exist)
-    nomem = !md_sampling_alloc(h, *p);
-    if (!nomem) {
-      corr.p = *p;
-      corr.on = true;
-    }
-  });
-  if (rc == TA_OK && nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_set_sampling: no device memory for rings of n_lags = " + std::to_string(p->n_lags) +
-                                 " snapshots; sampling is off");
-  return rc;
+  return md_sampler_set(h, h->md.corr, {*p}, "rings of n_lags = " + std::to_string(p->n_lags) + " snapshots");
 }
 
 int ta_md_get_correlations(ta_handle h, double *vacf_sum, double *msd_sum, int64_t *info) {
   if (!h) return TA_ERR_INVALID;
-  if (const int rc = md_samples_ready(h, "ta_md_get_correlations")) return rc;
+  if (const int rc = md_sampler_ready(h, h->md.corr, "ta_md_get_correlations")) return rc;
   return guarded(h, [&]() {
     const auto &corr = h->md.corr;
-    const size_t n = h->keep_natoms.size() * (size_t)h->n_elements * (size_t)corr.p.n_lags;
+    const size_t n = h->keep_natoms.size() * (size_t)h->n_elements * (size_t)corr.set.p.n_lags;
     HIP_CHECK(hipStreamSynchronize(h->stream));
     if (vacf_sum && n) HIP_CHECK(hipMemcpy(vacf_sum, corr.acc.ptr, n * sizeof(double), hipMemcpyDeviceToHost));
     if (msd_sum && n) HIP_CHECK(hipMemcpy(msd_sum, corr.acc.ptr + n, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (info) {
-      info[0] = corr.sched.taken();
-      info[1] = corr.p.n_lags;
-      info[2] = corr.p.sample_every;
-      info[3] = corr.sched.last;
-    }
+    if (info) fill_info(info, corr, corr.set.p.n_lags);
   });
 }
 
 int ta_md_get_samples(ta_handle h, int32_t first_lag, int32_t n, double *positions, double *velocities,
                       int64_t *steps) {
   if (!h) return TA_ERR_INVALID;
-  if (const int rc = md_samples_ready(h, "ta_md_get_samples")) return rc;
+  if (const int rc = md_sampler_ready(h, h->md.corr, "ta_md_get_samples")) return rc;
   const auto &corr = h->md.corr;
-  const int64_t taken = corr.sched.taken(), L = corr.p.n_lags, held = std::min(taken, L);
+  const int64_t taken = corr.sched.taken(), L = corr.set.p.n_lags, held = std::min(taken, L);
   if (first_lag < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_samples: first_lag must be >= 0");
   if (n < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_samples: n must be >= 0");
   if ((int64_t)first_lag + n > held)
@@ -636,14 +569,7 @@ int ta_md_get_samples(ta_handle h, int32_t first_lag, int32_t n, double *positio
 
 int ta_md_set_rdf(ta_handle h, const ta_md_rdf_params *p) {
   if (!h) return TA_ERR_INVALID;
-  auto &rdf = h->md.rdf;
-  if (!p || p->n_bins == 0) {
-    rdf.on = false;
-    return guarded(h, [&]() {
-      HIP_CHECK(hipStreamSynchronize(h->stream));
-      rdf.release();
-    });
-  }
+  if (!p || p->n_bins == 0) return md_sampler_off(h, h->md.rdf);
   if (p->n_bins < 0 || p->n_bins > TA_MD_MAX_BINS)
     return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: n_bins must be 0 .. " + std::to_string(TA_MD_MAX_BINS));
   if (p->sample_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: sample_every must be >= 1");
@@ -652,115 +578,50 @@ int ta_md_set_rdf(ta_handle h, const ta_md_rdf_params *p) {
   if (p->r_max > h->rmax)
     return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: r_max = " + std::to_string(p->r_max) + " exceeds the model's cutoff max(rcut, acut) = " +
                                    std::to_string(h->rmax) + "; the neighbour list is not complete beyond that");
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_rdf: no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_set_rdf called before ta_md_init");
-  bool nomem = false;
-  const int rc = guarded(h, [&]() {
-    rdf.on = false;  // (until the counts exist)
-    nomem = !md_rdf_alloc(h, *p);
-    if (!nomem) {
-      rdf.p = *p;
-      rdf.on = true;
-    }
-  });
-  if (rc == TA_OK && nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_set_rdf: no device memory for counts of n_bins = " + std::to_string(p->n_bins) +
-                                 "; the feature is off");
-  return rc;
+  return md_sampler_set(h, h->md.rdf, {*p}, "counts of n_bins = " + std::to_string(p->n_bins));
 }
 
 int ta_md_get_rdf(ta_handle h, int64_t *counts, int64_t *info, double *r_max) {
   if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_rdf: no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_get_rdf called before ta_md_init");
   const auto &rdf = h->md.rdf;
-  if (!rdf.on) return fail(h, TA_ERR_INVALID, "ta_md_get_rdf: the pair distributions are off (ta_md_set_rdf)");
-  if (!rdf.sched.valid)
-    return fail(h, TA_ERR_INVALID, "ta_md_get_rdf: a ta_md_run failed and left the counts invalid; call ta_md_set_rdf or "
-                                   "ta_md_init again");
+  if (const int rc = md_sampler_ready(h, rdf, "ta_md_get_rdf")) return rc;
   return guarded(h, [&]() {
-    const size_t E = (size_t)h->n_elements, n = h->keep_natoms.size() * E * E * (size_t)rdf.p.n_bins;
+    const size_t E = (size_t)h->n_elements, n = h->keep_natoms.size() * E * E * (size_t)rdf.set.p.n_bins;
     HIP_CHECK(hipStreamSynchronize(h->stream));
-    static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the counts are copied as they are");
     if (counts && n) HIP_CHECK(hipMemcpy(counts, rdf.acc.ptr, n * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (info) {
-      info[0] = rdf.sched.taken();
-      info[1] = rdf.p.n_bins;
-      info[2] = rdf.p.sample_every;
-      info[3] = rdf.sched.last;
-    }
-    if (r_max) *r_max = rdf.p.r_max;
+    if (info) fill_info(info, rdf, rdf.set.p.n_bins);
+    if (r_max) *r_max = rdf.set.p.r_max;
   });
 }
 
 int ta_md_set_adf(ta_handle h, const ta_md_adf_params *p, const double *r_bond_pairs) {
   if (!h) return TA_ERR_INVALID;
-  auto &adf = h->md.adf;
-  if (!p || p->n_bins == 0) {
-    adf.on = false;
-    return guarded(h, [&]() {
-      HIP_CHECK(hipStreamSynchronize(h->stream));
-      adf.release();
-    });
-  }
+  if (!p || p->n_bins == 0) return md_sampler_off(h, h->md.adf);
   if (p->n_bins < 0 || p->n_bins > TA_MD_MAX_BINS)
     return fail(h, TA_ERR_INVALID, "ta_md_set_adf: n_bins must be 0 .. " + std::to_string(TA_MD_MAX_BINS));
   if (p->sample_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_set_adf: sample_every must be >= 1");
   std::vector<double> rb;
   if (const int bad = md_bond_cutoffs(h, "ta_md_set_adf", p->r_bond, r_bond_pairs, rb)) return bad;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_adf: no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_set_adf called before ta_md_init");
-  bool nomem = false;
-  const int rc = guarded(h, [&]() {
-    adf.on = false;  // (until the counts exist)
-    nomem = !md_adf_alloc(h, *p, rb);
-    if (!nomem) {
-      adf.p = *p;
-      adf.rb = rb;
-      adf.on = true;
-    }
-  });
-  if (rc == TA_OK && nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_set_adf: no device memory for counts of n_bins = " + std::to_string(p->n_bins) +
-                                 "; the feature is off");
-  return rc;
+  return md_sampler_set(h, h->md.adf, {*p, rb}, "counts of n_bins = " + std::to_string(p->n_bins));
 }
 
 int ta_md_get_adf(ta_handle h, int64_t *counts, int64_t *info, double *r_bond_pairs) {
   if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_adf: no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_get_adf called before ta_md_init");
   const auto &adf = h->md.adf;
-  if (!adf.on) return fail(h, TA_ERR_INVALID, "ta_md_get_adf: the bond-angle distributions are off (ta_md_set_adf)");
-  if (!adf.sched.valid)
-    return fail(h, TA_ERR_INVALID, "ta_md_get_adf: a ta_md_run failed and left the counts invalid; call ta_md_set_adf or "
-                                   "ta_md_init again");
+  if (const int rc = md_sampler_ready(h, adf, "ta_md_get_adf")) return rc;
   return guarded(h, [&]() {
     const size_t E = (size_t)h->n_elements;
-    const size_t n = h->keep_natoms.size() * E * (E * (E + 1) / 2) * (size_t)adf.p.n_bins;
+    const size_t n = h->keep_natoms.size() * E * (E * (E + 1) / 2) * (size_t)adf.set.p.n_bins;
     HIP_CHECK(hipStreamSynchronize(h->stream));
-    static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the counts are copied as they are");
     if (counts && n) HIP_CHECK(hipMemcpy(counts, adf.acc.ptr, n * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (info) {
-      info[0] = adf.sched.taken();
-      info[1] = adf.p.n_bins;
-      info[2] = adf.p.sample_every;
-      info[3] = adf.sched.last;
-    }
-    if (r_bond_pairs) std::memcpy(r_bond_pairs, adf.rb.data(), E * E * sizeof(double));
+    if (info) fill_info(info, adf, adf.set.p.n_bins);
+    if (r_bond_pairs) std::memcpy(r_bond_pairs, adf.set.rb.data(), E * E * sizeof(double));
   });
 }
 
 int ta_md_set_order(ta_handle h, const ta_md_order_params *p, const double *r_bond_pairs) {
   if (!h) return TA_ERR_INVALID;
-  auto &order = h->md.order;
-  if (!p || p->n_bins == 0) {
-    order.on = false;
-    return guarded(h, [&]() {
-      HIP_CHECK(hipStreamSynchronize(h->stream));
-      order.release();
-    });
-  }
+  if (!p || p->n_bins == 0) return md_sampler_off(h, h->md.order);
   if (p->n_bins < 0 || p->n_bins > TA_MD_MAX_BINS)
     return fail(h, TA_ERR_INVALID, "ta_md_set_order: n_bins must be 0 .. " + std::to_string(TA_MD_MAX_BINS));
   if (p->sample_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_set_order: sample_every must be >= 1");
@@ -783,59 +644,38 @@ int ta_md_set_order(ta_handle h, const ta_md_order_params *p, const double *r_bo
     return fail(h, TA_ERR_INVALID, "ta_md_set_order: solid_threshold must be a finite number inside (-1, 1)");
   std::vector<double> rb;
   if (const int bad = md_bond_cutoffs(h, "ta_md_set_order", p->r_bond, r_bond_pairs, rb)) return bad;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_order: no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_set_order called before ta_md_init");
-  bool nomem = false;
-  const int rc = guarded(h, [&]() {
-    order.on = false;  // (until the buffers exist)
-    ta_md_order_params clean = *p;
-    for (int d = p->n_degrees; d < TA_MD_ORDER_MAX_DEGREES; ++d) clean.degrees[d] = 0;
-    nomem = !md_order_alloc(h, clean, rb);
-    if (!nomem) {
-      order.p = clean;
-      order.rb = rb;
-      order.on = true;
-    }
-  });
-  if (rc == TA_OK && nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_set_order: no device memory for buffers of n_bins = " + std::to_string(p->n_bins) +
-                                 "; the feature is off");
-  return rc;
+  ta_md_order_params clean = *p;
+  for (int d = p->n_degrees; d < TA_MD_ORDER_MAX_DEGREES; ++d) clean.degrees[d] = 0;
+  return md_sampler_set(h, h->md.order, {clean, rb}, "buffers of n_bins = " + std::to_string(p->n_bins));
 }
 
 int ta_md_get_order(ta_handle h, int64_t *hist_q, int64_t *hist_qbar, int64_t *hist_conn, int64_t *info,
                     double *r_bond_pairs) {
   if (!h) return TA_ERR_INVALID;
-  if (const int bad = md_order_ready(h, "ta_md_get_order")) return bad;
+  if (const int bad = md_sampler_ready(h, h->md.order, "ta_md_get_order")) return bad;
   const auto &order = h->md.order;
   return guarded(h, [&]() {
     const size_t E = (size_t)h->n_elements, F = h->keep_natoms.size();
-    const size_t n_hist = F * E * (size_t)order.p.n_degrees * (size_t)order.p.n_bins;
+    const size_t n_hist = F * E * (size_t)order.set.p.n_degrees * (size_t)order.set.p.n_bins;
     const size_t n_conn = F * E * (TA_MD_ORDER_MAX_CONN + 1);
     HIP_CHECK(hipStreamSynchronize(h->stream));
-    static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the counts are copied as they are");
     if (hist_q && n_hist) HIP_CHECK(hipMemcpy(hist_q, order.acc.ptr, n_hist * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (hist_qbar && n_hist)
       HIP_CHECK(hipMemcpy(hist_qbar, order.acc.ptr + n_hist, n_hist * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (hist_conn && n_conn)
       HIP_CHECK(hipMemcpy(hist_conn, order.acc.ptr + 2 * n_hist, n_conn * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (info) {
-      info[0] = order.sched.taken();
-      info[1] = order.p.n_bins;
-      info[2] = order.p.sample_every;
-      info[3] = order.sched.last;
-    }
-    if (r_bond_pairs) std::memcpy(r_bond_pairs, order.rb.data(), E * E * sizeof(double));
+    if (info) fill_info(info, order, order.set.p.n_bins);
+    if (r_bond_pairs) std::memcpy(r_bond_pairs, order.set.rb.data(), E * E * sizeof(double));
   });
 }
 
 int ta_md_get_order_atoms(ta_handle h, double *q, double *qbar, int32_t *n_bonds, int32_t *n_conn, double *qlm) {
   if (!h) return TA_ERR_INVALID;
-  if (const int bad = md_order_ready(h, "ta_md_get_order_atoms")) return bad;
+  if (const int bad = md_sampler_ready(h, h->md.order, "ta_md_get_order_atoms")) return bad;
   const auto &order = h->md.order;
   if (order.sched.last < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_order_atoms: no sample has been taken yet");
   return guarded(h, [&]() {
-    const size_t N = h->keep_species.size(), D = (size_t)order.p.n_degrees, M = (size_t)order.n_lm;
+    const size_t N = h->keep_species.size(), D = (size_t)order.set.p.n_degrees, M = (size_t)order.n_lm;
     HIP_CHECK(hipStreamSynchronize(h->stream));
     if (!N) return;
     if (q) HIP_CHECK(hipMemcpy(q, order.per_atom.ptr, N * D * sizeof(double), hipMemcpyDeviceToHost));
@@ -848,14 +688,7 @@ int ta_md_get_order_atoms(ta_handle h, double *q, double *qbar, int32_t *n_bonds
 
 int ta_md_set_clusters(ta_handle h, const ta_md_cluster_params *p, const double *r_link_pairs) {
   if (!h) return TA_ERR_INVALID;
-  auto &cluster = h->md.cluster;
-  if (!p || p->n_bins == 0) {
-    cluster.on = false;
-    return guarded(h, [&]() {
-      HIP_CHECK(hipStreamSynchronize(h->stream));
-      cluster.release();
-    });
-  }
+  if (!p || p->n_bins == 0) return md_sampler_off(h, h->md.cluster);
   if (p->n_bins < 0 || p->n_bins > TA_MD_MAX_BINS)
     return fail(h, TA_ERR_INVALID, "ta_md_set_clusters: n_bins must be 0 .. " + std::to_string(TA_MD_MAX_BINS));
   if (p->n_series < 1 || p->n_series > TA_MD_CLUSTER_MAX_SERIES)
@@ -870,58 +703,33 @@ int ta_md_set_clusters(ta_handle h, const ta_md_cluster_params *p, const double 
   std::vector<double> rl;
   const double r_link = !r_link_pairs && std::isnan(p->r_link) ? h->rmax : p->r_link;  // NaN: the model's cutoff
   if (const int bad = md_bond_cutoffs(h, "ta_md_set_clusters", r_link, r_link_pairs, rl, "r_link", "r_link_pairs")) return bad;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_clusters: no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_set_clusters called before ta_md_init");
-  bool nomem = false;
-  const int rc = guarded(h, [&]() {
-    cluster.on = false;  // (until the buffers exist)
-    nomem = !md_cluster_alloc(h, *p, rl);
-    if (!nomem) {
-      cluster.p = *p;
-      cluster.p.r_link = r_link;
-      cluster.rl = rl;
-      cluster.on = true;
-    }
-  });
-  if (rc == TA_OK && nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_set_clusters: no device memory for buffers of n_bins = " + std::to_string(p->n_bins) +
-                                 " and n_series = " + std::to_string(p->n_series) + "; the feature is off");
-  return rc;
+  ta_md_cluster_params clean = *p;
+  clean.r_link = r_link;
+  return md_sampler_set(h, h->md.cluster, {clean, rl}, "buffers of n_bins = " + std::to_string(p->n_bins) + " and n_series = " +
+                                                     std::to_string(p->n_series));
 }
 
 int ta_md_get_clusters(ta_handle h, int64_t *hist, int64_t *series, int64_t *steps, int64_t *info, double *r_link_pairs) {
   if (!h) return TA_ERR_INVALID;
-  if (const int bad = md_cluster_ready(h, "ta_md_get_clusters")) return bad;
+  if (const int bad = md_sampler_ready(h, h->md.cluster, "ta_md_get_clusters")) return bad;
   const auto &cluster = h->md.cluster;
   return guarded(h, [&]() {
-    const size_t E = (size_t)h->n_elements, F = h->keep_natoms.size(), n_hist = F * (size_t)cluster.p.n_bins;
-    const int64_t taken = cluster.sched.taken(), T = cluster.p.n_series, held = std::min(taken, T);
+    const size_t E = (size_t)h->n_elements, F = h->keep_natoms.size(), n_hist = F * (size_t)cluster.set.p.n_bins;
     HIP_CHECK(hipStreamSynchronize(h->stream));
-    static_assert(sizeof(int64_t) == sizeof(unsigned long long) && sizeof(int64_t) == sizeof(long long),
-                  "the counts and the rows are copied as they are");
     if (hist && n_hist) HIP_CHECK(hipMemcpy(hist, cluster.acc.ptr, n_hist * sizeof(int64_t), hipMemcpyDeviceToHost));
-    for (int64_t j = 0; j < held; ++j) {  // oldest first
-      const int64_t idx = taken - held + j;  // sample number
-      if (series && F)
-        HIP_CHECK(hipMemcpy(series + (size_t)j * F * 4, cluster.series.ptr + (size_t)(idx % T) * F * 4,
-                            F * 4 * sizeof(int64_t), hipMemcpyDeviceToHost));
-      if (steps) steps[j] = cluster.sched.step(idx);
-    }
+    const int64_t held = copy_series(cluster, cluster.series, cluster.set.p.n_series, F * 4, series, steps);
     if (info) {
-      info[0] = taken;
-      info[1] = cluster.p.n_bins;
-      info[2] = cluster.p.sample_every;
-      info[3] = cluster.sched.last;
+      fill_info(info, cluster, cluster.set.p.n_bins);
       info[4] = held;
-      info[5] = T;
+      info[5] = cluster.set.p.n_series;
     }
-    if (r_link_pairs) std::memcpy(r_link_pairs, cluster.rl.data(), E * E * sizeof(double));
+    if (r_link_pairs) std::memcpy(r_link_pairs, cluster.set.rl.data(), E * E * sizeof(double));
   });
 }
 
 int ta_md_get_cluster_atoms(ta_handle h, int32_t *label, int32_t *size) {
   if (!h) return TA_ERR_INVALID;
-  if (const int bad = md_cluster_ready(h, "ta_md_get_cluster_atoms")) return bad;
+  if (const int bad = md_sampler_ready(h, h->md.cluster, "ta_md_get_cluster_atoms")) return bad;
   const auto &cluster = h->md.cluster;
   if (cluster.sched.last < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_cluster_atoms: no sample has been taken yet");
   return guarded(h, [&]() {
@@ -935,14 +743,7 @@ int ta_md_get_cluster_atoms(ta_handle h, int32_t *label, int32_t *size) {
 
 int ta_md_set_cna(ta_handle h, const ta_md_cna_params *p) {
   if (!h) return TA_ERR_INVALID;
-  auto &cna = h->md.cna;
-  if (!p || p->n_series == 0) {
-    cna.on = false;
-    return guarded(h, [&]() {
-      HIP_CHECK(hipStreamSynchronize(h->stream));
-      cna.release();
-    });
-  }
+  if (!p || p->n_series == 0) return md_sampler_off(h, h->md.cna);
   if (p->mode != TA_MD_CNA_ADAPTIVE && p->mode != TA_MD_CNA_FIXED)
     return fail(h, TA_ERR_INVALID, "ta_md_set_cna: mode = " + std::to_string(p->mode) + " must be TA_MD_CNA_ADAPTIVE (0) or "
                                    "TA_MD_CNA_FIXED (1)");
@@ -958,56 +759,31 @@ int ta_md_set_cna(ta_handle h, const ta_md_cna_params *p) {
     return fail(h, TA_ERR_INVALID, std::string("ta_md_set_cna: ") + name + " = " + std::to_string(r) +
                                    " exceeds the model's cutoff max(rcut, acut) = " + std::to_string(h->rmax) +
                                    "; the neighbour list is not complete beyond that");
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_cna: no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_set_cna called before ta_md_init");
-  bool nomem = false;
-  const int rc = guarded(h, [&]() {
-    cna.on = false;  // (until the buffers exist)
-    nomem = !md_cna_alloc(h, *p);
-    if (!nomem) {
-      cna.p = *p;
-      if (fixed) cna.p.r_max = 0.0; else cna.p.r_max = r, cna.p.r_cut = 0.0;
-      cna.on = true;
-    }
-  });
-  if (rc == TA_OK && nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_set_cna: no device memory for buffers of n_series = " + std::to_string(p->n_series) +
-                                 "; the feature is off");
-  return rc;
+  ta_md_cna_params clean = *p;
+  if (fixed) clean.r_max = 0.0; else clean.r_max = r, clean.r_cut = 0.0;
+  return md_sampler_set(h, h->md.cna, {clean}, "buffers of n_series = " + std::to_string(p->n_series));
 }
 
 int ta_md_get_cna(ta_handle h, int64_t *counts, int64_t *series, int64_t *steps, int64_t *info) {
   if (!h) return TA_ERR_INVALID;
-  if (const int bad = md_cna_ready(h, "ta_md_get_cna")) return bad;
+  if (const int bad = md_sampler_ready(h, h->md.cna, "ta_md_get_cna")) return bad;
   const auto &cna = h->md.cna;
   return guarded(h, [&]() {
     const size_t E = (size_t)h->n_elements, F = h->keep_natoms.size(), n_acc = F * E * TA_MD_CNA_TYPES;
-    const size_t row = F * TA_MD_CNA_TYPES;
-    const int64_t taken = cna.sched.taken(), T = cna.p.n_series, held = std::min(taken, T);
     HIP_CHECK(hipStreamSynchronize(h->stream));
-    static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the counts and the rows are copied as they are");
     if (counts && n_acc) HIP_CHECK(hipMemcpy(counts, cna.acc.ptr, n_acc * sizeof(int64_t), hipMemcpyDeviceToHost));
-    for (int64_t j = 0; j < held; ++j) {  // oldest first
-      const int64_t idx = taken - held + j;  // sample number
-      if (series && row)
-        HIP_CHECK(hipMemcpy(series + (size_t)j * row, cna.series.ptr + (size_t)(idx % T) * row, row * sizeof(int64_t),
-                            hipMemcpyDeviceToHost));
-      if (steps) steps[j] = cna.sched.step(idx);
-    }
+    const int64_t held = copy_series(cna, cna.series, cna.set.p.n_series, F * TA_MD_CNA_TYPES, series, steps);
     if (info) {
-      info[0] = taken;
-      info[1] = cna.p.mode;
-      info[2] = cna.p.sample_every;
-      info[3] = cna.sched.last;
+      fill_info(info, cna, cna.set.p.mode);
       info[4] = held;
-      info[5] = T;
+      info[5] = cna.set.p.n_series;
     }
   });
 }
 
 int ta_md_get_cna_atoms(ta_handle h, int32_t *structure, double *r_local) {
   if (!h) return TA_ERR_INVALID;
-  if (const int bad = md_cna_ready(h, "ta_md_get_cna_atoms")) return bad;
+  if (const int bad = md_sampler_ready(h, h->md.cna, "ta_md_get_cna_atoms")) return bad;
   const auto &cna = h->md.cna;
   if (cna.sched.last < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_cna_atoms: no sample has been taken yet");
   return guarded(h, [&]() {
@@ -1021,14 +797,7 @@ int ta_md_get_cna_atoms(ta_handle h, int32_t *structure, double *r_local) {
 
 int ta_md_set_sq(ta_handle h, const ta_md_sq_params *p, const int32_t *miller) {
   if (!h) return TA_ERR_INVALID;
-  auto &sq = h->md.sq;
-  if (!p || p->n_q == 0) {
-    sq.on = false;
-    return guarded(h, [&]() {
-      HIP_CHECK(hipStreamSynchronize(h->stream));
-      sq.release();
-    });
-  }
+  if (!p || p->n_q == 0) return md_sampler_off(h, h->md.sq);
   if (p->n_q < 0 || p->n_q > TA_MD_SQ_MAX_Q)
     return fail(h, TA_ERR_INVALID, "ta_md_set_sq: n_q must be 0 .. " + std::to_string(TA_MD_SQ_MAX_Q));
   if (p->n_lags < 1 || p->n_lags > TA_MD_MAX_LAGS)
@@ -1040,67 +809,52 @@ int ta_md_set_sq(ta_handle h, const ta_md_sq_params *p, const int32_t *miller) {
     if (miller[j] < -TA_MD_SQ_MAX_INDEX || miller[j] > TA_MD_SQ_MAX_INDEX)
       return fail(h, TA_ERR_INVALID, "ta_md_set_sq: miller[" + std::to_string(j / 3) + "][" + std::to_string(j % 3) + "] = " +
                                      std::to_string(miller[j]) + " must be within +-" + std::to_string(TA_MD_SQ_MAX_INDEX));
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_set_sq: no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_set_sq called before ta_md_init");
-  if (const int bad = md_sq_frames(h)) return bad;
-  bool nomem = false;
   const std::vector<int32_t> triples(miller, miller + 3 * (size_t)p->n_q);
-  const int rc = guarded(h, [&]() {
-    sq.on = false;  // (until the buffers exist)
-    nomem = !md_sq_alloc(h, *p, triples);
-    if (!nomem) {
-      sq.p = *p;
-      sq.miller = triples;
-      sq.on = true;
-    }
-  });
-  if (rc == TA_OK && nomem)
-    return fail(h, TA_ERR_NOMEM, "ta_md_set_sq: no device memory for n_q = " + std::to_string(p->n_q) + " vectors at n_lags = " +
-                                 std::to_string(p->n_lags) + "; the feature is off");
-  return rc;
+  return md_sampler_set(h, h->md.sq, {*p, triples}, "n_q = " + std::to_string(p->n_q) + " vectors at n_lags = " + std::to_string(p->n_lags),
+                        md_sq_frames);
 }
 
 int ta_md_get_sq(ta_handle h, double *a_rho, double *a_l, double *a_j, int64_t *info, int32_t *miller) {
   if (!h) return TA_ERR_INVALID;
-  if (const int bad = md_sq_ready(h, "ta_md_get_sq")) return bad;
+  if (const int bad = md_sampler_ready(h, h->md.sq, "ta_md_get_sq")) return bad;
   const auto &sq = h->md.sq;
-  if ((a_l || a_j) && !sq.p.currents)
+  if ((a_l || a_j) && !sq.set.p.currents)
     return fail(h, TA_ERR_INVALID, "ta_md_get_sq: a_l and a_j need the currents (ta_md_sq_params.currents = 1)");
   return guarded(h, [&]() {
     const size_t E = (size_t)h->n_elements;
-    const size_t n = h->keep_natoms.size() * E * E * (size_t)sq.p.n_lags * (size_t)sq.p.n_q;
+    const size_t n = h->keep_natoms.size() * E * E * (size_t)sq.set.p.n_lags * (size_t)sq.set.p.n_q;
     HIP_CHECK(hipStreamSynchronize(h->stream));
     if (a_rho && n) HIP_CHECK(hipMemcpy(a_rho, sq.acc.ptr, n * sizeof(double), hipMemcpyDeviceToHost));
     if (a_l && n) HIP_CHECK(hipMemcpy(a_l, sq.acc.ptr + n, n * sizeof(double), hipMemcpyDeviceToHost));
     if (a_j && n) HIP_CHECK(hipMemcpy(a_j, sq.acc.ptr + 2 * n, n * sizeof(double), hipMemcpyDeviceToHost));
     if (info) {
       info[0] = sq.sched.taken();
-      info[1] = sq.p.n_q;
-      info[2] = sq.p.n_lags;
-      info[3] = sq.p.sample_every;
+      info[1] = sq.set.p.n_q;
+      info[2] = sq.set.p.n_lags;
+      info[3] = sq.set.p.sample_every;
       info[4] = sq.sched.last;
-      info[5] = sq.p.currents;
+      info[5] = sq.set.p.currents;
       info[6] = sq.chunk;
       info[7] = 0;
     }
-    if (miller) std::memcpy(miller, sq.miller.data(), sq.miller.size() * sizeof(int32_t));
+    if (miller) std::memcpy(miller, sq.set.miller.data(), sq.set.miller.size() * sizeof(int32_t));
   });
 }
 
 int ta_md_get_sq_amplitudes(ta_handle h, int32_t first_lag, int32_t n, double *rho, double *cur, int64_t *steps) {
   if (!h) return TA_ERR_INVALID;
-  if (const int bad = md_sq_ready(h, "ta_md_get_sq_amplitudes")) return bad;
+  if (const int bad = md_sampler_ready(h, h->md.sq, "ta_md_get_sq_amplitudes")) return bad;
   const auto &sq = h->md.sq;
-  const int64_t taken = sq.sched.taken(), L = sq.p.n_lags, held = std::min(taken, L);
+  const int64_t taken = sq.sched.taken(), L = sq.set.p.n_lags, held = std::min(taken, L);
   if (first_lag < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_sq_amplitudes: first_lag must be >= 0");
   if (n < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_sq_amplitudes: n must be >= 0");
   if ((int64_t)first_lag + n > held)
     return fail(h, TA_ERR_INVALID, "ta_md_get_sq_amplitudes: first_lag + n = " + std::to_string((int64_t)first_lag + n) +
                                    " exceeds the " + std::to_string(held) + " rows held (min(n_samples, n_lags))");
-  if (cur && !sq.p.currents)
+  if (cur && !sq.set.p.currents)
     return fail(h, TA_ERR_INVALID, "ta_md_get_sq_amplitudes: cur needs the currents (ta_md_sq_params.currents = 1)");
   return guarded(h, [&]() {
-    const size_t FE = h->keep_natoms.size() * (size_t)h->n_elements, Q = (size_t)sq.p.n_q, P = sq.p.currents ? 8 : 2;
+    const size_t FE = h->keep_natoms.size() * (size_t)h->n_elements, Q = (size_t)sq.set.p.n_q, P = sq.set.p.currents ? 8 : 2;
     const size_t row = FE * P * Q;
     HIP_CHECK(hipStreamSynchronize(h->stream));
     std::vector<double> buf(row);
@@ -1125,8 +879,7 @@ int ta_md_get_sq_amplitudes(ta_handle h, int32_t first_lag, int32_t n, double *r
 int ta_md_noise(ta_handle h, int64_t step, double *xi, double *eta) {
   if (!h) return TA_ERR_INVALID;
   if (!xi || !eta) return fail(h, TA_ERR_INVALID, "ta_md_noise: null argument");
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_noise: no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_noise called before ta_md_init");
+  if (const int rc = md_resident(h, "ta_md_noise")) return rc;
   if (step < 0) return fail(h, TA_ERR_INVALID, "ta_md_noise: step must be >= 0");
   return guarded(h, [&]() {
     const size_t N = h->keep_species.size();
@@ -1170,8 +923,7 @@ int ta_md_get_cell(ta_handle h, double *cells) {
 
 int ta_md_get_records(ta_handle h, double *volume, double *press) {
   if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_records: no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_get_records called before ta_md_init");
+  if (const int rc = md_resident(h, "ta_md_get_records")) return rc;
   const auto &baro = h->md.baro;
   if (!baro.rec_valid)
     return fail(h, TA_ERR_INVALID, "ta_md_get_records: the last ta_md_run of this batch had no barostat");
@@ -1224,17 +976,17 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     return fail(h, TA_ERR_INVALID, "ta_md_run: the structure factors (ta_md_set_sq) and the barostat (ta_md_set_barostat) are "
                                    "both on; cell and positions of a snapshot would belong to different states: switch one of "
                                    "them off");
-  if (md.cluster.on && md.cluster.p.n_min > 0) {  // n_conn of the order launches for the same state is read
+  if (md.cluster.on && md.cluster.set.p.n_min > 0) {  // n_conn of the order launches for the same state is read
     if (!md.order.on)
       return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and reads n_conn, but "
                                      "the bond-orientational order parameters (ta_md_set_order) are off");
     if (!md.order.sched.valid)
       return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and reads n_conn, but a "
                                      "ta_md_run failed and left the data of ta_md_set_order invalid; call ta_md_set_order again");
-    if (md.cluster.p.sample_every % md.order.p.sample_every != 0)
+    if (md.cluster.set.p.sample_every % md.order.set.p.sample_every != 0)
       return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and its sample_every = " +
-                                     std::to_string(md.cluster.p.sample_every) + " is no multiple of that of ta_md_set_order, " +
-                                     std::to_string(md.order.p.sample_every) + ": n_conn of a sampled state would be missing");
+                                     std::to_string(md.cluster.set.p.sample_every) + " is no multiple of that of ta_md_set_order, " +
+                                     std::to_string(md.order.set.p.sample_every) + ": n_conn of a sampled state would be missing");
     if (md.cluster.sched.origin < md.order.sched.origin)
       return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and its first sample, step " +
                                      std::to_string(md.cluster.sched.origin) + ", is in front of the first one of ta_md_set_order, "
@@ -1246,10 +998,7 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
   if (baro) want |= TA_WANT_VIRIAL;  // the pressure
   md.baro.rec_valid = false;
   md.nhc.rec_valid = false;
-  const bool corr_was_valid = md.corr.sched.suspend(), rdf_was_valid = md.rdf.sched.suspend();
-  const bool adf_was_valid = md.adf.sched.suspend(), order_was_valid = md.order.sched.suspend();
-  const bool sq_was_valid = md.sq.sched.suspend(), cluster_was_valid = md.cluster.sched.suspend();
-  const bool cna_was_valid = md.cna.sched.suspend();
+  for_each_sampler(md, [&](MdSampler &x) { x.begin_run(!h->keep_species.empty()); });
   res.cell_running = md.baro.running = baro;
   const int rc = guarded(h, [&]() {
     const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
@@ -1322,90 +1071,78 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     // Sampling: the launch of step k holds the whole-step state t = step0 + k and samples it when the schedule
     // says so (ta_schedule.h). Sample number and ring slot are functions of t alone, so the launches that returned
     // early behind a stale list and are enqueued again after the rebuild write what they would have written.
-    const bool sampling = md.corr.on && corr_was_valid && N > 0;
-    const ta::SampleSchedule &corr_sched = md.corr.sched;
-    const int64_t samp_L = md.corr.p.n_lags;
+    const int64_t samp_L = md.corr.set.p.n_lags;
     ta::MdCorrLaunch c;
     c.ring_x = md.corr.ring_x.ptr, c.ring_v = md.corr.ring_v.ptr;
     c.blk_start = md.corr.blk.ptr;
     c.part = md.corr.part.ptr;
     c.acc_v = md.corr.acc.ptr;
-    c.acc_x = sampling ? md.corr.acc.ptr + F * (size_t)h->n_elements * (size_t)samp_L : nullptr;
+    c.acc_x = md.corr.run ? md.corr.acc.ptr + F * (size_t)h->n_elements * (size_t)samp_L : nullptr;
     c.status = res.status.ptr;
     c.n_atoms = (long long)N;
-    c.n_lags = (int)samp_L, c.n_elements = h->n_elements, c.n_frames = (int)F, c.n_chunks = md.corr.n_chunks;
+    c.n_lags = (int)samp_L, c.n_elements = h->n_elements, c.n_frames = (int)F, c.n_chunks = md.corr.n_blk;
     // Pair distributions: the state t = step0 + k is counted by a launch IN FRONT OF the integrator launch of
     // step k, whose drift leaves x(t). With seq = k the integrator's predicate skips exactly the states that
     // were reached on a stale list; after the rebuild the launch is enqueued again with the rest and counts
     // then.
-    const bool rdf_run = md.rdf.on && rdf_was_valid && N > 0;
-    const ta::SampleSchedule &rdf_sched = md.rdf.sched;
     ta::MdRdfLaunch g;
     g.blk_start = md.rdf.blk.ptr;
     g.counts = md.rdf.acc.ptr;
     g.status = res.status.ptr;
-    g.n_bins = md.rdf.p.n_bins, g.n_elements = h->n_elements, g.n_frames = (int)F;
+    g.n_bins = md.rdf.set.p.n_bins, g.n_elements = h->n_elements, g.n_frames = (int)F;
     g.n_blk = md.rdf.n_blk, g.chunk = md.rdf.chunk;
-    g.dr = rdf_run ? md.rdf.p.r_max / (double)md.rdf.p.n_bins : 1.0;
+    g.dr = md.rdf.run ? md.rdf.set.p.r_max / (double)md.rdf.set.p.n_bins : 1.0;
     // Bond-angle distributions: a launch of their own in the same place, under the same predicate (no volume
     // enters, so they run under the barostat too: db.cells are those of the state t)
-    const bool adf_run = md.adf.on && adf_was_valid && N > 0;
-    const ta::SampleSchedule &adf_sched = md.adf.sched;
     ta::MdAdfLaunch t;
     t.blk_start = md.adf.blk.ptr;
     t.rb2 = md.adf.rb2.ptr;
     t.counts = md.adf.acc.ptr;
     t.status = res.status.ptr;
-    t.n_bins = md.adf.p.n_bins, t.n_elements = h->n_elements, t.n_frames = (int)F;
+    t.n_bins = md.adf.set.p.n_bins, t.n_elements = h->n_elements, t.n_frames = (int)F;
     t.n_blk = md.adf.n_blk, t.chunk = md.adf.chunk;
-    t.dtheta = adf_run ? M_PI / (double)md.adf.p.n_bins : 1.0;
+    t.dtheta = md.adf.run ? M_PI / (double)md.adf.set.p.n_bins : 1.0;
     // Bond-orientational order: its two launches in the same place, under the same predicate (no volume either)
-    const bool order_run = md.order.on && order_was_valid && N > 0;
-    const ta::SampleSchedule &order_sched = md.order.sched;
     ta::MdOrderLaunch o;
     o.blk_start = md.order.blk.ptr;
     o.rb2 = md.order.rb2.ptr;
     o.norm = md.order.norm.ptr;
     o.qlm = md.order.qlm.ptr;
     o.q = md.order.per_atom.ptr;
-    o.qbar = order_run ? md.order.per_atom.ptr + N * (size_t)md.order.p.n_degrees : nullptr;
+    o.qbar = md.order.run ? md.order.per_atom.ptr + N * (size_t)md.order.set.p.n_degrees : nullptr;
     o.n_bonds = md.order.per_atom_int.ptr;
-    o.n_conn = order_run ? md.order.per_atom_int.ptr + N : nullptr;
+    o.n_conn = md.order.run ? md.order.per_atom_int.ptr + N : nullptr;
     {
-      const size_t n_hist = F * (size_t)h->n_elements * (size_t)md.order.p.n_degrees * (size_t)md.order.p.n_bins;
+      const size_t n_hist = F * (size_t)h->n_elements * (size_t)md.order.set.p.n_degrees * (size_t)md.order.set.p.n_bins;
       o.hist_q = md.order.acc.ptr;
-      o.hist_qbar = order_run ? md.order.acc.ptr + n_hist : nullptr;
-      o.hist_conn = order_run ? md.order.acc.ptr + 2 * n_hist : nullptr;
+      o.hist_qbar = md.order.run ? md.order.acc.ptr + n_hist : nullptr;
+      o.hist_conn = md.order.run ? md.order.acc.ptr + 2 * n_hist : nullptr;
     }
     o.status = res.status.ptr;
-    o.n_bins = md.order.p.n_bins, o.n_elements = h->n_elements, o.n_frames = (int)F;
+    o.n_bins = md.order.set.p.n_bins, o.n_elements = h->n_elements, o.n_frames = (int)F;
     o.n_blk = md.order.n_blk, o.chunk = md.order.chunk;
-    o.n_degrees = md.order.p.n_degrees, o.n_lm = md.order.n_lm, o.solid = md.order.solid;
-    o.deg0 = md.order.p.degrees[0], o.deg1 = md.order.p.degrees[1], o.deg2 = md.order.p.degrees[2], o.deg3 = md.order.p.degrees[3];
-    o.threshold = md.order.p.solid_threshold;
+    o.n_degrees = md.order.set.p.n_degrees, o.n_lm = md.order.n_lm, o.solid = md.order.solid;
+    o.deg0 = md.order.set.p.degrees[0], o.deg1 = md.order.set.p.degrees[1], o.deg2 = md.order.set.p.degrees[2], o.deg3 = md.order.set.p.degrees[3];
+    o.threshold = md.order.set.p.solid_threshold;
     // Clusters: four launches in the same place, behind the order launches of the step (n_min > 0 reads their
     // n_conn), under the same predicate (no volume either)
-    const bool cluster_run = md.cluster.on && cluster_was_valid && N > 0;
-    const ta::SampleSchedule &cluster_sched = md.cluster.sched;
     ta::MdClusterLaunch cl;
     cl.blk_start = md.cluster.blk.ptr;
     cl.rl2 = md.cluster.rl2.ptr;
-    cl.n_conn = cluster_run && md.cluster.p.n_min > 0 ? md.order.per_atom_int.ptr + N : nullptr;
+    cl.n_conn = md.cluster.run && md.cluster.set.p.n_min > 0 ? md.order.per_atom_int.ptr + N : nullptr;
     cl.parent = md.cluster.per_atom.ptr;
-    cl.count = cluster_run ? md.cluster.per_atom.ptr + N : nullptr;
-    cl.label = cluster_run ? md.cluster.per_atom.ptr + 2 * N : nullptr;
-    cl.size = cluster_run ? md.cluster.per_atom.ptr + 3 * N : nullptr;
+    cl.count = md.cluster.run ? md.cluster.per_atom.ptr + N : nullptr;
+    cl.label = md.cluster.run ? md.cluster.per_atom.ptr + 2 * N : nullptr;
+    cl.size = md.cluster.run ? md.cluster.per_atom.ptr + 3 * N : nullptr;
     cl.hist = md.cluster.acc.ptr;
     cl.giveup = md.cluster.giveup.ptr;
     cl.status = res.status.ptr;
     cl.n_atoms = (long long)N;
-    cl.n_bins = md.cluster.p.n_bins, cl.n_elements = h->n_elements, cl.n_frames = (int)F;
+    cl.n_bins = md.cluster.set.p.n_bins, cl.n_elements = h->n_elements, cl.n_frames = (int)F;
     cl.n_blk = md.cluster.n_blk, cl.chunk = md.cluster.chunk;
-    cl.n_min = md.cluster.p.n_min, cl.species_mask = md.cluster.p.species_mask;
+    cl.n_min = md.cluster.set.p.n_min, cl.species_mask = md.cluster.set.p.species_mask;
     // Common neighbour analysis: its launch in the same place, behind the order and cluster launches, under the same
     // predicate (no volume either); sample n counts into row n % n_series, which a launch in front zeroes
-    const bool cna_run = md.cna.on && cna_was_valid && N > 0;
-    const ta::SampleSchedule &cna_sched = md.cna.sched;
     ta::MdCnaLaunch cn;
     cn.blk_start = md.cna.blk.ptr;
     cn.structure = md.cna.structure.ptr;
@@ -1414,92 +1151,55 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     cn.status = res.status.ptr;
     cn.n_elements = h->n_elements, cn.n_frames = (int)F;
     cn.n_blk = md.cna.n_blk, cn.chunk = md.cna.chunk;
-    cn.mode = md.cna.p.mode;
-    cn.r_cut = md.cna.p.r_cut;
+    cn.mode = md.cna.set.p.mode;
+    cn.r_cut = md.cna.set.p.r_cut;
     {
-      const double r = md.cna.p.mode == TA_MD_CNA_FIXED ? md.cna.p.r_cut : md.cna.p.r_max;
+      const double r = md.cna.set.p.mode == TA_MD_CNA_FIXED ? md.cna.set.p.r_cut : md.cna.set.p.r_max;
       cn.r2 = r * r;
     }
     // Structure factors: the integrator launch of a due step writes the whole-step state (x, v) to the slot of the
     // correlation ring when md_set_sampling is due at the same launch, to two rows of this feature's otherwise;
     // the three launches go BEHIND it, under the same predicate, and read that snapshot.
-    const bool sq_run = md.sq.on && sq_was_valid && N > 0;
-    const ta::SampleSchedule &sq_sched = md.sq.sched;
     ta::MdSqLaunch u;
     u.blk_start = md.sq.blk.ptr;
     u.miller = md.sq.miller_dev.ptr;
     u.part = md.sq.part.ptr;
     u.ring = md.sq.ring.ptr;
     {
-      const size_t E = (size_t)h->n_elements, n_acc = F * E * E * (size_t)md.sq.p.n_lags * (size_t)md.sq.p.n_q;
+      const size_t E = (size_t)h->n_elements, n_acc = F * E * E * (size_t)md.sq.set.p.n_lags * (size_t)md.sq.set.p.n_q;
       u.acc_rho = md.sq.acc.ptr;
-      u.acc_l = sq_run && md.sq.p.currents ? md.sq.acc.ptr + n_acc : nullptr;
-      u.acc_j = sq_run && md.sq.p.currents ? md.sq.acc.ptr + 2 * n_acc : nullptr;
+      u.acc_l = md.sq.run && md.sq.set.p.currents ? md.sq.acc.ptr + n_acc : nullptr;
+      u.acc_j = md.sq.run && md.sq.set.p.currents ? md.sq.acc.ptr + 2 * n_acc : nullptr;
     }
     u.status = res.status.ptr;
-    u.n_q = md.sq.p.n_q, u.n_lags = md.sq.p.n_lags, u.n_elements = h->n_elements, u.n_frames = (int)F;
-    u.n_blk = md.sq.n_blk, u.chunk = md.sq.chunk, u.currents = md.sq.p.currents;
+    u.n_q = md.sq.set.p.n_q, u.n_lags = md.sq.set.p.n_lags, u.n_elements = h->n_elements, u.n_frames = (int)F;
+    u.n_blk = md.sq.n_blk, u.chunk = md.sq.chunk, u.currents = md.sq.set.p.currents;
     auto integrate = [&](int k, bool drift) {
-      if (order_run && order_sched.due(step0, k)) {
-        o.pos = h->db.pos;
-        o.cells = h->db.cells;
-        o.species = h->db.species;
-        o.atom_start = h->db.atom_start;
-        o.pair_start = h->pair_start.ptr;  // the resident list
-        o.pair_j = h->pair_j.ptr;
-        o.pair_shift = h->pair_shift.ptr;
-        o.seq = (unsigned)k;
+      if (md.order.run && md.order.sched.due(step0, k)) {
+        point_at_list(h, o, k);
         ta::launch_md_order(o, s);
         HIP_CHECK(hipGetLastError());
       }
-      if (cluster_run && cluster_sched.due(step0, k)) {
-        cl.pos = h->db.pos;
-        cl.cells = h->db.cells;
-        cl.species = h->db.species;
-        cl.atom_start = h->db.atom_start;
-        cl.pair_start = h->pair_start.ptr;  // the resident list
-        cl.pair_j = h->pair_j.ptr;
-        cl.pair_shift = h->pair_shift.ptr;
-        cl.seq = (unsigned)k;
-        cl.row = md.cluster.series.ptr + (size_t)(cluster_sched.index(step0 + k) % md.cluster.p.n_series) * F * 4;
+      if (md.cluster.run && md.cluster.sched.due(step0, k)) {
+        point_at_list(h, cl, k);
+        cl.row = md.cluster.series.ptr + (size_t)(md.cluster.sched.index(step0 + k) % md.cluster.set.p.n_series) * F * 4;
         ta::launch_md_cluster(cl, s);
         HIP_CHECK(hipGetLastError());
       }
-      if (cna_run && cna_sched.due(step0, k)) {
-        cn.pos = h->db.pos;
-        cn.cells = h->db.cells;
-        cn.species = h->db.species;
-        cn.atom_start = h->db.atom_start;
-        cn.pair_start = h->pair_start.ptr;  // the resident list
-        cn.pair_j = h->pair_j.ptr;
-        cn.pair_shift = h->pair_shift.ptr;
-        cn.seq = (unsigned)k;
-        cn.row = md.cna.series.ptr + (size_t)(cna_sched.index(step0 + k) % md.cna.p.n_series) * F * TA_MD_CNA_TYPES;
+      if (md.cna.run && md.cna.sched.due(step0, k)) {
+        point_at_list(h, cn, k);
+        cn.row = md.cna.series.ptr + (size_t)(md.cna.sched.index(step0 + k) % md.cna.set.p.n_series) * F * TA_MD_CNA_TYPES;
         ta::launch_md_cna(cn, s);
         HIP_CHECK(hipGetLastError());
       }
-      if (adf_run && adf_sched.due(step0, k)) {
-        t.pos = h->db.pos;
-        t.cells = h->db.cells;
-        t.species = h->db.species;
-        t.atom_start = h->db.atom_start;
-        t.pair_start = h->pair_start.ptr;  // the resident list
-        t.pair_j = h->pair_j.ptr;
-        t.pair_shift = h->pair_shift.ptr;
-        t.seq = (unsigned)k;
+      if (md.adf.run && md.adf.sched.due(step0, k)) {
+        point_at_list(h, t, k);
         ta::launch_md_adf(t, s);
         HIP_CHECK(hipGetLastError());
       }
-      if (rdf_run && rdf_sched.due(step0, k)) {
-        g.pos = h->db.pos;
-        g.cells = h->db.cells;
-        g.species = h->db.species;
-        g.atom_start = h->db.atom_start;
-        g.pair_start = h->pair_start.ptr;  // the resident list, not the exact one filtered from it
+      if (md.rdf.run && md.rdf.sched.due(step0, k)) {
+        point_at_list(h, g, k);
         g.pair_i = h->pair_i.ptr;
-        g.pair_j = h->pair_j.ptr;
-        g.pair_shift = h->pair_shift.ptr;
-        g.seq = (unsigned)k;
         ta::launch_md_rdf(g, s);
         HIP_CHECK(hipGetLastError());
       }
@@ -1516,14 +1216,14 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
       a.drift = drift ? 1 : 0;
       a.rec = (k % record_every == 0) ? (long long)(k / record_every) : -1;
       a.snap_x = a.snap_v = nullptr;
-      const bool due = sampling && corr_sched.due(step0, k);
+      const bool due = md.corr.run && md.corr.sched.due(step0, k);
       if (due) {
-        c.n = (long long)corr_sched.index(step0 + k);
+        c.n = (long long)md.corr.sched.index(step0 + k);
         const size_t slot = (size_t)(c.n % samp_L);
         a.snap_x = md.corr.ring_x.ptr + slot * 3 * N;
         a.snap_v = md.corr.ring_v.ptr + slot * 3 * N;
       }
-      const bool sq_due = sq_run && sq_sched.due(step0, k);
+      const bool sq_due = md.sq.run && md.sq.sched.due(step0, k);
       if (sq_due && !due) a.snap_x = md.sq.snap_x.ptr, a.snap_v = md.sq.snap_v.ptr;
       ta::launch_md_integrate(a, threads, s);
       HIP_CHECK(hipGetLastError());
@@ -1540,7 +1240,7 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
         u.species = h->db.species;
         u.atom_start = h->db.atom_start;
         u.seq = (unsigned)k;
-        u.n = (long long)sq_sched.index(step0 + k);
+        u.n = (long long)md.sq.sched.index(step0 + k);
         ta::launch_md_sq(u, s);
         HIP_CHECK(hipGetLastError());
       }
@@ -1555,28 +1255,19 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     HIP_CHECK(hipStreamSynchronize(s));
     h->upload_pending = false;
     md.step = step0 + n_steps;
-    if (sampling) md.corr.sched.finish(md.step);
-    md.corr.sched.valid = corr_was_valid;
-    if (rdf_run) md.rdf.sched.finish(md.step);
-    md.rdf.sched.valid = rdf_was_valid;
-    if (adf_run) md.adf.sched.finish(md.step);
-    md.adf.sched.valid = adf_was_valid;
-    if (order_run) md.order.sched.finish(md.step);
-    md.order.sched.valid = order_was_valid;
-    if (sq_run) md.sq.sched.finish(md.step);
-    md.sq.sched.valid = sq_was_valid;
-    if (cluster_run) {
+    // The order in which the samplers' data become valid again is behaviour: corr, rdf, adf, order, sq, then cluster
+    // behind its give-up check, then cna. After a give-up, cluster and cna stay invalid and the five in front are valid.
+    for (MdSampler *x : std::initializer_list<MdSampler *>{&md.corr, &md.rdf, &md.adf, &md.order, &md.sq}) x->end_run(md.step);
+    if (md.cluster.run) {
       unsigned gave_up = 0u;
       HIP_CHECK(hipMemcpy(&gave_up, md.cluster.giveup.ptr, sizeof(unsigned), hipMemcpyDeviceToHost));
       if (gave_up) {  // the data stay invalid
         HIP_CHECK(hipMemset(md.cluster.giveup.ptr, 0, 4 * sizeof(unsigned)));
         throw HipError("ta_md_run: a loop of the cluster link launch overran its cap; the cluster data are invalid");
       }
-      md.cluster.sched.finish(md.step);
     }
-    md.cluster.sched.valid = cluster_was_valid;
-    if (cna_run) md.cna.sched.finish(md.step);
-    md.cna.sched.valid = cna_was_valid;
+    md.cluster.end_run(md.step);
+    md.cna.end_run(md.step);
     if (n_rebuilds) *n_rebuilds = rebuilds;
     if (baro && F) {
       std::vector<double> rec(4 * n_rec * F);
@@ -1620,8 +1311,7 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
 
 int ta_md_get_state(ta_handle h, double *positions, double *velocities) {
   if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_get_state: no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_get_state called before ta_md_init");
+  if (const int rc = md_resident(h, "ta_md_get_state")) return rc;
   return guarded(h, [&]() {
     const size_t N = h->keep_species.size();
     HIP_CHECK(hipStreamSynchronize(h->stream));

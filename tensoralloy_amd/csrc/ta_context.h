@@ -15,6 +15,7 @@
 #include "ta_internal.h"
 #include "ta_launch.h"
 #include "ta_relax.h"
+#include "ta_sampler_text.h"
 #include "ta_schedule.h"
 
 namespace ta {
@@ -83,6 +84,12 @@ struct DevBuf {
   }
 };
 
+// release() of every buffer given, of whatever element types
+template <typename... B>
+void release_all(B &...bufs) {
+  (bufs.release(), ...);
+}
+
 // grow-only page-locked host buffer (staging for the packed uploads / downloads); frees itself likewise
 struct PinnedBuf {
   char *ptr = nullptr;
@@ -128,6 +135,37 @@ struct ResidentLoop {
   volatile unsigned *host_words() const { return reinterpret_cast<volatile unsigned *>(status_host.ptr); }
 };
 
+// What every sampler of the MD loop keeps besides its own buffers (their shared lifecycle is in ta_api_md.hip): its
+// texts, whether it is on, the workgroup layout of its launch for the resident batch (`blk` [F + 1]: the first
+// workgroup of every frame, `chunk` items each), its schedule, and its part in the ta_md_run under way. A feature
+// adds a `Setting set` (the C parameter struct and whatever else allocating for it needs), its buffers and a
+// release() that frees them and ends in release_layout().
+struct MdSampler {
+  const MdSamplerText &text;
+  bool on = false;
+  DevBuf<int32_t> blk;
+  int n_blk = 0, chunk = 0;
+  SampleSchedule sched;
+  bool was_valid = false, run = false;  // set by begin_run
+  explicit MdSampler(const MdSamplerText &t) : text(t) {}
+  void release_layout() {
+    blk.release();
+    n_blk = 0;
+    sched.valid = false;
+    sched.last = -1;
+  }
+  // a ta_md_run begins: the data are invalid until end_run; `run`: the sampler has launches in it
+  void begin_run(bool have_atoms) {
+    was_valid = sched.suspend();
+    run = on && was_valid && have_atoms;
+  }
+  // the run (and whatever else the feature checks) succeeded and ended at absolute step `step`
+  void end_run(int64_t step) {
+    if (run) sched.finish(step);
+    sched.valid = was_valid;
+  }
+};
+
 // device-resident MD loop (ta_api_md.hip; the integrator launch is in ta_md.hip): masses, velocities, the
 // records of the running ta_md_run, the steps integrated since ta_md_init (the noise's step counter and the
 // clock of the sample schedules), and one struct per feature with its setting, buffers and host records
@@ -165,155 +203,123 @@ struct MdState {
     std::vector<double> rec_volume, rec_press;
   } baro;
   // Sampling (ta_md_set_sampling): the rings [L][N][3], the accumulators [2][F][E][L] (v . v, then |dx|^2), the
-  // correlation launch's partials and chunk layout
-  struct Corr {
-    bool on = false;
-    ta_md_sampling_params p = {0, 1};
+  // correlation launch's partials; its layout is in chunks of kMdCorrChunk ring doubles
+  struct Corr : MdSampler {
+    Corr() : MdSampler(md_text::corr) {}
+    struct Setting {
+      ta_md_sampling_params p = {0, 1};
+    } set;
     DevBuf<double> ring_x, ring_v, acc, part;
-    DevBuf<int32_t> blk;
-    int n_chunks = 0;
-    SampleSchedule sched;
     void release() {  // frees what sampling holds on the device; the setting stays
-      for (auto *b : {&ring_x, &ring_v, &acc, &part}) b->release();
-      blk.release();
-      n_chunks = 0;
-      sched.valid = false;
-      sched.last = -1;
+      release_all(ring_x, ring_v, acc, part);
+      release_layout();
     }
   } corr;
-  // Pair distributions (ta_md_set_rdf): the counts [F][E][E][n_bins] and the launch's workgroup layout
-  struct Rdf {
-    bool on = false;
-    ta_md_rdf_params p = {0.0, 0, 1};
+  // Pair distributions (ta_md_set_rdf): the counts [F][E][E][n_bins]
+  struct Rdf : MdSampler {
+    Rdf() : MdSampler(md_text::rdf) {}
+    struct Setting {
+      ta_md_rdf_params p = {0.0, 0, 1};
+    } set;
     DevBuf<unsigned long long> acc;
-    DevBuf<int32_t> blk;
-    int n_blk = 0, chunk = 0;
-    SampleSchedule sched;
     void release() {  // frees what the pair distributions hold on the device; the setting stays
       acc.release();
-      blk.release();
-      n_blk = 0;
-      sched.valid = false;
-      sched.last = -1;
+      release_layout();
     }
   } rdf;
   // Bond-angle distributions (ta_md_set_adf): the bond cutoffs [E][E] of the setting, their squares on the
-  // device, the counts [F][E][E (E + 1) / 2][n_bins] and the launch's workgroup layout
-  struct Adf {
-    bool on = false;
-    ta_md_adf_params p = {0.0, 0, 1};
-    std::vector<double> rb;
+  // device, the counts [F][E][E (E + 1) / 2][n_bins]
+  struct Adf : MdSampler {
+    Adf() : MdSampler(md_text::adf) {}
+    struct Setting {
+      ta_md_adf_params p = {0.0, 0, 1};
+      std::vector<double> rb;
+    } set;
     DevBuf<double> rb2;
     DevBuf<unsigned long long> acc;
-    DevBuf<int32_t> blk;
-    int n_blk = 0, chunk = 0;
-    SampleSchedule sched;
     void release() {  // frees what the bond-angle distributions hold on the device; the setting stays
-      rb2.release();
-      acc.release();
-      blk.release();
-      n_blk = 0;
-      sched.valid = false;
-      sched.last = -1;
+      release_all(rb2, acc);
+      release_layout();
     }
   } adf;
   // Bond-orientational order (ta_md_set_order): the bond cutoffs [E][E] of the setting, their squares and the N_lm
-  // on the device, the counts (hist_q, hist_qbar [F][E][D][n_bins], then hist_conn [F][E][32], one buffer), the
+  // on the device, the counts (hist_q, hist_qbar [F][E][D][n_bins], then hist_conn [F][E][32], one buffer) and the
   // per-atom arrays of the newest sample (q_lm [N][n_lm][2]; q, qbar [N][D] in `per_atom`; N_b, n_conn [N] in
-  // `per_atom_int`) and the launches' workgroup layout
-  struct Order {
-    bool on = false;
-    ta_md_order_params p = {0.0, 0.0, 0, 1, 0, {0, 0, 0, 0}, 0};
-    std::vector<double> rb;
+  // `per_atom_int`)
+  struct Order : MdSampler {
+    Order() : MdSampler(md_text::order) {}
+    struct Setting {
+      ta_md_order_params p = {0.0, 0.0, 0, 1, 0, {0, 0, 0, 0}, 0};
+      std::vector<double> rb;
+    } set;
     DevBuf<double> rb2, norm, qlm, per_atom;
     DevBuf<int32_t> per_atom_int;
     DevBuf<unsigned long long> acc;
-    DevBuf<int32_t> blk;
-    int n_blk = 0, chunk = 0, n_lm = 0, solid = 0;
-    SampleSchedule sched;
+    int n_lm = 0, solid = 0;
     void release() {  // frees what the order parameters hold on the device; the setting stays
-      for (auto *b : {&rb2, &norm, &qlm, &per_atom}) b->release();
-      per_atom_int.release();
-      acc.release();
-      blk.release();
-      n_blk = 0;
-      sched.valid = false;
-      sched.last = -1;
+      release_all(rb2, norm, qlm, per_atom, per_atom_int, acc);
+      release_layout();
     }
   } order;
   // Clusters of selected atoms (ta_md_set_clusters): the link cutoffs [E][E] of the setting and their squares on the
   // device, the per-atom arrays (parent, count, label, size, [N] each, one buffer), the histogram [F][n_bins], the
-  // ring of series rows [n_series][F][4], the give-up word of the link launch and that launch's workgroup layout
-  struct Cluster {
-    bool on = false;
-    ta_md_cluster_params p = {0.0, 0, 0, 0, 1, 1};
-    std::vector<double> rl;
+  // ring of series rows [n_series][F][4] and the give-up word of the link launch
+  struct Cluster : MdSampler {
+    Cluster() : MdSampler(md_text::cluster) {}
+    struct Setting {
+      ta_md_cluster_params p = {0.0, 0, 0, 0, 1, 1};
+      std::vector<double> rl;
+    } set;
     DevBuf<double> rl2;
     DevBuf<int32_t> per_atom;
     DevBuf<unsigned long long> acc;
     DevBuf<long long> series;
     DevBuf<unsigned> giveup;
-    DevBuf<int32_t> blk;
-    int n_blk = 0, chunk = 0;
-    SampleSchedule sched;
     void release() {  // frees what the clusters hold on the device; the setting stays
-      rl2.release();
-      per_atom.release();
-      acc.release();
-      series.release();
-      giveup.release();
-      blk.release();
-      n_blk = 0;
-      sched.valid = false;
-      sched.last = -1;
+      release_all(rl2, per_atom, acc, series, giveup);
+      release_layout();
     }
   } cluster;
   // Common neighbour analysis (ta_md_set_cna): the setting (r_max resolved), the per-atom arrays of the newest sample,
-  // the counts [F][E][5], the ring of series rows [n_series][F][5] and the launch's workgroup layout
-  struct Cna {
-    bool on = false;
-    ta_md_cna_params p = {0.0, 0.0, 0, 0, 1};
+  // the counts [F][E][5] and the ring of series rows [n_series][F][5]
+  struct Cna : MdSampler {
+    Cna() : MdSampler(md_text::cna) {}
+    struct Setting {
+      ta_md_cna_params p = {0.0, 0.0, 0, 0, 1};
+    } set;
     DevBuf<int32_t> structure;
     DevBuf<double> r_local;
-    DevBuf<unsigned long long> acc;
-    DevBuf<unsigned long long> series;
-    DevBuf<int32_t> blk;
-    int n_blk = 0, chunk = 0;
-    SampleSchedule sched;
+    DevBuf<unsigned long long> acc, series;
     void release() {  // frees what the analysis holds on the device; the setting stays
-      structure.release();
-      r_local.release();
-      acc.release();
-      series.release();
-      blk.release();
-      n_blk = 0;
-      sched.valid = false;
-      sched.last = -1;
+      release_all(structure, r_local, acc, series);
+      release_layout();
     }
   } cna;
   // Structure factors (ta_md_set_sq): the Miller triples [Q][3] of the setting and their device twin, the ring of
   // amplitude rows [L][F][E][planes][Q] (planes = 2, or 8 with currents), the accumulators (A_rho, then A_L and
-  // A_J with currents, [F][E][E][L][Q] each, one buffer), the amplitude launch's partials and workgroup layout, and
-  // the two rows [N][3] the integrator writes a sampled state to when md_set_sampling's ring does not take it
-  struct Sq {
-    bool on = false;
-    ta_md_sq_params p = {0, 1, 1, 0};
-    std::vector<int32_t> miller;
+  // A_J with currents, [F][E][E][L][Q] each, one buffer), the amplitude launch's partials, and the two rows [N][3]
+  // the integrator writes a sampled state to when md_set_sampling's ring does not take it
+  struct Sq : MdSampler {
+    Sq() : MdSampler(md_text::sq) {}
+    struct Setting {
+      ta_md_sq_params p = {0, 1, 1, 0};
+      std::vector<int32_t> miller;
+    } set;
     DevBuf<int32_t> miller_dev;
     DevBuf<double> ring, acc, part, snap_x, snap_v;
-    DevBuf<int32_t> blk;
-    int n_blk = 0, chunk = 0;
-    SampleSchedule sched;
     void release() {  // frees what the structure factors hold on the device; the setting stays
-      for (auto *b : {&ring, &acc, &part, &snap_x, &snap_v}) b->release();
-      miller_dev.release();
-      blk.release();
-      n_blk = 0;
-      sched.valid = false;
-      sched.last = -1;
+      release_all(ring, acc, part, snap_x, snap_v, miller_dev);
+      release_layout();
     }
   } sq;
 };
+
+// every sampler of the MD loop in the canonical order: the one ta_md_init allocates them in and reports the first
+// failure in (fn takes the feature's own struct: a generic lambda)
+template <typename Fn>
+void for_each_sampler(MdState &md, Fn &&fn) {
+  fn(md.corr), fn(md.rdf), fn(md.adf), fn(md.order), fn(md.cluster), fn(md.cna), fn(md.sq);
+}
 
 // device-resident relaxation (ta_api_relax.hip; the launches are in ta_relax.hip): FIRE velocities of its own,
 // the mask of fixed atoms (and the host's copy of ta_relax_init's), the two copies of the per-frame state with

@@ -1,5 +1,6 @@
-// When the device MD loop samples: the schedule that the correlations and the pair distributions each keep.
-// Plain C++ with no HIP include (tests/test_schedule_cpu.py compiles it alone).
+// When the device MD loop samples: the schedule that every sampler of the loop keeps an instance of (MdSampler in
+// ta_context.h; the sample_every of each is its own). Plain C++ with no HIP include (tests/test_schedule_cpu.py
+// compiles it alone).
 #pragma once
 #include <algorithm>
 #include <cstdint>
