@@ -743,7 +743,49 @@ int ta_step_view(ta_handle h, const double *positions, const double *cells, uint
  *                        newest): rho [n][n_frames][n_elements][n_q][2] (real, imaginary), cur
  *                        [n][n_frames][n_elements][n_q][3][2] and their absolute steps [n]; any pointer may be
  *                        NULL. TA_ERR_INVALID when first_lag < 0, n < 0, first_lag + n exceeds the
- *                        min(n_samples, n_lags) rows held, or cur is asked for without currents. */
+ *                        min(n_samples, n_lags) rows held, or cur is asked for without currents.
+ *
+ * Heat current and pressure tensor inside the loop (opt-in; with it never switched on nothing changes): the two
+ * Green-Kubo observables, which need the model's per-atom energies e_i and per-pair gradients and so cannot be
+ * made from a dumped trajectory. With p = (c -> n) a directed pair of the list the evaluation ran on,
+ * D_p = x_n + S h - x_c its pair vector and g_p = d e_c / d D_p the gradient of the CENTRE's energy, at the
+ * whole-step state (x(t), v(t)) of every absolute step t with t % sample_every == 0 (the schedule of ta_md_set_sq),
+ * per frame
+ *     J_conv = sum_i (1/2 m_i |v_i|^2 + e_i) v_i
+ *     J_pot  = - sum_p D_p (g_p . v_n(p))          (Fan et al., PRB 92, 094301)
+ *     K_ab   = sum_i m_i v_ia v_ib                 W_ab = 1/2 sum_p (g_pa D_pb + g_pb D_pa)
+ * with ab in the order xx yy zz yz xz xy; Pi_ab = K_ab - W_ab = P_ab V, the sign of the barostat's record. A
+ * sample's row is {J_conv[3], J_pot[3], K[6], W[6]}: TA_MD_FLUX_ROW = 18 doubles per frame. The device keeps the
+ * last n_lags rows in a ring, the sum of all rows (for the means) and, over every time origin, with J = J_conv +
+ * J_pot and sample number m against the lags k = 0 .. min(m, n_lags - 1),
+ *     a_heat [f][k][a]  += J_a(m) J_a(m - k)             a_press[f][k][ab] += Pi_ab(m) Pi_ab(m - k)
+ * The number of time origins at lag k is max(0, n_samples - k). No centre-of-mass correction is made, and no
+ * partial-enthalpy correction for mixtures: in a mixture the heat current contains the interdiffusion part. Units
+ * are the caller's: energy length / time for J, energy for K, W and Pi. Everything is fp64 and no sum uses
+ * floating-point atomics (a centre's pairs over 16 lanes, the centres of a workgroup, then the workgroups of a frame
+ * in index order): a run cut into calls reproduces the uncut run bit for bit, another skin reproduces it to
+ * rounding. While a ta_md_run has this sampler running, and only then, its evaluations leave g_p as defined above:
+ * one-element symmetry-function models take the per-apex backward build, not the triangle-once one, and
+ * EAM / ADP / eam/fs models with analytic or tabulated pair functions take the pair kernel and the force gather on
+ * the resident list, not the folded force kernels. The trajectory of such a run agrees with that of a run without
+ * the sampler to rounding, not bit for bit, and a step costs more (profiles/md_flux.md).
+ *   ta_md_set_flux       NULL or n_lags == 0 switches it off (the default; always allowed) and frees the buffers.
+ *                        Switching on needs a resident batch and ta_md_init; it allocates and zeroes the
+ *                        accumulators and forgets earlier samples (so does every further call). The life cycle is
+ *                        that of ta_md_set_sampling. TA_ERR_INVALID, with the argument named by ta_last_error and
+ *                        the setting left as it was: n_lags outside 0 .. TA_MD_MAX_LAGS; sample_every < 1.
+ *                        TA_ERR_NOMEM when the device allocation fails; the feature is then off.
+ *   ta_md_run            TA_ERR_INVALID while this feature and the barostat are both on (normalising needs one
+ *                        volume). A run that fails leaves the data invalid: both getters are TA_ERR_INVALID until
+ *                        ta_md_set_flux or ta_md_init is called again.
+ *   ta_md_get_flux       sums [n_frames][18], a_heat [n_frames][n_lags][3], a_press [n_frames][n_lags][6]: the raw
+ *                        sums; info [8] = {n_samples, n_lags, sample_every, absolute step of the newest sample or
+ *                        -1, absolute step of the first sample, atoms per workgroup of the pair sweep, most
+ *                        workgroups of one frame (a frame's partials are added one after another), lanes per
+ *                        centre}. Any pointer may be NULL.
+ *   ta_md_get_flux_rows  the rows first_lag .. first_lag + n - 1 back from the newest one (0 = the newest): rows
+ *                        [n][n_frames][18] and their absolute steps [n]; either may be NULL. TA_ERR_INVALID when
+ *                        first_lag < 0, n < 0 or first_lag + n exceeds the min(n_samples, n_lags) rows held. */
 #define TA_MD_MAX_CHAIN 8
 #define TA_MD_MAX_LAGS 4096
 #define TA_MD_MAX_BINS 4096
@@ -800,6 +842,11 @@ typedef struct {
   int32_t sample_every;  /* s >= 1 */
   int32_t currents;      /* 0, or 1: j_a(q), A_L and A_J as well */
 } ta_md_sq_params;
+#define TA_MD_FLUX_ROW 18
+typedef struct {
+  int32_t n_lags;        /* L, 1 .. TA_MD_MAX_LAGS; 0 switches the feature off (the default) */
+  int32_t sample_every;  /* s >= 1 */
+} ta_md_flux_params;
 typedef struct {
   double kT0;           /* target, energy; <= 0 switches the thermostat off (the default) */
   double tau;           /* time, finite, > 0 */
@@ -849,6 +896,9 @@ int ta_md_get_cna_atoms(ta_handle h, int32_t *structure, double *r_local);
 int ta_md_set_sq(ta_handle h, const ta_md_sq_params *p, const int32_t *miller);
 int ta_md_get_sq(ta_handle h, double *a_rho, double *a_l, double *a_j, int64_t *info, int32_t *miller);
 int ta_md_get_sq_amplitudes(ta_handle h, int32_t first_lag, int32_t n, double *rho, double *cur, int64_t *steps);
+int ta_md_set_flux(ta_handle h, const ta_md_flux_params *p);
+int ta_md_get_flux(ta_handle h, double *sums, double *a_heat, double *a_press, int64_t *info);
+int ta_md_get_flux_rows(ta_handle h, int32_t first_lag, int32_t n, double *rows, int64_t *steps);
 
 /* Device-resident structure relaxation: the resident batch is brought to a force minimum in ONE call, every
  * frame on its own, with positions, velocities and forces staying on the device. The optimiser is FIRE

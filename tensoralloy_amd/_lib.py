@@ -21,7 +21,7 @@ LIB_PATH = PKG_DIR / "libtensoralloy_amd.so"
 
 SOURCES = ["ta_api.hip", "ta_api_md.hip", "ta_api_relax.hip", "ta_resident.hip", "ta_kernels.hip", "ta_kernels_v2.hip", "ta_mlp.hip", "ta_eam.hip",
            "ta_nlist.hip", "ta_grap.hip", "ta_train.hip", "ta_hvp.hip", "ta_neighbor.cpp", "ta_td.hip",
-           "ta_td_train.hip", "ta_md.hip", "ta_md_corr.hip", "ta_md_rdf.hip", "ta_md_adf.hip", "ta_md_order.hip", "ta_md_cluster.hip", "ta_md_cna.hip", "ta_md_sq.hip", "ta_relax.hip", "ta_neb.hip",
+           "ta_td_train.hip", "ta_md.hip", "ta_md_corr.hip", "ta_md_rdf.hip", "ta_md_adf.hip", "ta_md_order.hip", "ta_md_cluster.hip", "ta_md_cna.hip", "ta_md_sq.hip", "ta_md_flux.hip", "ta_relax.hip", "ta_neb.hip",
            "ta_options.cpp"]
 OBJ_DIR = CSRC_DIR / "build"
 
@@ -69,6 +69,7 @@ EXPORTED_SYMBOLS = [
     "ta_md_set_clusters", "ta_md_get_clusters", "ta_md_get_cluster_atoms",
     "ta_md_set_cna", "ta_md_get_cna", "ta_md_get_cna_atoms",
     "ta_md_set_sq", "ta_md_get_sq", "ta_md_get_sq_amplitudes",
+    "ta_md_set_flux", "ta_md_get_flux", "ta_md_get_flux_rows",
     "ta_relax_init", "ta_relax_run", "ta_relax_get_state",
     "ta_relax_set_cell", "ta_relax_get_cell",
     "ta_relax_set_band", "ta_relax_get_band",
@@ -176,6 +177,13 @@ TA_MD_SQ_MAX_Q, TA_MD_SQ_MAX_INDEX = 4096, 64  # include/tensoralloy_amd.h
 
 class MdSqParams(C.Structure):
     _fields_ = [("n_q", C.c_int32), ("n_lags", C.c_int32), ("sample_every", C.c_int32), ("currents", C.c_int32)]
+
+
+TA_MD_FLUX_ROW = 18  # include/tensoralloy_amd.h: J_conv[3], J_pot[3], K[6], W[6]
+
+
+class MdFluxParams(C.Structure):
+    _fields_ = [("n_lags", C.c_int32), ("sample_every", C.c_int32)]
 
 
 class RelaxCellParams(C.Structure):
@@ -379,6 +387,9 @@ def load():
     lib.ta_md_set_sq.argtypes = [H, C.POINTER(MdSqParams), _ip]
     lib.ta_md_get_sq.argtypes = [H, _dp, _dp, _dp, C.POINTER(C.c_int64), _ip]
     lib.ta_md_get_sq_amplitudes.argtypes = [H, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int64)]
+    lib.ta_md_set_flux.argtypes = [H, C.POINTER(MdFluxParams)]
+    lib.ta_md_get_flux.argtypes = [H, _dp, _dp, _dp, C.POINTER(C.c_int64)]
+    lib.ta_md_get_flux_rows.argtypes = [H, C.c_int32, C.c_int32, _dp, C.POINTER(C.c_int64)]
     lib.ta_relax_init.argtypes = [H, C.POINTER(FireParams), C.POINTER(C.c_uint8)]
     lib.ta_relax_run.argtypes = [H, C.c_int32, C.c_double, C.c_uint32, _ip, _ip, _dp, _ip]
     lib.ta_relax_get_state.argtypes = [H, _dp, _dp, _dp, _dp, _ip]

@@ -656,7 +656,9 @@ void ta::host::compute_impl(ta_context *h, uint32_t want, bool timed, double *sl
     // (while cells relax or follow a barostat, a list stays valid until a width has shrunk by
     // rmax / (rmax + skin): the wider test)
     const bool tri_cells = (h->relax.cell.on || h->md.baro.on) ? h->tri_cells_wide_ok : h->tri_cells_ok;
-    const bool tri = h->use_v2 && h->triangles && tri_cells && h->n_elements == 1 && need_forces;
+    // (its owner puts the gradient of all three terms of a triangle onto its own two pairs: g is then a partition of
+    // the forces, not d e_c / d D_p, which a run that samples the heat current reads)
+    const bool tri = h->use_v2 && h->triangles && tri_cells && h->n_elements == 1 && need_forces && !h->centre_gradients;
     h->db.job_word_own = (tri && h->db.job_count) ? h->job_word_own.ptr : nullptr;
     h->db.job_count_own = (tri && h->db.job_count) ? h->job_count_own.ptr : nullptr;
     h->last_bwd_variant = 0;
@@ -887,10 +889,32 @@ void ensure_job_lists(ta_context *h, size_t n_blk) {
 bool filter_applies(const ta_context *h) {
   if (!(h->skin > 0.0) || h->hp.n_atoms == 0 || h->opt.no_list_filter) return false;
   if (h->kind == TA_MODEL_SF_MLP) return h->use_v2;
-  if (h->kind == TA_MODEL_EAM_ALLOY || h->kind == TA_MODEL_EAM_FS) return ta::eam_is_plain(h->eam);
+  if (h->kind == TA_MODEL_EAM_ALLOY || h->kind == TA_MODEL_EAM_FS) return ta::eam_is_plain(h->eam) && !h->centre_gradients;
   return false;
 }
 }  // namespace
+
+void ta::host::set_centre_gradients(ta_context *h, bool on) {
+  if (h->centre_gradients == on) return;
+  h->centre_gradients = on;
+  if (!h->eam) return;
+  ta::eam_set_pair_route(h->eam, on);
+  if (!h->have_batch) return;
+  if (on && h->filtered) {  // back to the resident list, as set_frames_impl left it
+    h->db.pair_start = h->pair_start.ptr;
+    h->db.pair_stop = nullptr;
+    h->db.seg_start = h->seg_start.ptr;
+    h->db.pair_i = h->pair_i.ptr;
+    h->db.pair_j = h->pair_j.ptr;
+    h->db.pair_shift = h->pair_shift.ptr;
+    h->db.pair_rev = h->pair_rev.ptr;
+    h->db.slot_q = h->db.rev_super = h->db.rev_map = nullptr;
+    h->filtered = false;
+  } else if (!on && filter_applies(h)) {
+    apply_filter(h);
+  }
+  ta::eam_set_list_cutoff(h->eam, (h->skin > 0.0 && !h->filtered) ? h->rmax : 0.0);
+}
 
 void ta::host::apply_filter(ta_context *h) {
   using namespace ta;

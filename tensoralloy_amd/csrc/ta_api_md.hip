@@ -1,9 +1,10 @@
 // C ABI of the device-resident MD loop: the ta_md_* entry points (include/tensoralloy_amd.h). The loop itself
 // is in ta_resident.hip; the integrator, correlation, pair-distribution, bond-angle and bond-order launches are in
 // ta_md.hip, ta_md_corr.hip, ta_md_rdf.hip, ta_md_adf.hip and ta_md_order.hip; the cluster launches in
-// ta_md_cluster.hip, the common neighbour analysis in ta_md_cna.hip, the structure-factor launches in ta_md_sq.hip.
+// ta_md_cluster.hip, the common neighbour analysis in ta_md_cna.hip, the structure-factor launches in ta_md_sq.hip,
+// the heat-current and pressure-tensor launches in ta_md_flux.hip.
 //
-// The seven samplers (ta_md_set_sampling, _rdf, _adf, _order, _clusters, _cna, _sq) share one host-side lifecycle,
+// The eight samplers (ta_md_set_sampling, _rdf, _adf, _order, _clusters, _cna, _sq, _flux) share one host-side lifecycle,
 // written once below: md_alloc_layout, md_sampler_ready, md_sampler_off / md_sampler_set, and the loops of ta_md_init
 // and ta_md_run. To add a sampler:
 //   1. ta_sampler_text.h: its texts, a constant in md_text;
@@ -196,6 +197,20 @@ bool md_alloc(ta_context *h, MdState::Sq &g, const MdState::Sq::Setting &s) {
         zero(g.acc, n_acc);
         upload(g.miller_dev, s.miller);
       });
+}
+
+// an empty ring, the accumulators {sums, a_heat, a_press}, the partials of the pair sweep and the snapshot rows
+bool md_alloc(ta_context *h, MdState::Flux &g, const MdState::Flux::Setting &s) {
+  static_assert(TA_MD_FLUX_ROW == ta::kMdFluxRow, "the header and the launch agree");
+  const size_t N = h->keep_species.size(), F = h->keep_natoms.size(), L = (size_t)s.p.n_lags, R = ta::kMdFluxRow;
+  const size_t n_acc = F * R + F * L * 9;
+  return md_alloc_layout(
+      h, g, s.p.sample_every, 1, ta::md_flux_chunk((long long)N),
+      [&](size_t n_blk) {
+        return g.acc.try_exact(n_acc) && g.ring.try_exact(L * F * R) && g.part.try_exact(n_blk * R) &&
+               g.snap_x.try_exact(3 * N) && g.snap_v.try_exact(3 * N);
+      },
+      [&]() { zero(g.acc, n_acc); });
 }
 
 // what ta_md_set_sq asks of the resident frames: periodic along all three axes, a cell that can be inverted.
@@ -876,6 +891,65 @@ int ta_md_get_sq_amplitudes(ta_handle h, int32_t first_lag, int32_t n, double *r
   });
 }
 
+int ta_md_set_flux(ta_handle h, const ta_md_flux_params *p) {
+  if (!h) return TA_ERR_INVALID;
+  if (!p || p->n_lags == 0) return md_sampler_off(h, h->md.flux);
+  if (p->n_lags < 0 || p->n_lags > TA_MD_MAX_LAGS)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_flux: n_lags must be 0 .. " + std::to_string(TA_MD_MAX_LAGS));
+  if (p->sample_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_set_flux: sample_every must be >= 1");
+  return md_sampler_set(h, h->md.flux, {*p}, "n_lags = " + std::to_string(p->n_lags) + " rows");
+}
+
+int ta_md_get_flux(ta_handle h, double *sums, double *a_heat, double *a_press, int64_t *info) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int bad = md_sampler_ready(h, h->md.flux, "ta_md_get_flux")) return bad;
+  const auto &fx = h->md.flux;
+  return guarded(h, [&]() {
+    const size_t F = h->keep_natoms.size(), L = (size_t)fx.set.p.n_lags, R = ta::kMdFluxRow;
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (sums && F) HIP_CHECK(hipMemcpy(sums, fx.acc.ptr, F * R * sizeof(double), hipMemcpyDeviceToHost));
+    if (a_heat && F) HIP_CHECK(hipMemcpy(a_heat, fx.acc.ptr + F * R, F * L * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (a_press && F)
+      HIP_CHECK(hipMemcpy(a_press, fx.acc.ptr + F * R + F * L * 3, F * L * 6 * sizeof(double), hipMemcpyDeviceToHost));
+    if (info) {
+      int64_t most = 0;
+      for (size_t f = 0; f < F; ++f)
+        most = std::max<int64_t>(most, std::max(1, (h->keep_natoms[f] + fx.chunk - 1) / fx.chunk));
+      info[0] = fx.sched.taken();
+      info[1] = fx.set.p.n_lags;
+      info[2] = fx.set.p.sample_every;
+      info[3] = fx.sched.last;
+      info[4] = fx.sched.taken() ? fx.sched.origin : -1;
+      info[5] = fx.chunk;
+      info[6] = most;
+      info[7] = ta::kMdFluxLanes;
+    }
+  });
+}
+
+int ta_md_get_flux_rows(ta_handle h, int32_t first_lag, int32_t n, double *rows, int64_t *steps) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int bad = md_sampler_ready(h, h->md.flux, "ta_md_get_flux_rows")) return bad;
+  const auto &fx = h->md.flux;
+  const int64_t taken = fx.sched.taken(), L = fx.set.p.n_lags, held = std::min(taken, L);
+  if (first_lag < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_flux_rows: first_lag must be >= 0");
+  if (n < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_flux_rows: n must be >= 0");
+  if ((int64_t)first_lag + n > held)
+    return fail(h, TA_ERR_INVALID, "ta_md_get_flux_rows: first_lag + n = " + std::to_string((int64_t)first_lag + n) +
+                                   " exceeds the " + std::to_string(held) + " rows held (min(n_samples, n_lags))");
+  return guarded(h, [&]() {
+    const size_t row = h->keep_natoms.size() * (size_t)ta::kMdFluxRow;
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    for (int32_t j = 0; j < n; ++j) {
+      const int64_t idx = taken - 1 - first_lag - j;  // sample number
+      if (steps) steps[j] = fx.sched.step(idx);
+      if (rows && row)
+        HIP_CHECK(hipMemcpy(rows + (size_t)j * row, fx.ring.ptr + (size_t)(idx % L) * row, row * sizeof(double),
+                            hipMemcpyDeviceToHost));
+    }
+  });
+}
+
 int ta_md_noise(ta_handle h, int64_t step, double *xi, double *eta) {
   if (!h) return TA_ERR_INVALID;
   if (!xi || !eta) return fail(h, TA_ERR_INVALID, "ta_md_noise: null argument");
@@ -976,6 +1050,10 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     return fail(h, TA_ERR_INVALID, "ta_md_run: the structure factors (ta_md_set_sq) and the barostat (ta_md_set_barostat) are "
                                    "both on; cell and positions of a snapshot would belong to different states: switch one of "
                                    "them off");
+  if (md.flux.on && baro)
+    return fail(h, TA_ERR_INVALID, "ta_md_run: the heat current and pressure tensor (ta_md_set_flux) and the barostat "
+                                   "(ta_md_set_barostat) are both on; normalising the correlations needs one volume: "
+                                   "switch one of them off");
   if (md.cluster.on && md.cluster.set.p.n_min > 0) {  // n_conn of the order launches for the same state is read
     if (!md.order.on)
       return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and reads n_conn, but "
@@ -1003,6 +1081,8 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
   const int rc = guarded(h, [&]() {
     const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
     hipStream_t s = h->stream;
+    // while the heat current is sampled every evaluation of the run leaves g_p = d e_c / d D_p (put back below)
+    set_centre_gradients(h, md.flux.run);
     const bool thermostat = md.berendsen.kT0 > 0.0, langevin = md.langevin.friction > 0.0;  // (never both)
     // with Berendsen scaling one workgroup owns a whole frame: the factor needs the frame's kinetic energy
     // (the barostat: the frame's three sums of m v_c^2; the Nose-Hoover chain: the kinetic energy again)
@@ -1174,6 +1254,21 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     u.status = res.status.ptr;
     u.n_q = md.sq.set.p.n_q, u.n_lags = md.sq.set.p.n_lags, u.n_elements = h->n_elements, u.n_frames = (int)F;
     u.n_blk = md.sq.n_blk, u.chunk = md.sq.chunk, u.currents = md.sq.set.p.currents;
+    // Heat current and pressure tensor: the three launches go BEHIND the integrator launch as well (v(t) exists only
+    // after its closing half-kick), under the same predicate. They read the velocities of the snapshot (the ring slot of
+    // md_set_sampling or the rows of md_set_sq when one of them is due at the same launch, this feature's own rows
+    // otherwise) and, through DeviceBatch, the list, pair records, g and eatom of the evaluation of x(t), which
+    // nothing rewrites before the next compute_impl, enqueued behind them.
+    ta::MdFluxLaunch fx;
+    fx.mass = md.mass.ptr;
+    fx.blk_start = md.flux.blk.ptr;
+    fx.part = md.flux.part.ptr;
+    fx.ring = md.flux.ring.ptr;
+    fx.sums = md.flux.acc.ptr;
+    fx.acc_heat = md.flux.run ? md.flux.acc.ptr + F * ta::kMdFluxRow : nullptr;
+    fx.acc_press = md.flux.run ? md.flux.acc.ptr + F * ta::kMdFluxRow + F * (size_t)md.flux.set.p.n_lags * 3 : nullptr;
+    fx.status = res.status.ptr;
+    fx.n_lags = md.flux.set.p.n_lags, fx.n_frames = (int)F, fx.n_blk = md.flux.n_blk, fx.chunk = md.flux.chunk;
     auto integrate = [&](int k, bool drift) {
       if (md.order.run && md.order.sched.due(step0, k)) {
         point_at_list(h, o, k);
@@ -1225,6 +1320,8 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
       }
       const bool sq_due = md.sq.run && md.sq.sched.due(step0, k);
       if (sq_due && !due) a.snap_x = md.sq.snap_x.ptr, a.snap_v = md.sq.snap_v.ptr;
+      const bool flux_due = md.flux.run && md.flux.sched.due(step0, k);
+      if (flux_due && !due && !sq_due) a.snap_x = md.flux.snap_x.ptr, a.snap_v = md.flux.snap_v.ptr;
       ta::launch_md_integrate(a, threads, s);
       HIP_CHECK(hipGetLastError());
       if (due) {  // directly behind the launch that sampled, under the same predicate
@@ -1244,6 +1341,13 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
         ta::launch_md_sq(u, s);
         HIP_CHECK(hipGetLastError());
       }
+      if (flux_due) {
+        fx.v = a.snap_v;
+        fx.seq = (unsigned)k;
+        fx.n = (long long)md.flux.sched.index(step0 + k);
+        ta::launch_md_flux(fx, h->db, s);
+        HIP_CHECK(hipGetLastError());
+      }
     };
 
     h->jvp_valid = false;
@@ -1255,9 +1359,10 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     HIP_CHECK(hipStreamSynchronize(s));
     h->upload_pending = false;
     md.step = step0 + n_steps;
-    // The order in which the samplers' data become valid again is behaviour: corr, rdf, adf, order, sq, then cluster
-    // behind its give-up check, then cna. After a give-up, cluster and cna stay invalid and the five in front are valid.
-    for (MdSampler *x : std::initializer_list<MdSampler *>{&md.corr, &md.rdf, &md.adf, &md.order, &md.sq}) x->end_run(md.step);
+    // The order in which the samplers' data become valid again is behaviour: corr, rdf, adf, order, sq, flux, then cluster
+    // behind its give-up check, then cna. After a give-up, cluster and cna stay invalid and the six in front are valid.
+    for (MdSampler *x : std::initializer_list<MdSampler *>{&md.corr, &md.rdf, &md.adf, &md.order, &md.sq, &md.flux})
+      x->end_run(md.step);
     if (md.cluster.run) {
       unsigned gave_up = 0u;
       HIP_CHECK(hipMemcpy(&gave_up, md.cluster.giveup.ptr, sizeof(unsigned), hipMemcpyDeviceToHost));
@@ -1306,6 +1411,12 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     }
   });
   res.cell_running = md.baro.running = false;
+  if (h->centre_gradients) {  // the evaluations of other calls take their usual builds again
+    const std::string why = h->err;
+    const int back = guarded(h, [&]() { set_centre_gradients(h, false); });
+    if (rc != TA_OK) h->err = why;
+    else if (back != TA_OK) return back;
+  }
   return rc;
 }
 

@@ -312,13 +312,27 @@ struct MdState {
       release_layout();
     }
   } sq;
+  // Heat current and pressure tensor (ta_md_set_flux): the ring of rows [L][F][18], the accumulators (sums [F][18],
+  // a_heat [F][L][3], a_press [F][L][6], one buffer in that order), the pair sweep's partials, and the two rows [N][3]
+  // the integrator writes a sampled state to when neither md_set_sampling's ring nor md_set_sq's rows take it
+  struct Flux : MdSampler {
+    Flux() : MdSampler(md_text::flux) {}
+    struct Setting {
+      ta_md_flux_params p = {0, 1};
+    } set;
+    DevBuf<double> ring, acc, part, snap_x, snap_v;
+    void release() {  // frees what the sampler holds on the device; the setting stays
+      release_all(ring, acc, part, snap_x, snap_v);
+      release_layout();
+    }
+  } flux;
 };
 
 // every sampler of the MD loop in the canonical order: the one ta_md_init allocates them in and reports the first
 // failure in (fn takes the feature's own struct: a generic lambda)
 template <typename Fn>
 void for_each_sampler(MdState &md, Fn &&fn) {
-  fn(md.corr), fn(md.rdf), fn(md.adf), fn(md.order), fn(md.cluster), fn(md.cna), fn(md.sq);
+  fn(md.corr), fn(md.rdf), fn(md.adf), fn(md.order), fn(md.cluster), fn(md.cna), fn(md.sq), fn(md.flux);
 }
 
 // device-resident relaxation (ta_api_relax.hip; the launches are in ta_relax.hip): FIRE velocities of its own,
@@ -419,6 +433,10 @@ struct ta_context {
   DevBuf<uint32_t> job_word_own;
   DevBuf<int32_t> job_count_own;
   bool triangles = true;
+  // A ta_md_run that samples the heat current is under way (set_centre_gradients): every evaluation leaves
+  // g_p = d e_c / d D_p, the gradient of the CENTRE's energy alone, in db.g together with the pair records. The
+  // triangle-once build and the folded EAM / ADP force kernels do not, and step aside while this is set.
+  bool centre_gradients = false;
   // the last second-generation forward pass left the full job list (db.job_word / job_count) behind: it
   // does not when every backward launch of its evaluation read the owned lists (forward_v2_launches)
   bool full_jobs_valid = false;
@@ -492,6 +510,10 @@ void staged_copy(double *dst, const double *src, size_t n, bool to_host, const t
 void wait_stream(hipStream_t s, const ta::Options &opt);
 void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms);
 void apply_filter(ta_context *h);
+// Switches ta_context::centre_gradients. A plain EAM model then evaluates through eam_pair_kernel and the force
+// gather, on the resident (skin) list itself: its per-pair launches walk [0, n_pairs), which the exact list of
+// apply_filter does not admit. Switched off, the exact list comes back. Throws.
+void set_centre_gradients(ta_context *h, bool on);
 // the resident frames again with new coordinates (cells: null = unchanged): the rebuild path of
 // ta_update_positions and the resident runs; throws
 void rebuild_list(ta_context *h, const double *positions, const double *cells);

@@ -714,7 +714,7 @@ __global__ __launch_bounds__(kBlock) void eam_geom_kernel(DeviceBatch b, double 
     dst[1] = make_double2(D[2], r2);
     dst[2] = make_double2(1.0 / r, 0.0);
   }
-  rbuf[q] = r;
+  if (rbuf) rbuf[q] = r;
 }
 
 // nn functions the launch evaluates: (class, element or pair type), one per blockIdx.y
@@ -1614,6 +1614,7 @@ struct EamModel {
   bool tables_on = false, trained = false;
   bool pair_nets_exact = false;
   EamParams p_exact;              // function masks of the exact evaluation
+  bool pair_route = false;        // eam_set_pair_route
   std::vector<TabDev> tabs_host;  // [n_slots] file tables and, while tables_on, the nn pair functions
   std::vector<double *> nn_coef;  // [n_slots] device coefficients of an nn function's table (or null)
   double *knot_fv = nullptr;      // [2 kNnTableKnots] scratch
@@ -2040,6 +2041,8 @@ void eam_tabulate(EamModel *m, int n_r, const double *r, int n_rho, const double
 
 // centre-driven kernels only (atom + force kernel): no per-pair launch that walks [0, n_pairs)
 bool eam_is_plain(const EamModel *m) { return !m->p.adp && !m->pair_nets; }
+
+void eam_set_pair_route(EamModel *m, bool on) { m->pair_route = on; }
 
 void eam_set_list_cutoff(EamModel *m, double rc) { m->p.list_rc2 = rc > 0.0 ? rc * rc + m->eps : 0.0; }
 
@@ -2707,7 +2710,13 @@ void eam_compute(EamModel *m, const DeviceBatch &b, uint32_t want, hipStream_t s
   // analytic / tabulated pair functions: forces in one pass per centre (eam_force_kernel,
   // adp_force_kernel); nn pair functions: dE/dD per pair, then the shared force gather
   const bool want_f = (want & (TA_WANT_FORCES | TA_WANT_VIRIAL)) && b.n_pairs > 0;
-  const bool fold = want_f && !pair_nets;
+  const bool fold = want_f && !pair_nets && !m->pair_route;
+  // eam_set_pair_route without nn pair functions: the pair kernel and the gather read the pair records, which only
+  // the geometry launch of the nn path writes (no per-pair columns: rbuf is null)
+  const bool records = want_f && !pair_nets && m->pair_route;
+  if (records)
+    hipLaunchKernelGGL(eam_geom_kernel, dim3((unsigned)((b.n_pairs + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, b,
+                       m->eps, static_cast<double *>(nullptr));
   // lanes per atom (measured, 4000-atom Ni frames, rc 6.5, us per frame for W = 16 / 32 / 64): EAM one
   // frame 25.5 / 26.2 / 28.0, 64 frames 11.3 / 14.1 / 16.7; ADP (one-pass force kernel, W = 16 / 32)
   // one frame 36.6 / 36.0, 64 frames 18.0 / 21.0
@@ -2715,7 +2724,7 @@ void eam_compute(EamModel *m, const DeviceBatch &b, uint32_t want, hipStream_t s
   by_model(fs, other, W, [&](auto o, auto f, auto w) {
     hipLaunchKernelGGL((eam_atom_kernel<o, w, f>), dim3((unsigned)((b.n_atoms * w + kBlock - 1) / kBlock)),
                        dim3(kBlock), 0, s, m->p, b, m->dF, m->mom, m->eps, m->pf, ps, m->rho_buf,
-                       pair_nets ? 1 : 2, m->tabs_dev);
+                       (pair_nets || records) ? 1 : 2, m->tabs_dev);
   });
   if (m->embed_nets) {
     EmbedTiles t;

@@ -100,6 +100,10 @@ void eam_compute(EamModel *, const DeviceBatch &b, uint32_t want, hipStream_t s,
                  hipEvent_t *ev /* 2 events or null */);
 void eam_set_list_cutoff(EamModel *, double rc /* 0: the list is exact, no test */);
 bool eam_is_plain(const EamModel *);
+// on: forces go through eam_pair_kernel and the force gather (the route of the nn pair functions) for every model,
+// so that an evaluation leaves the pair records and g[p] = the centre's terms of dE/dD; off (the default): analytic
+// and tabulated pair functions take the one-pass force kernels
+void eam_set_pair_route(EamModel *, bool on);
 void eam_set_nn_tables(EamModel *, bool on);
 bool eam_hvp_supported(const EamModel *);
 size_t eam_hvp_extra_doubles(const EamModel *, const DeviceBatch &b, int n_dir);

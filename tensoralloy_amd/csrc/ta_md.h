@@ -260,7 +260,38 @@ struct MdSqLaunch {
   int n_q, n_lags, n_elements, n_frames, n_blk, chunk, currents;
 };
 
+constexpr int kMdFluxLanes = 16;  // lanes per centre of the pair sweep (one DPP row, as in the force gather)
+constexpr int kMdFluxRow = 18;    // doubles of a sample's row: J_conv[3], J_pot[3], K[6], W[6] (xx yy zz yz xz xy)
+
+// Atoms per workgroup of the pair sweep for a batch of n_atoms: one pass of 16 centres for small batches, four for
+// large ones, which write fewer partials (the plan, blk_start, is made once by ta_md_set_flux)
+inline int md_flux_chunk(long long n_atoms) { return n_atoms <= 16384 ? 16 : 64; }
+
+// Arguments of the three heat-current / pressure-tensor launches (ta_md_flux.hip) that ta_md_run puts behind an
+// integrator launch that wrote the velocities of a sampled whole-step state to `v`: the pair sweep over the list,
+// records, g and eatom of the evaluation in front of that launch (DeviceBatch, the second kernel argument), the sum
+// of the workgroups' partials into ring slot n % n_lags and onto `sums`, and the correlation of that row with the
+// rows of the lags 0 .. min(n, n_lags - 1). A row is [F][kMdFluxRow].
+struct MdFluxLaunch {
+  const double *v;                // [N][3] the velocities the integrator launch in front wrote
+  const double *mass;             // [N]
+  const int32_t *blk_start;       // [F + 1] first workgroup of each frame (at least one each)
+  double *part;                   // [n_blk][kMdFluxRow] per-workgroup sums
+  double *ring;                   // [n_lags] rows
+  double *sums;                   // [F][kMdFluxRow] the sum of all rows
+  double *acc_heat;               // [F][n_lags][3] sum over time origins of J_a(n) J_a(n - k), J = J_conv + J_pot
+  double *acc_press;              // [F][n_lags][6] likewise of Pi_ab(n) Pi_ab(n - k), Pi = K - W
+  const unsigned *status;         // the integrator's status word and
+  unsigned seq;                   // sequence number: the same predicate
+  long long n;                    // index of the newest sample
+  int n_lags, n_frames, n_blk, chunk;
+};
+
+struct DeviceBatch;
+
 void launch_md_integrate(const MdLaunch &a, int threads, hipStream_t s);
+
+void launch_md_flux(const MdFluxLaunch &a, const DeviceBatch &b, hipStream_t s);
 
 void launch_md_correlate(const MdCorrLaunch &a, hipStream_t s);
 

@@ -1,5 +1,5 @@
 // What the error messages say about each sampler of the device MD loop (ta_md_set_sampling, _rdf, _adf, _order,
-// _clusters, _cna, _sq), and the functions that compose them. The texts are part of the documented behaviour.
+// _clusters, _cna, _sq, _flux), and the functions that compose them. The texts are part of the documented behaviour.
 // Plain C++ with no HIP include (tests/test_md_sampler_text_cpu.py compiles it alone).
 #pragma once
 #include <string>
@@ -23,6 +23,8 @@ constexpr MdSamplerText order = {"ta_md_set_order", "the bond-orientational orde
 constexpr MdSamplerText cluster = {"ta_md_set_clusters", "the cluster analysis is off", "data", "buffers", "the feature is off"};
 constexpr MdSamplerText cna = {"ta_md_set_cna", "the common neighbour analysis is off", "data", "buffers", "the feature is off"};
 constexpr MdSamplerText sq = {"ta_md_set_sq", "the structure factors are off", "data", "buffers", "the feature is off"};
+constexpr MdSamplerText flux = {"ta_md_set_flux", "the heat current and pressure tensor are off", "data", "buffers",
+                                "the feature is off"};
 }  // namespace md_text
 
 // `who` (a getter) found the sampler off

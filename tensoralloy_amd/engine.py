@@ -44,6 +44,7 @@ class Engine:
         self._md_order_degrees = ()        # its degrees
         self._md_order_solid = (0, 0.0)    # and (solid_degree, threshold)
         self._md_sq = (0, 1, False)        # `md_set_sq` is on: (n_q, n_lags, currents)
+        self._md_flux_lags = 0             # `md_set_flux` is on: n_lags
         self._md_cluster = (0, 1)          # `md_set_clusters` is on: (n_bins, n_series)
         self._md_cna = 0                   # `md_set_cna` is on: n_series
         self._n_elements = int(desc.n_elements)
@@ -294,6 +295,8 @@ class Engine:
                 self._md_lags = 0
             if b"ta_md_set_sq" in msg:
                 self._md_sq = (0, 1, False)
+            if b"ta_md_set_flux" in msg:
+                self._md_flux_lags = 0
         elif rc == _lib.TA_ERR_INVALID and b"ta_md_set_sq" in (self._lib.ta_last_error(self._handle) or b""):
             self._md_sq = (0, 1, False)   # (a batch without wave vectors: the library switched the feature off)
         self._check(rc)
@@ -821,6 +824,79 @@ class Engine:
         if cur:
             j = (j[..., 0] + 1j * j[..., 1])[:n][::-1].copy()
         return {"rho": rho, "cur": j, "steps": steps[:n][::-1].copy()}
+
+    def md_set_flux(self, n_lags=0, sample_every=1):
+        """Heat current and pressure tensor inside `md_run` (`ta_md_set_flux`), the two Green-Kubo observables. At
+        every step t (counted since `md_init`) with t % `sample_every` == 0 the loop makes, per frame and in fp64,
+        the row {J_conv[3], J_pot[3], K[6], W[6]} (six components: xx yy zz yz xz xy) from the per-atom energies and
+        per-pair gradients of the evaluation of that state: J_conv = sum_i (m_i |v_i|^2 / 2 + e_i) v_i,
+        J_pot = - sum_p D_p (g_p . v_n), K_ab = sum_i m_i v_ia v_ib, W_ab the symmetrised virial, Pi = K - W = P V.
+        It keeps the last `n_lags` rows in a ring on the device and adds J_a(n) J_a(n - k) (J = J_conv + J_pot) and
+        Pi_ab(n) Pi_ab(n - k) at every lag k onto accumulators that stay on the device (`md_flux`, `md_flux_rows`).
+        No centre-of-mass correction and no partial-enthalpy correction for mixtures is made. `n_lags` = 0 switches
+        it off (the default) and frees the buffers. Needs `md_init`; every call starts an empty ring and zero
+        accumulators, as `md_init` does. The setting stays on across `set_frames`. It runs under every thermostat
+        and beside every other sampler; `md_run` refuses it under the barostat. While it is on, the evaluations of
+        `md_run` take the builds that leave the centre-side pair gradients (per-apex instead of triangle-once; pair
+        kernel and force gather instead of the folded EAM / ADP force kernels): the trajectory agrees with an
+        unsampled run to rounding, not bit for bit."""
+        p = _lib.MdFluxParams(int(n_lags), int(sample_every))
+        rc = self._lib.ta_md_set_flux(self._handle, C.byref(p))
+        if rc == _lib.TA_ERR_NOMEM:   # (no room: the library switched the feature off)
+            self._md_flux_lags = 0
+        self._check(rc)
+        self._md_flux_lags = int(n_lags)
+
+    @property
+    def md_flux_lags(self):
+        """Rows per frame that `md_set_flux` switched on, 0 while the feature is off."""
+        return self._md_flux_lags
+
+    def _md_flux_info(self, who):
+        if self.info is None:
+            raise ValueError(f"{who}: no resident batch (call set_frames first)")
+        info = (C.c_int64 * 8)()
+        null = C.POINTER(C.c_double)()
+        self._check(self._lib.ta_md_get_flux(self._handle, null, null, null, info))
+        return info
+
+    def md_flux(self):
+        """What the loop has accumulated since `md_set_flux` (`ta_md_get_flux`), a dict: `sums` [n_frames, 18] (the sum
+        of all rows), `a_heat` [n_frames, n_lags, 3] and `a_press` [n_frames, n_lags, 6] (sums over the time origins
+        of J_a(n) J_a(n - k) and Pi_ab(n) Pi_ab(n - k)); `n_origins` [n_lags] = max(0, n_samples - k); `n_samples`,
+        `n_lags`, `sample_every`, `last_step` and `first_step` (absolute steps of the newest and the first sample,
+        -1: none), `chunk` (atoms per workgroup of the pair sweep), `blocks_per_frame` (the most workgroups of one
+        frame) and `lanes` (lanes per centre). `md.heat_current_acf` and `md.pressure_acf` normalise the sums."""
+        info = self._md_flux_info("md_flux")
+        F, L = int(self.info.n_frames), int(info[1])
+        sums, a_heat, a_press = np.zeros((F, _lib.TA_MD_FLUX_ROW)), np.zeros((F, L, 3)), np.zeros((F, L, 6))
+        self._check(self._lib.ta_md_get_flux(self._handle, _lib.as_dp(sums), _lib.as_dp(a_heat), _lib.as_dp(a_press), info))
+        n_samples = int(info[0])
+        return {"sums": sums, "a_heat": a_heat, "a_press": a_press,
+                "n_origins": np.maximum(0, n_samples - np.arange(L)).astype(np.int64), "n_samples": n_samples,
+                "n_lags": L, "sample_every": int(info[2]), "last_step": int(info[3]), "first_step": int(info[4]),
+                "chunk": int(info[5]), "blocks_per_frame": int(info[6]), "lanes": int(info[7])}
+
+    def md_flux_rows(self, n=None):
+        """The last `n` rows the ring holds, oldest first (`ta_md_get_flux_rows`; default: all, min(n_samples,
+        n_lags)): a dict `rows` [n, n_frames, 18], its views `j_conv`, `j_pot` [n, n_frames, 3] and `kinetic`,
+        `virial` [n, n_frames, 6], and `steps` [n] (absolute steps)."""
+        if self.info is not None:   # (its own refusals)
+            self._check(self._lib.ta_md_get_flux_rows(self._handle, 0, 0, C.POINTER(C.c_double)(), None))
+        info = self._md_flux_info("md_flux_rows")
+        if n is None:
+            n = min(int(info[0]), int(info[1]))
+        n = int(n)
+        if n < 0:
+            raise ValueError("md_flux_rows: n must be >= 0")
+        F = int(self.info.n_frames)
+        rows = np.zeros((max(n, 1), F, _lib.TA_MD_FLUX_ROW))
+        steps = np.zeros(max(n, 1), dtype=np.int64)
+        self._check(self._lib.ta_md_get_flux_rows(self._handle, 0, n, _lib.as_dp(rows),
+                                                  steps.ctypes.data_as(C.POINTER(C.c_int64))))
+        rows = rows[:n][::-1].copy()
+        return {"rows": rows, "j_conv": rows[..., 0:3], "j_pot": rows[..., 3:6], "kinetic": rows[..., 6:12],
+                "virial": rows[..., 12:18], "steps": steps[:n][::-1].copy()}
 
     def md_noise(self, step: int):
         """(xi, eta) [n_atoms, 3]: the standard normals the Langevin step with absolute index `step` (steps

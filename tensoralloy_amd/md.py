@@ -91,6 +91,17 @@ dispersions, sound velocities and damping are read. `intermediate_scattering` an
 sums (Ashcroft-Langreth partials), `transverse_current` splits the current trace, `dynamic_structure_factor`
 transforms to S(q, nu), `shell_average` bins over |q|. Everything is fp64 with a fixed order of addition: a run cut
 into calls gives the same bits. Refused under the barostat.
+
+Heat current and pressure tensor: with `flux_lags` (and `flux_every`) the loop makes, at every sampled step, the heat
+current J = J_conv + J_pot and the pressure tensor Pi = K - W = P V of every frame from the model's per-atom energies
+and per-pair gradients, which exist only on the device and only for one evaluation, keeps the last `flux_lags` rows
+and correlates them at every lag (`Engine.md_set_flux`; `DeviceMD.get_heat_current_acf`, `get_pressure_acf`):
+the two Green-Kubo observables, the lattice thermal conductivity (`green_kubo_thermal_conductivity`) and the shear
+viscosity (`green_kubo_viscosity`), that a dumped trajectory cannot give. `heat_current_acf` and `pressure_acf`
+normalise the sums. No centre-of-mass correction is made and no partial-enthalpy correction for mixtures: in a
+mixture J contains the interdiffusion part. Everything is fp64 with a fixed order of addition. While it is on, the
+evaluations of a run take the builds that leave the centre-side pair gradients, so the trajectory agrees with an
+unsampled one to rounding, not bit for bit. Refused under the barostat.
 """
 from __future__ import annotations
 
@@ -104,7 +115,8 @@ bar = 1.0e-4 * GPa
 __all__ = ["fs", "kB", "GPa", "bar", "maxwell_boltzmann", "DeviceMD", "vdos", "diffusion_coefficient",
            "green_kubo_diffusion", "rdf", "coordination_number", "adf", "order_distribution", "solid_fraction",
            "classify_solid", "largest_cluster", "cluster_size_distribution", "clusters_from_labels", "CNA_NAMES", "structure_fractions", "q_points", "intermediate_scattering", "structure_factor", "transverse_current",
-           "dynamic_structure_factor", "shell_average"]
+           "dynamic_structure_factor", "shell_average", "heat_current_acf", "pressure_acf",
+           "green_kubo_thermal_conductivity", "green_kubo_viscosity"]
 
 
 def maxwell_boltzmann(masses, kT, rng, zero_momentum=True):
@@ -482,6 +494,81 @@ def shell_average(values, q_norm, n_bins):
     return q, mean, counts
 
 
+def _origins(who, acc, n_samples):
+    a = np.asarray(acc, dtype=np.float64)
+    if a.ndim < 2:
+        raise ValueError(f"{who}: the sums must be [..., n_lags, components]")
+    n = int(n_samples) - np.arange(a.shape[-2])
+    return a, np.where(n > 0, n, 1).astype(np.float64), n > 0
+
+
+def heat_current_acf(a_heat, n_samples):
+    """<J_a(t_k) J_a(0)> [..., 3, n_lags] from the sums `a_heat` [..., n_lags, 3] of `Engine.md_flux`: lag k is
+    divided by its n_samples - k time origins (NaN where there is none). The mean of J is not subtracted: it
+    vanishes in equilibrium. Units: (eV A / ASE time)^2."""
+    a, n, ok = _origins("heat_current_acf", a_heat, n_samples)
+    return np.swapaxes(np.where(ok[:, None], a / n[:, None], np.nan), -1, -2)
+
+
+def pressure_acf(a_press, sums, n_samples):
+    """<dPi_ab(t_k) dPi_ab(0)> [..., 6, n_lags] (xx yy zz yz xz xy) from the sums `a_press` [..., n_lags, 6] and
+    `sums` [..., 18] of `Engine.md_flux`: lag k is divided by its n_samples - k time origins (NaN where there is
+    none), and the SQUARED MEAN of Pi_ab = K_ab - W_ab over all samples, taken from `sums`, is subtracted, so that the
+    diagonal components fluctuate about the mean pressure (the shear components have mean zero in a liquid and keep
+    a residual stress in a solid). Units: eV^2."""
+    a, n, ok = _origins("pressure_acf", a_press, n_samples)
+    r = np.asarray(sums, dtype=np.float64)
+    if r.shape[-1] != 18 or r.shape[:-1] != a.shape[:-2] or a.shape[-1] != 6:
+        raise ValueError("pressure_acf: a_press [..., n_lags, 6] and sums [..., 18] are needed")
+    mean = (r[..., 6:12] - r[..., 12:18]) / max(int(n_samples), 1)
+    return np.swapaxes(np.where(ok[:, None], a / n[:, None] - mean[..., None, :] ** 2, np.nan), -1, -2)
+
+
+_EV_IN_J = 1.0e-21 / GPa      # 1 eV / A^3 = (1 / GPa) GPa
+_TIME_IN_S = 1.0e-15 / fs     # one ASE time unit in seconds
+
+
+def _running_integral(y, dx):
+    y = np.asarray(y, dtype=np.float64)
+    return np.stack([_trapezoid(y[..., :k + 1], dx) for k in range(y.shape[-1])], axis=-1)
+
+
+def _green_kubo_arguments(who, acf, volume, temperature_K, dt_sample):
+    c = np.asarray(acf, dtype=np.float64)
+    if c.ndim < 2 or c.shape[-1] < 1:
+        raise ValueError(f"{who}: acf must be [..., components, n_lags]")
+    v = np.asarray(volume, dtype=np.float64)
+    if not (np.all(np.isfinite(v)) and np.all(v > 0.0)):
+        raise ValueError(f"{who}: volume must be finite and > 0")
+    if not (np.isfinite(temperature_K) and temperature_K > 0.0):
+        raise ValueError(f"{who}: temperature_K must be finite and > 0")
+    if not (np.isfinite(dt_sample) and dt_sample > 0.0):
+        raise ValueError(f"{who}: dt_sample must be a finite time > 0")
+    return c, v[..., None, None] if v.ndim else v
+
+
+def green_kubo_thermal_conductivity(acf, volume, temperature_K, dt_sample):
+    """Running Green-Kubo integral kappa_a(t_k) = 1 / (V kB T^2) int_0^{t_k} <J_a(t) J_a(0)> dt [..., 3, n_lags], in
+    W / (m K), of a heat-current autocorrelation `acf` [..., 3, n_lags] (`heat_current_acf`) sampled every `dt_sample`
+    (ASE time units) in the volume `volume` (A^3; a scalar or one per leading index) at `temperature_K`
+    (trapezoidal rule). Read the plateau; the mean of the three axes is the conductivity of an isotropic system."""
+    c, v = _green_kubo_arguments("green_kubo_thermal_conductivity", acf, volume, temperature_K, dt_sample)
+    si = _EV_IN_J / (1.0e-10 * _TIME_IN_S)   # eV / (A ASE-time K) in W / (m K)
+    return _running_integral(c, float(dt_sample)) / (v * kB * float(temperature_K) ** 2) * si
+
+
+def green_kubo_viscosity(acf, volume, temperature_K, dt_sample):
+    """Running Green-Kubo integral eta_ab(t_k) = 1 / (V kB T) int_0^{t_k} <Pi_ab(t) Pi_ab(0)> dt over the shear
+    components yz, xz, xy [..., 3, n_lags], in mPa s, of a pressure-tensor autocorrelation `acf` [..., 6, n_lags]
+    (`pressure_acf`) sampled every `dt_sample` (ASE time units) in the volume `volume` (A^3) at `temperature_K`
+    (trapezoidal rule). Read the plateau; the mean of the three is the shear viscosity of an isotropic liquid."""
+    c, v = _green_kubo_arguments("green_kubo_viscosity", acf, volume, temperature_K, dt_sample)
+    if c.shape[-2] != 6:
+        raise ValueError("green_kubo_viscosity: acf must be [..., 6, n_lags]")
+    si = _EV_IN_J / 1.0e-30 * _TIME_IN_S * 1.0e3   # eV ASE-time / A^3 in mPa s
+    return _running_integral(c[..., 3:6, :], float(dt_sample)) / (v * kB * float(temperature_K)) * si
+
+
 class DeviceMD:
     """
     NVE (velocity Verlet), Berendsen NVT, Langevin NVT or Nose-Hoover chain NVT dynamics of one structure or of a batch of
@@ -556,6 +643,12 @@ class DeviceMD:
                            directions and excludes the barostat. Without `sq_miller` no method of the structure
                            factors is called on the engine, unless its `md_sq_vectors` says that an earlier
                            `DeviceMD` left them on: they are then switched off
+    flux_lags, flux_every : `flux_lags` given (1 .. 4096): the loop makes the heat current and the pressure tensor of
+                           every `flux_every`-th step (the state at construction is the first sample), keeps
+                           `flux_lags` rows and correlates them on the device (`get_heat_current_acf`,
+                           `get_pressure_acf`); excludes the barostat. Without `flux_lags` no method of the sampler
+                           is called on the engine, unless its `md_flux_lags` says that an earlier `DeviceMD` left
+                           it on: it is then switched off
 
     Under the barostat the cell of every `Atoms` follows (the atoms are not scaled again), and every `run` call
     that moved the cells ends with one neighbour-list build for the final cells: an observer at interval 1
@@ -570,7 +663,7 @@ class DeviceMD:
                  adf_every=1, order_degrees=None, order_rbond=None, order_bins=None, order_every=1, order_solid=None,
                  sq_miller=None, sq_lags=None, sq_every=1, sq_currents=False, cluster_bins=None, cluster_rlink=None,
                  cluster_nmin=0, cluster_species=None, cluster_series=1, cluster_every=1, cna=None, cna_rcut=None,
-                 cna_rmax=None, cna_series=1, cna_every=1):
+                 cna_rmax=None, cna_series=1, cna_every=1, flux_lags=None, flux_every=1):
         if not (np.isfinite(timestep) and timestep > 0.0):
             raise ValueError("DeviceMD: timestep must be a finite time > 0")
         barostat = (pressure, taup, compressibility)
@@ -704,6 +797,17 @@ class DeviceMD:
                                  "compressibility): cell and positions of a snapshot would belong to different states")
         elif sq_lags is not None or sq_every != 1 or sq_currents is not False:
             raise ValueError("DeviceMD: sq_lags, sq_every and sq_currents belong to the structure factors (sq_miller)")
+        if flux_lags is not None:
+            whole = lambda a: isinstance(a, (int, np.integer)) and not isinstance(a, bool)
+            if not (whole(flux_lags) and 1 <= flux_lags <= 4096):
+                raise ValueError("DeviceMD: flux_lags must be an integer 1 .. 4096")
+            if not (whole(flux_every) and flux_every >= 1):
+                raise ValueError("DeviceMD: flux_every must be an integer >= 1")
+            if self._barostat:
+                raise ValueError("DeviceMD: flux_lags (heat current and pressure tensor) excludes the barostat "
+                                 "(pressure, taup, compressibility): normalising the correlations needs one volume")
+        elif flux_every != 1:
+            raise ValueError("DeviceMD: flux_every belongs to the heat current and pressure tensor (flux_lags)")
         if self._barostat:
             if any(p is None for p in barostat):
                 raise ValueError("DeviceMD: the barostat needs pressure, taup and compressibility")
@@ -837,6 +941,12 @@ class DeviceMD:
                              self._sq_every, self._sq_currents)
         elif getattr(engine, "md_sq_vectors", 0):
             engine.md_set_sq(None)
+        self._flux_lags = int(flux_lags) if flux_lags is not None else 0
+        self._flux_every = int(flux_every)
+        if self._flux_lags:   # (opt-in in the same way)
+            engine.md_set_flux(self._flux_lags, self._flux_every)
+        elif getattr(engine, "md_flux_lags", 0):
+            engine.md_set_flux(0)
         self._natoms = np.array([len(a) for a in self.atoms_list], dtype=np.int64)
         self.velocities = velocities.copy()
         self.epot = self.ekin = None   # per-frame records of the last state
@@ -1028,6 +1138,26 @@ class DeviceMD:
             res.append(intermediate_scattering(transverse_current(out["a_j"], out["a_l"]), out["n_samples"],
                                                out["n_by_element"]))
         return (t,) + tuple(r[0] if self._single else r for r in res)
+
+    def get_heat_current_acf(self):
+        """(t, C): the lag times arange(flux_lags) * flux_every * timestep and <J_a(t) J_a(0)> [3, flux_lags] (a
+        batch: [n_frames, 3, flux_lags]) over every time origin sampled so far, as `heat_current_acf` normalises it;
+        `green_kubo_thermal_conductivity` integrates it. Needs `flux_lags`."""
+        if not self._flux_lags:
+            raise ValueError("DeviceMD.get_heat_current_acf: the heat current is off (flux_lags)")
+        out = self.engine.md_flux()
+        c = heat_current_acf(out["a_heat"], out["n_samples"])
+        return np.arange(out["n_lags"]) * self._flux_every * self.dt, c[0] if self._single else c
+
+    def get_pressure_acf(self):
+        """(t, C): the lag times and <dPi_ab(t) dPi_ab(0)> [6, flux_lags] (xx yy zz yz xz xy; a batch: [n_frames, 6,
+        flux_lags]) with Pi = P V, the squared mean over all samples subtracted, as `pressure_acf` normalises it;
+        `green_kubo_viscosity` integrates its shear components. Needs `flux_lags`."""
+        if not self._flux_lags:
+            raise ValueError("DeviceMD.get_pressure_acf: the pressure tensor is off (flux_lags)")
+        out = self.engine.md_flux()
+        c = pressure_acf(out["a_press"], out["sums"], out["n_samples"])
+        return np.arange(out["n_lags"]) * self._flux_every * self.dt, c[0] if self._single else c
 
     def get_volume(self):
         """Cell volume per frame, in A^3."""
