@@ -19,7 +19,7 @@ CSRC_DIR = PKG_DIR / "csrc"
 INCLUDE_DIR = REPO_DIR / "include"
 LIB_PATH = PKG_DIR / "libtensoralloy_amd.so"
 
-SOURCES = ["ta_api.hip", "ta_api_md.hip", "ta_api_relax.hip", "ta_resident.hip", "ta_kernels.hip", "ta_kernels_v2.hip", "ta_mlp.hip", "ta_eam.hip",
+SOURCES = ["ta_api.hip", "ta_api_train.hip", "ta_api_md.hip", "ta_api_relax.hip", "ta_resident.hip", "ta_kernels.hip", "ta_kernels_v2.hip", "ta_mlp.hip", "ta_eam.hip",
            "ta_nlist.hip", "ta_grap.hip", "ta_train.hip", "ta_hvp.hip", "ta_neighbor.cpp", "ta_td.hip",
            "ta_td_train.hip", "ta_md.hip", "ta_md_corr.hip", "ta_md_rdf.hip", "ta_md_adf.hip", "ta_md_order.hip", "ta_md_cluster.hip", "ta_md_cna.hip", "ta_md_sq.hip", "ta_md_flux.hip", "ta_relax.hip", "ta_neb.hip",
            "ta_options.cpp"]

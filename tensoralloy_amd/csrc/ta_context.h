@@ -1,4 +1,4 @@
-// The handle behind the C ABI and what the host translation units (ta_api, ta_api_md, ta_api_relax,
+// The handle behind the C ABI and what the host translation units (ta_api, ta_api_train, ta_api_md, ta_api_relax,
 // ta_resident .hip) share: error mapping, self-freeing buffers, and the helpers that ta_api.hip defines
 // for the others. Private to the library; the public interface is include/tensoralloy_amd.h.
 #pragma once
@@ -509,6 +509,11 @@ int fail(ta_context *h, int code, const std::string &msg);  // keeps the message
 void staged_copy(double *dst, const double *src, size_t n, bool to_host, const ta::Options &opt, hipStream_t s);
 void wait_stream(hipStream_t s, const ta::Options &opt);
 void compute_impl(ta_context *h, uint32_t want, bool timed, double *slot_ms);
+// for ta_api_train.hip: the forward launches of the second-generation angular path alone (`tri`: see the definition),
+// and the texts of the two inference-only refusals
+void forward_v2_launches(ta_context *h, bool tri);
+std::string td_inference_only(const char *fn);
+std::string fs_inference_only(const char *fn);
 void apply_filter(ta_context *h);
 // Switches ta_context::centre_gradients. A plain EAM model then evaluates through eam_pair_kernel and the force
 // gather, on the resident (skin) list itself: its per-pair launches walk [0, n_pairs), which the exact list of
