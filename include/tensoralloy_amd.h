@@ -1315,6 +1315,15 @@ enum { TA_MLP_NONE = 0, TA_MLP_TILE = 1, TA_MLP_TILE_ALL = 2, TA_MLP_WAVE = 3, T
 enum { TA_MLP_DA_REGISTERS = 0, TA_MLP_DA_LDS = 1, TA_MLP_DA_GLOBAL = 2 };
 int ta_mlp_launch_info(ta_handle h, int64_t *info /*[8]*/);
 
+/* Which body the 16-row tile kernels of the last evaluation ran (read-only, like ta_mlp_launch_info):
+ * TA_MLP_BODY_NONE when the last launch was not a tile launch, TA_MLP_BODY_GENERIC (every network shape),
+ * TA_MLP_BODY_SCALAR (hidden layers without skip connections and one linear output unit: no padded output-layer
+ * GEMMs, no elementwise passes) or, for an all-elements launch whose networks differ, TA_MLP_BODY_MIXED. Elements
+ * without atoms in the batch do not count. TA_MLP_TILE_GENERIC=1 in the environment at ta_create forces the
+ * generic body. */
+enum { TA_MLP_BODY_NONE = 0, TA_MLP_BODY_GENERIC = 1, TA_MLP_BODY_SCALAR = 2, TA_MLP_BODY_MIXED = 3 };
+int ta_mlp_tile_body(ta_handle h, int32_t *body);
+
 /* debugging / parity: host copy of the pair list of the resident batch
  * (centre, neighbour, shift[3]) in the library's order. Arrays sized n_pairs. */
 int ta_get_pairs(ta_handle h, int32_t *i, int32_t *j, int32_t *shift /*[n][3]*/);

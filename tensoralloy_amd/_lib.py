@@ -37,6 +37,7 @@ TA_N_KERNEL_SLOTS = 10
 # ta_mlp_launch_info: info[0] (family) and info[7] (where act' lived)
 TA_MLP_FAMILY = {0: "none", 1: "tile", 2: "tile_all", 3: "wave", 4: "wave_all", 5: "quad", 6: "quad_all", 7: "td"}
 TA_MLP_DA = {0: "registers", 1: "lds", 2: "global"}
+TA_MLP_BODY = {0: "none", 1: "generic", 2: "scalar", 3: "mixed"}  # ta_mlp_tile_body
 # ta_model_desc.finite_temperature: bit 0 = temperature-dependent, bit 1 = Sommerfeld, bits 8-15 = H activation
 TA_TD_ON, TA_TD_SOMMERFELD, TA_TD_ACT_SHIFT = 1, 2, 8
 TA_LIST_VIEW = {"resident": 0, "kernel": 1}  # ta_list_info / ta_get_list
@@ -55,7 +56,7 @@ EXPORTED_SYMBOLS = [
     "ta_count_contributing_triples", "ta_loss_gradient", "ta_constant_count", "ta_get_constants", "ta_update_constants",
     "ta_constant_gradient", "ta_list_sizes", "ta_abi_version", "ta_model_desc_size", "ta_set_nn_tables", "ta_step", "ta_hessian_vectors", "ta_view_results", "ta_step_view",
     "ta_set_electron_temperatures", "ta_get_td_results", "ta_td_loss_gradient",
-    "ta_set_triangles", "ta_backward_variant", "ta_mlp_launch_info", "ta_count_owned_triangles", "ta_triangle_owner",
+    "ta_set_triangles", "ta_backward_variant", "ta_mlp_launch_info", "ta_mlp_tile_body", "ta_count_owned_triangles", "ta_triangle_owner",
     "ta_filter_param_count", "ta_update_filter_weights", "ta_grap_loss_gradient",
     "ta_set_filter_tables", "ta_filter_table_knots",
     "ta_md_init", "ta_md_set_thermostat", "ta_md_run", "ta_md_get_state",
@@ -340,6 +341,7 @@ def load():
     lib.ta_set_triangles.argtypes = [H, C.c_int]
     lib.ta_backward_variant.argtypes = [H, C.POINTER(C.c_int32)]
     lib.ta_mlp_launch_info.argtypes = [H, C.POINTER(C.c_int64)]
+    lib.ta_mlp_tile_body.argtypes = [H, _ip]
     lib.ta_count_owned_triangles.argtypes = [H, C.POINTER(C.c_int64)]
     lib.ta_triangle_owner.argtypes = [C.c_int64, _ip, _ip]
     lib.ta_hessian_vectors.argtypes = [H, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]

@@ -283,6 +283,11 @@ void build_net(ta_context *h, ta::MlpDev &md, int L, const int32_t *sizes, const
     wsrc += (size_t)ly.k * ly.n;
     for (int n = 0; n < ly.n; ++n) bb[n] = wsrc[n];
     wsrc += ly.n;
+    // mlp_tile_scalar reads the scalar output layer as the vector wt[0 .. kp): hidden units beyond the logical
+    // width carry act(0) != 0 and drop out only because these entries are zero
+    if (l == L - 1 && ly.n == 1)
+      for (int k = ly.k; k < ly.kp; ++k)
+        if (wt[k] != 0.0) throw std::logic_error("padded output weights are not zero");
     ly.w = upload(h, w);
     ly.wt = upload(h, wt);
     ly.b = upload(h, bb);
@@ -560,10 +565,15 @@ void fill_pairs_on_device(ta_context *h) {
 #ifdef TA_PHASE_STAMPS
 // diagnostic builds: phase stamps of the angular kernels of the LAST evaluation, written to the file
 // named by TA_PHASE_STAMPS_OUT (Options::phase_stamps_out) at ta_destroy (scripts/phase_stamps.sh)
+// (kernel 0 / 1: the angular kernels; kernel 2: the MLP tile kernel, workgroups that stamped nothing left out)
+static size_t mlp_stamp_blocks(const ta_context *h) {  // at least the grid of a tile launch
+  return (size_t)h->db.n_atoms / ta::kMlpStampRows + (size_t)h->n_elements + 1;
+}
 static void dump_stamps(ta_context *h) {
   const std::string &path = h->opt.phase_stamps_out;
   if (path.empty() || !h->db.stamps || h->db.n_blk <= 0) return;
-  const size_t n = (size_t)2 * h->db.n_blk * ta::kStampSlots;
+  const size_t n_mlp = mlp_stamp_blocks(h);
+  const size_t n = (size_t)(2 * h->db.n_blk + n_mlp) * ta::kStampSlots;
   std::vector<unsigned long long> v(n);
   (void)hipStreamSynchronize(h->stream);
   (void)hipMemcpy(v.data(), h->db.stamps, n * sizeof(unsigned long long), hipMemcpyDeviceToHost);
@@ -576,6 +586,13 @@ static void dump_stamps(ta_context *h) {
         std::fprintf(fp, " %llu", v[((size_t)k * h->db.n_blk + b) * ta::kStampSlots + q]);
       std::fprintf(fp, "\n");
     }
+  for (size_t b = 0; b < n_mlp; ++b) {
+    const unsigned long long *row = &v[((size_t)2 * h->db.n_blk + b) * ta::kStampSlots];
+    if (!row[0]) continue;
+    std::fprintf(fp, "2 %zu", b);
+    for (int q = 0; q < ta::kStampSlots; ++q) std::fprintf(fp, " %llu", row[q]);
+    std::fprintf(fp, "\n");
+  }
   std::fclose(fp);
 }
 #endif
@@ -614,10 +631,12 @@ void ta::host::compute_impl(ta_context *h, uint32_t want, bool timed, double *sl
   using namespace ta;
 #ifdef TA_PHASE_STAMPS
   if (h->db.n_blk > 0) {
-    h->stamp_buf.ensure((size_t)2 * h->db.n_blk * ta::kStampSlots + 8);
+    const size_t n_mlp = mlp_stamp_blocks(h);
+    h->stamp_buf.ensure((size_t)(2 * h->db.n_blk + n_mlp) * ta::kStampSlots + 8);
     h->db.stamps = h->stamp_buf.ptr;
-    (void)hipMemsetAsync(h->db.stamps, 0, (size_t)2 * h->db.n_blk * ta::kStampSlots * sizeof(unsigned long long),
-                         h->stream);
+    h->db.mlp_stamps = h->stamp_buf.ptr + (size_t)2 * h->db.n_blk * ta::kStampSlots;
+    (void)hipMemsetAsync(h->db.stamps, 0,
+                         (size_t)(2 * h->db.n_blk + n_mlp) * ta::kStampSlots * sizeof(unsigned long long), h->stream);
   }
 #endif
   h->db.rec4 = nullptr;  // only the second-generation angular path below sets it
@@ -1666,6 +1685,12 @@ int ta_mlp_launch_info(ta_handle h, int64_t *info) {
   info[5] = m.grid_y;
   info[6] = m.lds_bytes;
   info[7] = m.da;
+  return TA_OK;
+}
+
+int ta_mlp_tile_body(ta_handle h, int32_t *body) {
+  if (!h || !body) return fail(h, TA_ERR_INVALID, "null argument");
+  *body = h->last_mlp_launch.body;
   return TA_OK;
 }
 

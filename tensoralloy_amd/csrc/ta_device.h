@@ -19,6 +19,7 @@ constexpr int kCapMin = 192;      // pair records one v2 workgroup (one wavefron
 constexpr int kCapMax = 1024;
 constexpr int kMaxCentersPerBlock = 16;  // centres one angular workgroup may own
 constexpr int kMaxHd = 24;        // coefficients of the Hd(u) expansion
+constexpr int kMlpStampRows = 16;  // ... atoms per workgroup of the MLP tile kernels (kMlpRows)
 constexpr int kStampSlots = 10;   // -DTA_PHASE_STAMPS builds: stamps per angular workgroup (DeviceBatch::stamps)
 
 // Symmetry-function constants, passed by value to every kernel.
@@ -135,6 +136,8 @@ struct DeviceBatch {
   // diagnostic builds only (scripts/phase_stamps.sh): s_memrealtime (100 MHz) at the phase boundaries
   // of the angular kernels, [kernel 0 / 1][workgroup][kStampSlots]
   unsigned long long *stamps = nullptr;
+  // ... and of the 16-row MLP tile kernels, [workgroup][kStampSlots] (ta_mlp.hip::TA_MLP_STAMP)
+  unsigned long long *mlp_stamps = nullptr;
 #endif
   double *bpart = nullptr;  // [ceil(N / 16)][10] {E, W[9]} of every group of 16 consecutive atoms
   double *energy = nullptr; // [F]
@@ -291,6 +294,7 @@ struct MlpLaunchInfo {
   int grid_x = 0, grid_y = 0;
   long long lds_bytes = 0;  // dynamic LDS of one workgroup
   int da = 0;               // where act' lived
+  int body = 0;             // TA_MLP_BODY_*: which body a tile launch ran (ta_mlp_tile_body)
 };
 
 void launch_pair_geometry(const SFParams &sf, const DeviceBatch &b, hipStream_t s);

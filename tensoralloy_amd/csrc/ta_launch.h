@@ -15,7 +15,7 @@ namespace ta {
 size_t mlp_scratch_doubles(const MlpDev &mlp);
 void launch_mlp_impl(const MlpDev &mlp, int activation, int ndim, const int32_t *atoms, int n_atoms,
                      const DeviceBatch &b, const Options &opt, double *scratch, hipStream_t s,
-                     MlpLaunchInfo *info = nullptr);
+                     MlpLaunchInfo *info = nullptr, bool identity_atoms = false);
 size_t mlp_all_scratch_doubles(const MlpDev *mlps_host, int nel, const int32_t *elem_start);
 size_t td_scratch_doubles(const MlpDev *nets, int nel, int K, const int32_t *elem_start, bool da_global);
 void launch_td_all(const MlpDev *nets_dev, const MlpDev *nets_host, int nel, int K, int act_h, int act,

@@ -1,8 +1,8 @@
-// Stand-alone per-atom element-wise MLP kernel: 16 atoms of one element per
-// workgroup, forward + backward-to-inputs on the fp64 matrix cores (see
-// ta_mlp_tile.h for the tile code and the reference ops it replaces). Used when
-// the fused per-centre kernel does not apply (radial-only models, several
-// parameter chunks, more than 3 elements, very large neighbour counts).
+// The per-atom element-wise MLP kernels of an evaluation: forward + backward-to-inputs on the fp64
+// matrix cores, 16 atoms of one element per tile (see ta_mlp_tile.h for the tile code and the
+// reference ops it replaces). Three families, chosen by the tile count and the network's shape
+// (launch_mlp_impl / launch_mlp_all): the 16-row tile kernels with activations in LDS, the
+// one-wavefront throughput kernels and the four / eight-wavefront kernels with transposed GEMMs.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,6 +12,40 @@
 #include <stdexcept>
 
 #include "ta_device.h"
+
+#ifdef TA_PHASE_STAMPS
+// diagnostic builds: the tile kernels' phase boundaries (s_memrealtime) collected in LDS by thread 0 and
+// written to DeviceBatch::mlp_stamps[workgroup][kStampSlots] at the kernel's end. Slot 0 entry, 1 rows staged,
+// then one per forward GEMM phase, energies emitted, one per backward GEMM phase, dE/dG stored.
+namespace ta {
+static __shared__ unsigned long long s_mlp_stamp[kStampSlots];
+}
+#define TA_MLP_STAMP(k)                                                                               \
+  do {                                                                                                \
+    const int k_ = (k);                                                                               \
+    if (threadIdx.x == 0 && k_ < ta::kStampSlots) ta::s_mlp_stamp[k_] = __builtin_amdgcn_s_memrealtime(); \
+  } while (0)
+#define TA_MLP_STAMP_BEGIN()                                                       \
+  do {                                                                             \
+    if (threadIdx.x == 0) {                                                        \
+      for (int q_ = 1; q_ < kStampSlots; ++q_) s_mlp_stamp[q_] = 0;                \
+      s_mlp_stamp[0] = __builtin_amdgcn_s_memrealtime();                           \
+    }                                                                              \
+  } while (0)
+#define TA_MLP_STAMP_END(dst)                                                                              \
+  do {                                                                                                     \
+    if ((dst) && threadIdx.x == 0)                                                                         \
+      for (int q_ = 0; q_ < kStampSlots; ++q_) (dst)[(size_t)blockIdx.x * kStampSlots + q_] = s_mlp_stamp[q_]; \
+  } while (0)
+#define TA_MLP_STAMP_PARAM , unsigned long long *stamps
+#define TA_MLP_STAMP_ARG(b) , (b).mlp_stamps
+#else
+#define TA_MLP_STAMP_BEGIN() do {} while (0)
+#define TA_MLP_STAMP_END(dst) do {} while (0)
+#define TA_MLP_STAMP_PARAM
+#define TA_MLP_STAMP_ARG(b)
+#endif
+
 #include "ta_mlp_tile.h"
 
 namespace ta {
@@ -19,12 +53,16 @@ namespace {
 
 constexpr int kMlpThreads = 256;
 
-template <int THREADS>
+// SCALAR: the network is one `mlp_tile_scalar` takes (decided on the host); `atoms` may then be null: the
+// tile's rows are the atoms a0 + row themselves (one-element batches)
+template <int THREADS, bool SCALAR = false>
 __global__ __launch_bounds__(THREADS) void mlp_kernel(MlpDev mlp, int act, int ndim,
                                                           const int32_t *atoms, int n_atoms,
                                                           const double *G, double *dEdG,
-                                                          double *eatom, double *scratch, int stride) {
+                                                          double *eatom, double *scratch, int stride
+                                                          TA_MLP_STAMP_PARAM) {
   extern __shared__ double lds[];
+  TA_MLP_STAMP_BEGIN();
   double *buf0 = lds, *buf1 = lds + kMlpRows * stride;
   const int a0 = blockIdx.x * kMlpRows;
   const int nrows = min(kMlpRows, n_atoms - a0);
@@ -32,15 +70,27 @@ __global__ __launch_bounds__(THREADS) void mlp_kernel(MlpDev mlp, int act, int n
   // launch reserved room for them (scratch == nullptr), else in the global scratch slab
   double *da = scratch ? scratch + (size_t)blockIdx.x * mlp.n_layers * kMlpRows * stride
                        : lds + 2 * kMlpRows * stride;
-  for (int idx = threadIdx.x; idx < kMlpRows * ndim; idx += THREADS) {
-    const int row = idx / ndim, k = idx - row * ndim;
-    buf0[row * stride + k] = row < nrows ? G[(size_t)atoms[a0 + row] * ndim + k] : 0.0;
+  if constexpr (SCALAR) {
+    const auto atom_of = [&](int row) { return atoms ? atoms[a0 + row] : a0 + row; };
+    mlp_tile_stage<THREADS>(mlp, ndim, nrows, buf0, stride,
+                            [&](int row, int k) { return G[(size_t)atom_of(row) * ndim + k]; });
+    TA_MLP_STAMP(1);
+    mlp_tile_scalar<16>(
+        mlp, act, ndim, nrows, buf0, buf1, stride, da, [&](int row, double y) { eatom[atom_of(row)] = y; },
+        [&](int row, int k, double d) { dEdG[(size_t)atom_of(row) * ndim + k] = d; });
+  } else {
+    for (int idx = threadIdx.x; idx < kMlpRows * ndim; idx += THREADS) {
+      const int row = idx / ndim, k = idx - row * ndim;
+      buf0[row * stride + k] = row < nrows ? G[(size_t)atoms[a0 + row] * ndim + k] : 0.0;
+    }
+    __syncthreads();
+    TA_MLP_STAMP(1);
+    mlp_tile<16>(
+        mlp, act, ndim, nrows, buf0, buf1, stride, da,
+        [&](int row, double y) { eatom[atoms[a0 + row]] = y; },
+        [&](int row, int k, double d) { dEdG[(size_t)atoms[a0 + row] * ndim + k] = d; });
   }
-  __syncthreads();
-  mlp_tile<16>(
-      mlp, act, ndim, nrows, buf0, buf1, stride, da,
-      [&](int row, double y) { eatom[atoms[a0 + row]] = y; },
-      [&](int row, int k, double d) { dEdG[(size_t)atoms[a0 + row] * ndim + k] = d; });
+  TA_MLP_STAMP_END(stamps);
 }
 
 // All elements in one launch: blocks are laid out element after element, so the small
@@ -56,8 +106,10 @@ __global__ __launch_bounds__(THREADS) void mlp_all_kernel(const MlpDev *__restri
                                                               int ndim, const int32_t *atoms,
                                                               const double *G, double *dEdG,
                                                               double *eatom, double *scratch,
-                                                              int stride, int tile_doubles) {
+                                                              int stride, int tile_doubles,
+                                                              unsigned scalar_mask TA_MLP_STAMP_PARAM) {
   extern __shared__ double lds[];
+  TA_MLP_STAMP_BEGIN();
   double *buf0 = lds, *buf1 = lds + kMlpRows * stride;
   int e = 0;
   while (e + 1 < tiles.nel && (int)blockIdx.x >= tiles.tile_start[e + 1]) ++e;
@@ -67,15 +119,23 @@ __global__ __launch_bounds__(THREADS) void mlp_all_kernel(const MlpDev *__restri
   const int a0 = ((int)blockIdx.x - tiles.tile_start[e]) * kMlpRows;
   const int nrows = min(kMlpRows, n_atoms - a0);
   double *da = scratch ? scratch + (size_t)blockIdx.x * tile_doubles : lds + 2 * kMlpRows * stride;
-  for (int idx = threadIdx.x; idx < kMlpRows * ndim; idx += THREADS) {
-    const int row = idx / ndim, k = idx - row * ndim;
-    buf0[row * stride + k] = row < nrows ? G[(size_t)el_atoms[a0 + row] * ndim + k] : 0.0;
+  const auto emit_energy = [&](int row, double y) { eatom[el_atoms[a0 + row]] = y; };
+  const auto emit_grad = [&](int row, int k, double d) { dEdG[(size_t)el_atoms[a0 + row] * ndim + k] = d; };
+  if ((scalar_mask >> e) & 1) {  // bit e: element e's network goes through mlp_tile_scalar (host decision)
+    mlp_tile_stage<THREADS>(mlp, ndim, nrows, buf0, stride,
+                            [&](int row, int k) { return G[(size_t)el_atoms[a0 + row] * ndim + k]; });
+    TA_MLP_STAMP(1);
+    mlp_tile_scalar<16>(mlp, act, ndim, nrows, buf0, buf1, stride, da, emit_energy, emit_grad);
+  } else {
+    for (int idx = threadIdx.x; idx < kMlpRows * ndim; idx += THREADS) {
+      const int row = idx / ndim, k = idx - row * ndim;
+      buf0[row * stride + k] = row < nrows ? G[(size_t)el_atoms[a0 + row] * ndim + k] : 0.0;
+    }
+    __syncthreads();
+    TA_MLP_STAMP(1);
+    mlp_tile<16>(mlp, act, ndim, nrows, buf0, buf1, stride, da, emit_energy, emit_grad);
   }
-  __syncthreads();
-  mlp_tile<16>(
-      mlp, act, ndim, nrows, buf0, buf1, stride, da,
-      [&](int row, double y) { eatom[el_atoms[a0 + row]] = y; },
-      [&](int row, int k, double d) { dEdG[(size_t)el_atoms[a0 + row] * ndim + k] = d; });
+  TA_MLP_STAMP_END(stamps);
 }
 
 // ---- one wavefront per 16 atoms, the whole network in registers ---------------------------------
@@ -683,8 +743,10 @@ void allow_lds(K kernel, size_t bytes) {
   allowed[key] = kWaveLdsLimit;
 }
 
+// `identity_atoms`: atoms[i] == i for every i < n_atoms (the batch of a one-element model)
 void launch_mlp_impl(const MlpDev &mlp, int activation, int ndim, const int32_t *atoms, int n_atoms,
-                     const DeviceBatch &b, const Options &opt, double *scratch, hipStream_t s, MlpLaunchInfo *info) {
+                     const DeviceBatch &b, const Options &opt, double *scratch, hipStream_t s, MlpLaunchInfo *info,
+                     bool identity_atoms) {
   if (n_atoms == 0) return;
   // bookkeeping of the launch issued below (ta_mlp_launch_info)
   auto note = [&](int family, int threads, int lh, int nt, unsigned gx, unsigned gy, size_t lds, int da) {
@@ -735,13 +797,23 @@ void launch_mlp_impl(const MlpDev &mlp, int activation, int ndim, const int32_t 
     da = TA_MLP_DA_LDS;
   }
   note(TA_MLP_TILE, mlp.max_np >= 128 ? 512 : kMlpThreads, 0, 0, blocks, 1, lds, da);
+  // the tile body: same kernel geometry either way (Options::mlp_tile_generic forces the generic one)
+  const bool scalar = mlp_tile_scalar_ok(mlp) && !opt.mlp_tile_generic;
+  if (info) info->body = scalar ? TA_MLP_BODY_SCALAR : TA_MLP_BODY_GENERIC;
+  // the scalar body indexes G / dEdG / eatom by the tile's rows when `atoms` is the identity
+  const int32_t *tile_atoms = scalar && identity_atoms ? nullptr : atoms;
   // one wavefront per 16-column tile of the widest layer, at most 8
-  if (mlp.max_np >= 128)
-    hipLaunchKernelGGL(mlp_kernel<512>, dim3(blocks), dim3(512), lds, s, mlp, activation, ndim, atoms,
-                       n_atoms, b.G, b.dEdG, b.eatom, scratch, stride);
-  else
-    hipLaunchKernelGGL(mlp_kernel<kMlpThreads>, dim3(blocks), dim3(kMlpThreads), lds, s, mlp, activation,
-                       ndim, atoms, n_atoms, b.G, b.dEdG, b.eatom, scratch, stride);
+  auto go = [&](auto kernel, unsigned threads) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds, s, mlp, activation, ndim, tile_atoms, n_atoms, b.G,
+                       b.dEdG, b.eatom, scratch, stride TA_MLP_STAMP_ARG(b));
+  };
+  if (mlp.max_np >= 128) {
+    if (scalar) go(mlp_kernel<512, true>, 512);
+    else go(mlp_kernel<512, false>, 512);
+  } else {
+    if (scalar) go(mlp_kernel<kMlpThreads, true>, kMlpThreads);
+    else go(mlp_kernel<kMlpThreads, false>, kMlpThreads);
+  }
 }
 
 // one launch for every element; `mlps_dev` is the device copy of `mlps_host[0..nel)`
@@ -763,8 +835,9 @@ void launch_mlp_all(const MlpDev *mlps_dev, const MlpDev *mlps_host, int nel, in
     if (info) *info = MlpLaunchInfo{family, threads, lh, nt, (int)gx, (int)gy, (long long)lds, da};
   };
   if (nel == 1) {  // the model description travels as a kernel argument: scalar loads
+    // (one element: DeviceBatch::elem_atoms lists the batch's atoms in their own order)
     launch_mlp_impl(mlps_host[0], activation, ndim, b.elem_atoms, b.elem_start[1] - b.elem_start[0], b,
-                    opt, scratch, s, info);
+                    opt, scratch, s, info, true);
     return;
   }
   MlpTiles t;
@@ -837,14 +910,24 @@ void launch_mlp_all(const MlpDev *mlps_dev, const MlpDev *mlps_host, int nel, in
     da = TA_MLP_DA_LDS;
   }
   note(TA_MLP_TILE_ALL, width >= 128 ? 512 : kMlpThreads, 0, 0, (unsigned)blocks, 1, lds, da);
+  // the tile body of every element's network (bit e of the kernel's mask: mlp_tile_scalar)
+  unsigned scalar_mask = 0, present = 0;
+  for (int e = 0; e < nel; ++e) {
+    if (b.elem_start[e + 1] > b.elem_start[e]) present |= 1u << e;
+    if (mlp_tile_scalar_ok(mlps_host[e]) && !opt.mlp_tile_generic) scalar_mask |= 1u << e;
+  }
+  if (info)
+    info->body = (scalar_mask & present) == present ? TA_MLP_BODY_SCALAR
+                 : (scalar_mask & present) == 0     ? TA_MLP_BODY_GENERIC
+                                                    : TA_MLP_BODY_MIXED;
   if (width >= 128)
     hipLaunchKernelGGL(mlp_all_kernel<512>, dim3((unsigned)blocks), dim3(512), lds, s, mlps_dev, t,
                        activation, ndim, b.elem_atoms, b.G, b.dEdG, b.eatom, scratch, stride,
-                       layers * kMlpRows * stride);
+                       layers * kMlpRows * stride, scalar_mask TA_MLP_STAMP_ARG(b));
   else
     hipLaunchKernelGGL(mlp_all_kernel<kMlpThreads>, dim3((unsigned)blocks), dim3(kMlpThreads), lds, s,
                        mlps_dev, t, activation, ndim, b.elem_atoms, b.G, b.dEdG, b.eatom, scratch,
-                       stride, layers * kMlpRows * stride);
+                       stride, layers * kMlpRows * stride, scalar_mask TA_MLP_STAMP_ARG(b));
 }
 
 }  // namespace ta

@@ -45,6 +45,7 @@ Options options_from_env(const char *(*get)(const char *)) {
   o.nl_two_pass = first_is("TA_NL_TWO_PASS", '1');
   o.nl_copy_starts = first_is("TA_NL_COPY_STARTS", '1');
   o.sync_blocking = first_is("TA_SYNC_BLOCKING", '1');
+  o.mlp_tile_generic = first_is("TA_MLP_TILE_GENERIC", '1');
   o.eam_nn_tables = !first_is("TA_EAM_NN_TABLES", '0');
   o.fwd_wpe = number("TA_FWD_WPE", 0);
   o.bwd_wpe = number("TA_BWD_WPE", 0);

@@ -25,6 +25,7 @@ struct Options {
   bool nl_two_pass = false;     // TA_NL_TWO_PASS: two-pass device builder only
   bool nl_copy_starts = false;  // TA_NL_COPY_STARTS: per-atom offsets by a copy, not written by the builder
   bool sync_blocking = false;   // TA_SYNC_BLOCKING: no polling before a blocking wait for the stream
+  bool mlp_tile_generic = false;  // TA_MLP_TILE_GENERIC: the generic body of the tile kernels for every network
   // first character '0' switches off
   bool eam_nn_tables = true;  // TA_EAM_NN_TABLES: nn pair functions through their Hermite tables
   // atoi

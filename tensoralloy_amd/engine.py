@@ -1343,6 +1343,14 @@ class Engine:
         return {"family": _lib.TA_MLP_FAMILY[int(v[0])], "threads": int(v[1]), "lh": int(v[2]), "nt": int(v[3]),
                 "grid": (int(v[4]), int(v[5])), "lds_bytes": int(v[6]), "da": _lib.TA_MLP_DA[int(v[7])]}
 
+    def mlp_tile_body(self) -> str:
+        """Which body the tile kernels of the last per-atom network launch ran (`ta_mlp_tile_body`): "scalar"
+        (hidden layers without skips, one linear output unit), "generic", "mixed" (an all-elements launch whose
+        networks differ) or "none" when the last launch was not a tile launch."""
+        v = C.c_int32(0)
+        self._check(self._lib.ta_mlp_tile_body(self._handle, C.byref(v)))
+        return _lib.TA_MLP_BODY[int(v.value)]
+
     def measure_hbm_copy(self, nbytes: int = 1 << 30, reps: int = 10) -> float:
         """Achievable device-to-device copy rate in GB/s (read + written bytes)."""
         g = C.c_double(0.0)
