@@ -7,6 +7,11 @@ namespace ta {
 // exp(x) for x <= ~50 (the kernels only call it with x <= 0): round-to-nearest
 // range reduction with a two-part ln2 and a degree-13 Taylor polynomial on
 // |r| <= ln2/2 (truncation 4e-18 relative), scaled by v_ldexp_f64.
+// Tested domain (tests/test_gpu_math.py): -1e6 <= x <= 50 and NaN: <= 1.5 ulp where the result is
+// normal, <= 2 x 2^-1074 where it is subnormal, exactly 0 from x = -746 down. Outside it the function
+// is not exp: -inf gives NaN (the reduction forms inf - inf) and a finite x below about -1e25 gives
+// inf or NaN (the reduced argument overflows the polynomial). No caller reaches either with finite
+// positions; softplus_fn clamps for itself.
 __device__ __forceinline__ double ta_exp(double x) {
   const double kLog2e = 1.4426950408889634074;
   const double kLn2Hi = 6.93147180369123816490e-01;
@@ -43,65 +48,84 @@ constexpr double cos_coef(int k) {
   return v;
 }
 
+// Y(u) and Y'(u) (Horner on c_k and on k c_k)
+__device__ __forceinline__ void cos_half(double u, double &y, double &d) {
+  constexpr double c0 = cos_coef(0), c1 = cos_coef(1), c2 = cos_coef(2), c3 = cos_coef(3),
+                   c4 = cos_coef(4), c5 = cos_coef(5), c6 = cos_coef(6), c7 = cos_coef(7),
+                   c8 = cos_coef(8), c9 = cos_coef(9), c10 = cos_coef(10), c11 = cos_coef(11);
+  y = c11;
+  y = fma(y, u, c10);
+  y = fma(y, u, c9);
+  y = fma(y, u, c8);
+  y = fma(y, u, c7);
+  y = fma(y, u, c6);
+  y = fma(y, u, c5);
+  y = fma(y, u, c4);
+  y = fma(y, u, c3);
+  y = fma(y, u, c2);
+  y = fma(y, u, c1);
+  y = fma(y, u, c0);
+  d = 11.0 * c11;
+  d = fma(d, u, 10.0 * c10);
+  d = fma(d, u, 9.0 * c9);
+  d = fma(d, u, 8.0 * c8);
+  d = fma(d, u, 7.0 * c7);
+  d = fma(d, u, 6.0 * c6);
+  d = fma(d, u, 5.0 * c5);
+  d = fma(d, u, 4.0 * c4);
+  d = fma(d, u, 3.0 * c3);
+  d = fma(d, u, 2.0 * c2);
+  d = fma(d, u, c1);
+}
+
+// 1 + 5 x^6 - 6 x^5 = (1 - x)^2 (1 + 2 x + 3 x^2 + 4 x^3 + 5 x^4). The expanded form cancels towards
+// x = 1, where rounding can leave it negative; this one is a product of non-negative factors,
+// exact in 1 - x from x = 0.5 on, and 1 at x = 0.
+__device__ __forceinline__ double poly_cutoff_value(double x) {
+  const double t = 1.0 - x;
+  const double g = fma(fma(fma(fma(5.0, x, 4.0), x, 3.0), x, 2.0), x, 1.0);
+  return t * t * g;
+}
+
+// f and df / du from the shared intermediates: cutoff_u and cutoff_u2 both finish through these, so
+// the two return the same bits (a Hessian-vector product differentiates the very forces the
+// first-order kernels return).
+__device__ __forceinline__ void cos_cutoff_finish(double y, double d, double &f, double &dfdu) {
+  f = y * y;
+  dfdu = 2.0 * y * d;
+}
+// polynomial cutoff, gamma = 5 (reference nn/cutoff.py:78-85):
+// f = 1 + 5 x^6 - 6 x^5, x = sqrt(u);  df/du = 15 x^3 (x - 1)
+__device__ __forceinline__ void poly_cutoff_finish(double u, double x, double &f, double &dfdu) {
+  const double x3 = u * x;
+  f = poly_cutoff_value(x);
+  dfdu = 15.0 * x3 * (x - 1.0);
+}
+
 // fc(u) and d fc / d u for u = (r / rc)^2 in [0, 1). Callers mask u >= 1.
 __device__ __forceinline__ void cutoff_u(int kind, double u, double &f, double &dfdu) {
   if (kind == TA_CUTOFF_COSINE) {
-    constexpr double c0 = cos_coef(0), c1 = cos_coef(1), c2 = cos_coef(2), c3 = cos_coef(3),
-                     c4 = cos_coef(4), c5 = cos_coef(5), c6 = cos_coef(6), c7 = cos_coef(7),
-                     c8 = cos_coef(8), c9 = cos_coef(9), c10 = cos_coef(10), c11 = cos_coef(11);
-    double y = c11;
-    y = fma(y, u, c10);
-    y = fma(y, u, c9);
-    y = fma(y, u, c8);
-    y = fma(y, u, c7);
-    y = fma(y, u, c6);
-    y = fma(y, u, c5);
-    y = fma(y, u, c4);
-    y = fma(y, u, c3);
-    y = fma(y, u, c2);
-    y = fma(y, u, c1);
-    y = fma(y, u, c0);
-    double d = 11.0 * c11;
-    d = fma(d, u, 10.0 * c10);
-    d = fma(d, u, 9.0 * c9);
-    d = fma(d, u, 8.0 * c8);
-    d = fma(d, u, 7.0 * c7);
-    d = fma(d, u, 6.0 * c6);
-    d = fma(d, u, 5.0 * c5);
-    d = fma(d, u, 4.0 * c4);
-    d = fma(d, u, 3.0 * c3);
-    d = fma(d, u, 2.0 * c2);
-    d = fma(d, u, c1);
-    f = y * y;
-    dfdu = 2.0 * y * d;
+    double y, d;
+    cos_half(u, y, d);
+    cos_cutoff_finish(y, d, f, dfdu);
   } else {
-    // polynomial cutoff, gamma = 5 (reference nn/cutoff.py:78-85):
-    // f = 1 + 5 x^6 - 6 x^5, x = sqrt(u);  df/du = 15 x^3 (x - 1)
-    double x = sqrt(u);
-    double x2 = u, x3 = x2 * x, x5 = x3 * x2;
-    f = 1.0 + 5.0 * x5 * x - 6.0 * x5;
-    dfdu = 15.0 * x3 * (x - 1.0);
+    poly_cutoff_finish(u, sqrt(u), f, dfdu);
   }
 }
 
 // fc(u), d fc / d u and d^2 fc / d u^2 (analytic Hessian-vector products, ta_hvp.hip)
 __device__ __forceinline__ void cutoff_u2(int kind, double u, double &f, double &dfdu, double &d2fdu2) {
   if (kind == TA_CUTOFF_COSINE) {
-    double y = 0.0, d = 0.0, dd = 0.0;
+    double y, d;
+    cos_half(u, y, d);
+    cos_cutoff_finish(y, d, f, dfdu);
+    double dd = 110.0 * cos_coef(11);  // Y''(u) = sum_k k (k - 1) c_k u^(k - 2)
 #pragma unroll
-    for (int k = 11; k >= 0; --k) {  // Horner with first and second derivative
-      dd = fma(dd, u, 2.0 * d);
-      d = fma(d, u, y);
-      y = fma(y, u, cos_coef(k));
-    }
-    f = y * y;
-    dfdu = 2.0 * y * d;
+    for (int k = 10; k >= 2; --k) dd = fma(dd, u, double(k * (k - 1)) * cos_coef(k));
     d2fdu2 = 2.0 * (d * d + y * dd);
   } else {
     const double x = sqrt(u);
-    const double x3 = u * x, x5 = x3 * u;
-    f = 1.0 + 5.0 * x5 * x - 6.0 * x5;
-    dfdu = 15.0 * x3 * (x - 1.0);
+    poly_cutoff_finish(u, x, f, dfdu);
     d2fdu2 = 30.0 * u - 22.5 * x;
   }
 }
@@ -126,9 +150,7 @@ __device__ __forceinline__ double cutoff_u_value(int kind, double u) {
     y = fma(y, u, c0);
     return y * y;
   } else {
-    double x = sqrt(u);
-    double x5 = u * u * x;
-    return 1.0 + 5.0 * x5 * x - 6.0 * x5;
+    return poly_cutoff_value(sqrt(u));
   }
 }
 
@@ -273,9 +295,16 @@ __device__ __forceinline__ void activation_fn(int act, double x, double &h, doub
       dh = x > 0.0 ? 1.0 : exp(x);
       break;
     case TA_ACT_SQUAREPLUS: {
-      double s = sqrt(x * x + 4.0);
-      h = 0.5 * (x + s);
-      dh = 0.5 * (1.0 + x / s);
+      // x + s and 1 + x / s cancel for x < 0: there (x + s)(s - x) = 4 gives h = 2 / (s - x) and
+      // h' = 2 / (s (s - x)) = 2 / (w - x s), quotients of sums of positive terms
+      const double w = fma(x, x, 4.0), s = sqrt(w);
+      if (x >= 0.0) {
+        h = 0.5 * (x + s);
+        dh = fma(0.5, x / s, 0.5);
+      } else {
+        h = 2.0 / (s - x);
+        dh = 2.0 / fma(-x, s, w);
+      }
       break;
     }
     default:
@@ -298,16 +327,20 @@ __device__ __forceinline__ void activation_fn2(int act, double x, double &h, dou
       d2h = -2.0 * h * dh;
       break;
     case TA_ACT_SOFTSIGN: {
-      const double d = 1.0 + fabs(x);
-      d2h = (x >= 0.0 ? -2.0 : 2.0) / (d * d * d);
+      // -2 sign(x) / d^3 with sign(0) = 0 (oracle/train.py). d^3 would carry the rounding of
+      // d = 1 + |x| three times: e is that rounding exactly (Fast2Sum), (d + e)^3 = d^3 + 3 d^2 e
+      const double a = fabs(x), d = 1.0 + a;
+      const double e = a <= 1.0 ? a - (d - 1.0) : 1.0 - (d - a);
+      const double d2 = d * d;
+      d2h = (x > 0.0 ? -2.0 : x < 0.0 ? 2.0 : 0.0) / fma(3.0 * e, d2, d2 * d);
       break;
     }
     case TA_ACT_ELU:
       d2h = x > 0.0 ? 0.0 : exp(x);
       break;
     case TA_ACT_SQUAREPLUS: {
-      const double s = sqrt(x * x + 4.0);
-      d2h = 2.0 / (s * s * s);
+      const double w = fma(x, x, 4.0);
+      d2h = 2.0 / (w * sqrt(w));  // w = s^2 without the rounding of s
       break;
     }
     default:  // relu, leaky relu, linear

@@ -189,6 +189,44 @@ def test_every_activation_against_oracle(lib, activation):
     check_against_oracle(nn, frames, activation)
 
 
+SATURATING_SCALE = 30.0     # on the first layer's weights; the test asserts what it has to achieve
+
+
+def oracle_preactivations(nn, frames, monkeypatch):
+    """Every argument the oracle's own forward pass (oracle/sf.py::apply_mlp) hands to its activation."""
+    import oracle.sf as osf
+    seen, real = [], osf.activation
+
+    def recording(name, z):
+        seen.append(np.array(z, dtype=float).ravel())
+        return real(name, z)
+
+    with monkeypatch.context() as patch:
+        patch.setattr(osf, "activation", recording)
+        results = [oracle_eval(nn, a) for a in frames]
+    return np.concatenate(seen), results
+
+
+@pytest.mark.parametrize("activation", sorted(_lib.TA_ACT))
+def test_every_saturated_activation_against_oracle(lib, monkeypatch, activation):
+    """The network of test_every_activation_against_oracle with its first layer scaled up until at least 1 % of the
+    oracle's own pre-activations lie above 40 and at least 1 % below -40 (where softplus is max(x, 0) to double
+    precision and 1 - tanh^2 has cancelled to 0): forward, backward and second-order tiles against the same oracle
+    at the same bounds. tests/test_gpu_math.py holds the activations themselves to a 50-digit reference out there."""
+    nn = make_nn(["Mo", "Ni"], RC, True, [24, 16], activation=activation, resnet=True, seed=21)
+    for el in nn.elements:
+        W, b = nn.weights[el][0]
+        nn.weights[el][0] = (W * SATURATING_SCALE, b)
+    frames = small_frames(["Mo", "Ni"])
+    z, results = oracle_preactivations(nn, frames, monkeypatch)
+    n_hidden = sum(len(a) for a in frames) * (24 + 16)
+    assert z.size == n_hidden and np.all(np.isfinite(z))
+    assert (z > 40.0).mean() >= 0.01 and (z < -40.0).mean() >= 0.01, ((z > 40.0).mean(), (z < -40.0).mean())
+    for r in results:
+        assert np.isfinite(r["energy"]) and np.all(np.isfinite(r["forces"]))
+    check_against_oracle(nn, frames, activation + " (saturated)")
+
+
 # -- A. an element absent from the batch -----------------------------------------------------------------------
 
 def test_absent_element_slice_is_exactly_zero(lib):
