@@ -8,12 +8,14 @@
 // written once below: md_alloc_layout, md_sampler_ready, md_sampler_off / md_sampler_set, and the loops of ta_md_init
 // and ta_md_run. To add a sampler:
 //   1. ta_sampler_text.h: its texts, a constant in md_text;
-//   2. ta_context.h: a struct on MdSampler in MdState with its Setting, its buffers and its release(), and its place
-//      in for_each_sampler;
-//   3. here: its md_alloc (buffer sizes and uploads), its setter (parameter checks, then md_sampler_off or
-//      md_sampler_set) and its getters (md_sampler_ready, fill_info, copy_series);
-//   4. ta_md_run: its cross-checks, its launch struct, its place in the launch order of a step and in the order of
-//      the epilogue.
+//   2. ta_context.h: a struct on MdSampler in MdState with its Setting, its buffers with the accessors that state their
+//      layout, and its release(), and its place in for_each_sampler;
+//   3. here: its md_alloc (buffer sizes and uploads), md_launch (the launch struct's run-constant fields) and md_enqueue
+//      (where md_due says so: the fields of this launch and the launch, under the integrator's predicate with seq = k,
+//      IN FRONT OF the integrator launch of step k or BEHIND it with the snapshot it wrote), its setter (parameter
+//      checks, then md_sampler_off or md_sampler_set) and its getters (md_sampler_ready, fill_info, copy_series); its
+//      cross-checks, if any, in md_run_refusals;
+//   4. ta_md_run: its launch struct, its place in front of or behind the integrator in a step, and in the end_run order.
 #include <cmath>
 #include <cstring>
 
@@ -75,11 +77,49 @@ bool md_alloc_layout(ta_context *h, S &x, int64_t every, int per_atom, int chunk
   return true;
 }
 
-// md_alloc(h, x, s): sampler x allocated for setting `s` (its own, or a setter's candidate) as md_alloc_layout says.
+// the neighbour-list view of launch `k` of a run, for any launch struct that reads the resident list: the state and the
+// (skin) list of the batch, not the exact one filtered from it (a rebuild may have moved them: taken at every launch)
+template <typename L>
+void point_at_list(const ta_context *h, L &l, int k) {
+  l.pos = h->db.pos;
+  l.cells = h->db.cells;
+  l.species = h->db.species;
+  l.atom_start = h->db.atom_start;
+  l.pair_start = h->pair_start.ptr;
+  l.pair_j = h->pair_j.ptr;
+  l.pair_shift = h->pair_shift.ptr;
+  l.seq = (unsigned)k;
+}
+
+// Launch k of the run that began at absolute step step0 holds the whole-step state t = step0 + k; sampler x samples it
+// when this says so. Sample number, ring slot and series row are functions of t alone (ta_schedule.h), so the launches
+// that returned early behind a stale list and are enqueued again after the rebuild write what they would have written.
+bool md_due(const MdSampler &x, int64_t step0, int k) { return x.run && x.sched.due(step0, k); }
+
+// Where the integrator launch of a step writes the whole-step state (x, v) for the launches behind it: the slot of the
+// correlation ring when md_set_sampling is due at launch k, else the rows of md_set_sq when that is due, else the rows
+// of md_set_flux when that is due, else nowhere
+struct MdSnapshot {
+  double *x = nullptr, *v = nullptr;
+};
+MdSnapshot md_snapshot(const MdState::Corr &corr, const MdState::Sq &sq, const MdState::Flux &flux, size_t N, int64_t step0,
+                       int k) {
+  if (md_due(corr, step0, k)) {
+    const int64_t n = corr.sched.index(step0 + k);
+    return {corr.slot(corr.ring_x, n, N), corr.slot(corr.ring_v, n, N)};
+  }
+  if (md_due(sq, step0, k)) return {sq.snap_x.ptr, sq.snap_v.ptr};
+  if (md_due(flux, step0, k)) return {flux.snap_x.ptr, flux.snap_v.ptr};
+  return {};
+}
+
+// Every sampler x has three functions, one beside the other. md_alloc(h, x, s): x allocated for setting `s` (its own, or
+// a setter's candidate) as md_alloc_layout says. md_launch(h, x): its launch struct with every field that is fixed for
+// a ta_md_run (a pointer into a part of a buffer stays null while the sampler is not in the run). md_enqueue: see the file's head.
 // Here: the rings, the accumulators and the partials of the correlation launch
 bool md_alloc(ta_context *h, MdState::Corr &c, const MdState::Corr::Setting &s) {
   const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
-  const size_t L = (size_t)s.p.n_lags, E = (size_t)h->n_elements, n_acc = 2 * F * E * L;
+  const size_t L = (size_t)s.p.n_lags, E = (size_t)h->n_elements, n_acc = s.n_acc(F, E);
   return md_alloc_layout(
       h, c, s.p.sample_every, 3, ta::kMdCorrChunk,
       [&](size_t n_blk) {
@@ -87,6 +127,25 @@ bool md_alloc(ta_context *h, MdState::Corr &c, const MdState::Corr::Setting &s) 
                c.part.try_exact(n_blk * 2 * E * L);
       },
       [&]() { zero(c.acc, n_acc); });
+}
+ta::MdCorrLaunch md_launch(const ta_context *h, const MdState::Corr &x) {
+  const size_t F = h->keep_natoms.size(), E = (size_t)h->n_elements;
+  ta::MdCorrLaunch c;
+  c.ring_x = x.ring_x.ptr, c.ring_v = x.ring_v.ptr;
+  c.blk_start = x.blk.ptr, c.part = x.part.ptr;
+  c.acc_v = x.acc_v(), c.acc_x = x.run ? x.acc_x(F, E) : nullptr;
+  c.status = h->res.status.ptr;
+  c.n_atoms = (long long)h->keep_species.size();
+  c.n_lags = x.set.p.n_lags, c.n_elements = h->n_elements, c.n_frames = (int)F, c.n_chunks = x.n_blk;
+  return c;
+}
+// directly behind the launch that sampled into the ring, under the same predicate
+void md_enqueue(const ta_context *h, const MdState::Corr &x, ta::MdCorrLaunch &c, int64_t step0, int k, const MdSnapshot &) {
+  if (!md_due(x, step0, k)) return;
+  c.species = h->db.species, c.atom_start = h->db.atom_start;
+  c.seq = (unsigned)k, c.n = (long long)x.sched.index(step0 + k);
+  ta::launch_md_correlate(c, h->stream);
+  HIP_CHECK(hipGetLastError());
 }
 
 // the counts
@@ -96,6 +155,24 @@ bool md_alloc(ta_context *h, MdState::Rdf &g, const MdState::Rdf::Setting &s) {
   return md_alloc_layout(
       h, g, s.p.sample_every, 1, ta::md_rdf_chunk((long long)N), [&](size_t) { return g.acc.try_exact(n_acc); },
       [&]() { zero(g.acc, n_acc); });
+}
+ta::MdRdfLaunch md_launch(const ta_context *h, const MdState::Rdf &x) {
+  ta::MdRdfLaunch g;
+  g.blk_start = x.blk.ptr, g.counts = x.acc.ptr, g.status = h->res.status.ptr;
+  g.n_bins = x.set.p.n_bins, g.n_elements = h->n_elements, g.n_frames = (int)h->keep_natoms.size();
+  g.n_blk = x.n_blk, g.chunk = x.chunk;
+  g.dr = x.run ? x.set.p.r_max / (double)x.set.p.n_bins : 1.0;
+  return g;
+}
+// Pair distributions: the state t = step0 + k is counted by a launch IN FRONT OF the integrator launch of step k, whose
+// drift leaves x(t). With seq = k the integrator's predicate skips exactly the states that were reached on a stale
+// list; after the rebuild the launch is enqueued again with the rest and counts then.
+void md_enqueue(const ta_context *h, const MdState::Rdf &x, ta::MdRdfLaunch &g, int64_t step0, int k) {
+  if (!md_due(x, step0, k)) return;
+  point_at_list(h, g, k);
+  g.pair_i = h->pair_i.ptr;
+  ta::launch_md_rdf(g, h->stream);
+  HIP_CHECK(hipGetLastError());
 }
 
 // the counts and the squared cutoffs
@@ -110,12 +187,27 @@ bool md_alloc(ta_context *h, MdState::Adf &g, const MdState::Adf::Setting &s) {
         upload_squares(g.rb2, s.rb);
       });
 }
+ta::MdAdfLaunch md_launch(const ta_context *h, const MdState::Adf &x) {
+  ta::MdAdfLaunch t;
+  t.blk_start = x.blk.ptr, t.rb2 = x.rb2.ptr, t.counts = x.acc.ptr, t.status = h->res.status.ptr;
+  t.n_bins = x.set.p.n_bins, t.n_elements = h->n_elements, t.n_frames = (int)h->keep_natoms.size();
+  t.n_blk = x.n_blk, t.chunk = x.chunk;
+  t.dtheta = x.run ? M_PI / (double)x.set.p.n_bins : 1.0;
+  return t;
+}
+// Bond-angle distributions: a launch of their own in the same place as the pair distributions', under the same
+// predicate (no volume enters, so they run under the barostat too: db.cells are those of the state t)
+void md_enqueue(const ta_context *h, const MdState::Adf &x, ta::MdAdfLaunch &t, int64_t step0, int k) {
+  if (!md_due(x, step0, k)) return;
+  point_at_list(h, t, k);
+  ta::launch_md_adf(t, h->stream);
+  HIP_CHECK(hipGetLastError());
+}
 
 // the counts, the squared cutoffs, the N_lm and the per-atom arrays
 bool md_alloc(ta_context *h, MdState::Order &g, const MdState::Order::Setting &s) {
   const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
-  const size_t E = (size_t)h->n_elements, D = (size_t)s.p.n_degrees;
-  const size_t n_hist = F * E * D * (size_t)s.p.n_bins, n_acc = 2 * n_hist + F * E * (TA_MD_ORDER_MAX_CONN + 1);
+  const size_t E = (size_t)h->n_elements, n_acc = s.n_acc(F, E);
   // N_lm = sqrt((2 l + 1) / (4 pi) (l - m)! / (l + m)!), degree by degree, m = 0 .. l
   std::vector<double> norm;
   int solid = 0;
@@ -133,7 +225,7 @@ bool md_alloc(ta_context *h, MdState::Order &g, const MdState::Order::Setting &s
       h, g, s.p.sample_every, 1, ta::md_order_chunk((long long)N),
       [&](size_t) {
         return g.acc.try_exact(n_acc) && g.rb2.try_exact(E * E) && g.norm.try_exact(M) && g.qlm.try_exact(2 * M * N + 1) &&
-               g.per_atom.try_exact(2 * D * N + 1) && g.per_atom_int.try_exact(2 * N + 1);
+               g.per_atom.try_exact(2 * s.n_q(N) + 1) && g.per_atom_int.try_exact(2 * N + 1);
       },
       [&]() {
         zero(g.acc, n_acc);
@@ -143,18 +235,42 @@ bool md_alloc(ta_context *h, MdState::Order &g, const MdState::Order::Setting &s
         g.solid = solid;
       });
 }
+ta::MdOrderLaunch md_launch(const ta_context *h, const MdState::Order &x) {
+  const size_t N = h->keep_species.size(), F = h->keep_natoms.size(), E = (size_t)h->n_elements;
+  const auto &p = x.set.p;
+  ta::MdOrderLaunch o;
+  o.blk_start = x.blk.ptr, o.rb2 = x.rb2.ptr, o.norm = x.norm.ptr, o.qlm = x.qlm.ptr, o.status = h->res.status.ptr;
+  o.q = x.q(), o.qbar = x.run ? x.qbar(N) : nullptr;
+  o.n_bonds = x.n_bonds(), o.n_conn = x.run ? x.n_conn(N) : nullptr;
+  o.hist_q = x.hist_q();
+  o.hist_qbar = x.run ? x.hist_qbar(F, E) : nullptr, o.hist_conn = x.run ? x.hist_conn(F, E) : nullptr;
+  o.n_bins = p.n_bins, o.n_elements = h->n_elements, o.n_frames = (int)F;
+  o.n_blk = x.n_blk, o.chunk = x.chunk;
+  o.n_degrees = p.n_degrees, o.n_lm = x.n_lm, o.solid = x.solid;
+  o.deg0 = p.degrees[0], o.deg1 = p.degrees[1], o.deg2 = p.degrees[2], o.deg3 = p.degrees[3];
+  o.threshold = p.solid_threshold;
+  return o;
+}
+// Bond-orientational order: its two launches in the same place as the pair distributions', under the same predicate
+// (no volume either)
+void md_enqueue(const ta_context *h, const MdState::Order &x, ta::MdOrderLaunch &o, int64_t step0, int k) {
+  if (!md_due(x, step0, k)) return;
+  point_at_list(h, o, k);
+  ta::launch_md_order(o, h->stream);
+  HIP_CHECK(hipGetLastError());
+}
 
 // the histogram, the series, the give-up word, the squared cutoffs and the per-atom arrays; the layout is the link
 // launch's
 bool md_alloc(ta_context *h, MdState::Cluster &g, const MdState::Cluster::Setting &s) {
   static_assert(TA_MD_MAX_BINS <= ta::kMdClusterLdsWords, "the summary launch keeps all bins of a frame in LDS");
   const size_t N = h->keep_species.size(), F = h->keep_natoms.size(), E = (size_t)h->n_elements;
-  const size_t n_hist = F * (size_t)s.p.n_bins, n_series = (size_t)s.p.n_series * F * 4;
+  const size_t n_hist = s.n_hist(F), n_series = s.n_series(F);
   return md_alloc_layout(
       h, g, s.p.sample_every, 1, ta::md_order_chunk((long long)N),
       [&](size_t) {
         return g.acc.try_exact(n_hist) && g.series.try_exact(n_series) && g.rl2.try_exact(E * E) &&
-               g.per_atom.try_exact(4 * N + 1) && g.giveup.try_exact(4);
+               g.per_atom.try_exact(g.n_per_atom(N) + 1) && g.giveup.try_exact(4);
       },
       [&]() {
         zero(g.acc, n_hist);
@@ -163,13 +279,35 @@ bool md_alloc(ta_context *h, MdState::Cluster &g, const MdState::Cluster::Settin
         upload_squares(g.rl2, s.rl);
       });
 }
+ta::MdClusterLaunch md_launch(const ta_context *h, const MdState::Cluster &x) {
+  const size_t N = h->keep_species.size();
+  ta::MdClusterLaunch cl;
+  cl.blk_start = x.blk.ptr, cl.rl2 = x.rl2.ptr, cl.hist = x.acc.ptr, cl.giveup = x.giveup.ptr, cl.status = h->res.status.ptr;
+  cl.n_conn = x.run && x.set.p.n_min > 0 ? h->md.order.n_conn(N) : nullptr;
+  cl.parent = x.parent(), cl.count = x.run ? x.count(N) : nullptr;
+  cl.label = x.run ? x.label(N) : nullptr, cl.size = x.run ? x.size(N) : nullptr;
+  cl.n_atoms = (long long)N;
+  cl.n_bins = x.set.p.n_bins, cl.n_elements = h->n_elements, cl.n_frames = (int)h->keep_natoms.size();
+  cl.n_blk = x.n_blk, cl.chunk = x.chunk;
+  cl.n_min = x.set.p.n_min, cl.species_mask = x.set.p.species_mask;
+  return cl;
+}
+// Clusters: four launches in the same place as the pair distributions', behind the order launches of the step (n_min > 0
+// reads their n_conn), under the same predicate (no volume either)
+void md_enqueue(const ta_context *h, const MdState::Cluster &x, ta::MdClusterLaunch &cl, int64_t step0, int k) {
+  if (!md_due(x, step0, k)) return;
+  point_at_list(h, cl, k);
+  cl.row = x.series_row(x.sched.index(step0 + k), h->keep_natoms.size());
+  ta::launch_md_cluster(cl, h->stream);
+  HIP_CHECK(hipGetLastError());
+}
 
 // the counts, the series and the per-atom arrays
 bool md_alloc(ta_context *h, MdState::Cna &g, const MdState::Cna::Setting &s) {
   static_assert(TA_MD_CNA_TYPES == ta::kMdCnaTypes && TA_MD_CNA_ADAPTIVE == ta::kMdCnaAdaptive &&
                     TA_MD_CNA_FIXED == ta::kMdCnaFixed, "the header and the launch agree");
   const size_t N = h->keep_species.size(), F = h->keep_natoms.size(), E = (size_t)h->n_elements;
-  const size_t n_acc = F * E * TA_MD_CNA_TYPES, n_series = (size_t)s.p.n_series * F * TA_MD_CNA_TYPES;
+  const size_t n_acc = s.n_acc(F, E), n_series = s.n_series(F);
   return md_alloc_layout(
       h, g, s.p.sample_every, 1, ta::md_order_chunk((long long)N),
       [&](size_t) {
@@ -181,16 +319,36 @@ bool md_alloc(ta_context *h, MdState::Cna &g, const MdState::Cna::Setting &s) {
         zero(g.series, n_series);
       });
 }
+ta::MdCnaLaunch md_launch(const ta_context *h, const MdState::Cna &x) {
+  const auto &p = x.set.p;
+  const double r = p.mode == TA_MD_CNA_FIXED ? p.r_cut : p.r_max;
+  ta::MdCnaLaunch cn;
+  cn.blk_start = x.blk.ptr, cn.structure = x.structure.ptr, cn.r_local = x.r_local.ptr;
+  cn.counts = x.acc.ptr, cn.status = h->res.status.ptr;
+  cn.n_elements = h->n_elements, cn.n_frames = (int)h->keep_natoms.size();
+  cn.n_blk = x.n_blk, cn.chunk = x.chunk;
+  cn.mode = p.mode, cn.r_cut = p.r_cut, cn.r2 = r * r;
+  return cn;
+}
+// Common neighbour analysis: its launch in the same place as the pair distributions', behind the order and cluster
+// launches, under the same predicate (no volume either); sample n counts into row n % n_series, which a launch in front
+// zeroes
+void md_enqueue(const ta_context *h, const MdState::Cna &x, ta::MdCnaLaunch &cn, int64_t step0, int k) {
+  if (!md_due(x, step0, k)) return;
+  point_at_list(h, cn, k);
+  cn.row = x.series_row(x.sched.index(step0 + k), h->keep_natoms.size());
+  ta::launch_md_cna(cn, h->stream);
+  HIP_CHECK(hipGetLastError());
+}
 
 // the Miller triples, an empty ring, the accumulators, the partials of the amplitude launch and the snapshot rows
 bool md_alloc(ta_context *h, MdState::Sq &g, const MdState::Sq::Setting &s) {
   const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
-  const size_t E = (size_t)h->n_elements, Q = (size_t)s.p.n_q, L = (size_t)s.p.n_lags, P = s.p.currents ? 8 : 2;
-  const size_t n_acc = (s.p.currents ? 3 : 1) * F * E * E * L * Q;
+  const size_t E = (size_t)h->n_elements, Q = (size_t)s.p.n_q, L = (size_t)s.p.n_lags, n_acc = s.n_acc(F, E);
   return md_alloc_layout(
       h, g, s.p.sample_every, 1, ta::md_sq_chunk((long long)N),
       [&](size_t n_blk) {
-        return g.acc.try_exact(n_acc) && g.ring.try_exact(L * F * E * P * Q) && g.part.try_exact(n_blk * E * P * Q) &&
+        return g.acc.try_exact(n_acc) && g.ring.try_exact(L * s.row(F, E)) && g.part.try_exact(n_blk * E * s.planes() * Q) &&
                g.snap_x.try_exact(3 * N) && g.snap_v.try_exact(3 * N) && g.miller_dev.try_exact(3 * Q);
       },
       [&]() {
@@ -198,37 +356,77 @@ bool md_alloc(ta_context *h, MdState::Sq &g, const MdState::Sq::Setting &s) {
         upload(g.miller_dev, s.miller);
       });
 }
+ta::MdSqLaunch md_launch(const ta_context *h, const MdState::Sq &x) {
+  const size_t F = h->keep_natoms.size(), E = (size_t)h->n_elements;
+  const auto &p = x.set.p;
+  ta::MdSqLaunch u;
+  u.blk_start = x.blk.ptr, u.miller = x.miller_dev.ptr, u.part = x.part.ptr, u.ring = x.ring.ptr;
+  u.acc_rho = x.acc_rho(), u.status = h->res.status.ptr;
+  u.acc_l = x.run && p.currents ? x.acc_l(F, E) : nullptr, u.acc_j = x.run && p.currents ? x.acc_j(F, E) : nullptr;
+  u.n_q = p.n_q, u.n_lags = p.n_lags, u.n_elements = h->n_elements, u.n_frames = (int)F;
+  u.n_blk = x.n_blk, u.chunk = x.chunk, u.currents = p.currents;
+  return u;
+}
+// Structure factors: the integrator launch of a due step writes the whole-step state (x, v) where md_snapshot says; the
+// three launches go BEHIND it, under the same predicate, and read that snapshot
+void md_enqueue(const ta_context *h, const MdState::Sq &x, ta::MdSqLaunch &u, int64_t step0, int k, const MdSnapshot &snap) {
+  if (!md_due(x, step0, k)) return;
+  u.x = snap.x, u.v = snap.v;
+  u.cells = h->db.cells, u.species = h->db.species, u.atom_start = h->db.atom_start;
+  u.seq = (unsigned)k, u.n = (long long)x.sched.index(step0 + k);
+  ta::launch_md_sq(u, h->stream);
+  HIP_CHECK(hipGetLastError());
+}
 
 // an empty ring, the accumulators {sums, a_heat, a_press}, the partials of the pair sweep and the snapshot rows
 bool md_alloc(ta_context *h, MdState::Flux &g, const MdState::Flux::Setting &s) {
   static_assert(TA_MD_FLUX_ROW == ta::kMdFluxRow, "the header and the launch agree");
   const size_t N = h->keep_species.size(), F = h->keep_natoms.size(), L = (size_t)s.p.n_lags, R = ta::kMdFluxRow;
-  const size_t n_acc = F * R + F * L * 9;
+  const size_t n_acc = s.n_acc(F);
   return md_alloc_layout(
       h, g, s.p.sample_every, 1, ta::md_flux_chunk((long long)N),
       [&](size_t n_blk) {
-        return g.acc.try_exact(n_acc) && g.ring.try_exact(L * F * R) && g.part.try_exact(n_blk * R) &&
+        return g.acc.try_exact(n_acc) && g.ring.try_exact(L * s.row(F)) && g.part.try_exact(n_blk * R) &&
                g.snap_x.try_exact(3 * N) && g.snap_v.try_exact(3 * N);
       },
       [&]() { zero(g.acc, n_acc); });
 }
+ta::MdFluxLaunch md_launch(const ta_context *h, const MdState::Flux &x) {
+  const size_t F = h->keep_natoms.size();
+  ta::MdFluxLaunch fx;
+  fx.mass = h->md.mass.ptr, fx.blk_start = x.blk.ptr, fx.part = x.part.ptr, fx.ring = x.ring.ptr;
+  fx.sums = x.sums(), fx.status = h->res.status.ptr;
+  fx.acc_heat = x.run ? x.acc_heat(F) : nullptr, fx.acc_press = x.run ? x.acc_press(F) : nullptr;
+  fx.n_lags = x.set.p.n_lags, fx.n_frames = (int)F, fx.n_blk = x.n_blk, fx.chunk = x.chunk;
+  return fx;
+}
+// Heat current and pressure tensor: the three launches go BEHIND the integrator launch as well (v(t) exists only after
+// its closing half-kick), under the same predicate. They read the velocities of the snapshot (md_snapshot) and, through
+// DeviceBatch, the list, pair records, g and eatom of the evaluation of x(t), which nothing rewrites before the next
+// compute_impl, enqueued behind them.
+void md_enqueue(const ta_context *h, const MdState::Flux &x, ta::MdFluxLaunch &fx, int64_t step0, int k, const MdSnapshot &snap) {
+  if (!md_due(x, step0, k)) return;
+  fx.v = snap.v, fx.seq = (unsigned)k, fx.n = (long long)x.sched.index(step0 + k);
+  ta::launch_md_flux(fx, h->db, h->stream);
+  HIP_CHECK(hipGetLastError());
+}
 
-// what ta_md_set_sq asks of the resident frames: periodic along all three axes, a cell that can be inverted.
-// Returns 0 or the error code.
-int md_sq_frames(ta_context *h) {
+// What ta_md_set_sq and the barostat ask of the resident frames: periodic along all three axes, a cell that can be
+// inverted. The messages begin with `who` and say `why` of the first. Returns 0 or the error code.
+int md_frames_periodic(ta_context *h, const std::string &who, const char *why) {
   const size_t F = h->keep_natoms.size();
   for (size_t f = 0; f < F; ++f) {
     for (int k = 0; k < 3; ++k)
       if (!h->keep_pbc[3 * f + k])
-        return fail(h, TA_ERR_INVALID, "ta_md_set_sq: frame " + std::to_string(f) + " is not periodic along all three axes; "
-                                       "the wave vectors are those of the cell");
+        return fail(h, TA_ERR_INVALID, who + "frame " + std::to_string(f) + " is not periodic along all three axes" + why);
     const double *c = h->ref_cells.data() + 9 * f;
     const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
     if (!std::isfinite(det) || !(std::fabs(det) > 0.0))
-      return fail(h, TA_ERR_INVALID, "ta_md_set_sq: the cell of frame " + std::to_string(f) + " is singular");
+      return fail(h, TA_ERR_INVALID, who + "the cell of frame " + std::to_string(f) + " is singular");
   }
   return TA_OK;
 }
+int md_sq_frames(ta_context *h) { return md_frames_periodic(h, "ta_md_set_sq: ", "; the wave vectors are those of the cell"); }
 
 // The bond cutoffs [E][E] of ta_md_set_adf, ta_md_set_order and ta_md_set_clusters (`who`): r_bond for every pair, or
 // r_bond_pairs; the messages call them `one` and `pairs`. Returns 0 with `rb` filled, or the error code: a cutoff
@@ -310,18 +508,163 @@ int md_sampler_set(ta_context *h, S &x, const typename S::Setting &s, const std:
   return rc;
 }
 
-// the neighbour-list view of launch `k` of a run, for any launch struct that reads the resident list: the state and the
-// (skin) list of the batch, not the exact one filtered from it (a rebuild may have moved them: taken at every launch)
-template <typename L>
-void point_at_list(const ta_context *h, L &l, int k) {
-  l.pos = h->db.pos;
-  l.cells = h->db.cells;
-  l.species = h->db.species;
-  l.atom_start = h->db.atom_start;
-  l.pair_start = h->pair_start.ptr;
-  l.pair_j = h->pair_j.ptr;
-  l.pair_shift = h->pair_shift.ptr;
-  l.seq = (unsigned)k;
+// What ta_md_run refuses before anything is touched: its arguments, the resident frames under the barostat and the
+// chain, the samplers that exclude the barostat, and what the clusters need of the order parameters. Returns 0 or the
+// error code.
+int md_run_refusals(ta_context *h, int32_t n_steps, double dt, int32_t record_every) {
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_run: no resident batch");
+  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_run called before ta_md_init (ta_set_frames drops the MD state)");
+  if (n_steps < 0 || record_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_run: n_steps >= 0 and record_every >= 1 are needed");
+  if (!std::isfinite(dt)) return fail(h, TA_ERR_INVALID, "ta_md_run: dt must be finite");
+  const MdState &md = h->md;
+  if (md.langevin.friction > 0.0 && dt < 0.0) return fail(h, TA_ERR_INVALID, "ta_md_run: Langevin dynamics needs dt >= 0");
+  const bool baro = md.baro.on;
+  if (baro)
+    if (const int bad = md_frames_periodic(h, "ta_md_run: the barostat is on and ", "")) return bad;
+  for (size_t f = 0; md.nhc.on && f < h->keep_natoms.size(); ++f)
+    if (3 * (int64_t)h->keep_natoms[f] - (int64_t)md.nhc.p.dof_removed < 1)
+      return fail(h, TA_ERR_INVALID, "ta_md_run: the Nose-Hoover chain is on and frame " + std::to_string(f) +
+                                     " has fewer than one degree of freedom (3 n_atoms - dof_removed)");
+  // the samplers that need one cell for the whole run, in the order they are refused in
+  const std::pair<bool, const char *> no_barostat[] = {
+      {md.corr.on, "ta_md_run: sampling (ta_md_set_sampling) and the barostat (ta_md_set_barostat) are both on; "
+                   "displacements in a moving cell are not defined: switch one of them off"},
+      {md.rdf.on, "ta_md_run: the pair distributions (ta_md_set_rdf) and the barostat (ta_md_set_barostat) are both on; "
+                  "normalising the counts needs one volume: switch one of them off"},
+      {md.sq.on, "ta_md_run: the structure factors (ta_md_set_sq) and the barostat (ta_md_set_barostat) are both on; cell "
+                 "and positions of a snapshot would belong to different states: switch one of them off"},
+      {md.flux.on, "ta_md_run: the heat current and pressure tensor (ta_md_set_flux) and the barostat (ta_md_set_barostat) "
+                   "are both on; normalising the correlations needs one volume: switch one of them off"}};
+  for (const auto &x : no_barostat)
+    if (x.first && baro) return fail(h, TA_ERR_INVALID, x.second);
+  if (md.cluster.on && md.cluster.set.p.n_min > 0) {  // n_conn of the order launches for the same state is read
+    if (!md.order.on)
+      return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and reads n_conn, but "
+                                     "the bond-orientational order parameters (ta_md_set_order) are off");
+    if (!md.order.sched.valid)
+      return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and reads n_conn, but a "
+                                     "ta_md_run failed and left the data of ta_md_set_order invalid; call ta_md_set_order again");
+    if (md.cluster.set.p.sample_every % md.order.set.p.sample_every != 0)
+      return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and its sample_every = " +
+                                     std::to_string(md.cluster.set.p.sample_every) + " is no multiple of that of ta_md_set_order, " +
+                                     std::to_string(md.order.set.p.sample_every) + ": n_conn of a sampled state would be missing");
+    if (md.cluster.sched.origin < md.order.sched.origin)
+      return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and its first sample, step " +
+                                     std::to_string(md.cluster.sched.origin) + ", is in front of the first one of ta_md_set_order, "
+                                     "step " + std::to_string(md.order.sched.origin) + ": switch the order parameters on first");
+  }
+  return TA_OK;
+}
+
+// The integrator launch's arguments that are fixed for a ta_md_run of time step dt in workgroups of `chunk` atoms: the
+// buffers, the thermostat that is on (Berendsen, Langevin or the chain; never two), the barostat and the skin
+ta::MdLaunch md_launch(const ta_context *h, double dt, int chunk) {
+  const MdState &md = h->md;
+  const ResidentLoop &res = h->res;
+  const bool thermostat = md.berendsen.kT0 > 0.0, langevin = md.langevin.friction > 0.0, baro = md.baro.on, nhc = md.nhc.on;
+  ta::MdLaunch a;
+  a.vel = md.vel.ptr, a.mass = md.mass.ptr, a.epot = md.epot.ptr, a.ke_part = md.ke.ptr;
+  a.ref = res.ref.ptr, a.blk_start = res.blk_start.ptr;
+  a.status = res.status.ptr, a.status_host = const_cast<unsigned *>(res.host_words());
+  a.dt = dt;
+  a.kT0 = langevin ? md.langevin.kT0 : md.berendsen.kT0;
+  a.dt_over_tau = thermostat ? dt / md.berendsen.tau : 0.0;
+  a.langevin = langevin ? 1 : 0, a.seed = md.langevin.seed;
+  a.c1 = a.c2 = a.c3 = a.c4 = a.c5 = 0.0;
+  if (langevin) {  // ASE's Langevin.updatevars with sigma_i = sqrt(2 kT0 fr) / sqrt(m_i)
+    const double fr = md.langevin.friction, sigma = std::sqrt(2.0 * md.langevin.kT0 * fr);
+    a.c1 = dt / 2.0 - dt * dt * fr / 8.0;
+    a.c2 = dt * fr / 2.0 - dt * dt * fr * fr / 8.0;
+    a.c3 = std::sqrt(dt) * sigma / 2.0 - std::pow(dt, 1.5) * fr * sigma / 8.0;
+    a.c5 = std::pow(dt, 1.5) * sigma / (2.0 * std::sqrt(3.0));
+    a.c4 = fr / 2.0 * a.c5;
+  }
+  a.lim2 = h->skin > 0.0 ? 0.25 * h->skin * h->skin : -1.0;  // skin = 0: every step rebuilds
+  a.n_frames = (int)h->keep_natoms.size(), a.n_blk = res.n_blk, a.chunk = chunk;
+  a.baro = baro ? 1 : 0, a.baro_iso = md.baro.p.isotropic ? 1 : 0;
+  a.cells = nullptr, a.virial = nullptr;
+  a.baro_scale = md.baro.scale.ptr, a.baro_rec = md.baro.rec.ptr;
+  a.baro_p0 = md.baro.p.pressure;
+  a.baro_k = baro ? dt / md.baro.p.taup * md.baro.p.compressibility / 3.0 : 0.0;
+  for (int c = 0; c < 3; ++c) a.baro_mask[c] = md.baro.p.mask[c] ? 1 : 0;
+  a.skin = h->skin, a.r_list = h->rmax + h->skin;
+  a.nhc = nhc ? 1 : 0;
+  a.nhc_chain = md.nhc.p.chain, a.nhc_loops = md.nhc.p.loops, a.nhc_dof = md.nhc.p.dof_removed;
+  a.nhc_kT0 = nhc ? md.nhc.p.kT0 : 0.0;
+  a.nhc_q = nhc ? md.nhc.p.kT0 * md.nhc.p.tau * md.nhc.p.tau : 0.0;
+  a.nhc_eta = md.nhc.eta.ptr, a.nhc_veta = md.nhc.veta.ptr, a.nhc_rec = md.nhc.rec.ptr;
+  return a;
+}
+// The integrator launch k of the run that began at absolute step step0: it finishes step k - 1, records every
+// record_every-th state, writes the snapshot and, with `drift`, begins step k
+void md_enqueue(const ta_context *h, ta::MdLaunch &a, int threads, int64_t step0, int k, bool drift, int record_every,
+                const MdSnapshot &snap) {
+  // (a rebuild may have moved the batch's arrays: the pointers are taken at every launch)
+  a.pos = h->db.pos, a.forces = h->db.forces, a.energy = h->db.energy, a.atom_start = h->db.atom_start;
+  a.cells = h->db.cells, a.virial = h->db.virial;
+  a.seq = (unsigned)k, a.step = (long long)(step0 + k);  // (a step redone after a rebuild keeps its index)
+  a.kick2 = k > 0 ? 1 : 0;  // the state at entry is a whole step
+  a.drift = drift ? 1 : 0;
+  a.rec = (k % record_every == 0) ? (long long)(k / record_every) : -1;
+  a.snap_x = snap.x, a.snap_v = snap.v;
+  ta::launch_md_integrate(a, threads, h->stream);
+  HIP_CHECK(hipGetLastError());
+}
+
+// What a ta_md_run that succeeded leaves on the host, n_rec records each: the barostat's {V, P} (with the final cells on
+// a list of their own, and handed to a cell relaxation whose cells they replace: `cells_at_entry` are those the run
+// began with), the chain's terms, and to `epot` and `ekin` (either may be null) the potential energy and the kinetic
+// energy summed over a frame's workgroups
+void md_read_records(ta_context *h, size_t n_rec, uint32_t want, const std::vector<double> &cells_at_entry, double *epot,
+                     double *ekin, int *rebuilds, int32_t *n_rebuilds) {
+  MdState &md = h->md;
+  const size_t F = h->keep_natoms.size(), n_blk = (size_t)h->res.n_blk;
+  if (md.baro.on && F) {
+    std::vector<double> rec(4 * n_rec * F);
+    HIP_CHECK(hipMemcpy(rec.data(), md.baro.rec.ptr, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
+    md.baro.rec_volume.resize(n_rec * F);
+    md.baro.rec_press.resize(3 * n_rec * F);
+    for (size_t j = 0; j < n_rec * F; ++j) {
+      md.baro.rec_volume[j] = rec[4 * j];
+      for (int c = 0; c < 3; ++c) md.baro.rec_press[3 * j + c] = rec[4 * j + 1 + c];
+    }
+    resident_final_cells(h, "ta_md_run", want, rebuilds, n_rebuilds);
+    if (h->relax.cell.on && h->relax.valid &&
+        std::memcmp(cells_at_entry.data(), h->ref_cells.data(), 9 * F * sizeof(double)) != 0) {
+      // the barostat's cells replace the relaxed ones: they are h0 from here on, G = I, the cell velocities 0
+      HIP_CHECK(hipMemcpy(h->relax.cell.h0.ptr, h->ref_cells.data(), 9 * F * sizeof(double), hipMemcpyHostToDevice));
+      h->relax.cell.reset_deformation(F);
+    }
+    md.baro.rec_valid = true;
+  }
+  if (md.nhc.on) {
+    md.nhc.rec_host.resize(n_rec * F);
+    if (F) HIP_CHECK(hipMemcpy(md.nhc.rec_host.data(), md.nhc.rec.ptr, n_rec * F * sizeof(double), hipMemcpyDeviceToHost));
+    md.nhc.rec_valid = true;
+  }
+  if (epot && F) HIP_CHECK(hipMemcpy(epot, md.epot.ptr, n_rec * F * sizeof(double), hipMemcpyDeviceToHost));
+  if (ekin && F) {
+    std::vector<double> part(n_rec * n_blk);
+    HIP_CHECK(hipMemcpy(part.data(), md.ke.ptr, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const std::vector<int32_t> &start = h->res.blk_start_host;
+    for (size_t r = 0; r < n_rec; ++r)
+      for (size_t f = 0; f < F; ++f) {
+        double t = 0.0;
+        for (int32_t b = start[f]; b < start[f + 1]; ++b) t += part[r * n_blk + (size_t)b];
+        ekin[r * F + f] = t;
+      }
+  }
+}
+
+// what the getters of a ring ask of the window [first_lag, first_lag + n) of the `held` newest `rows` ("snapshots",
+// "rows"); returns 0 or the error code
+int md_ring_window(ta_context *h, const std::string &who, int32_t first_lag, int32_t n, int64_t held, const char *rows) {
+  if (first_lag < 0) return fail(h, TA_ERR_INVALID, who + ": first_lag must be >= 0");
+  if (n < 0) return fail(h, TA_ERR_INVALID, who + ": n must be >= 0");
+  if ((int64_t)first_lag + n > held)
+    return fail(h, TA_ERR_INVALID, who + ": first_lag + n = " + std::to_string((int64_t)first_lag + n) + " exceeds the " +
+                                   std::to_string(held) + " " + rows + " held (min(n_samples, n_lags))");
+  return TA_OK;
 }
 
 // the four words every sampler's getter begins its info with: samples taken, `size` (the feature's), sample_every, the
@@ -333,17 +676,17 @@ void fill_info(int64_t *info, const MdSampler &x, int64_t size) {
   info[3] = x.sched.last;
 }
 
-// The held rows of a series ring (`n_rows` rows of `row` words; sample n is in row n % n_rows), oldest first, to
-// `series` and their steps to `steps` (either may be null). Returns the rows held.
-template <typename T>
-int64_t copy_series(const MdSampler &x, const DevBuf<T> &ring, int64_t n_rows, size_t row, int64_t *series, int64_t *steps) {
-  static_assert(sizeof(T) == sizeof(int64_t), "the rows are copied as they are");
-  const int64_t taken = x.sched.taken(), held = std::min(taken, n_rows);
+// The held rows of the series ring of sampler x (clusters, CNA) for F frames, oldest first, to `series` and their steps
+// to `steps` (either may be null). Returns the rows held.
+template <typename S>
+int64_t copy_series(const S &x, size_t F, int64_t *series, int64_t *steps) {
+  static_assert(sizeof(*x.series.ptr) == sizeof(int64_t), "the rows are copied as they are");
+  const size_t row = x.set.row(F);
+  const int64_t taken = x.sched.taken(), held = std::min<int64_t>(taken, x.set.p.n_series);
   for (int64_t j = 0; j < held; ++j) {
     const int64_t idx = taken - held + j;  // sample number
     if (series && row)
-      HIP_CHECK(hipMemcpy(series + (size_t)j * row, ring.ptr + (size_t)(idx % n_rows) * row, row * sizeof(int64_t),
-                          hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(series + (size_t)j * row, x.series_row(idx, F), row * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (steps) steps[j] = x.sched.step(idx);
   }
   return held;
@@ -548,10 +891,10 @@ int ta_md_get_correlations(ta_handle h, double *vacf_sum, double *msd_sum, int64
   if (const int rc = md_sampler_ready(h, h->md.corr, "ta_md_get_correlations")) return rc;
   return guarded(h, [&]() {
     const auto &corr = h->md.corr;
-    const size_t n = h->keep_natoms.size() * (size_t)h->n_elements * (size_t)corr.set.p.n_lags;
+    const size_t F = h->keep_natoms.size(), E = (size_t)h->n_elements, n = corr.set.n_sums(F, E);
     HIP_CHECK(hipStreamSynchronize(h->stream));
-    if (vacf_sum && n) HIP_CHECK(hipMemcpy(vacf_sum, corr.acc.ptr, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (msd_sum && n) HIP_CHECK(hipMemcpy(msd_sum, corr.acc.ptr + n, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (vacf_sum && n) HIP_CHECK(hipMemcpy(vacf_sum, corr.acc_v(), n * sizeof(double), hipMemcpyDeviceToHost));
+    if (msd_sum && n) HIP_CHECK(hipMemcpy(msd_sum, corr.acc_x(F, E), n * sizeof(double), hipMemcpyDeviceToHost));
     if (info) fill_info(info, corr, corr.set.p.n_lags);
   });
 }
@@ -562,21 +905,16 @@ int ta_md_get_samples(ta_handle h, int32_t first_lag, int32_t n, double *positio
   if (const int rc = md_sampler_ready(h, h->md.corr, "ta_md_get_samples")) return rc;
   const auto &corr = h->md.corr;
   const int64_t taken = corr.sched.taken(), L = corr.set.p.n_lags, held = std::min(taken, L);
-  if (first_lag < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_samples: first_lag must be >= 0");
-  if (n < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_samples: n must be >= 0");
-  if ((int64_t)first_lag + n > held)
-    return fail(h, TA_ERR_INVALID, "ta_md_get_samples: first_lag + n = " + std::to_string((int64_t)first_lag + n) +
-                                   " exceeds the " + std::to_string(held) + " snapshots held (min(n_samples, n_lags))");
+  if (const int bad = md_ring_window(h, "ta_md_get_samples", first_lag, n, held, "snapshots")) return bad;
   return guarded(h, [&]() {
-    const size_t row = 3 * h->keep_species.size();
+    const size_t N = h->keep_species.size(), row = 3 * N;
     HIP_CHECK(hipStreamSynchronize(h->stream));
     for (int32_t j = 0; j < n; ++j) {
       const int64_t idx = taken - 1 - first_lag - j;  // sample number
-      const size_t slot = (size_t)(idx % L);
       if (positions && row)
-        HIP_CHECK(hipMemcpy(positions + (size_t)j * row, corr.ring_x.ptr + slot * row, row * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(positions + (size_t)j * row, corr.slot(corr.ring_x, idx, N), row * sizeof(double), hipMemcpyDeviceToHost));
       if (velocities && row)
-        HIP_CHECK(hipMemcpy(velocities + (size_t)j * row, corr.ring_v.ptr + slot * row, row * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(velocities + (size_t)j * row, corr.slot(corr.ring_v, idx, N), row * sizeof(double), hipMemcpyDeviceToHost));
       if (steps) steps[j] = corr.sched.step(idx);
     }
   });
@@ -671,14 +1009,13 @@ int ta_md_get_order(ta_handle h, int64_t *hist_q, int64_t *hist_qbar, int64_t *h
   const auto &order = h->md.order;
   return guarded(h, [&]() {
     const size_t E = (size_t)h->n_elements, F = h->keep_natoms.size();
-    const size_t n_hist = F * E * (size_t)order.set.p.n_degrees * (size_t)order.set.p.n_bins;
-    const size_t n_conn = F * E * (TA_MD_ORDER_MAX_CONN + 1);
+    const size_t n_hist = order.set.n_hist(F, E), n_conn = order.set.n_hist_conn(F, E);
     HIP_CHECK(hipStreamSynchronize(h->stream));
-    if (hist_q && n_hist) HIP_CHECK(hipMemcpy(hist_q, order.acc.ptr, n_hist * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (hist_q && n_hist) HIP_CHECK(hipMemcpy(hist_q, order.hist_q(), n_hist * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (hist_qbar && n_hist)
-      HIP_CHECK(hipMemcpy(hist_qbar, order.acc.ptr + n_hist, n_hist * sizeof(int64_t), hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(hist_qbar, order.hist_qbar(F, E), n_hist * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (hist_conn && n_conn)
-      HIP_CHECK(hipMemcpy(hist_conn, order.acc.ptr + 2 * n_hist, n_conn * sizeof(int64_t), hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(hist_conn, order.hist_conn(F, E), n_conn * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (info) fill_info(info, order, order.set.p.n_bins);
     if (r_bond_pairs) std::memcpy(r_bond_pairs, order.set.rb.data(), E * E * sizeof(double));
   });
@@ -690,13 +1027,13 @@ int ta_md_get_order_atoms(ta_handle h, double *q, double *qbar, int32_t *n_bonds
   const auto &order = h->md.order;
   if (order.sched.last < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_order_atoms: no sample has been taken yet");
   return guarded(h, [&]() {
-    const size_t N = h->keep_species.size(), D = (size_t)order.set.p.n_degrees, M = (size_t)order.n_lm;
+    const size_t N = h->keep_species.size(), n_q = order.set.n_q(N), M = (size_t)order.n_lm;
     HIP_CHECK(hipStreamSynchronize(h->stream));
     if (!N) return;
-    if (q) HIP_CHECK(hipMemcpy(q, order.per_atom.ptr, N * D * sizeof(double), hipMemcpyDeviceToHost));
-    if (qbar) HIP_CHECK(hipMemcpy(qbar, order.per_atom.ptr + N * D, N * D * sizeof(double), hipMemcpyDeviceToHost));
-    if (n_bonds) HIP_CHECK(hipMemcpy(n_bonds, order.per_atom_int.ptr, N * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (n_conn) HIP_CHECK(hipMemcpy(n_conn, order.per_atom_int.ptr + N, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (q) HIP_CHECK(hipMemcpy(q, order.q(), n_q * sizeof(double), hipMemcpyDeviceToHost));
+    if (qbar) HIP_CHECK(hipMemcpy(qbar, order.qbar(N), n_q * sizeof(double), hipMemcpyDeviceToHost));
+    if (n_bonds) HIP_CHECK(hipMemcpy(n_bonds, order.n_bonds(), N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (n_conn) HIP_CHECK(hipMemcpy(n_conn, order.n_conn(N), N * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (qlm) HIP_CHECK(hipMemcpy(qlm, order.qlm.ptr, N * 2 * M * sizeof(double), hipMemcpyDeviceToHost));
   });
 }
@@ -729,10 +1066,10 @@ int ta_md_get_clusters(ta_handle h, int64_t *hist, int64_t *series, int64_t *ste
   if (const int bad = md_sampler_ready(h, h->md.cluster, "ta_md_get_clusters")) return bad;
   const auto &cluster = h->md.cluster;
   return guarded(h, [&]() {
-    const size_t E = (size_t)h->n_elements, F = h->keep_natoms.size(), n_hist = F * (size_t)cluster.set.p.n_bins;
+    const size_t E = (size_t)h->n_elements, F = h->keep_natoms.size(), n_hist = cluster.set.n_hist(F);
     HIP_CHECK(hipStreamSynchronize(h->stream));
     if (hist && n_hist) HIP_CHECK(hipMemcpy(hist, cluster.acc.ptr, n_hist * sizeof(int64_t), hipMemcpyDeviceToHost));
-    const int64_t held = copy_series(cluster, cluster.series, cluster.set.p.n_series, F * 4, series, steps);
+    const int64_t held = copy_series(cluster, F, series, steps);
     if (info) {
       fill_info(info, cluster, cluster.set.p.n_bins);
       info[4] = held;
@@ -751,8 +1088,8 @@ int ta_md_get_cluster_atoms(ta_handle h, int32_t *label, int32_t *size) {
     const size_t N = h->keep_species.size();
     HIP_CHECK(hipStreamSynchronize(h->stream));
     if (!N) return;
-    if (label) HIP_CHECK(hipMemcpy(label, cluster.per_atom.ptr + 2 * N, N * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (size) HIP_CHECK(hipMemcpy(size, cluster.per_atom.ptr + 3 * N, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (label) HIP_CHECK(hipMemcpy(label, cluster.label(N), N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (size) HIP_CHECK(hipMemcpy(size, cluster.size(N), N * sizeof(int32_t), hipMemcpyDeviceToHost));
   });
 }
 
@@ -784,10 +1121,10 @@ int ta_md_get_cna(ta_handle h, int64_t *counts, int64_t *series, int64_t *steps,
   if (const int bad = md_sampler_ready(h, h->md.cna, "ta_md_get_cna")) return bad;
   const auto &cna = h->md.cna;
   return guarded(h, [&]() {
-    const size_t E = (size_t)h->n_elements, F = h->keep_natoms.size(), n_acc = F * E * TA_MD_CNA_TYPES;
+    const size_t E = (size_t)h->n_elements, F = h->keep_natoms.size(), n_acc = cna.set.n_acc(F, E);
     HIP_CHECK(hipStreamSynchronize(h->stream));
     if (counts && n_acc) HIP_CHECK(hipMemcpy(counts, cna.acc.ptr, n_acc * sizeof(int64_t), hipMemcpyDeviceToHost));
-    const int64_t held = copy_series(cna, cna.series, cna.set.p.n_series, F * TA_MD_CNA_TYPES, series, steps);
+    const int64_t held = copy_series(cna, F, series, steps);
     if (info) {
       fill_info(info, cna, cna.set.p.mode);
       info[4] = held;
@@ -836,12 +1173,11 @@ int ta_md_get_sq(ta_handle h, double *a_rho, double *a_l, double *a_j, int64_t *
   if ((a_l || a_j) && !sq.set.p.currents)
     return fail(h, TA_ERR_INVALID, "ta_md_get_sq: a_l and a_j need the currents (ta_md_sq_params.currents = 1)");
   return guarded(h, [&]() {
-    const size_t E = (size_t)h->n_elements;
-    const size_t n = h->keep_natoms.size() * E * E * (size_t)sq.set.p.n_lags * (size_t)sq.set.p.n_q;
+    const size_t F = h->keep_natoms.size(), E = (size_t)h->n_elements, n = sq.set.n_sums(F, E);
     HIP_CHECK(hipStreamSynchronize(h->stream));
-    if (a_rho && n) HIP_CHECK(hipMemcpy(a_rho, sq.acc.ptr, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (a_l && n) HIP_CHECK(hipMemcpy(a_l, sq.acc.ptr + n, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (a_j && n) HIP_CHECK(hipMemcpy(a_j, sq.acc.ptr + 2 * n, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (a_rho && n) HIP_CHECK(hipMemcpy(a_rho, sq.acc_rho(), n * sizeof(double), hipMemcpyDeviceToHost));
+    if (a_l && n) HIP_CHECK(hipMemcpy(a_l, sq.acc_l(F, E), n * sizeof(double), hipMemcpyDeviceToHost));
+    if (a_j && n) HIP_CHECK(hipMemcpy(a_j, sq.acc_j(F, E), n * sizeof(double), hipMemcpyDeviceToHost));
     if (info) {
       info[0] = sq.sched.taken();
       info[1] = sq.set.p.n_q;
@@ -861,23 +1197,19 @@ int ta_md_get_sq_amplitudes(ta_handle h, int32_t first_lag, int32_t n, double *r
   if (const int bad = md_sampler_ready(h, h->md.sq, "ta_md_get_sq_amplitudes")) return bad;
   const auto &sq = h->md.sq;
   const int64_t taken = sq.sched.taken(), L = sq.set.p.n_lags, held = std::min(taken, L);
-  if (first_lag < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_sq_amplitudes: first_lag must be >= 0");
-  if (n < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_sq_amplitudes: n must be >= 0");
-  if ((int64_t)first_lag + n > held)
-    return fail(h, TA_ERR_INVALID, "ta_md_get_sq_amplitudes: first_lag + n = " + std::to_string((int64_t)first_lag + n) +
-                                   " exceeds the " + std::to_string(held) + " rows held (min(n_samples, n_lags))");
+  if (const int bad = md_ring_window(h, "ta_md_get_sq_amplitudes", first_lag, n, held, "rows")) return bad;
   if (cur && !sq.set.p.currents)
     return fail(h, TA_ERR_INVALID, "ta_md_get_sq_amplitudes: cur needs the currents (ta_md_sq_params.currents = 1)");
   return guarded(h, [&]() {
-    const size_t FE = h->keep_natoms.size() * (size_t)h->n_elements, Q = (size_t)sq.set.p.n_q, P = sq.set.p.currents ? 8 : 2;
-    const size_t row = FE * P * Q;
+    const size_t F = h->keep_natoms.size(), E = (size_t)h->n_elements, FE = F * E;
+    const size_t Q = (size_t)sq.set.p.n_q, P = sq.set.planes(), row = sq.set.row(F, E);
     HIP_CHECK(hipStreamSynchronize(h->stream));
     std::vector<double> buf(row);
     for (int32_t j = 0; j < n; ++j) {
       const int64_t idx = taken - 1 - first_lag - j;  // sample number
       if (steps) steps[j] = sq.sched.step(idx);
       if (!row || (!rho && !cur)) continue;
-      HIP_CHECK(hipMemcpy(buf.data(), sq.ring.ptr + (size_t)(idx % L) * row, row * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(buf.data(), sq.ring_row(idx, F, E), row * sizeof(double), hipMemcpyDeviceToHost));
       // the device row is [f][e][plane][q]; the caller's arrays have q before the components
       for (size_t fe = 0; fe < FE; ++fe)
         for (size_t q = 0; q < Q; ++q) {
@@ -905,12 +1237,11 @@ int ta_md_get_flux(ta_handle h, double *sums, double *a_heat, double *a_press, i
   if (const int bad = md_sampler_ready(h, h->md.flux, "ta_md_get_flux")) return bad;
   const auto &fx = h->md.flux;
   return guarded(h, [&]() {
-    const size_t F = h->keep_natoms.size(), L = (size_t)fx.set.p.n_lags, R = ta::kMdFluxRow;
+    const size_t F = h->keep_natoms.size();
     HIP_CHECK(hipStreamSynchronize(h->stream));
-    if (sums && F) HIP_CHECK(hipMemcpy(sums, fx.acc.ptr, F * R * sizeof(double), hipMemcpyDeviceToHost));
-    if (a_heat && F) HIP_CHECK(hipMemcpy(a_heat, fx.acc.ptr + F * R, F * L * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (a_press && F)
-      HIP_CHECK(hipMemcpy(a_press, fx.acc.ptr + F * R + F * L * 3, F * L * 6 * sizeof(double), hipMemcpyDeviceToHost));
+    if (sums && F) HIP_CHECK(hipMemcpy(sums, fx.sums(), fx.set.row(F) * sizeof(double), hipMemcpyDeviceToHost));
+    if (a_heat && F) HIP_CHECK(hipMemcpy(a_heat, fx.acc_heat(F), fx.set.n_heat(F) * sizeof(double), hipMemcpyDeviceToHost));
+    if (a_press && F) HIP_CHECK(hipMemcpy(a_press, fx.acc_press(F), fx.set.n_press(F) * sizeof(double), hipMemcpyDeviceToHost));
     if (info) {
       int64_t most = 0;
       for (size_t f = 0; f < F; ++f)
@@ -932,20 +1263,15 @@ int ta_md_get_flux_rows(ta_handle h, int32_t first_lag, int32_t n, double *rows,
   if (const int bad = md_sampler_ready(h, h->md.flux, "ta_md_get_flux_rows")) return bad;
   const auto &fx = h->md.flux;
   const int64_t taken = fx.sched.taken(), L = fx.set.p.n_lags, held = std::min(taken, L);
-  if (first_lag < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_flux_rows: first_lag must be >= 0");
-  if (n < 0) return fail(h, TA_ERR_INVALID, "ta_md_get_flux_rows: n must be >= 0");
-  if ((int64_t)first_lag + n > held)
-    return fail(h, TA_ERR_INVALID, "ta_md_get_flux_rows: first_lag + n = " + std::to_string((int64_t)first_lag + n) +
-                                   " exceeds the " + std::to_string(held) + " rows held (min(n_samples, n_lags))");
+  if (const int bad = md_ring_window(h, "ta_md_get_flux_rows", first_lag, n, held, "rows")) return bad;
   return guarded(h, [&]() {
-    const size_t row = h->keep_natoms.size() * (size_t)ta::kMdFluxRow;
+    const size_t F = h->keep_natoms.size(), row = fx.set.row(F);
     HIP_CHECK(hipStreamSynchronize(h->stream));
     for (int32_t j = 0; j < n; ++j) {
       const int64_t idx = taken - 1 - first_lag - j;  // sample number
       if (steps) steps[j] = fx.sched.step(idx);
       if (rows && row)
-        HIP_CHECK(hipMemcpy(rows + (size_t)j * row, fx.ring.ptr + (size_t)(idx % L) * row, row * sizeof(double),
-                            hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(rows + (size_t)j * row, fx.ring_row(idx, F), row * sizeof(double), hipMemcpyDeviceToHost));
     }
   });
 }
@@ -1011,65 +1337,10 @@ int ta_md_get_records(ta_handle h, double *volume, double *press) {
 int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t record_every, double *epot,
               double *ekin, int32_t *n_rebuilds) {
   if (!h) return TA_ERR_INVALID;
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "ta_md_run: no resident batch");
-  if (!h->md.valid) return fail(h, TA_ERR_INVALID, "ta_md_run called before ta_md_init (ta_set_frames drops the MD state)");
-  if (n_steps < 0 || record_every < 1) return fail(h, TA_ERR_INVALID, "ta_md_run: n_steps >= 0 and record_every >= 1 are needed");
-  if (!std::isfinite(dt)) return fail(h, TA_ERR_INVALID, "ta_md_run: dt must be finite");
+  if (const int bad = md_run_refusals(h, n_steps, dt, record_every)) return bad;
   MdState &md = h->md;
   ResidentLoop &res = h->res;
-  if (md.langevin.friction > 0.0 && dt < 0.0) return fail(h, TA_ERR_INVALID, "ta_md_run: Langevin dynamics needs dt >= 0");
-  const bool baro = md.baro.on;
-  if (baro) {
-    const size_t F = h->keep_natoms.size();
-    for (size_t f = 0; f < F; ++f) {
-      for (int k = 0; k < 3; ++k)
-        if (!h->keep_pbc[3 * f + k])
-          return fail(h, TA_ERR_INVALID, "ta_md_run: the barostat is on and frame " + std::to_string(f) +
-                                         " is not periodic along all three axes");
-      const double *c = h->ref_cells.data() + 9 * f;
-      const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
-      if (!std::isfinite(det) || !(std::fabs(det) > 0.0))
-        return fail(h, TA_ERR_INVALID, "ta_md_run: the barostat is on and the cell of frame " + std::to_string(f) + " is singular");
-    }
-  }
-  const bool nhc = md.nhc.on;
-  if (nhc) {
-    const size_t F = h->keep_natoms.size();
-    for (size_t f = 0; f < F; ++f)
-      if (3 * (int64_t)h->keep_natoms[f] - (int64_t)md.nhc.p.dof_removed < 1)
-        return fail(h, TA_ERR_INVALID, "ta_md_run: the Nose-Hoover chain is on and frame " + std::to_string(f) +
-                                       " has fewer than one degree of freedom (3 n_atoms - dof_removed)");
-  }
-  if (md.corr.on && baro)
-    return fail(h, TA_ERR_INVALID, "ta_md_run: sampling (ta_md_set_sampling) and the barostat (ta_md_set_barostat) are both "
-                                   "on; displacements in a moving cell are not defined: switch one of them off");
-  if (md.rdf.on && baro)
-    return fail(h, TA_ERR_INVALID, "ta_md_run: the pair distributions (ta_md_set_rdf) and the barostat (ta_md_set_barostat) are "
-                                   "both on; normalising the counts needs one volume: switch one of them off");
-  if (md.sq.on && baro)
-    return fail(h, TA_ERR_INVALID, "ta_md_run: the structure factors (ta_md_set_sq) and the barostat (ta_md_set_barostat) are "
-                                   "both on; cell and positions of a snapshot would belong to different states: switch one of "
-                                   "them off");
-  if (md.flux.on && baro)
-    return fail(h, TA_ERR_INVALID, "ta_md_run: the heat current and pressure tensor (ta_md_set_flux) and the barostat "
-                                   "(ta_md_set_barostat) are both on; normalising the correlations needs one volume: "
-                                   "switch one of them off");
-  if (md.cluster.on && md.cluster.set.p.n_min > 0) {  // n_conn of the order launches for the same state is read
-    if (!md.order.on)
-      return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and reads n_conn, but "
-                                     "the bond-orientational order parameters (ta_md_set_order) are off");
-    if (!md.order.sched.valid)
-      return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and reads n_conn, but a "
-                                     "ta_md_run failed and left the data of ta_md_set_order invalid; call ta_md_set_order again");
-    if (md.cluster.set.p.sample_every % md.order.set.p.sample_every != 0)
-      return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and its sample_every = " +
-                                     std::to_string(md.cluster.set.p.sample_every) + " is no multiple of that of ta_md_set_order, " +
-                                     std::to_string(md.order.set.p.sample_every) + ": n_conn of a sampled state would be missing");
-    if (md.cluster.sched.origin < md.order.sched.origin)
-      return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and its first sample, step " +
-                                     std::to_string(md.cluster.sched.origin) + ", is in front of the first one of ta_md_set_order, "
-                                     "step " + std::to_string(md.order.sched.origin) + ": switch the order parameters on first");
-  }
+  const bool baro = md.baro.on, nhc = md.nhc.on;
   if (n_rebuilds) *n_rebuilds = 0;
   want |= TA_WANT_ENERGY | TA_WANT_FORCES;
   want &= ~(uint32_t)TA_WANT_REUSE_DESCRIPTORS;
@@ -1080,274 +1351,52 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
   res.cell_running = md.baro.running = baro;
   const int rc = guarded(h, [&]() {
     const size_t N = h->keep_species.size(), F = h->keep_natoms.size();
-    hipStream_t s = h->stream;
     // while the heat current is sampled every evaluation of the run leaves g_p = d e_c / d D_p (put back below)
     set_centre_gradients(h, md.flux.run);
-    const bool thermostat = md.berendsen.kT0 > 0.0, langevin = md.langevin.friction > 0.0;  // (never both)
     // with Berendsen scaling one workgroup owns a whole frame: the factor needs the frame's kinetic energy
     // (the barostat: the frame's three sums of m v_c^2; the Nose-Hoover chain: the kinetic energy again)
+    const bool whole_frames = md.berendsen.kT0 > 0.0 || baro || nhc;
     int chunk = ta::kMdChunk;
-    if (thermostat || baro || nhc)
+    if (whole_frames)
       for (size_t f = 0; f < F; ++f) chunk = std::max(chunk, h->keep_natoms[f]);
-    const int threads = (thermostat || baro || nhc) ? 1024 : 256;
+    const int threads = whole_frames ? 1024 : 256;
     md_plan_blocks(h, chunk);
-    const size_t n_blk = (size_t)res.n_blk, n_rec = (size_t)(n_steps / record_every) + 1;
+    const size_t n_rec = (size_t)(n_steps / record_every) + 1;
     md.epot.ensure(n_rec * F + 1);
-    md.ke.ensure(n_rec * n_blk + 1);
+    md.ke.ensure(n_rec * (size_t)res.n_blk + 1);
     if (nhc) md.nhc.rec.ensure(n_rec * F + 1);
     const std::vector<double> cells_at_entry(baro ? h->ref_cells : std::vector<double>());
     if (baro) {  // every run starts on a list built for the resident cells: the cumulative scale is 1
       md.baro.rec.ensure(4 * n_rec * F + 1);
       md.baro.scale.ensure(3 * F + 1);
       md.baro.ones.assign(3 * F, 1.0);
-      HIP_CHECK(hipStreamSynchronize(s));
+      HIP_CHECK(hipStreamSynchronize(h->stream));
       if (F) HIP_CHECK(hipMemcpy(md.baro.scale.ptr, md.baro.ones.data(), 3 * F * sizeof(double), hipMemcpyHostToDevice));
     }
     resident_begin(h);
 
-    ta::MdLaunch a;
-    a.vel = md.vel.ptr;
-    a.mass = md.mass.ptr;
-    a.ref = res.ref.ptr;
-    a.blk_start = res.blk_start.ptr;
-    a.epot = md.epot.ptr;
-    a.ke_part = md.ke.ptr;
-    a.status = res.status.ptr;
-    a.status_host = const_cast<unsigned *>(res.host_words());
-    a.dt = dt;
-    a.kT0 = langevin ? md.langevin.kT0 : md.berendsen.kT0;
-    a.dt_over_tau = thermostat ? dt / md.berendsen.tau : 0.0;
-    a.langevin = langevin ? 1 : 0;
-    a.seed = md.langevin.seed;
-    a.c1 = a.c2 = a.c3 = a.c4 = a.c5 = 0.0;
-    if (langevin) {  // ASE's Langevin.updatevars with sigma_i = sqrt(2 kT0 fr) / sqrt(m_i)
-      const double fr = md.langevin.friction, sigma = std::sqrt(2.0 * md.langevin.kT0 * fr);
-      a.c1 = dt / 2.0 - dt * dt * fr / 8.0;
-      a.c2 = dt * fr / 2.0 - dt * dt * fr * fr / 8.0;
-      a.c3 = std::sqrt(dt) * sigma / 2.0 - std::pow(dt, 1.5) * fr * sigma / 8.0;
-      a.c5 = std::pow(dt, 1.5) * sigma / (2.0 * std::sqrt(3.0));
-      a.c4 = fr / 2.0 * a.c5;
-    }
     const int64_t step0 = md.step;  // absolute index of this run's first step
-    a.lim2 = h->skin > 0.0 ? 0.25 * h->skin * h->skin : -1.0;  // skin = 0: every step rebuilds
-    a.n_frames = (int)F;
-    a.n_blk = (int)n_blk;
-    a.chunk = chunk;
-    a.baro = baro ? 1 : 0;
-    a.baro_iso = md.baro.p.isotropic ? 1 : 0;
-    a.cells = nullptr, a.virial = nullptr;
-    a.baro_scale = md.baro.scale.ptr;
-    a.baro_rec = md.baro.rec.ptr;
-    a.baro_p0 = md.baro.p.pressure;
-    a.baro_k = baro ? dt / md.baro.p.taup * md.baro.p.compressibility / 3.0 : 0.0;
-    for (int c = 0; c < 3; ++c) a.baro_mask[c] = md.baro.p.mask[c] ? 1 : 0;
-    a.skin = h->skin;
-    a.r_list = h->rmax + h->skin;
-    a.nhc = nhc ? 1 : 0;
-    a.nhc_chain = md.nhc.p.chain, a.nhc_loops = md.nhc.p.loops, a.nhc_dof = md.nhc.p.dof_removed;
-    a.nhc_kT0 = nhc ? md.nhc.p.kT0 : 0.0;
-    a.nhc_q = nhc ? md.nhc.p.kT0 * md.nhc.p.tau * md.nhc.p.tau : 0.0;
-    a.nhc_eta = md.nhc.eta.ptr, a.nhc_veta = md.nhc.veta.ptr, a.nhc_rec = md.nhc.rec.ptr;
-    // Sampling: the launch of step k holds the whole-step state t = step0 + k and samples it when the schedule
-    // says so (ta_schedule.h). Sample number and ring slot are functions of t alone, so the launches that returned
-    // early behind a stale list and are enqueued again after the rebuild write what they would have written.
-    const int64_t samp_L = md.corr.set.p.n_lags;
-    ta::MdCorrLaunch c;
-    c.ring_x = md.corr.ring_x.ptr, c.ring_v = md.corr.ring_v.ptr;
-    c.blk_start = md.corr.blk.ptr;
-    c.part = md.corr.part.ptr;
-    c.acc_v = md.corr.acc.ptr;
-    c.acc_x = md.corr.run ? md.corr.acc.ptr + F * (size_t)h->n_elements * (size_t)samp_L : nullptr;
-    c.status = res.status.ptr;
-    c.n_atoms = (long long)N;
-    c.n_lags = (int)samp_L, c.n_elements = h->n_elements, c.n_frames = (int)F, c.n_chunks = md.corr.n_blk;
-    // Pair distributions: the state t = step0 + k is counted by a launch IN FRONT OF the integrator launch of
-    // step k, whose drift leaves x(t). With seq = k the integrator's predicate skips exactly the states that
-    // were reached on a stale list; after the rebuild the launch is enqueued again with the rest and counts
-    // then.
-    ta::MdRdfLaunch g;
-    g.blk_start = md.rdf.blk.ptr;
-    g.counts = md.rdf.acc.ptr;
-    g.status = res.status.ptr;
-    g.n_bins = md.rdf.set.p.n_bins, g.n_elements = h->n_elements, g.n_frames = (int)F;
-    g.n_blk = md.rdf.n_blk, g.chunk = md.rdf.chunk;
-    g.dr = md.rdf.run ? md.rdf.set.p.r_max / (double)md.rdf.set.p.n_bins : 1.0;
-    // Bond-angle distributions: a launch of their own in the same place, under the same predicate (no volume
-    // enters, so they run under the barostat too: db.cells are those of the state t)
-    ta::MdAdfLaunch t;
-    t.blk_start = md.adf.blk.ptr;
-    t.rb2 = md.adf.rb2.ptr;
-    t.counts = md.adf.acc.ptr;
-    t.status = res.status.ptr;
-    t.n_bins = md.adf.set.p.n_bins, t.n_elements = h->n_elements, t.n_frames = (int)F;
-    t.n_blk = md.adf.n_blk, t.chunk = md.adf.chunk;
-    t.dtheta = md.adf.run ? M_PI / (double)md.adf.set.p.n_bins : 1.0;
-    // Bond-orientational order: its two launches in the same place, under the same predicate (no volume either)
-    ta::MdOrderLaunch o;
-    o.blk_start = md.order.blk.ptr;
-    o.rb2 = md.order.rb2.ptr;
-    o.norm = md.order.norm.ptr;
-    o.qlm = md.order.qlm.ptr;
-    o.q = md.order.per_atom.ptr;
-    o.qbar = md.order.run ? md.order.per_atom.ptr + N * (size_t)md.order.set.p.n_degrees : nullptr;
-    o.n_bonds = md.order.per_atom_int.ptr;
-    o.n_conn = md.order.run ? md.order.per_atom_int.ptr + N : nullptr;
-    {
-      const size_t n_hist = F * (size_t)h->n_elements * (size_t)md.order.set.p.n_degrees * (size_t)md.order.set.p.n_bins;
-      o.hist_q = md.order.acc.ptr;
-      o.hist_qbar = md.order.run ? md.order.acc.ptr + n_hist : nullptr;
-      o.hist_conn = md.order.run ? md.order.acc.ptr + 2 * n_hist : nullptr;
-    }
-    o.status = res.status.ptr;
-    o.n_bins = md.order.set.p.n_bins, o.n_elements = h->n_elements, o.n_frames = (int)F;
-    o.n_blk = md.order.n_blk, o.chunk = md.order.chunk;
-    o.n_degrees = md.order.set.p.n_degrees, o.n_lm = md.order.n_lm, o.solid = md.order.solid;
-    o.deg0 = md.order.set.p.degrees[0], o.deg1 = md.order.set.p.degrees[1], o.deg2 = md.order.set.p.degrees[2], o.deg3 = md.order.set.p.degrees[3];
-    o.threshold = md.order.set.p.solid_threshold;
-    // Clusters: four launches in the same place, behind the order launches of the step (n_min > 0 reads their
-    // n_conn), under the same predicate (no volume either)
-    ta::MdClusterLaunch cl;
-    cl.blk_start = md.cluster.blk.ptr;
-    cl.rl2 = md.cluster.rl2.ptr;
-    cl.n_conn = md.cluster.run && md.cluster.set.p.n_min > 0 ? md.order.per_atom_int.ptr + N : nullptr;
-    cl.parent = md.cluster.per_atom.ptr;
-    cl.count = md.cluster.run ? md.cluster.per_atom.ptr + N : nullptr;
-    cl.label = md.cluster.run ? md.cluster.per_atom.ptr + 2 * N : nullptr;
-    cl.size = md.cluster.run ? md.cluster.per_atom.ptr + 3 * N : nullptr;
-    cl.hist = md.cluster.acc.ptr;
-    cl.giveup = md.cluster.giveup.ptr;
-    cl.status = res.status.ptr;
-    cl.n_atoms = (long long)N;
-    cl.n_bins = md.cluster.set.p.n_bins, cl.n_elements = h->n_elements, cl.n_frames = (int)F;
-    cl.n_blk = md.cluster.n_blk, cl.chunk = md.cluster.chunk;
-    cl.n_min = md.cluster.set.p.n_min, cl.species_mask = md.cluster.set.p.species_mask;
-    // Common neighbour analysis: its launch in the same place, behind the order and cluster launches, under the same
-    // predicate (no volume either); sample n counts into row n % n_series, which a launch in front zeroes
-    ta::MdCnaLaunch cn;
-    cn.blk_start = md.cna.blk.ptr;
-    cn.structure = md.cna.structure.ptr;
-    cn.r_local = md.cna.r_local.ptr;
-    cn.counts = md.cna.acc.ptr;
-    cn.status = res.status.ptr;
-    cn.n_elements = h->n_elements, cn.n_frames = (int)F;
-    cn.n_blk = md.cna.n_blk, cn.chunk = md.cna.chunk;
-    cn.mode = md.cna.set.p.mode;
-    cn.r_cut = md.cna.set.p.r_cut;
-    {
-      const double r = md.cna.set.p.mode == TA_MD_CNA_FIXED ? md.cna.set.p.r_cut : md.cna.set.p.r_max;
-      cn.r2 = r * r;
-    }
-    // Structure factors: the integrator launch of a due step writes the whole-step state (x, v) to the slot of the
-    // correlation ring when md_set_sampling is due at the same launch, to two rows of this feature's otherwise;
-    // the three launches go BEHIND it, under the same predicate, and read that snapshot.
-    ta::MdSqLaunch u;
-    u.blk_start = md.sq.blk.ptr;
-    u.miller = md.sq.miller_dev.ptr;
-    u.part = md.sq.part.ptr;
-    u.ring = md.sq.ring.ptr;
-    {
-      const size_t E = (size_t)h->n_elements, n_acc = F * E * E * (size_t)md.sq.set.p.n_lags * (size_t)md.sq.set.p.n_q;
-      u.acc_rho = md.sq.acc.ptr;
-      u.acc_l = md.sq.run && md.sq.set.p.currents ? md.sq.acc.ptr + n_acc : nullptr;
-      u.acc_j = md.sq.run && md.sq.set.p.currents ? md.sq.acc.ptr + 2 * n_acc : nullptr;
-    }
-    u.status = res.status.ptr;
-    u.n_q = md.sq.set.p.n_q, u.n_lags = md.sq.set.p.n_lags, u.n_elements = h->n_elements, u.n_frames = (int)F;
-    u.n_blk = md.sq.n_blk, u.chunk = md.sq.chunk, u.currents = md.sq.set.p.currents;
-    // Heat current and pressure tensor: the three launches go BEHIND the integrator launch as well (v(t) exists only
-    // after its closing half-kick), under the same predicate. They read the velocities of the snapshot (the ring slot of
-    // md_set_sampling or the rows of md_set_sq when one of them is due at the same launch, this feature's own rows
-    // otherwise) and, through DeviceBatch, the list, pair records, g and eatom of the evaluation of x(t), which
-    // nothing rewrites before the next compute_impl, enqueued behind them.
-    ta::MdFluxLaunch fx;
-    fx.mass = md.mass.ptr;
-    fx.blk_start = md.flux.blk.ptr;
-    fx.part = md.flux.part.ptr;
-    fx.ring = md.flux.ring.ptr;
-    fx.sums = md.flux.acc.ptr;
-    fx.acc_heat = md.flux.run ? md.flux.acc.ptr + F * ta::kMdFluxRow : nullptr;
-    fx.acc_press = md.flux.run ? md.flux.acc.ptr + F * ta::kMdFluxRow + F * (size_t)md.flux.set.p.n_lags * 3 : nullptr;
-    fx.status = res.status.ptr;
-    fx.n_lags = md.flux.set.p.n_lags, fx.n_frames = (int)F, fx.n_blk = md.flux.n_blk, fx.chunk = md.flux.chunk;
+    auto integrator = md_launch(h, dt, chunk);
+    auto order = md_launch(h, md.order);
+    auto cluster = md_launch(h, md.cluster);
+    auto cna = md_launch(h, md.cna);
+    auto adf = md_launch(h, md.adf);
+    auto rdf = md_launch(h, md.rdf);
+    auto corr = md_launch(h, md.corr);
+    auto sq = md_launch(h, md.sq);
+    auto flux = md_launch(h, md.flux);
+    // launch k: the samplers of the state t = step0 + k in front, the integrator, the samplers of its snapshot behind
     auto integrate = [&](int k, bool drift) {
-      if (md.order.run && md.order.sched.due(step0, k)) {
-        point_at_list(h, o, k);
-        ta::launch_md_order(o, s);
-        HIP_CHECK(hipGetLastError());
-      }
-      if (md.cluster.run && md.cluster.sched.due(step0, k)) {
-        point_at_list(h, cl, k);
-        cl.row = md.cluster.series.ptr + (size_t)(md.cluster.sched.index(step0 + k) % md.cluster.set.p.n_series) * F * 4;
-        ta::launch_md_cluster(cl, s);
-        HIP_CHECK(hipGetLastError());
-      }
-      if (md.cna.run && md.cna.sched.due(step0, k)) {
-        point_at_list(h, cn, k);
-        cn.row = md.cna.series.ptr + (size_t)(md.cna.sched.index(step0 + k) % md.cna.set.p.n_series) * F * TA_MD_CNA_TYPES;
-        ta::launch_md_cna(cn, s);
-        HIP_CHECK(hipGetLastError());
-      }
-      if (md.adf.run && md.adf.sched.due(step0, k)) {
-        point_at_list(h, t, k);
-        ta::launch_md_adf(t, s);
-        HIP_CHECK(hipGetLastError());
-      }
-      if (md.rdf.run && md.rdf.sched.due(step0, k)) {
-        point_at_list(h, g, k);
-        g.pair_i = h->pair_i.ptr;
-        ta::launch_md_rdf(g, s);
-        HIP_CHECK(hipGetLastError());
-      }
-      // (a rebuild may have moved the batch's arrays: the pointers are taken at every launch)
-      a.pos = h->db.pos;
-      a.forces = h->db.forces;
-      a.energy = h->db.energy;
-      a.atom_start = h->db.atom_start;
-      a.cells = h->db.cells;
-      a.virial = h->db.virial;
-      a.seq = (unsigned)k;
-      a.step = (long long)(step0 + k);  // (a step redone after a rebuild keeps its index)
-      a.kick2 = k > 0 ? 1 : 0;  // the state at entry is a whole step
-      a.drift = drift ? 1 : 0;
-      a.rec = (k % record_every == 0) ? (long long)(k / record_every) : -1;
-      a.snap_x = a.snap_v = nullptr;
-      const bool due = md.corr.run && md.corr.sched.due(step0, k);
-      if (due) {
-        c.n = (long long)md.corr.sched.index(step0 + k);
-        const size_t slot = (size_t)(c.n % samp_L);
-        a.snap_x = md.corr.ring_x.ptr + slot * 3 * N;
-        a.snap_v = md.corr.ring_v.ptr + slot * 3 * N;
-      }
-      const bool sq_due = md.sq.run && md.sq.sched.due(step0, k);
-      if (sq_due && !due) a.snap_x = md.sq.snap_x.ptr, a.snap_v = md.sq.snap_v.ptr;
-      const bool flux_due = md.flux.run && md.flux.sched.due(step0, k);
-      if (flux_due && !due && !sq_due) a.snap_x = md.flux.snap_x.ptr, a.snap_v = md.flux.snap_v.ptr;
-      ta::launch_md_integrate(a, threads, s);
-      HIP_CHECK(hipGetLastError());
-      if (due) {  // directly behind the launch that sampled, under the same predicate
-        c.species = h->db.species;
-        c.atom_start = h->db.atom_start;
-        c.seq = (unsigned)k;
-        ta::launch_md_correlate(c, s);
-        HIP_CHECK(hipGetLastError());
-      }
-      if (sq_due) {
-        u.x = a.snap_x, u.v = a.snap_v;
-        u.cells = h->db.cells;
-        u.species = h->db.species;
-        u.atom_start = h->db.atom_start;
-        u.seq = (unsigned)k;
-        u.n = (long long)md.sq.sched.index(step0 + k);
-        ta::launch_md_sq(u, s);
-        HIP_CHECK(hipGetLastError());
-      }
-      if (flux_due) {
-        fx.v = a.snap_v;
-        fx.seq = (unsigned)k;
-        fx.n = (long long)md.flux.sched.index(step0 + k);
-        ta::launch_md_flux(fx, h->db, s);
-        HIP_CHECK(hipGetLastError());
-      }
+      md_enqueue(h, md.order, order, step0, k);
+      md_enqueue(h, md.cluster, cluster, step0, k);
+      md_enqueue(h, md.cna, cna, step0, k);
+      md_enqueue(h, md.adf, adf, step0, k);
+      md_enqueue(h, md.rdf, rdf, step0, k);
+      const MdSnapshot snap = md_snapshot(md.corr, md.sq, md.flux, N, step0, k);
+      md_enqueue(h, integrator, threads, step0, k, drift, record_every, snap);
+      md_enqueue(h, md.corr, corr, step0, k, snap);
+      md_enqueue(h, md.sq, sq, step0, k, snap);
+      md_enqueue(h, md.flux, flux, step0, k, snap);
     };
 
     h->jvp_valid = false;
@@ -1356,7 +1405,7 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     resident_steps(h, "ta_md_run", n_steps, want, [&](int q) { integrate(q, true); },
                    [](int, int) { return -1; }, &rebuilds, n_rebuilds);
     integrate(n_steps, false);  // the pending half-kick and the last record
-    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
     h->upload_pending = false;
     md.step = step0 + n_steps;
     // The order in which the samplers' data become valid again is behaviour: corr, rdf, adf, order, sq, flux, then cluster
@@ -1374,41 +1423,7 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     md.cluster.end_run(md.step);
     md.cna.end_run(md.step);
     if (n_rebuilds) *n_rebuilds = rebuilds;
-    if (baro && F) {
-      std::vector<double> rec(4 * n_rec * F);
-      HIP_CHECK(hipMemcpy(rec.data(), md.baro.rec.ptr, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
-      md.baro.rec_volume.resize(n_rec * F);
-      md.baro.rec_press.resize(3 * n_rec * F);
-      for (size_t j = 0; j < n_rec * F; ++j) {
-        md.baro.rec_volume[j] = rec[4 * j];
-        for (int c = 0; c < 3; ++c) md.baro.rec_press[3 * j + c] = rec[4 * j + 1 + c];
-      }
-      resident_final_cells(h, "ta_md_run", want, &rebuilds, n_rebuilds);
-      if (h->relax.cell.on && h->relax.valid &&
-          std::memcmp(cells_at_entry.data(), h->ref_cells.data(), 9 * F * sizeof(double)) != 0) {
-        // the barostat's cells replace the relaxed ones: they are h0 from here on, G = I, the cell velocities 0
-        HIP_CHECK(hipMemcpy(h->relax.cell.h0.ptr, h->ref_cells.data(), 9 * F * sizeof(double), hipMemcpyHostToDevice));
-        h->relax.cell.reset_deformation(F);
-      }
-      md.baro.rec_valid = true;
-    }
-    if (nhc) {
-      md.nhc.rec_host.resize(n_rec * F);
-      if (F) HIP_CHECK(hipMemcpy(md.nhc.rec_host.data(), md.nhc.rec.ptr, n_rec * F * sizeof(double), hipMemcpyDeviceToHost));
-      md.nhc.rec_valid = true;
-    }
-    if (epot && F) HIP_CHECK(hipMemcpy(epot, md.epot.ptr, n_rec * F * sizeof(double), hipMemcpyDeviceToHost));
-    if (ekin && F) {
-      std::vector<double> part(n_rec * n_blk);
-      HIP_CHECK(hipMemcpy(part.data(), md.ke.ptr, part.size() * sizeof(double), hipMemcpyDeviceToHost));
-      const std::vector<int32_t> &start = res.blk_start_host;
-      for (size_t r = 0; r < n_rec; ++r)
-        for (size_t f = 0; f < F; ++f) {
-          double t = 0.0;
-          for (int32_t b = start[f]; b < start[f + 1]; ++b) t += part[r * n_blk + (size_t)b];
-          ekin[r * F + f] = t;
-        }
-    }
+    md_read_records(h, n_rec, want, cells_at_entry, epot, ekin, &rebuilds, n_rebuilds);
   });
   res.cell_running = md.baro.running = false;
   if (h->centre_gradients) {  // the evaluations of other calls take their usual builds again

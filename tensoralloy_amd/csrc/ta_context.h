@@ -139,7 +139,10 @@ struct ResidentLoop {
 // texts, whether it is on, the workgroup layout of its launch for the resident batch (`blk` [F + 1]: the first
 // workgroup of every frame, `chunk` items each), its schedule, and its part in the ta_md_run under way. A feature
 // adds a `Setting set` (the C parameter struct and whatever else allocating for it needs), its buffers and a
-// release() that frees them and ends in release_layout().
+// release() that frees them and ends in release_layout(). Where one buffer holds several arrays, or a ring holds rows,
+// the Setting says how long each is and the struct where each starts (for F frames, E elements, N atoms of the
+// resident batch): the only statement of that layout, which md_alloc, md_launch, the enqueue and the getters of
+// ta_api_md.hip all go through.
 struct MdSampler {
   const MdSamplerText &text;
   bool on = false;
@@ -208,8 +211,14 @@ struct MdState {
     Corr() : MdSampler(md_text::corr) {}
     struct Setting {
       ta_md_sampling_params p = {0, 1};
+      size_t n_sums(size_t F, size_t E) const { return F * E * (size_t)p.n_lags; }  // of v . v; as many of |dx|^2
+      size_t n_acc(size_t F, size_t E) const { return 2 * n_sums(F, E); }
     } set;
     DevBuf<double> ring_x, ring_v, acc, part;
+    double *acc_v() const { return acc.ptr; }
+    double *acc_x(size_t F, size_t E) const { return acc.ptr + set.n_sums(F, E); }
+    // where sample n is held in a ring
+    double *slot(const DevBuf<double> &ring, int64_t n, size_t N) const { return ring.ptr + (size_t)(n % set.p.n_lags) * 3 * N; }
     void release() {  // frees what sampling holds on the device; the setting stays
       release_all(ring_x, ring_v, acc, part);
       release_layout();
@@ -251,11 +260,22 @@ struct MdState {
     struct Setting {
       ta_md_order_params p = {0.0, 0.0, 0, 1, 0, {0, 0, 0, 0}, 0};
       std::vector<double> rb;
+      size_t n_hist(size_t F, size_t E) const { return F * E * (size_t)p.n_degrees * (size_t)p.n_bins; }  // hist_q; hist_qbar
+      static size_t n_hist_conn(size_t F, size_t E) { return F * E * (TA_MD_ORDER_MAX_CONN + 1); }
+      size_t n_acc(size_t F, size_t E) const { return 2 * n_hist(F, E) + n_hist_conn(F, E); }
+      size_t n_q(size_t N) const { return N * (size_t)p.n_degrees; }  // q; qbar
     } set;
     DevBuf<double> rb2, norm, qlm, per_atom;
     DevBuf<int32_t> per_atom_int;
     DevBuf<unsigned long long> acc;
     int n_lm = 0, solid = 0;
+    unsigned long long *hist_q() const { return acc.ptr; }
+    unsigned long long *hist_qbar(size_t F, size_t E) const { return acc.ptr + set.n_hist(F, E); }
+    unsigned long long *hist_conn(size_t F, size_t E) const { return acc.ptr + 2 * set.n_hist(F, E); }
+    double *q() const { return per_atom.ptr; }
+    double *qbar(size_t N) const { return per_atom.ptr + set.n_q(N); }
+    int32_t *n_bonds() const { return per_atom_int.ptr; }
+    int32_t *n_conn(size_t N) const { return per_atom_int.ptr + N; }
     void release() {  // frees what the order parameters hold on the device; the setting stays
       release_all(rb2, norm, qlm, per_atom, per_atom_int, acc);
       release_layout();
@@ -269,12 +289,21 @@ struct MdState {
     struct Setting {
       ta_md_cluster_params p = {0.0, 0, 0, 0, 1, 1};
       std::vector<double> rl;
+      size_t n_hist(size_t F) const { return F * (size_t)p.n_bins; }
+      static size_t row(size_t F) { return F * 4; }  // words of a row of the series
+      size_t n_series(size_t F) const { return (size_t)p.n_series * row(F); }
     } set;
     DevBuf<double> rl2;
     DevBuf<int32_t> per_atom;
     DevBuf<unsigned long long> acc;
     DevBuf<long long> series;
     DevBuf<unsigned> giveup;
+    static size_t n_per_atom(size_t N) { return 4 * N; }
+    int32_t *parent() const { return per_atom.ptr; }
+    int32_t *count(size_t N) const { return per_atom.ptr + N; }
+    int32_t *label(size_t N) const { return per_atom.ptr + 2 * N; }
+    int32_t *size(size_t N) const { return per_atom.ptr + 3 * N; }
+    long long *series_row(int64_t n, size_t F) const { return series.ptr + (size_t)(n % set.p.n_series) * set.row(F); }  // of sample n
     void release() {  // frees what the clusters hold on the device; the setting stays
       release_all(rl2, per_atom, acc, series, giveup);
       release_layout();
@@ -286,10 +315,14 @@ struct MdState {
     Cna() : MdSampler(md_text::cna) {}
     struct Setting {
       ta_md_cna_params p = {0.0, 0.0, 0, 0, 1};
+      static size_t n_acc(size_t F, size_t E) { return F * E * TA_MD_CNA_TYPES; }
+      static size_t row(size_t F) { return F * TA_MD_CNA_TYPES; }  // words of a row of the series
+      size_t n_series(size_t F) const { return (size_t)p.n_series * row(F); }
     } set;
     DevBuf<int32_t> structure;
     DevBuf<double> r_local;
     DevBuf<unsigned long long> acc, series;
+    unsigned long long *series_row(int64_t n, size_t F) const { return series.ptr + (size_t)(n % set.p.n_series) * set.row(F); }  // of sample n
     void release() {  // frees what the analysis holds on the device; the setting stays
       release_all(structure, r_local, acc, series);
       release_layout();
@@ -304,9 +337,17 @@ struct MdState {
     struct Setting {
       ta_md_sq_params p = {0, 1, 1, 0};
       std::vector<int32_t> miller;
+      size_t planes() const { return p.currents ? 8 : 2; }
+      size_t row(size_t F, size_t E) const { return F * E * planes() * (size_t)p.n_q; }  // doubles of a row of the ring
+      size_t n_sums(size_t F, size_t E) const { return F * E * E * (size_t)p.n_lags * (size_t)p.n_q; }  // A_rho; A_L; A_J
+      size_t n_acc(size_t F, size_t E) const { return (p.currents ? 3 : 1) * n_sums(F, E); }
     } set;
     DevBuf<int32_t> miller_dev;
     DevBuf<double> ring, acc, part, snap_x, snap_v;
+    double *acc_rho() const { return acc.ptr; }
+    double *acc_l(size_t F, size_t E) const { return acc.ptr + set.n_sums(F, E); }  // (with currents)
+    double *acc_j(size_t F, size_t E) const { return acc.ptr + 2 * set.n_sums(F, E); }
+    double *ring_row(int64_t n, size_t F, size_t E) const { return ring.ptr + (size_t)(n % set.p.n_lags) * set.row(F, E); }  // of sample n
     void release() {  // frees what the structure factors hold on the device; the setting stays
       release_all(ring, acc, part, snap_x, snap_v, miller_dev);
       release_layout();
@@ -319,8 +360,16 @@ struct MdState {
     Flux() : MdSampler(md_text::flux) {}
     struct Setting {
       ta_md_flux_params p = {0, 1};
+      static size_t row(size_t F) { return F * TA_MD_FLUX_ROW; }  // doubles of a row of the ring, and of the sums
+      size_t n_heat(size_t F) const { return F * (size_t)p.n_lags * 3; }
+      size_t n_press(size_t F) const { return F * (size_t)p.n_lags * 6; }
+      size_t n_acc(size_t F) const { return row(F) + n_heat(F) + n_press(F); }
     } set;
     DevBuf<double> ring, acc, part, snap_x, snap_v;
+    double *sums() const { return acc.ptr; }
+    double *acc_heat(size_t F) const { return acc.ptr + set.row(F); }
+    double *acc_press(size_t F) const { return acc.ptr + set.row(F) + set.n_heat(F); }
+    double *ring_row(int64_t n, size_t F) const { return ring.ptr + (size_t)(n % set.p.n_lags) * set.row(F); }  // of sample n
     void release() {  // frees what the sampler holds on the device; the setting stays
       release_all(ring, acc, part, snap_x, snap_v);
       release_layout();

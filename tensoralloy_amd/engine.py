@@ -259,12 +259,40 @@ class Engine:
         return out
 
     # -- device-resident MD loop -------------------------------------------------------------
+    # what this side keeps of every sampler's setting, by the setter the library's messages name: (attribute, its value
+    # while the sampler is off)
+    _MD_OFF = {"ta_md_set_sampling": ("_md_lags", 0), "ta_md_set_rdf": ("_md_bins", 0), "ta_md_set_adf": ("_md_adf_bins", 0),
+               "ta_md_set_order": ("_md_order_bins", 0), "ta_md_set_clusters": ("_md_cluster", (0, 1)),
+               "ta_md_set_cna": ("_md_cna", 0), "ta_md_set_sq": ("_md_sq", (0, 1, False)),
+               "ta_md_set_flux": ("_md_flux_lags", 0)}
+
+    def _need_batch(self, who):
+        if self.info is None:
+            raise ValueError(f"{who}: no resident batch (call set_frames first)")
+
+    def _md_by_element(self):
+        """Atoms per frame and element of the resident batch, int64 [n_frames, n_elements]."""
+        E = self._n_elements
+        return np.array([np.bincount(fr.species, minlength=E)[:E] for fr in self._frames], dtype=np.int64).reshape(-1, E)
+
+    def _md_pair_cutoffs(self, who, name, r, default):
+        """The cutoff argument `name` = `r` of setter `who`, one distance (None: `default`) or an [n_elements, n_elements]
+        matrix, as the library takes it: (the distance or the matrix's largest, pointer to the matrix or NULL)."""
+        E = self._n_elements
+        if r is None:
+            r = default
+        if np.ndim(r) == 0:
+            return float(r), C.POINTER(C.c_double)()
+        m = np.ascontiguousarray(r, dtype=np.float64)
+        if m.shape != (E, E):
+            raise ValueError(f"{who}: {name} must be one distance or [{E}, {E}] (n_elements of the model)")
+        return float(m.max()), _lib.as_dp(m)
+
     def md_init(self, masses=None, velocities=None):
         """Masses (amu; default: `atoms.atomic_masses` by atomic number) and velocities
         (A / (A sqrt(amu / eV)), ASE's unit; default 0) of every atom of the resident batch, for
         `md_run` (`ta_md_init`). `set_frames` drops them; `update_positions` / `step` keep them."""
-        if self.info is None:
-            raise ValueError("md_init: no resident batch (call set_frames first)")
+        self._need_batch("md_init")
         N = int(self.info.n_atoms)
         if masses is None:
             from .atoms import atomic_masses
@@ -281,22 +309,9 @@ class Engine:
         rc = self._lib.ta_md_init(self._handle, _lib.as_dp(m), vptr)
         if rc == _lib.TA_ERR_NOMEM:   # no room for what a setting needs: the library switched that setting off
             msg = self._lib.ta_last_error(self._handle) or b""
-            if b"ta_md_set_rdf" in msg:
-                self._md_bins = 0
-            if b"ta_md_set_adf" in msg:
-                self._md_adf_bins = 0
-            if b"ta_md_set_order" in msg:
-                self._md_order_bins = 0
-            if b"ta_md_set_clusters" in msg:
-                self._md_cluster = (0, 1)
-            if b"ta_md_set_cna" in msg:
-                self._md_cna = 0
-            if b"ta_md_set_sampling" in msg:
-                self._md_lags = 0
-            if b"ta_md_set_sq" in msg:
-                self._md_sq = (0, 1, False)
-            if b"ta_md_set_flux" in msg:
-                self._md_flux_lags = 0
+            for setter, (attr, off) in self._MD_OFF.items():
+                if setter.encode() in msg:
+                    setattr(self, attr, off)
         elif rc == _lib.TA_ERR_INVALID and b"ta_md_set_sq" in (self._lib.ta_last_error(self._handle) or b""):
             self._md_sq = (0, 1, False)   # (a batch without wave vectors: the library switched the feature off)
         self._check(rc)
@@ -332,8 +347,7 @@ class Engine:
         self._md_lags = int(n_lags)
 
     def _md_corr_shape(self, who):
-        if self.info is None:
-            raise ValueError(f"{who}: no resident batch (call set_frames first)")
+        self._need_batch(who)
         return int(self.info.n_frames), self._n_elements, max(self._md_lags, 1)
 
     def md_correlations(self):
@@ -350,9 +364,7 @@ class Engine:
         self._check(self._lib.ta_md_get_correlations(self._handle, _lib.as_dp(vs), _lib.as_dp(xs), info))
         n_samples = int(info[0])
         n_origins = np.maximum(0, n_samples - np.arange(L)).astype(np.int64)
-        counts = np.zeros((F, E), dtype=np.int64)
-        for f, fr in enumerate(self._frames):
-            counts[f] = np.bincount(fr.species, minlength=E)[:E]
+        counts = self._md_by_element()
         den = (counts[:, :, None] * n_origins[None, None, :]).astype(np.float64)
         with np.errstate(divide="ignore", invalid="ignore"):
             vacf = np.where(den > 0, vs / den, np.nan)
@@ -410,17 +422,14 @@ class Engine:
         `n_samples`, `r_max`, `sample_every`, `last_step` (absolute step of the newest sample, -1: none);
         `n_by_element` [n_frames, n_elements] atoms per frame and element, `volumes` [n_frames] and `pbc`
         [n_frames, 3] of the resident frames: what `md.rdf` normalises the counts with."""
-        if self.info is None:
-            raise ValueError("md_rdf: no resident batch (call set_frames first)")
+        self._need_batch("md_rdf")
         F, E, B = int(self.info.n_frames), self._n_elements, max(self._md_bins, 1)
         counts = np.zeros((F, E, E, B), dtype=np.int64)
         info = (C.c_int64 * 4)()
         r_max = C.c_double(0.0)
         self._check(self._lib.ta_md_get_rdf(self._handle, counts.ctypes.data_as(C.POINTER(C.c_int64)), info,
                                             C.byref(r_max)))
-        n_by_element = np.zeros((F, E), dtype=np.int64)
-        for f, fr in enumerate(self._frames):
-            n_by_element[f] = np.bincount(fr.species, minlength=E)[:E]
+        n_by_element = self._md_by_element()
         return {"counts": counts, "n_samples": int(info[0]), "r_max": float(r_max.value),
                 "sample_every": int(info[2]), "last_step": int(info[3]), "n_by_element": n_by_element,
                 "volumes": self._volumes.copy(), "pbc": np.array([fr.pbc != 0 for fr in self._frames]).reshape(F, 3)}
@@ -435,17 +444,7 @@ class Engine:
         is also the largest value allowed. `n_bins` = 0 switches it off (the default) and frees them. Needs
         `md_init`; every call starts from zero counts, as `md_init` does. The setting stays on across
         `set_frames`. Independent of `md_set_sampling` and `md_set_rdf`; runs under the barostat too."""
-        E = self._n_elements
-        pairs = C.POINTER(C.c_double)()
-        if r_bond is None:
-            r_bond = self._md_cutoff
-        if np.ndim(r_bond) == 0:
-            scalar = float(r_bond)
-        else:
-            rb = np.ascontiguousarray(r_bond, dtype=np.float64)
-            if rb.shape != (E, E):
-                raise ValueError(f"md_set_adf: r_bond must be one distance or [{E}, {E}] (n_elements of the model)")
-            pairs, scalar = _lib.as_dp(rb), float(rb.max())
+        scalar, pairs = self._md_pair_cutoffs("md_set_adf", "r_bond", r_bond, self._md_cutoff)
         p = _lib.MdAdfParams(scalar, int(n_bins), int(sample_every))
         rc = self._lib.ta_md_set_adf(self._handle, C.byref(p), pairs)
         if rc == _lib.TA_ERR_NOMEM:   # (no room for the counts: the library switched the feature off)
@@ -465,8 +464,7 @@ class Engine:
         summed over the samples; `pairs`: the P = n_elements (n_elements + 1) / 2 tuples (b, c) in the order of p;
         `r_bond` [n_elements, n_elements]: the cutoffs in use; `n_samples`, `n_bins`, `sample_every`, `last_step`
         (absolute step of the newest sample, -1: none). `md.adf` normalises the counts."""
-        if self.info is None:
-            raise ValueError("md_adf: no resident batch (call set_frames first)")
+        self._need_batch("md_adf")
         F, E, B = int(self.info.n_frames), self._n_elements, max(self._md_adf_bins, 1)
         pairs = [(b, c) for b in range(E) for c in range(b, E)]
         counts = np.zeros((F, E, len(pairs), B), dtype=np.int64)
@@ -492,17 +490,7 @@ class Engine:
         `set_frames`. Independent of `md_set_sampling`, `md_set_rdf` and `md_set_adf`; runs under the barostat too.
         `md_run(0, dt)` samples the resident state once: `md_init`, `md_set_order`, `md_run(0, dt)` analyses a
         static structure."""
-        E = self._n_elements
-        pairs = C.POINTER(C.c_double)()
-        if r_bond is None:
-            r_bond = self._md_cutoff
-        if np.ndim(r_bond) == 0:
-            scalar = float(r_bond)
-        else:
-            rb = np.ascontiguousarray(r_bond, dtype=np.float64)
-            if rb.shape != (E, E):
-                raise ValueError(f"md_set_order: r_bond must be one distance or [{E}, {E}] (n_elements of the model)")
-            pairs, scalar = _lib.as_dp(rb), float(rb.max())
+        scalar, pairs = self._md_pair_cutoffs("md_set_order", "r_bond", r_bond, self._md_cutoff)
         degrees = [int(l) for l in np.atleast_1d(degrees)]
         solid_degree, threshold = solid
         p = _lib.MdOrderParams(scalar, float(threshold), int(n_bins), int(sample_every), len(degrees),   # (the library
@@ -529,8 +517,7 @@ class Engine:
         `n_samples`, `n_bins`, `sample_every`, `last_step` (absolute step of the newest sample, -1: none);
         `n_by_element` [n_frames, n_elements] atoms per frame and element. `md.order_distribution` and
         `md.solid_fraction` normalise the counts."""
-        if self.info is None:
-            raise ValueError("md_order: no resident batch (call set_frames first)")
+        self._need_batch("md_order")
         F, E, B = int(self.info.n_frames), self._n_elements, max(self._md_order_bins, 1)
         D = max(len(self._md_order_degrees), 1)
         hist_q, hist_qbar = np.zeros((F, E, D, B), dtype=np.int64), np.zeros((F, E, D, B), dtype=np.int64)
@@ -540,9 +527,7 @@ class Engine:
         ip = C.POINTER(C.c_int64)
         self._check(self._lib.ta_md_get_order(self._handle, hist_q.ctypes.data_as(ip), hist_qbar.ctypes.data_as(ip),
                                               hist_conn.ctypes.data_as(ip), info, _lib.as_dp(r_bond)))
-        n_by_element = np.zeros((F, E), dtype=np.int64)
-        for f, fr in enumerate(self._frames):
-            n_by_element[f] = np.bincount(fr.species, minlength=E)[:E]
+        n_by_element = self._md_by_element()
         return {"hist_q": hist_q, "hist_qbar": hist_qbar, "hist_conn": hist_conn, "degrees": self._md_order_degrees,
                 "solid": self._md_order_solid, "r_bond": r_bond, "n_samples": int(info[0]), "n_bins": int(info[1]),
                 "sample_every": int(info[2]), "last_step": int(info[3]), "n_by_element": n_by_element}
@@ -553,8 +538,7 @@ class Engine:
         bonds among them; `qlm` complex [n_atoms, sum (l + 1)]: q_lm degree by degree in the order of `degrees`,
         m = 0 .. l; `step`: the absolute step of that state. Costs a host sync and no list rebuild. Refused until
         the first sample has been taken."""
-        if self.info is None:
-            raise ValueError("md_order_atoms: no resident batch (call set_frames first)")
+        self._need_batch("md_order_atoms")
         N, D = int(self.info.n_atoms), max(len(self._md_order_degrees), 1)
         M = max(sum(l + 1 for l in self._md_order_degrees), 1)
         q, qbar, qlm = np.zeros((N, D)), np.zeros((N, D)), np.zeros((N, M, 2))
@@ -584,16 +568,8 @@ class Engine:
         `md_init` does. The setting stays on across `set_frames`. Runs under the barostat and every thermostat.
         `md_run(0, dt)` samples the resident state once."""
         E = self._n_elements
-        pairs = C.POINTER(C.c_double)()
-        if r_link is None:
-            scalar = float("nan")   # (the library takes the model's cutoff)
-        elif np.ndim(r_link) == 0:
-            scalar = float(r_link)
-        else:
-            rl = np.ascontiguousarray(r_link, dtype=np.float64)
-            if rl.shape != (E, E):
-                raise ValueError(f"md_set_clusters: r_link must be one distance or [{E}, {E}] (n_elements of the model)")
-            pairs, scalar = _lib.as_dp(rl), float(rl.max())
+        # (for NaN the library takes the model's cutoff)
+        scalar, pairs = self._md_pair_cutoffs("md_set_clusters", "r_link", r_link, float("nan"))
         if species is None:
             mask = (1 << E) - 1
         else:
@@ -626,8 +602,7 @@ class Engine:
         their absolute steps; `n_samples`, `n_bins`, `sample_every`, `last_step` (absolute step of the newest sample,
         -1: none), `rows`, `n_series`; `r_link` [n_elements, n_elements]: the cutoffs in use.
         `md.largest_cluster` and `md.cluster_size_distribution` read them."""
-        if self.info is None:
-            raise ValueError("md_clusters: no resident batch (call set_frames first)")
+        self._need_batch("md_clusters")
         F, E = int(self.info.n_frames), self._n_elements
         B, T = max(self._md_cluster[0], 1), max(self._md_cluster[1], 1)
         ip = C.POINTER(C.c_int64)
@@ -648,8 +623,7 @@ class Engine:
         [n_atoms], the smallest index of the atom's cluster in the batch, -1 for an atom that is not selected;
         `size` int32 [n_atoms], the atoms of that cluster, 0 likewise; `step`: the absolute step of that state. Costs
         a host sync and no list rebuild. Refused until the first sample has been taken."""
-        if self.info is None:
-            raise ValueError("md_cluster_atoms: no resident batch (call set_frames first)")
+        self._need_batch("md_cluster_atoms")
         N = int(self.info.n_atoms)
         label, size = np.zeros(N, dtype=np.int32), np.zeros(N, dtype=np.int32)
         info = (C.c_int64 * 6)()
@@ -698,8 +672,7 @@ class Engine:
         oldest first, and `steps` int64 [rows], their absolute steps; `n_samples`, `mode` ("adaptive" or "fixed"),
         `sample_every`, `last_step` (absolute step of the newest sample, -1: none), `rows`, `n_series`.
         `md.structure_fractions` normalises counts or series."""
-        if self.info is None:
-            raise ValueError("md_cna: no resident batch (call set_frames first)")
+        self._need_batch("md_cna")
         F, E, K = int(self.info.n_frames), self._n_elements, _lib.TA_MD_CNA_TYPES
         ip = C.POINTER(C.c_int64)
         info = (C.c_int64 * 6)()
@@ -718,8 +691,7 @@ class Engine:
         [n_atoms] (0 other, 1 fcc, 2 hcp, 3 bcc, 4 ico); `r_local` [n_atoms], the bond cutoff of the attempt that
         decided (adaptive mode; 0 with fewer than 12 candidates) or `r_cut` (fixed mode); `step`: the absolute step of
         that state. Costs a host sync and no list rebuild. Refused until the first sample has been taken."""
-        if self.info is None:
-            raise ValueError("md_cna_atoms: no resident batch (call set_frames first)")
+        self._need_batch("md_cna_atoms")
         N = int(self.info.n_atoms)
         structure, r_local = np.zeros(N, dtype=np.int32), np.zeros(N, dtype=np.float64)
         info = (C.c_int64 * 6)()
@@ -776,8 +748,7 @@ class Engine:
         `n_samples`, `n_lags`, `sample_every`, `last_step` (absolute step of the newest sample, -1: none),
         `currents`, `chunk` (atoms per workgroup of the amplitude launch). `md.intermediate_scattering` and
         `md.structure_factor` normalise the sums."""
-        if self.info is None:
-            raise ValueError("md_sq: no resident batch (call set_frames first)")
+        self._need_batch("md_sq")
         F, E = int(self.info.n_frames), self._n_elements
         Q, L, cur = max(self._md_sq[0], 1), self._md_sq[1], self._md_sq[2]
         a_rho = np.zeros((F, E, E, L, Q))
@@ -788,9 +759,7 @@ class Engine:
         self._check(self._lib.ta_md_get_sq(self._handle, _lib.as_dp(a_rho), _lib.as_dp(a_l) if cur else null,
                                            _lib.as_dp(a_j) if cur else null, info,
                                            miller.ctypes.data_as(C.POINTER(C.c_int32))))
-        n_by_element = np.zeros((F, E), dtype=np.int64)
-        for f, fr in enumerate(self._frames):
-            n_by_element[f] = np.bincount(fr.species, minlength=E)[:E]
+        n_by_element = self._md_by_element()
         q = 2.0 * np.pi * np.einsum("fjc,qc->fqj", np.linalg.inv(self.md_cells()), miller.astype(np.float64))
         n_samples = int(info[0])
         return {"a_rho": a_rho, "a_l": a_l, "a_j": a_j, "miller": miller, "q": q, "q_norm": np.linalg.norm(q, axis=-1),
@@ -802,8 +771,7 @@ class Engine:
         """The last `n` amplitude rows the ring holds, oldest first (`ta_md_get_sq_amplitudes`; default: all,
         min(n_samples, n_lags)): a dict `rho` complex [n, n_frames, n_elements, n_q], `cur` complex
         [n, n_frames, n_elements, n_q, 3] (None without currents) and `steps` [n] (absolute steps)."""
-        if self.info is None:
-            raise ValueError("md_sq_amplitudes: no resident batch (call set_frames first)")
+        self._need_batch("md_sq_amplitudes")
         null = C.POINTER(C.c_double)()
         if n is None:
             info = (C.c_int64 * 8)()
@@ -853,8 +821,7 @@ class Engine:
         return self._md_flux_lags
 
     def _md_flux_info(self, who):
-        if self.info is None:
-            raise ValueError(f"{who}: no resident batch (call set_frames first)")
+        self._need_batch(who)
         info = (C.c_int64 * 8)()
         null = C.POINTER(C.c_double)()
         self._check(self._lib.ta_md_get_flux(self._handle, null, null, null, info))
@@ -902,8 +869,7 @@ class Engine:
         """(xi, eta) [n_atoms, 3]: the standard normals the Langevin step with absolute index `step` (steps
         integrated since `md_init`) draws under the seed of `md_set_langevin`, made by the device function
         the integrator calls (`ta_md_noise`). Needs `md_init`."""
-        if self.info is None:
-            raise ValueError("md_noise: no resident batch (call set_frames first)")
+        self._need_batch("md_noise")
         step = int(step)
         if not -2 ** 63 <= step < 2 ** 63:
             raise ValueError("md_noise: the step must fit a signed 64-bit integer")
@@ -941,8 +907,7 @@ class Engine:
     def md_chain(self):
         """(eta, veta) [n_frames, chain]: positions and velocities of every frame's thermostat chain as the
         device holds them (`ta_md_get_chain`). Needs `md_init` and `md_set_nose_hoover`."""
-        if self.info is None:
-            raise ValueError("md_chain: no resident batch (call set_frames first)")
+        self._need_batch("md_chain")
         shape = (int(self.info.n_frames), max(self._md_chain, 1))
         eta, veta = np.empty(shape), np.empty(shape)
         self._check(self._lib.ta_md_get_chain(self._handle, _lib.as_dp(eta), _lib.as_dp(veta)))
@@ -951,8 +916,7 @@ class Engine:
     def md_set_chain(self, eta=None, veta=None):
         """Restart: hand the chains the (eta, veta) [n_frames, chain] of an earlier `md_chain` (None = zeros),
         after `set_frames` + `md_init` with the positions and velocities of that moment (`ta_md_set_chain`)."""
-        if self.info is None:
-            raise ValueError("md_set_chain: no resident batch (call set_frames first)")
+        self._need_batch("md_set_chain")
         n = int(self.info.n_frames) * max(self._md_chain, 1)
         arrays = []
         for name, a in (("eta", eta), ("veta", veta)):
@@ -966,8 +930,7 @@ class Engine:
 
     def md_cells(self):
         """Cells [n_frames, 3, 3] of the resident batch as the library holds them (`ta_md_get_cell`)."""
-        if self.info is None:
-            raise ValueError("md_cells: no resident batch (call set_frames first)")
+        self._need_batch("md_cells")
         cells = np.empty((int(self.info.n_frames), 3, 3))
         self._check(self._lib.ta_md_get_cell(self._handle, _lib.as_dp(cells)))
         return cells
@@ -975,8 +938,7 @@ class Engine:
     def md_records(self, n_rec: int):
         """(volume [n_rec, n_frames], press [n_rec, n_frames, 3]) of the last `md_run` under the barostat
         (`ta_md_get_records`); `n_rec` = that run's n_steps // record_every + 1."""
-        if self.info is None:
-            raise ValueError("md_records: no resident batch (call set_frames first)")
+        self._need_batch("md_records")
         F = int(self.info.n_frames)
         volume, press = np.empty((int(n_rec), F)), np.empty((int(n_rec), F, 3))
         self._check(self._lib.ta_md_get_records(self._handle, _lib.as_dp(volume), _lib.as_dp(press)))
@@ -993,8 +955,7 @@ class Engine:
         With `md_set_nose_hoover` on, the dict also holds `echain` [n_rec, n_frames], every record after the
         first is the state after the closing half-update of its step, and `epot + ekin + echain` is the
         conserved quantity."""
-        if self.info is None:
-            raise ValueError("md_run: no resident batch (call set_frames first)")
+        self._need_batch("md_run")
         n_steps, record_every = int(n_steps), int(record_every)
         if n_steps < 0 or record_every < 1:
             raise ValueError("md_run: n_steps >= 0 and record_every >= 1 are needed")
@@ -1024,8 +985,7 @@ class Engine:
 
     def md_state(self):
         """(positions, velocities) [n_atoms, 3] of the resident batch as the device holds them."""
-        if self.info is None:
-            raise ValueError("md_state: no resident batch (call set_frames first)")
+        self._need_batch("md_state")
         N = int(self.info.n_atoms)
         x, v = np.empty((N, 3)), np.empty((N, 3))
         self._check(self._lib.ta_md_get_state(self._handle, _lib.as_dp(x), _lib.as_dp(v)))
@@ -1037,8 +997,7 @@ class Engine:
         a = astart. `fixed`: boolean mask [n_atoms] or indices of atoms that do not move and do not count
         towards convergence. `params`: dt, dtmax, maxstep, finc, fdec, astart, fa, nmin (ASE's FIRE defaults).
         `set_frames` drops the state; `update_positions` / `step` keep it."""
-        if self.info is None:
-            raise ValueError("relax_init: no resident batch (call set_frames first)")
+        self._need_batch("relax_init")
         p = dict(dt=0.1, dtmax=1.0, maxstep=0.2, finc=1.1, fdec=0.5, astart=0.1, fa=0.99, nmin=5)
         unknown = sorted(set(params) - set(p))
         if unknown:
@@ -1064,8 +1023,7 @@ class Engine:
         xz, xy) or a symmetric 3 x 3 array, non-zero = free (None: all free); `hydrostatic`: only the volume
         changes. `on=False` returns to fixed cells and keeps the current ones. Needs `relax_init`, which
         switches the option off again."""
-        if self.info is None:
-            raise ValueError("relax_set_cell: no resident batch (call set_frames first)")
+        self._need_batch("relax_set_cell")
         if not on:
             self._check(self._lib.ta_relax_set_cell(self._handle, 0, None))
             self._relax_cell = False
@@ -1090,8 +1048,7 @@ class Engine:
         """cells (= h0 G^T), deform (G), cell_velocities [n_frames, 3, 3] and cell_fmax [n_frames] (largest row
         of the generalised cell force at the last state a cell run tested) of the relaxation
         (`ta_relax_get_cell`)."""
-        if self.info is None:
-            raise ValueError("relax_cell_state: no resident batch (call set_frames first)")
+        self._need_batch("relax_cell_state")
         F = int(self.info.n_frames)
         cells, G, v, fm = np.empty((F, 3, 3)), np.empty((F, 3, 3)), np.empty((F, 3, 3)), np.empty(F)
         self._check(self._lib.ta_relax_get_cell(self._handle, _lib.as_dp(cells), _lib.as_dp(G), _lib.as_dp(v),
@@ -1106,8 +1063,7 @@ class Engine:
         `on` restarts the optimiser (v = 0, dt, a); `on=False` returns to independent frames and resets their
         FIRE states the same way, also when the band was not on. Needs
         `relax_init`, which supplies the FIRE parameters and the fixed mask and switches the option off again."""
-        if self.info is None:
-            raise ValueError("relax_set_band: no resident batch (call set_frames first)")
+        self._need_batch("relax_set_band")
         if not on:
             self._check(self._lib.ta_relax_set_band(self._handle, 0, None))
             return
@@ -1117,8 +1073,7 @@ class Engine:
     def relax_band_state(self) -> dict:
         """forces (the band forces B) and tangents [n_atoms, 3], energies [n_frames] and climbing (image index,
         -1 without climb) of the state the last band run ended on (`ta_relax_get_band`)."""
-        if self.info is None:
-            raise ValueError("relax_band_state: no resident batch (call set_frames first)")
+        self._need_batch("relax_band_state")
         N, F = int(self.info.n_atoms), int(self.info.n_frames)
         b, t, e = np.empty((N, 3)), np.empty((N, 3)), np.empty(F)
         c = C.c_int32(-1)
@@ -1131,8 +1086,7 @@ class Engine:
         last run left. Returns per frame `steps` (taken in this run), `converged`, `fmax` (of the final state)
         and `energy`, and `n_rebuilds`. Afterwards `fetch(want | ENERGY | FORCES)` hands out the results of
         the final state."""
-        if self.info is None:
-            raise ValueError("relax_run: no resident batch (call set_frames first)")
+        self._need_batch("relax_run")
         max_steps = int(max_steps)
         if max_steps < 0:
             raise ValueError("relax_run: max_steps must be >= 0")
@@ -1165,8 +1119,7 @@ class Engine:
 
     def relax_state(self) -> dict:
         """positions, velocities [n_atoms, 3] and dt, a, npos [n_frames] of the relaxation as the device holds them."""
-        if self.info is None:
-            raise ValueError("relax_state: no resident batch (call set_frames first)")
+        self._need_batch("relax_state")
         N, F = int(self.info.n_atoms), int(self.info.n_frames)
         x, v = np.empty((N, 3)), np.empty((N, 3))
         dt, a, npos = np.empty(F), np.empty(F), np.zeros(F, dtype=np.int32)

@@ -14,7 +14,10 @@ Protocol (a few seconds): two fcc Ni frames of different size, a skin small enou
 runs, different `sample_every` (1, 2, 3, 2, 4, 3, 2), clusters with n_min > 0 (they read the order launches' n_conn),
 S(q) with currents (its snapshot is the correlation ring's on common steps, its own on the others); runs of 7 and 6
 steps, then `set_frames` with the frames swapped, `md_init` (every sampler is allocated again from its stored setting)
-and a run of 6 steps. Every getter is read after each of the three stages."""
+and a run of 6 steps. Every getter is read after each of the three stages.
+
+The last test is about the place the integrator writes a sampled state to (the correlation ring, the rows of
+`md_set_sq`, the rows of `md_set_flux`): one run that takes all three while all three readers are on."""
 import functools
 
 import numpy as np
@@ -172,3 +175,75 @@ def test_switching_one_off_leaves_the_others():
         print("after", name, "went off, differing outputs:", bad)
         assert not bad, (name, bad)
     assert after_off[-1][1] == {}
+
+
+# -- the three places the integrator writes a sampled state to, all taken in one run ------------------------------------
+# With sample_every = 1 of md_set_sampling (above) every sampled state goes to the correlation ring. Here the ring takes
+# the steps t % 4 == 0, the rows of md_set_sq those with t % 4 == 2 and the rows of md_set_flux the odd ones, while all
+# three readers of the snapshot are on. md_set_flux is on in every run compared: it switches the builds of the
+# evaluation, and with them the trajectory's rounding.
+ROUTES = {
+    "sampling": dict(n_lags=3, sample_every=4),
+    "sq": dict(miller=MILLER, n_lags=3, sample_every=2, currents=True),
+    "flux": dict(n_lags=3, sample_every=1),
+}
+ROUTE_GETTERS = {"sampling": ("md_correlations", "md_samples"), "sq": ("md_sq", "md_sq_amplitudes"),
+                 "flux": ("md_flux", "md_flux_rows")}
+
+
+def _routes_protocol(on):
+    """Runs of 7 and 6 steps with the samplers `on` at the settings of ROUTES: per run the trajectory's end and records
+    and every getter's output."""
+    from tensoralloy_amd import Engine
+    nn, frames, v = _setup()
+    stages = []
+    with Engine(nn) as eng:
+        eng.set_skin(SKIN)
+        eng.set_frames(list(frames))
+        eng.md_init(None, np.concatenate(v))
+        for name in on:
+            getattr(eng, "md_set_" + name)(**ROUTES[name])
+        for n in RUNS:
+            out = eng.md_run(n, DT)
+            x, vel = eng.md_state()
+            stages.append(dict(x=x, v=vel, epot=out["epot"], n_rebuilds=out["n_rebuilds"],
+                               got={g: getattr(eng, g)() for name in on for g in ROUTE_GETTERS[name]}))
+    return stages
+
+
+def _same_bits(a, b):
+    """np.array_equal; the normalised sums of a lag that has no time origin yet are NaN on both sides, which counts as
+    equal."""
+    if isinstance(a, np.ndarray) and isinstance(b, np.ndarray) and a.dtype == b.dtype and a.dtype.kind in "fc":
+        return np.array_equal(a, b, equal_nan=True)
+    return _same(a, b)
+
+
+def test_all_three_snapshot_routes_in_one_run():
+    """One trajectory of 13 steps in which the correlation ring (t % 4 == 0), the rows of md_set_sq (t % 4 == 2) and the
+    rows of md_set_flux (odd t) each take the integrator's snapshot, with all three readers on: every output of the six
+    getters equals, bit for bit, that of the same protocol with only that sampler and md_set_flux on, where the
+    snapshots take other routes (S(q) alone: its own rows at every sample; flux alone: its own rows always)."""
+    together = _routes_protocol(tuple(ROUTES))
+    print("n_rebuilds per run", [s["n_rebuilds"] for s in together])
+    assert 0 < together[1]["n_rebuilds"] < RUNS[1]
+    ends = [RUNS[0], RUNS[0] + RUNS[1]]
+    for stage, end in zip(together, ends):
+        for name, (head, ring) in ROUTE_GETTERS.items():
+            every, steps = ROUTES[name]["sample_every"], list(range(0, end + 1, ROUTES[name]["sample_every"]))
+            got = stage["got"][head]
+            assert (got["n_samples"], got["sample_every"], got["last_step"]) == (len(steps), every, steps[-1]), (name, end)
+            assert stage["got"][ring]["steps"].tolist() == steps[-ROUTES[name]["n_lags"]:], (name, end)
+    # all three routes are taken, each by more than one launch
+    taken = {route: [t for t in range(ends[-1] + 1) if cond(t)] for route, cond in
+             (("ring", lambda t: t % 4 == 0), ("sq rows", lambda t: t % 4 == 2), ("flux rows", lambda t: t % 2 == 1))}
+    assert all(len(ts) > 1 for ts in taken.values()), taken
+    for name in ROUTES:
+        alone = _routes_protocol((name,) if name == "flux" else (name, "flux"))
+        for j, (t, a) in enumerate(zip(together, alone)):
+            assert all(np.array_equal(t[k], a[k]) for k in ("x", "v", "epot")) and t["n_rebuilds"] == a["n_rebuilds"], (name, j)
+            for g in ROUTE_GETTERS[name]:
+                assert t["got"][g].keys() == a["got"][g].keys(), g
+                bad = [k for k in t["got"][g] if not _same_bits(t["got"][g][k], a["got"][g][k])]
+                print("run", j, g, "differing outputs:", bad)
+                assert not bad, (j, g, bad)
