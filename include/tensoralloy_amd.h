@@ -1356,6 +1356,64 @@ int ta_get_list(ta_handle h, int32_t which, int32_t *pair_start /*[N+1]*/, int32
                 int32_t *seg_start /*[N*(nel+1)+1]*/, int32_t *pair_i, int32_t *pair_j,
                 int32_t *pair_shift /*[n_slots][3]*/, int32_t *pair_rev, int32_t *blk_center /*[n_blk+1]*/);
 
+/* Harmonic phonons (replaces the phonopy step behind analysis/phonon.py: dynamical matrices, frequencies,
+ * normal modes and the density of states from the force constants of a supercell). Everything is fp64, there
+ * are no floating-point atomics and every sum has a fixed order: the same inputs give the same bits, however the
+ * q-points are chunked. Complex arrays are interleaved (re, im) doubles.
+ *   TA_PHONON_MAX_ORDER   the eigensolver's largest matrix: 3 n_basis <= 48, that is 16 atoms in the home cell
+ *                         (with eigenvectors one such matrix takes 75 KB of a workgroup's LDS).
+ *   TA_PHONON_THZ         nu [THz] = sign(l) sqrt(|l|) TA_PHONON_THZ for an eigenvalue l in eV / A^2 / amu:
+ *                         1000 fs / (2 pi) with fs = one femtosecond in A sqrt(amu / eV). Imaginary modes
+ *                         come out negative.
+ *   ta_phonon_set_cell    declares the ONE resident frame (N atoms) a supercell whose first n_basis atoms are
+ *                         the home cell. basis_of [N]: the home atom each atom is an image of (basis_of[b] = b
+ *                         for b < n_basis); mass [n_basis] amu, > 0; start [n_basis N + 1], vec [start[last]][3]:
+ *                         for the pair (b, s) at b N + s the shortest vectors (A) from home atom b to the
+ *                         periodic images of atom s under the supercell lattice, each weighted 1 / their number
+ *                         (phonopy's convention). q_chunk: q-points per internal pass, rounded up to a multiple
+ *                         of 64; 0 = chosen to keep the work space near 128 MB. Drops force constants set
+ *                         before. TA_ERR_INVALID: no or more than one resident frame, n_basis outside
+ *                         1 .. min(N, TA_PHONON_MAX_ORDER / 3), a basis_of outside the home cell, a mass that is
+ *                         not finite and > 0, start[0] != 0 or start not monotone. ta_set_frames drops the state.
+ *   ta_phonon_force_constants   Phi[b][s][a][c] = d2E / d x_ba d x_sc = -dF of ta_hessian_vectors for the unit
+ *                         displacements 0 .. 3 n_basis - 1, kept on the device; phi [n_basis][N][3][3] (may be
+ *                         NULL) receives a copy. Fails as ta_hessian_vectors does for models without the
+ *                         analytic path.
+ *   ta_phonon_load_force_constants   the same slot from the host (finite differences, a file).
+ *   ta_phonon_frequencies q_cart [Q][3] Cartesian wave vectors in 1 / A (2 pi included). Builds
+ *                             D[q][3b+a][3b'+c] = (m_b m_b')^(-1/2) sum_{s in b'} Phi_ac(b, s) (1/mult) sum_r exp(i q.r)
+ *                         and solves its Hermitian part (D + D^H) / 2. freq [Q][n] THz ascending (n = 3 n_basis);
+ *                         eigvec [Q][n][n] complex or NULL, row m = the unit eigenvector of mode m;
+ *                         info[0] = matrices the solver did not converge (0 in a sound run; never silent).
+ *   ta_phonon_dos         histogram of the same frequencies, which never leave the device: bin
+ *                         k = floor((nu - nu_min) * inv_dnu) with inv_dnu = n_bins / (nu_max - nu_min) formed
+ *                         in double by the library; total [n_bins] counts of modes; partial
+ *                         [n_basis][n_bins] (may be NULL) the modes' weights sum_a |e_ba|^2 per home atom;
+ *                         info[0] as above, info[1] = modes outside [nu_min, nu_max), which are counted nowhere
+ *                         else. n_bins 1 .. TA_MD_MAX_BINS, nu_max > nu_min, both finite.
+ *   ta_phonon_eigh        the eigensolver alone, on `batch` caller matrices A [batch][n][n] complex (row-major;
+ *                         the Hermitian part is solved): w [batch][n] ascending, V [batch][n][n] as eigvec or NULL,
+ *                         info[0] unconverged matrices. Cyclic Jacobi in a parallel ordering until the
+ *                         off-diagonal norm is <= n eps ||A||_F. Needs no resident batch. n above
+ *                         TA_PHONON_MAX_ORDER: TA_ERR_UNSUPPORTED.
+ *   ta_phonon_eigh_group  matrices of order n one workgroup of the solver takes (for tests of its edges). */
+#define TA_PHONON_MAX_ORDER 48
+#define TA_PHONON_THZ (1000.0 * 0.09822694788464063 / (2.0 * 3.141592653589793))
+typedef struct ta_phonon_params {
+  int32_t n_basis;
+  int32_t q_chunk;
+} ta_phonon_params;
+int ta_phonon_set_cell(ta_handle h, const ta_phonon_params *p, const int32_t *basis_of, const double *mass,
+                       const int32_t *start, const double *vec);
+int ta_phonon_force_constants(ta_handle h, double *phi);
+int ta_phonon_load_force_constants(ta_handle h, const double *phi);
+int ta_phonon_frequencies(ta_handle h, int64_t Q, const double *q_cart, double *freq_THz, double *eigvec,
+                          int64_t *info /*[1]*/);
+int ta_phonon_dos(ta_handle h, int64_t Q, const double *q_cart, int32_t n_bins, double nu_min, double nu_max,
+                  uint64_t *total, double *partial, int64_t *info /*[2]*/);
+int ta_phonon_eigh(ta_handle h, int32_t n, int64_t batch, const double *A, double *w, double *V, int64_t *info /*[1]*/);
+int ta_phonon_eigh_group(int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,10 +19,10 @@ CSRC_DIR = PKG_DIR / "csrc"
 INCLUDE_DIR = REPO_DIR / "include"
 LIB_PATH = PKG_DIR / "libtensoralloy_amd.so"
 
-SOURCES = ["ta_api.hip", "ta_api_train.hip", "ta_api_md.hip", "ta_api_relax.hip", "ta_resident.hip", "ta_kernels.hip", "ta_kernels_v2.hip", "ta_mlp.hip", "ta_eam.hip",
+SOURCES = ["ta_api.hip", "ta_api_train.hip", "ta_api_md.hip", "ta_api_relax.hip", "ta_api_phonon.hip", "ta_resident.hip", "ta_kernels.hip", "ta_kernels_v2.hip", "ta_mlp.hip", "ta_eam.hip",
            "ta_nlist.hip", "ta_grap.hip", "ta_train.hip", "ta_hvp.hip", "ta_neighbor.cpp", "ta_td.hip",
            "ta_td_train.hip", "ta_md.hip", "ta_md_corr.hip", "ta_md_rdf.hip", "ta_md_adf.hip", "ta_md_order.hip", "ta_md_cluster.hip", "ta_md_cna.hip", "ta_md_sq.hip", "ta_md_flux.hip", "ta_relax.hip", "ta_neb.hip",
-           "ta_options.cpp"]
+           "ta_phonon.hip", "ta_options.cpp"]
 OBJ_DIR = CSRC_DIR / "build"
 
 TA_OK = 0
@@ -75,6 +75,8 @@ EXPORTED_SYMBOLS = [
     "ta_relax_set_cell", "ta_relax_get_cell",
     "ta_relax_set_band", "ta_relax_get_band",
     "ta_list_info", "ta_get_list",
+    "ta_phonon_set_cell", "ta_phonon_force_constants", "ta_phonon_load_force_constants",
+    "ta_phonon_frequencies", "ta_phonon_dos", "ta_phonon_eigh", "ta_phonon_eigh_group",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -194,6 +196,14 @@ class RelaxCellParams(C.Structure):
 
 class BandParams(C.Structure):
     _fields_ = [("k", C.c_double), ("climb", C.c_int32), ("reserved_", C.c_int32)]
+
+
+TA_PHONON_MAX_ORDER = 48  # include/tensoralloy_amd.h: the eigensolver's largest matrix
+TA_PHONON_THZ = 1000.0 * 0.09822694788464063 / (2.0 * 3.141592653589793)  # include/tensoralloy_amd.h
+
+
+class PhononParams(C.Structure):
+    _fields_ = [("n_basis", C.c_int32), ("q_chunk", C.c_int32)]
 
 
 def hipcc_path() -> str:
@@ -399,6 +409,14 @@ def load():
     lib.ta_relax_get_cell.argtypes = [H, _dp, _dp, _dp, _dp]
     lib.ta_relax_set_band.argtypes = [H, C.c_int, C.POINTER(BandParams)]
     lib.ta_relax_get_band.argtypes = [H, _dp, _dp, _dp, _ip]
+    _i64p, _u64p = C.POINTER(C.c_int64), C.POINTER(C.c_uint64)
+    lib.ta_phonon_set_cell.argtypes = [H, C.POINTER(PhononParams), _ip, _dp, _ip, _dp]
+    lib.ta_phonon_force_constants.argtypes = [H, _dp]
+    lib.ta_phonon_load_force_constants.argtypes = [H, _dp]
+    lib.ta_phonon_frequencies.argtypes = [H, C.c_int64, _dp, _dp, _dp, _i64p]
+    lib.ta_phonon_dos.argtypes = [H, C.c_int64, _dp, C.c_int32, C.c_double, C.c_double, _u64p, _dp, _i64p]
+    lib.ta_phonon_eigh.argtypes = [H, C.c_int32, C.c_int64, _dp, _dp, _dp, _i64p]
+    lib.ta_phonon_eigh_group.argtypes = [C.c_int32]
     _lib = lib
     return lib
 

@@ -193,6 +193,31 @@ class TensorAlloyCalculator(BaseCalculator):
         clf = self.transformer.get_vap_transformer(atoms)
         return clf.reverse_map_hessian(hessian)
 
+    def get_frequencies_and_normal_modes(self, atoms=None):
+        """Vibrational frequencies [3N] in cm^-1 (ascending, imaginary modes negative) and the normal modes
+        [3N, 3N], one mode per row, at Gamma of the given cell (analysis/phonon.py's method name). The modes
+        are the unit eigenvectors of the mass-weighted Hessian M^-1/2 H M^-1/2. Up to 3N = 48 they come from
+        the device eigensolver on the analytic force constants, above it (or for models without analytic
+        second derivatives) from `numpy.linalg.eigh` of `get_hessian`.
+
+        The reference multiplies the EIGENVALUES by its conversion factor; a frequency is the square root of
+        an eigenvalue, so here nu = sign(l) sqrt(|l|) is converted, which is the physical quantity."""
+        from . import phonons as _ph
+        atoms = atoms if atoms is not None else self.atoms
+        n = 3 * len(atoms)
+        if n <= _lib.TA_PHONON_MAX_ORDER:
+            try:
+                ph = _ph.Phonons(self._engine, atoms, (1, 1, 1))
+                freq, modes = ph.frequencies(np.zeros((1, 3)), eigenvectors=True)
+                return freq[0] * _ph.THZ_TO_CM, modes[0]
+            except ValueError:
+                pass  # no analytic second derivatives: the differenced Hessian below
+        from .atoms import atomic_masses
+        inv = 1.0 / np.sqrt(np.repeat([atomic_masses[z] for z in atoms.numbers], 3))
+        H = self.get_hessian(atoms)
+        lam, vec = np.linalg.eigh(0.5 * (H + H.T) * inv[:, None] * inv[None, :])
+        return np.sign(lam) * np.sqrt(np.abs(lam)) * _ph.THZ * _ph.THZ_TO_CM, vec.T.copy()
+
     def get_forces(self, atoms=None):
         atoms = atoms if atoms is not None else self.atoms
         gsl = self.get_property("forces", atoms)

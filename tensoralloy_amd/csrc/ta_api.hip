@@ -1277,6 +1277,7 @@ int ta_set_frames(ta_handle h, int32_t n_frames, const ta_frame *frames, ta_batc
   h->relax.valid = false;
   h->relax.cell.on = false;
   h->relax.band.on = h->relax.band.ran = false;
+  h->phonon.valid = h->phonon.have_phi = false;  // the supercell description belongs to the frame that leaves
   return guarded(h, [&]() {
     set_frames_impl(h, n_frames, frames, info);
     if (h->td)  // every frame starts at T = 0, the reference's default (universal.py:295)

@@ -250,7 +250,7 @@ void frame_sums_of_rows(const ta_context *h, const double *rows, size_t n_dir, d
 // Jacobians, w-dot = H_mlp G-dot from the second-order MLP pass, then g and g-dot from the dual-arithmetic
 // backward expression (ta_hvp.hip).
 void hvp_descriptor_models(ta_context *h, int32_t n_dir, int32_t first, const double *dR, const double *dh, double *dF,
-                           double *dW) {
+                           double *dW, double *dF_dev) {
   const size_t N = (size_t)h->db.n_atoms, F = (size_t)h->db.n_frames;
   if (n_dir == 0 || N == 0) return;
   const bool grap_model = h->kind == TA_MODEL_GRAP_MLP, unit = !dR && !dh;
@@ -320,7 +320,8 @@ void hvp_descriptor_models(ta_context *h, int32_t n_dir, int32_t first, const do
     }
     ta::launch_hvp_gather(h->db, Dv, h->tan_dD.ptr, gv, gd, fdot, dW ? wrow : nullptr, s);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(dF + d * 3 * N, fdot, 3 * N * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (dF) HIP_CHECK(hipMemcpyAsync(dF + d * 3 * N, fdot, 3 * N * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (dF_dev) HIP_CHECK(hipMemcpyAsync(dF_dev + d * 3 * N, fdot, 3 * N * sizeof(double), hipMemcpyDeviceToDevice, s));
     if (dW) HIP_CHECK(hipMemcpyAsync(rows.data(), wrow, 9 * N * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));  // (the direction buffers are reused)
     if (dW) frame_sums_of_rows(h, rows.data(), 1, dW + d * F * 9);
@@ -328,7 +329,8 @@ void hvp_descriptor_models(ta_context *h, int32_t n_dir, int32_t first, const do
 }
 
 // ta_hessian_vectors of the EAM / ADP models: every direction in one set of launches (ta_eam.hip::eam_hvp)
-void hvp_eam(ta_context *h, int32_t n_dir, int32_t first, const double *dR, const double *dh, double *dF, double *dW) {
+void hvp_eam(ta_context *h, int32_t n_dir, int32_t first, const double *dR, const double *dh, double *dF, double *dW,
+             double *dF_dev) {
   const size_t N = (size_t)h->db.n_atoms, F = (size_t)h->db.n_frames;
   if (n_dir == 0 || N == 0) return;
   hipStream_t s = h->stream;
@@ -354,7 +356,8 @@ void hvp_eam(ta_context *h, int32_t n_dir, int32_t first, const double *dR, cons
   }
   ta::eam_hvp(h->eam, h->db, n_dir, !dR && !dh, first, d_dR, d_dh, dFdot, fdot, wdot, extra, s);
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpyAsync(dF, fdot, nd * N * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (dF) HIP_CHECK(hipMemcpyAsync(dF, fdot, nd * N * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (dF_dev) HIP_CHECK(hipMemcpyAsync(dF_dev, fdot, nd * N * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
   std::vector<double> wat;
   if (dW) {
     wat.resize(nd * N * 9);
@@ -365,6 +368,40 @@ void hvp_eam(ta_context *h, int32_t n_dir, int32_t first, const double *dR, cons
 }
 
 }  // namespace
+
+namespace ta {
+namespace host {
+
+int hessian_vectors_impl(ta_context *h, int32_t n_dir, int32_t first, const double *dR, const double *dh, double *dF,
+                         double *dW, double *dF_dev) {
+  if (!h || (!dF && !dF_dev) || n_dir < 0) return TA_ERR_INVALID;
+  if (h->td) return fail(h, TA_ERR_UNSUPPORTED, td_inference_only("ta_hessian_vectors"));
+  if (h->kind == TA_MODEL_EAM_FS) return fail(h, TA_ERR_INVALID, fs_inference_only("ta_hessian_vectors"));
+  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "no resident batch");
+  const bool grap_model = h->kind == TA_MODEL_GRAP_MLP;
+  const bool sf_model = h->kind == TA_MODEL_SF_MLP || grap_model;  // the descriptor + MLP models
+  if (sf_model) {
+    if (h->filtered) return fail(h, TA_ERR_UNSUPPORTED, filtered_refusal("ta_hessian_vectors"));
+    if (grap_model && !ta::grap_hvp_supported(h->grap))
+      return fail(h, TA_ERR_UNSUPPORTED, "ta_hessian_vectors: analytic second derivatives of GRAP models exist for the "
+                                         "sf / morse / density / pexp filters, not for the filter network");
+    for (const ChunkPlan &cp : h->chunks)
+      for (int iz = 0; iz < cp.nz && !grap_model; ++iz)
+        if (cp.ch.zeta_int[iz] <= 0)
+          return fail(h, TA_ERR_UNSUPPORTED, "ta_hessian_vectors: integer zetas only");
+  } else if (!h->eam || !ta::eam_hvp_supported(h->eam)) {
+    return fail(h, TA_ERR_UNSUPPORTED, "ta_hessian_vectors: analytic second derivatives exist for the symmetry-function and GRAP "
+                                       "models and for EAM / ADP models whose functions are of the Zjw04 family, networks or tabulated");
+  }
+  if (!dR && !dh && (first < 0 || (size_t)first + (size_t)n_dir > 3 * (size_t)h->db.n_atoms))
+    return fail(h, TA_ERR_INVALID, "ta_hessian_vectors: without dR / dh the directions are unit displacements "
+                                   "first .. first + n_dir - 1 of the 3 N");
+  if ((size_t)n_dir > 65535) return fail(h, TA_ERR_INVALID, "ta_hessian_vectors: at most 65535 directions per call");
+  return guarded(h, [&]() { (sf_model ? hvp_descriptor_models : hvp_eam)(h, n_dir, first, dR, dh, dF, dW, dF_dev); });
+}
+
+}  // namespace host
+}  // namespace ta
 
 extern "C" {
 
@@ -677,29 +714,7 @@ int ta_constant_gradient(ta_handle h, const double *frame_coeff, const double *d
 int ta_hessian_vectors(ta_handle h, int32_t n_dir, int32_t first, const double *dR, const double *dh, double *dF,
                        double *dW) {
   if (!h || !dF || n_dir < 0) return TA_ERR_INVALID;
-  if (h->td) return fail(h, TA_ERR_UNSUPPORTED, td_inference_only("ta_hessian_vectors"));
-  if (h->kind == TA_MODEL_EAM_FS) return fail(h, TA_ERR_INVALID, fs_inference_only("ta_hessian_vectors"));
-  if (!h->have_batch) return fail(h, TA_ERR_INVALID, "no resident batch");
-  const bool grap_model = h->kind == TA_MODEL_GRAP_MLP;
-  const bool sf_model = h->kind == TA_MODEL_SF_MLP || grap_model;  // the descriptor + MLP models
-  if (sf_model) {
-    if (h->filtered) return fail(h, TA_ERR_UNSUPPORTED, filtered_refusal("ta_hessian_vectors"));
-    if (grap_model && !ta::grap_hvp_supported(h->grap))
-      return fail(h, TA_ERR_UNSUPPORTED, "ta_hessian_vectors: analytic second derivatives of GRAP models exist for the "
-                                         "sf / morse / density / pexp filters, not for the filter network");
-    for (const ChunkPlan &cp : h->chunks)
-      for (int iz = 0; iz < cp.nz && !grap_model; ++iz)
-        if (cp.ch.zeta_int[iz] <= 0)
-          return fail(h, TA_ERR_UNSUPPORTED, "ta_hessian_vectors: integer zetas only");
-  } else if (!h->eam || !ta::eam_hvp_supported(h->eam)) {
-    return fail(h, TA_ERR_UNSUPPORTED, "ta_hessian_vectors: analytic second derivatives exist for the symmetry-function and GRAP "
-                                       "models and for EAM / ADP models whose functions are of the Zjw04 family, networks or tabulated");
-  }
-  if (!dR && !dh && (first < 0 || (size_t)first + (size_t)n_dir > 3 * (size_t)h->db.n_atoms))
-    return fail(h, TA_ERR_INVALID, "ta_hessian_vectors: without dR / dh the directions are unit displacements "
-                                   "first .. first + n_dir - 1 of the 3 N");
-  if ((size_t)n_dir > 65535) return fail(h, TA_ERR_INVALID, "ta_hessian_vectors: at most 65535 directions per call");
-  return guarded(h, [&]() { (sf_model ? hvp_descriptor_models : hvp_eam)(h, n_dir, first, dR, dh, dF, dW); });
+  return hessian_vectors_impl(h, n_dir, first, dR, dh, dF, dW, nullptr);
 }
 
 int ta_set_nn_tables(ta_handle h, int on) {

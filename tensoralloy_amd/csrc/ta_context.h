@@ -427,6 +427,18 @@ struct RelaxState {
   } band;
 };
 
+// harmonic phonons (ta_api_phonon.hip; the launches are in ta_phonon.hip): the supercell description of
+// ta_phonon_set_cell, the force-constant rows of the home cell, and the work space of a chunk of q-points
+struct PhononState {
+  bool valid = false;    // ta_phonon_set_cell has run for the resident frame
+  bool have_phi = false;
+  int n_basis = 0, N = 0;
+  int64_t q_chunk = 0;   // q-points per pass, a multiple of the DOS slab
+  DevBuf<int32_t> basis_of, start;
+  DevBuf<double> mass, vec, phi, q, D, w, V, nu, dos_part, dos_slab;
+  DevBuf<unsigned long long> counts;  // [n_bins] total, then the two info words
+};
+
 }  // namespace host
 }  // namespace ta
 
@@ -544,6 +556,7 @@ struct ta_context {
   ta::host::ResidentLoop res;  // ta_md_run and ta_relax_run: the loop they share
   ta::host::MdState md;
   ta::host::RelaxState relax;
+  ta::host::PhononState phonon;
 
   hipEvent_t ev[2 * TA_N_KERNEL_SLOTS + 2] = {nullptr};
   std::string err;
@@ -571,6 +584,12 @@ void set_centre_gradients(ta_context *h, bool on);
 // the resident frames again with new coordinates (cells: null = unchanged): the rebuild path of
 // ta_update_positions and the resident runs; throws
 void rebuild_list(ta_context *h, const double *positions, const double *cells);
+
+// ta_api_train.hip
+// ta_hessian_vectors with the force tangents left on the device as well: dF_dev [n_dir][N][3] (either of dF,
+// dF_dev may be null, not both). Same checks, same return codes, same values.
+int hessian_vectors_impl(ta_context *h, int32_t n_dir, int32_t first, const double *dR, const double *dh, double *dF,
+                         double *dW, double *dF_dev);
 
 // ta_resident.hip
 // workgroups of the integrator launch: `chunk` consecutive atoms of one frame each, at least one per frame

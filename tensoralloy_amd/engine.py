@@ -95,6 +95,7 @@ class Engine:
         self.batch_generation += 1  # what is resident changed (train.Trainer's shortcut checks this)
         self._md_sig = None
         self._relax_cell = False
+        self._phonon = None  # `phonon_set_cell` belongs to the batch that leaves
         self._volumes = np.array([abs(np.linalg.det(f.cell)) for f in frames])
         self._natoms = np.array([len(f.species) for f in frames], dtype=np.int64)
         self._numbers = np.concatenate([np.asarray(a.numbers, dtype=np.int64) for a in atoms_list]) \
@@ -1486,6 +1487,107 @@ class Engine:
                 self._handle, m, first, rp, hp, _lib.as_dp(dF[first:]),
                 _lib.as_dp(dW[first:]) if want_virial else null))
         return (dF, dW) if want_virial else dF
+
+    # -- harmonic phonons (ta_phonon_*; `phonons.Phonons` is the user-facing class) ----------------
+    def phonon_set_cell(self, n_basis, basis_of, masses, start, vectors, q_chunk=0):
+        """Declare the one resident frame a supercell whose first `n_basis` atoms are the home cell
+        (`ta_phonon_set_cell`): basis_of [N], masses [n_basis] amu, and the CSR list (start [n_basis N + 1],
+        vectors [*, 3] in Angstrom) of the shortest vectors from every home atom to the images of every atom."""
+        self._need_batch("phonon_set_cell")
+        basis_of = np.ascontiguousarray(basis_of, dtype=np.int32).reshape(-1)
+        masses = np.ascontiguousarray(masses, dtype=np.float64).reshape(-1)
+        start = np.ascontiguousarray(start, dtype=np.int32).reshape(-1)
+        vectors = np.ascontiguousarray(vectors, dtype=np.float64).reshape(-1, 3)
+        N, n_basis = int(self.info.n_atoms), int(n_basis)
+        if len(basis_of) != N or len(masses) != n_basis or len(start) != n_basis * N + 1 or \
+                (len(start) and len(vectors) < start[-1]):
+            raise ValueError("phonon_set_cell: basis_of [N], masses [n_basis], start [n_basis N + 1] and "
+                             "vectors [start[-1], 3] are expected")
+        p = _lib.PhononParams(n_basis, int(q_chunk))
+        vec = vectors if len(vectors) else np.zeros((1, 3))
+        self._check(self._lib.ta_phonon_set_cell(self._handle, C.byref(p), _lib.as_ip(basis_of), _lib.as_dp(masses),
+                                                 _lib.as_ip(start), _lib.as_dp(vec)))
+        self._phonon = (n_basis, N)
+
+    def _phonon_shape(self, who):
+        self._need_batch(who)
+        shape = getattr(self, "_phonon", None)
+        if shape is None or shape[1] != int(self.info.n_atoms):
+            raise ValueError(f"{who} called before phonon_set_cell")
+        return shape
+
+    def phonon_force_constants(self) -> np.ndarray:
+        """Phi [n_basis, N, 3, 3] of the home-cell atoms from the analytic Hessian-vector products; it stays
+        on the device for `phonon_frequencies` / `phonon_dos`. ValueError for models without the analytic path."""
+        nb, N = self._phonon_shape("phonon_force_constants")
+        phi = np.zeros((nb, N, 3, 3))
+        self._check(self._lib.ta_phonon_force_constants(self._handle, _lib.as_dp(phi)))
+        return phi
+
+    def phonon_load_force_constants(self, phi):
+        nb, N = self._phonon_shape("phonon_load_force_constants")
+        phi = np.ascontiguousarray(phi, dtype=np.float64)
+        if phi.shape != (nb, N, 3, 3):
+            raise ValueError(f"phonon_load_force_constants: Phi must be [{nb}, {N}, 3, 3]")
+        self._check(self._lib.ta_phonon_load_force_constants(self._handle, _lib.as_dp(phi)))
+
+    def phonon_frequencies(self, q_cart, eigenvectors=False):
+        """Frequencies [Q, n] in THz (ascending, imaginary modes negative) at the Cartesian wave vectors q_cart
+        [Q, 3] in 1/Angstrom; with `eigenvectors` also the modes [Q, n, n] complex, row m = mode m. Raises
+        RuntimeError if the solver left a matrix unconverged."""
+        nb, _ = self._phonon_shape("phonon_frequencies")
+        q = np.ascontiguousarray(q_cart, dtype=np.float64).reshape(-1, 3)
+        n, Q = 3 * nb, len(q)
+        freq = np.zeros((Q, n))
+        vec = np.zeros((Q, n, n), dtype=np.complex128) if eigenvectors else None
+        info = np.zeros(1, dtype=np.int64)
+        null = C.POINTER(C.c_double)()
+        self._check(self._lib.ta_phonon_frequencies(
+            self._handle, Q, _lib.as_dp(q if Q else np.zeros((1, 3))), _lib.as_dp(freq if Q else np.zeros(1)),
+            vec.ctypes.data_as(C.POINTER(C.c_double)) if eigenvectors and Q else null,
+            info.ctypes.data_as(C.POINTER(C.c_int64))))
+        if info[0]:
+            raise RuntimeError(f"phonon_frequencies: the eigensolver left {int(info[0])} matrices unconverged")
+        return (freq, vec) if eigenvectors else freq
+
+    def phonon_dos(self, q_cart, n_bins, nu_min, nu_max, partial=False) -> dict:
+        """Histogram of the frequencies at q_cart, formed on the device: `total` [n_bins] uint64 counts of
+        modes in the bins k = floor((nu - nu_min) * (n_bins / (nu_max - nu_min))), `outside` = modes beyond
+        the range (counted nowhere else), and with `partial` the per-home-atom weights [n_basis, n_bins]."""
+        nb, _ = self._phonon_shape("phonon_dos")
+        q = np.ascontiguousarray(q_cart, dtype=np.float64).reshape(-1, 3)
+        n_bins = int(n_bins)
+        total = np.zeros(max(n_bins, 1), dtype=np.uint64)
+        part = np.zeros((nb, max(n_bins, 1))) if partial else None
+        info = np.zeros(2, dtype=np.int64)
+        null = C.POINTER(C.c_double)()
+        self._check(self._lib.ta_phonon_dos(
+            self._handle, len(q), _lib.as_dp(q if len(q) else np.zeros((1, 3))), n_bins, float(nu_min), float(nu_max),
+            total.ctypes.data_as(C.POINTER(C.c_uint64)), _lib.as_dp(part) if partial else null,
+            info.ctypes.data_as(C.POINTER(C.c_int64))))
+        if info[0]:
+            raise RuntimeError(f"phonon_dos: the eigensolver left {int(info[0])} matrices unconverged")
+        out = {"total": total, "outside": int(info[1])}
+        if partial:
+            out["partial"] = part
+        return out
+
+    def phonon_eigh(self, A, eigenvectors=True):
+        """The batched Hermitian eigensolver alone: A [batch, n, n] complex (its Hermitian part is solved),
+        n <= TA_PHONON_MAX_ORDER. Returns (w [batch, n] ascending, V [batch, n, n] with row m = eigenvector m
+        or None, unconverged count)."""
+        A = np.ascontiguousarray(A, dtype=np.complex128)
+        if A.ndim != 3 or A.shape[1] != A.shape[2]:
+            raise ValueError("phonon_eigh: A must be [batch, n, n]")
+        batch, n = A.shape[0], A.shape[1]
+        w = np.zeros((batch, n))
+        V = np.zeros((batch, n, n), dtype=np.complex128) if eigenvectors else None
+        info = np.zeros(1, dtype=np.int64)
+        dp = C.POINTER(C.c_double)
+        self._check(self._lib.ta_phonon_eigh(
+            self._handle, n, batch, A.ctypes.data_as(dp) if batch else dp(), _lib.as_dp(w) if batch else dp(),
+            V.ctypes.data_as(dp) if eigenvectors and batch else dp(), info.ctypes.data_as(C.POINTER(C.c_int64))))
+        return w, V, int(info[0])
 
     def energies(self, reuse_descriptors=True) -> np.ndarray:
         """Frame energies of the resident batch; with `reuse_descriptors` only the MLP is re-run."""
