@@ -444,6 +444,68 @@ int ta_step_view(ta_handle h, const double *positions, const double *cells, uint
  *   ta_md_get_chain_records  e_chain [n_rec][n_frames] of the last successful run, at the slots of its epot /
  *                        ekin. TA_ERR_INVALID when that run did not use this thermostat.
  *
+ * Isothermal-isobaric ensemble: a Martyna-Tobias-Klein barostat (Martyna, Tobias, Klein, J. Chem. Phys. 101, 4177;
+ * the measure-preserving integrator of Tuckerman et al., J. Phys. A 39, 5629; what LAMMPS calls fix npt and ASE
+ * IsotropicMTKNPT / MTKNPT), coupled to the Nose-Hoover chain above and to a chain of its own, per frame and inside
+ * the integrator launch. Unlike the Berendsen barostat it samples the ensemble: the volume fluctuates as the
+ * compressibility says. Two modes: isotropic, one strain rate from the mean driving force; per axis, a diagonal
+ * strain-rate tensor in which every free axis follows its own pressure and a masked axis keeps its length exactly.
+ * A fully flexible cell and a run without the thermostat are not provided: the barostat needs the Nose-Hoover
+ * chain on and takes kT0 from it. Per frame: n atoms, g = 3 n - dof_removed, kT0 and tau the chain's, P0 the target
+ * pressure, tau_p the barostat's time, h the cell (rows are lattice vectors), V = |det h|, W_vir the virial (dE / d
+ * strain) of the last evaluation, S_c = sum_i m_i v_ic^2, K = (S_x + S_y + S_z) / 2, free_c in {0, 1} the free axes
+ * (isotropic: all three), d_b = 1 (isotropic) or sum_c free_c. State: the strain rates omega_c and the barostat's
+ * chain (xi_k, vxi_k), k = 1 .. M_p. Masses:
+ *     W_c = (g + 3) kT0 tau_p^2 / 3,   Q'_1 = d_b kT0 tau_p^2,   Q'_k = kT0 tau_p^2 (k >= 2)
+ * Driving force, and what follows from omega:
+ *     G_c = free_c [S_c - W_vir,cc - P0 V + 2 K / g] / W_c        isotropic: the three G_c are replaced by their mean
+ *     alpha_c = omega_c + (omega_x + omega_y + omega_z) / g,       K_b = sum_c W_c omega_c^2 / 2
+ * half(chain, K, dof, tau) is the half-update over dt / 2 spelled out above with (g, tau) -> (dof, tau); it returns
+ * the factor s. One step from (x, v, h, omega, chains) with F and W_vir of x, h:
+ *     1. s = half(particle chain, K, g, tau);  v <- s v
+ *     2. s_b = half(barostat chain, K_b, d_b, tau_p);  omega <- s_b omega
+ *     3. omega_c += (dt/2) G_c          K and S_c as they stand after 1, V and W_vir of the current state
+ *     4. v_c <- v_c exp(-(dt/2) alpha_c);  then v += (dt/2) F/m
+ *     5. x_c <- exp(omega_c dt) x_c + dt exp(omega_c dt/2) v_c;  h[:, c] <- exp(omega_c dt) h[:, c]
+ *     6. evaluate F and W_vir at the new x, h
+ *     7. v += (dt/2) F/m;  then v_c <- v_c exp(-(dt/2) alpha_c)        alpha from the omega of 3
+ *     8. omega_c += (dt/2) G_c          from the new S_c, K, V, W_vir
+ *     9. s_b = half(barostat chain, K_b, d_b, tau_p);  omega <- s_b omega;  then s = half(particle chain, K, g, tau);
+ *        v <- s v
+ * The conserved quantity per frame is
+ *     H' = K + E_pot + E_chain + E_baro
+ *     E_baro = P0 V + K_b + sum_k Q'_k vxi_k^2 / 2 + d_b kT0 xi_1 + kT0 sum_{k>=2} xi_k
+ * Its excursion falls by 4 per halving of dt, and a run reversed (v, omega, veta, vxi -> -) returns to its start.
+ * Record 0 is the state at entry and record r > 0 the state after step 9 of its step, so ekin + epot + e_chain +
+ * e_baro is H' at every slot. One workgroup owns a whole frame; the chain and barostat arithmetic is one thread's,
+ * in fp64 with a fixed order.
+ *   ta_md_set_mtk_barostat  NULL or tau_p <= 0 switches it off (the default; always allowed). A property of the
+ *                        handle like the other settings (ta_set_frames keeps it). TA_ERR_INVALID, with the argument
+ *                        named by ta_last_error and the setting left as it was: pressure or tau_p not finite, chain
+ *                        outside 1 .. TA_MD_MAX_CHAIN, loops outside 1 .. 16, isotropic == 0 with a mask of all
+ *                        zeros, the Berendsen barostat on (and ta_md_set_barostat refuses to go on while this one
+ *                        is: only one barostat at a time). A call that changes `chain` while the barostat is on
+ *                        puts the barostat's chain at rest, as ta_md_set_nose_hoover does with its own.
+ *   ta_md_run            with this barostat on: TA_ERR_INVALID while the Nose-Hoover chain is off or the Berendsen
+ *                        or the Langevin thermostat is on, for a batch with a frame that is not periodic along all
+ *                        three axes or has a singular cell, and with the samplers that refuse the Berendsen barostat
+ *                        (ta_md_set_sampling, _rdf, _sq, _flux), for the same reasons. Everything ta_md_run does for
+ *                        the Berendsen barostat holds unchanged: TA_WANT_VIRIAL is added to `want`; the launch
+ *                        keeps s_c, the product of the exp(omega_c dt) since the list was built, and the list test
+ *                        is the one stated there; rebuilds take the cells from the device; the triangle-once
+ *                        backward pass is selected by the wider rule; an exp(omega_c dt) that is not a finite
+ *                        number > 0 ends the run with TA_ERR_INVALID; a run that moved the cells ends with one list
+ *                        for the final cells, which ta_relax_set_cell takes over as its h0. A launch enqueued behind
+ *                        a stale list leaves omega and both chains alone.
+ *   ta_md_get_records    volume and press of the recorded states (after step 9), as under the Berendsen barostat.
+ *   ta_md_get_mtk_state  omega [n_frames][3], xi / vxi [n_frames][chain] of the resident state; any may be NULL.
+ *                        Needs ta_md_init and this barostat on, as does
+ *   ta_md_set_mtk_state  the restart call: finite values, NULL = zeros. ta_md_init zeroes all three. With
+ *                        ta_md_get_state, ta_md_get_chain and ta_md_get_cell a run goes on exactly where another
+ *                        stopped.
+ *   ta_md_get_mtk_records  e_baro [n_rec][n_frames] of the last successful run, at the slots of its epot / ekin.
+ *                        TA_ERR_INVALID when that run did not use this barostat.
+ *
  * Time correlations inside the loop (opt-in; with sampling never switched on nothing changes). Let t be the
  * absolute step (steps integrated since ta_md_init, the counter of the Langevin noise). With n_lags = L and
  * sample_every = s the whole-step state (x(t), v(t)) of every t with t % s == 0 is sampled, once: the positions
@@ -861,6 +923,14 @@ typedef struct {
   int32_t mask[3];         /* x, y, z: non-zero = the axis is free; read when isotropic == 0 */
   int32_t isotropic;       /* non-zero: one factor from the mean of the three pressures */
 } ta_md_barostat_params;
+typedef struct {
+  double pressure;      /* P0, energy / volume (eV / A^3) */
+  double tau_p;         /* time constant; <= 0: barostat off */
+  int32_t chain;        /* M_p, 1 .. TA_MD_MAX_CHAIN */
+  int32_t loops;        /* loops of a half-update of the barostat's chain, 1 .. 16 */
+  int32_t mask[3];      /* x, y, z: non-zero = the axis is free; read when isotropic == 0 */
+  int32_t isotropic;    /* non-zero: one strain rate from the mean driving force */
+} ta_md_mtk_params;
 int ta_md_init(ta_handle h, const double *masses, const double *velocities);
 int ta_md_set_thermostat(ta_handle h, double kT0, double tau);
 int ta_md_set_langevin(ta_handle h, double kT0, double friction, uint64_t seed);
@@ -875,6 +945,10 @@ int ta_md_set_nose_hoover(ta_handle h, const ta_md_nhc_params *p);
 int ta_md_get_chain(ta_handle h, double *eta, double *veta);
 int ta_md_set_chain(ta_handle h, const double *eta, const double *veta);
 int ta_md_get_chain_records(ta_handle h, double *e_chain);
+int ta_md_set_mtk_barostat(ta_handle h, const ta_md_mtk_params *p);
+int ta_md_get_mtk_state(ta_handle h, double *omega, double *xi, double *vxi);
+int ta_md_set_mtk_state(ta_handle h, const double *omega, const double *xi, const double *vxi);
+int ta_md_get_mtk_records(ta_handle h, double *e_baro);
 int ta_md_set_sampling(ta_handle h, const ta_md_sampling_params *p);
 int ta_md_get_correlations(ta_handle h, double *vacf_sum, double *msd_sum, int64_t *info);
 int ta_md_get_samples(ta_handle h, int32_t first_lag, int32_t n, double *positions, double *velocities,

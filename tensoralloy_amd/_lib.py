@@ -21,7 +21,7 @@ LIB_PATH = PKG_DIR / "libtensoralloy_amd.so"
 
 SOURCES = ["ta_api.hip", "ta_api_train.hip", "ta_api_md.hip", "ta_api_relax.hip", "ta_api_phonon.hip", "ta_resident.hip", "ta_kernels.hip", "ta_kernels_v2.hip", "ta_mlp.hip", "ta_eam.hip",
            "ta_nlist.hip", "ta_grap.hip", "ta_train.hip", "ta_hvp.hip", "ta_neighbor.cpp", "ta_td.hip",
-           "ta_td_train.hip", "ta_md.hip", "ta_md_corr.hip", "ta_md_rdf.hip", "ta_md_adf.hip", "ta_md_order.hip", "ta_md_cluster.hip", "ta_md_cna.hip", "ta_md_sq.hip", "ta_md_flux.hip", "ta_relax.hip", "ta_neb.hip",
+           "ta_td_train.hip", "ta_md.hip", "ta_md_mtk.hip", "ta_md_corr.hip", "ta_md_rdf.hip", "ta_md_adf.hip", "ta_md_order.hip", "ta_md_cluster.hip", "ta_md_cna.hip", "ta_md_sq.hip", "ta_md_flux.hip", "ta_relax.hip", "ta_neb.hip",
            "ta_phonon.hip", "ta_options.cpp"]
 OBJ_DIR = CSRC_DIR / "build"
 
@@ -63,6 +63,7 @@ EXPORTED_SYMBOLS = [
     "ta_md_set_langevin", "ta_md_noise",
     "ta_md_set_barostat", "ta_md_get_cell", "ta_md_get_records",
     "ta_md_set_nose_hoover", "ta_md_get_chain", "ta_md_set_chain", "ta_md_get_chain_records",
+    "ta_md_set_mtk_barostat", "ta_md_get_mtk_state", "ta_md_set_mtk_state", "ta_md_get_mtk_records",
     "ta_md_set_sampling", "ta_md_get_correlations", "ta_md_get_samples",
     "ta_md_set_rdf", "ta_md_get_rdf",
     "ta_md_set_adf", "ta_md_get_adf",
@@ -132,6 +133,11 @@ TA_MD_MAX_CHAIN = 8  # include/tensoralloy_amd.h: TA_MD_MAX_CHAIN
 class MdNhcParams(C.Structure):
     _fields_ = [("kT0", C.c_double), ("tau", C.c_double), ("chain", C.c_int32), ("loops", C.c_int32),
                 ("dof_removed", C.c_int32)]
+
+
+class MdMtkParams(C.Structure):
+    _fields_ = [("pressure", C.c_double), ("tau_p", C.c_double), ("chain", C.c_int32), ("loops", C.c_int32),
+                ("mask", C.c_int32 * 3), ("isotropic", C.c_int32)]
 
 
 TA_MD_MAX_LAGS = 4096  # include/tensoralloy_amd.h: TA_MD_MAX_LAGS
@@ -377,6 +383,10 @@ def load():
     lib.ta_md_get_chain.argtypes = [H, _dp, _dp]
     lib.ta_md_set_chain.argtypes = [H, _dp, _dp]
     lib.ta_md_get_chain_records.argtypes = [H, _dp]
+    lib.ta_md_set_mtk_barostat.argtypes = [H, C.POINTER(MdMtkParams)]
+    lib.ta_md_get_mtk_state.argtypes = [H, _dp, _dp, _dp]
+    lib.ta_md_set_mtk_state.argtypes = [H, _dp, _dp, _dp]
+    lib.ta_md_get_mtk_records.argtypes = [H, _dp]
     lib.ta_md_set_sampling.argtypes = [H, C.POINTER(MdSamplingParams)]
     lib.ta_md_get_correlations.argtypes = [H, _dp, _dp, C.POINTER(C.c_int64)]
     lib.ta_md_get_samples.argtypes = [H, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int64)]

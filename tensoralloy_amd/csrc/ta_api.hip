@@ -674,7 +674,7 @@ void ta::host::compute_impl(ta_context *h, uint32_t want, bool timed, double *sl
     // triangle-once backward pass: the forward launches also leave the owned job lists
     // (while cells relax or follow a barostat, a list stays valid until a width has shrunk by
     // rmax / (rmax + skin): the wider test)
-    const bool tri_cells = (h->relax.cell.on || h->md.baro.on) ? h->tri_cells_wide_ok : h->tri_cells_ok;
+    const bool tri_cells = (h->relax.cell.on || h->md.moves_cells()) ? h->tri_cells_wide_ok : h->tri_cells_ok;
     // (its owner puts the gradient of all three terms of a triangle onto its own two pairs: g is then a partition of
     // the forces, not d e_c / d D_p, which a run that samples the heat current reads)
     const bool tri = h->use_v2 && h->triangles && tri_cells && h->n_elements == 1 && need_forces && !h->centre_gradients;

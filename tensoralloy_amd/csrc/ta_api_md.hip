@@ -1,5 +1,5 @@
 // C ABI of the device-resident MD loop: the ta_md_* entry points (include/tensoralloy_amd.h). The loop itself
-// is in ta_resident.hip; the integrator, correlation, pair-distribution, bond-angle and bond-order launches are in
+// is in ta_resident.hip; the integrator (ta_md_mtk.hip: under the Martyna-Tobias-Klein barostat), correlation, pair-distribution, bond-angle and bond-order launches are in
 // ta_md.hip, ta_md_corr.hip, ta_md_rdf.hip, ta_md_adf.hip and ta_md_order.hip; the cluster launches in
 // ta_md_cluster.hip, the common neighbour analysis in ta_md_cna.hip, the structure-factor launches in ta_md_sq.hip,
 // the heat-current and pressure-tensor launches in ta_md_flux.hip.
@@ -468,6 +468,14 @@ int md_chain_ready(ta_context *h, const char *who) {
   return TA_OK;
 }
 
+// what ta_md_get_mtk_state and ta_md_set_mtk_state need; returns 0 or the error code
+int md_mtk_ready(ta_context *h, const char *who) {
+  if (const int rc = md_resident(h, who)) return rc;
+  if (!h->md.mtk.on)
+    return fail(h, TA_ERR_INVALID, std::string(who) + ": the Martyna-Tobias-Klein barostat is off (ta_md_set_mtk_barostat)");
+  return TA_OK;
+}
+
 // what the getters of sampler `x` need: it is on and holds the data of runs that succeeded; returns 0 or the error code
 int md_sampler_ready(ta_context *h, const MdSampler &x, const char *who) {
   if (const int rc = md_resident(h, who)) return rc;
@@ -518,7 +526,18 @@ int md_run_refusals(ta_context *h, int32_t n_steps, double dt, int32_t record_ev
   if (!std::isfinite(dt)) return fail(h, TA_ERR_INVALID, "ta_md_run: dt must be finite");
   const MdState &md = h->md;
   if (md.langevin.friction > 0.0 && dt < 0.0) return fail(h, TA_ERR_INVALID, "ta_md_run: Langevin dynamics needs dt >= 0");
-  const bool baro = md.baro.on;
+  const bool baro = md.moves_cells();
+  if (md.mtk.on) {  // it is coupled to the particle chain and takes kT0 from it
+    if (md.berendsen.kT0 > 0.0)
+      return fail(h, TA_ERR_INVALID, "ta_md_run: the Martyna-Tobias-Klein barostat (ta_md_set_mtk_barostat) is on and so is the "
+                                     "Berendsen thermostat; it needs the Nose-Hoover chain (ta_md_set_nose_hoover) instead");
+    if (md.langevin.friction > 0.0)
+      return fail(h, TA_ERR_INVALID, "ta_md_run: the Martyna-Tobias-Klein barostat (ta_md_set_mtk_barostat) is on and so is the "
+                                     "Langevin thermostat; it needs the Nose-Hoover chain (ta_md_set_nose_hoover) instead");
+    if (!md.nhc.on)
+      return fail(h, TA_ERR_INVALID, "ta_md_run: the Martyna-Tobias-Klein barostat (ta_md_set_mtk_barostat) is on and the "
+                                     "Nose-Hoover chain thermostat is off (ta_md_set_nose_hoover); it takes kT0 from the chain");
+  }
   if (baro)
     if (const int bad = md_frames_periodic(h, "ta_md_run: the barostat is on and ", "")) return bad;
   for (size_t f = 0; md.nhc.on && f < h->keep_natoms.size(); ++f)
@@ -536,7 +555,11 @@ int md_run_refusals(ta_context *h, int32_t n_steps, double dt, int32_t record_ev
       {md.flux.on, "ta_md_run: the heat current and pressure tensor (ta_md_set_flux) and the barostat (ta_md_set_barostat) "
                    "are both on; normalising the correlations needs one volume: switch one of them off"}};
   for (const auto &x : no_barostat)
-    if (x.first && baro) return fail(h, TA_ERR_INVALID, x.second);
+    if (x.first && baro) {
+      std::string why = x.second;  // (the same reasons under either barostat: the one that is on is named)
+      if (md.mtk.on) why.replace(why.find("ta_md_set_barostat"), std::strlen("ta_md_set_barostat"), "ta_md_set_mtk_barostat");
+      return fail(h, TA_ERR_INVALID, why);
+    }
   if (md.cluster.on && md.cluster.set.p.n_min > 0) {  // n_conn of the order launches for the same state is read
     if (!md.order.on)
       return fail(h, TA_ERR_INVALID, "ta_md_run: the cluster analysis (ta_md_set_clusters) has n_min > 0 and reads n_conn, but "
@@ -561,7 +584,7 @@ int md_run_refusals(ta_context *h, int32_t n_steps, double dt, int32_t record_ev
 ta::MdLaunch md_launch(const ta_context *h, double dt, int chunk) {
   const MdState &md = h->md;
   const ResidentLoop &res = h->res;
-  const bool thermostat = md.berendsen.kT0 > 0.0, langevin = md.langevin.friction > 0.0, baro = md.baro.on, nhc = md.nhc.on;
+  const bool thermostat = md.berendsen.kT0 > 0.0, langevin = md.langevin.friction > 0.0, baro = md.moves_cells(), nhc = md.nhc.on;
   ta::MdLaunch a;
   a.vel = md.vel.ptr, a.mass = md.mass.ptr, a.epot = md.epot.ptr, a.ke_part = md.ke.ptr;
   a.ref = res.ref.ptr, a.blk_start = res.blk_start.ptr;
@@ -585,7 +608,7 @@ ta::MdLaunch md_launch(const ta_context *h, double dt, int chunk) {
   a.cells = nullptr, a.virial = nullptr;
   a.baro_scale = md.baro.scale.ptr, a.baro_rec = md.baro.rec.ptr;
   a.baro_p0 = md.baro.p.pressure;
-  a.baro_k = baro ? dt / md.baro.p.taup * md.baro.p.compressibility / 3.0 : 0.0;
+  a.baro_k = md.baro.on ? dt / md.baro.p.taup * md.baro.p.compressibility / 3.0 : 0.0;
   for (int c = 0; c < 3; ++c) a.baro_mask[c] = md.baro.p.mask[c] ? 1 : 0;
   a.skin = h->skin, a.r_list = h->rmax + h->skin;
   a.nhc = nhc ? 1 : 0;
@@ -595,10 +618,21 @@ ta::MdLaunch md_launch(const ta_context *h, double dt, int chunk) {
   a.nhc_eta = md.nhc.eta.ptr, a.nhc_veta = md.nhc.veta.ptr, a.nhc_rec = md.nhc.rec.ptr;
   return a;
 }
+// The Martyna-Tobias-Klein launch's arguments beside those (fixed for a ta_md_run)
+ta::MdMtkLaunch md_mtk_launch(const ta_context *h) {
+  const MdState &md = h->md;
+  ta::MdMtkLaunch b;
+  b.omega = md.mtk.omega.ptr, b.xi = md.mtk.xi.ptr, b.vxi = md.mtk.vxi.ptr, b.rec = md.mtk.rec.ptr;
+  b.p0 = md.mtk.p.pressure;
+  b.q = md.mtk.on ? md.nhc.p.kT0 * md.mtk.p.tau_p * md.mtk.p.tau_p : 0.0;
+  b.chain = md.mtk.p.chain, b.loops = md.mtk.p.loops, b.iso = md.mtk.p.isotropic ? 1 : 0;
+  for (int c = 0; c < 3; ++c) b.mask[c] = md.mtk.p.mask[c] ? 1 : 0;
+  return b;
+}
 // The integrator launch k of the run that began at absolute step step0: it finishes step k - 1, records every
 // record_every-th state, writes the snapshot and, with `drift`, begins step k
-void md_enqueue(const ta_context *h, ta::MdLaunch &a, int threads, int64_t step0, int k, bool drift, int record_every,
-                const MdSnapshot &snap) {
+void md_enqueue(const ta_context *h, ta::MdLaunch &a, const ta::MdMtkLaunch &mtk, int threads, int64_t step0, int k,
+                bool drift, int record_every, const MdSnapshot &snap) {
   // (a rebuild may have moved the batch's arrays: the pointers are taken at every launch)
   a.pos = h->db.pos, a.forces = h->db.forces, a.energy = h->db.energy, a.atom_start = h->db.atom_start;
   a.cells = h->db.cells, a.virial = h->db.virial;
@@ -607,7 +641,10 @@ void md_enqueue(const ta_context *h, ta::MdLaunch &a, int threads, int64_t step0
   a.drift = drift ? 1 : 0;
   a.rec = (k % record_every == 0) ? (long long)(k / record_every) : -1;
   a.snap_x = snap.x, a.snap_v = snap.v;
-  ta::launch_md_integrate(a, threads, h->stream);
+  if (h->md.mtk.on)  // (no sampler that takes a snapshot runs under a barostat)
+    ta::launch_md_mtk(a, mtk, h->stream);
+  else
+    ta::launch_md_integrate(a, threads, h->stream);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -619,7 +656,7 @@ void md_read_records(ta_context *h, size_t n_rec, uint32_t want, const std::vect
                      double *ekin, int *rebuilds, int32_t *n_rebuilds) {
   MdState &md = h->md;
   const size_t F = h->keep_natoms.size(), n_blk = (size_t)h->res.n_blk;
-  if (md.baro.on && F) {
+  if (md.moves_cells() && F) {
     std::vector<double> rec(4 * n_rec * F);
     HIP_CHECK(hipMemcpy(rec.data(), md.baro.rec.ptr, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
     md.baro.rec_volume.resize(n_rec * F);
@@ -641,6 +678,11 @@ void md_read_records(ta_context *h, size_t n_rec, uint32_t want, const std::vect
     md.nhc.rec_host.resize(n_rec * F);
     if (F) HIP_CHECK(hipMemcpy(md.nhc.rec_host.data(), md.nhc.rec.ptr, n_rec * F * sizeof(double), hipMemcpyDeviceToHost));
     md.nhc.rec_valid = true;
+  }
+  if (md.mtk.on) {
+    md.mtk.rec_host.resize(n_rec * F);
+    if (F) HIP_CHECK(hipMemcpy(md.mtk.rec_host.data(), md.mtk.rec.ptr, n_rec * F * sizeof(double), hipMemcpyDeviceToHost));
+    md.mtk.rec_valid = true;
   }
   if (epot && F) HIP_CHECK(hipMemcpy(epot, md.epot.ptr, n_rec * F * sizeof(double), hipMemcpyDeviceToHost));
   if (ekin && F) {
@@ -726,6 +768,13 @@ int ta_md_init(ta_handle h, const double *masses, const double *velocities) {
     HIP_CHECK(hipMemset(md.nhc.eta.ptr, 0, (n_chain + 1) * sizeof(double)));
     HIP_CHECK(hipMemset(md.nhc.veta.ptr, 0, (n_chain + 1) * sizeof(double)));
     md.nhc.rec_valid = false;
+    md.mtk.omega.ensure(3 * h->keep_natoms.size() + 1);  // every frame's barostat starts at rest as well
+    md.mtk.xi.ensure(n_chain + 1);
+    md.mtk.vxi.ensure(n_chain + 1);
+    HIP_CHECK(hipMemset(md.mtk.omega.ptr, 0, (3 * h->keep_natoms.size() + 1) * sizeof(double)));
+    HIP_CHECK(hipMemset(md.mtk.xi.ptr, 0, (n_chain + 1) * sizeof(double)));
+    HIP_CHECK(hipMemset(md.mtk.vxi.ptr, 0, (n_chain + 1) * sizeof(double)));
+    md.mtk.rec_valid = false;
     if (N) {
       HIP_CHECK(hipMemcpy(md.mass.ptr, masses, N * sizeof(double), hipMemcpyHostToDevice));
       if (velocities)
@@ -1306,6 +1355,9 @@ int ta_md_set_barostat(ta_handle h, const ta_md_barostat_params *p) {
     return fail(h, TA_ERR_INVALID, "ta_md_set_barostat: compressibility must be finite and >= 0");
   if (!p->isotropic && !p->mask[0] && !p->mask[1] && !p->mask[2])
     return fail(h, TA_ERR_INVALID, "ta_md_set_barostat: mask leaves no axis of the cell free");
+  if (h->md.mtk.on)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_barostat: the Martyna-Tobias-Klein barostat is on; switch it off "
+                                   "(ta_md_set_mtk_barostat with NULL) before the Berendsen barostat goes on");
   h->md.baro.p = *p;
   h->md.baro.on = true;
   return TA_OK;
@@ -1334,19 +1386,108 @@ int ta_md_get_records(ta_handle h, double *volume, double *press) {
   return TA_OK;
 }
 
+int ta_md_set_mtk_barostat(ta_handle h, const ta_md_mtk_params *p) {
+  if (!h) return TA_ERR_INVALID;
+  if (p && !std::isfinite(p->tau_p)) return fail(h, TA_ERR_INVALID, "ta_md_set_mtk_barostat: tau_p must be finite");
+  auto &mtk = h->md.mtk;
+  if (!p || !(p->tau_p > 0.0)) {
+    mtk.on = false;
+    return TA_OK;
+  }
+  if (!std::isfinite(p->pressure)) return fail(h, TA_ERR_INVALID, "ta_md_set_mtk_barostat: pressure must be finite");
+  if (p->chain < 1 || p->chain > TA_MD_MAX_CHAIN)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_mtk_barostat: chain must be 1 .. " + std::to_string(TA_MD_MAX_CHAIN));
+  if (p->loops < 1 || p->loops > 16) return fail(h, TA_ERR_INVALID, "ta_md_set_mtk_barostat: loops must be 1 .. 16");
+  if (!p->isotropic && !p->mask[0] && !p->mask[1] && !p->mask[2])
+    return fail(h, TA_ERR_INVALID, "ta_md_set_mtk_barostat: mask leaves no axis of the cell free");
+  if (h->md.baro.on)
+    return fail(h, TA_ERR_INVALID, "ta_md_set_mtk_barostat: the Berendsen barostat is on; switch it off "
+                                   "(ta_md_set_barostat with NULL) before the Martyna-Tobias-Klein barostat goes on");
+  if (mtk.on && mtk.p.chain != p->chain && h->md.valid) {
+    // another chain length: the slots beyond the old one hold nothing, the barostat's chain starts again at rest
+    const size_t n_chain = h->keep_natoms.size() * ta::kMdMaxChain;
+    const int rc = guarded(h, [&]() {
+      HIP_CHECK(hipStreamSynchronize(h->stream));
+      HIP_CHECK(hipMemset(mtk.xi.ptr, 0, (n_chain + 1) * sizeof(double)));
+      HIP_CHECK(hipMemset(mtk.vxi.ptr, 0, (n_chain + 1) * sizeof(double)));
+    });
+    if (rc != TA_OK) return rc;
+  }
+  mtk.p = *p;
+  mtk.on = true;
+  return TA_OK;
+}
+
+int ta_md_get_mtk_state(ta_handle h, double *omega, double *xi, double *vxi) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int rc = md_mtk_ready(h, "ta_md_get_mtk_state")) return rc;
+  return guarded(h, [&]() {
+    const size_t F = h->keep_natoms.size(), M = (size_t)h->md.mtk.p.chain;
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (omega && F) HIP_CHECK(hipMemcpy(omega, h->md.mtk.omega.ptr, 3 * F * sizeof(double), hipMemcpyDeviceToHost));
+    std::vector<double> buf(F * ta::kMdMaxChain);
+    for (int w = 0; w < 2; ++w) {
+      double *out = w ? vxi : xi;
+      if (!out || !F) continue;
+      HIP_CHECK(hipMemcpy(buf.data(), w ? h->md.mtk.vxi.ptr : h->md.mtk.xi.ptr, buf.size() * sizeof(double),
+                          hipMemcpyDeviceToHost));
+      for (size_t f = 0; f < F; ++f)
+        for (size_t k = 0; k < M; ++k) out[f * M + k] = buf[f * ta::kMdMaxChain + k];
+    }
+  });
+}
+
+int ta_md_set_mtk_state(ta_handle h, const double *omega, const double *xi, const double *vxi) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int rc = md_mtk_ready(h, "ta_md_set_mtk_state")) return rc;
+  const size_t F = h->keep_natoms.size(), M = (size_t)h->md.mtk.p.chain;
+  for (size_t j = 0; omega && j < 3 * F; ++j)
+    if (!std::isfinite(omega[j])) return fail(h, TA_ERR_INVALID, "ta_md_set_mtk_state: non-finite omega");
+  for (size_t j = 0; j < F * M; ++j) {
+    if (xi && !std::isfinite(xi[j])) return fail(h, TA_ERR_INVALID, "ta_md_set_mtk_state: non-finite xi");
+    if (vxi && !std::isfinite(vxi[j])) return fail(h, TA_ERR_INVALID, "ta_md_set_mtk_state: non-finite vxi");
+  }
+  return guarded(h, [&]() {
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    std::vector<double> buf(std::max<size_t>(3 * F, F * ta::kMdMaxChain) + 1, 0.0);
+    if (omega) std::copy(omega, omega + 3 * F, buf.begin());
+    HIP_CHECK(hipMemcpy(h->md.mtk.omega.ptr, buf.data(), (3 * F + 1) * sizeof(double), hipMemcpyHostToDevice));
+    for (int w = 0; w < 2; ++w) {
+      const double *in = w ? vxi : xi;
+      std::fill(buf.begin(), buf.end(), 0.0);
+      if (in)
+        for (size_t f = 0; f < F; ++f)
+          for (size_t k = 0; k < M; ++k) buf[f * ta::kMdMaxChain + k] = in[f * M + k];
+      HIP_CHECK(hipMemcpy(w ? h->md.mtk.vxi.ptr : h->md.mtk.xi.ptr, buf.data(), (F * ta::kMdMaxChain + 1) * sizeof(double),
+                          hipMemcpyHostToDevice));
+    }
+  });
+}
+
+int ta_md_get_mtk_records(ta_handle h, double *e_baro) {
+  if (!h) return TA_ERR_INVALID;
+  if (const int rc = md_resident(h, "ta_md_get_mtk_records")) return rc;
+  if (!h->md.mtk.rec_valid)
+    return fail(h, TA_ERR_INVALID, "ta_md_get_mtk_records: the last ta_md_run of this batch had no Martyna-Tobias-Klein barostat");
+  const std::vector<double> &rec = h->md.mtk.rec_host;
+  if (e_baro && !rec.empty()) std::memcpy(e_baro, rec.data(), rec.size() * sizeof(double));
+  return TA_OK;
+}
+
 int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t record_every, double *epot,
               double *ekin, int32_t *n_rebuilds) {
   if (!h) return TA_ERR_INVALID;
   if (const int bad = md_run_refusals(h, n_steps, dt, record_every)) return bad;
   MdState &md = h->md;
   ResidentLoop &res = h->res;
-  const bool baro = md.baro.on, nhc = md.nhc.on;
+  const bool baro = md.moves_cells(), nhc = md.nhc.on;
   if (n_rebuilds) *n_rebuilds = 0;
   want |= TA_WANT_ENERGY | TA_WANT_FORCES;
   want &= ~(uint32_t)TA_WANT_REUSE_DESCRIPTORS;
   if (baro) want |= TA_WANT_VIRIAL;  // the pressure
   md.baro.rec_valid = false;
   md.nhc.rec_valid = false;
+  md.mtk.rec_valid = false;
   for_each_sampler(md, [&](MdSampler &x) { x.begin_run(!h->keep_species.empty()); });
   res.cell_running = md.baro.running = baro;
   const int rc = guarded(h, [&]() {
@@ -1365,6 +1506,7 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
     md.epot.ensure(n_rec * F + 1);
     md.ke.ensure(n_rec * (size_t)res.n_blk + 1);
     if (nhc) md.nhc.rec.ensure(n_rec * F + 1);
+    if (md.mtk.on) md.mtk.rec.ensure(n_rec * F + 1);
     const std::vector<double> cells_at_entry(baro ? h->ref_cells : std::vector<double>());
     if (baro) {  // every run starts on a list built for the resident cells: the cumulative scale is 1
       md.baro.rec.ensure(4 * n_rec * F + 1);
@@ -1377,6 +1519,7 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
 
     const int64_t step0 = md.step;  // absolute index of this run's first step
     auto integrator = md_launch(h, dt, chunk);
+    const auto mtk = md_mtk_launch(h);
     auto order = md_launch(h, md.order);
     auto cluster = md_launch(h, md.cluster);
     auto cna = md_launch(h, md.cna);
@@ -1393,7 +1536,7 @@ int ta_md_run(ta_handle h, int32_t n_steps, double dt, uint32_t want, int32_t re
       md_enqueue(h, md.adf, adf, step0, k);
       md_enqueue(h, md.rdf, rdf, step0, k);
       const MdSnapshot snap = md_snapshot(md.corr, md.sq, md.flux, N, step0, k);
-      md_enqueue(h, integrator, threads, step0, k, drift, record_every, snap);
+      md_enqueue(h, integrator, mtk, threads, step0, k, drift, record_every, snap);
       md_enqueue(h, md.corr, corr, step0, k, snap);
       md_enqueue(h, md.sq, sq, step0, k, snap);
       md_enqueue(h, md.flux, flux, step0, k, snap);

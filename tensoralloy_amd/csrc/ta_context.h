@@ -205,6 +205,18 @@ struct MdState {
     bool rec_valid = false;
     std::vector<double> rec_volume, rec_press;
   } baro;
+  // Martyna-Tobias-Klein barostat (ta_md_set_mtk_barostat): the strain rates [F][3] and the barostat's chain
+  // [F][TA_MD_MAX_CHAIN] (zeroed by ta_md_init), the record of E_baro of the running ta_md_run and the host's copy
+  // [n_rec][F] of the last successful run's. While it runs it uses what `baro` keeps for a run that moves the cells:
+  // scale, ones, rec {V, P_c}, rec_volume, rec_press and `running`
+  struct {
+    bool on = false;
+    ta_md_mtk_params p = {0.0, 0.0, 3, 1, {1, 1, 1}, 1};
+    DevBuf<double> omega, xi, vxi, rec;
+    bool rec_valid = false;
+    std::vector<double> rec_host;
+  } mtk;
+  bool moves_cells() const { return baro.on || mtk.on; }  // a barostat is on: ta_md_run moves the cells
   // Sampling (ta_md_set_sampling): the rings [L][N][3], the accumulators [2][F][E][L] (v . v, then |dx|^2), the
   // correlation launch's partials; its layout is in chunks of kMdCorrChunk ring doubles
   struct Corr : MdSampler {

@@ -63,7 +63,21 @@ struct MdLaunch {
   double *snap_x, *snap_v;
 };
 
-constexpr int kMdCorrChunk = 768;   // ring doubles (256 atoms x 3) per workgroup of the correlation launch
+// What the Martyna-Tobias-Klein launch (ta_md_mtk.hip) takes beside an MdLaunch with baro = nhc = 1 and every
+// workgroup a whole frame (n_blk = n_frames): the strain rates, the barostat's chain and the record of E_baro, the
+// target pressure, kT0 taup^2 (Q'_k for k >= 2; Q'_1 = d_b Q'_k, W_c = (g + 3) Q'_k / 3), chain length and loops of
+// a half-update of the barostat's chain, and the free axes (read unless iso). MdLaunch's baro_p0, baro_k, baro_iso
+// and baro_mask are not read.
+struct MdMtkLaunch {
+  double *omega;      // [F][3]
+  double *xi, *vxi;   // [F][kMdMaxChain]
+  double *rec;        // [n_rec][F]
+  double p0, q;
+  int chain, loops, iso;
+  int mask[3];
+};
+
+constexpr int kMdCorrChunk = 768;  // ring doubles (256 atoms x 3) per workgroup of the correlation launch
 constexpr int kMdCorrLagTile = 8;   // lags per workgroup of the correlation launch
 
 // Arguments of the correlation launch (ta_md_corr.hip) that ta_md_run puts behind an integrator launch that
@@ -290,6 +304,8 @@ struct MdFluxLaunch {
 struct DeviceBatch;
 
 void launch_md_integrate(const MdLaunch &a, int threads, hipStream_t s);
+
+void launch_md_mtk(const MdLaunch &a, const MdMtkLaunch &b, hipStream_t s);
 
 void launch_md_flux(const MdFluxLaunch &a, const DeviceBatch &b, hipStream_t s);
 

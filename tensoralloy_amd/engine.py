@@ -37,6 +37,7 @@ class Engine:
         self._relax_cell = False   # `relax_set_cell` is on: `relax_run` moves the cells
         self._md_barostat = False  # `md_set_barostat` is on: `md_run` moves the cells
         self._md_chain = 0         # `md_set_nose_hoover` is on: thermostats per chain
+        self._md_mtk = 0           # `md_set_mtk` is on: thermostats of the barostat's chain; `md_run` moves the cells
         self._md_lags = 0          # `md_set_sampling` is on: snapshots in the ring
         self._md_bins = 0          # `md_set_rdf` is on: bins of the pair distributions
         self._md_adf_bins = 0      # `md_set_adf` is on: bins of the bond-angle distributions
@@ -929,6 +930,50 @@ class Engine:
         null = C.POINTER(C.c_double)()
         self._check(self._lib.ta_md_set_chain(self._handle, *[null if a is None else _lib.as_dp(a) for a in arrays]))
 
+    def md_set_mtk(self, pressure=0.0, pdamp=0.0, chain=3, loops=1, mask=None):
+        """Martyna-Tobias-Klein barostat of `md_run` (`ta_md_set_mtk_barostat`; ASE's `IsotropicMTKNPT` / `MTKNPT`
+        with pdamp, pchain = `chain`, ploop = `loops`; LAMMPS `fix npt`): the isothermal-isobaric ensemble, volume
+        fluctuations included. Target `pressure` (eV / A^3), time constant `pdamp` (ASE time units; <= 0 switches
+        it off, the default), thermostats of the barostat's own chain (1 .. 8), loops per half-update (1 .. 16) and
+        `mask`: None = isotropic, one strain rate from the mean driving force; three flags (x, y, z) = every free
+        axis follows its own pressure, the others keep their length exactly. `md_run` needs the Nose-Hoover chain
+        (`md_set_nose_hoover`) on beside it, whose kT it takes, and the Berendsen barostat off. It stays on across
+        `set_frames`; `md_init` puts it at rest. `md_run` then also returns `ebaro`, and `epot + ekin + echain +
+        ebaro` is conserved."""
+        iso = mask is None
+        m = np.ones(3, dtype=np.int64) if iso else np.asarray(mask)
+        if m.shape != (3,):
+            raise ValueError("md_set_mtk: mask must have three entries (x, y, z)")
+        p = _lib.MdMtkParams(float(pressure), float(pdamp), int(chain), int(loops),
+                             (C.c_int32 * 3)(*[int(bool(v)) for v in m]), 1 if iso else 0)
+        self._check(self._lib.ta_md_set_mtk_barostat(self._handle, C.byref(p)))
+        self._md_mtk = int(chain) if pdamp > 0.0 else 0
+
+    def md_mtk_state(self):
+        """(omega [n_frames, 3], xi, vxi [n_frames, chain]): strain rates and the barostat's chain of every frame
+        as the device holds them (`ta_md_get_mtk_state`). Needs `md_init` and `md_set_mtk`."""
+        self._need_batch("md_mtk_state")
+        F = int(self.info.n_frames)
+        omega, xi, vxi = np.empty((F, 3)), np.empty((F, max(self._md_mtk, 1))), np.empty((F, max(self._md_mtk, 1)))
+        self._check(self._lib.ta_md_get_mtk_state(self._handle, _lib.as_dp(omega), _lib.as_dp(xi), _lib.as_dp(vxi)))
+        return omega, xi, vxi
+
+    def md_set_mtk_state(self, omega=None, xi=None, vxi=None):
+        """Restart: hand the barostat the (omega, xi, vxi) of an earlier `md_mtk_state` (None = zeros), after
+        `set_frames` + `md_init` + `md_set_chain` with the state of that moment (`ta_md_set_mtk_state`)."""
+        self._need_batch("md_set_mtk_state")
+        F = int(self.info.n_frames)
+        arrays = []
+        for name, a, n in (("omega [n_frames, 3]", omega, 3 * F), ("xi [n_frames, chain]", xi, F * max(self._md_mtk, 1)),
+                           ("vxi [n_frames, chain]", vxi, F * max(self._md_mtk, 1))):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.size != n:
+                    raise ValueError(f"md_set_mtk_state: {name} for every frame of the resident batch is needed")
+            arrays.append(a)
+        null = C.POINTER(C.c_double)()
+        self._check(self._lib.ta_md_set_mtk_state(self._handle, *[null if a is None else _lib.as_dp(a) for a in arrays]))
+
     def md_cells(self):
         """Cells [n_frames, 3, 3] of the resident batch as the library holds them (`ta_md_get_cell`)."""
         self._need_batch("md_cells")
@@ -955,7 +1000,9 @@ class Engine:
         cells ends with one list build for the final cells (counted in `n_rebuilds`).
         With `md_set_nose_hoover` on, the dict also holds `echain` [n_rec, n_frames], every record after the
         first is the state after the closing half-update of its step, and `epot + ekin + echain` is the
-        conserved quantity."""
+        conserved quantity.
+        With `md_set_mtk` on, the dict holds `volume` and `press` as under the Berendsen barostat and `ebaro`
+        [n_rec, n_frames], and `epot + ekin + echain + ebaro` is the conserved quantity."""
         self._need_batch("md_run")
         n_steps, record_every = int(n_steps), int(record_every)
         if n_steps < 0 or record_every < 1:
@@ -978,7 +1025,10 @@ class Engine:
         if self._md_chain:   # the chain terms of the conserved quantity, at the slots of epot / ekin
             out["echain"] = np.empty((n_rec, F))
             self._check(self._lib.ta_md_get_chain_records(self._handle, _lib.as_dp(out["echain"])))
-        if self._md_barostat:   # the cells moved on the device: stress and pressure follow them
+        if self._md_mtk:   # the barostat's terms of the conserved quantity
+            out["ebaro"] = np.empty((n_rec, F))
+            self._check(self._lib.ta_md_get_mtk_records(self._handle, _lib.as_dp(out["ebaro"])))
+        if self._md_barostat or self._md_mtk:   # the cells moved on the device: stress and pressure follow them
             out["volume"], out["press"] = self.md_records(n_rec)
             self._volumes = np.abs(np.linalg.det(self.md_cells()))
             self._md_sig = None

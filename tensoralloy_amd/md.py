@@ -34,6 +34,22 @@ settings. The scaling factor is computed inside the integrator launch from the f
 positions, one force evaluation per step (what ASE does when forces are handed to its `step`). `GPa` and `bar`
 are the same numbers as `ase.units.GPa` and `ase.units.bar`.
 
+The isothermal-isobaric ensemble: with `pressure` and `pdamp` (names as ASE's `IsotropicMTKNPT`: `pdamp`, `pchain`,
+`ploop`; LAMMPS `fix npt`) the cells follow a Martyna-Tobias-Klein barostat instead, coupled to the Nose-Hoover chain
+(`temperature_K`, `tdamp`, which it needs) and to a chain of `pchain` thermostats of its own. Where the Berendsen
+barostat relaxes a cell towards a pressure and suppresses its fluctuations, this one samples the ensemble: thermal
+expansion, densities, coexistence and, from <dV^2>, the compressibility (`isothermal_compressibility`) come out
+right. Without a `mask` one strain rate follows the mean driving force; with one, every free axis has its own rate
+and a masked axis keeps its length exactly. State per frame: the strain rates omega_c and the chain (xi_k, vxi_k);
+masses W_c = (g + 3) kT pdamp^2 / 3, Q'_1 = d_b kT pdamp^2, Q'_k = kT pdamp^2 with d_b = 1 (isotropic) or the
+number of free axes. A step is: the two chains' half-updates, a half-kick of omega by
+G_c = [sum m v_c^2 - W_cc - P0 V + 2 ekin / g] / W_c, the velocities scaled by exp(-(dt/2) (omega_c + tr omega / g))
+and kicked, x_c <- exp(omega_c dt) x_c + dt exp(omega_c dt / 2) v_c with the cell's column scaled likewise, the
+evaluation, and the same in reverse; it is written out in include/tensoralloy_amd.h. The conserved quantity gains
+    ebaro = P0 V + sum_c W_c omega_c^2 / 2 + sum_k Q'_k vxi_k^2 / 2 + d_b kT xi_1 + kT sum_{k>=2} xi_k
+which `get_conserved_energy()` includes. To restart, keep `Engine.md_mtk_state()` and `Engine.md_cells()` beside the
+state and the chain, and hand them to `set_frames` / `md_init`, `md_set_chain` and `Engine.md_set_mtk_state`.
+
 Time correlations: with `n_lags` (and `sample_every`) the loop itself keeps the last `n_lags` sampled
 whole-step states in a ring on the device and, at every sample, adds the velocity autocorrelation
 <v(t0 + k) . v(t0)> and the mean-square displacement <|x(t0 + k) - x(t0)|^2> at all lags k, per frame and per
@@ -132,6 +148,18 @@ def maxwell_boltzmann(masses, kT, rng, zero_momentum=True):
     if zero_momentum and len(m):
         v -= (m[:, None] * v).sum(axis=0) / m.sum()
     return v
+
+
+def isothermal_compressibility(volumes, temperature_K):
+    """<dV^2> / (kB T <V>) in A^3 / eV from the volumes [n] of one frame along a run in the isothermal-isobaric
+    ensemble (`pdamp`; the Berendsen barostat suppresses these fluctuations and gives no such number)."""
+    V = np.asarray(volumes, dtype=np.float64)
+    if V.ndim != 1 or len(V) < 2:
+        raise ValueError("isothermal_compressibility: the volumes [n] of one frame, n >= 2, are needed")
+    if not (np.isfinite(temperature_K) and temperature_K > 0.0):
+        raise ValueError("isothermal_compressibility: temperature_K must be finite and > 0")
+    mean = V.mean()
+    return float(((V - mean) ** 2).mean() / (kB * temperature_K * mean))
 
 
 def _trapezoid(y, dx):
@@ -592,6 +620,10 @@ class DeviceMD:
                            `1.0 * GPa`), time constant (> 0) and compressibility (A^3 / eV, >= 0), with any
                            thermostat setting; every frame must be periodic along all three axes
     mask                 : None = isotropic; three flags (x, y, z) = each free axis follows its own pressure
+    pressure, pdamp      : both given, with `temperature_K` and `tdamp`: Martyna-Tobias-Klein barostat with that
+                           target and time constant (> 0, e.g. `1000 * fs`); excludes `taup` and `compressibility`;
+                           `mask` as above; every frame must be periodic along all three axes
+    pchain, ploop        : thermostats of the barostat's chain (1 .. 8) and loops per half-update (1 .. 16)
     n_lags, sample_every : `n_lags` given (1 .. 4096): the loop samples every `sample_every`-th step (the state at
                            construction is the first sample) and accumulates the velocity autocorrelation and
                            the mean-square displacement at `n_lags` lags on the device (`get_vacf`, `get_msd`,
@@ -658,7 +690,8 @@ class DeviceMD:
 
     def __init__(self, engine_or_calculator, atoms_or_list, timestep, temperature_K=None, taut=None,
                  velocities=None, masses=None, friction=None, seed=0, pressure=None, taup=None,
-                 compressibility=None, mask=None, tdamp=None, tchain=3, tloop=1, dof_removed=0, n_lags=None,
+                 compressibility=None, mask=None, tdamp=None, tchain=3, tloop=1, dof_removed=0, pdamp=None, pchain=3,
+                 ploop=1, n_lags=None,
                  sample_every=1, rdf_bins=None, rdf_rmax=None, rdf_every=1, adf_bins=None, adf_rbond=None,
                  adf_every=1, order_degrees=None, order_rbond=None, order_bins=None, order_every=1, order_solid=None,
                  sq_miller=None, sq_lags=None, sq_every=1, sq_currents=False, cluster_bins=None, cluster_rlink=None,
@@ -666,7 +699,11 @@ class DeviceMD:
                  cna_rmax=None, cna_series=1, cna_every=1, flux_lags=None, flux_every=1):
         if not (np.isfinite(timestep) and timestep > 0.0):
             raise ValueError("DeviceMD: timestep must be a finite time > 0")
-        barostat = (pressure, taup, compressibility)
+        self._mtk = pdamp is not None
+        if self._mtk and taup is not None:
+            raise ValueError("DeviceMD: pdamp (Martyna-Tobias-Klein barostat) and taup (Berendsen barostat) exclude each "
+                             "other: only one barostat at a time")
+        barostat = (pressure, pdamp) if self._mtk else (pressure, taup, compressibility)
         self._barostat = any(p is not None for p in barostat)
         if n_lags is not None:
             whole = lambda a: isinstance(a, (int, np.integer)) and not isinstance(a, bool)
@@ -808,7 +845,23 @@ class DeviceMD:
                                  "(pressure, taup, compressibility): normalising the correlations needs one volume")
         elif flux_every != 1:
             raise ValueError("DeviceMD: flux_every belongs to the heat current and pressure tensor (flux_lags)")
-        if self._barostat:
+        if self._mtk:
+            if pressure is None or tdamp is None:
+                raise ValueError("DeviceMD: the Martyna-Tobias-Klein barostat needs pressure with pdamp, and the Nose-Hoover "
+                                 "chain thermostat (temperature_K, tdamp), whose temperature it takes")
+            if compressibility is not None:
+                raise ValueError("DeviceMD: compressibility belongs to the Berendsen barostat (taup), not to pdamp")
+            if not np.isfinite(pressure):
+                raise ValueError("DeviceMD: pressure must be finite")
+            if not (np.isfinite(pdamp) and pdamp > 0.0):
+                raise ValueError("DeviceMD: pdamp must be a finite time > 0")
+            if not 1 <= int(pchain) <= 8:
+                raise ValueError("DeviceMD: pchain must be 1 .. 8")
+            if not 1 <= int(ploop) <= 16:
+                raise ValueError("DeviceMD: ploop must be 1 .. 16")
+            if mask is not None and (np.shape(mask) != (3,) or not np.any(mask)):
+                raise ValueError("DeviceMD: mask must have three flags (x, y, z), at least one of them set")
+        elif self._barostat:
             if any(p is None for p in barostat):
                 raise ValueError("DeviceMD: the barostat needs pressure, taup and compressibility")
             if not np.isfinite(pressure):
@@ -897,10 +950,16 @@ class DeviceMD:
             engine.md_set_langevin(0.0, 0.0, 0)
             engine.md_set_thermostat(kB * temperature_K if temperature_K is not None else 0.0,
                                      taut if taut is not None else 0.0)
-        if self._barostat:
-            engine.md_set_barostat(pressure, taup, compressibility, mask)
-        else:
+        if self._mtk:   # (one barostat at a time: the other goes off first)
             engine.md_set_barostat(0.0, 0.0, 0.0)
+            engine.md_set_mtk(pressure, pdamp, int(pchain), int(ploop), mask)
+        else:
+            if getattr(engine, "_md_mtk", 0):   # (an earlier DeviceMD left it on)
+                engine.md_set_mtk(0.0, 0.0)
+            if self._barostat:
+                engine.md_set_barostat(pressure, taup, compressibility, mask)
+            else:
+                engine.md_set_barostat(0.0, 0.0, 0.0)
         self._lags = int(n_lags) if n_lags is not None else 0
         self._sample_every = int(sample_every)
         engine.md_set_sampling(self._lags, self._sample_every)   # (state 0 is the first sample)
@@ -951,6 +1010,7 @@ class DeviceMD:
         self.velocities = velocities.copy()
         self.epot = self.ekin = None   # per-frame records of the last state
         self.echain = None   # ... under the Nose-Hoover chain: the chain terms of the conserved quantity
+        self.ebaro = None    # ... under the Martyna-Tobias-Klein barostat: its terms of the conserved quantity
         self.volume = self.press = None   # ... under the barostat: V [n_frames] and P_c [n_frames, 3]
         self.n_rebuilds = 0
         self._refresh(engine.md_run(0, self.dt))
@@ -966,6 +1026,8 @@ class DeviceMD:
         self.n_rebuilds += out["n_rebuilds"]
         if self._chain:
             self.echain = out["echain"][-1].copy()
+        if self._mtk:
+            self.ebaro = out["ebaro"][-1].copy()
         x, v = self.engine.md_state()
         self.velocities = v
         a = 0
@@ -1007,11 +1069,14 @@ class DeviceMD:
         return float(self.ekin[0]) if self._single else self.ekin.copy()
 
     def get_conserved_energy(self):
-        """ekin + epot + the chain terms per frame: the conserved quantity of the Nose-Hoover chain dynamics.
-        Needs the Nose-Hoover chain thermostat."""
+        """ekin + epot + the chain terms per frame: the conserved quantity of the Nose-Hoover chain dynamics; with
+        `pdamp`, + the barostat's terms (`ebaro`): that of the Martyna-Tobias-Klein dynamics. Needs the Nose-Hoover
+        chain thermostat."""
         if self.echain is None:
             raise ValueError("DeviceMD.get_conserved_energy: the Nose-Hoover chain thermostat is off (temperature_K, tdamp)")
         e = self.ekin + self.epot + self.echain
+        if self._mtk:
+            e = e + self.ebaro
         return float(e[0]) if self._single else e
 
     def _correlation(self, who, key):
