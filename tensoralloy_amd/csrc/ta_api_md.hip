@@ -77,10 +77,17 @@ bool md_alloc_layout(ta_context *h, S &x, int64_t every, int per_atom, int chunk
   return true;
 }
 
-// the neighbour-list view of launch `k` of a run, for any launch struct that reads the resident list: the state and the
-// (skin) list of the batch, not the exact one filtered from it (a rebuild may have moved them: taken at every launch)
-template <typename L>
-void point_at_list(const ta_context *h, L &l, int k) {
+// the part of a launch's list view that is fixed for a ta_md_run: the predicate's word and the plan of sampler x
+void md_fixed_list(const ta_context *h, const MdSampler &x, ta::MdList &l) {
+  l.blk_start = x.blk.ptr;
+  l.status = h->res.status.ptr;
+  l.n_elements = h->n_elements, l.n_frames = (int)h->keep_natoms.size();
+  l.n_blk = x.n_blk, l.chunk = x.chunk;
+}
+
+// the neighbour-list view of launch `k` of a run: the state and the (skin) list of the batch, not the exact one filtered
+// from it (a rebuild may have moved them: taken at every launch)
+void point_at_list(const ta_context *h, ta::MdList &l, int k) {
   l.pos = h->db.pos;
   l.cells = h->db.cells;
   l.species = h->db.species;
@@ -158,9 +165,8 @@ bool md_alloc(ta_context *h, MdState::Rdf &g, const MdState::Rdf::Setting &s) {
 }
 ta::MdRdfLaunch md_launch(const ta_context *h, const MdState::Rdf &x) {
   ta::MdRdfLaunch g;
-  g.blk_start = x.blk.ptr, g.counts = x.acc.ptr, g.status = h->res.status.ptr;
-  g.n_bins = x.set.p.n_bins, g.n_elements = h->n_elements, g.n_frames = (int)h->keep_natoms.size();
-  g.n_blk = x.n_blk, g.chunk = x.chunk;
+  md_fixed_list(h, x, g.list);
+  g.counts = x.acc.ptr, g.n_bins = x.set.p.n_bins;
   g.dr = x.run ? x.set.p.r_max / (double)x.set.p.n_bins : 1.0;
   return g;
 }
@@ -169,7 +175,7 @@ ta::MdRdfLaunch md_launch(const ta_context *h, const MdState::Rdf &x) {
 // list; after the rebuild the launch is enqueued again with the rest and counts then.
 void md_enqueue(const ta_context *h, const MdState::Rdf &x, ta::MdRdfLaunch &g, int64_t step0, int k) {
   if (!md_due(x, step0, k)) return;
-  point_at_list(h, g, k);
+  point_at_list(h, g.list, k);
   g.pair_i = h->pair_i.ptr;
   ta::launch_md_rdf(g, h->stream);
   HIP_CHECK(hipGetLastError());
@@ -189,9 +195,8 @@ bool md_alloc(ta_context *h, MdState::Adf &g, const MdState::Adf::Setting &s) {
 }
 ta::MdAdfLaunch md_launch(const ta_context *h, const MdState::Adf &x) {
   ta::MdAdfLaunch t;
-  t.blk_start = x.blk.ptr, t.rb2 = x.rb2.ptr, t.counts = x.acc.ptr, t.status = h->res.status.ptr;
-  t.n_bins = x.set.p.n_bins, t.n_elements = h->n_elements, t.n_frames = (int)h->keep_natoms.size();
-  t.n_blk = x.n_blk, t.chunk = x.chunk;
+  md_fixed_list(h, x, t.list);
+  t.rb2 = x.rb2.ptr, t.counts = x.acc.ptr, t.n_bins = x.set.p.n_bins;
   t.dtheta = x.run ? M_PI / (double)x.set.p.n_bins : 1.0;
   return t;
 }
@@ -199,7 +204,7 @@ ta::MdAdfLaunch md_launch(const ta_context *h, const MdState::Adf &x) {
 // predicate (no volume enters, so they run under the barostat too: db.cells are those of the state t)
 void md_enqueue(const ta_context *h, const MdState::Adf &x, ta::MdAdfLaunch &t, int64_t step0, int k) {
   if (!md_due(x, step0, k)) return;
-  point_at_list(h, t, k);
+  point_at_list(h, t.list, k);
   ta::launch_md_adf(t, h->stream);
   HIP_CHECK(hipGetLastError());
 }
@@ -239,13 +244,13 @@ ta::MdOrderLaunch md_launch(const ta_context *h, const MdState::Order &x) {
   const size_t N = h->keep_species.size(), F = h->keep_natoms.size(), E = (size_t)h->n_elements;
   const auto &p = x.set.p;
   ta::MdOrderLaunch o;
-  o.blk_start = x.blk.ptr, o.rb2 = x.rb2.ptr, o.norm = x.norm.ptr, o.qlm = x.qlm.ptr, o.status = h->res.status.ptr;
+  md_fixed_list(h, x, o.list);
+  o.rb2 = x.rb2.ptr, o.norm = x.norm.ptr, o.qlm = x.qlm.ptr;
   o.q = x.q(), o.qbar = x.run ? x.qbar(N) : nullptr;
   o.n_bonds = x.n_bonds(), o.n_conn = x.run ? x.n_conn(N) : nullptr;
   o.hist_q = x.hist_q();
   o.hist_qbar = x.run ? x.hist_qbar(F, E) : nullptr, o.hist_conn = x.run ? x.hist_conn(F, E) : nullptr;
-  o.n_bins = p.n_bins, o.n_elements = h->n_elements, o.n_frames = (int)F;
-  o.n_blk = x.n_blk, o.chunk = x.chunk;
+  o.n_bins = p.n_bins;
   o.n_degrees = p.n_degrees, o.n_lm = x.n_lm, o.solid = x.solid;
   o.deg0 = p.degrees[0], o.deg1 = p.degrees[1], o.deg2 = p.degrees[2], o.deg3 = p.degrees[3];
   o.threshold = p.solid_threshold;
@@ -255,7 +260,7 @@ ta::MdOrderLaunch md_launch(const ta_context *h, const MdState::Order &x) {
 // (no volume either)
 void md_enqueue(const ta_context *h, const MdState::Order &x, ta::MdOrderLaunch &o, int64_t step0, int k) {
   if (!md_due(x, step0, k)) return;
-  point_at_list(h, o, k);
+  point_at_list(h, o.list, k);
   ta::launch_md_order(o, h->stream);
   HIP_CHECK(hipGetLastError());
 }
@@ -282,13 +287,13 @@ bool md_alloc(ta_context *h, MdState::Cluster &g, const MdState::Cluster::Settin
 ta::MdClusterLaunch md_launch(const ta_context *h, const MdState::Cluster &x) {
   const size_t N = h->keep_species.size();
   ta::MdClusterLaunch cl;
-  cl.blk_start = x.blk.ptr, cl.rl2 = x.rl2.ptr, cl.hist = x.acc.ptr, cl.giveup = x.giveup.ptr, cl.status = h->res.status.ptr;
+  md_fixed_list(h, x, cl.list);
+  cl.rl2 = x.rl2.ptr, cl.hist = x.acc.ptr, cl.giveup = x.giveup.ptr;
   cl.n_conn = x.run && x.set.p.n_min > 0 ? h->md.order.n_conn(N) : nullptr;
   cl.parent = x.parent(), cl.count = x.run ? x.count(N) : nullptr;
   cl.label = x.run ? x.label(N) : nullptr, cl.size = x.run ? x.size(N) : nullptr;
   cl.n_atoms = (long long)N;
-  cl.n_bins = x.set.p.n_bins, cl.n_elements = h->n_elements, cl.n_frames = (int)h->keep_natoms.size();
-  cl.n_blk = x.n_blk, cl.chunk = x.chunk;
+  cl.n_bins = x.set.p.n_bins;
   cl.n_min = x.set.p.n_min, cl.species_mask = x.set.p.species_mask;
   return cl;
 }
@@ -296,7 +301,7 @@ ta::MdClusterLaunch md_launch(const ta_context *h, const MdState::Cluster &x) {
 // reads their n_conn), under the same predicate (no volume either)
 void md_enqueue(const ta_context *h, const MdState::Cluster &x, ta::MdClusterLaunch &cl, int64_t step0, int k) {
   if (!md_due(x, step0, k)) return;
-  point_at_list(h, cl, k);
+  point_at_list(h, cl.list, k);
   cl.row = x.series_row(x.sched.index(step0 + k), h->keep_natoms.size());
   ta::launch_md_cluster(cl, h->stream);
   HIP_CHECK(hipGetLastError());
@@ -323,10 +328,8 @@ ta::MdCnaLaunch md_launch(const ta_context *h, const MdState::Cna &x) {
   const auto &p = x.set.p;
   const double r = p.mode == TA_MD_CNA_FIXED ? p.r_cut : p.r_max;
   ta::MdCnaLaunch cn;
-  cn.blk_start = x.blk.ptr, cn.structure = x.structure.ptr, cn.r_local = x.r_local.ptr;
-  cn.counts = x.acc.ptr, cn.status = h->res.status.ptr;
-  cn.n_elements = h->n_elements, cn.n_frames = (int)h->keep_natoms.size();
-  cn.n_blk = x.n_blk, cn.chunk = x.chunk;
+  md_fixed_list(h, x, cn.list);
+  cn.structure = x.structure.ptr, cn.r_local = x.r_local.ptr, cn.counts = x.acc.ptr;
   cn.mode = p.mode, cn.r_cut = p.r_cut, cn.r2 = r * r;
   return cn;
 }
@@ -335,7 +338,7 @@ ta::MdCnaLaunch md_launch(const ta_context *h, const MdState::Cna &x) {
 // zeroes
 void md_enqueue(const ta_context *h, const MdState::Cna &x, ta::MdCnaLaunch &cn, int64_t step0, int k) {
   if (!md_due(x, step0, k)) return;
-  point_at_list(h, cn, k);
+  point_at_list(h, cn.list, k);
   cn.row = x.series_row(x.sched.index(step0 + k), h->keep_natoms.size());
   ta::launch_md_cna(cn, h->stream);
   HIP_CHECK(hipGetLastError());

@@ -96,6 +96,24 @@ struct MdCorrLaunch {
   int n_lags, n_elements, n_frames, n_chunks;
 };
 
+// What every launch that sweeps the resident (skin) list takes, as the first member `list` of its arguments: the
+// whole-step state and the list (taken at every launch: a rebuild may have moved them), the integrator's predicate,
+// and the launch's plan of `chunk` consecutive centres of one frame per workgroup (fixed for a run). The device
+// functions on it are in ta_md_sweep.h.
+struct MdList {
+  const double *pos;              // [N][3] db.pos
+  const double *cells;            // [F][9]
+  const int32_t *species;         // [N]
+  const int32_t *atom_start;      // [F + 1]
+  const int32_t *blk_start;       // [F + 1] first workgroup of each frame (at least one each)
+  const int32_t *pair_start;      // [N + 1] the resident list: centre i owns pair_start[i] .. pair_start[i + 1] - 1
+  const int32_t *pair_j;          // [P]
+  const int32_t *pair_shift;      // [P][3]
+  const unsigned *status;         // the integrator's status word and
+  unsigned seq;                   // sequence number: the same predicate
+  int n_elements, n_frames, n_blk, chunk;
+};
+
 constexpr int kMdRdfLdsWords = 8192;  // most 32-bit bins of the pair-distribution launch's LDS histogram (32 KB)
 
 // Centres per workgroup of the pair-distribution launch for a batch of n_atoms: small batches spread over the
@@ -105,18 +123,10 @@ inline int md_rdf_chunk(long long n_atoms) { return n_atoms <= 16384 ? 8 : 64; }
 // Arguments of the pair-distribution launch (ta_md_rdf.hip) that ta_md_run puts in front of the integrator
 // launch of a sampled step: the resident (skin) list, the positions and cells of that whole-step state.
 struct MdRdfLaunch {
-  const double *pos;              // [N][3] db.pos
-  const double *cells;            // [F][9]
-  const int32_t *species;         // [N]
-  const int32_t *atom_start;      // [F + 1]
-  const int32_t *blk_start;       // [F + 1] first workgroup of each frame (at least one each)
-  const int32_t *pair_start;      // [N + 1] the resident list: centre i owns pair_start[i] .. pair_start[i + 1] - 1
-  const int32_t *pair_i, *pair_j; // [P]
-  const int32_t *pair_shift;      // [P][3]
+  MdList list;
+  const int32_t *pair_i;          // [P] the centre of every pair
   unsigned long long *counts;     // [F][E][E][n_bins] the accumulators
-  const unsigned *status;         // the integrator's status word and
-  unsigned seq;                   // sequence number: the same predicate
-  int n_bins, n_elements, n_frames, n_blk, chunk;
+  int n_bins;
   double dr;                      // r_max / n_bins
 };
 
@@ -131,19 +141,10 @@ inline int md_adf_chunk(long long n_atoms) { return n_atoms <= 16384 ? 8 : 64; }
 // Arguments of the bond-angle launch (ta_md_adf.hip) that ta_md_run puts in front of the integrator launch of a
 // sampled step: the resident (skin) list, the positions and cells of that whole-step state.
 struct MdAdfLaunch {
-  const double *pos;              // [N][3] db.pos
-  const double *cells;            // [F][9]
-  const int32_t *species;         // [N]
-  const int32_t *atom_start;      // [F + 1]
-  const int32_t *blk_start;       // [F + 1] first workgroup of each frame (at least one each)
-  const int32_t *pair_start;      // [N + 1] the resident list: centre i owns pair_start[i] .. pair_start[i + 1] - 1
-  const int32_t *pair_j;          // [P]
-  const int32_t *pair_shift;      // [P][3]
+  MdList list;
   const double *rb2;              // [E][E] squares of the bond cutoffs
   unsigned long long *counts;     // [F][E][E (E + 1) / 2][n_bins] the accumulators
-  const unsigned *status;         // the integrator's status word and
-  unsigned seq;                   // sequence number: the same predicate
-  int n_bins, n_elements, n_frames, n_blk, chunk;
+  int n_bins;
   double dtheta;                  // pi / n_bins
 };
 
@@ -164,14 +165,7 @@ inline int md_order_chunk(long long n_atoms) { return n_atoms <= 16384 ? 8 : kMd
 // integrator launch of a sampled step, in stream order: the resident (skin) list, the positions and cells of that
 // whole-step state. Pass 1 writes qlm and n_bonds, pass 2 reads them and writes everything else.
 struct MdOrderLaunch {
-  const double *pos;              // [N][3] db.pos
-  const double *cells;            // [F][9]
-  const int32_t *species;         // [N]
-  const int32_t *atom_start;      // [F + 1]
-  const int32_t *blk_start;       // [F + 1] first workgroup of each frame (at least one each)
-  const int32_t *pair_start;      // [N + 1] the resident list: centre i owns pair_start[i] .. pair_start[i + 1] - 1
-  const int32_t *pair_j;          // [P]
-  const int32_t *pair_shift;      // [P][3]
+  MdList list;
   const double *rb2;              // [E][E] squares of the bond cutoffs
   const double *norm;             // [n_lm] N_lm of every (degree, m >= 0), degree by degree
   double *qlm;                    // [N][n_lm][2] q_lm of the newest sample
@@ -179,10 +173,8 @@ struct MdOrderLaunch {
   int32_t *n_bonds, *n_conn;      // [N]
   unsigned long long *hist_q, *hist_qbar;  // [F][E][n_degrees][n_bins] the accumulators
   unsigned long long *hist_conn;           // [F][E][kMdOrderMaxConn + 1]
-  const unsigned *status;         // the integrator's status word and
-  unsigned seq;                   // sequence number: the same predicate
-  int n_bins, n_elements, n_frames, n_blk, chunk;
-  int n_degrees, n_lm, solid;     // solid: index of solid_degree among the degrees
+  int n_bins;
+  int n_degrees, n_lm, solid;    // solid: index of solid_degree among the degrees
   int deg0, deg1, deg2, deg3;     // the degrees (0 beyond n_degrees)
   double threshold;               // c of the solid-bond test
 };
@@ -194,14 +186,7 @@ constexpr int kMdClusterLdsWords = 4096;  // 32-bit bins of the cluster summary'
 // The link launch has the workgroup layout of the order launches (md_order_chunk); select and flatten take a thread
 // per atom, the summary a workgroup per frame.
 struct MdClusterLaunch {
-  const double *pos;              // [N][3] db.pos
-  const double *cells;            // [F][9]
-  const int32_t *species;         // [N]
-  const int32_t *atom_start;      // [F + 1]
-  const int32_t *blk_start;       // [F + 1] first workgroup of each frame (at least one each)
-  const int32_t *pair_start;      // [N + 1] the resident list: centre i owns pair_start[i] .. pair_start[i + 1] - 1
-  const int32_t *pair_j;          // [P]
-  const int32_t *pair_shift;      // [P][3]
+  MdList list;
   const double *rl2;              // [E][E] squares of the link cutoffs
   const int32_t *n_conn;          // [N] of the order launches for the same state; read when n_min > 0
   int32_t *parent, *count;        // [N] the union-find forest (-1: not selected) and the atoms under every root
@@ -209,10 +194,8 @@ struct MdClusterLaunch {
   unsigned long long *hist;       // [F][n_bins] the accumulator
   long long *row;                 // [F][4] this sample's row of the series
   unsigned *giveup;               // set when a loop overran its cap
-  const unsigned *status;         // the integrator's status word and
-  unsigned seq;                   // sequence number: the same predicate
   long long n_atoms;              // N
-  int n_bins, n_elements, n_frames, n_blk, chunk;
+  int n_bins;
   int n_min, species_mask;
 };
 
@@ -224,21 +207,11 @@ constexpr int kMdCnaAdaptive = 0, kMdCnaFixed = 1;  // TA_MD_CNA_ADAPTIVE, TA_MD
 // a sampled step, behind the order and cluster launches of that step: a launch that zeroes this sample's row of the
 // series and the analysis itself, which has the workgroup layout of the order launches (md_order_chunk).
 struct MdCnaLaunch {
-  const double *pos;              // [N][3] db.pos
-  const double *cells;            // [F][9]
-  const int32_t *species;         // [N]
-  const int32_t *atom_start;      // [F + 1]
-  const int32_t *blk_start;       // [F + 1] first workgroup of each frame (at least one each)
-  const int32_t *pair_start;      // [N + 1] the resident list: centre i owns pair_start[i] .. pair_start[i + 1] - 1
-  const int32_t *pair_j;          // [P]
-  const int32_t *pair_shift;      // [P][3]
+  MdList list;
   int32_t *structure;             // [N] of the newest sample
   double *r_local;                // [N] likewise
   unsigned long long *counts;     // [F][E][kMdCnaTypes] the accumulator
   unsigned long long *row;        // [F][kMdCnaTypes] this sample's row of the series
-  const unsigned *status;         // the integrator's status word and
-  unsigned seq;                   // sequence number: the same predicate
-  int n_elements, n_frames, n_blk, chunk;
   int mode;                       // kMdCnaAdaptive or kMdCnaFixed
   double r2;                      // square of the candidates' reach: r_max (adaptive) or r_cut (fixed)
   double r_cut;                   // fixed mode: the bond cutoff and r_local of every atom

@@ -72,6 +72,7 @@
 #include "ta_math.h"
 #include "ta_md.h"
 #include "ta_md_device.h"
+#include "ta_md_sweep.h"
 
 namespace ta {
 namespace {
@@ -129,18 +130,8 @@ __global__ __launch_bounds__(1024) void md_integrate_kernel(MdLaunch a) {
   __shared__ double s_baro[kBaro ? kBaroWords : 1];  // (unused, and dropped, in the fixed-cell builds)
   __shared__ double s_nhc[kNhc ? kNhcWords : 1];     // (likewise without the chain)
   // (0, or the value this very launch writes, or the mark of an earlier launch: the same branch in every thread)
-  const unsigned mark = *static_cast<volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
-  // frame of this workgroup: the last f with blk_start[f] <= blockIdx.x (every frame has at least one)
-  int f = 0;
-  {
-    int lo = 0, hi = a.n_frames - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (a.blk_start[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    f = lo;
-  }
+  if (md_stale(a.status, a.seq)) return;
+  const int f = md_frame_of(a.blk_start, a.n_frames, (int)blockIdx.x);
   const int blk0 = a.blk_start[f];
   const int64_t f_lo = a.atom_start[f], f_hi = a.atom_start[f + 1];
   const int64_t lo = f_lo + (int64_t)((int)blockIdx.x - blk0) * a.chunk;

@@ -7,11 +7,11 @@
 //     C[f][a][p][kbin] += 1,   p = b E - b (b - 1) / 2 + (c - b) for the species b <= c of the two neighbours
 // A NaN counts nowhere. Nothing is stored per triple.
 //
-// A workgroup of 256 threads (four waves) owns `chunk` consecutive centres of ONE frame and finds its frame in
-// blk_start the way md_rdf_kernel does. ONE WAVE takes one centre at a time and sweeps that centre's run
-// pair_start[i] .. pair_start[i + 1] of the list, 64 entries a round. The neighbours that pass the cutoff are
-// compacted (ballot and prefix count) into the wave's LDS slab (dx, dy, dz, species) of kMdAdfSlab entries; the
-// n (n - 1) / 2 pairs of the slab are then spread evenly over the 64 lanes, whatever n is.
+// A workgroup of 256 threads (four waves) owns `chunk` consecutive centres of ONE frame (md_centres; ta_md_sweep.h
+// holds what the launches on the resident list share). ONE WAVE takes one centre at a time and sweeps that centre's
+// run pair_start[i] .. pair_start[i + 1] of the list, 64 entries a round (md_entry). The neighbours that pass the
+// cutoff are compacted (ballot and prefix count) into the wave's LDS slab (dx, dy, dz, species) of kMdAdfSlab
+// entries; the n (n - 1) / 2 pairs of the slab are then spread evenly over the 64 lanes, whatever n is.
 //
 // A centre with more neighbours than the slab holds is swept in tiles: the slab takes the neighbours of as many
 // whole rounds as fit (block A), the pairs inside A are counted as above, then every later entry of the run is
@@ -35,6 +35,7 @@
 
 #include "ta_device.h"
 #include "ta_md.h"
+#include "ta_md_sweep.h"
 
 namespace ta {
 namespace {
@@ -53,16 +54,8 @@ static_assert(kMdAdfSlab >= 64 && kMdAdfSlab % 64 == 0, "an empty slab takes one
 static_assert(kMaxElements * (kMaxElements * (kMaxElements + 1) / 2) <= kMdAdfLdsWords, "at least one bin per pass");
 
 __device__ __forceinline__ void pin_args(const MdAdfLaunch &a) {
-  asm volatile("" ::"s"(a.pos), "s"(a.cells), "s"(a.species), "s"(a.atom_start), "s"(a.blk_start), "s"(a.pair_start),
-               "s"(a.pair_j), "s"(a.pair_shift), "s"(a.rb2), "s"(a.counts), "s"(a.status), "s"(a.seq), "s"(a.n_bins),
-               "s"(a.n_elements), "s"(a.n_frames), "s"(a.chunk), "s"(a.dtheta));
-}
-
-// what a wave wrote to its slab is read by its other lanes (and the reverse, before the slab is filled again)
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  pin_list(a.list);
+  asm volatile("" ::"s"(a.rb2), "s"(a.counts), "s"(a.n_bins), "s"(a.dtheta));
 }
 
 struct AdfNeighbour {
@@ -74,30 +67,17 @@ struct AdfNeighbour {
 __global__ __launch_bounds__(kAdfThreads) void md_adf_kernel(MdAdfLaunch a) {
   extern __shared__ double s_mem[];  // the four slabs, then min(E P n_bins, kMdAdfLdsWords) histogram words
   pin_args(a);
-  const unsigned mark = *static_cast<const volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
-  const int E = a.n_elements, B = a.n_bins, P = E * (E + 1) / 2, EP = E * P;
+  const MdList &l = a.list;
+  if (md_stale(l.status, l.seq)) return;
+  const int E = l.n_elements, B = a.n_bins, P = E * (E + 1) / 2, EP = E * P;
   const int lane = (int)threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   double *sx = s_mem + wave * kAdfSlabDoubles, *sy = sx + kMdAdfSlab, *sz = sy + kMdAdfSlab;
   int *ss = reinterpret_cast<int *>(sz + kMdAdfSlab);
   unsigned *s_hist = reinterpret_cast<unsigned *>(s_mem + kAdfWaves * kAdfSlabDoubles);
-  // frame of this workgroup: the last f with blk_start[f] <= blockIdx.x (every frame has at least one)
-  int f = 0;
-  {
-    int lo = 0, hi = a.n_frames - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (a.blk_start[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    f = lo;
-  }
-  const int i_end = a.atom_start[f + 1];
-  const int i_lo = a.atom_start[f] + ((int)blockIdx.x - a.blk_start[f]) * a.chunk;
-  const int i_hi = i_lo + a.chunk < i_end ? i_lo + a.chunk : i_end;
+  const auto [f, i_lo, i_hi] = md_centres(l);
   if (i_lo >= i_hi) return;  // (the whole workgroup: an empty frame's one workgroup)
   double h[9];
-#pragma unroll
-  for (int c = 0; c < 9; ++c) h[c] = a.cells[9 * (size_t)f + c];
+  md_load_cell(l.cells, f, h);
   const int tile = B < kMdAdfLdsWords / EP ? B : kMdAdfLdsWords / EP;  // bins per pass
   unsigned long long *acc = a.counts + (size_t)f * EP * B;
   const double inv_dtheta = 1.0 / a.dtheta, margin = kAdfSingleRad * inv_dtheta;  // (the margin in bins)
@@ -106,22 +86,17 @@ __global__ __launch_bounds__(kAdfThreads) void md_adf_kernel(MdAdfLaunch a) {
     for (int t = (int)threadIdx.x; t < EP * nk; t += kAdfThreads) s_hist[t] = 0u;
     __syncthreads();
     for (int i = i_lo + wave; i < i_hi; i += kAdfWaves) {
-      const int q_lo = a.pair_start[i], q_hi = a.pair_start[i + 1];
-      const int sa = a.species[i];
-      const double xi = a.pos[3 * (size_t)i], yi = a.pos[3 * (size_t)i + 1], zi = a.pos[3 * (size_t)i + 2];
+      const int q_lo = l.pair_start[i], q_hi = l.pair_start[i + 1];
+      const int sa = l.species[i];
+      const double xi = l.pos[3 * (size_t)i], yi = l.pos[3 * (size_t)i + 1], zi = l.pos[3 * (size_t)i + 2];
       unsigned *hist = s_hist + (size_t)sa * P * nk;
       // entry q + lane of the list as a neighbour of i (not ok beyond the run or the cutoff; a NaN is not ok)
       auto neighbour = [&](int q) {
+        const MdEntry e = md_entry(l, h, q, q_hi, lane, xi, yi, zi);
         AdfNeighbour n;
-        n.ok = q + lane < q_hi;
-        const size_t qc = (size_t)(n.ok ? q + lane : q);
-        const int j = a.pair_j[qc];
-        const double S0 = a.pair_shift[3 * qc], S1 = a.pair_shift[3 * qc + 1], S2 = a.pair_shift[3 * qc + 2];
-        n.x = (a.pos[3 * (size_t)j] - xi) + (S0 * h[0] + S1 * h[3] + S2 * h[6]);
-        n.y = (a.pos[3 * (size_t)j + 1] - yi) + (S0 * h[1] + S1 * h[4] + S2 * h[7]);
-        n.z = (a.pos[3 * (size_t)j + 2] - zi) + (S0 * h[2] + S1 * h[5] + S2 * h[8]);
-        n.sp = a.species[j];
-        n.ok = n.ok && n.x * n.x + n.y * n.y + n.z * n.z < a.rb2[sa * E + n.sp];
+        n.x = e.x, n.y = e.y, n.z = e.z;
+        n.sp = l.species[e.j];
+        n.ok = e.in_run && n.x * n.x + n.y * n.y + n.z * n.z < a.rb2[sa * E + n.sp];
         return n;
       };
       // the triple of the neighbours u (species b) and w (species c) of this centre
@@ -181,12 +156,7 @@ __global__ __launch_bounds__(kAdfThreads) void md_adf_kernel(MdAdfLaunch a) {
       }
     }
     __syncthreads();
-    for (int t = (int)threadIdx.x; t < EP * nk; t += kAdfThreads) {
-      const unsigned c = s_hist[t];
-      if (c != 0u)
-        __hip_atomic_fetch_add(acc + (size_t)(t / nk) * B + (k0 + t % nk), (unsigned long long)c, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-    }
+    md_merge_hist<kAdfThreads>(s_hist, EP, nk, acc, B, k0);
     __syncthreads();
   }
 }
@@ -194,11 +164,12 @@ __global__ __launch_bounds__(kAdfThreads) void md_adf_kernel(MdAdfLaunch a) {
 }  // namespace
 
 void launch_md_adf(const MdAdfLaunch &a, hipStream_t s) {
-  if (a.n_blk <= 0 || a.n_bins <= 0) return;
-  const long long words = (long long)a.n_elements * (a.n_elements * (a.n_elements + 1) / 2) * a.n_bins;
+  if (a.list.n_blk <= 0 || a.n_bins <= 0) return;
+  const int E = a.list.n_elements;
+  const long long words = (long long)E * (E * (E + 1) / 2) * a.n_bins;
   const size_t lds = (size_t)kAdfWaves * kAdfSlabDoubles * sizeof(double) +
                      (size_t)(words < kMdAdfLdsWords ? words : kMdAdfLdsWords) * sizeof(unsigned);
-  hipLaunchKernelGGL(md_adf_kernel, dim3((unsigned)a.n_blk), dim3(kAdfThreads), lds, s, a);
+  hipLaunchKernelGGL(md_adf_kernel, dim3((unsigned)a.list.n_blk), dim3(kAdfThreads), lds, s, a);
 }
 
 }  // namespace ta

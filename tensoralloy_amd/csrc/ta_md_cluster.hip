@@ -6,15 +6,16 @@
 // being that of the bond-order launches for the same state. Two selected atoms i != j are LINKED when the resident
 // (skin) list holds an entry (j, S) of centre i with
 //     d = x_j - x_i + S . h (fp64),   d . d < rl[a][b]^2,   b = species of j
-// (an image of i itself links nothing, several images of j link once). A cluster is a connected component of the
-// selected atoms under links; its label is the smallest index of its members in the batch, its size the number
-// of its atoms. Everything is an integer and a function of the state alone.
+// (md_entry, then this test; ta_md_sweep.h holds what the launches on the resident list share; an image of i itself
+// links nothing, several images of j link once). A cluster is a connected component of the selected atoms under
+// links; its label is the smallest index of its members in the batch, its size the number of its atoms. Everything
+// is an integer and a function of the state alone.
 //
 // 1. md_cluster_select_kernel   a thread per atom: parent[i] = i when selected, -1 otherwise; count[i] = 0.
 // 2. md_cluster_link_kernel     lock-free union by index on parent[]. A workgroup of four waves owns `chunk`
-//    consecutive centres of one frame (the layout of the bond-order launches); a wave takes one selected centre at
-//    a time and sweeps its run of the list 64 entries a round, a lane per entry. A lane that holds a link (i, j)
-//    with j < i (the list holds every link from both ends: the larger end joins the two, once)
+//    consecutive centres of one frame (md_centres, on the plan of the bond-order launches); a wave takes one selected
+//    centre at a time and sweeps its run of the list 64 entries a round, a lane per entry. A lane that holds a link
+//    (i, j) with j < i (the list holds every link from both ends: the larger end joins the two, once)
 //    walks both ends to their roots and, with hi and lo the larger and the smaller root, does
 //        old = atomic fetch-min(&parent[hi], lo);
 //    it is done when old == hi (hi was a root and now hangs under lo) or old == lo (someone else did it), and goes
@@ -43,6 +44,7 @@
 
 #include "ta_device.h"
 #include "ta_md.h"
+#include "ta_md_sweep.h"
 
 namespace ta {
 namespace {
@@ -51,26 +53,9 @@ constexpr int kClusterThreads = 256, kClusterWaves = kClusterThreads / 64;
 constexpr int kClusterSummaryThreads = 1024, kClusterSummaryWaves = kClusterSummaryThreads / 64;
 
 __device__ __forceinline__ void pin_args(const MdClusterLaunch &a) {
-  asm volatile("" ::"s"(a.pos), "s"(a.cells), "s"(a.species), "s"(a.atom_start), "s"(a.blk_start), "s"(a.pair_start),
-               "s"(a.pair_j), "s"(a.pair_shift), "s"(a.rl2), "s"(a.n_conn), "s"(a.parent), "s"(a.count), "s"(a.label),
-               "s"(a.size));
-  asm volatile("" ::"s"(a.hist), "s"(a.row), "s"(a.giveup), "s"(a.status), "s"(a.seq), "s"(a.n_atoms), "s"(a.n_bins),
-               "s"(a.n_elements), "s"(a.n_frames), "s"(a.chunk), "s"(a.n_min), "s"(a.species_mask));
-}
-
-__device__ __forceinline__ bool stale(const MdClusterLaunch &a) {
-  const unsigned mark = *static_cast<const volatile unsigned *>(a.status);
-  return mark != 0u && mark <= a.seq;
-}
-
-// the last f with start[f] <= v (start[0] = 0 <= v)
-__device__ __forceinline__ int last_at_or_below(const int32_t *start, int n, int v) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (start[mid] <= v) lo = mid; else hi = mid - 1;
-  }
-  return lo;
+  pin_list(a.list);
+  asm volatile("" ::"s"(a.rl2), "s"(a.n_conn), "s"(a.parent), "s"(a.count), "s"(a.label), "s"(a.size), "s"(a.hist),
+               "s"(a.row), "s"(a.giveup), "s"(a.n_atoms), "s"(a.n_bins), "s"(a.n_min), "s"(a.species_mask));
 }
 
 __device__ __forceinline__ void give_up(const MdClusterLaunch &a) {
@@ -112,10 +97,11 @@ __device__ __forceinline__ bool unite(int32_t *parent, int &a, int b, int cap) {
 
 __global__ __launch_bounds__(kClusterThreads) void md_cluster_select_kernel(MdClusterLaunch a) {
   pin_args(a);
-  if (stale(a)) return;
+  const MdList &l = a.list;
+  if (md_stale(l.status, l.seq)) return;
   const long long i = (long long)blockIdx.x * kClusterThreads + threadIdx.x;
   if (i >= a.n_atoms) return;
-  bool sel = ((a.species_mask >> a.species[i]) & 1) != 0;
+  bool sel = ((a.species_mask >> l.species[i]) & 1) != 0;
   if (a.n_min > 0) sel = sel && a.n_conn[i] >= a.n_min;
   a.parent[i] = sel ? (int32_t)i : -1;
   a.count[i] = 0;
@@ -123,37 +109,28 @@ __global__ __launch_bounds__(kClusterThreads) void md_cluster_select_kernel(MdCl
 
 __global__ __launch_bounds__(kClusterThreads) void md_cluster_link_kernel(MdClusterLaunch a) {
   pin_args(a);
-  if (stale(a)) return;
+  const MdList &l = a.list;
+  if (md_stale(l.status, l.seq)) return;
   const int lane = (int)threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  const int f = last_at_or_below(a.blk_start, a.n_frames, (int)blockIdx.x);
-  const int i_begin = a.atom_start[f], i_end = a.atom_start[f + 1];
-  const int i_lo = i_begin + ((int)blockIdx.x - a.blk_start[f]) * a.chunk;
-  const int i_hi = i_lo + a.chunk < i_end ? i_lo + a.chunk : i_end;
+  const auto [f, i_lo, i_hi] = md_centres(l);
   if (i_lo >= i_hi) return;  // (the whole workgroup: an empty frame's one workgroup)
-  const int cap = i_end - i_begin;
+  const int cap = l.atom_start[f + 1] - l.atom_start[f];
   double h[9];
-#pragma unroll
-  for (int c = 0; c < 9; ++c) h[c] = a.cells[9 * (size_t)f + c];
+  md_load_cell(l.cells, f, h);
   bool ok_all = true;
   for (int i = i_lo + wave; i < i_hi; i += kClusterWaves) {
     // (whether an atom is selected never changes within the launch)
     if (__hip_atomic_load(a.parent + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0) continue;
-    const int q_lo = a.pair_start[i], q_hi = a.pair_start[i + 1];
-    const int sa = a.species[i];
-    const double xi = a.pos[3 * (size_t)i], yi = a.pos[3 * (size_t)i + 1], zi = a.pos[3 * (size_t)i + 2];
+    const int q_lo = l.pair_start[i], q_hi = l.pair_start[i + 1];
+    const int sa = l.species[i];
+    const double xi = l.pos[3 * (size_t)i], yi = l.pos[3 * (size_t)i + 1], zi = l.pos[3 * (size_t)i + 2];
     int up = i;  // an ancestor of i, the lowest this lane has seen: its walks start there, not at i again
     for (int q = q_lo; q < q_hi; q += 64) {
-      bool ok = q + lane < q_hi;
-      const size_t qc = (size_t)(ok ? q + lane : q);
-      const int j = a.pair_j[qc];
+      const MdEntry e = md_entry(l, h, q, q_hi, lane, xi, yi, zi);
+      const int j = e.j;
       // the list holds every link from both ends, as entry (j, S) of centre i and as entry (i, -S) of centre j, and
       // d is the same number but for its sign: the larger end joins the two, once
-      ok = ok && j < i;
-      const double S0 = a.pair_shift[3 * qc], S1 = a.pair_shift[3 * qc + 1], S2 = a.pair_shift[3 * qc + 2];
-      const double dx = (a.pos[3 * (size_t)j] - xi) + (S0 * h[0] + S1 * h[3] + S2 * h[6]);
-      const double dy = (a.pos[3 * (size_t)j + 1] - yi) + (S0 * h[1] + S1 * h[4] + S2 * h[7]);
-      const double dz = (a.pos[3 * (size_t)j + 2] - zi) + (S0 * h[2] + S1 * h[5] + S2 * h[8]);
-      ok = ok && dx * dx + dy * dy + dz * dz < a.rl2[sa * a.n_elements + a.species[j]];
+      const bool ok = e.in_run && j < i && e.x * e.x + e.y * e.y + e.z * e.z < a.rl2[sa * l.n_elements + l.species[j]];
       // the parent of j says whether j is selected, and is the first hop of its walk
       const int pj = ok ? __hip_atomic_load(a.parent + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -1;
       if (pj >= 0) ok_all = unite(a.parent, up, pj, cap) && ok_all;
@@ -164,12 +141,13 @@ __global__ __launch_bounds__(kClusterThreads) void md_cluster_link_kernel(MdClus
 
 __global__ __launch_bounds__(kClusterThreads) void md_cluster_flatten_kernel(MdClusterLaunch a) {
   pin_args(a);
-  if (stale(a)) return;
+  const MdList &l = a.list;
+  if (md_stale(l.status, l.seq)) return;
   const long long i = (long long)blockIdx.x * kClusterThreads + threadIdx.x;
   int root = -1;
   if (i < a.n_atoms && a.parent[i] >= 0) {
-    const int f = last_at_or_below(a.atom_start, a.n_frames + 1, (int)i);
-    const int cap = a.atom_start[f + 1] - a.atom_start[f];
+    const int f = md_frame_of(l.atom_start, l.n_frames + 1, (int)i);  // (the last f with atom_start[f] <= i)
+    const int cap = l.atom_start[f + 1] - l.atom_start[f];
     root = (int)i;
     bool ok = false;
     for (int n = 0; n <= cap && !ok; ++n) {
@@ -204,9 +182,10 @@ __global__ __launch_bounds__(kClusterSummaryThreads) void md_cluster_summary_ker
   __shared__ long long s_sel[kClusterSummaryWaves], s_clu[kClusterSummaryWaves];
   __shared__ unsigned long long s_best[kClusterSummaryWaves];
   pin_args(a);
-  if (stale(a)) return;
+  const MdList &l = a.list;
+  if (md_stale(l.status, l.seq)) return;
   const int f = (int)blockIdx.x, B = a.n_bins;
-  const int i_begin = a.atom_start[f], i_end = a.atom_start[f + 1];
+  const int i_begin = l.atom_start[f], i_end = l.atom_start[f + 1];
   for (int t = (int)threadIdx.x; t < B; t += kClusterSummaryThreads) s_hist[t] = 0u;
   __syncthreads();
   // the largest size wins, among equals the smallest label: the largest key (size, INT32_MAX - label); 0: none
@@ -246,22 +225,18 @@ __global__ __launch_bounds__(kClusterSummaryThreads) void md_cluster_summary_ker
     row[2] = (long long)(best >> 32);
     row[3] = best ? (long long)(0x7fffffff - (int)(unsigned)(best & 0xffffffffull)) : -1ll;
   }
-  for (int t = (int)threadIdx.x; t < B; t += kClusterSummaryThreads) {
-    const unsigned c = s_hist[t];
-    if (c != 0u)
-      __hip_atomic_fetch_add(a.hist + (size_t)f * B + t, (unsigned long long)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  md_merge_counts<kClusterSummaryThreads>(s_hist, B, a.hist + (size_t)f * B);
 }
 
 }  // namespace
 
 void launch_md_cluster(const MdClusterLaunch &a, hipStream_t s) {
-  if (a.n_blk <= 0 || a.n_bins <= 0 || a.n_bins > kMdClusterLdsWords || a.n_atoms <= 0) return;
+  if (a.list.n_blk <= 0 || a.n_bins <= 0 || a.n_bins > kMdClusterLdsWords || a.n_atoms <= 0) return;
   const unsigned per_atom = (unsigned)((a.n_atoms + kClusterThreads - 1) / kClusterThreads);
   hipLaunchKernelGGL(md_cluster_select_kernel, dim3(per_atom), dim3(kClusterThreads), 0, s, a);
-  hipLaunchKernelGGL(md_cluster_link_kernel, dim3((unsigned)a.n_blk), dim3(kClusterThreads), 0, s, a);
+  hipLaunchKernelGGL(md_cluster_link_kernel, dim3((unsigned)a.list.n_blk), dim3(kClusterThreads), 0, s, a);
   hipLaunchKernelGGL(md_cluster_flatten_kernel, dim3(per_atom), dim3(kClusterThreads), 0, s, a);
-  hipLaunchKernelGGL(md_cluster_summary_kernel, dim3((unsigned)a.n_frames), dim3(kClusterSummaryThreads),
+  hipLaunchKernelGGL(md_cluster_summary_kernel, dim3((unsigned)a.list.n_frames), dim3(kClusterSummaryThreads),
                      (size_t)a.n_bins * sizeof(unsigned), s, a);
 }
 

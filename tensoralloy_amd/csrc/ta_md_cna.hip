@@ -5,7 +5,8 @@
 // `compute cna/atom`) or adaptively (Stukowski 2012, OVITO's default).
 //
 // Candidates of a centre i are the entries (j, S) of the resident (skin) list with
-//     d = x_j - x_i + S . h (fp64, the expression of the order launches),   d . d < r^2,
+//     d = x_j - x_i + S . h (fp64),   d . d < r^2,
+// (md_entry, then this test; ta_md_sweep.h holds what the launches on the resident list share),
 // r = r_max (adaptive) or r_cut (fixed); species do not enter; self-images and several images of one atom are
 // neighbours like any other. They are ordered by the key (d . d, j, S0, S1, S2), so the selection is a function of
 // the state and not of the order of the list.
@@ -21,7 +22,7 @@
 //     fixed:    all N candidates, rc = r_cut = r_local; N = 12 tests FCC, HCP, ICO, N = 14 tests BCC.
 //
 // A workgroup of 512 threads (eight waves: one centre per wave in a chunk of eight) owns `chunk` consecutive centres
-// of ONE frame and finds its frame in blk_start the way the order launches do. ONE WAVE takes one centre at a time
+// of ONE frame (md_centres, on the plan of the order launches). ONE WAVE takes one centre at a time
 // and sweeps that centre's run pair_start[i] .. pair_start[i + 1] of the list, 64 entries a round, one entry per
 // lane, and keeps the 14 smallest keys, sorted, in its part of LDS: a round's candidates that beat the 14th key held
 // are ranked against the keys held and against each other, and every survivor stores itself at its rank. A round with
@@ -44,6 +45,7 @@
 
 #include "ta_device.h"
 #include "ta_md.h"
+#include "ta_md_sweep.h"
 
 namespace ta {
 namespace {
@@ -59,27 +61,8 @@ static_assert(kMdCnaTypes == 5, "OTHER, FCC, HCP, BCC, ICO");
 constexpr int kSig421 = 40201, kSig422 = 40202, kSig555 = 50505, kSig666 = 60606, kSig444 = 40404;
 
 __device__ __forceinline__ void pin_args(const MdCnaLaunch &a) {
-  asm volatile("" ::"s"(a.pos), "s"(a.cells), "s"(a.species), "s"(a.atom_start), "s"(a.blk_start), "s"(a.pair_start),
-               "s"(a.pair_j), "s"(a.pair_shift), "s"(a.structure), "s"(a.r_local), "s"(a.counts), "s"(a.row),
-               "s"(a.status), "s"(a.seq), "s"(a.n_elements), "s"(a.n_frames), "s"(a.chunk), "s"(a.mode), "s"(a.r2),
-               "s"(a.r_cut));
-}
-
-// what one lane of a wave wrote to the wave's part of LDS is read by its other lanes
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// frame of this workgroup: the last f with blk_start[f] <= blockIdx.x (every frame has at least one)
-__device__ __forceinline__ int frame_of_block(const MdCnaLaunch &a) {
-  int lo = 0, hi = a.n_frames - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (a.blk_start[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  return lo;
+  pin_list(a.list);
+  asm volatile("" ::"s"(a.structure), "s"(a.r_local), "s"(a.counts), "s"(a.row), "s"(a.mode), "s"(a.r2), "s"(a.r_cut));
 }
 
 // (d . d, j, S) of one candidate before that of another; S is packed so that its order is that of (S0, S1, S2)
@@ -166,9 +149,8 @@ __device__ __forceinline__ int cna_type14(const CnaTally &t) {
 
 // this sample's row of the series starts from zero
 __global__ __launch_bounds__(64) void md_cna_zero_kernel(MdCnaLaunch a) {
-  const unsigned mark = *static_cast<const volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
-  const int n = a.n_frames * kMdCnaTypes;
+  if (md_stale(a.list.status, a.list.seq)) return;
+  const int n = a.list.n_frames * kMdCnaTypes;
   for (int t = (int)(blockIdx.x * blockDim.x + threadIdx.x); t < n; t += (int)(gridDim.x * blockDim.x)) a.row[t] = 0ull;
 }
 
@@ -176,39 +158,29 @@ __global__ __launch_bounds__(kCnaThreads) void md_cna_kernel(MdCnaLaunch a) {
   __shared__ CnaWave s_wave[kCnaWaves];
   __shared__ unsigned s_cnt[kMaxElements * kMdCnaTypes];
   pin_args(a);
-  const unsigned mark = *static_cast<const volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
+  const MdList &l = a.list;
+  if (md_stale(l.status, l.seq)) return;
   const int lane = (int)threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  const int f = frame_of_block(a);
-  const int i_end = a.atom_start[f + 1];
-  const int i_lo = a.atom_start[f] + ((int)blockIdx.x - a.blk_start[f]) * a.chunk;
-  const int i_hi = i_lo + a.chunk < i_end ? i_lo + a.chunk : i_end;
+  const auto [f, i_lo, i_hi] = md_centres(l);
   if (i_lo >= i_hi) return;  // (the whole workgroup: an empty frame's one workgroup)
-  const int n_cnt = a.n_elements * kMdCnaTypes;
+  const int n_cnt = l.n_elements * kMdCnaTypes;
   for (int t = (int)threadIdx.x; t < n_cnt; t += kCnaThreads) s_cnt[t] = 0u;
   __syncthreads();
   double h[9];
-#pragma unroll
-  for (int c = 0; c < 9; ++c) h[c] = a.cells[9 * (size_t)f + c];
+  md_load_cell(l.cells, f, h);
   CnaWave &w = s_wave[wave];
   for (int i = i_lo + wave; i < i_hi; i += kCnaWaves) {
-    const int q_lo = a.pair_start[i], q_hi = a.pair_start[i + 1];
-    const double xi = a.pos[3 * (size_t)i], yi = a.pos[3 * (size_t)i + 1], zi = a.pos[3 * (size_t)i + 2];
+    const int q_lo = l.pair_start[i], q_hi = l.pair_start[i + 1];
+    const double xi = l.pos[3 * (size_t)i], yi = l.pos[3 * (size_t)i + 1], zi = l.pos[3 * (size_t)i + 2];
     int n_keep = 0, n_cand = 0;  // neighbours kept (at most 14) and candidates seen
     if (lane < kCnaSlots) w.d2[lane] = kCnaFar;
     wave_sync();
     for (int q = q_lo; q < q_hi; q += 64) {
-      bool ok = q + lane < q_hi;
-      const size_t qc = (size_t)(ok ? q + lane : q);
-      const int j = a.pair_j[qc];
-      const int S0 = a.pair_shift[3 * qc], S1 = a.pair_shift[3 * qc + 1], S2 = a.pair_shift[3 * qc + 2];
-      const double fS0 = S0, fS1 = S1, fS2 = S2;
-      const double dx = (a.pos[3 * (size_t)j] - xi) + (fS0 * h[0] + fS1 * h[3] + fS2 * h[6]);
-      const double dy = (a.pos[3 * (size_t)j + 1] - yi) + (fS0 * h[1] + fS1 * h[4] + fS2 * h[7]);
-      const double dz = (a.pos[3 * (size_t)j + 2] - zi) + (fS0 * h[2] + fS1 * h[5] + fS2 * h[8]);
-      const double d2 = dx * dx + dy * dy + dz * dz;
-      const unsigned long long sk = pack_shift(S0, S1, S2);
-      ok = ok && d2 < a.r2;  // (a NaN is no candidate)
+      const MdEntry e = md_entry(l, h, q, q_hi, lane, xi, yi, zi);
+      const int j = e.j;
+      const double dx = e.x, dy = e.y, dz = e.z, d2 = dx * dx + dy * dy + dz * dz;
+      const unsigned long long sk = pack_shift(e.S0, e.S1, e.S2);
+      const bool ok = e.in_run && d2 < a.r2;  // (a NaN is no candidate)
       const unsigned long long okm = __ballot(ok);
       if (okm == 0ull) continue;
       n_cand += __popcll(okm);
@@ -297,19 +269,15 @@ __global__ __launch_bounds__(kCnaThreads) void md_cna_kernel(MdCnaLaunch a) {
     if (lane == 0) {
       a.structure[i] = type;
       a.r_local[i] = r_local;
-      atomicAdd(&s_cnt[a.species[i] * kMdCnaTypes + type], 1u);
+      atomicAdd(&s_cnt[l.species[i] * kMdCnaTypes + type], 1u);
     }
     wave_sync();  // (before the next centre's neighbours replace these)
   }
   __syncthreads();
-  for (int t = (int)threadIdx.x; t < n_cnt; t += kCnaThreads) {
-    const unsigned c = s_cnt[t];
-    if (c != 0u)
-      __hip_atomic_fetch_add(a.counts + (size_t)f * n_cnt + t, (unsigned long long)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  md_merge_counts<kCnaThreads>(s_cnt, n_cnt, a.counts + (size_t)f * n_cnt);
   if ((int)threadIdx.x < kMdCnaTypes) {  // the row is summed over the species
     unsigned c = 0u;
-    for (int e = 0; e < a.n_elements; ++e) c += s_cnt[e * kMdCnaTypes + (int)threadIdx.x];
+    for (int e = 0; e < l.n_elements; ++e) c += s_cnt[e * kMdCnaTypes + (int)threadIdx.x];
     if (c != 0u)
       __hip_atomic_fetch_add(a.row + (size_t)f * kMdCnaTypes + threadIdx.x, (unsigned long long)c, __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_AGENT);
@@ -319,10 +287,10 @@ __global__ __launch_bounds__(kCnaThreads) void md_cna_kernel(MdCnaLaunch a) {
 }  // namespace
 
 void launch_md_cna(const MdCnaLaunch &a, hipStream_t s) {
-  if (a.n_blk <= 0) return;
-  const int n_row = a.n_frames * kMdCnaTypes;
+  if (a.list.n_blk <= 0) return;
+  const int n_row = a.list.n_frames * kMdCnaTypes;
   hipLaunchKernelGGL(md_cna_zero_kernel, dim3((unsigned)((n_row + 63) / 64)), dim3(64), 0, s, a);
-  hipLaunchKernelGGL(md_cna_kernel, dim3((unsigned)a.n_blk), dim3(kCnaThreads), 0, s, a);
+  hipLaunchKernelGGL(md_cna_kernel, dim3((unsigned)a.list.n_blk), dim3(kCnaThreads), 0, s, a);
 }
 
 }  // namespace ta

@@ -22,6 +22,7 @@
 #include "ta_device.h"
 #include "ta_math.h"
 #include "ta_md.h"
+#include "ta_md_sweep.h"
 
 namespace ta {
 namespace {
@@ -32,22 +33,12 @@ static_assert(2 * kMaxElements * kMdCorrLagTile <= kCorrThreads, "one thread per
 
 __global__ __launch_bounds__(kCorrThreads) void md_corr_kernel(MdCorrLaunch a) {
   __shared__ double s_part[kCorrWaves][2][kMaxElements][kMdCorrLagTile];
-  const unsigned mark = *static_cast<const volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
+  if (md_stale(a.status, a.seq)) return;
   const int L = a.n_lags, E = a.n_elements;
   const long long kmax = a.n < (long long)(L - 1) ? a.n : (long long)(L - 1);
   const int k0 = (int)blockIdx.y * kMdCorrLagTile;
   if ((long long)k0 > kmax) return;  // (the whole workgroup: the ring has no row for this tile yet)
-  // frame of this chunk: the last f with blk_start[f] <= blockIdx.x (every frame has at least one)
-  int f = 0;
-  {
-    int lo = 0, hi = a.n_frames - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (a.blk_start[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    f = lo;
-  }
+  const int f = md_frame_of(a.blk_start, a.n_frames, (int)blockIdx.x);
   const long long j_hi = 3ll * a.atom_start[f + 1];
   const long long j_lo = 3ll * a.atom_start[f] + (long long)((int)blockIdx.x - a.blk_start[f]) * kMdCorrChunk;
   const size_t row = 3 * (size_t)a.n_atoms;
@@ -104,8 +95,7 @@ __global__ __launch_bounds__(kCorrThreads) void md_corr_kernel(MdCorrLaunch a) {
 
 // acc[f][e][k] += the partials of the frame's chunks, in chunk order; one thread per (f, e, k), k <= min(n, L - 1)
 __global__ __launch_bounds__(256) void md_corr_add_kernel(MdCorrLaunch a) {
-  const unsigned mark = *static_cast<const volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
+  if (md_stale(a.status, a.seq)) return;
   const int L = a.n_lags, E = a.n_elements;
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long long)a.n_frames * E * L) return;

@@ -26,6 +26,7 @@
 
 #include "ta_device.h"
 #include "ta_md.h"
+#include "ta_md_sweep.h"
 #include "ta_reduce.h"
 
 namespace ta {
@@ -33,23 +34,12 @@ namespace {
 
 static_assert(kMdFluxLanes == 16 && kMdFluxRow == 18, "a centre is one DPP row; a row is {J_conv, J_pot, K, W}");
 
-// frame of workgroup `blk`: the last f with blk_start[f] <= blk (every frame has at least one)
-__device__ __forceinline__ int flux_frame_of(const int32_t *blk_start, int n_frames, int blk) {
-  int lo = 0, hi = n_frames - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (blk_start[mid] <= blk) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(16 * kMdFluxLanes) void md_flux_sweep_kernel(MdFluxLaunch a, DeviceBatch b) {
   __shared__ double s_part[16 * kMdFluxLanes / 64][kMdFluxRow];
-  const unsigned mark = *static_cast<const volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
+  if (md_stale(a.status, a.seq)) return;
   const int blk = (int)blockIdx.x;
   const int grp = (int)threadIdx.x / kMdFluxLanes, lane = (int)threadIdx.x & (kMdFluxLanes - 1);
-  const int f = flux_frame_of(a.blk_start, a.n_frames, blk);
+  const int f = md_frame_of(a.blk_start, a.n_frames, blk);
   const long long i_end = b.atom_start[f + 1];
   const long long i_lo = (long long)b.atom_start[f] + (long long)(blk - a.blk_start[f]) * a.chunk;
   const long long i_hi = i_lo + a.chunk < i_end ? i_lo + a.chunk : i_end;
@@ -113,8 +103,7 @@ constexpr int kMdFluxSumTile = 128;
 
 __global__ __launch_bounds__(256) void md_flux_sum_kernel(MdFluxLaunch a) {
   __shared__ double s_tile[kMdFluxSumTile * kMdFluxRow];
-  const unsigned mark = *static_cast<const volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;  // (the same word in every lane: the barriers below are uniform)
+  if (md_stale(a.status, a.seq)) return;  // (the same word in every lane: the barriers below are uniform)
   const int f = (int)blockIdx.x, c = (int)threadIdx.x;
   const int b0 = a.blk_start[f], b1 = a.blk_start[f + 1];
   double sum = 0.0;
@@ -134,8 +123,7 @@ __global__ __launch_bounds__(256) void md_flux_sum_kernel(MdFluxLaunch a) {
 }
 
 __global__ __launch_bounds__(256) void md_flux_corr_kernel(MdFluxLaunch a) {
-  const unsigned mark = *static_cast<const volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
+  if (md_stale(a.status, a.seq)) return;
   const int L = a.n_lags;
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (size_t)a.n_frames * L * 9) return;

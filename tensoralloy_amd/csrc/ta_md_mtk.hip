@@ -26,6 +26,7 @@
 #include "ta_device.h"
 #include "ta_md.h"
 #include "ta_md_device.h"
+#include "ta_md_sweep.h"
 
 namespace ta {
 namespace {
@@ -40,8 +41,7 @@ __global__ __launch_bounds__(1024) void md_integrate_mtk_kernel(MdLaunch a, MdMt
   __shared__ double s_total;
   __shared__ double s_mtk[kMtkWords];
   // (0, or the value this very launch writes, or the mark of an earlier launch: the same branch in every thread)
-  const unsigned mark = *static_cast<volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
+  if (md_stale(a.status, a.seq)) return;
   const int f = (int)blockIdx.x;  // (the host made every workgroup a whole frame)
   const int64_t lo = a.atom_start[f], hi = a.atom_start[f + 1];
   const double hdt = 0.5 * a.dt;

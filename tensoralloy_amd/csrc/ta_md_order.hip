@@ -2,7 +2,7 @@
 // the integrator launch of a sampled step, while the device still holds the whole-step state x(t). For every
 // centre i (species a) the neighbours are the entries (j, S) of the resident (skin) list with
 //     d = x_j - x_i + S . h (fp64),   d . d < rb[a][b]^2,   b = species of j
-// (the neighbour rule of the bond-angle launch), N_b(i) of them. For every chosen degree l and m = 0 .. l
+// (md_entry of ta_md_sweep.h, then this test), N_b(i) of them. For every chosen degree l and m = 0 .. l
 //     q_lm(i)    = (1 / N_b) sum_neigh Y_lm(d / |d|)                                   (pass 1)
 //     qbar_lm(i) = (q_lm(i) + sum_neigh q_lm(j)) / (N_b + 1)                            (pass 2)
 //     q_l        = sqrt(4 pi / (2 l + 1) (|q_l0|^2 + 2 sum_{m > 0} |q_lm|^2)),  qbar_l likewise from qbar_lm
@@ -16,9 +16,9 @@
 //     Q_l^m = ((2 l - 1) t Q_{l-1}^m - (l + m - 1) Q_{l-2}^m) / (l - m)
 // (Condon-Shortley phase, as scipy.special.sph_harm). The N_lm come from the host in fp64.
 //
-// A workgroup of 256 threads (four waves) owns `chunk` consecutive centres of ONE frame and finds its frame in
-// blk_start the way md_adf_kernel does. ONE WAVE takes one centre at a time and sweeps that centre's run
-// pair_start[i] .. pair_start[i + 1] of the list, 64 entries a round, one entry per lane. Every term of a round
+// A workgroup of 256 threads (four waves) owns `chunk` consecutive centres of ONE frame (md_centres; ta_md_sweep.h
+// holds what the launches on the resident list share). ONE WAVE takes one centre at a time and sweeps that centre's
+// run pair_start[i] .. pair_start[i + 1] of the list, 64 entries a round, one entry per lane. Every term of a round
 // (a lane outside the cutoff adds 0.0) is summed over the wave by the same butterfly (lane ^ 32, 16, .. 1) and one
 // lane adds the round's sum to the centre's sum in LDS: rounds in list order. All sums are fp64 and their order
 // is a function of the list alone, so a run reproduces itself bit for bit however it is cut into calls; another
@@ -44,6 +44,7 @@
 
 #include "ta_device.h"
 #include "ta_md.h"
+#include "ta_md_sweep.h"
 
 namespace ta {
 namespace {
@@ -53,22 +54,14 @@ static_assert(2 * kMaxElements * kMdOrderMaxDegrees <= kMdOrderLdsWords, "at lea
 static_assert(13 + 12 + 11 + 10 == kMdOrderMaxLm && kMdOrderMaxL == 12 && kMdOrderMaxDegrees == 4, "the largest setting");
 
 __device__ __forceinline__ void pin_args(const MdOrderLaunch &a) {
-  asm volatile("" ::"s"(a.pos), "s"(a.cells), "s"(a.species), "s"(a.atom_start), "s"(a.blk_start), "s"(a.pair_start),
-               "s"(a.pair_j), "s"(a.pair_shift), "s"(a.rb2), "s"(a.norm), "s"(a.qlm), "s"(a.q), "s"(a.qbar),
-               "s"(a.n_bonds), "s"(a.n_conn));
-  asm volatile("" ::"s"(a.hist_q), "s"(a.hist_qbar), "s"(a.hist_conn), "s"(a.status), "s"(a.seq), "s"(a.n_bins),
-               "s"(a.n_elements), "s"(a.n_frames), "s"(a.chunk), "s"(a.n_degrees), "s"(a.n_lm), "s"(a.solid),
-               "s"(a.deg0), "s"(a.deg1), "s"(a.deg2), "s"(a.deg3), "s"(a.threshold));
+  pin_list(a.list);
+  asm volatile("" ::"s"(a.rb2), "s"(a.norm), "s"(a.qlm), "s"(a.q), "s"(a.qbar), "s"(a.n_bonds), "s"(a.n_conn),
+               "s"(a.hist_q), "s"(a.hist_qbar), "s"(a.hist_conn), "s"(a.n_bins), "s"(a.n_degrees), "s"(a.n_lm),
+               "s"(a.solid), "s"(a.deg0), "s"(a.deg1), "s"(a.deg2), "s"(a.deg3), "s"(a.threshold));
 }
 
-// what one lane of a wave wrote to the wave's part of LDS is read by its other lanes
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// the sum over the 64 lanes, in every lane, by a tree that is the same for every call
+// The sum over the 64 lanes, in every lane, by a tree that is the same for every call. This launch's own: the
+// wave_sum of ta_math.h adds in another order, which would round every q_lm differently.
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -77,16 +70,6 @@ __device__ __forceinline__ double wave_sum(double v) {
 
 __device__ __forceinline__ int degree_of(const MdOrderLaunch &a, int d) {
   return d == 0 ? a.deg0 : d == 1 ? a.deg1 : d == 2 ? a.deg2 : a.deg3;
-}
-
-// frame of this workgroup: the last f with blk_start[f] <= blockIdx.x (every frame has at least one)
-__device__ __forceinline__ int frame_of_block(const MdOrderLaunch &a) {
-  int lo = 0, hi = a.n_frames - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (a.blk_start[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  return lo;
 }
 
 struct OrderNeighbour {
@@ -99,15 +82,11 @@ struct OrderNeighbour {
 // cutoff; a NaN is not ok)
 __device__ __forceinline__ OrderNeighbour order_neighbour(const MdOrderLaunch &a, const double (&h)[9], int q, int q_hi,
                                                           int lane, double xi, double yi, double zi, int sa) {
+  const MdList &l = a.list;
+  const MdEntry e = md_entry(l, h, q, q_hi, lane, xi, yi, zi);
   OrderNeighbour n;
-  n.ok = q + lane < q_hi;
-  const size_t qc = (size_t)(n.ok ? q + lane : q);
-  n.j = a.pair_j[qc];
-  const double S0 = a.pair_shift[3 * qc], S1 = a.pair_shift[3 * qc + 1], S2 = a.pair_shift[3 * qc + 2];
-  n.x = (a.pos[3 * (size_t)n.j] - xi) + (S0 * h[0] + S1 * h[3] + S2 * h[6]);
-  n.y = (a.pos[3 * (size_t)n.j + 1] - yi) + (S0 * h[1] + S1 * h[4] + S2 * h[7]);
-  n.z = (a.pos[3 * (size_t)n.j + 2] - zi) + (S0 * h[2] + S1 * h[5] + S2 * h[8]);
-  n.ok = n.ok && n.x * n.x + n.y * n.y + n.z * n.z < a.rb2[sa * a.n_elements + a.species[n.j]];
+  n.x = e.x, n.y = e.y, n.z = e.z, n.j = e.j;
+  n.ok = e.in_run && n.x * n.x + n.y * n.y + n.z * n.z < a.rb2[sa * l.n_elements + l.species[n.j]];
   return n;
 }
 
@@ -123,23 +102,19 @@ __device__ __forceinline__ double order_invariant(const double *c, int l, double
 __global__ __launch_bounds__(kOrderThreads) void md_order_qlm_kernel(MdOrderLaunch a) {
   __shared__ double s_sum[kOrderWaves][2 * kMdOrderMaxLm];
   pin_args(a);
-  const unsigned mark = *static_cast<const volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
+  const MdList &l = a.list;
+  if (md_stale(l.status, l.seq)) return;
   const int lane = (int)threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int M2 = 2 * a.n_lm;
-  const int f = frame_of_block(a);
-  const int i_end = a.atom_start[f + 1];
-  const int i_lo = a.atom_start[f] + ((int)blockIdx.x - a.blk_start[f]) * a.chunk;
-  const int i_hi = i_lo + a.chunk < i_end ? i_lo + a.chunk : i_end;
+  const auto [f, i_lo, i_hi] = md_centres(l);
   if (i_lo >= i_hi) return;  // (the whole workgroup: an empty frame's one workgroup)
   double h[9];
-#pragma unroll
-  for (int c = 0; c < 9; ++c) h[c] = a.cells[9 * (size_t)f + c];
+  md_load_cell(l.cells, f, h);
   double *sum = s_sum[wave];
   for (int i = i_lo + wave; i < i_hi; i += kOrderWaves) {
-    const int q_lo = a.pair_start[i], q_hi = a.pair_start[i + 1];
-    const int sa = a.species[i];
-    const double xi = a.pos[3 * (size_t)i], yi = a.pos[3 * (size_t)i + 1], zi = a.pos[3 * (size_t)i + 2];
+    const int q_lo = l.pair_start[i], q_hi = l.pair_start[i + 1];
+    const int sa = l.species[i];
+    const double xi = l.pos[3 * (size_t)i], yi = l.pos[3 * (size_t)i + 1], zi = l.pos[3 * (size_t)i + 2];
     for (int t = lane; t < M2; t += 64) sum[t] = 0.0;
     wave_sync();
     int nb = 0;
@@ -192,27 +167,23 @@ __global__ __launch_bounds__(kOrderThreads) void md_order_bar_kernel(MdOrderLaun
   __shared__ double s_val[kMdOrderMaxChunk][2 * kMdOrderMaxDegrees];  // q then qbar of the workgroup's centres
   __shared__ int s_conn[kMdOrderMaxChunk], s_sp[kMdOrderMaxChunk];
   pin_args(a);
-  const unsigned mark = *static_cast<const volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
+  const MdList &l = a.list;
+  if (md_stale(l.status, l.seq)) return;
   const int lane = (int)threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  const int E = a.n_elements, B = a.n_bins, D = a.n_degrees, M = a.n_lm, M2 = 2 * M;
-  const int f = frame_of_block(a);
-  const int i_end = a.atom_start[f + 1];
-  const int i_lo = a.atom_start[f] + ((int)blockIdx.x - a.blk_start[f]) * a.chunk;
-  const int i_hi = i_lo + a.chunk < i_end ? i_lo + a.chunk : i_end;
+  const int E = l.n_elements, B = a.n_bins, D = a.n_degrees, M = a.n_lm, M2 = 2 * M;
+  const auto [f, i_lo, i_hi] = md_centres(l);
   if (i_lo >= i_hi) return;  // (the whole workgroup: an empty frame's one workgroup)
   double h[9];
-#pragma unroll
-  for (int c = 0; c < 9; ++c) h[c] = a.cells[9 * (size_t)f + c];
+  md_load_cell(l.cells, f, h);
   // where the solid degree's q_lm start, and its l
   int so = 0;
   for (int d = 0; d < a.solid; ++d) so += degree_of(a, d) + 1;
   const int sl = degree_of(a, a.solid);
   double *cen = s_cen[wave], *sum = s_sum[wave];
   for (int i = i_lo + wave; i < i_hi; i += kOrderWaves) {
-    const int q_lo = a.pair_start[i], q_hi = a.pair_start[i + 1];
-    const int sa = a.species[i];
-    const double xi = a.pos[3 * (size_t)i], yi = a.pos[3 * (size_t)i + 1], zi = a.pos[3 * (size_t)i + 2];
+    const int q_lo = l.pair_start[i], q_hi = l.pair_start[i + 1];
+    const int sa = l.species[i];
+    const double xi = l.pos[3 * (size_t)i], yi = l.pos[3 * (size_t)i + 1], zi = l.pos[3 * (size_t)i + 2];
     for (int t = lane; t < M2; t += 64) cen[t] = sum[t] = a.qlm[(size_t)i * M2 + t];
     wave_sync();
     // |q_l(i)|^2 over all m of the solid degree
@@ -273,12 +244,7 @@ __global__ __launch_bounds__(kOrderThreads) void md_order_bar_kernel(MdOrderLaun
     atomicAdd(&s_hconn[s_sp[t] * (kMdOrderMaxConn + 1) + (nc < kMdOrderMaxConn ? nc : kMdOrderMaxConn)], 1u);
   }
   __syncthreads();
-  for (int t = (int)threadIdx.x; t < n_conn_words; t += kOrderThreads) {
-    const unsigned c = s_hconn[t];
-    if (c != 0u)
-      __hip_atomic_fetch_add(a.hist_conn + (size_t)f * n_conn_words + t, (unsigned long long)c, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-  }
+  md_merge_counts<kOrderThreads>(s_hconn, n_conn_words, a.hist_conn + (size_t)f * n_conn_words);
   for (int k0 = 0; k0 < B; k0 += tile) {
     const int nk = B - k0 < tile ? B - k0 : tile;
     for (int t = (int)threadIdx.x; t < 2 * ED * nk; t += kOrderThreads) s_hist[t] = 0u;
@@ -292,13 +258,8 @@ __global__ __launch_bounds__(kOrderThreads) void md_order_bar_kernel(MdOrderLaun
       atomicAdd(&s_hist[((which * E + s_sp[ic]) * D + d) * nk + k], 1u);
     }
     __syncthreads();
-    for (int t = (int)threadIdx.x; t < 2 * ED * nk; t += kOrderThreads) {
-      const unsigned c = s_hist[t];
-      if (c == 0u) continue;
-      const int row = t / nk, which = row / ED;
-      unsigned long long *acc = (which ? a.hist_qbar : a.hist_q) + ((size_t)f * ED + (row - which * ED)) * B;
-      __hip_atomic_fetch_add(acc + (k0 + t % nk), (unsigned long long)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    md_merge_hist<kOrderThreads>(s_hist, ED, nk, a.hist_q + (size_t)f * ED * B, B, k0);  // (q first, then qbar)
+    md_merge_hist<kOrderThreads>(s_hist + ED * nk, ED, nk, a.hist_qbar + (size_t)f * ED * B, B, k0);
     __syncthreads();
   }
 }
@@ -306,12 +267,12 @@ __global__ __launch_bounds__(kOrderThreads) void md_order_bar_kernel(MdOrderLaun
 }  // namespace
 
 void launch_md_order(const MdOrderLaunch &a, hipStream_t s) {
-  if (a.n_blk <= 0 || a.n_bins <= 0) return;
-  const long long words = 2ll * a.n_elements * a.n_degrees * a.n_bins;
+  if (a.list.n_blk <= 0 || a.n_bins <= 0) return;
+  const long long words = 2ll * a.list.n_elements * a.n_degrees * a.n_bins;
   const size_t lds = ((size_t)(words < kMdOrderLdsWords ? words : kMdOrderLdsWords) +
-                      (size_t)a.n_elements * (kMdOrderMaxConn + 1)) * sizeof(unsigned);
-  hipLaunchKernelGGL(md_order_qlm_kernel, dim3((unsigned)a.n_blk), dim3(kOrderThreads), 0, s, a);
-  hipLaunchKernelGGL(md_order_bar_kernel, dim3((unsigned)a.n_blk), dim3(kOrderThreads), lds, s, a);
+                      (size_t)a.list.n_elements * (kMdOrderMaxConn + 1)) * sizeof(unsigned);
+  hipLaunchKernelGGL(md_order_qlm_kernel, dim3((unsigned)a.list.n_blk), dim3(kOrderThreads), 0, s, a);
+  hipLaunchKernelGGL(md_order_bar_kernel, dim3((unsigned)a.list.n_blk), dim3(kOrderThreads), lds, s, a);
 }
 
 }  // namespace ta

@@ -7,9 +7,9 @@
 // self-image (i == j, S != 0) is a pair like any other. The resident list holds every pair below
 // max(rcut, acut) whenever the integrator's list test holds, and r_max does not exceed that.
 //
-// A workgroup of 256 threads owns `chunk` consecutive centres of ONE frame; it finds its frame in blk_start the
-// way md_corr_kernel does. The pairs are sorted by centre and contiguous, so the workgroup's pairs are ONE run
-// pair_start[first centre] .. pair_start[last centre + 1] of the list: thread t takes pairs t, t + 256, ... of
+// A workgroup of 256 threads owns `chunk` consecutive centres of ONE frame (md_centres; ta_md_sweep.h holds what the
+// launches on the resident list share). The pairs are sorted by centre and contiguous, so the workgroup's pairs are
+// ONE run pair_start[first centre] .. pair_start[last centre + 1] of the list: thread t takes pairs t, t + 256, ... of
 // that run, four at a time, with the centre from pair_i: every lane works whatever the neighbour counts are,
 // and the list entries of the four pairs, then their position and species gathers, are in flight together (the
 // sweep is two dependent rounds of loads per pair, so its time is latency over the pairs in flight).
@@ -32,6 +32,7 @@
 
 #include "ta_device.h"
 #include "ta_md.h"
+#include "ta_md_sweep.h"
 
 namespace ta {
 namespace {
@@ -40,35 +41,21 @@ constexpr int kRdfThreads = 256, kRdfBatch = 4;
 static_assert(kMaxElements * kMaxElements <= kMdRdfLdsWords, "at least one bin per pass");
 
 __device__ __forceinline__ void pin_args(const MdRdfLaunch &a) {
-  asm volatile("" ::"s"(a.pos), "s"(a.cells), "s"(a.species), "s"(a.atom_start), "s"(a.blk_start), "s"(a.pair_start),
-               "s"(a.pair_i), "s"(a.pair_j), "s"(a.pair_shift), "s"(a.counts), "s"(a.status), "s"(a.seq), "s"(a.n_bins),
-               "s"(a.n_elements), "s"(a.n_frames), "s"(a.chunk), "s"(a.dr));
+  pin_list(a.list);
+  asm volatile("" ::"s"(a.pair_i), "s"(a.counts), "s"(a.n_bins), "s"(a.dr));
 }
 
 __global__ __launch_bounds__(kRdfThreads) void md_rdf_kernel(MdRdfLaunch a) {
   extern __shared__ unsigned s_hist[];  // min(E^2 n_bins, kMdRdfLdsWords) words
   pin_args(a);
-  const unsigned mark = *static_cast<const volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
-  const int E = a.n_elements, B = a.n_bins, EE = E * E;
-  // frame of this workgroup: the last f with blk_start[f] <= blockIdx.x (every frame has at least one)
-  int f = 0;
-  {
-    int lo = 0, hi = a.n_frames - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (a.blk_start[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    f = lo;
-  }
-  const int i_end = a.atom_start[f + 1];
-  const int i_lo = a.atom_start[f] + ((int)blockIdx.x - a.blk_start[f]) * a.chunk;
-  const int i_hi = i_lo + a.chunk < i_end ? i_lo + a.chunk : i_end;
+  const MdList &l = a.list;
+  if (md_stale(l.status, l.seq)) return;
+  const int E = l.n_elements, B = a.n_bins, EE = E * E;
+  const auto [f, i_lo, i_hi] = md_centres(l);
   if (i_lo >= i_hi) return;  // (the whole workgroup: an empty frame's one workgroup)
   double h[9];
-#pragma unroll
-  for (int c = 0; c < 9; ++c) h[c] = a.cells[9 * (size_t)f + c];
-  const int q_lo = a.pair_start[i_lo], q_hi = a.pair_start[i_hi];
+  md_load_cell(l.cells, f, h);
+  const int q_lo = l.pair_start[i_lo], q_hi = l.pair_start[i_hi];
   const int tile = B < kMdRdfLdsWords / EE ? B : kMdRdfLdsWords / EE;  // bins per pass
   unsigned long long *acc = a.counts + (size_t)f * EE * B;
   for (int k0 = 0; k0 < B; k0 += tile) {
@@ -86,21 +73,20 @@ __global__ __launch_bounds__(kRdfThreads) void md_rdf_kernel(MdRdfLaunch a) {
         const int q = q0 + u * kRdfThreads;
         ok[u] = q < q_hi;
         const size_t qc = (size_t)(ok[u] ? q : q0);
-        i[u] = a.pair_i[qc], j[u] = a.pair_j[qc];
-        S[u][0] = a.pair_shift[3 * qc], S[u][1] = a.pair_shift[3 * qc + 1], S[u][2] = a.pair_shift[3 * qc + 2];
+        i[u] = a.pair_i[qc], j[u] = l.pair_j[qc];
+        S[u][0] = l.pair_shift[3 * qc], S[u][1] = l.pair_shift[3 * qc + 1], S[u][2] = l.pair_shift[3 * qc + 2];
       }
 #pragma unroll
       for (int u = 0; u < kRdfBatch; ++u) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) d[u][c] = a.pos[3 * (size_t)j[u] + c] - a.pos[3 * (size_t)i[u] + c];
-        ab[u] = a.species[i[u]] * E + a.species[j[u]];
+        for (int c = 0; c < 3; ++c) d[u][c] = l.pos[3 * (size_t)j[u] + c] - l.pos[3 * (size_t)i[u] + c];
+        ab[u] = l.species[i[u]] * E + l.species[j[u]];
       }
 #pragma unroll
       for (int u = 0; u < kRdfBatch; ++u) {
-        const double S0 = S[u][0], S1 = S[u][1], S2 = S[u][2];
-        const double dx = d[u][0] + (S0 * h[0] + S1 * h[3] + S2 * h[6]);
-        const double dy = d[u][1] + (S0 * h[1] + S1 * h[4] + S2 * h[7]);
-        const double dz = d[u][2] + (S0 * h[2] + S1 * h[5] + S2 * h[8]);
+        double ix, iy, iz;
+        md_image(h, S[u][0], S[u][1], S[u][2], ix, iy, iz);
+        const double dx = d[u][0] + ix, dy = d[u][1] + iy, dz = d[u][2] + iz;
         const double kf = floor(sqrt(dx * dx + dy * dy + dz * dz) / a.dr);
         // k >= n_bins is dropped (a NaN distance counts nowhere); k outside [k0, k0 + nk) is another pass's
         const int k = kf < (double)B ? (int)kf - k0 : -1;
@@ -108,12 +94,7 @@ __global__ __launch_bounds__(kRdfThreads) void md_rdf_kernel(MdRdfLaunch a) {
       }
     }
     __syncthreads();
-    for (int t = (int)threadIdx.x; t < EE * nk; t += kRdfThreads) {
-      const unsigned c = s_hist[t];
-      if (c != 0u)
-        __hip_atomic_fetch_add(acc + (size_t)(t / nk) * B + (k0 + t % nk), (unsigned long long)c, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-    }
+    md_merge_hist<kRdfThreads>(s_hist, EE, nk, acc, B, k0);
     __syncthreads();
   }
 }
@@ -121,10 +102,10 @@ __global__ __launch_bounds__(kRdfThreads) void md_rdf_kernel(MdRdfLaunch a) {
 }  // namespace
 
 void launch_md_rdf(const MdRdfLaunch &a, hipStream_t s) {
-  if (a.n_blk <= 0 || a.n_bins <= 0) return;
-  const long long words = (long long)a.n_elements * a.n_elements * a.n_bins;
+  if (a.list.n_blk <= 0 || a.n_bins <= 0) return;
+  const long long words = (long long)a.list.n_elements * a.list.n_elements * a.n_bins;
   const size_t lds = (size_t)(words < kMdRdfLdsWords ? words : kMdRdfLdsWords) * sizeof(unsigned);
-  hipLaunchKernelGGL(md_rdf_kernel, dim3((unsigned)a.n_blk), dim3(kRdfThreads), lds, s, a);
+  hipLaunchKernelGGL(md_rdf_kernel, dim3((unsigned)a.list.n_blk), dim3(kRdfThreads), lds, s, a);
 }
 
 }  // namespace ta

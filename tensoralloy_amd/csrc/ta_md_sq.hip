@@ -29,21 +29,12 @@
 
 #include "ta_device.h"
 #include "ta_md.h"
+#include "ta_md_sweep.h"
 
 namespace ta {
 namespace {
 
 static_assert(kMdSqTile == 64 && kMdSqSlab == kMdSqTile, "one wave: lane t stages atom t of the slab and owns q-vector t of the tile");
-
-// frame of workgroup `blk`: the last f with blk_start[f] <= blk (every frame has at least one)
-__device__ __forceinline__ int sq_frame_of(const int32_t *blk_start, int n_frames, int blk) {
-  int lo = 0, hi = n_frames - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (blk_start[mid] <= blk) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // g = h^-1 (row-major, as h): adjugate over determinant
 __device__ __forceinline__ void sq_inverse(const double *h, double *g) {
@@ -60,10 +51,9 @@ __global__ __launch_bounds__(kMdSqTile) void md_sq_amplitude_kernel(MdSqLaunch a
   __shared__ double s_s[kMdSqSlab][3];
   __shared__ double s_v[kCurrents ? kMdSqSlab : 1][3];
   __shared__ int s_sp[kMdSqSlab];
-  const unsigned mark = *static_cast<const volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
+  if (md_stale(a.status, a.seq)) return;
   const int blk = (int)blockIdx.x, lane = (int)threadIdx.x;
-  const int f = sq_frame_of(a.blk_start, a.n_frames, blk);
+  const int f = md_frame_of(a.blk_start, a.n_frames, blk);
   const long long i_end = a.atom_start[f + 1];
   const long long i_lo = (long long)a.atom_start[f] + (long long)(blk - a.blk_start[f]) * a.chunk;
   const long long i_hi = i_lo + a.chunk < i_end ? i_lo + a.chunk : i_end;
@@ -118,8 +108,7 @@ __global__ __launch_bounds__(kMdSqTile) void md_sq_amplitude_kernel(MdSqLaunch a
 
 // ring row of sample n [f][e][plane][q] = the partials of the frame's chunks, in chunk order
 __global__ __launch_bounds__(256) void md_sq_sum_kernel(MdSqLaunch a) {
-  const unsigned mark = *static_cast<const volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
+  if (md_stale(a.status, a.seq)) return;
   const int Q = a.n_q, E = a.n_elements, P = a.currents ? 8 : 2;
   const size_t row = (size_t)a.n_frames * E * P * Q;
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -135,8 +124,7 @@ __global__ __launch_bounds__(256) void md_sq_sum_kernel(MdSqLaunch a) {
 template <bool kCurrents>
 __global__ __launch_bounds__(256) void md_sq_corr_kernel(MdSqLaunch a) {
   constexpr int kPlanes = kCurrents ? 8 : 2;
-  const unsigned mark = *static_cast<const volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
+  if (md_stale(a.status, a.seq)) return;
   const int Q = a.n_q, E = a.n_elements, L = a.n_lags;
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (size_t)a.n_frames * E * E * Q) return;

@@ -33,6 +33,7 @@
 
 #include "ta_device.h"
 #include "ta_math.h"
+#include "ta_md_sweep.h"
 #include "ta_neb.h"
 
 namespace ta {
@@ -55,8 +56,7 @@ __device__ __forceinline__ void neb_tangent_weights(double em, double e0, double
 
 __global__ __launch_bounds__(kNebThreads) void neb_reduce_kernel(NebLaunch a) {
   __shared__ double s_wave[4][kNebThreads / 64];
-  const unsigned mark = *static_cast<const volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
+  if (md_stale(a.status, a.seq)) return;
   const int img = 1 + (int)blockIdx.x / a.blk_per_image;  // interior: 1 .. F - 2
   const int lo = ((int)blockIdx.x % a.blk_per_image) * a.chunk;
   const int hi = lo + a.chunk < a.n ? lo + a.chunk : a.n;
@@ -103,8 +103,7 @@ __global__ __launch_bounds__(kNebThreads) void neb_reduce_kernel(NebLaunch a) {
 __global__ __launch_bounds__(kNebThreads) void neb_apply_kernel(NebLaunch a) {
   __shared__ double s_sum[4];
   __shared__ int s_climb;
-  const unsigned mark = *static_cast<const volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
+  if (md_stale(a.status, a.seq)) return;
   const int img = 1 + (int)blockIdx.x / a.blk_per_image;
   const int lo = ((int)blockIdx.x % a.blk_per_image) * a.chunk;
   const int hi = lo + a.chunk < a.n ? lo + a.chunk : a.n;

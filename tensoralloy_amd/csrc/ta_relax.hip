@@ -44,22 +44,13 @@
 
 #include "ta_device.h"
 #include "ta_math.h"
+#include "ta_md_sweep.h"
 #include "ta_relax.h"
 
 namespace ta {
 namespace {
 
 constexpr int kRelaxThreads = 256;
-
-// frame of this workgroup: the last f with blk_start[f] <= blockIdx.x (every frame has at least one)
-__device__ __forceinline__ int relax_frame_of_block(const int32_t *blk_start, int n_frames) {
-  int lo = 0, hi = n_frames - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (blk_start[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // o = m^-1 (row-major 3x3); returns det m
 __device__ __forceinline__ double relax_inv3(const double *m, double *o) {
@@ -86,9 +77,8 @@ constexpr int kCellG = 0, kCellGinv = 9, kCellGnew = 18, kCellA = 27, kCellLim2 
 template <bool kCell>
 __global__ __launch_bounds__(kRelaxThreads) void relax_reduce_kernel(RelaxLaunch a) {
   __shared__ double s_wave[4][kRelaxThreads / 64];
-  const unsigned mark = *static_cast<volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
-  const int f = relax_frame_of_block(a.blk_start, a.n_frames);
+  if (md_stale(a.status, a.seq)) return;
+  const int f = md_frame_of(a.blk_start, a.n_frames, (int)blockIdx.x);
   if (a.state[(size_t)(a.seq & 1u) * a.n_frames + f].converged) return;  // (the step launch does not read its partial)
   const int64_t f_hi = a.atom_start[f + 1];
   const int64_t lo = a.atom_start[f] + (int64_t)((int)blockIdx.x - a.blk_start[f]) * a.chunk;
@@ -143,9 +133,8 @@ __global__ __launch_bounds__(kRelaxThreads) void relax_step_kernel(RelaxLaunch a
   __shared__ double s_sum[4];
   __shared__ double s_cell[kCell ? kCellWords : 1];  // (unused, and dropped, in the fixed-cell build)
   // (0, or the value this very launch writes, or the mark of an earlier launch: the same branch in every thread)
-  const unsigned mark = *static_cast<volatile unsigned *>(a.status);
-  if (mark != 0u && mark <= a.seq) return;
-  const int f = relax_frame_of_block(a.blk_start, a.n_frames);
+  if (md_stale(a.status, a.seq)) return;
+  const int f = md_frame_of(a.blk_start, a.n_frames, (int)blockIdx.x);
   const int blk0 = a.blk_start[f], blk1 = a.blk_start[f + 1];
   const bool writer = (int)blockIdx.x == blk0 && threadIdx.x == 0;  // of the frame's record
   RelaxFrameState st = a.state[(size_t)(a.seq & 1u) * a.n_frames + f];
